@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- separated-seconds/sec of the SuDoRM-RF forward hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +9,8 @@ A "step" = one forward of Improved SuDoRM-RF U16/512 (BASELINE.json configs[1]) 
 synthetic 4 s @ 8 kHz mixtures already resident in HBM, through the C ABI (srf_forward).  With N GPUs
 every rank runs its own batch of 32 (batch sharding = weak scaling, no data-path collective); the
 timed region is bracketed by barrier + synchronize and the max over ranks is reported.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run does only that; --full adds the untimed extras (self-check of the timed
+outputs, power pass, per-kernel profile, CPU baseline) to the line.
 """
 import argparse
 import json
@@ -62,6 +63,13 @@ def parse():
     ap.add_argument("--feeder", action="store_true",
                     help="time the input feeder on this host (native WAV readers -> pinned -> H2D -> device normalise) on a "
                          "synthetic WHAM-shaped tree under $TMPDIR: examples/s per reader-thread count, one JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed extras: the self-check of the timed outputs, the power "
+                         "pass, the per-kernel profile and the CPU baseline (--no-cpu-baseline / --no-kernel-profile drop "
+                         "parts of them); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32, at most 64 MB "
+                         "in all; the inputs are seeded, so two builds can be compared output for output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=4)
@@ -505,6 +513,9 @@ def train_step_bench(args, cls, variant, kw, T, fs, batch, rank, world, dev):
         return l
 
     r = train_loop(step, lambda: model._engine().last_flat_grad, args.steps, args.warmup, rank, world, dev)
+    if args.dump_outputs and rank == 0:      # (before the --full passes below: they run more steps)
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([r["loss"]]), "grad": model._engine().last_flat_grad,
+                                         "params": torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
     if world > 1:            # the collectives are over: rank 0's untimed passes below must not keep the others in a barrier
         dist.barrier()
         dist.destroy_process_group()
@@ -523,7 +534,7 @@ def train_step_bench(args, cls, variant, kw, T, fs, batch, rank, world, dev):
                                     "algorithmic_bytes_per_step": alg_bytes, "algorithmic_tflops": alg_flops / sec / 1e12,
                                     "model": "roofline.train_bytes_per_example: 2 x the forward's fusion-minimal bytes (SURVEY.md 8d) + one "
                                              "re-read of every materialised activation + the mask pre-activation (DESIGN.md 6c)"}}
-        if not args.no_kernel_profile:
+        if args.full and not args.no_kernel_profile:
             import ctypes as C
             lib = _lib.load()
             stream = _lib.current_stream(dev)
@@ -582,7 +593,7 @@ def train_step_bench(args, cls, variant, kw, T, fs, batch, rank, world, dev):
                                                          "frac": ks / sec / 1e9 / roofline.HBM_PEAK_GBS}
         else:
             extra["roofline"] = dict(extra["train_roofline"], traffic=None)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             extra["cpu_baseline"] = cpu_baseline_subprocess(args)
             if extra["cpu_baseline"].get("value"):
                 extra["gpu_over_cpu"] = batch * (T / fs) / sec / extra["cpu_baseline"]["value"]
@@ -635,6 +646,24 @@ def timed_forwards(run, n_steps, dev, barrier):
     per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_steps)) if cuda else \
         sorted(1e3 * (stamps[i + 1] - stamps[i]) for i in range(n_steps))
     return o, wall, per_step
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor) as path/<name>.npy in float32.  When the whole set would pass
+    DUMP_LIMIT_BYTES, every array keeps the same fraction of its elements, a fixed seeded sample (flattened, in index order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for i, (name, t) in enumerate(sorted(arrays.items())):
+        a = t.detach().float().cpu().numpy()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            idx = np.sort(np.random.default_rng(1234 + i).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def forward_result(args, variant, kw, T, fs, batch, n_gpus, dt, per_rank_ms, per_step_ms, self_check, split, graphs, backend,
@@ -750,6 +779,8 @@ def cpu_stub_bench(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.feeder or args.launch_check or args.cpu_stub):
+        raise SystemExit("bench.py: --dump-outputs applies to the forward and --train runs")
     if args.cpu_baseline_worker or args.cpu_train_worker:
         os.environ.setdefault("OMP_PROC_BIND", "close")
         variant, kw, T, fs, _ = WORKLOADS[args.workload]
@@ -813,47 +844,52 @@ def main():
     # without one half of its moments): no output checks, and the line says so -- such a line is an A/B instrument, never a result
     timing_only = os.environ.get("SRF_BENCH_TIMING_ONLY") == "1"
     assert out.shape == (batch, kw["num_sources"], T) and (timing_only or bool(torch.isfinite(out).all()))
-    # Self-check (untimed, product kernels only): the timed forward's outputs against (a) the same forward on one stream
-    # and (b) the shape-agnostic generic kernels (kernel mode 1: no MFMA, no fusion, different code everywhere) on the
-    # first and last example.  A throughput measured on wrong outputs is worthless; the parity proper is tests/.
-    with torch.no_grad():
-        eng = model._engine()
-        was_multi = eng.multi_stream
-        eng.multi_stream = False
-        single = model(wav)
-        eng.multi_stream = was_multi
-        ops.set_kernel_mode(1)
-        try:
-            generic = torch.cat([model(wav[:1]), model(wav[-1:])])
-        finally:
-            ops.set_kernel_mode(args.kernel_mode)
-        scale = float(out.abs().max().clamp_min(1e-12))
-        d_single = float((out - single).abs().max())
-        d_generic = float((torch.cat([out[:1], out[-1:]]) - generic).abs().max())
-    self_check = {"max_abs_vs_single_stream": d_single, "max_abs_vs_generic_kernels": d_generic, "output_abs_max": scale}
-    self_check["ok"] = not (d_single > 1e-5 * max(scale, 1.0) or d_generic > 1e-3 * max(scale, 1e-3))
-    # every rank takes the same branch below (the re-timing contains collectives)
-    any_bad = (not timing_only) and D.max_over_ranks(0.0 if self_check["ok"] else 1.0, dev) > 0.5
-    any_generic_bad = D.max_over_ranks(0.0 if d_generic <= 1e-3 * max(scale, 1e-3) else 1.0, dev) > 0.5
-    if any_bad and was_multi and not any_generic_bad:
-        # the split forward disagrees with the single-stream one: time the single-stream forward instead (its outputs
-        # were just checked against the generic kernels on the same examples) rather than report a number for outputs
-        # that are not right
-        print("bench.py: stream-split outputs differ from the single-stream forward (%s); timing single-stream"
-              % json.dumps(self_check), file=sys.stderr)
-        eng.multi_stream = False
+    if args.full:
+        # Self-check (untimed, product kernels only): the timed forward's outputs against (a) the same forward on one stream
+        # and (b) the shape-agnostic generic kernels (kernel mode 1: no MFMA, no fusion, different code everywhere) on the
+        # first and last example.  A throughput measured on wrong outputs is worthless; the parity proper is tests/.
         with torch.no_grad():
-            for _ in range(args.warmup):
-                out = model(wav)
-            out, dt_local, per_step_ms = timed(args.steps)
-            per_rank_ms = [1e3 * t / args.steps for t in D.gather_over_ranks(dt_local, dev)]
-            dt = D.max_over_ranks(dt_local, dev)
-            d2 = float((torch.cat([out[:1], out[-1:]]) - generic).abs().max())
-        self_check.update(retimed_single_stream=True, max_abs_vs_generic_kernels=d2, ok=d2 <= 1e-3 * max(scale, 1e-3))
+            eng = model._engine()
+            was_multi = eng.multi_stream
+            eng.multi_stream = False
+            single = model(wav)
+            eng.multi_stream = was_multi
+            ops.set_kernel_mode(1)
+            try:
+                generic = torch.cat([model(wav[:1]), model(wav[-1:])])
+            finally:
+                ops.set_kernel_mode(args.kernel_mode)
+            scale = float(out.abs().max().clamp_min(1e-12))
+            d_single = float((out - single).abs().max())
+            d_generic = float((torch.cat([out[:1], out[-1:]]) - generic).abs().max())
+        self_check = {"max_abs_vs_single_stream": d_single, "max_abs_vs_generic_kernels": d_generic, "output_abs_max": scale}
+        self_check["ok"] = not (d_single > 1e-5 * max(scale, 1.0) or d_generic > 1e-3 * max(scale, 1e-3))
+        # every rank takes the same branch below (the re-timing contains collectives)
+        any_bad = (not timing_only) and D.max_over_ranks(0.0 if self_check["ok"] else 1.0, dev) > 0.5
+        any_generic_bad = D.max_over_ranks(0.0 if d_generic <= 1e-3 * max(scale, 1e-3) else 1.0, dev) > 0.5
+        if any_bad and was_multi and not any_generic_bad:
+            # the split forward disagrees with the single-stream one: time the single-stream forward instead (its outputs
+            # were just checked against the generic kernels on the same examples) rather than report a number for outputs
+            # that are not right
+            print("bench.py: stream-split outputs differ from the single-stream forward (%s); timing single-stream"
+                  % json.dumps(self_check), file=sys.stderr)
+            eng.multi_stream = False
+            with torch.no_grad():
+                for _ in range(args.warmup):
+                    out = model(wav)
+                out, dt_local, per_step_ms = timed(args.steps)
+                per_rank_ms = [1e3 * t / args.steps for t in D.gather_over_ranks(dt_local, dev)]
+                dt = D.max_over_ranks(dt_local, dev)
+                d2 = float((torch.cat([out[:1], out[-1:]]) - generic).abs().max())
+            self_check.update(retimed_single_stream=True, max_abs_vs_generic_kernels=d2, ok=d2 <= 1e-3 * max(scale, 1e-3))
     if timing_only:
         self_check = {"ok": None, "timing_only": "SRF_BENCH_TIMING_ONLY=1: outputs NOT checked (A/B instrument, not a result)"}
+    elif not args.full:
+        self_check = {"ok": None, "not_run": "plain run: bench.py --full checks the timed outputs"}
     elif D.max_over_ranks(0.0 if self_check["ok"] else 1.0, dev) > 0.5:
         raise SystemExit("bench.py self-check failed: %s" % json.dumps(self_check))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": out})
     result, dims, ms_per_step, value = forward_result(
         args, variant, kw, T, fs, batch, n_gpus, dt, per_rank_ms, per_step_ms, self_check,
         list(model._engine()._split_choice.get((dev.index, batch, T), (batch,))), bool(model._engine()._graphs),
@@ -871,7 +907,7 @@ def main():
     if rank != 0:
         return
 
-    if rank == 0 and not args.no_kernel_profile:
+    if rank == 0 and args.full and not args.no_kernel_profile:
         with torch.no_grad():
             try:
                 result["power"] = power_pass(lambda: model(wav))
@@ -879,7 +915,7 @@ def main():
                 result["power"] = {"error": str(e)[:200]}
 
     # ---- per-kernel durations with HIP events on the launch stream (separate instrumented pass) ----
-    if rank == 0 and not args.no_kernel_profile:
+    if rank == 0 and args.full and not args.no_kernel_profile:
         import ctypes as C
         lib = _lib.load()
         stream = _lib.current_stream(dev)
@@ -959,7 +995,7 @@ def main():
     elif rank == 0:
         result["roofline"] = dict(result["forward_roofline"], traffic=None)
 
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_subprocess(args)
         if result["cpu_baseline"].get("value"):
             result["gpu_over_cpu"] = value / result["cpu_baseline"]["value"]

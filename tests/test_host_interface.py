@@ -1,10 +1,9 @@
 """Host-side mirror of the reference interface: schema, attributes, pickles, error behaviour (CPU)."""
-import importlib.util
 import io
+import json
 import os
 import pickle
 import re
-import warnings
 
 import numpy as np
 import pytest
@@ -12,23 +11,20 @@ import torch
 
 from oracle.schema import CONFIGS, ModelConfig, state_dict_schema
 
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="/root/reference only exists in the build container")
+# what the reference's own classes made (tools/make_golden_host.py): state_dict digests and attributes per SMALL
+# configuration, and a whole-module pickle
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _host_manifest():
+    with open(os.path.join(GOLDEN, "HOST_MANIFEST.json")) as f:
+        return json.load(f)
 
 
 def _ours(cfg):
     import sudo_rm_rf_amd.dnn.models.improved_sudormrf as imp
     import sudo_rm_rf_amd.dnn.models.groupcomm_sudormrf_v2 as gc
     return (imp.SuDORMRF if cfg.variant == "improved" else gc.GroupCommSudoRmRf)(**cfg.ctor_kwargs())
-
-
-def _ref_module(rel, name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(REF, rel))
-    mod = importlib.util.module_from_spec(spec)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        spec.loader.exec_module(mod)
-    return mod
 
 
 SMALL = [ModelConfig("improved", 16, 32, 2, 3, 21, 24, 2),
@@ -105,53 +101,37 @@ def test_pickle_roundtrip_own_class():
         assert k1 == k2 and torch.equal(v1, v2)
 
 
-@needs_ref
 @pytest.mark.parametrize("cfg", SMALL, ids=lambda c: f"{c.variant}-U{c.num_blocks}")
 def test_same_seed_same_weights_as_reference(cfg):
-    rel = "sudo_rm_rf/dnn/models/" + ("improved_sudormrf.py" if cfg.variant == "improved" else "groupcomm_sudormrf_v2.py")
-    ref = _ref_module(rel, "_ref_" + cfg.variant)
-    cls = ref.SuDORMRF if cfg.variant == "improved" else ref.GroupCommSudoRmRf
-    torch.manual_seed(1234)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        r = cls(**cfg.ctor_kwargs())
+    """Under one torch seed our constructor makes the reference's weights: same keys in the same order, and every tensor
+    bit for bit (sha256 of its bytes against the reference's state_dict), so a state_dict loads either way; and the
+    public attributes the README recipe reads back (README.md:81-88) agree."""
+    import hashlib
+    want = [c for c in _host_manifest()["cases"].values() if ModelConfig(**c["config"]) == cfg]
+    assert len(want) == 1, cfg
+    want = want[0]
+    assert want["seed"] == 1234
     torch.manual_seed(1234)
     o = _ours(cfg)
-    rsd, osd = r.state_dict(), o.state_dict()
-    assert list(rsd.keys()) == list(osd.keys())
-    for k in rsd:
-        assert torch.equal(rsd[k], osd[k]), k
-    # load_state_dict both directions
-    o.load_state_dict(rsd)
-    r.load_state_dict(osd)
-    # public attributes the README recipe reads back (README.md:81-88)
-    for a in ("out_channels", "in_channels", "num_blocks", "upsampling_depth", "enc_kernel_size",
-              "enc_num_basis", "num_sources", "n_least_samples_req"):
-        assert getattr(r, a) == getattr(o, a)
+    osd = o.state_dict()
+    assert list(osd.keys()) == [k for k, _, _, _ in want["state_dict"]]
+    for k, shape, dtype, digest in want["state_dict"]:
+        v = osd[k]
+        assert list(v.shape) == shape and str(v.dtype) == "torch." + dtype, k
+        assert hashlib.sha256(v.contiguous().numpy().tobytes()).hexdigest() == digest, k
+    o.load_state_dict({k: v.clone() for k, v in osd.items()})
+    for a, v in want["attributes"].items():
+        assert getattr(o, a) == v, a
 
 
-@needs_ref
-def test_reference_whole_module_pickle_unpickles_into_our_classes(tmp_path):
+def test_reference_whole_module_pickle_unpickles_into_our_classes():
     """Published checkpoints are whole-module pickles (README.md:75): a pickle made by the REFERENCE
-    classes must resolve to OUR classes when this repo is first on sys.path."""
-    import subprocess
-    import sys
-    cfg = SMALL[2]
-    path = tmp_path / "ref_model.pt"
-    code = f"""
-import sys, warnings, torch
-sys.path.insert(0, {REF!r})
-warnings.simplefilter('ignore')
-import sudo_rm_rf.dnn.models.groupcomm_sudormrf_v2 as g
-torch.manual_seed(7)
-m = g.GroupCommSudoRmRf(**{cfg.ctor_kwargs()!r})
-assert type(m).__module__ == 'sudo_rm_rf.dnn.models.groupcomm_sudormrf_v2'
-torch.save(m, {str(path)!r})
-"""
-    env = dict(os.environ, PYTHONPATH="")
-    subprocess.run([sys.executable, "-c", code], check=True, cwd="/tmp", env=env)
+    classes (tests/golden/ref_groupcomm_module.pt, tools/make_golden_host.py) must resolve to OUR classes when this
+    repo is first on sys.path."""
+    meta = _host_manifest()["pickle"]
+    cfg = ModelConfig(**meta["config"])
     import sudo_rm_rf_amd.dnn.models.groupcomm_sudormrf_v2 as ours
-    m = torch.load(str(path), weights_only=False)
+    m = torch.load(os.path.join(GOLDEN, meta["file"]), weights_only=False)
     assert type(m) is ours.GroupCommSudoRmRf
     assert type(m.sm[0].TAC) is ours.TAC
     assert m.num_sources == cfg.num_sources and m._config_tuple()[-1] == cfg.group_size

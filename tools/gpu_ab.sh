@@ -11,7 +11,7 @@ mkdir -p "$OUT"; export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 for w in $W; do
   for rep in $(seq 1 $REPS); do
     for f in $F; do
-      timeout 600 python bench.py --workload $w $EXTRA --no-cpu-baseline --debug-flags $f > "$OUT/${w}_f${f}_$rep.json" 2> "$OUT/${w}_f${f}_$rep.err"
+      timeout 600 python bench.py --full --workload $w $EXTRA --no-cpu-baseline --debug-flags $f > "$OUT/${w}_f${f}_$rep.json" 2> "$OUT/${w}_f${f}_$rep.err"
       python - "$OUT/${w}_f${f}_$rep.json" "$w flags=$f" <<'PY'
 import json, sys
 try:

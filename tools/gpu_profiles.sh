@@ -16,15 +16,15 @@ if [[ $PARTS == *t* ]]; then
   timeout 1500 python -m pytest tests -q -m gpu > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?"; tail -3 "$OUT/pytest_gpu.log"
 fi
 if [[ $PARTS == *b* ]]; then
-  timeout 900 python bench.py --steps 50 --warmup 10 > "$OUT/bench_cfg2_improved_u16.json" 2> "$OUT/bench_cfg2.err"; echo "bench rc=$?"; tail -c 300 "$OUT/bench_cfg2_improved_u16.json"
-  timeout 600 python bench.py --steps 20 --warmup 5 --kernel-mode 2 --no-cpu-baseline > "$OUT/bench_cfg2_exact_fp32.json" 2> "$OUT/bench_cfg2_exact.err"
+  timeout 900 python bench.py --full --steps 50 --warmup 10 > "$OUT/bench_cfg2_improved_u16.json" 2> "$OUT/bench_cfg2.err"; echo "bench rc=$?"; tail -c 300 "$OUT/bench_cfg2_improved_u16.json"
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --kernel-mode 2 --no-cpu-baseline > "$OUT/bench_cfg2_exact_fp32.json" 2> "$OUT/bench_cfg2_exact.err"
   for w in cfg1_improved_u8 cfg3_groupcomm_u8 cfg4_improved_u36_n2048 cfg5_improved_u36_n4096; do
-    timeout 600 python bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
+    timeout 600 python bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"
   done
-  timeout 900 python bench.py --train --steps 10 --warmup 3 > "$OUT/train_cfg2_improved_u16.json" 2> "$OUT/train_cfg2.err"; echo "train rc=$?"; tail -c 300 "$OUT/train_cfg2_improved_u16.json"
+  timeout 900 python bench.py --full --train --steps 10 --warmup 3 > "$OUT/train_cfg2_improved_u16.json" 2> "$OUT/train_cfg2.err"; echo "train rc=$?"; tail -c 300 "$OUT/train_cfg2_improved_u16.json"
   # (cfg 3 with its cpu_baseline too -- VERDICT r5 next 8; cfg 4's CPU step does not fit the time budget)
-  timeout 900 python bench.py --train --workload cfg3_groupcomm_u8 --steps 5 --warmup 2 > "$OUT/train_cfg3_groupcomm_u8.json" 2> "$OUT/train_cfg3_groupcomm_u8.err"
-  timeout 600 python bench.py --train --workload cfg4_improved_u36_n2048 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/train_cfg4_improved_u36_n2048.json" 2> "$OUT/train_cfg4_improved_u36_n2048.err"
+  timeout 900 python bench.py --full --train --workload cfg3_groupcomm_u8 --steps 5 --warmup 2 > "$OUT/train_cfg3_groupcomm_u8.json" 2> "$OUT/train_cfg3_groupcomm_u8.err"
+  timeout 600 python bench.py --full --train --workload cfg4_improved_u36_n2048 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/train_cfg4_improved_u36_n2048.json" 2> "$OUT/train_cfg4_improved_u36_n2048.err"
   for w in proj res_conv forward copy; do timeout 120 python tools/power_probe.py $w 3 2>/dev/null | tail -1 >> "$OUT/power.log"; done
 fi
 prof() {   # name, bench args...
@@ -72,9 +72,9 @@ if [[ $PARTS == *c* ]]; then   # completion pass: cfg-3 counters (forward + trai
       i=$((i+1)); pmc $w $i "$grp" --workload $w; pmc train_$w $i "$grp" --train --workload $w
     done
   done
-  timeout 900 python bench.py --train --workload cfg4_improved_u36_n2048 --steps 5 --warmup 2 > "$OUT/train_cfg4_improved_u36_n2048.json" 2> "$OUT/train_cfg4.err"
-  timeout 900 python bench.py --steps 50 --warmup 10 > "$OUT/bench_cfg2_improved_u16.json" 2> "$OUT/bench_cfg2.err"
-  timeout 900 python bench.py --train --steps 10 --warmup 3 > "$OUT/train_cfg2_improved_u16.json" 2> "$OUT/train_cfg2.err"
+  timeout 900 python bench.py --full --train --workload cfg4_improved_u36_n2048 --steps 5 --warmup 2 > "$OUT/train_cfg4_improved_u36_n2048.json" 2> "$OUT/train_cfg4.err"
+  timeout 900 python bench.py --full --steps 50 --warmup 10 > "$OUT/bench_cfg2_improved_u16.json" 2> "$OUT/bench_cfg2.err"
+  timeout 900 python bench.py --full --train --steps 10 --warmup 3 > "$OUT/train_cfg2_improved_u16.json" 2> "$OUT/train_cfg2.err"
 fi
 if [[ $PARTS == *R* ]]; then   # the training step's kernel stats and counter passes again (after a change to its kernel set)
   for w in cfg2_improved_u16 cfg4_improved_u36_n2048; do
@@ -86,8 +86,8 @@ if [[ $PARTS == *R* ]]; then   # the training step's kernel stats and counter pa
   done
 fi
 if [[ $PARTS == *T* ]]; then   # the three training lines again (after a change to the training step)
-  timeout 900 python bench.py --train --steps 10 --warmup 3 > "$OUT/train_cfg2_improved_u16.json" 2> "$OUT/train_cfg2.err"
-  timeout 600 python bench.py --train --workload cfg3_groupcomm_u8 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/train_cfg3_groupcomm_u8.json" 2> "$OUT/train_cfg3.err"
-  timeout 900 python bench.py --train --workload cfg4_improved_u36_n2048 --steps 5 --warmup 2 > "$OUT/train_cfg4_improved_u36_n2048.json" 2> "$OUT/train_cfg4.err"
+  timeout 900 python bench.py --full --train --steps 10 --warmup 3 > "$OUT/train_cfg2_improved_u16.json" 2> "$OUT/train_cfg2.err"
+  timeout 600 python bench.py --full --train --workload cfg3_groupcomm_u8 --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/train_cfg3_groupcomm_u8.json" 2> "$OUT/train_cfg3.err"
+  timeout 900 python bench.py --full --train --workload cfg4_improved_u36_n2048 --steps 5 --warmup 2 > "$OUT/train_cfg4_improved_u36_n2048.json" 2> "$OUT/train_cfg4.err"
 fi
 echo "== done"; du -sh "$OUT"

@@ -64,7 +64,7 @@ ab() {     # "--train" or "", flags (comma separated)
   for w in $WL; do
     for rep in $(seq 1 ${REPS:-2}); do
       for f in $flags; do
-        timeout 600 python bench.py $mode --workload $w ${AB_ARGS:---steps 20 --warmup 5} --no-cpu-baseline --debug-flags $f \
+        timeout 600 python bench.py --full $mode --workload $w ${AB_ARGS:---steps 20 --warmup 5} --no-cpu-baseline --debug-flags $f \
           > "$OUT/ab${mode#--}_${w}_f${f}_$rep.json" 2> "$OUT/ab${mode#--}_${w}_f${f}_$rep.err"
         summ "$OUT/ab${mode#--}_${w}_f${f}_$rep.json" "$w ${mode#--} flags=$f rep=$rep"
       done
@@ -78,17 +78,17 @@ for part in "$@"; do
     smoke) timeout 300 python __graft_entry__.py smoke > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?"; tail -3 "$OUT/smoke.log" ;;
     tests) timeout ${TEST_TIMEOUT:-1500} python -m pytest tests -q -m gpu -p no:cacheprovider --tb=short ${PYTEST_ARGS:-} > "$OUT/pytest_gpu.log" 2>&1
            echo "pytest rc=$?"; grep -E "passed|failed|error" "$OUT/pytest_gpu.log" | tail -3; grep -E "^(FAILED|ERROR)" "$OUT/pytest_gpu.log" | head -30 ;;
-    bench) timeout 900 python bench.py --steps ${STEPS:-50} --warmup ${WARMUP:-10} > "$OUT/bench_cfg2_improved_u16.json" 2> "$OUT/bench_cfg2.err"
+    bench) timeout 900 python bench.py --full --steps ${STEPS:-50} --warmup ${WARMUP:-10} > "$OUT/bench_cfg2_improved_u16.json" 2> "$OUT/bench_cfg2.err"
            echo "bench rc=$?"; summ "$OUT/bench_cfg2_improved_u16.json" cfg2 ;;
     benchall)
-      timeout 600 python bench.py --steps 20 --warmup 5 --kernel-mode 2 --no-cpu-baseline > "$OUT/bench_cfg2_exact_fp32.json" 2> "$OUT/bench_cfg2_exact.err"
+      timeout 600 python bench.py --full --steps 20 --warmup 5 --kernel-mode 2 --no-cpu-baseline > "$OUT/bench_cfg2_exact_fp32.json" 2> "$OUT/bench_cfg2_exact.err"
       for w in cfg1_improved_u8 cfg3_groupcomm_u8 cfg4_improved_u36_n2048 cfg5_improved_u36_n4096; do
-        timeout 600 python bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"; summ "$OUT/bench_$w.json" $w
+        timeout 600 python bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err"; summ "$OUT/bench_$w.json" $w
       done ;;
     train)
-      timeout 900 python bench.py --train --steps 10 --warmup 3 > "$OUT/train_cfg2_improved_u16.json" 2> "$OUT/train_cfg2.err"; summ "$OUT/train_cfg2_improved_u16.json" "train cfg2"
-      timeout 900 python bench.py --train --workload cfg3_groupcomm_u8 --steps 5 --warmup 2 > "$OUT/train_cfg3_groupcomm_u8.json" 2> "$OUT/train_cfg3.err"; summ "$OUT/train_cfg3_groupcomm_u8.json" "train cfg3"
-      timeout 900 python bench.py --train --workload cfg4_improved_u36_n2048 --steps 5 --warmup 2 > "$OUT/train_cfg4_improved_u36_n2048.json" 2> "$OUT/train_cfg4.err"; summ "$OUT/train_cfg4_improved_u36_n2048.json" "train cfg4" ;;
+      timeout 900 python bench.py --full --train --steps 10 --warmup 3 > "$OUT/train_cfg2_improved_u16.json" 2> "$OUT/train_cfg2.err"; summ "$OUT/train_cfg2_improved_u16.json" "train cfg2"
+      timeout 900 python bench.py --full --train --workload cfg3_groupcomm_u8 --steps 5 --warmup 2 > "$OUT/train_cfg3_groupcomm_u8.json" 2> "$OUT/train_cfg3.err"; summ "$OUT/train_cfg3_groupcomm_u8.json" "train cfg3"
+      timeout 900 python bench.py --full --train --workload cfg4_improved_u36_n2048 --steps 5 --warmup 2 > "$OUT/train_cfg4_improved_u36_n2048.json" 2> "$OUT/train_cfg4.err"; summ "$OUT/train_cfg4_improved_u36_n2048.json" "train cfg4" ;;
     prof) for w in $WL; do prof $w --workload $w; done ;;
     proftrain) for w in $WL; do prof train_$w --train --workload $w; done ;;
     pmc) for w in $WL; do pmc $w --workload $w; done ;;
@@ -106,8 +106,8 @@ for part in "$@"; do
         cp gpurun_ab_$v.so $LIB; echo "-- $v rep $rep"
         case ${part#libab:} in
           pair) PAIR_ROUNDS=3 timeout 300 python tools/pair_ab.py ${PAIR_BATCHES:-32 20} 2>&1 | grep -E " pair|two_x3p" | tee -a "$OUT/libab_pair_$v.log" ;;
-          bench) timeout 600 python bench.py ${AB_ARGS:---steps 30 --warmup 6} --no-cpu-baseline > "$OUT/libab_bench_${v}_$rep.json" 2> "$OUT/libab_bench_${v}_$rep.err"; summ "$OUT/libab_bench_${v}_$rep.json" "$v" ;;
-          train) for w in $WL; do timeout 600 python bench.py --train --workload $w ${AB_ARGS:---steps 8 --warmup 3} --no-cpu-baseline > "$OUT/libab_train_${w}_${v}_$rep.json" 2> "$OUT/libab_train_${w}_${v}_$rep.err"; summ "$OUT/libab_train_${w}_${v}_$rep.json" "$v $w"; done ;;
+          bench) timeout 600 python bench.py --full ${AB_ARGS:---steps 30 --warmup 6} --no-cpu-baseline > "$OUT/libab_bench_${v}_$rep.json" 2> "$OUT/libab_bench_${v}_$rep.err"; summ "$OUT/libab_bench_${v}_$rep.json" "$v" ;;
+          train) for w in $WL; do timeout 600 python bench.py --full --train --workload $w ${AB_ARGS:---steps 8 --warmup 3} --no-cpu-baseline > "$OUT/libab_train_${w}_${v}_$rep.json" 2> "$OUT/libab_train_${w}_${v}_$rep.err"; summ "$OUT/libab_train_${w}_${v}_$rep.json" "$v $w"; done ;;
         esac
       done; done
       cp gpurun_ab_new.so $LIB ;;

@@ -59,7 +59,7 @@ def part2(train):
     batches = (4, 8, 12, 16, 24, 32)
     for b in batches:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(b), "--steps", "10", "--warmup", "4",
-               "--no-cpu-baseline"] + (["--train"] if train else [])
+               "--no-cpu-baseline", "--full"] + (["--train"] if train else [])
         env = dict(os.environ, SRF_STREAM_SPLIT="off")
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         try:

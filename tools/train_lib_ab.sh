@@ -13,7 +13,7 @@ for rep in 1 2; do
       case "$lib" in *:*) flags=${lib#*:}; lib=${lib%%:*};; esac
       [ "$lib" = "-" ] && lib=$GRAFT_REPO_ROOT/sudo_rm_rf_amd/libsudormrf_hip.so
       SRF_LIB=$lib timeout 400 python "$GRAFT_REPO_ROOT/bench.py" --train --workload $wl --steps 10 --warmup 3 --no-cpu-baseline \
-          --debug-flags $flags > "$OUT/${wl}_${name}_$rep.json" 2> "$OUT/${wl}_${name}_$rep.err"
+          --full --debug-flags $flags > "$OUT/${wl}_${name}_$rep.json" 2> "$OUT/${wl}_${name}_$rep.err"
       python - "$OUT/${wl}_${name}_$rep.json" "$wl $name $rep" <<'PY'
 import json, sys
 try:
