@@ -125,7 +125,8 @@ int srf_profile_timeline(int i, const char** name, float* t_ms, int* stream_inde
  *   32768    WITHOUT the fused tail: mask GEMM -> masked tensor -> decoder frame GEMM -> overlap-add as separate launches
  *   1<<17    pyramid pass 1 on a grid of co-resident wavefronts, several rows each (rounds 2-5) -- default since round 6: one row per wavefront
  *   1<<16    srf_backward WITHOUT the fused head of the blocks' pyramid backward (round 6: level 0 + proj_1x1's norm as two passes
- *            over {G_0, y1}): the level-0 conv kernel + the norm's apply pass of rounds 3-5
+ *            over {G_0, y1}): the level-0 conv kernel + the norm's apply pass of rounds 3-5 (set it around BOTH calls: a forward
+ *            run without it leaves d_0 out of `saved`, and its backward then takes the head whatever the flag says)
  *   1<<18    weight-gradient GEMM WITHOUT the wide tile (round 6: 256 x 128 / 128 x 256, one block per CU): the 128 x 128 kernel;
  *            small-channel form on a fixed 1024 blocks (rounds 3-5) instead of one resident round
  *   1<<19    weight-gradient GEMM, 128 x 128 kernel: the masked form for full shapes too (rounds 3-5)
@@ -427,7 +428,10 @@ int srf_frames_gather(const float* src, float* out, int Bt, int R, int T, int K,
  *   params; the caller zeroes them like optimizer.zero_grad()).  Reference: torch autograd over
  *   SuDORMRF.forward (improved_sudormrf.py:283-301), run_improved_sudormrf.py:167-172.
  * saved / scratch: 256-byte aligned device buffers of srf_train_saved_bytes / srf_train_scratch_bytes; `saved`
- *   must stay untouched between the two calls, `scratch` may be reused by anything in between. */
+ *   must stay untouched between the two calls, `scratch` may be reused by anything in between.
+ * The backward follows what the srf_forward_train that filled `saved` did (recorded host-side per device and address),
+ *   not the kernel mode / debug flags at its own call: when that forward left the level-0 depthwise output out (the fused
+ *   backward head re-computes it) and the head cannot run under the current settings, it returns SRF_EINVAL naming both. */
 size_t srf_train_saved_bytes(const srf_plan* plan);
 size_t srf_train_scratch_bytes(const srf_plan* plan);
 int srf_forward_train(const srf_plan* plan, const float* const* params, int num_params, const float* wav, float* out,

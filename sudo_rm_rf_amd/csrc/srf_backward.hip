@@ -1422,11 +1422,17 @@ __global__ __launch_bounds__(256) void srf_bwd_l0p_kernel(L0pArgs a, long rows) 
 // pn_scratch: norm p's slice -- pass A writes it (buckets zeroed by the caller: the deferred mode's arena), pass B reads it;
 // dw_scratch: conv 0's row-partial slice.  dw / dbias: conv 0's parameter gradients (deferred through ctx, or reduced here).
 // gy1 must not alias G0 (halo lanes re-read what a neighbouring trip's own lanes would have overwritten).
-bool srf_bwd_level0_proj_ok(int L, const void* const* ptrs, int nptrs) {
-  if ((L % 4) != 0 || L < 8 || srf_kernel_mode() == 1 || (srf_debug_flags() & ((1 << 16) | (1 << 29) | (1 << 30)))) return false;
+// _shape_ok: what the kernels need of the shape and the operands; _ok: that, and the kernel mode / debug flags do not switch the
+// head off (srf_train.hip asks _shape_ok alone when the forward it follows already chose the head and left d_0 out of `saved`).
+bool srf_bwd_level0_proj_shape_ok(int L, const void* const* ptrs, int nptrs) {
+  if ((L % 4) != 0 || L < 8) return false;
   for (int i = 0; i < nptrs; ++i)
     if (!ptrs[i] || !srf_aligned16(ptrs[i])) return false;
   return true;
+}
+bool srf_bwd_level0_proj_ok(int L, const void* const* ptrs, int nptrs) {
+  if (srf_kernel_mode() == 1 || (srf_debug_flags() & ((1 << 16) | (1 << 29) | (1 << 30)))) return false;
+  return srf_bwd_level0_proj_shape_ok(L, ptrs, nptrs);
 }
 int srf_bwd_level0_proj(const float* G0, const float* y1, const srf_norm* pn, const srf_norm* n0, const float* w0, const float* b0,
                         const void* n0_scratch, void* pn_scratch, void* dw_scratch, float* dw, float* dbias, float* gy1,

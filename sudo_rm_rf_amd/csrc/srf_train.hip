@@ -14,6 +14,9 @@
 // GroupComm: each block is preceded by TAC (MLP + TAC_norm + residual, groupcomm_sudormrf_v2.py:356-384) and the
 // U-ConvBlock runs on the (batch x group)-folded tensor with channels / G (:388-418); `saved` additionally keeps the
 // TAC MLP output q and the block input u = x + GlobLN(q).
+#include <map>
+#include <mutex>
+
 #include "srf_plan.h"
 
 int srf_transpose_launch(const float* w, float* wt, int Ci, int M, hipStream_t st);
@@ -53,6 +56,7 @@ int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_n
                          void* stream, SrfBwdCtx* ctx);
 
 bool srf_bwd_level0_proj_ok(int L, const void* const* ptrs, int nptrs);
+bool srf_bwd_level0_proj_shape_ok(int L, const void* const* ptrs, int nptrs);
 int srf_bwd_level0_proj(const float* G0, const float* y1, const srf_norm* pn, const srf_norm* n0, const float* w0, const float* b0,
                         const void* n0_scratch, void* pn_scratch, void* dw_scratch, float* dw, float* dbias, float* gy1,
                         int groups, int C, int L, void* stream, SrfBwdCtx* ctx);
@@ -66,10 +70,58 @@ static size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
 // Round 6: levels 1 and 0 of a block's pyramid backward and proj_1x1's norm backward run on the fused-head kernels
 // (srf_backward.hip: srf_bwd_l1h_kernel, srf_bwd_l0p_kernel), which re-compute d_0 from y1 -- so srf_forward_train does not WRITE
-// d_0 either.  One predicate for both sides (a pure function of the plan, the kernel mode and the debug flags: they must not
-// change between a srf_forward_train and its srf_backward); every buffer involved is a 256-byte-aligned slice of saved / scratch.
+// d_0 either.  The forward decides from the plan, the kernel mode and the debug flags, and RECORDS what it did (below); the
+// backward follows that record, not the mode / flags of its own time: a forward that left d_0 out gets the head (or SRF_EINVAL
+// when the head cannot run now), a forward that wrote d_0 gets the head or the row kernels, whichever the backward's own
+// settings and shapes allow.  Every buffer involved is a 256-byte-aligned slice of saved / scratch.
 static bool train_fused_head(const srf_plan* p) {
   return p->cfg.upsampling_depth > 1 && srf_bwd_level0_proj_ok(p->L, nullptr, 0);
+}
+
+// What a srf_forward_train did to its `saved` buffer, for the srf_backward that reads it: whether d_0 was left out,
+// and the kernel mode / debug flags the forward ran under (for the error message).  Host-side, keyed by (device, address) like
+// the packed3 format table (srf_pwconv.hip), so the backward needs no read of device memory.  A forward replaces every record
+// its `saved` extent overlaps (the allocator re-uses addresses); at most kTrainRecMax records are kept, the oldest goes first.
+struct TrainRec {
+  size_t bytes;
+  unsigned long long seq;
+  bool skip_d0;
+  int mode, flags;
+};
+static std::mutex g_trec_mu;
+static std::map<unsigned long long, TrainRec> g_trec;     // key: device << 56 | address (ordered: range queries)
+static unsigned long long g_trec_seq = 0;
+static const size_t kTrainRecMax = 1024;
+static unsigned long long train_rec_key(const void* p) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  return ((unsigned long long)dev << 56) | ((unsigned long long)(size_t)p & ((1ull << 56) - 1));
+}
+// valid = false: only drop what the extent overlaps (a forward that failed leaves no record behind)
+static void train_rec_put(const void* saved, size_t bytes, bool valid, bool skip_d0, int mode, int flags) {
+  const unsigned long long k0 = train_rec_key(saved), k1 = k0 + bytes;
+  std::lock_guard<std::mutex> lk(g_trec_mu);
+  auto it = g_trec.lower_bound(k0);
+  if (it != g_trec.begin()) {
+    auto prev = std::prev(it);
+    if (prev->first + prev->second.bytes > k0) it = prev;
+  }
+  while (it != g_trec.end() && it->first < k1) it = g_trec.erase(it);
+  if (!valid) return;
+  if (g_trec.size() >= kTrainRecMax) {
+    auto oldest = g_trec.begin();
+    for (auto j = g_trec.begin(); j != g_trec.end(); ++j)
+      if (j->second.seq < oldest->second.seq) oldest = j;
+    g_trec.erase(oldest);
+  }
+  g_trec[k0] = TrainRec{bytes, ++g_trec_seq, skip_d0, mode, flags};
+}
+static bool train_rec_get(const void* saved, TrainRec* out) {
+  std::lock_guard<std::mutex> lk(g_trec_mu);
+  const auto it = g_trec.find(train_rec_key(saved));
+  if (it == g_trec.end()) return false;
+  *out = it->second;
+  return true;
 }
 
 struct TrainLayout {
@@ -216,7 +268,8 @@ extern "C" size_t srf_train_saved_bytes(const srf_plan* p) { return p ? train_la
 extern "C" size_t srf_train_scratch_bytes(const srf_plan* p) { return p ? scratch_layout(p).total : 0; }
 
 static int forward_train_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
-                              void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, bool split_tail, void* stream);
+                              void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, bool split_tail, bool* skip_d0_out,
+                              void* stream);
 
 // The training forward runs its 1x1 convolutions in the EXACT-fp32 CLASS (kernel mode 2: since round 3 the three-part split
 // GEMM where the 256 x 128 kernel takes the launch, else the exact fp32 MFMA kernel) unless debug flag 1<<28 is set.
@@ -228,15 +281,19 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
 // split-bf16: with an exact forward every parameter gradient is within 2e-5 of the reference's.
 extern "C" int srf_forward_train(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                                  void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-  const bool exact = srf_kernel_mode() == 0 && !(srf_debug_flags() & (1 << 28));
+  const int mode = srf_kernel_mode(), flags = srf_debug_flags();
+  const bool exact = mode == 0 && !(flags & (1 << 28));
   const int prev = exact ? srf_kernel_mode_override(2) : -1;
-  const int rc = forward_train_impl(p, P, num_params, wav, out, saved, saved_bytes, scratch, scratch_bytes, exact, stream);
+  bool skip_d0 = false;
+  const int rc = forward_train_impl(p, P, num_params, wav, out, saved, saved_bytes, scratch, scratch_bytes, exact, &skip_d0, stream);
   if (exact) srf_kernel_mode_override(prev);
+  if (saved) train_rec_put(saved, saved_bytes, rc == SRF_OK, skip_d0, mode, flags);
   return rc;
 }
 
 static int forward_train_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
-                              void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, bool split_tail, void* stream) {
+                              void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, bool split_tail, bool* skip_d0_out,
+                              void* stream) {
   SRF_CHECK_ARG(p && P && wav && out && saved && scratch, "srf_forward_train: null pointer");
   SRF_CHECK_ARG(num_params == p->n_params, "srf_forward_train: expected %d parameter tensors, got %d", p->n_params,
                 num_params);
@@ -319,6 +376,7 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
                          srf_pyramid_supported(nC, (int)L, D) && srf_pyramid_reg_supported((int)L, D) &&
                          srf_pyramid_scratch_bytes(Bg, nC, (int)L, D) <= (s.gd + F_ * Bt * c.in_channels * L) - s.gf;
   const bool skip_d0 = fused_pyr && train_fused_head(p);     // (the backward re-computes d_0: nothing reads it)
+  *skip_d0_out = skip_d0;                                     // (srf_forward_train records it for the backward)
   for (int i = 0; i < U; ++i) {
     const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
     const float* const* Pu = Pb + p->p_ublock_off;
@@ -494,6 +552,30 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
   } ctx_owner;
   SrfBwdCtx* ctx = ctx_owner.c;
 
+  // Levels 1 and 0 of every block follow the forward that filled `saved` (its record; no record -- a buffer no srf_forward_train
+  // of this process filled, or one evicted from the table -- is taken as "d_0 may be missing").  d_0 left out: the fused head must
+  // run, whatever the kernel mode / debug flags say now; what it needs of the row kernels (level 1) and of the shape is checked
+  // here, before the first launch, so a backward that cannot follow its forward fails without touching `grads`.
+  TrainRec rec{};
+  const bool known = train_rec_get(saved, &rec);
+  const bool d0_missing = c.upsampling_depth > 1 && (!known || rec.skip_d0);
+  const char* who = grad_wav ? "srf_backward_wav" : "srf_backward";
+  auto head_lost = [&](const char* where) {
+    if (known)
+      srf_set_error("%s: the srf_forward_train that filled `saved` left d_0 out for the fused backward head (kernel mode %d, debug "
+                    "flags 0x%x), but the head cannot run %s under kernel mode %d / debug flags 0x%x -- run the backward under the "
+                    "forward's settings", who, rec.mode, (unsigned)rec.flags, where, srf_kernel_mode(), (unsigned)srf_debug_flags());
+    else
+      srf_set_error("%s: no srf_forward_train of this process filled `saved` (%p): d_0 may be missing, and the fused backward head "
+                    "that re-computes it cannot run %s under kernel mode %d / debug flags 0x%x", who, saved, where, srf_kernel_mode(),
+                    (unsigned)srf_debug_flags());
+    return SRF_EINVAL;
+  };
+  if (d0_missing) {
+    if (!srf_bwd_level0_proj_shape_ok(L, nullptr, 0)) return head_lost("at level 0 (L)");
+    if (!srf_dwconv5_bwd_rowwise_ok(L, 2, nullptr, 0)) return head_lost("at level 1 (the row kernels)");
+  }
+
   const int pt = p->p_tail;
   // The data-gradient GEMMs g_x = W^T g run on the 256 x 128 split-bf16 kernel with the TRANSPOSED weights pre-split into its
   // stage images, all of them in one launch here (shapes / launches that kernel does not take keep the transposed fp32 copy
@@ -608,7 +690,7 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     // (one slice per call -- the alternation is now simply "this call's slice, the next call's slice")
     int pre_reduced = 0, pp = 1;
     bool head_done = false;  // level 0 + proj_1x1's norm ran as the fused head (g_y1 in the g_d buffer)
-    const bool head = train_fused_head(p);   // (re-computes d_0: needed whenever the forward skipped it, harmless otherwise)
+    bool head = d0_missing || train_fused_head(p);   // (re-computes d_0: needed when the forward left it out, harmless otherwise)
     const float* g_o = go;   // where level 0's conv leaves the gradient w.r.t. o = PReLU(GlobLN(y1))
     for (int k = D - 1; k >= 0; --k) {
       const float* const* Pk = Pu + 5 + 4 * k;   // conv.weight, conv.bias, norm.gamma, norm.beta
@@ -644,10 +726,11 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       // Level 0 with its norm already reduced (by level 1's kernel) and the complete G_0 in one buffer: the fused head
       // (round 6, srf_backward.hip: two passes over {G_0, y1} -- conv 0's backward, its norm's apply, proj_1x1's norm reduce
       // and apply; neither d_0 nor g_o travels) leaves g_y1 in the g_d buffer; the two buffers swap roles for the rest of the block.
-      if (k == 0 && head) {
-        const void* hp[3] = {gout1, y1, gd};
-        SRF_CHECK_ARG(pre_reduced && !gout2 && gout1 != gd && srf_bwd_level0_proj_ok(L, hp, 3),
-                      "srf_backward: the fused backward head lost its preconditions at level 0");
+      // (the head's preconditions missing here: an error when d_0 is not in `saved`, else level 0 on the row kernels below)
+      const void* hp[3] = {gout1, y1, gd};
+      const bool head0 = k == 0 && head && pre_reduced && !gout2 && gout1 != gd && srf_bwd_level0_proj_shape_ok(L, hp, 3);
+      if (k == 0 && head && !head0 && d0_missing) return head_lost("at level 0");
+      if (head0) {
         {
           rc = srf_gln_bwd_impl(gout1, nullptr, dk, &nk, Bg, nC, Lk, nullptr, 0, Gk[2], Gk[3], nullptr, cur_sl, 3, stream, ctx);
           if (rc) return rc;      // (norm 0's parameter sums, reduced by level 1's kernel: recorded for the batched flush)
@@ -671,9 +754,12 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       rc = srf_gln_bwd_impl(gout1, gout2, dk, &nk, Bg, nC, Lk, gd, 0, Gk[2], Gk[3], nullptr, cur_sl,
                             (pre_reduced ? 1 : 0) | (on_load ? 2 : 0), stream, ctx);
       if (rc) return rc;
+      if (k == 1 && head && !on_load) {
+        if (d0_missing) return head_lost("at level 1 (the row kernels)");
+        head = false;       // d_0 is in `saved`: levels 1 and 0 on the conv kernels
+      }
       if (k == 1 && head) {
-        // level 1 on the fused-head kernel: conv 1's input n_0 re-computed from y1 (the forward did not keep d_0)
-        SRF_CHECK_ARG(on_load, "srf_backward: the fused backward head needs the row kernels' preconditions at level 1");
+        // level 1 on the fused-head kernel: conv 1's input n_0 re-computed from y1 (the forward may not have kept d_0)
         const srf_norm pn1{slot(s0), Pu[2], Pu[3], Pu[4]};
         rc = srf_bwd_level1_head(gout1, dk, &nk, cur_sl, y1, &pn1, &in, Pu[5], Pu[6], Pk[0], gadd, gin, next_sl,
                                  dw_sl + (size_t)k * s.dw_slice, Gk[0], Gk[1], Bg, nC, L, stream, ctx);

@@ -597,3 +597,284 @@ def test_gradients_are_one_flat_buffer_and_accumulate_safely():
     assert D.flat_gradient_view(params) is not None
     for p, g in zip(params, g1):
         assert torch.allclose(p.grad, g, rtol=1e-5, atol=1e-7)
+
+
+# ---- the training step at the batch bench.py --train times it (32) --------------------------------------------------------------
+_BENCH_TRAIN = ["train_cfg2_bench", "train_cfg3_bench", "train_cfg4_bench"]
+_OPTIMIZER_FAMILIES = {"grad_sqnorm", "clip_adam"}       # (the model's step includes the optimizer; these tests stop at backward)
+
+
+def _family_model(cfg, T, Bt, **kw):
+    from sudo_rm_rf_amd import roofline
+    return roofline.train_family_model(cfg.variant, cfg.out_channels, cfg.in_channels, cfg.num_blocks, cfg.upsampling_depth,
+                                       cfg.enc_kernel_size, cfg.enc_num_basis, cfg.num_sources, T, Bt, G=cfg.group_size,
+                                       A=cfg.in_audio_channels, **kw)
+
+
+def _check_family_model(cfg, T, Bt, names):
+    """The families the launch model names at this batch ran, and the ones it names only for OTHER batches / dispatch choices
+    (without the pairs, without the fused head, the other batch of the two these tests run) did not."""
+    want = set(_family_model(cfg, T, Bt)) - _OPTIMIZER_FAMILIES
+    other = set()
+    for b in (4, 32):
+        for kw in ({}, {"dgrad_pairs": False}, {"fused_head": False}):
+            other |= set(_family_model(cfg, T, b, **kw))
+    other -= want | _OPTIMIZER_FAMILIES
+    assert not want - names, ("the launch model names families that did not run", sorted(want - names), sorted(names))
+    assert not other & names, ("families the launch model does not expect at Bt = %d ran" % Bt, sorted(other & names))
+
+
+def _count(tr, name):
+    return sum(1 for k, _ in tr.launches if k == name)
+
+
+def _free_gpu():
+    import gc
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("name", _BENCH_TRAIN, ids=["cfg2", "cfg3", "cfg4"])
+def test_bench_batch_training_step_matches_reference_golden(name):
+    """The runner's step at the BATCH `bench.py --train` times (32), against the fp64 reference: the train_cfg*_bench fixture's 4
+    examples tiled 8 x (mixture and targets), so the batch-mean loss, its clamp and every parameter gradient are the fixture's.
+    The batch-4 fixtures alone never reach the kernels the timed step runs: the training forward's fp16-part pairs and the
+    backward's data-gradient pair need Bt * ceil(L / 128) >= 256 (cfg 2: 800 at batch 32, 100 at batch 4), and the split-K
+    weight-gradient geometry, the small-channel wgrad's block count and the (batch x group)-folded TAC / norm kernels of cfg 3
+    all depend on Bt.  The profiler proves the step ran the batch-32 kernel set (roofline.train_family_model's families, and
+    cfg 2's pair / fused-head launch counts).  Bars: those of the big fixtures (test_training_step_matches_reference_golden);
+    cfg 3 also pins d loss / d mixture (srf_backward_wav, through mixture consistency) per example, at 2e-4 of its scale or 4 x
+    the reference's own fp32 deviation from fp64 for that example (the fixture's `d:gwav`), the big fixtures' yardstick rule.
+    Measured: 9.21e-3 on the worst example, where the reference's own fp32 backward is 9.22e-3 off fp64 (3.4e-3 .. 9.2e-3 over
+    the four examples): at U = 8, T = 32000 the input gradient carries the fp32 conditioning of the first layers' gradients, so a
+    flat 2e-4 sits below what any fp32 implementation reaches; the sub-batch test below holds the kernels to each other instead."""
+    import sudo_rm_rf.dnn.experiments.utils.mixture_consistency as mixture_consistency
+    import sudo_rm_rf.dnn.losses.sisdr as sisdr_lib
+    from sudo_rm_rf_amd import ops
+    from test_oracle_golden import check_grads_against_golden, train_case
+    cfg, sd, mix, tgt, z = train_case(name)
+    nb, reps, Bt, T = mix.shape[0], 8, 32, mix.shape[-1]
+    assert nb * reps == Bt
+    gc_ = cfg.variant == "groupcomm"
+    model = build(cfg, sd).train()
+    try:
+        loss_fn = sisdr_lib.PITLossWrapper(sisdr_lib.PairwiseNegSDR("sisdr"), pit_from='pw_mtx')
+        x = mix.repeat(reps, 1, 1).to(DEV)
+        y = tgt.repeat(reps, 1, 1).to(DEV)
+        if gc_:
+            x.requires_grad_()
+        with ops.kernel_trace(DEV) as tr:
+            rec = model(x)
+            if gc_:
+                rec = mixture_consistency.apply(rec, x)
+            l = torch.clamp(loss_fn(rec, y), min=-30., max=+30.)
+            l.backward()
+        torch.cuda.synchronize()
+        print("%s batch %d: loss %.6f (fixture %.6f)" % (name, Bt, l.item(), float(z["loss"])))
+        assert abs(l.item() - float(z["loss"])) <= 1e-3
+        check_grads_against_golden([(k, p.grad.cpu().numpy()) for k, p in model.state_dict(keep_vars=True).items()],
+                                   z, 2e-3, fp32_yardstick=4.0, flip_budget=0.01)
+        if gc_:
+            want = torch.from_numpy(z["gwav"]).double() / reps
+            got = x.grad.detach().cpu().double()
+            rel = [((got[i] - want[i % nb]).abs().max() / want[i % nb].abs().max()).item() for i in range(Bt)]
+            bars = [max(2e-4, 4.0 * float(z["d:gwav"][i % nb])) for i in range(Bt)]
+            i = max(range(Bt), key=lambda j: rel[j] / bars[j])
+            print("%s batch %d: d loss / d mixture, worst example %d: %.3e of its scale (bar %.1e; the reference's own fp32 "
+                  "backward: %.3e)" % (name, Bt, i, rel[i], bars[i], float(z["d:gwav"][i % nb])))
+            assert all(r <= b for r, b in zip(rel, bars)), list(zip(rel, bars))
+        U = cfg.num_blocks
+        if cfg.variant == "improved" and cfg.out_channels == 256:
+            # cfg 2: bottleneck + proj_1x1(0) and res_conv(i) + proj_1x1(i + 1) as forward pairs, U - 1 backward data-gradient pairs,
+            # the fused backward head in every block
+            nfwd = sum(1 for k, _ in tr.launches if k.startswith("pw_pair_x3f4<"))
+            counts = (nfwd, _count(tr, "pw_pair_x3f<0>"), _count(tr, "bwd_l0p_reduce"), _count(tr, "bwd_l0p_apply"), _count(tr, "bwd_l1h"))
+            assert counts == (U, U - 1, U, U, U), (counts, sorted(tr.names))
+        if gc_:
+            for fam in ("tac_mfma", "tac_bwd_mfma", "pw_wgrad_small"):
+                assert fam in tr.names, (fam, sorted(tr.names))
+        _check_family_model(cfg, T, Bt, tr.names)
+    finally:
+        del model
+        _free_gpu()
+
+
+def _flip_budget_compare(named, bar_of, tol, scalar_tol, flip_budget=0.01):
+    """named: [(name, got, want)] of gradient tensors.  Per tensor: max |got - want| <= bar_of(name) x max |want|; up to
+    flip_budget of the tensors may miss it by at most 5 x as long as the whole gradient (each tensor scaled by its largest entry)
+    is within tol in the L2 sense -- check_grads_against_golden's rule.  Scalars (PReLU slopes): scalar_tol each.  Returns
+    (report line, [assertion failures])."""
+    over, worst_t, worst_s, bad = [], ("", 0.0, 1.0), ("", 0.0), []
+    num = den = 0.0
+    for k, got, want in named:
+        if not torch.isfinite(got).all():
+            bad.append(("non-finite", k))
+        scale = max(float(want.abs().max()), 1e-30)
+        d = (got.double() - want.double()) / scale
+        err = float(d.abs().max())
+        if want.numel() == 1:
+            worst_s = max(worst_s, (k, err), key=lambda kv: kv[1])
+            if err > scalar_tol:
+                bad.append(("scalar", k, err))
+            continue
+        num += float((d ** 2).sum())
+        den += float(((want.double() / scale) ** 2).sum())
+        bar = bar_of(k)
+        worst_t = max(worst_t, (k, err, bar), key=lambda kv: kv[1] / kv[2])
+        if err > bar:
+            over.append((k, err, bar))
+    l2 = (num / max(den, 1e-300)) ** 0.5
+    ntens = sum(1 for _, _, w in named if w.numel() > 1)
+    if len(over) > flip_budget * ntens or any(e > 5 * b for _, e, b in over):
+        bad.append(("over bar", len(over), ntens, over[:12]))
+    if l2 > tol:
+        bad.append(("L2", l2))
+    report = ("worst gradient tensor %s %.2e (bar %.1e), worst PReLU slope %s %.2e, whole-gradient L2 %.2e, %d of %d tensors "
+              "over their bar" % (worst_t + worst_s + (l2, len(over), ntens)))
+    return report, bad
+
+
+@pytest.mark.parametrize("name", _BENCH_TRAIN, ids=["cfg2", "cfg3", "cfg4"])
+def test_bench_batch_training_gradient_is_the_mean_over_its_sub_batches(name):
+    """Tiling cannot catch a kernel that mixes example b with example b + 4 k: here 32 DISTINCT examples (the fixtures' generator,
+    another seed, T = 32000, the fixture's weights) with the unclamped PIT loss -- a mean over examples -- so the batch-32 step's
+    parameter gradient is the mean of the 8 disjoint batch-4 steps' and its d loss / d mixture rows are theirs / 8.  The batch-4
+    steps run the kernel set train_cfg*_bench pins against fp64, the batch-32 step the one bench.py times (cfg 2: the profiler
+    proves the backward's data-gradient pair ran at batch 32 only).  Bars: forward output per example 1e-5 of its scale; parameter
+    gradients 2e-4 of each tensor's maximum (test_training_step_with_and_without_fused_pairs' bar) or, where larger, 2 x the
+    reference's own fp32 deviation from fp64 for that kind of parameter at this configuration and length (the train_cfg*_bench
+    fixture's `d:` entries: two fp32 runs, each about that far from fp64), with the flip budget of check_grads_against_golden
+    and its whole-gradient L2 bar for these fixtures, 2e-3 (measured 2.3e-4 / 7.6e-4 / 3.1e-4 for cfg 2 / 3 / 4; 2e-4 would fail);
+    PReLU slopes 1e-2; d loss / d mixture per row: relative L2 error 5e-3, max error 0.1 of the row's largest entry.
+    Why not a flat 2e-4 (measured first): the two kernel sets round differently (tile shapes, the pairs' statistics, summation
+    orders), and at U = 16 / 8 / 36 and T = 32000 the first layers' gradients amplify that rounding (srf_train.hip: the forward's
+    exact-fp32 class) -- 13 / 62 / 79 tensors of cfg 2 / 3 / 4 exceeded 2e-4, all by less than the reference's own fp32 deviation
+    there (cfg 2 bottleneck.weight 9.1e-4 vs 5.8e-4 x 2; cfg 3 ln.gamma 1.3e-3 vs 6.8e-4 x 2), while the forward outputs agree per
+    example to 1e-5: a kernel that mixed examples would move every output and gradient by O(1).  d loss / d mixture is one
+    element per sample, nothing averages its rounding: the rows differed by 3.4e-2 / 4.0e-2 / 2.0e-2 of their largest entry
+    (cfg 2 / 3 / 4) at a flat 2e-4 bar, at interior samples, with a relative L2 error of 3e-4 .. 1.5e-3 per row; each batch
+    size is bitwise repeatable run to run, and the reference's own fp32 input gradient is 3.4e-3 .. 9.2e-3 (max) off fp64 on
+    the cfg-3 fixture's four examples -- rounding, not a mixed or missing term, which would show in the L2 figure."""
+    import sudo_rm_rf.dnn.experiments.utils.mixture_consistency as mixture_consistency
+    import sudo_rm_rf.dnn.losses.sisdr as sisdr_lib
+    from sudo_rm_rf_amd import ops
+    from test_oracle_golden import train_case
+    import re
+    cfg, sd, _, _, z = train_case(name)
+    kind_dev = {}
+    for k in z.files:
+        if k.startswith("d:") and k != "d:gwav":
+            kind = re.sub(r"\d+", "#", k[2:])
+            kind_dev[kind] = max(kind_dev.get(kind, 0.0), float(z[k]))
+    bar_of = lambda k: max(2e-4, 2.0 * kind_dev.get(re.sub(r"\d+", "#", k), 0.0))
+    Bt, sub, T = 32, 4, 32000
+    _, tgt_np = loss_oracle.make_loss_case(Bt, cfg.num_sources, T, 4242, 5.0, "random")
+    tgt = torch.from_numpy(tgt_np)
+    mix = tgt.sum(1, keepdim=True)
+    mix = (mix - mix.mean(-1, keepdim=True)) / (mix.std(-1, keepdim=True) + 1e-8)
+    gc_ = cfg.variant == "groupcomm"
+    loss_fn = sisdr_lib.PITLossWrapper(sisdr_lib.PairwiseNegSDR("sisdr"), pit_from='pw_mtx')
+    model = build(cfg, sd).train()
+    pair = cfg.variant == "improved" and cfg.out_channels == 256
+
+    def step(lo, hi):
+        model.zero_grad(set_to_none=True)
+        x = mix[lo:hi].to(DEV).requires_grad_()
+        with ops.kernel_trace(DEV) as tr:
+            rec = model(x)
+            out = rec.detach().clone()
+            if gc_:
+                rec = mixture_consistency.apply(rec, x)
+            loss_fn(rec, tgt[lo:hi].to(DEV)).backward()
+        grads = [p.grad.detach().double() for p in model.parameters()]
+        return out, grads, x.grad.detach(), tr
+
+    try:
+        out32, g32, x32, tr32 = step(0, Bt)
+        if pair:
+            assert _count(tr32, "pw_pair_x3f<0>") == cfg.num_blocks - 1, sorted(tr32.names)
+        gsum = [torch.zeros_like(g) for g in g32]
+        worst_out = worst_x = worst_xl2 = 0.0
+        for j in range(Bt // sub):
+            lo, hi = j * sub, (j + 1) * sub
+            out4, g4, x4, tr4 = step(lo, hi)
+            if pair:
+                assert "pw_pair_x3f<0>" not in tr4.names, sorted(tr4.names)
+            for a, g in zip(gsum, g4):
+                a += g
+            for i in range(sub):
+                o32, o4 = out32[lo + i].double(), out4[i].double()
+                worst_out = max(worst_out, float((o32 - o4).abs().max()) / max(float(o4.abs().max()), 1e-30))
+                w = x4[i].double() / (Bt // sub)
+                worst_x = max(worst_x, float((x32[lo + i].double() - w).abs().max()) / max(float(w.abs().max()), 1e-30))
+                worst_xl2 = max(worst_xl2, float((x32[lo + i].double() - w).norm()) / max(float(w.norm()), 1e-30))
+            del g4
+        names = [k for k, _ in model.named_parameters()]
+        report, bad = _flip_budget_compare([(k, g, a / (Bt // sub)) for k, g, a in zip(names, g32, gsum)], bar_of, 2e-3, 1e-2)
+        print("%s batch %d vs %d x batch %d: forward output worst %.2e of scale; d loss / d mixture worst row %.2e of its scale, "
+              "%.2e relative L2; %s" % (name, Bt, Bt // sub, sub, worst_out, worst_x, worst_xl2, report))
+        assert worst_out <= 1e-5, worst_out
+        assert worst_xl2 <= 5e-3 and worst_x <= 0.1, (worst_xl2, worst_x)
+        assert not bad, bad
+    finally:
+        del model
+        _free_gpu()
+
+
+# ---- the backward follows the forward it belongs to ------------------------------------------------------------------------------
+_SWITCHES = [  # (id, forward (debug flags, kernel mode), backward (debug flags, kernel mode))
+    ("flags_0_to_head_off", (0, 0), (1 << 16, 0)),
+    ("flags_0_to_chunked_dwconv", (0, 0), (1 << 29, 0)),
+    ("flags_0_to_chunked_norm", (0, 0), (1 << 30, 0)),
+    ("mode_0_to_1", (0, 0), (0, 1)),
+    ("flags_head_off_to_0", (1 << 16, 0), (0, 0)),
+]
+
+
+@pytest.mark.parametrize("fwd,bwd", [s[1:] for s in _SWITCHES], ids=[s[0] for s in _SWITCHES])
+def test_backward_follows_its_forward_when_flags_change_in_between(fwd, bwd):
+    """srf_forward_train leaves d_0 out of `saved` when the backward's fused head will re-compute it; that choice reads the
+    process-global kernel mode and debug flags (1 << 16, 1 << 29, 1 << 30).  The backward must follow what ITS forward did,
+    not re-read that state: if the state changed in between, the step still matches fp64 autograd, or the backward refuses
+    with an SrfError that says so -- never plausible gradients computed from a d_0 that was not written (`saved` is
+    torch.empty: the allocator may hand back an earlier step's d_0).  The input is this case's own (seeded by the case), so no
+    earlier forward of the test left the right d_0 in a recycled block.  Bars: those of test_forward_train_and_backward_match_autograd."""
+    from sudo_rm_rf_amd import _lib, ops
+    cfg, Bt, T = ModelConfig("improved", 64, 128, 3, 5, 21, 128, 2), 3, 8000
+    seed = 500 + [s[1:] for s in _SWITCHES].index((fwd, bwd))
+    sd = weights.make_state_dict(cfg, seed=seed)
+    wav = torch.from_numpy(weights.make_mixture(Bt, T, seed=seed + 50))
+    gout = torch.randn(Bt, cfg.num_sources, T, generator=torch.Generator().manual_seed(seed + 100), dtype=torch.float64)
+    sd64 = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in sd.items()}
+    out64 = torch_oracle.forward(cfg, sd64, wav.double())
+    (out64 * gout).sum().backward()
+
+    model = build(cfg, sd).train()
+    err = None
+    try:
+        ops.set_debug_flags(fwd[0])
+        ops.set_kernel_mode(fwd[1])
+        out = model(wav.to(DEV))
+        ops.set_debug_flags(bwd[0])
+        ops.set_kernel_mode(bwd[1])
+        try:
+            (out * gout.to(torch.float32).to(DEV)).sum().backward()
+            torch.cuda.synchronize()
+        except _lib.SrfError as e:
+            err = str(e)
+    finally:
+        ops.set_debug_flags(0)
+        ops.set_kernel_mode(0)
+    oerr = (out.detach().cpu().double() - out64.detach()).abs().max().item()
+    assert oerr <= 1e-4, oerr
+    if err is not None:
+        print("forward %s -> backward %s: refused: %s" % (fwd, bwd, err))
+        assert "srf_forward_train" in err and "d_0" in err and "debug flags" in err, err
+        return
+    worst = ("", 0.0)
+    for (k, ref), p in zip(sd64.items(), model.state_dict(keep_vars=True).values()):
+        assert p.grad is not None, k
+        rel = ((p.grad.cpu().double() - ref.grad).abs().max() / ref.grad.abs().max().clamp_min(1e-12)).item()
+        worst = max(worst, (k, rel), key=lambda kv: kv[1])
+    print("forward %s -> backward %s: output %.2e, worst gradient %s %.2e" % ((fwd, bwd, oerr) + worst))
+    assert worst[1] <= 2e-3, worst

@@ -40,7 +40,11 @@ CASES = {
 
     "train_cfg2_bench": (ModelConfig("improved", 256, 512, 16, 5, 21, 512, 2), 4, 32000, 124, 214),
     "train_cfg4_bench": (ModelConfig("improved", 512, 512, 36, 6, 21, 2048, 2), 4, 32000, 105, 205),
+    # cfg 3 (GroupComm U8, G = 16) at the bench length: the TAC and (batch x group)-folded norm kernels at L = 3200
+    "train_cfg3_bench": (ModelConfig("groupcomm", 256, 512, 8, 5, 21, 512, 2, 1, 16), 4, 32000, 106, 206),
 }
+# fp64 cases that ALSO pin the gradient w.r.t. the input waveform (srf_backward_wav at a bench shape)
+GWAV_F64 = {"train_cfg3_bench"}
 SAMPLE = 4096      # gradient entries kept per parameter (strided)
 BIG_SAMPLE = 384   # ... for the BASELINE-shape cases (hundreds of tensors)
 
@@ -94,8 +98,9 @@ def main():
             model.pad_to_appropriate_length = lambda x: x
             mix, tgt = mix.double(), tgt.double()
         # the small cases also pin the gradient w.r.t. the INPUT waveform (round 6: srf_backward_wav), which the reference's
-        # autograd returns for a mixture that requires grad -- through the model and, for GroupComm, the mixture-consistency term
-        want_gwav = not f64
+        # autograd returns for a mixture that requires grad -- through the model and, for GroupComm, the mixture-consistency term;
+        # of the fp64 cases only those in GWAV_F64 (stored as float32 like the others)
+        want_gwav = not f64 or name in GWAV_F64
         if want_gwav:
             mix.requires_grad_()
         rec = model(mix)
@@ -117,11 +122,16 @@ def main():
                 m32 = (ref_imp.SuDORMRF if cfg.variant == "improved" else ref_gc.GroupCommSudoRmRf)(**cfg.ctor_kwargs())
             m32.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
             m32.train()
-            rec32 = m32(mix.float())
+            mix32 = mix.float().requires_grad_(want_gwav)
+            rec32 = m32(mix32)
             if cfg.variant == "groupcomm":
-                rec32 = ref_mc.apply(rec32, mix.float())
+                rec32 = ref_mc.apply(rec32, mix32)
             torch.clamp(loss_fn(rec32, tgt.float()), min=-30.0, max=30.0).backward()
             g32 = {k: p.grad.numpy().astype(np.float64) for k, p in m32.state_dict(keep_vars=True).items()}
+            if want_gwav:     # ... and per example for the input gradient
+                gw = arrays["gwav"].astype(np.float64)
+                dw = np.abs(mix32.grad.numpy().astype(np.float64) - gw).reshape(batch, -1).max(1)
+                arrays["d:gwav"] = dw / np.maximum(np.abs(gw).reshape(batch, -1).max(1), 1e-300)
         for k, p in model.state_dict(keep_vars=True).items():
             g = p.grad.numpy()
             if g32 is not None:
