@@ -1,6 +1,6 @@
 /*
  * sudormrf_hip.h -- C ABI of libsudormrf_hip.so, the MI355X (gfx950) hot path of
- * SuDoRM-RF (Improved SuDORMRF and GroupComm SuDoRM-RF v2) inference forward.
+ * SuDoRM-RF (Improved SuDORMRF, GroupComm SuDoRM-RF v2 and Causal SuDORMRF v3) inference forward.
  *
  * Boundary replaced (reference is pure PyTorch, paths relative to
  * /root/reference/sudo_rm_rf/dnn/):
@@ -21,6 +21,9 @@
  *   srf_wav_normalize / srf_wav_denormalize <- the callers' normalise / rescale lines   README.md:100-114
  *   srf_pit_sisdr_*        <- PITLossWrapper(PairwiseNegSDR("sisdr")) fwd/bwd        losses/sisdr.py:254-311,426-458
  *   srf_perm_inv_sisdr     <- PermInvariantSISDR.forward (validation metric)        losses/sisdr.py:66-196
+ *   srf_forward (causal)   <- CausalSuDORMRF.forward      models/causal_improved_sudormrf_v3.py (ABI 16)
+ *   srf_causal_encoder     <- its encoder (ScaledWSConv1d, 2K-1 taps of which K are live)
+ *   srf_causal_dwconv / _merge / _pyramid <- UConvBlock's causal k = 21 depthwise pyramid + upsample/add
  *
  * Conventions
  *   - every pointer is a DEVICE pointer to contiguous fp32 (or fp64 for GlobLN sums) owned by the
@@ -44,7 +47,7 @@
 extern "C" {
 #endif
 
-#define SRF_ABI_VERSION 15
+#define SRF_ABI_VERSION 16
 
 /* GlobLN statistics layout: "sums" = fp64 [groups][SRF_STAT_BUCKETS][2] {sum, sum of squares}; the
  * statistic of a group is the total over its buckets (producers spread their atomics over buckets). */
@@ -57,12 +60,14 @@ extern "C" {
 
 #define SRF_VARIANT_IMPROVED 0
 #define SRF_VARIANT_GROUPCOMM 1
+#define SRF_VARIANT_CAUSAL 2      /* CausalSuDORMRF (causal_improved_sudormrf_v3.py), ABI 16: inference forward only */
 
 /* Constructor arguments of the reference models, same meaning
- * (improved_sudormrf.py:224-231, groupcomm_sudormrf_v2.py:232-241). */
+ * (improved_sudormrf.py:224-231, groupcomm_sudormrf_v2.py:232-241, causal_improved_sudormrf_v3.py CausalSuDORMRF).
+ * Causal: in_audio_channels is used (A), group_size must be 1. */
 typedef struct srf_config {
   int variant;           /* SRF_VARIANT_* */
-  int in_audio_channels; /* 1 for Improved */
+  int in_audio_channels; /* 1 for Improved; A for GroupComm and Causal */
   int out_channels;      /* B */
   int in_channels;       /* C */
   int num_blocks;        /* U */
@@ -154,7 +159,9 @@ int srf_plan_padded_length(const srf_plan* plan); /* T' */
 int srf_plan_num_launches(const srf_plan* plan);  /* kernel launches per forward (informational) */
 
 /* params: host array of num_params device pointers in the reference's state_dict() order
- * (SURVEY.md Appendix A).  wav: [batch, in_audio_channels, T].  out: [batch, S*in_audio, T]. */
+ * (causal: DESIGN.md §11).  wav: [batch, in_audio_channels, T].  out: [batch, S*in_audio, T].
+ * Causal plans: skipinit_gain (a device scalar per block) is folded into res_conv inside the forward, never read by the
+ * host; the training entry points, their buffer sizes and srf_separate refuse causal plans with SRF_EINVAL. */
 int srf_forward(const srf_plan* plan, const float* const* params, int num_params,
                 const float* wav, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -166,8 +173,14 @@ int srf_forward(const srf_plan* plan, const float* const* params, int num_params
 int srf_separate(const srf_plan* plan, const float* const* params, int num_params, const float* wav, float* out,
                  float* stats, int mixture_consistency, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Causal plans only: the per-block plain attributes alpha / beta of UConvBlock (both 1.0 as the reference constructs them,
+ * the default of a new plan).  srf_forward computes res_conv(.) * skipinit_gain * alpha[i] + x and proj_1x1(x / beta[i]).
+ * alpha, beta: host arrays of n = num_blocks floats.  Call before the plan's first forward. */
+int srf_plan_set_block_scales(srf_plan* plan, const float* alpha, const float* beta, int n);
+
 /* Copy an intermediate of the LAST srf_forward on this workspace into dst (for parity tests).
- * what: 0 = encoder output [Bt,N,L], 1 = separation-module output [Bt,B,L], 2 = masked [Bt,S*A*N,L].
+ * what: 0 = encoder output [Bt,N,L], 1 = separation-module output [Bt,B,L], 2 = masked [Bt,S*A*N,L]
+ * (causal plans: 2 = mask_net output before mask_nl_class).
  * 2 fails (SRF_EINVAL) at shapes whose forward runs the mask GEMM fused with the decoder (launches with at least as many
  * 256 x 128 tiles as the GPU has CUs): the masked tensor then never exists in memory. */
 int srf_debug_fetch(const srf_plan* plan, const void* workspace, int what, float* dst, size_t dst_floats,
@@ -288,6 +301,30 @@ size_t srf_pyramid_scratch_bytes(int groups, int C, int L, int D);
 int srf_pyramid(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
                 const float* const* bias, const float* const* gamma, const float* const* beta, int groups,
                 int C, int L, int D, void* scratch, double* out_sums, void* stream);
+
+/* ---- Causal SuDORMRF (ABI 16; causal_improved_sudormrf_v3.py) ----
+ * srf_causal_encoder: out[b,n,l] = sum_{a, k<K} w[n,a,k] * x[b,a, h*l+k-2h], h = K/2, w: [N, A, 2K-1] (the stored
+ *   ScaledWSConv1d weight; taps K..2K-2 are masked in the reference and never read here).  Samples outside [0,T) are 0.
+ * srf_causal_dwconv: one spp_dw level, y[r,j] = PReLU_out(bias[c] + sum_{k<=10} w[c,k] * f(x[r, stride*j-10+k])),
+ *   r = (b,c), w: [C,1,21] (taps 11..20 never read), f = PReLU_in (in_prelu: [1] slope, NULL = identity), zero left of 0
+ *   after f; out_prelu NULL = no activation.  x: [Bt,C,Lin], y: [Bt,C,(Lin-1)/stride+1], y must not alias x.
+ * srf_causal_merge: y[r,j] = l_0[j] + (l_1[j>>1] + (... + l_{D-1}[j>>(D-1)])), levels[k]: [Bt,C,L>>k].
+ * srf_causal_pyramid: the whole pyramid of one UConvBlock in ONE launch: levels = D x srf_causal_dwconv (level 0 from y1
+ *   with in_prelu = proj_1x1's PReLU, stride 1; level k from level k-1, stride 2; each with its own bias and PReLU), then
+ *   srf_causal_merge -- bit-identical to that sequence, but y1 is read once and merged written once.  w / bias / prelu:
+ *   D pointers each (spp_dw[k].conv.weight / .bias, spp_dw[k].act.weight).  merged must NOT alias y1.
+ *   srf_causal_pyramid_supported: the shapes it takes (1 <= D <= 8, L % 2^(D-1) == 0). */
+int srf_causal_encoder(const float* wav, const float* w, float* out, int Bt, int A, int T, int N, int K, int L, void* stream);
+int srf_causal_dwconv(const float* x, const float* w, const float* bias, const float* in_prelu, const float* out_prelu,
+                      float* y, int Bt, int C, int Lin, int stride, void* stream);
+int srf_causal_merge(const float* const* levels, int D, float* y, int Bt, int C, int L, void* stream);
+int srf_causal_pyramid_supported(int C, int L, int D);
+int srf_causal_pyramid(const float* y1, float* merged, const float* in_prelu, const float* const* w,
+                       const float* const* bias, const float* const* prelu, int Bt, int C, int L, int D, void* stream);
+/* dst = src * dscale[0] * hscale (dscale: a DEVICE scalar, NULL = 1) -- the skipinit_gain * alpha / 1 / beta folding.
+ * srf_prelu_apply: y = PReLU_a(x), slope[0] on the device (a stand-alone nn.PReLU).  n elements, y may alias x. */
+int srf_causal_scale(const float* src, float* dst, long n, const float* dscale, float hscale, void* stream);
+int srf_prelu_apply(const float* x, const float* slope, float* y, long n, void* stream);
 
 /* Transposed conv synthesis + crop: out[b,o,t] = sum_{ci,l,k: h*l+k-h=t} v[b,ci,l]*w[ci,o,k], t<T.
  * v: [Bt,Ci,L], w: [Ci,Co,K] (ConvTranspose1d layout), out: [Bt,Co,T].

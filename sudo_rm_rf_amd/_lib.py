@@ -12,11 +12,11 @@ import torch  # noqa: F401  (loads torch's libamdhip64 first so the extension bi
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # SRF_LIB: an alternative build of the same library (same-box A/B of kernel variants, tools/); default = the in-tree build
 LIB_PATH = os.environ.get("SRF_LIB") or os.path.join(_PKG, "libsudormrf_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 STAT_BUCKETS = 64
 
 SRF_OK = 0
-VARIANT_IMPROVED, VARIANT_GROUPCOMM = 0, 1
+VARIANT_IMPROVED, VARIANT_GROUPCOMM, VARIANT_CAUSAL = 0, 1, 2
 
 
 class SrfError(RuntimeError):
@@ -130,6 +130,14 @@ _PROTOS = {
     "srf_feeder_submit": (_i, [_vp, _vp, _vp, _vp]),
     "srf_feeder_wait": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i)]),
     "srf_feeder_normalize": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.c_float, _vp, _vp, _vp]),
+    "srf_plan_set_block_scales": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _i]),
+    "srf_causal_encoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "srf_causal_dwconv": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "srf_causal_merge": (_i, [C.POINTER(_vp), _i, _vp, _i, _i, _i, _vp]),
+    "srf_causal_pyramid_supported": (_i, [_i, _i, _i]),
+    "srf_causal_pyramid": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp]),
+    "srf_causal_scale": (_i, [_vp, _vp, _l, _vp, C.c_float, _vp]),
+    "srf_prelu_apply": (_i, [_vp, _vp, _vp, _l, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

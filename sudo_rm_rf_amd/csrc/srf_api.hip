@@ -208,14 +208,17 @@ extern "C" size_t srf_decoder_scratch_floats(int Bt, int Ci, int Co, int K, int 
 }
 
 static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T,
-                            float* scratch, const float* post_stats, const float* post_wav, int post_mc, void* stream);
+                            float* scratch, const float* post_stats, const float* post_wav, int post_mc, void* stream,
+                            const float* in_prelu = nullptr);
 extern "C" int srf_decoder(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K,
                            int L, int T, float* scratch, void* stream) {
   return srf_decoder_impl(v, w, out, Bt, Ci, Co, K, L, T, scratch, nullptr, nullptr, 0, stream);
 }
 // post_stats / post_wav / post_mc: the callers' rescale (+ mixture consistency) folded into the overlap-add (srf_separate)
+// in_prelu: a PReLU slope applied to v as the frame GEMM loads it (the causal model's mask_nl_class), NULL = none
 static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T,
-                            float* scratch, const float* post_stats, const float* post_wav, int post_mc, void* stream) {
+                            float* scratch, const float* post_stats, const float* post_wav, int post_mc, void* stream,
+                            const float* in_prelu) {
   SRF_CHECK_ARG(v && w && out && scratch, "srf_decoder: null pointer");
   SRF_CHECK_ARG(Bt > 0 && Ci > 0 && Co > 0 && L > 0 && T > 0, "srf_decoder: bad sizes");
   SRF_CHECK_ARG(K >= 3 && (K & 1), "srf_decoder: kernel size must be odd (got %d)", K);
@@ -230,7 +233,8 @@ static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, 
   if (rc) return rc;
   rc = srf_zero_launch(zb, sizeof(float) * align_up((size_t)M, 64), st);
   if (rc) return rc;
-  rc = srf_pw_conv(v, wt, zb, z, Bt, Ci, M, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
+  const srf_norm act{nullptr, nullptr, nullptr, in_prelu};
+  rc = srf_pw_conv(v, wt, zb, z, Bt, Ci, M, L, in_prelu ? &act : nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
   if (rc) return rc;
   return srf_overlap_add_launch(z, out, Bt, Co, K, L, T, 1, post_stats, post_wav, post_mc, st);
 }
@@ -245,11 +249,13 @@ static int plan_fail(srf_plan* p, int rc) {
   return rc;
 }
 
+static int causal_plan_create(const srf_config* c, int batch, int T, srf_plan** out);
 extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan** out) {
   SRF_CHECK_ARG(c && out, "srf_plan_create: null pointer");
   *out = nullptr;
-  SRF_CHECK_ARG(c->variant == SRF_VARIANT_IMPROVED || c->variant == SRF_VARIANT_GROUPCOMM,
+  SRF_CHECK_ARG(c->variant == SRF_VARIANT_IMPROVED || c->variant == SRF_VARIANT_GROUPCOMM || c->variant == SRF_VARIANT_CAUSAL,
                 "srf_plan_create: unknown variant %d", c->variant);
+  if (c->variant == SRF_VARIANT_CAUSAL) return causal_plan_create(c, batch, T, out);
   SRF_CHECK_ARG(batch > 0 && T > 0, "srf_plan_create: batch and T must be positive");
   SRF_CHECK_ARG(c->out_channels > 0 && c->in_channels > 0 && c->num_blocks > 0 && c->enc_num_basis > 0 &&
                     c->num_sources > 0,
@@ -361,6 +367,114 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   return SRF_OK;
 }
 
+// ---- causal variant (CausalSuDORMRF, causal_improved_sudormrf_v3.py) -----------------------------------------------------
+// state_dict order: encoder.weight, bottleneck.{weight,bias}; per block: skipinit_gain, proj_1x1.conv.{weight,bias},
+// proj_1x1.act.weight, D x spp_dw.k.{conv.weight, conv.bias, act.weight}, res_conv.{weight,bias}; tail: mask_net.0.weight,
+// mask_net.1.{weight,bias}, decoder.weight, mask_nl_class.weight.
+static int causal_plan_create(const srf_config* c, int batch, int T, srf_plan** out) {
+  SRF_CHECK_ARG(batch > 0 && T > 0, "srf_plan_create: batch and T must be positive");
+  SRF_CHECK_ARG(c->in_audio_channels > 0 && c->out_channels > 0 && c->in_channels > 0 && c->num_blocks > 0 &&
+                    c->enc_num_basis > 0 && c->num_sources > 0,
+                "srf_plan_create: non-positive model dimension (causal variant)");
+  SRF_CHECK_ARG(c->group_size == 1, "srf_plan_create: the causal variant has no groups (group_size must be 1, got %d)",
+                c->group_size);
+  SRF_CHECK_ARG(c->upsampling_depth >= 1 && c->upsampling_depth <= SRF_MAX_DEPTH,
+                "srf_plan_create: upsampling_depth %d unsupported (1..%d)", c->upsampling_depth, SRF_MAX_DEPTH);
+  SRF_CHECK_ARG(c->enc_kernel_size >= 3 && (c->enc_kernel_size & 1),
+                "srf_plan_create: enc_kernel_size must be odd for the causal variant (got %d)", c->enc_kernel_size);
+  srf_plan* p = new (std::nothrow) srf_plan();
+  SRF_CHECK_ARG(p != nullptr, "srf_plan_create: out of host memory");
+  p->cfg = *c;
+  const int D = c->upsampling_depth, U = c->num_blocks, K = c->enc_kernel_size, N = c->enc_num_basis;
+  const int B = c->out_channels, Cc = c->in_channels;
+  const int h = K / 2;
+  const long nls = (long)h << D;   // n_least_samples_req
+  const long Tp = (T < nls) ? nls : ((T / nls) + (T % nls ? 1 : 0)) * nls;
+  if (Tp > (1L << 30)) {
+    srf_set_error("srf_plan_create: T=%d too long", T);
+    return plan_fail(p, SRF_EINVAL);
+  }
+  p->A = c->in_audio_channels;
+  p->Bt = batch;
+  p->T = T;
+  p->Tp = (int)Tp;
+  p->L = (int)(Tp / h);            // (T' + 2(K-1) - (2K-1)) / h + 1
+  p->SA = c->num_sources * p->A;
+  p->Bg = batch;
+  p->nB = B;
+  p->nC = Cc;
+  if (batch > 65535) {
+    srf_set_error("srf_plan_create: batch %d too large (max 65535 per call)", batch);
+    return plan_fail(p, SRF_EINVAL);
+  }
+  p->p_block0 = 3;
+  p->p_ublock_off = 0;
+  p->p_block_stride = 6 + 3 * D;
+  p->p_tail = 3 + U * p->p_block_stride;
+  p->n_params = p->p_tail + 5;
+  p->slots_per_block = 0;
+  p->n_slots = 0;
+  p->alpha.assign(U, 1.f);
+  p->beta.assign(U, 1.f);
+  const size_t F = sizeof(float), L = p->L;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off = align_up(off + (bytes ? bytes : 1), 256);
+    return o;
+  };
+  p->stats_bytes = 0;
+  p->off_stats = 0;
+  p->off_enc = take(F * batch * N * L);
+  p->off_xa = take(F * batch * B * L);
+  p->off_xb = take(F * batch * B * L);
+  p->off_xq = p->off_xu = 0;
+  p->off_y1 = take(F * batch * Cc * L);
+  p->off_merged = take(F * batch * Cc * L);
+  for (int k = 0; k < D; ++k) p->off_lv[k] = take(F * batch * Cc * (L >> k));
+  p->off_masked = take(F * batch * p->SA * N * L);
+  p->off_dec = take(F * srf_decoder_scratch_floats(batch, p->SA * N, p->SA, K, p->L));
+  p->fused_pyramid = srf_causal_pyramid_supported(Cc, p->L, D);
+  p->off_pyr = 0;
+  // per block: res_conv weight * (gain * alpha) [B][C] | its bias [B]   and   proj_1x1 weight / beta [C][B]
+  const size_t res_floats = align_up((size_t)B * Cc, 64) + align_up((size_t)B, 64);
+  p->off_fold_res = take(F * res_floats * U);
+  p->off_fold_proj = take(F * (size_t)Cc * B * U);
+  p->pk_of_param.assign(p->n_params, 0);
+  auto add_pack = [&](int param, int cout, int cin) {
+    const size_t bytes = srf_packed_pw_weight_bytes(cout, cin);
+    if (!bytes) return;
+    const size_t o = take(bytes);
+    p->pk_param.push_back(param);
+    p->pk_cout.push_back(cout);
+    p->pk_cin.push_back(cin);
+    p->pk_off.push_back(o);
+    p->pk_of_param[param] = o;
+  };
+  add_pack(1, B, N);
+  for (int i = 0; i < U; ++i) {
+    const int pb = p->p_block0 + i * p->p_block_stride;
+    add_pack(pb + 1, Cc, B);
+    add_pack(pb + 4 + 3 * D, B, Cc);
+  }
+  add_pack(p->p_tail + 1, p->SA * N, B);
+  p->off_wdpack = 0;
+  p->total_bytes = off;
+  p->n_launches = 3 /*fold, pack, encoder*/ + 1 + U * 3 + 1 + 4;
+  *out = p;
+  return SRF_OK;
+}
+
+extern "C" int srf_plan_set_block_scales(srf_plan* p, const float* alpha, const float* beta, int n) {
+  SRF_CHECK_ARG(p && alpha && beta, "srf_plan_set_block_scales: null pointer");
+  SRF_CHECK_ARG(p->cfg.variant == SRF_VARIANT_CAUSAL, "srf_plan_set_block_scales: causal plans only (variant %d)", p->cfg.variant);
+  SRF_CHECK_ARG(n == p->cfg.num_blocks, "srf_plan_set_block_scales: expected %d blocks, got %d", p->cfg.num_blocks, n);
+  for (int i = 0; i < n; ++i) SRF_CHECK_ARG(beta[i] != 0.f, "srf_plan_set_block_scales: beta[%d] is zero", i);
+  p->alpha.assign(alpha, alpha + n);
+  p->beta.assign(beta, beta + n);
+  return SRF_OK;
+}
+
 extern "C" void srf_plan_destroy(srf_plan* p) { delete p; }
 extern "C" size_t srf_plan_workspace_bytes(const srf_plan* p) { return p ? p->total_bytes : 0; }
 extern "C" int srf_plan_num_params(const srf_plan* p) { return p ? p->n_params : 0; }
@@ -387,6 +501,7 @@ extern "C" int srf_forward(const srf_plan* p, const float* const* P, int num_par
 extern "C" int srf_separate(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                             float* stats, int mixture_consistency, void* workspace, size_t workspace_bytes, void* stream) {
   SRF_CHECK_ARG(p && wav && stats, "srf_separate: null pointer");
+  SRF_CHECK_ARG(p->cfg.variant != SRF_VARIANT_CAUSAL, "srf_separate: not available for the causal variant (CausalSuDORMRF)");
   SRF_CHECK_ARG(p->A == 1, "srf_separate: the recipe is defined for single-channel mixtures (in_audio_channels = %d)", p->A);
   int rc = srf_wav_stats(wav, stats, p->Bt * p->A, p->T, stream);
   if (rc) return rc;
@@ -396,6 +511,7 @@ extern "C" int srf_separate(const srf_plan* p, const float* const* P, int num_pa
 static int srf_forward_body(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                             void* workspace, size_t workspace_bytes, const float* wav_stats, int mixture_consistency,
                             void* stream);
+static int causal_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace, void* stream);
 void srf_pw_prefer_paired(bool on);   // srf_pwconv.hip: the paired-block form of the 256 x 128 GEMM for this thread's launches
 static int srf_forward_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                             void* workspace, size_t workspace_bytes, const float* wav_stats, int mixture_consistency,
@@ -423,6 +539,7 @@ static int srf_forward_body(const srf_plan* p, const float* const* P, int num_pa
   // profiler: intervals run from mark to mark, so without this one the first kernel's interval would also hold the
   // host-side gap since the previous forward
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
+  if (p->cfg.variant == SRF_VARIANT_CAUSAL) return causal_forward(p, P, wav, out, workspace, stream);
 
   const srf_config& c = p->cfg;
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
@@ -644,4 +761,138 @@ extern "C" int srf_debug_fetch(const srf_plan* p, const void* workspace, int wha
   SRF_CHECK_HIP(hipMemcpyAsync(dst, ws + off, n * sizeof(float), hipMemcpyDeviceToDevice,
                                (hipStream_t)stream));
   return SRF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// causal forward (CausalSuDORMRF.forward): encoder -> bottleneck -> U x [proj_1x1 -> fused causal pyramid -> res_conv with
+// skipinit_gain * alpha folded into its weights, + residual] -> PReLU + mask conv -> PReLU folded into the decoder's load.
+// ---------------------------------------------------------------------------------------------
+int srf_causal_scale_many(const float* const* src, float* const* dst, const long* n, const float* const* dscale,
+                          const float* hscale, int count, hipStream_t st);
+static int causal_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace, void* stream) {
+  const srf_config& c = p->cfg;
+  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
+  const int Bt = p->Bt, L = p->L, B = p->nB, Cc = p->nC;
+  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  auto fptr = [&](size_t o) { return (float*)(ws + o); };
+  int rc;
+  // ---- fold: res_conv weight / bias * (skipinit_gain * alpha) for every block, proj_1x1 weight / beta where beta != 1
+  const size_t res_floats = align_up((size_t)B * Cc, 64) + align_up((size_t)B, 64);
+  std::vector<const float*> fsrc, fscale;
+  std::vector<float*> fdst;
+  std::vector<long> fn;
+  std::vector<float> fh;
+  std::vector<const float*> wproj(U), wres(U), bres(U);
+  for (int i = 0; i < U; ++i) {
+    const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
+    float* rw = fptr(p->off_fold_res) + (size_t)i * res_floats;
+    float* rb = rw + align_up((size_t)B * Cc, 64);
+    fsrc.push_back(Pb[4 + 3 * D]); fdst.push_back(rw); fn.push_back((long)B * Cc); fscale.push_back(Pb[0]); fh.push_back(p->alpha[i]);
+    fsrc.push_back(Pb[5 + 3 * D]); fdst.push_back(rb); fn.push_back((long)B); fscale.push_back(Pb[0]); fh.push_back(p->alpha[i]);
+    wres[i] = rw;
+    bres[i] = rb;
+    wproj[i] = Pb[1];
+    if (p->beta[i] != 1.f) {
+      float* pw = fptr(p->off_fold_proj) + (size_t)i * Cc * B;
+      fsrc.push_back(Pb[1]); fdst.push_back(pw); fn.push_back((long)Cc * B); fscale.push_back(nullptr); fh.push_back(1.f / p->beta[i]);
+      wproj[i] = pw;
+    }
+  }
+  rc = srf_causal_scale_many(fsrc.data(), fdst.data(), fn.data(), fscale.data(), fh.data(), (int)fsrc.size(), st);
+  if (rc) return rc;
+  // ---- split-bf16 weight images of the packed shapes (kernel mode 0), from the folded copies where there are any
+  const bool use_pack = srf_kernel_mode() == 0 && !(srf_debug_flags() & 8) && !p->pk_param.empty();
+  auto source_of = [&](int param) -> const float* {
+    const int rel = param - p->p_block0;
+    if (param >= p->p_block0 && param < p->p_tail) {
+      const int i = rel / p->p_block_stride, r = rel % p->p_block_stride;
+      if (r == 1) return wproj[i];
+      if (r == 4 + 3 * D) return wres[i];
+    }
+    return P[param];
+  };
+  if (use_pack) {
+    std::vector<const float*> pw(p->pk_param.size());
+    std::vector<void*> pd(p->pk_param.size());
+    for (size_t i = 0; i < p->pk_param.size(); ++i) {
+      pw[i] = source_of(p->pk_param[i]);
+      pd[i] = ws + p->pk_off[i];
+    }
+    rc = srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
+    if (rc) return rc;
+  }
+  auto packed = [&](int param) -> const void* {
+    return (use_pack && p->pk_of_param[param]) ? (const void*)(ws + p->pk_of_param[param]) : nullptr;
+  };
+  // ---- front end: causal encoder, bottleneck (no norm)
+  float* enc = fptr(p->off_enc);
+  rc = srf_causal_encoder(wav, P[0], enc, Bt, p->A, p->T, N, K, L, stream);
+  if (rc) return rc;
+  float* cur = fptr(p->off_xa);
+  float* nxt = fptr(p->off_xb);
+  float* y1 = fptr(p->off_y1);
+  float* merged = fptr(p->off_merged);
+  rc = srf_pw_conv_packed(enc, P[1], packed(1), P[2], cur, Bt, N, B, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
+  if (rc) return rc;
+  // ---- separation module.  res_conv of block i + proj_1x1 of block i + 1 as one launch where the pair kernel takes the
+  // shape (its no-prologue form: residual required), as in the Improved forward
+  const bool fused = p->fused_pyramid && srf_kernel_mode() != 1 && !(srf_debug_flags() & 16);
+  const bool pair = use_pack && !(srf_debug_flags() & 1) && srf_pw_conv_pair_supported(Bt, Cc, B, Cc, L);
+  bool y1_ready = false;
+  for (int i = 0; i < U; ++i) {
+    const int pb = p->p_block0 + i * p->p_block_stride;
+    const float* const* Pb = P + pb;
+    if (!y1_ready) {
+      rc = srf_pw_conv_packed(cur, wproj[i], packed(pb + 1), Pb[2], y1, Bt, B, Cc, L, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                              stream);
+      if (rc) return rc;
+    }
+    y1_ready = false;
+    if (fused) {
+      const float *pw[SRF_MAX_DEPTH], *pbias[SRF_MAX_DEPTH], *pa[SRF_MAX_DEPTH];
+      for (int k = 0; k < D; ++k) {
+        pw[k] = Pb[4 + 3 * k];
+        pbias[k] = Pb[5 + 3 * k];
+        pa[k] = Pb[6 + 3 * k];
+      }
+      rc = srf_causal_pyramid(y1, merged, Pb[3], pw, pbias, pa, Bt, Cc, L, D, stream);
+      if (rc) return rc;
+    } else {
+      const float* levels[SRF_MAX_DEPTH];
+      for (int k = 0; k < D; ++k) {
+        float* dk = fptr(p->off_lv[k]);
+        rc = srf_causal_dwconv(k == 0 ? y1 : levels[k - 1], Pb[4 + 3 * k], Pb[5 + 3 * k], k == 0 ? Pb[3] : nullptr,
+                               Pb[6 + 3 * k], dk, Bt, Cc, k == 0 ? L : (L >> (k - 1)), k == 0 ? 1 : 2, stream);
+        if (rc) return rc;
+        levels[k] = dk;
+      }
+      rc = srf_causal_merge(levels, D, merged, Bt, Cc, L, stream);
+      if (rc) return rc;
+    }
+    const int pn = pb + p->p_block_stride;
+    if (pair && i + 1 < U && packed(pb + 4 + 3 * D) && packed(pn + 1)) {
+      rc = srf_pw_conv_pair(merged, packed(pb + 4 + 3 * D), bres[i], nxt, nullptr, cur, packed(pn + 1), P[pn + 2], y1, nullptr,
+                            Bt, Cc, B, Cc, L, stream);
+      y1_ready = true;
+    } else {
+      rc = srf_pw_conv_packed(merged, wres[i], packed(pb + 4 + 3 * D), bres[i], nxt, Bt, Cc, B, L, nullptr, cur, nullptr, 0,
+                              nullptr, 0, stream);
+    }
+    if (rc) return rc;
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  // ---- mask_net (PReLU on load + 1x1) -> mask_nl_class PReLU on the decoder frame GEMM's load -> overlap-add + crop
+  const float* const* Pt = P + p->p_tail;
+  float* masks = fptr(p->off_masked);
+  {
+    srf_norm pre{nullptr, nullptr, nullptr, Pt[0]};
+    rc = srf_pw_conv_packed(cur, Pt[1], packed(p->p_tail + 1), Pt[2], masks, Bt, B, p->SA * N, L, &pre, nullptr, nullptr, 0,
+                            nullptr, 0, stream);
+    if (rc) return rc;
+  }
+  return srf_decoder_impl(masks, Pt[3], out, Bt, p->SA * N, p->SA, K, L, p->T, fptr(p->off_dec), nullptr, nullptr, 0, stream,
+                          Pt[4]);
 }

@@ -19,4 +19,8 @@ struct srf_plan {
   std::vector<int> pk_param, pk_cout, pk_cin;
   std::vector<size_t> pk_off;
   std::vector<size_t> pk_of_param;  // [n_params] offset or 0
+  // causal variant (SRF_VARIANT_CAUSAL): UConvBlock's plain attributes alpha / beta per block (srf_plan_set_block_scales)
+  // and the workspace copies of the weights they and skipinit_gain are folded into
+  std::vector<float> alpha, beta;
+  size_t off_fold_res, off_fold_proj, off_merged;
 };

@@ -264,8 +264,19 @@ static int train_check(const srf_plan* p, const char* who) {
   return SRF_OK;
 }
 
-extern "C" size_t srf_train_saved_bytes(const srf_plan* p) { return p ? train_layout(p).total : 0; }
-extern "C" size_t srf_train_scratch_bytes(const srf_plan* p) { return p ? scratch_layout(p).total : 0; }
+// The causal variant (CausalSuDORMRF) has an inference forward only: every training entry point refuses its plans before
+// anything is launched; the two size queries return 0 with the same message in srf_last_error().
+static bool causal_refused(const srf_plan* p, const char* who) {
+  if (!p || p->cfg.variant != SRF_VARIANT_CAUSAL) return false;
+  srf_set_error("%s: not available for the causal variant (CausalSuDORMRF has an inference forward only)", who);
+  return true;
+}
+extern "C" size_t srf_train_saved_bytes(const srf_plan* p) {
+  return p && !causal_refused(p, "srf_train_saved_bytes") ? train_layout(p).total : 0;
+}
+extern "C" size_t srf_train_scratch_bytes(const srf_plan* p) {
+  return p && !causal_refused(p, "srf_train_scratch_bytes") ? scratch_layout(p).total : 0;
+}
 
 static int forward_train_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                               void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, bool split_tail, bool* skip_d0_out,
@@ -281,6 +292,7 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
 // split-bf16: with an exact forward every parameter gradient is within 2e-5 of the reference's.
 extern "C" int srf_forward_train(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                                  void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (causal_refused(p, "srf_forward_train")) return SRF_EINVAL;
   const int mode = srf_kernel_mode(), flags = srf_debug_flags();
   const bool exact = mode == 0 && !(flags & (1 << 28));
   const int prev = exact ? srf_kernel_mode_override(2) : -1;
@@ -514,6 +526,7 @@ extern "C" int srf_backward_wav(const srf_plan* p, const float* const* P, float*
 static int backward_impl(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
                          const float* grad_out, const void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
                          float* grad_wav, void* stream) {
+  if (causal_refused(p, grad_wav ? "srf_backward_wav" : "srf_backward")) return SRF_EINVAL;
   SRF_CHECK_ARG(p && P && G && wav && grad_out && saved && scratch, "srf_backward: null pointer");
   SRF_CHECK_ARG(num_params == p->n_params, "srf_backward: expected %d parameter tensors, got %d", p->n_params, num_params);
   int rc = train_check(p, "srf_backward");

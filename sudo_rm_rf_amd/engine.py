@@ -34,8 +34,9 @@ _MAX_GRAPHS = 4
 
 def _config_struct(variant, in_audio_channels, out_channels, in_channels, num_blocks, upsampling_depth,
                    enc_kernel_size, enc_num_basis, num_sources, group_size):
+    variants = {"improved": _lib.VARIANT_IMPROVED, "groupcomm": _lib.VARIANT_GROUPCOMM, "causal": _lib.VARIANT_CAUSAL}
     return _lib.srf_config(
-        variant=_lib.VARIANT_GROUPCOMM if variant == "groupcomm" else _lib.VARIANT_IMPROVED,
+        variant=variants.get(variant, _lib.VARIANT_IMPROVED),
         in_audio_channels=in_audio_channels, out_channels=out_channels, in_channels=in_channels,
         num_blocks=num_blocks, upsampling_depth=upsampling_depth, enc_kernel_size=enc_kernel_size,
         enc_num_basis=enc_num_basis, num_sources=num_sources, group_size=group_size)
@@ -47,10 +48,16 @@ class Plan:
     def __init__(self, cfg_tuple, batch, T, device):
         lib = _lib.load()
         self.cfg_tuple, self.batch, self.T, self.device = cfg_tuple, batch, T, device
-        cfg = _config_struct(*cfg_tuple)
+        # (the causal model appends its blocks' (alpha, beta) attributes to the 10 constructor fields)
+        cfg = _config_struct(*cfg_tuple[:10])
         handle = C.c_void_p()
         _lib.check(lib.srf_plan_create(C.byref(cfg), batch, T, C.byref(handle)), "srf_plan_create")
         self.handle = handle
+        if len(cfg_tuple) > 10:
+            scales = cfg_tuple[10]
+            alpha = (C.c_float * len(scales))(*[a for a, _ in scales])
+            beta = (C.c_float * len(scales))(*[b for _, b in scales])
+            _lib.check(lib.srf_plan_set_block_scales(handle, alpha, beta, len(scales)), "srf_plan_set_block_scales")
         self.workspace_bytes = lib.srf_plan_workspace_bytes(handle)
         self.num_params = lib.srf_plan_num_params(handle)
         self.frames = lib.srf_plan_frames(handle)

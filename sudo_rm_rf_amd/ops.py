@@ -449,6 +449,84 @@ def wav_denormalize(est, stats, mix_norm=None):
     return out
 
 
+# ---- causal SuDoRM-RF (causal_improved_sudormrf_v3.py) ---------------------------------------------------------------
+def causal_encoder(wav, weight, L):
+    """wav [Bt,A,T], weight [N,A,2K-1] (the stored ScaledWSConv1d weight; its masked taps are not read) -> [Bt,N,L]."""
+    dev = _chk(wav, weight)
+    Bt, A, T = wav.shape
+    N, A2, KW = weight.shape
+    if A != A2 or KW % 2 == 0:
+        raise _lib.SrfError("causal_encoder: weight %s does not fit input %s" % (tuple(weight.shape), tuple(wav.shape)))
+    K = (KW + 1) // 2
+    out = torch.empty((Bt, N, L), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().srf_causal_encoder(_lib.ptr(wav), _lib.ptr(weight), _lib.ptr(out), Bt, A, T, N, K, L,
+                                              _lib.current_stream(dev)), "srf_causal_encoder")
+    return out
+
+
+def causal_dwconv(x, weight, bias, stride, in_prelu=None, out_prelu=None):
+    """One causal k = 21 depthwise level: x [Bt,C,Lin], weight [C,1,21] -> PReLU_out(conv(PReLU_in(x))) [Bt,C,(Lin-1)/s+1]."""
+    dev = _chk(x, weight, bias, in_prelu, out_prelu)
+    Bt, Cc, Lin = x.shape
+    if weight.shape != (Cc, 1, 21):
+        raise _lib.SrfError("causal_dwconv: weight must be [%d, 1, 21], got %s" % (Cc, tuple(weight.shape)))
+    y = torch.empty((Bt, Cc, (Lin - 1) // stride + 1), dtype=torch.float32, device=dev)
+    rc = _lib.load().srf_causal_dwconv(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(in_prelu), _lib.ptr(out_prelu),
+                                       _lib.ptr(y), Bt, Cc, Lin, stride, _lib.current_stream(dev))
+    _lib.check(rc, "srf_causal_dwconv")
+    return y
+
+
+def causal_merge(levels):
+    """Bottom-up nearest-x2 upsample-and-add: levels[k] [Bt,C,L>>k] -> [Bt,C,L]."""
+    dev = _chk(*levels)
+    Bt, Cc, L = levels[0].shape
+    D = len(levels)
+    y = torch.empty_like(levels[0])
+    arr = (C.c_void_p * D)(*[t.data_ptr() for t in levels])
+    _lib.check(_lib.load().srf_causal_merge(arr, D, _lib.ptr(y), Bt, Cc, L, _lib.current_stream(dev)), "srf_causal_merge")
+    return y
+
+
+def causal_pyramid_supported(C_, L, D):
+    return bool(_lib.load().srf_causal_pyramid_supported(C_, L, D))
+
+
+def causal_pyramid(y1, in_prelu, weights, biases, prelus):
+    """Fused causal pyramid of one UConvBlock: y1 [Bt,C,L] (proj_1x1 conv output, its PReLU applied on load) -> merged."""
+    dev = _chk(y1, in_prelu, *weights, *biases, *prelus)
+    Bt, Cc, L = y1.shape
+    D = len(weights)
+    lib = _lib.load()
+    if not lib.srf_causal_pyramid_supported(Cc, L, D):
+        raise _lib.SrfError("srf_causal_pyramid: unsupported shape C=%d L=%d D=%d" % (Cc, L, D))
+    merged = torch.empty_like(y1)
+    arr = lambda ts: (C.c_void_p * D)(*[t.data_ptr() for t in ts])
+    rc = lib.srf_causal_pyramid(_lib.ptr(y1), _lib.ptr(merged), _lib.ptr(in_prelu), arr(weights), arr(biases), arr(prelus),
+                                Bt, Cc, L, D, _lib.current_stream(dev))
+    _lib.check(rc, "srf_causal_pyramid")
+    return merged
+
+
+def causal_scale(src, dscale=None, hscale=1.0):
+    """src * dscale[0] * hscale (dscale: a device scalar tensor or None) as a new tensor, without a host synchronisation."""
+    dev = _chk(src, dscale)
+    dst = torch.empty_like(src)
+    rc = _lib.load().srf_causal_scale(_lib.ptr(src), _lib.ptr(dst), src.numel(), _lib.ptr(dscale), float(hscale),
+                                      _lib.current_stream(dev))
+    _lib.check(rc, "srf_causal_scale")
+    return dst
+
+
+def prelu(x, slope):
+    """PReLU with one shared (device) slope."""
+    dev = _chk(x, slope)
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().srf_prelu_apply(_lib.ptr(x), _lib.ptr(slope), _lib.ptr(y), x.numel(), _lib.current_stream(dev)),
+               "srf_prelu_apply")
+    return y
+
+
 def set_debug_flags(flags):
     _lib.load().srf_set_debug_flags(int(flags))
 
@@ -457,6 +535,10 @@ def set_kernel_mode(mode):
     """0 = fast paths, split-bf16x3 MFMA GEMMs (default); 1 = generic kernels only; 2 = fast paths with
     exact-fp32 MFMA GEMMs."""
     _lib.load().srf_set_kernel_mode(int(mode))
+
+
+def get_kernel_mode():
+    return int(_lib.load().srf_get_kernel_mode())
 
 
 class kernel_trace:

@@ -32,6 +32,21 @@ def flops_per_example(variant, B, C, U, D, K, N, S, T, G=1):
     return 2.0 * mac
 
 
+
+def causal_bytes_per_example(A, B, C, U, D, K, N, S, T):
+    """CausalSuDORMRF (causal_improved_sudormrf_v3.py) forward, fp32, weights ignored, at the kernel boundaries of its HIP
+    forward: encoder output written and read once, per block proj_1x1 (x -> y1), the fused causal pyramid (y1 -> merged:
+    2 C L), res_conv (merged + residual -> x'), mask conv (x -> masks), decoder (masks -> S A T samples).  L = T' / h
+    (the causal encoder: kernel 2K - 1, padding K - 1), the same L as frames()."""
+    L = frames(T, K, D)
+    SA = S * A
+    return 4.0 * (A * T + 2 * N * L + B * L + U * (3 * B * L + 4 * C * L) + B * L + 2 * SA * N * L + SA * T)
+
+
+def causal_pyramid_bytes(Bt, C, L):
+    """Algorithmic bytes of one fused causal pyramid launch: y1 read once, merged written once (the halo is re-read)."""
+    return 4.0 * 2 * Bt * C * L
+
 def pyramid_fused(C, L, D):
     """Mirror of srf_pyramid_supported() (csrc/srf_pyramid.hip)."""
     if D < 1 or D > 8 or C > 2048:

@@ -1,0 +1,240 @@
+"""Causal SuDoRM-RF (v3) on the MI355X: reference parity of every fixture (tests/golden/CAUSAL_MANIFEST.json, made by
+tools/make_golden_causal.py from the reference), the dispatch at the bench shape, fused vs per-level vs a CPU restatement,
+bit-exact causality, batch independence, the stand-alone block and the training refusal."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import causal_fixtures as cf
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4
+
+
+@pytest.fixture(scope="module")
+def dev():
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    return torch.device("cuda:0")
+
+
+def _model(name, dev, cfg=None, seed=None):
+    from sudo_rm_rf_amd.dnn.models.causal_improved_sudormrf_v3 import CausalSuDORMRF
+    cfg = cfg or cf.CASES[name][0]
+    seed = cf.CASES[name][3] if seed is None else seed
+    torch.manual_seed(0)
+    m = CausalSuDORMRF(**cfg)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in cf.make_state_dict(cfg, seed).items()})
+    return m.to(dev).eval()
+
+
+def _run(m, wav):
+    with torch.no_grad():
+        out = m(wav)
+    torch.cuda.synchronize()
+    return out
+
+
+class _kernel_mode:
+    def __init__(self, mode):
+        self.mode = mode
+
+    def __enter__(self):
+        from sudo_rm_rf_amd import ops
+        ops.set_kernel_mode(self.mode)
+
+    def __exit__(self, *exc):
+        from sudo_rm_rf_amd import ops
+        ops.set_kernel_mode(0)
+        return False
+
+
+@pytest.mark.parametrize("name", list(cf.CASES))
+def test_reference_parity(dev, name):
+    m = _model(name, dev)
+    gold = cf.load_golden(name)
+    out = _run(m, torch.from_numpy(cf.make_input(name)).to(dev))
+    assert out.shape == gold["out"].shape
+    err = float(np.abs(out.cpu().numpy() - gold["out"]).max())
+    line = "%s: max|hip - reference| out %.3e" % (name, err)
+    plan = m._engine().last_plan
+    for what, key in ((0, "enc"), (1, "sep")):
+        if key in gold:
+            e = float(np.abs(plan.debug_fetch(what, gold[key].shape).cpu().numpy() - gold[key]).max())
+            line += " %s %.3e" % (key, e)
+            assert e <= TOL, (key, e)
+    print(line)
+    assert err <= TOL
+
+
+@pytest.mark.parametrize("name", ["causal_tiny", "causal_tiny_a2_k11", "causal_default"])
+def test_kernel_mode_1_agrees_with_mode_0(dev, name):
+    m = _model(name, dev)
+    wav = torch.from_numpy(cf.make_input(name)).to(dev)
+    out0 = _run(m, wav)
+    with _kernel_mode(1):
+        out1 = _run(m, wav)
+    gold = cf.load_golden(name)["out"]
+    assert float((out0 - out1).abs().max()) <= TOL
+    assert float(np.abs(out1.cpu().numpy() - gold).max()) <= TOL
+
+
+def test_bench_shape_dispatch_and_parity(dev, monkeypatch):
+    from sudo_rm_rf_amd import engine, ops
+    m = _model("causal_default", dev)
+    U = m.num_blocks
+    x4 = cf.make_input("causal_default")
+    gold = np.tile(cf.load_golden("causal_default")["out"], (8, 1, 1))
+    wav = torch.from_numpy(np.tile(x4, (8, 1, 1))).to(dev)
+    eng = m._engine()
+    eng.multi_stream = False
+    with torch.no_grad():
+        with ops.kernel_trace(dev) as tr:
+            out = m(wav)
+    torch.cuda.synchronize()
+    assert float(np.abs(out.cpu().numpy() - gold).max()) <= TOL
+    names = [n for n, _ in tr.launches]
+    cnt = {n: names.count(n) for n in set(names)}
+    # the causal kernels: one fused pyramid per block, no per-level launches, one encoder, one fold of all scales
+    assert cnt.get("causal_pyramid") == U and "causal_dwconv" not in cnt and "causal_merge" not in cnt
+    assert cnt.get("causal_encoder") == 1 and cnt.get("causal_scale") == 1 and cnt.get("pack_pw_weights") == 1
+    # the 1x1 convolutions on the families the Improved forward uses at these shapes (B = 128, C = 512, N = 512, L = 3200,
+    # batch 32): proj_1x1 (512 x 128, packed, no prologue) on the paired-block 256 x 128 kernel, mask conv (1024 x 128,
+    # packed, PReLU prologue) likewise, bottleneck / res_conv (Cout = 128: not packed) and the decoder's frame GEMM on the
+    # 128 x 128 split-bf16 kernel
+    assert cnt.get("pw_conv_x3p<0>") == U
+    assert cnt.get("pw_conv_x3p<3>") == 1
+    assert cnt.get("pw_conv_bf16x3_w8") == U + 2
+    assert set(cnt) <= {"causal_scale", "pack_pw_weights", "causal_encoder", "causal_pyramid", "pw_conv_x3p<0>",
+                        "pw_conv_x3p<3>", "pw_conv_bf16x3_w8", "transpose", "zero_fill", "overlap_add"}, cnt
+    # explicit two-stream splits and the auto-tuned path give the same rows
+    eng.multi_stream = True
+    for mode in ("half", "5:3", "auto"):
+        monkeypatch.setattr(engine, "_SPLIT_MODE", mode)
+        eng._split_choice.clear()
+        eng._seen.clear()
+        for _ in range(engine._TUNE_AFTER + 1):
+            out = _run(m, wav)
+            assert float(np.abs(out.cpu().numpy() - gold).max()) <= TOL, mode
+
+
+def _cpu_pyramid(y1, ap, ws, bs, acts):
+    """torch.nn.functional restatement of the reference's pyramid (masked taps dropped, left zero padding of 10)."""
+    lv, src = [], F.prelu(y1, ap)
+    for k in range(len(ws)):
+        x = F.pad(src, (10, 0))
+        src = F.prelu(F.conv1d(x, ws[k][..., :11], bs[k], stride=1 if k == 0 else 2, groups=y1.shape[1]), acts[k])
+        lv.append(src)
+    out = lv[-1]
+    for k in range(len(lv) - 2, -1, -1):
+        out = lv[k] + torch.repeat_interleave(out, 2, dim=-1)
+    return out
+
+
+@pytest.mark.parametrize("Bt,Cc,L,D", [(1, 40, 96, 1), (2, 72, 1000, 2), (1, 100, 1040, 5), (3, 64, 2048, 4),
+                                       (2, 33, 3200, 3), (1, 512, 1024, 4), (1, 16, 176, 5)])
+def test_fused_vs_per_level_vs_cpu(dev, Bt, Cc, L, D):
+    from sudo_rm_rf_amd import ops
+    g = torch.Generator().manual_seed(Bt * 1000 + Cc + L + D)
+    y1 = torch.randn(Bt, Cc, L, generator=g)
+    ws = [torch.randn(Cc, 1, 21, generator=g) * 0.3 for _ in range(D)]
+    bs = [torch.randn(Cc, generator=g) * 0.1 for _ in range(D)]
+    acts = [torch.rand(1, generator=g) * 0.4 for _ in range(D)]
+    ap = torch.rand(1, generator=g) * 0.4
+    want = _cpu_pyramid(y1.double(), ap.double(), [w.double() for w in ws], [b.double() for b in bs],
+                        [a.double() for a in acts])
+    d = lambda t: t.to(dev)
+    assert ops.causal_pyramid_supported(Cc, L, D)
+    fused = ops.causal_pyramid(d(y1), d(ap), [d(w) for w in ws], [d(b) for b in bs], [d(a) for a in acts])
+    lv, src = [], d(y1)
+    for k in range(D):
+        src = ops.causal_dwconv(src, d(ws[k]), d(bs[k]), 1 if k == 0 else 2, in_prelu=d(ap) if k == 0 else None,
+                                out_prelu=d(acts[k]))
+        lv.append(src)
+    per_level = ops.causal_merge(lv)
+    torch.cuda.synchronize()
+    assert torch.equal(fused, per_level)
+    assert float((fused.cpu().double() - want).abs().max()) <= 1e-5
+
+
+def test_causality_is_bit_exact(dev):
+    cfg = cf.TINY
+    m = _model("causal_tiny", dev)
+    h = cfg["enc_kernel_size"] // 2
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal((1, 1, 2400)).astype(np.float32)
+    m._engine().multi_stream = False     # (single stream: both forwards dispatch the same kernels)
+    for t0 in (1003, 1500):
+        y = x.copy()
+        y[..., t0:] += rng.standard_normal(y[..., t0:].shape).astype(np.float32)
+        a = _run(m, torch.from_numpy(x).to(dev)).cpu().numpy()
+        b = _run(m, torch.from_numpy(y).to(dev)).cpu().numpy()
+        t = np.arange(x.shape[-1])
+        safe = h * (t // h) + h < t0
+        assert np.array_equal(a[..., safe], b[..., safe]), t0
+        first = int(t[~safe][0])
+        assert not np.array_equal(a[..., first], b[..., first]), (t0, first)
+
+
+def test_batch_independence_and_two_stream_split(dev, monkeypatch):
+    from sudo_rm_rf_amd import engine
+    m = _model("causal_tiny", dev)
+    rng = np.random.default_rng(9)
+    x = torch.from_numpy(rng.standard_normal((8, 1, 1001)).astype(np.float32)).to(dev)
+    eng = m._engine()
+    eng.multi_stream = False
+    whole = _run(m, x)
+    for i in (0, 3, 7):
+        alone = _run(m, x[i:i + 1].contiguous())
+        assert float((alone - whole[i:i + 1]).abs().max()) <= 1e-6, i
+    eng.multi_stream = True
+    monkeypatch.setattr(engine, "_SPLIT_MODE", "half")
+    eng._split_choice.clear()
+    split = _run(m, x)
+    assert eng._split_choice[(x.device.index, 8, 1001)] == (4, 4)
+    assert float((split - whole).abs().max()) <= 1e-6
+
+
+def test_uconvblock_standalone_matches_cpu(dev):
+    from sudo_rm_rf_amd.dnn.models.causal_improved_sudormrf_v3 import UConvBlock
+    torch.manual_seed(3)
+    blk = UConvBlock(out_channels=32, in_channels=64, upsampling_depth=3, alpha=1.0, beta=1.0)
+    with torch.no_grad():
+        for p in blk.parameters():
+            p.uniform_(-0.4, 0.4)
+        blk.skipinit_gain.fill_(0.7)
+        for m in [blk.proj_1x1] + list(blk.spp_dw):
+            m.act.weight.fill_(0.2)
+    blk.alpha, blk.beta = 0.8, 1.25
+    x = torch.randn(2, 32, 512)
+    with torch.no_grad():
+        y1 = F.conv1d(x.double() / blk.beta, blk.proj_1x1.conv.weight.double(), blk.proj_1x1.conv.bias.double())
+        merged = _cpu_pyramid(y1, blk.proj_1x1.act.weight.double(), [m.conv.weight.double() for m in blk.spp_dw],
+                              [m.conv.bias.double() for m in blk.spp_dw], [m.act.weight.double() for m in blk.spp_dw])
+        want = F.conv1d(merged, blk.res_conv.weight.double(), blk.res_conv.bias.double()) * 0.7 * blk.alpha + x.double()
+        got = blk.to(dev)(x.to(dev))
+    torch.cuda.synchronize()
+    assert float((got.cpu().double() - want).abs().max()) <= TOL
+
+
+def test_training_is_refused(dev):
+    from sudo_rm_rf_amd import _lib
+    m = _model("causal_tiny", dev).train()
+    wav = torch.from_numpy(cf.make_input("causal_tiny")).to(dev)
+    with pytest.raises(NotImplementedError, match="forward-only"):
+        m(wav)
+    with pytest.raises(NotImplementedError):
+        m.sm[0](torch.zeros(1, 32, 64, device=dev))
+    plan = m._engine().plan_for(2, 1001, dev)
+    lib = _lib.load()
+    params = [p.detach() for p in m.state_dict().values()]
+    table = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
+    out = torch.empty(2, 2, 1001, device=dev)
+    buf = torch.empty(1 << 20, dtype=torch.uint8, device=dev)
+    rc = lib.srf_forward_train(plan.handle, table, len(params), _lib.ptr(wav), _lib.ptr(out), _lib.ptr(buf), buf.numel(),
+                               _lib.ptr(buf), buf.numel(), _lib.current_stream(dev))
+    with pytest.raises(_lib.SrfError, match="causal"):
+        _lib.check(rc, "srf_forward_train")
