@@ -22,6 +22,7 @@
  *   srf_pit_sisdr_*        <- PITLossWrapper(PairwiseNegSDR("sisdr")) fwd/bwd        losses/sisdr.py:254-311,426-458
  *   srf_perm_inv_sisdr     <- PermInvariantSISDR.forward (validation metric)        losses/sisdr.py:66-196
  *   srf_forward (causal)   <- CausalSuDORMRF.forward      models/causal_improved_sudormrf_v3.py (ABI 16)
+ *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17)
  *   srf_causal_encoder     <- its encoder (ScaledWSConv1d, 2K-1 taps of which K are live)
  *   srf_causal_dwconv / _merge / _pyramid <- UConvBlock's causal k = 21 depthwise pyramid + upsample/add
  *
@@ -47,7 +48,7 @@
 extern "C" {
 #endif
 
-#define SRF_ABI_VERSION 16
+#define SRF_ABI_VERSION 17
 
 /* GlobLN statistics layout: "sums" = fp64 [groups][SRF_STAT_BUCKETS][2] {sum, sum of squares}; the
  * statistic of a group is the total over its buckets (producers spread their atomics over buckets). */
@@ -325,6 +326,47 @@ int srf_causal_pyramid(const float* y1, float* merged, const float* in_prelu, co
  * srf_prelu_apply: y = PReLU_a(x), slope[0] on the device (a stand-alone nn.PReLU).  n elements, y may alias x. */
 int srf_causal_scale(const float* src, float* dst, long n, const float* dscale, float hscale, void* stream);
 int srf_prelu_apply(const float* x, const float* slope, float* y, long n, void* stream);
+
+/* ---- Streaming inference for the causal model (ABI 17) ----
+ * A session serves `batch` independent streams of one causal config.  A push takes the next n samples of every stream,
+ * n a positive multiple of the granule g = h * 2^(D-1) (h = K/2) and at most max_chunk_samples, and returns n separated
+ * samples delayed by h: a push that covers samples [pos, pos + n) returns those at [pos - h, pos + n - h).  After a reset the
+ * first h returned samples lie at negative time; the caller drops them.  Feeding zeros up to the reference's padded length T'
+ * and then srf_stream_flush reproduces srf_forward on the whole signal.  The same samples under ANY chunk schedule give the
+ * same bits: no kernel choice or accumulation order depends on n.
+ * Caller-owned device buffers, 256-byte aligned; the library allocates nothing and a push never synchronises:
+ *   weights_buf  srf_stream_weights_bytes    snapshot made by srf_stream_prepare (skipinit_gain * alpha folded into res_conv
+ *                                            on the device, 1/beta into proj_1x1, decoder weight transposed).  Call it again
+ *                                            only when the parameters changed.
+ *   state        srf_stream_state_bytes =    4 * (align64(batch*A*2h) + align64(U*D*batch*C*10) + align64(batch*S*A*(h+1)))
+ *                                            floats: encoder history | the last 10 inputs of every depthwise level | the
+ *                                            pending overlap-add tail.  srf_stream_reset zeroes it (row = -1: every stream).
+ *   workspace    srf_stream_workspace_bytes  activations of one push.
+ * wav: [batch, A, n]; out: [batch, S*A, n]; out_tail: [batch, S*A, h] (the pending samples; the state is left unchanged).
+ * srf_stream_num_launches: kernels per push (3 U + 5), all of the families stream_encoder / stream_pw / stream_pyramid /
+ * stream_ola.  Every refusal (non-causal config, n <= 0, n % g != 0, n > max_chunk_samples, small or misaligned buffers, row
+ * out of range) returns SRF_EINVAL before anything is launched.
+ * srf_causal_stream_pyramid: one block's pyramid for a chunk of Lc frames (Lc % 2^(D-1) == 0): y1 / merged [Bt,C,Lc], state:
+ * D pointers to [Bt,C,10] holding the last 10 inputs of each level (level 0: after proj_1x1's PReLU), read and then
+ * rolled.  Chunk after chunk it is bit-identical to srf_causal_pyramid on the whole sequence. */
+typedef struct srf_stream srf_stream;
+int srf_stream_create(const srf_config* cfg, int batch, int max_chunk_samples, srf_stream** out);
+void srf_stream_destroy(srf_stream* s);
+int srf_stream_granule(const srf_stream* s);
+int srf_stream_delay(const srf_stream* s);
+size_t srf_stream_state_bytes(const srf_stream* s);
+size_t srf_stream_weights_bytes(const srf_stream* s);
+size_t srf_stream_workspace_bytes(const srf_stream* s);
+int srf_stream_num_launches(const srf_stream* s);
+int srf_stream_set_block_scales(srf_stream* s, const float* alpha, const float* beta, int n);
+int srf_stream_prepare(const srf_stream* s, const float* const* params, int num_params, void* weights_buf, void* stream);
+int srf_stream_reset(const srf_stream* s, void* state, int row, void* stream);
+int srf_stream_push(const srf_stream* s, const void* weights_buf, void* state, const float* wav, int n, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int srf_stream_flush(const srf_stream* s, const void* state, float* out_tail, void* stream);
+int srf_causal_stream_pyramid(const float* y1, float* merged, float* const* state, const float* in_prelu,
+                              const float* const* w, const float* const* bias, const float* const* prelu, int Bt, int C, int Lc,
+                              int D, void* stream);
 
 /* Transposed conv synthesis + crop: out[b,o,t] = sum_{ci,l,k: h*l+k-h=t} v[b,ci,l]*w[ci,o,k], t<T.
  * v: [Bt,Ci,L], w: [Ci,Co,K] (ConvTranspose1d layout), out: [Bt,Co,T].

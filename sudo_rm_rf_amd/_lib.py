@@ -12,7 +12,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64 first so the extension bi
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # SRF_LIB: an alternative build of the same library (same-box A/B of kernel variants, tools/); default = the in-tree build
 LIB_PATH = os.environ.get("SRF_LIB") or os.path.join(_PKG, "libsudormrf_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 STAT_BUCKETS = 64
 
 SRF_OK = 0
@@ -138,6 +138,21 @@ _PROTOS = {
     "srf_causal_pyramid": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "srf_causal_scale": (_i, [_vp, _vp, _l, _vp, C.c_float, _vp]),
     "srf_prelu_apply": (_i, [_vp, _vp, _vp, _l, _vp]),
+    "srf_stream_create": (_i, [C.POINTER(srf_config), _i, _i, C.POINTER(_vp)]),
+    "srf_stream_destroy": (None, [_vp]),
+    "srf_stream_granule": (_i, [_vp]),
+    "srf_stream_delay": (_i, [_vp]),
+    "srf_stream_state_bytes": (_sz, [_vp]),
+    "srf_stream_weights_bytes": (_sz, [_vp]),
+    "srf_stream_workspace_bytes": (_sz, [_vp]),
+    "srf_stream_num_launches": (_i, [_vp]),
+    "srf_stream_set_block_scales": (_i, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), _i]),
+    "srf_stream_prepare": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),
+    "srf_stream_reset": (_i, [_vp, _vp, _i, _vp]),
+    "srf_stream_push": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "srf_stream_flush": (_i, [_vp, _vp, _vp, _vp]),
+    "srf_causal_stream_pyramid": (_i, [_vp, _vp, C.POINTER(_vp), _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i,
+                                       _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

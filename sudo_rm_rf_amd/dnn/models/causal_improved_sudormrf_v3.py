@@ -251,6 +251,14 @@ class CausalSuDORMRF(nn.Module):
                          [input_wav if isinstance(input_wav, torch.Tensor) else None] + list(self.parameters()))
         return self._engine().run(self, input_wav, self.in_audio_channels)
 
+    def stream(self, batch=1, max_chunk=None, device=None):
+        """A streaming session over `batch` independent streams (sudo_rm_rf_amd.streaming.CausalStream): push() samples as
+        they arrive, get separated samples back with a delay of enc_kernel_size // 2; finish() ends the streams so that the
+        concatenated outputs equal forward() on the whole signal.  max_chunk: the most samples one kernel pass takes (a
+        multiple of the granule, default 16 granules; longer pushes are cut).  Nothing is stored on the module."""
+        from ...streaming import CausalStream
+        return CausalStream(self, batch=batch, max_chunk=max_chunk, device=device)
+
     def pad_to_appropriate_length(self, x):
         """Kept for API parity; the HIP path folds the padding into its bounds checks."""
         input_length = x.shape[-1]

@@ -508,6 +508,22 @@ def causal_pyramid(y1, in_prelu, weights, biases, prelus):
     return merged
 
 
+def causal_stream_pyramid(y1, state, in_prelu, weights, biases, prelus):
+    """One chunk of the streaming pyramid: y1 [Bt,C,Lc] (Lc % 2^(D-1) == 0), state: D tensors [Bt,C,10] holding the last
+    10 inputs of each level (zeros at the start of a stream), UPDATED IN PLACE -> merged [Bt,C,Lc]."""
+    dev = _chk(y1, in_prelu, *state, *weights, *biases, *prelus)
+    Bt, Cc, Lc = y1.shape
+    D = len(weights)
+    if len(state) != D or any(tuple(s.shape) != (Bt, Cc, 10) for s in state):
+        raise _lib.SrfError("causal_stream_pyramid: state must be %d tensors of shape [%d, %d, 10]" % (D, Bt, Cc))
+    merged = torch.empty_like(y1)
+    arr = lambda ts: (C.c_void_p * D)(*[t.data_ptr() for t in ts])
+    rc = _lib.load().srf_causal_stream_pyramid(_lib.ptr(y1), _lib.ptr(merged), arr(state), _lib.ptr(in_prelu), arr(weights),
+                                               arr(biases), arr(prelus), Bt, Cc, Lc, D, _lib.current_stream(dev))
+    _lib.check(rc, "srf_causal_stream_pyramid")
+    return merged
+
+
 def causal_scale(src, dscale=None, hscale=1.0):
     """src * dscale[0] * hscale (dscale: a device scalar tensor or None) as a new tensor, without a host synchronisation."""
     dev = _chk(src, dscale)

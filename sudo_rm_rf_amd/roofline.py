@@ -43,6 +43,22 @@ def causal_bytes_per_example(A, B, C, U, D, K, N, S, T):
     return 4.0 * (A * T + 2 * N * L + B * L + U * (3 * B * L + 4 * C * L) + B * L + 2 * SA * N * L + SA * T)
 
 
+def causal_stream_push_bytes(Bt, A, B, C, U, D, K, N, S, n):
+    """One streaming push of n samples on Bt streams (csrc/srf_causal_stream.hip), fp32: every weight read ONCE (they do not
+    depend on Bt or n: 4 * ~3.1 M parameters at the reference defaults, resident in the Infinity Cache between pushes) +
+    the activations at the kernel boundaries of the push (the causal forward's terms on Lc = n / h frames, plus the decoder's
+    frame values written and read) + the state read and written (encoder history, 10 inputs per depthwise level, the
+    overlap-add tail).  At one stream x one granule the weights are 73 % of it (11 of 15 MB at the defaults) and the push is bound by launch count x launch latency
+    (3 U + 5 dependent launches), not by this figure."""
+    h = K // 2
+    Lc = n // h
+    SA = S * A
+    weights = N * A * K + B * N + B + U * (2 * C * B + C + B + D * (11 * C + C)) + SA * N * B + SA * N + SA * N * SA * K
+    acts = Bt * (A * n + 2 * N * Lc + B * Lc + U * (3 * B * Lc + 4 * C * Lc) + B * Lc + 2 * SA * N * Lc + 2 * SA * K * Lc + SA * n)
+    state = 2 * Bt * (A * 2 * h + U * D * C * 10 + SA * (h + 1))
+    return 4.0 * (weights + acts + state)
+
+
 def causal_pyramid_bytes(Bt, C, L):
     """Algorithmic bytes of one fused causal pyramid launch: y1 read once, merged written once (the halo is re-read)."""
     return 4.0 * 2 * Bt * C * L

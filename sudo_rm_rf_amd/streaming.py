@@ -1,0 +1,208 @@
+"""Stateful streaming inference for the causal SuDoRM-RF (v3): ``CausalSuDORMRF.stream()`` returns a ``CausalStream``.
+
+A session owns three device buffers (prepared weights, state, workspace) and a small remainder of samples that do not
+fill a granule yet.  ``push`` takes any number of new samples per stream and returns every separated sample that
+became final; ``finish`` pads to the reference's length rule and returns the rest, so that the concatenation is the full
+forward's output.  All arithmetic is the srf_stream_* entry points of libsudormrf_hip.so (include/sudormrf_hip.h); torch
+is used for memory, slicing and concatenation only, and nothing here synchronises with the host.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .engine import _config_struct, _weights
+
+
+class _Session:
+    """The srf_stream handle and its geometry (needs no GPU)."""
+
+    def __init__(self, cfg_tuple, batch, max_chunk=None):
+        lib = _lib.load()
+        cfg = _config_struct(*cfg_tuple[:10])
+        if max_chunk is None:
+            # 16 granules, from the config alone (the library checks the same arithmetic)
+            max_chunk = 16 * (cfg.enc_kernel_size // 2) * 2 ** max(cfg.upsampling_depth - 1, 0)
+        handle = C.c_void_p()
+        _lib.check(lib.srf_stream_create(C.byref(cfg), int(batch), int(max_chunk), C.byref(handle)), "srf_stream_create")
+        self.handle = handle
+        if len(cfg_tuple) > 10:
+            scales = cfg_tuple[10]
+            alpha = (C.c_float * len(scales))(*[a for a, _ in scales])
+            beta = (C.c_float * len(scales))(*[b for _, b in scales])
+            _lib.check(lib.srf_stream_set_block_scales(handle, alpha, beta, len(scales)), "srf_stream_set_block_scales")
+        self.batch, self.max_chunk = int(batch), int(max_chunk)
+        self.granule = lib.srf_stream_granule(handle)
+        self.delay = lib.srf_stream_delay(handle)
+        self.state_bytes = lib.srf_stream_state_bytes(handle)
+        self.weights_bytes = lib.srf_stream_weights_bytes(handle)
+        self.workspace_bytes = lib.srf_stream_workspace_bytes(handle)
+        self.num_launches = lib.srf_stream_num_launches(handle)
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                _lib.load().srf_stream_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def _buffer(nbytes, device):
+    t = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    if t.data_ptr() % 256:
+        raise _lib.SrfError("torch returned a buffer that is not 256-byte aligned")
+    return t
+
+
+class CausalStream:
+    """One streaming session over ``batch`` independent streams of a CausalSuDORMRF.
+
+    The weights are snapshot at construction (and by ``refresh_weights()``): later in-place changes of the module's
+    parameters do not reach a running session until it is refreshed."""
+
+    def __init__(self, module, batch=1, max_chunk=None, device=None):
+        from .dnn.models.causal_improved_sudormrf_v3 import _refuse_autograd
+        self._module = module
+        _refuse_autograd("CausalSuDORMRF.stream", list(module.parameters()))
+        weights = _weights(module)
+        device = torch.device(device) if device is not None else weights[0].device
+        if device.type != "cuda":
+            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: the module is on %s.  There is deliberately no CPU "
+                                "fallback (use the reference implementation for CPU inference)." % device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device
+        self._cfg_tuple = module._config_tuple()
+        self._s = _Session(self._cfg_tuple, batch, max_chunk)
+        self._A = module.in_audio_channels
+        self._SA = module.num_sources * module.in_audio_channels
+        # the reference pads a signal to a multiple of this many samples (n_least_samples_req)
+        self._pad_unit = module.n_least_samples_req
+        with torch.cuda.device(device):
+            self._weights = _buffer(self._s.weights_bytes, device)
+            self._state = _buffer(self._s.state_bytes, device)
+            self._workspace = _buffer(self._s.workspace_bytes, device)
+        self._rem = torch.empty((self._s.batch, self._A, 0), dtype=torch.float32, device=device)
+        self._pos = 0              # samples pushed through the kernels since the last reset
+        self._emitted = 0          # samples returned since the last reset
+        self._head_pending = True  # the next output still starts with `delay` negative-time samples
+        self.refresh_weights()
+        self.reset()
+
+    # -- geometry ----------------------------------------------------------------------------
+    granule = property(lambda self: self._s.granule, doc="samples per granule g = h * 2^(D-1): pushes are cut at multiples of it")
+    delay = property(lambda self: self._s.delay, doc="output delay h = enc_kernel_size // 2 samples")
+    state_bytes = property(lambda self: self._s.state_bytes, doc="device bytes of state carried between pushes")
+    batch = property(lambda self: self._s.batch)
+    max_chunk = property(lambda self: self._s.max_chunk)
+    num_launches = property(lambda self: self._s.num_launches, doc="kernel launches per srf_stream_push")
+
+    def _stream(self):
+        return _lib.current_stream(self.device)
+
+    # -- weights and state -------------------------------------------------------------------
+    def refresh_weights(self):
+        """Snapshot the module's parameters again (srf_stream_prepare): skipinit_gain is read on the device."""
+        if self._module._config_tuple() != self._cfg_tuple:
+            raise _lib.SrfError("CausalStream: the module's configuration or block scales changed; open a new stream")
+        params = [p.detach() for p in _weights(self._module)]
+        for p in params:
+            if p.device != self.device or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % self.device)
+        arr = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
+        with torch.cuda.device(self.device):
+            rc = _lib.load().srf_stream_prepare(self._s.handle, arr, len(params), _lib.ptr(self._weights), self._stream())
+        _lib.check(rc, "srf_stream_prepare")
+
+    def reset(self, rows=None):
+        """Start new streams.  rows=None: every stream, position and remainder included.  rows=[...]: only those streams'
+        state, on a granule boundary (no remainder pending); the batch position carries on, so the first `delay` samples
+        the next push returns for those rows lie before their new start and are the caller's to drop."""
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            if rows is None:
+                _lib.check(lib.srf_stream_reset(self._s.handle, _lib.ptr(self._state), -1, self._stream()), "srf_stream_reset")
+                self._rem = self._rem[..., :0]
+                self._pos = 0
+                self._emitted = 0
+                self._head_pending = True
+                return
+            if self._rem.shape[-1]:
+                raise _lib.SrfError("CausalStream.reset(rows): %d samples are pending below a granule; single streams restart "
+                                    "on a granule boundary" % self._rem.shape[-1])
+            for r in rows:
+                _lib.check(lib.srf_stream_reset(self._s.handle, _lib.ptr(self._state), int(r), self._stream()), "srf_stream_reset")
+
+    # -- data path ---------------------------------------------------------------------------
+    def _check_input(self, x):
+        from .dnn.models.causal_improved_sudormrf_v3 import _refuse_autograd
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("input must be a torch.Tensor")
+        _refuse_autograd("CausalStream.push", [x])
+        if x.device.type != "cuda":
+            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
+                                "fallback (use the reference implementation for CPU inference)." % x.device)
+        if x.dim() != 3 or x.shape[0] != self._s.batch or x.shape[1] != self._A:
+            raise RuntimeError("expected input of shape [%d, %d, n], got %s" % (self._s.batch, self._A, tuple(x.shape)))
+        if x.device != self.device:
+            raise _lib.SrfError("input is on %s, the stream on %s" % (x.device, self.device))
+        return x.detach().to(torch.float32)
+
+    def _push_whole(self, x):
+        """x: [batch, A, n], n a positive multiple of the granule -> the n delayed samples minus the negative-time head
+        after a reset; run in pieces of at most max_chunk."""
+        lib = _lib.load()
+        n = x.shape[-1]
+        pieces = []
+        for lo in range(0, n, self._s.max_chunk):
+            m = min(self._s.max_chunk, n - lo)
+            xi = x[..., lo:lo + m].contiguous()
+            oi = torch.empty((self._s.batch, self._SA, m), dtype=torch.float32, device=self.device)
+            rc = lib.srf_stream_push(self._s.handle, _lib.ptr(self._weights), _lib.ptr(self._state), _lib.ptr(xi), m,
+                                     _lib.ptr(oi), _lib.ptr(self._workspace), self._s.workspace_bytes, self._stream())
+            _lib.check(rc, "srf_stream_push")
+            pieces.append(oi)
+        self._pos += n
+        y = pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=-1)
+        if self._head_pending:
+            y = y[..., self._s.delay:]
+            self._head_pending = False
+        return y
+
+    def push(self, x):
+        """x: [batch, A, n] on the device, any n >= 0 -> [batch, S*A, m]: every sample that became final (m may be 0)."""
+        x = self._check_input(x)
+        with torch.cuda.device(self.device):
+            if self._rem.shape[-1]:
+                x = torch.cat([self._rem, x], dim=-1)
+            n = x.shape[-1] // self._s.granule * self._s.granule
+            self._rem = x[..., n:].clone()
+            if n == 0:
+                return torch.empty((self._s.batch, self._SA, 0), dtype=torch.float32, device=self.device)
+            y = self._push_whole(x[..., :n]).contiguous()
+            self._emitted += y.shape[-1]
+            return y
+
+    def finish(self):
+        """End of every stream: zero-pad to the reference's padded length T', return the samples still owed so that
+        cat(pushes + [finish()]) is the full forward's [batch, S*A, T]; the session is reset afterwards."""
+        with torch.cuda.device(self.device):
+            T = self._pos + self._rem.shape[-1]
+            if T == 0:
+                self.reset()
+                return torch.empty((self._s.batch, self._SA, 0), dtype=torch.float32, device=self.device)
+            u = self._pad_unit
+            Tp = u if T < u else -(-T // u) * u
+            outs = []
+            if Tp > self._pos:
+                pad = torch.zeros((self._s.batch, self._A, Tp - self._pos), dtype=torch.float32, device=self.device)
+                pad[..., :self._rem.shape[-1]] = self._rem
+                outs.append(self._push_whole(pad))
+            tail = torch.empty((self._s.batch, self._SA, self._s.delay), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().srf_stream_flush(self._s.handle, _lib.ptr(self._state), _lib.ptr(tail), self._stream()),
+                       "srf_stream_flush")
+            outs.append(tail)
+            y = torch.cat(outs, dim=-1)[..., :T - self._emitted].contiguous()
+            self.reset()
+            return y
