@@ -23,6 +23,9 @@
  *   srf_perm_inv_sisdr     <- PermInvariantSISDR.forward (validation metric)        losses/sisdr.py:66-196
  *   srf_forward (causal)   <- CausalSuDORMRF.forward      models/causal_improved_sudormrf_v3.py (ABI 16)
  *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17)
+ *   srf_zeroref_snr_*      <- PermInvariantSNRwithZeroRefs fwd/bwd (FUSS training loss)  losses/snr.py:13-142 (ABI 18)
+ *   srf_stab_sisdr         <- StabilizedPermInvSISDRMetric.forward (FUSS validation)    losses/sisdr.py:460-576
+ *   srf_fuss_augment       <- online_augment + mixture normalisation   experiments/run_fuss_separation.py:195-243
  *   srf_causal_encoder     <- its encoder (ScaledWSConv1d, 2K-1 taps of which K are live)
  *   srf_causal_dwconv / _merge / _pyramid <- UConvBlock's causal k = 21 depthwise pyramid + upsample/add
  *
@@ -48,7 +51,7 @@
 extern "C" {
 #endif
 
-#define SRF_ABI_VERSION 17
+#define SRF_ABI_VERSION 18
 
 /* GlobLN statistics layout: "sums" = fp64 [groups][SRF_STAT_BUCKETS][2] {sum, sum of squares}; the
  * statistic of a group is the total over its buckets (producers spread their atomics over buckets). */
@@ -438,6 +441,45 @@ int srf_pit_sisdr_backward(const float* est, const float* tgt, int Bt, int S, in
 size_t srf_perm_inv_sisdr_work_bytes(int Bt, int S);
 int srf_perm_inv_sisdr(const float* pr, const float* tgt, const float* mix, int Bt, int S, int T, int zero_mean,
                        double eps, void* work, float* best, int* best_perm, float* base, void* stream);
+
+/* ---- The FUSS recipe (ABI 18; experiments/run_fuss_separation.py) ----
+ * Training loss PermInvariantSNRwithZeroRefs (losses/snr.py:13-142): up to 4 sources of which any number may be silent.
+ * Per example, with M = |sum_j t_j|^2, P_j = |t_j|^2, active_j = [10 log10(P_j / (M + eps)) >= threshold_db],
+ * n_act = sum_j active_j and stab_j = thresh (active_j ? P_j : M):
+ *   term(i, j) = 10 active_j log10((P_j + eps) / (|e_i - t_j|^2 + stab_j + eps) + eps)
+ *   values[b]  = max over permutations (itertools order, first maximum) of n_act sum_j term(perm(j), j)
+ *   loss[0]    = -mean_b values[b];  best_perm[b] = index of the maximising permutation in itertools.permutations(range(S)).
+ * est, tgt, grad_est: [Bt,S,T] float32; zero_mean subtracts every row's time mean first.  S = 1..4 ONLY: S > 4 is refused
+ * with SRF_EINVAL and a message naming the limit before anything is launched (FUSS's maximum; the sums of one example live
+ * in registers).  Any T >= 1; rows are read with 16-byte loads when T % 4 == 0 and the bases are 16-byte aligned.
+ *   work: srf_zeroref_snr_work_bytes(Bt,S,T) bytes, 8-byte aligned, written by _forward and read by _backward.  Every block
+ *         of the streaming pass writes its partial sums there and the finalize launch adds them in block order: the same
+ *         inputs give the same bits on every run.  No allocation, no memset, no host synchronisation; 2 launches.
+ *   _backward (1 launch): grad_est is OVERWRITTEN completely; an estimate matched with an inactive target gets exact zeros.
+ *         upstream is a DEVICE pointer (NULL = 1): upstream_per_example == 0 -> one scalar, grad = upstream[0] d loss[0] / d est;
+ *         != 0 -> [Bt], grad of example b = upstream[b] d values[b] / d est. */
+size_t srf_zeroref_snr_work_bytes(int Bt, int S, int T);
+int srf_zeroref_snr_forward(const float* est, const float* tgt, int Bt, int S, int T, int zero_mean, float threshold_db,
+                            float thresh, float eps, void* work, float* values, int* best_perm, float* loss, void* stream);
+int srf_zeroref_snr_backward(const float* est, const float* tgt, int Bt, int S, int T, const void* work,
+                             const float* upstream, int upstream_per_example, float* grad_est, void* stream);
+/* Validation metric StabilizedPermInvSISDRMetric.forward (losses/sisdr.py:460-576), fewer targets than estimates allowed:
+ * pr [Bt,pr_rows,T], tgt [Bt,n_act,T], 1 <= n_act <= n_est <= 4; pr_rows == n_est, or n_est == 1 and the pr_rows <= 4 rows are
+ * summed into the one estimate (single_source).  rho^2(i,j) = <p_i,t_j>^2 / (|p_i|^2 |t_j|^2 + eps);
+ * value(i,j) = 10 log10((rho^2 + eps) / (1 - rho^2 + eps)); values[b] = max over itertools.permutations(range(n_est), r = n_act)
+ * (first maximum; best_perm[b] = its index) of the mean over the targets; improvement != 0 subtracts the batch-and-source mean
+ * of value(sum of the targets, t_j).  work: srf_stab_sisdr_work_bytes(Bt,T), 8-byte aligned.  2 launches, deterministic. */
+size_t srf_stab_sisdr_work_bytes(int Bt, int T);
+int srf_stab_sisdr(const float* pr, const float* tgt, int Bt, int pr_rows, int n_est, int n_act, int T, int zero_mean,
+                   int improvement, double eps, void* work, float* values, int* best_perm, void* stream);
+/* online_augment (run_fuss_separation.py:195-215) and the loop's mixture normalisation (:237-243):
+ *   out[b,k] = clean[src_b[src_s[k]][b], src_s[k]] * gain[b,k];  mix[b] = (m - mean(m)) / (std(m) + eps), m = sum_k out[b,k],
+ * std unbiased; stats[b] = {mean, std} of m.  clean, out: [B,S,T] (out must not alias clean), mix: [B,T]; src_b [S][B] and
+ * src_s [S] int32, gain [B][S] float32, all on the device; S <= 4; scratch: srf_fuss_augment_scratch_bytes(B,T), 8-byte
+ * aligned.  2 launches, deterministic. */
+size_t srf_fuss_augment_scratch_bytes(int B, int T);
+int srf_fuss_augment(const float* clean, const int* src_b, const int* src_s, const float* gain, int B, int S, int T, float eps,
+                     float* out, float* mix, float* stats, void* scratch, void* stream);
 
 /* ---- training step, backward kernels (one entry point per kernel for unit parity) ---- */
 

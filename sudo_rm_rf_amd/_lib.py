@@ -12,7 +12,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64 first so the extension bi
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # SRF_LIB: an alternative build of the same library (same-box A/B of kernel variants, tools/); default = the in-tree build
 LIB_PATH = os.environ.get("SRF_LIB") or os.path.join(_PKG, "libsudormrf_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 STAT_BUCKETS = 64
 
 SRF_OK = 0
@@ -76,6 +76,13 @@ _PROTOS = {
     "srf_pit_sdr_forward": (_i, [_vp, _vp, _i, _i, _i, C.c_float, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "srf_pit_sisdr_match": (_i, [_vp, _i, _i, _vp, _vp]),
     "srf_pit_sisdr_backward": (_i, [_vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "srf_zeroref_snr_work_bytes": (_sz, [_i, _i, _i]),
+    "srf_zeroref_snr_forward": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "srf_zeroref_snr_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "srf_stab_sisdr_work_bytes": (_sz, [_i, _i]),
+    "srf_stab_sisdr": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp]),
+    "srf_fuss_augment_scratch_bytes": (_sz, [_i, _i]),
+    "srf_fuss_augment": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "srf_pw_wgrad_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "srf_pw_wgrad_cols": (_i, [_vp, _vp, C.POINTER(srf_norm), _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "srf_pw_wgrad_ld": (_i, [_vp, _vp, C.POINTER(srf_norm), _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp]),

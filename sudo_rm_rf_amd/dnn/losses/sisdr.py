@@ -5,6 +5,7 @@
     PairwiseNegSDR                                                  losses/sisdr.py:390-458
     PITLossWrapper                                                  losses/sisdr.py:199-387
     PermInvariantSISDR (the runners' validation metric, SI-SDRi)    losses/sisdr.py:66-196; run_improved_sudormrf.py:82-85
+    StabilizedPermInvSISDRMetric (the FUSS runner's metric)         losses/sisdr.py:460-576; run_fuss_separation.py:123-131
 
 Same class names, constructor arguments and call signatures; the arithmetic runs in csrc/srf_loss.hip (one
 streaming pass for the forward, one for the gradient).  PairwiseNegSDR takes all of its configurations
@@ -206,6 +207,70 @@ class PermInvariantSISDR(nn.Module):
             best_sisdr = best_sisdr - base.mean()             # one batch-and-source mean, as sisdr.py:154
         if not self.return_individual_results:
             best_sisdr = best_sisdr.mean()
+        out = -best_sisdr if self.backward_loss else best_sisdr
+        if return_best_permutation:
+            return out, self.permutations_tensor[perm.long().cpu()]
+        return out
+
+
+class StabilizedPermInvSISDRMetric(nn.Module):
+    """The FUSS runner's validation metric (reference: losses/sisdr.py:460-576): stabilized SI-SDR of the best assignment of
+    ``n_actual_sources`` targets to ``n_estimated_sources`` >= n_actual_sources estimates, optionally as an improvement over the
+    sum of the targets.  Same constructor (asserts included) and ``forward`` arguments; one streaming pass + a finalize launch
+    (csrc/srf_loss_fuss.hip: srf_stab_sisdr), up to 4 estimated sources.  Evaluation only: it raises under autograd."""
+
+    def __init__(self, zero_mean=False, single_source=False, n_estimated_sources=None, n_actual_sources=None,
+                 backward_loss=True, improvement=False, return_individual_results=False):
+        super().__init__()
+        self.perform_zero_mean = zero_mean
+        self.backward_loss = backward_loss
+        self.improvement = improvement
+        self.n_estimated_sources = n_estimated_sources
+        self.n_actual_sources = n_actual_sources
+        assert self.n_estimated_sources >= self.n_actual_sources, (
+            'Estimates need to be at least: {} but got: {}'.format(self.n_actual_sources, self.n_estimated_sources))
+        self.permutations = list(itertools.permutations(torch.arange(self.n_estimated_sources), r=self.n_actual_sources))
+        self.permutations_tensor = torch.LongTensor(self.permutations)
+        self.return_individual_results = return_individual_results
+        self.single_source = single_source
+        if self.single_source:
+            assert self.n_actual_sources == 1
+
+    def forward(self, pr_batch, t_batch, eps=1e-9, return_best_permutation=False):
+        if torch.is_grad_enabled() and (pr_batch.requires_grad or t_batch.requires_grad):
+            raise NotImplementedError("StabilizedPermInvSISDRMetric is an evaluation metric on the HIP path (no backward): "
+                                      "call it under torch.no_grad(), train with PermInvariantSNRwithZeroRefs")
+        if pr_batch.dim() != 3 or t_batch.dim() != 3 or pr_batch.shape[0] != t_batch.shape[0] or \
+                pr_batch.shape[-1] != t_batch.shape[-1]:
+            raise RuntimeError("expected [batch, n_sources, time] estimates and targets of one length, got %s and %s" %
+                               (tuple(pr_batch.shape), tuple(t_batch.shape)))
+        assert t_batch.shape[-2] == self.n_actual_sources                                   # sisdr.py:521
+        rows = pr_batch.shape[1]
+        if self.single_source:
+            if self.n_estimated_sources != 1:      # the reference indexes the one summed estimate with permutations of n_est
+                raise IndexError("single_source needs n_estimated_sources == 1, got %d" % self.n_estimated_sources)
+        elif rows != self.n_estimated_sources:
+            raise RuntimeError("constructed for %s estimated sources, got %d" % (self.n_estimated_sources, rows))
+        if pr_batch.device.type != "cuda" or t_batch.device != pr_batch.device:
+            raise _lib.SrfError("sudo_rm_rf_amd losses run on an MI355X only (estimates on %s, targets on %s); "
+                                "there is deliberately no CPU fallback" % (pr_batch.device, t_batch.device))
+        if max(self.n_estimated_sources, rows) > 4:
+            raise NotImplementedError("the HIP stabilized metric supports up to 4 estimated sources, got %d" %
+                                      max(self.n_estimated_sources, rows))
+        dev = pr_batch.device
+        pr = pr_batch.detach().to(torch.float32).contiguous()
+        tg = t_batch.detach().to(torch.float32).contiguous()
+        Bt, _, T = pr.shape
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            work = torch.empty(lib.srf_stab_sisdr_work_bytes(Bt, T), dtype=torch.uint8, device=dev)
+            best = torch.empty(Bt, dtype=torch.float32, device=dev)
+            perm = torch.empty(Bt, dtype=torch.int32, device=dev)
+            rc = lib.srf_stab_sisdr(_lib.ptr(pr), _lib.ptr(tg), Bt, rows, self.n_estimated_sources, self.n_actual_sources, T,
+                                    1 if self.perform_zero_mean else 0, 1 if self.improvement else 0, C.c_double(float(eps)),
+                                    _lib.ptr(work), _lib.ptr(best), _lib.ptr(perm), _lib.current_stream(dev))
+        _lib.check(rc, "srf_stab_sisdr")
+        best_sisdr = best if self.return_individual_results else best.mean()
         out = -best_sisdr if self.backward_loss else best_sisdr
         if return_best_permutation:
             return out, self.permutations_tensor[perm.long().cpu()]
