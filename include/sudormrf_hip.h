@@ -192,6 +192,38 @@ int srf_debug_fetch(const srf_plan* plan, const void* workspace, int what, float
 
 /* ---- per-kernel entry points (unit parity + building blocks) -------------------------------- */
 
+/* Operand placement.  Every device pointer below must be aligned for its element type (float: 4 bytes, double: 8).
+ * Outputs and scratch need NO initialisation (every element an entry point documents as written is written; nothing is
+ * read before it is written); only what is documented as "+=" / ACCUMULATED must hold the caller's running value
+ * (zero for a fresh sum).  Nothing is read or written outside the extents given.  What a base that is element aligned
+ * but NOT 16-byte aligned does (a view such as x[..., a:b] of a [1, 1, T] signal, a parameter carved out of a flat
+ * buffer) is, per entry point -- the same table as tests/placement.py PLACEMENT, which the GPU suite runs:
+ *   any address   every float operand of srf_encoder, srf_gln_stats, srf_gln_apply(_add), srf_conv1d,
+ *                 srf_mixture_consistency(_magsq), srf_mask_apply, srf_mask_bwd, srf_frames_gather, srf_wav_normalize,
+ *                 srf_wav_stats, srf_wav_denormalize, srf_causal_encoder, srf_causal_dwconv, srf_causal_merge,
+ *                 srf_causal_stream_pyramid, srf_causal_scale, srf_prelu_apply, srf_clip_adam_step's tensors, the PIT /
+ *                 permutation-invariant SI-SDR inputs; every bias / gamma / beta / PReLU slope / depthwise or TAC weight
+ *                 of every entry point; every out_sums (accumulated one double at a time).
+ *   falls back    the result is the same to rounding, a slower kernel serves the call:
+ *                 srf_pw_conv / _packed / _packed3: x, w, y, residual, mul -> the scalar kernel (pw_conv_generic); w_packed /
+ *                   w_packed3 -> the kernels that split the fp32 weight themselves;
+ *                 srf_dwconv5: x, y -> dwconv5_generic;  srf_merge: levels, y -> merge_generic;
+ *                 srf_decoder: v -> the scalar frame GEMM (out: any address);
+ *                 srf_tac: x, q -> the VALU kernels;  srf_causal_pyramid: y1 -> scalar loads;
+ *                 srf_pw_wgrad*: dw, scratch -> the scalar fold of the partial sums;
+ *                 srf_gln_bwd: gout, gout2, x, gx;  srf_merge_bwd: g_merged, g_levels (the chain of pair sums);
+ *                 srf_dwconv5_bwd: gd, xin, gin;  srf_prelu_bwd: gout, x, gx;
+ *                 the zero-reference SNR / stabilized SI-SDR / FUSS augmentation rows (16-byte loads only when T % 4 == 0 and
+ *                 the bases are on the grid).
+ *   refused       SRF_EINVAL before anything is launched, srf_last_error() names the operand ("operand 'x' is not 16-byte
+ *                 aligned"): every GlobLN statistics INPUT (srf_norm.sums: read as pairs of doubles);
+ *                 srf_pack_pw_weights / srf_pack3_pw_weights: packed;  srf_pw_conv_pair / _pair_packed3: x, y, y2,
+ *                 residual, both packed images;  srf_pyramid: y1, merged, scratch;  srf_decoder: scratch;
+ *                 srf_pw_wgrad*: g, x;  srf_gln_bwd: scratch;  srf_tac_bwd: x, go, gx, scratch.
+ *   256 bytes     the whole-model buffers (workspace, saved, train scratch) and the stream session's weights_buf / state /
+ *                 workspace, as stated with those entry points; wav and out of srf_forward / srf_separate / srf_forward_train /
+ *                 srf_stream_push: any address. */
+
 /* out[b,n,l] = sum_{a,k} w[n,a,k] * xpad[b,a,h*l+k-h], h=K/2; samples outside [0,T) are zero, so the
  * reference's right zero-padding is implicit in L.  sums (nullable): [Bt][SRF_STAT_BUCKETS][2] += {sum, sumsq}. */
 int srf_encoder(const float* wav, const float* w, float* out, double* sums,

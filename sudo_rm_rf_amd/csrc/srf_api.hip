@@ -224,6 +224,7 @@ static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, 
   SRF_CHECK_ARG(K >= 3 && (K & 1), "srf_decoder: kernel size must be odd (got %d)", K);
   SRF_CHECK_ARG(T <= (K / 2) * L, "srf_decoder: T=%d exceeds hop*L=%d", T, (K / 2) * L);
   SRF_CHECK_ARG(Co <= 65535 && Bt <= 65535, "srf_decoder: too many channels / batch");
+  SRF_CHECK_ALIGNED16("srf_decoder", {"scratch", scratch});      // (zero-filled with 16-byte stores; checked before the first launch)
   hipStream_t st = (hipStream_t)stream;
   const int M = Co * K;
   float* wt = scratch;

@@ -469,6 +469,7 @@ int srf_gln_bwd_impl(const float* gout, const float* gout2, const float* x, cons
 extern "C" int srf_gln_bwd(const float* gout, const float* gout2, const float* x, const srf_norm* norm, int groups, int C,
                            int L, float* gx, int accumulate_gx, float* dgamma, float* dbeta, float* dslope,
                            void* scratch, void* stream) {
+  SRF_CHECK_ALIGNED16("srf_gln_bwd", {"scratch", scratch}, {"norm.sums", norm ? norm->sums : nullptr});      // (starts with fp64 bucket sums that are accumulated atomically)
   return srf_gln_bwd_impl(gout, gout2, x, norm, groups, C, L, gx, accumulate_gx, dgamma, dbeta, dslope, scratch, 0, stream,
                           nullptr);
 }
@@ -537,7 +538,7 @@ extern "C" int srf_merge_bwd(const float* g_merged, float* const* g_levels, int 
   if (D == 1) return SRF_OK;
   bool aligned = srf_aligned16(g_merged);
   for (int k = 1; k < D; ++k) aligned = aligned && srf_aligned16(g_levels[k]);
-  if (aligned && D >= 3 && srf_kernel_mode() != 1) {
+  if (aligned && D >= 3 && D <= 6 && srf_kernel_mode() != 1) {      // (the one-pass kernel exists for depths 3..6; deeper: the chain)
     MergeBwdArgs a;
     a.g = g_merged;
     for (int k = 0; k < SRF_MAX_DEPTH; ++k) a.lv[k] = (k >= 1 && k < D) ? g_levels[k] : nullptr;
@@ -1256,6 +1257,7 @@ int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_n
 extern "C" int srf_dwconv5_bwd(const float* gd, const float* xin, const srf_norm* in_norm, const float* w, int groups,
                                int C, int Lin, int stride, float* gin, float* dw, float* dbias, void* scratch,
                                void* stream) {
+  SRF_CHECK_ALIGNED16("srf_dwconv5_bwd", {"in_norm.sums", in_norm ? in_norm->sums : nullptr});     // (read as pairs of doubles)
   return srf_dwconv5_bwd_impl(gd, xin, in_norm, w, groups, C, Lin, stride, gin, dw, dbias, scratch, nullptr, nullptr,
                               nullptr, nullptr, nullptr, nullptr, stream, nullptr);
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <initializer_list>
 #define SRF_DIAGNOSTICS 1   // the library itself sees (and defines) the diagnostics switches
 #include "../../include/sudormrf_hip.h"
 
@@ -59,6 +60,25 @@ long srf_device_cached(int slot, long (*compute)(void*), void* arg);
   } while (0)
 
 static inline bool srf_aligned16(const void* p) { return (((size_t)p) & 15) == 0; }
+
+// Refusal of a misplaced operand, BEFORE anything is launched, naming it: every (name, pointer) pair whose pointer is not
+// NULL must be 16-byte aligned.  SRF_CHECK_ALIGNED16("srf_x", {"g", g}, {"x", x});
+struct SrfNamedPtr {
+  const char* name;
+  const void* p;
+};
+static inline const char* srf_first_unaligned16(std::initializer_list<SrfNamedPtr> ops) {
+  for (const SrfNamedPtr& o : ops)
+    if (o.p && !srf_aligned16(o.p)) return o.name;
+  return nullptr;
+}
+#define SRF_CHECK_ALIGNED16(fn, ...)                                                                        \
+  do {                                                                                                      \
+    if (const char* u__ = srf_first_unaligned16({__VA_ARGS__})) {                                           \
+      srf_set_error("%s: operand '%s' is not 16-byte aligned (this entry point has no unaligned form)", fn, u__); \
+      return SRF_EINVAL;                                                                                    \
+    }                                                                                                       \
+  } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // device side

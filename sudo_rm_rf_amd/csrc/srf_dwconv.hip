@@ -198,6 +198,7 @@ extern "C" int srf_dwconv5(const float* x, const float* w, const float* bias, fl
                            void* stream) {
   SRF_CHECK_ARG(x && w && bias && y, "srf_dwconv5: null pointer");
   SRF_CHECK_ARG(Bt > 0 && C > 0 && Lin > 0, "srf_dwconv5: bad sizes");
+  SRF_CHECK_ALIGNED16("srf_dwconv5", {"in_norm.sums", in_norm ? in_norm->sums : nullptr});     // (read as pairs of doubles)
   SRF_CHECK_ARG(stride == 1 || stride == 2, "srf_dwconv5: stride must be 1 or 2 (got %d)", stride);
   const int Lout = (Lin - 1) / stride + 1;
   const long rows = (long)Bt * C;
@@ -354,6 +355,7 @@ extern "C" int srf_merge(const float* const* levels, const srf_norm* norms, int 
     a.inv_count[k] = 1.0;
     if (k < D) {
       SRF_CHECK_ARG(levels[k] != nullptr, "srf_merge: null level %d", k);
+      SRF_CHECK_ALIGNED16("srf_merge", {"norms.sums", norms[k].sums});
       a.lv[k] = levels[k];
       a.nrm[k] = srf_norm_dev(&norms[k]);
       a.inv_count[k] = 1.0 / ((double)C * (double)(L >> k));

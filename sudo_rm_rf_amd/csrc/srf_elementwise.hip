@@ -75,6 +75,7 @@ __global__ __launch_bounds__(256) void srf_gln_apply_kernel(const float* __restr
 static int gln_apply_launch(const float* xres, const float* q, float* y, const srf_norm* norm, int groups,
                             int channels, int length, void* stream, bool add) {
   SRF_CHECK_ARG(q && y && norm && groups > 0 && channels > 0 && length > 0, "srf_gln_apply: bad arguments");
+  SRF_CHECK_ALIGNED16("srf_gln_apply", {"norm.sums", norm->sums});     // (read as pairs of doubles)
   const int chunks = (length + 1023) / 1024;
   const long blocks = (long)groups * channels * chunks;
   SRF_CHECK_ARG(blocks < (1L << 31), "srf_gln_apply: tensor too large");

@@ -265,9 +265,8 @@ extern "C" int srf_pw_conv_pair(const float* x, const void* w1_packed, const flo
   SRF_CHECK_ARG(!in_norm || (in_norm->sums && in_norm->gamma && in_norm->beta), "srf_pw_conv_pair: a prologue needs statistics, gamma and beta");
   SRF_CHECK_ARG(srf_pw_conv_pair_supported(Bt, Cin1, Cmid, Cout2, L), "srf_pw_conv_pair: unsupported shape / mode (Bt=%d %d->%d->%d L=%d)",
                 Bt, Cin1, Cmid, Cout2, L);
-  SRF_CHECK_ARG(srf_aligned16(x) && srf_aligned16(y) && srf_aligned16(y2) && srf_aligned16(w1_packed) && srf_aligned16(w2_packed) &&
-                    (!residual || srf_aligned16(residual)),
-                "srf_pw_conv_pair: unaligned operand");
+  SRF_CHECK_ALIGNED16("srf_pw_conv_pair", {"in_norm.sums", in_norm ? in_norm->sums : nullptr}, {"x", x}, {"y", y}, {"y2", y2}, {"w1_packed", w1_packed}, {"w2_packed", w2_packed},
+                      {"residual", residual});
   PwPairArgs a;
   a.x = x;
   a.residual = residual;
@@ -406,9 +405,11 @@ extern "C" size_t srf_packed3_pw_weight_bytes(int Cout, int Cin) {
 extern "C" int srf_pack3_pw_weights(const float* const* w, void* const* packed, const int* Cout, const int* Cin, int n,
                                     void* stream) {
   SRF_CHECK_ARG(w && packed && Cout && Cin && n > 0, "srf_pack3_pw_weights: bad arguments");
-  for (int i = 0; i < n; ++i)
-    SRF_CHECK_ARG(w[i] && packed[i] && srf_packed3_pw_weight_bytes(Cout[i], Cin[i]) > 0 && srf_aligned16(packed[i]),
+  for (int i = 0; i < n; ++i) {
+    SRF_CHECK_ARG(w[i] && packed[i] && srf_packed3_pw_weight_bytes(Cout[i], Cin[i]) > 0,
                   "srf_pack3_pw_weights: entry %d unsupported (Cout=%d Cin=%d)", i, Cout[i], Cin[i]);
+    SRF_CHECK_ALIGNED16("srf_pack3_pw_weights", {"packed", packed[i]});
+  }
   const bool f16 = srf_train_f16_split();
   {
     std::lock_guard<std::mutex> lk(g_pk3_mu);
@@ -442,6 +443,7 @@ extern "C" int srf_pw_conv_packed3(const float* x, const float* w, const void* w
                                              (long)Bt * ((Cout + 255) / 256) * ((L + 127) / 128) >= srf_device_cus()));
   if (!ok) return srf_pw_conv(x, w, bias, y, Bt, Cin, Cout, L, in_norm, residual, out_sums, 0, nullptr, 0, stream);
   if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_pw_conv: norm without gamma/beta");
+  SRF_CHECK_ALIGNED16("srf_pw_conv", {"in_norm.sums", nd.sums});
   PwArgs a;
   a.x = x;
   a.w = w;
@@ -492,11 +494,10 @@ extern "C" int srf_pw_conv_pair_packed3(const float* x, const void* w1_packed3, 
   SRF_CHECK_ARG(in_norm->sums && in_norm->gamma && in_norm->beta, "srf_pw_conv_pair_packed3: conv 1 needs a GlobLN prologue");
   SRF_CHECK_ARG(srf_pw_conv_pair_packed3_supported(Bt, Cin1, Cmid, Cout2, L),
                 "srf_pw_conv_pair_packed3: unsupported shape / mode (Bt=%d %d->%d->%d L=%d)", Bt, Cin1, Cmid, Cout2, L);
+  SRF_CHECK_ALIGNED16("srf_pw_conv_pair_packed3", {"in_norm.sums", in_norm->sums}, {"x", x}, {"y", y}, {"y2", y2}, {"w1_packed3", w1_packed3},
+                      {"w2_packed3", w2_packed3}, {"residual", residual});
   SRF_CHECK_ARG(srf_pk3_is_f16(w1_packed3) && srf_pk3_is_f16(w2_packed3),
                 "srf_pw_conv_pair_packed3: both weight images must have been packed as two fp16 parts by srf_pack3_pw_weights");
-  SRF_CHECK_ARG(srf_aligned16(x) && srf_aligned16(y) && srf_aligned16(y2) && srf_aligned16(w1_packed3) && srf_aligned16(w2_packed3) &&
-                    (!residual || srf_aligned16(residual)),
-                "srf_pw_conv_pair_packed3: unaligned operand");
   PwPairArgs a;
   a.x = x;
   a.residual = residual;
@@ -591,10 +592,11 @@ int srf_pack_pw_weights_transposed(const float* const* w, void* const* packed, c
 extern "C" int srf_pack_pw_weights(const float* const* w, void* const* packed, const int* Cout, const int* Cin,
                                    int n, void* stream) {
   SRF_CHECK_ARG(w && packed && Cout && Cin && n > 0, "srf_pack_pw_weights: bad arguments");
-  for (int i = 0; i < n; ++i)
-    SRF_CHECK_ARG(w[i] && packed[i] && srf_packed_pw_weight_bytes(Cout[i], Cin[i]) > 0 &&
-                      srf_aligned16(packed[i]),
+  for (int i = 0; i < n; ++i) {
+    SRF_CHECK_ARG(w[i] && packed[i] && srf_packed_pw_weight_bytes(Cout[i], Cin[i]) > 0,
                   "srf_pack_pw_weights: entry %d unsupported (Cout=%d Cin=%d)", i, Cout[i], Cin[i]);
+    SRF_CHECK_ALIGNED16("srf_pack_pw_weights", {"packed", packed[i]});
+  }
   return srf_pack_both(w, packed, Cout, Cin, n, (hipStream_t)stream);
 }
 
@@ -630,11 +632,15 @@ extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_
   a.mul_channels = mul_channels > 0 ? mul_channels : 1;
   a.epi_mask = epilogue_mask ? 1 : 0;
   if (a.nrm.sums) SRF_CHECK_ARG(a.nrm.gamma && a.nrm.beta, "srf_pw_conv: norm without gamma/beta");
+  SRF_CHECK_ALIGNED16("srf_pw_conv", {"in_norm.sums", a.nrm.sums});     // (every kernel reads the statistics as pairs of doubles)
   hipStream_t st = (hipStream_t)stream;
 
   const int mode = srf_kernel_mode();
+  // every MFMA kernel's epilogue moves y / residual / mul as 16-byte rows (srf_pw.h): a float-aligned base of any of them
+  // takes the generic kernel, like one of x or w
+  const bool io16 = srf_aligned16(y) && (!residual || srf_aligned16(residual)) && (!(a.epi_mask & 1) || srf_aligned16(mul));
   const bool mfma_ok = mode != 1 && (Cin % PW_BK == 0) && (L % 4 == 0) && Cout >= 32 && Cin >= 32 &&
-                       srf_aligned16(x) && srf_aligned16(w);
+                       srf_aligned16(x) && srf_aligned16(w) && io16;
   const int pro_sel = a.nrm.sums ? (a.nrm.prelu ? 2 : 1) : (a.nrm.prelu ? 3 : 0);
   // GroupComm's per-group convs (<= 32 -> <= 64 channels): register-resident streaming kernel
   if (mode != 1 && !(a.epi_mask & 1) && srf_pw_small_supported(Cin, Cout, L) && srf_aligned16(x) &&
@@ -642,7 +648,7 @@ extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_
     return srf_pw_small_launch(a, st);
   // 256 x 128 tiles with pre-split weights: whenever the packed image is there and the launch fills the chip (fewer tiles
   // than CUs: the 128 x 128 kernels below make twice as many).  (That kernel never reads the fp32 weights.)
-  if (srf_pw_256_serves(w_packed, x, Bt, Cin, Cout, L, pro_sel))
+  if (io16 && srf_pw_256_serves(w_packed, x, Bt, Cin, Cout, L, pro_sel))
     return srf_pw_256_launch(a, reinterpret_cast<const char*>(w_packed), pro_sel, st);
   // An activation tensor beyond the 2 GB reach of the kernel's 32-bit buffer offsets (cfg 5's bottleneck: 16 x 4096 x 12800
   // floats = 3.4 GB) goes out as several launches over runs of whole examples: examples are independent, every per-example

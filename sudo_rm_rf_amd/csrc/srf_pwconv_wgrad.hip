@@ -994,7 +994,7 @@ extern "C" int srf_pw_wgrad_ld(const float* g, const float* x, const srf_norm* i
   SRF_CHECK_ARG(g && x && dw && scratch, "srf_pw_wgrad: null pointer");
   SRF_CHECK_ARG(Bt > 0 && Cin > 0 && Cout > 0 && L > 0 && (L % 4) == 0, "srf_pw_wgrad: bad sizes (L %% 4 == 0 required)");
   SRF_CHECK_ARG(dw_cols > 0 && dw_cols <= Cin && dw_ld >= dw_cols, "srf_pw_wgrad: dw_cols / dw_ld out of range");
-  SRF_CHECK_ARG(srf_aligned16(g) && srf_aligned16(x), "srf_pw_wgrad: operands must be 16-byte aligned");
+  SRF_CHECK_ALIGNED16("srf_pw_wgrad", {"g", g}, {"x", x}, {"in_norm.sums", in_norm ? in_norm->sums : nullptr});
   WgArgs a;
   a.g = g;
   a.x = x;

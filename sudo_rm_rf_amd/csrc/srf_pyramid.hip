@@ -835,8 +835,7 @@ int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, co
   SRF_CHECK_ARG(y1 && merged && w && bias && gamma && beta && scratch, "srf_pyramid: null pointer");
   SRF_CHECK_ARG(groups > 0 && C > 0 && L > 0, "srf_pyramid: bad sizes");
   SRF_CHECK_ARG(srf_pyramid_supported(C, L, D), "srf_pyramid: unsupported shape C=%d L=%d D=%d", C, L, D);
-  SRF_CHECK_ARG(srf_aligned16(y1) && srf_aligned16(merged) && srf_aligned16(scratch),
-                "srf_pyramid: buffers must be 16-byte aligned");
+  SRF_CHECK_ALIGNED16("srf_pyramid", {"in_norm.sums", in_norm ? in_norm->sums : nullptr}, {"y1", y1}, {"merged", merged}, {"scratch", scratch});
   hipStream_t st = (hipStream_t)stream;
   const long rows = (long)groups * C;
   SRF_CHECK_ARG(rows < (1L << 31), "srf_pyramid: too many rows");

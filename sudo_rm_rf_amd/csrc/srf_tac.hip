@@ -617,8 +617,9 @@ extern "C" int srf_tac(const float* x, float* q, const float* const* params, int
   dim3 grid((L + 127) / 128, Bt), block(128);
   hipStream_t st = (hipStream_t)stream;
   // debug flags 1 << 22 / 24 / 25 / 26, 1024: the VALU kernels (the MFMA form serves n = 16, G = 16; 1 << 22 = just not the MFMA form)
+  // (the MFMA form moves x and q with 16-byte buffer accesses: float-aligned bases take the VALU kernels)
   if (srf_kernel_mode() != 1 && n == 16 && G == 16 && !(srf_debug_flags() & ((1 << 22) | (1 << 24) | (1 << 26) | 1024)) &&
-      (long)G * n * L * 4 < (1L << 31)) {
+      (long)G * n * L * 4 < (1L << 31) && srf_aligned16(x) && srf_aligned16(q)) {
     const int tiles_per_row = (L + 31) / 32;
     const long total = (long)Bt * tiles_per_row;
     if (total < (1L << 30)) {
@@ -1355,6 +1356,9 @@ extern "C" int srf_tac_bwd(const float* x, const float* go, const float* const* 
   SRF_CHECK_ARG(Bt > 0 && G > 0 && n > 0 && L > 0 && Bt <= 65535 && (L % 4) == 0, "srf_tac_bwd: bad sizes (L %% 4 == 0)");
   SRF_CHECK_ARG(H == 3 * n, "srf_tac_bwd: hidden size must be 3*n");
   for (int i = 0; i < 9; ++i) SRF_CHECK_ARG(params[i] && grads[i], "srf_tac_bwd: null parameter / gradient %d", i);
+  // x and the scratch slices feed srf_pw_wgrad (which has no unaligned form) after the first launch; go / gx move as 16-byte
+  // rows in the MFMA kernel: refuse here, before anything runs
+  SRF_CHECK_ALIGNED16("srf_tac_bwd", {"x", x}, {"go", go}, {"gx", gx}, {"scratch", scratch});
   hipStream_t st = (hipStream_t)stream;
   const size_t BG = (size_t)Bt * G;
   float* f = reinterpret_cast<float*>(scratch);
