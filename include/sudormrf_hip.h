@@ -118,38 +118,80 @@ int srf_profile_timeline(int i, const char** name, float* t_ms, int* stream_inde
  * NOT part of the drop-in surface: process-wide switches between kernel variants for A/B measurements and bisection
  * (tools/, bench.py --debug-flags, a handful of tests).  They act on every thread's subsequent launches; a caller that does
  * not define SRF_DIAGNOSTICS before including this header does not see them.  Default 0 = the shipped paths.
- *   1        srf_forward WITHOUT the fused conv pairs (round 5: res_conv / bottleneck + the next proj_1x1 in one launch)
- *   2        256 x 128 GEMMs: no m-tile groups (round 2's tile order); paired-block form: plain cache policy
- *   4        without the 256 x 128 GEMM (128 x 128 kernels)
- *   8        WITHOUT pre-packed weights (srf_forward packs by default)
- *   16       per-level depthwise + merge kernels instead of the fused pyramid (inference and training)
- *   32 / 64  LDS pyramid kernels instead of the register ones      128       non-persistent pyramid pass 1
- *   256      leftover GEMM tiles as whole tiles (no quarter tiles) 512       quarter tiles last
- *   1024     TAC forward with one time step per lane               2048      one-tile-per-block 128 x 128 GEMM everywhere
- *                                                                            (also: no 64 x 64 tiles for small launches)
- *   4096     weight-gradient GEMM: round 3's block -> (tile, partial) mapping (every XCD re-reads its rows through its own L2)
- *   8192     swap the two forms of the 256 x 128 GEMM: srf_forward / srf_separate run the one-block-per-CU kernel (srf_pwconv_x3w.hip),
- *            every other caller the paired-block kernel (srf_pwconv_x3p.hip) -- default: the paired form inside the forward only
- *   16384    training forward: three bf16 parts per operand (6 MFMAs, round 3) instead of two fp16 parts (3 MFMAs, round 4)
- *   32768    WITHOUT the fused tail: mask GEMM -> masked tensor -> decoder frame GEMM -> overlap-add as separate launches
- *   1<<17    pyramid pass 1 on a grid of co-resident wavefronts, several rows each (rounds 2-5) -- default since round 6: one row per wavefront
- *   1<<16    srf_backward WITHOUT the fused head of the blocks' pyramid backward (round 6: level 0 + proj_1x1's norm as two passes
- *            over {G_0, y1}): the level-0 conv kernel + the norm's apply pass of rounds 3-5 (set it around BOTH calls: a forward
- *            run without it leaves d_0 out of `saved`, and its backward then takes the head whatever the flag says)
- *   1<<18    weight-gradient GEMM WITHOUT the wide tile (round 6: 256 x 128 / 128 x 256, one block per CU): the 128 x 128 kernel;
- *            small-channel form on a fixed 1024 blocks (rounds 3-5) instead of one resident round
- *   1<<19    weight-gradient GEMM, 128 x 128 kernel: the masked form for full shapes too (rounds 3-5)
- *   1<<20    weight-gradient GEMM, wide tile: 800-column time chunks (several per block) instead of one long chunk per block
- *   1<<21    fused conv pair on persistent blocks (2 per CU, several tiles each) whatever the launch size -- default: one tile per block
- *   1<<23    fused conv pair with every counted wait of its DMA pipeline as a full drain (bisection aid, same results)
- *   1<<22    TAC forward / backward on the VALU kernels instead of the MFMA forms (n = 16, G = 16)
- *   1<<24    TAC forward on the generic kernel (no lane-per-time-step form)      1<<26   its lane form with four tiles per block
- *   1<<25    weight-gradient partials folded by one chain per output (rounds 3-4) instead of four groups per output (round 5)
- *   1<<27    64-bit pointer loads in the 128 x 128 GEMM (no buffer loads)
- *   1<<28    training forward on the split-bf16 GEMMs (faster; gradients then differ from the reference by ~3e-3)
- *   1<<29 / 1<<30  chunked depthwise-backward / scalar GlobLN-backward kernels and no backward fusion
- *   1<<31    training forward on the exact-fp32 MFMA kernel instead of the three-part split GEMM (pass INT_MIN) */
+ * One bit per switch: enum srf_debug_flag below.  The VALUES are frozen (bench.py --debug-flags and tools/gpu_ab.sh take
+ * numbers on their command lines); sudo_rm_rf_amd.ops.DebugFlag mirrors the names without the SRF_DBG_ prefix. */
 #ifdef SRF_DIAGNOSTICS
+enum srf_debug_flag {
+  /* srf_forward WITHOUT the fused conv pairs (round 5: res_conv / bottleneck + the next proj_1x1 in one launch) */
+  SRF_DBG_NO_PAIRS = 1,
+  /* 256 x 128 GEMMs: no m-tile groups (round 2's tile order); paired-block form: plain cache policy */
+  SRF_DBG_GEMM_NO_MGROUPS = 2,
+  /* without the 256 x 128 GEMM (128 x 128 kernels) */
+  SRF_DBG_NO_GEMM_256 = 4,
+  /* WITHOUT pre-packed weights (srf_forward packs by default) */
+  SRF_DBG_NO_PACKED_WEIGHTS = 8,
+  /* per-level depthwise + merge kernels instead of the fused pyramid (inference and training) */
+  SRF_DBG_PYR_PER_LEVEL = 16,
+  /* LDS pyramid kernels (with PYR_NO_REG): the block-per-row kernel instead of the wave-per-tile one */
+  SRF_DBG_PYR_NO_LDS_TILES = 32,
+  /* LDS pyramid kernels instead of the register ones */
+  SRF_DBG_PYR_NO_REG = 64,
+  /* non-persistent pyramid pass 1 */
+  SRF_DBG_PYR_PASS1_NONPERSISTENT = 128,
+  /* leftover GEMM tiles as whole tiles (no quarter tiles) */
+  SRF_DBG_GEMM_WHOLE_TAIL_TILES = 256,
+  /* quarter tiles last */
+  SRF_DBG_GEMM_QUARTER_TILES_LAST = 512,
+  /* TAC forward with one time step per lane */
+  SRF_DBG_TAC_ONE_STEP_PER_LANE = 1024,
+  /* one-tile-per-block 128 x 128 GEMM everywhere (also: no 64 x 64 tiles for small launches) */
+  SRF_DBG_GEMM_128_ONE_TILE_PER_BLOCK = 2048,
+  /* weight-gradient GEMM: round 3's block -> (tile, partial) mapping (every XCD re-reads its rows through its own L2) */
+  SRF_DBG_WGRAD_NO_XCD_MAP = 4096,
+  /* swap the two forms of the 256 x 128 GEMM: srf_forward / srf_separate run the one-block-per-CU kernel (srf_pwconv_x3w.hip),
+   * every other caller the paired-block kernel (srf_pwconv_x3p.hip) -- default: the paired form inside the forward only */
+  SRF_DBG_GEMM_256_SWAP_FORMS = 8192,
+  /* training forward: three bf16 parts per operand (6 MFMAs, round 3) instead of two fp16 parts (3 MFMAs, round 4) */
+  SRF_DBG_TRAIN_BF16X3 = 16384,
+  /* WITHOUT the fused tail: mask GEMM -> masked tensor -> decoder frame GEMM -> overlap-add as separate launches */
+  SRF_DBG_NO_FUSED_TAIL = 32768,
+  /* srf_backward WITHOUT the fused head of the blocks' pyramid backward (round 6: level 0 + proj_1x1's norm as two passes
+   * over {G_0, y1}): the level-0 conv kernel + the norm's apply pass of rounds 3-5 (set it around BOTH calls: a forward
+   * run without it leaves d_0 out of `saved`, and its backward then takes the head whatever the flag says) */
+  SRF_DBG_BWD_NO_FUSED_HEAD = 1 << 16,
+  /* pyramid pass 1 on a grid of co-resident wavefronts, several rows each (rounds 2-5) -- default since round 6: one row
+   * per wavefront */
+  SRF_DBG_PYR_PASS1_ROWS_PER_WAVE = 1 << 17,
+  /* weight-gradient GEMM WITHOUT the wide tile (round 6: 256 x 128 / 128 x 256, one block per CU): the 128 x 128 kernel;
+   * small-channel form on a fixed 1024 blocks (rounds 3-5) instead of one resident round */
+  SRF_DBG_WGRAD_NO_WIDE_TILE = 1 << 18,
+  /* weight-gradient GEMM, 128 x 128 kernel: the masked form for full shapes too (rounds 3-5) */
+  SRF_DBG_WGRAD_128_MASKED = 1 << 19,
+  /* weight-gradient GEMM, wide tile: 800-column time chunks (several per block) instead of one long chunk per block */
+  SRF_DBG_WGRAD_SHORT_CHUNKS = 1 << 20,
+  /* fused conv pair on persistent blocks (2 per CU, several tiles each) whatever the launch size -- default: one tile per block */
+  SRF_DBG_PAIR_PERSISTENT = 1 << 21,
+  /* TAC forward / backward on the VALU kernels instead of the MFMA forms (n = 16, G = 16) */
+  SRF_DBG_TAC_VALU = 1 << 22,
+  /* fused conv pair with every counted wait of its DMA pipeline as a full drain (bisection aid, same results) */
+  SRF_DBG_PAIR_FULL_DRAIN = 1 << 23,
+  /* TAC forward on the generic kernel (no lane-per-time-step form) */
+  SRF_DBG_TAC_GENERIC = 1 << 24,
+  /* weight-gradient partials folded by one chain per output (rounds 3-4) instead of four groups per output (round 5) */
+  SRF_DBG_WGRAD_ONE_CHAIN_FOLD = 1 << 25,
+  /* TAC forward: the lane-per-time-step form with four tiles per block */
+  SRF_DBG_TAC_LANES_4TILES = 1 << 26,
+  /* 64-bit pointer loads in the 128 x 128 GEMM (no buffer loads) */
+  SRF_DBG_GEMM_128_POINTER_LOADS = 1 << 27,
+  /* training forward on the split-bf16 GEMMs (faster; gradients then differ from the reference by ~3e-3) */
+  SRF_DBG_TRAIN_FWD_SPLIT_BF16 = 1 << 28,
+  /* chunked depthwise-backward kernels and no backward fusion */
+  SRF_DBG_BWD_DW_CHUNKED = 1 << 29,
+  /* scalar GlobLN-backward kernels and no backward fusion */
+  SRF_DBG_BWD_GLN_SCALAR = 1 << 30,
+  /* training forward on the exact-fp32 MFMA kernel instead of the three-part split GEMM.  Bit 31 of an int: INT_MIN */
+  SRF_DBG_TRAIN_FWD_EXACT_MFMA = -2147483647 - 1
+};
 void srf_set_debug_flags(int flags);
 #endif
 

@@ -11,7 +11,7 @@
 #include <new>
 #include <vector>
 
-#include "srf_common.h"
+#include "srf_plan.h"
 
 // ---------------------------------------------------------------------------------------------
 // error string / kernel mode
@@ -176,35 +176,13 @@ static int srf_zero_launch(void* p, size_t bytes, hipStream_t st) {
   return SRF_OK;
 }
 
-int srf_transpose_launch(const float* w, float* wt, int Ci, int M, hipStream_t st);
-int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, int L, int T, int nparts, const float* stats,
-                           const float* wav, int mc, hipStream_t st);
-bool srf_pw_conv_preadd_supported(int Cin, int Cout, int L, const void* const* ptrs, int nptrs);
-int srf_pw_conv_preadd(const float* x, const float* q, const srf_norm* qnorm, float* u, const float* w, const float* bias,
-                       float* y, int Bt, int Cin, int Cout, int L, double* out_sums, hipStream_t st);
-bool srf_mask_decode_supported(int Bt, int Cin, int Cout, int L, int M);
-size_t srf_mask_decode_pack_bytes(int Cout);
-int srf_mask_decode_pack(const float* wd, void* dst, int Ci, int M, hipStream_t st);
-int srf_mask_decode(const float* x, const float* w, const void* w_packed, const float* bias, const float* prelu,
-                    const float* mul, int mul_channels, const void* wd_packed, float* zpart, int Bt, int Cin, int Cout, int L,
-                    int M, hipStream_t st);
-int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
-                     const float* in_stats, void* stream);
-extern "C" int srf_wav_stats(const float* wav, float* stats, int rows, int T, void* stream);
-extern "C" int srf_pw_conv_pair_supported(int Bt, int Cin1, int Cmid, int Cout2, int L);
-extern "C" int srf_pw_conv_pair(const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
-                                const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2,
-                                int Bt, int Cin1, int Cmid, int Cout2, int L, void* stream);
-
 // ---------------------------------------------------------------------------------------------
 // decoder = transpose(weight) -> frame GEMM (K2) -> overlap-add + crop
 // ---------------------------------------------------------------------------------------------
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 extern "C" size_t srf_decoder_scratch_floats(int Bt, int Ci, int Co, int K, int L) {
   const size_t M = (size_t)Co * K;
   // wt [M][Ci] | zero bias [M] | z [Bt][M][L]   (each section 64-float aligned)
-  return align_up(M * Ci, 64) + align_up(M, 64) + align_up((size_t)Bt * M * L, 64);
+  return srf_align_up(M * Ci, 64) + srf_align_up(M, 64) + srf_align_up((size_t)Bt * M * L, 64);
 }
 
 static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T,
@@ -228,11 +206,11 @@ static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, 
   hipStream_t st = (hipStream_t)stream;
   const int M = Co * K;
   float* wt = scratch;
-  float* zb = wt + align_up((size_t)M * Ci, 64);
-  float* z = zb + align_up((size_t)M, 64);
+  float* zb = wt + srf_align_up((size_t)M * Ci, 64);
+  float* z = zb + srf_align_up((size_t)M, 64);
   int rc = srf_transpose_launch(w, wt, Ci, M, st);
   if (rc) return rc;
-  rc = srf_zero_launch(zb, sizeof(float) * align_up((size_t)M, 64), st);
+  rc = srf_zero_launch(zb, sizeof(float) * srf_align_up((size_t)M, 64), st);
   if (rc) return rc;
   const srf_norm act{nullptr, nullptr, nullptr, in_prelu};
   rc = srf_pw_conv(v, wt, zb, z, Bt, Ci, M, L, in_prelu ? &act : nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
@@ -243,7 +221,23 @@ static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, 
 // ---------------------------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------------------------
-#include "srf_plan.h"
+// T padded up to a multiple of n_least_samples_req = h * 2^D, at least one (improved_sudormrf.py:244,303-314)
+static long plan_padded_length(int T, int h, int D) {
+  const long nls = (long)h << D;
+  return (T < nls) ? nls : ((T / nls) + (T % nls ? 1 : 0)) * nls;
+}
+// A packed (split-bf16) image of parameter `param` ([cout, cin]) in the workspace, for the shapes the 256 x 128 GEMM supports
+static void plan_add_pack(srf_plan* p, size_t* off, int param, int cout, int cin) {
+  const size_t bytes = srf_packed_pw_weight_bytes(cout, cin);
+  if (!bytes) return;
+  const size_t o = *off;
+  *off = srf_align_up(*off + bytes, 256);
+  p->pk_param.push_back(param);
+  p->pk_cout.push_back(cout);
+  p->pk_cin.push_back(cin);
+  p->pk_off.push_back(o);
+  p->pk_of_param[param] = o;
+}
 
 static int plan_fail(srf_plan* p, int rc) {
   delete p;
@@ -291,8 +285,7 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   }
   const int D = c->upsampling_depth, U = c->num_blocks, K = c->enc_kernel_size;
   const int h = K / 2;
-  const long nls = (long)h << D;  // n_least_samples_req, improved_sudormrf.py:244
-  long Tp = (T < nls) ? nls : ((T / nls) + (T % nls ? 1 : 0)) * nls;
+  const long Tp = plan_padded_length(T, h, D);
   p->Bt = batch;
   p->T = T;
   p->Tp = (int)Tp;
@@ -325,7 +318,7 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
-    off = align_up(off + bytes, 256);
+    off = srf_align_up(off + bytes, 256);
     return o;
   };
   p->stats_bytes = (size_t)p->n_slots * p->Bg * SRF_STAT_BUCKETS * 2 * sizeof(double);
@@ -343,23 +336,13 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   p->off_pyr = p->fused_pyramid ? take(srf_pyramid_scratch_bytes(p->Bg, p->nC, p->L, D)) : 0;
   // packed weights for the split-precision GEMM (only shapes the kernel supports)
   p->pk_of_param.assign(p->n_params, 0);
-  auto add_pack = [&](int param, int cout, int cin) {
-    const size_t bytes = srf_packed_pw_weight_bytes(cout, cin);
-    if (!bytes) return;
-    const size_t o = take(bytes);
-    p->pk_param.push_back(param);
-    p->pk_cout.push_back(cout);
-    p->pk_cin.push_back(cin);
-    p->pk_off.push_back(o);
-    p->pk_of_param[param] = o;
-  };
-  add_pack(3, c->out_channels, c->enc_num_basis);
+  plan_add_pack(p, &off, 3, c->out_channels, c->enc_num_basis);
   for (int i = 0; i < U; ++i) {
     const int pu = p->p_block0 + i * p->p_block_stride + p->p_ublock_off;
-    add_pack(pu + 0, p->nC, p->nB);
-    add_pack(pu + 5 + 4 * D + 3, p->nB, p->nC);
+    plan_add_pack(p, &off, pu + 0, p->nC, p->nB);
+    plan_add_pack(p, &off, pu + 5 + 4 * D + 3, p->nB, p->nC);
   }
-  add_pack(p->p_tail + 1, p->SA * c->enc_num_basis, c->out_channels);
+  plan_add_pack(p, &off, p->p_tail + 1, p->SA * c->enc_num_basis, c->out_channels);
   // decoder weights as MFMA fragments for the fused tail (K5); whether it runs is decided per forward
   p->off_wdpack = (p->SA * K <= 64 && p->pk_of_param[p->p_tail + 1]) ? take(srf_mask_decode_pack_bytes(p->SA * c->enc_num_basis)) : 0;
   p->total_bytes = off;
@@ -389,8 +372,7 @@ static int causal_plan_create(const srf_config* c, int batch, int T, srf_plan** 
   const int D = c->upsampling_depth, U = c->num_blocks, K = c->enc_kernel_size, N = c->enc_num_basis;
   const int B = c->out_channels, Cc = c->in_channels;
   const int h = K / 2;
-  const long nls = (long)h << D;   // n_least_samples_req
-  const long Tp = (T < nls) ? nls : ((T / nls) + (T % nls ? 1 : 0)) * nls;
+  const long Tp = plan_padded_length(T, h, D);
   if (Tp > (1L << 30)) {
     srf_set_error("srf_plan_create: T=%d too long", T);
     return plan_fail(p, SRF_EINVAL);
@@ -421,7 +403,7 @@ static int causal_plan_create(const srf_config* c, int batch, int T, srf_plan** 
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
-    off = align_up(off + (bytes ? bytes : 1), 256);
+    off = srf_align_up(off + (bytes ? bytes : 1), 256);
     return o;
   };
   p->stats_bytes = 0;
@@ -438,27 +420,17 @@ static int causal_plan_create(const srf_config* c, int batch, int T, srf_plan** 
   p->fused_pyramid = srf_causal_pyramid_supported(Cc, p->L, D);
   p->off_pyr = 0;
   // per block: res_conv weight * (gain * alpha) [B][C] | its bias [B]   and   proj_1x1 weight / beta [C][B]
-  const size_t res_floats = align_up((size_t)B * Cc, 64) + align_up((size_t)B, 64);
+  const size_t res_floats = srf_align_up((size_t)B * Cc, 64) + srf_align_up((size_t)B, 64);
   p->off_fold_res = take(F * res_floats * U);
   p->off_fold_proj = take(F * (size_t)Cc * B * U);
   p->pk_of_param.assign(p->n_params, 0);
-  auto add_pack = [&](int param, int cout, int cin) {
-    const size_t bytes = srf_packed_pw_weight_bytes(cout, cin);
-    if (!bytes) return;
-    const size_t o = take(bytes);
-    p->pk_param.push_back(param);
-    p->pk_cout.push_back(cout);
-    p->pk_cin.push_back(cin);
-    p->pk_off.push_back(o);
-    p->pk_of_param[param] = o;
-  };
-  add_pack(1, B, N);
+  plan_add_pack(p, &off, 1, B, N);
   for (int i = 0; i < U; ++i) {
     const int pb = p->p_block0 + i * p->p_block_stride;
-    add_pack(pb + 1, Cc, B);
-    add_pack(pb + 4 + 3 * D, B, Cc);
+    plan_add_pack(p, &off, pb + 1, Cc, B);
+    plan_add_pack(p, &off, pb + 4 + 3 * D, B, Cc);
   }
-  add_pack(p->p_tail + 1, p->SA * N, B);
+  plan_add_pack(p, &off, p->p_tail + 1, p->SA * N, B);
   p->off_wdpack = 0;
   p->total_bytes = off;
   p->n_launches = 3 /*fold, pack, encoder*/ + 1 + U * 3 + 1 + 4;
@@ -513,7 +485,6 @@ static int srf_forward_body(const srf_plan* p, const float* const* P, int num_pa
                             void* workspace, size_t workspace_bytes, const float* wav_stats, int mixture_consistency,
                             void* stream);
 static int causal_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace, void* stream);
-void srf_pw_prefer_paired(bool on);   // srf_pwconv.hip: the paired-block form of the 256 x 128 GEMM for this thread's launches
 static int srf_forward_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                             void* workspace, size_t workspace_bytes, const float* wav_stats, int mixture_consistency,
                             void* stream) {
@@ -557,8 +528,7 @@ static int srf_forward_body(const srf_plan* p, const float* const* P, int num_pa
   rc = srf_zero_launch(stats, p->stats_bytes, st);
   if (rc) return rc;
   // split + lay out every 1x1 weight for the 256 x 128 split-precision GEMMs (srf_pwconv_x3w.hip / _x3p.hip), one launch per form and forward
-  // (kernel mode 0 only; debug flag 8 = without: the 128 x 128 kernels that split W on the fly)
-  const bool use_pack = srf_kernel_mode() == 0 && !(srf_debug_flags() & 8) && !p->pk_param.empty();
+  const bool use_pack = plan_use_pack(p);
   if (use_pack) {
     std::vector<const float*> pw(p->pk_param.size());
     std::vector<void*> pd(p->pk_param.size());
@@ -584,9 +554,9 @@ static int srf_forward_body(const srf_plan* p, const float* const* P, int num_pa
   // tensor handed over in registers (srf_pwconv_x3f.hip): bottleneck -> proj_1x1 of block 0, res_conv of block i -> proj_1x1 of
   // block i + 1 (improved_sudormrf.py:292 -> :205, :220 -> :205).  Needs the fused pyramid (its merged tensor has a buffer of
   // its own: the pair kernel writes y1 while it reads the merged tensor).  Debug flag 1 = separate launches.
-  const bool pyr_fused_now = p->fused_pyramid && srf_kernel_mode() != 1 && !(srf_debug_flags() & 16);
+  const bool fused = plan_fused_pyramid_now(p);
   const int pu0 = p->p_block0 + p->p_ublock_off;
-  const bool pair_res = !gc && use_pack && pyr_fused_now && packed(pu0) && packed(pu0 + 5 + 4 * D + 3) &&
+  const bool pair_res = !gc && use_pack && fused && packed(pu0) && packed(pu0 + 5 + 4 * D + 3) &&
                         srf_pw_conv_pair_supported(Bt, nC, nB, nC, L);
   const bool pair_head = pair_res && packed(3) && srf_pw_conv_pair_supported(Bt, N, nB, nC, L);
   bool y1_ready = false;      // proj_1x1 of the coming block has already been computed (with its statistics) by a pair launch
@@ -640,7 +610,6 @@ static int srf_forward_body(const srf_plan* p, const float* const* P, int num_pa
     // depthwise pyramid + upsample/add                         :206-216
     // unfused path: the merged tensor aliases y1 (dead once every level has been produced); fused path:
     // its own buffer (the otherwise unused level-0 buffer), because pass 2 re-reads y1 with halos
-    const bool fused = p->fused_pyramid && srf_kernel_mode() != 1 && !(srf_debug_flags() & 16);
     float* merged = fused ? fptr(p->off_lv[0]) : y1;
     if (fused) {
       // two passes with every level kept on chip (srf_pyramid.hip)
@@ -711,8 +680,7 @@ static int srf_forward_body(const srf_plan* p, const float* const* P, int num_pa
   // K5: mask GEMM and decoder contraction in ONE launch -- the [Bt, S N, L] masked tensor (the largest of the forward) never
   // reaches HBM; the GEMM leaves per-256-channel partial decoder frames (in the masked tensor's workspace region, <= 1/4 of
   // it) and the overlap-add sums them.  Only where the 256 x 128 GEMM would have run the mask conv anyway.
-  if (p->off_wdpack && use_pack && packed(p->p_tail + 1) && N % 8 == 0 &&
-      srf_mask_decode_supported(Bt, c.out_channels, p->SA * N, L, p->SA * K)) {
+  if (plan_fused_tail_now(p, use_pack)) {
     const int M = p->SA * K, nparts = (p->SA * N + 255) / 256;
     rc = srf_mask_decode_pack(Pt[3], ws + p->off_wdpack, p->SA * N, M, st);
     if (rc) return rc;
@@ -746,8 +714,7 @@ extern "C" int srf_debug_fetch(const srf_plan* p, const void* workspace, int wha
     n = (size_t)p->Bt * c.out_channels * p->L;
   } else if (what == 2) {
     // the fused tail (K5) never materialises the masked tensor: its workspace region holds partial decoder frames
-    if (p->off_wdpack && srf_kernel_mode() == 0 && !(srf_debug_flags() & 8) && c.enc_num_basis % 8 == 0 &&
-        srf_mask_decode_supported(p->Bt, c.out_channels, p->SA * c.enc_num_basis, p->L, p->SA * c.enc_kernel_size)) {
+    if (plan_fused_tail_now(p, plan_use_pack(p))) {
       srf_set_error("srf_debug_fetch: the masked tensor is not materialised at this shape (mask GEMM and decoder run fused); "
                     "set debug flag 32768 to run the tail unfused");
       return SRF_EINVAL;
@@ -768,8 +735,6 @@ extern "C" int srf_debug_fetch(const srf_plan* p, const void* workspace, int wha
 // causal forward (CausalSuDORMRF.forward): encoder -> bottleneck -> U x [proj_1x1 -> fused causal pyramid -> res_conv with
 // skipinit_gain * alpha folded into its weights, + residual] -> PReLU + mask conv -> PReLU folded into the decoder's load.
 // ---------------------------------------------------------------------------------------------
-int srf_causal_scale_many(const float* const* src, float* const* dst, const long* n, const float* const* dscale,
-                          const float* hscale, int count, hipStream_t st);
 static int causal_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace, void* stream) {
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
@@ -779,7 +744,7 @@ static int causal_forward(const srf_plan* p, const float* const* P, const float*
   auto fptr = [&](size_t o) { return (float*)(ws + o); };
   int rc;
   // ---- fold: res_conv weight / bias * (skipinit_gain * alpha) for every block, proj_1x1 weight / beta where beta != 1
-  const size_t res_floats = align_up((size_t)B * Cc, 64) + align_up((size_t)B, 64);
+  const size_t res_floats = srf_align_up((size_t)B * Cc, 64) + srf_align_up((size_t)B, 64);
   std::vector<const float*> fsrc, fscale;
   std::vector<float*> fdst;
   std::vector<long> fn;
@@ -788,7 +753,7 @@ static int causal_forward(const srf_plan* p, const float* const* P, const float*
   for (int i = 0; i < U; ++i) {
     const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
     float* rw = fptr(p->off_fold_res) + (size_t)i * res_floats;
-    float* rb = rw + align_up((size_t)B * Cc, 64);
+    float* rb = rw + srf_align_up((size_t)B * Cc, 64);
     fsrc.push_back(Pb[4 + 3 * D]); fdst.push_back(rw); fn.push_back((long)B * Cc); fscale.push_back(Pb[0]); fh.push_back(p->alpha[i]);
     fsrc.push_back(Pb[5 + 3 * D]); fdst.push_back(rb); fn.push_back((long)B); fscale.push_back(Pb[0]); fh.push_back(p->alpha[i]);
     wres[i] = rw;
@@ -803,7 +768,7 @@ static int causal_forward(const srf_plan* p, const float* const* P, const float*
   rc = srf_causal_scale_many(fsrc.data(), fdst.data(), fn.data(), fscale.data(), fh.data(), (int)fsrc.size(), st);
   if (rc) return rc;
   // ---- split-bf16 weight images of the packed shapes (kernel mode 0), from the folded copies where there are any
-  const bool use_pack = srf_kernel_mode() == 0 && !(srf_debug_flags() & 8) && !p->pk_param.empty();
+  const bool use_pack = plan_use_pack(p);
   auto source_of = [&](int param) -> const float* {
     const int rel = param - p->p_block0;
     if (param >= p->p_block0 && param < p->p_tail) {
@@ -838,8 +803,8 @@ static int causal_forward(const srf_plan* p, const float* const* P, const float*
   if (rc) return rc;
   // ---- separation module.  res_conv of block i + proj_1x1 of block i + 1 as one launch where the pair kernel takes the
   // shape (its no-prologue form: residual required), as in the Improved forward
-  const bool fused = p->fused_pyramid && srf_kernel_mode() != 1 && !(srf_debug_flags() & 16);
-  const bool pair = use_pack && !(srf_debug_flags() & 1) && srf_pw_conv_pair_supported(Bt, Cc, B, Cc, L);
+  const bool fused = plan_fused_pyramid_now(p);
+  const bool pair = use_pack && !srf_dbg(SRF_DBG_NO_PAIRS) && srf_pw_conv_pair_supported(Bt, Cc, B, Cc, L);
   bool y1_ready = false;
   for (int i = 0; i < U; ++i) {
     const int pb = p->p_block0 + i * p->p_block_stride;

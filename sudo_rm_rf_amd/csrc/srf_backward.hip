@@ -5,7 +5,7 @@
 //   depthwise k=5 conv (s=1|2)      improved_sudormrf.py:138-159,178-189
 //   mask ReLU * encoder output      improved_sudormrf.py:296-298
 //   conv_transpose1d / conv1d frame gathers for the decoder / encoder weight gradients  :247-251,272-279
-#include "srf_common.h"
+#include "srf_internal.h"
 
 // The streamed operands of the row kernels below (gradients, saved activations: each read once per kernel) as non-temporal loads
 // (round 4; -DSRF_BWD_NT=false for the A/B build)
@@ -430,7 +430,7 @@ int srf_gln_bwd_impl(const float* gout, const float* gout2, const float* x, cons
   // (deferred mode: the caller's scratch slices are zeroed once per backward)
   if (!pre_reduced && !defer) SRF_CHECK_HIP(hipMemsetAsync(a.bsums, 0, sizeof(double) * (size_t)groups * SRF_STAT_BUCKETS * 2, st));
   const bool v4 = (L % 4) == 0 && srf_aligned16(gout) && srf_aligned16(x) && (!gx || srf_aligned16(gx)) &&
-                  (!gout2 || srf_aligned16(gout2)) && srf_kernel_mode() != 1 && !(srf_debug_flags() & (1 << 30));
+                  (!gout2 || srf_aligned16(gout2)) && srf_kernel_mode() != 1 && !srf_dbg(SRF_DBG_BWD_GLN_SCALAR);
   const dim3 grid4((unsigned)((rows + 3) / 4));
   if (!pre_reduced) {
     if (v4)
@@ -1152,7 +1152,7 @@ extern "C" size_t srf_dwconv5_bwd_scratch_bytes(int groups, int C) {
 // srf_dwconv5_bwd_rowwise_ok first): gd is then the gradient w.r.t. the OUTPUT of the norm `anorm` that follows this
 // conv, ax that norm's input (= this conv's output) and a_scratch its reduced sums (srf_gln_bwd_impl mode bit 1).
 bool srf_dwconv5_bwd_rowwise_ok(int Lin, int stride, const void* const* ptrs, int nptrs) {
-  if ((Lin % 4) != 0 || srf_kernel_mode() == 1 || (srf_debug_flags() & ((1 << 29) | (1 << 30)))) return false;
+  if ((Lin % 4) != 0 || srf_kernel_mode() == 1 || srf_dbg(SRF_DBG_BWD_DW_CHUNKED | SRF_DBG_BWD_GLN_SCALAR)) return false;
   if (stride == 2 && ((Lin - 1) / 2 + 1) * 2 != Lin) return false;
   for (int i = 0; i < nptrs; ++i)
     if (ptrs[i] && !srf_aligned16(ptrs[i])) return false;
@@ -1195,11 +1195,11 @@ int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_n
   const int per_block = fast ? 1024 : 2048;
   const int chunks = (Lin + per_block - 1) / per_block;
   // stride 2 with an odd output count (Lin % 8 == 4) keeps the chunked kernel: its float2 loads assume Lout = Lin / 2
-  const bool rowwise = fast && (stride == 1 || a.Lout * 2 == Lin) && !(srf_debug_flags() & (1 << 29));
+  const bool rowwise = fast && (stride == 1 || a.Lout * 2 == Lin) && !srf_dbg(SRF_DBG_BWD_DW_CHUNKED);
   if (rowwise) {
     const dim3 grid4((unsigned)((rows + 3) / 4));
     const bool fuse = gln_scratch && gin && in_norm && in_norm->sums && in_norm->gamma && in_norm->beta &&
-                      (!gadd || srf_aligned16(gadd)) && !(srf_debug_flags() & (1 << 30));
+                      (!gadd || srf_aligned16(gadd)) && !srf_dbg(SRF_DBG_BWD_GLN_SCALAR);
     SRF_CHECK_ARG(!ax || (fuse && anorm && anorm->sums && anorm->gamma && anorm->beta && a_scratch && srf_aligned16(ax)),
                   "srf_dwconv5_bwd: apply-on-load needs the fused row kernel");
     if (fuse) {
@@ -1433,7 +1433,7 @@ bool srf_bwd_level0_proj_shape_ok(int L, const void* const* ptrs, int nptrs) {
   return true;
 }
 bool srf_bwd_level0_proj_ok(int L, const void* const* ptrs, int nptrs) {
-  if (srf_kernel_mode() == 1 || (srf_debug_flags() & ((1 << 16) | (1 << 29) | (1 << 30)))) return false;
+  if (srf_kernel_mode() == 1 || srf_dbg(SRF_DBG_BWD_NO_FUSED_HEAD | SRF_DBG_BWD_DW_CHUNKED | SRF_DBG_BWD_GLN_SCALAR)) return false;
   return srf_bwd_level0_proj_shape_ok(L, ptrs, nptrs);
 }
 int srf_bwd_level0_proj(const float* G0, const float* y1, const srf_norm* pn, const srf_norm* n0, const float* w0, const float* b0,

@@ -7,10 +7,8 @@
 //   srf_causal_scale          <- skipinit_gain * alpha folded into res_conv, 1 / beta into proj_1x1 (device scalars)
 //   srf_prelu_apply           <- a stand-alone nn.PReLU (ConvAct with a 1x1 conv)
 // The masked taps of the stored weights (the reference multiplies them by causal_mask at every forward) are never read.
-#include "srf_common.h"
+#include "srf_internal.h"
 
-#define SRF_CAUSAL_TAPS 11   // live taps of the k = 21 depthwise convs (21 - 21 // 2)
-#define SRF_CAUSAL_KW 21     // weight row stride of those convs
 #define SRF_CAUSAL_TILE 1024 // level-0 frames per block of the fused pyramid
 
 // ---------------------------------------------------------------------------------------------

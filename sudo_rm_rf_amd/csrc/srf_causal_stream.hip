@@ -15,20 +15,12 @@
 #include <new>
 #include <vector>
 
-#include "srf_common.h"
+#include "srf_internal.h"
 
-#define SRF_CAUSAL_TAPS 11   // live taps of the k = 21 depthwise convs
-#define SRF_CAUSAL_KW 21     // weight row stride of those convs
 #define SRF_STREAM_HIST (SRF_CAUSAL_TAPS - 1)
 #define SRF_STREAM_TN 8      // columns per GEMM tile
 #define SRF_STREAM_RPW 4     // pyramid rows per wavefront (16 lanes each)
 #define SRF_STREAM_LDS_MAX (64 * 1024)
-
-int srf_causal_scale_many(const float* const* src, float* const* dst, const long* n, const float* const* dscale,
-                          const float* hscale, int count, hipStream_t st);
-int srf_transpose_launch(const float* w, float* wt, int Ci, int M, hipStream_t st);
-
-static size_t st_align(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // ---------------------------------------------------------------------------------------------
 // encoder: out[nb][b Lc + l] = sum_{a, k<K} w[nb,a,k] win[b,a, h l + k],  win = [hist (2h) | chunk (n)].
@@ -411,18 +403,18 @@ extern "C" int srf_stream_create(const srf_config* c, int batch, int max_chunk_s
   size_t off = 0;
   for (int p = 0; p < s->n_params; ++p) {
     s->w_off[p] = off;
-    off += st_align((size_t)s->w_n[p], 64);
+    off += srf_align_up((size_t)s->w_n[p], 64);
   }
   s->weights_floats = off;
   // state: three sections, each 64-float aligned
   s->st_hist = 0;
-  s->st_dw = st_align((size_t)batch * s->A * 2 * h, 64);
-  s->st_tail = s->st_dw + st_align((size_t)U * D * batch * s->C * SRF_STREAM_HIST, 64);
-  s->state_floats = s->st_tail + st_align((size_t)batch * SA * (h + 1), 64);
+  s->st_dw = srf_align_up((size_t)batch * s->A * 2 * h, 64);
+  s->st_tail = s->st_dw + srf_align_up((size_t)U * D * batch * s->C * SRF_STREAM_HIST, 64);
+  s->state_floats = s->st_tail + srf_align_up((size_t)batch * SA * (h + 1), 64);
   // workspace
   const size_t ncol = (size_t)batch * max_lc;
   off = 0;
-  auto take = [&](size_t f) { const size_t o = off; off += st_align(f, 64); return o; };
+  auto take = [&](size_t f) { const size_t o = off; off += srf_align_up(f, 64); return o; };
   s->ws_enc = take((size_t)N * ncol);
   s->ws_xa = take((size_t)s->B * ncol);
   s->ws_xb = take((size_t)s->B * ncol);

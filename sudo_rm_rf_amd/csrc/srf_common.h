@@ -16,7 +16,8 @@
 void srf_set_error(const char* fmt, ...);
 int srf_kernel_mode();  // 0 = fast paths, 1 = generic kernels only, 2 = fast paths with exact-fp32 MFMA GEMMs
 int srf_kernel_mode_override(int mode);   // per-thread override (-1 = none); returns the previous override
-int srf_debug_flags();  // kernel-variant switches for A/B runs and tests (table: include/sudormrf_hip.h, SRF_DIAGNOSTICS)
+int srf_debug_flags();  // kernel-variant switches for A/B runs and tests (enum srf_debug_flag: include/sudormrf_hip.h, SRF_DIAGNOSTICS)
+static inline bool srf_dbg(int mask) { return (srf_debug_flags() & mask) != 0; }   // any of the SRF_DBG_* bits of `mask` set
 bool srf_profiling();
 void srf_prof_hold(int delta);   // +1 / -1 around all but the last launch of an operation that is one profiler interval
 void srf_prof_mark(const char* name, hipStream_t st);
@@ -60,6 +61,7 @@ long srf_device_cached(int slot, long (*compute)(void*), void* arg);
   } while (0)
 
 static inline bool srf_aligned16(const void* p) { return (((size_t)p) & 15) == 0; }
+static inline size_t srf_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Refusal of a misplaced operand, BEFORE anything is launched, naming it: every (name, pointer) pair whose pointer is not
 // NULL must be 16-byte aligned.  SRF_CHECK_ALIGNED16("srf_x", {"g", g}, {"x", x});

@@ -4,7 +4,7 @@
 //   TAC_norm + residual         groupcomm_sudormrf_v2.py:378-382
 //   mixture_consistency.apply   experiments/utils/mixture_consistency.py:14-36
 //   ConvTranspose1d overlap-add improved_sudormrf.py:272-279,300 and crop :316-318
-#include "srf_common.h"
+#include "srf_internal.h"
 
 // ---- GlobLN statistics ------------------------------------------------------------------------
 // grid: (chunks, groups); each block reduces a contiguous slice of its group.

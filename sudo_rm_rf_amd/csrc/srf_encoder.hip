@@ -6,7 +6,7 @@
 // time (coalesced 256-B stores per channel row); channels are wave-uniform so the filter taps are
 // scalar (SGPR) operands of the FMAs.  GlobLN {sum,sumsq} of the output are produced here so that
 // `ln` never needs its own pass over the tensor.
-#include "srf_common.h"
+#include "srf_internal.h"
 
 // Fast path: one audio channel, compile-time K.  Each lane owns two frames (l, l+64) whose KT-sample
 // windows live in registers; the block's input window is staged once through LDS.

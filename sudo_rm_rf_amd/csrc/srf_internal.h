@@ -1,0 +1,96 @@
+// Library-internal entry points: every non-static function that one .hip defines and another calls is declared here, once
+// (those that take PwArgs / PwPairArgs: srf_pw.h; PyrRegArgs: srf_pyr.h).  The defining file includes this header too, so the
+// compiler checks each definition against the declaration its callers see.  The public extern "C" functions come from
+// include/sudormrf_hip.h (through srf_common.h) and are never re-declared.
+#pragma once
+#include "srf_common.h"
+
+// ---- causal model: shared by the whole-sequence kernels (srf_causal.hip) and the streaming ones (srf_causal_stream.hip);
+// "bit-identical under any chunking" rests on both reading the same taps
+#define SRF_CAUSAL_TAPS 11   // live taps of the k = 21 depthwise convs (21 - 21 // 2)
+#define SRF_CAUSAL_KW 21     // weight row stride of those convs
+
+// ---- srf_elementwise.hip
+int srf_transpose_launch(const float* w, float* wt, int Ci, int M, hipStream_t st);
+// stats: null = plain overlap-add; else [Bt][2] {mean, std} of the raw mixture `wav` [Bt][T] (mc: also mixture consistency)
+int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, int L, int T, int nparts, const float* stats,
+                           const float* wav, int mc, hipStream_t st);
+
+// ---- srf_encoder.hip
+int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
+                     const float* in_stats, void* stream);
+
+// ---- srf_causal.hip: srf_forward folds every block's scales with as few launches as possible
+int srf_causal_scale_many(const float* const* src, float* const* dst, const long* n, const float* const* dscale,
+                          const float* hscale, int count, hipStream_t st);
+
+// ---- srf_pyramid.hip / srf_pyramid_reg.hip
+bool srf_pyramid_reg_supported(int L, int D);
+// lv_out / lv_sums (both or neither; register-resident kernels only): the training forward's extra outputs
+int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
+                     const float* const* bias, const float* const* gamma, const float* const* beta, int groups, int C,
+                     int L, int D, void* scratch, double* out_sums, float* const* lv_out, double* const* lv_sums,
+                     void* stream);
+
+// ---- srf_pwconv.hip
+void srf_pw_prefer_paired(bool on);   // the paired-block form of the 256 x 128 GEMM for this thread's launches
+bool srf_pw_conv_preadd_supported(int Cin, int Cout, int L, const void* const* ptrs, int nptrs);
+int srf_pw_conv_preadd(const float* x, const float* q, const srf_norm* qnorm, float* u, const float* w, const float* bias,
+                       float* y, int Bt, int Cin, int Cout, int L, double* out_sums, hipStream_t st);
+// K5 (srf_forward's tail): mask GEMM + decoder contraction in one launch
+bool srf_mask_decode_supported(int Bt, int Cin, int Cout, int L, int M);
+size_t srf_mask_decode_pack_bytes(int Cout);
+int srf_mask_decode_pack(const float* wd, void* dst, int Ci, int M, hipStream_t st);
+// zpart[Bt][ceil(Cout / 256)][M][L] = per-256-channel partial sums of Wd^T (relu(W prelu(x) + bias) * mul)
+int srf_mask_decode(const float* x, const float* w, const void* w_packed, const float* bias, const float* prelu,
+                    const float* mul, int mul_channels, const void* wd_packed, float* zpart, int Bt, int Cin, int Cout, int L,
+                    int M, hipStream_t st);
+int srf_pack_pw_weights_transposed(const float* const* w, void* const* packed, const int* Cout, const int* Cin, int n,
+                                   hipStream_t st);
+bool srf_pw_packed_only(const void* w_packed, const float* x, int Bt, int Cin, int Cout, int L);
+
+// ---- srf_pwconv_x3w.hip (the 256 x 128 kernel), _x3p.hip (its paired-block form), _x3f.hip (the fused pair), _small.hip
+bool srf_x3w_supported(int Bt, int pro);
+bool srf_x3w_shape_supported(int Cin, int Cout, int L);
+size_t srf_x3w_packed_bytes(int Cout, int Cin);
+int srf_x3w_pack_launch(const float* const* w, char* const* dst, const int* Cout, const int* Cin, int n, hipStream_t st);
+int srf_x3w_pack2_launch(const float* const* w, char* const* dst, char* const* dst16, const int* Cout, const int* Cin, int n,
+                         hipStream_t st);
+size_t srf_x3w_dec_pack_bytes(int Ci);
+int srf_x3w_pack_dec_launch(const float* w, void* dst, int Ci, int M, hipStream_t st);
+int srf_x3w_pack_f16_launch(const float* const* w, char* const* dst, const int* Cout, const int* Cin, int n, hipStream_t st,
+                            char* const* dst16);
+size_t srf_x3w_packed3_bytes(int Cout, int Cin);
+int srf_x3w_pack3_launch(const float* const* w, char* const* dst, const int* Cout, const int* Cin, int n, hipStream_t st);
+size_t srf_x3p_packed_bytes(int Cout, int Cin);
+bool srf_x3f_supported(int Bt, int K1, int C2, int L);
+bool srf_pw_small_supported(int Cin, int Cout, int L);
+
+// ---- srf_backward.hip
+int srf_accumulate_launch(float* dst, const float* src, long n, hipStream_t st);
+// What one srf_backward call carries across its kernel-level calls -- the deferred parameter-gradient reductions and the
+// "merge backward rides on the next GlobLN apply" request (an explicit object; NULL = neither)
+struct SrfBwdCtx;
+SrfBwdCtx* srf_bwd_ctx_new();
+void srf_bwd_ctx_free(SrfBwdCtx* c);
+void srf_bwd_ctx_defer(SrfBwdCtx* c, bool on);
+void srf_bwd_ctx_merge_sink(SrfBwdCtx* c, float* const* levels, int D);
+bool srf_bwd_ctx_merge_taken(const SrfBwdCtx* c);
+int srf_bwd_ctx_flush(SrfBwdCtx* c, hipStream_t st);
+int srf_gln_bwd_impl(const float* gout, const float* gout2, const float* x, const srf_norm* norm, int groups, int C,
+                     int L, float* gx, int accumulate_gx, float* dgamma, float* dbeta, float* dslope, void* scratch,
+                     int mode, void* stream, SrfBwdCtx* ctx);
+bool srf_dwconv5_bwd_rowwise_ok(int Lin, int stride, const void* const* ptrs, int nptrs);
+int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_norm, const float* w, int groups, int C,
+                         int Lin, int stride, float* gin, float* dw, float* dbias, void* scratch, const float* gadd,
+                         void* gln_scratch, int* fused, const float* ax, const srf_norm* anorm, const void* a_scratch,
+                         void* stream, SrfBwdCtx* ctx);
+bool srf_bwd_level0_proj_ok(int L, const void* const* ptrs, int nptrs);
+bool srf_bwd_level0_proj_shape_ok(int L, const void* const* ptrs, int nptrs);
+int srf_bwd_level0_proj(const float* G0, const float* y1, const srf_norm* pn, const srf_norm* n0, const float* w0, const float* b0,
+                        const void* n0_scratch, void* pn_scratch, void* dw_scratch, float* dw, float* dbias, float* gy1,
+                        int groups, int C, int L, void* stream, SrfBwdCtx* ctx);
+int srf_bwd_level1_head(const float* G1, const float* d1, const srf_norm* n1, const void* n1_scratch, const float* y1,
+                        const srf_norm* pn, const srf_norm* n0, const float* w0, const float* b0, const float* w1, const float* gadd,
+                        float* G0, void* n0_scratch, void* dw_scratch, float* dw1, float* db1, int groups, int C, int L,
+                        void* stream, SrfBwdCtx* ctx);

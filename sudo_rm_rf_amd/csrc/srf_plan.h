@@ -1,7 +1,7 @@
 // The plan object behind the opaque srf_plan* of include/sudormrf_hip.h (shared by srf_api.hip and srf_train.hip).
 #pragma once
 #include <vector>
-#include "srf_common.h"
+#include "srf_internal.h"
 
 struct srf_plan {
   srf_config cfg;
@@ -24,3 +24,23 @@ struct srf_plan {
   std::vector<float> alpha, beta;
   size_t off_fold_res, off_fold_proj, off_merged;
 };
+
+// ---- dispatch decisions of a forward.  They depend on the kernel mode and the debug flags at CALL time, so they are
+// functions of the plan, not fields of it.
+
+// split + lay out every 1x1 weight for the 256 x 128 split-precision GEMMs at the start of the forward (kernel mode 0 only;
+// SRF_DBG_NO_PACKED_WEIGHTS = without: the 128 x 128 kernels that split W on the fly)
+static inline bool plan_use_pack(const srf_plan* p) {
+  return srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_NO_PACKED_WEIGHTS) && !p->pk_param.empty();
+}
+// the blocks' depthwise pyramids run as the fused kernels (else: per-level kernels + merge)
+static inline bool plan_fused_pyramid_now(const srf_plan* p) {
+  return p->fused_pyramid && srf_kernel_mode() != 1 && !srf_dbg(SRF_DBG_PYR_PER_LEVEL);
+}
+// K5: mask GEMM and decoder contraction in ONE launch, the masked tensor never reaches memory.  Only where the 256 x 128 GEMM
+// would have run the mask conv anyway (off_wdpack != 0 implies that the mask conv's weight has a packed image).
+static inline bool plan_fused_tail_now(const srf_plan* p, bool use_pack) {
+  const srf_config& c = p->cfg;
+  return p->off_wdpack && use_pack && c.enc_num_basis % 8 == 0 &&
+         srf_mask_decode_supported(p->Bt, c.out_channels, p->SA * c.enc_num_basis, p->L, p->SA * c.enc_kernel_size);
+}

@@ -1,6 +1,6 @@
 // Shared pieces of the pointwise-conv GEMM kernels (srf_pwconv.hip, srf_pwconv_bf16x3.hip).
 #pragma once
-#include "srf_common.h"
+#include "srf_internal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -44,6 +44,20 @@ struct PwPairArgs {
   double* out_sums2;
   int K1, C2, L, Bt, nLt, total;
 };
+
+// ---- launchers of the GEMM files, called by the dispatch in srf_pwconv.hip (the rest of the cross-file surface: srf_internal.h)
+int srf_pw_bf16x3_launch(const PwArgs& a, int pro, hipStream_t st);
+int srf_pw_w4_launch(const PwArgs& a, int pro, hipStream_t st);   // 64 x 64 tiles for small launches (srf_pwconv_w4.hip)
+bool srf_pw_w4_wanted(const PwArgs& a);
+int srf_pw_x3w_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);   // the 256 x 128 kernel (srf_pwconv_x3w.hip)
+int srf_pw_x3p_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);   // its paired-block form (srf_pwconv_x3p.hip)
+bool srf_x3p_supported(const PwArgs& a, int pro);
+int srf_pw_small_launch(const PwArgs& a, hipStream_t st);
+int srf_pw_x3f_launch(const PwPairArgs& a, int pro, hipStream_t st, bool f16 = false);   // the fused pair (srf_pwconv_x3f.hip)
+// K5: mask GEMM + decoder contraction in one launch (srf_pwconv_x3w.hip, EPI 4)
+int srf_pw_x3w_fused_tail_launch(const PwArgs& a, const char* wpack, const char* wdpack, float* zpart, int M, hipStream_t st);
+int srf_pw_x3w3_launch(const PwArgs& a, const char* wpack3, int pro, hipStream_t st);   // three bf16 parts (training forward)
+int srf_pw_x3w4_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);    // two fp16 parts (training forward)
 
 
 // XCD-aware tile numbering: hardware places block id on XCD id%8; give each XCD a contiguous run of

@@ -16,7 +16,6 @@
 // Blocks are numbered so that the M-tiles sharing one X tile run back-to-back on one XCD (L2 reuse).
 // Generic path (any shape, small channel counts): one thread per time step, MT outputs in registers,
 // weights as scalar operands.
-#include "srf_common.h"
 
 #include "srf_pw.h"
 #include <iterator>
@@ -207,14 +206,6 @@ __global__ __launch_bounds__(256) void srf_pw_mfma_kernel(PwArgs a, int nMt, int
   if (a.out_sums) srf_block_stats_atomic<4>((double)s, (double)q, srf_stat_slot(a.out_sums, b, v), red);
 }
 
-int srf_pw_bf16x3_launch(const PwArgs& a, int pro, hipStream_t st);
-int srf_pw_w4_launch(const PwArgs& a, int pro, hipStream_t st);   // 64 x 64 tiles for small launches (srf_pwconv_w4.hip)
-bool srf_pw_w4_wanted(const PwArgs& a);
-int srf_pw_x3w_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);   // the 256 x 128 kernel (srf_pwconv_x3w.hip)
-bool srf_x3w_supported(int Bt, int pro);
-bool srf_x3w_shape_supported(int Cin, int Cout, int L);
-size_t srf_x3w_packed_bytes(int Cout, int Cin);
-int srf_x3w_pack_launch(const float* const* w, char* const* dst, const int* Cout, const int* Cin, int n, hipStream_t st);
 // Round 4: the paired-block form of the 256 x 128 kernel (srf_pwconv_x3p.hip: two co-resident blocks per CU; bit-identical
 // outputs).  In isolation it ties with the one-block kernel on proj_1x1 / bottleneck and loses on res_conv (127 vs 113 us) and
 // in the single-stream training step (+3.5 % / +4.5 % at cfg 2 / cfg 4); INSIDE srf_forward, whose caller runs two sub-batches
@@ -222,32 +213,23 @@ int srf_x3w_pack_launch(const float* const* w, char* const* dst, const int* Cout
 // asks for it (srf_pw_prefer_paired, thread-local, scoped to the call) and every other caller -- srf_pw_conv_packed on its
 // own, the backward's data-gradient GEMMs -- keeps the one-block kernel.  Debug flag 8192 swaps the two choices (A/B, tests).
 // A packed weight buffer holds TWO images: [x3w image | x3p image].
-int srf_pw_x3p_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);
-bool srf_x3p_supported(const PwArgs& a, int pro);
-size_t srf_x3p_packed_bytes(int Cout, int Cin);
-int srf_x3w_pack2_launch(const float* const* w, char* const* dst, char* const* dst16, const int* Cout, const int* Cin, int n,
-                         hipStream_t st);
 static thread_local int g_pw_prefer_paired = 0;
 void srf_pw_prefer_paired(bool on) { g_pw_prefer_paired = on ? 1 : 0; }      // (srf_forward: around its launches)
 static bool srf_pw_paired_wanted() { return g_pw_prefer_paired != 0; }
 static int srf_pw_256_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st) {
   const char* wpack_p = wpack + srf_x3w_packed_bytes(a.Cout, a.Cin);
-  const bool paired = srf_pw_paired_wanted() != ((srf_debug_flags() & 8192) != 0);
+  const bool paired = srf_pw_paired_wanted() != srf_dbg(SRF_DBG_GEMM_256_SWAP_FORMS);
   if (paired && srf_x3p_supported(a, pro)) return srf_pw_x3p_launch(a, wpack_p, pro, st);
   return srf_pw_x3w_launch(a, wpack, pro, st);
 }
-int srf_pw_small_launch(const PwArgs& a, hipStream_t st);
-bool srf_pw_small_supported(int Cin, int Cout, int L);
 
 // Round 5: two 1x1 convolutions back to back in one launch, the intermediate handed over in registers (srf_pwconv_x3f.hip):
 // res_conv (or the bottleneck) and the proj_1x1 that consumes its output.  Both weights come as packed buffers of
 // srf_pack_pw_weights; the kernel streams their paired-block images.
-bool srf_x3f_supported(int Bt, int K1, int C2, int L);
-int srf_pw_x3f_launch(const PwPairArgs& a, int pro, hipStream_t st, bool f16 = false);
 // Whether the fused pair serves (Bt, Cin1 -> 256 -> Cout2, L): the kernel's shape limits, the default kernel mode, and a launch
 // that fills the chip (fewer 128-column tiles than CUs: the separate launches' small-launch kernels do better).
 static bool srf_pw_pair_shape_ok(int Bt, int Cin1, int Cmid, int Cout2, int L) {      // (whatever the kernel mode)
-  if (srf_debug_flags() & (1 | 4 | 8)) return false;
+  if (srf_dbg(SRF_DBG_NO_PAIRS | SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS)) return false;
   if (Cmid != 256 || !srf_x3f_supported(Bt, Cin1, Cout2, L)) return false;
   if (!srf_x3w_shape_supported(Cin1, Cmid, L) || !srf_x3w_shape_supported(Cmid, Cout2, L)) return false;
   return (long)Bt * ((L + 127) / 128) >= srf_device_cus();
@@ -291,7 +273,7 @@ extern "C" int srf_pw_conv_pair(const float* x, const void* w1_packed, const flo
 // THE predicate of the 256 x 128 dispatch for a whole launch (srf_pw_conv_packed, srf_pw_conv_packed3 and srf_pw_packed_only all
 // use it -- ADVICE r3: the backward's "the fp32 weight is never read" shortcut was a hand-written copy of the dispatch test).
 static bool srf_pw_256_serves(const void* w_packed, const float* x, int Bt, int Cin, int Cout, int L, int pro) {
-  if (!w_packed || srf_kernel_mode() != 0 || (srf_debug_flags() & 4)) return false;
+  if (!w_packed || srf_kernel_mode() != 0 || srf_dbg(SRF_DBG_NO_GEMM_256)) return false;
   if ((Cin % PW_BK) || (L % 4) || Cout < 32 || Cin < 32 || !srf_aligned16(x) || !srf_aligned16(w_packed)) return false;
   if (!srf_x3w_shape_supported(Cin, Cout, L) || !srf_x3w_supported(Bt, pro)) return false;
   if ((long)Bt * Cin * L * 4 >= (1L << 31)) return false;      // (beyond the 32-bit buffer range: the chunked form decides per chunk)
@@ -299,15 +281,11 @@ static bool srf_pw_256_serves(const void* w_packed, const float* x, int Bt, int 
 }
 
 // ---- K5 (library-internal; srf_forward's tail): mask GEMM + decoder contraction in one launch (srf_pwconv_x3w.hip, EPI 4)
-int srf_pw_x3w_fused_tail_launch(const PwArgs& a, const char* wpack, const char* wdpack, float* zpart, int M, hipStream_t st);
-size_t srf_x3w_dec_pack_bytes(int Ci);
-int srf_x3w_pack_dec_launch(const float* w, void* dst, int Ci, int M, hipStream_t st);
-
 // Whether srf_forward may run its tail fused: the shapes the round-3 256 x 128 kernel is dispatched for (same test as in
 // srf_pw_conv_packed) and a decoder of at most 64 frame rows (sources x taps: 42 for the reference's 2 x 21).
 // Debug flag 32768 = without (the masked tensor is then materialised: srf_debug_fetch(2), A/B).
 bool srf_mask_decode_supported(int Bt, int Cin, int Cout, int L, int M) {
-  if (srf_kernel_mode() != 0 || (srf_debug_flags() & (4 | 8 | 32768))) return false;
+  if (srf_kernel_mode() != 0 || srf_dbg(SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS | SRF_DBG_NO_FUSED_TAIL)) return false;
   if (M <= 0 || M > 64 || Cout % 8 || Cin % PW_BK || L % 4 || !srf_x3w_shape_supported(Cin, Cout, L) || !srf_x3w_supported(Bt, 3)) return false;
   if ((long)Bt * Cin * L * 4 >= (1L << 31)) return false;
   return (long)Bt * ((Cout + 255) / 256) * ((L + 127) / 128) >= srf_device_cus();
@@ -347,10 +325,6 @@ int srf_mask_decode(const float* x, const float* w, const void* w_packed, const 
 
 // ---- three-part split GEMM (six bf16 MFMAs per product block: the exact-fp32 class at ~1.6 x the 3-MFMA kernel's time instead
 // of the exact-fp32 MFMA kernel's 2.5 x) -- the training forward's 1x1 convolutions (srf_forward_train) ----------------------
-int srf_pw_x3w3_launch(const PwArgs& a, const char* wpack3, int pro, hipStream_t st);
-int srf_pw_x3w4_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);
-int srf_x3w_pack_f16_launch(const float* const* w, char* const* dst, const int* Cout, const int* Cin, int n, hipStream_t st,
-                            char* const* dst16);
 // The training forward's GEMMs run on TWO fp16 parts per operand (hi = fp16(x), lo = fp16(x - hi): 22 mantissa bits, 3 MFMAs per
 // product block -- round 4) unless debug flag 16384 selects round 3's three bf16 parts (24 bits, 6 MFMAs).
 // Measured (tools/f16_split_probe.py -> profiles/r04_f16_split_probe.txt): error against fp64 on a model-sized GEMM 2.6e-6 --
@@ -361,7 +335,7 @@ int srf_x3w_pack_f16_launch(const float* const* w, char* const* dst, const int* 
 // we have; an operand beyond the range (or NaN / inf) makes its output column non-finite -- loud, like the fp32 reference's own
 // overflow, not clamped (round 5) -- and flag 16384 (three bf16 parts) is the form without the limit.
 // The packed3 buffer then holds the fp16 image (half its size).
-static bool srf_train_f16_split() { return (srf_debug_flags() & 16384) == 0; }
+static bool srf_train_f16_split() { return !srf_dbg(SRF_DBG_TRAIN_BF16X3); }
 // The two image formats differ in layout and size, and which one a buffer holds is decided at PACK time: every
 // buffer srf_pack3_pw_weights has written is remembered with its format (device, address), and a launch whose flag disagrees
 // with the buffer it is handed is refused with SRF_EINVAL instead of reinterpreting the bits.  (A buffer this process never
@@ -395,8 +369,6 @@ extern "C" void srf_pack3_forget(const void* packed) {
   std::lock_guard<std::mutex> lk(g_pk3_mu);
   g_pk3_format.erase(srf_pk3_key(packed));
 }
-size_t srf_x3w_packed3_bytes(int Cout, int Cin);
-int srf_x3w_pack3_launch(const float* const* w, char* const* dst, const int* Cout, const int* Cin, int n, hipStream_t st);
 
 extern "C" size_t srf_packed3_pw_weight_bytes(int Cout, int Cin) {
   if (Cout <= 0 || Cin <= 0 || !srf_x3w_shape_supported(Cin, Cout, 4)) return 0;
@@ -439,7 +411,7 @@ extern "C" int srf_pw_conv_packed3(const float* x, const float* w, const void* w
                   (srf_kernel_mode() == 0 ? srf_pw_256_serves(w_packed3, x, Bt, Cin, Cout, L, pro)
                                           : (w_packed3 && srf_x3w_shape_supported(Cin, Cout, L) && srf_x3w_supported(Bt, pro) &&
                                              srf_aligned16(x) && srf_aligned16(w_packed3) && (long)Bt * Cin * L * 4 < (1L << 31) &&
-                                             !(srf_debug_flags() & 4) &&
+                                             !srf_dbg(SRF_DBG_NO_GEMM_256) &&
                                              (long)Bt * ((Cout + 255) / 256) * ((L + 127) / 128) >= srf_device_cus()));
   if (!ok) return srf_pw_conv(x, w, bias, y, Bt, Cin, Cout, L, in_norm, residual, out_sums, 0, nullptr, 0, stream);
   if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_pw_conv: norm without gamma/beta");
@@ -654,7 +626,7 @@ extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_
   // floats = 3.4 GB) goes out as several launches over runs of whole examples: examples are independent, every per-example
   // pointer (statistics slots included) just moves along.
   if (mfma_ok && mode == 0 && w_packed && srf_x3w_shape_supported(Cin, Cout, L) && srf_x3w_supported(Bt, pro_sel) && srf_aligned16(w_packed) &&
-      (long)Bt * Cin * L * 4 >= (1L << 31) && (long)Cin * L * 4 < (1L << 31) && !(srf_debug_flags() & 4)) {
+      (long)Bt * Cin * L * 4 >= (1L << 31) && (long)Cin * L * 4 < (1L << 31) && !srf_dbg(SRF_DBG_NO_GEMM_256)) {
     const int cap = (int)(((1L << 31) - 1) / ((long)Cin * L * 4));   // examples one launch can address
     const int nch = (Bt + cap - 1) / cap, per = (Bt + nch - 1) / nch;  // balanced runs of whole examples
     const int last = Bt - (nch - 1) * per;

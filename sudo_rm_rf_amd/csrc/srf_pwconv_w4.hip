@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256, 4) void srf_pw_w4_kernel(PwArgs a, int nMt, in
 // 37 vs 30 us.  Hence: at most one 128 x 128 tile per two CUs.  Debug flag 2048 (the one-tile-per-block 128 x 128 kernel
 // everywhere) switches it off for A/B.
 bool srf_pw_w4_wanted(const PwArgs& a) {
-  if (srf_debug_flags() & 2048) return false;
+  if (srf_dbg(SRF_DBG_GEMM_128_ONE_TILE_PER_BLOCK)) return false;
   if (a.Cin % 64 || a.L % 4 || (long)a.Bt * a.Cin * a.L * 4 >= (1L << 31) || (long)a.Cout * a.Cin * 4 >= (1L << 31)) return false;
   const long tiles128 = (long)a.Bt * ((a.Cout + 127) / 128) * ((a.L + 127) / 128);
   return 2 * tiles128 <= srf_device_cus();

@@ -737,7 +737,7 @@ static int wg_small_blocks(int Bt, int M, int N, int L) {
   // 3-5 were 1.33 rounds at the GroupComm shapes (3 blocks of 50 KB per CU = 768 slots): the last third of the pieces ran on a third
   // of the chip.  (Debug flag 1 << 18: 1024.)
   long slots = 1024;
-  if (!(srf_debug_flags() & (1 << 18))) {
+  if (!srf_dbg(SRF_DBG_WGRAD_NO_WIDE_TILE)) {
     long per_cu = (long)(160 * 1024 / wg_small_lds(M, N));
     per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
     slots = per_cu * srf_device_cus();
@@ -921,12 +921,12 @@ static void wg_geometry(int M, int N, int L, int Bt, WgArgs* a) {
   if (a->kc_len > L) a->kc_len = (L + 31) / 32 * 32;
   a->nKc = (L + a->kc_len - 1) / a->kc_len;
   a->P = wg_pick_partials(a->nMt * a->nNt, Bt * a->nKc);
-  a->xcd_map = (a->P % 8 == 0 && !(srf_debug_flags() & 4096)) ? 1 : 0;
+  a->xcd_map = (a->P % 8 == 0 && !srf_dbg(SRF_DBG_WGRAD_NO_XCD_MAP)) ? 1 : 0;
 }
 
 // The wide tile (srf_pw_wgrad_wide_kernel): 1 = 256 x 128, 2 = 128 x 256, 0 = not for this shape.  (Debug flag 1 << 18: never -- A/B.)
 static int wg_wide_form(int M, int N, int L) {
-  if (L % WG_BK || srf_kernel_mode() == 1 || (srf_debug_flags() & (1 << 18))) return 0;
+  if (L % WG_BK || srf_kernel_mode() == 1 || srf_dbg(SRF_DBG_WGRAD_NO_WIDE_TILE)) return 0;
   if (M % 256 == 0 && N % 128 == 0) return 1;
   if (M % 128 == 0 && N % 256 == 0) return 2;
   return 0;
@@ -951,7 +951,7 @@ static void wg_geometry_wide(int form, int M, int N, int L, int Bt, WgArgs* a) {
   // k chunks per block -> one chunk k times as long where the time chunks divide evenly: one pipeline fill per block instead of k
   // (cfg 2: 2 x 25 k-tiles -> 1 x 50)
   const int k = nchunks / a->P;
-  if (k >= 2 && nchunks % a->P == 0 && a->nKc % k == 0 && L % (a->kc_len * k) == 0 && !(srf_debug_flags() & (1 << 20))) {
+  if (k >= 2 && nchunks % a->P == 0 && a->nKc % k == 0 && L % (a->kc_len * k) == 0 && !srf_dbg(SRF_DBG_WGRAD_SHORT_CHUNKS)) {
     a->kc_len *= k;
     a->nKc /= k;
   }
@@ -1052,7 +1052,7 @@ extern "C" int srf_pw_wgrad_ld(const float* g, const float* x, const srf_norm* i
   } else {
   dim3 grid((unsigned)(a.nMt * a.nNt * a.P)), block(512);
   // (debug flag 1 << 19: the masked form for full shapes too -- A/B)
-  const bool full = Cout % WG_BM == 0 && Cin % WG_BN == 0 && L % WG_BK == 0 && a.kc_len % WG_BK == 0 && !(srf_debug_flags() & (1 << 19));
+  const bool full = Cout % WG_BM == 0 && Cin % WG_BN == 0 && L % WG_BK == 0 && a.kc_len % WG_BK == 0 && !srf_dbg(SRF_DBG_WGRAD_128_MASKED);
 #define WG_GO(P_) \
   if (full) hipLaunchKernelGGL((srf_pw_wgrad_kernel<P_, true>), grid, block, 0, st, a); \
   else hipLaunchKernelGGL((srf_pw_wgrad_kernel<P_, false>), grid, block, 0, st, a)
@@ -1069,7 +1069,7 @@ extern "C" int srf_pw_wgrad_ld(const float* g, const float* x, const srf_norm* i
   if (dbias && !(a.P >= 64 && (long)Cout * dw_cols * 4 <= 65536)) {   // (large outputs: no partial split, one launch for both)
     const bool p4 = (Cin % 4 == 0) && (dw_cols % 4 == 0) && srf_aligned16(a.part);      // float4 reads of the partials
     const bool v4 = p4 && (dw_ld % 4 == 0) && srf_aligned16(dw);                          // ... and float4 stores of the result
-    const bool four_groups = p4 && a.P >= 16 && !(srf_debug_flags() & (1 << 25));        // (debug flag 1 << 25: the one-chain fold, A/B)
+    const bool four_groups = p4 && a.P >= 16 && !srf_dbg(SRF_DBG_WGRAD_ONE_CHAIN_FOLD);        // (debug flag 1 << 25: the one-chain fold, A/B)
     const long n = (long)Cout * (dw_cols / ((v4 || four_groups) ? 4 : 1)) + Cout;
     if (four_groups) {
       if (v4)

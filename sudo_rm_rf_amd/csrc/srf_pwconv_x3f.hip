@@ -610,7 +610,7 @@ int srf_pw_x3f_launch(const PwPairArgs& a0, int pro, hipStream_t st, bool f16) {
   const long total = (long)a.Bt * a.nLt;
   SRF_CHECK_ARG(total < (1L << 30), "srf_pw_conv_pair: too many tiles");
   a.total = (int)total;
-  const bool drain = (srf_debug_flags() & (1 << 23)) != 0;
+  const bool drain = srf_dbg(SRF_DBG_PAIR_FULL_DRAIN);
   const long ok = srf_device_cached(7, [](void*) -> long {
     bool good = true;
     const void* fns[] = {(const void*)&srf_pw_x3f_kernel<1, 0, false>, (const void*)&srf_pw_x3f_kernel<2, 1, false>,
@@ -626,7 +626,7 @@ int srf_pw_x3f_launch(const PwPairArgs& a0, int pro, hipStream_t st, bool f16) {
   // are left: with one tile per block the dispatcher hands the next tile to whichever slot frees first (cfg 2: 800 tiles on 512
   // slots = 1.56 rounds instead of the 2 full rounds of a static split).
   const long slots = 2L * srf_device_cus();
-  long nb = total <= 16 * slots && !(srf_debug_flags() & (1 << 21)) ? total : slots - slots % 8;   // (flag 1 << 21: always persistent -- tests)
+  long nb = total <= 16 * slots && !srf_dbg(SRF_DBG_PAIR_PERSISTENT) ? total : slots - slots % 8;   // (flag 1 << 21: always persistent -- tests)
   if (nb > total) nb = total;
   dim3 grid((unsigned)nb), block(256);
 #define F_GO(...) hipLaunchKernelGGL((srf_pw_x3f_kernel<__VA_ARGS__>), grid, block, F_LDS_BYTES, st, a, a.nrm.gamma, a.nrm.beta)

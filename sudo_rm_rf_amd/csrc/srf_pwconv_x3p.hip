@@ -409,9 +409,9 @@ int srf_pw_x3p_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t s
   dim3 grid((unsigned)nb), block(512);
   const bool res = a.residual != nullptr;
 #define P_GO(...) hipLaunchKernelGGL((srf_pw_x3p_kernel<__VA_ARGS__>), grid, block, P_LDS_BYTES, st, a, wpack, nMt, nLt, (int)total, a.nrm.gamma, a.nrm.beta, a.bias)
-  if (pro == 1 && !res && !(srf_debug_flags() & 2)) {
+  if (pro == 1 && !res && !srf_dbg(SRF_DBG_GEMM_NO_MGROUPS)) {
     P_GO(1, 0, 4);                // bottleneck
-  } else if (pro == 2 && res && !(srf_debug_flags() & 2)) {
+  } else if (pro == 2 && res && !srf_dbg(SRF_DBG_GEMM_NO_MGROUPS)) {
     P_GO(2, 1, 4);                // res_conv (debug flag 2: the plain cache policy)
   } else if (!res) {
     switch (pro) {

@@ -1087,14 +1087,14 @@ static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, co
   if (nb < 8) nb = 8;
   if (nb > total) nb = total - total % 8;   // (the tile cursors need nb % 8 == 0; the host dispatches this kernel for total >= #CUs)
   SRF_CHECK_ARG(nb >= 8, "srf_pw_conv: too few tiles for the 256 x 128 kernel");
-  const int rounds = (srf_debug_flags() & 256) ? (int)((total + nb - 1) / nb) : (int)(total / nb);
+  const int rounds = srf_dbg(SRF_DBG_GEMM_WHOLE_TAIL_TILES) ? (int)((total + nb - 1) / nb) : (int)(total / nb);
   // m-tile groups (see the tile cursors): as many m-tiles as keep their packed weight slabs (256 x Cin x 4 B each) within half
   // of an XCD's 4-MB L2, when the whole weight image does not fit it.  Debug flag 2 (the round-2 kernel's fragment-read order,
   // unused by this kernel) = one group = the round-2 tile order, for A/B.
   int mgrp = nMt;
   {
     const long slab = (long)W_BM * a.Cin * 4 * (np == 3 ? 2 : 1), image = slab * nMt;
-    if (image > (3L << 20) && !(srf_debug_flags() & 2)) {
+    if (image > (3L << 20) && !srf_dbg(SRF_DBG_GEMM_NO_MGROUPS)) {
       int g = (int)((2L << 20) / slab);
       while (g > 1 && nMt % g) --g;
       if (g >= 1 && g < nMt) mgrp = g;
@@ -1102,7 +1102,7 @@ static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, co
   }
   dim3 grid((unsigned)nb), block(512);
   PwArgs ap = a;
-  if (!(srf_debug_flags() & 512)) ap.epi_mask |= 1 << 12;   // quarter tiles first (flag 512: last)
+  if (!srf_dbg(SRF_DBG_GEMM_QUARTER_TILES_LAST)) ap.epi_mask |= 1 << 12;   // quarter tiles first (flag 512: last)
   const bool res = a.residual != nullptr, mask = !res && (a.epi_mask & 1);
 #define W_GO(P, E, C) hipLaunchKernelGGL((srf_pw_x3w_kernel<P, E, C>), grid, block, lds, st, ap, wpack, nMt, nLt, (int)total, rounds, a.nrm.gamma, a.nrm.beta, a.bias, fuse_wd, fuse_z, fuse_M, mgrp)
   // Cache policy (CP) of the four model forms: bit 0 = non-temporal output stores, bit 2 = non-temporal activation loads,

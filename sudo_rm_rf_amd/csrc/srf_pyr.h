@@ -1,6 +1,6 @@
 // Arguments of the register-resident pyramid kernels (srf_pyramid_reg.hip), filled by srf_pyramid() (srf_pyramid.hip).
 #pragma once
-#include "srf_common.h"
+#include "srf_internal.h"
 
 struct PyrRegArgs {
   const float* y1;     // pass 1 input
@@ -24,5 +24,4 @@ struct PyrRegArgs {
                        // re-computes d_0 from y1)
 };
 
-bool srf_pyramid_reg_supported(int L, int D);
 int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st);

@@ -22,7 +22,7 @@
 // One 256-thread block per row; the row's levels live in LDS ([0..3] and [L_k+4..L_k+7] are physical
 // zero pads so that taps never need masks).  Requires L % (4 * 2^(D-1)) == 0 and L >> (D-1) >= 8;
 // otherwise srf_forward falls back to the per-level kernels (srf_dwconv.hip).
-#include "srf_common.h"
+#include "srf_pyr.h"   // arguments of the register-resident kernels (srf_pyramid_reg.hip)
 
 struct PyrArgs {
   const float* y1;
@@ -756,11 +756,10 @@ static void srf_pyramid_finalize_launch(const PyrFinArgs& f, int groups, int C, 
     hipLaunchKernelGGL((srf_pyramid_finalize_kernel<SRF_FIN_CPT>), dim3((unsigned)groups), dim3(256), 0, st, f);
 }
 
-bool srf_pyramid_reg_supported(int L, int D);
 extern "C" int srf_pyramid_supported(int C, int L, int D) {
   if (D < 1 || D > SRF_MAX_DEPTH || C > 256 * SRF_FIN_CPT) return 0;
   if ((L >> (D - 1)) < 8 || (L % (1 << (D - 1))) != 0) return 0;   // finalize needs distinct edge positions
-  if (!(srf_debug_flags() & 64) && srf_pyramid_reg_supported(L, D)) return 1;   // register-resident kernels
+  if (!srf_dbg(SRF_DBG_PYR_NO_REG) && srf_pyramid_reg_supported(L, D)) return 1;   // register-resident kernels
   if (L % (4 << (D - 1)) != 0) return 0;                              // LDS kernels work on float4 groups
   return pyr_lds_bytes(L, D) <= 160 * 1024 - 1024;
 }
@@ -807,9 +806,6 @@ static bool pyr_pick_tile(int L, int D, PyrTile* t) {
   t->wave_floats = len0 + ((lenA + 3) & ~3) + 8 * SRF_MAX_DEPTH;   // + coefficient table
   return (size_t)t->wave_floats * 4 * sizeof(float) <= 64 * 1024;
 }
-
-// register-resident kernels (srf_pyramid_reg.hip)
-#include "srf_pyr.h"
 
 
 // lv_out / lv_sums (both or neither; register-resident kernels only -- srf_pyramid_reg_supported): the training
@@ -873,9 +869,9 @@ int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, co
   f.L = L;
   f.D = D;
   for (int k = 0; k < SRF_MAX_DEPTH; ++k) f.lv_sums[k] = (lv_sums && k < D) ? lv_sums[k] : nullptr;
-  SRF_CHECK_ARG(!lv_out || (!(srf_debug_flags() & (64 | 128)) && srf_pyramid_reg_supported(L, D)),
+  SRF_CHECK_ARG(!lv_out || (!srf_dbg(SRF_DBG_PYR_NO_REG | SRF_DBG_PYR_PASS1_NONPERSISTENT) && srf_pyramid_reg_supported(L, D)),
                 "srf_pyramid: level outputs need the register-resident kernels");
-  if (!(srf_debug_flags() & 64) && srf_pyramid_reg_supported(L, D)) {
+  if (!srf_dbg(SRF_DBG_PYR_NO_REG) && srf_pyramid_reg_supported(L, D)) {
     PyrRegArgs r;
     for (int k = 0; k < SRF_MAX_DEPTH; ++k) r.lv_out[k] = (lv_out && k < D) ? lv_out[k] : nullptr;
     r.save = lv_out != nullptr;
@@ -899,7 +895,7 @@ int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, co
     r.D = D;
     r.rows = r.rpw = 0;
     r.tiles = r.own = 0;
-    if (srf_debug_flags() & 128) {   // non-persistent pass 1: atomics into mom + pre-finalised statistics
+    if (srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT)) {   // non-persistent pass 1: atomics into mom + pre-finalised statistics
       SRF_CHECK_HIP(hipMemsetAsync(mom, 0, sizeof(double) * (size_t)rows * D * 5, st));
       if (a.in_norm.sums) {
         hipLaunchKernelGGL(srf_stats_finalize_kernel, dim3((unsigned)groups), dim3(64), 0, st, a.in_norm.sums,
@@ -910,13 +906,13 @@ int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, co
     SRF_CHECK_ARG(merged != y1, "srf_pyramid: merged must not alias y1 (pass 2 re-reads y1 with halos)");
     int rc = srf_pyramid_reg_launch(r, true, rows, st);
     if (rc) return rc;
-    if (!(srf_debug_flags() & 128)) f.in_sums = a.in_norm.sums;
+    if (!srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT)) f.in_sums = a.in_norm.sums;
     srf_pyramid_finalize_launch(f, groups, C, st);
     SRF_CHECK_LAUNCH("pyramid_finalize", st);
     return srf_pyramid_reg_launch(r, false, rows, st);
   }
   PyrTile tile;
-  if (!(srf_debug_flags() & 32) && pyr_pick_tile(L, D, &tile)) {
+  if (!srf_dbg(SRF_DBG_PYR_NO_LDS_TILES) && pyr_pick_tile(L, D, &tile)) {
     tile.tasks = rows * tile.tiles;
     const size_t tl = (size_t)tile.wave_floats * 4 * sizeof(float);
     const unsigned nb = (unsigned)((tile.tasks + 3) / 4);

@@ -440,7 +440,7 @@ int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st
   SRF_CHECK_ARG(rows * a.tiles < (1L << 31) && rows / a.C <= 65535, "srf_pyramid: too many rows");
   a.rows = (int)rows;
   // pass 1 persistent (grid = co-resident wavefronts, cached occupancy query) unless debug flag 128
-  const bool persist = moments && !(srf_debug_flags() & 128);
+  const bool persist = moments && !srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT);
   // co-resident wavefronts of the persistent pass 1 on THIS device (per-device cache, srf_common.h)
   long cw = 0;
   if (persist) {
@@ -461,7 +461,7 @@ int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st
     // 5.3 blocks per CU); pass 1 is bound by the loads it has in flight, not by its VALU count (profiles/r06_pyramid_pass1_*):
     // 1 / 2 / 3 / 4 rows per wave = 54.5 / 55.5 / 61 / 62.8 us at cfg 2, same box.  Debug flag 1 << 17: the old sizing.
     long nwaves = cw < rows ? cw : rows;
-    a.rpw = (srf_debug_flags() & (1 << 17)) ? (int)((rows + nwaves - 1) / nwaves) : 1;   // whole rows per wave
+    a.rpw = srf_dbg(SRF_DBG_PYR_PASS1_ROWS_PER_WAVE) ? (int)((rows + nwaves - 1) / nwaves) : 1;   // whole rows per wave
     nwaves = (rows + a.rpw - 1) / a.rpw;
     grid = dim3((unsigned)((nwaves + 3) / 4));
   } else {

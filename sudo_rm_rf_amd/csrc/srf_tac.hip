@@ -314,13 +314,13 @@ __global__ __launch_bounds__(256) void srf_tac_lanes_kernel(
 template <int NN, int G>
 static void srf_tac_lanes_go(const TacArgs& a, int Bt, hipStream_t st) {
   constexpr int CW = 64 / G;
-  const int TW = (a.L % 2 == 0 && !(srf_debug_flags() & 1024)) ? 2 : 1;   // debug flag 1024: one time step per lane
+  const int TW = (a.L % 2 == 0 && !srf_dbg(SRF_DBG_TAC_ONE_STEP_PER_LANE)) ? 2 : 1;   // debug flag 1024: one time step per lane
   const int tiles = (a.L + 4 * CW * TW - 1) / (4 * CW * TW);   // block-tiles (4 wavefronts x CW*TW columns) per row
   // enough blocks to keep >= ~8 per CU in flight, otherwise fold tiles into one block (fewer atomics,
   // weight staging amortised)
   int tpb = 1;
   while (tpb < 8 && (long)Bt * (tiles / (tpb * 2)) >= 8 * 256) tpb *= 2;
-  if (srf_debug_flags() & (1 << 26)) tpb = 4;      // (tests: the several-tiles-per-block path at small sizes)
+  if (srf_dbg(SRF_DBG_TAC_LANES_4TILES)) tpb = 4;      // (tests: the several-tiles-per-block path at small sizes)
   dim3 grid((tiles + tpb - 1) / tpb, Bt), block(256);
   if (TW == 2)
     hipLaunchKernelGGL((srf_tac_lanes_kernel<NN, G, 2>), grid, block, 0, st, a, tpb, a.wi, a.bi, a.wo, a.bo);
@@ -618,7 +618,7 @@ extern "C" int srf_tac(const float* x, float* q, const float* const* params, int
   hipStream_t st = (hipStream_t)stream;
   // debug flags 1 << 22 / 24 / 25 / 26, 1024: the VALU kernels (the MFMA form serves n = 16, G = 16; 1 << 22 = just not the MFMA form)
   // (the MFMA form moves x and q with 16-byte buffer accesses: float-aligned bases take the VALU kernels)
-  if (srf_kernel_mode() != 1 && n == 16 && G == 16 && !(srf_debug_flags() & ((1 << 22) | (1 << 24) | (1 << 26) | 1024)) &&
+  if (srf_kernel_mode() != 1 && n == 16 && G == 16 && !srf_dbg(SRF_DBG_TAC_ONE_STEP_PER_LANE | SRF_DBG_TAC_VALU | SRF_DBG_TAC_GENERIC | SRF_DBG_TAC_LANES_4TILES) &&
       (long)G * n * L * 4 < (1L << 31) && srf_aligned16(x) && srf_aligned16(q)) {
     const int tiles_per_row = (L + 31) / 32;
     const long total = (long)Bt * tiles_per_row;
@@ -629,7 +629,7 @@ extern "C" int srf_tac(const float* x, float* q, const float* const* params, int
       return SRF_OK;
     }
   }
-  if (srf_kernel_mode() != 1 && !(srf_debug_flags() & (1 << 24)) && srf_tac_lanes_launch(a, n, Bt, st)) {
+  if (srf_kernel_mode() != 1 && !srf_dbg(SRF_DBG_TAC_GENERIC) && srf_tac_lanes_launch(a, n, Bt, st)) {
     SRF_CHECK_LAUNCH("tac", st);
     return SRF_OK;
   }
@@ -646,10 +646,6 @@ extern "C" int srf_tac(const float* x, float* q, const float* const* params, int
   SRF_CHECK_LAUNCH("tac", st);
   return SRF_OK;
 }
-
-extern "C" int srf_pw_wgrad_ld(const float* g, const float* x, const srf_norm* in_norm, int Bt, int Cin, int Cout, int L,
-                               float* dw, int dw_cols, int dw_ld, float* dbias, int accumulate, void* scratch,
-                               void* stream);
 
 __global__ void srf_tac_slope_add_kernel(const float* __restrict__ d, float* gi, float* gm, float* go) {
   if (threadIdx.x == 0) {
@@ -1393,7 +1389,7 @@ extern "C" int srf_tac_bwd(const float* x, const float* go, const float* const* 
   SRF_CHECK_HIP(hipMemsetAsync(a.dslope, 0, 3 * sizeof(float), st));
   bool ok = false, mfma = false;
   // debug flag 1 << 22: the VALU kernel (the MFMA form serves n = 16, G = 16)
-  if (srf_kernel_mode() != 1 && n == 16 && G == 16 && !(srf_debug_flags() & (1 << 22)) && (long)G * H * L * 4 < (1L << 31) &&
+  if (srf_kernel_mode() != 1 && n == 16 && G == 16 && !srf_dbg(SRF_DBG_TAC_VALU) && (long)G * H * L * 4 < (1L << 31) &&
       (long)Bt * ((L + 31) / 32) < (1L << 30)) {
     const int tiles_per_row = (L + 31) / 32;
     const long total = (long)Bt * tiles_per_row;

@@ -19,55 +19,6 @@
 
 #include "srf_plan.h"
 
-int srf_transpose_launch(const float* w, float* wt, int Ci, int M, hipStream_t st);
-int srf_accumulate_launch(float* dst, const float* src, long n, hipStream_t st);
-// srf_backward.hip: what one srf_backward call carries across its kernel-level calls -- the deferred parameter-gradient
-// reductions and the "merge backward rides on the next GlobLN apply" request (an explicit object; NULL = neither)
-struct SrfBwdCtx;
-SrfBwdCtx* srf_bwd_ctx_new();
-void srf_bwd_ctx_free(SrfBwdCtx* c);
-void srf_bwd_ctx_defer(SrfBwdCtx* c, bool on);
-void srf_bwd_ctx_merge_sink(SrfBwdCtx* c, float* const* levels, int D);
-bool srf_bwd_ctx_merge_taken(const SrfBwdCtx* c);
-int srf_bwd_ctx_flush(SrfBwdCtx* c, hipStream_t st);
-int srf_gln_bwd_impl(const float* gout, const float* gout2, const float* x, const srf_norm* norm, int groups, int C,
-                     int L, float* gx, int accumulate_gx, float* dgamma, float* dbeta, float* dslope, void* scratch,
-                     int mode, void* stream, SrfBwdCtx* ctx);
-bool srf_dwconv5_bwd_rowwise_ok(int Lin, int stride, const void* const* ptrs, int nptrs);
-bool srf_pyramid_reg_supported(int L, int D);
-int srf_pack_pw_weights_transposed(const float* const* w, void* const* packed, const int* Cout, const int* Cin, int n,
-                                   hipStream_t st);   // srf_pwconv.hip
-bool srf_pw_packed_only(const void* w_packed, const float* x, int Bt, int Cin, int Cout, int L);   // srf_pwconv.hip
-extern "C" size_t srf_packed3_pw_weight_bytes(int Cout, int Cin);
-extern "C" int srf_pack3_pw_weights(const float* const* w, void* const* packed, const int* Cout, const int* Cin, int n, void* stream);
-extern "C" int srf_pw_conv_packed3(const float* x, const float* w, const void* w_packed3, const float* bias, float* y, int Bt,
-                                   int Cin, int Cout, int L, const srf_norm* in_norm, const float* residual, double* out_sums,
-                                   void* stream);
-bool srf_pw_conv_preadd_supported(int Cin, int Cout, int L, const void* const* ptrs, int nptrs);
-int srf_pw_conv_preadd(const float* x, const float* q, const srf_norm* qnorm, float* u, const float* w, const float* bias,
-                       float* y, int Bt, int Cin, int Cout, int L, double* out_sums, hipStream_t st);
-int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
-                     const float* const* bias, const float* const* gamma, const float* const* beta, int groups, int C,
-                     int L, int D, void* scratch, double* out_sums, float* const* lv_out, double* const* lv_sums,
-                     void* stream);
-int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_norm, const float* w, int groups, int C,
-                         int Lin, int stride, float* gin, float* dw, float* dbias, void* scratch, const float* gadd,
-                         void* gln_scratch, int* fused, const float* ax, const srf_norm* anorm, const void* a_scratch,
-                         void* stream, SrfBwdCtx* ctx);
-
-bool srf_bwd_level0_proj_ok(int L, const void* const* ptrs, int nptrs);
-bool srf_bwd_level0_proj_shape_ok(int L, const void* const* ptrs, int nptrs);
-int srf_bwd_level0_proj(const float* G0, const float* y1, const srf_norm* pn, const srf_norm* n0, const float* w0, const float* b0,
-                        const void* n0_scratch, void* pn_scratch, void* dw_scratch, float* dw, float* dbias, float* gy1,
-                        int groups, int C, int L, void* stream, SrfBwdCtx* ctx);
-
-int srf_bwd_level1_head(const float* G1, const float* d1, const srf_norm* n1, const void* n1_scratch, const float* y1,
-                        const srf_norm* pn, const srf_norm* n0, const float* w0, const float* b0, const float* w1, const float* gadd,
-                        float* G0, void* n0_scratch, void* dw_scratch, float* dw1, float* db1, int groups, int C, int L,
-                        void* stream, SrfBwdCtx* ctx);
-
-static size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
 // Round 6: levels 1 and 0 of a block's pyramid backward and proj_1x1's norm backward run on the fused-head kernels
 // (srf_backward.hip: srf_bwd_l1h_kernel, srf_bwd_l0p_kernel), which re-compute d_0 from y1 -- so srf_forward_train does not WRITE
 // d_0 either.  The forward decides from the plan, the kernel mode and the debug flags, and RECORDS what it did (below); the
@@ -136,18 +87,18 @@ static TrainLayout train_layout(const srf_plan* p) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
-    off = al256(off + bytes);
+    off = srf_align_up(off + bytes, 256);
     return o;
   };
   t.stats = take(p->stats_bytes);
   t.enc = take(F * Bt * c.enc_num_basis * L);
-  t.x_stride = al256(F * Bt * c.out_channels * L);
+  t.x_stride = srf_align_up(F * Bt * c.out_channels * L, 256);
   t.x0 = take(t.x_stride * (U + 1));
   // per block (relative offsets)
   size_t rel = 0;
   auto rtake = [&](size_t bytes) {
     const size_t o = rel;
-    rel = al256(rel + bytes);
+    rel = srf_align_up(rel + bytes, 256);
     return o;
   };
   t.y1 = rtake(F * Bt * c.in_channels * L);
@@ -181,7 +132,7 @@ static ScratchLayout scratch_layout(const srf_plan* p) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
-    off = al256(off + bytes);
+    off = srf_align_up(off + bytes, 256);
     return o;
   };
   s.dec = take(F * srf_decoder_scratch_floats(p->Bt, SAN, p->SA, K, p->L));
@@ -227,20 +178,20 @@ static ScratchLayout scratch_layout(const srf_plan* p) {
   s.tac = gc ? take(srf_tac_bwd_scratch_bytes(p->Bt, c.group_size, p->nB, p->L)) : 0;
   // per-call scratch slices of the blocks' norm / depthwise-conv backwards (zeroed once per backward; their parameter-gradient
   // reductions are deferred to one batched flush: srf_backward.hip, SrfDeferCtx): per block D + 2 norm slices and D conv slices
-  s.gln_slice = al256(srf_gln_bwd_scratch_bytes(p->Bg, p->nC));
-  s.dw_slice = al256(srf_dwconv5_bwd_scratch_bytes(p->Bg, p->nC));
+  s.gln_slice = srf_align_up(srf_gln_bwd_scratch_bytes(p->Bg, p->nC), 256);
+  s.dw_slice = srf_align_up(srf_dwconv5_bwd_scratch_bytes(p->Bg, p->nC), 256);
   s.arena_bytes = (size_t)c.num_blocks * ((size_t)(D + 2) * s.gln_slice + (size_t)D * s.dw_slice);
   s.arena = take(s.arena_bytes);
   // two-part images of the TRANSPOSED weights for the backward's data-gradient GEMMs (packed once per backward)
   {
-    size_t pk = al256(srf_packed_pw_weight_bytes(B, SAN)) + al256(srf_packed_pw_weight_bytes(N, B));
-    pk += (size_t)c.num_blocks * (al256(srf_packed_pw_weight_bytes(p->nC, p->nB)) + al256(srf_packed_pw_weight_bytes(p->nB, p->nC)));
+    size_t pk = srf_align_up(srf_packed_pw_weight_bytes(B, SAN), 256) + srf_align_up(srf_packed_pw_weight_bytes(N, B), 256);
+    pk += (size_t)c.num_blocks * (srf_align_up(srf_packed_pw_weight_bytes(p->nC, p->nB), 256) + srf_align_up(srf_packed_pw_weight_bytes(p->nB, p->nC), 256));
     s.pkT = take(pk);
   }
   // three-part weight images of the forward's 1x1 convolutions (packed once per step by srf_forward_train)
   {
-    size_t pk = al256(srf_packed3_pw_weight_bytes(B, N)) + al256(srf_packed3_pw_weight_bytes(SAN, B));
-    pk += (size_t)c.num_blocks * (al256(srf_packed3_pw_weight_bytes(p->nC, p->nB)) + al256(srf_packed3_pw_weight_bytes(p->nB, p->nC)));
+    size_t pk = srf_align_up(srf_packed3_pw_weight_bytes(B, N), 256) + srf_align_up(srf_packed3_pw_weight_bytes(SAN, B), 256);
+    pk += (size_t)c.num_blocks * (srf_align_up(srf_packed3_pw_weight_bytes(p->nC, p->nB), 256) + srf_align_up(srf_packed3_pw_weight_bytes(p->nB, p->nC), 256));
     s.pk3 = take(pk);
   }
   s.total = off;
@@ -294,7 +245,7 @@ extern "C" int srf_forward_train(const srf_plan* p, const float* const* P, int n
                                  void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
   if (causal_refused(p, "srf_forward_train")) return SRF_EINVAL;
   const int mode = srf_kernel_mode(), flags = srf_debug_flags();
-  const bool exact = mode == 0 && !(flags & (1 << 28));
+  const bool exact = mode == 0 && !(flags & SRF_DBG_TRAIN_FWD_SPLIT_BF16);
   const int prev = exact ? srf_kernel_mode_override(2) : -1;
   bool skip_d0 = false;
   const int rc = forward_train_impl(p, P, num_params, wav, out, saved, saved_bytes, scratch, scratch_bytes, exact, &skip_d0, stream);
@@ -331,7 +282,7 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
   // The 1x1 convolutions of the exact forward (kernel mode 2) run on the THREE-part split GEMM (six bf16 MFMAs per product
   // block, 24-bit operands: srf_pwconv_x3w.hip NP 3) where the 256 x 128 kernel takes the launch; their weights are split and
   // laid out once per step, here.  Debug flag 1 << 31: the exact-fp32 MFMA kernel instead (A/B).
-  const bool three = srf_kernel_mode() == 2 && !((unsigned)srf_debug_flags() & 0x80000000u);
+  const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
   std::vector<const float*> pk_w;
   std::vector<void*> pk_d;
   std::vector<int> pk_co, pk_ci;
@@ -340,7 +291,7 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
     const size_t bytes = srf_packed3_pw_weight_bytes(cout, cin);
     if (!three || !bytes) return nullptr;
     void* d = sc + pk_off;
-    pk_off += al256(bytes);
+    pk_off += srf_align_up(bytes, 256);
     pk_w.push_back(w);
     pk_d.push_back(d);
     pk_co.push_back(cout);
@@ -382,9 +333,11 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
     if (rc) return rc;
   }
   // fused pyramid with level outputs (register-resident kernels only); its scratch lives in the backward's gradient
-  // buffers gf | go | gd, idle during the forward.  Debug flag 16 (as in srf_forward) selects the per-level kernels.
+  // buffers gf | go | gd, idle during the forward.  SRF_DBG_PYR_PER_LEVEL (as in srf_forward) selects the per-level kernels.
+  // Not plan_fused_pyramid_now(p): p->fused_pyramid was decided under the flags of the plan's creation and also admits the
+  // LDS kernels; this test needs the register kernels, under the flags of this call.
   const size_t F_ = sizeof(float);
-  const bool fused_pyr = !(srf_debug_flags() & (16 | 64 | 128)) && srf_kernel_mode() != 1 &&
+  const bool fused_pyr = !srf_dbg(SRF_DBG_PYR_PER_LEVEL | SRF_DBG_PYR_NO_REG | SRF_DBG_PYR_PASS1_NONPERSISTENT) && srf_kernel_mode() != 1 &&
                          srf_pyramid_supported(nC, (int)L, D) && srf_pyramid_reg_supported((int)L, D) &&
                          srf_pyramid_scratch_bytes(Bg, nC, (int)L, D) <= (s.gd + F_ * Bt * c.in_channels * L) - s.gf;
   const bool skip_d0 = fused_pyr && train_fused_head(p);     // (the backward re-computes d_0: nothing reads it)
@@ -601,7 +554,7 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     const size_t bytes = srf_packed_pw_weight_bytes(cout_d, cin_d);
     if (!bytes || srf_kernel_mode() != 0) return nullptr;
     void* d = sc + pk_off;
-    pk_off += al256(bytes);
+    pk_off += srf_align_up(bytes, 256);
     pk_w.push_back(w);
     pk_d.push_back(d);
     pk_co.push_back(cout_d);

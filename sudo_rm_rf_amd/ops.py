@@ -4,7 +4,9 @@ Every function takes CUDA float32 tensors, launches on torch's current stream an
 tensors.  GlobLN statistics travel as float64 ``sums`` tensors of shape [groups, 2]
 ({sum, sum of squares}); producers accumulate into them, so pass zero-initialised tensors.
 """
+import contextlib
 import ctypes as C
+import enum
 import weakref
 
 import torch
@@ -543,8 +545,64 @@ def prelu(x, slope):
     return y
 
 
+class DebugFlag(enum.IntFlag):
+    """The kernel-variant switches of the library: enum srf_debug_flag of include/sudormrf_hip.h (which says what each one
+    selects) without the SRF_DBG_ prefix.  The values are frozen; tests/test_build_lint.py compares the two."""
+    NO_PAIRS = 1
+    GEMM_NO_MGROUPS = 2
+    NO_GEMM_256 = 4
+    NO_PACKED_WEIGHTS = 8
+    PYR_PER_LEVEL = 16
+    PYR_NO_LDS_TILES = 32
+    PYR_NO_REG = 64
+    PYR_PASS1_NONPERSISTENT = 128
+    GEMM_WHOLE_TAIL_TILES = 256
+    GEMM_QUARTER_TILES_LAST = 512
+    TAC_ONE_STEP_PER_LANE = 1024
+    GEMM_128_ONE_TILE_PER_BLOCK = 2048
+    WGRAD_NO_XCD_MAP = 4096
+    GEMM_256_SWAP_FORMS = 8192
+    TRAIN_BF16X3 = 16384
+    NO_FUSED_TAIL = 32768
+    BWD_NO_FUSED_HEAD = 1 << 16
+    PYR_PASS1_ROWS_PER_WAVE = 1 << 17
+    WGRAD_NO_WIDE_TILE = 1 << 18
+    WGRAD_128_MASKED = 1 << 19
+    WGRAD_SHORT_CHUNKS = 1 << 20
+    PAIR_PERSISTENT = 1 << 21
+    TAC_VALU = 1 << 22
+    PAIR_FULL_DRAIN = 1 << 23
+    TAC_GENERIC = 1 << 24
+    WGRAD_ONE_CHAIN_FOLD = 1 << 25
+    TAC_LANES_4TILES = 1 << 26
+    GEMM_128_POINTER_LOADS = 1 << 27
+    TRAIN_FWD_SPLIT_BF16 = 1 << 28
+    BWD_DW_CHUNKED = 1 << 29
+    BWD_GLN_SCALAR = 1 << 30
+    TRAIN_FWD_EXACT_MFMA = 1 << 31
+
+
+_debug_flags = 0    # what set_debug_flags last set (the library has no getter); debug_flags() restores it
+
+
 def set_debug_flags(flags):
-    _lib.load().srf_set_debug_flags(int(flags))
+    """Process-wide; `flags`: a DebugFlag combination or the same number as an int (bit 31 also as INT_MIN)."""
+    global _debug_flags
+    bits = int(flags) & 0xFFFFFFFF
+    _lib.load().srf_set_debug_flags(bits - (1 << 32) if bits >> 31 else bits)     # (a C int)
+    _debug_flags = bits
+
+
+@contextlib.contextmanager
+def debug_flags(flags):
+    """``with ops.debug_flags(DebugFlag.NO_PAIRS | DebugFlag.PYR_PER_LEVEL): ...`` runs the block under these switches and
+    puts back the ones in force on entry."""
+    prev = _debug_flags
+    set_debug_flags(flags)
+    try:
+        yield
+    finally:
+        set_debug_flags(prev)
 
 
 def set_kernel_mode(mode):

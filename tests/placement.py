@@ -345,6 +345,8 @@ PLACEMENT = {
 # public names of ops that take no caller tensors
 EXCLUDED = {
     "set_debug_flags": "a process-wide switch, no tensor",
+    "DebugFlag": "the names of that switch's bits, no tensor",
+    "debug_flags": "that switch as a context manager, no tensor",
     "set_kernel_mode": "a process-wide switch, no tensor",
     "get_kernel_mode": "a query, no tensor",
     "kernel_trace": "the in-library profiler's context manager, no tensor",

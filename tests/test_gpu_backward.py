@@ -3,6 +3,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from sudo_rm_rf_amd.ops import DebugFlag
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -65,7 +67,8 @@ def test_pw_wgrad(Bt, Cin, Cout, L, pro):
     assert rel_err(dw2, 2 * want_w) <= 2e-5 and rel_err(db2, 2 * want_b) <= 2e-5
 
 
-@pytest.mark.parametrize("flags", [1 << 18, (1 << 18) | (1 << 19)])
+@pytest.mark.parametrize("flags", [DebugFlag.WGRAD_NO_WIDE_TILE, DebugFlag.WGRAD_NO_WIDE_TILE | DebugFlag.WGRAD_128_MASKED],
+                         ids=["262144", "786432"])
 @pytest.mark.parametrize("Bt,Cin,Cout,L,pro", [(3, 256, 512, 3200, 2), (2, 512, 256, 832, 0), (2, 128, 256, 1664, 1), (1, 256, 256, 32, 3)])
 def test_pw_wgrad_kernel_forms_agree(Bt, Cin, Cout, L, pro, flags):
     """Round 6: full shapes run the wide-tile kernel (256 x 128 / 128 x 256); debug flag 1 << 18 keeps them on the 128 x 128 kernel's
@@ -84,11 +87,8 @@ def test_pw_wgrad_kernel_forms_agree(Bt, Cin, Cout, L, pro, flags):
         kw.update(in_prelu=dev32(slope))
     want_w, want_b = torch.einsum("bml,bnl->mn", g, fx), g.sum(dim=(0, 2))
     dw0, db0 = ops.pw_wgrad(dev32(g), dev32(x), **kw)
-    ops.set_debug_flags(flags)
-    try:
+    with ops.debug_flags(flags):
         dw1, db1 = ops.pw_wgrad(dev32(g), dev32(x), **kw)
-    finally:
-        ops.set_debug_flags(0)
     for dw, db in ((dw0, db0), (dw1, db1)):
         assert rel_err(dw, want_w) <= 2e-5 and rel_err(db, want_b) <= 2e-5
     assert rel_err(dw1, dw0.double().cpu()) <= 1e-5

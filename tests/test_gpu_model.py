@@ -94,12 +94,8 @@ def test_unfused_pyramid_agrees(manifest, name):
     from sudo_rm_rf_amd import ops
     cfg, sd, wav, gold = load_case(manifest, name)
     model = build(cfg, sd)
-    try:
-        ops.set_debug_flags(16)
-        with torch.no_grad():
-            out = model(torch.from_numpy(wav).to(DEV)).cpu().numpy()
-    finally:
-        ops.set_debug_flags(0)
+    with ops.debug_flags(ops.DebugFlag.PYR_PER_LEVEL), torch.no_grad():
+        out = model(torch.from_numpy(wav).to(DEV)).cpu().numpy()
     assert np.abs(out - gold["out"]).max() <= TOL
 
 
@@ -202,11 +198,10 @@ def test_fused_tail_agrees_with_materialised_masked_tensor(manifest, case, batch
         assert "pw_mask_decode" in names, sorted(names)
         again, _ = run()
         assert torch.equal(fused, again)
-        ops.set_debug_flags(32768)
-        plain, names = run()
+        with ops.debug_flags(ops.DebugFlag.NO_FUSED_TAIL):
+            plain, names = run()
         assert "pw_mask_decode" not in names and "pw_conv_x3w<3>" in names, sorted(names)
     finally:
-        ops.set_debug_flags(0)
         eng.multi_stream = True
     if not recipe:      # the masked tensor does not exist after a fused forward: asking for it must fail, not return partial frames
         plan = eng.last_plan
@@ -303,11 +298,9 @@ def test_fused_pairs_equal_separate_launches_on_ragged_lengths(T):
         with torch.no_grad(), ops.kernel_trace(DEV) as tr:
             fused = model(x)
         assert {"pw_pair_x3f<1>", "pw_pair_x3f<2>"} <= tr.names, tr.names
-        ops.set_debug_flags(1)
-        with torch.no_grad(), ops.kernel_trace(DEV) as tr0:
+        with ops.debug_flags(ops.DebugFlag.NO_PAIRS), torch.no_grad(), ops.kernel_trace(DEV) as tr0:
             plain = model(x)
         assert not any(n.startswith("pw_pair") for n in tr0.names), tr0.names
-        ops.set_debug_flags(0)
         scale = float(plain.abs().max())
         assert torch.isfinite(fused).all() and float((fused - plain).abs().max()) <= 2e-5 * scale, float((fused - plain).abs().max()) / scale
         eng.multi_stream = True
@@ -319,7 +312,6 @@ def test_fused_pairs_equal_separate_launches_on_ragged_lengths(T):
                     eng._forward_split(parts, x, out, eng._param_table(params, x.device))
                 assert float((out - plain).abs().max()) <= 2e-5 * scale, parts
     finally:
-        ops.set_debug_flags(0)
         eng.multi_stream = True
 
 

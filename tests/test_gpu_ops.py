@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from sudo_rm_rf_amd.ops import DebugFlag
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -155,11 +157,8 @@ def test_pw_conv_buffer_and_pointer_loads_agree(Bt, Cin, Cout, L, pro):
                   in_beta=dev32(rnd(Cin, seed=34)), in_prelu=dev32(torch.tensor([0.2], dtype=torch.float64)))
     want = F.conv1d(x.double().cpu(), w.double().cpu(), bias.double().cpu()) if pro == 0 else None
     a = ops.pw_conv(x, w, bias, **kw)
-    try:
-        ops.set_debug_flags(1 << 27)
+    with ops.debug_flags(DebugFlag.GEMM_128_POINTER_LOADS):
         b = ops.pw_conv(x, w, bias, **kw)
-    finally:
-        ops.set_debug_flags(0)
     assert torch.equal(a, b)
     if want is not None:
         check(a, want, 5e-5, "pw_conv buffer loads")
@@ -188,21 +187,16 @@ def test_pw_conv_persistent_variants(Bt, Cin, Cout, L, pro):
         xin = torch.where(xin >= 0, xin, 0.17 * xin)
     want = F.conv1d(xin, w.double().cpu(), bias.double().cpu()) + res.double().cpu()
     outs = {}
-    try:
-        for name, flags in (("dispatched", 0), ("pointer loads", 1 << 27), ("one tile per block", 2048)):
-            ops.set_debug_flags(flags)
+    for name, flags in (("dispatched", 0), ("pointer loads", DebugFlag.GEMM_128_POINTER_LOADS),
+                        ("one tile per block", DebugFlag.GEMM_128_ONE_TILE_PER_BLOCK)):
+        with ops.debug_flags(flags):
             outs[name] = ops.pw_conv(x, w, bias, residual=res, **kw)
-    finally:
-        ops.set_debug_flags(0)
     # the 256 x 128 kernel with pre-split weights (what srf_forward dispatches: srf_pwconv_x3w.hip)
     packed = ops.pack_pw_weight(w)
     assert packed is not None
     outs["packed 256x128"] = ops.pw_conv(x, w, bias, residual=res, packed=packed, **kw)
-    try:
-        ops.set_debug_flags(8192)        # (round 4) the paired-block form, what srf_forward runs: two co-resident blocks per CU
+    with ops.debug_flags(DebugFlag.GEMM_256_SWAP_FORMS):   # (round 4) the paired-block form, what srf_forward runs: two co-resident blocks per CU
         outs["packed 256x128, two blocks per CU"] = ops.pw_conv(x, w, bias, residual=res, packed=packed, **kw)
-    finally:
-        ops.set_debug_flags(0)
     assert torch.equal(outs["packed 256x128"], outs["packed 256x128, two blocks per CU"])
     for name, got in outs.items():
         check(got, want, 1e-4, "persistent pw_conv pro=%d (%s)" % (pro, name))
@@ -254,14 +248,11 @@ def test_pw_conv_pair_is_bitwise_the_two_launches(Bt, Cin1, Cout2, L, pro):
     y2_ref = ops.pw_conv(y_ref, w2, b2, out_sums=sums_ref, packed=p2)
     want2 = F.conv1d(y_ref.double().cpu(), w2.double().cpu(), b2.double().cpu())
     outs = {}
-    try:
-        for name, flags in (("counted waits", 0), ("full drains", 1 << 23), ("persistent blocks", 1 << 21)):
-            ops.set_debug_flags(flags)
+    for name, flags in (("counted waits", 0), ("full drains", DebugFlag.PAIR_FULL_DRAIN), ("persistent blocks", DebugFlag.PAIR_PERSISTENT)):
+        with ops.debug_flags(flags):
             sums = ops.new_sums(Bt, DEV)
             y, y2 = ops.pw_conv_pair(x, p1, b1, kw["in_sums"], kw["in_gamma"], kw["in_beta"], slope, res, p2, b2, Cmid, Cout2, out_sums2=sums)
             outs[name] = (y, y2, sums)
-    finally:
-        ops.set_debug_flags(0)
     def where(got, ref):      # a failure report that shows the pattern (which examples / row blocks / column phases)
         bad = (got != ref) | torch.isnan(got)
         if not bad.any():
@@ -317,16 +308,13 @@ def test_pw_conv_narrow_tiles_for_small_launches(Bt, Cin, Cout, L, pro, epi):
         kw.update(mask_mul=mul)
         want = torch.relu(want) * mul.double().cpu().repeat(1, Cout // mc, 1)
     got_sums = ops.new_sums(Bt, DEV) if epi == "sums" else None
-    try:
-        with ops.kernel_trace(DEV) as tr:
-            got = ops.pw_conv(x, w, bias, out_sums=got_sums, **kw)
-        assert tr.names == {"pw_conv_bf16x3_w4"}, tr.names
-        ops.set_debug_flags(2048)
+    with ops.kernel_trace(DEV) as tr:
+        got = ops.pw_conv(x, w, bias, out_sums=got_sums, **kw)
+    assert tr.names == {"pw_conv_bf16x3_w4"}, tr.names
+    with ops.debug_flags(DebugFlag.GEMM_128_ONE_TILE_PER_BLOCK):
         with ops.kernel_trace(DEV) as tr:
             ref = ops.pw_conv(x, w, bias, out_sums=ops.new_sums(Bt, DEV) if epi == "sums" else None, **kw)
         assert "pw_conv_bf16x3_w4" not in tr.names, tr.names
-    finally:
-        ops.set_debug_flags(0)
     if epi == "sums":
         tot = got_sums.double().sum(dim=1).cpu()              # [Bt][buckets][2] -> per-example {sum, sumsq}
         exp = torch.stack([want.sum(dim=(1, 2)), (want * want).sum(dim=(1, 2))], dim=1)
@@ -347,7 +335,7 @@ def test_pw_conv_three_part_split(Bt, Cin, Cout, L, pro, parts):
     that have one.  Forms as the training forward uses them: pro 2 with the residual, the others without."""
     from sudo_rm_rf_amd import ops
     ops.set_kernel_mode(0)
-    ops.set_debug_flags(16384 if parts == "bf16x3" else 0)
+    ops.set_debug_flags(DebugFlag.TRAIN_BF16X3 if parts == "bf16x3" else 0)
     g = torch.Generator(device=DEV).manual_seed(700 + Cin + Cout + L + pro)
     x = torch.randn(Bt, Cin, L, generator=g, device=DEV) * 1.3 + 0.2
     w = torch.randn(Cout, Cin, 1, generator=g, device=DEV) * Cin ** -0.5
@@ -447,11 +435,8 @@ def test_pw_conv_fp16_split_is_loud_beyond_its_range():
     assert float((got.double() - want)[sel].abs().max()) <= 1e-5 * float(want[sel].abs().max())
     x2 = torch.randn(Bt, Cin, L, generator=g, device=DEV)
     x2[0, 5, 17] = 3.0e5
-    try:
-        ops.set_debug_flags(16384)
+    with ops.debug_flags(DebugFlag.TRAIN_BF16X3):
         exact = ops.pw_conv3(x2, w, bias, ops.pack3_pw_weight(w))
-    finally:
-        ops.set_debug_flags(0)
     want2 = torch.einsum("mk,bkl->bml", w[:, :, 0].double(), x2.double())
     assert float((exact.double() - want2).abs().max()) <= 1e-5 * float(want2.abs().max())
 
@@ -513,14 +498,11 @@ def test_pw_conv_packed3_refuses_an_image_of_the_other_format():
     bias = torch.zeros(Cout, device=DEV)
     packed = ops.pack3_pw_weight(w)                       # fp16 parts
     ref = ops.pw_conv3(x, w, bias, packed)
-    try:
-        ops.set_debug_flags(16384)
+    with ops.debug_flags(DebugFlag.TRAIN_BF16X3):
         with pytest.raises(RuntimeError, match="packed as two fp16 parts"):
             ops.pw_conv3(x, w, bias, packed)
         packed3 = ops.pack3_pw_weight(w)                  # re-packed under the flag: served
         again = ops.pw_conv3(x, w, bias, packed3)
-    finally:
-        ops.set_debug_flags(0)
     assert float((again - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
     with pytest.raises(RuntimeError, match="packed as three bf16 parts"):
         ops.pw_conv3(x, w, bias, packed3)
@@ -596,24 +578,16 @@ def test_pw_conv_x3w_at_cfg4_cfg5_shapes(Bt, Cin, Cout, L, pro, epi):
     if epi != "mask":
         # (round 4) the PAIRED-BLOCK form of the kernel -- what srf_forward runs for every form but the mask epilogue; stand-alone
         # calls get it with debug flag 8192 -- is bit-identical and its statistics agree to rounding
-        try:
-            ops.set_debug_flags(8192)
-            with ops.kernel_trace(DEV) as tr1:
-                one = ops.pw_conv(x, w, bias, packed=packed, **kw)
-        finally:
-            ops.set_debug_flags(0)
+        with ops.debug_flags(DebugFlag.GEMM_256_SWAP_FORMS), ops.kernel_trace(DEV) as tr1:
+            one = ops.pw_conv(x, w, bias, packed=packed, **kw)
         assert tr1.names == {"pw_conv_x3p<%d>" % pro}, tr1.names
         assert torch.equal(got, one)
         if sums is not None:
             assert torch.allclose(kw["out_sums"].sum(1), sums.sum(1), rtol=1e-6, atol=1e-6 * got[0].numel())
             kw["out_sums"] = ops.new_sums(Bt, DEV)
         del one
-    try:
-        ops.set_debug_flags(4)                                   # without the 256 x 128 kernel
-        with ops.kernel_trace(DEV) as tr2:
-            ref = ops.pw_conv(x, w, bias, packed=packed, **kw)
-    finally:
-        ops.set_debug_flags(0)
+    with ops.debug_flags(DebugFlag.NO_GEMM_256), ops.kernel_trace(DEV) as tr2:
+        ref = ops.pw_conv(x, w, bias, packed=packed, **kw)
     assert not any(n.startswith(("pw_conv_x3w", "pw_conv_x3p")) for n in tr2.names), tr2.names
     assert torch.equal(got, ref)
 
@@ -636,11 +610,8 @@ def test_pw_conv_beyond_2gb_is_chunked_over_examples():
     packed = ops.pack_pw_weight(w)
     s_a, s_b = ops.new_sums(Bt, DEV), ops.new_sums(Bt, DEV)
     got = ops.pw_conv(x, w, bias, packed=packed, out_sums=s_a, **kw)
-    try:
-        ops.set_debug_flags(4)                                   # without the 256 x 128 kernel: 64-bit pointer form
+    with ops.debug_flags(DebugFlag.NO_GEMM_256):                 # 64-bit pointer form
         want = ops.pw_conv(x, w, bias, packed=packed, out_sums=s_b, **kw)
-    finally:
-        ops.set_debug_flags(0)
     assert torch.equal(got, want)
     ta, tb = s_a.sum(1), s_b.sum(1)                              # [example][{sum, sumsq}]
     assert ((ta - tb).abs() <= 1e-7 * tb.abs().clamp_min(1.0)).all()      # (fp32 partial sums in a different order)
@@ -715,7 +686,8 @@ def test_merge(mode, Bt, C, L, D):
     check_sums(osums, u, "merge sums")
 
 
-@pytest.mark.parametrize("flags", [0, 64, 96], ids=["registers", "lds-tiles", "lds-rows"])
+@pytest.mark.parametrize("flags", [0, DebugFlag.PYR_NO_REG, DebugFlag.PYR_NO_REG | DebugFlag.PYR_NO_LDS_TILES],
+                         ids=["registers", "lds-tiles", "lds-rows"])
 @pytest.mark.parametrize("Bt,C,L,D", [(2, 64, 3200, 5), (2, 16, 6400, 6), (1, 8, 128, 4), (3, 20, 256, 2),
                                       (2, 4, 64, 1), (1, 5, 12800, 6), (2, 3, 64, 3), (2, 6, 3232, 5),
                                       (1, 3, 3264, 6)])
@@ -742,13 +714,10 @@ def test_fused_pyramid(Bt, C, L, D, flags):
         u = outs[k] + u.repeat_interleave(2, dim=-1)
     osums = ops.new_sums(Bt, DEV)
     from sudo_rm_rf_amd import _lib
-    ops.set_debug_flags(flags)
-    try:
+    with ops.debug_flags(flags):
         if not _lib.load().srf_pyramid_supported(C, L, D):
             pytest.skip("shape not supported by this kernel family")
         got = _run_pyramid(ops, y1, g_in, b_in, slope, W, Bi, Ga, Be, osums)
-    finally:
-        ops.set_debug_flags(0)
     check(got, u, 5e-5, "fused pyramid")
     check_sums(osums, u, "fused pyramid sums")
 
@@ -770,17 +739,14 @@ def test_decoder(mode, Bt, Ci, Co, K, L, T):
     check(got, want, 3e-5, "decoder")
 
 
-@pytest.mark.parametrize("flags", [0, 1 << 26, 1 << 24], ids=["lanes", "lanes-4tiles", "columns"])
+@pytest.mark.parametrize("flags", [0, DebugFlag.TAC_LANES_4TILES, DebugFlag.TAC_GENERIC], ids=["lanes", "lanes-4tiles", "columns"])
 @pytest.mark.parametrize("Bt,G,n,L", [(2, 16, 16, 300), (1, 4, 8, 77), (2, 8, 4, 130), (1, 2, 32, 64),
                                       (3, 16, 16, 1601), (2, 4, 4, 100), (2, 2, 2, 70), (1, 8, 16, 50),
                                       (2, 16, 8, 64), (1, 16, 2, 33), (1, 3, 4, 40)])
 def test_tac(Bt, G, n, L, flags):
     from sudo_rm_rf_amd import ops
-    ops.set_debug_flags(flags)
-    try:
+    with ops.debug_flags(flags):
         _tac_case(Bt, G, n, L)
-    finally:
-        ops.set_debug_flags(0)
 
 
 def test_tac_mfma_forms_serve_the_cfg3_shape_and_agree_with_the_valu_kernels():
@@ -802,13 +768,9 @@ def test_tac_mfma_forms_serve_the_cfg3_shape_and_agree_with_the_valu_kernels():
         q = ops.tac(x, P)
         gx, grads = ops.tac_bwd(x, go, P)
     assert {"tac_mfma", "tac_bwd_mfma"} <= tr.names, tr.names
-    try:
-        ops.set_debug_flags(1 << 22)
-        with ops.kernel_trace(DEV) as tr2:
-            q2 = ops.tac(x, P)
-            gx2, grads2 = ops.tac_bwd(x, go, P)
-    finally:
-        ops.set_debug_flags(0)
+    with ops.debug_flags(DebugFlag.TAC_VALU), ops.kernel_trace(DEV) as tr2:
+        q2 = ops.tac(x, P)
+        gx2, grads2 = ops.tac_bwd(x, go, P)
     assert {"tac", "tac_bwd"} <= tr2.names and not (tr2.names & {"tac_mfma", "tac_bwd_mfma"}), tr2.names
     assert float((q - q2).abs().max()) <= 5e-6 * max(1.0, float(q2.abs().max()))
     rel = lambda a, b: float((a - b).norm() / b.norm())

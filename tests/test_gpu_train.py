@@ -6,6 +6,7 @@ import torch
 
 from oracle import loss_oracle, torch_oracle, weights
 from oracle.schema import ModelConfig
+from sudo_rm_rf_amd.ops import DebugFlag
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -201,12 +202,9 @@ def test_fast_training_forward_flag():
     cfg, sd, mix, tgt, z = train_case("train_improved_mfma")
     model = build(cfg, sd).train()
     loss_fn = sisdr_lib.PITLossWrapper(sisdr_lib.PairwiseNegSDR("sisdr"), pit_from='pw_mtx')
-    ops.set_debug_flags(1 << 28)
-    try:
+    with ops.debug_flags(DebugFlag.TRAIN_FWD_SPLIT_BF16):
         l = torch.clamp(loss_fn(model(mix.to(DEV)), tgt.to(DEV)), min=-30., max=+30.)
         l.backward()
-    finally:
-        ops.set_debug_flags(0)
     assert abs(l.item() - float(z["loss"])) <= 1e-3
     num = den = 0.0
     for k, p in model.state_dict(keep_vars=True).items():
@@ -235,23 +233,19 @@ def test_training_step_with_and_without_fused_pairs():
     tgt = tgt.to(DEV)
     loss_fn = sisdr_lib.PITLossWrapper(sisdr_lib.PairwiseNegSDR("sisdr"), pit_from='pw_mtx')
     grads = {}
-    try:
-        for flags in (0, 1):
-            model = build(cfg, sd).train()
-            ops.set_debug_flags(flags)
-            with ops.kernel_trace(DEV) as tr:
-                loss_fn(model(mix), tgt).backward()
-            npair = sum(1 for k, _ in tr.launches if k == "pw_pair_x3f<0>")
-            assert npair == (cfg.num_blocks - 1 if flags == 0 else 0), (flags, npair, sorted(tr.names))
-            # the forward's pairs (fp16 parts): bottleneck + proj_1x1(0), res_conv(i) + proj_1x1(i + 1)
-            nfwd = sum(1 for k, _ in tr.launches if k.startswith("pw_pair_x3f4<"))
-            assert nfwd == (cfg.num_blocks if flags == 0 else 0), (flags, nfwd, sorted(tr.names))
-            grads[flags] = {k: p.grad.clone() for k, p in model.state_dict(keep_vars=True).items()}
-    finally:
-        ops.set_debug_flags(0)
+    for flags in (0, DebugFlag.NO_PAIRS):
+        model = build(cfg, sd).train()
+        with ops.debug_flags(flags), ops.kernel_trace(DEV) as tr:
+            loss_fn(model(mix), tgt).backward()
+        npair = sum(1 for k, _ in tr.launches if k == "pw_pair_x3f<0>")
+        assert npair == (cfg.num_blocks - 1 if flags == 0 else 0), (flags, npair, sorted(tr.names))
+        # the forward's pairs (fp16 parts): bottleneck + proj_1x1(0), res_conv(i) + proj_1x1(i + 1)
+        nfwd = sum(1 for k, _ in tr.launches if k.startswith("pw_pair_x3f4<"))
+        assert nfwd == (cfg.num_blocks if flags == 0 else 0), (flags, nfwd, sorted(tr.names))
+        grads[flags] = {k: p.grad.clone() for k, p in model.state_dict(keep_vars=True).items()}
     worst_t, worst_s = ("", 0.0), ("", 0.0)
     for k in grads[0]:
-        a, b = grads[0][k], grads[1][k]
+        a, b = grads[0][k], grads[DebugFlag.NO_PAIRS][k]
         assert torch.isfinite(a).all(), k
         err = float((a - b).abs().max()) / max(float(b.abs().max()), 1e-12)
         if a.numel() > 1:
@@ -293,21 +287,17 @@ def test_training_step_with_and_without_the_fused_backward_head(shape):
     tgt = tgt.to(DEV)
     loss_fn = sisdr_lib.PITLossWrapper(sisdr_lib.PairwiseNegSDR("sisdr"), pit_from='pw_mtx')
     grads = {}
-    try:
-        for flags in (0, 1 << 16):
-            model = build(cfg, sd).train()
-            ops.set_debug_flags(flags)
-            with ops.kernel_trace(DEV) as tr:
-                loss_fn(model(mix), tgt).backward()
-            for fam in ("bwd_l0p_reduce", "bwd_l0p_apply", "bwd_l1h"):
-                nhead = sum(1 for k, _ in tr.launches if k == fam)
-                want = cfg.num_blocks if (flags == 0 and cfg.upsampling_depth > 1) else 0
-                assert nhead == want, (fam, flags, nhead, sorted(tr.names))
-            grads[flags] = {k: p.grad.clone() for k, p in model.state_dict(keep_vars=True).items()}
-    finally:
-        ops.set_debug_flags(0)
+    for flags in (0, DebugFlag.BWD_NO_FUSED_HEAD):
+        model = build(cfg, sd).train()
+        with ops.debug_flags(flags), ops.kernel_trace(DEV) as tr:
+            loss_fn(model(mix), tgt).backward()
+        for fam in ("bwd_l0p_reduce", "bwd_l0p_apply", "bwd_l1h"):
+            nhead = sum(1 for k, _ in tr.launches if k == fam)
+            want = cfg.num_blocks if (flags == 0 and cfg.upsampling_depth > 1) else 0
+            assert nhead == want, (fam, flags, nhead, sorted(tr.names))
+        grads[flags] = {k: p.grad.clone() for k, p in model.state_dict(keep_vars=True).items()}
     for k in grads[0]:
-        a, b = grads[0][k], grads[1 << 16][k]
+        a, b = grads[0][k], grads[DebugFlag.BWD_NO_FUSED_HEAD][k]
         assert torch.isfinite(a).all(), k
         err = float((a - b).abs().max()) / max(float(b.abs().max()), 1e-12)
         assert err <= (2e-3 if a.numel() == 1 else 5e-5), (k, err)
@@ -823,11 +813,11 @@ def test_bench_batch_training_gradient_is_the_mean_over_its_sub_batches(name):
 
 # ---- the backward follows the forward it belongs to ------------------------------------------------------------------------------
 _SWITCHES = [  # (id, forward (debug flags, kernel mode), backward (debug flags, kernel mode))
-    ("flags_0_to_head_off", (0, 0), (1 << 16, 0)),
-    ("flags_0_to_chunked_dwconv", (0, 0), (1 << 29, 0)),
-    ("flags_0_to_chunked_norm", (0, 0), (1 << 30, 0)),
+    ("flags_0_to_head_off", (0, 0), (DebugFlag.BWD_NO_FUSED_HEAD, 0)),
+    ("flags_0_to_chunked_dwconv", (0, 0), (DebugFlag.BWD_DW_CHUNKED, 0)),
+    ("flags_0_to_chunked_norm", (0, 0), (DebugFlag.BWD_GLN_SCALAR, 0)),
     ("mode_0_to_1", (0, 0), (0, 1)),
-    ("flags_head_off_to_0", (1 << 16, 0), (0, 0)),
+    ("flags_head_off_to_0", (DebugFlag.BWD_NO_FUSED_HEAD, 0), (0, 0)),
 ]
 
 

@@ -119,14 +119,13 @@ def main():
     print("block period (pair + pyramid on BOTH streams, Bt %d each): phase-locked with events %6.1f us, free-running %6.1f us" % (Bt, lk, fr), flush=True)
 
     for flags, name in ((0, "pair at 2 blocks / CU"),):
-        ops.set_debug_flags(flags)
         rows = []
-        for _ in range(5):
-            a_alone = timed(pair, None)[0]
-            b_alone = timed(None, pyr)[1]
-            a_co, b_co = timed(pair, pyr)
-            rows.append((a_alone, b_alone, a_co, b_co))
-        ops.set_debug_flags(0)
+        with ops.debug_flags(flags):
+            for _ in range(5):
+                a_alone = timed(pair, None)[0]
+                b_alone = timed(None, pyr)[1]
+                a_co, b_co = timed(pair, pyr)
+                rows.append((a_alone, b_alone, a_co, b_co))
         m = [statistics.median(r[i] for r in rows) for i in range(4)]
         print("%-24s Bt %d per stream: pair alone %6.1f us, pyramid alone %6.1f us | together: pair %6.1f (x %.2f), pyramid %6.1f (x %.2f); "
               "serial %6.1f vs overlapped %6.1f us per (pair + pyramid)" %

@@ -38,13 +38,13 @@ def fetch(plan, lo, n):
 
 CONFIGS = [
     ("default", 0, 0),
-    ("tac_one_step(1024)", 1024, 0),
-    ("tac_generic(1<<24)", 1 << 24, 0),
-    ("pyramid_unfused(16)", 16, 0),
-    ("pyramid_pass1_nonpersistent(128)", 128, 0),
-    ("pyramid_lds(64)", 64, 0),
-    ("gemm_pointer(1<<27)", 1 << 27, 0),
-    ("gemm_one_tile(2048)", 2048, 0),
+    ("tac_one_step(1024)", ops.DebugFlag.TAC_ONE_STEP_PER_LANE, 0),
+    ("tac_generic(1<<24)", ops.DebugFlag.TAC_GENERIC, 0),
+    ("pyramid_unfused(16)", ops.DebugFlag.PYR_PER_LEVEL, 0),
+    ("pyramid_pass1_nonpersistent(128)", ops.DebugFlag.PYR_PASS1_NONPERSISTENT, 0),
+    ("pyramid_lds(64)", ops.DebugFlag.PYR_NO_REG, 0),
+    ("gemm_pointer(1<<27)", ops.DebugFlag.GEMM_128_POINTER_LOADS, 0),
+    ("gemm_one_tile(2048)", ops.DebugFlag.GEMM_128_ONE_TILE_PER_BLOCK, 0),
     ("generic_kernels(mode1)", 0, 1),
 ]
 only = os.environ.get("ONLY")

@@ -9,6 +9,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sudo_rm_rf_amd import ops
 DEV = "cuda:0"
+POINTER = ops.DebugFlag.GEMM_128_POINTER_LOADS
 
 
 def rnd(*s, seed=0, scale=1.0):
@@ -17,10 +18,8 @@ def rnd(*s, seed=0, scale=1.0):
 
 
 def run(x, w, b, flags, **kw):
-    ops.set_debug_flags(flags)
-    y = ops.pw_conv(x, w, b, **kw)
-    ops.set_debug_flags(0)
-    return y
+    with ops.debug_flags(flags):
+        return ops.pw_conv(x, w, b, **kw)
 
 
 out = {}
@@ -34,7 +33,7 @@ sums[:, 0, 0] = xf.sum(1)
 sums[:, 0, 1] = (xf * xf).sum(1)
 gamma, beta = rnd(Cin, seed=4) + 1, rnd(Cin, seed=5)
 kw = dict(in_sums=sums, in_gamma=gamma, in_beta=beta)
-ref = run(x, w, b, 1 << 27, **kw)          # pointer form
+ref = run(x, w, b, POINTER, **kw)          # pointer form
 mean = (xf.sum(1) / xf.shape[1]).float().view(Bt, 1, 1)
 var = ((xf * xf).sum(1) / xf.shape[1]).float().view(Bt, 1, 1) - mean * mean
 xn = (x - mean) * torch.rsqrt(var + 1e-8) * gamma.view(1, -1, 1) + beta.view(1, -1, 1)
@@ -69,7 +68,7 @@ wrong_k = []
 for k0 in range(0, Cin):
     x0.zero_()
     x0[:, k0, :] = 1.0
-    a = run(x0, w, b, 1 << 27, in_sums=s1, in_gamma=g1, in_beta=b0)
+    a = run(x0, w, b, POINTER, in_sums=s1, in_gamma=g1, in_beta=b0)
     c = run(x0, w, b, 0, in_sums=s1, in_gamma=g1, in_beta=b0)
     e = (a - c).abs().max().item()
     if e > 1e-6:
@@ -83,7 +82,7 @@ wrong_g = []
 for k0 in range(0, Cin, 1):
     gk = torch.zeros(Cin, device=DEV)
     gk[k0] = 1.0
-    a = run(x0, w, b, 1 << 27, in_sums=s2, in_gamma=gk, in_beta=b0)
+    a = run(x0, w, b, POINTER, in_sums=s2, in_gamma=gk, in_beta=b0)
     c = run(x0, w, b, 0, in_sums=s2, in_gamma=gk, in_beta=b0)
     e = (a - c).abs().max().item()
     if e > 1e-6:
@@ -93,7 +92,7 @@ wrong_b = []
 for k0 in range(0, Cin, 1):
     bk = torch.zeros(Cin, device=DEV)
     bk[k0] = 1.0
-    a = run(x0, w, b, 1 << 27, in_sums=s2, in_gamma=b0, in_beta=bk)
+    a = run(x0, w, b, POINTER, in_sums=s2, in_gamma=b0, in_beta=bk)
     c = run(x0, w, b, 0, in_sums=s2, in_gamma=b0, in_beta=bk)
     e = (a - c).abs().max().item()
     if e > 1e-6:
@@ -106,7 +105,7 @@ for i in range(Bt):       # mean_i = i, var = 1  ->  xn = 1 - i
     n = Cin * L
     s3[i, 0, 0] = i * n
     s3[i, 0, 1] = (1.0 + i * i) * n
-a = run(xs, w, b, 1 << 27, in_sums=s3, in_gamma=g1, in_beta=b0)
+a = run(xs, w, b, POINTER, in_sums=s3, in_gamma=g1, in_beta=b0)
 c = run(xs, w, b, 0, in_sums=s3, in_gamma=g1, in_beta=b0)
 print("stats probe by example:", ["%.2e" % v for v in (a - c).abs().amax(dim=(1, 2)).tolist()])
 os.makedirs("gpurun_out", exist_ok=True)

@@ -21,17 +21,16 @@ import sudo_rm_rf.dnn.losses.sisdr as sisdr_lib  # noqa: E402
 def step(cfg, sd, mix, tgt, flags=0, mode=0):
     model = build(cfg, sd).train()
     loss_fn = sisdr_lib.PITLossWrapper(sisdr_lib.PairwiseNegSDR("sisdr"), pit_from='pw_mtx')
-    ops.set_debug_flags(flags)
     ops.set_kernel_mode(mode)
     try:
-        rec = model(mix.to(DEV))
-        if cfg.variant == "groupcomm":
-            rec = mixture_consistency.apply(rec, mix.to(DEV))
-        l = torch.clamp(loss_fn(rec, tgt.to(DEV)), min=-30., max=+30.)
-        l.backward()
-        torch.cuda.synchronize()
+        with ops.debug_flags(flags):
+            rec = model(mix.to(DEV))
+            if cfg.variant == "groupcomm":
+                rec = mixture_consistency.apply(rec, mix.to(DEV))
+            l = torch.clamp(loss_fn(rec, tgt.to(DEV)), min=-30., max=+30.)
+            l.backward()
+            torch.cuda.synchronize()
     finally:
-        ops.set_debug_flags(0)
         ops.set_kernel_mode(0)
     return l.item(), {k: p.grad.cpu().numpy().astype(np.float64) for k, p in model.state_dict(keep_vars=True).items()}
 
@@ -52,9 +51,9 @@ for name in (sys.argv[1:] or ["train_cfg2_shape", "train_cfg4_shape"]):
     cfg, sd, mix, tgt, z = train_case(name)
     print("=====", name, "loss golden", float(z["loss"]))
     base = None
-    for tag, flags, mode in (("default#1", 0, 0), ("default#2", 0, 0), ("default#3", 0, 0), ("fast-fwd(1<<28)", 1 << 28, 0),
-                             ("no-rowwise(1<<29)", 1 << 29, 0), ("no-fused-bwd(1<<30)", 1 << 30, 0),
-                             ("per-level pyramid(16)", 16, 0), ("mode2 exact MFMA", 0, 2), ("mode1 generic", 0, 1)):
+    for tag, flags, mode in (("default#1", 0, 0), ("default#2", 0, 0), ("default#3", 0, 0), ("fast-fwd(1<<28)", ops.DebugFlag.TRAIN_FWD_SPLIT_BF16, 0),
+                             ("no-rowwise(1<<29)", ops.DebugFlag.BWD_DW_CHUNKED, 0), ("no-fused-bwd(1<<30)", ops.DebugFlag.BWD_GLN_SCALAR, 0),
+                             ("per-level pyramid(16)", ops.DebugFlag.PYR_PER_LEVEL, 0), ("mode2 exact MFMA", 0, 2), ("mode1 generic", 0, 1)):
         try:
             loss, g = step(cfg, sd, mix, tgt, flags, mode)
         except Exception as e:  # noqa: BLE001
@@ -73,7 +72,7 @@ full = os.path.join(ROOT, "tools", "tmp_cond_cfg2.npz")
 if os.path.exists(full) and (not sys.argv[1:] or "train_cfg2_shape" in sys.argv[1:]):
     ref = np.load(full)
     cfg, sd, mix, tgt, z = train_case("train_cfg2_shape")
-    for tag, flags in (("default", 0), ("per-level pyramid", 16)):
+    for tag, flags in (("default", 0), ("per-level pyramid", ops.DebugFlag.PYR_PER_LEVEL)):
         _, g = step(cfg, sd, mix, tgt, flags, 0)
         print("== full-tensor check (%s)" % tag)
         rows = []

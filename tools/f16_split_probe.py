@@ -41,22 +41,20 @@ for (Bt, Cin, Cout, L, pro) in [(16, 256, 512, 3200, 0), (16, 512, 256, 3200, 2)
         out = {}
 
         def run(name, fn, flags=0):
-            ops.set_debug_flags(flags)
-            y = fn()
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(10):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ops.set_debug_flags(0)
+            with ops.debug_flags(flags):
+                y = fn()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(10):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
             out[name] = (float((y[:, :, cols].double() - want).abs().max()), e0.elapsed_time(e1) * 100)
 
-        ops.set_debug_flags(16384)
-        p3 = ops.pack3_pw_weight(w)
-        ops.set_debug_flags(0)
-        run("three bf16 parts", lambda: ops.pw_conv3(x, w, bias, p3, **kw), 16384)
+        with ops.debug_flags(ops.DebugFlag.TRAIN_BF16X3):
+            p3 = ops.pack3_pw_weight(w)
+        run("three bf16 parts", lambda: ops.pw_conv3(x, w, bias, p3, **kw), ops.DebugFlag.TRAIN_BF16X3)
         p4 = ops.pack3_pw_weight(w)
         run("two fp16 parts  ", lambda: ops.pw_conv3(x, w, bias, p4, **kw))
         p2 = ops.pack_pw_weight(w)

@@ -43,7 +43,7 @@ def main():
         ref = None
         for mode in modes:
             ops.set_kernel_mode(int(mode[0]))
-            ops.set_debug_flags({"p": 2048, "h": 256, "e": 10 << 16}.get(mode[-1], 0))   # p: one tile per block, h: no half-tile tail, e: no epilogue stores
+            ops.set_debug_flags({"p": ops.DebugFlag.GEMM_128_ONE_TILE_PER_BLOCK, "h": ops.DebugFlag.GEMM_WHOLE_TAIL_TILES}.get(mode[-1], 0))
             kw["packed"] = ops.pack_pw_weight(w) if mode in ("0", "0n") else torch.zeros(0, device=DEV)
             if kw["packed"] is None or kw["packed"].numel() == 0:
                 kw["packed"] = None

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON the GPU box (via gpurun): ONE parametrised driver for a round's measurements (replaces the
-# one-shot gpu_r5a.sh ... gpu_r5n.sh, now under tools/lab/).
+# one-shot gpu_r5a.sh ... gpu_r5n.sh, which remain in git history only).
 #   tools/gpu_round.sh <out dir under gpurun_out> <part> [<part> ...]
 # parts (each writes its own files under gpurun_out/<out dir>/):
 #   smoke            __graft_entry__.smoke()

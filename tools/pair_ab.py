@@ -55,24 +55,21 @@ def main():
 
             def two(flags):
                 def f():
-                    ops.set_debug_flags(flags)
-                    y = ops.pw_conv(x, w1, b1, in_sums=sums, in_gamma=gamma, in_beta=beta, in_prelu=slope, residual=res, packed=p1)
-                    y2 = ops.pw_conv(y, w2, b2, out_sums=osum, packed=p2)
-                    ops.set_debug_flags(0)
+                    with ops.debug_flags(flags):
+                        y = ops.pw_conv(x, w1, b1, in_sums=sums, in_gamma=gamma, in_beta=beta, in_prelu=slope, residual=res, packed=p1)
+                        y2 = ops.pw_conv(y, w2, b2, out_sums=osum, packed=p2)
                     return y, y2
                 return f
 
             def pair(flags):
                 def f():
-                    ops.set_debug_flags(flags)
-                    r = ops.pw_conv_pair(x, p1, b1, sums, gamma, beta, slope, res, p2, b2, Cmid, C2, out_sums2=osum)
-                    ops.set_debug_flags(0)
-                    return r
+                    with ops.debug_flags(flags):
+                        return ops.pw_conv_pair(x, p1, b1, sums, gamma, beta, slope, res, p2, b2, Cmid, C2, out_sums2=osum)
                 return f
 
-            variants = {"two_x3w": two(0), "two_x3p": two(8192), "pair": pair(0), "pair_drain": pair(1 << 23)}
-            # PAIR_FLAGS="name=flags,...": extra variants of the pair under diagnostic flags (round 6: 1 << 18 the CU's second
-            # block at s_setprio 1, 1 << 19 / 1 << 20 that block half a k-step / half a tile late)
+            variants = {"two_x3w": two(0), "two_x3p": two(ops.DebugFlag.GEMM_256_SWAP_FORMS), "pair": pair(0),
+                        "pair_drain": pair(ops.DebugFlag.PAIR_FULL_DRAIN)}
+            # PAIR_FLAGS="name=flags,...": extra variants of the pair under debug flags given as numbers (ops.DebugFlag)
             for item in filter(None, os.environ.get("PAIR_FLAGS", "").split(",")):
                 nm, fl = item.split("=")
                 variants["pair_" + nm] = pair(int(fl, 0))

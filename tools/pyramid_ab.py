@@ -17,7 +17,7 @@ DEV = "cuda:0"
 
 
 def main():
-    flags = [int(a, 0) for a in sys.argv[1:]] or [0, 128, 1 << 17]
+    flags = [int(a, 0) for a in sys.argv[1:]] or [0, int(ops.DebugFlag.PYR_PASS1_NONPERSISTENT), int(ops.DebugFlag.PYR_PASS1_ROWS_PER_WAVE)]
     Bt, C, L, D = (int(os.environ.get(k, d)) for k, d in (("PYR_BT", 32), ("PYR_C", 512), ("PYR_L", 3200), ("PYR_D", 5)))
     g = torch.Generator(device=DEV).manual_seed(0)
     y1 = torch.randn(Bt, C, L, generator=g, device=DEV)
@@ -32,12 +32,10 @@ def main():
     per = {f: {} for f in flags}
     for rnd in range(6):
         for f in flags:
-            ops.set_debug_flags(f)
             osum = ops.new_sums(Bt, DEV)
-            with ops.kernel_trace(DEV) as tr:
+            with ops.debug_flags(f), ops.kernel_trace(DEV) as tr:
                 for _ in range(5):
                     out = ops.pyramid(y1, sums, gam, bet, slope, ws, bs, gs, be, out_sums=osum)
-            ops.set_debug_flags(0)
             if ref is None:
                 ref = out.clone()
             err = float((out - ref).abs().max())
