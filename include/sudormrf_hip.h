@@ -22,7 +22,7 @@
  *   srf_pit_sisdr_*        <- PITLossWrapper(PairwiseNegSDR("sisdr")) fwd/bwd        losses/sisdr.py:254-311,426-458
  *   srf_perm_inv_sisdr     <- PermInvariantSISDR.forward (validation metric)        losses/sisdr.py:66-196
  *   srf_forward (causal)   <- CausalSuDORMRF.forward      models/causal_improved_sudormrf_v3.py (ABI 16)
- *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17)
+ *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17; row-table push: ABI 19)
  *   srf_zeroref_snr_*      <- PermInvariantSNRwithZeroRefs fwd/bwd (FUSS training loss)  losses/snr.py:13-142 (ABI 18)
  *   srf_stab_sisdr         <- StabilizedPermInvSISDRMetric.forward (FUSS validation)    losses/sisdr.py:460-576
  *   srf_fuss_augment       <- online_augment + mixture normalisation   experiments/run_fuss_separation.py:195-243
@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define SRF_ABI_VERSION 18
+#define SRF_ABI_VERSION 19
 
 /* GlobLN statistics layout: "sums" = fp64 [groups][SRF_STAT_BUCKETS][2] {sum, sum of squares}; the
  * statistic of a group is the total over its buckets (producers spread their atomics over buckets). */
@@ -264,7 +264,8 @@ int srf_debug_fetch(const srf_plan* plan, const void* workspace, int what, float
  *                 srf_pw_wgrad*: g, x;  srf_gln_bwd: scratch;  srf_tac_bwd: x, go, gx, scratch.
  *   256 bytes     the whole-model buffers (workspace, saved, train scratch) and the stream session's weights_buf / state /
  *                 workspace, as stated with those entry points; wav and out of srf_forward / srf_separate / srf_forward_train /
- *                 srf_stream_push: any address. */
+ *                 srf_stream_push / srf_stream_push_rows, and out_tail of srf_stream_flush / srf_stream_flush_rows: any
+ *                 address. */
 
 /* out[b,n,l] = sum_{a,k} w[n,a,k] * xpad[b,a,h*l+k-h], h=K/2; samples outside [0,T) are zero, so the
  * reference's right zero-padding is implicit in L.  sums (nullable): [Bt][SRF_STAT_BUCKETS][2] += {sum, sumsq}. */
@@ -425,8 +426,27 @@ int srf_prelu_apply(const float* x, const float* slope, float* y, long n, void* 
  * out of range) returns SRF_EINVAL before anything is launched.
  * srf_causal_stream_pyramid: one block's pyramid for a chunk of Lc frames (Lc % 2^(D-1) == 0): y1 / merged [Bt,C,Lc], state:
  * D pointers to [Bt,C,10] holding the last 10 inputs of each level (level 0: after proj_1x1's PReLU), read and then
- * rolled.  Chunk after chunk it is bit-identical to srf_causal_pyramid on the whole sequence. */
+ * rolled.  Chunk after chunk it is bit-identical to srf_causal_pyramid on the whole sequence.
+ *
+ * Independent streams (ABI 19).  srf_stream_push runs the session's `batch` streams in lock-step.  srf_stream_push_rows serves
+ * ANY subset of them in one push, each with its own number of granules: rows[j] = {slot, n} is a HOST array of m rows,
+ * slot = the stream's index in the state (0 .. batch - 1), n = its samples in this push.  Packed operands, with
+ * frames_j = n_j / h and col0_j = the sum of the frames of the rows before j:
+ *   wav   row j is a contiguous [A, n_j] block at float offset A * h * col0_j
+ *   out   row j is a contiguous [S*A, n_j] block at float offset S*A * h * col0_j
+ * (for equal n these are the [m, A, n] / [m, S*A, n] tensors of srf_stream_push).  The state layout is the one above, addressed
+ * by slot; slots that are not listed are neither read nor written.  The rows travel to the encoder, pyramid and overlap-add
+ * kernels as a kernel argument, SRF_STREAM_ROWS_PER_LAUNCH at a time: there is no device-side table, and a push still allocates
+ * nothing on the device, copies nothing and never synchronises.  Those three kernels go out once per group of rows, the 1x1
+ * GEMMs once over all columns: srf_stream_push_rows_num_launches(s, m) = 2 U + 3 + ceil(m / 128) * (U + 2) (= 3 U + 5 up to 128
+ * rows), same four families.  Every stream gets bit for bit what a batch-1 session of its own would have returned.
+ * Refused with SRF_EINVAL before anything is launched: m < 1 or m > batch, a slot outside 0 .. batch - 1, the same slot twice
+ * (two rows would race on one state), n_j <= 0, n_j % g != 0, n_j > max_chunk_samples, a small or misaligned buffer, a null
+ * pointer.  The session's workspace is large enough for any accepted push.
+ * srf_stream_flush_rows: out_tail [m, S*A, h] = the pending samples of slots[0 .. m) (a HOST array); the state is unchanged. */
+#define SRF_STREAM_ROWS_PER_LAUNCH 128
 typedef struct srf_stream srf_stream;
+typedef struct { int slot; int n; } srf_stream_row;
 int srf_stream_create(const srf_config* cfg, int batch, int max_chunk_samples, srf_stream** out);
 void srf_stream_destroy(srf_stream* s);
 int srf_stream_granule(const srf_stream* s);
@@ -441,6 +461,10 @@ int srf_stream_reset(const srf_stream* s, void* state, int row, void* stream);
 int srf_stream_push(const srf_stream* s, const void* weights_buf, void* state, const float* wav, int n, float* out,
                     void* workspace, size_t workspace_bytes, void* stream);
 int srf_stream_flush(const srf_stream* s, const void* state, float* out_tail, void* stream);
+int srf_stream_push_rows(const srf_stream* s, const void* weights_buf, void* state, const srf_stream_row* rows, int m,
+                         const float* wav, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int srf_stream_flush_rows(const srf_stream* s, const void* state, const int* slots, int m, float* out_tail, void* stream);
+int srf_stream_push_rows_num_launches(const srf_stream* s, int m);
 int srf_causal_stream_pyramid(const float* y1, float* merged, float* const* state, const float* in_prelu,
                               const float* const* w, const float* const* bias, const float* const* prelu, int Bt, int C, int Lc,
                               int D, void* stream);

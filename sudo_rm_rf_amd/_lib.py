@@ -12,7 +12,7 @@ import torch  # noqa: F401  (loads torch's libamdhip64 first so the extension bi
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # SRF_LIB: an alternative build of the same library (same-box A/B of kernel variants, tools/); default = the in-tree build
 LIB_PATH = os.environ.get("SRF_LIB") or os.path.join(_PKG, "libsudormrf_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 STAT_BUCKETS = 64
 
 SRF_OK = 0
@@ -31,6 +31,10 @@ class srf_config(C.Structure):
 
 class srf_norm(C.Structure):
     _fields_ = [("sums", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("prelu", C.c_void_p)]
+
+
+class srf_stream_row(C.Structure):
+    _fields_ = [("slot", C.c_int), ("n", C.c_int)]
 
 
 _vp, _i, _sz, _l = C.c_void_p, C.c_int, C.c_size_t, C.c_long
@@ -158,6 +162,9 @@ _PROTOS = {
     "srf_stream_reset": (_i, [_vp, _vp, _i, _vp]),
     "srf_stream_push": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "srf_stream_flush": (_i, [_vp, _vp, _vp, _vp]),
+    "srf_stream_push_rows": (_i, [_vp, _vp, _vp, C.POINTER(srf_stream_row), _i, _vp, _vp, _vp, _sz, _vp]),
+    "srf_stream_flush_rows": (_i, [_vp, _vp, C.POINTER(_i), _i, _vp, _vp]),
+    "srf_stream_push_rows_num_launches": (_i, [_vp, _i]),
     "srf_causal_stream_pyramid": (_i, [_vp, _vp, C.POINTER(_vp), _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i,
                                        _i, _vp]),
 }

@@ -12,6 +12,10 @@
 //   srf_stream_pyramid_kernel  all D levels + merge of one block for a chunk, reads and rolls the depthwise state
 //   srf_stream_ola_kernel      overlap-add of the decoder frames with the stored tail; also rolls the encoder history
 // Plain launches only; a push allocates nothing, copies nothing and never synchronises.
+// Only the encoder, the pyramid and the overlap-add (and the flush) turn a column into a stream.  Each is ONE device body
+// templated on a row mapper: StreamRowsUniform is the lock-step push (row b of the launch = state slot b, Lc frames each),
+// StreamRowsTable the row-table push of srf_stream_push_rows (row j = {state slot, first column, frames}, passed by value as
+// a kernel argument).  FMA order, LDS layout and merge order are therefore shared by construction.
 #include <new>
 #include <vector>
 
@@ -23,24 +27,72 @@
 #define SRF_STREAM_LDS_MAX (64 * 1024)
 
 // ---------------------------------------------------------------------------------------------
-// encoder: out[nb][b Lc + l] = sum_{a, k<K} w[nb,a,k] win[b,a, h l + k],  win = [hist (2h) | chunk (n)].
-// A block = 32 basis functions x 8 frames of one stream.  Same FMA order per output as srf_causal_encoder_kernel.
+// row mappers.  Row j of a launch owns columns [col0(j), col0(j) + frames(j)) of the [channels][ncol] activations, the
+// contiguous [A, h frames] block at float offset A h col0(j) of wav, the [S*A, h frames] block at S*A h col0(j) of out, and
+// the state of slot(j).  For the uniform mapper these are the [Bt, A, n] / [Bt, S*A, n] tensors of srf_stream_push.
+// ---------------------------------------------------------------------------------------------
+struct StreamRowsUniform {
+  int Bt, Lc;
+  int chan_major;   // pyramid only: rows of y1 / merged ordered (c, b) (the push's layout) instead of (b, c)
+  __device__ __forceinline__ int slot(int j) const { return j; }
+  __device__ __forceinline__ int col0(int j) const { return j * Lc; }
+  __device__ __forceinline__ int frames(int) const { return Lc; }
+  __device__ __forceinline__ int max_frames() const { return Lc; }
+  __device__ __forceinline__ size_t ncol() const { return (size_t)Bt * Lc; }
+  // pyramid row r of `rows` -> channel, state slot, offset of its y1 / merged row, frames
+  __device__ __forceinline__ void pyr_row(long r, int C, int& c, int& sl, size_t& off, int& frames_) const {
+    c = chan_major ? (int)(r / Bt) : (int)(r % C);
+    sl = chan_major ? (int)(r % Bt) : (int)(r / C);
+    off = (size_t)r * Lc;
+    frames_ = Lc;
+  }
+};
+
+// The host validates every entry before a launch (slots in range and distinct, frames a positive multiple of 2^(D-1) and at
+// most max_lc, col0 the prefix sum): no kernel indexes memory through a value the host has not checked.
+struct StreamRowsTable {
+  int slot_[SRF_STREAM_ROWS_PER_LAUNCH], col0_[SRF_STREAM_ROWS_PER_LAUNCH], frames_[SRF_STREAM_ROWS_PER_LAUNCH];
+  int rows, max_frames_, ncol_;   // rows of this group, its largest frames, columns of the whole push
+  __device__ __forceinline__ int slot(int j) const { return slot_[j]; }
+  __device__ __forceinline__ int col0(int j) const { return col0_[j]; }
+  __device__ __forceinline__ int frames(int j) const { return frames_[j]; }
+  __device__ __forceinline__ int max_frames() const { return max_frames_; }
+  __device__ __forceinline__ size_t ncol() const { return (size_t)ncol_; }
+  __device__ __forceinline__ void pyr_row(long r, int, int& c, int& sl, size_t& off, int& frames_o) const {
+    c = (int)(r / rows);
+    const int j = (int)(r % rows);
+    sl = slot_[j];
+    off = (size_t)c * ncol_ + col0_[j];
+    frames_o = frames_[j];
+  }
+};
+static_assert(sizeof(StreamRowsTable) <= 2048, "the row table travels as a kernel argument");
+
+// ---------------------------------------------------------------------------------------------
+// encoder: out[nb][col0 + l] = sum_{a, k<K} w[nb,a,k] win[a, h l + k],  win = [hist of the slot (2h) | the row's chunk].
+// A block = 32 basis functions x 8 frames of one row; grid z = the rows of the launch, grid y covers the longest row and a
+// block past its own row's frames exits before touching memory.  Same FMA order per output as srf_causal_encoder_kernel.
 // The history is NOT written here (every basis tile of the stream reads it): srf_stream_ola_kernel rolls it.
 // ---------------------------------------------------------------------------------------------
+template <class M>
 __global__ __launch_bounds__(256) void srf_stream_enc_kernel(const float* __restrict__ wav, const float* __restrict__ hist,
                                                              const float* __restrict__ w, float* __restrict__ out, int A,
-                                                             int n, int N, int K, int Lc, int Bt) {
+                                                             int N, int K, M m) {
   extern __shared__ float win[];   // [A][WIN]
   const int H = K / 2, KW = 2 * K - 1;
   const int WIN = 7 * H + K;
-  const int b = blockIdx.z;
+  const int j = blockIdx.z;
   const int l0 = blockIdx.y * 8;
+  const int Lc = m.frames(j);
+  if (l0 >= Lc) return;            // the whole block: a shorter row of a row-table launch
+  const int n = H * Lc, sl = m.slot(j), c0 = m.col0(j);
+  const float* wr = wav + (size_t)A * H * c0;   // this row's [A, n] block
   for (int i = threadIdx.x; i < A * WIN; i += 256) {
-    const int a = i / WIN, j = i - a * WIN;
-    const int s = H * l0 + j;                  // index into [hist | chunk]
+    const int a = i / WIN, q = i - a * WIN;
+    const int s = H * l0 + q;                  // index into [hist | chunk]
     float v = 0.f;
-    if (s < 2 * H) v = hist[((size_t)b * A + a) * 2 * H + s];
-    else if (s - 2 * H < n) v = wav[((size_t)b * A + a) * n + s - 2 * H];
+    if (s < 2 * H) v = hist[((size_t)sl * A + a) * 2 * H + s];
+    else if (s - 2 * H < n) v = wr[(size_t)a * n + s - 2 * H];
     win[i] = v;
   }
   __syncthreads();
@@ -54,7 +106,7 @@ __global__ __launch_bounds__(256) void srf_stream_enc_kernel(const float* __rest
     const float* xw = win + a * WIN + H * lf;
     for (int k = 0; k < K; ++k) acc = fmaf(wn[k], xw[k], acc);
   }
-  out[(size_t)nb * Bt * Lc + (size_t)b * Lc + l] = acc;
+  out[(size_t)nb * m.ncol() + c0 + l] = acc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -123,12 +175,15 @@ static int stream_pw(const float* x, const float* w, const float* bias, const fl
 }
 
 // ---------------------------------------------------------------------------------------------
-// streaming pyramid.  A wavefront owns SRF_STREAM_RPW rows (b, c), 16 lanes each, and nobody else touches their state.  Per row,
+// streaming pyramid.  A wavefront owns SRF_STREAM_RPW rows (stream, c), 16 lanes each, and nobody else touches their state.  Per row,
 // in LDS:  in_k = [state_k (10) | chunk input of level k]  for every level, where the chunk input of level 0 is PReLU_p(y1) and
 // that of level k >= 1 is level k-1's output.  The state is copied into LDS before any of it is overwritten; the new state
 // is the last 10 entries of in_k (old entries shifted where the chunk is shorter than 10 frames).  Output j of level k reads
 // in_k[s j .. s j + 10] (s = 1 for level 0, 2 below): the same operands, FMA order and merge order as srf_causal_dw_kernel /
 // srf_causal_merge_kernel on the whole sequence, because chunk boundaries fall on even positions of every strided level.
+// The LDS stride of a row comes from the launch's largest frames; every row lays out its levels (stream_pyr_off) and bounds
+// its loops by its OWN frames, so the four rows of a wavefront may belong to streams with different chunk lengths.  The
+// barriers are unconditional.
 // ---------------------------------------------------------------------------------------------
 struct StreamPyrArgs {
   const float* y1;
@@ -138,8 +193,7 @@ struct StreamPyrArgs {
   const float* w[SRF_MAX_DEPTH];
   const float* b[SRF_MAX_DEPTH];
   const float* a[SRF_MAX_DEPTH];
-  int C, Bt, Lc;
-  int chan_major;   // rows of y1 / merged ordered (c, b) (the push's layout) instead of (b, c)
+  int C;
   long rows;
 };
 
@@ -150,17 +204,18 @@ __host__ __device__ constexpr int stream_pyr_off(int k, int Lc) {   // offset of
   return o;
 }
 
-template <int D>
-__global__ __launch_bounds__(64) void srf_stream_pyramid_kernel(StreamPyrArgs a) {
+template <int D, class M>
+__global__ __launch_bounds__(64) void srf_stream_pyramid_kernel(StreamPyrArgs a, M m) {
   extern __shared__ float sm[];
-  const int Lc = a.Lc;
-  const int per_row = stream_pyr_off<D>(D, Lc) + (Lc >> (D - 1));
+  const int Lm = m.max_frames();
+  const int per_row = stream_pyr_off<D>(D, Lm) + (Lm >> (D - 1));
   const int sub = threadIdx.x & 15;
   const long r = (long)blockIdx.x * SRF_STREAM_RPW + (threadIdx.x >> 4);
   const bool live = r < a.rows;
-  const int c = live ? (a.chan_major ? (int)(r / a.Bt) : (int)(r % a.C)) : 0;
-  const int b = live ? (a.chan_major ? (int)(r % a.Bt) : (int)(r / a.C)) : 0;
-  const size_t srow = ((size_t)b * a.C + c) * SRF_STREAM_HIST;
+  int c = 0, sl = 0, Lc = 0;
+  size_t yoff = 0;
+  if (live) m.pyr_row(r, a.C, c, sl, yoff, Lc);
+  const size_t srow = ((size_t)sl * a.C + c) * SRF_STREAM_HIST;
   float* row = sm + (size_t)(threadIdx.x >> 4) * per_row;
   if (live) {
     if (sub < SRF_STREAM_HIST) {
@@ -168,7 +223,7 @@ __global__ __launch_bounds__(64) void srf_stream_pyramid_kernel(StreamPyrArgs a)
       for (int k = 0; k < D; ++k) row[stream_pyr_off<D>(k, Lc) + sub] = a.state[k][srow + sub];
     }
     const float ap = a.in_prelu[0];
-    const float* yr = a.y1 + (size_t)r * Lc;
+    const float* yr = a.y1 + yoff;
     for (int i = sub; i < Lc; i += 16) row[SRF_STREAM_HIST + i] = srf_prelu(yr[i], ap);
   }
   __syncthreads();
@@ -196,7 +251,7 @@ __global__ __launch_bounds__(64) void srf_stream_pyramid_kernel(StreamPyrArgs a)
     __syncthreads();
   }
   if (live) {
-    float* mr = a.merged + (size_t)r * Lc;
+    float* mr = a.merged + yoff;
     for (int j = sub; j < Lc; j += 16) {
       float acc = row[stream_pyr_off<D>(D, Lc) + (j >> (D - 1))];
 #pragma unroll
@@ -213,21 +268,23 @@ static size_t stream_pyr_lds(int D, int Lc) {
   return sizeof(float) * per_row * SRF_STREAM_RPW;
 }
 
-static int stream_pyramid_launch(const StreamPyrArgs& a, int D, hipStream_t st) {
-  const size_t lds = stream_pyr_lds(D, a.Lc);
+// max_frames: the largest frames of the launch's rows (what m.max_frames() returns on the device)
+template <class M>
+static int stream_pyramid_launch(const StreamPyrArgs& a, const M& m, int max_frames, int D, hipStream_t st) {
+  const size_t lds = stream_pyr_lds(D, max_frames);
   const long blocks = (a.rows + SRF_STREAM_RPW - 1) / SRF_STREAM_RPW;
-  SRF_CHECK_ARG(lds <= SRF_STREAM_LDS_MAX, "srf_causal_stream_pyramid: a chunk of %d frames does not fit LDS at depth %d", a.Lc, D);
+  SRF_CHECK_ARG(lds <= SRF_STREAM_LDS_MAX, "srf_causal_stream_pyramid: a chunk of %d frames does not fit LDS at depth %d", max_frames, D);
   SRF_CHECK_ARG(blocks < (1L << 31), "srf_causal_stream_pyramid: too many rows");
   dim3 grid((unsigned)blocks), block(64);
   switch (D) {
-    case 1: hipLaunchKernelGGL(srf_stream_pyramid_kernel<1>, grid, block, lds, st, a); break;
-    case 2: hipLaunchKernelGGL(srf_stream_pyramid_kernel<2>, grid, block, lds, st, a); break;
-    case 3: hipLaunchKernelGGL(srf_stream_pyramid_kernel<3>, grid, block, lds, st, a); break;
-    case 4: hipLaunchKernelGGL(srf_stream_pyramid_kernel<4>, grid, block, lds, st, a); break;
-    case 5: hipLaunchKernelGGL(srf_stream_pyramid_kernel<5>, grid, block, lds, st, a); break;
-    case 6: hipLaunchKernelGGL(srf_stream_pyramid_kernel<6>, grid, block, lds, st, a); break;
-    case 7: hipLaunchKernelGGL(srf_stream_pyramid_kernel<7>, grid, block, lds, st, a); break;
-    default: hipLaunchKernelGGL(srf_stream_pyramid_kernel<8>, grid, block, lds, st, a); break;
+    case 1: hipLaunchKernelGGL((srf_stream_pyramid_kernel<1, M>), grid, block, lds, st, a, m); break;
+    case 2: hipLaunchKernelGGL((srf_stream_pyramid_kernel<2, M>), grid, block, lds, st, a, m); break;
+    case 3: hipLaunchKernelGGL((srf_stream_pyramid_kernel<3, M>), grid, block, lds, st, a, m); break;
+    case 4: hipLaunchKernelGGL((srf_stream_pyramid_kernel<4, M>), grid, block, lds, st, a, m); break;
+    case 5: hipLaunchKernelGGL((srf_stream_pyramid_kernel<5, M>), grid, block, lds, st, a, m); break;
+    case 6: hipLaunchKernelGGL((srf_stream_pyramid_kernel<6, M>), grid, block, lds, st, a, m); break;
+    case 7: hipLaunchKernelGGL((srf_stream_pyramid_kernel<7, M>), grid, block, lds, st, a, m); break;
+    default: hipLaunchKernelGGL((srf_stream_pyramid_kernel<8, M>), grid, block, lds, st, a, m); break;
   }
   SRF_CHECK_LAUNCH("stream_pyramid", st);
   return SRF_OK;
@@ -254,66 +311,70 @@ extern "C" int srf_causal_stream_pyramid(const float* y1, float* merged, float* 
     a.a[k] = prelu[k];
   }
   a.C = C;
-  a.Bt = Bt;
-  a.Lc = Lc;
-  a.chan_major = 0;
   a.rows = (long)Bt * C;
-  return stream_pyramid_launch(a, D, (hipStream_t)stream);
+  const StreamRowsUniform m{Bt, Lc, 0};
+  return stream_pyramid_launch(a, m, Lc, D, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
-// decoder overlap-add.  z[(co K + k)][b Lc + l] are the frame values (stream_pw over the transposed decoder weight, with
-// mask_nl_class's PReLU applied on load).  Position i of the push = sample pos - h + i; frame l covers i = h l .. h l + 2h.
-//   i < n:       out[b,co,i]  = tail[i] (i <= h) + the frames covering i, ascending l
+// decoder overlap-add.  z[(co K + k)][col0 + l] are the frame values of a row (stream_pw over the transposed decoder weight,
+// with mask_nl_class's PReLU applied on load).  Position i of the row's push = sample pos - h + i; frame l covers
+// i = h l .. h l + 2h; n = h frames of THIS row.
+//   i < n:       out[co,i]  = tail[i] (i <= h) + the frames covering i, ascending l
 //   n <= i <= n+h: new tail[i - n] = tail[i] (only where i <= h) + the frames covering i
 // Starting from the stored partial sum and adding frames in ascending order gives the same bits wherever the chunk was cut.
-// The block (0, 0, b) also rolls stream b's encoder history: no encoder block of this push is still running.
+// The block (0, 0, row) also rolls the encoder history of the row's slot: no encoder block of this push is still running.
 // ---------------------------------------------------------------------------------------------
 // sum of position i: the stored partial sum (i <= h) plus the frames covering i, ascending
-__device__ __forceinline__ float srf_stream_ola_at(const float* __restrict__ z, const float* tl, int i, int co, int b, int H, int K,
-                                                   int Lc, int Bt) {
+__device__ __forceinline__ float srf_stream_ola_at(const float* __restrict__ z, const float* tl, int i, int co, int c0, int H, int K,
+                                                   int Lc, size_t ld) {
   float acc = i <= H ? tl[i] : 0.f;
   const int l_lo = i < 2 * H ? 0 : (i - H - 1) / H;   // ceil((i - 2h) / h)
   const int l_hi = min(Lc - 1, i / H);
-  const size_t ld = (size_t)Bt * Lc;
-  for (int l = l_lo; l <= l_hi; ++l) acc += z[(size_t)(co * K + i - H * l) * ld + (size_t)b * Lc + l];
+  for (int l = l_lo; l <= l_hi; ++l) acc += z[(size_t)(co * K + i - H * l) * ld + (size_t)c0 + l];
   return acc;
 }
 
-// grid (ceil(n / 256), S*A, Bt).  Block x = 0 is the only reader and writer of its (b, co) tail (h + 1 <= 256 entries): it
-// reads all of it before a barrier and writes the new one after it.
+// grid (ceil(longest n / 256), S*A, rows).  Block x = 0 is the only reader and writer of its (slot, co) tail (h + 1 <= 256
+// entries): it reads all of it before a barrier and writes the new one after it.  Threads with i >= the row's n write nothing.
+template <class M>
 __global__ __launch_bounds__(256) void srf_stream_ola_kernel(const float* __restrict__ z, float* __restrict__ tail,
                                                              float* __restrict__ out, const float* __restrict__ wav,
-                                                             float* __restrict__ hist, int A, int SA, int K, int Lc, int n,
-                                                             int Bt) {
+                                                             float* __restrict__ hist, int A, int SA, int K, M m) {
   const int H = K / 2;
-  const int b = blockIdx.z, co = blockIdx.y;
+  const int j = blockIdx.z, co = blockIdx.y;
   const int tid = threadIdx.x;
   const int i = blockIdx.x * 256 + tid;
-  float* tl = tail + ((size_t)b * SA + co) * (H + 1);
-  if (i < n) out[((size_t)b * SA + co) * n + i] = srf_stream_ola_at(z, tl, i, co, b, H, K, Lc, Bt);
+  const int Lc = m.frames(j), n = H * Lc, sl = m.slot(j), c0 = m.col0(j);
+  const size_t ld = m.ncol();
+  float* tl = tail + ((size_t)sl * SA + co) * (H + 1);
+  if (i < n) out[(size_t)SA * H * c0 + (size_t)co * n + i] = srf_stream_ola_at(z, tl, i, co, c0, H, K, Lc, ld);
   if (blockIdx.x != 0) return;
-  const float pend = tid <= H ? srf_stream_ola_at(z, tl, n + tid, co, b, H, K, Lc, Bt) : 0.f;
+  const float pend = tid <= H ? srf_stream_ola_at(z, tl, n + tid, co, c0, H, K, Lc, ld) : 0.f;
   __syncthreads();
   if (tid <= H) tl[tid] = pend;
   if (co != 0) return;
+  const float* wr = wav + (size_t)A * H * c0;   // this row's [A, n] block
   for (int a = 0; a < A; ++a) {
-    float* hr = hist + ((size_t)b * A + a) * 2 * H;
+    float* hr = hist + ((size_t)sl * A + a) * 2 * H;
     const int s = n + tid;   // index into [hist | chunk]
     float v = 0.f;
-    if (tid < 2 * H) v = s < 2 * H ? hr[s] : wav[((size_t)b * A + a) * n + s - 2 * H];
+    if (tid < 2 * H) v = s < 2 * H ? hr[s] : wr[(size_t)a * n + s - 2 * H];
     __syncthreads();
     if (tid < 2 * H) hr[tid] = v;
   }
 }
 
-// out_tail[b,co,j] = tail[b,co,j], j < h: the pending samples as they are (the stream's last h samples once zeros were fed)
+// out[j,co,t] = tail[slot(j),co,t], t < h, for the `rows` rows of the launch: the pending samples as they are (the stream's
+// last h samples once zeros were fed)
+template <class M>
 __global__ __launch_bounds__(256) void srf_stream_flush_kernel(const float* __restrict__ tail, float* __restrict__ out, long rows,
-                                                               int H) {
-  const long n = rows * H;
+                                                               int SA, int H, M m) {
+  const long n = rows * SA * H;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const long r = i / H;
-    out[i] = tail[r * (H + 1) + (i - r * H)];
+    const long r = i / H;            // (j, co)
+    const int j = (int)(r / SA), co = (int)(r - (long)j * SA);
+    out[i] = tail[((size_t)m.slot(j) * SA + co) * (H + 1) + (i - r * H)];
   }
 }
 
@@ -497,22 +558,12 @@ extern "C" int srf_stream_reset(const srf_stream* s, void* state, int row, void*
   return SRF_OK;
 }
 
-extern "C" int srf_stream_push(const srf_stream* s, const void* weights_buf, void* state, const float* wav, int n, float* out,
-                               void* workspace, size_t workspace_bytes, void* stream) {
-  SRF_CHECK_ARG(s && weights_buf && state && wav && out && workspace, "srf_stream_push: null pointer");
-  SRF_CHECK_ARG(n > 0, "srf_stream_push: n = %d samples (must be positive)", n);
-  SRF_CHECK_ARG(n % s->g == 0, "srf_stream_push: n = %d is not a multiple of the granule %d", n, s->g);
-  SRF_CHECK_ARG(n <= s->max_n, "srf_stream_push: n = %d exceeds the session's max_chunk_samples %d", n, s->max_n);
-  SRF_CHECK_ARG(workspace_bytes >= sizeof(float) * s->ws_floats, "srf_stream_push: workspace of %zu bytes is too small (need %zu)",
-                workspace_bytes, sizeof(float) * s->ws_floats);
-  SRF_CHECK_ARG((((size_t)weights_buf | (size_t)state | (size_t)workspace) & 255) == 0,
-                "srf_stream_push: weights_buf %p, state %p and workspace %p must be 256-byte aligned", weights_buf, state, workspace);
-  hipStream_t st = (hipStream_t)stream;
-  const float* wb = (const float*)weights_buf;
-  float* sp = (float*)state;
-  float* ws = (float*)workspace;
-  const int Bt = s->Bt, Lc = n / s->h, D = s->D;
-  const long ncol = (long)Bt * Lc;
+// The launches of one push.  ncol columns in all; the encoder, the pyramids and the overlap-add go out once per group of rows
+// (mapper grp[i], its largest frames maxf[i], its rows nrows[i]), the 1x1 GEMMs once over all columns.
+template <class M>
+static int stream_forward(const srf_stream* s, const float* wb, float* sp, const float* wav, float* out, float* ws, long ncol,
+                          const M* grp, const int* maxf, const int* nrows, int ngrp, hipStream_t st) {
+  const int D = s->D;
   auto W = [&](int p) { return wb + s->w_off[p]; };
   float* enc = ws + s->ws_enc;
   float* cur = ws + s->ws_xa;
@@ -522,10 +573,10 @@ extern "C" int srf_stream_push(const srf_stream* s, const void* weights_buf, voi
   float* masks = ws + s->ws_masks;
   float* z = ws + s->ws_z;
   float* hist = sp + s->st_hist;
-  {
+  for (int gi = 0; gi < ngrp; ++gi) {
     const size_t lds = sizeof(float) * (size_t)s->A * (7 * s->h + s->K);
-    hipLaunchKernelGGL(srf_stream_enc_kernel, dim3((s->N + 31) / 32, (Lc + 7) / 8, Bt), dim3(256), lds, st, wav, hist, W(0), enc,
-                       s->A, n, s->N, s->K, Lc, Bt);
+    hipLaunchKernelGGL(srf_stream_enc_kernel<M>, dim3((s->N + 31) / 32, (maxf[gi] + 7) / 8, nrows[gi]), dim3(256), lds, st, wav,
+                       hist, W(0), enc, s->A, s->N, s->K, grp[gi]);
     SRF_CHECK_LAUNCH("stream_encoder", st);
   }
   int rc = stream_pw(enc, W(1), W(2), nullptr, nullptr, cur, s->N, s->B, ncol, st);
@@ -539,18 +590,17 @@ extern "C" int srf_stream_push(const srf_stream* s, const void* weights_buf, voi
     a.merged = merged;
     a.in_prelu = W(pb + 3);
     for (int k = 0; k < D; ++k) {
-      a.state[k] = sp + s->st_dw + ((size_t)i * D + k) * Bt * s->C * SRF_STREAM_HIST;
+      a.state[k] = sp + s->st_dw + ((size_t)i * D + k) * s->Bt * s->C * SRF_STREAM_HIST;
       a.w[k] = W(pb + 4 + 3 * k);
       a.b[k] = W(pb + 5 + 3 * k);
       a.a[k] = W(pb + 6 + 3 * k);
     }
     a.C = s->C;
-    a.Bt = Bt;
-    a.Lc = Lc;
-    a.chan_major = 1;
-    a.rows = (long)Bt * s->C;
-    rc = stream_pyramid_launch(a, D, st);
-    if (rc) return rc;
+    for (int gi = 0; gi < ngrp; ++gi) {
+      a.rows = (long)nrows[gi] * s->C;
+      rc = stream_pyramid_launch(a, grp[gi], maxf[gi], D, st);
+      if (rc) return rc;
+    }
     rc = stream_pw(merged, W(pb + 4 + 3 * D), W(pb + 5 + 3 * D), nullptr, cur, nxt, s->C, s->B, ncol, st);
     if (rc) return rc;
     float* t = cur;
@@ -562,19 +612,107 @@ extern "C" int srf_stream_push(const srf_stream* s, const void* weights_buf, voi
   if (rc) return rc;
   rc = stream_pw(masks, W(pt + 3), nullptr, W(pt + 4), nullptr, z, s->SA * s->N, s->M, ncol, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(srf_stream_ola_kernel, dim3((n + 255) / 256, s->SA, Bt), dim3(256), 0, st, z, sp + s->st_tail, out,
-                     wav, hist, s->A, s->SA, s->K, Lc, n, Bt);
-  SRF_CHECK_LAUNCH("stream_ola", st);
+  for (int gi = 0; gi < ngrp; ++gi) {
+    hipLaunchKernelGGL(srf_stream_ola_kernel<M>, dim3((s->h * maxf[gi] + 255) / 256, s->SA, nrows[gi]), dim3(256), 0, st, z,
+                       sp + s->st_tail, out, wav, hist, s->A, s->SA, s->K, grp[gi]);
+    SRF_CHECK_LAUNCH("stream_ola", st);
+  }
   return SRF_OK;
+}
+
+extern "C" int srf_stream_push(const srf_stream* s, const void* weights_buf, void* state, const float* wav, int n, float* out,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  SRF_CHECK_ARG(s && weights_buf && state && wav && out && workspace, "srf_stream_push: null pointer");
+  SRF_CHECK_ARG(n > 0, "srf_stream_push: n = %d samples (must be positive)", n);
+  SRF_CHECK_ARG(n % s->g == 0, "srf_stream_push: n = %d is not a multiple of the granule %d", n, s->g);
+  SRF_CHECK_ARG(n <= s->max_n, "srf_stream_push: n = %d exceeds the session's max_chunk_samples %d", n, s->max_n);
+  SRF_CHECK_ARG(workspace_bytes >= sizeof(float) * s->ws_floats, "srf_stream_push: workspace of %zu bytes is too small (need %zu)",
+                workspace_bytes, sizeof(float) * s->ws_floats);
+  SRF_CHECK_ARG((((size_t)weights_buf | (size_t)state | (size_t)workspace) & 255) == 0,
+                "srf_stream_push: weights_buf %p, state %p and workspace %p must be 256-byte aligned", weights_buf, state, workspace);
+  const int Lc = n / s->h;
+  const StreamRowsUniform m{s->Bt, Lc, 1};
+  return stream_forward(s, (const float*)weights_buf, (float*)state, wav, out, (float*)workspace, (long)s->Bt * Lc, &m, &Lc,
+                        &s->Bt, 1, (hipStream_t)stream);
+}
+
+extern "C" int srf_stream_push_rows_num_launches(const srf_stream* s, int m) {
+  if (!s || m < 1) return 0;
+  const int groups = (m + SRF_STREAM_ROWS_PER_LAUNCH - 1) / SRF_STREAM_ROWS_PER_LAUNCH;
+  return 2 * s->U + 3 + groups * (s->U + 2);
+}
+
+// One push for any subset of the session's streams, each with its own number of granules.  rows is a HOST array; everything a
+// kernel will index with is checked here, and the row tables travel as kernel arguments (no device-side table, no copy).
+extern "C" int srf_stream_push_rows(const srf_stream* s, const void* weights_buf, void* state, const srf_stream_row* rows, int m,
+                                    const float* wav, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  SRF_CHECK_ARG(s && weights_buf && state && rows && wav && out && workspace, "srf_stream_push_rows: null pointer");
+  SRF_CHECK_ARG(m >= 1 && m <= s->Bt, "srf_stream_push_rows: m = %d rows out of range (1..%d, the session's batch)", m, s->Bt);
+  SRF_CHECK_ARG(workspace_bytes >= sizeof(float) * s->ws_floats, "srf_stream_push_rows: workspace of %zu bytes is too small (need %zu)",
+                workspace_bytes, sizeof(float) * s->ws_floats);
+  SRF_CHECK_ARG((((size_t)weights_buf | (size_t)state | (size_t)workspace) & 255) == 0,
+                "srf_stream_push_rows: weights_buf %p, state %p and workspace %p must be 256-byte aligned", weights_buf, state, workspace);
+  const int ngrp = (m + SRF_STREAM_ROWS_PER_LAUNCH - 1) / SRF_STREAM_ROWS_PER_LAUNCH;
+  std::vector<unsigned char> seen((size_t)s->Bt, 0);
+  std::vector<StreamRowsTable> grp((size_t)ngrp);
+  std::vector<int> maxf((size_t)ngrp, 0), nrows((size_t)ngrp, 0);
+  long ncol = 0;
+  for (int j = 0; j < m; ++j) {
+    const int slot = rows[j].slot, n = rows[j].n;
+    SRF_CHECK_ARG(slot >= 0 && slot < s->Bt, "srf_stream_push_rows: row %d: slot %d out of range (0..%d)", j, slot, s->Bt - 1);
+    SRF_CHECK_ARG(!seen[slot], "srf_stream_push_rows: row %d: slot %d is listed twice (two rows would race on one state)", j, slot);
+    SRF_CHECK_ARG(n > 0, "srf_stream_push_rows: row %d: n = %d samples (must be positive)", j, n);
+    SRF_CHECK_ARG(n % s->g == 0, "srf_stream_push_rows: row %d: n = %d is not a multiple of the granule %d", j, n, s->g);
+    SRF_CHECK_ARG(n <= s->max_n, "srf_stream_push_rows: row %d: n = %d exceeds the session's max_chunk_samples %d", j, n, s->max_n);
+    seen[slot] = 1;
+    const int gi = j / SRF_STREAM_ROWS_PER_LAUNCH, q = j % SRF_STREAM_ROWS_PER_LAUNCH, frames = n / s->h;
+    StreamRowsTable& t = grp[gi];
+    t.slot_[q] = slot;
+    t.col0_[q] = (int)ncol;        // m <= batch rows of at most max_lc frames: ncol <= batch * max_lc, which create bounds
+    t.frames_[q] = frames;
+    ncol += frames;
+    nrows[gi] = q + 1;
+    if (frames > maxf[gi]) maxf[gi] = frames;
+  }
+  for (int gi = 0; gi < ngrp; ++gi) {
+    StreamRowsTable& t = grp[gi];
+    for (int q = nrows[gi]; q < SRF_STREAM_ROWS_PER_LAUNCH; ++q) t.slot_[q] = t.col0_[q] = t.frames_[q] = 0;   // never indexed
+    t.rows = nrows[gi];
+    t.max_frames_ = maxf[gi];
+    t.ncol_ = (int)ncol;
+  }
+  return stream_forward(s, (const float*)weights_buf, (float*)state, wav, out, (float*)workspace, ncol, grp.data(), maxf.data(),
+                        nrows.data(), ngrp, (hipStream_t)stream);
 }
 
 extern "C" int srf_stream_flush(const srf_stream* s, const void* state, float* out_tail, void* stream) {
   SRF_CHECK_ARG(s && state && out_tail, "srf_stream_flush: null pointer");
   SRF_CHECK_ARG(((size_t)state & 255) == 0, "srf_stream_flush: state %p is not 256-byte aligned", state);
-  const long rows = (long)s->Bt * s->SA, n = rows * s->h, blocks = (n + 255) / 256;
+  const long n = (long)s->Bt * s->SA * s->h, blocks = (n + 255) / 256;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(srf_stream_flush_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st,
-                     (const float*)state + s->st_tail, out_tail, rows, s->h);
+  const StreamRowsUniform m{s->Bt, 0, 0};
+  hipLaunchKernelGGL(srf_stream_flush_kernel<StreamRowsUniform>, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st,
+                     (const float*)state + s->st_tail, out_tail, (long)s->Bt, s->SA, s->h, m);
   SRF_CHECK_LAUNCH("stream_flush", st);
+  return SRF_OK;
+}
+
+// out_tail[j] = the pending h samples of slots[j] (a HOST array), j < m; the state is left unchanged
+extern "C" int srf_stream_flush_rows(const srf_stream* s, const void* state, const int* slots, int m, float* out_tail, void* stream) {
+  SRF_CHECK_ARG(s && state && slots && out_tail, "srf_stream_flush_rows: null pointer");
+  SRF_CHECK_ARG(((size_t)state & 255) == 0, "srf_stream_flush_rows: state %p is not 256-byte aligned", state);
+  SRF_CHECK_ARG(m >= 1 && m <= s->Bt, "srf_stream_flush_rows: m = %d rows out of range (1..%d, the session's batch)", m, s->Bt);
+  for (int j = 0; j < m; ++j)
+    SRF_CHECK_ARG(slots[j] >= 0 && slots[j] < s->Bt, "srf_stream_flush_rows: row %d: slot %d out of range (0..%d)", j, slots[j], s->Bt - 1);
+  hipStream_t st = (hipStream_t)stream;
+  for (int j0 = 0; j0 < m; j0 += SRF_STREAM_ROWS_PER_LAUNCH) {
+    StreamRowsTable t = {};
+    t.rows = m - j0 < SRF_STREAM_ROWS_PER_LAUNCH ? m - j0 : SRF_STREAM_ROWS_PER_LAUNCH;
+    for (int q = 0; q < t.rows; ++q) t.slot_[q] = slots[j0 + q];
+    const long n = (long)t.rows * s->SA * s->h, blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(srf_stream_flush_kernel<StreamRowsTable>, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st,
+                       (const float*)state + s->st_tail, out_tail + (size_t)j0 * s->SA * s->h, (long)t.rows, s->SA, s->h, t);
+    SRF_CHECK_LAUNCH("stream_flush", st);
+  }
   return SRF_OK;
 }

@@ -259,6 +259,13 @@ class CausalSuDORMRF(nn.Module):
         from ...streaming import CausalStream
         return CausalStream(self, batch=batch, max_chunk=max_chunk, device=device)
 
+    def stream_pool(self, capacity, max_chunk=None, device=None):
+        """Up to `capacity` streams that open, push and close independently of each other
+        (sudo_rm_rf_amd.streaming.CausalStreamPool): one push serves any subset of them, each with its own number of samples,
+        in one pass of the kernels, and each stream gets the bits a stream(batch=1) of its own would return."""
+        from ...streaming import CausalStreamPool
+        return CausalStreamPool(self, capacity, max_chunk=max_chunk, device=device)
+
     def pad_to_appropriate_length(self, x):
         """Kept for API parity; the HIP path folds the padding into its bounds checks."""
         input_length = x.shape[-1]

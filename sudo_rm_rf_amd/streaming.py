@@ -1,4 +1,5 @@
-"""Stateful streaming inference for the causal SuDoRM-RF (v3): ``CausalSuDORMRF.stream()`` returns a ``CausalStream``.
+"""Stateful streaming inference for the causal SuDoRM-RF (v3): ``CausalSuDORMRF.stream()`` returns a ``CausalStream``,
+``CausalSuDORMRF.stream_pool()`` a ``CausalStreamPool`` whose streams open, push and close independently of each other.
 
 A session owns three device buffers (prepared weights, state, workspace) and a small remainder of samples that do not
 fill a granule yet.  ``push`` takes any number of new samples per stream and returns every separated sample that
@@ -55,6 +56,20 @@ def _buffer(nbytes, device):
     return t
 
 
+def _prepare_weights(owner, who):
+    """srf_stream_prepare of owner._module's parameters into owner._weights (CausalStream and CausalStreamPool)."""
+    if owner._module._config_tuple() != owner._cfg_tuple:
+        raise _lib.SrfError("%s: the module's configuration or block scales changed; open a new stream" % who)
+    params = [p.detach() for p in _weights(owner._module)]
+    for p in params:
+        if p.device != owner.device or p.dtype != torch.float32 or not p.is_contiguous():
+            raise _lib.SrfError("all parameters must be contiguous float32 on %s" % owner.device)
+    arr = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
+    with torch.cuda.device(owner.device):
+        rc = _lib.load().srf_stream_prepare(owner._s.handle, arr, len(params), _lib.ptr(owner._weights), owner._stream())
+    _lib.check(rc, "srf_stream_prepare")
+
+
 class CausalStream:
     """One streaming session over ``batch`` independent streams of a CausalSuDORMRF.
 
@@ -104,16 +119,7 @@ class CausalStream:
     # -- weights and state -------------------------------------------------------------------
     def refresh_weights(self):
         """Snapshot the module's parameters again (srf_stream_prepare): skipinit_gain is read on the device."""
-        if self._module._config_tuple() != self._cfg_tuple:
-            raise _lib.SrfError("CausalStream: the module's configuration or block scales changed; open a new stream")
-        params = [p.detach() for p in _weights(self._module)]
-        for p in params:
-            if p.device != self.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % self.device)
-        arr = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-        with torch.cuda.device(self.device):
-            rc = _lib.load().srf_stream_prepare(self._s.handle, arr, len(params), _lib.ptr(self._weights), self._stream())
-        _lib.check(rc, "srf_stream_prepare")
+        _prepare_weights(self, "CausalStream")
 
     def reset(self, rows=None):
         """Start new streams.  rows=None: every stream, position and remainder included.  rows=[...]: only those streams'
@@ -206,3 +212,232 @@ class CausalStream:
             y = torch.cat(outs, dim=-1)[..., :T - self._emitted].contiguous()
             self.reset()
             return y
+
+
+class _PoolStream:
+    """What CausalStream keeps per session, per stream of a pool."""
+
+    def __init__(self, slot, rem):
+        self.slot = slot
+        self.rem = rem             # [A, r] on the device: samples that do not fill a granule yet
+        self.pos = 0               # samples pushed through the kernels since open()
+        self.emitted = 0           # samples returned since open()
+        self.head_pending = True   # the next output still starts with `delay` negative-time samples
+
+
+class CausalStreamPool:
+    """Up to ``capacity`` streams of one CausalSuDORMRF that open, push and close independently: one ``push`` serves any
+    subset of them, each with its own number of samples, in ONE pass of the kernels (srf_stream_push_rows), and every stream
+    gets bit for bit what a ``CausalStream(batch=1)`` of its own would have returned.
+
+    The weights are snapshot at construction (and by ``refresh_weights()``), as for ``CausalStream``."""
+
+    def __init__(self, module, capacity, max_chunk=None, device=None):
+        from .dnn.models.causal_improved_sudormrf_v3 import _refuse_autograd
+        self._module = module
+        _refuse_autograd("CausalSuDORMRF.stream_pool", list(module.parameters()))
+        weights = _weights(module)
+        device = torch.device(device) if device is not None else weights[0].device
+        if device.type != "cuda":
+            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: the module is on %s.  There is deliberately no CPU "
+                                "fallback (use the reference implementation for CPU inference)." % device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device
+        self._cfg_tuple = module._config_tuple()
+        self._s = _Session(self._cfg_tuple, capacity, max_chunk)
+        self._A = module.in_audio_channels
+        self._SA = module.num_sources * module.in_audio_channels
+        self._pad_unit = module.n_least_samples_req
+        # the documented state layout (include/sudormrf_hip.h): three sections, each padded to 64 floats
+        h, Bt = self._s.delay, self._s.batch
+        self._UD, self._C = module.num_blocks * module.upsampling_depth, module.in_channels
+        a64 = lambda n: -(-n // 64) * 64
+        self._off_dw = a64(Bt * self._A * 2 * h)
+        self._off_tail = self._off_dw + a64(self._UD * Bt * self._C * 10)
+        with torch.cuda.device(device):
+            self._weights = _buffer(self._s.weights_bytes, device)
+            self._state = _buffer(self._s.state_bytes, device)
+            self._workspace = _buffer(self._s.workspace_bytes, device)
+        self._streams = {}         # sid -> _PoolStream
+        self._next_sid = 0
+        self.refresh_weights()
+
+    # -- geometry ----------------------------------------------------------------------------
+    granule = property(lambda self: self._s.granule, doc="samples per granule g = h * 2^(D-1): pushes are cut at multiples of it")
+    delay = property(lambda self: self._s.delay, doc="output delay h = enc_kernel_size // 2 samples")
+    state_bytes = property(lambda self: self._s.state_bytes, doc="device bytes of state of all `capacity` streams")
+    capacity = property(lambda self: self._s.batch, doc="the most streams that can be open at once")
+    max_chunk = property(lambda self: self._s.max_chunk)
+    active = property(lambda self: sorted(self._streams), doc="the open stream ids")
+
+    def num_launches(self, m):
+        """Kernel launches of one pass over m streams (srf_stream_push_rows_num_launches)."""
+        return _lib.load().srf_stream_push_rows_num_launches(self._s.handle, int(m))
+
+    def slot_of(self, sid):
+        """The state slot (0 .. capacity - 1) stream `sid` occupies."""
+        return self._get(sid).slot
+
+    def _stream(self):
+        return _lib.current_stream(self.device)
+
+    def _get(self, sid):
+        st = self._streams.get(sid)
+        if st is None:
+            raise _lib.SrfError("CausalStreamPool: stream %r is not open" % (sid,))
+        return st
+
+    def refresh_weights(self):
+        """Snapshot the module's parameters again (srf_stream_prepare): skipinit_gain is read on the device."""
+        _prepare_weights(self, "CausalStreamPool")
+
+    def _sections(self, slot):
+        """Views of one slot's encoder history [A, 2h], depthwise state [U*D, C, 10] and decoder tail [S*A, h+1]."""
+        f = self._state.view(torch.float32)
+        h, Bt, A, SA = self._s.delay, self._s.batch, self._A, self._SA
+        hist = f[:Bt * A * 2 * h].view(Bt, A, 2 * h)[slot]
+        dw = f[self._off_dw:self._off_dw + self._UD * Bt * self._C * 10].view(self._UD, Bt, self._C, 10)[:, slot]
+        tail = f[self._off_tail:self._off_tail + Bt * SA * (h + 1)].view(Bt, SA, h + 1)[slot]
+        return {"hist": hist, "dw": dw, "tail": tail}
+
+    # -- life of a stream --------------------------------------------------------------------
+    def open(self):
+        """Start a stream in the lowest free slot (its state zeroed) and return its id.  No other stream is touched and no
+        granule boundary is needed: nothing is shared between streams."""
+        used = {st.slot for st in self._streams.values()}
+        slot = next((i for i in range(self._s.batch) if i not in used), None)
+        if slot is None:
+            raise _lib.SrfError("CausalStreamPool: all %d streams are open" % self._s.batch)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().srf_stream_reset(self._s.handle, _lib.ptr(self._state), slot, self._stream()), "srf_stream_reset")
+            rem = torch.empty((self._A, 0), dtype=torch.float32, device=self.device)
+        sid = self._next_sid
+        self._next_sid += 1
+        self._streams[sid] = _PoolStream(slot, rem)
+        return sid
+
+    def _check_input(self, sid, x):
+        from .dnn.models.causal_improved_sudormrf_v3 import _refuse_autograd
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("input must be a torch.Tensor")
+        _refuse_autograd("CausalStreamPool.push", [x])
+        if x.device.type != "cuda":
+            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
+                                "fallback (use the reference implementation for CPU inference)." % x.device)
+        if x.dim() != 2 or x.shape[0] != self._A:
+            raise RuntimeError("stream %r: expected input of shape [%d, n], got %s" % (sid, self._A, tuple(x.shape)))
+        if x.device != self.device:
+            raise _lib.SrfError("input is on %s, the stream on %s" % (x.device, self.device))
+        return x.detach().to(torch.float32)
+
+    def _run(self, work):
+        """work: [(_PoolStream, x [A, n])], n a positive multiple of the granule, distinct streams -> [y [S*A, n'] per
+        entry]: the n delayed samples minus the negative-time head after open().  One srf_stream_push_rows per round of at
+        most max_chunk samples per stream."""
+        lib = _lib.load()
+        mc, h, SA = self._s.max_chunk, self._s.delay, self._SA
+        pieces = [[] for _ in work]
+        lo = 0
+        while True:
+            todo = [(i, st, x[:, lo:lo + mc]) for i, (st, x) in enumerate(work) if x.shape[-1] > lo]
+            if not todo:
+                break
+            rows = (_lib.srf_stream_row * len(todo))(*[(st.slot, xi.shape[-1]) for _, st, xi in todo])
+            wav = torch.cat([xi.reshape(-1) for _, _, xi in todo])           # row j: a contiguous [A, n_j] block
+            out = torch.empty(SA * (wav.numel() // self._A), dtype=torch.float32, device=self.device)
+            rc = lib.srf_stream_push_rows(self._s.handle, _lib.ptr(self._weights), _lib.ptr(self._state), rows, len(todo),
+                                          _lib.ptr(wav), _lib.ptr(out), _lib.ptr(self._workspace), self._s.workspace_bytes,
+                                          self._stream())
+            _lib.check(rc, "srf_stream_push_rows")
+            o = 0
+            for i, _, xi in todo:                                            # row j: a contiguous [S*A, n_j] block
+                n = xi.shape[-1]
+                pieces[i].append(out[o:o + SA * n].view(SA, n))
+                o += SA * n
+            lo += mc
+        ys = []
+        for (st, x), p in zip(work, pieces):
+            st.pos += x.shape[-1]
+            y = p[0] if len(p) == 1 else torch.cat(p, dim=-1)
+            if st.head_pending:
+                y = y[:, h:]
+                st.head_pending = False
+            ys.append(y)
+        return ys
+
+    def push(self, chunks):
+        """chunks: {sid: x [A, n]} on the device, any n >= 0 per stream, any subset of the open streams -> {sid: y [S*A, m]}:
+        every sample of that stream that became final (m may be 0: a stream without a whole granule is left out of the
+        launch).  Streams that are not listed are not touched."""
+        g = self._s.granule
+        checked = [(sid, self._get(sid), self._check_input(sid, x)) for sid, x in chunks.items()]
+        with torch.cuda.device(self.device):
+            res, work, sids = {}, [], []
+            for sid, st, x in checked:
+                if st.rem.shape[-1]:
+                    x = torch.cat([st.rem, x], dim=-1)
+                n = x.shape[-1] // g * g
+                st.rem = x[:, n:].clone()
+                if n == 0:
+                    res[sid] = torch.empty((self._SA, 0), dtype=torch.float32, device=self.device)
+                else:
+                    work.append((st, x[:, :n]))
+                    sids.append(sid)
+            for sid, (st, _), y in zip(sids, work, self._run(work) if work else []):
+                res[sid] = y.contiguous()
+                st.emitted += y.shape[-1]
+            return {sid: res[sid] for sid in chunks}
+
+    def close(self, sid):
+        """End of stream `sid`: zero-pad it to the reference's padded length T', return the samples still owed so that
+        cat(its pushes + [close(sid)]) is the full forward's [S*A, T] of its samples, and free its slot."""
+        st = self._get(sid)
+        with torch.cuda.device(self.device):
+            T = st.pos + st.rem.shape[-1]
+            if T == 0:
+                del self._streams[sid]
+                return torch.empty((self._SA, 0), dtype=torch.float32, device=self.device)
+            u = self._pad_unit
+            Tp = u if T < u else -(-T // u) * u
+            outs = []
+            if Tp > st.pos:
+                pad = torch.zeros((self._A, Tp - st.pos), dtype=torch.float32, device=self.device)
+                pad[:, :st.rem.shape[-1]] = st.rem
+                outs += self._run([(st, pad)])
+            tail = torch.empty((1, self._SA, self._s.delay), dtype=torch.float32, device=self.device)
+            slots = (C.c_int * 1)(st.slot)
+            _lib.check(_lib.load().srf_stream_flush_rows(self._s.handle, _lib.ptr(self._state), slots, 1, _lib.ptr(tail),
+                                                         self._stream()), "srf_stream_flush_rows")
+            outs.append(tail[0])
+            y = torch.cat(outs, dim=-1)[:, :T - st.emitted].contiguous()
+            del self._streams[sid]
+            return y
+
+    # -- moving a stream ---------------------------------------------------------------------
+    def export_state(self, sid):
+        """Everything stream `sid` is: clones of its three state sections, its remainder and its host-side counters.
+        import_state() of it into an open stream of a pool of the same configuration continues the stream there."""
+        st = self._get(sid)
+        with torch.cuda.device(self.device):
+            out = {k: v.clone() for k, v in self._sections(st.slot).items()}
+            out.update(rem=st.rem.clone(), pos=st.pos, emitted=st.emitted, head_pending=st.head_pending, granule=self._s.granule)
+        return out
+
+    def import_state(self, sid, state):
+        """Make the open stream `sid` the continuation of an exported one (its slot stays its own)."""
+        st = self._get(sid)
+        with torch.cuda.device(self.device):
+            mine = self._sections(st.slot)
+            for k, v in mine.items():
+                if k not in state or tuple(state[k].shape) != tuple(v.shape):
+                    raise _lib.SrfError("CausalStreamPool.import_state: section '%s' of shape %s does not fit this pool's %s (another "
+                                        "model geometry)" % (k, tuple(state[k].shape) if k in state else None, tuple(v.shape)))
+            if state["granule"] != self._s.granule or state["rem"].dim() != 2 or state["rem"].shape[0] != self._A or \
+                    state["rem"].shape[1] >= self._s.granule or state["pos"] % self._s.granule:
+                raise _lib.SrfError("CausalStreamPool.import_state: remainder / position do not fit this pool's granule %d"
+                                    % self._s.granule)
+            for k, v in mine.items():
+                v.copy_(state[k])
+            st.rem = state["rem"].to(self.device, torch.float32).clone()
+            st.pos, st.emitted, st.head_pending = int(state["pos"]), int(state["emitted"]), bool(state["head_pending"])
