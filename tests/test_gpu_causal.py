@@ -82,20 +82,9 @@ def test_kernel_mode_1_agrees_with_mode_0(dev, name):
     assert float(np.abs(out1.cpu().numpy() - gold).max()) <= TOL
 
 
-def test_bench_shape_dispatch_and_parity(dev, monkeypatch):
-    from sudo_rm_rf_amd import engine, ops
-    m = _model("causal_default", dev)
-    U = m.num_blocks
-    x4 = cf.make_input("causal_default")
-    gold = np.tile(cf.load_golden("causal_default")["out"], (8, 1, 1))
-    wav = torch.from_numpy(np.tile(x4, (8, 1, 1))).to(dev)
-    eng = m._engine()
-    eng.multi_stream = False
-    with torch.no_grad():
-        with ops.kernel_trace(dev) as tr:
-            out = m(wav)
-    torch.cuda.synchronize()
-    assert float(np.abs(out.cpu().numpy() - gold).max()) <= TOL
+def assert_bench_dispatch(tr, U):
+    """The launch counts of ONE single-stream causal forward at the bench batch (`tr`: its ops.kernel_trace; U blocks).
+    Shared with tests/test_gpu_batch_distinct.py, which asserts the same dispatch at a shorter length."""
     names = [n for n, _ in tr.launches]
     cnt = {n: names.count(n) for n in set(names)}
     # the causal kernels: one fused pyramid per block, no per-level launches, one encoder, one fold of all scales
@@ -110,6 +99,24 @@ def test_bench_shape_dispatch_and_parity(dev, monkeypatch):
     assert cnt.get("pw_conv_bf16x3_w8") == U + 2
     assert set(cnt) <= {"causal_scale", "pack_pw_weights", "causal_encoder", "causal_pyramid", "pw_conv_x3p<0>",
                         "pw_conv_x3p<3>", "pw_conv_bf16x3_w8", "transpose", "zero_fill", "overlap_add"}, cnt
+    return cnt
+
+
+def test_bench_shape_dispatch_and_parity(dev, monkeypatch):
+    from sudo_rm_rf_amd import engine, ops
+    m = _model("causal_default", dev)
+    U = m.num_blocks
+    x4 = cf.make_input("causal_default")
+    gold = np.tile(cf.load_golden("causal_default")["out"], (8, 1, 1))
+    wav = torch.from_numpy(np.tile(x4, (8, 1, 1))).to(dev)
+    eng = m._engine()
+    eng.multi_stream = False
+    with torch.no_grad():
+        with ops.kernel_trace(dev) as tr:
+            out = m(wav)
+    torch.cuda.synchronize()
+    assert float(np.abs(out.cpu().numpy() - gold).max()) <= TOL
+    assert_bench_dispatch(tr, U)
     # explicit two-stream splits and the auto-tuned path give the same rows
     eng.multi_stream = True
     for mode in ("half", "5:3", "auto"):

@@ -108,6 +108,31 @@ _BENCH_BATCH = [("cfg2_improved_u16", 32, _PAIRS), ("cfg3_groupcomm_u8", 32, {"p
                 ("cfg4_improved_u36_n2048", 32, _X3W), ("cfg5_improved_u36_n4096", 16, _X3W)]
 
 
+def assert_bench_dispatch(cfg, tr, families):
+    """The kernel families and launch counts of ONE single-stream forward at the bench batch (`tr`: its ops.kernel_trace).
+    Shared with tests/test_gpu_batch_distinct.py, which asserts the same dispatch at a shorter length."""
+    missing = families - tr.names
+    assert not missing, "single-stream forward did not run %s (ran %s)" % (sorted(missing), sorted(tr.names))
+    count = {n: sum(1 for k, _ in tr.launches if k == n) for n in tr.names}
+    U = cfg.num_blocks
+    if cfg.variant == "improved" and cfg.out_channels == 256:
+        # B = 256 (cfg 2): bottleneck + proj_1x1 of block 0 and res_conv of block i + proj_1x1 of block i + 1 as fused pairs
+        # (srf_pwconv_x3f.hip); the last res_conv and the mask + decoder on the 256 x 128 kernels
+        assert (count["pw_pair_x3f<1>"], count["pw_pair_x3f<2>"], count["pw_conv_x3p<2>"], count["pw_mask_decode"]) == \
+            (1, U - 1, 1, 1), count
+        assert "pw_conv_x3p<0>" not in count and "pw_conv_x3p<1>" not in count, count
+    elif cfg.variant == "improved":   # bottleneck, U x proj_1x1, U x res_conv, mask + decoder -- ALL on the 256 x 128 kernel
+        assert (count["pw_conv_x3p<1>"], count["pw_conv_x3p<0>"], count["pw_conv_x3p<2>"], count["pw_mask_decode"]) == \
+            (1, U, U, 1), count
+    else:                             # GroupComm: bottleneck + mask on it, the per-group convs on the thin-shape kernel
+        assert (count["pw_conv_x3p<1>"], count["pw_mask_decode"], count["pw_conv_small"]) == (1, 1, 2 * U), count
+    # (the fused tail contracts the masked values with the decoder inside the mask GEMM: no GEMM is left on the 128 x 128
+    # kernels and the masked tensor is never stored)
+    assert sum(v for k, v in count.items() if k.startswith("pw_conv_bf16x3") or k == "pw_conv_mfma") == 0, count
+    assert "pw_conv_x3w<3>" not in count and "transpose" not in count, count
+    return count
+
+
 @pytest.mark.parametrize("case,batch,families", _BENCH_BATCH, ids=[c for c, _, _ in _BENCH_BATCH])
 def test_bench_batch_examples_match_reference_golden(manifest, case, batch, families):
     """Every BASELINE configuration AT THE BATCH bench.py TIMES IT (cfg 2 / 3 / 4: 32, cfg 5: 16), through the kernels the
@@ -138,25 +163,7 @@ def test_bench_batch_examples_match_reference_golden(manifest, case, batch, fami
         with torch.no_grad(), ops.kernel_trace(DEV) as tr:
             out = model(x)
         check(out, "single stream")
-        missing = families - tr.names
-        assert not missing, "single-stream forward did not run %s (ran %s)" % (sorted(missing), sorted(tr.names))
-        count = {n: sum(1 for k, _ in tr.launches if k == n) for n in tr.names}
-        U = cfg.num_blocks
-        if cfg.variant == "improved" and cfg.out_channels == 256:
-            # B = 256 (cfg 2): bottleneck + proj_1x1 of block 0 and res_conv of block i + proj_1x1 of block i + 1 as fused pairs
-            # (srf_pwconv_x3f.hip); the last res_conv and the mask + decoder on the 256 x 128 kernels
-            assert (count["pw_pair_x3f<1>"], count["pw_pair_x3f<2>"], count["pw_conv_x3p<2>"], count["pw_mask_decode"]) == \
-                (1, U - 1, 1, 1), count
-            assert "pw_conv_x3p<0>" not in count and "pw_conv_x3p<1>" not in count, count
-        elif cfg.variant == "improved":   # bottleneck, U x proj_1x1, U x res_conv, mask + decoder -- ALL on the 256 x 128 kernel
-            assert (count["pw_conv_x3p<1>"], count["pw_conv_x3p<0>"], count["pw_conv_x3p<2>"], count["pw_mask_decode"]) == \
-                (1, U, U, 1), count
-        else:                             # GroupComm: bottleneck + mask on it, the per-group convs on the thin-shape kernel
-            assert (count["pw_conv_x3p<1>"], count["pw_mask_decode"], count["pw_conv_small"]) == (1, 1, 2 * U), count
-        # (the fused tail contracts the masked values with the decoder inside the mask GEMM: no GEMM is left on the 128 x 128
-        # kernels and the masked tensor is never stored)
-        assert sum(v for k, v in count.items() if k.startswith("pw_conv_bf16x3") or k == "pw_conv_mfma") == 0, count
-        assert "pw_conv_x3w<3>" not in count and "transpose" not in count, count
+        assert_bench_dispatch(cfg, tr, families)
         eng.multi_stream = True
         for parts in eng._split_candidates(batch)[1:]:        # the explicit splits: halves, 5 : 3 and 9 : 7
             out = torch.empty_like(out)

@@ -402,3 +402,28 @@ def test_gradient_check_catches_what_it_claims():
             g["sm.%d.act.weight" % b] *= 1.03           # inside 4 x 1e-2 each, far outside as a vector
     with pytest.raises(AssertionError):
         run(slopes)
+
+
+@pytest.mark.parametrize("name", ["tiny", "groupcomm"])
+def test_torch_oracle_treats_examples_independently(name):
+    """tests/test_gpu_batch_distinct.py computes the reference of a SUBSET of the rows of a bench batch from that subset alone.
+    That is only a reference if the oracle (like the model: SURVEY.md §8e) mixes nothing across examples -- every GlobLN
+    reduces over (channels, time) of ONE example, TAC over the groups of one example.  Pinned here on the tiny Improved and
+    tiny GroupComm configurations of test_gpu_train.CASES at batch 8, with rows that differ in level by up to 400 x: rows
+    [0, 3, 4, 7] run alone equal the same rows of the batch-8 run within 1e-6 (fp32 round-off of outputs of ~0.1: ATen may
+    block a reduction differently for another batch size; a leak of one row's statistics into another's moves it by ~1e-2)."""
+    from oracle import weights
+    from test_gpu_train import CASES
+    cfg, T = next((c, t) for n, c, _, t in CASES if n == name)
+    sd = torch_oracle.to_torch(weights.make_state_dict(cfg, seed=11))
+    A = cfg.in_audio_channels if cfg.variant == "groupcomm" else 1
+    gain = np.geomspace(0.05, 20.0, 8)[[5, 0, 7, 2, 6, 1, 4, 3]].astype(np.float32)
+    wav = torch.from_numpy(weights.make_mixture(8, T, seed=808, channels=A) * gain[:, None, None])
+    rows = [0, 3, 4, 7]
+    with torch.no_grad():
+        whole = torch_oracle.forward(cfg, sd, wav)
+        alone = torch_oracle.forward(cfg, sd, wav[rows].contiguous())
+    assert float(whole.abs().max()) > 1e-2
+    err = float((alone - whole[rows]).abs().max())
+    print(f"{name}: rows {rows} alone vs inside the batch of 8: max abs difference {err:.3e}")
+    assert err <= 1e-6
