@@ -64,7 +64,7 @@ extern "C" {
 
 #define SRF_VARIANT_IMPROVED 0
 #define SRF_VARIANT_GROUPCOMM 1
-#define SRF_VARIANT_CAUSAL 2      /* CausalSuDORMRF (causal_improved_sudormrf_v3.py), ABI 16: inference forward only */
+#define SRF_VARIANT_CAUSAL 2      /* CausalSuDORMRF (causal_improved_sudormrf_v3.py), ABI 16; trains through srf_causal_* only */
 
 /* Constructor arguments of the reference models, same meaning
  * (improved_sudormrf.py:224-231, groupcomm_sudormrf_v2.py:232-241, causal_improved_sudormrf_v3.py CausalSuDORMRF).
@@ -207,7 +207,8 @@ int srf_plan_num_launches(const srf_plan* plan);  /* kernel launches per forward
 /* params: host array of num_params device pointers in the reference's state_dict() order
  * (causal: DESIGN.md §11).  wav: [batch, in_audio_channels, T].  out: [batch, S*in_audio, T].
  * Causal plans: skipinit_gain (a device scalar per block) is folded into res_conv inside the forward, never read by the
- * host; the training entry points, their buffer sizes and srf_separate refuse causal plans with SRF_EINVAL. */
+ * host; srf_forward_train / srf_backward[_wav], their buffer sizes and srf_separate refuse causal plans with SRF_EINVAL --
+ * the causal model trains through the opt-in srf_causal_forward_train / srf_causal_backward below. */
 int srf_forward(const srf_plan* plan, const float* const* params, int num_params,
                 const float* wav, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -404,6 +405,48 @@ int srf_causal_pyramid(const float* y1, float* merged, const float* in_prelu, co
  * srf_prelu_apply: y = PReLU_a(x), slope[0] on the device (a stand-alone nn.PReLU).  n elements, y may alias x. */
 int srf_causal_scale(const float* src, float* dst, long n, const float* dscale, float hscale, void* stream);
 int srf_prelu_apply(const float* x, const float* slope, float* y, long n, void* stream);
+
+/* ---- Training the causal model (opt-in, additive to ABI 19) ----
+ * srf_causal_forward_train: the forward of srf_forward for a causal plan with its 1x1 convolutions in the exact-fp32 class
+ *   (as srf_forward_train, under the same diagnostics switches), keeping in `saved`: encoder output, residual stream
+ *   x_0..x_U, per block proj_1x1's PRE-activation u, the D PRE-activations d_k of the pyramid and merged, and mask_net's output.
+ * srf_causal_backward: grad_out [Bt, S*A, T] -> every parameter gradient, WRITTEN to grads[i] (same order and shapes as params,
+ *   the masked taps of the encoder / depthwise weights as 0); skipinit_gain is read on the device; alpha / beta of
+ *   srf_plan_set_block_scales are honoured.  No gradient w.r.t. wav.
+ * saved / scratch: 256-byte aligned, srf_causal_train_saved_bytes / _scratch_bytes (0 for a non-causal plan); `saved` stays
+ *   untouched between the two calls, `scratch` may be reused in between.  Caller's stream, no host synchronisation; refusals
+ *   (non-causal plan, null pointer, wrong num_params, short or misaligned buffer, L % 4 != 0) return SRF_EINVAL before the
+ *   first launch.
+ * Kernel level.  u = proj_1x1's pre-activation, d_k = level k's, a_k = PReLU_k(d_k) (a_p = PReLU_p(u)), live taps t = 0..10:
+ * srf_causal_dwconv_bwd: ONE level.  G[i] = pairwise-tree sum of g_pool[i * 2^shift .. (i + 1) * 2^shift) (g_pool NULL: 0)
+ *     + sum_t w_next[c, t] g_next[n], n = i + 10 - t (next_stride 1) or (i + 10 - t) / 2 where even (next_stride 2), n < Lnext
+ *     (g_next NULL: none; Lnext = Lout / next_stride);   gd = G * (d > 0 ? 1 : slope)  -- an exact 0 takes the slope, as torch;
+ *   dslope[0] = sum G min(d, 0);  with xin (the conv's input BEFORE its PReLU in_slope, [Bt, C, Lout * stride]):
+ *   dbias[c] = sum gd, dw[c, t] = sum_j gd[j] PReLU(xin[stride j - 10 + t]) (0 left of the row), dw[c, 11..20] = 0.
+ *   xin NULL (proj_1x1's PReLU: d = u, g_next = gd_0, next_stride 1): dw, dbias NULL.  Outputs are written; gd aliases no input.
+ * srf_causal_pyramid_bwd: all D levels and proj_1x1's PReLU of one block in one launch + the finalize launches: g_merged, u, gu
+ *   [Bt, C, L], d[k] [Bt, C, L >> k]; w / prelu: spp_dw[k].conv.weight / .act.weight, in_prelu: proj_1x1.act.weight; dw[k]
+ *   [C, 21], dbias[k] [C], dslope[k] [1], dslope_in [1].  gu is BIT-IDENTICAL to the D + 1 srf_causal_dwconv_bwd calls.  Tiles of
+ *   srf_causal_pyramid_bwd_tile() level-0 frames; _supported: 1 <= D <= 8, L % 2^(D-1) == 0.
+ * scratch (any float-aligned address): srf_causal_dwconv_bwd_scratch_bytes / srf_causal_pyramid_bwd_scratch_bytes: one record of
+ *   partial sums per (row, chunk or tile), added in index order by the finalize launch -- no atomics, same inputs same bits. */
+size_t srf_causal_train_saved_bytes(const srf_plan* plan);
+size_t srf_causal_train_scratch_bytes(const srf_plan* plan);
+int srf_causal_forward_train(const srf_plan* plan, const float* const* params, int num_params, const float* wav, float* out,
+                             void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream);
+int srf_causal_backward(const srf_plan* plan, const float* const* params, float* const* grads, int num_params, const float* wav,
+                        const float* grad_out, const void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                        void* stream);
+size_t srf_causal_dwconv_bwd_scratch_bytes(int Bt, int C, int Lout);
+int srf_causal_dwconv_bwd(const float* g_pool, int shift, const float* g_next, const float* w_next, int next_stride,
+                          const float* d, const float* slope, const float* xin, const float* in_slope, int stride, float* gd,
+                          float* dw, float* dbias, float* dslope, int Bt, int C, int Lout, void* scratch, void* stream);
+int srf_causal_pyramid_bwd_tile(void);
+int srf_causal_pyramid_bwd_supported(int C, int L, int D);
+size_t srf_causal_pyramid_bwd_scratch_bytes(int Bt, int C, int L, int D);
+int srf_causal_pyramid_bwd(const float* g_merged, const float* u, const float* const* d, const float* in_prelu,
+                           const float* const* w, const float* const* prelu, float* gu, float* const* dw, float* const* dbias,
+                           float* const* dslope, float* dslope_in, int Bt, int C, int L, int D, void* scratch, void* stream);
 
 /* ---- Streaming inference for the causal model (ABI 17) ----
  * A session serves `batch` independent streams of one causal config.  A push takes the next n samples of every stream,

@@ -149,6 +149,17 @@ _PROTOS = {
     "srf_causal_pyramid": (_i, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _i, _vp]),
     "srf_causal_scale": (_i, [_vp, _vp, _l, _vp, C.c_float, _vp]),
     "srf_prelu_apply": (_i, [_vp, _vp, _vp, _l, _vp]),
+    "srf_causal_train_saved_bytes": (_sz, [_vp]),
+    "srf_causal_train_scratch_bytes": (_sz, [_vp]),
+    "srf_causal_forward_train": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "srf_causal_backward": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "srf_causal_dwconv_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
+    "srf_causal_dwconv_bwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "srf_causal_pyramid_bwd_tile": (_i, []),
+    "srf_causal_pyramid_bwd_supported": (_i, [_i, _i, _i]),
+    "srf_causal_pyramid_bwd_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "srf_causal_pyramid_bwd": (_i, [_vp, _vp, C.POINTER(_vp), _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(_vp),
+                                    C.POINTER(_vp), C.POINTER(_vp), _vp, _i, _i, _i, _i, _vp, _vp]),
     "srf_stream_create": (_i, [C.POINTER(srf_config), _i, _i, C.POINTER(_vp)]),
     "srf_stream_destroy": (None, [_vp]),
     "srf_stream_granule": (_i, [_vp]),

@@ -24,6 +24,18 @@ int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums,
 int srf_causal_scale_many(const float* const* src, float* const* dst, const long* n, const float* const* dscale,
                           const float* hscale, int count, hipStream_t st);
 
+// ---- srf_causal_bwd.hip: what the causal training step (srf_causal_train.hip) needs besides the public kernels
+int srf_causal_merge_act(const float* const* d, const float* const* prelu, int D, float* y, int Bt, int C, int L, hipStream_t st);
+int srf_causal_gain_fold(float* const* dw, float* const* db, const float* const* w, const float* const* b,
+                         const float* const* gain, float* const* dgain, const float* alpha, int nw, int nb, int count,
+                         hipStream_t st);
+int srf_causal_enc_scatter(const float* src, float* dst, int N, int A, int K, hipStream_t st);
+// gx = gout * (x > 0 ? 1 : slope) (may alias gout), dslope[0] = sum gout min(x, 0), WRITTEN, block partials added in block order;
+// scratch: srf_causal_prelu_bwd_scratch_floats() floats
+size_t srf_causal_prelu_bwd_scratch_floats();
+int srf_causal_prelu_bwd(const float* gout, const float* x, const float* slope, float* gx, float* dslope, long n, float* scratch,
+                         hipStream_t st);
+
 // ---- srf_pyramid.hip / srf_pyramid_reg.hip
 bool srf_pyramid_reg_supported(int L, int D);
 // lv_out / lv_sums (both or neither; register-resident kernels only): the training forward's extra outputs
@@ -65,6 +77,9 @@ int srf_x3w_pack3_launch(const float* const* w, char* const* dst, const int* Cou
 size_t srf_x3p_packed_bytes(int Cout, int Cin);
 bool srf_x3f_supported(int Bt, int K1, int C2, int L);
 bool srf_pw_small_supported(int Cin, int Cout, int L);
+
+// ---- srf_pwconv_wgrad.hip: this thread's weight-gradient GEMMs fold their partial sums in a fixed order (no atomic split)
+void srf_pw_wgrad_ordered(bool on);
 
 // ---- srf_backward.hip
 int srf_accumulate_launch(float* dst, const float* src, long n, hipStream_t st);

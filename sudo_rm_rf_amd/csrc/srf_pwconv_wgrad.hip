@@ -883,12 +883,17 @@ __global__ __launch_bounds__(256) void srf_wgrad_reduce2g_kernel(const float* __
   }
 }
 
+// Per-thread request (srf_causal_backward): fold the partials of a small output in ONE chain per element instead of splitting
+// them over blockIdx.y with atomic adds -- the same inputs then give the same bits.  Off by default.
+static thread_local bool g_wgrad_ordered = false;
+void srf_pw_wgrad_ordered(bool on) { g_wgrad_ordered = on; }
+
 // dst [rows][ld] <- sum over P partials [P][rows][cols] (first cols_out columns)
 static int wg_reduce_launch(const float* part, float* out, int rows, int cols, int cols_out, int ld_out, int P,
                             int accumulate, hipStream_t st) {
   const long nw = (long)rows * cols_out;
   int psplit = 1;
-  if (P >= 64 && nw * 4 <= 65536) psplit = P / 16;   // >= 16 partials per thread
+  if (P >= 64 && nw * 4 <= 65536 && !g_wgrad_ordered) psplit = P / 16;   // >= 16 partials per thread
   if (psplit > 64) psplit = 64;
   if (psplit > 1 && !accumulate)
     SRF_CHECK_HIP(hipMemset2DAsync(out, sizeof(float) * ld_out, 0, sizeof(float) * cols_out, rows, st));

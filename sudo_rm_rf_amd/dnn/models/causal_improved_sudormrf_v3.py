@@ -5,8 +5,9 @@ resolve), constructor signatures / defaults, public attributes (``causal_mask``,
 tree and therefore the exact ``state_dict()`` key / shape / order schema, and -- the parameter containers are created in the
 same order with the same torch initialisers -- the same weights for the same ``torch.manual_seed``.  The torch sub-modules
 are PARAMETER CONTAINERS ONLY: ``CausalSuDORMRF.forward`` is one ``srf_forward`` call (include/sudormrf_hip.h, variant
-SRF_VARIANT_CAUSAL).  The path is inference-only: a forward that autograd would have to differentiate raises
-NotImplementedError.  There is no CPU fallback.
+SRF_VARIANT_CAUSAL).  By default the path is inference-only: a forward that autograd would have to differentiate raises
+NotImplementedError.  ``CausalSuDORMRF.enable_hip_training()`` opts a model into the HIP training step
+(srf_causal_forward_train / srf_causal_backward).  There is no CPU fallback.
 """
 import torch
 import torch.nn as nn
@@ -243,12 +244,35 @@ class CausalSuDORMRF(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state.pop("_srf_engine", None)
+        state.pop("_srf_hip_training", None)
         return state
 
+    def enable_hip_training(self, flag=True):
+        """Opt this model into (flag=False: out of) the HIP training step and return self.  With it, a forward that autograd
+        has to differentiate runs srf_causal_forward_train and its backward srf_causal_backward: gradients for every parameter,
+        as torch autograd over the reference's forward gives them (the masked taps of the encoder / depthwise weights get exact
+        zeros).  Without autograd the inference path is untouched; the sub-module forwards, stream() and stream_pool() keep
+        refusing autograd; a mixture that requires grad is refused (no gradient w.r.t. the input).
+        The flag is a plain attribute beside the engine: not in state_dict() and dropped from pickles, so a model that was
+        unpickled has to opt in again.  Not claimed: torch.nn.DataParallel replicas and copy.deepcopy of an opted-in model
+        (neither carries the flag)."""
+        if flag:
+            self.__dict__["_srf_hip_training"] = True
+        else:
+            self.__dict__.pop("_srf_hip_training", None)
+        return self
+
     def forward(self, input_wav):
-        """[batch, A, time] float -> [batch, num_sources * A, time] float32, one srf_forward call.  Inference only."""
-        _refuse_autograd("CausalSuDORMRF.forward",
-                         [input_wav if isinstance(input_wav, torch.Tensor) else None] + list(self.parameters()))
+        """[batch, A, time] float -> [batch, num_sources * A, time] float32, one srf_forward call.  Inference only, unless
+        enable_hip_training() was called: then a forward under autograd is the HIP training step."""
+        tensors = [input_wav if isinstance(input_wav, torch.Tensor) else None] + list(self.parameters())
+        if self.__dict__.get("_srf_hip_training") and torch.is_grad_enabled() and any(
+                t is not None and t.requires_grad for t in tensors):
+            if tensors[0] is not None and tensors[0].requires_grad:
+                raise NotImplementedError("CausalSuDORMRF.forward: the HIP training step has no gradient w.r.t. the input "
+                                          "mixture; pass a mixture that does not require grad")
+            return self._engine().run_causal_train(self, input_wav, self.in_audio_channels)
+        _refuse_autograd("CausalSuDORMRF.forward", tensors)
         return self._engine().run(self, input_wav, self.in_audio_channels)
 
     def stream(self, batch=1, max_chunk=None, device=None):
