@@ -212,6 +212,28 @@ int srf_plan_num_launches(const srf_plan* plan);  /* kernel launches per forward
 int srf_forward(const srf_plan* plan, const float* const* params, int num_params,
                 const float* wav, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Ragged-batch forward (additive to ABI 19): ONE set of launches over utterances of unequal length.  wav: [batch, 1, T] padded
+ * rows, lengths: HOST array [batch], 1 <= lengths[b] <= T (T = the plan's: no example has to be that long, so a caller keeps
+ * one plan per length bucket).  out[b, :, :lengths[b]] is what srf_forward on a batch-1 plan of length lengths[b] returns
+ * for wav[b, :, :lengths[b]] alone (each example is padded to ITS OWN multiple of (K/2) 2^D, its GlobLNs run over its own
+ * frames); out[b, :, lengths[b]:] is exactly 0; wav[b, :, lengths[b]:] is never read and may hold anything, NaN included.
+ * The lengths reach the kernels by value in the launch arguments (see "Ragged forms" below): nothing is uploaded or
+ * synchronised, and a ragged batch is capped at SRF_RAGGED_MAX_BATCH = 128 examples.
+ * srf_plan_ragged_supported: 1 for an Improved plan (one audio channel, K = 21, out_channels = 256, batch <= 128) whose
+ * uniform forward, under the current kernel mode, runs the packed 256 x 128 GEMMs, the register-resident fused pyramid and
+ * the fused mask + decoder tail; GroupComm and causal plans: 0.  The ragged forward runs the fused conv pair and the 256 x 128
+ * kernel whatever the uniform forward's "at least as many tiles as CUs" gates say; plans too small for the fused tail are
+ * not supported (run those examples one by one).
+ * srf_plan_ragged_workspace_bytes: the workspace the ragged call needs (0 = not supported); srf_plan_workspace_bytes is
+ * unchanged.  Refused with SRF_EINVAL BEFORE anything is launched, srf_last_error() naming the example: an unsupported plan,
+ * a length outside 1..T, an example whose padded length the fused pyramid does not take as a row length of its own
+ * (srf_pyramid_ragged_frames_ok: shorter than 8 * 2^(D-1) frames, or off the kernels' chunk grid). */
+int srf_plan_ragged_supported(const srf_plan* plan);
+size_t srf_plan_ragged_workspace_bytes(const srf_plan* plan);
+int srf_forward_ragged(const srf_plan* plan, const float* const* params, int num_params, const float* wav,
+                       const int* lengths /* host, [batch] */, float* out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* The whole caller-side inference recipe in ONE forward (README.md:100-114): per-example {mean,
  * unbiased std} of the RAW mixture (written to `stats`, [batch][2] device floats), normalisation folded into the encoder's
  * load, "estimates * std + mean" and -- mixture_consistency != 0, as the README prescribes for the GroupComm models --
@@ -273,6 +295,21 @@ int srf_debug_fetch(const srf_plan* plan, const void* workspace, int what, float
 int srf_encoder(const float* wav, const float* w, float* out, double* sums,
                 int Bt, int A, int T, int N, int K, int L, void* stream);
 
+/* ---- Ragged forms: one launch over examples of unequal length (additive; SRF_ABI_VERSION unchanged) ----
+ * A ragged form takes its uniform twin's arguments plus HOST tables with one entry per example.  The layout does not change:
+ * T and L stay the row strides of [Bt, ., T] / [Bt, ., L] tensors; example b is lengths[b] <= T samples and frames[b] <= L
+ * frames long.  Everything at or past an example's end is treated as the zero padding its own batch-1 call would see:
+ * it is never read (it may hold anything, NaN included), statistics count the example's own elements only, and outputs
+ * that carry statistics are stored as exact zeros from the example's end to the row stride.  The tables reach the kernels BY
+ * VALUE in the launch arguments -- no upload, no synchronisation -- which caps a ragged batch at SRF_RAGGED_MAX_BATCH examples;
+ * larger batches, out-of-range entries and lengths a kernel cannot take are refused (SRF_EINVAL, the message names the
+ * example) before anything is launched.  The profiler names of the ragged kernels carry the suffix "_ragged". */
+#define SRF_RAGGED_MAX_BATCH 128
+/* srf_encoder over a ragged batch (A = 1, K = 21 only: the shape of the published Improved models).  Requires
+ * lengths[b] <= (K/2) * frames[b]; frames[b] = padded length / hop of example b (srf_plan_padded_length of a batch-1 plan). */
+int srf_encoder_ragged(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
+                       const int* lengths, const int* frames, void* stream);
+
 /* sums[g][bucket][0..1] += {sum, sumsq} of x[g, :, :] (x: [groups, channels*length]). */
 int srf_gln_stats(const float* x, double* sums, int groups, long per_group, void* stream);
 /* y = gamma_c * (x - mu_g) / sqrt(var_g + 1e-8) + beta_c, then optional PReLU. */
@@ -322,6 +359,27 @@ int srf_pw_conv_pair_supported(int Bt, int Cin1, int Cmid, int Cout2, int L);
 int srf_pw_conv_pair(const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
                      const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2,
                      int Bt, int Cin1, int Cmid, int Cout2, int L, void* stream);
+
+/* The ragged forms of the two (see "Ragged forms" above; frames[b] % 4 == 0).  Columns are independent in a 1x1 convolution, so
+ * nothing is masked on load.  What an output holds past an example's end: exact zeros where the launch accumulates statistics
+ * (srf_pw_conv_packed_ragged with out_sums, and y2 of the pair), unspecified otherwise (y of the pair and the residual form:
+ * the model's block stream, which only pointwise consumers read).  The prologue's GlobLN counts Cin * frames[b] values.
+ * Both always run their 256 x 128 kernels, whatever the "at least as many tiles as CUs" gates of their uniform twins say -- a
+ * ragged batch has no other kernel to go to: the packed images are required, shapes outside those kernels' limits are refused
+ * (srf_pw_conv_pair_ragged_supported; srf_packed_pw_weight_bytes != 0 and Cin >= 128 for the single conv, at least 8 tiles).
+ *   srf_pw_conv_packed_ragged  forms: no prologue or GlobLN, no residual (out_sums allowed); GlobLN + PReLU with residual
+ *                              (no out_sums).  No mask epilogue.  Every tile is computed.
+ *   srf_pw_conv_pair_ragged    forms: GlobLN (no residual), GlobLN + PReLU (residual required).  One 128-column tile per
+ *                              block; a tile that starts at or past its example's end stores its zeros of y2 and returns
+ *                              before any load or MFMA -- this is where a ragged batch does less work than a padded one. */
+int srf_pw_conv_packed_ragged(const float* x, const float* w, const void* w_packed, const float* bias, float* y,
+                              int Bt, int Cin, int Cout, int L, const srf_norm* in_norm, const float* residual,
+                              double* out_sums, int epilogue_mask, const float* mul, int mul_channels, const int* frames,
+                              void* stream);
+int srf_pw_conv_pair_ragged_supported(int Cin1, int Cmid, int Cout2, int L);
+int srf_pw_conv_pair_ragged(const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
+                            const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2,
+                            int Bt, int Cin1, int Cmid, int Cout2, int L, const int* frames, void* stream);
 
 /* The same GEMM in the exact-fp32 class for the training forward.  Round 4 (default): TWO FP16 parts per operand (22 mantissa
  * bits, three MFMAs per product block, the inference kernel's speed; range: |operand| < 65520 -- beyond it, and for NaN / inf operands,
@@ -381,6 +439,17 @@ size_t srf_pyramid_scratch_bytes(int groups, int C, int L, int D);
 int srf_pyramid(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
                 const float* const* bias, const float* const* gamma, const float* const* beta, int groups,
                 int C, int L, int D, void* scratch, double* out_sums, void* stream);
+
+/* srf_pyramid over a ragged batch (register-resident kernels only: L % 16 == 0 for D <= 5, L % 32 == 0 for D = 6).  y1 must be
+ * finite inside every example (what lies past frames[g] is not read); merged is written over the whole row stride, exact zeros
+ * from frames[g] on; out_sums and every level's GlobLN count the example's own C * (frames[g] >> k) values.
+ * srf_pyramid_ragged_frames_ok: whether one example may be `frames` long -- frames <= L, a multiple of 2^(D-1) and of the
+ * kernels' chunk (16 / 32), at least 4 chunks and 8 positions on the deepest level (the finalize step needs distinct edges).
+ * Scratch: srf_pyramid_scratch_bytes(groups, C, L, D), as for srf_pyramid. */
+int srf_pyramid_ragged_frames_ok(int frames, int L, int D);
+int srf_pyramid_ragged(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
+                       const float* const* bias, const float* const* gamma, const float* const* beta, int groups,
+                       int C, int L, int D, void* scratch, double* out_sums, const int* frames, void* stream);
 
 /* ---- Causal SuDORMRF (ABI 16; causal_improved_sudormrf_v3.py) ----
  * srf_causal_encoder: out[b,n,l] = sum_{a, k<K} w[n,a,k] * x[b,a, h*l+k-2h], h = K/2, w: [N, A, 2K-1] (the stored

@@ -13,6 +13,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # SRF_LIB: an alternative build of the same library (same-box A/B of kernel variants, tools/); default = the in-tree build
 LIB_PATH = os.environ.get("SRF_LIB") or os.path.join(_PKG, "libsudormrf_hip.so")
 ABI_VERSION = 19
+RAGGED_MAX_BATCH = 128     # SRF_RAGGED_MAX_BATCH
 STAT_BUCKETS = 64
 
 SRF_OK = 0
@@ -121,6 +122,18 @@ _PROTOS = {
     "srf_pyramid_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "srf_pyramid": (_i, [_vp, _vp, C.POINTER(srf_norm), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                         C.POINTER(_vp), _i, _i, _i, _i, _vp, _vp, _vp]),
+    "srf_pyramid_ragged_frames_ok": (_i, [_i, _i, _i]),
+    "srf_pyramid_ragged": (_i, [_vp, _vp, C.POINTER(srf_norm), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                               C.POINTER(_vp), _i, _i, _i, _i, _vp, _vp, C.POINTER(_i), _vp]),
+    "srf_pw_conv_packed_ragged": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(srf_norm), _vp, _vp, _i, _vp, _i,
+                                      C.POINTER(_i), _vp]),
+    "srf_pw_conv_pair_ragged_supported": (_i, [_i, _i, _i, _i]),
+    "srf_pw_conv_pair_ragged": (_i, [_vp, _vp, _vp, _vp, C.POINTER(srf_norm), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                    C.POINTER(_i), _vp]),
+    "srf_plan_ragged_supported": (_i, [_vp]),
+    "srf_plan_ragged_workspace_bytes": (_sz, [_vp]),
+    "srf_forward_ragged": (_i, [_vp, C.POINTER(_vp), _i, _vp, C.POINTER(_i), _vp, _vp, _sz, _vp]),
+    "srf_encoder_ragged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "srf_merge": (_i, [C.POINTER(_vp), C.POINTER(srf_norm), _i, _vp, _i, _i, _i, _vp, _vp]),
     "srf_decoder_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),
     "srf_decoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),

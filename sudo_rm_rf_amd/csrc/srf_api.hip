@@ -700,6 +700,165 @@ static int srf_forward_body(const srf_plan* p, const float* const* P, int num_pa
   return rc;
 }
 
+// ---- the by-value table of every ragged entry point (srf_internal.h)
+int srf_frames_table(const char* what, const int* frames, int groups, int L, SrfFrames* out) {
+  SRF_CHECK_ARG(frames != nullptr, "%s: null frames table", what);
+  SRF_CHECK_ARG(groups >= 1 && groups <= SRF_RAGGED_MAX_BATCH, "%s: a ragged batch holds 1..%d examples (got %d)", what,
+                SRF_RAGGED_MAX_BATCH, groups);
+  for (int g = 0; g < SRF_RAGGED_MAX_BATCH; ++g) out->n[g] = 0;
+  for (int g = 0; g < groups; ++g) {
+    SRF_CHECK_ARG(frames[g] >= 1 && frames[g] <= L, "%s: example %d has %d frames (allowed: 1..%d)", what, g, frames[g], L);
+    out->n[g] = frames[g];
+  }
+  return SRF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// ragged forward: unequal-length examples in one set of launches (include/sudormrf_hip.h, "Ragged forms")
+// ---------------------------------------------------------------------------------------------
+// The layout is the uniform forward's -- [batch, C, L] with L the PLAN's frame count as row stride, the same workspace carve-up
+// and two-buffer scheme -- and every kernel takes the example's own frame count L_b from a by-value table.  The invariant:
+//   * a tensor whose GlobLN statistics are taken (enc, y1, merged) is exactly zero at columns >= L_b, so the sums come out
+//     right and only the count changes (C * L_b): encoder, y2 of the pair, the pyramid's merged tensor;
+//   * a tensor read with a halo (the wave by the encoder, y1 by the pyramid) is never read past the example's end;
+//   * the block stream (cur / nxt: pointwise consumers only) may hold anything there -- so may the partial decoder frames the
+//     unchanged mask + decoder GEMM leaves at those columns: the ragged overlap-add never reads them.
+static bool plan_ragged_now(const srf_plan* p, const char** why) {
+  const srf_config& c = p->cfg;
+  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis;
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (c.variant != SRF_VARIANT_IMPROVED) return no("only the Improved model has ragged kernels (GroupComm / causal plans: per-example calls)");
+  if (p->A != 1 || c.enc_kernel_size != 21) return no("the ragged encoder is the one-channel K = 21 kernel");
+  if (p->Bt > SRF_RAGGED_MAX_BATCH) return no("the batch exceeds SRF_RAGGED_MAX_BATCH");
+  if (!plan_use_pack(p)) return no("the forward does not run the packed 256 x 128 GEMMs (kernel mode / debug flags / shapes)");
+  if (!plan_fused_pyramid_now(p) || srf_dbg(SRF_DBG_PYR_NO_REG) || !srf_pyramid_reg_supported(p->L, D))
+    return no("the forward does not run the register-resident fused pyramid at this length");
+  const int pu0 = p->p_block0;
+  if (!p->pk_of_param[3] || !p->pk_of_param[p->p_tail + 1]) return no("bottleneck / mask conv shapes outside the 256 x 128 GEMM");
+  for (int i = 0; i < U; ++i)
+    if (!p->pk_of_param[pu0 + i * p->p_block_stride] || !p->pk_of_param[pu0 + i * p->p_block_stride + 5 + 4 * D + 3])
+      return no("block conv shapes outside the 256 x 128 GEMM");
+  if (!srf_pw_conv_pair_ragged_supported(N, p->nB, p->nC, p->L) || !srf_pw_conv_pair_ragged_supported(p->nC, p->nB, p->nC, p->L))
+    return no("channel counts outside the fused conv pair (needs out_channels = 256)");
+  if (!srf_x3w_shape_supported(p->nC, p->nB, p->L) || (long)p->Bt * ((p->L + 127) / 128) < 8)
+    return no("too few tiles for the 256 x 128 GEMM");
+  if (!plan_fused_tail_now(p, true)) return no("the forward does not run the fused mask + decoder tail at this size (small launches)");
+  return true;
+}
+extern "C" int srf_plan_ragged_supported(const srf_plan* p) { return p && plan_ragged_now(p, nullptr) ? 1 : 0; }
+extern "C" size_t srf_plan_ragged_workspace_bytes(const srf_plan* p) { return p && plan_ragged_now(p, nullptr) ? p->total_bytes : 0; }
+
+extern "C" int srf_forward_ragged(const srf_plan* p, const float* const* P, int num_params, const float* wav, const int* lengths,
+                                  float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  SRF_CHECK_ARG(p && P && wav && lengths && out && workspace, "srf_forward_ragged: null pointer");
+  const char* why = "";
+  SRF_CHECK_ARG(plan_ragged_now(p, &why), "srf_forward_ragged: plan not supported: %s", why);
+  SRF_CHECK_ARG(num_params == p->n_params, "srf_forward_ragged: expected %d parameter tensors, got %d", p->n_params, num_params);
+  if (workspace_bytes < p->total_bytes) {
+    srf_set_error("srf_forward_ragged: workspace too small (%zu < %zu bytes)", workspace_bytes, p->total_bytes);
+    return SRF_EWORKSPACE;
+  }
+  SRF_CHECK_ARG((((size_t)workspace) & 255) == 0, "srf_forward_ragged: workspace must be 256-byte aligned");
+  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "srf_forward_ragged: parameter %d is null", i);
+  const srf_config& c = p->cfg;
+  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, h = K / 2;
+  const int Bt = p->Bt, L = p->L, nB = p->nB, nC = p->nC;
+  // ---- every example's own padded length, as its batch-1 plan would have it; all refusals BEFORE the first launch
+  int frames[SRF_RAGGED_MAX_BATCH];
+  SrfFrames lens_t, frames_t;
+  for (int b = 0; b < Bt; ++b) {
+    SRF_CHECK_ARG(lengths[b] >= 1 && lengths[b] <= p->T, "srf_forward_ragged: example %d has length %d (allowed: 1..%d)", b,
+                  lengths[b], p->T);
+    frames[b] = (int)(plan_padded_length(lengths[b], h, D) / h);
+    SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(frames[b], L, D),
+                  "srf_forward_ragged: example %d (length %d = %d frames) is too short for the fused pyramid or off its chunk grid", b,
+                  lengths[b], frames[b]);
+  }
+  int rc = srf_frames_table("srf_forward_ragged", lengths, Bt, p->T, &lens_t);
+  if (rc) return rc;
+  rc = srf_frames_table("srf_forward_ragged", frames, Bt, L, &frames_t);
+  if (rc) return rc;
+  if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
+
+  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  auto fptr = [&](size_t o) { return (float*)(ws + o); };
+  double* stats = (double*)(ws + p->off_stats);
+  auto slot = [&](int s) { return stats + (size_t)s * Bt * SRF_STAT_BUCKETS * 2; };
+  rc = srf_zero_launch(stats, p->stats_bytes, st);
+  if (rc) return rc;
+  {
+    std::vector<const float*> pw(p->pk_param.size());
+    std::vector<void*> pd(p->pk_param.size());
+    for (size_t i = 0; i < p->pk_param.size(); ++i) {
+      pw[i] = P[p->pk_param[i]];
+      pd[i] = ws + p->pk_off[i];
+    }
+    rc = srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
+    if (rc) return rc;
+  }
+  auto packed = [&](int param_index) -> const void* { return (const void*)(ws + p->pk_of_param[param_index]); };
+
+  float* enc = fptr(p->off_enc);
+  rc = srf_encoder_ragged(wav, P[0], enc, slot(0), Bt, 1, p->T, N, K, L, lengths, frames, stream);
+  if (rc) return rc;
+  float* cur = fptr(p->off_xa);
+  float* nxt = fptr(p->off_xb);
+  float* y1 = fptr(p->off_y1);
+  float* merged = fptr(p->off_lv[0]);
+  const int pu0 = p->p_block0;
+  {   // ln folded into the bottleneck, + proj_1x1 of block 0
+    srf_norm ln{slot(0), P[1], P[2], nullptr};
+    rc = srf_pw_conv_pair_ragged(enc, packed(3), P[4], cur, &ln, nullptr, packed(pu0), P[pu0 + 1], y1, slot(1), Bt, N, nB, nC, L,
+                                 frames, stream);
+    if (rc) return rc;
+  }
+  for (int i = 0; i < U; ++i) {
+    const int pu_index = pu0 + i * p->p_block_stride;
+    const float* const* Pu = P + pu_index;
+    const int s0 = 1 + i * p->slots_per_block;
+    const float *pw[SRF_MAX_DEPTH], *pb[SRF_MAX_DEPTH], *pg[SRF_MAX_DEPTH], *pbe[SRF_MAX_DEPTH];
+    for (int k = 0; k < D; ++k) {
+      const float* const* Pk = Pu + 5 + 4 * k;
+      pw[k] = Pk[0];
+      pb[k] = Pk[1];
+      pg[k] = Pk[2];
+      pbe[k] = Pk[3];
+    }
+    srf_norm in{slot(s0), Pu[2], Pu[3], Pu[4]};
+    rc = srf_pyramid_ragged(y1, merged, &in, pw, pb, pg, pbe, Bt, nC, L, D, ws + p->off_pyr, slot(s0 + 1 + D), frames, stream);
+    if (rc) return rc;
+    const float* const* Pf = Pu + 5 + 4 * D;
+    srf_norm fn{slot(s0 + 1 + D), Pf[0], Pf[1], Pf[2]};
+    if (i + 1 < U) {   // res_conv of this block + proj_1x1 of the next one
+      const int pn = pu_index + p->p_block_stride;
+      rc = srf_pw_conv_pair_ragged(merged, packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, &fn, cur, packed(pn), P[pn + 1], y1,
+                                   slot(1 + (i + 1) * p->slots_per_block), Bt, nC, nB, nC, L, frames, stream);
+    } else {
+      rc = srf_pw_conv_packed_ragged(merged, Pf[3], packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, Bt, nC, nB, L, &fn, cur, nullptr,
+                                     0, nullptr, 0, frames, stream);
+    }
+    if (rc) return rc;
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+  // ---- tail: the uniform mask + decoder GEMM over every column (the block stream is unspecified past an example's end, and so
+  // are the partial frames it makes there), then the ragged overlap-add, which reads the example's own frames only
+  const float* const* Pt = P + p->p_tail;
+  float* zpart = fptr(p->off_masked);
+  const int M = p->SA * K, nparts = (p->SA * N + 255) / 256;
+  rc = srf_mask_decode_pack(Pt[3], ws + p->off_wdpack, p->SA * N, M, st);
+  if (rc) return rc;
+  rc = srf_mask_decode(cur, Pt[1], packed(p->p_tail + 1), Pt[2], Pt[0], enc, N, ws + p->off_wdpack, zpart, Bt, c.out_channels,
+                       p->SA * N, L, M, st);
+  if (rc) return rc;
+  return srf_overlap_add_launch(zpart, out, Bt, p->SA, K, L, p->T, nparts, nullptr, nullptr, 0, st, &lens_t, &frames_t);
+}
+
 extern "C" int srf_debug_fetch(const srf_plan* p, const void* workspace, int what, float* dst,
                                size_t dst_floats, void* stream) {
   SRF_CHECK_ARG(p && workspace && dst, "srf_debug_fetch: null pointer");

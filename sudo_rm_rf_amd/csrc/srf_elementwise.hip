@@ -210,10 +210,15 @@ int srf_transpose_launch(const float* w, float* wt, int Ci, int M, hipStream_t s
 // post-processing of README.md:106-114 folded in -- out = est * std + mean and, with `mc`, mixture_consistency.apply against
 // the mixture re-normalised on the fly from the raw waveform).
 constexpr int OA_Q = 64;      // frames per block (fewer when Co * K rows of them would not fit 64 KB of LDS)
-template <bool POST>
+// TABS: none, or (SrfFrames samples, SrfFrames frames) = the RAGGED form (srf_forward_ragged's tail): L and T stay the row
+// strides; frames of example b at or past frames[b] are never read -- they count as zero, whatever the frame GEMM left there
+// (it computes every column, from a block stream that is unspecified past the example's end) -- and samples at or past
+// lens[b] are written as 0.
+template <bool POST, typename... TABS>
 __global__ __launch_bounds__(256) void srf_overlap_add_kernel(const float* __restrict__ z, float* __restrict__ out, int Co, int K,
                                                               int L, int T, int nparts, int qw, const float* __restrict__ stats,
-                                                              const float* __restrict__ wav, int mc) {
+                                                              const float* __restrict__ wav, int mc, TABS... tabs) {
+  constexpr bool RAGGED = sizeof...(TABS) != 0;
   extern __shared__ float oa_s[];                 // [Co * K][qw + 2]: frames q0 - 1 .. q0 + qw
   const int W = qw + 2;
   const int q0 = blockIdx.x * qw;
@@ -224,12 +229,13 @@ __global__ __launch_bounds__(256) void srf_overlap_add_kernel(const float* __res
   // (four frames per load, four parts in flight: 64 B per thread keep enough bytes in flight to cover the HBM latency -- one
   // dword at a time measured 2.7 TB/s on cfg 5's 1.1 GB of partial frames)
   const int W4 = W >> 2;                          // W % 4 == 0 (host)
+  const int Lr = RAGGED ? srf_frames2_of((int)b, tabs...) : L;      // frames that hold data
   typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
   for (int idx = threadIdx.x; idx < M * W4; idx += 256) {
     const int m = idx / W4, j = (idx - m * W4) * 4;
     const int l = q0 - 1 + j;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (l >= 0 && l + 3 < L) {
+    if (l >= 0 && l + 3 < Lr) {
       const float* src = zb + (size_t)m * L + l;
       int p = 0;
       for (; p + 4 <= nparts; p += 4, src += 4 * pstride) {
@@ -247,7 +253,7 @@ __global__ __launch_bounds__(256) void srf_overlap_add_kernel(const float* __res
     } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if (l + e >= 0 && l + e < L) {
+        if (l + e >= 0 && l + e < Lr) {
           const float* src = zb + (size_t)m * L + l + e;
           int p = 0;
           for (; p + 4 <= nparts; p += 4, src += 4 * pstride) v[e] += (src[0] + src[pstride]) + (src[2 * pstride] + src[3 * pstride]);
@@ -283,7 +289,8 @@ __global__ __launch_bounds__(256) void srf_overlap_add_kernel(const float* __res
       corr = ((wav[b * (long)T + t] - mean) / (sd + 1e-9f) - tot) * (1.f / (float)Co);
     }
     for (int o = 0; o < Co; ++o) {
-      const float v = est(o);
+      float v = est(o);
+      if constexpr (RAGGED) v = t < srf_frames_of((int)b, tabs...) ? v : 0.f;
       out[((size_t)b * Co + o) * T + t] = (POST && mc) ? v + corr : v;
     }
   }
@@ -291,7 +298,7 @@ __global__ __launch_bounds__(256) void srf_overlap_add_kernel(const float* __res
 
 // stats: null = plain overlap-add; else [Bt][2] {mean, std} of the raw mixture `wav` [Bt][T] (mc: also mixture consistency)
 int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, int L, int T, int nparts, const float* stats,
-                           const float* wav, int mc, hipStream_t st) {
+                           const float* wav, int mc, hipStream_t st, const SrfFrames* lens, const SrfFrames* frames) {
   // frames per block: rows of 128 floats (fewer partly used cache lines at the unaligned row ends) when there are partial
   // frames to sum and the launch still has >= 4 blocks per CU, else rows of 64 (the single-part case is latency-bound:
   // more, smaller blocks); fewer when Co * K rows would not fit 64 KB of LDS.  qw + 2 must be a multiple of 4.
@@ -304,6 +311,13 @@ int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, in
   const size_t lds = sizeof(float) * (size_t)Co * K * (qw + 2);
   const int h = K / 2;
   dim3 grid(((T + h - 1) / h + qw - 1) / qw, Bt);
+  if (lens) {
+    SRF_CHECK_ARG(frames && !stats, "internal: the ragged overlap-add takes both tables and no post-processing");
+    hipLaunchKernelGGL((srf_overlap_add_kernel<false, SrfFrames, SrfFrames>), grid, dim3(256), lds, st, z, out, Co, K, L, T, nparts,
+                       qw, stats, wav, mc, *lens, *frames);
+    SRF_CHECK_LAUNCH("overlap_add_ragged", st);
+    return SRF_OK;
+  }
   if (stats)
     hipLaunchKernelGGL(srf_overlap_add_kernel<true>, grid, dim3(256), lds, st, z, out, Co, K, L, T, nparts, qw, stats, wav, mc);
   else

@@ -10,12 +10,17 @@
 
 // Fast path: one audio channel, compile-time K.  Each lane owns two frames (l, l+64) whose KT-sample
 // windows live in registers; the block's input window is staged once through LDS.
-template <int KT>
+// RAGGED (srf_encoder_ragged): T and L stay the row strides of wav and out; example b is lens[b] samples and frames[b]
+// frames long.  Samples at or past lens[b] are never read (they may hold anything), frames at or past frames[b] are stored
+// as 0 -- frame frames[b] would otherwise see the example's last H samples -- and add nothing to the statistics; a block
+// wholly past the example's end stores its zeros without staging a window.
+template <int KT, typename... TABS>   // TABS: none, or (SrfFrames samples, SrfFrames frames)
 __global__ __launch_bounds__(256) void srf_encoder_fast_kernel(const float* __restrict__ wav,
                                                                const float* __restrict__ w,
                                                                float* __restrict__ out,
                                                                double* __restrict__ sums, int T, int N,
-                                                               int L, const float* __restrict__ in_stats) {
+                                                               int L, const float* __restrict__ in_stats, TABS... tabs) {
+  constexpr bool RAGGED = sizeof...(TABS) != 0;
   constexpr int H = KT / 2;
   constexpr int FR = 128;                  // frames per block
   constexpr int WIN = (FR - 1) * H + KT;   // samples needed by FR frames
@@ -24,12 +29,25 @@ __global__ __launch_bounds__(256) void srf_encoder_fast_kernel(const float* __re
   const int b = blockIdx.y;
   const int l0 = blockIdx.x * FR;
   const float* xb = wav + (size_t)b * T;
+  const int Tb = RAGGED ? srf_frames_of(b, tabs...) : T;     // samples / frames of this example
+  const int Lb = RAGGED ? srf_frames2_of(b, tabs...) : L;
+  if constexpr (RAGGED) {
+    if (l0 >= Lb) {   // block-uniform
+      const int per = ((N + (int)gridDim.z - 1) / (int)gridDim.z + 3) & ~3;
+      const int n_lo = blockIdx.z * per, n_hi = min(N, n_lo + per);
+      for (int n = n_lo + (int)(threadIdx.x >> 6); n < n_hi; n += 4) {
+        float* o = out + ((size_t)b * N + n) * L;
+        for (int l = l0 + (int)(threadIdx.x & 63); l < min(l0 + FR, L); l += 64) o[l] = 0.f;
+      }
+      return;
+    }
+  }
   // in_stats (caller-side recipe folded in, README.md:100-104): the model sees (x - mean) / (std + 1e-9); the conv's zero
   // padding applies to the NORMALISED signal
   const float im = in_stats ? in_stats[2 * b] : 0.f, iden = in_stats ? in_stats[2 * b + 1] + 1e-9f : 1.f;
   for (int i = threadIdx.x; i < WIN; i += 256) {
     const int t = H * l0 - H + i;
-    win[i] = (t >= 0 && t < T) ? (in_stats ? (xb[t] - im) / iden : xb[t]) : 0.f;
+    win[i] = (t >= 0 && t < Tb) ? (in_stats ? (xb[t] - im) / iden : xb[t]) : 0.f;
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -57,6 +75,10 @@ __global__ __launch_bounds__(256) void srf_encoder_fast_kernel(const float* __re
     }
     float* o = out + ((size_t)b * N + n) * L;
     float s = 0.f, q = 0.f;
+    if constexpr (RAGGED) {
+      a0 = la < Lb ? a0 : 0.f;
+      a1 = lb < Lb ? a1 : 0.f;
+    }
     if (va) {
       o[la] = a0;
       s += a0;
@@ -122,6 +144,32 @@ __global__ __launch_bounds__(256) void srf_encoder_generic_kernel(const float* _
 
 int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
                      const float* in_stats, void* stream);
+// The ragged form exists for the shape the fast kernel serves (one audio channel, K = 21: every published Improved model).
+extern "C" int srf_encoder_ragged(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N,
+                                  int K, int L, const int* lengths, const int* frames, void* stream) {
+  SRF_CHECK_ARG(wav && w && out, "srf_encoder_ragged: null pointer");
+  SRF_CHECK_ARG(Bt > 0 && T > 0 && N > 0 && L > 0, "srf_encoder_ragged: bad sizes");
+  SRF_CHECK_ARG(A == 1 && K == 21 && srf_kernel_mode() != 1,
+                "srf_encoder_ragged: only the one-channel K = 21 kernel has a ragged form (A=%d K=%d, kernel mode %d)", A, K,
+                srf_kernel_mode());
+  SrfFrames lens, fr;
+  int rc = srf_frames_table("srf_encoder_ragged (lengths)", lengths, Bt, T, &lens);
+  if (rc) return rc;
+  rc = srf_frames_table("srf_encoder_ragged (frames)", frames, Bt, L, &fr);
+  if (rc) return rc;
+  for (int b = 0; b < Bt; ++b)
+    SRF_CHECK_ARG((long)lengths[b] <= (long)(K / 2) * frames[b], "srf_encoder_ragged: example %d: %d samples exceed hop * frames = %d",
+                  b, lengths[b], (K / 2) * frames[b]);
+  hipStream_t st = (hipStream_t)stream;
+  const long bxy = (long)((L + 127) / 128) * Bt, want = 64L * srf_device_cus();   // (grid: as srf_encoder_impl)
+  int nz = bxy >= want ? 1 : (int)((want + bxy - 1) / bxy);
+  nz = nz > N / 16 ? (N / 16 > 0 ? N / 16 : 1) : nz;
+  dim3 grid((L + 127) / 128, Bt, nz);
+  hipLaunchKernelGGL((srf_encoder_fast_kernel<21, SrfFrames, SrfFrames>), grid, dim3(256), 0, st, wav, w, out, sums, T, N, L, (const float*)nullptr,
+                     lens, fr);
+  SRF_CHECK_LAUNCH("encoder_ragged", st);
+  return SRF_OK;
+}
 extern "C" int srf_encoder(const float* wav, const float* w, float* out, double* sums, int Bt, int A,
                            int T, int N, int K, int L, void* stream) {
   return srf_encoder_impl(wav, w, out, sums, Bt, A, T, N, K, L, nullptr, stream);

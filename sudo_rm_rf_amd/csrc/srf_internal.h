@@ -10,11 +10,29 @@
 #define SRF_CAUSAL_TAPS 11   // live taps of the k = 21 depthwise convs (21 - 21 // 2)
 #define SRF_CAUSAL_KW 21     // weight row stride of those convs
 
+// ---- ragged forms (srf_*_ragged): the frame count of every example of the batch, handed to the kernels BY VALUE next to their
+// uniform twins' arguments (no upload, no synchronisation; the table caps the batch at SRF_RAGGED_MAX_BATCH)
+struct SrfFrames {
+  int n[SRF_RAGGED_MAX_BATCH];
+};
+// A kernel template takes the table(s) as a trailing parameter PACK: empty in the uniform instantiations (their arguments and
+// their code stay what they were), one SrfFrames (encoder: two -- samples, frames) in the ragged ones.
+__device__ __forceinline__ int srf_frames_of(int) { return 0; }    // (uniform: never evaluated)
+__device__ __forceinline__ int srf_frames2_of(int) { return 0; }
+template <typename... R>
+__device__ __forceinline__ int srf_frames_of(int g, const SrfFrames& f, const R&...) { return f.n[g]; }
+__device__ __forceinline__ int srf_frames2_of(int g, const SrfFrames&, const SrfFrames& f2) { return f2.n[g]; }
+// checks frames[0 .. groups) against the row stride L and fills the table; `what` names the caller in the error string
+int srf_frames_table(const char* what, const int* frames, int groups, int L, SrfFrames* out);
+
 // ---- srf_elementwise.hip
 int srf_transpose_launch(const float* w, float* wt, int Ci, int M, hipStream_t st);
 // stats: null = plain overlap-add; else [Bt][2] {mean, std} of the raw mixture `wav` [Bt][T] (mc: also mixture consistency)
+// lens / frames (both or neither): the ragged form -- frames of example b at or past frames[b] count as zero and are never
+// read, samples at or past lens[b] are written as 0 (no stats)
 int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, int L, int T, int nparts, const float* stats,
-                           const float* wav, int mc, hipStream_t st);
+                           const float* wav, int mc, hipStream_t st, const SrfFrames* lens = nullptr,
+                           const SrfFrames* frames = nullptr);
 
 // ---- srf_encoder.hip
 int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,

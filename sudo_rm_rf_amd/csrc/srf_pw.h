@@ -49,11 +49,13 @@ struct PwPairArgs {
 int srf_pw_bf16x3_launch(const PwArgs& a, int pro, hipStream_t st);
 int srf_pw_w4_launch(const PwArgs& a, int pro, hipStream_t st);   // 64 x 64 tiles for small launches (srf_pwconv_w4.hip)
 bool srf_pw_w4_wanted(const PwArgs& a);
-int srf_pw_x3w_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);   // the 256 x 128 kernel (srf_pwconv_x3w.hip)
+// the 256 x 128 kernel (srf_pwconv_x3w.hip); frames: null = the uniform kernels, else its ragged form
+int srf_pw_x3w_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st, const SrfFrames* frames = nullptr);
 int srf_pw_x3p_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);   // its paired-block form (srf_pwconv_x3p.hip)
 bool srf_x3p_supported(const PwArgs& a, int pro);
 int srf_pw_small_launch(const PwArgs& a, hipStream_t st);
-int srf_pw_x3f_launch(const PwPairArgs& a, int pro, hipStream_t st, bool f16 = false);   // the fused pair (srf_pwconv_x3f.hip)
+// the fused pair (srf_pwconv_x3f.hip); frames: null = the uniform kernels, else its ragged form (bf16 parts, pro 1 / 2)
+int srf_pw_x3f_launch(const PwPairArgs& a, int pro, hipStream_t st, bool f16 = false, const SrfFrames* frames = nullptr);
 // K5: mask GEMM + decoder contraction in one launch (srf_pwconv_x3w.hip, EPI 4)
 int srf_pw_x3w_fused_tail_launch(const PwArgs& a, const char* wpack, const char* wdpack, float* zpart, int M, hipStream_t st);
 int srf_pw_x3w3_launch(const PwArgs& a, const char* wpack3, int pro, hipStream_t st);   // three bf16 parts (training forward)

@@ -234,19 +234,48 @@ static bool srf_pw_pair_shape_ok(int Bt, int Cin1, int Cmid, int Cout2, int L) {
   if (!srf_x3w_shape_supported(Cin1, Cmid, L) || !srf_x3w_shape_supported(Cmid, Cout2, L)) return false;
   return (long)Bt * ((L + 127) / 128) >= srf_device_cus();
 }
+extern "C" int srf_pw_conv_pair_ragged_supported(int Cin1, int Cmid, int Cout2, int L) {
+  if (srf_kernel_mode() != 0 || srf_dbg(SRF_DBG_NO_PAIRS | SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS)) return 0;
+  if (Cmid != 256 || !srf_x3f_supported(1, Cin1, Cout2, L)) return 0;
+  return srf_x3w_shape_supported(Cin1, Cmid, L) && srf_x3w_shape_supported(Cmid, Cout2, L) ? 1 : 0;
+}
 extern "C" int srf_pw_conv_pair_supported(int Bt, int Cin1, int Cmid, int Cout2, int L) {
   return srf_kernel_mode() == 0 && srf_pw_pair_shape_ok(Bt, Cin1, Cmid, Cout2, L) ? 1 : 0;
 }
 // y = W1 f(x) + bias1 (+ residual), f = in_norm (GlobLN, or GlobLN + PReLU: then the residual is required -- the two forms the
 // model has -- or NULL: no prologue, residual required -- the backward's data-gradient pair); y2 = W2 y + bias2; out_sums2
 // (nullable) += {sum, sumsq} of y2.  w1_packed / w2_packed: srf_pack_pw_weights.
+static int pw_conv_pair_run(const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
+                           const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2,
+                           int Bt, int Cin1, int Cmid, int Cout2, int L, void* stream, const SrfFrames* frames);
 extern "C" int srf_pw_conv_pair(const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
                                 const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2,
                                 int Bt, int Cin1, int Cmid, int Cout2, int L, void* stream) {
+  return pw_conv_pair_run(x, w1_packed, bias1, y, in_norm, residual, w2_packed, bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2, L,
+                          stream, nullptr);
+}
+// The ragged pair.  Shapes: the pair kernel's own limits under the default kernel mode -- NOT the "at least as many tiles as
+// CUs" gate of srf_pw_conv_pair_supported: a ragged batch has no other kernel to fall back to.  in_norm required.
+extern "C" int srf_pw_conv_pair_ragged(const float* x, const void* w1_packed, const float* bias1, float* y,
+                                       const srf_norm* in_norm, const float* residual, const void* w2_packed, const float* bias2,
+                                       float* y2, double* out_sums2, int Bt, int Cin1, int Cmid, int Cout2, int L,
+                                       const int* frames, void* stream) {
+  SrfFrames fr;
+  int rc = srf_frames_table("srf_pw_conv_pair_ragged", frames, Bt, L, &fr);
+  if (rc) return rc;
+  for (int b = 0; b < Bt; ++b)
+    SRF_CHECK_ARG(frames[b] % 4 == 0, "srf_pw_conv_pair_ragged: example %d has %d frames: not a multiple of 4", b, frames[b]);
+  SRF_CHECK_ARG(in_norm != nullptr, "srf_pw_conv_pair_ragged: in_norm required (forms built: GlobLN, GlobLN + PReLU with residual)");
+  return pw_conv_pair_run(x, w1_packed, bias1, y, in_norm, residual, w2_packed, bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2, L,
+                          stream, &fr);
+}
+static int pw_conv_pair_run(const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
+                           const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2,
+                           int Bt, int Cin1, int Cmid, int Cout2, int L, void* stream, const SrfFrames* frames) {
   SRF_CHECK_ARG(x && w1_packed && bias1 && y && w2_packed && bias2 && y2, "srf_pw_conv_pair: null pointer");
   SRF_CHECK_ARG(!in_norm || (in_norm->sums && in_norm->gamma && in_norm->beta), "srf_pw_conv_pair: a prologue needs statistics, gamma and beta");
-  SRF_CHECK_ARG(srf_pw_conv_pair_supported(Bt, Cin1, Cmid, Cout2, L), "srf_pw_conv_pair: unsupported shape / mode (Bt=%d %d->%d->%d L=%d)",
-                Bt, Cin1, Cmid, Cout2, L);
+  SRF_CHECK_ARG(frames ? srf_pw_conv_pair_ragged_supported(Cin1, Cmid, Cout2, L) : srf_pw_conv_pair_supported(Bt, Cin1, Cmid, Cout2, L),
+                "srf_pw_conv_pair: unsupported shape / mode (Bt=%d %d->%d->%d L=%d)", Bt, Cin1, Cmid, Cout2, L);
   SRF_CHECK_ALIGNED16("srf_pw_conv_pair", {"in_norm.sums", in_norm ? in_norm->sums : nullptr}, {"x", x}, {"y", y}, {"y2", y2}, {"w1_packed", w1_packed}, {"w2_packed", w2_packed},
                       {"residual", residual});
   PwPairArgs a;
@@ -267,7 +296,7 @@ extern "C" int srf_pw_conv_pair(const float* x, const void* w1_packed, const flo
   a.Bt = Bt;
   a.nLt = 0;
   a.total = 0;
-  return srf_pw_x3f_launch(a, !in_norm ? 0 : (a.nrm.prelu ? 2 : 1), (hipStream_t)stream);
+  return srf_pw_x3f_launch(a, !in_norm ? 0 : (a.nrm.prelu ? 2 : 1), (hipStream_t)stream, false, frames);
 }
 
 // THE predicate of the 256 x 128 dispatch for a whole launch (srf_pw_conv_packed, srf_pw_conv_packed3 and srf_pw_packed_only all
@@ -578,6 +607,55 @@ extern "C" int srf_pw_conv(const float* x, const float* w, const float* bias, fl
                            void* stream) {
   return srf_pw_conv_packed(x, w, nullptr, bias, y, Bt, Cin, Cout, L, in_norm, residual, out_sums,
                             epilogue_mask, mul, mul_channels, stream);
+}
+
+// The ragged 1x1 convolution: always the 256 x 128 kernel's ragged form -- whatever the "launch fills the chip" gate of
+// srf_pw_conv_packed says, a ragged batch has no other kernel to go to -- so the packed image is required and the fp32
+// weight is never read.  Forms: no prologue / GlobLN (out_sums allowed: y is then exact zeros past every example's end),
+// GlobLN + PReLU with residual (the res_conv form: no statistics; y past an example's end is unspecified).
+extern "C" int srf_pw_conv_packed_ragged(const float* x, const float* w, const void* w_packed, const float* bias, float* y,
+                                         int Bt, int Cin, int Cout, int L, const srf_norm* in_norm, const float* residual,
+                                         double* out_sums, int epilogue_mask, const float* mul, int mul_channels,
+                                         const int* frames, void* stream) {
+  (void)w;
+  (void)mul;
+  (void)mul_channels;
+  SrfFrames fr;
+  int rc = srf_frames_table("srf_pw_conv_packed_ragged", frames, Bt, L, &fr);
+  if (rc) return rc;
+  for (int b = 0; b < Bt; ++b)
+    SRF_CHECK_ARG(frames[b] % 4 == 0, "srf_pw_conv_packed_ragged: example %d has %d frames: not a multiple of 4", b, frames[b]);
+  SRF_CHECK_ARG(x && w_packed && bias && y, "srf_pw_conv_packed_ragged: null pointer (the packed weight image is required)");
+  SRF_CHECK_ARG(Cin > 0 && Cout > 0, "srf_pw_conv_packed_ragged: bad sizes");
+  SRF_CHECK_ARG(!epilogue_mask, "srf_pw_conv_packed_ragged: the mask epilogue has no ragged form");
+  PwArgs a;
+  a.x = x;
+  a.w = nullptr;
+  a.bias = bias;
+  a.y = y;
+  a.residual = residual;
+  a.out_sums = out_sums;
+  a.mul = nullptr;
+  a.nrm = srf_norm_dev(in_norm);
+  a.inv_count = 1.0 / ((double)Cin * (double)L);
+  a.Cin = Cin;
+  a.Cout = Cout;
+  a.L = L;
+  a.Bt = Bt;
+  a.mul_channels = 1;
+  a.epi_mask = 0;
+  const int pro = a.nrm.sums ? (a.nrm.prelu ? 2 : 1) : (a.nrm.prelu ? 3 : 0);
+  SRF_CHECK_ARG(pro != 3 && (pro == 2) == (residual != nullptr) && !(pro == 2 && out_sums),
+                "srf_pw_conv_packed_ragged: forms built: no prologue / GlobLN without residual, GlobLN + PReLU with residual and "
+                "without statistics");
+  if (a.nrm.sums) SRF_CHECK_ARG(a.nrm.gamma && a.nrm.beta, "srf_pw_conv_packed_ragged: norm without gamma/beta");
+  SRF_CHECK_ARG(srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS) &&
+                    srf_x3w_shape_supported(Cin, Cout, L) && (long)Bt * Cin * L * 4 < (1L << 31),
+                "srf_pw_conv_packed_ragged: the 256 x 128 kernel does not take %d -> %d channels, L=%d in kernel mode %d", Cin, Cout, L,
+                srf_kernel_mode());
+  SRF_CHECK_ALIGNED16("srf_pw_conv_packed_ragged", {"in_norm.sums", a.nrm.sums}, {"x", x}, {"y", y}, {"residual", residual},
+                      {"w_packed", w_packed});
+  return srf_pw_x3w_launch(a, reinterpret_cast<const char*>(w_packed), pro, (hipStream_t)stream, &fr);
 }
 
 extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_packed, const float* bias,

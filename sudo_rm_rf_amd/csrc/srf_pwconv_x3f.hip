@@ -85,11 +85,28 @@ using f_int = std::integral_constant<int, V>;
 // 2 = GlobLN + PReLU (conv 1's operand load).  EPI: 0 = bias, 1 = bias + residual (conv 1's epilogue).
 // DRAIN: every counted wait of the DMA pipeline becomes vmcnt(0) -- the conservative form (debug flag 1 << 23), kept so that a
 // test can hold the counted waits against it bit for bit (same results, ~1.5 % slower).
-template <int PRO, int EPI, bool DRAIN, bool F16 = false>
+// FR: empty, or one SrfFrames = the RAGGED form (srf_pw_conv_pair_ragged): L stays the row stride, example b is frames[b]
+// columns long (a multiple of 4).  Launched with one tile per block; a block whose tile starts at or past its example's end
+// stores the tile's zeros of y2 and returns before any load or MFMA.  Columns are independent in a 1x1 convolution, so inside a
+// tile nothing is masked on load: x past the end may hold anything, y -- the residual stream, read by pointwise consumers only
+// -- gets whatever comes out there, and y2, whose statistics the next GlobLN uses, is selected to exact zeros before the store
+// and the sums.  The prologue's statistics count K1 * frames[b] values.
+template <int PRO, int EPI, bool DRAIN, bool F16 = false, typename... FR>
 __global__ __launch_bounds__(256, 2) void srf_pw_x3f_kernel(PwPairArgs a, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta) {
+                                                            const float* __restrict__ beta, FR... fr) {
   static_assert(PRO >= 0 && PRO <= 2, "conv 1's prologue: none, GlobLN, GlobLN + PReLU");
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  if constexpr (RAGGED) {      // (grid = total: this block's only tile is blockIdx.x)
+    const int b0 = (int)blockIdx.x / a.nLt, col0 = ((int)blockIdx.x - b0 * a.nLt) * 128;
+    if (col0 >= srf_frames_of(b0, fr...)) {      // block-uniform
+      const int c4z = col0 + ((int)threadIdx.x & 31) * 4;
+      if (c4z < a.L)
+        for (int r = (int)threadIdx.x >> 5; r < a.C2; r += 8)
+          *reinterpret_cast<float4*>(a.y2 + ((size_t)b0 * a.C2 + r) * a.L + c4z) = make_float4(0.f, 0.f, 0.f, 0.f);
+      return;
+    }
+  }
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = lane & 31, h = lane >> 5;
@@ -97,7 +114,8 @@ __global__ __launch_bounds__(256, 2) void srf_pw_x3f_kernel(PwPairArgs a, const 
   const int nk1 = K1 >> 4;                 // 16-k steps of conv 1 (multiple of 4, >= 8: host checks)
   const int npass = C2 >> 7;               // 128-row passes of conv 2
   const int nblk = gridDim.x;
-  const int ntile = (a.total - (int)blockIdx.x + nblk - 1) / nblk;   // >= 1 (grid <= total)
+  // >= 1 (grid <= total); the ragged form is launched with one tile per block: no next tile, no prefetch across tiles
+  const int ntile = RAGGED ? 1 : (a.total - (int)blockIdx.x + nblk - 1) / nblk;
   const float slope = PRO == 2 ? a.nrm.prelu[0] : 1.f;
   const int x_bytes = a.Bt * K1 * L * 4;
 
@@ -135,7 +153,9 @@ __global__ __launch_bounds__(256, 2) void srf_pw_x3f_kernel(PwPairArgs a, const 
     // same order as srf_pwconv_x3p.hip's table: identical {mean, rstd})
     t.mean = 0.f;
     t.rstd = 1.f;
-    if constexpr (PRO != 0) srf_finalize_stats_dpp(a.nrm.sums, t.b, a.inv_count, t.mean, t.rstd);
+    if constexpr (PRO != 0)
+      srf_finalize_stats_dpp(a.nrm.sums, t.b, RAGGED ? 1.0 / ((double)K1 * (double)srf_frames_of(t.b, fr...)) : a.inv_count, t.mean,
+                             t.rstd);
     return t;
   };
   __amdgpu_buffer_rsrc_t x_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
@@ -547,6 +567,12 @@ __global__ __launch_bounds__(256, 2) void srf_pw_x3f_kernel(PwPairArgs a, const 
             o.y += bs[it];
             o.z += bs[it];
             o.w += bs[it];
+            if constexpr (RAGGED) {      // (re-derived from a scalar at the point of use: nothing more lives across the k-loops)
+              // this lane's float4 lies inside the example (the limit pinned to a scalar register: left to itself hipcc keeps it
+              // per lane across the k-loops and spills two registers)
+              const bool in4 = c4 < __builtin_amdgcn_readfirstlane(srf_frames_of(b, fr...) - tc.colw);
+              o = in4 ? o : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
             ob[uu][it] = u32x4{__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(o.w)};
             if (ok4) {
               s += (o.x + o.y) + (o.z + o.w);
@@ -600,7 +626,7 @@ bool srf_x3f_supported(int Bt, int K1, int C2, int L) {
 
 // wpack1 / wpack2: the PAIRED-BLOCK image of the two weights (srf_x3p_packed_bytes; the second image of a packed buffer)
 // f16: the training forward's form (packed3 fp16 images, PRO 1 / 2 only)
-int srf_pw_x3f_launch(const PwPairArgs& a0, int pro, hipStream_t st, bool f16) {
+int srf_pw_x3f_launch(const PwPairArgs& a0, int pro, hipStream_t st, bool f16, const SrfFrames* frames) {
   PwPairArgs a = a0;
   SRF_CHECK_ARG(srf_x3f_supported(a.Bt, a.K1, a.C2, a.L), "srf_pw_conv_pair: shape not served by the fused pair kernel");
   SRF_CHECK_ARG(pro >= 0 && pro <= 2, "srf_pw_conv_pair: prologue %d", pro);
@@ -616,7 +642,9 @@ int srf_pw_x3f_launch(const PwPairArgs& a0, int pro, hipStream_t st, bool f16) {
     const void* fns[] = {(const void*)&srf_pw_x3f_kernel<1, 0, false>, (const void*)&srf_pw_x3f_kernel<2, 1, false>,
                          (const void*)&srf_pw_x3f_kernel<1, 0, true>, (const void*)&srf_pw_x3f_kernel<2, 1, true>,
                          (const void*)&srf_pw_x3f_kernel<0, 1, false>, (const void*)&srf_pw_x3f_kernel<0, 1, true>,
-                         (const void*)&srf_pw_x3f_kernel<1, 0, false, true>, (const void*)&srf_pw_x3f_kernel<2, 1, false, true>};
+                         (const void*)&srf_pw_x3f_kernel<1, 0, false, true>, (const void*)&srf_pw_x3f_kernel<2, 1, false, true>,
+                         (const void*)&srf_pw_x3f_kernel<1, 0, false, false, SrfFrames>,
+                         (const void*)&srf_pw_x3f_kernel<2, 1, false, false, SrfFrames>};
     for (const void* f : fns) good &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES) == hipSuccess;
     return good ? 1 : 0;
   }, nullptr);
@@ -629,6 +657,17 @@ int srf_pw_x3f_launch(const PwPairArgs& a0, int pro, hipStream_t st, bool f16) {
   long nb = total <= 16 * slots && !srf_dbg(SRF_DBG_PAIR_PERSISTENT) ? total : slots - slots % 8;   // (flag 1 << 21: always persistent -- tests)
   if (nb > total) nb = total;
   dim3 grid((unsigned)nb), block(256);
+  if (frames) {      // the ragged forms: one tile per block whatever the size (a block skips its tile as a whole)
+    SRF_CHECK_ARG(!f16 && (pro == 1 || pro == 2), "srf_pw_conv_pair_ragged: forms built: GlobLN, GlobLN + PReLU with residual");
+    SRF_CHECK_ARG(total <= 0x7fffffffL, "srf_pw_conv_pair_ragged: too many tiles");
+    grid = dim3((unsigned)total);
+    if (pro == 1)
+      hipLaunchKernelGGL((srf_pw_x3f_kernel<1, 0, false, false, SrfFrames>), grid, block, F_LDS_BYTES, st, a, a.nrm.gamma, a.nrm.beta, *frames);
+    else
+      hipLaunchKernelGGL((srf_pw_x3f_kernel<2, 1, false, false, SrfFrames>), grid, block, F_LDS_BYTES, st, a, a.nrm.gamma, a.nrm.beta, *frames);
+    SRF_CHECK_LAUNCH(pro == 1 ? "pw_pair_x3f_ragged<1>" : "pw_pair_x3f_ragged<2>", st);
+    return SRF_OK;
+  }
 #define F_GO(...) hipLaunchKernelGGL((srf_pw_x3f_kernel<__VA_ARGS__>), grid, block, F_LDS_BYTES, st, a, a.nrm.gamma, a.nrm.beta)
   if (f16) {
     SRF_CHECK_ARG(pro == 1 || pro == 2, "srf_pw_conv_pair (fp16 parts): prologue %d not built", pro);

@@ -109,11 +109,18 @@ __device__ __forceinline__ void w_split8_f16(const float (&v)[8], bf16x8& hi, bf
 //     (VERDICT r2 next 4).  Same stages, DMA, swizzle and fragment reads: a k-tile then holds 16 k instead of 32 -- the "hi"
 //     image carries h (slots 0-15) and m (slots 16-31) of those 16 k, the "lo" image l (slots 0-15) -- so what was the second
 //     k-sub-step's fragment pair is the m part (srf_x3w_pack3_kernel writes the weights that way, lds_store the activations).
-template <int PRO, int EPI, int CP = 0, int NP = 2>
+// FR: empty, or one SrfFrames = the RAGGED form (srf_pw_conv_packed_ragged): L stays the row stride, example b is frames[b]
+//     columns long.  The statistics table counts Cin * frames[b] values per example; an epilogue that accumulates statistics
+//     (EPI 0) selects exact zeros for columns at or past frames[b] before the store and the sums.  Columns are independent in a
+//     1x1 convolution, so nothing is masked on load and the residual form (EPI 1: the block stream, pointwise consumers only)
+//     stores whatever comes out past the end.  Every tile is computed: this form skips nothing (the fused pair does).
+template <int PRO, int EPI, int CP = 0, int NP = 2, typename... FR>
 __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char* __restrict__ wpack, int nMt, int nLt,
                                                             int total, int rounds, const float* __restrict__ gamma,
                                                             const float* __restrict__ beta, const float* __restrict__ bias_r,
-                                                            const char* __restrict__ wdpack, float* __restrict__ zpart, int zM, int mgrp) {
+                                                            const char* __restrict__ wdpack, float* __restrict__ zpart, int zM, int mgrp,
+                                                            FR... rg) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // W_NSTAGE * W_STAGE (+ the statistics table)
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -145,8 +152,10 @@ __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const double s = srf_dpp_wave_sum(bk[u].x), q = srf_dpp_wave_sum(bk[u].y);   // totals in lane 63
-        const double m = s * a.inv_count;
-        double v = q * a.inv_count - m * m;
+        const double inv_count =
+            RAGGED ? 1.0 / ((double)Cin * (double)srf_frames_of(min(b0 + u, a.Bt - 1), rg...)) : a.inv_count;
+        const double m = s * inv_count;
+        double v = q * inv_count - m * m;
         v = v < 0.0 ? 0.0 : v;
         if (lane == 63 && b0 + u < a.Bt) stat_tab[b0 + u] = make_float2((float)m, (float)(1.0 / sqrt(v + 1e-8)));
       }
@@ -804,6 +813,9 @@ __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char
               }
               int mc, lc;
               const bool okr = epi_row(mi, ii, mc), okc = epi_col(ni, lc);
+              if constexpr (RAGGED && EPI == 0) {      // (frames % 4 == 0: a float4 lies inside or outside as a whole)
+                if (lcol + ni * 32 + c4 >= srf_frames_of((int)b, rg...)) o = make_float4(0.f, 0.f, 0.f, 0.f);
+              }
               if (okr && okc) {
                 if constexpr ((CP & 3) == 0) {
                   *reinterpret_cast<float4*>(yb + mc * L + lc) = o;
@@ -938,9 +950,9 @@ int srf_x3w_pack_f16_launch(const float* const* w, char* const* dst, const int* 
 
 // fuse_wd != null: the mask epilogue fused with the decoder's contraction (EPI 4; pro 3, mask epilogue, fuse_M <= 64)
 static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, const char* fuse_wd, float* fuse_z, int fuse_M,
-                                 hipStream_t st, int np = 2);
-int srf_pw_x3w_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st) {
-  return srf_pw_x3w_launch_any(a, wpack, pro, nullptr, nullptr, 0, st);
+                                 hipStream_t st, int np = 2, const SrfFrames* frames = nullptr);
+int srf_pw_x3w_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st, const SrfFrames* frames) {
+  return srf_pw_x3w_launch_any(a, wpack, pro, nullptr, nullptr, 0, st, 2, frames);
 }
 // three-part operands, six MFMAs per product block (the training forward); wpack3: srf_x3w_pack3_launch's image
 // two fp16 parts, three MFMAs per product block (the training forward's default); wpack: srf_x3w_pack_f16_launch's image
@@ -1053,7 +1065,7 @@ int srf_pw_x3w_fused_tail_launch(const PwArgs& a, const char* wpack, const char*
 }
 
 static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, const char* fuse_wd, float* fuse_z, int fuse_M,
-                                 hipStream_t st, int np) {
+                                 hipStream_t st, int np, const SrfFrames* frames) {
   const int nMt = (a.Cout + W_BM - 1) / W_BM, nLt = (a.L + W_BN - 1) / W_BN;
   const long total = (long)a.Bt * nMt * nLt;
   SRF_CHECK_ARG(total < (1L << 31), "srf_pw_conv: too many tiles");
@@ -1075,6 +1087,9 @@ static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, co
         // three bf16 parts per operand (training forward, debug flag 16384)
         (const void*)&srf_pw_x3w_kernel<0, 0, 0, 3>, (const void*)&srf_pw_x3w_kernel<1, 0, 5, 3>,
         (const void*)&srf_pw_x3w_kernel<2, 1, 5, 3>, (const void*)&srf_pw_x3w_kernel<3, 0, 5, 3>,
+        // the ragged forms (srf_pw_conv_packed_ragged)
+        (const void*)&srf_pw_x3w_kernel<0, 0, 0, 2, SrfFrames>, (const void*)&srf_pw_x3w_kernel<1, 0, 5, 2, SrfFrames>,
+        (const void*)&srf_pw_x3w_kernel<2, 1, 5, 2, SrfFrames>,
         // any other prologue / epilogue combination (unit tests, stand-alone srf_pw_conv callers)
         (const void*)&srf_pw_x3w_kernel<0, 3>, (const void*)&srf_pw_x3w_kernel<1, 3>,
         (const void*)&srf_pw_x3w_kernel<2, 3>, (const void*)&srf_pw_x3w_kernel<3, 3>};
@@ -1112,6 +1127,18 @@ static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, co
   // stores looked 10 % faster on proj_1x1 alone and cost 5 % in the model, where the next kernel reads that tensor): proj_1x1
   // plain (CP 0); bottleneck, res_conv, mask non-temporal activation loads + stores (CP 5; the fused mask + decoder GEMM
   // has no output tensor to mark: CP 4).
+  if (frames) {
+#define W_GOR(P, E, C) hipLaunchKernelGGL((srf_pw_x3w_kernel<P, E, C, 2, SrfFrames>), grid, block, lds, st, ap, wpack, nMt, nLt, (int)total, rounds, a.nrm.gamma, a.nrm.beta, a.bias, fuse_wd, fuse_z, fuse_M, mgrp, *frames)
+    SRF_CHECK_ARG(np == 2 && !mask && !fuse_wd && (pro == 2) == res && pro != 3,
+                  "srf_pw_conv_packed_ragged: forms built: no prologue / GlobLN (statistics out), GlobLN + PReLU with residual");
+    if (pro == 0) W_GOR(0, 0, 0);
+    else if (pro == 1) W_GOR(1, 0, 5);
+    else W_GOR(2, 1, 5);
+#undef W_GOR
+    static const char* const kLabelR[3] = {"pw_conv_x3w_ragged<0>", "pw_conv_x3w_ragged<1>", "pw_conv_x3w_ragged<2>"};
+    SRF_CHECK_LAUNCH(kLabelR[pro], st);
+    return SRF_OK;
+  }
   if (np == 4) {
 #define W_GO4(P, E, C) hipLaunchKernelGGL((srf_pw_x3w_kernel<P, E, C, 4>), grid, block, lds, st, ap, wpack, nMt, nLt, (int)total, rounds, a.nrm.gamma, a.nrm.beta, a.bias, fuse_wd, fuse_z, fuse_M, mgrp)
     SRF_CHECK_ARG(!mask && !fuse_wd && (pro == 2) == res && !(pro != 2 && res), "srf_pw_conv (fp16 two-part): form not built");

@@ -24,4 +24,5 @@ struct PyrRegArgs {
                        // re-computes d_0 from y1)
 };
 
-int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st);
+// frames: null = the uniform kernels; else the ragged forms (pass 1 always persistent, no level outputs)
+int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st, const SrfFrames* frames = nullptr);

@@ -609,14 +609,19 @@ struct PyrFinArgs {
 #define SRF_FIN_CPT 8   // channels per thread (C <= 256 * 8)
 // CPT = channels per thread (C <= 256 * CPT): 2 covers the published models (C = 512) and keeps the whole example's
 // moments in registers; 8 is the general fallback (moments fetched level by level).
-template <int CPT>
-__global__ __launch_bounds__(256) void srf_pyramid_finalize_kernel(PyrFinArgs a) {
+// RAGGED (srf_pyramid_ragged): the example's own length frames[g] replaces L in the three places the edge algebra uses it --
+// the count of interior positions (L_k - 3), the position of the last edge (pass 1 took C_k[last] there) and the statistics'
+// count C * L_k -- and in the count of the input norm.
+template <int CPT, typename... FR>
+__global__ __launch_bounds__(256) void srf_pyramid_finalize_kernel(PyrFinArgs a, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   __shared__ double red[16];
   const long g = blockIdx.x;
   const int tid = threadIdx.x, C = a.C, D = a.D;
+  const int Lg = srf_frames_of((int)g, fr...);   // (RAGGED only)
   if (a.in_sums && tid < 64) {   // wavefront 0: the input norm's {mean, rstd} for pass 2
     float m, r;
-    srf_finalize_stats(a.in_sums, g, a.in_inv_count, m, r);
+    srf_finalize_stats(a.in_sums, g, RAGGED ? 1.0 / ((double)C * (double)Lg) : a.in_inv_count, m, r);
     if (tid == 0) {
       a.in_mr[2 * g] = m;
       a.in_mr[2 * g + 1] = r;
@@ -650,7 +655,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_finalize_kernel(PyrFinArgs a)
 #pragma unroll
   for (int k = 0; k < SRF_MAX_DEPTH; ++k) {
     if (k >= D) break;
-    const int Lk = a.L >> k;
+    const int Lk = (RAGGED ? Lg : a.L) >> k;
     const int slot = PRE ? k : 0;
     if (!PRE) load_level(0, k);
     // next level's coefficients (independent of this level's statistics)
@@ -749,8 +754,13 @@ static size_t pyr_lds_bytes(int L, int D) {
   return sizeof(float) * ((size_t)L + 8 + sizeA) + sizeof(double) * (4 * SRF_MAX_DEPTH * 2 + 8);
 }
 
-static void srf_pyramid_finalize_launch(const PyrFinArgs& f, int groups, int C, hipStream_t st) {
-  if (C <= 512)
+static void srf_pyramid_finalize_launch(const PyrFinArgs& f, int groups, int C, hipStream_t st, const SrfFrames* frames = nullptr) {
+  if (frames && C <= 512)
+    hipLaunchKernelGGL((srf_pyramid_finalize_kernel<2, SrfFrames>), dim3((unsigned)groups), dim3(256), 0, st, f, *frames);
+  else if (frames)
+    hipLaunchKernelGGL((srf_pyramid_finalize_kernel<SRF_FIN_CPT, SrfFrames>), dim3((unsigned)groups), dim3(256), 0, st, f,
+                       *frames);
+  else if (C <= 512)
     hipLaunchKernelGGL(srf_pyramid_finalize_kernel<2>, dim3((unsigned)groups), dim3(256), 0, st, f);
   else
     hipLaunchKernelGGL((srf_pyramid_finalize_kernel<SRF_FIN_CPT>), dim3((unsigned)groups), dim3(256), 0, st, f);
@@ -823,10 +833,45 @@ extern "C" int srf_pyramid(const float* y1, float* merged, const srf_norm* in_no
                           stream);
 }
 
+static int pyramid_run(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
+                       const float* const* bias, const float* const* gamma, const float* const* beta, int groups, int C,
+                       int L, int D, void* scratch, double* out_sums, float* const* lv_out, double* const* lv_sums,
+                       void* stream, const SrfFrames* frames);
 int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
                      const float* const* bias, const float* const* gamma, const float* const* beta, int groups, int C,
                      int L, int D, void* scratch, double* out_sums, float* const* lv_out, double* const* lv_sums,
                      void* stream) {
+  return pyramid_run(y1, merged, in_norm, w, bias, gamma, beta, groups, C, L, D, scratch, out_sums, lv_out, lv_sums, stream,
+                     nullptr);
+}
+
+// The length an example of a ragged batch may have: what the register-resident kernels and the finalize step's edge algebra
+// accept as a row length of its own (srf_pyramid_supported's first two conditions), at most the row stride.
+extern "C" int srf_pyramid_ragged_frames_ok(int frames, int L, int D) {
+  if (D < 1 || D > SRF_MAX_DEPTH || frames < 1 || frames > L) return 0;
+  if ((frames >> (D - 1)) < 8 || (frames % (1 << (D - 1))) != 0) return 0;
+  return srf_pyramid_reg_supported(frames, D) ? 1 : 0;
+}
+
+extern "C" int srf_pyramid_ragged(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
+                                  const float* const* bias, const float* const* gamma, const float* const* beta, int groups,
+                                  int C, int L, int D, void* scratch, double* out_sums, const int* frames, void* stream) {
+  SrfFrames fr;
+  int rc = srf_frames_table("srf_pyramid_ragged", frames, groups, L, &fr);
+  if (rc) return rc;
+  SRF_CHECK_ARG(srf_pyramid_supported(C, L, D) && !srf_dbg(SRF_DBG_PYR_NO_REG) && srf_pyramid_reg_supported(L, D),
+                "srf_pyramid_ragged: the register-resident pyramid does not take C=%d L=%d D=%d", C, L, D);
+  for (int g = 0; g < groups; ++g)
+    SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(frames[g], L, D),
+                  "srf_pyramid_ragged: example %d has %d frames: too short for the pyramid's edge algebra or off its chunk grid "
+                  "(D=%d)", g, frames[g], D);
+  return pyramid_run(y1, merged, in_norm, w, bias, gamma, beta, groups, C, L, D, scratch, out_sums, nullptr, nullptr, stream, &fr);
+}
+
+static int pyramid_run(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
+                       const float* const* bias, const float* const* gamma, const float* const* beta, int groups, int C,
+                       int L, int D, void* scratch, double* out_sums, float* const* lv_out, double* const* lv_sums,
+                       void* stream, const SrfFrames* frames) {
   SRF_CHECK_ARG((lv_out == nullptr) == (lv_sums == nullptr), "srf_pyramid: level outputs and level sums come together");
   SRF_CHECK_ARG(y1 && merged && w && bias && gamma && beta && scratch, "srf_pyramid: null pointer");
   SRF_CHECK_ARG(groups > 0 && C > 0 && L > 0, "srf_pyramid: bad sizes");
@@ -895,7 +940,7 @@ int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, co
     r.D = D;
     r.rows = r.rpw = 0;
     r.tiles = r.own = 0;
-    if (srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT)) {   // non-persistent pass 1: atomics into mom + pre-finalised statistics
+    if (!frames && srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT)) {   // non-persistent pass 1: atomics into mom + pre-finalised statistics
       SRF_CHECK_HIP(hipMemsetAsync(mom, 0, sizeof(double) * (size_t)rows * D * 5, st));
       if (a.in_norm.sums) {
         hipLaunchKernelGGL(srf_stats_finalize_kernel, dim3((unsigned)groups), dim3(64), 0, st, a.in_norm.sums,
@@ -904,13 +949,15 @@ int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, co
       }
     }
     SRF_CHECK_ARG(merged != y1, "srf_pyramid: merged must not alias y1 (pass 2 re-reads y1 with halos)");
-    int rc = srf_pyramid_reg_launch(r, true, rows, st);
+    int rc = srf_pyramid_reg_launch(r, true, rows, st, frames);
     if (rc) return rc;
-    if (!srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT)) f.in_sums = a.in_norm.sums;
-    srf_pyramid_finalize_launch(f, groups, C, st);
-    SRF_CHECK_LAUNCH("pyramid_finalize", st);
-    return srf_pyramid_reg_launch(r, false, rows, st);
+    if (frames || !srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT)) f.in_sums = a.in_norm.sums;
+    srf_pyramid_finalize_launch(f, groups, C, st, frames);
+    if (frames) SRF_CHECK_LAUNCH("pyramid_finalize_ragged", st);
+    else SRF_CHECK_LAUNCH("pyramid_finalize", st);
+    return srf_pyramid_reg_launch(r, false, rows, st, frames);
   }
+  SRF_CHECK_ARG(!frames, "srf_pyramid: internal: the ragged form exists for the register-resident kernels only");
   PyrTile tile;
   if (!srf_dbg(SRF_DBG_PYR_NO_LDS_TILES) && pyr_pick_tile(L, D, &tile)) {
     tile.tasks = rows * tile.tiles;

@@ -146,9 +146,14 @@ __device__ __forceinline__ void srf_pyr_store_level(float* dst, const float (&v)
 // SAVE (pass 2 only): also write every level's raw conv output d_k -- what the training backward needs -- so the
 // training forward is the same two fused passes instead of D depthwise kernels + a merge kernel (7.75 -> 4.94 C*L of
 // traffic per block).
-template <bool MOMENTS, int CH, bool PERSIST = MOMENTS, bool SAVE = false>
+// RAGGED (srf_pyramid_ragged): L stays the row STRIDE, the row LENGTH of example g is frames[g] (a multiple of CH, at most L).
+// Chunks at or past it are zero padding exactly as chunks past L are in the uniform form: loads are clamped to the example's
+// last chunk, the edge moments sit at its own last position, the proj statistics count C * frames[g] values, pass 1 walks only
+// the tiles that reach into the example, and pass 2 writes zeros from frames[g] to L (a tile wholly past the end loads nothing).
+template <bool MOMENTS, int CH, bool PERSIST = MOMENTS, bool SAVE = false, typename... FR>
 // (no occupancy attribute: pinning 6 wavefronts per SIMD made the persistent pass 1 spill VGPRs to scratch memory)
-__global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
+__global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   __shared__ float4 pyr_strip[MOMENTS ? 1 : 4 * 60 * (CH / 4 + 1)];   // pass 2: store transposition
   const int lane = threadIdx.x & 63;
   const int L = a.L, D = a.D, C = a.C;
@@ -178,8 +183,22 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
     if (tile >= a.tiles) return;   // wave-uniform
   }
   const float* in_base = a.y1;   // both passes start from y1: pass 2 recomputes level 0 instead of re-reading it
-  auto chunk_src = [&](int row_, int tile_) {
-    const int ci_ = min(max(tile_ * a.own - 2 + lane, 0), nchunks - 1);   // clamped: loads unconditional
+  // nch = chunks of the current row that hold data, ntl = tiles that reach into them (uniform: every chunk, every tile)
+  int nch = nchunks, ntl = a.tiles;
+  if constexpr (RAGGED) {
+    nch = srf_frames_of(g, fr...) / CH;
+    ntl = (nch + a.own - 1) / a.own;
+    if (!MOMENTS && tile >= ntl) {   // wave-uniform: the whole tile lies past the example's end -- zeros, no load
+      float zv[CH];
+      srf_zero(zv);
+      const int ci0 = tile * a.own - 2 + lane;
+      srf_pyr_store_chunks<CH>(pyr_strip + wave * (60 * (CH / 4 + 1)), zv, ci0 < nchunks && lane >= 2 && lane < 2 + a.own,
+                               a.merged + (size_t)row * L, tile * a.own, min(a.own, nchunks - tile * a.own), lane);
+      return;
+    }
+  }
+  auto chunk_src = [&](int row_, int tile_, int nch_) {
+    const int ci_ = min(max(tile_ * a.own - 2 + lane, 0), nch_ - 1);   // clamped: loads unconditional
     return reinterpret_cast<const float4*>(in_base + (size_t)row_ * L + ci_ * CH);
   };
   float s1[6], s2[6];
@@ -187,20 +206,24 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
   float in_mean = 0.f, in_rstd = 1.f;
   float4 pre[CH / 4];
   {
-    const float4* src = chunk_src(row, tile);
+    const float4* src = chunk_src(row, tile, nch);
 #pragma unroll
     for (int i = 0; i < CH / 4; ++i) pre[i] = src[i];
   }
   for (;;) {
   // the task after this one (persistent only)
   int nrow = row, ntile = tile + 1;
-  if (ntile == a.tiles) {
+  int nnch = nch;                                  // chunks of the next task's row (RAGGED: the next example's when c wraps)
+  if (ntile == ntl) {
     ntile = 0;
     nrow = row + 1;
+    if constexpr (RAGGED) {
+      if (c + 1 == C && nrow < row_end) nnch = srf_frames_of(g + 1, fr...) / CH;
+    }
   }
   const bool last_task = !PERSIST || nrow >= row_end;
   const int ci = tile * a.own - 2 + lane;          // this lane's chunk index in the row
-  const bool valid = ci >= 0 && ci < nchunks;      // inside the row (else: zero padding)
+  const bool valid = ci >= 0 && ci < nch;          // inside the row (else: zero padding)
   const bool own = valid && lane >= 2 && lane < 2 + a.own;
 
   // per-level coefficients (wave-uniform -> scalar loads, all issued up front)
@@ -229,7 +252,8 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
     if (a.in_norm.sums) {
       if (PERSIST) {
         if (g != cur_g) {   // wave-uniform
-          srf_finalize_stats(a.in_norm.sums, g, a.in_inv_count, in_mean, in_rstd);
+          const double inv_count = RAGGED ? 1.0 / ((double)C * (double)(nch * CH)) : a.in_inv_count;
+          srf_finalize_stats(a.in_norm.sums, g, inv_count, in_mean, in_rstd);
           cur_g = g;
         }
       } else {
@@ -271,7 +295,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
   }
 
   if (PERSIST) {  // prefetch the next task's chunk (the last task re-reads its own: surplus loads are harmless)
-    const float4* src = chunk_src(last_task ? row : nrow, last_task ? tile : ntile);
+    const float4* src = chunk_src(last_task ? row : nrow, last_task ? tile : ntile, last_task ? nch : nnch);
 #pragma unroll
     for (int i = 0; i < CH / 4; ++i) pre[i] = src[i];
   }
@@ -292,7 +316,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
   double* mrow = a.mom + (size_t)row * D * 5;
   if (MOMENTS && own) {
     srf_acc_moments<CH>(x0, s1[0], s2[0]);
-    srf_pyr_edges<CH>(mrow, x0, ci, nchunks);
+    srf_pyr_edges<CH>(mrow, x0, ci, nch);
   }
   if (D > 1) {
     srf_conv_s2<CH>(x0, x1, lc[1].w, lc[1].b);
@@ -300,7 +324,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
     srf_affine_mask<CH / 2>(x1, lc[1].a, lc[1].c, valid);
     if (MOMENTS && own) {
       srf_acc_moments<CH / 2>(x1, s1[1], s2[1]);
-      srf_pyr_edges<CH / 2>(mrow + 5, x1, ci, nchunks);
+      srf_pyr_edges<CH / 2>(mrow + 5, x1, ci, nch);
     }
   }
   if (D > 2) {
@@ -309,7 +333,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
     srf_affine_mask<CH / 4>(x2, lc[2].a, lc[2].c, valid);
     if (MOMENTS && own) {
       srf_acc_moments<CH / 4>(x2, s1[2], s2[2]);
-      srf_pyr_edges<CH / 4>(mrow + 10, x2, ci, nchunks);
+      srf_pyr_edges<CH / 4>(mrow + 10, x2, ci, nch);
     }
   }
   if (D > 3) {
@@ -318,7 +342,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
     srf_affine_mask<CH / 8>(x3, lc[3].a, lc[3].c, valid);
     if (MOMENTS && own) {
       srf_acc_moments<CH / 8>(x3, s1[3], s2[3]);
-      srf_pyr_edges<CH / 8>(mrow + 15, x3, ci, nchunks);
+      srf_pyr_edges<CH / 8>(mrow + 15, x3, ci, nch);
     }
   }
   if (D > 4) {
@@ -327,7 +351,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
     srf_affine_mask<CH / 16>(x4, lc[4].a, lc[4].c, valid);
     if (MOMENTS && own) {
       srf_acc_moments<CH / 16>(x4, s1[4], s2[4]);
-      srf_pyr_edges<CH / 16>(mrow + 20, x4, ci, nchunks);
+      srf_pyr_edges<CH / 16>(mrow + 20, x4, ci, nch);
     }
   }
   if constexpr (CH >= 32) {
@@ -337,7 +361,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
       srf_affine_mask<CH / 32>(x5, lc[5].a, lc[5].c, valid);
       if (MOMENTS && own) {
         srf_acc_moments<CH / 32>(x5, s1[5], s2[5]);
-        srf_pyr_edges<CH / 32>(mrow + 25, x5, ci, nchunks);
+        srf_pyr_edges<CH / 32>(mrow + 25, x5, ci, nch);
       }
     }
   }
@@ -345,7 +369,7 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
   if (MOMENTS) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-      if (PERSIST && tile != a.tiles - 1) break;   // the row's last tile flushes
+      if (PERSIST && tile != ntl - 1) break;   // the row's last tile flushes
       if (k < D) {
         const float r1 = srf_dpp_wave_sum(s1[k]);
         const float r2 = srf_dpp_wave_sum(s2[k]);
@@ -403,7 +427,9 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
       ms = 0.f;
       mq = 0.f;
     }
-    srf_pyr_store_chunks<CH>(pyr_strip + wave * (60 * (CH / 4 + 1)), outv, own, a.merged + (size_t)row * L, tile * a.own,
+    // (RAGGED: chunks from the example's end to the row stride are stored too; their lanes hold exact zeros)
+    const bool own_st = RAGGED ? ci >= 0 && ci < nchunks && lane >= 2 && lane < 2 + a.own : own;
+    srf_pyr_store_chunks<CH>(pyr_strip + wave * (60 * (CH / 4 + 1)), outv, own_st, a.merged + (size_t)row * L, tile * a.own,
                              min(a.own, nchunks - tile * a.own), lane);
     if (a.out_sums) {
       // (DPP wave sums: VALU only; the __shfl_xor form is 24 ds_bpermute per tile on every wavefront's critical path)
@@ -419,6 +445,10 @@ __global__ __launch_bounds__(256) void srf_pyramid_reg_kernel(PyrRegArgs a) {
   if (ntile == 0 && ++c == C) {
     c = 0;
     ++g;
+    if constexpr (RAGGED) {
+      nch = nnch;
+      ntl = (nch + a.own - 1) / a.own;
+    }
   }
   row = nrow;
   tile = ntile;
@@ -432,7 +462,7 @@ bool srf_pyramid_reg_supported(int L, int D) {
 }
 
 // moments / finalize / merge launches are driven by srf_pyramid() in srf_pyramid.hip
-int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st) {
+int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st, const SrfFrames* frames) {
   const int CH = a.D <= 5 ? 16 : 32;
   const int nchunks = a.L / CH;
   a.tiles = (nchunks + 59) / 60;
@@ -440,7 +470,7 @@ int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st
   SRF_CHECK_ARG(rows * a.tiles < (1L << 31) && rows / a.C <= 65535, "srf_pyramid: too many rows");
   a.rows = (int)rows;
   // pass 1 persistent (grid = co-resident wavefronts, cached occupancy query) unless debug flag 128
-  const bool persist = moments && !srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT);
+  const bool persist = moments && (frames || !srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT));   // (the ragged pass 1: always)
   // co-resident wavefronts of the persistent pass 1 on THIS device (per-device cache, srf_common.h)
   long cw = 0;
   if (persist) {
@@ -472,6 +502,16 @@ int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st
   if (save)
     for (int k = 0; k < a.D; ++k)
       SRF_CHECK_ARG((a.lv_out[k] || (k == 0 && a.D > 1)) && srf_aligned16(a.lv_out[k]), "srf_pyramid: level output %d missing / unaligned", k);
+  if (frames) {
+    SRF_CHECK_ARG(!save, "srf_pyramid: the ragged form keeps no level outputs");
+    const SrfFrames& fr = *frames;
+    if (CH == 16 && moments) hipLaunchKernelGGL((srf_pyramid_reg_kernel<true, 16, true, false, SrfFrames>), grid, dim3(256), 0, st, a, fr);
+    else if (CH == 16) hipLaunchKernelGGL((srf_pyramid_reg_kernel<false, 16, false, false, SrfFrames>), grid, dim3(256), 0, st, a, fr);
+    else if (moments) hipLaunchKernelGGL((srf_pyramid_reg_kernel<true, 32, true, false, SrfFrames>), grid, dim3(256), 0, st, a, fr);
+    else hipLaunchKernelGGL((srf_pyramid_reg_kernel<false, 32, false, false, SrfFrames>), grid, dim3(256), 0, st, a, fr);
+    SRF_CHECK_LAUNCH(moments ? "pyramid_moments_ragged" : "pyramid_merge_ragged", st);
+    return SRF_OK;
+  }
   if (CH == 16) {
     if (moments && persist)
       hipLaunchKernelGGL((srf_pyramid_reg_kernel<true, 16, true>), grid, dim3(256), 0, st, a);

@@ -209,6 +209,12 @@ class SuDORMRF(nn.Module):
         """[batch, 1, time] float -> [batch, num_sources, time] float32, one srf_forward call."""
         return self._engine().run(self, input_wav, 1)
 
+    def forward_ragged(self, input_wav, lengths):
+        """Unequal-length utterances in ONE forward: input_wav [batch, 1, time] padded rows on the GPU, lengths a list or
+        CPU int tensor.  Row b of the result equals self(input_wav[b:b+1, :, :lengths[b]]) up to lengths[b] -- the example
+        padded to its own length, its GlobLNs over its own frames -- and is exactly zero past it.  eval() / no_grad only."""
+        return self._engine().run_ragged(self, input_wav, lengths)
+
     def pad_to_appropriate_length(self, x):
         """Kept for API parity (reference :303-314); the HIP path folds the padding into its bounds
         checks and never materialises the padded tensor."""

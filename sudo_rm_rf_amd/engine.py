@@ -123,6 +123,22 @@ class Plan:
                               _lib.current_stream(wav.device))
         _lib.check(rc, "srf_separate")
 
+    @property
+    def ragged_supported(self):
+        """Whether srf_forward_ragged takes this plan under the current kernel mode (srf_plan_ragged_supported)."""
+        return bool(_lib.load().srf_plan_ragged_supported(self.handle))
+
+    def forward_ragged(self, param_ptrs, wav, lengths, out):
+        """srf_forward_ragged: `lengths` is a host list; it travels in the launch arguments (nothing synchronises)."""
+        lib = _lib.load()
+        need = lib.srf_plan_ragged_workspace_bytes(self.handle)
+        if need > self.workspace_bytes:
+            raise _lib.SrfError("the ragged forward needs %d workspace bytes, the plan holds %d" % (need, self.workspace_bytes))
+        arr = (C.c_int * len(lengths))(*lengths)
+        rc = lib.srf_forward_ragged(self.handle, param_ptrs, self.num_params, _lib.ptr(wav), arr, _lib.ptr(out),
+                                    _lib.ptr(self.workspace), self.workspace_bytes, _lib.current_stream(wav.device))
+        _lib.check(rc, "srf_forward_ragged")
+
     def debug_fetch(self, what, shape):
         dst = torch.empty(shape, dtype=torch.float32, device=self.device)
         rc = _lib.load().srf_debug_fetch(self.handle, _lib.ptr(self.workspace), what, _lib.ptr(dst),
@@ -437,6 +453,49 @@ class ModelEngine:
             self._forward_split(self._splits(batch, T, x, out, table), x, out, table)
             self.last_plan = plan
         return out
+
+    def run_ragged(self, module, wav, lengths):
+        """Unequal-length utterances in one forward (srf_forward_ragged).  wav: [batch, 1, T] on the GPU, row b valid up to
+        lengths[b] (a list or CPU int tensor; what lies past it is never read); returns [batch, num_sources, T] with row b
+        equal to model(wav[b:b+1, :, :lengths[b]]) up to lengths[b] and exactly zero past it.  Inference only: a single
+        stream, no autograd graph."""
+        if not isinstance(wav, torch.Tensor) or wav.dim() != 3 or wav.shape[1] != 1:
+            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(getattr(wav, "shape", ())),))
+        if wav.device.type != "cuda":
+            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
+                                "fallback." % wav.device)
+        if isinstance(lengths, torch.Tensor):
+            if lengths.device.type != "cpu":
+                raise _lib.SrfError("lengths must be a list or a CPU tensor (reading a device tensor would synchronise)")
+            lengths = lengths.tolist()
+        lengths = [int(n) for n in lengths]
+        weights = _weights(module)
+        if module.training or (torch.is_grad_enabled() and any(t.requires_grad for t in weights)):
+            raise NotImplementedError("forward_ragged: the ragged batch is an inference path (model.eval() under "
+                                      "torch.no_grad()); there is no ragged training step")
+        params = [p.detach() for p in weights]
+        for p in params:
+            if p.device != wav.device or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % wav.device)
+        x = wav.detach().to(torch.float32).contiguous()
+        batch, _, T = x.shape
+        if batch == 0 or T == 0:
+            raise RuntimeError("empty input %s" % (tuple(wav.shape),))
+        if len(lengths) != batch:
+            raise RuntimeError("%d lengths for a batch of %d" % (len(lengths), batch))
+        with torch.cuda.device(x.device), self._run_lock(x.device):
+            plan = self.plan_for(batch, T, x.device)
+            if plan.num_params != len(params):
+                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
+            out = torch.empty((batch, module.num_sources, T), dtype=torch.float32, device=x.device)
+            plan.forward_ragged(self._param_table(params, x.device), x, lengths, out)
+            self.last_plan = plan
+        return out
+
+    def ragged_plan_supported(self, batch, T, device):
+        """Whether run_ragged would take a [batch, 1, T] input on `device` (creates / caches the plan, no workspace)."""
+        with torch.cuda.device(device):
+            return self.plan_for(batch, T, torch.device(device)).ragged_supported
 
     def separate(self, module, mixture, mixture_consistency):
         """The reference's caller-side recipe around model() (README.md:100-114) as one srf_separate call: mixture

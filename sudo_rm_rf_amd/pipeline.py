@@ -31,3 +31,88 @@ def separate(model, mixture, mixture_consistency=None):
         norm, stats = ops.wav_normalize(x)          # (multi-channel front ends: the three-kernel form)
         est = model(norm)
         return ops.wav_denormalize(est, stats, norm if mixture_consistency else None)
+
+
+# ---- lists of utterances of unequal length ----------------------------------------------------------------------------------
+BUCKET = 4000      # a batch's padded length is rounded up to a multiple of this many samples (0.5 s at 8 kHz): a folder of files
+                   # then re-uses a handful of (batch, T) plans instead of making one per distinct longest member
+
+
+def ragged_batches(lengths, max_batch=32, bucket=BUCKET):
+    """The batching of separate_list as a pure function.  lengths: the utterances' lengths in samples.  Returns a list of
+    (indices, T): utterances sorted by length (ties by index) and cut into runs of at most max_batch; T = the run's longest
+    member rounded up to the bucket grid.  Every index appears exactly once; neighbours in length share a batch, so the padding
+    a batch carries is small and the tiles past an example's end few."""
+    if max_batch < 1 or bucket < 1:
+        raise ValueError("max_batch and bucket must be positive")
+    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    out = []
+    for k in range(0, len(order), max_batch):
+        idx = order[k:k + max_batch]
+        longest = int(lengths[idx[-1]])
+        out.append((idx, -(-longest // bucket) * bucket))
+    return out
+
+
+def ragged_route(model, length=None):
+    """Where separate_list sends an utterance, decided from the model's configuration alone (no GPU): "ragged" = a candidate
+    for the ragged batch (the Improved model with one input channel, K = 21, 256 bottleneck channels; with `length`, also long
+    enough for the fused pyramid to take it as an example of its own), "single" = the per-example path (GroupComm and causal
+    models, other configurations, too-short utterances).  A candidate batch still falls back as a whole when the plan of its
+    (batch, T) is refused (srf_plan_ragged_supported: small shapes)."""
+    if type(model).__name__ != "SuDORMRF" or not hasattr(model, "forward_ragged"):
+        return "single"
+    if getattr(model, "enc_kernel_size", 0) != 21 or getattr(model, "out_channels", 0) != 256:
+        return "single"
+    if length is not None:
+        D = model.upsampling_depth
+        n_req = (model.enc_kernel_size // 2) << D
+        frames = max(n_req, -(-int(length) // n_req) * n_req) // (model.enc_kernel_size // 2)
+        chunk = 16 if D <= 5 else 32
+        if D > 6 or (frames >> (D - 1)) < 8 or frames % chunk or frames // chunk < 4:
+            return "single"
+    return "ragged"
+
+
+def separate_list(model, mixtures, mixture_consistency=None, max_batch=32):
+    """separate() over a list of utterances of unequal length: mixtures = tensors [T_i] or [1, T_i] on the model's MI355X;
+    returns the estimates [num_sources, T_i] in the caller's order.  The README recipe per utterance (mean / std over its own
+    samples, forward, rescale; mixture consistency as in separate()), with the forwards of a length-sorted batch run as ONE
+    ragged forward (SuDORMRF.forward_ragged) where the model and the batch allow it, and through separate() one by one where
+    they do not -- so the answer is always the per-utterance one."""
+    mixes = []
+    for m in mixtures:
+        if m.dim() == 2 and m.shape[0] == 1:
+            m = m[0]
+        if m.dim() != 1 or m.numel() == 0:
+            raise RuntimeError("separate_list() expects tensors [time] or [1, time], got %s" % (tuple(m.shape),))
+        mixes.append(m.detach().to(torch.float32))
+    if mixture_consistency is None:
+        mixture_consistency = type(model).__name__ == "GroupCommSudoRmRf"
+    results = [None] * len(mixes)
+    routes = [ragged_route(model, m.numel()) for m in mixes]
+    single = [i for i, r in enumerate(routes) if r == "single"]
+    cand = [i for i, r in enumerate(routes) if r != "single"]
+    with torch.no_grad():
+        for idx, T in ragged_batches([mixes[i].numel() for i in cand], max_batch):
+            idx = [cand[j] for j in idx]
+            dev = mixes[idx[0]].device
+            if len(idx) < 2 or not model._engine().ragged_plan_supported(len(idx), T, dev):
+                single.extend(idx)
+                continue
+            lens = [mixes[i].numel() for i in idx]
+            x = torch.zeros((len(idx), 1, T), dtype=torch.float32, device=dev)
+            stats = []
+            for r, i in enumerate(idx):           # per-utterance normalisation over its own samples (README.md:100-104)
+                mean, std = mixes[i].mean(), mixes[i].std()
+                x[r, 0, :lens[r]] = (mixes[i] - mean) / (std + 1e-9)
+                stats.append((mean, std))
+            est = model.forward_ragged(x, lens)
+            for r, i in enumerate(idx):
+                e = est[r, :, :lens[r]] * stats[r][1] + stats[r][0]
+                if mixture_consistency:           # (README.md:106-114: applied to the rescaled estimates, against the normalised mixture)
+                    e = e + (x[r, :, :lens[r]] - e.sum(0, keepdim=True)) / e.shape[0]
+                results[i] = e
+        for i in single:
+            results[i] = separate(model, mixes[i].unsqueeze(0), mixture_consistency)[0]
+    return results

@@ -1,0 +1,112 @@
+"""Ragged-batch forms of the kernels: one launch over examples of unequal length (include/sudormrf_hip.h, "Ragged forms").
+
+The tensors keep their uniform layout -- [batch, channels, L] with L the row stride -- and every example brings its own length
+in a host-side list.  What lies at or past an example's end is never read and may hold anything; outputs that carry GlobLN
+statistics are exact zeros there, and the statistics count the example's own elements only, so every example is treated as
+its own batch-1 call would treat it.  The lists travel in the launch arguments: nothing is uploaded, nothing synchronises."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .ops import _chk
+
+MAX_BATCH = _lib.RAGGED_MAX_BATCH
+
+
+def _table(values, what):
+    if isinstance(values, torch.Tensor) and values.device.type != "cpu":
+        raise _lib.SrfError("%s must be a list or a CPU tensor (reading a device tensor would synchronise)" % what)
+    vals = [int(v) for v in (values.tolist() if isinstance(values, torch.Tensor) else values)]
+    return (C.c_int * len(vals))(*vals), len(vals)
+
+
+def padded_frames(length, kernel_size, depth):
+    """Frames of one example of `length` samples as its own batch-1 forward would have them: the length padded up to a
+    multiple of (K // 2) * 2^depth (at least one), in hops (improved_sudormrf.py:244,303-314)."""
+    h = kernel_size // 2
+    n = h << depth
+    return max(n, -(-int(length) // n) * n) // h
+
+
+def frames_ok(frames, L, D):
+    """Whether an example of a ragged pyramid call may be `frames` long under row stride L (no GPU needed)."""
+    return bool(_lib.load().srf_pyramid_ragged_frames_ok(int(frames), int(L), int(D)))
+
+
+def encoder(wav, weight, L, lengths, frames, sums=None):
+    """srf_encoder_ragged: wav [Bt,1,T] (row b valid up to lengths[b]), weight [N,1,21] -> [Bt,N,L], zeros from frames[b] on."""
+    dev = _chk(wav, weight, sums)
+    Bt, A, T = wav.shape
+    N, A2, K = weight.shape
+    assert A == A2
+    lens, n1 = _table(lengths, "lengths")
+    frs, n2 = _table(frames, "frames")
+    if n1 != Bt or n2 != Bt:
+        raise _lib.SrfError("srf_encoder_ragged: %d lengths / %d frames for a batch of %d" % (n1, n2, Bt))
+    out = torch.empty((Bt, N, L), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().srf_encoder_ragged(_lib.ptr(wav), _lib.ptr(weight), _lib.ptr(out), _lib.ptr(sums), Bt, A, T, N, K, L,
+                                              lens, frs, _lib.current_stream(dev)), "srf_encoder_ragged")
+    return out
+
+
+def pyramid(y1, in_sums, in_gamma, in_beta, in_prelu, weights, biases, gammas, betas, frames, out_sums=None):
+    """srf_pyramid_ragged: y1 [groups,C,L] (row g valid up to frames[g]) -> merged [groups,C,L], zeros from frames[g] on."""
+    dev = _chk(y1, in_sums, in_gamma, in_beta, in_prelu, *weights, *biases, *gammas, *betas, out_sums)
+    groups, Cc, L = y1.shape
+    D = len(weights)
+    lib = _lib.load()
+    frs, n = _table(frames, "frames")
+    if n != groups:
+        raise _lib.SrfError("srf_pyramid_ragged: %d frames for %d examples" % (n, groups))
+    merged = torch.empty_like(y1)
+    scratch = torch.empty(lib.srf_pyramid_scratch_bytes(groups, Cc, L, D), dtype=torch.uint8, device=dev)
+    arr = lambda ts: (C.c_void_p * D)(*[t.data_ptr() for t in ts])
+    nrm = _lib.make_norm(in_sums, in_gamma, in_beta, in_prelu)
+    rc = lib.srf_pyramid_ragged(_lib.ptr(y1), _lib.ptr(merged), C.byref(nrm), arr(weights), arr(biases), arr(gammas),
+                                arr(betas), groups, Cc, L, D, _lib.ptr(scratch), _lib.ptr(out_sums), frs,
+                                _lib.current_stream(dev))
+    _lib.check(rc, "srf_pyramid_ragged")
+    return merged
+
+
+def pw_conv(x, packed, bias, Cout, frames, in_sums=None, in_gamma=None, in_beta=None, in_prelu=None, residual=None,
+            out_sums=None):
+    """srf_pw_conv_packed_ragged: x [Bt,Cin,L] (row b valid up to frames[b]), packed = ops.pack_pw_weight(W [Cout,Cin]) ->
+    [Bt,Cout,L].  With out_sums the output is exact zeros from frames[b] on; the residual form leaves it unspecified there."""
+    dev = _chk(x, packed, bias, in_sums, in_gamma, in_beta, in_prelu, residual, out_sums)
+    Bt, Cin, L = x.shape
+    frs, n = _table(frames, "frames")
+    if n != Bt:
+        raise _lib.SrfError("srf_pw_conv_packed_ragged: %d frames for a batch of %d" % (n, Bt))
+    y = torch.empty((Bt, Cout, L), dtype=torch.float32, device=dev)
+    nrm = None if in_sums is None and in_prelu is None else C.byref(_lib.make_norm(in_sums, in_gamma, in_beta, in_prelu))
+    rc = _lib.load().srf_pw_conv_packed_ragged(_lib.ptr(x), None, _lib.ptr(packed), _lib.ptr(bias), _lib.ptr(y), Bt, Cin, Cout, L,
+                                               nrm, _lib.ptr(residual), _lib.ptr(out_sums), 0, None, 0, frs,
+                                               _lib.current_stream(dev))
+    _lib.check(rc, "srf_pw_conv_packed_ragged")
+    return y
+
+
+def pw_conv_pair_supported(Cin1, Cmid, Cout2, L):
+    """Whether srf_pw_conv_pair_ragged serves these channel counts / this row stride (no GPU needed)."""
+    return bool(_lib.load().srf_pw_conv_pair_ragged_supported(Cin1, Cmid, Cout2, L))
+
+
+def pw_conv_pair(x, packed1, bias1, in_sums, in_gamma, in_beta, in_prelu, residual, packed2, bias2, Cmid, Cout2, frames,
+                 out_sums2=None):
+    """srf_pw_conv_pair_ragged: y = W1 f(x) + b1 (+ residual) (unspecified past frames[b]), y2 = W2 y + b2 (exact zeros past
+    frames[b], statistics over the example's own columns).  Returns (y, y2)."""
+    dev = _chk(x, packed1, bias1, in_sums, in_gamma, in_beta, in_prelu, residual, packed2, bias2, out_sums2)
+    Bt, Cin1, L = x.shape
+    frs, n = _table(frames, "frames")
+    if n != Bt:
+        raise _lib.SrfError("srf_pw_conv_pair_ragged: %d frames for a batch of %d" % (n, Bt))
+    y = torch.empty((Bt, Cmid, L), dtype=torch.float32, device=dev)
+    y2 = torch.empty((Bt, Cout2, L), dtype=torch.float32, device=dev)
+    nrm = C.byref(_lib.make_norm(in_sums, in_gamma, in_beta, in_prelu)) if in_sums is not None else None
+    rc = _lib.load().srf_pw_conv_pair_ragged(_lib.ptr(x), _lib.ptr(packed1), _lib.ptr(bias1), _lib.ptr(y), nrm,
+                                             _lib.ptr(residual), _lib.ptr(packed2), _lib.ptr(bias2), _lib.ptr(y2),
+                                             _lib.ptr(out_sums2), Bt, Cin1, Cmid, Cout2, L, frs, _lib.current_stream(dev))
+    _lib.check(rc, "srf_pw_conv_pair_ragged")
+    return y, y2
