@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <atomic>
 #include <initializer_list>
 #define SRF_DIAGNOSTICS 1   // the library itself sees (and defines) the diagnostics switches
 #include "../../include/sudormrf_hip.h"
@@ -30,7 +31,25 @@ int srf_device_cus();                           // multiProcessorCount of the cu
 // Slot `slot` (0 .. SRF_OCC_SLOTS-1) of the current device's occupancy cache: returns the cached value or, when empty,
 // evaluates `compute` once (under the lock) and stores it.
 #define SRF_OCC_SLOTS 16
+enum SrfOccSlot { SRF_OCC_PYR_PASS1_CH16 = 0, SRF_OCC_PYR_PASS1_CH32 = 1 };   // (srf_pyramid_reg.hip: co-resident wavefronts of pass 1)
 long srf_device_cached(int slot, long (*compute)(void*), void* arg);
+
+// Launch of a kernel that wants more dynamic LDS than the 64 KB a kernel gets unasked: raises Kernel's MaxDynamicSharedMemorySize
+// to max_lds (the most any launch of it asks for) once per (device, instantiation), then launches it with `lds` bytes -- so the
+// instantiation that runs is the one that was opted in.  One flag per device and no lock: the library is called from one thread
+// per GPU, and setting the attribute twice is harmless.  false = the attribute was refused, nothing launched.
+template <auto Kernel, typename... Args>
+static inline bool srf_launch_lds(int max_lds, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  static std::atomic<bool> raised[SRF_MAX_DEVICES];
+  const int dev = srf_current_device();
+  const bool known = dev >= 0 && dev < SRF_MAX_DEVICES;
+  if (!known || !raised[dev].load(std::memory_order_acquire)) {
+    if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess) return false;
+    if (known) raised[dev].store(true, std::memory_order_release);
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+  return true;
+}
 
 #define SRF_CHECK_ARG(cond, ...)          \
   do {                                    \

@@ -1,8 +1,29 @@
-// Shared pieces of the pointwise-conv GEMM kernels (srf_pwconv.hip, srf_pwconv_bf16x3.hip).
+// Shared pieces of the pointwise-conv GEMM kernels (srf_pwconv*.hip).
 #pragma once
 #include "srf_internal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// 8 fp32 values -> their bf16 hi | lo parts (hi = bf16(v), lo = bf16(v - hi): 16 mantissa bits, three MFMAs per product block)
+__device__ __forceinline__ void srf_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const __bf16 h = (__bf16)v[j];
+    hi[j] = h;
+    lo[j] = (__bf16)(v[j] - (float)h);
+  }
+}
+
+// Byte offset of 16-byte chunk c (0..3) of row r in a [rows][32] bf16 image with 64-byte rows, XOR-swizzled.  The packed weight
+// images (srf_x3w_pack_kernel) are written with it and read back by the x3w / x3p / x3f kernels: ONE function, or the format breaks.
+__host__ __device__ __forceinline__ int srf_swz(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
+
+#define SRF_LDS(p) ((__attribute__((address_space(3))) void*)(p))   // a pointer into LDS as the DMA builtins want it
+
+// 0 = identity, 1 = GlobLN, 2 = GlobLN + PReLU, 3 = PReLU only: the PRO template argument of every GEMM kernel
+static inline int srf_pw_pro(const SrfNormDev& n) { return n.sums ? (n.prelu ? 2 : 1) : (n.prelu ? 3 : 0); }
 
 struct PwArgs {
   const float* x;
@@ -60,6 +81,12 @@ int srf_pw_x3f_launch(const PwPairArgs& a, int pro, hipStream_t st, bool f16 = f
 int srf_pw_x3w_fused_tail_launch(const PwArgs& a, const char* wpack, const char* wdpack, float* zpart, int M, hipStream_t st);
 int srf_pw_x3w3_launch(const PwArgs& a, const char* wpack3, int pro, hipStream_t st);   // three bf16 parts (training forward)
 int srf_pw_x3w4_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);    // two fp16 parts (training forward)
+
+// Launch macros of the kernels that have a ragged form (template arguments ..., SrfFrames): SRF_FRAMES_ARG(the optional template
+// arguments) is `, *frames` behind the kernel arguments when SrfFrames is the last of them, nothing otherwise
+#define SRF_FRAMES_ARG(opt, ...) SRF_FRAMES_ARG_##__VA_ARGS__
+#define SRF_FRAMES_ARG_
+#define SRF_FRAMES_ARG_SrfFrames , *frames
 
 
 // XCD-aware tile numbering: hardware places block id on XCD id%8; give each XCD a contiguous run of

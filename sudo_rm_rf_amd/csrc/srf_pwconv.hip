@@ -206,6 +206,63 @@ __global__ __launch_bounds__(256) void srf_pw_mfma_kernel(PwArgs a, int nMt, int
   if (a.out_sums) srf_block_stats_atomic<4>((double)s, (double)q, srf_stat_slot(a.out_sums, b, v), red);
 }
 
+// ---- the argument blocks, filled in one place each ------------------------------------------------------------------------
+static PwArgs pw_args(const float* x, const float* w, const float* bias, float* y, const float* residual, double* out_sums,
+                      const float* mul, int mul_channels, int epi_mask, const SrfNormDev& nrm, int Bt, int Cin, int Cout, int L) {
+  PwArgs a;
+  a.x = x;
+  a.w = w;
+  a.bias = bias;
+  a.y = y;
+  a.residual = residual;
+  a.out_sums = out_sums;
+  a.mul = mul;
+  a.nrm = nrm;
+  a.inv_count = 1.0 / ((double)Cin * (double)L);
+  a.Cin = Cin;
+  a.Cout = Cout;
+  a.L = L;
+  a.Bt = Bt;
+  a.mul_channels = mul_channels;
+  a.epi_mask = epi_mask;
+  return a;
+}
+// w1_packed / w2_packed: packed buffers [x3w image | paired-block image]; the pair kernel streams the second.  (nLt, total: its launcher's)
+static PwPairArgs pw_pair_args(const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
+                               const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2, int Bt,
+                               int Cin1, int Cmid, int Cout2, int L) {
+  PwPairArgs a;
+  a.x = x;
+  a.residual = residual;
+  a.bias1 = bias1;
+  a.y = y;
+  a.nrm = srf_norm_dev(in_norm);
+  a.inv_count = 1.0 / ((double)Cin1 * (double)L);
+  a.wpack1 = reinterpret_cast<const char*>(w1_packed) + srf_x3w_packed_bytes(Cmid, Cin1);
+  a.wpack2 = reinterpret_cast<const char*>(w2_packed) + srf_x3w_packed_bytes(Cout2, Cmid);
+  a.bias2 = bias2;
+  a.y2 = y2;
+  a.out_sums2 = out_sums2;
+  a.K1 = Cin1;
+  a.C2 = Cout2;
+  a.L = L;
+  a.Bt = Bt;
+  a.nLt = 0;
+  a.total = 0;
+  return a;
+}
+
+// ---- the 256 x 128 dispatch test in its three parts; every form of it below is written through them --------------------------
+// shape: what the kernel takes -- Cin % 64 == 0, Cin >= 128, L % 4 == 0, Cout >= 192 (so the MFMA kernels' own Cin % PW_BK,
+// L % 4, Cin >= 32, Cout >= 32 are implied) -- and a batch its LDS statistics table holds
+static bool pw256_shape(int Bt, int Cin, int Cout, int L, int pro) {
+  return srf_x3w_shape_supported(Cin, Cout, L) && srf_x3w_supported(Bt, pro);
+}
+// reach: the activations of Bt examples lie within the kernel's 32-bit buffer offsets
+static bool pw256_reach(long Bt, int Cin, int L) { return Bt * Cin * L * 4 < (1L << 31); }
+// fills the chip: no fewer 256 x 128 tiles than CUs (fewer: the 128 x 128 / 64 x 64 kernels make more blocks and do better)
+static bool pw256_fills_chip(long Bt, int Cout, int L) { return Bt * ((Cout + 255) / 256) * ((L + 127) / 128) >= srf_device_cus(); }
+
 // Round 4: the paired-block form of the 256 x 128 kernel (srf_pwconv_x3p.hip: two co-resident blocks per CU; bit-identical
 // outputs).  In isolation it ties with the one-block kernel on proj_1x1 / bottleneck and loses on res_conv (127 vs 113 us) and
 // in the single-stream training step (+3.5 % / +4.5 % at cfg 2 / cfg 4); INSIDE srf_forward, whose caller runs two sub-batches
@@ -228,16 +285,16 @@ static int srf_pw_256_launch(const PwArgs& a, const char* wpack, int pro, hipStr
 // srf_pack_pw_weights; the kernel streams their paired-block images.
 // Whether the fused pair serves (Bt, Cin1 -> 256 -> Cout2, L): the kernel's shape limits, the default kernel mode, and a launch
 // that fills the chip (fewer 128-column tiles than CUs: the separate launches' small-launch kernels do better).
-static bool srf_pw_pair_shape_ok(int Bt, int Cin1, int Cmid, int Cout2, int L) {      // (whatever the kernel mode)
+static bool srf_pw_pair_kernel_takes(int Bt, int Cin1, int Cmid, int Cout2, int L) {      // (whatever the kernel mode)
   if (srf_dbg(SRF_DBG_NO_PAIRS | SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS)) return false;
   if (Cmid != 256 || !srf_x3f_supported(Bt, Cin1, Cout2, L)) return false;
-  if (!srf_x3w_shape_supported(Cin1, Cmid, L) || !srf_x3w_shape_supported(Cmid, Cout2, L)) return false;
-  return (long)Bt * ((L + 127) / 128) >= srf_device_cus();
+  return srf_x3w_shape_supported(Cin1, Cmid, L) && srf_x3w_shape_supported(Cmid, Cout2, L);
+}
+static bool srf_pw_pair_shape_ok(int Bt, int Cin1, int Cmid, int Cout2, int L) {      // (Cmid = 256: one m-tile, Bt * ceil(L / 128) tiles)
+  return srf_pw_pair_kernel_takes(Bt, Cin1, Cmid, Cout2, L) && pw256_fills_chip(Bt, Cmid, L);
 }
 extern "C" int srf_pw_conv_pair_ragged_supported(int Cin1, int Cmid, int Cout2, int L) {
-  if (srf_kernel_mode() != 0 || srf_dbg(SRF_DBG_NO_PAIRS | SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS)) return 0;
-  if (Cmid != 256 || !srf_x3f_supported(1, Cin1, Cout2, L)) return 0;
-  return srf_x3w_shape_supported(Cin1, Cmid, L) && srf_x3w_shape_supported(Cmid, Cout2, L) ? 1 : 0;
+  return srf_kernel_mode() == 0 && srf_pw_pair_kernel_takes(1, Cin1, Cmid, Cout2, L) ? 1 : 0;
 }
 extern "C" int srf_pw_conv_pair_supported(int Bt, int Cin1, int Cmid, int Cout2, int L) {
   return srf_kernel_mode() == 0 && srf_pw_pair_shape_ok(Bt, Cin1, Cmid, Cout2, L) ? 1 : 0;
@@ -278,35 +335,20 @@ static int pw_conv_pair_run(const float* x, const void* w1_packed, const float* 
                 "srf_pw_conv_pair: unsupported shape / mode (Bt=%d %d->%d->%d L=%d)", Bt, Cin1, Cmid, Cout2, L);
   SRF_CHECK_ALIGNED16("srf_pw_conv_pair", {"in_norm.sums", in_norm ? in_norm->sums : nullptr}, {"x", x}, {"y", y}, {"y2", y2}, {"w1_packed", w1_packed}, {"w2_packed", w2_packed},
                       {"residual", residual});
-  PwPairArgs a;
-  a.x = x;
-  a.residual = residual;
-  a.bias1 = bias1;
-  a.y = y;
-  a.nrm = srf_norm_dev(in_norm);
-  a.inv_count = 1.0 / ((double)Cin1 * (double)L);
-  a.wpack1 = reinterpret_cast<const char*>(w1_packed) + srf_x3w_packed_bytes(Cmid, Cin1);
-  a.wpack2 = reinterpret_cast<const char*>(w2_packed) + srf_x3w_packed_bytes(Cout2, Cmid);
-  a.bias2 = bias2;
-  a.y2 = y2;
-  a.out_sums2 = out_sums2;
-  a.K1 = Cin1;
-  a.C2 = Cout2;
-  a.L = L;
-  a.Bt = Bt;
-  a.nLt = 0;
-  a.total = 0;
-  return srf_pw_x3f_launch(a, !in_norm ? 0 : (a.nrm.prelu ? 2 : 1), (hipStream_t)stream, false, frames);
+  const PwPairArgs a = pw_pair_args(x, w1_packed, bias1, y, in_norm, residual, w2_packed, bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2, L);
+  return srf_pw_x3f_launch(a, srf_pw_pro(a.nrm), (hipStream_t)stream, false, frames);
 }
 
 // THE predicate of the 256 x 128 dispatch for a whole launch (srf_pw_conv_packed, srf_pw_conv_packed3 and srf_pw_packed_only all
 // use it -- ADVICE r3: the backward's "the fp32 weight is never read" shortcut was a hand-written copy of the dispatch test).
-static bool srf_pw_256_serves(const void* w_packed, const float* x, int Bt, int Cin, int Cout, int L, int pro) {
-  if (!w_packed || srf_kernel_mode() != 0 || srf_dbg(SRF_DBG_NO_GEMM_256)) return false;
-  if ((Cin % PW_BK) || (L % 4) || Cout < 32 || Cin < 32 || !srf_aligned16(x) || !srf_aligned16(w_packed)) return false;
-  if (!srf_x3w_shape_supported(Cin, Cout, L) || !srf_x3w_supported(Bt, pro)) return false;
-  if ((long)Bt * Cin * L * 4 >= (1L << 31)) return false;      // (beyond the 32-bit buffer range: the chunked form decides per chunk)
-  return (long)Bt * ((Cout + 255) / 256) * ((L + 127) / 128) >= srf_device_cus();
+// mode2_too: kernel mode 2 is served as well as 0 -- srf_pw_conv_packed3 alone, whose split GEMM IS the exact-fp32 class.
+static bool srf_pw_256_serves(const void* w_packed, const float* x, int Bt, int Cin, int Cout, int L, int pro, bool mode2_too = false) {
+  const int mode = srf_kernel_mode();
+  if (!w_packed || !(mode == 0 || (mode2_too && mode == 2)) || srf_dbg(SRF_DBG_NO_GEMM_256)) return false;
+  if (!srf_aligned16(x) || !srf_aligned16(w_packed)) return false;
+  if (!pw256_shape(Bt, Cin, Cout, L, pro)) return false;
+  if (!pw256_reach(Bt, Cin, L)) return false;      // (beyond the 32-bit buffer range: the chunked form decides per chunk)
+  return pw256_fills_chip(Bt, Cout, L);
 }
 
 // ---- K5 (library-internal; srf_forward's tail): mask GEMM + decoder contraction in one launch (srf_pwconv_x3w.hip, EPI 4)
@@ -315,9 +357,8 @@ static bool srf_pw_256_serves(const void* w_packed, const float* x, int Bt, int 
 // Debug flag 32768 = without (the masked tensor is then materialised: srf_debug_fetch(2), A/B).
 bool srf_mask_decode_supported(int Bt, int Cin, int Cout, int L, int M) {
   if (srf_kernel_mode() != 0 || srf_dbg(SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS | SRF_DBG_NO_FUSED_TAIL)) return false;
-  if (M <= 0 || M > 64 || Cout % 8 || Cin % PW_BK || L % 4 || !srf_x3w_shape_supported(Cin, Cout, L) || !srf_x3w_supported(Bt, 3)) return false;
-  if ((long)Bt * Cin * L * 4 >= (1L << 31)) return false;
-  return (long)Bt * ((Cout + 255) / 256) * ((L + 127) / 128) >= srf_device_cus();
+  if (M <= 0 || M > 64 || Cout % 8) return false;      // (this form's own limits)
+  return pw256_shape(Bt, Cin, Cout, L, 3) && pw256_reach(Bt, Cin, L) && pw256_fills_chip(Bt, Cout, L);
 }
 size_t srf_mask_decode_pack_bytes(int Cout) { return srf_x3w_dec_pack_bytes(Cout); }
 int srf_mask_decode_pack(const float* wd, void* dst, int Ci, int M, hipStream_t st) {
@@ -331,23 +372,9 @@ int srf_mask_decode(const float* x, const float* w, const void* w_packed, const 
   SRF_CHECK_ARG(srf_mask_decode_supported(Bt, Cin, Cout, L, M) && mul_channels > 0 && mul_channels % 8 == 0,
                 "srf_mask_decode: unsupported shape");
   SRF_CHECK_ARG(srf_aligned16(x) && srf_aligned16(w_packed) && srf_aligned16(wd_packed), "srf_mask_decode: unaligned operand");
-  PwArgs a;
-  a.x = x;
-  a.w = w;
-  a.bias = bias;
-  a.y = zpart;          // (never written by this form)
-  a.residual = nullptr;
-  a.out_sums = nullptr;
-  a.mul = mul;
-  srf_norm nm{nullptr, nullptr, nullptr, prelu};
-  a.nrm = srf_norm_dev(&nm);
-  a.inv_count = 1.0 / ((double)Cin * (double)L);
-  a.Cin = Cin;
-  a.Cout = Cout;
-  a.L = L;
-  a.Bt = Bt;
-  a.mul_channels = mul_channels;
-  a.epi_mask = 1;
+  const srf_norm nm{nullptr, nullptr, nullptr, prelu};
+  const PwArgs a = pw_args(x, w, bias, /*y: never written by this form*/ zpart, nullptr, nullptr, mul, mul_channels, 1, srf_norm_dev(&nm), Bt,
+                           Cin, Cout, L);
   return srf_pw_x3w_fused_tail_launch(a, reinterpret_cast<const char*>(w_packed), reinterpret_cast<const char*>(wd_packed), zpart,
                                       M, st);
 }
@@ -433,34 +460,15 @@ extern "C" int srf_pw_conv_packed3(const float* x, const float* w, const void* w
   SRF_CHECK_ARG(x && w && bias && y, "srf_pw_conv: null pointer");
   SRF_CHECK_ARG(Bt > 0 && Cin > 0 && Cout > 0 && L > 0, "srf_pw_conv: bad sizes");
   const SrfNormDev nd = srf_norm_dev(in_norm);
-  const int pro = nd.sums ? (nd.prelu ? 2 : 1) : (nd.prelu ? 3 : 0);
+  const int pro = srf_pw_pro(nd);
   const bool form_ok = (pro == 2) == (residual != nullptr);      // the built forms: res_conv has the residual, the others none
   // (kernel mode 2 -- the exact-fp32 MFMA kernels -- still takes this three-part split GEMM: it IS the exact-fp32 class)
-  const bool ok = form_ok && srf_kernel_mode() != 1 && srf_aligned16(y) && (!residual || srf_aligned16(residual)) &&
-                  (srf_kernel_mode() == 0 ? srf_pw_256_serves(w_packed3, x, Bt, Cin, Cout, L, pro)
-                                          : (w_packed3 && srf_x3w_shape_supported(Cin, Cout, L) && srf_x3w_supported(Bt, pro) &&
-                                             srf_aligned16(x) && srf_aligned16(w_packed3) && (long)Bt * Cin * L * 4 < (1L << 31) &&
-                                             !srf_dbg(SRF_DBG_NO_GEMM_256) &&
-                                             (long)Bt * ((Cout + 255) / 256) * ((L + 127) / 128) >= srf_device_cus()));
+  const bool ok = form_ok && srf_aligned16(y) && (!residual || srf_aligned16(residual)) &&
+                  srf_pw_256_serves(w_packed3, x, Bt, Cin, Cout, L, pro, /*mode2_too=*/true);
   if (!ok) return srf_pw_conv(x, w, bias, y, Bt, Cin, Cout, L, in_norm, residual, out_sums, 0, nullptr, 0, stream);
   if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_pw_conv: norm without gamma/beta");
   SRF_CHECK_ALIGNED16("srf_pw_conv", {"in_norm.sums", nd.sums});
-  PwArgs a;
-  a.x = x;
-  a.w = w;
-  a.bias = bias;
-  a.y = y;
-  a.residual = residual;
-  a.out_sums = out_sums;
-  a.mul = nullptr;
-  a.nrm = nd;
-  a.inv_count = 1.0 / ((double)Cin * (double)L);
-  a.Cin = Cin;
-  a.Cout = Cout;
-  a.L = L;
-  a.Bt = Bt;
-  a.mul_channels = 1;
-  a.epi_mask = 0;
+  const PwArgs a = pw_args(x, w, bias, y, residual, out_sums, nullptr, 1, 0, nd, Bt, Cin, Cout, L);
   const bool f16 = srf_train_f16_split();
   {
     std::lock_guard<std::mutex> lk(g_pk3_mu);
@@ -499,25 +507,8 @@ extern "C" int srf_pw_conv_pair_packed3(const float* x, const void* w1_packed3, 
                       {"w2_packed3", w2_packed3}, {"residual", residual});
   SRF_CHECK_ARG(srf_pk3_is_f16(w1_packed3) && srf_pk3_is_f16(w2_packed3),
                 "srf_pw_conv_pair_packed3: both weight images must have been packed as two fp16 parts by srf_pack3_pw_weights");
-  PwPairArgs a;
-  a.x = x;
-  a.residual = residual;
-  a.bias1 = bias1;
-  a.y = y;
-  a.nrm = srf_norm_dev(in_norm);
-  a.inv_count = 1.0 / ((double)Cin1 * (double)L);
-  a.wpack1 = reinterpret_cast<const char*>(w1_packed3) + srf_x3w_packed_bytes(Cmid, Cin1);
-  a.wpack2 = reinterpret_cast<const char*>(w2_packed3) + srf_x3w_packed_bytes(Cout2, Cmid);
-  a.bias2 = bias2;
-  a.y2 = y2;
-  a.out_sums2 = out_sums2;
-  a.K1 = Cin1;
-  a.C2 = Cout2;
-  a.L = L;
-  a.Bt = Bt;
-  a.nLt = 0;
-  a.total = 0;
-  return srf_pw_x3f_launch(a, a.nrm.prelu ? 2 : 1, (hipStream_t)stream, true);
+  const PwPairArgs a = pw_pair_args(x, w1_packed3, bias1, y, in_norm, residual, w2_packed3, bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2, L);
+  return srf_pw_x3f_launch(a, srf_pw_pro(a.nrm), (hipStream_t)stream, true);
 }
 
 // ---- GroupComm (library-internal; srf_forward): proj_1x1 with the TAC's "x + GlobLN(q)" folded into its operand load ----
@@ -534,22 +525,7 @@ int srf_pw_conv_preadd(const float* x, const float* q, const srf_norm* qnorm, fl
   SRF_CHECK_ARG(x && q && qnorm && qnorm->sums && qnorm->gamma && qnorm->beta && u && w && bias && y, "srf_pw_conv_preadd: null pointer");
   const void* ptrs[4] = {x, q, u, y};
   SRF_CHECK_ARG(srf_pw_conv_preadd_supported(Cin, Cout, L, ptrs, 4), "srf_pw_conv_preadd: unsupported shape");
-  PwArgs a;
-  a.x = x;
-  a.w = w;
-  a.bias = bias;
-  a.y = y;
-  a.residual = nullptr;
-  a.out_sums = out_sums;
-  a.mul = nullptr;
-  a.nrm = srf_norm_dev(nullptr);
-  a.inv_count = 1.0 / ((double)Cin * (double)L);
-  a.Cin = Cin;
-  a.Cout = Cout;
-  a.L = L;
-  a.Bt = Bt;
-  a.mul_channels = 1;
-  a.epi_mask = 0;
+  PwArgs a = pw_args(x, w, bias, y, nullptr, out_sums, nullptr, 1, 0, srf_norm_dev(nullptr), Bt, Cin, Cout, L);
   a.pre_q = q;
   a.pre_u = u;
   a.pre_nrm = srf_norm_dev(qnorm);
@@ -628,29 +604,15 @@ extern "C" int srf_pw_conv_packed_ragged(const float* x, const float* w, const v
   SRF_CHECK_ARG(x && w_packed && bias && y, "srf_pw_conv_packed_ragged: null pointer (the packed weight image is required)");
   SRF_CHECK_ARG(Cin > 0 && Cout > 0, "srf_pw_conv_packed_ragged: bad sizes");
   SRF_CHECK_ARG(!epilogue_mask, "srf_pw_conv_packed_ragged: the mask epilogue has no ragged form");
-  PwArgs a;
-  a.x = x;
-  a.w = nullptr;
-  a.bias = bias;
-  a.y = y;
-  a.residual = residual;
-  a.out_sums = out_sums;
-  a.mul = nullptr;
-  a.nrm = srf_norm_dev(in_norm);
-  a.inv_count = 1.0 / ((double)Cin * (double)L);
-  a.Cin = Cin;
-  a.Cout = Cout;
-  a.L = L;
-  a.Bt = Bt;
-  a.mul_channels = 1;
-  a.epi_mask = 0;
-  const int pro = a.nrm.sums ? (a.nrm.prelu ? 2 : 1) : (a.nrm.prelu ? 3 : 0);
+  const PwArgs a = pw_args(x, nullptr, bias, y, residual, out_sums, nullptr, 1, 0, srf_norm_dev(in_norm), Bt, Cin, Cout, L);
+  const int pro = srf_pw_pro(a.nrm);
   SRF_CHECK_ARG(pro != 3 && (pro == 2) == (residual != nullptr) && !(pro == 2 && out_sums),
                 "srf_pw_conv_packed_ragged: forms built: no prologue / GlobLN without residual, GlobLN + PReLU with residual and "
                 "without statistics");
   if (a.nrm.sums) SRF_CHECK_ARG(a.nrm.gamma && a.nrm.beta, "srf_pw_conv_packed_ragged: norm without gamma/beta");
+  // (shape and reach, no "fills the chip": see above; the statistics table's limit on Bt is the launch's own check and message)
   SRF_CHECK_ARG(srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS) &&
-                    srf_x3w_shape_supported(Cin, Cout, L) && (long)Bt * Cin * L * 4 < (1L << 31),
+                    srf_x3w_shape_supported(Cin, Cout, L) && pw256_reach(Bt, Cin, L),
                 "srf_pw_conv_packed_ragged: the 256 x 128 kernel does not take %d -> %d channels, L=%d in kernel mode %d", Cin, Cout, L,
                 srf_kernel_mode());
   SRF_CHECK_ALIGNED16("srf_pw_conv_packed_ragged", {"in_norm.sums", a.nrm.sums}, {"x", x}, {"y", y}, {"residual", residual},
@@ -665,22 +627,8 @@ extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_
   SRF_CHECK_ARG(x && w && bias && y, "srf_pw_conv: null pointer");
   SRF_CHECK_ARG(Bt > 0 && Cin > 0 && Cout > 0 && L > 0, "srf_pw_conv: bad sizes");
   SRF_CHECK_ARG(!epilogue_mask || (mul && mul_channels > 0), "srf_pw_conv: mask epilogue needs mul");
-  PwArgs a;
-  a.x = x;
-  a.w = w;
-  a.bias = bias;
-  a.y = y;
-  a.residual = residual;
-  a.out_sums = out_sums;
-  a.mul = mul;
-  a.nrm = srf_norm_dev(in_norm);
-  a.inv_count = 1.0 / ((double)Cin * (double)L);
-  a.Cin = Cin;
-  a.Cout = Cout;
-  a.L = L;
-  a.Bt = Bt;
-  a.mul_channels = mul_channels > 0 ? mul_channels : 1;
-  a.epi_mask = epilogue_mask ? 1 : 0;
+  const PwArgs a = pw_args(x, w, bias, y, residual, out_sums, mul, mul_channels > 0 ? mul_channels : 1, epilogue_mask ? 1 : 0,
+                           srf_norm_dev(in_norm), Bt, Cin, Cout, L);
   if (a.nrm.sums) SRF_CHECK_ARG(a.nrm.gamma && a.nrm.beta, "srf_pw_conv: norm without gamma/beta");
   SRF_CHECK_ALIGNED16("srf_pw_conv", {"in_norm.sums", a.nrm.sums});     // (every kernel reads the statistics as pairs of doubles)
   hipStream_t st = (hipStream_t)stream;
@@ -691,24 +639,26 @@ extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_
   const bool io16 = srf_aligned16(y) && (!residual || srf_aligned16(residual)) && (!(a.epi_mask & 1) || srf_aligned16(mul));
   const bool mfma_ok = mode != 1 && (Cin % PW_BK == 0) && (L % 4 == 0) && Cout >= 32 && Cin >= 32 &&
                        srf_aligned16(x) && srf_aligned16(w) && io16;
-  const int pro_sel = a.nrm.sums ? (a.nrm.prelu ? 2 : 1) : (a.nrm.prelu ? 3 : 0);
+  const int pro = srf_pw_pro(a.nrm);
   // GroupComm's per-group convs (<= 32 -> <= 64 channels): register-resident streaming kernel
   if (mode != 1 && !(a.epi_mask & 1) && srf_pw_small_supported(Cin, Cout, L) && srf_aligned16(x) &&
       srf_aligned16(y) && (!residual || srf_aligned16(residual)))
     return srf_pw_small_launch(a, st);
   // 256 x 128 tiles with pre-split weights: whenever the packed image is there and the launch fills the chip (fewer tiles
   // than CUs: the 128 x 128 kernels below make twice as many).  (That kernel never reads the fp32 weights.)
-  if (io16 && srf_pw_256_serves(w_packed, x, Bt, Cin, Cout, L, pro_sel))
-    return srf_pw_256_launch(a, reinterpret_cast<const char*>(w_packed), pro_sel, st);
+  if (io16 && srf_pw_256_serves(w_packed, x, Bt, Cin, Cout, L, pro))
+    return srf_pw_256_launch(a, reinterpret_cast<const char*>(w_packed), pro, st);
   // An activation tensor beyond the 2 GB reach of the kernel's 32-bit buffer offsets (cfg 5's bottleneck: 16 x 4096 x 12800
   // floats = 3.4 GB) goes out as several launches over runs of whole examples: examples are independent, every per-example
   // pointer (statistics slots included) just moves along.
-  if (mfma_ok && mode == 0 && w_packed && srf_x3w_shape_supported(Cin, Cout, L) && srf_x3w_supported(Bt, pro_sel) && srf_aligned16(w_packed) &&
-      (long)Bt * Cin * L * 4 >= (1L << 31) && (long)Cin * L * 4 < (1L << 31) && !srf_dbg(SRF_DBG_NO_GEMM_256)) {
+  // The 256 x 128 test again, with "reach" failing for the batch and holding per example and "fills the chip" asked of the LAST
+  // run.  (mfma_ok: its shape tests are implied; its alignment tests -- the fp32 weight's among them -- are this branch's own.)
+  if (mfma_ok && mode == 0 && w_packed && srf_aligned16(w_packed) && !srf_dbg(SRF_DBG_NO_GEMM_256) && pw256_shape(Bt, Cin, Cout, L, pro) &&
+      !pw256_reach(Bt, Cin, L) && pw256_reach(1, Cin, L)) {
     const int cap = (int)(((1L << 31) - 1) / ((long)Cin * L * 4));   // examples one launch can address
     const int nch = (Bt + cap - 1) / cap, per = (Bt + nch - 1) / nch;  // balanced runs of whole examples
     const int last = Bt - (nch - 1) * per;
-    if ((long)last * ((Cout + 255) / 256) * ((L + 127) / 128) >= srf_device_cus()) {
+    if (pw256_fills_chip(last, Cout, L)) {
       for (int b0 = 0; b0 < Bt; b0 += per) {
         PwArgs c = a;
         c.Bt = Bt - b0 < per ? Bt - b0 : per;
@@ -720,7 +670,7 @@ extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_
         if (a.nrm.sums) c.nrm.sums = a.nrm.sums + (size_t)b0 * SRF_STAT_BUCKETS * 2;
         const bool more = b0 + per < Bt;    // (one profiler interval for the whole operation: only the last launch is marked)
         if (more) srf_prof_hold(+1);
-        const int rc = srf_pw_256_launch(c, reinterpret_cast<const char*>(w_packed), pro_sel, st);
+        const int rc = srf_pw_256_launch(c, reinterpret_cast<const char*>(w_packed), pro, st);
         if (more) srf_prof_hold(-1);
         if (rc) return rc;
       }
@@ -728,13 +678,12 @@ extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_
     }
   }
   // launches that would leave CUs idle on 128 x 128 tiles (a batch-1 forward): 64 x 64 tiles, four times the blocks
-  if (mfma_ok && mode == 0 && (Cin % 64 == 0) && srf_aligned16(y) && srf_pw_w4_wanted(a)) return srf_pw_w4_launch(a, pro_sel, st);
-  if (mfma_ok && mode == 0 && (Cin % 64 == 0)) return srf_pw_bf16x3_launch(a, pro_sel, st);
+  if (mfma_ok && mode == 0 && (Cin % 64 == 0) && srf_aligned16(y) && srf_pw_w4_wanted(a)) return srf_pw_w4_launch(a, pro, st);
+  if (mfma_ok && mode == 0 && (Cin % 64 == 0)) return srf_pw_bf16x3_launch(a, pro, st);
   if (mfma_ok) {
     const int nMt = (Cout + PW_BM - 1) / PW_BM, nLt = (L + PW_BN - 1) / PW_BN;
     const long total = (long)Bt * nMt * nLt;
-    SRF_CHECK_ARG(total < (1L << 31), "srf_pw_conv: too many tiles");
-    const int pro = a.nrm.sums ? (a.nrm.prelu ? 2 : 1) : (a.nrm.prelu ? 3 : 0);
+    SRF_CHECK_ARG(total <= 0x7fffffffL, "srf_pw_conv: too many tiles");
     dim3 grid((unsigned)total), block(256);
     switch (pro) {
       case 0: hipLaunchKernelGGL(srf_pw_mfma_kernel<0>, grid, block, 0, st, a, nMt, nLt, (int)total); break;

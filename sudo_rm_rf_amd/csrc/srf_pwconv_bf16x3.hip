@@ -23,21 +23,10 @@
 // (800 tiles) and the backward's small data-gradient GEMMs.  Batch 1 goes to the 64 x 64 tiles of srf_pwconv_w4.hip.
 #include "srf_pw.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int X3_BM = 128, X3_BN = 128, X3_BK = 32;
 constexpr int X3_PITCH = 80;                    // bytes per LDS row (32 bf16 = 64 B + 16 B pad)
 constexpr int X3_IMG = X3_BM * X3_PITCH;        // one [128][32] bf16 image
 constexpr int X3_STAGE = 4 * X3_IMG;            // A_hi, A_lo, B_hi, B_lo
-
-__device__ __forceinline__ void srf_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h = (__bf16)v[j];
-    hi[j] = h;
-    lo[j] = (__bf16)(v[j] - (float)h);
-  }
-}
 
 // PRO: 0 = identity, 1 = GlobLN, 2 = GlobLN + PReLU, 3 = PReLU only
 //

@@ -14,21 +14,10 @@
 // (reference sites: improved_sudormrf.py:256-259, :174, :196, :220, :268-269, :295-298)
 #include "srf_pw.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int W4_BM = 64, W4_BN = 64, W4_BK = 32;
 constexpr int W4_PITCH = 80;                    // bytes per LDS row (32 bf16 = 64 B + 16 B pad: conflict-free b128 fragment reads)
 constexpr int W4_IMG = W4_BM * W4_PITCH;        // one [64][32] bf16 image
 constexpr int W4_STAGE = 4 * W4_IMG;            // A_hi, A_lo, B_hi, B_lo = 20 KB
-
-__device__ __forceinline__ void w4_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h = (__bf16)v[j];
-    hi[j] = h;
-    lo[j] = (__bf16)(v[j] - (float)h);
-  }
-}
 
 // PRO: 0 = identity, 1 = GlobLN, 2 = GlobLN + PReLU, 3 = PReLU only
 template <int PRO>
@@ -79,7 +68,7 @@ __global__ __launch_bounds__(256, 4) void srf_pw_w4_kernel(PwArgs a, int nMt, in
     char* base = smem + stage * W4_STAGE;
     const float va[8] = {r.a[0].x, r.a[0].y, r.a[0].z, r.a[0].w, r.a[1].x, r.a[1].y, r.a[1].z, r.a[1].w};
     bf16x8 hi, lo;
-    w4_split8(va, hi, lo);
+    srf_split8(va, hi, lo);
     float vb[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -93,7 +82,7 @@ __global__ __launch_bounds__(256, 4) void srf_pw_w4_kernel(PwArgs a, int nMt, in
       vb[j] = x0;
     }
     bf16x8 hib, lob;
-    w4_split8(vb, hib, lob);
+    srf_split8(vb, hib, lob);
     *reinterpret_cast<bf16x8*>(base + 0 * W4_IMG + a_lds) = hi;
     *reinterpret_cast<bf16x8*>(base + 1 * W4_IMG + a_lds) = lo;
     *reinterpret_cast<bf16x8*>(base + 2 * W4_IMG + b_lds) = hib;

@@ -13,8 +13,6 @@
 
 #include "srf_pw.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int WG_BM = 128, WG_BN = 128, WG_BK = 32;
 constexpr int WG_PITCH = 80;                  // bytes per LDS row (32 bf16 + 16 B pad): conflict-free b128 reads
 constexpr int WG_IMG = WG_BM * WG_PITCH;
@@ -32,15 +30,6 @@ struct WgArgs {
   int nMt, nNt;
   int xcd_map;         // block -> (tile, partial) mapping that puts ALL output tiles of a partial on one XCD (P % 8 == 0)
 };
-
-__device__ __forceinline__ void wg_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h = (__bf16)v[j];
-    hi[j] = h;
-    lo[j] = (__bf16)(v[j] - (float)h);
-  }
-}
 
 // PRO: 0 identity, 1 GlobLN, 2 GlobLN + PReLU, 3 PReLU
 // FULL (round 6): M and N multiples of 128 and every time chunk a whole number of 32-wide k-tiles (L % 32 == 0) -- no row / tail masks.
@@ -144,7 +133,7 @@ __global__ __launch_bounds__(512, 4) void srf_pw_wgrad_kernel(WgArgs a) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) bsum += vg[j];
       bf16x8 hi, lo;
-      wg_split8(vg, hi, lo);
+      srf_split8(vg, hi, lo);
       char* base = smem + stage * WG_STAGE + lds_off;
       *reinterpret_cast<bf16x8*>(base + 0 * WG_IMG) = hi;
       *reinterpret_cast<bf16x8*>(base + 1 * WG_IMG) = lo;
@@ -163,7 +152,7 @@ __global__ __launch_bounds__(512, 4) void srf_pw_wgrad_kernel(WgArgs a) {
         }
       }
       bf16x8 hi, lo;
-      wg_split8(vx, hi, lo);
+      srf_split8(vx, hi, lo);
       char* base = smem + stage * WG_STAGE + lds_off;
       *reinterpret_cast<bf16x8*>(base + 2 * WG_IMG) = hi;
       *reinterpret_cast<bf16x8*>(base + 3 * WG_IMG) = lo;
@@ -1014,7 +1003,7 @@ extern "C" int srf_pw_wgrad_ld(const float* g, const float* x, const srf_norm* i
   a.bias_part = dbias ? a.part + (size_t)a.P * Cout * Cin : nullptr;
   if (a.nrm.sums) SRF_CHECK_ARG(a.nrm.gamma && a.nrm.beta, "srf_pw_wgrad: norm without gamma/beta");
   hipStream_t st = (hipStream_t)stream;
-  const int pro = a.nrm.sums ? (a.nrm.prelu ? 2 : 1) : (a.nrm.prelu ? 3 : 0);
+  const int pro = srf_pw_pro(a.nrm);
   if (wg_small_ok(Cout, Cin, L) && srf_kernel_mode() != 1) {
     const int LC = wg_small_lc(Cout, Cin), npl = (L + LC - 1) / LC;
     a.P = wg_small_blocks(Bt, Cout, Cin, L);
@@ -1032,27 +1021,20 @@ extern "C" int srf_pw_wgrad_ld(const float* g, const float* x, const srf_norm* i
     wg_geometry_wide(wide, Cout, Cin, L, Bt, &a);
     a.bias_part = dbias ? a.part + (size_t)a.P * Cout * Cin : nullptr;
     constexpr int lds = 2 * 2 * (256 + 128) * WG_PITCH;
-    const long ok = srf_device_cached(8, [](void*) -> long {
-      bool good = true;
-      const void* fns[] = {(const void*)&srf_pw_wgrad_wide_kernel<0, 256, 128>, (const void*)&srf_pw_wgrad_wide_kernel<1, 256, 128>,
-                           (const void*)&srf_pw_wgrad_wide_kernel<2, 256, 128>, (const void*)&srf_pw_wgrad_wide_kernel<3, 256, 128>,
-                           (const void*)&srf_pw_wgrad_wide_kernel<0, 128, 256>, (const void*)&srf_pw_wgrad_wide_kernel<1, 128, 256>,
-                           (const void*)&srf_pw_wgrad_wide_kernel<2, 128, 256>, (const void*)&srf_pw_wgrad_wide_kernel<3, 128, 256>};
-      for (const void* f : fns) good &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-      return good ? 1 : 0;
-    }, nullptr);
-    SRF_CHECK_ARG(ok == 1, "srf_pw_wgrad: cannot reserve %d bytes of LDS", lds);
     dim3 grid((unsigned)(a.nMt * a.nNt * a.P)), block(512);
-#define WG_WIDE(P_) \
-  if (wide == 1) hipLaunchKernelGGL((srf_pw_wgrad_wide_kernel<P_, 256, 128>), grid, block, lds, st, a); \
-  else hipLaunchKernelGGL((srf_pw_wgrad_wide_kernel<P_, 128, 256>), grid, block, lds, st, a)
-    switch (pro) {
-      case 0: WG_WIDE(0); break;
-      case 1: WG_WIDE(1); break;
-      case 2: WG_WIDE(2); break;
-      default: WG_WIDE(3); break;
-    }
+#define WG_WIDE_(P_, BM_, BN_) \
+  SRF_CHECK_ARG((srf_launch_lds<srf_pw_wgrad_wide_kernel<P_, BM_, BN_>>(lds, grid, block, lds, st, a)), "srf_pw_wgrad: cannot reserve %d bytes of LDS", lds)
+#define WG_WIDE(BM_, BN_)                      \
+  switch (pro) {                               \
+    case 0: WG_WIDE_(0, BM_, BN_); break;      \
+    case 1: WG_WIDE_(1, BM_, BN_); break;      \
+    case 2: WG_WIDE_(2, BM_, BN_); break;      \
+    default: WG_WIDE_(3, BM_, BN_); break;     \
+  }
+    if (wide == 1) WG_WIDE(256, 128)
+    else WG_WIDE(128, 256)
 #undef WG_WIDE
+#undef WG_WIDE_
     SRF_CHECK_LAUNCH("pw_wgrad", st);
   } else {
   dim3 grid((unsigned)(a.nMt * a.nNt * a.P)), block(512);

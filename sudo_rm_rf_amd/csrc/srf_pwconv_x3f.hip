@@ -34,8 +34,6 @@
 
 #include "srf_pw.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // F16 (the training forward, srf_pwconv_x3w.hip NP = 4): operands split into two FP16 parts (hi = fp16(x), lo = fp16(x - hi): 22
@@ -73,10 +71,6 @@ constexpr int F_OFF_GB = F_OFF_STRIP + 4 * F_STRIP_FLOATS * 4;
 constexpr int F_OFF_BIAS = F_OFF_GB + 2 * F_MAX_K1 * 4;
 constexpr int F_LDS_BYTES = F_OFF_BIAS + (F_BM + F_MAX_C2) * 4;
 static_assert(2 * F_LDS_BYTES <= 160 * 1024, "two blocks per CU");
-
-__device__ __forceinline__ int f_swz(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
-#define F_LDS(p) ((__attribute__((address_space(3))) void*)(p))
-
 
 template <int V>
 using f_int = std::integral_constant<int, V>;
@@ -223,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void srf_pw_x3f_kernel(PwPairArgs a, const 
     const size_t sa = (size_t)src_any;             // (wave-uniform by construction; hipcc needs to be told)
     const char* src = (const char*)(((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(sa >> 32)) << 32) |
                                     (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa));
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)F_LDS(smem + stage * F_STAGE + wave * 4096));
+    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)SRF_LDS(smem + stage * F_STAGE + wave * 4096));
     unsigned keep;
     asm volatile(
         "s_mov_b32 %0, m0\n\t"
@@ -242,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void srf_pw_x3f_kernel(PwPairArgs a, const 
   auto srcB = [&](int p, int ks) __attribute__((always_inline)) {
     return w2 + (size_t)((p >> 1) * (F_BM / 16) + 2 * ks + (wave >> 1)) * F_STAGE + (p & 1) * 8192 + (wave & 1) * 4096;
   };
-  const int a_hi0 = f_swz(n, h), a_lo0 = a_hi0 ^ 32;   // fragment of virtual row 32 m + n: + 2048 m
+  const int a_hi0 = srf_swz(n, h), a_lo0 = a_hi0 ^ 32;   // fragment of virtual row 32 m + n: + 2048 m
   int s0 = 0;                                          // stage of the current step
   auto stage_after = [](int s, int d) __attribute__((always_inline)) {
     s += d;
@@ -637,18 +631,6 @@ int srf_pw_x3f_launch(const PwPairArgs& a0, int pro, hipStream_t st, bool f16, c
   SRF_CHECK_ARG(total < (1L << 30), "srf_pw_conv_pair: too many tiles");
   a.total = (int)total;
   const bool drain = srf_dbg(SRF_DBG_PAIR_FULL_DRAIN);
-  const long ok = srf_device_cached(7, [](void*) -> long {
-    bool good = true;
-    const void* fns[] = {(const void*)&srf_pw_x3f_kernel<1, 0, false>, (const void*)&srf_pw_x3f_kernel<2, 1, false>,
-                         (const void*)&srf_pw_x3f_kernel<1, 0, true>, (const void*)&srf_pw_x3f_kernel<2, 1, true>,
-                         (const void*)&srf_pw_x3f_kernel<0, 1, false>, (const void*)&srf_pw_x3f_kernel<0, 1, true>,
-                         (const void*)&srf_pw_x3f_kernel<1, 0, false, true>, (const void*)&srf_pw_x3f_kernel<2, 1, false, true>,
-                         (const void*)&srf_pw_x3f_kernel<1, 0, false, false, SrfFrames>,
-                         (const void*)&srf_pw_x3f_kernel<2, 1, false, false, SrfFrames>};
-    for (const void* f : fns) good &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES) == hipSuccess;
-    return good ? 1 : 0;
-  }, nullptr);
-  SRF_CHECK_ARG(ok == 1, "srf_pw_conv_pair: cannot reserve %d bytes of LDS", F_LDS_BYTES);
   // ONE TILE PER BLOCK up to 16 rounds of the chip's 2 x CUs block slots (beyond: persistent blocks, static round-robin).  A tile
   // takes a block the same time whether or not a second block shares its CU, so what matters is that no slot idles while tiles
   // are left: with one tile per block the dispatcher hands the next tile to whichever slot frees first (cfg 2: 800 tiles on 512
@@ -657,18 +639,20 @@ int srf_pw_x3f_launch(const PwPairArgs& a0, int pro, hipStream_t st, bool f16, c
   long nb = total <= 16 * slots && !srf_dbg(SRF_DBG_PAIR_PERSISTENT) ? total : slots - slots % 8;   // (flag 1 << 21: always persistent -- tests)
   if (nb > total) nb = total;
   dim3 grid((unsigned)nb), block(256);
+  // F_GO(PRO, EPI, DRAIN[, F16[, SrfFrames]]): LDS opt-in and launch of that instantiation; the ragged form gets its frames table
+#define F_GO(P, E, D, ...)                                                                                                   \
+  SRF_CHECK_ARG((srf_launch_lds<srf_pw_x3f_kernel<P, E, D, ##__VA_ARGS__>>(F_LDS_BYTES, grid, block, F_LDS_BYTES, st, a,     \
+                                                                           a.nrm.gamma, a.nrm.beta SRF_FRAMES_ARG(__VA_ARGS__))), \
+                "srf_pw_conv_pair: cannot reserve %d bytes of LDS", F_LDS_BYTES)
   if (frames) {      // the ragged forms: one tile per block whatever the size (a block skips its tile as a whole)
     SRF_CHECK_ARG(!f16 && (pro == 1 || pro == 2), "srf_pw_conv_pair_ragged: forms built: GlobLN, GlobLN + PReLU with residual");
     SRF_CHECK_ARG(total <= 0x7fffffffL, "srf_pw_conv_pair_ragged: too many tiles");
     grid = dim3((unsigned)total);
-    if (pro == 1)
-      hipLaunchKernelGGL((srf_pw_x3f_kernel<1, 0, false, false, SrfFrames>), grid, block, F_LDS_BYTES, st, a, a.nrm.gamma, a.nrm.beta, *frames);
-    else
-      hipLaunchKernelGGL((srf_pw_x3f_kernel<2, 1, false, false, SrfFrames>), grid, block, F_LDS_BYTES, st, a, a.nrm.gamma, a.nrm.beta, *frames);
+    if (pro == 1) F_GO(1, 0, false, false, SrfFrames);
+    else F_GO(2, 1, false, false, SrfFrames);
     SRF_CHECK_LAUNCH(pro == 1 ? "pw_pair_x3f_ragged<1>" : "pw_pair_x3f_ragged<2>", st);
     return SRF_OK;
   }
-#define F_GO(...) hipLaunchKernelGGL((srf_pw_x3f_kernel<__VA_ARGS__>), grid, block, F_LDS_BYTES, st, a, a.nrm.gamma, a.nrm.beta)
   if (f16) {
     SRF_CHECK_ARG(pro == 1 || pro == 2, "srf_pw_conv_pair (fp16 parts): prologue %d not built", pro);
     if (pro == 1) F_GO(1, 0, false, true);

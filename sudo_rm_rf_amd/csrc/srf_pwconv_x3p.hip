@@ -25,7 +25,6 @@
 
 #include "srf_pw.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int P_BM = 256, P_BN = 128, P_KT = 16;
@@ -36,10 +35,6 @@ constexpr int P_NSTAGE = 3;
 constexpr int P_MAX_STAT_EXAMPLES = 512;           // 4 KB behind the stages
 constexpr int P_LDS_BYTES = P_NSTAGE * P_STAGE + P_MAX_STAT_EXAMPLES * 8;
 static_assert(2 * P_LDS_BYTES <= 160 * 1024, "two blocks per CU");
-
-__device__ __forceinline__ int p_swz(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
-
-#define P_LDS(p) ((__attribute__((address_space(3))) void*)(p))
 
 // ---- packed weights: the image is written by srf_x3w_pack_kernel (srf_pwconv_x3w.hip, WPackEntry::dst16) in the launch that
 // writes the one-block kernel's image -- same bf16 parts, laid out per 16-k step ---------------------------------------------
@@ -100,8 +95,8 @@ __global__ __launch_bounds__(512, 4) void srf_pw_x3p_kernel(PwArgs a, const char
   };
   // ---- B staging: thread -> time step n = tid & 127, k rows 4 kg .. 4 kg + 3 (kg = tid >> 7, wave-uniform)
   const int b_n = tid & 127, kg = wave >> 1;
-  const int b_hi = P_A_IMG + p_swz(b_n, kg >> 1) + (kg & 1) * 8;
-  const int b_lo = P_A_IMG + p_swz(b_n, 2 + (kg >> 1)) + (kg & 1) * 8;
+  const int b_hi = P_A_IMG + srf_swz(b_n, kg >> 1) + (kg & 1) * 8;
+  const int b_lo = P_A_IMG + srf_swz(b_n, 2 + (kg >> 1)) + (kg & 1) * 8;
   __amdgpu_buffer_rsrc_t b_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
 
   struct TileP {
@@ -128,7 +123,7 @@ __global__ __launch_bounds__(512, 4) void srf_pw_x3p_kernel(PwArgs a, const char
   };
   auto gload_a = [&](const TileP& t, int kt, int stage) __attribute__((always_inline)) {
     const char* src = t.a_src + (size_t)kt * P_A_IMG + lane * 16;
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)P_LDS(smem + stage * P_STAGE + wave * 2048));
+    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)SRF_LDS(smem + stage * P_STAGE + wave * 2048));
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       unsigned keep;
@@ -179,8 +174,8 @@ __global__ __launch_bounds__(512, 4) void srf_pw_x3p_kernel(PwArgs a, const char
   int a_off[2], b_off[2];   // hi fragments; the lo fragment of the same row sits at offset ^ 32 (logical chunk + 2)
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
-    a_off[t] = p_swz(wm * 64 + t * 32 + fr, fc);
-    b_off[t] = P_A_IMG + p_swz(wn * 64 + t * 32 + fr, fc);
+    a_off[t] = srf_swz(wm * 64 + t * 32 + fr, fc);
+    b_off[t] = P_A_IMG + srf_swz(wn * 64 + t * 32 + fr, fc);
   }
   struct Frags {
     bf16x8 ah[2], al[2], bh[2], bl[2];
@@ -392,23 +387,15 @@ int srf_pw_x3p_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t s
   const long total = (long)a.Bt * nMt * nLt;
   SRF_CHECK_ARG(total < (1L << 30), "srf_pw_conv: too many tiles");
   SRF_CHECK_ARG(srf_x3p_supported(a, pro), "srf_pw_conv: shape not served by the paired 256 x 128 kernel");
-  const long ok = srf_device_cached(6, [](void*) -> long {
-    bool good = true;
-    const void* fns[] = {(const void*)&srf_pw_x3p_kernel<0, 0>, (const void*)&srf_pw_x3p_kernel<1, 0>,
-                         (const void*)&srf_pw_x3p_kernel<2, 0>, (const void*)&srf_pw_x3p_kernel<3, 0>,
-                         (const void*)&srf_pw_x3p_kernel<0, 1>, (const void*)&srf_pw_x3p_kernel<1, 1>,
-                         (const void*)&srf_pw_x3p_kernel<2, 1>, (const void*)&srf_pw_x3p_kernel<3, 1>,
-                         (const void*)&srf_pw_x3p_kernel<1, 0, 4>, (const void*)&srf_pw_x3p_kernel<2, 1, 4>};
-    for (const void* f : fns) good &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS_BYTES) == hipSuccess;
-    return good ? 1 : 0;
-  }, nullptr);
-  SRF_CHECK_ARG(ok == 1, "srf_pw_conv: cannot reserve %d bytes of LDS", P_LDS_BYTES);
   long nb = 2L * srf_device_cus();      // two resident blocks per CU
   nb -= nb % 8;
   if (nb > total) nb = total;
   dim3 grid((unsigned)nb), block(512);
   const bool res = a.residual != nullptr;
-#define P_GO(...) hipLaunchKernelGGL((srf_pw_x3p_kernel<__VA_ARGS__>), grid, block, P_LDS_BYTES, st, a, wpack, nMt, nLt, (int)total, a.nrm.gamma, a.nrm.beta, a.bias)
+#define P_GO(...)                                                                                                               \
+  SRF_CHECK_ARG((srf_launch_lds<srf_pw_x3p_kernel<__VA_ARGS__>>(P_LDS_BYTES, grid, block, P_LDS_BYTES, st, a, wpack, nMt, nLt, (int)total, \
+                                                                a.nrm.gamma, a.nrm.beta, a.bias)),                                \
+                "srf_pw_conv: cannot reserve %d bytes of LDS", P_LDS_BYTES)
   if (pro == 1 && !res && !srf_dbg(SRF_DBG_GEMM_NO_MGROUPS)) {
     P_GO(1, 0, 4);                // bottleneck
   } else if (pro == 2 && res && !srf_dbg(SRF_DBG_GEMM_NO_MGROUPS)) {

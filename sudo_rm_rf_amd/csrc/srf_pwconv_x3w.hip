@@ -47,8 +47,6 @@
 
 #include "srf_pw.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int W_BM = 256, W_BN = 128, W_BK = 32;
 constexpr int W_A_IMG = W_BM * 64;                       // [256][32] bf16, 64-B rows
 constexpr int W_B_IMG = W_BN * 64;                       // [128][32] bf16
@@ -57,17 +55,6 @@ constexpr int W_NSTAGE = 3;
 constexpr int W_WTILE_BYTES = 2 * W_A_IMG;               // packed weights of one (m-tile, k-tile) (srf_x3w_pack_kernel's format)
 constexpr int W_MAX_STAT_EXAMPLES = 1024;                // LDS statistics table: 8 KB behind the stages
 
-__host__ __device__ __forceinline__ int w_swz(int r, int c) { return r * 64 + ((c ^ ((r >> 2) & 3)) << 4); }
-
-__device__ __forceinline__ void w_split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h = (__bf16)v[j];
-    hi[j] = h;
-    lo[j] = (__bf16)(v[j] - (float)h);
-  }
-}
-
 // NP 4: the two parts are fp16 (11 + 11 mantissa bits instead of bf16's 8 + 8): hi = fp16(x), lo = fp16(x - hi).
 // The weights are stored times 2^4 (W_F16_WSCALE) so that the lo parts of typical weights (~0.03) stay in fp16's normal range;
 // the epilogue multiplies the accumulators by 2^-4 (exact).  Packets keep the bf16x8 container type (16 bytes).
@@ -75,7 +62,6 @@ __device__ __forceinline__ void w_split8(const float (&v)[8], bf16x8& hi, bf16x8
 // lose their lo part to fp16's subnormal range, i.e. they carry 11 instead of 22 bits -- an absolute error of <= 3e-8 per term,
 // invisible next to O(1) terms, but a tensor that is tiny AS A WHOLE (every |x| < 1e-3) reaches only the two-part bf16
 // kernel's accuracy class; the three-part bf16 form (flag 16384) has neither limit.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr float W_F16_WSCALE = 16.f;
 __device__ __forceinline__ void w_split8_f16(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
   f16x8 h8, l8;
@@ -93,8 +79,6 @@ __device__ __forceinline__ void w_split8_f16(const float (&v)[8], bf16x8& hi, bf
   hi = __builtin_bit_cast(bf16x8, h8);
   lo = __builtin_bit_cast(bf16x8, l8);
 }
-
-#define W_LDS(p) ((__attribute__((address_space(3))) void*)(p))
 
 // PRO: 0 = identity, 1 = GlobLN, 2 = GlobLN + PReLU, 3 = PReLU only.
 // EPI: 0 = bias (+ statistics), 1 = bias + residual, 2 = ReLU(bias + .) x mul (mask epilogue), 3 = decided at run time (any),
@@ -226,8 +210,8 @@ __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char
   //      (NP 3: 4 k rows per thread; h -> chunk b_c >> 1 of the hi image, m -> chunk 2 + (b_c >> 1), l -> chunk b_c >> 1 of the lo
   //      image, at byte (b_c & 1) * 8 of the 16-byte chunk)
   const int b_n = tid & 127, b_c = wave >> 1, b_kg = NP == 3 ? b_c * 4 : b_c * 8;
-  const int b_lds = NP == 3 ? 2 * W_A_IMG + w_swz(b_n, b_c >> 1) + (b_c & 1) * 8 : 2 * W_A_IMG + w_swz(b_n, b_c);
-  const int b_lds_m = 2 * W_A_IMG + w_swz(b_n, 2 + (b_c >> 1)) + (b_c & 1) * 8;   // NP 3 only
+  const int b_lds = NP == 3 ? 2 * W_A_IMG + srf_swz(b_n, b_c >> 1) + (b_c & 1) * 8 : 2 * W_A_IMG + srf_swz(b_n, b_c);
+  const int b_lds_m = 2 * W_A_IMG + srf_swz(b_n, 2 + (b_c >> 1)) + (b_c & 1) * 8;   // NP 3 only
   __amdgpu_buffer_rsrc_t b_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
 
   struct TileP {
@@ -258,7 +242,7 @@ __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char
   // A: LDS DMA through inline asm (invisible to hipcc's vmcnt bookkeeping: counted by hand, see `step`)
   auto gload_a = [&](const TileP& t, int kt, int stage) __attribute__((always_inline)) {
     const char* src = t.a_src + (size_t)kt * W_WTILE_BYTES + lane * 16;
-    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)W_LDS(smem + stage * W_STAGE + wave * 4096));
+    const unsigned dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)SRF_LDS(smem + stage * W_STAGE + wave * 4096));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       unsigned keep;
@@ -326,7 +310,7 @@ __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char
     }
     bf16x8 hi, lo;
     if constexpr (NP == 4) w_split8_f16(vb, hi, lo);
-    else w_split8(vb, hi, lo);
+    else srf_split8(vb, hi, lo);
     *reinterpret_cast<bf16x8*>(base) = hi;
     *reinterpret_cast<bf16x8*>(base + W_B_IMG) = lo;
   };
@@ -346,8 +330,8 @@ __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        a_off[t][ks] = w_swz(quarter ? wave * 32 + fr : wm * 64 + t * 32 + fr, 2 * ks + fc);
-        b_off[t][ks] = 2 * W_A_IMG + w_swz(quarter ? fr : wn * 64 + t * 32 + fr, 2 * ks + fc);
+        a_off[t][ks] = srf_swz(quarter ? wave * 32 + fr : wm * 64 + t * 32 + fr, 2 * ks + fc);
+        b_off[t][ks] = 2 * W_A_IMG + srf_swz(quarter ? fr : wn * 64 + t * 32 + fr, 2 * ks + fc);
       }
   };
   struct Frags {   // the fragments of one k-sub-step (16 of the k-tile's 32 k): 32 registers
@@ -719,7 +703,7 @@ __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char
                   hi4[j] = h;
                   lo4[j] = (__bf16)(v - (float)h);
                 }
-                char* dst = buf + w_swz(row, g) + 8 * lhalf;
+                char* dst = buf + srf_swz(row, g) + 8 * lhalf;
                 *reinterpret_cast<bf16x4*>(dst) = hi4;
                 *reinterpret_cast<bf16x4*>(dst + W_B_IMG) = lo4;
               }
@@ -733,7 +717,7 @@ __global__ __launch_bounds__(512, 2) void srf_pw_x3w_kernel(PwArgs a, const char
           if (z_active) {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-              const int off = w_swz(znb * 32 + lcol32, 2 * ks + lhalf);
+              const int off = srf_swz(znb * 32 + lcol32, 2 * ks + lhalf);
               const bf16x8 vh = *reinterpret_cast<const bf16x8*>(buf + off);
               const bf16x8 vl = *reinterpret_cast<const bf16x8*>(buf + W_B_IMG + off);
               zacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc.f[ks][1], vh, zacc, 0, 0, 0);
@@ -907,14 +891,14 @@ __global__ __launch_bounds__(256) void srf_x3w_pack_kernel(WPackTable t) {
       vv[j] = F16 ? v * W_F16_WSCALE : v;
     }
     if constexpr (F16) w_split8_f16(vv, hi, lo);
-    else w_split8(vv, hi, lo);
-    char* base = e.dst + (size_t)tile * W_WTILE_BYTES + w_swz(row, c);
+    else srf_split8(vv, hi, lo);
+    char* base = e.dst + (size_t)tile * W_WTILE_BYTES + srf_swz(row, c);
     *reinterpret_cast<bf16x8*>(base) = hi;
     *reinterpret_cast<bf16x8*>(base + W_A_IMG) = lo;
     if (e.dst16) {              // 16-k step 2 kt + (c >> 1) of the m-tile, 8-k packet c & 1
       char* b16 = e.dst16 + ((size_t)mt * (2 * nKt) + 2 * kt + (c >> 1)) * (size_t)(W_BM * 64);
-      *reinterpret_cast<bf16x8*>(b16 + w_swz(row, c & 1)) = hi;
-      *reinterpret_cast<bf16x8*>(b16 + w_swz(row, 2 + (c & 1))) = lo;
+      *reinterpret_cast<bf16x8*>(b16 + srf_swz(row, c & 1)) = hi;
+      *reinterpret_cast<bf16x8*>(b16 + srf_swz(row, 2 + (c & 1))) = lo;
     }
   }
 }
@@ -972,15 +956,14 @@ __global__ __launch_bounds__(256) void srf_x3w_pack_dec_kernel(const float* __re
   if (idx >= nblocks * 4 * 64) return;
   const int lane = idx & 63, ks = (idx >> 6) & 1, mb = (idx >> 7) & 1, blk = idx >> 8;
   const int m = mb * 32 + (lane & 31);
-  bf16x8 hi, lo;
+  float v[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int ci = blk * 32 + 16 * ks + 8 * (lane >> 5) + e;
-    const float v = (ci < Ci && m < M) ? w[(size_t)ci * M + m] : 0.f;
-    const __bf16 h = (__bf16)v;
-    hi[e] = h;
-    lo[e] = (__bf16)(v - (float)h);
+    v[e] = (ci < Ci && m < M) ? w[(size_t)ci * M + m] : 0.f;
   }
+  bf16x8 hi, lo;
+  srf_split8(v, hi, lo);
   char* o = dst + ((size_t)(blk * 2 + mb) * 4 + ks * 2) * 1024 + lane * 16;
   *reinterpret_cast<bf16x8*>(o) = hi;
   *reinterpret_cast<bf16x8*>(o + 1024) = lo;
@@ -1033,10 +1016,10 @@ __global__ __launch_bounds__(256) void srf_x3w_pack3_kernel(W3PackTable t) {
       zero[j] = (__bf16)0.f;
     }
     char* base = e.dst + (size_t)tile * W_WTILE_BYTES;
-    *reinterpret_cast<bf16x8*>(base + w_swz(row, c)) = ph;
-    *reinterpret_cast<bf16x8*>(base + w_swz(row, 2 + c)) = pm;
-    *reinterpret_cast<bf16x8*>(base + W_A_IMG + w_swz(row, c)) = pl;
-    *reinterpret_cast<bf16x8*>(base + W_A_IMG + w_swz(row, 2 + c)) = zero;
+    *reinterpret_cast<bf16x8*>(base + srf_swz(row, c)) = ph;
+    *reinterpret_cast<bf16x8*>(base + srf_swz(row, 2 + c)) = pm;
+    *reinterpret_cast<bf16x8*>(base + W_A_IMG + srf_swz(row, c)) = pl;
+    *reinterpret_cast<bf16x8*>(base + W_A_IMG + srf_swz(row, 2 + c)) = zero;
   }
 }
 size_t srf_x3w_packed3_bytes(int Cout, int Cin) {
@@ -1072,31 +1055,6 @@ static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, co
   SRF_CHECK_ARG((long)a.Bt * a.Cin * a.L * 4 < (1L << 31), "srf_pw_conv: activation tensor too large for buffer loads");
   SRF_CHECK_ARG(srf_x3w_supported(a.Bt, pro), "srf_pw_conv: too many examples for the statistics table");
   const size_t lds = (size_t)W_NSTAGE * W_STAGE + ((pro == 1 || pro == 2) ? (size_t)a.Bt * sizeof(float2) : 0);
-  // dynamic LDS beyond 64 KB needs the attribute once per device (per-device cache, srf_common.h)
-  const long ok = srf_device_cached(3, [](void*) -> long {
-    const int bytes = W_NSTAGE * W_STAGE + W_MAX_STAT_EXAMPLES * (int)sizeof(float2);
-    bool good = true;
-    const void* fns[] = {
-        // the forms the models launch, each with its cache policy (see the launch function)
-        (const void*)&srf_pw_x3w_kernel<0, 0, 0>, (const void*)&srf_pw_x3w_kernel<1, 0, 5>,
-        (const void*)&srf_pw_x3w_kernel<2, 1, 5>, (const void*)&srf_pw_x3w_kernel<3, 2, 5>,
-        (const void*)&srf_pw_x3w_kernel<3, 4, 4>, (const void*)&srf_pw_x3w_kernel<0, 1, 0>,
-        // two fp16 parts per operand (training forward, the default)
-        (const void*)&srf_pw_x3w_kernel<0, 0, 0, 4>, (const void*)&srf_pw_x3w_kernel<1, 0, 5, 4>,
-        (const void*)&srf_pw_x3w_kernel<2, 1, 5, 4>, (const void*)&srf_pw_x3w_kernel<3, 0, 5, 4>,
-        // three bf16 parts per operand (training forward, debug flag 16384)
-        (const void*)&srf_pw_x3w_kernel<0, 0, 0, 3>, (const void*)&srf_pw_x3w_kernel<1, 0, 5, 3>,
-        (const void*)&srf_pw_x3w_kernel<2, 1, 5, 3>, (const void*)&srf_pw_x3w_kernel<3, 0, 5, 3>,
-        // the ragged forms (srf_pw_conv_packed_ragged)
-        (const void*)&srf_pw_x3w_kernel<0, 0, 0, 2, SrfFrames>, (const void*)&srf_pw_x3w_kernel<1, 0, 5, 2, SrfFrames>,
-        (const void*)&srf_pw_x3w_kernel<2, 1, 5, 2, SrfFrames>,
-        // any other prologue / epilogue combination (unit tests, stand-alone srf_pw_conv callers)
-        (const void*)&srf_pw_x3w_kernel<0, 3>, (const void*)&srf_pw_x3w_kernel<1, 3>,
-        (const void*)&srf_pw_x3w_kernel<2, 3>, (const void*)&srf_pw_x3w_kernel<3, 3>};
-    for (const void* f : fns) good &= hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
-    return good ? 1 : 0;
-  }, nullptr);
-  SRF_CHECK_ARG(ok == 1, "srf_pw_conv: cannot reserve %zu bytes of LDS", lds);
   long nb = srf_device_cus();
   nb -= nb % 8;
   if (nb < 8) nb = 8;
@@ -1119,7 +1077,13 @@ static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, co
   PwArgs ap = a;
   if (!srf_dbg(SRF_DBG_GEMM_QUARTER_TILES_LAST)) ap.epi_mask |= 1 << 12;   // quarter tiles first (flag 512: last)
   const bool res = a.residual != nullptr, mask = !res && (a.epi_mask & 1);
-#define W_GO(P, E, C) hipLaunchKernelGGL((srf_pw_x3w_kernel<P, E, C>), grid, block, lds, st, ap, wpack, nMt, nLt, (int)total, rounds, a.nrm.gamma, a.nrm.beta, a.bias, fuse_wd, fuse_z, fuse_M, mgrp)
+  // W_GO(PRO, EPI, CP[, NP[, SrfFrames]]): LDS opt-in and launch of that instantiation (srf_launch_lds: the most a launch asks for is the
+  // stages + a full statistics table); the ragged form gets its frames table behind the arguments
+#define W_GO(P, E, C, ...)                                                                                                              \
+  SRF_CHECK_ARG((srf_launch_lds<srf_pw_x3w_kernel<P, E, C, ##__VA_ARGS__>>(                                                             \
+                    W_NSTAGE * W_STAGE + W_MAX_STAT_EXAMPLES * 8, grid, block, lds, st, ap, wpack, nMt, nLt, (int)total, rounds,        \
+                    a.nrm.gamma, a.nrm.beta, a.bias, fuse_wd, fuse_z, fuse_M, mgrp SRF_FRAMES_ARG(__VA_ARGS__))),                       \
+                "srf_pw_conv: cannot reserve %zu bytes of LDS", lds)
   // Cache policy (CP) of the four model forms: bit 0 = non-temporal output stores, bit 2 = non-temporal activation loads,
   // bit 3 = non-temporal residual / mask-multiplier loads.  Every CU re-reads the whole packed weight image from L2 for every
   // tile, while activations, residuals and outputs stream through once: marked non-temporal they stop displacing the weights.
@@ -1128,37 +1092,31 @@ static int srf_pw_x3w_launch_any(const PwArgs& a, const char* wpack, int pro, co
   // plain (CP 0); bottleneck, res_conv, mask non-temporal activation loads + stores (CP 5; the fused mask + decoder GEMM
   // has no output tensor to mark: CP 4).
   if (frames) {
-#define W_GOR(P, E, C) hipLaunchKernelGGL((srf_pw_x3w_kernel<P, E, C, 2, SrfFrames>), grid, block, lds, st, ap, wpack, nMt, nLt, (int)total, rounds, a.nrm.gamma, a.nrm.beta, a.bias, fuse_wd, fuse_z, fuse_M, mgrp, *frames)
     SRF_CHECK_ARG(np == 2 && !mask && !fuse_wd && (pro == 2) == res && pro != 3,
                   "srf_pw_conv_packed_ragged: forms built: no prologue / GlobLN (statistics out), GlobLN + PReLU with residual");
-    if (pro == 0) W_GOR(0, 0, 0);
-    else if (pro == 1) W_GOR(1, 0, 5);
-    else W_GOR(2, 1, 5);
-#undef W_GOR
+    if (pro == 0) W_GO(0, 0, 0, 2, SrfFrames);
+    else if (pro == 1) W_GO(1, 0, 5, 2, SrfFrames);
+    else W_GO(2, 1, 5, 2, SrfFrames);
     static const char* const kLabelR[3] = {"pw_conv_x3w_ragged<0>", "pw_conv_x3w_ragged<1>", "pw_conv_x3w_ragged<2>"};
     SRF_CHECK_LAUNCH(kLabelR[pro], st);
     return SRF_OK;
   }
   if (np == 4) {
-#define W_GO4(P, E, C) hipLaunchKernelGGL((srf_pw_x3w_kernel<P, E, C, 4>), grid, block, lds, st, ap, wpack, nMt, nLt, (int)total, rounds, a.nrm.gamma, a.nrm.beta, a.bias, fuse_wd, fuse_z, fuse_M, mgrp)
     SRF_CHECK_ARG(!mask && !fuse_wd && (pro == 2) == res && !(pro != 2 && res), "srf_pw_conv (fp16 two-part): form not built");
-    if (pro == 0) W_GO4(0, 0, 0);
-    else if (pro == 1) W_GO4(1, 0, 5);
-    else if (pro == 2) W_GO4(2, 1, 5);
-    else W_GO4(3, 0, 5);
-#undef W_GO4
+    if (pro == 0) W_GO(0, 0, 0, 4);
+    else if (pro == 1) W_GO(1, 0, 5, 4);
+    else if (pro == 2) W_GO(2, 1, 5, 4);
+    else W_GO(3, 0, 5, 4);
     static const char* const kLabel4[4] = {"pw_conv_x3w4<0>", "pw_conv_x3w4<1>", "pw_conv_x3w4<2>", "pw_conv_x3w4<3>"};
     SRF_CHECK_LAUNCH(kLabel4[pro < 0 || pro > 3 ? 3 : pro], st);
     return SRF_OK;
   }
   if (np == 3) {
-#define W_GO3(P, E, C) hipLaunchKernelGGL((srf_pw_x3w_kernel<P, E, C, 3>), grid, block, lds, st, ap, wpack, nMt, nLt, (int)total, rounds, a.nrm.gamma, a.nrm.beta, a.bias, fuse_wd, fuse_z, fuse_M, mgrp)
     SRF_CHECK_ARG(!mask && !fuse_wd && (pro == 2) == res && !(pro != 2 && res), "srf_pw_conv (three-part): form not built");
-    if (pro == 0) W_GO3(0, 0, 0);
-    else if (pro == 1) W_GO3(1, 0, 5);
-    else if (pro == 2) W_GO3(2, 1, 5);
-    else W_GO3(3, 0, 5);
-#undef W_GO3
+    if (pro == 0) W_GO(0, 0, 0, 3);
+    else if (pro == 1) W_GO(1, 0, 5, 3);
+    else if (pro == 2) W_GO(2, 1, 5, 3);
+    else W_GO(3, 0, 5, 3);
     static const char* const kLabel3[4] = {"pw_conv_x3w3<0>", "pw_conv_x3w3<1>", "pw_conv_x3w3<2>", "pw_conv_x3w3<3>"};
     SRF_CHECK_LAUNCH(kLabel3[pro < 0 || pro > 3 ? 3 : pro], st);
     return SRF_OK;

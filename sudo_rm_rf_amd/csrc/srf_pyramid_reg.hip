@@ -475,7 +475,7 @@ int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st
   long cw = 0;
   if (persist) {
     struct Q { int ch; } q{CH};
-    cw = srf_device_cached(CH == 16 ? 0 : 1, [](void* p) -> long {
+    cw = srf_device_cached(CH == 16 ? SRF_OCC_PYR_PASS1_CH16 : SRF_OCC_PYR_PASS1_CH32, [](void* p) -> long {
       const int ch = static_cast<Q*>(p)->ch;
       int per_cu = 0;
       const void* fn = ch == 16 ? (const void*)&srf_pyramid_reg_kernel<true, 16, true>
