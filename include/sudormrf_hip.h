@@ -221,9 +221,14 @@ int srf_forward(const srf_plan* plan, const float* const* params, int num_params
  * synchronised, and a ragged batch is capped at SRF_RAGGED_MAX_BATCH = 128 examples.
  * srf_plan_ragged_supported: 1 for an Improved plan (one audio channel, K = 21, out_channels = 256, batch <= 128) whose
  * uniform forward, under the current kernel mode, runs the packed 256 x 128 GEMMs, the register-resident fused pyramid and
- * the fused mask + decoder tail; GroupComm and causal plans: 0.  The ragged forward runs the fused conv pair and the 256 x 128
+ * the fused mask + decoder tail; 1 for a GroupComm plan with one audio channel, K = 21, group_size = 16, out_channels = 256,
+ * in_channels = 512 (the thin conv's ragged forms: 16 <-> 32 channels per group), batch <= 128, whose uniform forward runs
+ * the packed bottleneck GEMM, the MFMA TAC, the fused pre-add, the register-resident pyramid and the fused tail; every other
+ * GroupComm plan and causal plans: 0.  The ragged forward runs the fused conv pair and the 256 x 128
  * kernel whatever the uniform forward's "at least as many tiles as CUs" gates say; plans too small for the fused tail are
- * not supported (run those examples one by one).
+ * not supported (run those examples one by one).  GroupComm launch sequence: encoder, bottleneck GEMM, per block TAC ->
+ * pre-add proj_1x1 -> pyramid (16 folded rows per example) -> res_conv, then the unchanged mask + decoder GEMM and the ragged
+ * overlap-add (srf_tac_ragged, srf_pw_conv_small_ragged, srf_pyramid_ragged_rows below).
  * srf_plan_ragged_workspace_bytes: the workspace the ragged call needs (0 = not supported); srf_plan_workspace_bytes is
  * unchanged.  Refused with SRF_EINVAL BEFORE anything is launched, srf_last_error() naming the example: an unsupported plan,
  * a length outside 1..T, an example whose padded length the fused pyramid does not take as a row length of its own
@@ -303,7 +308,10 @@ int srf_encoder(const float* wav, const float* w, float* out, double* sums,
  * that carry statistics are stored as exact zeros from the example's end to the row stride.  The tables reach the kernels BY
  * VALUE in the launch arguments -- no upload, no synchronisation -- which caps a ragged batch at SRF_RAGGED_MAX_BATCH examples;
  * larger batches, out-of-range entries and lengths a kernel cannot take are refused (SRF_EINVAL, the message names the
- * example) before anything is launched.  The profiler names of the ragged kernels carry the suffix "_ragged". */
+ * example) before anything is launched.  The profiler names of the ragged kernels carry the suffix "_ragged".
+ * Kernels that run over FOLDED rows (GroupComm folds its groups into the batch: rows = examples * rows_per_example) keep
+ * the table at ONE ENTRY PER EXAMPLE and find a row's example as row / rows_per_example: srf_pyramid_ragged_rows,
+ * srf_pw_conv_small_ragged. */
 #define SRF_RAGGED_MAX_BATCH 128
 /* srf_encoder over a ragged batch (A = 1, K = 21 only: the shape of the published Improved models).  Requires
  * lengths[b] <= (K/2) * frames[b]; frames[b] = padded length / hop of example b (srf_plan_padded_length of a batch-1 plan). */
@@ -376,6 +384,20 @@ int srf_pw_conv_packed_ragged(const float* x, const float* w, const void* w_pack
                               int Bt, int Cin, int Cout, int L, const srf_norm* in_norm, const float* residual,
                               double* out_sums, int epilogue_mask, const float* mul, int mul_channels, const int* frames,
                               void* stream);
+/* GroupComm's per-group convolutions over a ragged batch (the thin-shape kernel; 16 -> 32 and 32 -> 16 channels, L % 4 == 0,
+ * frames[b] % 4 == 0; srf_pw_conv_small_ragged_supported).  x, y, residual, pre_q, pre_u: [rows, channels, L] with
+ * rows = examples * rows_per_example; frames: one entry per EXAMPLE.  Two forms:
+ *   pre-add (proj_1x1)   pre_q, pre_norm {sums, gamma, beta}, pre_u and out_sums given; no in_norm, no residual.
+ *                        u = x + GlobLN(pre_q) with count Cin * frames, written to pre_u for the example's own columns only
+ *                        (unspecified past them: the block's residual); y = W u + bias stored as exact 0 from the example's
+ *                        end to L; out_sums over the example's own columns.  A wavefront wholly past the end stores its zeros
+ *                        without loading anything.
+ *   residual (res_conv)  in_norm {sums, gamma, beta, prelu} (count Cin * frames) and residual given; no out_sums, no pre_*.
+ *                        y is written for the example's own columns only (the block stream). */
+int srf_pw_conv_small_ragged_supported(int Cin, int Cout, int L);
+int srf_pw_conv_small_ragged(const float* x, const float* w, const float* bias, float* y, int rows, int Cin, int Cout, int L,
+                             const srf_norm* in_norm, const float* residual, double* out_sums, const float* pre_q,
+                             const srf_norm* pre_norm, float* pre_u, const int* frames, int rows_per_example, void* stream);
 int srf_pw_conv_pair_ragged_supported(int Cin1, int Cmid, int Cout2, int L);
 int srf_pw_conv_pair_ragged(const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
                             const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2,
@@ -450,6 +472,12 @@ int srf_pyramid_ragged_frames_ok(int frames, int L, int D);
 int srf_pyramid_ragged(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
                        const float* const* bias, const float* const* gamma, const float* const* beta, int groups,
                        int C, int L, int D, void* scratch, double* out_sums, const int* frames, void* stream);
+/* The same over folded rows: groups = examples * groups_per_example, every group a GlobLN group of its own with C channels
+ * (GroupComm: C = in_channels / G), frames: one entry per EXAMPLE.  srf_pyramid_ragged is groups_per_example = 1. */
+int srf_pyramid_ragged_rows(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
+                            const float* const* bias, const float* const* gamma, const float* const* beta, int groups,
+                            int C, int L, int D, void* scratch, double* out_sums, const int* frames, int groups_per_example,
+                            void* stream);
 
 /* ---- Causal SuDORMRF (ABI 16; causal_improved_sudormrf_v3.py) ----
  * srf_causal_encoder: out[b,n,l] = sum_{a, k<K} w[n,a,k] * x[b,a, h*l+k-2h], h = K/2, w: [N, A, 2K-1] (the stored
@@ -595,6 +623,12 @@ int srf_decoder(const float* v, const float* w, float* out, int Bt, int Ci, int 
  * TAC_output.0.weight/.bias, TAC_output.1.weight).  out_sums: [Bt*G][SRF_STAT_BUCKETS][2]. */
 int srf_tac(const float* x, float* q, const float* const* params, int Bt, int G, int n, int H, int L,
             double* out_sums, void* stream);
+/* srf_tac over a ragged batch: the MFMA kernel only (n = 16, H = 48, G = 16, 16-byte aligned x / q; anything else is refused
+ * before a launch).  TAC is pointwise in time, so x past an example's end is never interpreted (it may hold NaN); q is stored
+ * as exact 0 from frames[b] to L -- per column: a 32-column tile may straddle the end -- and out_sums run over the example's
+ * own columns (the consumer's count is n * frames[b]).  A tile wholly past the end stores zeros without loads or MFMAs. */
+int srf_tac_ragged(const float* x, float* q, const float* const* params, int Bt, int G, int n, int H, int L,
+                   double* out_sums, const int* frames /* host, [Bt] */, void* stream);
 
 /* pr + w * (mix - sum_s pr), uniform weights (w = 1/S).  pr,out: [Bt,S,T], mix: [Bt,1,T]. */
 int srf_mixture_consistency(const float* pr, const float* mix, float* out, int Bt, int S, int T,

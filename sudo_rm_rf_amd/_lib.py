@@ -130,6 +130,12 @@ _PROTOS = {
     "srf_pw_conv_pair_ragged_supported": (_i, [_i, _i, _i, _i]),
     "srf_pw_conv_pair_ragged": (_i, [_vp, _vp, _vp, _vp, C.POINTER(srf_norm), _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                     C.POINTER(_i), _vp]),
+    "srf_pyramid_ragged_rows": (_i, [_vp, _vp, C.POINTER(srf_norm), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                    C.POINTER(_vp), _i, _i, _i, _i, _vp, _vp, C.POINTER(_i), _i, _vp]),
+    "srf_tac_ragged": (_i, [_vp, _vp, C.POINTER(_vp), _i, _i, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
+    "srf_pw_conv_small_ragged_supported": (_i, [_i, _i, _i]),
+    "srf_pw_conv_small_ragged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(srf_norm), _vp, _vp, _vp, C.POINTER(srf_norm),
+                                     _vp, C.POINTER(_i), _i, _vp]),
     "srf_plan_ragged_supported": (_i, [_vp]),
     "srf_plan_ragged_workspace_bytes": (_sz, [_vp]),
     "srf_forward_ragged": (_i, [_vp, C.POINTER(_vp), _i, _vp, C.POINTER(_i), _vp, _vp, _sz, _vp]),

@@ -730,12 +730,29 @@ static bool plan_ragged_now(const srf_plan* p, const char** why) {
     if (why) *why = w;
     return false;
   };
-  if (c.variant != SRF_VARIANT_IMPROVED) return no("only the Improved model has ragged kernels (GroupComm / causal plans: per-example calls)");
+  const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
+  if (c.variant == SRF_VARIANT_CAUSAL) return no("the causal model has no ragged kernels (per-example calls)");
   if (p->A != 1 || c.enc_kernel_size != 21) return no("the ragged encoder is the one-channel K = 21 kernel");
+  if (gc && (c.group_size != 16 || p->nB != 16))
+    return no("GroupComm: the ragged TAC is the MFMA kernel (group_size = 16, out_channels = 256)");
+  if (gc && !(srf_pw_small_ragged_supported(p->nB, p->nC, p->L) && srf_pw_small_ragged_supported(p->nC, p->nB, p->L)))
+    return no("GroupComm: in_channels / 16 is not a shape the thin conv's ragged forms take in both directions");
   if (p->Bt > SRF_RAGGED_MAX_BATCH) return no("the batch exceeds SRF_RAGGED_MAX_BATCH");
   if (!plan_use_pack(p)) return no("the forward does not run the packed 256 x 128 GEMMs (kernel mode / debug flags / shapes)");
   if (!plan_fused_pyramid_now(p) || srf_dbg(SRF_DBG_PYR_NO_REG) || !srf_pyramid_reg_supported(p->L, D))
     return no("the forward does not run the register-resident fused pyramid at this length");
+  if (gc) {
+    // what the uniform GroupComm forward must be running: the MFMA TAC, the fused pre-add, the packed bottleneck, the fused tail
+    if (srf_dbg(SRF_DBG_TAC_ONE_STEP_PER_LANE | SRF_DBG_TAC_VALU | SRF_DBG_TAC_GENERIC | SRF_DBG_TAC_LANES_4TILES) ||
+        (long)c.out_channels * p->L * 4 >= (1L << 31))
+      return no("GroupComm: the forward does not run the MFMA TAC (debug flags / length)");
+    if (!p->pk_of_param[3] || !p->pk_of_param[p->p_tail + 1] || !srf_x3w_shape_supported(N, c.out_channels, p->L) ||
+        (long)p->Bt * ((p->L + 127) / 128) < 8)
+      return no("bottleneck / mask conv shapes outside the 256 x 128 GEMM, or too few tiles for it");
+    if (!plan_fused_tail_now(p, true))
+      return no("the forward does not run the fused mask + decoder tail at this size (small launches)");
+    return true;
+  }
   const int pu0 = p->p_block0;
   if (!p->pk_of_param[3] || !p->pk_of_param[p->p_tail + 1]) return no("bottleneck / mask conv shapes outside the 256 x 128 GEMM");
   for (int i = 0; i < U; ++i)
@@ -755,7 +772,9 @@ extern "C" int srf_forward_ragged(const srf_plan* p, const float* const* P, int 
                                   float* out, void* workspace, size_t workspace_bytes, void* stream) {
   SRF_CHECK_ARG(p && P && wav && lengths && out && workspace, "srf_forward_ragged: null pointer");
   const char* why = "";
-  SRF_CHECK_ARG(plan_ragged_now(p, &why), "srf_forward_ragged: plan not supported: %s", why);
+  SRF_CHECK_ARG(plan_ragged_now(p, &why), "srf_forward_ragged: plan not supported%s: %s",
+                p->cfg.variant == SRF_VARIANT_IMPROVED ? "" : " (ragged kernels exist for the Improved model and for GroupComm with 16 groups of 16 channels)",
+                why);
   SRF_CHECK_ARG(num_params == p->n_params, "srf_forward_ragged: expected %d parameter tensors, got %d", p->n_params, num_params);
   if (workspace_bytes < p->total_bytes) {
     srf_set_error("srf_forward_ragged: workspace too small (%zu < %zu bytes)", workspace_bytes, p->total_bytes);
@@ -766,6 +785,8 @@ extern "C" int srf_forward_ragged(const srf_plan* p, const float* const* P, int 
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, h = K / 2;
   const int Bt = p->Bt, L = p->L, nB = p->nB, nC = p->nC;
+  const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
+  const int G = gc ? c.group_size : 1, Bg = p->Bg;
   // ---- every example's own padded length, as its batch-1 plan would have it; all refusals BEFORE the first launch
   int frames[SRF_RAGGED_MAX_BATCH];
   SrfFrames lens_t, frames_t;
@@ -787,7 +808,7 @@ extern "C" int srf_forward_ragged(const srf_plan* p, const float* const* P, int 
   hipStream_t st = (hipStream_t)stream;
   auto fptr = [&](size_t o) { return (float*)(ws + o); };
   double* stats = (double*)(ws + p->off_stats);
-  auto slot = [&](int s) { return stats + (size_t)s * Bt * SRF_STAT_BUCKETS * 2; };
+  auto slot = [&](int s) { return stats + (size_t)s * Bg * SRF_STAT_BUCKETS * 2; };   // (slots hold one entry per FOLDED row)
   rc = srf_zero_launch(stats, p->stats_bytes, st);
   if (rc) return rc;
   {
@@ -809,42 +830,85 @@ extern "C" int srf_forward_ragged(const srf_plan* p, const float* const* P, int 
   float* nxt = fptr(p->off_xb);
   float* y1 = fptr(p->off_y1);
   float* merged = fptr(p->off_lv[0]);
-  const int pu0 = p->p_block0;
-  {   // ln folded into the bottleneck, + proj_1x1 of block 0
+  if (gc) {
+    // GroupComm: the bottleneck alone (its output is block stream: no statistics), then per block
+    // TAC -> proj_1x1 with u = x + GlobLN(q) folded into its load -> pyramid over G rows per example -> res_conv, every kernel
+    // over the Bt * G folded rows finding its example as row / G
     srf_norm ln{slot(0), P[1], P[2], nullptr};
-    rc = srf_pw_conv_pair_ragged(enc, packed(3), P[4], cur, &ln, nullptr, packed(pu0), P[pu0 + 1], y1, slot(1), Bt, N, nB, nC, L,
-                                 frames, stream);
+    rc = srf_pw_conv_packed_ragged(enc, P[3], packed(3), P[4], cur, Bt, N, c.out_channels, L, &ln, nullptr, nullptr, 0, nullptr, 0,
+                                   frames, stream);
     if (rc) return rc;
-  }
-  for (int i = 0; i < U; ++i) {
-    const int pu_index = pu0 + i * p->p_block_stride;
-    const float* const* Pu = P + pu_index;
-    const int s0 = 1 + i * p->slots_per_block;
-    const float *pw[SRF_MAX_DEPTH], *pb[SRF_MAX_DEPTH], *pg[SRF_MAX_DEPTH], *pbe[SRF_MAX_DEPTH];
-    for (int k = 0; k < D; ++k) {
-      const float* const* Pk = Pu + 5 + 4 * k;
-      pw[k] = Pk[0];
-      pb[k] = Pk[1];
-      pg[k] = Pk[2];
-      pbe[k] = Pk[3];
+    float* xq = fptr(p->off_xq);
+    float* xu = fptr(p->off_xu);
+    for (int i = 0; i < U; ++i) {
+      const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
+      const float* const* Pu = Pb + p->p_ublock_off;
+      const int s0 = 1 + i * p->slots_per_block;      // tac | proj | d0 .. d{D-1} | merged
+      rc = srf_tac_ragged(cur, xq, Pb, Bt, G, nB, 3 * nB, L, slot(s0), frames, stream);
+      if (rc) return rc;
+      srf_norm tn{slot(s0), Pb[9], Pb[10], nullptr};
+      rc = srf_pw_conv_small_ragged(cur, Pu[0], Pu[1], y1, Bg, nB, nC, L, nullptr, nullptr, slot(s0 + 1), xq, &tn, xu, frames, G,
+                                    stream);
+      if (rc) return rc;
+      const float *pw[SRF_MAX_DEPTH], *pb[SRF_MAX_DEPTH], *pg[SRF_MAX_DEPTH], *pbe[SRF_MAX_DEPTH];
+      for (int k = 0; k < D; ++k) {
+        const float* const* Pk = Pu + 5 + 4 * k;
+        pw[k] = Pk[0];
+        pb[k] = Pk[1];
+        pg[k] = Pk[2];
+        pbe[k] = Pk[3];
+      }
+      srf_norm in{slot(s0 + 1), Pu[2], Pu[3], Pu[4]};
+      rc = srf_pyramid_ragged_rows(y1, merged, &in, pw, pb, pg, pbe, Bg, nC, L, D, ws + p->off_pyr, slot(s0 + 2 + D), frames, G,
+                                   stream);
+      if (rc) return rc;
+      const float* const* Pf = Pu + 5 + 4 * D;
+      srf_norm fn{slot(s0 + 2 + D), Pf[0], Pf[1], Pf[2]};
+      rc = srf_pw_conv_small_ragged(merged, Pf[3], Pf[4], nxt, Bg, nC, nB, L, &fn, xu, nullptr, nullptr, nullptr, nullptr, frames,
+                                    G, stream);
+      if (rc) return rc;
+      float* t = cur;
+      cur = nxt;
+      nxt = t;
     }
-    srf_norm in{slot(s0), Pu[2], Pu[3], Pu[4]};
-    rc = srf_pyramid_ragged(y1, merged, &in, pw, pb, pg, pbe, Bt, nC, L, D, ws + p->off_pyr, slot(s0 + 1 + D), frames, stream);
-    if (rc) return rc;
-    const float* const* Pf = Pu + 5 + 4 * D;
-    srf_norm fn{slot(s0 + 1 + D), Pf[0], Pf[1], Pf[2]};
-    if (i + 1 < U) {   // res_conv of this block + proj_1x1 of the next one
-      const int pn = pu_index + p->p_block_stride;
-      rc = srf_pw_conv_pair_ragged(merged, packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, &fn, cur, packed(pn), P[pn + 1], y1,
-                                   slot(1 + (i + 1) * p->slots_per_block), Bt, nC, nB, nC, L, frames, stream);
-    } else {
-      rc = srf_pw_conv_packed_ragged(merged, Pf[3], packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, Bt, nC, nB, L, &fn, cur, nullptr,
-                                     0, nullptr, 0, frames, stream);
+  } else {
+    const int pu0 = p->p_block0;
+    {   // ln folded into the bottleneck, + proj_1x1 of block 0
+      srf_norm ln{slot(0), P[1], P[2], nullptr};
+      rc = srf_pw_conv_pair_ragged(enc, packed(3), P[4], cur, &ln, nullptr, packed(pu0), P[pu0 + 1], y1, slot(1), Bt, N, nB, nC, L,
+                                   frames, stream);
+      if (rc) return rc;
     }
-    if (rc) return rc;
-    float* t = cur;
-    cur = nxt;
-    nxt = t;
+    for (int i = 0; i < U; ++i) {
+      const int pu_index = pu0 + i * p->p_block_stride;
+      const float* const* Pu = P + pu_index;
+      const int s0 = 1 + i * p->slots_per_block;
+      const float *pw[SRF_MAX_DEPTH], *pb[SRF_MAX_DEPTH], *pg[SRF_MAX_DEPTH], *pbe[SRF_MAX_DEPTH];
+      for (int k = 0; k < D; ++k) {
+        const float* const* Pk = Pu + 5 + 4 * k;
+        pw[k] = Pk[0];
+        pb[k] = Pk[1];
+        pg[k] = Pk[2];
+        pbe[k] = Pk[3];
+      }
+      srf_norm in{slot(s0), Pu[2], Pu[3], Pu[4]};
+      rc = srf_pyramid_ragged(y1, merged, &in, pw, pb, pg, pbe, Bt, nC, L, D, ws + p->off_pyr, slot(s0 + 1 + D), frames, stream);
+      if (rc) return rc;
+      const float* const* Pf = Pu + 5 + 4 * D;
+      srf_norm fn{slot(s0 + 1 + D), Pf[0], Pf[1], Pf[2]};
+      if (i + 1 < U) {   // res_conv of this block + proj_1x1 of the next one
+        const int pn = pu_index + p->p_block_stride;
+        rc = srf_pw_conv_pair_ragged(merged, packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, &fn, cur, packed(pn), P[pn + 1], y1,
+                                     slot(1 + (i + 1) * p->slots_per_block), Bt, nC, nB, nC, L, frames, stream);
+      } else {
+        rc = srf_pw_conv_packed_ragged(merged, Pf[3], packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, Bt, nC, nB, L, &fn, cur, nullptr,
+                                       0, nullptr, 0, frames, stream);
+      }
+      if (rc) return rc;
+      float* t = cur;
+      cur = nxt;
+      nxt = t;
+    }
   }
   // ---- tail: the uniform mask + decoder GEMM over every column (the block stream is unspecified past an example's end, and so
   // are the partial frames it makes there), then the ragged overlap-add, which reads the example's own frames only

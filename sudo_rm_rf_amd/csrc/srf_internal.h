@@ -22,6 +22,9 @@ __device__ __forceinline__ int srf_frames2_of(int) { return 0; }
 template <typename... R>
 __device__ __forceinline__ int srf_frames_of(int g, const SrfFrames& f, const R&...) { return f.n[g]; }
 __device__ __forceinline__ int srf_frames2_of(int g, const SrfFrames&, const SrfFrames& f2) { return f2.n[g]; }
+// Kernels that run over FOLDED rows (GroupComm: batch x groups) take (SrfFrames, int rows_per_example): the table stays one
+// entry per example and row r (wave-uniform) belongs to example r / rows_per_example (the Improved model passes 1)
+__device__ __forceinline__ int srf_frames_of(int row, const SrfFrames& f, int rows_per_example) { return f.n[row / rows_per_example]; }
 // checks frames[0 .. groups) against the row stride L and fills the table; `what` names the caller in the error string
 int srf_frames_table(const char* what, const int* frames, int groups, int L, SrfFrames* out);
 
@@ -95,6 +98,7 @@ int srf_x3w_pack3_launch(const float* const* w, char* const* dst, const int* Cou
 size_t srf_x3p_packed_bytes(int Cout, int Cin);
 bool srf_x3f_supported(int Bt, int K1, int C2, int L);
 bool srf_pw_small_supported(int Cin, int Cout, int L);
+bool srf_pw_small_ragged_supported(int Cin, int Cout, int L);   // the shapes its ragged forms are built for
 
 // ---- srf_pwconv_wgrad.hip: this thread's weight-gradient GEMMs fold their partial sums in a fixed order (no atomic split)
 void srf_pw_wgrad_ordered(bool on);

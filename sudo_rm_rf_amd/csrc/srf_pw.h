@@ -74,7 +74,9 @@ bool srf_pw_w4_wanted(const PwArgs& a);
 int srf_pw_x3w_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st, const SrfFrames* frames = nullptr);
 int srf_pw_x3p_launch(const PwArgs& a, const char* wpack, int pro, hipStream_t st);   // its paired-block form (srf_pwconv_x3p.hip)
 bool srf_x3p_supported(const PwArgs& a, int pro);
-int srf_pw_small_launch(const PwArgs& a, hipStream_t st);
+// the thin-shape kernel (srf_pwconv_small.hip); frames: null = the uniform kernels, else its ragged forms over folded rows
+// (a.Bt rows, rows_per_example of them per table entry)
+int srf_pw_small_launch(const PwArgs& a, hipStream_t st, const SrfFrames* frames = nullptr, int rows_per_example = 1);
 // the fused pair (srf_pwconv_x3f.hip); frames: null = the uniform kernels, else its ragged form (bf16 parts, pro 1 / 2)
 int srf_pw_x3f_launch(const PwPairArgs& a, int pro, hipStream_t st, bool f16 = false, const SrfFrames* frames = nullptr);
 // K5: mask GEMM + decoder contraction in one launch (srf_pwconv_x3w.hip, EPI 4)

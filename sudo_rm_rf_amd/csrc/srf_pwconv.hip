@@ -533,6 +533,54 @@ int srf_pw_conv_preadd(const float* x, const float* q, const srf_norm* qnorm, fl
   return srf_pw_small_launch(a, st);
 }
 
+// The ragged forms of GroupComm's per-group convolutions (srf_pwconv_small.hip) over `rows` = examples * rows_per_example folded
+// rows; frames: one entry per EXAMPLE.  Two forms:
+//   pre-add (proj_1x1): pre_q / pre_norm / pre_u given, no in_norm, no residual, out_sums required -- u = x + GlobLN(pre_q)
+//     (count Cin * frames) written for the example's own columns, y = W u + bias exact zeros past them, statistics of y;
+//   norm + PReLU + residual (res_conv): in_norm with sums and prelu, residual, no out_sums -- y written for the example's own
+//     columns only (the block stream).
+extern "C" int srf_pw_conv_small_ragged_supported(int Cin, int Cout, int L) {
+  return srf_kernel_mode() != 1 && srf_pw_small_ragged_supported(Cin, Cout, L) ? 1 : 0;
+}
+extern "C" int srf_pw_conv_small_ragged(const float* x, const float* w, const float* bias, float* y, int rows, int Cin, int Cout,
+                                        int L, const srf_norm* in_norm, const float* residual, double* out_sums,
+                                        const float* pre_q, const srf_norm* pre_norm, float* pre_u, const int* frames,
+                                        int rows_per_example, void* stream) {
+  SRF_CHECK_ARG(rows > 0 && rows_per_example >= 1 && rows % rows_per_example == 0,
+                "srf_pw_conv_small_ragged: %d rows are not a whole number of examples of %d rows each", rows, rows_per_example);
+  const int examples = rows / rows_per_example;
+  SrfFrames fr;
+  int rc = srf_frames_table("srf_pw_conv_small_ragged", frames, examples, L, &fr);
+  if (rc) return rc;
+  for (int b = 0; b < examples; ++b)
+    SRF_CHECK_ARG(frames[b] % 4 == 0, "srf_pw_conv_small_ragged: example %d has %d frames: not a multiple of 4", b, frames[b]);
+  SRF_CHECK_ARG(x && w && bias && y, "srf_pw_conv_small_ragged: null pointer");
+  SRF_CHECK_ARG(srf_pw_conv_small_ragged_supported(Cin, Cout, L),
+                "srf_pw_conv_small_ragged: forms built: 16 -> 32 and 32 -> 16 channels, L %% 4 == 0, not kernel mode 1 (got %d -> %d, "
+                "L=%d, mode %d)", Cin, Cout, L, srf_kernel_mode());
+  const bool pre = pre_q || pre_norm || pre_u;
+  if (pre) {
+    SRF_CHECK_ARG(pre_q && pre_u && pre_norm && pre_norm->sums && pre_norm->gamma && pre_norm->beta && !pre_norm->prelu && !in_norm &&
+                      !residual && out_sums,
+                  "srf_pw_conv_small_ragged: the pre-add form takes pre_q, pre_norm (sums, gamma, beta), pre_u and out_sums, and "
+                  "neither in_norm nor residual");
+  } else {
+    SRF_CHECK_ARG(in_norm && in_norm->sums && in_norm->gamma && in_norm->beta && in_norm->prelu && residual && !out_sums,
+                  "srf_pw_conv_small_ragged: forms built: pre-add with statistics; GlobLN + PReLU with residual and without "
+                  "statistics");
+  }
+  PwArgs a = pw_args(x, w, bias, y, residual, out_sums, nullptr, 1, 0, srf_norm_dev(in_norm), rows, Cin, Cout, L);
+  if (pre) {
+    a.pre_q = pre_q;
+    a.pre_u = pre_u;
+    a.pre_nrm = srf_norm_dev(pre_norm);
+    a.pre_inv_count = 1.0 / ((double)Cin * (double)L);
+  }
+  SRF_CHECK_ALIGNED16("srf_pw_conv_small_ragged", {"in_norm.sums", a.nrm.sums}, {"pre_norm.sums", a.pre_nrm.sums}, {"x", x}, {"y", y},
+                      {"residual", residual}, {"pre_q", pre_q}, {"pre_u", pre_u});
+  return srf_pw_small_launch(a, (hipStream_t)stream, &fr, rows_per_example);
+}
+
 extern "C" size_t srf_packed_pw_weight_bytes(int Cout, int Cin) {
   if (Cout <= 0 || Cin <= 0 || !srf_x3w_shape_supported(Cin, Cout, 4)) return 0;
   return srf_x3w_packed_bytes(Cout, Cin) + srf_x3p_packed_bytes(Cout, Cin);

@@ -20,14 +20,21 @@ struct SrfVec<4> {
   typedef float type __attribute__((ext_vector_type(4)));
 };
 
-template <int CIN, int COUT, int VEC>
+// RAGGED (srf_pw_conv_small_ragged; FR = SrfFrames, int rows_per_example): L stays the row stride, folded row b belongs to
+// example b / rows_per_example and is frames[...] columns long.  Columns are independent, so nothing is masked on load; both
+// prologues' GlobLNs count CIN * frames values.  With out_sums (the pre-add proj_1x1: y has statistics and a halo reader) y is
+// selected to exact 0 from the example's end to the row stride before the store and the sums, and a wavefront wholly past
+// the end stores its zeros without a load; without (res_conv: the block stream) nothing is written there and such a
+// wavefront returns at once.  u (pre_u) is written for the example's own columns only.
+template <int CIN, int COUT, int VEC, typename... FR>
 __global__ __launch_bounds__(256) void srf_pw_small_kernel(
     PwArgs a, int wavesPerRow, int totalWaves,
     // weights / bias / affine again as noalias kernel arguments: only then are they provably not
     // clobbered by the stores to y and fetched with scalar loads (SGPR operands) instead of VMEM
     const float* __restrict__ wgt, const float* __restrict__ bias, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ pre_gamma, const float* __restrict__ pre_beta) {
+    const float* __restrict__ beta, const float* __restrict__ pre_gamma, const float* __restrict__ pre_beta, FR... fr) {
   typedef typename SrfVec<VEC>::type vecf;
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   constexpr int MC = 4;   // outputs per pass: MC*CIN weights must fit the SGPR file
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -37,11 +44,26 @@ __global__ __launch_bounds__(256) void srf_pw_small_kernel(
   const int l = (wr * 64 + lane) * VEC;
   const bool valid = l < a.L;          // L % VEC == 0: a vector is entirely inside or outside the row
   const int lc = valid ? l : 0;        // clamped: loads stay unconditional
+  bool live = valid;                   // inside the example (frames % VEC == 0: a vector is entirely inside or outside)
+  double inv_count = a.inv_count, pre_inv_count = a.pre_inv_count;
+  if constexpr (RAGGED) {
+    const int Lb = srf_frames_of((int)b, fr...);
+    if (wr * 64 * VEC >= Lb) {         // wave-uniform: this wavefront's columns all lie past the example's end
+      if (a.out_sums && valid) {
+        float* yb = a.y + (size_t)b * COUT * a.L + l;
+#pragma unroll 4
+        for (int m = 0; m < COUT; ++m) *reinterpret_cast<vecf*>(yb + (size_t)m * a.L) = (vecf)(0.f);
+      }
+      return;
+    }
+    live = l < Lb;
+    inv_count = pre_inv_count = 1.0 / ((double)CIN * (double)Lb);
+  }
 
   const bool has_norm = a.nrm.sums != nullptr;
   const bool act = a.nrm.prelu != nullptr;
   float mean = 0.f, rstd = 1.f;
-  if (has_norm) srf_finalize_stats(a.nrm.sums, b, a.inv_count, mean, rstd);
+  if (has_norm) srf_finalize_stats(a.nrm.sums, b, inv_count, mean, rstd);
   const float slope = act ? a.nrm.prelu[0] : 1.f;
 
   const float* xb = a.x + (size_t)b * CIN * a.L + lc;
@@ -55,7 +77,7 @@ __global__ __launch_bounds__(256) void srf_pw_small_kernel(
     // then the add), so the fused forward is bitwise the unfused one -- and u goes out once, for the block's residual.
     // Saves the separate kernel's launch and one read of the [Bt, B, L] tensor per block.
     float pm, pr;
-    srf_finalize_stats(a.pre_nrm.sums, b, a.pre_inv_count, pm, pr);
+    srf_finalize_stats(a.pre_nrm.sums, b, pre_inv_count, pm, pr);
     const float* qb = a.pre_q + (size_t)b * CIN * a.L + lc;
     float* ub = a.pre_u + (size_t)b * CIN * a.L + lc;
 #pragma unroll
@@ -65,7 +87,7 @@ __global__ __launch_bounds__(256) void srf_pw_small_kernel(
       const float sh = pre_beta[k] - pm * sc;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) x[k][v] = x[k][v] + fmaf(qv[v], sc, sh);
-      if (valid) *reinterpret_cast<vecf*>(ub + (size_t)k * a.L) = x[k];
+      if (live) *reinterpret_cast<vecf*>(ub + (size_t)k * a.L) = x[k];
     }
   }
   if (has_norm) {
@@ -84,6 +106,8 @@ __global__ __launch_bounds__(256) void srf_pw_small_kernel(
       for (int v = 0; v < VEC; ++v) x[k][v] = srf_prelu(x[k][v], slope);
   }
 
+  // stored: every column of the row (uniform; RAGGED with statistics: zeros past the end) or the example's own (RAGGED without)
+  const bool st_ok = RAGGED ? (a.out_sums ? valid : live) : valid;
   float s = 0.f, q = 0.f;
   const size_t ybase = (size_t)b * COUT * a.L + lc;
   // not unrolled: a fully unrolled body lets the scheduler hoist all Cin*Cout scalar weight loads to
@@ -107,7 +131,8 @@ __global__ __launch_bounds__(256) void srf_pw_small_kernel(
       const size_t idx = ybase + (size_t)(m0 + i) * a.L;
       vecf o = acc[i] + bias[m0 + i];
       if (a.residual) o += __builtin_nontemporal_load(reinterpret_cast<const vecf*>(a.residual + idx));
-      if (valid) {
+      if constexpr (RAGGED) o = live ? o : (vecf)(0.f);
+      if (st_ok) {
         *reinterpret_cast<vecf*>(a.y + idx) = o;
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
@@ -153,8 +178,30 @@ static void srf_pw_small_cout(const PwArgs& a, hipStream_t st) {
   }
 }
 
-int srf_pw_small_launch(const PwArgs& a, hipStream_t st) {
+template <int CIN, int COUT>
+static void srf_pw_small_go_ragged(const PwArgs& a, hipStream_t st, const SrfFrames& fr, int rpe) {
+  constexpr int VEC = CIN <= 16 ? 4 : 2;
+  const int wavesPerRow = (a.L / VEC + 63) / 64;
+  const long total = (long)a.Bt * wavesPerRow;
+  hipLaunchKernelGGL((srf_pw_small_kernel<CIN, COUT, VEC, SrfFrames, int>), dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, a,
+                     wavesPerRow, (int)total, a.w, a.bias, a.nrm.gamma, a.nrm.beta, a.pre_nrm.gamma, a.pre_nrm.beta, fr, rpe);
+}
+
+bool srf_pw_small_ragged_supported(int Cin, int Cout, int L) {
+  return ((Cin == 16 && Cout == 32) || (Cin == 32 && Cout == 16)) && L % 4 == 0;
+}
+
+int srf_pw_small_launch(const PwArgs& a, hipStream_t st, const SrfFrames* frames, int rows_per_example) {
   SRF_CHECK_ARG((long)a.Bt * ((a.L / 2 + 63) / 64) < (1L << 31), "srf_pw_conv: too many rows");
+  if (frames) {      // the ragged forms: the two per-group shapes of the 256 / 512-channel GroupComm model with 16 groups
+    SRF_CHECK_ARG(srf_pw_small_ragged_supported(a.Cin, a.Cout, a.L) && rows_per_example >= 1,
+                  "srf_pw_conv_small_ragged: forms built: 16 -> 32 and 32 -> 16 channels, L %% 4 == 0 (got %d -> %d, L=%d)", a.Cin,
+                  a.Cout, a.L);
+    if (a.Cin == 16) srf_pw_small_go_ragged<16, 32>(a, st, *frames, rows_per_example);
+    else srf_pw_small_go_ragged<32, 16>(a, st, *frames, rows_per_example);
+    SRF_CHECK_LAUNCH("pw_conv_small_ragged", st);
+    return SRF_OK;
+  }
   switch (a.Cin) {
     case 8: srf_pw_small_cout<8>(a, st); break;
     case 16: srf_pw_small_cout<16>(a, st); break;

@@ -24,5 +24,7 @@ struct PyrRegArgs {
                        // re-computes d_0 from y1)
 };
 
-// frames: null = the uniform kernels; else the ragged forms (pass 1 always persistent, no level outputs)
-int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st, const SrfFrames* frames = nullptr);
+// frames: null = the uniform kernels; else the ragged forms (pass 1 always persistent, no level outputs), the table holding one
+// entry per rows_per_example GROUPS (GroupComm folds its groups into the batch: G groups per example; Improved: 1)
+int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st, const SrfFrames* frames = nullptr,
+                           int rows_per_example = 1);

@@ -609,7 +609,8 @@ struct PyrFinArgs {
 #define SRF_FIN_CPT 8   // channels per thread (C <= 256 * 8)
 // CPT = channels per thread (C <= 256 * CPT): 2 covers the published models (C = 512) and keeps the whole example's
 // moments in registers; 8 is the general fallback (moments fetched level by level).
-// RAGGED (srf_pyramid_ragged): the example's own length frames[g] replaces L in the three places the edge algebra uses it --
+// RAGGED (srf_pyramid_ragged; FR = SrfFrames, int groups_per_example): the example's own length frames[g / groups_per_example]
+// replaces L in the three places the edge algebra uses it --
 // the count of interior positions (L_k - 3), the position of the last edge (pass 1 took C_k[last] there) and the statistics'
 // count C * L_k -- and in the count of the input norm.
 template <int CPT, typename... FR>
@@ -754,12 +755,13 @@ static size_t pyr_lds_bytes(int L, int D) {
   return sizeof(float) * ((size_t)L + 8 + sizeA) + sizeof(double) * (4 * SRF_MAX_DEPTH * 2 + 8);
 }
 
-static void srf_pyramid_finalize_launch(const PyrFinArgs& f, int groups, int C, hipStream_t st, const SrfFrames* frames = nullptr) {
+static void srf_pyramid_finalize_launch(const PyrFinArgs& f, int groups, int C, hipStream_t st, const SrfFrames* frames = nullptr,
+                                        int rpe = 1) {
   if (frames && C <= 512)
-    hipLaunchKernelGGL((srf_pyramid_finalize_kernel<2, SrfFrames>), dim3((unsigned)groups), dim3(256), 0, st, f, *frames);
+    hipLaunchKernelGGL((srf_pyramid_finalize_kernel<2, SrfFrames, int>), dim3((unsigned)groups), dim3(256), 0, st, f, *frames, rpe);
   else if (frames)
-    hipLaunchKernelGGL((srf_pyramid_finalize_kernel<SRF_FIN_CPT, SrfFrames>), dim3((unsigned)groups), dim3(256), 0, st, f,
-                       *frames);
+    hipLaunchKernelGGL((srf_pyramid_finalize_kernel<SRF_FIN_CPT, SrfFrames, int>), dim3((unsigned)groups), dim3(256), 0, st, f,
+                       *frames, rpe);
   else if (C <= 512)
     hipLaunchKernelGGL(srf_pyramid_finalize_kernel<2>, dim3((unsigned)groups), dim3(256), 0, st, f);
   else
@@ -836,13 +838,13 @@ extern "C" int srf_pyramid(const float* y1, float* merged, const srf_norm* in_no
 static int pyramid_run(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
                        const float* const* bias, const float* const* gamma, const float* const* beta, int groups, int C,
                        int L, int D, void* scratch, double* out_sums, float* const* lv_out, double* const* lv_sums,
-                       void* stream, const SrfFrames* frames);
+                       void* stream, const SrfFrames* frames, int rpe);
 int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
                      const float* const* bias, const float* const* gamma, const float* const* beta, int groups, int C,
                      int L, int D, void* scratch, double* out_sums, float* const* lv_out, double* const* lv_sums,
                      void* stream) {
   return pyramid_run(y1, merged, in_norm, w, bias, gamma, beta, groups, C, L, D, scratch, out_sums, lv_out, lv_sums, stream,
-                     nullptr);
+                     nullptr, 1);
 }
 
 // The length an example of a ragged batch may have: what the register-resident kernels and the finalize step's edge algebra
@@ -856,22 +858,34 @@ extern "C" int srf_pyramid_ragged_frames_ok(int frames, int L, int D) {
 extern "C" int srf_pyramid_ragged(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
                                   const float* const* bias, const float* const* gamma, const float* const* beta, int groups,
                                   int C, int L, int D, void* scratch, double* out_sums, const int* frames, void* stream) {
+  return srf_pyramid_ragged_rows(y1, merged, in_norm, w, bias, gamma, beta, groups, C, L, D, scratch, out_sums, frames, 1, stream);
+}
+
+// groups = examples * groups_per_example folded rows of C channels each; frames: one entry per EXAMPLE
+extern "C" int srf_pyramid_ragged_rows(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
+                                       const float* const* bias, const float* const* gamma, const float* const* beta, int groups,
+                                       int C, int L, int D, void* scratch, double* out_sums, const int* frames,
+                                       int groups_per_example, void* stream) {
+  SRF_CHECK_ARG(groups_per_example >= 1 && groups % groups_per_example == 0,
+                "srf_pyramid_ragged: %d groups are not a whole number of examples of %d groups each", groups, groups_per_example);
+  const int examples = groups / groups_per_example;
   SrfFrames fr;
-  int rc = srf_frames_table("srf_pyramid_ragged", frames, groups, L, &fr);
+  int rc = srf_frames_table("srf_pyramid_ragged", frames, examples, L, &fr);
   if (rc) return rc;
   SRF_CHECK_ARG(srf_pyramid_supported(C, L, D) && !srf_dbg(SRF_DBG_PYR_NO_REG) && srf_pyramid_reg_supported(L, D),
                 "srf_pyramid_ragged: the register-resident pyramid does not take C=%d L=%d D=%d", C, L, D);
-  for (int g = 0; g < groups; ++g)
+  for (int g = 0; g < examples; ++g)
     SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(frames[g], L, D),
                   "srf_pyramid_ragged: example %d has %d frames: too short for the pyramid's edge algebra or off its chunk grid "
                   "(D=%d)", g, frames[g], D);
-  return pyramid_run(y1, merged, in_norm, w, bias, gamma, beta, groups, C, L, D, scratch, out_sums, nullptr, nullptr, stream, &fr);
+  return pyramid_run(y1, merged, in_norm, w, bias, gamma, beta, groups, C, L, D, scratch, out_sums, nullptr, nullptr, stream, &fr,
+                     groups_per_example);
 }
 
 static int pyramid_run(const float* y1, float* merged, const srf_norm* in_norm, const float* const* w,
                        const float* const* bias, const float* const* gamma, const float* const* beta, int groups, int C,
                        int L, int D, void* scratch, double* out_sums, float* const* lv_out, double* const* lv_sums,
-                       void* stream, const SrfFrames* frames) {
+                       void* stream, const SrfFrames* frames, int rpe) {
   SRF_CHECK_ARG((lv_out == nullptr) == (lv_sums == nullptr), "srf_pyramid: level outputs and level sums come together");
   SRF_CHECK_ARG(y1 && merged && w && bias && gamma && beta && scratch, "srf_pyramid: null pointer");
   SRF_CHECK_ARG(groups > 0 && C > 0 && L > 0, "srf_pyramid: bad sizes");
@@ -949,13 +963,13 @@ static int pyramid_run(const float* y1, float* merged, const srf_norm* in_norm, 
       }
     }
     SRF_CHECK_ARG(merged != y1, "srf_pyramid: merged must not alias y1 (pass 2 re-reads y1 with halos)");
-    int rc = srf_pyramid_reg_launch(r, true, rows, st, frames);
+    int rc = srf_pyramid_reg_launch(r, true, rows, st, frames, rpe);
     if (rc) return rc;
     if (frames || !srf_dbg(SRF_DBG_PYR_PASS1_NONPERSISTENT)) f.in_sums = a.in_norm.sums;
-    srf_pyramid_finalize_launch(f, groups, C, st, frames);
+    srf_pyramid_finalize_launch(f, groups, C, st, frames, rpe);
     if (frames) SRF_CHECK_LAUNCH("pyramid_finalize_ragged", st);
     else SRF_CHECK_LAUNCH("pyramid_finalize", st);
-    return srf_pyramid_reg_launch(r, false, rows, st, frames);
+    return srf_pyramid_reg_launch(r, false, rows, st, frames, rpe);
   }
   SRF_CHECK_ARG(!frames, "srf_pyramid: internal: the ragged form exists for the register-resident kernels only");
   PyrTile tile;

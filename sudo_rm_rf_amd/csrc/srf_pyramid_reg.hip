@@ -146,7 +146,8 @@ __device__ __forceinline__ void srf_pyr_store_level(float* dst, const float (&v)
 // SAVE (pass 2 only): also write every level's raw conv output d_k -- what the training backward needs -- so the
 // training forward is the same two fused passes instead of D depthwise kernels + a merge kernel (7.75 -> 4.94 C*L of
 // traffic per block).
-// RAGGED (srf_pyramid_ragged): L stays the row STRIDE, the row LENGTH of example g is frames[g] (a multiple of CH, at most L).
+// RAGGED (srf_pyramid_ragged; FR = SrfFrames, int groups_per_example): L stays the row STRIDE, the row LENGTH of group g is
+// frames[g / groups_per_example] (a multiple of CH, at most L).
 // Chunks at or past it are zero padding exactly as chunks past L are in the uniform form: loads are clamped to the example's
 // last chunk, the edge moments sit at its own last position, the proj statistics count C * frames[g] values, pass 1 walks only
 // the tiles that reach into the example, and pass 2 writes zeros from frames[g] to L (a tile wholly past the end loads nothing).
@@ -462,7 +463,7 @@ bool srf_pyramid_reg_supported(int L, int D) {
 }
 
 // moments / finalize / merge launches are driven by srf_pyramid() in srf_pyramid.hip
-int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st, const SrfFrames* frames) {
+int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st, const SrfFrames* frames, int rpe) {
   const int CH = a.D <= 5 ? 16 : 32;
   const int nchunks = a.L / CH;
   a.tiles = (nchunks + 59) / 60;
@@ -505,10 +506,11 @@ int srf_pyramid_reg_launch(PyrRegArgs a, bool moments, long rows, hipStream_t st
   if (frames) {
     SRF_CHECK_ARG(!save, "srf_pyramid: the ragged form keeps no level outputs");
     const SrfFrames& fr = *frames;
-    if (CH == 16 && moments) hipLaunchKernelGGL((srf_pyramid_reg_kernel<true, 16, true, false, SrfFrames>), grid, dim3(256), 0, st, a, fr);
-    else if (CH == 16) hipLaunchKernelGGL((srf_pyramid_reg_kernel<false, 16, false, false, SrfFrames>), grid, dim3(256), 0, st, a, fr);
-    else if (moments) hipLaunchKernelGGL((srf_pyramid_reg_kernel<true, 32, true, false, SrfFrames>), grid, dim3(256), 0, st, a, fr);
-    else hipLaunchKernelGGL((srf_pyramid_reg_kernel<false, 32, false, false, SrfFrames>), grid, dim3(256), 0, st, a, fr);
+    SRF_CHECK_ARG(rpe >= 1, "srf_pyramid: internal: rows per example");
+    if (CH == 16 && moments) hipLaunchKernelGGL((srf_pyramid_reg_kernel<true, 16, true, false, SrfFrames, int>), grid, dim3(256), 0, st, a, fr, rpe);
+    else if (CH == 16) hipLaunchKernelGGL((srf_pyramid_reg_kernel<false, 16, false, false, SrfFrames, int>), grid, dim3(256), 0, st, a, fr, rpe);
+    else if (moments) hipLaunchKernelGGL((srf_pyramid_reg_kernel<true, 32, true, false, SrfFrames, int>), grid, dim3(256), 0, st, a, fr, rpe);
+    else hipLaunchKernelGGL((srf_pyramid_reg_kernel<false, 32, false, false, SrfFrames, int>), grid, dim3(256), 0, st, a, fr, rpe);
     SRF_CHECK_LAUNCH(moments ? "pyramid_moments_ragged" : "pyramid_merge_ragged", st);
     return SRF_OK;
   }

@@ -10,7 +10,7 @@
 // spilled (n*H MACs are cheaper than 4*H bytes of traffic per group and column).  The q-half of Wo
 // is group-independent and folded into a per-column vector r once.
 // The output is the PRE-norm tensor; {sum,sumsq} per (batch, group) feed TAC_norm (GlobLN).
-#include "srf_common.h"
+#include "srf_internal.h"
 
 struct TacArgs {
   const float* x;
@@ -365,6 +365,11 @@ static bool srf_tac_lanes_launch(const TacArgs& a, int n, int Bt, hipStream_t st
 // 8 (r >> 2) + 4 (lane >> 5)) becomes the next GEMM's B operand (lane = column, 8 consecutive k) with four
 // v_permlane32_swap_b32 per 8 rows -- no LDS round trip.  The A fragments of Wm / Wo live in LDS (24 KB, built once per block),
 // Wi's in registers.  One 32-column tile per wavefront, four per block: the hardware balances 3 200 tiles.
+// RAGGED (srf_tac_ragged; FR = one SrfFrames): L stays the row stride, example b is frames[b] columns long.  TAC is pointwise in
+// time -- the group mean is per time step and the MFMAs' B columns are independent -- so nothing is masked on load (x past the
+// end may hold anything, NaN included); q carries GlobLN statistics, so columns >= frames[b] are selected to exact 0 before
+// the store and the sums, per column (a tile may straddle the end).  A tile wholly past the end stores its zeros without a
+// load of x or an MFMA -- after the block's barrier.
 typedef _Float16 tac_f16x8 __attribute__((ext_vector_type(8)));
 typedef float tac_f32x16 __attribute__((ext_vector_type(16)));
 constexpr float TAC_WS = 16.f;
@@ -396,8 +401,10 @@ __device__ __forceinline__ void tac_c_to_b(const float (&c)[8], float (&v)[8]) {
   }
 }
 
-__global__ __launch_bounds__(256) void srf_tac_mfma_kernel(TacArgs a, int tiles_per_row, int total_tiles) {
+template <typename... FR>
+__global__ __launch_bounds__(256) void srf_tac_mfma_kernel(TacArgs a, int tiles_per_row, int total_tiles, FR... fr) {
   constexpr int NN = 16, HH = 48, G = 16;
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   __shared__ tac_f16x8 s_frag[24][64];     // A fragments {hi, lo}: Wm (2 M-blocks x 3 k-steps), Wo[:, H:] (3), Wo[:, :H] (3)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform for the compiler: buffer descriptors in SGPRs)
@@ -465,6 +472,17 @@ __global__ __launch_bounds__(256) void srf_tac_mfma_kernel(TacArgs a, int tiles_
   __amdgpu_buffer_rsrc_t qrs = __builtin_amdgcn_make_buffer_rsrc(a.q + (size_t)b * G * NN * L, 0, G * NN * L * 4, 0x00020000);
   const int x_vo = valid ? (8 * h * L + col) * 4 : 0x7ffffff0;     // (out of range: the load returns 0, the store is dropped)
   const int q_vo = valid ? (4 * h * L + col) * 4 : 0x7ffffff0;
+  int Lb = L;                      // (RAGGED: the example's own length; a column at or past it is stored as 0)
+  if constexpr (RAGGED) {
+    Lb = srf_frames_of(b, fr...);
+    if (l0 >= Lb) {                // wave-uniform: the whole tile lies past the example's end
+      for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+          __builtin_amdgcn_raw_buffer_store_b32(0u, qrs, q_vo, (g * NN + (r & 3) + 8 * (r >> 2)) * L * 4, 0);
+      return;
+    }
+  }
 
   // x_g's B fragment: 8 dword loads (rows 8 h + e of group g at this lane's column), requested one group ahead
   struct XRaw {
@@ -573,8 +591,9 @@ __global__ __launch_bounds__(256) void srf_tac_mfma_kernel(TacArgs a, int tiles_
 #pragma unroll
     for (int r = 0; r < 8; ++r) {                    // rows (r & 3) + 8 (r >> 2) + 4 h = 0 .. 15
       const float v = srf_prelu(o[r] * (1.f / (TAC_WS * TAC_WS)), ao);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), qrs, q_vo, (g * NN + (r & 3) + 8 * (r >> 2)) * L * 4, 0);
-      const float vz = valid ? v : 0.f;
+      if constexpr (!RAGGED) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), qrs, q_vo, (g * NN + (r & 3) + 8 * (r >> 2)) * L * 4, 0);
+      const float vz = (RAGGED ? col < Lb : valid) ? v : 0.f;
+      if constexpr (RAGGED) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(vz), qrs, q_vo, (g * NN + (r & 3) + 8 * (r >> 2)) * L * 4, 0);
       ss += vz;
       sq = fmaf(vz, vz, sq);
     }
@@ -624,7 +643,7 @@ extern "C" int srf_tac(const float* x, float* q, const float* const* params, int
     const long total = (long)Bt * tiles_per_row;
     if (total < (1L << 30)) {
       const long blocks = (total + 3) / 4;
-      hipLaunchKernelGGL(srf_tac_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, tiles_per_row, (int)total);
+      hipLaunchKernelGGL(srf_tac_mfma_kernel<>, dim3((unsigned)blocks), dim3(256), 0, st, a, tiles_per_row, (int)total);
       SRF_CHECK_LAUNCH("tac_mfma", st);
       return SRF_OK;
     }
@@ -644,6 +663,45 @@ extern "C" int srf_tac(const float* x, float* q, const float* const* params, int
       return SRF_EINVAL;
   }
   SRF_CHECK_LAUNCH("tac", st);
+  return SRF_OK;
+}
+
+// The ragged form: the MFMA kernel only (n = 16, G = 16), everything else is refused before any launch.
+extern "C" int srf_tac_ragged(const float* x, float* q, const float* const* params, int Bt, int G, int n, int H, int L,
+                              double* out_sums, const int* frames, void* stream) {
+  SrfFrames fr;
+  int rc = srf_frames_table("srf_tac_ragged", frames, Bt, L, &fr);
+  if (rc) return rc;
+  SRF_CHECK_ARG(x && q && params, "srf_tac_ragged: null pointer");
+  SRF_CHECK_ARG(G > 0 && n > 0 && L > 0, "srf_tac_ragged: bad sizes");
+  SRF_CHECK_ARG(n == 16 && G == 16 && H == 48,
+                "srf_tac_ragged: only the MFMA kernel has a ragged form (n = 16, H = 48, G = 16; got n=%d H=%d G=%d)", n, H, G);
+  for (int i = 0; i < 9; ++i) SRF_CHECK_ARG(params[i] != nullptr, "srf_tac_ragged: null parameter %d", i);
+  SRF_CHECK_ARG(srf_kernel_mode() != 1 && !srf_dbg(SRF_DBG_TAC_ONE_STEP_PER_LANE | SRF_DBG_TAC_VALU | SRF_DBG_TAC_GENERIC | SRF_DBG_TAC_LANES_4TILES),
+                "srf_tac_ragged: the MFMA kernel is switched off (kernel mode %d / debug flags)", srf_kernel_mode());
+  SRF_CHECK_ARG((long)G * n * L * 4 < (1L << 31), "srf_tac_ragged: L=%d beyond the reach of the kernel's 32-bit offsets", L);
+  SRF_CHECK_ALIGNED16("srf_tac_ragged", {"x", x}, {"q", q});
+  TacArgs a;
+  a.x = x;
+  a.q = q;
+  a.wi = params[0];
+  a.bi = params[1];
+  a.ai = params[2];
+  a.wm = params[3];
+  a.bm = params[4];
+  a.am = params[5];
+  a.wo = params[6];
+  a.bo = params[7];
+  a.ao = params[8];
+  a.out_sums = out_sums;
+  a.G = G;
+  a.L = L;
+  const int tiles_per_row = (L + 31) / 32;
+  const long total = (long)Bt * tiles_per_row;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((srf_tac_mfma_kernel<SrfFrames>), dim3((unsigned)((total + 3) / 4)), dim3(256), 0, st, a, tiles_per_row,
+                     (int)total, fr);
+  SRF_CHECK_LAUNCH("tac_mfma_ragged", st);
   return SRF_OK;
 }
 

@@ -134,6 +134,13 @@ class GroupCommSudoRmRf(nn.Module):
     def forward(self, input_wav):
         return self._engine().run(self, input_wav, self.in_audio_channels)
 
+    def forward_ragged(self, input_wav, lengths):
+        """Unequal-length utterances in ONE forward (one audio channel, 16 groups of 16 channels: pipeline.ragged_route):
+        input_wav [batch, 1, time] padded rows on the GPU, lengths a list or CPU int tensor.  Row b of the result equals
+        self(input_wav[b:b+1, :, :lengths[b]]) up to lengths[b] -- the example padded to its own length, every GlobLN (ln,
+        TAC's per group, the pyramid's) over its own frames -- and is exactly zero past it.  eval() / no_grad only."""
+        return self._engine().run_ragged(self, input_wav, lengths)
+
     def pad_to_appropriate_length(self, x):
         """Kept for API parity (reference :324-335); the HIP path never materialises the padding."""
         input_length = x.shape[-1]

@@ -56,13 +56,17 @@ def ragged_batches(lengths, max_batch=32, bucket=BUCKET):
 
 def ragged_route(model, length=None):
     """Where separate_list sends an utterance, decided from the model's configuration alone (no GPU): "ragged" = a candidate
-    for the ragged batch (the Improved model with one input channel, K = 21, 256 bottleneck channels; with `length`, also long
-    enough for the fused pyramid to take it as an example of its own), "single" = the per-example path (GroupComm and causal
-    models, other configurations, too-short utterances).  A candidate batch still falls back as a whole when the plan of its
-    (batch, T) is refused (srf_plan_ragged_supported: small shapes)."""
-    if type(model).__name__ != "SuDORMRF" or not hasattr(model, "forward_ragged"):
+    for the ragged batch (the Improved model with one input channel, K = 21, 256 bottleneck channels; the GroupComm model with
+    one input channel, K = 21, 16 groups of 16 -> 32 channels, i.e. 256 / 512 channels; with `length`, also long enough for
+    the fused pyramid to take it as an example of its own), "single" = the per-example path (the causal model, other
+    configurations, too-short utterances).  A candidate batch still falls back as a whole when the plan of its (batch, T) is
+    refused (srf_plan_ragged_supported: small shapes)."""
+    kind = type(model).__name__
+    if kind not in ("SuDORMRF", "GroupCommSudoRmRf") or not hasattr(model, "forward_ragged"):
         return "single"
     if getattr(model, "enc_kernel_size", 0) != 21 or getattr(model, "out_channels", 0) != 256:
+        return "single"
+    if kind == "GroupCommSudoRmRf" and (model.in_audio_channels != 1 or model._group_size() != 16 or model.in_channels != 512):
         return "single"
     if length is not None:
         D = model.upsampling_depth
@@ -78,7 +82,7 @@ def separate_list(model, mixtures, mixture_consistency=None, max_batch=32):
     """separate() over a list of utterances of unequal length: mixtures = tensors [T_i] or [1, T_i] on the model's MI355X;
     returns the estimates [num_sources, T_i] in the caller's order.  The README recipe per utterance (mean / std over its own
     samples, forward, rescale; mixture consistency as in separate()), with the forwards of a length-sorted batch run as ONE
-    ragged forward (SuDORMRF.forward_ragged) where the model and the batch allow it, and through separate() one by one where
+    ragged forward (forward_ragged of the Improved and the GroupComm model) where the model and the batch allow it, and through separate() one by one where
     they do not -- so the answer is always the per-utterance one."""
     mixes = []
     for m in mixtures:

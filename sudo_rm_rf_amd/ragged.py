@@ -50,22 +50,24 @@ def encoder(wav, weight, L, lengths, frames, sums=None):
     return out
 
 
-def pyramid(y1, in_sums, in_gamma, in_beta, in_prelu, weights, biases, gammas, betas, frames, out_sums=None):
-    """srf_pyramid_ragged: y1 [groups,C,L] (row g valid up to frames[g]) -> merged [groups,C,L], zeros from frames[g] on."""
+def pyramid(y1, in_sums, in_gamma, in_beta, in_prelu, weights, biases, gammas, betas, frames, out_sums=None, rows_per_example=1):
+    """srf_pyramid_ragged: y1 [groups,C,L] (row g valid up to frames[g]) -> merged [groups,C,L], zeros from frames[g] on.
+    rows_per_example > 1 (GroupComm's folded rows): groups = examples * rows_per_example GlobLN groups, `frames` holds one
+    entry per EXAMPLE and group g is frames[g // rows_per_example] long (srf_pyramid_ragged_rows)."""
     dev = _chk(y1, in_sums, in_gamma, in_beta, in_prelu, *weights, *biases, *gammas, *betas, out_sums)
     groups, Cc, L = y1.shape
     D = len(weights)
     lib = _lib.load()
     frs, n = _table(frames, "frames")
-    if n != groups:
-        raise _lib.SrfError("srf_pyramid_ragged: %d frames for %d examples" % (n, groups))
+    if n * int(rows_per_example) != groups:
+        raise _lib.SrfError("srf_pyramid_ragged: %d frames for %d examples" % (n, groups // max(1, int(rows_per_example))))
     merged = torch.empty_like(y1)
     scratch = torch.empty(lib.srf_pyramid_scratch_bytes(groups, Cc, L, D), dtype=torch.uint8, device=dev)
     arr = lambda ts: (C.c_void_p * D)(*[t.data_ptr() for t in ts])
     nrm = _lib.make_norm(in_sums, in_gamma, in_beta, in_prelu)
-    rc = lib.srf_pyramid_ragged(_lib.ptr(y1), _lib.ptr(merged), C.byref(nrm), arr(weights), arr(biases), arr(gammas),
-                                arr(betas), groups, Cc, L, D, _lib.ptr(scratch), _lib.ptr(out_sums), frs,
-                                _lib.current_stream(dev))
+    rc = lib.srf_pyramid_ragged_rows(_lib.ptr(y1), _lib.ptr(merged), C.byref(nrm), arr(weights), arr(biases), arr(gammas),
+                                     arr(betas), groups, Cc, L, D, _lib.ptr(scratch), _lib.ptr(out_sums), frs,
+                                     int(rows_per_example), _lib.current_stream(dev))
     _lib.check(rc, "srf_pyramid_ragged")
     return merged
 
@@ -110,3 +112,50 @@ def pw_conv_pair(x, packed1, bias1, in_sums, in_gamma, in_beta, in_prelu, residu
                                              _lib.ptr(out_sums2), Bt, Cin1, Cmid, Cout2, L, frs, _lib.current_stream(dev))
     _lib.check(rc, "srf_pw_conv_pair_ragged")
     return y, y2
+
+
+def tac(x, params, G, frames, out_sums=None):
+    """srf_tac_ragged (the MFMA kernel: n = 16, G = 16): x [Bt, G*n, L] (row b valid up to frames[b]; what lies past it may hold
+    anything), params = the 9 TAC tensors in state_dict order -> q [Bt, G*n, L] (pre-norm), exact zeros from frames[b] on;
+    out_sums [Bt*G, 64, 2] += the sums of the stored q per (example, group)."""
+    dev = _chk(x, *params, out_sums)
+    Bt, Ctot, L = x.shape
+    n = Ctot // G
+    frs, cnt = _table(frames, "frames")
+    if cnt != Bt:
+        raise _lib.SrfError("srf_tac_ragged: %d frames for a batch of %d" % (cnt, Bt))
+    q = torch.empty_like(x)
+    arr = (C.c_void_p * 9)(*[p.data_ptr() for p in params])
+    rc = _lib.load().srf_tac_ragged(_lib.ptr(x), _lib.ptr(q), arr, Bt, G, n, 3 * n, L, _lib.ptr(out_sums), frs,
+                                    _lib.current_stream(dev))
+    _lib.check(rc, "srf_tac_ragged")
+    return q
+
+
+def pw_conv_small_supported(Cin, Cout, L):
+    """Whether srf_pw_conv_small_ragged serves these channel counts / this row stride (no GPU needed)."""
+    return bool(_lib.load().srf_pw_conv_small_ragged_supported(Cin, Cout, L))
+
+
+def pw_conv_small(x, weight, bias, frames, rows_per_example=1, in_sums=None, in_gamma=None, in_beta=None, in_prelu=None,
+                  residual=None, out_sums=None, pre_q=None, pre_sums=None, pre_gamma=None, pre_beta=None):
+    """srf_pw_conv_small_ragged: GroupComm's per-group 1x1 convolutions over folded rows.  x [rows, Cin, L] with
+    rows = examples * rows_per_example, weight [Cout, Cin(, 1)], `frames` one entry per EXAMPLE.
+    Pre-add form (pre_q, pre_sums, pre_gamma, pre_beta, out_sums): returns (y, u) -- u = x + GlobLN(pre_q) valid on the
+    example's own columns, y = W u + bias exact zeros past them.  Residual form (in_sums, in_gamma, in_beta, in_prelu,
+    residual): returns y, valid on the example's own columns only."""
+    dev = _chk(x, weight, bias, in_sums, in_gamma, in_beta, in_prelu, residual, out_sums, pre_q, pre_sums, pre_gamma, pre_beta)
+    rows, Cin, L = x.shape
+    Cout = weight.shape[0]
+    frs, n = _table(frames, "frames")
+    if n * int(rows_per_example) != rows:
+        raise _lib.SrfError("srf_pw_conv_small_ragged: %d frames for %d rows of %d per example" % (n, rows, rows_per_example))
+    y = torch.empty((rows, Cout, L), dtype=torch.float32, device=dev)
+    u = torch.empty_like(x) if pre_q is not None else None
+    nrm = None if in_sums is None and in_prelu is None else C.byref(_lib.make_norm(in_sums, in_gamma, in_beta, in_prelu))
+    pre = None if pre_q is None else C.byref(_lib.make_norm(pre_sums, pre_gamma, pre_beta, None))
+    rc = _lib.load().srf_pw_conv_small_ragged(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), rows, Cin, Cout, L, nrm,
+                                              _lib.ptr(residual), _lib.ptr(out_sums), _lib.ptr(pre_q), pre, _lib.ptr(u), frs,
+                                              int(rows_per_example), _lib.current_stream(dev))
+    _lib.check(rc, "srf_pw_conv_small_ragged")
+    return (y, u) if pre_q is not None else y
