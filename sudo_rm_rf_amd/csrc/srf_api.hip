@@ -303,13 +303,12 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
     return plan_fail(p, SRF_EINVAL);
   }
   // ---- parameter indexing (state_dict order)
-  const int ublock_params = 10 + 4 * D;
-  p->p_block0 = 5;
-  p->p_ublock_off = gc ? 11 : 0;
-  p->p_block_stride = ublock_params + p->p_ublock_off;
-  p->p_tail = 5 + U * p->p_block_stride;
-  p->n_params = p->p_tail + 4;
-  // ---- statistic slots: ln | per block: [tac] proj d0..d{D-1} merged
+  p->p_block0 = SRF_P_FRONT;
+  p->p_ublock_off = gc ? SRF_P_TAC : 0;
+  p->p_block_stride = plan_block_params(D, gc);
+  p->p_tail = p->p_block0 + U * p->p_block_stride;
+  p->n_params = p->p_tail + SRF_P_TAIL;
+  // ---- statistic slots: ln | per block: [tac] proj d0..d{D-1} merged (plan_slots)
   p->slots_per_block = D + 2 + (gc ? 1 : 0);
   p->n_slots = 1 + U * p->slots_per_block;
   // ---- workspace
@@ -336,15 +335,14 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   p->off_pyr = p->fused_pyramid ? take(srf_pyramid_scratch_bytes(p->Bg, p->nC, p->L, D)) : 0;
   // packed weights for the split-precision GEMM (only shapes the kernel supports)
   p->pk_of_param.assign(p->n_params, 0);
-  plan_add_pack(p, &off, 3, c->out_channels, c->enc_num_basis);
+  plan_add_pack(p, &off, SRF_P_BOTTLENECK, c->out_channels, c->enc_num_basis);
   for (int i = 0; i < U; ++i) {
-    const int pu = p->p_block0 + i * p->p_block_stride + p->p_ublock_off;
-    plan_add_pack(p, &off, pu + 0, p->nC, p->nB);
-    plan_add_pack(p, &off, pu + 5 + 4 * D + 3, p->nB, p->nC);
+    plan_add_pack(p, &off, plan_p_proj(p, i), p->nC, p->nB);
+    plan_add_pack(p, &off, plan_p_res(p, i), p->nB, p->nC);
   }
-  plan_add_pack(p, &off, p->p_tail + 1, p->SA * c->enc_num_basis, c->out_channels);
+  plan_add_pack(p, &off, plan_p_mask(p), p->SA * c->enc_num_basis, c->out_channels);
   // decoder weights as MFMA fragments for the fused tail (K5); whether it runs is decided per forward
-  p->off_wdpack = (p->SA * K <= 64 && p->pk_of_param[p->p_tail + 1]) ? take(srf_mask_decode_pack_bytes(p->SA * c->enc_num_basis)) : 0;
+  p->off_wdpack = (p->SA * K <= 64 && p->pk_of_param[plan_p_mask(p)]) ? take(srf_mask_decode_pack_bytes(p->SA * c->enc_num_basis)) : 0;
   p->total_bytes = off;
   p->n_launches = 1 /*memset*/ + 2 + U * (D + 3 + (gc ? 2 : 0)) + 1 + 4;
   *out = p;
@@ -481,9 +479,245 @@ extern "C" int srf_separate(const srf_plan* p, const float* const* P, int num_pa
   return srf_forward_impl(p, P, num_params, wav, out, workspace, workspace_bytes, stats, mixture_consistency, stream);
 }
 
-static int srf_forward_body(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
-                            void* workspace, size_t workspace_bytes, const float* wav_stats, int mixture_consistency,
-                            void* stream);
+// what srf_forward / srf_separate and srf_forward_ragged (`who`) ask of their arguments; ptrs: none of the caller's pointers is null
+static int forward_check_args(const char* who, bool ptrs, const srf_plan* p, const float* const* P, int num_params,
+                              const void* workspace, size_t workspace_bytes) {
+  SRF_CHECK_ARG(ptrs, "%s: null pointer", who);
+  SRF_CHECK_ARG(num_params == p->n_params, "%s: expected %d parameter tensors, got %d", who, p->n_params, num_params);
+  if (workspace_bytes < p->total_bytes) {
+    srf_set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, p->total_bytes);
+    return SRF_EWORKSPACE;
+  }
+  SRF_CHECK_ARG((((size_t)workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
+  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "%s: parameter %d is null", who, i);
+  return SRF_OK;
+}
+
+// split + lay out every packable 1x1 weight for the 256 x 128 split-precision GEMMs (srf_pwconv_x3w.hip / _x3p.hip), one launch
+// per forward.  source(parameter index): the fp32 weight that goes into the image (the causal forward: its folded copies)
+template <typename F>
+static int plan_pack_weights(const srf_plan* p, F source, char* ws, void* stream) {
+  std::vector<const float*> pw(p->pk_param.size());
+  std::vector<void*> pd(p->pk_param.size());
+  for (size_t i = 0; i < p->pk_param.size(); ++i) {
+    pw[i] = source(p->pk_param[i]);
+    pd[i] = ws + p->pk_off[i];
+  }
+  return srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
+}
+
+// ---- the steps of the walk, one per kernel family: the uniform entry point, or -- rg != NULL, srf_forward_ragged -- its ragged
+// twin with the batch's frame counts.  Every per-launch refusal stays with the entry point.
+struct Ragged {
+  const int* lengths;                 // samples per example (host, the caller's)
+  int frames[SRF_RAGGED_MAX_BATCH];   // frames per example: its own padded length / hop, as its batch-1 plan would have it
+  SrfFrames lens_t, frames_t;         // the same two by value, for the overlap-add
+};
+static int step_encoder(const Ragged* rg, const float* wav, const float* w, float* enc, double* sums, int Bt, int A, int T, int N,
+                        int K, int L, const float* wav_stats, void* stream) {
+  return rg ? srf_encoder_ragged(wav, w, enc, sums, Bt, A, T, N, K, L, rg->lengths, rg->frames, stream)
+            : srf_encoder_impl(wav, w, enc, sums, Bt, A, T, N, K, L, wav_stats, stream);
+}
+// rows = examples * rows_per_example (GroupComm's per-group convs run over the folded rows).  Ragged: as in srf_pw_conv_packed
+// the thin-shape kernel has precedence, everything else is the 256 x 128 kernel (rows_per_example = 1)
+static int step_conv(const Ragged* rg, int rows_per_example, const float* x, const float* w, const void* w_packed, const float* bias,
+                     float* y, int rows, int Cin, int Cout, int L, const srf_norm* in_norm, const float* residual, double* out_sums,
+                     void* stream) {
+  if (!rg) return srf_pw_conv_packed(x, w, w_packed, bias, y, rows, Cin, Cout, L, in_norm, residual, out_sums, 0, nullptr, 0, stream);
+  if (srf_pw_small_ragged_supported(Cin, Cout, L))
+    return srf_pw_conv_small_ragged(x, w, bias, y, rows, Cin, Cout, L, in_norm, residual, out_sums, nullptr, nullptr, nullptr,
+                                    rg->frames, rows_per_example, stream);
+  return srf_pw_conv_packed_ragged(x, w, w_packed, bias, y, rows, Cin, Cout, L, in_norm, residual, out_sums, 0, nullptr, 0, rg->frames,
+                                   stream);
+}
+static int step_pair(const Ragged* rg, const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
+                     const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2, int Bt, int Cin1,
+                     int Cmid, int Cout2, int L, void* stream) {
+  return rg ? srf_pw_conv_pair_ragged(x, w1_packed, bias1, y, in_norm, residual, w2_packed, bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2,
+                                      L, rg->frames, stream)
+            : srf_pw_conv_pair(x, w1_packed, bias1, y, in_norm, residual, w2_packed, bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2, L,
+                               stream);
+}
+static int step_tac(const Ragged* rg, const float* x, float* q, const float* const* params, int Bt, int G, int n, int H, int L,
+                    double* out_sums, void* stream) {
+  return rg ? srf_tac_ragged(x, q, params, Bt, G, n, H, L, out_sums, rg->frames, stream)
+            : srf_tac(x, q, params, Bt, G, n, H, L, out_sums, stream);
+}
+// proj_1x1 with u = x + GlobLN(q) folded into its operand load (u is written for the block's residual as it goes)
+static int step_preadd(const Ragged* rg, int G, const float* x, const float* q, const srf_norm* qnorm, float* u, const float* w,
+                       const float* bias, float* y, int Bg, int Cin, int Cout, int L, double* out_sums, void* stream) {
+  return rg ? srf_pw_conv_small_ragged(x, w, bias, y, Bg, Cin, Cout, L, nullptr, nullptr, out_sums, q, qnorm, u, rg->frames, G, stream)
+            : srf_pw_conv_preadd(x, q, qnorm, u, w, bias, y, Bg, Cin, Cout, L, out_sums, (hipStream_t)stream);
+}
+// the fused pyramid: two passes with every level kept on chip (srf_pyramid.hip), over G folded rows per example
+static int step_pyramid(const Ragged* rg, int G, const float* y1, float* merged, const srf_norm* in_norm, const SrfBlock<const float>& b,
+                        int Bg, int C, int L, int D, void* scratch, double* out_sums, void* stream) {
+  return rg ? srf_pyramid_ragged_rows(y1, merged, in_norm, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bg, C, L, D, scratch, out_sums, rg->frames, G,
+                                      stream)
+            : srf_pyramid(y1, merged, in_norm, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bg, C, L, D, scratch, out_sums, stream);
+}
+// the ragged form reads the example's own frames only and has no post-processing (pipeline.py rescales outside)
+static int step_overlap_add(const Ragged* rg, const float* z, float* out, int Bt, int Co, int K, int L, int T, int nparts,
+                            const float* wav_stats, const float* wav, int mc, hipStream_t st) {
+  return rg ? srf_overlap_add_launch(z, out, Bt, Co, K, L, T, nparts, nullptr, nullptr, 0, st, &rg->lens_t, &rg->frames_t)
+            : srf_overlap_add_launch(z, out, Bt, Co, K, L, T, nparts, wav_stats, wav, mc, st);
+}
+
+// THE walk of the Improved / GroupComm inference forward: srf_forward, srf_separate (wav_stats) and srf_forward_ragged (rg).
+// The ragged forward keeps the layout -- [batch, C, L] with L the PLAN's frame count as row stride, the same workspace carve-up
+// and two-buffer scheme -- and every kernel takes the example's own frame count L_b from a by-value table.  The invariant:
+//   * a tensor whose GlobLN statistics are taken (enc, y1, merged; GroupComm: q) is exactly zero at columns >= L_b, so the
+//     sums come out right and only the count changes (C * L_b);
+//   * a tensor read with a halo (the wave by the encoder, y1 by the pyramid) is never read past the example's end;
+//   * the block stream (cur / nxt / u: pointwise consumers only) may hold anything there -- so may the partial decoder frames the
+//     unchanged mask + decoder GEMM leaves at those columns: the ragged overlap-add never reads them.
+static int forward_walk(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
+                        const float* wav_stats, int mixture_consistency, const Ragged* rg, void* stream) {
+  const srf_config& c = p->cfg;
+  const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
+  const int G = gc ? c.group_size : 1;
+  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
+  const int Bt = p->Bt, L = p->L, Bg = p->Bg, nB = p->nB, nC = p->nC;
+  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  auto fptr = [&](size_t o) { return (float*)(ws + o); };
+  double* stats = (double*)(ws + p->off_stats);      // (the slot of ln is the first)
+  int rc;
+
+  rc = srf_zero_launch(stats, p->stats_bytes, st);
+  if (rc) return rc;
+  // A ragged batch runs what plan_ragged_now has made sure the uniform forward would choose here -- the packed weights, the fused
+  // pyramid, the pair at the head and after every block (Improved) or the pre-add form (GroupComm), the fused tail -- whatever
+  // the "at least as many tiles as CUs" gates of the pair and of the 256 x 128 GEMM say: it has no other kernel to go to.
+  const bool use_pack = rg || plan_use_pack(p);
+  if (use_pack) {
+    rc = plan_pack_weights(p, [&](int param) { return P[param]; }, ws, stream);
+    if (rc) return rc;
+  }
+  auto packed = [&](int param_index) -> const void* {
+    return (use_pack && p->pk_of_param[param_index]) ? (const void*)(ws + p->pk_of_param[param_index]) : nullptr;
+  };
+
+  // ---- front end: encoder (+ ln statistics), ln folded into the bottleneck GEMM's operand load
+  const SrfFront<const float> f = plan_front(P);
+  const SrfBlock<const float> b0 = plan_block(p, P, 0);
+  float* enc = fptr(p->off_enc);
+  rc = step_encoder(rg, wav, f.enc_w, enc, stats, Bt, p->A, p->T, N, K, L, wav_stats, stream);
+  if (rc) return rc;
+  float* cur = fptr(p->off_xa);
+  float* nxt = fptr(p->off_xb);
+  float* y1 = fptr(p->off_y1);
+  // Round 5: a 1x1 conv with 256 output channels and the proj_1x1 that consumes its output run as ONE launch, the 256-channel
+  // tensor handed over in registers (srf_pwconv_x3f.hip): bottleneck -> proj_1x1 of block 0, res_conv of block i -> proj_1x1 of
+  // block i + 1 (improved_sudormrf.py:292 -> :205, :220 -> :205).  Needs the fused pyramid (its merged tensor has a buffer of
+  // its own: the pair kernel writes y1 while it reads the merged tensor).  Debug flag 1 = separate launches.
+  const bool fused = rg || plan_fused_pyramid_now(p);
+  const bool pair_res = !gc && (rg || (use_pack && fused && packed(b0.i_proj) && packed(b0.i_res) &&
+                                       srf_pw_conv_pair_supported(Bt, nC, nB, nC, L)));
+  const bool pair_head = pair_res && (rg || (packed(SRF_P_BOTTLENECK) && srf_pw_conv_pair_supported(Bt, N, nB, nC, L)));
+  bool y1_ready = false;      // proj_1x1 of the coming block has already been computed (with its statistics) by a pair launch
+  {
+    srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
+    if (pair_head) {
+      rc = step_pair(rg, enc, packed(SRF_P_BOTTLENECK), f.bott_b, cur, &ln, nullptr, packed(b0.i_proj), b0.proj_b, y1,
+                     plan_slots(p, stats, 0).proj, Bt, N, nB, nC, L, stream);
+      y1_ready = true;
+    } else {
+      rc = step_conv(rg, 1, enc, f.bott_w, packed(SRF_P_BOTTLENECK), f.bott_b, cur, Bt, N, c.out_channels, L, &ln, nullptr, nullptr,
+                     stream);
+    }
+    if (rc) return rc;
+  }
+
+  // ---- separation module (GroupComm: every kernel of a block over the Bt * G folded rows, finding its example as row / G)
+  for (int i = 0; i < U; ++i) {
+    const SrfBlock<const float> b = plan_block(p, P, i);
+    const SrfSlots s = plan_slots(p, stats, i);
+    const float* xin = cur;
+    bool tac_norm_fused = false;
+    if (gc) {
+      // TAC (groupcomm_sudormrf_v2.py:356-384): q = TAC MLPs, u = x + GlobLN_(b,g)(q)
+      float* xq = fptr(p->off_xq);
+      float* xu = fptr(p->off_xu);
+      rc = step_tac(rg, cur, xq, b.tac, Bt, G, nB, 3 * nB, L, s.tac, stream);
+      if (rc) return rc;
+      srf_norm tn{s.tac, b.tac_g, b.tac_b, nullptr};
+      // u = x + GlobLN(q): folded into the proj conv's operand load where the thin-shape kernel runs it (it writes u for
+      // the block's residual as it goes); else its own kernel
+      const void* al[4] = {cur, xq, xu, y1};
+      tac_norm_fused = rg || srf_pw_conv_preadd_supported(nB, nC, L, al, 4);
+      if (tac_norm_fused) {
+        rc = step_preadd(rg, G, cur, xq, &tn, xu, b.proj_w, b.proj_b, y1, Bg, nB, nC, L, s.proj, stream);
+      } else {
+        rc = srf_gln_apply_add(cur, xq, xu, &tn, Bg, nB, L, stream);
+      }
+      if (rc) return rc;
+      xin = xu;
+    }
+    // proj_1x1 conv (+ statistics for its GlobLN)            improved_sudormrf.py:205
+    if (!tac_norm_fused && !y1_ready) {
+      rc = step_conv(rg, G, xin, b.proj_w, packed(b.i_proj), b.proj_b, y1, Bg, nB, nC, L, nullptr, nullptr, s.proj, stream);
+      if (rc) return rc;
+    }
+    y1_ready = false;
+    // depthwise pyramid + upsample/add                         :206-216
+    // unfused path: the merged tensor aliases y1 (dead once every level has been produced); fused path:
+    // its own buffer (the otherwise unused level-0 buffer), because pass 2 re-reads y1 with halos
+    float* merged = fused ? fptr(p->off_lv[0]) : y1;
+    if (fused) {
+      srf_norm in{s.proj, b.proj_g, b.proj_be, b.proj_prelu};
+      rc = step_pyramid(rg, G, y1, merged, &in, b, Bg, nC, L, D, ws + p->off_pyr, s.merged, stream);
+    } else {
+      float* lv[SRF_MAX_DEPTH];
+      for (int k = 0; k < D; ++k) lv[k] = fptr(p->off_lv[k]);
+      rc = srf_pyramid_per_level(y1, lv, merged, b, s, Bg, nC, L, D, stream);
+    }
+    if (rc) return rc;
+    // final_norm + PReLU folded into res_conv, + residual     :218-220
+    srf_norm fn{s.merged, b.fin_g, b.fin_be, b.fin_prelu};
+    if (pair_res && i + 1 < U) {
+      // res_conv of this block + proj_1x1 of the next one (its output into y1 -- dead since this block's pyramid -- and its
+      // statistics into the next block's first slot)
+      const SrfBlock<const float> nb = plan_block(p, P, i + 1);
+      rc = step_pair(rg, merged, packed(b.i_res), b.res_b, nxt, &fn, xin, packed(nb.i_proj), nb.proj_b, y1,
+                     plan_slots(p, stats, i + 1).proj, Bt, nC, nB, nC, L, stream);
+      y1_ready = true;
+    } else {
+      rc = step_conv(rg, G, merged, b.res_w, packed(b.i_res), b.res_b, nxt, Bg, nC, nB, L, &fn, xin, nullptr, stream);
+    }
+    if (rc) return rc;
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+  }
+
+  // ---- mask estimation + decoder                            :295-301
+  const SrfTail<const float> t = plan_tail(p, P);
+  float* masked = fptr(p->off_masked);
+  // K5: mask GEMM and decoder contraction in ONE launch -- the [Bt, S N, L] masked tensor (the largest of the forward) never
+  // reaches HBM; the GEMM leaves per-256-channel partial decoder frames (in the masked tensor's workspace region, <= 1/4 of
+  // it) and the overlap-add sums them.  Only where the 256 x 128 GEMM would have run the mask conv anyway.  (Ragged: the
+  // uniform GEMM over every column -- the block stream is unspecified past an example's end, and so are the partial frames it
+  // makes there -- then the ragged overlap-add.)
+  if (rg || plan_fused_tail_now(p, use_pack)) {
+    const int M = p->SA * K, nparts = (p->SA * N + 255) / 256;
+    rc = srf_mask_decode_pack(t.dec_w, ws + p->off_wdpack, p->SA * N, M, st);
+    if (rc) return rc;
+    rc = srf_mask_decode(cur, t.mask_w, packed(plan_p_mask(p)), t.mask_b, t.mask_prelu, enc, N, ws + p->off_wdpack, masked, Bt,
+                         c.out_channels, p->SA * N, L, M, st);
+    if (rc) return rc;
+    return step_overlap_add(rg, masked, out, Bt, p->SA, K, L, p->T, nparts, wav_stats, wav, mixture_consistency, st);
+  }
+  {
+    srf_norm pre{nullptr, nullptr, nullptr, t.mask_prelu};
+    rc = srf_pw_conv_packed(cur, t.mask_w, packed(plan_p_mask(p)), t.mask_b, masked, Bt, c.out_channels, p->SA * N, L,
+                            &pre, nullptr, nullptr, 1, enc, N, stream);
+    if (rc) return rc;
+  }
+  return srf_decoder_impl(masked, t.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, fptr(p->off_dec), wav_stats, wav,
+                          mixture_consistency, stream);
+}
+
 static int causal_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace, void* stream);
 static int srf_forward_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                             void* workspace, size_t workspace_bytes, const float* wav_stats, int mixture_consistency,
@@ -494,210 +728,13 @@ static int srf_forward_impl(const srf_plan* p, const float* const* P, int num_pa
     Paired() { srf_pw_prefer_paired(true); }
     ~Paired() { srf_pw_prefer_paired(false); }
   } paired_for_this_call;
-  return srf_forward_body(p, P, num_params, wav, out, workspace, workspace_bytes, wav_stats, mixture_consistency, stream);
-}
-static int srf_forward_body(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
-                            void* workspace, size_t workspace_bytes, const float* wav_stats, int mixture_consistency,
-                            void* stream) {
-  SRF_CHECK_ARG(p && P && wav && out && workspace, "srf_forward: null pointer");
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_forward: expected %d parameter tensors, got %d",
-                p->n_params, num_params);
-  if (workspace_bytes < p->total_bytes) {
-    srf_set_error("srf_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, p->total_bytes);
-    return SRF_EWORKSPACE;
-  }
-  SRF_CHECK_ARG((((size_t)workspace) & 255) == 0, "srf_forward: workspace must be 256-byte aligned");
-  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "srf_forward: parameter %d is null", i);
+  const int rc = forward_check_args("srf_forward", p && P && wav && out && workspace, p, P, num_params, workspace, workspace_bytes);
+  if (rc) return rc;
   // profiler: intervals run from mark to mark, so without this one the first kernel's interval would also hold the
   // host-side gap since the previous forward
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
   if (p->cfg.variant == SRF_VARIANT_CAUSAL) return causal_forward(p, P, wav, out, workspace, stream);
-
-  const srf_config& c = p->cfg;
-  const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
-  const int G = gc ? c.group_size : 1;
-  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
-  const int Bt = p->Bt, L = p->L, Bg = p->Bg, nB = p->nB, nC = p->nC;
-  char* ws = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  auto fptr = [&](size_t o) { return (float*)(ws + o); };
-  double* stats = (double*)(ws + p->off_stats);
-  auto slot = [&](int s) { return stats + (size_t)s * Bg * SRF_STAT_BUCKETS * 2; };
-  int rc;
-
-  rc = srf_zero_launch(stats, p->stats_bytes, st);
-  if (rc) return rc;
-  // split + lay out every 1x1 weight for the 256 x 128 split-precision GEMMs (srf_pwconv_x3w.hip / _x3p.hip), one launch per form and forward
-  const bool use_pack = plan_use_pack(p);
-  if (use_pack) {
-    std::vector<const float*> pw(p->pk_param.size());
-    std::vector<void*> pd(p->pk_param.size());
-    for (size_t i = 0; i < p->pk_param.size(); ++i) {
-      pw[i] = P[p->pk_param[i]];
-      pd[i] = ws + p->pk_off[i];
-    }
-    rc = srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
-    if (rc) return rc;
-  }
-  auto packed = [&](int param_index) -> const void* {
-    return (use_pack && p->pk_of_param[param_index]) ? (const void*)(ws + p->pk_of_param[param_index]) : nullptr;
-  };
-
-  // ---- front end: encoder (+ ln statistics), ln folded into the bottleneck GEMM's operand load
-  float* enc = fptr(p->off_enc);
-  rc = srf_encoder_impl(wav, P[0], enc, slot(0), Bt, p->A, p->T, N, K, L, wav_stats, stream);
-  if (rc) return rc;
-  float* cur = fptr(p->off_xa);
-  float* nxt = fptr(p->off_xb);
-  float* y1 = fptr(p->off_y1);
-  // Round 5: a 1x1 conv with 256 output channels and the proj_1x1 that consumes its output run as ONE launch, the 256-channel
-  // tensor handed over in registers (srf_pwconv_x3f.hip): bottleneck -> proj_1x1 of block 0, res_conv of block i -> proj_1x1 of
-  // block i + 1 (improved_sudormrf.py:292 -> :205, :220 -> :205).  Needs the fused pyramid (its merged tensor has a buffer of
-  // its own: the pair kernel writes y1 while it reads the merged tensor).  Debug flag 1 = separate launches.
-  const bool fused = plan_fused_pyramid_now(p);
-  const int pu0 = p->p_block0 + p->p_ublock_off;
-  const bool pair_res = !gc && use_pack && fused && packed(pu0) && packed(pu0 + 5 + 4 * D + 3) &&
-                        srf_pw_conv_pair_supported(Bt, nC, nB, nC, L);
-  const bool pair_head = pair_res && packed(3) && srf_pw_conv_pair_supported(Bt, N, nB, nC, L);
-  bool y1_ready = false;      // proj_1x1 of the coming block has already been computed (with its statistics) by a pair launch
-  {
-    srf_norm ln{slot(0), P[1], P[2], nullptr};
-    if (pair_head) {
-      rc = srf_pw_conv_pair(enc, packed(3), P[4], cur, &ln, nullptr, packed(pu0), P[pu0 + 1], y1, slot(1), Bt, N, nB, nC, L, stream);
-      y1_ready = true;
-    } else {
-      rc = srf_pw_conv_packed(enc, P[3], packed(3), P[4], cur, Bt, N, c.out_channels, L, &ln, nullptr, nullptr,
-                              0, nullptr, 0, stream);
-    }
-    if (rc) return rc;
-  }
-
-  // ---- separation module
-  for (int i = 0; i < U; ++i) {
-    const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
-    const float* const* Pu = Pb + p->p_ublock_off;
-    int s0 = 1 + i * p->slots_per_block;
-    const float* xin = cur;
-    bool tac_norm_fused = false;
-    if (gc) {
-      // TAC (groupcomm_sudormrf_v2.py:356-384): q = TAC MLPs, u = x + GlobLN_(b,g)(q)
-      float* xq = fptr(p->off_xq);
-      float* xu = fptr(p->off_xu);
-      rc = srf_tac(cur, xq, Pb, Bt, G, nB, 3 * nB, L, slot(s0), stream);
-      if (rc) return rc;
-      srf_norm tn{slot(s0), Pb[9], Pb[10], nullptr};
-      // u = x + GlobLN(q): folded into the proj conv's operand load where the thin-shape kernel runs it (it writes u for
-      // the block's residual as it goes); else its own kernel
-      const void* al[4] = {cur, xq, xu, y1};
-      tac_norm_fused = srf_pw_conv_preadd_supported(nB, nC, L, al, 4);
-      if (tac_norm_fused) {
-        rc = srf_pw_conv_preadd(cur, xq, &tn, xu, Pu[0], Pu[1], y1, Bg, nB, nC, L, slot(s0 + 1), st);
-      } else {
-        rc = srf_gln_apply_add(cur, xq, xu, &tn, Bg, nB, L, stream);
-      }
-      if (rc) return rc;
-      xin = xu;
-      s0 += 1;
-    }
-    // proj_1x1 conv (+ statistics for its GlobLN)            improved_sudormrf.py:205
-    const int pu_index = p->p_block0 + i * p->p_block_stride + p->p_ublock_off;
-    if (!tac_norm_fused && !y1_ready) {
-      rc = srf_pw_conv_packed(xin, Pu[0], packed(pu_index), Pu[1], y1, Bg, nB, nC, L, nullptr, nullptr, slot(s0),
-                              0, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    y1_ready = false;
-    // depthwise pyramid + upsample/add                         :206-216
-    // unfused path: the merged tensor aliases y1 (dead once every level has been produced); fused path:
-    // its own buffer (the otherwise unused level-0 buffer), because pass 2 re-reads y1 with halos
-    float* merged = fused ? fptr(p->off_lv[0]) : y1;
-    if (fused) {
-      // two passes with every level kept on chip (srf_pyramid.hip)
-      const float *pw[SRF_MAX_DEPTH], *pb[SRF_MAX_DEPTH], *pg[SRF_MAX_DEPTH], *pbe[SRF_MAX_DEPTH];
-      for (int k = 0; k < D; ++k) {
-        const float* const* Pk = Pu + 5 + 4 * k;
-        pw[k] = Pk[0];
-        pb[k] = Pk[1];
-        pg[k] = Pk[2];
-        pbe[k] = Pk[3];
-      }
-      srf_norm in{slot(s0), Pu[2], Pu[3], Pu[4]};
-      rc = srf_pyramid(y1, merged, &in, pw, pb, pg, pbe, Bg, nC, L, D, ws + p->off_pyr, slot(s0 + 1 + D), stream);
-      if (rc) return rc;
-    } else {
-    const float* levels[SRF_MAX_DEPTH];
-    srf_norm norms[SRF_MAX_DEPTH];
-    for (int k = 0; k < D; ++k) {
-      const float* const* Pk = Pu + 5 + 4 * k;
-      float* dk = fptr(p->off_lv[k]);
-      srf_norm in;
-      const float* src;
-      int Lin, stride;
-      if (k == 0) {
-        in = srf_norm{slot(s0), Pu[2], Pu[3], Pu[4]};  // proj_1x1.norm + act
-        src = y1;
-        Lin = L;
-        stride = 1;
-      } else {
-        const float* const* Pprev = Pu + 5 + 4 * (k - 1);
-        in = srf_norm{slot(s0 + k), Pprev[2], Pprev[3], nullptr};  // previous level's norm
-        src = fptr(p->off_lv[k - 1]);
-        Lin = L >> (k - 1);
-        stride = 2;
-      }
-      rc = srf_dwconv5(src, Pk[0], Pk[1], dk, Bg, nC, Lin, stride, &in, slot(s0 + 1 + k), stream);
-      if (rc) return rc;
-      levels[k] = dk;
-      norms[k] = srf_norm{slot(s0 + 1 + k), Pk[2], Pk[3], nullptr};
-    }
-    // upsample + add                                          :214-216   (output aliases y1: dead)
-    rc = srf_merge(levels, norms, D, merged, Bg, nC, L, slot(s0 + 1 + D), stream);
-    if (rc) return rc;
-    }
-    // final_norm + PReLU folded into res_conv, + residual     :218-220
-    const float* const* Pf = Pu + 5 + 4 * D;
-    srf_norm fn{slot(s0 + 1 + D), Pf[0], Pf[1], Pf[2]};
-    if (pair_res && fused && i + 1 < U) {
-      // res_conv of this block + proj_1x1 of the next one (its output into y1 -- dead since this block's pyramid -- and its
-      // statistics into the next block's first slot)
-      const int pn = pu_index + p->p_block_stride;
-      rc = srf_pw_conv_pair(merged, packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, &fn, xin, packed(pn), P[pn + 1], y1,
-                            slot(1 + (i + 1) * p->slots_per_block), Bt, nC, nB, nC, L, stream);
-      y1_ready = true;
-    } else {
-      rc = srf_pw_conv_packed(merged, Pf[3], packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, Bg, nC, nB, L, &fn, xin,
-                              nullptr, 0, nullptr, 0, stream);
-    }
-    if (rc) return rc;
-    float* t = cur;
-    cur = nxt;
-    nxt = t;
-  }
-
-  // ---- mask estimation + decoder                            :295-301
-  const float* const* Pt = P + p->p_tail;
-  float* masked = fptr(p->off_masked);
-  // K5: mask GEMM and decoder contraction in ONE launch -- the [Bt, S N, L] masked tensor (the largest of the forward) never
-  // reaches HBM; the GEMM leaves per-256-channel partial decoder frames (in the masked tensor's workspace region, <= 1/4 of
-  // it) and the overlap-add sums them.  Only where the 256 x 128 GEMM would have run the mask conv anyway.
-  if (plan_fused_tail_now(p, use_pack)) {
-    const int M = p->SA * K, nparts = (p->SA * N + 255) / 256;
-    rc = srf_mask_decode_pack(Pt[3], ws + p->off_wdpack, p->SA * N, M, st);
-    if (rc) return rc;
-    rc = srf_mask_decode(cur, Pt[1], packed(p->p_tail + 1), Pt[2], Pt[0], enc, N, ws + p->off_wdpack, masked, Bt,
-                         c.out_channels, p->SA * N, L, M, st);
-    if (rc) return rc;
-    return srf_overlap_add_launch(masked, out, Bt, p->SA, K, L, p->T, nparts, wav_stats, wav, mixture_consistency, st);
-  }
-  {
-    srf_norm pre{nullptr, nullptr, nullptr, Pt[0]};
-    rc = srf_pw_conv_packed(cur, Pt[1], packed(p->p_tail + 1), Pt[2], masked, Bt, c.out_channels, p->SA * N, L,
-                            &pre, nullptr, nullptr, 1, enc, N, stream);
-    if (rc) return rc;
-  }
-  rc = srf_decoder_impl(masked, Pt[3], out, Bt, p->SA * N, p->SA, K, L, p->T, fptr(p->off_dec), wav_stats, wav,
-                        mixture_consistency, stream);
-  return rc;
+  return forward_walk(p, P, wav, out, workspace, wav_stats, mixture_consistency, nullptr, stream);
 }
 
 // ---- the by-value table of every ragged entry point (srf_internal.h)
@@ -716,13 +753,8 @@ int srf_frames_table(const char* what, const int* frames, int groups, int L, Srf
 // ---------------------------------------------------------------------------------------------
 // ragged forward: unequal-length examples in one set of launches (include/sudormrf_hip.h, "Ragged forms")
 // ---------------------------------------------------------------------------------------------
-// The layout is the uniform forward's -- [batch, C, L] with L the PLAN's frame count as row stride, the same workspace carve-up
-// and two-buffer scheme -- and every kernel takes the example's own frame count L_b from a by-value table.  The invariant:
-//   * a tensor whose GlobLN statistics are taken (enc, y1, merged) is exactly zero at columns >= L_b, so the sums come out
-//     right and only the count changes (C * L_b): encoder, y2 of the pair, the pyramid's merged tensor;
-//   * a tensor read with a halo (the wave by the encoder, y1 by the pyramid) is never read past the example's end;
-//   * the block stream (cur / nxt: pointwise consumers only) may hold anything there -- so may the partial decoder frames the
-//     unchanged mask + decoder GEMM leaves at those columns: the ragged overlap-add never reads them.
+// It IS the uniform walk (forward_walk above) with a frames table: plan_ragged_now is the gate -- whether the uniform forward of
+// this plan, now, runs exactly the kernels that have ragged twins -- and the walk's step helpers pick the twins.
 static bool plan_ragged_now(const srf_plan* p, const char** why) {
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis;
@@ -746,18 +778,16 @@ static bool plan_ragged_now(const srf_plan* p, const char** why) {
     if (srf_dbg(SRF_DBG_TAC_ONE_STEP_PER_LANE | SRF_DBG_TAC_VALU | SRF_DBG_TAC_GENERIC | SRF_DBG_TAC_LANES_4TILES) ||
         (long)c.out_channels * p->L * 4 >= (1L << 31))
       return no("GroupComm: the forward does not run the MFMA TAC (debug flags / length)");
-    if (!p->pk_of_param[3] || !p->pk_of_param[p->p_tail + 1] || !srf_x3w_shape_supported(N, c.out_channels, p->L) ||
+    if (!p->pk_of_param[SRF_P_BOTTLENECK] || !p->pk_of_param[plan_p_mask(p)] || !srf_x3w_shape_supported(N, c.out_channels, p->L) ||
         (long)p->Bt * ((p->L + 127) / 128) < 8)
       return no("bottleneck / mask conv shapes outside the 256 x 128 GEMM, or too few tiles for it");
     if (!plan_fused_tail_now(p, true))
       return no("the forward does not run the fused mask + decoder tail at this size (small launches)");
     return true;
   }
-  const int pu0 = p->p_block0;
-  if (!p->pk_of_param[3] || !p->pk_of_param[p->p_tail + 1]) return no("bottleneck / mask conv shapes outside the 256 x 128 GEMM");
+  if (!p->pk_of_param[SRF_P_BOTTLENECK] || !p->pk_of_param[plan_p_mask(p)]) return no("bottleneck / mask conv shapes outside the 256 x 128 GEMM");
   for (int i = 0; i < U; ++i)
-    if (!p->pk_of_param[pu0 + i * p->p_block_stride] || !p->pk_of_param[pu0 + i * p->p_block_stride + 5 + 4 * D + 3])
-      return no("block conv shapes outside the 256 x 128 GEMM");
+    if (!p->pk_of_param[plan_p_proj(p, i)] || !p->pk_of_param[plan_p_res(p, i)]) return no("block conv shapes outside the 256 x 128 GEMM");
   if (!srf_pw_conv_pair_ragged_supported(N, p->nB, p->nC, p->L) || !srf_pw_conv_pair_ragged_supported(p->nC, p->nB, p->nC, p->L))
     return no("channel counts outside the fused conv pair (needs out_channels = 256)");
   if (!srf_x3w_shape_supported(p->nC, p->nB, p->L) || (long)p->Bt * ((p->L + 127) / 128) < 8)
@@ -775,152 +805,29 @@ extern "C" int srf_forward_ragged(const srf_plan* p, const float* const* P, int 
   SRF_CHECK_ARG(plan_ragged_now(p, &why), "srf_forward_ragged: plan not supported%s: %s",
                 p->cfg.variant == SRF_VARIANT_IMPROVED ? "" : " (ragged kernels exist for the Improved model and for GroupComm with 16 groups of 16 channels)",
                 why);
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_forward_ragged: expected %d parameter tensors, got %d", p->n_params, num_params);
-  if (workspace_bytes < p->total_bytes) {
-    srf_set_error("srf_forward_ragged: workspace too small (%zu < %zu bytes)", workspace_bytes, p->total_bytes);
-    return SRF_EWORKSPACE;
-  }
-  SRF_CHECK_ARG((((size_t)workspace) & 255) == 0, "srf_forward_ragged: workspace must be 256-byte aligned");
-  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "srf_forward_ragged: parameter %d is null", i);
-  const srf_config& c = p->cfg;
-  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, h = K / 2;
-  const int Bt = p->Bt, L = p->L, nB = p->nB, nC = p->nC;
-  const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
-  const int G = gc ? c.group_size : 1, Bg = p->Bg;
-  // ---- every example's own padded length, as its batch-1 plan would have it; all refusals BEFORE the first launch
-  int frames[SRF_RAGGED_MAX_BATCH];
-  SrfFrames lens_t, frames_t;
-  for (int b = 0; b < Bt; ++b) {
+  int rc = forward_check_args("srf_forward_ragged", true /* checked above: the gate comes first */, p, P, num_params, workspace, workspace_bytes);
+  if (rc) return rc;
+  // ---- every example's own padded length, as its batch-1 plan would have it; all refusals BEFORE the first launch (a length the
+  // pyramid takes is on its 16- / 32-frame chunk grid: the "multiple of 4 frames" the GEMMs' ragged forms ask for is implied)
+  const int D = p->cfg.upsampling_depth, h = p->cfg.enc_kernel_size / 2;
+  Ragged rg;
+  rg.lengths = lengths;
+  for (int b = 0; b < p->Bt; ++b) {
     SRF_CHECK_ARG(lengths[b] >= 1 && lengths[b] <= p->T, "srf_forward_ragged: example %d has length %d (allowed: 1..%d)", b,
                   lengths[b], p->T);
-    frames[b] = (int)(plan_padded_length(lengths[b], h, D) / h);
-    SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(frames[b], L, D),
+    rg.frames[b] = (int)(plan_padded_length(lengths[b], h, D) / h);
+    SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(rg.frames[b], p->L, D),
                   "srf_forward_ragged: example %d (length %d = %d frames) is too short for the fused pyramid or off its chunk grid", b,
-                  lengths[b], frames[b]);
+                  lengths[b], rg.frames[b]);
   }
-  int rc = srf_frames_table("srf_forward_ragged", lengths, Bt, p->T, &lens_t);
+  rc = srf_frames_table("srf_forward_ragged", lengths, p->Bt, p->T, &rg.lens_t);
   if (rc) return rc;
-  rc = srf_frames_table("srf_forward_ragged", frames, Bt, L, &frames_t);
+  rc = srf_frames_table("srf_forward_ragged", rg.frames, p->Bt, p->L, &rg.frames_t);
   if (rc) return rc;
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
-
-  char* ws = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  auto fptr = [&](size_t o) { return (float*)(ws + o); };
-  double* stats = (double*)(ws + p->off_stats);
-  auto slot = [&](int s) { return stats + (size_t)s * Bg * SRF_STAT_BUCKETS * 2; };   // (slots hold one entry per FOLDED row)
-  rc = srf_zero_launch(stats, p->stats_bytes, st);
-  if (rc) return rc;
-  {
-    std::vector<const float*> pw(p->pk_param.size());
-    std::vector<void*> pd(p->pk_param.size());
-    for (size_t i = 0; i < p->pk_param.size(); ++i) {
-      pw[i] = P[p->pk_param[i]];
-      pd[i] = ws + p->pk_off[i];
-    }
-    rc = srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
-    if (rc) return rc;
-  }
-  auto packed = [&](int param_index) -> const void* { return (const void*)(ws + p->pk_of_param[param_index]); };
-
-  float* enc = fptr(p->off_enc);
-  rc = srf_encoder_ragged(wav, P[0], enc, slot(0), Bt, 1, p->T, N, K, L, lengths, frames, stream);
-  if (rc) return rc;
-  float* cur = fptr(p->off_xa);
-  float* nxt = fptr(p->off_xb);
-  float* y1 = fptr(p->off_y1);
-  float* merged = fptr(p->off_lv[0]);
-  if (gc) {
-    // GroupComm: the bottleneck alone (its output is block stream: no statistics), then per block
-    // TAC -> proj_1x1 with u = x + GlobLN(q) folded into its load -> pyramid over G rows per example -> res_conv, every kernel
-    // over the Bt * G folded rows finding its example as row / G
-    srf_norm ln{slot(0), P[1], P[2], nullptr};
-    rc = srf_pw_conv_packed_ragged(enc, P[3], packed(3), P[4], cur, Bt, N, c.out_channels, L, &ln, nullptr, nullptr, 0, nullptr, 0,
-                                   frames, stream);
-    if (rc) return rc;
-    float* xq = fptr(p->off_xq);
-    float* xu = fptr(p->off_xu);
-    for (int i = 0; i < U; ++i) {
-      const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
-      const float* const* Pu = Pb + p->p_ublock_off;
-      const int s0 = 1 + i * p->slots_per_block;      // tac | proj | d0 .. d{D-1} | merged
-      rc = srf_tac_ragged(cur, xq, Pb, Bt, G, nB, 3 * nB, L, slot(s0), frames, stream);
-      if (rc) return rc;
-      srf_norm tn{slot(s0), Pb[9], Pb[10], nullptr};
-      rc = srf_pw_conv_small_ragged(cur, Pu[0], Pu[1], y1, Bg, nB, nC, L, nullptr, nullptr, slot(s0 + 1), xq, &tn, xu, frames, G,
-                                    stream);
-      if (rc) return rc;
-      const float *pw[SRF_MAX_DEPTH], *pb[SRF_MAX_DEPTH], *pg[SRF_MAX_DEPTH], *pbe[SRF_MAX_DEPTH];
-      for (int k = 0; k < D; ++k) {
-        const float* const* Pk = Pu + 5 + 4 * k;
-        pw[k] = Pk[0];
-        pb[k] = Pk[1];
-        pg[k] = Pk[2];
-        pbe[k] = Pk[3];
-      }
-      srf_norm in{slot(s0 + 1), Pu[2], Pu[3], Pu[4]};
-      rc = srf_pyramid_ragged_rows(y1, merged, &in, pw, pb, pg, pbe, Bg, nC, L, D, ws + p->off_pyr, slot(s0 + 2 + D), frames, G,
-                                   stream);
-      if (rc) return rc;
-      const float* const* Pf = Pu + 5 + 4 * D;
-      srf_norm fn{slot(s0 + 2 + D), Pf[0], Pf[1], Pf[2]};
-      rc = srf_pw_conv_small_ragged(merged, Pf[3], Pf[4], nxt, Bg, nC, nB, L, &fn, xu, nullptr, nullptr, nullptr, nullptr, frames,
-                                    G, stream);
-      if (rc) return rc;
-      float* t = cur;
-      cur = nxt;
-      nxt = t;
-    }
-  } else {
-    const int pu0 = p->p_block0;
-    {   // ln folded into the bottleneck, + proj_1x1 of block 0
-      srf_norm ln{slot(0), P[1], P[2], nullptr};
-      rc = srf_pw_conv_pair_ragged(enc, packed(3), P[4], cur, &ln, nullptr, packed(pu0), P[pu0 + 1], y1, slot(1), Bt, N, nB, nC, L,
-                                   frames, stream);
-      if (rc) return rc;
-    }
-    for (int i = 0; i < U; ++i) {
-      const int pu_index = pu0 + i * p->p_block_stride;
-      const float* const* Pu = P + pu_index;
-      const int s0 = 1 + i * p->slots_per_block;
-      const float *pw[SRF_MAX_DEPTH], *pb[SRF_MAX_DEPTH], *pg[SRF_MAX_DEPTH], *pbe[SRF_MAX_DEPTH];
-      for (int k = 0; k < D; ++k) {
-        const float* const* Pk = Pu + 5 + 4 * k;
-        pw[k] = Pk[0];
-        pb[k] = Pk[1];
-        pg[k] = Pk[2];
-        pbe[k] = Pk[3];
-      }
-      srf_norm in{slot(s0), Pu[2], Pu[3], Pu[4]};
-      rc = srf_pyramid_ragged(y1, merged, &in, pw, pb, pg, pbe, Bt, nC, L, D, ws + p->off_pyr, slot(s0 + 1 + D), frames, stream);
-      if (rc) return rc;
-      const float* const* Pf = Pu + 5 + 4 * D;
-      srf_norm fn{slot(s0 + 1 + D), Pf[0], Pf[1], Pf[2]};
-      if (i + 1 < U) {   // res_conv of this block + proj_1x1 of the next one
-        const int pn = pu_index + p->p_block_stride;
-        rc = srf_pw_conv_pair_ragged(merged, packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, &fn, cur, packed(pn), P[pn + 1], y1,
-                                     slot(1 + (i + 1) * p->slots_per_block), Bt, nC, nB, nC, L, frames, stream);
-      } else {
-        rc = srf_pw_conv_packed_ragged(merged, Pf[3], packed(pu_index + 5 + 4 * D + 3), Pf[4], nxt, Bt, nC, nB, L, &fn, cur, nullptr,
-                                       0, nullptr, 0, frames, stream);
-      }
-      if (rc) return rc;
-      float* t = cur;
-      cur = nxt;
-      nxt = t;
-    }
-  }
-  // ---- tail: the uniform mask + decoder GEMM over every column (the block stream is unspecified past an example's end, and so
-  // are the partial frames it makes there), then the ragged overlap-add, which reads the example's own frames only
-  const float* const* Pt = P + p->p_tail;
-  float* zpart = fptr(p->off_masked);
-  const int M = p->SA * K, nparts = (p->SA * N + 255) / 256;
-  rc = srf_mask_decode_pack(Pt[3], ws + p->off_wdpack, p->SA * N, M, st);
-  if (rc) return rc;
-  rc = srf_mask_decode(cur, Pt[1], packed(p->p_tail + 1), Pt[2], Pt[0], enc, N, ws + p->off_wdpack, zpart, Bt, c.out_channels,
-                       p->SA * N, L, M, st);
-  if (rc) return rc;
-  return srf_overlap_add_launch(zpart, out, Bt, p->SA, K, L, p->T, nparts, nullptr, nullptr, 0, st, &lens_t, &frames_t);
+  // no normalisation on load, no mixture consistency: pipeline.py does both outside.  (Not under srf_pw_prefer_paired: the ragged
+  // forward runs on one stream.)
+  return forward_walk(p, P, wav, out, workspace, nullptr, 0, &rg, stream);
 }
 
 extern "C" int srf_debug_fetch(const srf_plan* p, const void* workspace, int what, float* dst,
@@ -1002,13 +909,7 @@ static int causal_forward(const srf_plan* p, const float* const* P, const float*
     return P[param];
   };
   if (use_pack) {
-    std::vector<const float*> pw(p->pk_param.size());
-    std::vector<void*> pd(p->pk_param.size());
-    for (size_t i = 0; i < p->pk_param.size(); ++i) {
-      pw[i] = source_of(p->pk_param[i]);
-      pd[i] = ws + p->pk_off[i];
-    }
-    rc = srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
+    rc = plan_pack_weights(p, source_of, ws, stream);
     if (rc) return rc;
   }
   auto packed = [&](int param) -> const void* {

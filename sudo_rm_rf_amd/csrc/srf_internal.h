@@ -57,6 +57,13 @@ size_t srf_causal_prelu_bwd_scratch_floats();
 int srf_causal_prelu_bwd(const float* gout, const float* x, const float* slope, float* gx, float* dslope, long n, float* scratch,
                          hipStream_t st);
 
+// ---- srf_dwconv.hip: the per-level pyramid of the inference and the training forward (views: srf_plan.h)
+template <typename T>
+struct SrfBlock;
+struct SrfSlots;
+int srf_pyramid_per_level(const float* y1, float* const* lv, float* merged, const SrfBlock<const float>& b, const SrfSlots& s,
+                          int Bg, int nC, int L, int D, void* stream);
+
 // ---- srf_pyramid.hip / srf_pyramid_reg.hip
 bool srf_pyramid_reg_supported(int L, int D);
 // lv_out / lv_sums (both or neither; register-resident kernels only): the training forward's extra outputs

@@ -25,6 +25,87 @@ struct srf_plan {
   size_t off_fold_res, off_fold_proj, off_merged;
 };
 
+// ---- named views of the parameter table and of the GlobLN statistic slots (Improved / GroupComm layout; the causal variant
+// has its own).  state_dict order:
+//   front   encoder.weight | ln.{gamma, beta} | bottleneck.{weight, bias}
+//   block   [GroupComm: the 11 TAC tensors, the last two TAC_norm.{gamma, beta}] | proj_1x1.conv.{weight, bias},
+//           proj_1x1.norm.{gamma, beta}, proj_1x1.act.weight | D x {conv.weight, conv.bias, norm.gamma, norm.beta} |
+//           final_norm.{gamma, beta}, final_act.weight | res_conv.{weight, bias}
+//   tail    mask_net.0.weight (PReLU) | mask_net.1.{weight, bias} | decoder.weight
+// slots     ln | per block: [GroupComm: TAC_norm] proj_1x1.norm, level 0 .. D-1, final_norm (the merged tensor)
+// This is the ONE place that spells the layout out.  T = const float: the parameters; T = float: the backward's gradients.
+enum { SRF_P_BOTTLENECK = 3, SRF_P_FRONT = 5, SRF_P_TAC = 11, SRF_P_TAIL = 4 };
+// inside a U-ConvBlock's run of tensors: conv.weight of level k (k = D: final_norm.gamma)
+static inline int plan_u_level(int k) { return 5 + 4 * k; }
+static inline int plan_block_params(int D, bool gc) { return (gc ? SRF_P_TAC : 0) + plan_u_level(D) + 5; }
+static inline int plan_p_proj(const srf_plan* p, int i) { return p->p_block0 + i * p->p_block_stride + p->p_ublock_off; }
+static inline int plan_p_res(const srf_plan* p, int i) { return plan_p_proj(p, i) + plan_u_level(p->cfg.upsampling_depth) + 3; }
+static inline int plan_p_mask(const srf_plan* p) { return p->p_tail + 1; }
+
+template <typename T>
+struct SrfFront {
+  T *enc_w, *ln_g, *ln_b, *bott_w, *bott_b;
+};
+template <typename T>
+struct SrfBlock {
+  T* const* tac;   // GroupComm: the TAC sub-table as srf_tac / srf_tac_bwd take it (else null) and its norm
+  T *tac_g, *tac_b;
+  T *proj_w, *proj_b, *proj_g, *proj_be, *proj_prelu;
+  T *lv_w[SRF_MAX_DEPTH], *lv_b[SRF_MAX_DEPTH], *lv_g[SRF_MAX_DEPTH], *lv_be[SRF_MAX_DEPTH];   // (as srf_pyramid* take them)
+  T *fin_g, *fin_be, *fin_prelu;
+  T *res_w, *res_b;
+  int i_proj, i_res;   // parameter indices of the two packable weights (pk_of_param)
+};
+template <typename T>
+struct SrfTail {
+  T *mask_prelu, *mask_w, *mask_b, *dec_w;
+};
+struct SrfSlots {
+  double *tac, *proj, *level[SRF_MAX_DEPTH], *merged;
+};
+
+template <typename T>
+static inline SrfFront<T> plan_front(T* const* t) {
+  return SrfFront<T>{t[0], t[1], t[2], t[SRF_P_BOTTLENECK], t[SRF_P_BOTTLENECK + 1]};
+}
+template <typename T>
+static inline SrfBlock<T> plan_block(const srf_plan* p, T* const* t, int i) {
+  const int D = p->cfg.upsampling_depth;
+  SrfBlock<T> b{};
+  b.i_proj = plan_p_proj(p, i);
+  b.i_res = plan_p_res(p, i);
+  if (p->p_ublock_off) {
+    b.tac = t + b.i_proj - SRF_P_TAC;
+    b.tac_g = b.tac[SRF_P_TAC - 2];
+    b.tac_b = b.tac[SRF_P_TAC - 1];
+  }
+  T* const* u = t + b.i_proj;
+  b.proj_w = u[0], b.proj_b = u[1], b.proj_g = u[2], b.proj_be = u[3], b.proj_prelu = u[4];
+  for (int k = 0; k < D; ++k) {
+    T* const* l = u + plan_u_level(k);
+    b.lv_w[k] = l[0], b.lv_b[k] = l[1], b.lv_g[k] = l[2], b.lv_be[k] = l[3];
+  }
+  T* const* f = u + plan_u_level(D);
+  b.fin_g = f[0], b.fin_be = f[1], b.fin_prelu = f[2], b.res_w = f[3], b.res_b = f[4];
+  return b;
+}
+template <typename T>
+static inline SrfTail<T> plan_tail(const srf_plan* p, T* const* t) {
+  return SrfTail<T>{t[p->p_tail], t[plan_p_mask(p)], t[p->p_tail + 2], t[p->p_tail + 3]};
+}
+// stats: the zero-filled statistics region (one entry per FOLDED row and slot); the slot of ln is the first: `stats` itself
+static inline SrfSlots plan_slots(const srf_plan* p, double* stats, int i) {
+  const size_t each = (size_t)p->Bg * SRF_STAT_BUCKETS * 2;
+  const bool gc = p->p_ublock_off != 0;
+  double* s = stats + (1 + (size_t)i * p->slots_per_block) * each;
+  SrfSlots v{};
+  if (gc) v.tac = s, s += each;
+  v.proj = s;
+  for (int k = 0; k < p->cfg.upsampling_depth; ++k) v.level[k] = s + (1 + k) * each;
+  v.merged = s + (1 + p->cfg.upsampling_depth) * each;
+  return v;
+}
+
 // ---- dispatch decisions of a forward.  They depend on the kernel mode and the debug flags at CALL time, so they are
 // functions of the plan, not fields of it.
 

@@ -272,8 +272,7 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
   char* sv = (char*)saved;
   char* sc = (char*)scratch;
   hipStream_t st = (hipStream_t)stream;
-  double* stats = (double*)(sv + t.stats);
-  auto slot = [&](int i) { return stats + (size_t)i * p->Bg * SRF_STAT_BUCKETS * 2; };
+  double* stats = (double*)(sv + t.stats);      // (the slot of ln is the first)
   auto xbuf = [&](int i) { return (float*)(sv + t.x0 + t.x_stride * i); };
   SRF_CHECK_HIP(hipMemsetAsync(stats, 0, p->stats_bytes, st));
 
@@ -298,37 +297,37 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
     pk_ci.push_back(cin);
     return d;
   };
-  const float* const* Ptail = P + p->p_tail;
-  const void* pk_bottleneck = pack3(P[3], B, N);
+  const SrfFront<const float> f = plan_front(P);
+  const SrfTail<const float> tl = plan_tail(p, P);
+  const void* pk_bottleneck = pack3(f.bott_w, B, N);
   std::vector<const void*> pk_proj(U, nullptr), pk_res(U, nullptr);
   for (int i = 0; i < U; ++i) {
-    const float* const* Pu_ = P + p->p_block0 + (size_t)i * p->p_block_stride + p->p_ublock_off;
-    pk_proj[i] = pack3(Pu_[0], nC, nB);
-    pk_res[i] = pack3((Pu_ + 5 + 4 * D)[3], nB, nC);
+    const SrfBlock<const float> b = plan_block(p, P, i);
+    pk_proj[i] = pack3(b.proj_w, nC, nB);
+    pk_res[i] = pack3(b.res_w, nB, nC);
   }
-  const void* pk_mask = pack3(Ptail[1], p->SA * N, B);
+  const void* pk_mask = pack3(tl.mask_w, p->SA * N, B);
   if (!pk_w.empty()) {
     rc = srf_pack3_pw_weights(pk_w.data(), pk_d.data(), pk_co.data(), pk_ci.data(), (int)pk_w.size(), stream);
     if (rc) return rc;
   }
 
   float* enc = (float*)(sv + t.enc);
-  rc = srf_encoder(wav, P[0], enc, slot(0), Bt, p->A, p->T, N, K, L, stream);
+  rc = srf_encoder(wav, f.enc_w, enc, stats, Bt, p->A, p->T, N, K, L, stream);
   if (rc) return rc;
   // Round 5: like srf_forward, the B = 256 Improved models run bottleneck + proj_1x1(0) and res_conv(i) + proj_1x1(i + 1) as ONE
   // launch each (srf_pwconv_x3f.hip on the two-fp16-part images: both outputs bit-identical to the two launches; both are saved
   // activations anyway -- the residual stream and the block's y1).  Debug flag 1 = without.
   bool y1_ready = false;          // block i's y1 (and its statistics) came out of the pair that ended block i - 1
   auto y1_of = [&](int i) { return (float*)(sv + t.blk0 + t.blk_stride * i + t.y1); };
-  auto pu_of = [&](int i) { return P + p->p_block0 + (size_t)i * p->p_block_stride + p->p_ublock_off; };
   {
-    srf_norm ln{slot(0), P[1], P[2], nullptr};
+    srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
     if (!gc && pk_bottleneck && pk_proj[0] && srf_pw_conv_pair_packed3_supported(Bt, N, B, nC, (int)L)) {
-      rc = srf_pw_conv_pair_packed3(enc, pk_bottleneck, P[4], xbuf(0), &ln, nullptr, pk_proj[0], pu_of(0)[1], y1_of(0), slot(1), Bt, N,
-                                    B, nC, (int)L, stream);
+      rc = srf_pw_conv_pair_packed3(enc, pk_bottleneck, f.bott_b, xbuf(0), &ln, nullptr, pk_proj[0], plan_block(p, P, 0).proj_b, y1_of(0),
+                                    plan_slots(p, stats, 0).proj, Bt, N, B, nC, (int)L, stream);
       y1_ready = true;
     } else {
-      rc = srf_pw_conv_packed3(enc, P[3], pk_bottleneck, P[4], xbuf(0), Bt, N, B, L, &ln, nullptr, nullptr, stream);
+      rc = srf_pw_conv_packed3(enc, f.bott_w, pk_bottleneck, f.bott_b, xbuf(0), Bt, N, B, L, &ln, nullptr, nullptr, stream);
     }
     if (rc) return rc;
   }
@@ -343,9 +342,8 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
   const bool skip_d0 = fused_pyr && train_fused_head(p);     // (the backward re-computes d_0: nothing reads it)
   *skip_d0_out = skip_d0;                                     // (srf_forward_train records it for the backward)
   for (int i = 0; i < U; ++i) {
-    const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
-    const float* const* Pu = Pb + p->p_ublock_off;
-    int s0 = 1 + i * p->slots_per_block;
+    const SrfBlock<const float> b = plan_block(p, P, i);
+    const SrfSlots sl = plan_slots(p, stats, i);
     char* blk = sv + t.blk0 + t.blk_stride * i;
     float* y1 = (float*)(blk + t.y1);
     float* merged = (float*)(blk + t.merged);
@@ -355,95 +353,53 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
       // TAC: q = MLPs(x), u = x + GlobLN_(b,g)(q)                 groupcomm_sudormrf_v2.py:356-384
       float* q = (float*)(blk + t.q);
       float* u = (float*)(blk + t.u);
-      rc = srf_tac(xin, q, Pb, Bt, G, nB, 3 * nB, L, slot(s0), stream);
+      rc = srf_tac(xin, q, b.tac, Bt, G, nB, 3 * nB, L, sl.tac, stream);
       if (rc) return rc;
-      srf_norm tn{slot(s0), Pb[9], Pb[10], nullptr};
+      srf_norm tn{sl.tac, b.tac_g, b.tac_b, nullptr};
       // u = x + GlobLN(q) folded into the proj conv's operand load where the thin-shape kernel runs it (as in srf_forward;
       // bitwise the separate kernels' results, u is still written: the backward reads it)
       const void* al[4] = {xin, q, u, y1};
       tac_norm_fused = srf_pw_conv_preadd_supported(nB, nC, L, al, 4);
       if (tac_norm_fused)
-        rc = srf_pw_conv_preadd(xin, q, &tn, u, Pu[0], Pu[1], y1, Bg, nB, nC, L, slot(s0 + 1), st);
+        rc = srf_pw_conv_preadd(xin, q, &tn, u, b.proj_w, b.proj_b, y1, Bg, nB, nC, L, sl.proj, st);
       else
         rc = srf_gln_apply_add(xin, q, u, &tn, Bg, nB, L, stream);
       if (rc) return rc;
       xin = u;
-      s0 += 1;
     }
     if (!tac_norm_fused && !y1_ready) {
-      rc = srf_pw_conv_packed3(xin, Pu[0], pk_proj[i], Pu[1], y1, Bg, nB, nC, L, nullptr, nullptr, slot(s0), stream);
+      rc = srf_pw_conv_packed3(xin, b.proj_w, pk_proj[i], b.proj_b, y1, Bg, nB, nC, L, nullptr, nullptr, sl.proj, stream);
       if (rc) return rc;
     }
     y1_ready = false;
     // The pyramid: the two fused passes of the inference path with the per-level conv outputs d_k and their
     // statistics written on the side (what the backward reads) when the register-resident kernels cover the shape;
     // otherwise D depthwise kernels + the merge kernel.
+    float* lv[SRF_MAX_DEPTH];
+    for (int k = 0; k < D; ++k) lv[k] = (float*)(blk + t.lv[k]);
     if (fused_pyr) {
-      const float* wv[SRF_MAX_DEPTH];
-      const float* bv[SRF_MAX_DEPTH];
-      const float* gv_[SRF_MAX_DEPTH];
-      const float* bev[SRF_MAX_DEPTH];
-      float* lv_out[SRF_MAX_DEPTH];
-      double* lv_sums[SRF_MAX_DEPTH];
-      for (int k = 0; k < D; ++k) {
-        const float* const* Pk = Pu + 5 + 4 * k;
-        wv[k] = Pk[0];
-        bv[k] = Pk[1];
-        gv_[k] = Pk[2];
-        bev[k] = Pk[3];
-        lv_out[k] = (k == 0 && skip_d0) ? nullptr : (float*)(blk + t.lv[k]);
-        lv_sums[k] = slot(s0 + 1 + k);
-      }
-      const srf_norm in{slot(s0), Pu[2], Pu[3], Pu[4]};
-      rc = srf_pyramid_impl(y1, merged, &in, wv, bv, gv_, bev, Bg, nC, L, D, sc + s.gf, slot(s0 + 1 + D), lv_out,
-                            lv_sums, stream);
-      if (rc) return rc;
+      if (skip_d0) lv[0] = nullptr;
+      const srf_norm in{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
+      rc = srf_pyramid_impl(y1, merged, &in, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bg, nC, L, D, sc + s.gf, sl.merged, lv, sl.level, stream);
     } else {
-    const float* levels[SRF_MAX_DEPTH];
-    srf_norm norms[SRF_MAX_DEPTH];
-    for (int k = 0; k < D; ++k) {
-      const float* const* Pk = Pu + 5 + 4 * k;
-      float* dk = (float*)(blk + t.lv[k]);
-      srf_norm in;
-      const float* src;
-      int Lin, stride;
-      if (k == 0) {
-        in = srf_norm{slot(s0), Pu[2], Pu[3], Pu[4]};
-        src = y1;
-        Lin = L;
-        stride = 1;
-      } else {
-        const float* const* Pprev = Pu + 5 + 4 * (k - 1);
-        in = srf_norm{slot(s0 + k), Pprev[2], Pprev[3], nullptr};
-        src = (const float*)(blk + t.lv[k - 1]);
-        Lin = L >> (k - 1);
-        stride = 2;
-      }
-      rc = srf_dwconv5(src, Pk[0], Pk[1], dk, Bg, nC, Lin, stride, &in, slot(s0 + 1 + k), stream);
-      if (rc) return rc;
-      levels[k] = dk;
-      norms[k] = srf_norm{slot(s0 + 1 + k), Pk[2], Pk[3], nullptr};
+      rc = srf_pyramid_per_level(y1, lv, merged, b, sl, Bg, nC, L, D, stream);
     }
-    rc = srf_merge(levels, norms, D, merged, Bg, nC, L, slot(s0 + 1 + D), stream);
     if (rc) return rc;
-    }
-    const float* const* Pf = Pu + 5 + 4 * D;
-    srf_norm fn{slot(s0 + 1 + D), Pf[0], Pf[1], Pf[2]};
+    srf_norm fn{sl.merged, b.fin_g, b.fin_be, b.fin_prelu};
     if (i + 1 < U && !gc && pk_res[i] && pk_proj[i + 1] && srf_pw_conv_pair_packed3_supported(Bg, nC, nB, nC, (int)L)) {
-      rc = srf_pw_conv_pair_packed3(merged, pk_res[i], Pf[4], xbuf(i + 1), &fn, xin, pk_proj[i + 1], pu_of(i + 1)[1], y1_of(i + 1),
-                                    slot(1 + (i + 1) * p->slots_per_block), Bg, nC, nB, nC, (int)L, stream);
+      rc = srf_pw_conv_pair_packed3(merged, pk_res[i], b.res_b, xbuf(i + 1), &fn, xin, pk_proj[i + 1], plan_block(p, P, i + 1).proj_b,
+                                    y1_of(i + 1), plan_slots(p, stats, i + 1).proj, Bg, nC, nB, nC, (int)L, stream);
       y1_ready = true;
     } else {
-      rc = srf_pw_conv_packed3(merged, Pf[3], pk_res[i], Pf[4], xbuf(i + 1), Bg, nC, nB, L, &fn, xin, nullptr, stream);
+      rc = srf_pw_conv_packed3(merged, b.res_w, pk_res[i], b.res_b, xbuf(i + 1), Bg, nC, nB, L, &fn, xin, nullptr, stream);
     }
     if (rc) return rc;
   }
-  const float* const* Pt = P + p->p_tail;
   float* m = (float*)(sv + t.m);
   float* v = (float*)(sv + t.v);
   {
-    srf_norm pre{nullptr, nullptr, nullptr, Pt[0]};
-    rc = srf_pw_conv_packed3(xbuf(U), Pt[1], pk_mask, Pt[2], m, Bt, B, p->SA * N, L, &pre, nullptr, nullptr, stream);
+    srf_norm pre{nullptr, nullptr, nullptr, tl.mask_prelu};
+    rc = srf_pw_conv_packed3(xbuf(U), tl.mask_w, pk_mask, tl.mask_b, m, Bt, B, p->SA * N, L, &pre, nullptr, nullptr, stream);
     if (rc) return rc;
   }
   rc = srf_mask_apply(m, enc, v, Bt, p->SA, N, L, stream);
@@ -453,7 +409,7 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
   // exact class was this function's own choice it runs on the split kernel (round 6: 292 -> 130 us at cfg 2, 4 x that at N = 2048)
   // instead of the exact-fp32 MFMA kernel the thin output (42 rows) would otherwise fall to.
   const int tail_prev = split_tail ? srf_kernel_mode_override(0) : -1;
-  rc = srf_decoder(v, Pt[3], out, Bt, p->SA * N, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
+  rc = srf_decoder(v, tl.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
   if (split_tail) srf_kernel_mode_override(tail_prev);
   return rc;
 }
@@ -494,8 +450,7 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
   const char* sv = (const char*)saved;
   char* sc = (char*)scratch;
   hipStream_t st = (hipStream_t)stream;
-  double* stats = (double*)(sv + t.stats);
-  auto slot = [&](int i) { return stats + (size_t)i * p->Bg * SRF_STAT_BUCKETS * 2; };
+  double* stats = (double*)(sv + t.stats);      // (the slot of ln is the first)
   auto xbuf = [&](int i) { return (const float*)(sv + t.x0 + t.x_stride * i); };
   auto fp = [&](size_t o) { return (float*)(sc + o); };
   const float* enc = (const float*)(sv + t.enc);
@@ -542,7 +497,10 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     if (!srf_dwconv5_bwd_rowwise_ok(L, 2, nullptr, 0)) return head_lost("at level 1 (the row kernels)");
   }
 
-  const int pt = p->p_tail;
+  const SrfFront<const float> f = plan_front(P);
+  const SrfFront<float> gf_ = plan_front(G);
+  const SrfTail<const float> tl = plan_tail(p, P);
+  const SrfTail<float> gtl = plan_tail(p, G);
   // The data-gradient GEMMs g_x = W^T g run on the 256 x 128 split-bf16 kernel with the TRANSPOSED weights pre-split into its
   // stage images, all of them in one launch here (shapes / launches that kernel does not take keep the transposed fp32 copy
   // `wt` and the 128 x 128 kernels).
@@ -561,13 +519,13 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     pk_ci.push_back(cin_d);
     return d;
   };
-  const void* pkT_mask = packT(P[pt + 1], B, SAN);
-  const void* pkT_bott = packT(P[3], N, B);
+  const void* pkT_mask = packT(tl.mask_w, B, SAN);
+  const void* pkT_bott = packT(f.bott_w, N, B);
   std::vector<const void*> pkT_res(U, nullptr), pkT_proj(U, nullptr);
   for (int i = 0; i < U; ++i) {
-    const float* const* Pu_ = P + p->p_block0 + (size_t)i * p->p_block_stride + p->p_ublock_off;
-    pkT_res[i] = packT(Pu_[5 + 4 * D + 3], p->nC, p->nB);    // res_conv: forward [nB][nC], gradient GEMM nB -> nC
-    pkT_proj[i] = packT(Pu_[0], p->nB, p->nC);               // proj_1x1: forward [nC][nB], gradient GEMM nC -> nB
+    const SrfBlock<const float> b = plan_block(p, P, i);
+    pkT_res[i] = packT(b.res_w, p->nC, p->nB);               // res_conv: forward [nB][nC], gradient GEMM nB -> nC
+    pkT_proj[i] = packT(b.proj_w, p->nB, p->nC);             // proj_1x1: forward [nC][nB], gradient GEMM nC -> nB
   }
   if (!pk_w.empty()) {
     rc = srf_pack_pw_weights_transposed(pk_w.data(), pk_d.data(), pk_co.data(), pk_ci.data(), (int)pk_w.size(), st);
@@ -577,11 +535,11 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
   float* frames = fp(s.frames);
   rc = srf_frames_gather(grad_out, frames, Bt, SA, p->T, K, h, h, L, s.dec_rows, stream);
   if (rc) return rc;
-  rc = srf_pw_wgrad_cols(v, frames, nullptr, Bt, s.dec_rows, SAN, L, G[pt + 3], SA * K, nullptr, 1, wg, stream);
+  rc = srf_pw_wgrad_cols(v, frames, nullptr, Bt, s.dec_rows, SAN, L, gtl.dec_w, SA * K, nullptr, 1, wg, stream);
   if (rc) return rc;
   float* wdpad = fp(s.wdpad);
   SRF_CHECK_HIP(hipMemsetAsync(wdpad, 0, sizeof(float) * (size_t)SAN * s.dec_rows, st));
-  SRF_CHECK_HIP(hipMemcpy2DAsync(wdpad, sizeof(float) * s.dec_rows, P[pt + 3], sizeof(float) * SA * K,
+  SRF_CHECK_HIP(hipMemcpy2DAsync(wdpad, sizeof(float) * s.dec_rows, tl.dec_w, sizeof(float) * SA * K,
                                  sizeof(float) * SA * K, SAN, hipMemcpyDeviceToDevice, st));
   float* gv = fp(s.gv);
   rc = srf_pw_conv(frames, wdpad, zeros, gv, Bt, s.dec_rows, SAN, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
@@ -594,15 +552,15 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
   float* gx = fp(s.gxa);
   float* gx_other = fp(s.gxb);
   {
-    srf_norm pre{nullptr, nullptr, nullptr, P[pt]};
-    rc = srf_pw_wgrad(gv, xbuf(U), &pre, Bt, B, SAN, L, G[pt + 1], G[pt + 2], 1, wg, stream);
+    srf_norm pre{nullptr, nullptr, nullptr, tl.mask_prelu};
+    rc = srf_pw_wgrad(gv, xbuf(U), &pre, Bt, B, SAN, L, gtl.mask_w, gtl.mask_b, 1, wg, stream);
     if (rc) return rc;
     if (!srf_pw_packed_only(pkT_mask, gv, Bt, SAN, B, L))    // (the packed image of W^T serves the GEMM: no fp32 copy needed)
-      rc = srf_transpose_launch(P[pt + 1], wt, SAN, B, st);   // [SAN][B] -> [B][SAN]
+      rc = srf_transpose_launch(tl.mask_w, wt, SAN, B, st);   // [SAN][B] -> [B][SAN]
     if (rc) return rc;
     rc = srf_pw_conv_packed(gv, wt, pkT_mask, zeros, gx, Bt, SAN, B, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
     if (rc) return rc;
-    rc = srf_prelu_bwd(gx, xbuf(U), P[pt], gx, G[pt], (long)Bt * B * L, stream);
+    rc = srf_prelu_bwd(gx, xbuf(U), tl.mask_prelu, gx, gtl.mask_prelu, (long)Bt * B * L, stream);
     if (rc) return rc;
   }
   // ---- blocks in reverse: U-ConvBlock :198-220 (GroupComm: on the folded tensor, preceded by TAC)
@@ -613,23 +571,20 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
   float* gd = fp(s.gd);
   bool gf_ready = false;      // block i's g_f was produced by block i + 1's data-gradient pair
   for (int i = U - 1; i >= 0; --i) {
-    const int pb = p->p_block0 + i * p->p_block_stride;
-    const int pu = pb + p->p_ublock_off;
-    const float* const* Pu = P + pu;
-    float* const* Gu = G + pu;
-    const int s0 = 1 + i * p->slots_per_block + (gc ? 1 : 0);
+    const SrfBlock<const float> b = plan_block(p, P, i);
+    const SrfBlock<float> g = plan_block(p, G, i);
+    const SrfSlots sl = plan_slots(p, stats, i);
     const char* blk = sv + t.blk0 + t.blk_stride * i;
     const float* y1 = (const float*)(blk + t.y1);
     const float* merged = (const float*)(blk + t.merged);
     const float* xin = gc ? (const float*)(blk + t.u) : xbuf(i);   // the U-ConvBlock's input
-    const int pf = 5 + 4 * D;   // final_norm.gamma, .beta, act.weight, res_conv.weight, .bias
     // res_conv: x_{i+1} = W_r PReLU(GlobLN(merged)) + b_r + xin
-    srf_norm fn{slot(s0 + 1 + D), Pu[pf], Pu[pf + 1], Pu[pf + 2]};
-    rc = srf_pw_wgrad(gx, merged, &fn, Bg, nC, nB, L, Gu[pf + 3], Gu[pf + 4], 1, wg, stream);
+    srf_norm fn{sl.merged, b.fin_g, b.fin_be, b.fin_prelu};
+    rc = srf_pw_wgrad(gx, merged, &fn, Bg, nC, nB, L, g.res_w, g.res_b, 1, wg, stream);
     if (rc) return rc;
     if (!gf_ready) {        // (else: block i + 1's data-gradient pair below already left g_f = W_r^T g_x here)
       if (!srf_pw_packed_only(pkT_res[i], gx, Bg, nB, nC, L))
-        rc = srf_transpose_launch(Pu[pf + 3], wt, nB, nC, st);    // [nB][nC] -> [nC][nB]
+        rc = srf_transpose_launch(b.res_w, wt, nB, nC, st);    // [nB][nC] -> [nC][nB]
       if (rc) return rc;
       rc = srf_pw_conv_packed(gx, wt, pkT_res[i], zeros, gf, Bg, nB, nC, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
       if (rc) return rc;
@@ -642,7 +597,7 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     gn[0] = gf;
     for (int k = 1; k < D; ++k) gn[k] = fp(s.gn[k]);
     srf_bwd_ctx_merge_sink(ctx, gn, D);  // the merge backward rides on the norm's apply pass (the levels' pair sums of its output)
-    rc = srf_gln_bwd_impl(gf, nullptr, merged, &fn, Bg, nC, L, gf, 0, Gu[pf], Gu[pf + 1], Gu[pf + 2], gln_sl, 0, stream, ctx);
+    rc = srf_gln_bwd_impl(gf, nullptr, merged, &fn, Bg, nC, L, gf, 0, g.fin_g, g.fin_be, g.fin_prelu, gln_sl, 0, stream, ctx);
     if (rc) return rc;                                       // gf now holds g_merged = g_n_0 (merge part)
     if (!srf_bwd_ctx_merge_taken(ctx)) {
       rc = srf_merge_bwd(gf, gn, D, (long)Bg * nC, L, stream);
@@ -659,11 +614,9 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     bool head = d0_missing || train_fused_head(p);   // (re-computes d_0: needed when the forward left it out, harmless otherwise)
     const float* g_o = go;   // where level 0's conv leaves the gradient w.r.t. o = PReLU(GlobLN(y1))
     for (int k = D - 1; k >= 0; --k) {
-      const float* const* Pk = Pu + 5 + 4 * k;   // conv.weight, conv.bias, norm.gamma, norm.beta
-      float* const* Gk = Gu + 5 + 4 * k;
       const float* dk = (const float*)(blk + t.lv[k]);
       const int Lk = L >> k;
-      srf_norm nk{slot(s0 + 1 + k), Pk[2], Pk[3], nullptr};
+      srf_norm nk{sl.level[k], b.lv_g[k], b.lv_be[k], nullptr};
       // gradient w.r.t. the normalised level k: merge part (gn[k]) + what level k+1's conv sent down
       const float* gu_in = (k < D - 1) ? (k == 0 ? go : fp(s.gu[k])) : nullptr;
       const float* gout1 = pre_reduced ? gu_in : gn[k];    // pre-reduced: gu_in already holds the sum of both
@@ -673,14 +626,13 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       int Lin, stride;
       float* gin;
       if (k == 0) {
-        in = srf_norm{slot(s0), Pu[2], Pu[3], Pu[4]};
+        in = srf_norm{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
         src = y1;
         Lin = L;
         stride = 1;
         gin = go;       // gradient w.r.t. o = PReLU(GlobLN(y1)) (go is consumed as gu_in by this level first)
       } else {
-        const float* const* Pprev = Pu + 5 + 4 * (k - 1);
-        in = srf_norm{slot(s0 + k), Pprev[2], Pprev[3], nullptr};
+        in = srf_norm{sl.level[k - 1], b.lv_g[k - 1], b.lv_be[k - 1], nullptr};
         src = (const float*)(blk + t.lv[k - 1]);
         Lin = L >> (k - 1);
         stride = 2;
@@ -698,12 +650,12 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       if (k == 0 && head && !head0 && d0_missing) return head_lost("at level 0");
       if (head0) {
         {
-          rc = srf_gln_bwd_impl(gout1, nullptr, dk, &nk, Bg, nC, Lk, nullptr, 0, Gk[2], Gk[3], nullptr, cur_sl, 3, stream, ctx);
+          rc = srf_gln_bwd_impl(gout1, nullptr, dk, &nk, Bg, nC, Lk, nullptr, 0, g.lv_g[k], g.lv_be[k], nullptr, cur_sl, 3, stream, ctx);
           if (rc) return rc;      // (norm 0's parameter sums, reduced by level 1's kernel: recorded for the batched flush)
-          rc = srf_bwd_level0_proj(gout1, y1, &in, &nk, Pk[0], Pk[1], cur_sl, next_sl, dw_sl, Gk[0], Gk[1], gd, Bg, nC, L,
+          rc = srf_bwd_level0_proj(gout1, y1, &in, &nk, b.lv_w[k], b.lv_b[k], cur_sl, next_sl, dw_sl, g.lv_w[k], g.lv_b[k], gd, Bg, nC, L,
                                    stream, ctx);
           if (rc) return rc;
-          rc = srf_gln_bwd_impl(gd, nullptr, y1, &in, Bg, nC, L, nullptr, 0, Gu[2], Gu[3], Gu[4], next_sl, 3, stream, ctx);
+          rc = srf_gln_bwd_impl(gd, nullptr, y1, &in, Bg, nC, L, nullptr, 0, g.proj_g, g.proj_be, g.proj_prelu, next_sl, 3, stream, ctx);
           if (rc) return rc;      // (proj_1x1's norm: parameter sums recorded; its apply ran inside the fused head)
           head_done = true;
           pp += 1;
@@ -717,7 +669,7 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       const bool on_load = !gout2 && gout1 != gin && srf_dwconv5_bwd_rowwise_ok(Lin, stride, ptrs, 5);
       if (!on_load && k == 0) gin = go;
       if (k == 0) g_o = gin;
-      rc = srf_gln_bwd_impl(gout1, gout2, dk, &nk, Bg, nC, Lk, gd, 0, Gk[2], Gk[3], nullptr, cur_sl,
+      rc = srf_gln_bwd_impl(gout1, gout2, dk, &nk, Bg, nC, Lk, gd, 0, g.lv_g[k], g.lv_be[k], nullptr, cur_sl,
                             (pre_reduced ? 1 : 0) | (on_load ? 2 : 0), stream, ctx);
       if (rc) return rc;
       if (k == 1 && head && !on_load) {
@@ -726,15 +678,15 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       }
       if (k == 1 && head) {
         // level 1 on the fused-head kernel: conv 1's input n_0 re-computed from y1 (the forward may not have kept d_0)
-        const srf_norm pn1{slot(s0), Pu[2], Pu[3], Pu[4]};
-        rc = srf_bwd_level1_head(gout1, dk, &nk, cur_sl, y1, &pn1, &in, Pu[5], Pu[6], Pk[0], gadd, gin, next_sl,
-                                 dw_sl + (size_t)k * s.dw_slice, Gk[0], Gk[1], Bg, nC, L, stream, ctx);
+        const srf_norm pn1{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
+        rc = srf_bwd_level1_head(gout1, dk, &nk, cur_sl, y1, &pn1, &in, b.lv_w[0], b.lv_b[0], b.lv_w[k], gadd, gin, next_sl,
+                                 dw_sl + (size_t)k * s.dw_slice, g.lv_w[k], g.lv_b[k], Bg, nC, L, stream, ctx);
         if (rc) return rc;
         pre_reduced = 1;
         pp += 1;
         continue;
       }
-      rc = srf_dwconv5_bwd_impl(on_load ? gout1 : gd, src, &in, Pk[0], Bg, nC, Lin, stride, gin, Gk[0], Gk[1],
+      rc = srf_dwconv5_bwd_impl(on_load ? gout1 : gd, src, &in, b.lv_w[k], Bg, nC, Lin, stride, gin, g.lv_w[k], g.lv_b[k],
                                 dw_sl + (size_t)k * s.dw_slice, gadd, next_sl, &pre_reduced, on_load ? dk : nullptr,
                                 on_load ? &nk : nullptr, on_load ? cur_sl : nullptr, stream, ctx);
       if (rc) return rc;
@@ -746,8 +698,8 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       gd = t2;
     } else {
       // proj_1x1: y1 = W_p xin + b_p, o = PReLU(GlobLN(y1))
-      srf_norm pn{slot(s0), Pu[2], Pu[3], Pu[4]};
-      rc = srf_gln_bwd_impl(g_o, nullptr, y1, &pn, Bg, nC, L, go, 0, Gu[2], Gu[3], Gu[4], gln_sl + (size_t)pp * s.gln_slice,
+      srf_norm pn{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
+      rc = srf_gln_bwd_impl(g_o, nullptr, y1, &pn, Bg, nC, L, go, 0, g.proj_g, g.proj_be, g.proj_prelu, gln_sl + (size_t)pp * s.gln_slice,
                             pre_reduced, stream, ctx);   // go = g_y1
       if (rc) {
         srf_bwd_ctx_defer(ctx, false);
@@ -755,7 +707,7 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       }
     }
     srf_bwd_ctx_defer(ctx, false);
-    rc = srf_pw_wgrad(go, xin, nullptr, Bg, nB, nC, L, Gu[0], Gu[1], 1, wg, stream);
+    rc = srf_pw_wgrad(go, xin, nullptr, Bg, nB, nC, L, g.proj_w, g.proj_b, 1, wg, stream);
     if (rc) return rc;
     // Data gradients back to back (round 5; srf_pwconv_x3f.hip, no prologue): g_x(i) = W_p^T g_y1 + g_x(i + 1) -- the block's
     // input gradient, skip included -- and, from registers, block i - 1's g_f = W_r^T g_x(i): one launch, bit-identical to the
@@ -768,7 +720,7 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
       gf_ready = true;
     } else {
       if (!srf_pw_packed_only(pkT_proj[i], go, Bg, nC, nB, L))
-        rc = srf_transpose_launch(Pu[0], wt, nC, nB, st);          // [nC][nB] -> [nB][nC]
+        rc = srf_transpose_launch(b.proj_w, wt, nC, nB, st);          // [nC][nB] -> [nB][nC]
       if (rc) return rc;
       rc = srf_pw_conv_packed(go, wt, pkT_proj[i], zeros, gx_other, Bg, nC, nB, L, nullptr, gx, nullptr, 0, nullptr, 0, stream);   // + skip
       if (rc) return rc;
@@ -778,15 +730,13 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     gx_other = tmp;
     if (gc) {
       // gx = g_u.  u = x + GlobLN_(b,g)(q), q = TAC_MLP(x):  g_x = g_u + MLP^T(GlobLN^T(g_u))
-      const float* const* Pb = P + pb;
-      float* const* Gb = G + pb;
       const float* q = (const float*)(blk + t.q);
       float* gq = fp(s.gq);
       float* gxm = fp(s.gxm);
-      srf_norm tn{slot(s0 - 1), Pb[9], Pb[10], nullptr};
-      rc = srf_gln_bwd(gx, nullptr, q, &tn, Bg, nB, L, gq, 0, Gb[9], Gb[10], nullptr, sc + s.gln, stream);
+      srf_norm tn{sl.tac, b.tac_g, b.tac_b, nullptr};
+      rc = srf_gln_bwd(gx, nullptr, q, &tn, Bg, nB, L, gq, 0, g.tac_g, g.tac_b, nullptr, sc + s.gln, stream);
       if (rc) return rc;
-      rc = srf_tac_bwd(xbuf(i), gq, Pb, Gb, Bt, G_, nB, 3 * nB, L, gxm, sc + s.tac, stream);
+      rc = srf_tac_bwd(xbuf(i), gq, b.tac, g.tac, Bt, G_, nB, 3 * nB, L, gxm, sc + s.tac, stream);
       if (rc) return rc;
       rc = srf_accumulate_launch(gx, gxm, (long)Bt * B * L, st);
       if (rc) return rc;
@@ -794,16 +744,16 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
   }
   // ---- bottleneck: x_0 = W_b GlobLN(enc) + b_b                  :256-259,292
   {
-    srf_norm ln{slot(0), P[1], P[2], nullptr};
-    rc = srf_pw_wgrad(gx, enc, &ln, Bt, N, B, L, G[3], G[4], 1, wg, stream);
+    srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
+    rc = srf_pw_wgrad(gx, enc, &ln, Bt, N, B, L, gf_.bott_w, gf_.bott_b, 1, wg, stream);
     if (rc) return rc;
     if (!srf_pw_packed_only(pkT_bott, gx, Bt, B, N, L))
-      rc = srf_transpose_launch(P[3], wt, B, N, st);           // [B][N] -> [N][B]
+      rc = srf_transpose_launch(f.bott_w, wt, B, N, st);          // [B][N] -> [N][B]
     if (rc) return rc;
     // g_ln into the (now free) gv buffer, then GlobLN backward accumulated onto the mask path's g_enc
     rc = srf_pw_conv_packed(gx, wt, pkT_bott, zeros, gv, Bt, B, N, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
     if (rc) return rc;
-    rc = srf_gln_bwd(gv, nullptr, enc, &ln, Bt, N, L, genc, 1, G[1], G[2], nullptr, sc + s.gln, stream);
+    rc = srf_gln_bwd(gv, nullptr, enc, &ln, Bt, N, L, genc, 1, gf_.ln_g, gf_.ln_b, nullptr, sc + s.gln, stream);
     if (rc) return rc;
   }
   // ---- the blocks' deferred parameter-gradient reductions, batched
@@ -812,9 +762,9 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
   // ---- encoder weight                                           :247-251,286
   rc = srf_frames_gather(wav, frames, Bt, p->A, p->T, K, h, h, L, p->A * K, stream);
   if (rc) return rc;
-  rc = srf_pw_wgrad(genc, frames, nullptr, Bt, p->A * K, N, L, G[0], nullptr, 1, wg, stream);
+  rc = srf_pw_wgrad(genc, frames, nullptr, Bt, p->A * K, N, L, gf_.enc_w, nullptr, 1, wg, stream);
   if (rc || !grad_wav) return rc;
   // ---- input waveform: g_wav[b,a,t] = sum_{n,l,k: h l + k - h = t} W_e[n,a,k] g_enc[b,n,l]   (the decoder's arithmetic with
   // the encoder's weight [N, A, K] in ConvTranspose1d layout; its scratch fits the forward decoder's: N <= S A N, A <= S A)
-  return srf_decoder(genc, P[0], grad_wav, Bt, N, p->A, K, L, p->T, fp(s.dec), stream);
+  return srf_decoder(genc, f.enc_w, grad_wav, Bt, N, p->A, K, L, p->T, fp(s.dec), stream);
 }

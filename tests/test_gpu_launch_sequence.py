@@ -1,0 +1,166 @@
+"""The ORDERED list of kernel launches of one forward (and of one training step), pinned launch by launch.
+
+The uniform forward, the ragged forward and the training forward share their parameter views, their step helpers and the
+per-level pyramid walk; a change to any of them must leave every configuration's launch sequence what it was.  The expected
+lists below were recorded with ops.kernel_trace (single stream) on the commit BEFORE the walks were folded together and are
+literals: (names of a run of launches, how often the run repeats) pairs, expanded by _expand.  The ragged forwards are
+pinned by name and count in test_gpu_ragged.py / test_gpu_ragged_groupcomm.py.
+
+Shapes: the two smallest golden cases at their own batch and T (per-level pyramid, separate convs, unfused tail -- what the
+big shape never runs), cfg 2 and cfg 3 at batch 32, T = 10400 (the smallest shapes that keep the pairs, the fused pyramid and
+the fused tail: test_gpu_ragged.py, test_gpu_ragged_groupcomm.py), cfg 2 again under the two debug flags that take the pairs
+and the fused pyramid away, and the training step at the shape of the golden case train_cfg2_shape."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_case
+from oracle import weights
+from test_gpu_model import build
+from tests.test_gpu_ops import DEV
+
+pytestmark = pytest.mark.gpu
+
+BATCH, T = 32, 10400
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _lib_loaded():
+    if not torch.cuda.is_available():
+        pytest.fail("gpu-marked test run without a GPU")
+    from sudo_rm_rf_amd import _lib, ops
+    _lib.load()
+    ops.set_kernel_mode(0)
+
+
+def _expand(runs):
+    out = []
+    for names, times in runs:
+        out += list(names) * times
+    return out
+
+
+def _forward_trace(model, x, flags=0):
+    """launch names, in order, of ONE single-stream inference forward of a model whose plan for x's shape already exists
+    (a plan decides its fused pyramid under the flags of its creation: always the default ones here)"""
+    from sudo_rm_rf_amd import ops
+    eng = model._engine()
+    eng.multi_stream = False
+    eng.plan_for(x.shape[0], x.shape[2], torch.device(DEV))
+    with torch.no_grad(), ops.debug_flags(flags), ops.kernel_trace(DEV) as tr:
+        model(x)
+    assert ops._debug_flags == 0, "the debug flags were not put back"
+    return [n for n, _ in tr.launches]
+
+
+def _golden_model(manifest, case, batch=None, T_=None, seed=9120):
+    cfg, sd, wav, _ = load_case(manifest, case)
+    x = torch.from_numpy(wav if batch is None else weights.make_mixture(batch, T_, seed).astype(np.float32))
+    return build(cfg, sd), x.to(DEV)
+
+
+@pytest.fixture(scope="module")
+def cfg2(manifest):
+    return _golden_model(manifest, "cfg2_improved_u16", BATCH, T)
+
+
+def trace_tiny_improved(manifest):
+    return _forward_trace(*_golden_model(manifest, "tiny_improved"))
+
+
+def trace_tiny_groupcomm(manifest):
+    return _forward_trace(*_golden_model(manifest, "tiny_groupcomm"))
+
+
+def trace_cfg3(manifest):
+    return _forward_trace(*_golden_model(manifest, "cfg3_groupcomm_u8", BATCH, T))
+
+
+def trace_train(manifest):
+    """forward + backward of the training step (model.train(), gradients on) at the shape of train_cfg2_shape"""
+    from sudo_rm_rf_amd import ops
+    from test_oracle_golden import train_case
+    cfg, sd, mix, _, _ = train_case("train_cfg2_shape")
+    model = build(cfg, sd).train()
+    with ops.kernel_trace(DEV) as tr:
+        rec = model(mix.to(DEV))
+        (rec * rec).mean().backward()
+    return [n for n, _ in tr.launches]
+
+
+EXPECTED = {
+    "tiny_improved": [      # 20 launches
+        (("zero_fill", "encoder", "pw_conv_generic"), 1),
+        (("pw_conv_small", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_generic", "merge_fast", "pw_conv_small"), 2),
+        (("pw_conv_generic", "transpose", "zero_fill", "pw_conv_mfma", "overlap_add"), 1),
+    ],
+    "tiny_groupcomm": [      # 22 launches
+        (("zero_fill", "encoder", "pw_conv_generic"), 1),
+        (("tac", "pw_conv_small", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_generic", "merge_fast", "pw_conv_small"), 2),
+        (("pw_conv_mfma", "transpose", "zero_fill", "pw_conv_mfma", "overlap_add"), 1),
+    ],
+    "cfg3": [      # 55 launches
+        (("zero_fill", "pack_pw_weights", "encoder", "pw_conv_x3p<1>"), 1),
+        (("tac_mfma", "pw_conv_small", "pyramid_moments", "pyramid_finalize", "pyramid_merge", "pw_conv_small"), 8),
+        (("pack_decoder", "pw_mask_decode", "overlap_add"), 1),
+    ],
+    "train": [      # 387 launches
+        (("pack_pw_weights_f16", "encoder"), 1),
+        (("pw_conv_mfma", "pw_conv_mfma", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save"), 16),
+        (("pw_conv_mfma",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "pack_pw_weights", "frames_gather",
+          "pw_wgrad", "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose",
+          "pw_conv_bf16x3_w4", "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "dwconv5_bwd", "dwconv5_bwd", "dwconv5_bwd", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply",
+          "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 16),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply"), 1),
+        (("gln_bwd_params",), 3),
+        (("dwconv5_bwd_params",), 2),
+        (("frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "cfg2 0": [      # 71 launches
+        (("zero_fill", "pack_pw_weights", "encoder", "pw_pair_x3f<1>"), 1),
+        (("pyramid_moments", "pyramid_finalize", "pyramid_merge", "pw_pair_x3f<2>"), 15),
+        (("pyramid_moments", "pyramid_finalize", "pyramid_merge", "pw_conv_x3p<2>", "pack_decoder", "pw_mask_decode",
+          "overlap_add"), 1),
+    ],
+    "cfg2 NO_PAIRS": [      # 87 launches
+        (("zero_fill", "pack_pw_weights", "encoder", "pw_conv_x3p<1>"), 1),
+        (("pw_conv_x3p<0>", "pyramid_moments", "pyramid_finalize", "pyramid_merge", "pw_conv_x3p<2>"), 16),
+        (("pack_decoder", "pw_mask_decode", "overlap_add"), 1),
+    ],
+    "cfg2 PYR_PER_LEVEL": [      # 135 launches
+        (("zero_fill", "pack_pw_weights", "encoder", "pw_conv_x3p<1>"), 1),
+        (("pw_conv_x3p<0>", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_s2_fast", "dwconv5_s2_fast",
+          "dwconv5_generic", "merge_fast", "pw_conv_x3p<2>"), 16),
+        (("pack_decoder", "pw_mask_decode", "overlap_add"), 1),
+    ],
+    "cfg2 NO_PAIRS|PYR_PER_LEVEL": [      # 135 launches
+        (("zero_fill", "pack_pw_weights", "encoder", "pw_conv_x3p<1>"), 1),
+        (("pw_conv_x3p<0>", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_s2_fast", "dwconv5_s2_fast",
+          "dwconv5_generic", "merge_fast", "pw_conv_x3p<2>"), 16),
+        (("pack_decoder", "pw_mask_decode", "overlap_add"), 1),
+    ],
+}
+
+
+def _check(name, got):
+    want = _expand(EXPECTED[name])
+    first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+    assert got == want, "%s: %d launches (expected %d), first difference at launch %d: got %s, expected %s" % (
+        name, len(got), len(want), first, got[first:first + 4], want[first:first + 4])
+
+
+@pytest.mark.parametrize("fn", [trace_tiny_improved, trace_tiny_groupcomm, trace_cfg3, trace_train],
+                         ids=["tiny_improved", "tiny_groupcomm", "cfg3_groupcomm_u8", "train_cfg2_shape"])
+def test_launch_sequence(manifest, fn):
+    _check(fn.__name__[len("trace_"):], fn(manifest))
+
+
+@pytest.mark.parametrize("flags", ["0", "NO_PAIRS", "PYR_PER_LEVEL", "NO_PAIRS|PYR_PER_LEVEL"])
+def test_launch_sequence_cfg2_under_debug_flags(cfg2, flags):
+    from sudo_rm_rf_amd import ops
+    value = sum(int(getattr(ops.DebugFlag, f)) for f in flags.split("|")) if flags != "0" else 0
+    _check("cfg2 " + flags, _forward_trace(*cfg2, flags=value))
