@@ -380,9 +380,35 @@ __global__ __launch_bounds__(256) void srf_gln_bwd_apply_v4_kernel(GlnBwdArgs a,
   }
 }
 
+// A norm's scratch slice: the per-example fp64 {S1, S2} buckets, then the row partials [rows][4]
+struct GlnBwdSlice {
+  double* bsums;
+  float* rowpart;
+  size_t bsums_bytes, bytes;
+};
+static GlnBwdSlice gln_bwd_slice(void* scratch, int groups, int C) {      // (scratch = NULL: the sizes alone)
+  const size_t bb = sizeof(double) * (size_t)groups * SRF_STAT_BUCKETS * 2;
+  return GlnBwdSlice{reinterpret_cast<double*>(scratch), scratch ? reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + bb) : nullptr,
+                     bb, bb + sizeof(float) * (size_t)groups * C * 4};
+}
 extern "C" size_t srf_gln_bwd_scratch_bytes(int groups, int C) {
-  if (groups <= 0 || C <= 0) return 0;
-  return sizeof(double) * (size_t)groups * SRF_STAT_BUCKETS * 2 + sizeof(float) * (size_t)groups * C * 4;
+  return groups > 0 && C > 0 ? gln_bwd_slice(nullptr, groups, C).bytes : 0;
+}
+
+// A norm's parameter sums, from the row partials in its scratch slice (there already, or before the flush runs): recorded in
+// the context for the batched flush (deferred mode), else folded into the gradients now
+int srf_bwd_ctx_gln_params(SrfBwdCtx* ctx, const srf_norm* norm, void* scratch, int groups, int C, float* dgamma, float* dbeta,
+                           float* dslope, hipStream_t st) {
+  const GlnParamsDesc d{gln_bwd_slice(scratch, groups, C).rowpart, dgamma, dbeta, norm->prelu ? dslope : nullptr, groups, C};
+  if (!d.dgamma && !d.dbeta && !d.dslope) return SRF_OK;
+  if (ctx && ctx->defer) {
+    ctx->gln.push_back(d);
+    return SRF_OK;
+  }
+  hipLaunchKernelGGL(srf_gln_bwd_params_kernel, dim3((unsigned)((C + 31) / 32), (unsigned)((groups + 63) / 64)), dim3(256), 0, st,
+                     d.rowpart, groups, C, d.dgamma, d.dbeta, d.dslope);
+  SRF_CHECK_LAUNCH("gln_bwd_params", st);
+  return SRF_OK;
 }
 
 // gout (+gout2): [groups,C,L] gradient w.r.t. PReLU(GlobLN(x)) (PReLU only if norm->prelu); x: the GlobLN input;
@@ -406,7 +432,6 @@ int srf_gln_bwd_impl(const float* gout, const float* gout2, const float* x, cons
                      int mode, void* stream, SrfBwdCtx* ctx) {
   const int sink_D = ctx ? ctx->merge_D : 0;      // (consumed by this call, whatever happens)
   if (ctx) ctx->merge_D = 0;
-  const bool defer = ctx && ctx->defer;
   const int pre_reduced = mode & 1, no_apply = (mode >> 1) & 1;
   SRF_CHECK_ARG(gout && x && norm && norm->sums && norm->gamma && norm->beta && (gx || no_apply) && scratch,
                 "srf_gln_bwd: null pointer");
@@ -421,14 +446,15 @@ int srf_gln_bwd_impl(const float* gout, const float* gout2, const float* x, cons
   a.x = x;
   a.nrm = srf_norm_dev(norm);
   a.inv_count = 1.0 / ((double)C * (double)L);
-  a.bsums = reinterpret_cast<double*>(scratch);
-  a.rowpart = reinterpret_cast<float*>(a.bsums + (size_t)groups * SRF_STAT_BUCKETS * 2);
+  const GlnBwdSlice sl = gln_bwd_slice(scratch, groups, C);
+  a.bsums = sl.bsums;
+  a.rowpart = sl.rowpart;
   a.gx = gx;
   a.C = C;
   a.L = L;
   a.accumulate = accumulate_gx;
   // (deferred mode: the caller's scratch slices are zeroed once per backward)
-  if (!pre_reduced && !defer) SRF_CHECK_HIP(hipMemsetAsync(a.bsums, 0, sizeof(double) * (size_t)groups * SRF_STAT_BUCKETS * 2, st));
+  if (!pre_reduced && !(ctx && ctx->defer)) SRF_CHECK_HIP(hipMemsetAsync(sl.bsums, 0, sl.bsums_bytes, st));
   const bool v4 = (L % 4) == 0 && srf_aligned16(gout) && srf_aligned16(x) && (!gx || srf_aligned16(gx)) &&
                   (!gout2 || srf_aligned16(gout2)) && srf_kernel_mode() != 1 && !srf_dbg(SRF_DBG_BWD_GLN_SCALAR);
   const dim3 grid4((unsigned)((rows + 3) / 4));
@@ -439,16 +465,8 @@ int srf_gln_bwd_impl(const float* gout, const float* gout2, const float* x, cons
       hipLaunchKernelGGL(srf_gln_bwd_reduce_kernel, dim3((unsigned)rows), dim3(256), 0, st, a);
     SRF_CHECK_LAUNCH("gln_bwd_reduce", st);
   }
-  if (dgamma || dbeta || (dslope && norm->prelu)) {
-    if (defer) {
-      ctx->gln.push_back(GlnParamsDesc{a.rowpart, dgamma, dbeta, norm->prelu ? dslope : nullptr, groups, C});
-    } else {
-      hipLaunchKernelGGL(srf_gln_bwd_params_kernel, dim3((unsigned)((C + 31) / 32), (unsigned)((groups + 63) / 64)),
-                         dim3(256), 0, st, a.rowpart, groups, C, dgamma, dbeta, norm->prelu ? dslope : nullptr);
-      SRF_CHECK_LAUNCH("gln_bwd_params", st);
-    }
-  }
-  if (no_apply) return SRF_OK;
+  const int rc = srf_bwd_ctx_gln_params(ctx, norm, scratch, groups, C, dgamma, dbeta, dslope, st);
+  if (rc || no_apply) return rc;
   if (v4 && sink_D > 1 && (L % (1 << (sink_D - 1))) == 0 && !accumulate_gx) {
     bool ok = true;
     for (int k = 1; k < sink_D; ++k) ok = ok && ctx->merge_lv[k] && srf_aligned16(ctx->merge_lv[k]);
@@ -1100,41 +1118,41 @@ __global__ __launch_bounds__(256) void srf_dwconv5_bwd_params_batch_kernel(DwPar
   srf_dwconv5_bwd_params_body(d.rowpart, d.groups, d.C, d.dw, d.dbias);
 }
 
-// Fold every recorded partial into its parameter gradients (batched launches of up to SRF_PB_MAX reductions) and clear the list.
-int srf_bwd_ctx_flush(SrfBwdCtx* c, hipStream_t st) {
-  for (size_t base = 0; base < c->gln.size(); base += SRF_PB_MAX) {
-    GlnParamsTable t;
-    const int cnt = (int)std::min<size_t>(SRF_PB_MAX, c->gln.size() - base);
-    int maxC = 0, maxG = 0;
-    for (int i = 0; i < SRF_PB_MAX; ++i) {
-      t.d[i] = c->gln[base + (i < cnt ? i : 0)];
-      if (i < cnt) {
-        maxC = std::max(maxC, t.d[i].C);
-        maxG = std::max(maxG, t.d[i].groups);
-      }
-    }
-    hipLaunchKernelGGL(srf_gln_bwd_params_batch_kernel, dim3((unsigned)((maxC + 31) / 32), (unsigned)((maxG + 63) / 64), (unsigned)cnt),
-                       dim3(256), 0, st, t);
-    SRF_CHECK_LAUNCH("gln_bwd_params", st);
+static int dwconv5_bwd_params(SrfBwdCtx* ctx, const DwParamsDesc& d, hipStream_t st) {      // (as gln_bwd_params)
+  if (!d.dw && !d.dbias) return SRF_OK;
+  if (ctx && ctx->defer) {
+    ctx->dw.push_back(d);
+    return SRF_OK;
   }
-  c->gln.clear();
-  for (size_t base = 0; base < c->dw.size(); base += SRF_PB_MAX) {
-    DwParamsTable t;
-    const int cnt = (int)std::min<size_t>(SRF_PB_MAX, c->dw.size() - base);
-    int maxC = 0, maxG = 0;
-    for (int i = 0; i < SRF_PB_MAX; ++i) {
-      t.d[i] = c->dw[base + (i < cnt ? i : 0)];
-      if (i < cnt) {
-        maxC = std::max(maxC, t.d[i].C);
-        maxG = std::max(maxG, t.d[i].groups);
-      }
-    }
-    hipLaunchKernelGGL(srf_dwconv5_bwd_params_batch_kernel, dim3((unsigned)((maxC + 31) / 32), (unsigned)((maxG + 63) / 64), (unsigned)cnt),
-                       dim3(256), 0, st, t);
-    SRF_CHECK_LAUNCH("dwconv5_bwd_params", st);
-  }
-  c->dw.clear();
+  hipLaunchKernelGGL(srf_dwconv5_bwd_params_kernel, dim3((unsigned)((d.C + 31) / 32), (unsigned)((d.groups + 63) / 64)), dim3(256), 0, st,
+                     d.rowpart, d.groups, d.C, d.dw, d.dbias);
+  SRF_CHECK_LAUNCH("dwconv5_bwd_params", st);
   return SRF_OK;
+}
+
+// Fold every recorded partial into its parameter gradients (batched launches of up to SRF_PB_MAX reductions) and clear the list.
+template <typename Table, typename Desc, typename Kernel>
+static int flush_params(std::vector<Desc>& v, Kernel kernel, const char* family, hipStream_t st) {
+  for (size_t base = 0; base < v.size(); base += SRF_PB_MAX) {
+    Table t;
+    const int cnt = (int)std::min<size_t>(SRF_PB_MAX, v.size() - base);
+    int maxC = 0, maxG = 0;
+    for (int i = 0; i < SRF_PB_MAX; ++i) {
+      t.d[i] = v[base + (i < cnt ? i : 0)];
+      if (i < cnt) {
+        maxC = std::max(maxC, t.d[i].C);
+        maxG = std::max(maxG, t.d[i].groups);
+      }
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((maxC + 31) / 32), (unsigned)((maxG + 63) / 64), (unsigned)cnt), dim3(256), 0, st, t);
+    SRF_CHECK_LAUNCH(family, st);
+  }
+  v.clear();
+  return SRF_OK;
+}
+int srf_bwd_ctx_flush(SrfBwdCtx* c, hipStream_t st) {
+  const int rc = flush_params<GlnParamsTable>(c->gln, srf_gln_bwd_params_batch_kernel, "gln_bwd_params", st);
+  return rc ? rc : flush_params<DwParamsTable>(c->dw, srf_dwconv5_bwd_params_batch_kernel, "dwconv5_bwd_params", st);
 }
 
 extern "C" size_t srf_dwconv5_bwd_scratch_bytes(int groups, int C) {
@@ -1146,25 +1164,31 @@ extern "C" size_t srf_dwconv5_bwd_scratch_bytes(int groups, int C) {
 // dbias [C] are ACCUMULATED into.
 // gln_scratch != NULL asks for the fused form: gin <- conv input gradient + gadd (gadd may be NULL), and the reduce
 // pass of srf_gln_bwd for the prologue norm `in_norm` over that complete gradient written into gln_scratch (layout of
-// srf_gln_bwd's scratch).  *fused reports whether that happened (row kernel preconditions); when it did not, gin
-// holds the plain conv input gradient and the caller runs the unfused sequence.
+// srf_gln_bwd's scratch).  Whether that happens is srf_dwconv5_bwd_form's answer (the caller asks it beforehand, through
+// srf_dwconv5_bwd_rowwise_ok); when it does not, gin holds the plain conv input gradient and the caller runs the unfused sequence.
 // ax != NULL asks for the apply-on-load form on top (only together with the fused form; check
 // srf_dwconv5_bwd_rowwise_ok first): gd is then the gradient w.r.t. the OUTPUT of the norm `anorm` that follows this
 // conv, ax that norm's input (= this conv's output) and a_scratch its reduced sums (srf_gln_bwd_impl mode bit 1).
+// THE choice of the kernel form (srf_dwconv5_bwd_impl takes it through this function, and so does whoever must know beforehand:
+// srf_dwconv5_bwd_rowwise_ok for srf_backward's path table).  aligned: gd, xin and gin (if any) are 16-byte aligned;
+// fuse_asked: the fused form was asked for and can be served (gln_scratch, gin, a complete in_norm, gadd absent or aligned).
+SrfDwBwdForm srf_dwconv5_bwd_form(int Lin, int stride, bool aligned, bool fuse_asked) {
+  if ((Lin % 4) != 0 || !aligned || srf_kernel_mode() == 1) return SRF_DW_BWD_CHUNKED;
+  // stride 2 with an odd output count (Lin % 8 == 4) keeps the chunked kernel: its float2 loads assume Lout = Lin / 2
+  if ((stride == 2 && ((Lin - 1) / 2 + 1) * 2 != Lin) || srf_dbg(SRF_DBG_BWD_DW_CHUNKED)) return SRF_DW_BWD_CHUNKED_FAST;
+  return fuse_asked && !srf_dbg(SRF_DBG_BWD_GLN_SCALAR) ? SRF_DW_BWD_ROW_FUSED : SRF_DW_BWD_ROW;
+}
+// the fused row kernel (and with it the apply-on-load form) will serve a call with these operands
 bool srf_dwconv5_bwd_rowwise_ok(int Lin, int stride, const void* const* ptrs, int nptrs) {
-  if ((Lin % 4) != 0 || srf_kernel_mode() == 1 || srf_dbg(SRF_DBG_BWD_DW_CHUNKED | SRF_DBG_BWD_GLN_SCALAR)) return false;
-  if (stride == 2 && ((Lin - 1) / 2 + 1) * 2 != Lin) return false;
-  for (int i = 0; i < nptrs; ++i)
-    if (ptrs[i] && !srf_aligned16(ptrs[i])) return false;
-  return true;
+  bool aligned = true;
+  for (int i = 0; i < nptrs; ++i) aligned = aligned && (!ptrs[i] || srf_aligned16(ptrs[i]));
+  return srf_dwconv5_bwd_form(Lin, stride, aligned, true) == SRF_DW_BWD_ROW_FUSED;
 }
 
 int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_norm, const float* w, int groups, int C,
                          int Lin, int stride, float* gin, float* dw, float* dbias, void* scratch, const float* gadd,
-                         void* gln_scratch, int* fused, const float* ax, const srf_norm* anorm, const void* a_scratch,
+                         void* gln_scratch, const float* ax, const srf_norm* anorm, const void* a_scratch,
                          void* stream, SrfBwdCtx* ctx) {
-  if (fused) *fused = 0;
-  const bool defer = ctx && ctx->defer;
   SRF_CHECK_ARG(gd && xin && w && scratch, "srf_dwconv5_bwd: null pointer");
   SRF_CHECK_ARG(groups > 0 && C > 0 && Lin > 0 && (stride == 1 || stride == 2), "srf_dwconv5_bwd: bad sizes");
   const long rows = (long)groups * C;
@@ -1190,23 +1214,22 @@ int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_n
   a.a_bsums = nullptr;
   hipStream_t st = (hipStream_t)stream;
   SRF_CHECK_ARG(groups <= 65535 && C <= 65535, "srf_dwconv5_bwd: groups / channels exceed 65535");
-  const bool fast = (Lin % 4) == 0 && srf_aligned16(gd) && srf_aligned16(xin) && (!gin || srf_aligned16(gin)) &&
-                    srf_kernel_mode() != 1;
+  const SrfDwBwdForm form = srf_dwconv5_bwd_form(
+      Lin, stride, srf_aligned16(gd) && srf_aligned16(xin) && (!gin || srf_aligned16(gin)),
+      gln_scratch && gin && in_norm && in_norm->sums && in_norm->gamma && in_norm->beta && (!gadd || srf_aligned16(gadd)));
+  const bool fast = form != SRF_DW_BWD_CHUNKED, fuse = form == SRF_DW_BWD_ROW_FUSED;
   const int per_block = fast ? 1024 : 2048;
   const int chunks = (Lin + per_block - 1) / per_block;
-  // stride 2 with an odd output count (Lin % 8 == 4) keeps the chunked kernel: its float2 loads assume Lout = Lin / 2
-  const bool rowwise = fast && (stride == 1 || a.Lout * 2 == Lin) && !srf_dbg(SRF_DBG_BWD_DW_CHUNKED);
-  if (rowwise) {
+  if (form == SRF_DW_BWD_ROW || fuse) {
     const dim3 grid4((unsigned)((rows + 3) / 4));
-    const bool fuse = gln_scratch && gin && in_norm && in_norm->sums && in_norm->gamma && in_norm->beta &&
-                      (!gadd || srf_aligned16(gadd)) && !srf_dbg(SRF_DBG_BWD_GLN_SCALAR);
     SRF_CHECK_ARG(!ax || (fuse && anorm && anorm->sums && anorm->gamma && anorm->beta && a_scratch && srf_aligned16(ax)),
                   "srf_dwconv5_bwd: apply-on-load needs the fused row kernel");
     if (fuse) {
       a.gadd = gadd;
-      a.nrm_bsums = reinterpret_cast<double*>(gln_scratch);
-      a.nrm_rowpart = reinterpret_cast<float*>(a.nrm_bsums + (size_t)groups * SRF_STAT_BUCKETS * 2);
-      if (!defer) SRF_CHECK_HIP(hipMemsetAsync(a.nrm_bsums, 0, sizeof(double) * (size_t)groups * SRF_STAT_BUCKETS * 2, st));
+      const GlnBwdSlice sl = gln_bwd_slice(gln_scratch, groups, C);
+      a.nrm_bsums = sl.bsums;
+      a.nrm_rowpart = sl.rowpart;
+      if (!(ctx && ctx->defer)) SRF_CHECK_HIP(hipMemsetAsync(sl.bsums, 0, sl.bsums_bytes, st));
       if (ax) {
         a.ax = ax;
         a.anrm = srf_norm_dev(anorm);
@@ -1221,7 +1244,6 @@ int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_n
       } else {
         hipLaunchKernelGGL((srf_dwconv5_bwd_row_kernel<2, true, false>), grid4, dim3(256), 0, st, a, rows);
       }
-      if (fused) *fused = 1;
     } else if (stride == 1) {
       hipLaunchKernelGGL((srf_dwconv5_bwd_row_kernel<1, false, false>), grid4, dim3(256), 0, st, a, rows);
     } else {
@@ -1242,16 +1264,7 @@ int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_n
     hipLaunchKernelGGL(srf_dwconv5_bwd_kernel<2>, grid, dim3(256), 0, st, a);
   SRF_CHECK_LAUNCH("dwconv5_bwd", st);
   }
-  if (dw || dbias) {
-    if (defer) {
-      ctx->dw.push_back(DwParamsDesc{a.rowpart, dw, dbias, groups, C});
-    } else {
-      hipLaunchKernelGGL(srf_dwconv5_bwd_params_kernel, dim3((unsigned)((C + 31) / 32), (unsigned)((groups + 63) / 64)),
-                         dim3(256), 0, st, a.rowpart, groups, C, dw, dbias);
-      SRF_CHECK_LAUNCH("dwconv5_bwd_params", st);
-    }
-  }
-  return SRF_OK;
+  return dwconv5_bwd_params(ctx, DwParamsDesc{a.rowpart, dw, dbias, groups, C}, st);
 }
 
 extern "C" int srf_dwconv5_bwd(const float* gd, const float* xin, const srf_norm* in_norm, const float* w, int groups,
@@ -1259,7 +1272,7 @@ extern "C" int srf_dwconv5_bwd(const float* gd, const float* xin, const srf_norm
                                void* stream) {
   SRF_CHECK_ALIGNED16("srf_dwconv5_bwd", {"in_norm.sums", in_norm ? in_norm->sums : nullptr});     // (read as pairs of doubles)
   return srf_dwconv5_bwd_impl(gd, xin, in_norm, w, groups, C, Lin, stride, gin, dw, dbias, scratch, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, nullptr, stream, nullptr);
+                              nullptr, nullptr, nullptr, stream, nullptr);
 }
 
 // =============================================================================================
@@ -1453,27 +1466,20 @@ int srf_bwd_level0_proj(const float* G0, const float* y1, const srf_norm* pn, co
   a.n0 = srf_norm_dev(n0);
   a.pn_inv = a.n0_inv = 1.0 / ((double)C * (double)L);
   a.n0_bsums = reinterpret_cast<const double*>(n0_scratch);
-  a.pn_bsums = reinterpret_cast<double*>(pn_scratch);
-  a.pn_rowpart = reinterpret_cast<float*>(a.pn_bsums + (size_t)groups * SRF_STAT_BUCKETS * 2);
+  const GlnBwdSlice psl = gln_bwd_slice(pn_scratch, groups, C);
+  a.pn_bsums = psl.bsums;
+  a.pn_rowpart = psl.rowpart;
   a.w = w0;
   a.bias = b0;
   a.dw_rowpart = reinterpret_cast<float*>(dw_scratch);
   a.C = C;
   a.L = L;
-  const bool defer = ctx && ctx->defer;
-  if (!defer) SRF_CHECK_HIP(hipMemsetAsync(a.pn_bsums, 0, sizeof(double) * (size_t)groups * SRF_STAT_BUCKETS * 2, st));
+  if (!(ctx && ctx->defer)) SRF_CHECK_HIP(hipMemsetAsync(psl.bsums, 0, psl.bsums_bytes, st));
   const dim3 grid4((unsigned)((rows + 3) / 4));
   hipLaunchKernelGGL(srf_bwd_l0p_kernel<false>, grid4, dim3(256), 0, st, a, rows);
   SRF_CHECK_LAUNCH("bwd_l0p_reduce", st);
-  if (dw || dbias) {
-    if (defer) {
-      ctx->dw.push_back(DwParamsDesc{a.dw_rowpart, dw, dbias, groups, C});
-    } else {
-      hipLaunchKernelGGL(srf_dwconv5_bwd_params_kernel, dim3((unsigned)((C + 31) / 32), (unsigned)((groups + 63) / 64)), dim3(256),
-                         0, st, a.dw_rowpart, groups, C, dw, dbias);
-      SRF_CHECK_LAUNCH("dwconv5_bwd_params", st);
-    }
-  }
+  const int rc = dwconv5_bwd_params(ctx, DwParamsDesc{a.dw_rowpart, dw, dbias, groups, C}, st);
+  if (rc) return rc;
   hipLaunchKernelGGL(srf_bwd_l0p_kernel<true>, grid4, dim3(256), 0, st, a, rows);
   SRF_CHECK_LAUNCH("bwd_l0p_apply", st);
   return SRF_OK;
@@ -1661,28 +1667,19 @@ int srf_bwd_level1_head(const float* G1, const float* d1, const srf_norm* n1, co
   a.inv0 = 1.0 / ((double)C * (double)L);
   a.inv1 = 1.0 / ((double)C * (double)(L >> 1));
   a.n1_bsums = reinterpret_cast<const double*>(n1_scratch);
-  a.n0_bsums = reinterpret_cast<double*>(n0_scratch);
-  a.n0_rowpart = reinterpret_cast<float*>(a.n0_bsums + (size_t)groups * SRF_STAT_BUCKETS * 2);
+  const GlnBwdSlice sl0 = gln_bwd_slice(n0_scratch, groups, C);
+  a.n0_bsums = sl0.bsums;
+  a.n0_rowpart = sl0.rowpart;
   a.w0 = w0;
   a.b0 = b0;
   a.w1 = w1;
   a.dw_rowpart = reinterpret_cast<float*>(dw_scratch);
   a.C = C;
   a.L = L;
-  const bool defer = ctx && ctx->defer;
-  if (!defer) SRF_CHECK_HIP(hipMemsetAsync(a.n0_bsums, 0, sizeof(double) * (size_t)groups * SRF_STAT_BUCKETS * 2, st));
+  if (!(ctx && ctx->defer)) SRF_CHECK_HIP(hipMemsetAsync(sl0.bsums, 0, sl0.bsums_bytes, st));
   hipLaunchKernelGGL(srf_bwd_l1h_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, rows);
   SRF_CHECK_LAUNCH("bwd_l1h", st);
-  if (dw1 || db1) {
-    if (defer) {
-      ctx->dw.push_back(DwParamsDesc{a.dw_rowpart, dw1, db1, groups, C});
-    } else {
-      hipLaunchKernelGGL(srf_dwconv5_bwd_params_kernel, dim3((unsigned)((C + 31) / 32), (unsigned)((groups + 63) / 64)), dim3(256),
-                         0, st, a.dw_rowpart, groups, C, dw1, db1);
-      SRF_CHECK_LAUNCH("dwconv5_bwd_params", st);
-    }
-  }
-  return SRF_OK;
+  return dwconv5_bwd_params(ctx, DwParamsDesc{a.dw_rowpart, dw1, db1, groups, C}, st);
 }
 
 // =============================================================================================

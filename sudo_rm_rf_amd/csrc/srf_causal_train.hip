@@ -331,10 +331,7 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   }
   // g_x = W^T g (+ residual): cin_d -> cout_d, w the forward weight [cin_d][cout_d]
   auto data_grad = [&](const float* g, const float* w, const void* pk, float* y, int cin_d, int cout_d, const float* residual) -> int {
-    int r = SRF_OK;
-    if (!srf_pw_packed_only(pk, g, Bt, cin_d, cout_d, L)) r = srf_transpose_launch(w, wt, cin_d, cout_d, st);
-    if (r) return r;
-    return srf_pw_conv_packed(g, wt, pk, zeros, y, Bt, cin_d, cout_d, L, nullptr, residual, nullptr, 0, nullptr, 0, stream);
+    return srf_pw_data_grad(g, w, pk, wt, zeros, y, Bt, cin_d, cout_d, L, residual, st);
   };
   // ---- decoder: out = overlap_add(W_d^T PReLU_c(m))
   float* frames = fp(s.frames);

@@ -88,6 +88,10 @@ int srf_mask_decode(const float* x, const float* w, const void* w_packed, const 
 int srf_pack_pw_weights_transposed(const float* const* w, void* const* packed, const int* Cout, const int* Cin, int n,
                                    hipStream_t st);
 bool srf_pw_packed_only(const void* w_packed, const float* x, int Bt, int Cin, int Cout, int L);
+// A backward's data-gradient GEMM gx = W^T g (+ skip), Cin -> Cout, W the FORWARD weight [Cin][Cout]: from the packed image
+// of W^T where that serves the whole launch (srf_pw_packed_only), else from its fp32 transpose, made in `wt` first
+int srf_pw_data_grad(const float* g, const float* w, const void* wT_packed, float* wt, const float* zero_bias, float* gx, int Bt,
+                     int Cin, int Cout, int L, const float* skip, hipStream_t st);
 
 // ---- srf_pwconv_x3w.hip (the 256 x 128 kernel), _x3p.hip (its paired-block form), _x3f.hip (the fused pair), _small.hip
 bool srf_x3w_supported(int Bt, int pro);
@@ -124,11 +128,18 @@ int srf_bwd_ctx_flush(SrfBwdCtx* c, hipStream_t st);
 int srf_gln_bwd_impl(const float* gout, const float* gout2, const float* x, const srf_norm* norm, int groups, int C,
                      int L, float* gx, int accumulate_gx, float* dgamma, float* dbeta, float* dslope, void* scratch,
                      int mode, void* stream, SrfBwdCtx* ctx);
+// one norm's parameter sums from the row partials of its scratch slice: recorded for the flush when the context defers, else now
+int srf_bwd_ctx_gln_params(SrfBwdCtx* ctx, const srf_norm* norm, void* scratch, int groups, int C, float* dgamma, float* dbeta,
+                           float* dslope, hipStream_t st);
+// the kernel form a srf_dwconv5_bwd_impl call takes: the chunked kernels (scalar / float4), the row kernel, the row kernel with
+// the input norm's reduce pass fused in (what apply-on-load needs)
+enum SrfDwBwdForm { SRF_DW_BWD_CHUNKED, SRF_DW_BWD_CHUNKED_FAST, SRF_DW_BWD_ROW, SRF_DW_BWD_ROW_FUSED };
+SrfDwBwdForm srf_dwconv5_bwd_form(int Lin, int stride, bool aligned, bool fuse_asked);
 bool srf_dwconv5_bwd_rowwise_ok(int Lin, int stride, const void* const* ptrs, int nptrs);
 int srf_dwconv5_bwd_impl(const float* gd, const float* xin, const srf_norm* in_norm, const float* w, int groups, int C,
                          int Lin, int stride, float* gin, float* dw, float* dbias, void* scratch, const float* gadd,
-                         void* gln_scratch, int* fused, const float* ax, const srf_norm* anorm, const void* a_scratch,
-                         void* stream, SrfBwdCtx* ctx);
+                         void* gln_scratch, const float* ax, const srf_norm* anorm, const void* a_scratch, void* stream,
+                         SrfBwdCtx* ctx);
 bool srf_bwd_level0_proj_ok(int L, const void* const* ptrs, int nptrs);
 bool srf_bwd_level0_proj_shape_ok(int L, const void* const* ptrs, int nptrs);
 int srf_bwd_level0_proj(const float* G0, const float* y1, const srf_norm* pn, const srf_norm* n0, const float* w0, const float* b0,

@@ -600,6 +600,14 @@ bool srf_pw_packed_only(const void* w_packed, const float* x, int Bt, int Cin, i
   if (srf_pw_small_supported(Cin, Cout, L)) return false;     // (the thin-shape kernel has precedence and reads the fp32 weights)
   return srf_pw_256_serves(w_packed, x, Bt, Cin, Cout, L, 0);
 }
+int srf_pw_data_grad(const float* g, const float* w, const void* wT_packed, float* wt, const float* zero_bias, float* gx, int Bt,
+                     int Cin, int Cout, int L, const float* skip, hipStream_t st) {
+  if (!srf_pw_packed_only(wT_packed, g, Bt, Cin, Cout, L)) {
+    const int rc = srf_transpose_launch(w, wt, Cin, Cout, st);     // [Cin][Cout] -> [Cout][Cin]
+    if (rc) return rc;
+  }
+  return srf_pw_conv_packed(g, wt, wT_packed, zero_bias, gx, Bt, Cin, Cout, L, nullptr, skip, nullptr, 0, nullptr, 0, st);
+}
 
 // (library-internal: the backward's data-gradient GEMMs) w[i] is the FORWARD weight [Cin][Cout]; the image is that of its
 // transpose [Cout][Cin] -- no transposed copy is made

@@ -11,10 +11,16 @@
 //                       pre-activation m and the masked encoding v.
 //   srf_backward      : walks the graph in reverse; parameter gradients are ACCUMULATED into `grads` (same
 //                       order / shapes as the parameters; the caller zeroes them, like optimizer.zero_grad()).
+//                       In stages over one BwdWalk: tail (decoder, mask, mask_net), U x block (res_conv, the pyramid,
+//                       proj_1x1, GroupComm: TAC), front (bottleneck, the deferred parameter sums, encoder).  How a
+//                       block's pyramid runs -- which kernel form per level -- is a table (PyrBwdPath) filled before
+//                       the first launch, from the shape, the kernel mode, the debug flags and the forward's record;
+//                       a backward that cannot follow its forward is refused there, with `grads` untouched.
 // GroupComm: each block is preceded by TAC (MLP + TAC_norm + residual, groupcomm_sudormrf_v2.py:356-384) and the
 // U-ConvBlock runs on the (batch x group)-folded tensor with channels / G (:388-418); `saved` additionally keeps the
 // TAC MLP output q and the block input u = x + GlobLN(q).
 #include <map>
+#include <memory>
 #include <mutex>
 
 #include "srf_plan.h"
@@ -414,73 +420,35 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
   return rc;
 }
 
-static int backward_impl(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
-                         const float* grad_out, const void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                         float* grad_wav, void* stream);
-extern "C" int srf_backward(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
-                            const float* grad_out, const void* saved, size_t saved_bytes, void* scratch,
-                            size_t scratch_bytes, void* stream) {
-  return backward_impl(p, P, G, num_params, wav, grad_out, saved, saved_bytes, scratch, scratch_bytes, nullptr, stream);
-}
-// ... and the gradient w.r.t. the input waveform on top (ABI 15; the reference's autograd produces it when the caller's
-// mixture requires grad, improved_sudormrf.py:283-301 is plain ATen): grad_wav [Bt, in_audio_channels, T] (overwritten) =
-// the encoder's transposed convolution (:247-251,286; the right zero-pad of :303-314 is a crop) of the gradient w.r.t.
-// the encoder output, which the backward forms anyway (mask path + GlobLN path).
-extern "C" int srf_backward_wav(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
-                                const float* grad_out, const void* saved, size_t saved_bytes, void* scratch,
-                                size_t scratch_bytes, float* grad_wav, void* stream) {
-  SRF_CHECK_ARG(grad_wav, "srf_backward_wav: null grad_wav");
-  return backward_impl(p, P, G, num_params, wav, grad_out, saved, saved_bytes, scratch, scratch_bytes, grad_wav, stream);
-}
-static int backward_impl(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
-                         const float* grad_out, const void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
-                         float* grad_wav, void* stream) {
-  if (causal_refused(p, grad_wav ? "srf_backward_wav" : "srf_backward")) return SRF_EINVAL;
-  SRF_CHECK_ARG(p && P && G && wav && grad_out && saved && scratch, "srf_backward: null pointer");
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_backward: expected %d parameter tensors, got %d", p->n_params, num_params);
-  int rc = train_check(p, "srf_backward");
-  if (rc) return rc;
-  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] && G[i], "srf_backward: parameter / gradient %d is null", i);
-  const TrainLayout t = train_layout(p);
-  const ScratchLayout s = scratch_layout(p);
-  SRF_CHECK_ARG(saved_bytes >= t.total && scratch_bytes >= s.total, "srf_backward: saved / scratch buffer too small");
-  const srf_config& c = p->cfg;
-  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, h = K / 2;
-  const int Bt = p->Bt, L = p->L, B = c.out_channels, C = c.in_channels, SA = p->SA, SAN = p->SA * N;
-  const char* sv = (const char*)saved;
-  char* sc = (char*)scratch;
-  hipStream_t st = (hipStream_t)stream;
-  double* stats = (double*)(sv + t.stats);      // (the slot of ln is the first)
-  auto xbuf = [&](int i) { return (const float*)(sv + t.x0 + t.x_stride * i); };
-  auto fp = [&](size_t o) { return (float*)(sc + o); };
-  const float* enc = (const float*)(sv + t.enc);
-  const float* m = (const float*)(sv + t.m);
-  const float* v = (const float*)(sv + t.v);
-  float* zeros = fp(s.zeros);
-  float* wt = fp(s.wt);
-  void* wg = sc + s.wg;
-  const size_t zmax = max3(C, SAN, N);
-  SRF_CHECK_HIP(hipMemsetAsync(zeros, 0, sizeof(float) * zmax, st));
-  // the blocks' norm / conv backwards get one scratch slice per call (statistic buckets zeroed here, once) and leave their
-  // parameter-gradient reductions to one batched flush after the block loop
-  // (the WHOLE arena, 75 MB at cfg 2 / 170 MB at cfg 4 = 0.1 % of a step, not just the fp64 buckets at the head of each norm slice
-  // -- ADVICE r3: the chunked fallback kernels (debug flags 1<<29 / 1<<30, rows beyond the row kernels' limits) accumulate
-  // their row partials with atomicAdd and rely on zeroed slices)
-  SRF_CHECK_HIP(hipMemsetAsync(sc + s.arena, 0, s.arena_bytes, st));
-  struct BwdCtxOwner {          // (freed on every exit path: a backward that fails half-way leaves nothing behind)
-    SrfBwdCtx* c = srf_bwd_ctx_new();
-    ~BwdCtxOwner() { srf_bwd_ctx_free(c); }
-  } ctx_owner;
-  SrfBwdCtx* ctx = ctx_owner.c;
+// ---- srf_backward: the graph in reverse, in stages over one walk state (as the forwards of srf_api.hip) ----------------------
 
-  // Levels 1 and 0 of every block follow the forward that filled `saved` (its record; no record -- a buffer no srf_forward_train
-  // of this process filled, or one evicted from the table -- is taken as "d_0 may be missing").  d_0 left out: the fused head must
-  // run, whatever the kernel mode / debug flags say now; what it needs of the row kernels (level 1) and of the shape is checked
-  // here, before the first launch, so a backward that cannot follow its forward fails without touching `grads`.
+// How one block's pyramid backward runs, level by level, decided ONCE per backward and before any device work.  Level k's conv
+// backward can also produce the COMPLETE gradient w.r.t. its (normalised) input -- its own input gradient + the merge part -- and
+// the reduce pass of that input's GlobLN backward (the input tensor is in its registers); and it can evaluate the apply pass of
+// its OWN level's norm on load.  Where the row kernels serve every level that is one conv kernel per level, g_d never written.
+enum PyrBwdForm {
+  PYR_BWD_SEQ,          // norm backward (reduce unless pre-reduced, apply into the g_d buffer), then the conv backward on the chunked kernels
+  PYR_BWD_ROW,          // the same two calls; the conv's row kernel also reduces the norm of the level below
+  PYR_BWD_ROW_ONLOAD,   // norm: reduce only (if at all); the row kernel applies it on load
+  PYR_BWD_HEAD1,        // level 1 on the fused-head kernel: as ROW_ONLOAD with conv 1's input re-computed from y1 (d_0 is not read)
+  PYR_BWD_HEAD0,        // level 0 + proj_1x1's norm as the fused head (two passes over {G_0, y1}); g_y1 lands in the g_d buffer
+};
+struct PyrBwdPath {
+  PyrBwdForm form[SRF_MAX_DEPTH];
+  bool pre[SRF_MAX_DEPTH];    // level k's incoming gradient arrives complete in ONE buffer, its norm's reduce pass done (by level k + 1)
+  bool proj_pre;              // ... and proj_1x1's norm (by level 0; without the head)
+};
+
+// The path is a function of L, D, the kernel mode and debug flags of NOW, where `saved` and `scratch` lie (every operand is a
+// 256-byte-aligned slice of one of the two: the predicates get the two bases) and of the forward that filled `saved`: levels 1
+// and 0 follow its record; no record -- a buffer no srf_forward_train of this process filled, or one evicted from the table -- is
+// taken as "d_0 may be missing".  d_0 left out: the fused head must run, whatever the mode / flags say now.  This is the ONE place
+// where a backward that cannot follow its forward is refused: nothing has been launched, `grads` is untouched.
+static int pyr_bwd_path(const srf_plan* p, const void* saved, const void* scratch, const char* who, PyrBwdPath* path) {
+  const int D = p->cfg.upsampling_depth, L = p->L;
   TrainRec rec{};
   const bool known = train_rec_get(saved, &rec);
-  const bool d0_missing = c.upsampling_depth > 1 && (!known || rec.skip_d0);
-  const char* who = grad_wav ? "srf_backward_wav" : "srf_backward";
+  const bool d0_missing = D > 1 && (!known || rec.skip_d0);
   auto head_lost = [&](const char* where) {
     if (known)
       srf_set_error("%s: the srf_forward_train that filled `saved` left d_0 out for the fused backward head (kernel mode %d, debug "
@@ -496,14 +464,77 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     if (!srf_bwd_level0_proj_shape_ok(L, nullptr, 0)) return head_lost("at level 0 (L)");
     if (!srf_dwconv5_bwd_rowwise_ok(L, 2, nullptr, 0)) return head_lost("at level 1 (the row kernels)");
   }
+  const void* base[2] = {saved, scratch};
+  bool head = d0_missing || train_fused_head(p);   // (re-computes d_0: needed when the forward left it out, harmless otherwise)
+  bool pre = false;
+  for (int k = D - 1; k >= 0; --k) {
+    path->pre[k] = pre;
+    if (k == 0 && head) {     // (head still set: level 1 ran on the head kernel, so G_0 is complete and norm 0 reduced)
+      if (pre && srf_bwd_level0_proj_shape_ok(L, base, 2)) {
+        path->form[0] = PYR_BWD_HEAD0;
+        break;
+      }
+      if (d0_missing) return head_lost("at level 0");
+    }
+    const bool rows = srf_dwconv5_bwd_rowwise_ok(k ? L >> (k - 1) : L, k ? 2 : 1, base, 2);
+    // apply-on-load needs the level's gradient in one buffer: pre-reduced, or the deepest level's (only the merge part)
+    const bool on_load = rows && (pre || k == D - 1);
+    if (k == 1 && head && !on_load) {
+      if (d0_missing) return head_lost("at level 1 (the row kernels)");
+      head = false;           // d_0 is in `saved`: levels 1 and 0 on the conv kernels
+    }
+    path->form[k] = (k == 1 && head) ? PYR_BWD_HEAD1 : on_load ? PYR_BWD_ROW_ONLOAD : rows ? PYR_BWD_ROW : PYR_BWD_SEQ;
+    pre = rows;
+  }
+  path->proj_pre = pre;
+  return SRF_OK;
+}
 
-  const SrfFront<const float> f = plan_front(P);
-  const SrfFront<float> gf_ = plan_front(G);
-  const SrfTail<const float> tl = plan_tail(p, P);
-  const SrfTail<float> gtl = plan_tail(p, G);
-  // The data-gradient GEMMs g_x = W^T g run on the 256 x 128 split-bf16 kernel with the TRANSPOSED weights pre-split into its
-  // stage images, all of them in one launch here (shapes / launches that kernel does not take keep the transposed fp32 copy
-  // `wt` and the 128 x 128 kernels).
+// One backward: what its stages share, and the stages
+struct BwdWalk {
+  const srf_plan* p;
+  const float* const* P;      // parameters, and their gradients (accumulated into)
+  float* const* G;
+  const TrainLayout t;
+  const ScratchLayout s;
+  const char* sv;
+  char* sc;
+  hipStream_t st;
+  SrfBwdCtx* ctx;
+  const int D, U, N, K, Bt, L, B, SA, SAN, Bg, nB, nC;
+  PyrBwdPath path;
+  const void *pkT_mask, *pkT_bott;              // packed images of the TRANSPOSED weights (NULL: none)
+  std::vector<const void*> pkT_res, pkT_proj;
+  float *gx, *gx_other;       // gradient w.r.t. the residual stream x_i (ping-pong)
+  float *go, *gd;             // a block's g_o / g_y1 and its g_d buffer (they swap roles after a block that ran the fused head)
+  bool gf_ready;              // block i's g_f was produced by block i + 1's data-gradient pair
+
+  BwdWalk(const srf_plan* p, const float* const* P, float* const* G, const void* saved, void* scratch, void* stream, SrfBwdCtx* ctx)
+      : p(p), P(P), G(G), t(train_layout(p)), s(scratch_layout(p)), sv((const char*)saved), sc((char*)scratch),
+        st((hipStream_t)stream), ctx(ctx), D(p->cfg.upsampling_depth), U(p->cfg.num_blocks), N(p->cfg.enc_num_basis),
+        K(p->cfg.enc_kernel_size), Bt(p->Bt), L(p->L), B(p->cfg.out_channels), SA(p->SA), SAN(p->SA * N), Bg(p->Bg), nB(p->nB),
+        nC(p->nC), gx(fp(s.gxa)), gx_other(fp(s.gxb)), go(fp(s.go)), gd(fp(s.gd)), gf_ready(false) {}
+  float* fp(size_t o) const { return (float*)(sc + o); }
+  double* stats() const { return (double*)(sv + t.stats); }      // (the slot of ln is the first)
+  const float* xbuf(int i) const { return (const float*)(sv + t.x0 + t.x_stride * i); }
+  const float* enc() const { return (const float*)(sv + t.enc); }
+  const char* blk(int i) const { return sv + t.blk0 + t.blk_stride * i; }
+  // g = W^T g_in (+ skip) of a 1x1 conv with forward weight w [cin][cout]
+  int data_grad(const float* g_in, const float* w, const void* pkT, float* g, int batch, int cin, int cout, const float* skip) const {
+    return srf_pw_data_grad(g_in, w, pkT, fp(s.wt), fp(s.zeros), g, batch, cin, cout, L, skip, st);
+  }
+  int pack_weights();
+  int tail(const float* grad_out);
+  int block(int i);
+  int block_pyramid(int i);
+  int block_tac(int i);
+  int front(const float* wav, float* grad_wav);
+};
+
+// The data-gradient GEMMs g_x = W^T g run on the 256 x 128 split-bf16 kernel with the TRANSPOSED weights pre-split into its
+// stage images, all of them in one launch here (shapes / launches that kernel does not take keep the transposed fp32 copy
+// `wt` and the 128 x 128 kernels).
+int BwdWalk::pack_weights() {
   std::vector<const float*> pk_w;
   std::vector<void*> pk_d;
   std::vector<int> pk_co, pk_ci;
@@ -519,252 +550,240 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
     pk_ci.push_back(cin_d);
     return d;
   };
-  const void* pkT_mask = packT(tl.mask_w, B, SAN);
-  const void* pkT_bott = packT(f.bott_w, N, B);
-  std::vector<const void*> pkT_res(U, nullptr), pkT_proj(U, nullptr);
+  pkT_mask = packT(plan_tail(p, P).mask_w, B, SAN);
+  pkT_bott = packT(plan_front(P).bott_w, N, B);
+  pkT_res.assign(U, nullptr);
+  pkT_proj.assign(U, nullptr);
   for (int i = 0; i < U; ++i) {
     const SrfBlock<const float> b = plan_block(p, P, i);
-    pkT_res[i] = packT(b.res_w, p->nC, p->nB);               // res_conv: forward [nB][nC], gradient GEMM nB -> nC
-    pkT_proj[i] = packT(b.proj_w, p->nB, p->nC);             // proj_1x1: forward [nC][nB], gradient GEMM nC -> nB
+    pkT_res[i] = packT(b.res_w, nC, nB);               // res_conv: forward [nB][nC], gradient GEMM nB -> nC
+    pkT_proj[i] = packT(b.proj_w, nB, nC);             // proj_1x1: forward [nC][nB], gradient GEMM nC -> nB
   }
-  if (!pk_w.empty()) {
-    rc = srf_pack_pw_weights_transposed(pk_w.data(), pk_d.data(), pk_co.data(), pk_ci.data(), (int)pk_w.size(), st);
-    if (rc) return rc;
-  }
+  if (pk_w.empty()) return SRF_OK;
+  return srf_pack_pw_weights_transposed(pk_w.data(), pk_d.data(), pk_co.data(), pk_ci.data(), (int)pk_w.size(), st);
+}
+
+// Decoder, mask, mask_net: grad_out -> gx = gradient w.r.t. x_U; leaves the mask path's g_enc in s.genc
+int BwdWalk::tail(const float* grad_out) {
+  const SrfTail<const float> tl = plan_tail(p, P);
+  const SrfTail<float> gtl = plan_tail(p, G);
+  const float *m = (const float*)(sv + t.m), *v = (const float*)(sv + t.v);
+  const int h = K / 2;
+  void* wg = sc + s.wg;
   // ---- decoder: out = overlap_add(W_d^T v)                       improved_sudormrf.py:272-279,300
   float* frames = fp(s.frames);
-  rc = srf_frames_gather(grad_out, frames, Bt, SA, p->T, K, h, h, L, s.dec_rows, stream);
+  int rc = srf_frames_gather(grad_out, frames, Bt, SA, p->T, K, h, h, L, s.dec_rows, st);
   if (rc) return rc;
-  rc = srf_pw_wgrad_cols(v, frames, nullptr, Bt, s.dec_rows, SAN, L, gtl.dec_w, SA * K, nullptr, 1, wg, stream);
+  rc = srf_pw_wgrad_cols(v, frames, nullptr, Bt, s.dec_rows, SAN, L, gtl.dec_w, SA * K, nullptr, 1, wg, st);
   if (rc) return rc;
   float* wdpad = fp(s.wdpad);
   SRF_CHECK_HIP(hipMemsetAsync(wdpad, 0, sizeof(float) * (size_t)SAN * s.dec_rows, st));
   SRF_CHECK_HIP(hipMemcpy2DAsync(wdpad, sizeof(float) * s.dec_rows, tl.dec_w, sizeof(float) * SA * K,
                                  sizeof(float) * SA * K, SAN, hipMemcpyDeviceToDevice, st));
   float* gv = fp(s.gv);
-  rc = srf_pw_conv(frames, wdpad, zeros, gv, Bt, s.dec_rows, SAN, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
+  rc = srf_pw_conv(frames, wdpad, fp(s.zeros), gv, Bt, s.dec_rows, SAN, L, nullptr, nullptr, nullptr, 0, nullptr, 0, st);
   if (rc) return rc;
   // ---- mask: v = relu(m) * enc                                  :296-298
-  float* genc = fp(s.genc);
-  rc = srf_mask_bwd(gv, m, enc, gv, genc, 0, Bt, SA, N, L, stream);   // gv now holds g_m
+  rc = srf_mask_bwd(gv, m, enc(), gv, fp(s.genc), 0, Bt, SA, N, L, st);   // gv now holds g_m
   if (rc) return rc;
   // ---- mask_net: m = W_m PReLU(x_U) + b_m                       :268-269,295
-  float* gx = fp(s.gxa);
-  float* gx_other = fp(s.gxb);
-  {
-    srf_norm pre{nullptr, nullptr, nullptr, tl.mask_prelu};
-    rc = srf_pw_wgrad(gv, xbuf(U), &pre, Bt, B, SAN, L, gtl.mask_w, gtl.mask_b, 1, wg, stream);
-    if (rc) return rc;
-    if (!srf_pw_packed_only(pkT_mask, gv, Bt, SAN, B, L))    // (the packed image of W^T serves the GEMM: no fp32 copy needed)
-      rc = srf_transpose_launch(tl.mask_w, wt, SAN, B, st);   // [SAN][B] -> [B][SAN]
-    if (rc) return rc;
-    rc = srf_pw_conv_packed(gv, wt, pkT_mask, zeros, gx, Bt, SAN, B, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
-    if (rc) return rc;
-    rc = srf_prelu_bwd(gx, xbuf(U), tl.mask_prelu, gx, gtl.mask_prelu, (long)Bt * B * L, stream);
+  srf_norm pre{nullptr, nullptr, nullptr, tl.mask_prelu};
+  rc = srf_pw_wgrad(gv, xbuf(U), &pre, Bt, B, SAN, L, gtl.mask_w, gtl.mask_b, 1, wg, st);
+  if (rc) return rc;
+  rc = data_grad(gv, tl.mask_w, pkT_mask, gx, Bt, SAN, B, nullptr);
+  if (rc) return rc;
+  return srf_prelu_bwd(gx, xbuf(U), tl.mask_prelu, gx, gtl.mask_prelu, (long)Bt * B * L, st);
+}
+
+// Block i's pyramid: g_f (in s.gf) -> go = g_y1: final_norm, merge, the D levels as the path table says, proj_1x1's norm.
+// Norm slices of the block's arena: 0 final_norm, D - k level k (the order they run in), D + 1 proj_1x1's norm -- a conv kernel
+// reads its own level's slice (reduced) and writes the next one.
+int BwdWalk::block_pyramid(int i) {
+  const SrfBlock<const float> b = plan_block(p, P, i);
+  const SrfBlock<float> g = plan_block(p, G, i);
+  const SrfSlots sl = plan_slots(p, stats(), i);
+  const float* y1 = (const float*)(blk(i) + t.y1);
+  const float* merged = (const float*)(blk(i) + t.merged);
+  char* gln_sl = sc + s.arena + (size_t)i * ((size_t)(D + 2) * s.gln_slice + (size_t)D * s.dw_slice);   // D + 2 norm slices,
+  char* dw_sl = gln_sl + (size_t)(D + 2) * s.gln_slice;                                                 // then D conv slices
+  float* gn[SRF_MAX_DEPTH];       // the merge part of the gradient w.r.t. the normalised level k
+  gn[0] = fp(s.gf);
+  for (int k = 1; k < D; ++k) gn[k] = fp(s.gn[k]);
+  const srf_norm fn{sl.merged, b.fin_g, b.fin_be, b.fin_prelu}, pn{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
+  srf_bwd_ctx_merge_sink(ctx, gn, D);  // the merge backward rides on the norm's apply pass (the levels' pair sums of its output)
+  int rc = srf_gln_bwd_impl(gn[0], nullptr, merged, &fn, Bg, nC, L, gn[0], 0, g.fin_g, g.fin_be, g.fin_prelu, gln_sl, 0, st, ctx);
+  if (rc) return rc;                                       // gf now holds g_merged = g_n_0 (merge part)
+  if (!srf_bwd_ctx_merge_taken(ctx)) {
+    rc = srf_merge_bwd(gn[0], gn, D, (long)Bg * nC, L, st);
     if (rc) return rc;
   }
-  // ---- blocks in reverse: U-ConvBlock :198-220 (GroupComm: on the folded tensor, preceded by TAC)
-  const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
-  const int G_ = gc ? c.group_size : 1, Bg = p->Bg, nB = p->nB, nC = p->nC;
-  float* gf = fp(s.gf);
-  float* go = fp(s.go);
-  float* gd = fp(s.gd);
-  bool gf_ready = false;      // block i's g_f was produced by block i + 1's data-gradient pair
-  for (int i = U - 1; i >= 0; --i) {
-    const SrfBlock<const float> b = plan_block(p, P, i);
-    const SrfBlock<float> g = plan_block(p, G, i);
-    const SrfSlots sl = plan_slots(p, stats, i);
-    const char* blk = sv + t.blk0 + t.blk_stride * i;
-    const float* y1 = (const float*)(blk + t.y1);
-    const float* merged = (const float*)(blk + t.merged);
-    const float* xin = gc ? (const float*)(blk + t.u) : xbuf(i);   // the U-ConvBlock's input
-    // res_conv: x_{i+1} = W_r PReLU(GlobLN(merged)) + b_r + xin
-    srf_norm fn{sl.merged, b.fin_g, b.fin_be, b.fin_prelu};
-    rc = srf_pw_wgrad(gx, merged, &fn, Bg, nC, nB, L, g.res_w, g.res_b, 1, wg, stream);
+  const float* g_o = go;      // where level 0's conv leaves the gradient w.r.t. o = PReLU(GlobLN(y1))
+  for (int k = D - 1; k >= 0; --k) {
+    const PyrBwdForm form = path.form[k];
+    const bool pre = path.pre[k], on_load = form == PYR_BWD_ROW_ONLOAD || form == PYR_BWD_HEAD1;
+    const float* dk = (const float*)(blk(i) + t.lv[k]);
+    const srf_norm nk{sl.level[k], b.lv_g[k], b.lv_be[k], nullptr};
+    // gradient w.r.t. the normalised level k: merge part (gn[k]) + what level k + 1's conv sent down (pre: already their sum)
+    const float* gu_in = (k < D - 1) ? (k == 0 ? go : fp(s.gu[k])) : nullptr;
+    const float* gout1 = pre ? gu_in : gn[k];
+    const float* gout2 = pre ? nullptr : gu_in;
+    char* cur_sl = gln_sl + (size_t)(D - k) * s.gln_slice;
+    char* next_sl = cur_sl + s.gln_slice;
+    if (form == PYR_BWD_HEAD0) {      // (neither d_0 nor g_o travels; the two norms' parameter sums: recorded for the batched flush)
+      rc = srf_bwd_ctx_gln_params(ctx, &nk, cur_sl, Bg, nC, g.lv_g[0], g.lv_be[0], nullptr, st);
+      if (rc) return rc;
+      rc = srf_bwd_level0_proj(gout1, y1, &pn, &nk, b.lv_w[0], b.lv_b[0], cur_sl, next_sl, dw_sl, g.lv_w[0], g.lv_b[0], gd, Bg, nC, L, st,
+                               ctx);
+      if (rc) return rc;
+      std::swap(go, gd);      // g_y1 sits in the former g_d buffer: the two swap roles for the rest of the backward
+      return srf_bwd_ctx_gln_params(ctx, &pn, next_sl, Bg, nC, g.proj_g, g.proj_be, g.proj_prelu, st);
+    }
+    // the conv's input: the normalised level k - 1 (stride 2), at level 0 o = PReLU(GlobLN(y1)); its gradient goes to g_u[k - 1],
+    // at levels 1 and 0 to `go` -- but apply-on-load at level 0 reads G_0 from `go` (with halos) while the same kernel writes its
+    // input gradient: that one goes to the g_d buffer, which the on-load form leaves unused
+    const srf_norm in = k ? srf_norm{sl.level[k - 1], b.lv_g[k - 1], b.lv_be[k - 1], nullptr} : pn;
+    const float* src = k ? (const float*)(blk(i) + t.lv[k - 1]) : y1;
+    float* gin = k > 1 ? fp(s.gu[k - 1]) : (k == 0 && on_load && pre) ? gd : go;
+    const float* gadd = k > 0 ? gn[k - 1] : nullptr;
+    if (k == 0) g_o = gin;
+    rc = srf_gln_bwd_impl(gout1, gout2, dk, &nk, Bg, nC, L >> k, gd, 0, g.lv_g[k], g.lv_be[k], nullptr, cur_sl,
+                          (pre ? 1 : 0) | (on_load ? 2 : 0), st, ctx);
     if (rc) return rc;
-    if (!gf_ready) {        // (else: block i + 1's data-gradient pair below already left g_f = W_r^T g_x here)
-      if (!srf_pw_packed_only(pkT_res[i], gx, Bg, nB, nC, L))
-        rc = srf_transpose_launch(b.res_w, wt, nB, nC, st);    // [nB][nC] -> [nC][nB]
-      if (rc) return rc;
-      rc = srf_pw_conv_packed(gx, wt, pkT_res[i], zeros, gf, Bg, nB, nC, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
-      if (rc) return rc;
-    }
-    gf_ready = false;
-    char* gln_sl = sc + s.arena + (size_t)i * ((size_t)(D + 2) * s.gln_slice + (size_t)D * s.dw_slice);   // D + 2 norm slices,
-    char* dw_sl = gln_sl + (size_t)(D + 2) * s.gln_slice;                                                 // then D conv slices
-    srf_bwd_ctx_defer(ctx, true);
-    float* gn[SRF_MAX_DEPTH];
-    gn[0] = gf;
-    for (int k = 1; k < D; ++k) gn[k] = fp(s.gn[k]);
-    srf_bwd_ctx_merge_sink(ctx, gn, D);  // the merge backward rides on the norm's apply pass (the levels' pair sums of its output)
-    rc = srf_gln_bwd_impl(gf, nullptr, merged, &fn, Bg, nC, L, gf, 0, g.fin_g, g.fin_be, g.fin_prelu, gln_sl, 0, stream, ctx);
-    if (rc) return rc;                                       // gf now holds g_merged = g_n_0 (merge part)
-    if (!srf_bwd_ctx_merge_taken(ctx)) {
-      rc = srf_merge_bwd(gf, gn, D, (long)Bg * nC, L, stream);
-      if (rc) return rc;
-    }
-    // Level k's conv backward also produces the COMPLETE gradient w.r.t. its (normalised) input -- its own input
-    // gradient + the merge part gn[k-1] -- and the reduce pass of that input's GlobLN backward (the input tensor
-    // is in its registers); and it evaluates the apply pass of its OWN level's norm on load.  So per level: one
-    // parameter-sum kernel + one conv-backward kernel, g_d never written; only the deepest level needs a reduce
-    // pass.  The two norm scratch areas alternate (level k's sums are read while level k-1's are written).
-    // (one slice per call -- the alternation is now simply "this call's slice, the next call's slice")
-    int pre_reduced = 0, pp = 1;
-    bool head_done = false;  // level 0 + proj_1x1's norm ran as the fused head (g_y1 in the g_d buffer)
-    bool head = d0_missing || train_fused_head(p);   // (re-computes d_0: needed when the forward left it out, harmless otherwise)
-    const float* g_o = go;   // where level 0's conv leaves the gradient w.r.t. o = PReLU(GlobLN(y1))
-    for (int k = D - 1; k >= 0; --k) {
-      const float* dk = (const float*)(blk + t.lv[k]);
-      const int Lk = L >> k;
-      srf_norm nk{sl.level[k], b.lv_g[k], b.lv_be[k], nullptr};
-      // gradient w.r.t. the normalised level k: merge part (gn[k]) + what level k+1's conv sent down
-      const float* gu_in = (k < D - 1) ? (k == 0 ? go : fp(s.gu[k])) : nullptr;
-      const float* gout1 = pre_reduced ? gu_in : gn[k];    // pre-reduced: gu_in already holds the sum of both
-      const float* gout2 = pre_reduced ? nullptr : gu_in;
-      srf_norm in;
-      const float* src;
-      int Lin, stride;
-      float* gin;
-      if (k == 0) {
-        in = srf_norm{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
-        src = y1;
-        Lin = L;
-        stride = 1;
-        gin = go;       // gradient w.r.t. o = PReLU(GlobLN(y1)) (go is consumed as gu_in by this level first)
-      } else {
-        in = srf_norm{sl.level[k - 1], b.lv_g[k - 1], b.lv_be[k - 1], nullptr};
-        src = (const float*)(blk + t.lv[k - 1]);
-        Lin = L >> (k - 1);
-        stride = 2;
-        gin = (k - 1 == 0) ? go : fp(s.gu[k - 1]);   // gradient w.r.t. normalised level k-1
-      }
-      const float* gadd = k > 0 ? gn[k - 1] : nullptr;
-      char* cur_sl = gln_sl + (size_t)pp * s.gln_slice;
-      char* next_sl = cur_sl + s.gln_slice;
-      // Level 0 with its norm already reduced (by level 1's kernel) and the complete G_0 in one buffer: the fused head
-      // (round 6, srf_backward.hip: two passes over {G_0, y1} -- conv 0's backward, its norm's apply, proj_1x1's norm reduce
-      // and apply; neither d_0 nor g_o travels) leaves g_y1 in the g_d buffer; the two buffers swap roles for the rest of the block.
-      // (the head's preconditions missing here: an error when d_0 is not in `saved`, else level 0 on the row kernels below)
-      const void* hp[3] = {gout1, y1, gd};
-      const bool head0 = k == 0 && head && pre_reduced && !gout2 && gout1 != gd && srf_bwd_level0_proj_shape_ok(L, hp, 3);
-      if (k == 0 && head && !head0 && d0_missing) return head_lost("at level 0");
-      if (head0) {
-        {
-          rc = srf_gln_bwd_impl(gout1, nullptr, dk, &nk, Bg, nC, Lk, nullptr, 0, g.lv_g[k], g.lv_be[k], nullptr, cur_sl, 3, stream, ctx);
-          if (rc) return rc;      // (norm 0's parameter sums, reduced by level 1's kernel: recorded for the batched flush)
-          rc = srf_bwd_level0_proj(gout1, y1, &in, &nk, b.lv_w[k], b.lv_b[k], cur_sl, next_sl, dw_sl, g.lv_w[k], g.lv_b[k], gd, Bg, nC, L,
-                                   stream, ctx);
-          if (rc) return rc;
-          rc = srf_gln_bwd_impl(gd, nullptr, y1, &in, Bg, nC, L, nullptr, 0, g.proj_g, g.proj_be, g.proj_prelu, next_sl, 3, stream, ctx);
-          if (rc) return rc;      // (proj_1x1's norm: parameter sums recorded; its apply ran inside the fused head)
-          head_done = true;
-          pp += 1;
-          break;
-        }
-      }
-      // apply-on-load reads gout1 (with halos) while the same kernel writes gin: at level 0 both would be `go`, so
-      // the input gradient goes to the g_d buffer instead, which the on-load form leaves unused
-      if (k == 0 && !gout2 && gout1 == go) gin = gd;
-      const void* ptrs[5] = {gout1, dk, src, gin, gadd};
-      const bool on_load = !gout2 && gout1 != gin && srf_dwconv5_bwd_rowwise_ok(Lin, stride, ptrs, 5);
-      if (!on_load && k == 0) gin = go;
-      if (k == 0) g_o = gin;
-      rc = srf_gln_bwd_impl(gout1, gout2, dk, &nk, Bg, nC, Lk, gd, 0, g.lv_g[k], g.lv_be[k], nullptr, cur_sl,
-                            (pre_reduced ? 1 : 0) | (on_load ? 2 : 0), stream, ctx);
-      if (rc) return rc;
-      if (k == 1 && head && !on_load) {
-        if (d0_missing) return head_lost("at level 1 (the row kernels)");
-        head = false;       // d_0 is in `saved`: levels 1 and 0 on the conv kernels
-      }
-      if (k == 1 && head) {
-        // level 1 on the fused-head kernel: conv 1's input n_0 re-computed from y1 (the forward may not have kept d_0)
-        const srf_norm pn1{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
-        rc = srf_bwd_level1_head(gout1, dk, &nk, cur_sl, y1, &pn1, &in, b.lv_w[0], b.lv_b[0], b.lv_w[k], gadd, gin, next_sl,
-                                 dw_sl + (size_t)k * s.dw_slice, g.lv_w[k], g.lv_b[k], Bg, nC, L, stream, ctx);
-        if (rc) return rc;
-        pre_reduced = 1;
-        pp += 1;
-        continue;
-      }
-      rc = srf_dwconv5_bwd_impl(on_load ? gout1 : gd, src, &in, b.lv_w[k], Bg, nC, Lin, stride, gin, g.lv_w[k], g.lv_b[k],
-                                dw_sl + (size_t)k * s.dw_slice, gadd, next_sl, &pre_reduced, on_load ? dk : nullptr,
-                                on_load ? &nk : nullptr, on_load ? cur_sl : nullptr, stream, ctx);
-      if (rc) return rc;
-      pp += 1;
-    }
-    if (head_done) {
-      float* t2 = go;       // g_y1 sits in the former g_d buffer
-      go = gd;
-      gd = t2;
-    } else {
-      // proj_1x1: y1 = W_p xin + b_p, o = PReLU(GlobLN(y1))
-      srf_norm pn{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
-      rc = srf_gln_bwd_impl(g_o, nullptr, y1, &pn, Bg, nC, L, go, 0, g.proj_g, g.proj_be, g.proj_prelu, gln_sl + (size_t)pp * s.gln_slice,
-                            pre_reduced, stream, ctx);   // go = g_y1
-      if (rc) {
-        srf_bwd_ctx_defer(ctx, false);
-        return rc;
-      }
-    }
-    srf_bwd_ctx_defer(ctx, false);
-    rc = srf_pw_wgrad(go, xin, nullptr, Bg, nB, nC, L, g.proj_w, g.proj_b, 1, wg, stream);
+    if (form == PYR_BWD_HEAD1)
+      rc = srf_bwd_level1_head(gout1, dk, &nk, cur_sl, y1, &pn, &in, b.lv_w[0], b.lv_b[0], b.lv_w[k], gadd, gin, next_sl,
+                               dw_sl + (size_t)k * s.dw_slice, g.lv_w[k], g.lv_b[k], Bg, nC, L, st, ctx);
+    else
+      rc = srf_dwconv5_bwd_impl(on_load ? gout1 : gd, src, &in, b.lv_w[k], Bg, nC, k ? L >> (k - 1) : L, k ? 2 : 1, gin, g.lv_w[k],
+                                g.lv_b[k], dw_sl + (size_t)k * s.dw_slice, gadd, next_sl, on_load ? dk : nullptr, on_load ? &nk : nullptr,
+                                on_load ? cur_sl : nullptr, st, ctx);
     if (rc) return rc;
-    // Data gradients back to back (round 5; srf_pwconv_x3f.hip, no prologue): g_x(i) = W_p^T g_y1 + g_x(i + 1) -- the block's
-    // input gradient, skip included -- and, from registers, block i - 1's g_f = W_r^T g_x(i): one launch, bit-identical to the
-    // two it replaces (the B = 256 Improved models, launches of at least one tile per CU; debug flag 1 = without).
-    if (i > 0 && !gc && pkT_proj[i] && pkT_res[i - 1] && srf_pw_conv_pair_supported(Bg, nC, nB, nC, L) &&
-        srf_pw_packed_only(pkT_proj[i], go, Bg, nC, nB, L) && srf_pw_packed_only(pkT_res[i - 1], gx, Bg, nB, nC, L)) {
-      rc = srf_pw_conv_pair(go, pkT_proj[i], zeros, gx_other, nullptr, gx, pkT_res[i - 1], zeros, gf, nullptr, Bg, nC, nB, nC, L,
-                            stream);
-      if (rc) return rc;
-      gf_ready = true;
-    } else {
-      if (!srf_pw_packed_only(pkT_proj[i], go, Bg, nC, nB, L))
-        rc = srf_transpose_launch(b.proj_w, wt, nC, nB, st);          // [nC][nB] -> [nB][nC]
-      if (rc) return rc;
-      rc = srf_pw_conv_packed(go, wt, pkT_proj[i], zeros, gx_other, Bg, nC, nB, L, nullptr, gx, nullptr, 0, nullptr, 0, stream);   // + skip
-      if (rc) return rc;
-    }
-    float* tmp = gx;
-    gx = gx_other;
-    gx_other = tmp;
-    if (gc) {
-      // gx = g_u.  u = x + GlobLN_(b,g)(q), q = TAC_MLP(x):  g_x = g_u + MLP^T(GlobLN^T(g_u))
-      const float* q = (const float*)(blk + t.q);
-      float* gq = fp(s.gq);
-      float* gxm = fp(s.gxm);
-      srf_norm tn{sl.tac, b.tac_g, b.tac_b, nullptr};
-      rc = srf_gln_bwd(gx, nullptr, q, &tn, Bg, nB, L, gq, 0, g.tac_g, g.tac_b, nullptr, sc + s.gln, stream);
-      if (rc) return rc;
-      rc = srf_tac_bwd(xbuf(i), gq, b.tac, g.tac, Bt, G_, nB, 3 * nB, L, gxm, sc + s.tac, stream);
-      if (rc) return rc;
-      rc = srf_accumulate_launch(gx, gxm, (long)Bt * B * L, st);
-      if (rc) return rc;
-    }
   }
+  // proj_1x1: y1 = W_p xin + b_p, o = PReLU(GlobLN(y1))
+  return srf_gln_bwd_impl(g_o, nullptr, y1, &pn, Bg, nC, L, go, 0, g.proj_g, g.proj_be, g.proj_prelu, gln_sl + (size_t)(D + 1) * s.gln_slice,
+                          path.proj_pre ? 1 : 0, st, ctx);   // go = g_y1
+}
+
+// GroupComm: gx = g_u.  u = x + GlobLN_(b,g)(q), q = TAC_MLP(x):  g_x = g_u + MLP^T(GlobLN^T(g_u))
+int BwdWalk::block_tac(int i) {
+  const SrfBlock<const float> b = plan_block(p, P, i);
+  const SrfBlock<float> g = plan_block(p, G, i);
+  const float* q = (const float*)(blk(i) + t.q);
+  float *gq = fp(s.gq), *gxm = fp(s.gxm);
+  srf_norm tn{plan_slots(p, stats(), i).tac, b.tac_g, b.tac_b, nullptr};
+  int rc = srf_gln_bwd(gx, nullptr, q, &tn, Bg, nB, L, gq, 0, g.tac_g, g.tac_b, nullptr, sc + s.gln, st);
+  if (rc) return rc;
+  rc = srf_tac_bwd(xbuf(i), gq, b.tac, g.tac, Bt, p->cfg.group_size, nB, 3 * nB, L, gxm, sc + s.tac, st);
+  if (rc) return rc;
+  return srf_accumulate_launch(gx, gxm, (long)Bt * B * L, st);
+}
+
+// Block i, U-ConvBlock :198-220 (GroupComm: on the folded tensor, preceded by TAC): gx = g_x(i + 1) -> g_x(i)
+int BwdWalk::block(int i) {
+  const bool gc = p->cfg.variant == SRF_VARIANT_GROUPCOMM;
+  const SrfBlock<const float> b = plan_block(p, P, i);
+  const SrfBlock<float> g = plan_block(p, G, i);
+  const float* merged = (const float*)(blk(i) + t.merged);
+  const float* xin = gc ? (const float*)(blk(i) + t.u) : xbuf(i);   // the U-ConvBlock's input
+  float *zeros = fp(s.zeros), *gf = fp(s.gf);
+  void* wg = sc + s.wg;
+  // res_conv: x_{i+1} = W_r PReLU(GlobLN(merged)) + b_r + xin
+  srf_norm fn{plan_slots(p, stats(), i).merged, b.fin_g, b.fin_be, b.fin_prelu};
+  int rc = srf_pw_wgrad(gx, merged, &fn, Bg, nC, nB, L, g.res_w, g.res_b, 1, wg, st);
+  if (rc) return rc;
+  if (!gf_ready) {        // (else: block i + 1's data-gradient pair below already left g_f = W_r^T g_x here)
+    rc = data_grad(gx, b.res_w, pkT_res[i], gf, Bg, nB, nC, nullptr);
+    if (rc) return rc;
+  }
+  gf_ready = false;
+  srf_bwd_ctx_defer(ctx, true);     // the block's norm / conv backwards leave their parameter-gradient reductions to the batched flush
+  rc = block_pyramid(i);
+  srf_bwd_ctx_defer(ctx, false);
+  if (rc) return rc;
+  rc = srf_pw_wgrad(go, xin, nullptr, Bg, nB, nC, L, g.proj_w, g.proj_b, 1, wg, st);
+  if (rc) return rc;
+  // Data gradients back to back (round 5; srf_pwconv_x3f.hip, no prologue): g_x(i) = W_p^T g_y1 + g_x(i + 1) -- the block's
+  // input gradient, skip included -- and, from registers, block i - 1's g_f = W_r^T g_x(i): one launch, bit-identical to the
+  // two it replaces (the B = 256 Improved models, launches of at least one tile per CU; debug flag 1 = without).
+  if (i > 0 && !gc && pkT_proj[i] && pkT_res[i - 1] && srf_pw_conv_pair_supported(Bg, nC, nB, nC, L) &&
+      srf_pw_packed_only(pkT_proj[i], go, Bg, nC, nB, L) && srf_pw_packed_only(pkT_res[i - 1], gx, Bg, nB, nC, L)) {
+    rc = srf_pw_conv_pair(go, pkT_proj[i], zeros, gx_other, nullptr, gx, pkT_res[i - 1], zeros, gf, nullptr, Bg, nC, nB, nC, L, st);
+    gf_ready = true;
+  } else {
+    rc = data_grad(go, b.proj_w, pkT_proj[i], gx_other, Bg, nC, nB, gx);   // + skip
+  }
+  if (rc) return rc;
+  std::swap(gx, gx_other);
+  return gc ? block_tac(i) : SRF_OK;
+}
+
+// Bottleneck, the blocks' deferred reductions, encoder weight, and on request the input waveform
+int BwdWalk::front(const float* wav, float* grad_wav) {
+  const SrfFront<const float> f = plan_front(P);
+  const SrfFront<float> gf_ = plan_front(G);
+  const int h = K / 2;
+  void* wg = sc + s.wg;
+  float *genc = fp(s.genc), *gv = fp(s.gv), *frames = fp(s.frames);
   // ---- bottleneck: x_0 = W_b GlobLN(enc) + b_b                  :256-259,292
-  {
-    srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
-    rc = srf_pw_wgrad(gx, enc, &ln, Bt, N, B, L, gf_.bott_w, gf_.bott_b, 1, wg, stream);
-    if (rc) return rc;
-    if (!srf_pw_packed_only(pkT_bott, gx, Bt, B, N, L))
-      rc = srf_transpose_launch(f.bott_w, wt, B, N, st);          // [B][N] -> [N][B]
-    if (rc) return rc;
-    // g_ln into the (now free) gv buffer, then GlobLN backward accumulated onto the mask path's g_enc
-    rc = srf_pw_conv_packed(gx, wt, pkT_bott, zeros, gv, Bt, B, N, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
-    if (rc) return rc;
-    rc = srf_gln_bwd(gv, nullptr, enc, &ln, Bt, N, L, genc, 1, gf_.ln_g, gf_.ln_b, nullptr, sc + s.gln, stream);
-    if (rc) return rc;
-  }
+  srf_norm ln{stats(), f.ln_g, f.ln_b, nullptr};
+  int rc = srf_pw_wgrad(gx, enc(), &ln, Bt, N, B, L, gf_.bott_w, gf_.bott_b, 1, wg, st);
+  if (rc) return rc;
+  // g_ln into the (now free) gv buffer, then GlobLN backward accumulated onto the mask path's g_enc
+  rc = data_grad(gx, f.bott_w, pkT_bott, gv, Bt, B, N, nullptr);
+  if (rc) return rc;
+  rc = srf_gln_bwd(gv, nullptr, enc(), &ln, Bt, N, L, genc, 1, gf_.ln_g, gf_.ln_b, nullptr, sc + s.gln, st);
+  if (rc) return rc;
   // ---- the blocks' deferred parameter-gradient reductions, batched
   rc = srf_bwd_ctx_flush(ctx, st);
   if (rc) return rc;
   // ---- encoder weight                                           :247-251,286
-  rc = srf_frames_gather(wav, frames, Bt, p->A, p->T, K, h, h, L, p->A * K, stream);
+  rc = srf_frames_gather(wav, frames, Bt, p->A, p->T, K, h, h, L, p->A * K, st);
   if (rc) return rc;
-  rc = srf_pw_wgrad(genc, frames, nullptr, Bt, p->A * K, N, L, gf_.enc_w, nullptr, 1, wg, stream);
+  rc = srf_pw_wgrad(genc, frames, nullptr, Bt, p->A * K, N, L, gf_.enc_w, nullptr, 1, wg, st);
   if (rc || !grad_wav) return rc;
   // ---- input waveform: g_wav[b,a,t] = sum_{n,l,k: h l + k - h = t} W_e[n,a,k] g_enc[b,n,l]   (the decoder's arithmetic with
   // the encoder's weight [N, A, K] in ConvTranspose1d layout; its scratch fits the forward decoder's: N <= S A N, A <= S A)
-  return srf_decoder(genc, f.enc_w, grad_wav, Bt, N, p->A, K, L, p->T, fp(s.dec), stream);
+  return srf_decoder(genc, f.enc_w, grad_wav, Bt, N, p->A, K, L, p->T, fp(s.dec), st);
+}
+
+static int backward_impl(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
+                         const float* grad_out, const void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                         float* grad_wav, void* stream) {
+  if (causal_refused(p, grad_wav ? "srf_backward_wav" : "srf_backward")) return SRF_EINVAL;
+  SRF_CHECK_ARG(p && P && G && wav && grad_out && saved && scratch, "srf_backward: null pointer");
+  SRF_CHECK_ARG(num_params == p->n_params, "srf_backward: expected %d parameter tensors, got %d", p->n_params, num_params);
+  int rc = train_check(p, "srf_backward");
+  if (rc) return rc;
+  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] && G[i], "srf_backward: parameter / gradient %d is null", i);
+  // (freed on every exit path: a backward that fails half-way leaves nothing behind)
+  const std::unique_ptr<SrfBwdCtx, void (*)(SrfBwdCtx*)> ctx(srf_bwd_ctx_new(), srf_bwd_ctx_free);
+  BwdWalk w(p, P, G, saved, scratch, stream, ctx.get());
+  SRF_CHECK_ARG(saved_bytes >= w.t.total && scratch_bytes >= w.s.total, "srf_backward: saved / scratch buffer too small");
+  rc = pyr_bwd_path(p, saved, scratch, grad_wav ? "srf_backward_wav" : "srf_backward", &w.path);
+  if (rc) return rc;
+  SRF_CHECK_HIP(hipMemsetAsync(w.fp(w.s.zeros), 0, sizeof(float) * max3(p->cfg.in_channels, w.SAN, w.N), w.st));
+  // the blocks' norm / conv backwards get one scratch slice per call (statistic buckets zeroed here, once)
+  // (the WHOLE arena, 75 MB at cfg 2 / 170 MB at cfg 4 = 0.1 % of a step, not just the fp64 buckets at the head of each norm slice
+  // -- ADVICE r3: the chunked fallback kernels (debug flags 1<<29 / 1<<30, rows beyond the row kernels' limits) accumulate
+  // their row partials with atomicAdd and rely on zeroed slices)
+  SRF_CHECK_HIP(hipMemsetAsync(w.sc + w.s.arena, 0, w.s.arena_bytes, w.st));
+  rc = w.pack_weights();
+  if (!rc) rc = w.tail(grad_out);
+  for (int i = w.U - 1; i >= 0 && !rc; --i) rc = w.block(i);
+  return rc ? rc : w.front(wav, grad_wav);
+}
+
+extern "C" int srf_backward(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
+                            const float* grad_out, const void* saved, size_t saved_bytes, void* scratch,
+                            size_t scratch_bytes, void* stream) {
+  return backward_impl(p, P, G, num_params, wav, grad_out, saved, saved_bytes, scratch, scratch_bytes, nullptr, stream);
+}
+// ... and the gradient w.r.t. the input waveform on top (ABI 15; the reference's autograd produces it when the caller's
+// mixture requires grad, improved_sudormrf.py:283-301 is plain ATen): grad_wav [Bt, in_audio_channels, T] (overwritten) =
+// the encoder's transposed convolution (:247-251,286; the right zero-pad of :303-314 is a crop) of the gradient w.r.t.
+// the encoder output, which the backward forms anyway (mask path + GlobLN path).
+extern "C" int srf_backward_wav(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
+                                const float* grad_out, const void* saved, size_t saved_bytes, void* scratch,
+                                size_t scratch_bytes, float* grad_wav, void* stream) {
+  SRF_CHECK_ARG(grad_wav, "srf_backward_wav: null grad_wav");
+  return backward_impl(p, P, G, num_params, wav, grad_out, saved, saved_bytes, scratch, scratch_bytes, grad_wav, stream);
 }

@@ -9,13 +9,18 @@ pinned by name and count in test_gpu_ragged.py / test_gpu_ragged_groupcomm.py.
 Shapes: the two smallest golden cases at their own batch and T (per-level pyramid, separate convs, unfused tail -- what the
 big shape never runs), cfg 2 and cfg 3 at batch 32, T = 10400 (the smallest shapes that keep the pairs, the fused pyramid and
 the fused tail: test_gpu_ragged.py, test_gpu_ragged_groupcomm.py), cfg 2 again under the two debug flags that take the pairs
-and the fused pyramid away, and the training step at the shape of the golden case train_cfg2_shape."""
+and the fused pyramid away, and the training step at the shape of the golden case train_cfg2_shape.
+
+Training steps (forward + backward; "train ..." below): srf_backward chooses every block's pyramid path -- chunked / row
+kernels, apply-on-load, the fused head -- from L, D, the kernel mode, the debug flags and its forward's record.  TRAIN_SHAPES are
+the smallest shapes that reach each of those paths, recorded on the commit BEFORE the path became a table."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import load_case
 from oracle import weights
+from oracle.schema import ModelConfig
 from test_gpu_model import build
 from tests.test_gpu_ops import DEV
 
@@ -88,6 +93,38 @@ def trace_train(manifest):
     return [n for n, _ in tr.launches]
 
 
+TRAIN_SHAPES = {      # name: (configuration, batch, T)
+    "improved_d5": (ModelConfig("improved", 64, 128, 3, 5, 21, 128, 2), 3, 8000),
+    "improved_d2": (ModelConfig("improved", 16, 24, 2, 2, 21, 32, 2), 3, 2530),     # level 1 is the deepest: the head starts from a gradient that is not pre-reduced
+    "improved_d2_l36": (ModelConfig("improved", 8, 16, 1, 2, 11, 8, 3), 3, 180),    # L = 36: nine float4 per row, L % 8 == 4
+    "improved_d1": (ModelConfig("improved", 16, 24, 2, 1, 21, 32, 2), 2, 1000),     # no head, no pyramid loop beyond level 0
+    "groupcomm_d4": (ModelConfig("groupcomm", 64, 128, 2, 4, 21, 64, 2, 1, 4), 2, 4000),   # TAC; the non-deferred srf_gln_bwd
+}
+TRAIN_STEPS = [("improved_d5", "0"), ("improved_d5", "BWD_NO_FUSED_HEAD"), ("improved_d5", "BWD_DW_CHUNKED"),
+               ("improved_d5", "BWD_GLN_SCALAR"), ("improved_d5", "kernel_mode_1"), ("improved_d2", "0"), ("improved_d2_l36", "0"),
+               ("improved_d1", "0"), ("groupcomm_d4", "0")]
+
+
+def train_step_trace(shape, setting):
+    """launch names, in order, of one training step (forward + backward) of TRAIN_SHAPES[shape] under a debug flag, or under
+    kernel mode 1 (forward and backward both)"""
+    from sudo_rm_rf_amd import ops
+    cfg, batch, T_ = TRAIN_SHAPES[shape]
+    if shape == "improved_d2_l36":
+        assert cfg.frames(T_) == 36
+    model = build(cfg, weights.make_state_dict(cfg, seed=31)).train()
+    x = torch.from_numpy(weights.make_mixture(batch, T_, 9120).astype(np.float32)).to(DEV)
+    flags = int(getattr(ops.DebugFlag, setting)) if setting.startswith("BWD_") else 0
+    try:
+        ops.set_kernel_mode(1 if setting == "kernel_mode_1" else 0)
+        with ops.debug_flags(flags), ops.kernel_trace(DEV) as tr:
+            rec = model(x)
+            (rec * rec).mean().backward()
+    finally:
+        ops.set_kernel_mode(0)
+    return [n for n, _ in tr.launches]
+
+
 EXPECTED = {
     "tiny_improved": [      # 20 launches
         (("zero_fill", "encoder", "pw_conv_generic"), 1),
@@ -143,6 +180,128 @@ EXPECTED = {
           "dwconv5_generic", "merge_fast", "pw_conv_x3p<2>"), 16),
         (("pack_decoder", "pw_mask_decode", "overlap_add"), 1),
     ],
+    "train improved_d5 0": [      # 96 launches
+        (("encoder",), 1),
+        (("pw_conv_mfma", "pw_conv_mfma", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save"), 3),
+        (("pw_conv_mfma",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4",
+          "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "dwconv5_bwd", "dwconv5_bwd", "dwconv5_bwd", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply",
+          "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 3),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d5 BWD_NO_FUSED_HEAD": [      # 96 launches
+        (("encoder",), 1),
+        (("pw_conv_mfma", "pw_conv_mfma", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save"), 3),
+        (("pw_conv_mfma",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4",
+          "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "dwconv5_bwd", "dwconv5_bwd", "dwconv5_bwd", "dwconv5_bwd", "dwconv5_bwd", "gln_bwd_apply",
+          "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 3),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d5 BWD_DW_CHUNKED": [      # 126 launches
+        (("encoder",), 1),
+        (("pw_conv_mfma", "pw_conv_mfma", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save"), 3),
+        (("pw_conv_mfma",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4",
+          "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "pw_wgrad", "pw_wgrad_reduce",
+          "transpose", "pw_conv_bf16x3_w4"), 3),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d5 BWD_GLN_SCALAR": [      # 129 launches
+        (("encoder",), 1),
+        (("pw_conv_mfma", "pw_conv_mfma", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save"), 3),
+        (("pw_conv_mfma",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4",
+          "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_apply", "merge_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "pw_wgrad", "pw_wgrad_reduce",
+          "transpose", "pw_conv_bf16x3_w4"), 3),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d5 kernel_mode_1": [      # 138 launches
+        (("encoder",), 1),
+        (("pw_conv_generic", "pw_conv_generic", "dwconv5_generic", "dwconv5_generic", "dwconv5_generic", "dwconv5_generic",
+          "dwconv5_generic", "merge_generic"), 3),
+        (("pw_conv_generic",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_generic", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_generic", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic",
+          "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_bwd_reduce", "gln_bwd_apply", "merge_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "pw_wgrad", "pw_wgrad_reduce",
+          "transpose", "pw_conv_generic"), 3),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply",
+          "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d2 0": [      # 68 launches
+        (("encoder", "pw_conv_small"), 1),
+        (("pw_conv_generic", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save", "pw_conv_generic"), 2),
+        (("pw_conv_small", "mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather",
+          "pw_wgrad_small", "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad_small", "pw_wgrad_reduce",
+          "transpose", "pw_conv_generic", "prelu_bwd"), 1),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply", "pw_wgrad_small", "pw_wgrad_reduce", "transpose",
+          "pw_conv_generic"), 2),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d2_l36 0": [      # 49 launches
+        (("encoder",), 1),
+        (("pw_conv_small",), 2),
+        (("dwconv5_s1_fast", "dwconv5_generic", "merge_fast", "pw_conv_small", "pw_conv_generic", "mask_apply", "transpose",
+          "zero_fill", "pw_conv_generic", "overlap_add", "frames_gather", "pw_wgrad_small", "pw_wgrad_reduce",
+          "pw_conv_generic", "mask_bwd", "pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "prelu_bwd",
+          "pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply"), 1),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small"), 2),
+        (("gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather",
+          "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d1 0": [      # 64 launches
+        (("encoder", "pw_conv_small"), 1),
+        (("pw_conv_generic", "dwconv5_s1_fast", "merge_fast", "pw_conv_generic"), 2),
+        (("pw_conv_small", "mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather",
+          "pw_wgrad_small", "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad_small", "pw_wgrad_reduce",
+          "transpose", "pw_conv_generic", "prelu_bwd"), 1),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "dwconv5_bwd", "gln_bwd_apply", "pw_wgrad_small", "pw_wgrad_reduce", "transpose",
+          "pw_conv_generic"), 2),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train groupcomm_d4 0": [      # 102 launches
+        (("encoder", "pw_conv_mfma"), 1),
+        (("tac", "pw_conv_small", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save", "pw_conv_small"), 2),
+        (("pw_conv_mfma", "mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather",
+          "pw_wgrad", "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose",
+          "pw_conv_bf16x3_w4", "prelu_bwd"), 1),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "dwconv5_bwd", "dwconv5_bwd", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply", "pw_wgrad_small",
+          "pw_wgrad_reduce", "transpose", "pw_conv_small", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "tac_bwd",
+          "pw_wgrad_small", "pw_wgrad_reduce", "pw_wgrad_small", "pw_wgrad_reduce", "pw_wgrad_small", "pw_wgrad_reduce",
+          "pw_wgrad_small", "pw_wgrad_reduce", "tac_bwd_slopes", "accumulate"), 2),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
 }
 
 
@@ -164,3 +323,8 @@ def test_launch_sequence_cfg2_under_debug_flags(cfg2, flags):
     from sudo_rm_rf_amd import ops
     value = sum(int(getattr(ops.DebugFlag, f)) for f in flags.split("|")) if flags != "0" else 0
     _check("cfg2 " + flags, _forward_trace(*cfg2, flags=value))
+
+
+@pytest.mark.parametrize("shape,setting", TRAIN_STEPS, ids=["%s-%s" % s for s in TRAIN_STEPS])
+def test_launch_sequence_of_a_training_step(shape, setting):
+    _check("train %s %s" % (shape, setting), train_step_trace(shape, setting))

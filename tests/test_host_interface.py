@@ -181,6 +181,40 @@ def test_plan_geometry_matches_reference_padding_rule():
     assert b"odd" in lib.srf_last_error()
 
 
+@pytest.mark.skipif(torch.cuda.is_available(), reason="host-memory pointers must never reach a HIP call on a GPU box; "
+                    "test_backward_follows_its_forward_when_flags_change_in_between[mode_0_to_1] covers it with real buffers")
+def test_backward_that_cannot_follow_its_forward_is_refused_before_any_device_call():
+    """srf_backward decides every block's pyramid path -- and refuses a backward that cannot follow its forward -- before its first
+    HIP call.  No forward filled these buffers (plain host memory), so d_0 counts as missing; under kernel mode 1 the fused head
+    that would re-compute it cannot run: SRF_EINVAL with the message that says so, not a HIP error from a memset."""
+    import ctypes as C
+    from sudo_rm_rf_amd import _lib
+    from sudo_rm_rf_amd.engine import _config_struct
+    lib = _lib.load()
+    cfg = ModelConfig("improved", 16, 32, 2, 3, 21, 24, 2)
+    st = _config_struct(cfg.variant, cfg.in_audio_channels, cfg.out_channels, cfg.in_channels, cfg.num_blocks,
+                        cfg.upsampling_depth, cfg.enc_kernel_size, cfg.enc_num_basis, cfg.num_sources, cfg.group_size)
+    Bt, T = 2, 517
+    h = C.c_void_p()
+    _lib.check(lib.srf_plan_create(C.byref(st), Bt, T, C.byref(h)))
+    prev = lib.srf_get_kernel_mode()
+    try:
+        n = lib.srf_plan_num_params(h)
+        saved_bytes, scratch_bytes = lib.srf_train_saved_bytes(h), lib.srf_train_scratch_bytes(h)
+        assert saved_bytes > 0 and scratch_bytes > 0
+        host = np.zeros((saved_bytes + scratch_bytes) // 4 + 256, np.float32)
+        base = (host.ctypes.data + 255) // 256 * 256
+        ptrs = (C.c_void_p * n)(*([base] * n))
+        lib.srf_set_kernel_mode(1)
+        rc = lib.srf_backward(h, ptrs, ptrs, n, base, base, base, saved_bytes, base + saved_bytes // 256 * 256 + 256, scratch_bytes, None)
+        msg = lib.srf_last_error().decode()
+        assert rc == -1, (rc, msg)      # SRF_EINVAL
+        assert "d_0" in msg and "kernel mode 1" in msg, msg
+    finally:
+        lib.srf_set_kernel_mode(prev)
+        lib.srf_plan_destroy(h)
+
+
 # ---------------------------------------------------------------------------------------------
 # checkpoint tooling (SURVEY.md §8f rank 4): DataParallel prefixes, whole-module pickles, wrapped dicts
 # ---------------------------------------------------------------------------------------------
