@@ -247,6 +247,20 @@ int srf_forward_ragged(const srf_plan* plan, const float* const* params, int num
 int srf_separate(const srf_plan* plan, const float* const* params, int num_params, const float* wav, float* out,
                  float* stats, int mixture_consistency, void* workspace, size_t workspace_bytes, void* stream);
 
+/* srf_separate over a ragged batch (additive to ABI 19): srf_forward_ragged with the recipe folded in, every step over the
+ * example's OWN samples.  wav: the RAW padded mixture [batch, 1, T]; lengths: HOST array [batch]; stats: [batch][2] device
+ * floats, WRITTEN: {mean, unbiased std} of wav[b, 0, :lengths[b]] (one srf_wav_stats_ragged launch in front of the forward).
+ * The ragged encoder normalises on load -- the zero padding past lengths[b] is that of the NORMALISED signal -- and the
+ * ragged overlap-add stores est * std + mean and, mixture_consistency != 0, the correction against the mixture re-normalised
+ * from the raw row, for t < lengths[b]; out[b, :, lengths[b]:] is exactly 0, and wav[b, :, lengths[b]:] is never read, by
+ * the mixture-consistency step either.  Same gate (srf_plan_ragged_supported), workspace and length rules as
+ * srf_forward_ragged; refused with SRF_EINVAL BEFORE anything is launched, srf_last_error() naming the example: an
+ * unsupported plan (causal plans included), a length outside 1..T, a length the pyramid does not take, a null pointer.
+ * Placement: workspace 256-byte aligned; wav, out and stats at any float-aligned address. */
+int srf_separate_ragged(const srf_plan* plan, const float* const* params, int num_params, const float* wav,
+                        const int* lengths /* host, [batch] */, float* out, float* stats /* [batch][2], written */,
+                        int mixture_consistency, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Causal plans only: the per-block plain attributes alpha / beta of UConvBlock (both 1.0 as the reference constructs them,
  * the default of a new plan).  srf_forward computes res_conv(.) * skipinit_gain * alpha[i] + x and proj_1x1(x / beta[i]).
  * alpha, beta: host arrays of n = num_blocks floats.  Call before the plan's first forward. */
@@ -317,6 +331,24 @@ int srf_encoder(const float* wav, const float* w, float* out, double* sums,
  * lengths[b] <= (K/2) * frames[b]; frames[b] = padded length / hop of example b (srf_plan_padded_length of a batch-1 plan). */
 int srf_encoder_ragged(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
                        const int* lengths, const int* frames, void* stream);
+/* A test and building-block entry (srf_separate_ragged reaches the same kernel internally; nothing else in the library calls
+ * this one).  The same with the caller-side normalisation folded into the load: in_stats [Bt][2] {mean, std} per row (srf_wav_stats_ragged);
+ * the kernel sees (x - mean) / (std + 1e-9) on [0, lengths[b]) and zeros past it.  in_stats: any float-aligned address. */
+int srf_encoder_ragged_stats(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K,
+                             int L, const int* lengths, const int* frames, const float* in_stats, void* stream);
+/* stats[r] = {mean, unbiased std} of wav[r, :lengths[r]] for the rows of a padded [rows, T] tensor (T = the row stride;
+ * rows <= SRF_RAGGED_MAX_BATCH, 1 <= lengths[r] <= T, lengths on the HOST).  The arithmetic of srf_wav_stats: fp64 mean, then
+ * the fp64 sum of squared deviations over max(lengths[r] - 1, 1); one block per row and a fixed reduction order, so a row's
+ * two numbers are the same bits whatever the other rows hold.  Nothing at or past lengths[r] is read.  wav, stats: any
+ * float-aligned address. */
+int srf_wav_stats_ragged(const float* wav, const int* lengths /* host */, float* stats, int rows, int T, void* stream);
+/* The padded batch from the caller's separate utterance buffers, in one launch: rows = HOST array of `batch` DEVICE pointers,
+ * utterance b = lengths[b] floats at rows[b].  wav[b, 0, :lengths[b]] receives them bit for bit; wav[b, 0, lengths[b]:] is NOT
+ * written (no ragged entry point reads it).  The pointers travel by value in the launch arguments, as the lengths do
+ * (batch <= SRF_RAGGED_MAX_BATCH).  Refused before the launch: a null entry of rows (the message names the example), a
+ * length outside 1..T.  Sources and wav: any float-aligned address (4-byte copies); a source must not overlap wav. */
+int srf_wav_gather_ragged(const float* const* rows /* host array of device pointers */, const int* lengths /* host */,
+                          float* wav /* [batch, 1, T] */, int batch, int T, void* stream);
 
 /* sums[g][bucket][0..1] += {sum, sumsq} of x[g, :, :] (x: [groups, channels*length]). */
 int srf_gln_stats(const float* x, double* sums, int groups, long per_group, void* stream);

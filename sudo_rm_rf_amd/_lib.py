@@ -140,6 +140,10 @@ _PROTOS = {
     "srf_plan_ragged_workspace_bytes": (_sz, [_vp]),
     "srf_forward_ragged": (_i, [_vp, C.POINTER(_vp), _i, _vp, C.POINTER(_i), _vp, _vp, _sz, _vp]),
     "srf_encoder_ragged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "srf_encoder_ragged_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
+    "srf_wav_stats_ragged": (_i, [_vp, C.POINTER(_i), _vp, _i, _i, _vp]),
+    "srf_wav_gather_ragged": (_i, [C.POINTER(_vp), C.POINTER(_i), _vp, _i, _i, _vp]),
+    "srf_separate_ragged": (_i, [_vp, C.POINTER(_vp), _i, _vp, C.POINTER(_i), _vp, _vp, _i, _vp, _sz, _vp]),
     "srf_merge": (_i, [C.POINTER(_vp), C.POINTER(srf_norm), _i, _vp, _i, _i, _i, _vp, _vp]),
     "srf_decoder_scratch_floats": (_sz, [_i, _i, _i, _i, _i]),
     "srf_decoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),

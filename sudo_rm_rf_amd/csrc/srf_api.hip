@@ -515,7 +515,7 @@ struct Ragged {
 };
 static int step_encoder(const Ragged* rg, const float* wav, const float* w, float* enc, double* sums, int Bt, int A, int T, int N,
                         int K, int L, const float* wav_stats, void* stream) {
-  return rg ? srf_encoder_ragged(wav, w, enc, sums, Bt, A, T, N, K, L, rg->lengths, rg->frames, stream)
+  return rg ? srf_encoder_ragged_impl(wav, w, enc, sums, Bt, A, T, N, K, L, rg->lengths, rg->frames, wav_stats, stream)
             : srf_encoder_impl(wav, w, enc, sums, Bt, A, T, N, K, L, wav_stats, stream);
 }
 // rows = examples * rows_per_example (GroupComm's per-group convs run over the folded rows).  Ragged: as in srf_pw_conv_packed
@@ -556,14 +556,16 @@ static int step_pyramid(const Ragged* rg, int G, const float* y1, float* merged,
                                       stream)
             : srf_pyramid(y1, merged, in_norm, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bg, C, L, D, scratch, out_sums, stream);
 }
-// the ragged form reads the example's own frames only and has no post-processing (pipeline.py rescales outside)
+// the ragged form reads the example's own frames only; its post-processing (wav_stats: srf_separate_ragged) stays on the example's
+// own samples
 static int step_overlap_add(const Ragged* rg, const float* z, float* out, int Bt, int Co, int K, int L, int T, int nparts,
                             const float* wav_stats, const float* wav, int mc, hipStream_t st) {
-  return rg ? srf_overlap_add_launch(z, out, Bt, Co, K, L, T, nparts, nullptr, nullptr, 0, st, &rg->lens_t, &rg->frames_t)
+  return rg ? srf_overlap_add_launch(z, out, Bt, Co, K, L, T, nparts, wav_stats, wav, mc, st, &rg->lens_t, &rg->frames_t)
             : srf_overlap_add_launch(z, out, Bt, Co, K, L, T, nparts, wav_stats, wav, mc, st);
 }
 
-// THE walk of the Improved / GroupComm inference forward: srf_forward, srf_separate (wav_stats) and srf_forward_ragged (rg).
+// THE walk of the Improved / GroupComm inference forward: srf_forward, srf_separate (wav_stats), srf_forward_ragged (rg) and
+// srf_separate_ragged (both).
 // The ragged forward keeps the layout -- [batch, C, L] with L the PLAN's frame count as row stride, the same workspace carve-up
 // and two-buffer scheme -- and every kernel takes the example's own frame count L_b from a by-value table.  The invariant:
 //   * a tensor whose GlobLN statistics are taken (enc, y1, merged; GroupComm: q) is exactly zero at columns >= L_b, so the
@@ -798,36 +800,57 @@ static bool plan_ragged_now(const srf_plan* p, const char** why) {
 extern "C" int srf_plan_ragged_supported(const srf_plan* p) { return p && plan_ragged_now(p, nullptr) ? 1 : 0; }
 extern "C" size_t srf_plan_ragged_workspace_bytes(const srf_plan* p) { return p && plan_ragged_now(p, nullptr) ? p->total_bytes : 0; }
 
+// What srf_forward_ragged and srf_separate_ragged (`who`) share: the gate, the argument checks and every example's own padded
+// length, as its batch-1 plan would have it -- all refusals BEFORE the first launch (a length the pyramid takes is on its 16- /
+// 32-frame chunk grid: the "multiple of 4 frames" the GEMMs' ragged forms ask for is implied)
+static int ragged_prepare(const char* who, const srf_plan* p, const float* const* P, int num_params, const int* lengths,
+                          const void* workspace, size_t workspace_bytes, Ragged* rg) {
+  const char* why = "";
+  SRF_CHECK_ARG(plan_ragged_now(p, &why), "%s: plan not supported%s: %s", who,
+                p->cfg.variant == SRF_VARIANT_IMPROVED ? "" : " (ragged kernels exist for the Improved model and for GroupComm with 16 groups of 16 channels)",
+                why);
+  int rc = forward_check_args(who, true /* checked by the caller: the gate comes first */, p, P, num_params, workspace, workspace_bytes);
+  if (rc) return rc;
+  const int D = p->cfg.upsampling_depth, h = p->cfg.enc_kernel_size / 2;
+  rg->lengths = lengths;
+  for (int b = 0; b < p->Bt; ++b) {
+    SRF_CHECK_ARG(lengths[b] >= 1 && lengths[b] <= p->T, "%s: example %d has length %d (allowed: 1..%d)", who, b, lengths[b], p->T);
+    rg->frames[b] = (int)(plan_padded_length(lengths[b], h, D) / h);
+    SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(rg->frames[b], p->L, D),
+                  "%s: example %d (length %d = %d frames) is too short for the fused pyramid or off its chunk grid", who, b,
+                  lengths[b], rg->frames[b]);
+  }
+  rc = srf_frames_table(who, lengths, p->Bt, p->T, &rg->lens_t);
+  if (rc) return rc;
+  return srf_frames_table(who, rg->frames, p->Bt, p->L, &rg->frames_t);
+}
+
 extern "C" int srf_forward_ragged(const srf_plan* p, const float* const* P, int num_params, const float* wav, const int* lengths,
                                   float* out, void* workspace, size_t workspace_bytes, void* stream) {
   SRF_CHECK_ARG(p && P && wav && lengths && out && workspace, "srf_forward_ragged: null pointer");
-  const char* why = "";
-  SRF_CHECK_ARG(plan_ragged_now(p, &why), "srf_forward_ragged: plan not supported%s: %s",
-                p->cfg.variant == SRF_VARIANT_IMPROVED ? "" : " (ragged kernels exist for the Improved model and for GroupComm with 16 groups of 16 channels)",
-                why);
-  int rc = forward_check_args("srf_forward_ragged", true /* checked above: the gate comes first */, p, P, num_params, workspace, workspace_bytes);
-  if (rc) return rc;
-  // ---- every example's own padded length, as its batch-1 plan would have it; all refusals BEFORE the first launch (a length the
-  // pyramid takes is on its 16- / 32-frame chunk grid: the "multiple of 4 frames" the GEMMs' ragged forms ask for is implied)
-  const int D = p->cfg.upsampling_depth, h = p->cfg.enc_kernel_size / 2;
   Ragged rg;
-  rg.lengths = lengths;
-  for (int b = 0; b < p->Bt; ++b) {
-    SRF_CHECK_ARG(lengths[b] >= 1 && lengths[b] <= p->T, "srf_forward_ragged: example %d has length %d (allowed: 1..%d)", b,
-                  lengths[b], p->T);
-    rg.frames[b] = (int)(plan_padded_length(lengths[b], h, D) / h);
-    SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(rg.frames[b], p->L, D),
-                  "srf_forward_ragged: example %d (length %d = %d frames) is too short for the fused pyramid or off its chunk grid", b,
-                  lengths[b], rg.frames[b]);
-  }
-  rc = srf_frames_table("srf_forward_ragged", lengths, p->Bt, p->T, &rg.lens_t);
-  if (rc) return rc;
-  rc = srf_frames_table("srf_forward_ragged", rg.frames, p->Bt, p->L, &rg.frames_t);
+  const int rc = ragged_prepare("srf_forward_ragged", p, P, num_params, lengths, workspace, workspace_bytes, &rg);
   if (rc) return rc;
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
-  // no normalisation on load, no mixture consistency: pipeline.py does both outside.  (Not under srf_pw_prefer_paired: the ragged
-  // forward runs on one stream.)
+  // no normalisation on load, no mixture consistency: the caller's business here (srf_separate_ragged folds both in).  (Not under
+  // srf_pw_prefer_paired: the ragged forward runs on one stream.)
   return forward_walk(p, P, wav, out, workspace, nullptr, 0, &rg, stream);
+}
+
+// srf_separate over a ragged batch: srf_forward_ragged with a statistics launch over every row's own samples in front, the
+// normalisation in the ragged encoder's load and the rescale (+ mixture consistency) in the ragged overlap-add's store.  wav: the
+// RAW padded mixture; nothing at or past lengths[b] is read by any of the three.
+extern "C" int srf_separate_ragged(const srf_plan* p, const float* const* P, int num_params, const float* wav, const int* lengths,
+                                   float* out, float* stats, int mixture_consistency, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+  SRF_CHECK_ARG(p && P && wav && lengths && out && stats && workspace, "srf_separate_ragged: null pointer");
+  Ragged rg;
+  int rc = ragged_prepare("srf_separate_ragged", p, P, num_params, lengths, workspace, workspace_bytes, &rg);
+  if (rc) return rc;
+  if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
+  rc = srf_wav_stats_ragged_launch(wav, rg.lens_t, stats, p->Bt, p->T, (hipStream_t)stream);
+  if (rc) return rc;
+  return forward_walk(p, P, wav, out, workspace, stats, mixture_consistency, &rg, stream);
 }
 
 extern "C" int srf_debug_fetch(const srf_plan* p, const void* workspace, int what, float* dst,

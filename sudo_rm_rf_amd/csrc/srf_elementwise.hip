@@ -282,16 +282,23 @@ __global__ __launch_bounds__(256) void srf_overlap_add_kernel(const float* __res
       acc += row[r * W + qi + 2];
       return POST ? acc * sd + mean : acc;
     };
+    // RAGGED with POST: a sample at or past the example's end is stored as exact 0 -- est() there is `mean`, not 0 -- with no
+    // read of wav (it may hold anything there) and no correction
+    bool live = true;
+    if constexpr (RAGGED && POST) live = t < srf_frames_of((int)b, tabs...);
     float corr = 0.f;
-    if (POST && mc) {
+    if (POST && mc && live) {
       float tot = 0.f;
       for (int o = 0; o < Co; ++o) tot += est(o);
       corr = ((wav[b * (long)T + t] - mean) / (sd + 1e-9f) - tot) * (1.f / (float)Co);
     }
     for (int o = 0; o < Co; ++o) {
       float v = est(o);
-      if constexpr (RAGGED) v = t < srf_frames_of((int)b, tabs...) ? v : 0.f;
-      out[((size_t)b * Co + o) * T + t] = (POST && mc) ? v + corr : v;
+      if constexpr (RAGGED && !POST) v = t < srf_frames_of((int)b, tabs...) ? v : 0.f;
+      if constexpr (RAGGED && POST)
+        out[((size_t)b * Co + o) * T + t] = live ? (mc ? v + corr : v) : 0.f;
+      else
+        out[((size_t)b * Co + o) * T + t] = (POST && mc) ? v + corr : v;
     }
   }
 }
@@ -312,9 +319,13 @@ int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, in
   const int h = K / 2;
   dim3 grid(((T + h - 1) / h + qw - 1) / qw, Bt);
   if (lens) {
-    SRF_CHECK_ARG(frames && !stats, "internal: the ragged overlap-add takes both tables and no post-processing");
-    hipLaunchKernelGGL((srf_overlap_add_kernel<false, SrfFrames, SrfFrames>), grid, dim3(256), lds, st, z, out, Co, K, L, T, nparts,
-                       qw, stats, wav, mc, *lens, *frames);
+    SRF_CHECK_ARG(frames && (!stats || wav), "internal: the ragged overlap-add takes both tables (and the raw mixture with stats)");
+    if (stats)     // srf_separate_ragged: rescale (+ mixture consistency) on the example's own samples
+      hipLaunchKernelGGL((srf_overlap_add_kernel<true, SrfFrames, SrfFrames>), grid, dim3(256), lds, st, z, out, Co, K, L, T, nparts,
+                         qw, stats, wav, mc, *lens, *frames);
+    else
+      hipLaunchKernelGGL((srf_overlap_add_kernel<false, SrfFrames, SrfFrames>), grid, dim3(256), lds, st, z, out, Co, K, L, T, nparts,
+                         qw, stats, wav, mc, *lens, *frames);
     SRF_CHECK_LAUNCH("overlap_add_ragged", st);
     return SRF_OK;
   }
@@ -335,12 +346,18 @@ int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, in
 // srf_wav_normalize = the first two lines (one block per row: mean, then sum of squared deviations, both
 // fp64, then the normalised row; the row stays in L2 between the three sweeps); srf_wav_denormalize = the
 // last line in one pass.
+// TABS: none, or one SrfFrames = the RAGGED form (srf_wav_stats_ragged): T stays the row stride, row r is lens[r] samples long
+// and nothing at or past them is read.  One block per row, a fixed reduction order, no atomics: a row's two numbers are the same
+// bits whatever the other rows hold.
+template <typename... TABS>
 __global__ __launch_bounds__(256) void srf_wav_normalize_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                float* __restrict__ stats, int T) {
+                                                                float* __restrict__ stats, int Tstride, TABS... tabs) {
+  constexpr bool RAGGED = sizeof...(TABS) != 0;
   __shared__ double red[8];
   __shared__ double bc;
   const long r = blockIdx.x;
-  const float* xr = x + r * (long)T;
+  const float* xr = x + r * (long)Tstride;
+  const int T = RAGGED ? srf_frames_of((int)r, tabs...) : Tstride;      // samples of this row
   const int tid = threadIdx.x;
   auto block_sum = [&](double v) {
     v = srf_wave_sum(v);
@@ -367,21 +384,81 @@ __global__ __launch_bounds__(256) void srf_wav_normalize_kernel(const float* __r
   }
   if (!y) return;   // statistics only (srf_wav_stats: the normalisation itself happens in the encoder's load)
   const float den = fs + 1e-9f;
-  float* yr = y + r * (long)T;
+  float* yr = y + r * (long)Tstride;
   for (int i = tid; i < T; i += 256) yr[i] = (xr[i] - fm) / den;
 }
 
 extern "C" int srf_wav_stats(const float* wav, float* stats, int rows, int T, void* stream) {
   SRF_CHECK_ARG(wav && stats && rows > 0 && T > 0, "srf_wav_stats: bad arguments");
-  hipLaunchKernelGGL(srf_wav_normalize_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, wav, (float*)nullptr,
+  hipLaunchKernelGGL(srf_wav_normalize_kernel<>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, wav, (float*)nullptr,
                      stats, T);
   SRF_CHECK_LAUNCH("wav_stats", stream);
   return SRF_OK;
 }
 
+// {mean, unbiased std} of wav[r, :lengths[r]] per row of a padded [rows, T] tensor (the statistics launch of srf_separate_ragged)
+extern "C" int srf_wav_stats_ragged(const float* wav, const int* lengths, float* stats, int rows, int T, void* stream) {
+  SRF_CHECK_ARG(wav && lengths && stats, "srf_wav_stats_ragged: null pointer");
+  SRF_CHECK_ARG(T > 0, "srf_wav_stats_ragged: bad row stride %d", T);
+  SrfFrames lens;
+  const int rc = srf_frames_table("srf_wav_stats_ragged (lengths in samples)", lengths, rows, T, &lens);
+  if (rc) return rc;
+  return srf_wav_stats_ragged_launch(wav, lens, stats, rows, T, (hipStream_t)stream);
+}
+// the launch alone, from a table the caller has checked (srf_separate_ragged: the one its forward uses)
+int srf_wav_stats_ragged_launch(const float* wav, const SrfFrames& lens, float* stats, int rows, int T, hipStream_t st) {
+  hipLaunchKernelGGL((srf_wav_normalize_kernel<SrfFrames>), dim3((unsigned)rows), dim3(256), 0, st, wav, (float*)nullptr, stats, T,
+                     lens);
+  SRF_CHECK_LAUNCH("wav_stats_ragged", st);
+  return SRF_OK;
+}
+
+// ---- gather of a ragged batch: the caller's separate utterance buffers -> the padded [batch, 1, T] tensor, one launch.  The
+// source pointers travel BY VALUE next to the lengths (1 KB + 512 B of kernel arguments: no upload, no synchronisation).  Dword
+// copies: a source may sit at any element-aligned address, and the whole batch is a few MB.  Row b receives [0, lens[b]);
+// what lies past it is NOT written (no ragged kernel reads it), and a block wholly past the example's end returns at once.
+struct SrfRowPtrs {
+  const unsigned* p[SRF_RAGGED_MAX_BATCH];
+};
+constexpr int GATHER_PER_BLOCK = 256 * 8;      // samples per block
+__global__ __launch_bounds__(256) void srf_wav_gather_ragged_kernel(SrfRowPtrs rows, SrfFrames lens, unsigned* __restrict__ out,
+                                                                    int T) {
+  const int b = blockIdx.y;
+  const int n = lens.n[b];
+  const int i0 = blockIdx.x * GATHER_PER_BLOCK;
+  if (i0 >= n) return;     // block-uniform
+  const unsigned* __restrict__ src = rows.p[b];
+  unsigned* dst = out + (size_t)b * T;
+#pragma unroll
+  for (int k = 0; k < GATHER_PER_BLOCK / 256; ++k) {
+    const int i = i0 + k * 256 + (int)threadIdx.x;
+    if (i < n) dst[i] = src[i];
+  }
+}
+
+extern "C" int srf_wav_gather_ragged(const float* const* rows, const int* lengths, float* wav, int batch, int T, void* stream) {
+  SRF_CHECK_ARG(rows && lengths && wav, "srf_wav_gather_ragged: null pointer");
+  SRF_CHECK_ARG(T > 0, "srf_wav_gather_ragged: bad row stride %d", T);
+  SrfFrames lens;
+  const int rc = srf_frames_table("srf_wav_gather_ragged (lengths in samples)", lengths, batch, T, &lens);
+  if (rc) return rc;
+  SrfRowPtrs ptrs;
+  for (int b = 0; b < SRF_RAGGED_MAX_BATCH; ++b) ptrs.p[b] = nullptr;
+  for (int b = 0; b < batch; ++b) {
+    SRF_CHECK_ARG(rows[b] != nullptr, "srf_wav_gather_ragged: example %d: null source pointer", b);
+    SRF_CHECK_ARG((((size_t)rows[b]) & 3) == 0, "srf_wav_gather_ragged: example %d: source is not 4-byte aligned", b);
+    ptrs.p[b] = reinterpret_cast<const unsigned*>(rows[b]);
+  }
+  dim3 grid((unsigned)((T + GATHER_PER_BLOCK - 1) / GATHER_PER_BLOCK), (unsigned)batch);
+  hipLaunchKernelGGL(srf_wav_gather_ragged_kernel, grid, dim3(256), 0, (hipStream_t)stream, ptrs, lens,
+                     reinterpret_cast<unsigned*>(wav), T);
+  SRF_CHECK_LAUNCH("wav_gather_ragged", stream);
+  return SRF_OK;
+}
+
 extern "C" int srf_wav_normalize(const float* wav, float* out, float* stats, int rows, int T, void* stream) {
   SRF_CHECK_ARG(wav && out && stats && rows > 0 && T > 0, "srf_wav_normalize: bad arguments");
-  hipLaunchKernelGGL(srf_wav_normalize_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, wav, out,
+  hipLaunchKernelGGL(srf_wav_normalize_kernel<>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, wav, out,
                      stats, T);
   SRF_CHECK_LAUNCH("wav_normalize", stream);
   return SRF_OK;

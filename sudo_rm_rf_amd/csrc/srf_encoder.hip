@@ -142,11 +142,21 @@ __global__ __launch_bounds__(256) void srf_encoder_generic_kernel(const float* _
   if (sums) srf_block_stats_atomic<4>(ds, dq, srf_stat_slot(sums, b, blockIdx.x), red);
 }
 
-int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
-                     const float* in_stats, void* stream);
 // The ragged form exists for the shape the fast kernel serves (one audio channel, K = 21: every published Improved model).
 extern "C" int srf_encoder_ragged(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N,
                                   int K, int L, const int* lengths, const int* frames, void* stream) {
+  return srf_encoder_ragged_impl(wav, w, out, sums, Bt, A, T, N, K, L, lengths, frames, nullptr, stream);
+}
+extern "C" int srf_encoder_ragged_stats(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N,
+                                        int K, int L, const int* lengths, const int* frames, const float* in_stats,
+                                        void* stream) {
+  SRF_CHECK_ARG(in_stats != nullptr, "srf_encoder_ragged_stats: null in_stats");
+  return srf_encoder_ragged_impl(wav, w, out, sums, Bt, A, T, N, K, L, lengths, frames, in_stats, stream);
+}
+// in_stats: null, or [Bt][2] {mean, std} per row: row b is normalised on load (srf_separate_ragged); the zero padding past
+// lengths[b] applies to the normalised signal, and nothing past lengths[b] is read either way
+int srf_encoder_ragged_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
+                            const int* lengths, const int* frames, const float* in_stats, void* stream) {
   SRF_CHECK_ARG(wav && w && out, "srf_encoder_ragged: null pointer");
   SRF_CHECK_ARG(Bt > 0 && T > 0 && N > 0 && L > 0, "srf_encoder_ragged: bad sizes");
   SRF_CHECK_ARG(A == 1 && K == 21 && srf_kernel_mode() != 1,
@@ -165,7 +175,7 @@ extern "C" int srf_encoder_ragged(const float* wav, const float* w, float* out, 
   int nz = bxy >= want ? 1 : (int)((want + bxy - 1) / bxy);
   nz = nz > N / 16 ? (N / 16 > 0 ? N / 16 : 1) : nz;
   dim3 grid((L + 127) / 128, Bt, nz);
-  hipLaunchKernelGGL((srf_encoder_fast_kernel<21, SrfFrames, SrfFrames>), grid, dim3(256), 0, st, wav, w, out, sums, T, N, L, (const float*)nullptr,
+  hipLaunchKernelGGL((srf_encoder_fast_kernel<21, SrfFrames, SrfFrames>), grid, dim3(256), 0, st, wav, w, out, sums, T, N, L, in_stats,
                      lens, fr);
   SRF_CHECK_LAUNCH("encoder_ragged", st);
   return SRF_OK;

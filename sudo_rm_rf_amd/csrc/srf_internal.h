@@ -32,14 +32,19 @@ int srf_frames_table(const char* what, const int* frames, int groups, int L, Srf
 int srf_transpose_launch(const float* w, float* wt, int Ci, int M, hipStream_t st);
 // stats: null = plain overlap-add; else [Bt][2] {mean, std} of the raw mixture `wav` [Bt][T] (mc: also mixture consistency)
 // lens / frames (both or neither): the ragged form -- frames of example b at or past frames[b] count as zero and are never
-// read, samples at or past lens[b] are written as 0 (no stats)
+// read, samples at or past lens[b] are written as exact 0; with stats (srf_separate_ragged) the example's own samples are
+// rescaled (mc: + mixture consistency) and wav is read on [0, lens[b]) only
 int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, int L, int T, int nparts, const float* stats,
                            const float* wav, int mc, hipStream_t st, const SrfFrames* lens = nullptr,
                            const SrfFrames* frames = nullptr);
+// per-row {mean, unbiased std} over lens.n[r] samples of a padded [rows, T] tensor; `lens` already checked against T
+int srf_wav_stats_ragged_launch(const float* wav, const SrfFrames& lens, float* stats, int rows, int T, hipStream_t st);
 
 // ---- srf_encoder.hip
 int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
                      const float* in_stats, void* stream);
+int srf_encoder_ragged_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
+                            const int* lengths, const int* frames, const float* in_stats, void* stream);
 
 // ---- srf_causal.hip: srf_forward folds every block's scales with as few launches as possible
 int srf_causal_scale_many(const float* const* src, float* const* dst, const long* n, const float* const* dscale,

@@ -141,6 +141,13 @@ class GroupCommSudoRmRf(nn.Module):
         TAC's per group, the pyramid's) over its own frames -- and is exactly zero past it.  eval() / no_grad only."""
         return self._engine().run_ragged(self, input_wav, lengths)
 
+    def separate_ragged(self, input_wav, lengths, mixture_consistency=True):
+        """The caller-side recipe over a ragged batch in ONE call: input_wav [batch, 1, time] RAW padded mixtures on the GPU.
+        Returns (estimates, stats): estimates[b, :, :lengths[b]] is pipeline.separate of that utterance alone -- normalised by
+        the mean / std of its own samples, forward_ragged, rescaled, mixture consistency (the README's prescription for this
+        model, on by default) -- and exactly zero past it; stats [batch, 2] = {mean, std} per row.  eval() / no_grad only."""
+        return self._engine().run_separate_ragged(self, input_wav, lengths, mixture_consistency)
+
     def pad_to_appropriate_length(self, x):
         """Kept for API parity (reference :324-335); the HIP path never materialises the padding."""
         input_length = x.shape[-1]

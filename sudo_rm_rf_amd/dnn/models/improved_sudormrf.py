@@ -215,6 +215,13 @@ class SuDORMRF(nn.Module):
         padded to its own length, its GlobLNs over its own frames -- and is exactly zero past it.  eval() / no_grad only."""
         return self._engine().run_ragged(self, input_wav, lengths)
 
+    def separate_ragged(self, input_wav, lengths, mixture_consistency=False):
+        """The caller-side recipe over a ragged batch in ONE call: input_wav [batch, 1, time] RAW padded mixtures on the GPU.
+        Returns (estimates, stats): estimates[b, :, :lengths[b]] is pipeline.separate of that utterance alone -- normalised by
+        the mean / std of its own samples, forward_ragged, rescaled (mixture consistency on request) -- and exactly zero past
+        it; stats [batch, 2] = {mean, std} per row.  eval() / no_grad only."""
+        return self._engine().run_separate_ragged(self, input_wav, lengths, mixture_consistency)
+
     def pad_to_appropriate_length(self, x):
         """Kept for API parity (reference :303-314); the HIP path folds the padding into its bounds
         checks and never materialises the padded tensor."""

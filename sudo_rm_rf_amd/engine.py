@@ -139,6 +139,19 @@ class Plan:
                                     _lib.ptr(self.workspace), self.workspace_bytes, _lib.current_stream(wav.device))
         _lib.check(rc, "srf_forward_ragged")
 
+    def separate_ragged(self, param_ptrs, wav, lengths, out, stats, mixture_consistency):
+        """srf_separate_ragged: per-row statistics over the row's own samples, normalise-on-load, the ragged forward, rescale
+        (+ mixture consistency) -- `wav` is the RAW padded mixture, `stats` [batch, 2] is written."""
+        lib = _lib.load()
+        need = lib.srf_plan_ragged_workspace_bytes(self.handle)
+        if need > self.workspace_bytes:
+            raise _lib.SrfError("the ragged forward needs %d workspace bytes, the plan holds %d" % (need, self.workspace_bytes))
+        arr = (C.c_int * len(lengths))(*lengths)
+        rc = lib.srf_separate_ragged(self.handle, param_ptrs, self.num_params, _lib.ptr(wav), arr, _lib.ptr(out), _lib.ptr(stats),
+                                     int(bool(mixture_consistency)), _lib.ptr(self.workspace), self.workspace_bytes,
+                                     _lib.current_stream(wav.device))
+        _lib.check(rc, "srf_separate_ragged")
+
     def debug_fetch(self, what, shape):
         dst = torch.empty(shape, dtype=torch.float32, device=self.device)
         rc = _lib.load().srf_debug_fetch(self.handle, _lib.ptr(self.workspace), what, _lib.ptr(dst),
@@ -459,6 +472,16 @@ class ModelEngine:
         lengths[b] (a list or CPU int tensor; what lies past it is never read); returns [batch, num_sources, T] with row b
         equal to model(wav[b:b+1, :, :lengths[b]]) up to lengths[b] and exactly zero past it.  Inference only: a single
         stream, no autograd graph."""
+        return self._run_ragged(module, wav, lengths, None)
+
+    def run_separate_ragged(self, module, wav, lengths, mixture_consistency):
+        """The caller-side recipe over a ragged batch in one call (srf_separate_ragged).  wav: the RAW mixtures, [batch, 1, T]
+        on the GPU, row b valid up to lengths[b]; returns (estimates [batch, num_sources, T] in each mixture's own scale, exactly
+        zero past lengths[b]; stats [batch, 2] = {mean, unbiased std} of each row's own samples).  Same checks as run_ragged."""
+        return self._run_ragged(module, wav, lengths, bool(mixture_consistency))
+
+    def _run_ragged(self, module, wav, lengths, separate_mc):
+        """separate_mc: None = the plain ragged forward, else srf_separate_ragged with that mixture-consistency setting"""
         if not isinstance(wav, torch.Tensor) or wav.dim() != 3 or wav.shape[1] != 1:
             raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(getattr(wav, "shape", ())),))
         if wav.device.type != "cuda":
@@ -488,9 +511,13 @@ class ModelEngine:
             if plan.num_params != len(params):
                 raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
             out = torch.empty((batch, module.num_sources, T), dtype=torch.float32, device=x.device)
-            plan.forward_ragged(self._param_table(params, x.device), x, lengths, out)
+            if separate_mc is None:
+                plan.forward_ragged(self._param_table(params, x.device), x, lengths, out)
+            else:
+                stats = torch.empty((batch, 2), dtype=torch.float32, device=x.device)
+                plan.separate_ragged(self._param_table(params, x.device), x, lengths, out, stats, separate_mc)
             self.last_plan = plan
-        return out
+        return out if separate_mc is None else (out, stats)
 
     def ragged_plan_supported(self, batch, T, device):
         """Whether run_ragged would take a [batch, 1, T] input on `device` (creates / caches the plan, no workspace)."""

@@ -9,7 +9,7 @@ rescale and the mixture consistency in the decoder's overlap-add.  The stand-alo
 srf_wav_denormalize, ``ops``) remain for callers that need the normalised mixture itself."""
 import torch
 
-from . import ops
+from . import ops, ragged
 
 
 def separate(model, mixture, mixture_consistency=None):
@@ -62,7 +62,7 @@ def ragged_route(model, length=None):
     configurations, too-short utterances).  A candidate batch still falls back as a whole when the plan of its (batch, T) is
     refused (srf_plan_ragged_supported: small shapes)."""
     kind = type(model).__name__
-    if kind not in ("SuDORMRF", "GroupCommSudoRmRf") or not hasattr(model, "forward_ragged"):
+    if kind not in ("SuDORMRF", "GroupCommSudoRmRf") or not hasattr(model, "separate_ragged"):
         return "single"
     if getattr(model, "enc_kernel_size", 0) != 21 or getattr(model, "out_channels", 0) != 256:
         return "single"
@@ -81,16 +81,17 @@ def ragged_route(model, length=None):
 def separate_list(model, mixtures, mixture_consistency=None, max_batch=32):
     """separate() over a list of utterances of unequal length: mixtures = tensors [T_i] or [1, T_i] on the model's MI355X;
     returns the estimates [num_sources, T_i] in the caller's order.  The README recipe per utterance (mean / std over its own
-    samples, forward, rescale; mixture consistency as in separate()), with the forwards of a length-sorted batch run as ONE
-    ragged forward (forward_ragged of the Improved and the GroupComm model) where the model and the batch allow it, and through separate() one by one where
-    they do not -- so the answer is always the per-utterance one."""
+    samples, forward, rescale; mixture consistency as in separate()), with a length-sorted batch run as ONE gather launch
+    (ragged.wav_gather) and ONE separate_ragged call of the Improved / the GroupComm model -- the recipe folded into the ragged
+    forward as separate() folds it into the uniform one; the results are then views of that call's output -- where the model and
+    the batch allow it, and through separate() one by one where they do not -- so the answer is always the per-utterance one."""
     mixes = []
     for m in mixtures:
         if m.dim() == 2 and m.shape[0] == 1:
             m = m[0]
         if m.dim() != 1 or m.numel() == 0:
             raise RuntimeError("separate_list() expects tensors [time] or [1, time], got %s" % (tuple(m.shape),))
-        mixes.append(m.detach().to(torch.float32))
+        mixes.append(m.detach().to(torch.float32).contiguous())
     if mixture_consistency is None:
         mixture_consistency = type(model).__name__ == "GroupCommSudoRmRf"
     results = [None] * len(mixes)
@@ -104,19 +105,13 @@ def separate_list(model, mixtures, mixture_consistency=None, max_batch=32):
             if len(idx) < 2 or not model._engine().ragged_plan_supported(len(idx), T, dev):
                 single.extend(idx)
                 continue
-            lens = [mixes[i].numel() for i in idx]
-            x = torch.zeros((len(idx), 1, T), dtype=torch.float32, device=dev)
-            stats = []
-            for r, i in enumerate(idx):           # per-utterance normalisation over its own samples (README.md:100-104)
-                mean, std = mixes[i].mean(), mixes[i].std()
-                x[r, 0, :lens[r]] = (mixes[i] - mean) / (std + 1e-9)
-                stats.append((mean, std))
-            est = model.forward_ragged(x, lens)
+            # the whole recipe of the batch on the device: one gather launch from the utterances' own buffers into the padded
+            # batch, then statistics over each row's own samples, normalise-on-load, the ragged forward, rescale and mixture
+            # consistency in ONE separate_ragged call; the results are views of its output
+            x, lens = ragged.wav_gather([mixes[i] for i in idx], T)
+            est, _ = model.separate_ragged(x, lens, mixture_consistency)
             for r, i in enumerate(idx):
-                e = est[r, :, :lens[r]] * stats[r][1] + stats[r][0]
-                if mixture_consistency:           # (README.md:106-114: applied to the rescaled estimates, against the normalised mixture)
-                    e = e + (x[r, :, :lens[r]] - e.sum(0, keepdim=True)) / e.shape[0]
-                results[i] = e
+                results[i] = est[r, :, :lens[r]]
         for i in single:
             results[i] = separate(model, mixes[i].unsqueeze(0), mixture_consistency)[0]
     return results

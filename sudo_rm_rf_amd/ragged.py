@@ -34,9 +34,53 @@ def frames_ok(frames, L, D):
     return bool(_lib.load().srf_pyramid_ragged_frames_ok(int(frames), int(L), int(D)))
 
 
-def encoder(wav, weight, L, lengths, frames, sums=None):
-    """srf_encoder_ragged: wav [Bt,1,T] (row b valid up to lengths[b]), weight [N,1,21] -> [Bt,N,L], zeros from frames[b] on."""
-    dev = _chk(wav, weight, sums)
+def wav_stats(wav, lengths):
+    """srf_wav_stats_ragged: wav [rows, T] or [rows, 1, T] (row b valid up to lengths[b]; nothing at or past it is read) ->
+    stats [rows, 2] = {mean, unbiased std} of wav[b, :lengths[b]] (fp64 sums in a fixed order: a row's two numbers do not
+    depend on the other rows)."""
+    dev = _chk(wav)
+    if wav.dtype != torch.float32 or wav.dim() not in (2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+        raise _lib.SrfError("srf_wav_stats_ragged: expected a float32 tensor [rows, T] or [rows, 1, T], got %s %s"
+                            % (wav.dtype, tuple(wav.shape)))
+    rows, T = wav.shape[0], wav.shape[-1]
+    lens, n = _table(lengths, "lengths")
+    if n != rows:
+        raise _lib.SrfError("srf_wav_stats_ragged: %d lengths for %d rows" % (n, rows))
+    stats = torch.empty((rows, 2), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().srf_wav_stats_ragged(_lib.ptr(wav), lens, _lib.ptr(stats), rows, T, _lib.current_stream(dev)),
+               "srf_wav_stats_ragged")
+    return stats
+
+
+def wav_gather(utterances, T):
+    """srf_wav_gather_ragged: a list of 1-D contiguous float32 tensors on one GPU (any element-aligned address: views into a
+    larger buffer are fine) -> (wav [batch, 1, T] from torch.empty, lengths).  Row b holds utterance b in [0, lengths[b]);
+    what lies past it is NOT written -- no ragged kernel reads it.  One launch; the pointers travel in its arguments."""
+    utterances = list(utterances)
+    if not utterances:
+        raise _lib.SrfError("srf_wav_gather_ragged: empty list of utterances")
+    for i, u in enumerate(utterances):
+        if not isinstance(u, torch.Tensor) or u.dim() != 1 or u.dtype != torch.float32 or u.numel() == 0:
+            raise _lib.SrfError("srf_wav_gather_ragged: utterance %d must be a non-empty 1-D float32 tensor, got %s %s"
+                                % (i, getattr(u, "dtype", type(u).__name__), tuple(getattr(u, "shape", ()))))
+        if u.device != utterances[0].device:
+            raise _lib.SrfError("srf_wav_gather_ragged: utterance %d is on %s, utterance 0 on %s" % (i, u.device, utterances[0].device))
+    dev = _chk(*utterances)
+    batch = len(utterances)
+    lengths = [u.numel() for u in utterances]
+    lens, _ = _table(lengths, "lengths")
+    rows = (C.c_void_p * batch)(*[u.data_ptr() for u in utterances])
+    wav = torch.empty((batch, 1, int(T)), dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().srf_wav_gather_ragged(rows, lens, _lib.ptr(wav), batch, int(T), _lib.current_stream(dev)),
+               "srf_wav_gather_ragged")
+    return wav, lengths
+
+
+def encoder(wav, weight, L, lengths, frames, sums=None, in_stats=None):
+    """srf_encoder_ragged: wav [Bt,1,T] (row b valid up to lengths[b]), weight [N,1,21] -> [Bt,N,L], zeros from frames[b] on.
+    in_stats [Bt,2] = {mean, std} per row (wav_stats): the row is normalised on load, (x - mean) / (std + 1e-9), and the zero
+    padding past lengths[b] applies to the normalised signal (srf_encoder_ragged_stats)."""
+    dev = _chk(wav, weight, sums, in_stats)
     Bt, A, T = wav.shape
     N, A2, K = weight.shape
     assert A == A2
@@ -45,6 +89,14 @@ def encoder(wav, weight, L, lengths, frames, sums=None):
     if n1 != Bt or n2 != Bt:
         raise _lib.SrfError("srf_encoder_ragged: %d lengths / %d frames for a batch of %d" % (n1, n2, Bt))
     out = torch.empty((Bt, N, L), dtype=torch.float32, device=dev)
+    if in_stats is not None:
+        if in_stats.dtype != torch.float32 or tuple(in_stats.shape) != (Bt, 2):
+            raise _lib.SrfError("srf_encoder_ragged_stats: in_stats must be float32 [%d, 2], got %s %s"
+                                % (Bt, in_stats.dtype, tuple(in_stats.shape)))
+        _lib.check(_lib.load().srf_encoder_ragged_stats(_lib.ptr(wav), _lib.ptr(weight), _lib.ptr(out), _lib.ptr(sums), Bt, A, T, N,
+                                                        K, L, lens, frs, _lib.ptr(in_stats), _lib.current_stream(dev)),
+                   "srf_encoder_ragged_stats")
+        return out
     _lib.check(_lib.load().srf_encoder_ragged(_lib.ptr(wav), _lib.ptr(weight), _lib.ptr(out), _lib.ptr(sums), Bt, A, T, N, K, L,
                                               lens, frs, _lib.current_stream(dev)), "srf_encoder_ragged")
     return out

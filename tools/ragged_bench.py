@@ -11,7 +11,19 @@ alternating, timed with device events:
 
 Writes profiles/ragged_forward.txt (--model groupcomm: profiles/ragged_forward_groupcomm.txt), or --out.  The Improved mode
 exits 1 unless (a) beats (b) and is no slower than (c) by more than the spread; the GroupComm mode only reports -- for that
-model the comparison that matters is (a) against (b), the per-utterance path separate_list took before."""
+model the comparison that matters is (a) against (b), the per-utterance path separate_list took before.
+
+--mode separate_list: pipeline.separate_list on a length-sorted list of 32 utterances, lengths on [T/2, T], both models
+(--model picks one), two arms in one process, alternating, device events, median over the rounds:
+
+  (s) pipeline.separate_list: ragged.wav_gather + model.separate_ragged, the recipe inside the kernels
+  (p) the recipe as torch operators around the unchanged model.forward_ragged -- a zeroed padded tensor, mean / std / normalise /
+      slice-assign per utterance, and after the forward the rescale and the mixture consistency per utterance -- restated here
+
+with the library's launches (ops.kernel_trace) and the ATen operators that launch a kernel (a TorchDispatchMode count; views
+and allocations left out) of one call of each arm.  The arms are not symmetric: (s) is the whole of separate_list, its Python
+sort, bucketing and plan lookup included; (p) only the recipe on the batch already sorted and bucketed -- the ratio understates
+the gain.  Writes profiles/ragged_separate_list.txt, or --out."""
 import argparse
 import json
 import os
@@ -25,18 +37,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--T", type=int, default=32000)
-    ap.add_argument("--model", choices=["improved", "groupcomm"], default="improved")
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    gc = args.model == "groupcomm"
-    if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "ragged_forward_groupcomm.txt" if gc else "ragged_forward.txt")
+def load_model(gc, dev):
+    """cfg 3 (GroupComm) or cfg 2 (Improved) with the golden weights, in eval mode on `dev`"""
     from oracle import weights
     from oracle.schema import ModelConfig
     import sudo_rm_rf.dnn.models.groupcomm_sudormrf_v2 as groupcomm_sudormrf_v2
@@ -45,10 +47,135 @@ def main():
     man = json.load(open(os.path.join(ROOT, "tests", "golden", "MANIFEST.json")))["cases"][case]
     cfg = ModelConfig(**man["config"])
     sd = weights.make_state_dict(cfg, man["weight_seed"])
-    dev = torch.device("cuda:0")
     model = (groupcomm_sudormrf_v2.GroupCommSudoRmRf if gc else improved_sudormrf.SuDORMRF)(**cfg.ctor_kwargs())
     model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
-    model = model.to(dev).eval()
+    return model.to(dev).eval()
+
+
+def torch_op_recipe(model, mixes, mixture_consistency, T):
+    """Arm (p): one length-sorted ragged batch the way separate_list ran it before separate_ragged existed -- the recipe as torch
+    operators per utterance around model.forward_ragged."""
+    lens = [m.numel() for m in mixes]
+    x = torch.zeros((len(mixes), 1, T), dtype=torch.float32, device=mixes[0].device)
+    stats = []
+    for r, m in enumerate(mixes):
+        mean, std = m.mean(), m.std()
+        x[r, 0, :lens[r]] = (m - mean) / (std + 1e-9)
+        stats.append((mean, std))
+    est = model.forward_ragged(x, lens)
+    out = []
+    for r in range(len(mixes)):
+        e = est[r, :, :lens[r]] * stats[r][1] + stats[r][0]
+        if mixture_consistency:
+            e = e + (x[r, :, :lens[r]] - e.sum(0, keepdim=True)) / e.shape[0]
+        out.append(e)
+    return out
+
+
+# ATen operators that launch no kernel: views, allocations, metadata
+_NO_KERNEL = {"empty", "empty_like", "empty_strided", "select", "slice", "view", "_unsafe_view", "reshape", "unsqueeze", "squeeze",
+              "expand", "detach", "alias", "as_strided", "t", "transpose", "permute", "_to_copy", "lift_fresh", "resize_"}
+
+
+def count_launches(fn, dev):
+    """(library launches by name, kernel-launching ATen operators by name) of one call of fn"""
+    from collections import Counter
+    from torch.utils._python_dispatch import TorchDispatchMode
+    from sudo_rm_rf_amd import ops
+    aten = Counter()
+
+    class Count(TorchDispatchMode):
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            name = func.overloadpacket.__name__
+            if name not in _NO_KERNEL:
+                aten[name] += 1
+            return func(*args, **(kwargs or {}))
+
+    with ops.kernel_trace(dev) as tr, Count():
+        fn()
+    return Counter(n for n, _ in tr.launches), aten
+
+
+def separate_list_mode(args):
+    from oracle import weights
+    from sudo_rm_rf_amd import pipeline
+    dev = torch.device("cuda:0")
+    B, T = args.batch, args.T
+    lines = ["separate_list on one ragged batch: %d utterances, lengths uniform on [T/2, T], T = %d (seed 2026), sorted by length"
+             % (B, T),
+             "device: %s; %d alternating rounds after %d warm-up rounds; device-event times in ms: median [min .. max]"
+             % (torch.cuda.get_device_name(dev), args.rounds, args.warmup),
+             "(s) pipeline.separate_list: wav_gather + separate_ragged    (p) the recipe as torch operators around forward_ragged",
+             "(s) times the whole call, its sort, bucketing and plan lookup included; (p) only the recipe on the sorted batch"]
+    rng = np.random.default_rng(2026)
+    lens = sorted(int(v) for v in rng.integers(T // 2, T + 1, B))
+    gain = np.geomspace(0.05, 20.0, B)[rng.permutation(B)]
+    for gc in ([False, True] if args.model is None else [args.model == "groupcomm"]):
+        model = load_model(gc, dev)
+        mixes = [torch.from_numpy((gain[i] * weights.make_mixture(1, n, 9400 + i)[0, 0] + 0.1).astype(np.float32)).to(dev)
+                 for i, n in enumerate(lens)]
+        (idx, Tb), = pipeline.ragged_batches(lens, B)
+        assert idx == list(range(B)) and model._engine().ragged_plan_supported(B, Tb, dev)
+        runs = [("s", lambda: pipeline.separate_list(model, mixes, max_batch=B)),
+                ("p", lambda: torch_op_recipe(model, mixes, gc, Tb))]
+        times = {k: [] for k, _ in runs}
+        with torch.no_grad():
+            for _ in range(args.warmup):
+                for _, fn in runs:
+                    fn()
+            torch.cuda.synchronize()
+            got, want = runs[0][1](), runs[1][1]()
+            worst = max(float((g - w).abs().max()) / max(1.0, float(m.std())) for g, w, m in zip(got, want, mixes))
+            counts = {k: count_launches(fn, dev) for k, fn in runs}
+            torch.cuda.synchronize()
+            for _ in range(args.rounds):
+                for k, fn in runs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    e1.synchronize()
+                    times[k].append(e0.elapsed_time(e1))
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        lines.append("")
+        lines.append("%s weights, mixture consistency %s, padded length %d: %.1f %% of the padded samples are real"
+                     % ("cfg 3 (GroupComm)" if gc else "cfg 2 (Improved)", "on" if gc else "off", Tb, 100 * sum(lens) / float(B * Tb)))
+        lines.append("max |(s) - (p)| / max(1, std) over the utterances: %.3e" % worst)
+        for k, name in (("s", "(s) separate_list"), ("p", "(p) torch-operator recipe")):
+            lib, aten = counts[k]
+            lines.append("%-28s %8.3f [%8.3f .. %8.3f]   library launches %3d, ATen operators with a kernel %4d"
+                         % (name, med[k], min(times[k]), max(times[k]), sum(lib.values()), sum(aten.values())))
+        lines.append("(p) / (s) = %.2f;  (s) faster than (p): %s" % (med["p"] / med["s"], med["s"] < med["p"]))
+        lines.append("ATen operators of (s): %s" % (dict(counts["s"][1]) or "none"))
+        lines.append("ATen operators of (p): %s" % dict(counts["p"][1]))
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--T", type=int, default=32000)
+    ap.add_argument("--mode", choices=["forward", "separate_list"], default="forward")
+    ap.add_argument("--model", choices=["improved", "groupcomm"], default=None,
+                    help="default: improved (--mode forward), both in turn (--mode separate_list)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.mode == "separate_list":
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "ragged_separate_list.txt")
+        return separate_list_mode(args)
+    gc = args.model == "groupcomm"
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "ragged_forward_groupcomm.txt" if gc else "ragged_forward.txt")
+    from oracle import weights
+    dev = torch.device("cuda:0")
+    model = load_model(gc, dev)
     B, T = args.batch, args.T
     rng = np.random.default_rng(2026)
     lens = [int(v) for v in rng.integers(T // 2, T + 1, B)]
