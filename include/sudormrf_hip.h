@@ -1,6 +1,6 @@
 /*
  * sudormrf_hip.h -- C ABI of libsudormrf_hip.so, the MI355X (gfx950) hot path of
- * SuDoRM-RF (Improved SuDORMRF, GroupComm SuDoRM-RF v2 and Causal SuDORMRF v3) inference forward.
+ * SuDoRM-RF (Improved SuDORMRF, GroupComm SuDoRM-RF v2, Causal SuDORMRF v3 and attentive SuDORMRF v2) inference forward.
  *
  * Boundary replaced (reference is pure PyTorch, paths relative to
  * /root/reference/sudo_rm_rf/dnn/):
@@ -22,6 +22,8 @@
  *   srf_pit_sisdr_*        <- PITLossWrapper(PairwiseNegSDR("sisdr")) fwd/bwd        losses/sisdr.py:254-311,426-458
  *   srf_perm_inv_sisdr     <- PermInvariantSISDR.forward (validation metric)        losses/sisdr.py:66-196
  *   srf_forward (causal)   <- CausalSuDORMRF.forward      models/causal_improved_sudormrf_v3.py (ABI 16)
+ *   srf_forward (attentive)<- SuDORMRF.forward             models/attentive_sudormrf_v2.py (srf_attentive_plan_create, below)
+ *   srf_mha_attention      <- MHAttentionLayer.forward: softmax(q k^T / sqrt(d)) v per head, between its four Linear layers
  *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17; row-table push: ABI 19)
  *   srf_zeroref_snr_*      <- PermInvariantSNRwithZeroRefs fwd/bwd (FUSS training loss)  losses/snr.py:13-142 (ABI 18)
  *   srf_stab_sisdr         <- StabilizedPermInvSISDRMetric.forward (FUSS validation)    losses/sisdr.py:460-576
@@ -907,6 +909,37 @@ int srf_feeder_wait(srf_feeder* f, float** wave, int** len, float** stat, int* n
  * with the population std of the padded mixture. */
 int srf_feeder_normalize(const float* raw, const int* len, const float* stat, int B, int n_streams, int T, int normalize,
                          float eps, float* mix, float* src, void* stream);
+
+/* ---- Attentive SuDoRM-RF v2 (additive to ABI 19; attentive_sudormrf_v2.py) ----
+ * The Improved model with a TransformerLayer on the deepest level of every U-block.  Inference only.
+ * srf_attentive_plan_create: base = the Improved model's fields (variant is ignored, in_audio_channels and group_size must be 1);
+ *   n_heads / att_dims = the blocks' MHAttentionLayer (H heads of d channels).  The input is padded as the reference pads it, to
+ *   a multiple of lcm(K / 2, 2^D) -- not the Improved model's (K / 2) 2^D.  The plan works with srf_forward, srf_separate,
+ *   srf_plan_workspace_bytes / _num_params / _frames / _padded_length and the profiler.  Parameters in state_dict() order, per
+ *   block: the Improved block's tensors, then mha.{Q,K,V,O}_proj.{weight, bias}, out_norm.{gamma, beta},
+ *   out_mha_norm.{gamma, beta}, ffn.conv.{weight, bias}, ffn.norm.{gamma, beta}, ffn.act.weight, pos_enc.pe ([1, 5000, C], read
+ *   on the device).  Refused before anything is launched (SRF_EINVAL, the message names the argument): upsampling_depth < 2,
+ *   a deepest level of more than SRF_ATT_MAX_LEN or fewer than 1 positions, n_heads / att_dims < 1; srf_forward_train,
+ *   srf_backward(_wav) and srf_forward_ragged / srf_separate_ragged refuse such a plan, srf_plan_ragged_supported is 0.
+ * srf_mha_attention: softmax attention per (example, head).  q: [Bt, H d, Lq], k, v: [Bt, H d, Lk], o: [Bt, H d, Lq] (WRITTEN),
+ *   channel h d + j belongs to head h; o[., h d + j, lq] = sum_lk softmax_lk(scale * <q[., h, lq], k[., h, lk]>) v[., h d + j, lk].
+ *   q is scaled before the product, as the reference does.  Any float-aligned address; any Lq, Lk >= 1 (online softmax over key
+ *   tiles, the score matrix never reaches memory).  Kernels: the exact-fp32 MFMA form for d % 16 == 0, 16 <= d <= 256
+ *   (srf_mha_attention_mfma_supported, kernel modes 0 and 2; profiler name mha_attention_mfma), a VALU form for every other
+ *   d <= 1024 (mha_attention_generic).
+ * srf_posenc_apply: x[b, c, l] = norm(a)[b, c, l] + pe[l, c] (norm nullable = identity; prelu ignored); pe: [max_len, C].
+ * srf_gln_apply2_add: z = fnorm(f) + ynorm(y), each GlobLN (+ PReLU where its prelu is set) from its own statistics;
+ *   out_sums (nullable) += {sum, sumsq} of z.  f, y, z: [groups, channels, length] at any float-aligned address. */
+#define SRF_VARIANT_ATTENTIVE 3
+#define SRF_ATT_MAX_LEN 5000
+int srf_attentive_plan_create(const srf_config* base, int n_heads, int att_dims, int batch, int T, srf_plan** out);
+int srf_mha_attention_mfma_supported(int d);
+int srf_mha_attention(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq, int Lk, float scale,
+                      void* stream);
+int srf_posenc_apply(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L, int max_len,
+                     void* stream);
+int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z, double* out_sums,
+                       int groups, int channels, int length, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,8 @@ RAGGED_MAX_BATCH = 128     # SRF_RAGGED_MAX_BATCH
 STAT_BUCKETS = 64
 
 SRF_OK = 0
-VARIANT_IMPROVED, VARIANT_GROUPCOMM, VARIANT_CAUSAL = 0, 1, 2
+VARIANT_IMPROVED, VARIANT_GROUPCOMM, VARIANT_CAUSAL, VARIANT_ATTENTIVE = 0, 1, 2, 3
+ATT_MAX_LEN = 5000         # SRF_ATT_MAX_LEN
 
 
 class SrfError(RuntimeError):
@@ -201,6 +202,11 @@ _PROTOS = {
     "srf_stream_push_rows_num_launches": (_i, [_vp, _i]),
     "srf_causal_stream_pyramid": (_i, [_vp, _vp, C.POINTER(_vp), _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i,
                                        _i, _vp]),
+    "srf_attentive_plan_create": (_i, [C.POINTER(srf_config), _i, _i, _i, _i, C.POINTER(_vp)]),
+    "srf_mha_attention_mfma_supported": (_i, [_i]),
+    "srf_mha_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp]),
+    "srf_posenc_apply": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _i, _vp]),
+    "srf_gln_apply2_add": (_i, [_vp, C.POINTER(srf_norm), _vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

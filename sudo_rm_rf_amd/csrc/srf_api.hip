@@ -166,7 +166,7 @@ extern "C" int srf_get_kernel_mode(void) { return g_kernel_mode.load(std::memory
 __global__ __launch_bounds__(256) void srf_zero_kernel(uint4* __restrict__ p, size_t n16) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0, 0, 0, 0);
 }
-static int srf_zero_launch(void* p, size_t bytes, hipStream_t st) {
+int srf_zero_launch(void* p, size_t bytes, hipStream_t st) {
   SRF_CHECK_ARG(srf_aligned16(p) && bytes % 16 == 0, "internal: zero fill needs 16-byte granules");
   const size_t n16 = bytes / 16;
   if (!n16) return SRF_OK;
@@ -185,18 +185,15 @@ extern "C" size_t srf_decoder_scratch_floats(int Bt, int Ci, int Co, int K, int 
   return srf_align_up(M * Ci, 64) + srf_align_up(M, 64) + srf_align_up((size_t)Bt * M * L, 64);
 }
 
-static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T,
-                            float* scratch, const float* post_stats, const float* post_wav, int post_mc, void* stream,
-                            const float* in_prelu = nullptr);
 extern "C" int srf_decoder(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K,
                            int L, int T, float* scratch, void* stream) {
   return srf_decoder_impl(v, w, out, Bt, Ci, Co, K, L, T, scratch, nullptr, nullptr, 0, stream);
 }
 // post_stats / post_wav / post_mc: the callers' rescale (+ mixture consistency) folded into the overlap-add (srf_separate)
 // in_prelu: a PReLU slope applied to v as the frame GEMM loads it (the causal model's mask_nl_class), NULL = none
-static int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T,
-                            float* scratch, const float* post_stats, const float* post_wav, int post_mc, void* stream,
-                            const float* in_prelu) {
+int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T,
+                     float* scratch, const float* post_stats, const float* post_wav, int post_mc, void* stream,
+                     const float* in_prelu) {
   SRF_CHECK_ARG(v && w && out && scratch, "srf_decoder: null pointer");
   SRF_CHECK_ARG(Bt > 0 && Ci > 0 && Co > 0 && L > 0 && T > 0, "srf_decoder: bad sizes");
   SRF_CHECK_ARG(K >= 3 && (K & 1), "srf_decoder: kernel size must be odd (got %d)", K);
@@ -249,7 +246,9 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   SRF_CHECK_ARG(c && out, "srf_plan_create: null pointer");
   *out = nullptr;
   SRF_CHECK_ARG(c->variant == SRF_VARIANT_IMPROVED || c->variant == SRF_VARIANT_GROUPCOMM || c->variant == SRF_VARIANT_CAUSAL,
-                "srf_plan_create: unknown variant %d", c->variant);
+                c->variant == SRF_VARIANT_ATTENTIVE ? "srf_plan_create: variant %d (attentive) takes srf_attentive_plan_create"
+                                                    : "srf_plan_create: unknown variant %d",
+                c->variant);
   if (c->variant == SRF_VARIANT_CAUSAL) return causal_plan_create(c, batch, T, out);
   SRF_CHECK_ARG(batch > 0 && T > 0, "srf_plan_create: batch and T must be positive");
   SRF_CHECK_ARG(c->out_channels > 0 && c->in_channels > 0 && c->num_blocks > 0 && c->enc_num_basis > 0 &&
@@ -736,6 +735,8 @@ static int srf_forward_impl(const srf_plan* p, const float* const* P, int num_pa
   // host-side gap since the previous forward
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
   if (p->cfg.variant == SRF_VARIANT_CAUSAL) return causal_forward(p, P, wav, out, workspace, stream);
+  if (p->cfg.variant == SRF_VARIANT_ATTENTIVE)
+    return srf_attentive_forward(p, P, wav, out, workspace, wav_stats, mixture_consistency, stream);
   return forward_walk(p, P, wav, out, workspace, wav_stats, mixture_consistency, nullptr, stream);
 }
 
@@ -766,6 +767,7 @@ static bool plan_ragged_now(const srf_plan* p, const char** why) {
   };
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
   if (c.variant == SRF_VARIANT_CAUSAL) return no("the causal model has no ragged kernels (per-example calls)");
+  if (c.variant == SRF_VARIANT_ATTENTIVE) return no("the attentive model has no ragged kernels (per-example calls)");
   if (p->A != 1 || c.enc_kernel_size != 21) return no("the ragged encoder is the one-channel K = 21 kernel");
   if (gc && (c.group_size != 16 || p->nB != 16))
     return no("GroupComm: the ragged TAC is the MFMA kernel (group_size = 16, out_channels = 256)");

@@ -1,0 +1,341 @@
+// Softmax attention and the two small glue kernels of the attentive model's transformer layer
+// (attentive_sudormrf_v2.py: MHAttentionLayer.forward, TransformerLayer.forward).
+//
+//   srf_mha_attention   o[b, h d + j, lq] = sum_lk softmax_lk(scale * sum_j q[b, h d + j, lq] k[b, h d + j, lk]) v[b, h d + j, lk]
+//   srf_posenc_apply    x[b, c, l] = GlobLN(a)[b, c, l] + pe[l, c]                      (PositionalEncoding on the transposed tensor)
+//   srf_gln_apply2_add  z = norm_f(f) + norm_y(y), {sum, sumsq} of z accumulated       (out_norm's input: ffn(y) + y)
+//
+// Every tensor is [batch, channel, time] like the rest of the library: q, k, v are the outputs of 1x1 convolutions, channel
+// h d + j belongs to head h, and nothing is transposed in memory.
+//
+// The MFMA form (d % 16 == 0, 16 <= d <= 256): one wavefront per (example, head, 32 queries), key tiles of 32, online softmax.
+// Both contractions run on v_mfma_f32_32x32x2_f32 (exact fp32) with the QUERY as the N index of both products:
+//     S^T[key, query] = sum_j K[j, key] Q[j, query]        A = K (lane: key = l & 31, j = 2 s + (l >> 5)), B = Q, d / 2 steps
+//     O^T[j, query]  += sum_key V[j, key] P^T[key, query]   A = V, B = P^T, 16 steps per 32 output channels
+// so that a lane owns ONE query (column l & 31) in S^T, P^T and O^T alike: the running maximum, the running denominator and the
+// rescale of the accumulators are per-lane scalars, and the probabilities go from the first product's accumulator registers
+// straight into the second product's B operand -- register r of S^T holds key (r & 3) + 8 (r >> 2) + 4 (l >> 5), and step r of
+// the second product simply contracts over THAT pair of keys (the order of a contraction is free as long as A agrees: V is
+// read from LDS at the same key).  The score matrix never leaves the registers.
+//   Q (pre-scaled, as the reference scales it before the product) is staged once in LDS, [d][32 queries]; O^T takes 16
+//   accumulator registers per 32 channels;
+//   K is read from global memory as the A operand (a half-wavefront reads 32 consecutive keys of one channel);
+//   V goes through LDS 32 channels at a time (32 keys x 32 channels, XOR-swizzled rows: the A operand of the second product
+//   walks channels across lanes), so that a block holds 32 d + 1024 floats of LDS -- 36 KB at d = 256, four blocks per CU.
+// Edges.  Every global load is predicated (keys >= Lk, queries >= Lq, channels >= d read nothing and count as 0) and a dword
+// wide: rows are L floats long with L generally odd, so no wider load is aligned.  Keys >= Lk get the score -inf, i.e. the
+// weight exp(-inf) = 0 exactly; a key tile always holds at least one real key (kt < Lk), so the new running maximum is finite and
+// "m_old - m_new" is never inf - inf (m_old = -inf gives the rescale factor exp(-inf) = 0).  Queries >= Lq compute on zeros and
+// store nothing.
+//
+// The generic form (any other d <= 1024): one wavefront per query, a lane per key for the scores and a lane per output channel
+// for the weighted sum (the probabilities travel by v_readlane), plain fp32 FMA.
+#include "srf_internal.h"
+
+typedef float srf_f32x16 __attribute__((ext_vector_type(16)));
+
+struct MhaArgs {
+  const float *q, *k, *v;
+  float* o;
+  long qs, ks, vs, os;   // example strides (floats)
+  int H, d, Lq, Lk;
+  float scale;
+};
+
+#define SRF_MHA_NEG_INF (-__builtin_inff())
+
+template <int NCH>   // 32-channel chunks of the head dimension (d <= 32 NCH): 16 accumulator registers each
+__global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a) {
+  __shared__ float Qs[NCH * 32 * 32];   // [channel][query], pre-scaled
+  __shared__ float Vs[32 * 32];         // one 32-channel chunk of the key tile: [channel][key ^ channel]
+  const int lane = threadIdx.x, col = lane & 31, half = lane >> 5;
+  const int h = blockIdx.y, b = blockIdx.z, d = a.d, Lq = a.Lq, Lk = a.Lk;
+  const float* qh = a.q + (size_t)b * a.qs + (size_t)h * d * Lq;
+  const float* kh = a.k + (size_t)b * a.ks + (size_t)h * d * Lk;
+  const float* vh = a.v + (size_t)b * a.vs + (size_t)h * d * Lk;
+  float* oh = a.o + (size_t)b * a.os + (size_t)h * d * Lq;
+  const int ql = blockIdx.x * 32 + col;
+  const bool qok = ql < Lq;
+
+  // (a uniform row pointer + one per-lane offset per operand: 32-bit offsets, checked by the launcher)
+  for (int j0 = 0; j0 < NCH * 32; j0 += 2) {
+    const int j = j0 + half;
+    Qs[j * 32 + col] = (qok && j0 < d) ? qh[(size_t)j * Lq + ql] * a.scale : 0.f;
+  }
+  srf_f32x16 acc[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+  float m = SRF_MHA_NEG_INF, den = 0.f;
+  __syncthreads();
+
+  for (int kt = 0; kt < Lk; kt += 32) {
+    const int key = kt + col;
+    const bool kok = key < Lk;
+    const float* kp = kh + (size_t)half * Lk + key;   // (dereferenced under kok only)
+    const float* vp = vh + (size_t)half * Lk + key;
+    // ---- S^T = K^T Q, 16 contraction steps (32 channels) at a time
+    srf_f32x16 st;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) st[r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (c * 32 < d) {
+        float t[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) t[r] = (kok && c * 32 + 2 * r < d) ? kp[(size_t)(c * 32 + 2 * r) * Lk] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          st = __builtin_amdgcn_mfma_f32_32x32x2f32(t[r], Qs[(c * 32 + 2 * r + half) * 32 + col], st, 0, 0, 0);
+      }
+    }
+    // ---- online softmax over this lane's 16 keys and the other half-wavefront's 16
+    float tmax = SRF_MHA_NEG_INF;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int ki = kt + (r & 3) + 8 * (r >> 2) + 4 * half;
+      st[r] = ki < Lk ? st[r] : SRF_MHA_NEG_INF;
+      tmax = fmaxf(tmax, st[r]);
+    }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float mn = fmaxf(m, tmax);       // finite: key kt itself is inside
+    const float alpha = expf(m - mn);      // m = -inf (first tile): 0
+    float psum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      st[r] = expf(st[r] - mn);            // masked keys: exp(-inf) = 0
+      psum += st[r];
+    }
+    psum += __shfl_xor(psum, 32, 64);
+    den = den * alpha + psum;
+    m = mn;
+    // ---- O^T = alpha O^T + V P^T per 32-channel chunk, contracting over the key pair that register s of S^T holds
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (c * 32 < d) {
+        float t[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) t[r] = (kok && c * 32 + 2 * r < d) ? vp[(size_t)(c * 32 + 2 * r) * Lk] : 0.f;
+        __syncthreads();   // (the previous chunk's reads of Vs are done)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int j = 2 * r + half;
+          Vs[j * 32 + (col ^ j)] = t[r];
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[c][r] *= alpha;
+        __syncthreads();   // (Vs is written)
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+          const int kk = (s & 3) + 8 * (s >> 2) + 4 * half;
+          acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[col * 32 + (kk ^ col)], st[s], acc[c], 0, 0, 0);
+        }
+      }
+    }
+  }
+  const float inv = 1.f / den;
+  if (qok) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = c * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (j < d) oh[(size_t)j * Lq + ql] = acc[c][r] * inv;
+      }
+  }
+}
+
+// ---- generic form: one wavefront per query
+#define SRF_MHA_GEN_T 16   // output channels per lane: d <= 64 * 16
+__device__ __forceinline__ float srf_mha_wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float srf_mha_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__global__ __launch_bounds__(256) void srf_mha_generic_kernel(MhaArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int ql = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int h = blockIdx.y, b = blockIdx.z, d = a.d, Lq = a.Lq, Lk = a.Lk;
+  if (ql >= Lq) return;   // (wavefront-uniform; the kernel has no block-wide barrier)
+  const float* qh = a.q + (size_t)b * a.qs + (size_t)h * d * Lq + ql;
+  const float* kh = a.k + (size_t)b * a.ks + (size_t)h * d * Lk;
+  const float* vh = a.v + (size_t)b * a.vs + (size_t)h * d * Lk;
+  float* oh = a.o + (size_t)b * a.os + (size_t)h * d * Lq + ql;
+  float acc[SRF_MHA_GEN_T];
+#pragma unroll
+  for (int t = 0; t < SRF_MHA_GEN_T; ++t) acc[t] = 0.f;
+  float m = SRF_MHA_NEG_INF, den = 0.f;
+  for (int kt = 0; kt < Lk; kt += 64) {
+    const int key = kt + lane;
+    const bool kok = key < Lk;
+    float s = 0.f;
+    if (kok)
+      for (int j = 0; j < d; ++j) s = fmaf(qh[(size_t)j * Lq] * a.scale, kh[(size_t)j * Lk + key], s);
+    s = kok ? s : SRF_MHA_NEG_INF;
+    const float mn = fmaxf(m, srf_mha_wave_max(s));   // finite: key kt itself is inside
+    const float alpha = expf(m - mn);
+    const float p = expf(s - mn);                     // masked keys: 0
+    den = den * alpha + srf_mha_wave_sum(p);
+    m = mn;
+#pragma unroll
+    for (int t = 0; t < SRF_MHA_GEN_T; ++t) acc[t] *= alpha;
+    const int nk = Lk - kt < 64 ? Lk - kt : 64;
+    for (int kk = 0; kk < nk; ++kk) {
+      const float pk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), kk));
+#pragma unroll
+      for (int t = 0; t < SRF_MHA_GEN_T; ++t) {
+        const int j = lane + 64 * t;
+        if (j < d) acc[t] = fmaf(pk, vh[(size_t)j * Lk + kt + kk], acc[t]);
+      }
+    }
+  }
+  const float inv = 1.f / den;
+#pragma unroll
+  for (int t = 0; t < SRF_MHA_GEN_T; ++t) {
+    const int j = lane + 64 * t;
+    if (j < d) oh[(size_t)j * Lq] = acc[t] * inv;
+  }
+}
+
+// the dispatch test: 1 = the MFMA form serves head dimension d under the current kernel mode (mode 1: generic kernels only)
+extern "C" int srf_mha_attention_mfma_supported(int d) {
+  return srf_kernel_mode() != 1 && d % 16 == 0 && d >= 16 && d <= 256;
+}
+
+int srf_mha_attention_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os, int Bt,
+                              int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
+  SRF_CHECK_ARG(q && k && v && o, "srf_mha_attention: null pointer");
+  SRF_CHECK_ARG(Bt > 0 && H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention: bad sizes (Bt %d, H %d, d %d, Lq %d, Lk %d)", Bt,
+                H, d, Lq, Lk);
+  SRF_CHECK_ARG(Bt <= 65535 && H <= 65535, "srf_mha_attention: batch / heads too large (max 65535 each)");
+  SRF_CHECK_ARG((long)H * d * (Lq > Lk ? Lq : Lk) < (1L << 31), "srf_mha_attention: one example exceeds 2^31 elements");
+  const MhaArgs a{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale};
+  if (srf_mha_attention_mfma_supported(d)) {
+    const dim3 grid((Lq + 31) / 32, H, Bt), block(64);
+    if (d <= 32) hipLaunchKernelGGL(srf_mha_mfma_kernel<1>, grid, block, 0, st, a);
+    else if (d <= 64) hipLaunchKernelGGL(srf_mha_mfma_kernel<2>, grid, block, 0, st, a);
+    else if (d <= 128) hipLaunchKernelGGL(srf_mha_mfma_kernel<4>, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(srf_mha_mfma_kernel<8>, grid, block, 0, st, a);
+    SRF_CHECK_LAUNCH("mha_attention_mfma", st);
+    return SRF_OK;
+  }
+  SRF_CHECK_ARG(d <= 64 * SRF_MHA_GEN_T, "srf_mha_attention: head dimension d = %d exceeds the generic kernel's %d", d,
+                64 * SRF_MHA_GEN_T);
+  hipLaunchKernelGGL(srf_mha_generic_kernel, dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a);
+  SRF_CHECK_LAUNCH("mha_attention_generic", st);
+  return SRF_OK;
+}
+
+extern "C" int srf_mha_attention(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq, int Lk,
+                                 float scale, void* stream) {
+  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
+  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
+  return srf_mha_attention_strided(q, k, v, o, sq, sk, sk, sq, Bt, H, d, Lq, Lk, scale, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// x[b, c, l] = GlobLN(a)[b, c, l] + pe[l, c]: the level's lazy norm applied on load, the position table read through a
+// 32 x 32 LDS tile (pe is [max_len, C]: consecutive lanes read consecutive channels, then write consecutive positions)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void srf_posenc_apply_kernel(const float* __restrict__ a, SrfNormDev nrm, const float* __restrict__ pe,
+                                                               float* __restrict__ x, double inv_count, int C, int L) {
+  __shared__ float tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+  const long g = blockIdx.z;
+  float mean = 0.f, rstd = 1.f;
+  if (nrm.sums) srf_finalize_stats(nrm.sums, g, inv_count, mean, rstd);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int l = l0 + ty + 8 * i, c = c0 + tx;
+    tile[ty + 8 * i][tx] = (l < L && c < C) ? pe[(size_t)l * C + c] : 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = c0 + ty + 8 * i, l = l0 + tx;
+    if (c < C && l < L) {
+      float sc = 1.f, sh = 0.f;
+      if (nrm.sums) {
+        sc = nrm.gamma[c] * rstd;
+        sh = nrm.beta[c] - mean * sc;
+      }
+      const size_t at = ((size_t)g * C + c) * L + l;
+      x[at] = fmaf(a[at], sc, sh) + tile[tx][ty + 8 * i];
+    }
+  }
+}
+
+extern "C" int srf_posenc_apply(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L,
+                                int max_len, void* stream) {
+  SRF_CHECK_ARG(a && pe && x && Bt > 0 && C > 0 && L > 0, "srf_posenc_apply: bad arguments");
+  SRF_CHECK_ARG(L <= max_len, "srf_posenc_apply: L = %d positions exceed the table's max_len = %d", L, max_len);
+  SRF_CHECK_ARG(Bt <= 65535 && (C + 31) / 32 <= 65535, "srf_posenc_apply: batch / channels too large");
+  const SrfNormDev nd = srf_norm_dev(norm);
+  if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_posenc_apply: norm without gamma/beta");
+  SRF_CHECK_ALIGNED16("srf_posenc_apply", {"norm.sums", nd.sums});
+  hipLaunchKernelGGL(srf_posenc_apply_kernel, dim3((L + 31) / 32, (C + 31) / 32, Bt), dim3(256), 0, (hipStream_t)stream, a, nd, pe, x,
+                     1.0 / ((double)C * (double)L), C, L);
+  SRF_CHECK_LAUNCH("posenc_apply", stream);
+  return SRF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// z = norm_f(f) + norm_y(y) (each a GlobLN with optional PReLU, statistics from its own slot), out_sums += {sum, sumsq} of z.
+// The transformer layer's closing step: ffn's GlobLN + PReLU and out_mha_norm applied on load, the sum's statistics for out_norm.
+// One block per (row = (g, c), chunk of 1024 positions), as srf_gln_apply.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void srf_gln_apply2_add_kernel(const float* __restrict__ f, SrfNormDev nf, const float* __restrict__ y,
+                                                                 SrfNormDev ny, float* __restrict__ z, double* __restrict__ out_sums,
+                                                                 double inv_count, int channels, int length, int chunks) {
+  __shared__ double red[8];
+  const long row = blockIdx.x / chunks;
+  const int chunk = blockIdx.x - row * chunks;
+  const int c = (int)(row % channels);
+  const long g = row / channels;
+  float mf, rf, my, ry;
+  srf_finalize_stats(nf.sums, g, inv_count, mf, rf);
+  srf_finalize_stats(ny.sums, g, inv_count, my, ry);
+  const float scf = nf.gamma[c] * rf, shf = nf.beta[c] - mf * scf;
+  const float scy = ny.gamma[c] * ry, shy = ny.beta[c] - my * scy;
+  const bool actf = nf.prelu != nullptr, acty = ny.prelu != nullptr;
+  const float slf = actf ? nf.prelu[0] : 1.f, sly = acty ? ny.prelu[0] : 1.f;
+  const size_t base = (size_t)row * length;
+  double ds = 0.0, dq = 0.0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int l = chunk * 1024 + u * 256 + threadIdx.x;
+    if (l < length) {
+      float vf = fmaf(f[base + l], scf, shf);
+      if (actf) vf = srf_prelu(vf, slf);
+      float vy = fmaf(y[base + l], scy, shy);
+      if (acty) vy = srf_prelu(vy, sly);
+      const float v = vf + vy;
+      z[base + l] = v;
+      ds += (double)v;
+      dq += (double)v * (double)v;
+    }
+  }
+  if (out_sums) srf_block_stats_atomic<4>(ds, dq, srf_stat_slot(out_sums, g, blockIdx.x), red);
+}
+
+extern "C" int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z,
+                                  double* out_sums, int groups, int channels, int length, void* stream) {
+  SRF_CHECK_ARG(f && y && z && fnorm && ynorm && groups > 0 && channels > 0 && length > 0, "srf_gln_apply2_add: bad arguments");
+  SRF_CHECK_ARG(fnorm->sums && fnorm->gamma && fnorm->beta && ynorm->sums && ynorm->gamma && ynorm->beta,
+                "srf_gln_apply2_add: both norms need statistics, gamma and beta");
+  SRF_CHECK_ALIGNED16("srf_gln_apply2_add", {"fnorm.sums", fnorm->sums}, {"ynorm.sums", ynorm->sums});
+  const int chunks = (length + 1023) / 1024;
+  const long blocks = (long)groups * channels * chunks;
+  SRF_CHECK_ARG(blocks < (1L << 31), "srf_gln_apply2_add: tensor too large");
+  hipLaunchKernelGGL(srf_gln_apply2_add_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, f, srf_norm_dev(fnorm), y,
+                     srf_norm_dev(ynorm), z, out_sums, 1.0 / ((double)channels * (double)length), channels, length, chunks);
+  SRF_CHECK_LAUNCH("gln_apply2_add", stream);
+  return SRF_OK;
+}

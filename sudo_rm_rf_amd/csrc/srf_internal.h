@@ -40,6 +40,20 @@ int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, in
 // per-row {mean, unbiased std} over lens.n[r] samples of a padded [rows, T] tensor; `lens` already checked against T
 int srf_wav_stats_ragged_launch(const float* wav, const SrfFrames& lens, float* stats, int rows, int T, hipStream_t st);
 
+// ---- srf_api.hip: what the attentive model's walk (srf_attentive.hip) shares with forward_walk
+int srf_zero_launch(void* p, size_t bytes, hipStream_t st);
+// post_stats / post_wav / post_mc: the callers' rescale (+ mixture consistency) folded into the overlap-add (srf_separate)
+int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T, float* scratch,
+                     const float* post_stats, const float* post_wav, int post_mc, void* stream, const float* in_prelu = nullptr);
+
+// ---- srf_attention.hip / srf_attentive.hip
+// srf_mha_attention with an example stride per operand (q, k, v as thirds of one [Bt, 3 H d, L] projection)
+int srf_mha_attention_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os, int Bt,
+                              int H, int d, int Lq, int Lk, float scale, hipStream_t st);
+struct srf_plan;
+int srf_attentive_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
+                          const float* wav_stats, int mixture_consistency, void* stream);
+
 // ---- srf_encoder.hip
 int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,
                      const float* in_stats, void* stream);

@@ -23,7 +23,14 @@ struct srf_plan {
   // and the workspace copies of the weights they and skipinit_gain are folded into
   std::vector<float> alpha, beta;
   size_t off_fold_res, off_fold_proj, off_merged;
+  // attentive variant (SRF_VARIANT_ATTENTIVE): the transformer layer's heads, head dimension and positions (L >> (D - 1)), its
+  // activations x | qkv | o | y | f and the concatenated [3 H d, C] Q/K/V weights + biases of every block
+  int att_heads = 0, att_dims = 0, att_len = 0;
+  size_t off_att_x = 0, off_att_qkv = 0, off_att_o = 0, off_att_y = 0, off_att_f = 0, off_att_wqkv = 0;
 };
+// attentive blocks: the Improved block's tensors, then these (state_dict order of TransformerLayer)
+enum { SRF_PA_Q = 0, SRF_PA_K = 2, SRF_PA_V = 4, SRF_PA_O = 6, SRF_PA_OUT_NORM = 8, SRF_PA_MHA_NORM = 10, SRF_PA_FFN = 12,
+       SRF_PA_FFN_NORM = 14, SRF_PA_FFN_PRELU = 16, SRF_PA_PE = 17, SRF_PA_COUNT = 18 };
 
 // ---- named views of the parameter table and of the GlobLN statistic slots (Improved / GroupComm layout; the causal variant
 // has its own).  state_dict order:

@@ -224,6 +224,10 @@ static int train_check(const srf_plan* p, const char* who) {
 // The causal variant (CausalSuDORMRF) has an inference forward only: every training entry point refuses its plans before
 // anything is launched; the two size queries return 0 with the same message in srf_last_error().
 static bool causal_refused(const srf_plan* p, const char* who) {
+  if (p && p->cfg.variant == SRF_VARIANT_ATTENTIVE) {
+    srf_set_error("%s: not available for the attentive variant (attentive SuDORMRF v2 has an inference forward only)", who);
+    return true;
+  }
   if (!p || p->cfg.variant != SRF_VARIANT_CAUSAL) return false;
   srf_set_error("%s: not available for the causal variant (CausalSuDORMRF has an inference forward only)", who);
   return true;

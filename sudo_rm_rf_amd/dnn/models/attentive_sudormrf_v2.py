@@ -1,0 +1,304 @@
+"""Attentive SuDoRM-RF (v2) on MI355X: the reference's module surface over hand-written HIP kernels.
+
+Mirrors the reference's sudo_rm_rf/dnn/models/attentive_sudormrf_v2.py: the same class names (whole-module pickles resolve),
+constructor signatures and defaults, public attributes, sub-module tree -- therefore the same ``state_dict()`` keys, shapes
+and order, the ``pos_enc.pe`` buffers included -- and, the containers being created in the same order with the same torch
+initialisers, the same weights for the same ``torch.manual_seed``.  The torch sub-modules are PARAMETER CONTAINERS ONLY:
+``SuDORMRF.forward`` hands the parameter pointers to one ``srf_forward`` call on a plan of ``srf_attentive_plan_create``
+(include/sudormrf_hip.h) and no ATen compute op runs.  Inference only; there is no CPU fallback.
+
+Like the reference, ``SuDORMRF`` builds every block with 4 heads of 256 channels WHATEVER ``n_heads`` / ``att_dims`` say
+(the arguments are accepted and ignored there); ``AttentiveUConvBlock`` itself honours them.  The reference's ``MHANormLayer``
+is dead code and has no counterpart here.
+"""
+import math
+
+import torch
+import torch.nn as nn
+
+from ... import _lib, attention, ops
+from ...engine import ModelEngine, _weights
+from .improved_sudormrf import (_LayerNorm, GlobLN, ConvNormAct, NormAct, DilatedConvNorm, _hip_only)  # noqa: F401
+
+
+class ConvNorm(nn.Module):
+    """Conv1d + GlobLN (parameter container; the model does not use it)."""
+
+    def __init__(self, nIn, nOut, kSize, stride=1, groups=1):
+        super().__init__()
+        padding = int((kSize - 1) / 2)
+        self.conv = nn.Conv1d(nIn, nOut, kSize, stride=stride, padding=padding, bias=True, groups=groups)
+        self.norm = GlobLN(nOut)
+
+    def forward(self, input):
+        c = self.conv
+        x = _hip_only(input)
+        sums = ops.new_sums(x.shape[0], x.device)
+        y = ops.conv1d(x, c.weight.detach(), c.bias.detach(), c.stride[0], c.padding[0], c.dilation[0], c.groups, out_sums=sums)
+        return ops.gln_apply(y, sums, self.norm.gamma.detach(), self.norm.beta.detach())
+
+
+class DilatedConv(nn.Module):
+    """A plain (dilated) Conv1d (parameter container; the model does not use it)."""
+
+    def __init__(self, nIn, nOut, kSize, stride=1, d=1, groups=1):
+        super().__init__()
+        self.conv = nn.Conv1d(nIn, nOut, kSize, stride=stride, dilation=d, padding=((kSize - 1) // 2) * d, groups=groups)
+
+    def forward(self, input):
+        c = self.conv
+        return ops.conv1d(_hip_only(input), c.weight.detach(), c.bias.detach(), c.stride[0], c.padding[0], c.dilation[0], c.groups)
+
+
+class PositionalEncoding(nn.Module):
+    """The sinusoid table as a registered buffer ``pe`` [1, max_len, d_model]; forward adds its first rows to [batch, len, d_model].
+    The kernels READ the buffer (a checkpoint's values are the values used)."""
+
+    def __init__(self, d_model, dropout=0.1, max_len=3200):
+        super().__init__()
+        self.dropout = nn.Dropout(p=dropout)
+        position = torch.arange(0, max_len, dtype=torch.float).unsqueeze(1)
+        div_term = torch.exp(torch.arange(0, d_model, 2).float() * (-math.log(10000.0) / d_model))
+        pe = torch.zeros(max_len, d_model)
+        pe[:, 0::2] = torch.sin(position * div_term)
+        pe[:, 1::2] = torch.cos(position * div_term)
+        self.register_buffer('pe', pe.unsqueeze(0))
+
+    def forward(self, x):
+        _no_random_dropout(self, self.dropout.p)
+        x = _hip_only(x)                                        # [batch, len, d_model]
+        return attention.posenc_apply(x.transpose(1, 2).contiguous(), self.pe.detach()).transpose(1, 2).contiguous()
+
+
+def _no_random_dropout(module, p):
+    if module.training and p > 0:
+        raise RuntimeError("attentive SuDoRM-RF on HIP is an inference path: in train() mode the reference's dropout (p = %g) is "
+                           "random; call model.eval()" % p)
+
+
+class MHAttentionLayer(nn.Module):
+    """Q / K / V / O projections around softmax attention; forward(Q, K, V) takes [batch, len, emb_dim] like the reference."""
+
+    def __init__(self, emb_dim, d_model, n_heads, dropout=0.0):
+        super().__init__()
+        self.dropout = nn.Dropout(dropout)
+        self.Q_proj = nn.Linear(emb_dim, d_model * n_heads)
+        self.K_proj = nn.Linear(emb_dim, d_model * n_heads)
+        self.V_proj = nn.Linear(emb_dim, d_model * n_heads)
+        self.O_proj = nn.Linear(d_model * n_heads, emb_dim)
+        self.n_heads = n_heads
+        self.d_model = d_model
+        self.q_normalizer = 1. / math.sqrt(d_model)
+
+    def forward(self, Q, K, V):
+        _no_random_dropout(self, self.dropout.p)
+        t = lambda x: _hip_only(x).transpose(1, 2).contiguous()
+        lin = lambda m, x: ops.pw_conv(x, m.weight.detach(), m.bias.detach())
+        o = attention.mha_attention(lin(self.Q_proj, t(Q)), lin(self.K_proj, t(K)), lin(self.V_proj, t(V)), self.n_heads,
+                                    self.q_normalizer)
+        return lin(self.O_proj, o).transpose(1, 2).contiguous()
+
+
+class TransformerLayer(nn.Module):
+    """[batch, channels, len] -> the same: position table, attention + residual, GlobLN, 1x1 FFN + residual, GlobLN."""
+
+    def __init__(self, emb_dim, d_model, n_heads, dropout=0.1, max_len=5000):
+        super().__init__()
+        self.mha = MHAttentionLayer(emb_dim, d_model, n_heads, dropout=0.0)
+        self.out_norm = GlobLN(emb_dim)
+        self.out_mha_norm = GlobLN(emb_dim)
+        self.ffn = ConvNormAct(emb_dim, emb_dim, 1, stride=1, groups=1)
+        self.pos_enc = PositionalEncoding(d_model=emb_dim, dropout=dropout, max_len=max_len)
+
+    def forward(self, x, in_sums=None, in_gamma=None, in_beta=None):
+        """The kernel sequence srf_forward runs on the deepest level (stand-alone use / unit tests).  in_sums / in_gamma /
+        in_beta: a GlobLN to apply to x on load (the level's lazy norm); returns the layer's output, out_norm applied."""
+        _no_random_dropout(self, self.pos_enc.dropout.p)
+        x = _hip_only(x)
+        Bt, dev = x.shape[0], x.device
+        d = lambda p: p.detach()
+        m = self.mha
+        xp = attention.posenc_apply(x, d(self.pos_enc.pe), in_sums, in_gamma, in_beta)
+        wqkv = torch.cat([d(m.Q_proj.weight), d(m.K_proj.weight), d(m.V_proj.weight)], 0).contiguous()
+        bqkv = torch.cat([d(m.Q_proj.bias), d(m.K_proj.bias), d(m.V_proj.bias)], 0).contiguous()
+        qkv = ops.pw_conv(xp, wqkv, bqkv)
+        hd = m.n_heads * m.d_model
+        q, k, v = (qkv[:, i * hd:(i + 1) * hd].contiguous() for i in range(3))
+        o = attention.mha_attention(q, k, v, m.n_heads, m.q_normalizer)
+        s_mha, s_ffn, s_out = (ops.new_sums(Bt, dev) for _ in range(3))
+        y = ops.pw_conv(o, d(m.O_proj.weight), d(m.O_proj.bias), residual=xp, out_sums=s_mha)
+        g, b = d(self.out_mha_norm.gamma), d(self.out_mha_norm.beta)
+        f = ops.pw_conv(y, d(self.ffn.conv.weight), d(self.ffn.conv.bias), in_sums=s_mha, in_gamma=g, in_beta=b, out_sums=s_ffn)
+        z = attention.gln_apply2_add(f, s_ffn, d(self.ffn.norm.gamma), d(self.ffn.norm.beta), d(self.ffn.act.weight), y, s_mha, g, b,
+                                     out_sums=s_out)
+        return ops.gln_apply(z, s_out, d(self.out_norm.gamma), d(self.out_norm.beta))
+
+
+class AttentiveUConvBlock(nn.Module):
+    """U-ConvBlock whose deepest level goes through a TransformerLayer before the upsample-and-add."""
+
+    def __init__(self, out_channels=128, in_channels=512, upsampling_depth=4, n_heads=4, att_dims=256, att_dropout=0.1):
+        super().__init__()
+        self.proj_1x1 = ConvNormAct(out_channels, in_channels, 1, stride=1, groups=1)
+        self.depth = upsampling_depth
+        self.spp_dw = nn.ModuleList()
+        self.spp_dw.append(DilatedConvNorm(in_channels, in_channels, kSize=5, stride=1, groups=in_channels, d=1))
+        for _ in range(1, upsampling_depth):
+            self.spp_dw.append(DilatedConvNorm(in_channels, in_channels, kSize=5, stride=2, groups=in_channels, d=1))
+        if upsampling_depth > 1:
+            self.upsampler = torch.nn.Upsample(scale_factor=2)
+        self.final_norm = NormAct(in_channels)
+        self.res_conv = nn.Conv1d(in_channels, out_channels, 1)
+        self.attention = TransformerLayer(in_channels, att_dims, n_heads, dropout=att_dropout, max_len=5000)
+
+    def forward(self, x):
+        """The kernel sequence srf_forward runs for one block (stand-alone use / unit tests)."""
+        D = self.depth
+        if D < 2:
+            raise RuntimeError("AttentiveUConvBlock: upsampling_depth = %d; the HIP path needs at least 2 levels" % D)
+        x = _hip_only(x)
+        Bt, _, L = x.shape
+        if L % (1 << (D - 1)):
+            raise RuntimeError("time length %d must be divisible by 2^(depth-1)" % L)
+        dev = x.device
+        d = lambda p: p.detach()
+        s_in = ops.new_sums(Bt, dev)
+        src = ops.pw_conv(x, d(self.proj_1x1.conv.weight), d(self.proj_1x1.conv.bias), out_sums=s_in)
+        g_in, b_in, a_in = d(self.proj_1x1.norm.gamma), d(self.proj_1x1.norm.beta), d(self.proj_1x1.act.weight)
+        levels, sums = [], []
+        for k in range(D):
+            m = self.spp_dw[k]
+            s_k = ops.new_sums(Bt, dev)
+            src = ops.dwconv5(src, d(m.conv.weight), d(m.conv.bias), 1 if k == 0 else 2, in_sums=s_in, in_gamma=g_in, in_beta=b_in,
+                              in_prelu=a_in, out_sums=s_k)
+            levels.append(src)
+            sums.append(s_k)
+            s_in, g_in, b_in, a_in = s_k, d(m.norm.gamma), d(m.norm.beta), None
+        z = self.attention(levels[-1], s_in, g_in, b_in)          # (out_norm already applied: merged as a plain level below)
+        top = z
+        for k in range(D - 2, -1, -1):
+            m = self.spp_dw[k]
+            top = ops.gln_apply(levels[k], sums[k], d(m.norm.gamma), d(m.norm.beta)) + top.repeat_interleave(2, dim=-1)
+        s_m = ops.gln_stats(top.contiguous(), Bt)
+        return ops.pw_conv(top.contiguous(), d(self.res_conv.weight), d(self.res_conv.bias), in_sums=s_m,
+                           in_gamma=d(self.final_norm.norm.gamma), in_beta=d(self.final_norm.norm.beta),
+                           in_prelu=d(self.final_norm.act.weight), residual=x)
+
+
+class SuDORMRF(nn.Module):
+    """Drop-in for the reference's attentive ``SuDORMRF``: forward([batch, 1, time]) -> [batch, num_sources, time]."""
+
+    def __init__(self,
+                 out_channels=128,
+                 in_channels=512,
+                 num_blocks=16,
+                 upsampling_depth=4,
+                 enc_kernel_size=21,
+                 enc_num_basis=512,
+                 n_heads=4,
+                 att_dims=256,
+                 att_dropout=0.1,
+                 num_sources=2):
+        super().__init__()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.num_blocks = num_blocks
+        self.upsampling_depth = upsampling_depth
+        self.enc_kernel_size = enc_kernel_size
+        self.enc_num_basis = enc_num_basis
+        self.num_sources = num_sources
+        self.lcm = abs(self.enc_kernel_size // 2 * 2 ** self.upsampling_depth) // math.gcd(
+            self.enc_kernel_size // 2, 2 ** self.upsampling_depth)
+
+        self.encoder = nn.Conv1d(in_channels=1, out_channels=enc_num_basis, kernel_size=enc_kernel_size,
+                                 stride=enc_kernel_size // 2, padding=enc_kernel_size // 2, bias=False)
+        torch.nn.init.xavier_uniform_(self.encoder.weight)
+        self.ln = GlobLN(enc_num_basis)
+        self.bottleneck = nn.Conv1d(in_channels=enc_num_basis, out_channels=out_channels, kernel_size=1)
+        # (as the reference: 4 heads of 256 channels and dropout 0.1 in every block, whatever the arguments say)
+        self.sm = nn.Sequential(*[
+            AttentiveUConvBlock(out_channels=out_channels, in_channels=in_channels, upsampling_depth=upsampling_depth,
+                                n_heads=4, att_dims=256, att_dropout=0.1)
+            for _ in range(num_blocks)])
+        mask_conv = nn.Conv1d(out_channels, num_sources * enc_num_basis, 1)
+        self.mask_net = nn.Sequential(nn.PReLU(), mask_conv)
+        self.decoder = nn.ConvTranspose1d(
+            in_channels=enc_num_basis * num_sources, out_channels=num_sources,
+            output_padding=(enc_kernel_size // 2) - 1, kernel_size=enc_kernel_size,
+            stride=enc_kernel_size // 2, padding=enc_kernel_size // 2, groups=1, bias=False)
+        torch.nn.init.xavier_uniform_(self.decoder.weight)
+        self.mask_nl_class = nn.ReLU()
+
+    # -- engine plumbing (kept out of state_dict and rebuilt lazily, e.g. after unpickling) --------
+    def _config_tuple(self):
+        mha = self.sm[0].attention.mha
+        return ("attentive", 1, self.out_channels, self.in_channels, self.num_blocks, self.upsampling_depth,
+                self.enc_kernel_size, self.enc_num_basis, self.num_sources, 1, (mha.n_heads, mha.d_model))
+
+    def _engine(self):
+        eng = self.__dict__.get("_srf_engine")
+        if eng is None or eng.cfg_tuple != self._config_tuple():
+            eng = ModelEngine(self._config_tuple())
+            eng.multi_stream = False          # single stream only: the sub-batch split is not extended to this variant
+            self.__dict__["_srf_engine"] = eng
+        return eng
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state.pop("_srf_engine", None)
+        return state
+
+    def _check_inference(self, weights):
+        dropout = max([self.sm[0].attention.pos_enc.dropout.p] + [b.attention.pos_enc.dropout.p for b in self.sm])
+        _no_random_dropout(self, dropout)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in weights):
+            raise RuntimeError("attentive SuDoRM-RF on HIP has an inference forward only (no backward kernels): run it under "
+                               "torch.no_grad()")
+
+    def forward(self, input_wav):
+        """[batch, 1, time] float -> [batch, num_sources, time] float32: one srf_forward call on the caller's stream."""
+        if not isinstance(input_wav, torch.Tensor):
+            raise TypeError("input must be a torch.Tensor")
+        if input_wav.dim() != 3 or input_wav.shape[1] != 1:
+            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(input_wav.shape),))
+        weights = _weights(self)
+        self._check_inference(weights)
+        if input_wav.device.type != "cuda":
+            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
+                                "fallback (use the reference implementation for CPU inference)." % input_wav.device)
+        params = [p.detach() for p in weights]
+        for p in params:
+            if p.device != input_wav.device or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.SrfError("all parameters and buffers must be contiguous float32 on %s" % input_wav.device)
+        x = input_wav.detach().to(torch.float32).contiguous()
+        batch, _, T = x.shape
+        if batch == 0 or T == 0:
+            raise RuntimeError("empty input %s" % (tuple(input_wav.shape),))
+        eng = self._engine()
+        with torch.cuda.device(x.device), eng._run_lock(x.device):
+            plan = eng.plan_for(batch, T, x.device)
+            if plan.num_params != len(params):
+                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
+            out = torch.empty((batch, self.num_sources, T), dtype=torch.float32, device=x.device)
+            plan.forward(eng._param_table(params, x.device), x, out)
+            eng.last_plan = plan
+        return out
+
+    def forward_ragged(self, input_wav, lengths):
+        raise NotImplementedError("the attentive model has no ragged kernels: run the utterances one by one "
+                                  "(pipeline.separate_list does)")
+
+    def pad_to_appropriate_length(self, x):
+        """Kept for API parity: up to a multiple of lcm(K // 2, 2^D), only when the length is not one already.  The HIP path
+        folds the padding into its bounds checks and never materialises the padded tensor."""
+        values_to_pad = int(x.shape[-1]) % self.lcm
+        if values_to_pad:
+            padded = torch.zeros(list(x.shape[:-1]) + [x.shape[-1] + self.lcm - values_to_pad], dtype=torch.float32,
+                                 device=x.device)
+            padded[..., :x.shape[-1]] = x
+            return padded
+        return x
+
+    @staticmethod
+    def remove_trailing_zeros(padded_x, initial_x):
+        return padded_x[..., :initial_x.shape[-1]]

@@ -51,9 +51,14 @@ class Plan:
         # (the causal model appends its blocks' (alpha, beta) attributes to the 10 constructor fields)
         cfg = _config_struct(*cfg_tuple[:10])
         handle = C.c_void_p()
-        _lib.check(lib.srf_plan_create(C.byref(cfg), batch, T, C.byref(handle)), "srf_plan_create")
+        attentive = cfg_tuple[0] == "attentive"      # (its 11th field: the blocks' (n_heads, att_dims))
+        if attentive:
+            _lib.check(lib.srf_attentive_plan_create(C.byref(cfg), cfg_tuple[10][0], cfg_tuple[10][1], batch, T, C.byref(handle)),
+                       "srf_attentive_plan_create")
+        else:
+            _lib.check(lib.srf_plan_create(C.byref(cfg), batch, T, C.byref(handle)), "srf_plan_create")
         self.handle = handle
-        if len(cfg_tuple) > 10:
+        if len(cfg_tuple) > 10 and not attentive:
             scales = cfg_tuple[10]
             alpha = (C.c_float * len(scales))(*[a for a, _ in scales])
             beta = (C.c_float * len(scales))(*[b for _, b in scales])
