@@ -45,6 +45,18 @@ CASES = {
     "attn_default_u2": (DEFAULT_U2, 4, 10400, 203, 203),
     "attn_main_u2": (MAIN_U2, 2, 32079, 204, 204),
 }
+# Deepest levels of Ld % 4 == 0 positions: only there do the transformer layer's three GEMMs (Q/K/V, O_proj, ffn: 1x1 convs of
+# length Ld) leave the scalar kernel -- every case above but the 16-channel pickle has Ld % 4 != 0.  No goldens: the yardstick is
+# tests/attentive_ref.py in fp64.
+#   TINY (D = 3: Ld = Tp / 40) on the weights of attn_tiny: (T, batch, Ld, input seed) -- one position group | a multiple of 4
+#   that is none of 8 (Tp = 1120) | 4 short of a 128-column tile | exactly one | one plus a 4-column tile | batch 1
+TINY_GRID = ((160, 2, 4, 240), (1100, 2, 28, 241), (4960, 2, 124, 242), (5120, 2, 128, 243), (5280, 2, 132, 244),
+             (1100, 1, 28, 245))
+#   WIDE: the default model's channel counts (C = 512, 4 heads of 256) at D = 2, so that Ld = Tp / 20 and a batch that gives the
+#   layer's GEMMs as many 256 x 128 tiles as the chip has CUs stays small: T = 2640 -> L = 264, Ld = 132 = 128 + 4
+WIDE = _cfg(128, 512, 2, 2, 128, 4, 256, 2)
+WIDE_T, WIDE_LD, WIDE_WSEED, WIDE_INPUT_SEED = 2640, 132, 206, 206
+GAINS = (1.0, 0.5, 2.0, 1.5, 0.8)          # per-example gains of the distinct-example batches, cycled
 DIGEST_CONFIGS = {"tiny": TINY, "pickle": PICKLE}
 PICKLE_SEED, PICKLE_BATCH, PICKLE_T, PICKLE_INPUT_SEED = 7, 2, 777, 205
 
@@ -128,6 +140,12 @@ def make_mixture(batch, T, seed):
     if T > 1:
         x = (x - x.mean(-1, keepdims=True)) / (x.std(-1, ddof=1, keepdims=True) + 1e-9)
     return np.ascontiguousarray(x, dtype=np.float32)
+
+
+def make_distinct(batch, T, seed):
+    """make_mixture with example b scaled by GAINS[b % 5]: rows that differ in level as well as in content."""
+    gains = np.array([GAINS[b % len(GAINS)] for b in range(batch)], dtype=np.float32)
+    return make_mixture(batch, T, seed) * gains[:, None, None]
 
 
 def make_input(name):

@@ -206,3 +206,53 @@ def test_restatement_agrees_with_the_reference(restated, name):
     if name == "attn_tiny":
         a, z = taps[0]
         assert np.abs(a.numpy() - gold["att_in"]).max() <= 1e-4 and np.abs(z.numpy() - gold["att_out"]).max() <= 1e-4
+
+
+# ---- the Ld % 4 == 0 cases of tests/test_gpu_attentive.py and tests/test_gpu_ops.py ---------------------------------------
+def test_the_named_cases_sit_where_the_gpu_tests_need_them():
+    """The deepest-level length decides which GEMM kernel the transformer layer runs (an MFMA one only for Ld % 4 == 0): a change
+    to the padding rule must not quietly move a case on or off that grid."""
+    named = [(af.TINY, 1001, 26), (af.TINY, 50, 2), (af.DEFAULT_U2, 10400, 130), (af.MAIN_U2, 32079, 201), (af.PICKLE, 777, 20),
+             (af.WIDE, af.WIDE_T, af.WIDE_LD)] + [(af.TINY, T, Ld) for T, _, Ld, _ in af.TINY_GRID]
+    assert [af.deepest_length(cfg, T) for cfg, T, _ in named] == [Ld for _, _, Ld in named]
+    assert [Ld for _, _, Ld in named[:5]] == [26, 2, 130, 201, 20] and af.WIDE_LD == 132
+    assert [Ld for _, _, Ld, _ in af.TINY_GRID] == [4, 28, 124, 128, 132, 28]
+    # the goldens' cases keep off the grid (the pickle apart), the new ones are on it
+    assert [Ld % 4 == 0 for _, _, Ld in named] == [False] * 4 + [True] * (2 + len(af.TINY_GRID))
+    for (cfg, _, T, _, _), Ld in zip((af.CASES[n] for n in ("attn_tiny", "attn_tiny_short", "attn_default_u2", "attn_main_u2")),
+                                     (26, 2, 130, 201)):
+        assert af.deepest_length(cfg, T) == Ld
+    assert _plan(af.WIDE, 1, af.WIDE_T).frames == 2 * af.WIDE_LD
+
+
+def test_restatement_in_fp32_leaves_headroom_under_the_gpu_bar():
+    """attentive_ref in fp32 against itself in fp64 on the TINY T = 1100 case: a tenth of the 1e-4 the GPU is held to."""
+    T, batch, _, iseed = af.TINY_GRID[1]
+    assert (T, batch) == (1100, 2)
+    sd, wav = af.make_state_dict(af.TINY, af.CASES["attn_tiny"][3]), af.make_mixture(batch, T, iseed)
+    y64 = ar.forward(af.TINY, sd, wav, torch.float64)
+    y32 = ar.forward(af.TINY, sd, wav, torch.float32)
+    err = float((y32.double() - y64).abs().max())
+    print("TINY T = 1100: max|attentive_ref fp32 - fp64| = %.3e (max|ref| %.3f), bar %.1e" % (err, float(y64.abs().max()), 1e-4 / 10))
+    assert y32.dtype == torch.float32 and err <= 1e-4 / 10
+
+
+def test_wide_reference_for_64_examples_is_affordable():
+    """The GPU test of the WIDE model computes this once per module: under a minute on at most 16 threads."""
+    import time
+    sd = af.make_state_dict(af.WIDE, af.WIDE_WSEED)
+    wav = af.make_distinct(64, af.WIDE_T, af.WIDE_INPUT_SEED)
+    before = torch.get_num_threads()
+    torch.set_num_threads(min(16, before))
+    try:
+        t0 = time.perf_counter()
+        y = ar.forward(af.WIDE, sd, wav, torch.float64)
+        dt = time.perf_counter() - t0
+    finally:
+        torch.set_num_threads(before)
+    peak = y.abs().amax(dim=(1, 2))
+    print("WIDE fp64 reference, 64 examples: %.1f s on %d threads; max|ref| per example %.3f .. %.3f"
+          % (dt, min(16, before), float(peak.min()), float(peak.max())))
+    assert y.shape == (64, 2, af.WIDE_T) and bool(torch.isfinite(y).all())
+    assert float(peak.max()) >= 0.1          # (the outputs are of a size at which 1e-4 absolute means something)
+    assert dt < 60.0

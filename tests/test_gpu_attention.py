@@ -18,8 +18,12 @@ DEV = "cuda:0"
 
 # (Bt, H, d, Lq, Lk): smallest MFMA shape | fewer keys than a tile | one key | two past a 128 boundary | the __main__ shapes
 # (201 positions, and the issue's 202) | several key tiles + a remainder | generic form, odd rows | Lq != Lk
+# | head dimensions that are no multiple of 32, so that a 32-channel chunk of the MFMA form is half full or skipped (with
+# d in {16, 32, 64, 256} "c * 32 < d" never prunes a chunk and "c * 32 + 2 r < d" never goes false past the first):
+# NCH = 2, second chunk half full | NCH = 4, third half full, fourth skipped | NCH = 8, fifth half full, three skipped
 SHAPES = [(2, 3, 16, 26, 26), (3, 1, 64, 2, 2), (1, 4, 256, 1, 1), (2, 4, 256, 130, 130), (1, 3, 256, 202, 202),
-          (1, 3, 256, 201, 201), (1, 2, 32, 321, 321), (2, 3, 24, 25, 25), (2, 1, 64, 70, 45)]
+          (1, 3, 256, 201, 201), (1, 2, 32, 321, 321), (2, 3, 24, 25, 25), (2, 1, 64, 70, 45),
+          (1, 2, 48, 33, 33), (1, 1, 80, 5, 37), (1, 1, 144, 40, 70)]
 LARGE = (2, 4, 256, 130, 130)          # run once more with logits of +-80
 
 
@@ -121,7 +125,8 @@ def arena():
     return pl.Arena(DEV, 64 << 20)
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 16, 26, 26), (2, 4, 256, 130, 130), (2, 3, 24, 25, 25), (2, 1, 64, 70, 45)], ids=_id)
+@pytest.mark.parametrize("shape", [(2, 3, 16, 26, 26), (2, 4, 256, 130, 130), (2, 3, 24, 25, 25), (2, 1, 64, 70, 45),
+                                   (1, 2, 48, 33, 33)], ids=_id)
 @pytest.mark.parametrize("shifts", [(0, 0, 0, 0), (1, 2, 3, 1), (3, 1, 2, 3)], ids=lambda s: "shift%d%d%d%d" % s)
 def test_attention_off_the_16_byte_grid_with_guard_bands(arena, shape, shifts):
     from sudo_rm_rf_amd import attention

@@ -205,6 +205,132 @@ def test_pw_conv_persistent_variants(Bt, Cin, Cout, L, pro):
     assert torch.equal(outs["packed 256x128"], outs["dispatched"])
 
 
+# ---- the attentive transformer layer's three GEMM forms (srf_attentive.hip), at deepest-level lengths Ld % 4 == 0 ----------
+# (a) O_proj: no prologue, residual AND statistics -- srf_x3p_supported refuses that pair, so the 256 x 128 launch is the x3w form
+#     under either setting of GEMM_256_SWAP_FORMS; (b) ffn: GlobLN on load, statistics; (c) Q/K/V as one conv: nothing.
+# Operands scaled as in test_pw_conv_persistent_variants (w by Cin ** -0.5): neither the outputs nor the random-sign rounding
+# error grow with K, so its bars hold at K = 1024 unchanged.
+LAYER_FORMS = {"O_proj": (0, True, True), "ffn": (1, False, True), "qkv": (0, False, False)}    # prologue, residual, statistics
+MFMA_GEMMS = ("pw_conv_bf16x3", "pw_conv_x3w<", "pw_conv_x3p<", "pw_conv_mfma")
+
+
+def _layer_form_case(form, Bt, Cin, Cout, L):
+    """(x, w, bias, keyword operands, fp64 reference, whether statistics are taken) of one form at one shape"""
+    pro, with_res, with_sums = LAYER_FORMS[form]
+    x = dev32(rnd(Bt, Cin, L, seed=40, scale=1.3, shift=0.2))
+    w, bias = dev32(rnd(Cout, Cin, 1, seed=41, scale=Cin ** -0.5)), dev32(rnd(Cout, seed=42, scale=0.2))
+    kw, xin = {}, x.double().cpu()
+    if pro == 1:
+        gamma, beta = rnd(Cin, seed=44, scale=0.3, shift=1.0), rnd(Cin, seed=45, scale=0.3)
+        kw.update(in_sums=sums64(xin).to(DEV), in_gamma=dev32(gamma), in_beta=dev32(beta))
+        xin = gln64(xin, gamma, beta)
+    want = F.conv1d(xin, w.double().cpu(), bias.double().cpu())
+    if with_res:
+        kw.update(residual=dev32(rnd(Bt, Cout, L, seed=43)))
+        want = want + kw["residual"].double().cpu()
+    return x, w, bias, kw, want, with_sums
+
+
+def _run_layer_form(x, w, bias, kw, with_sums, packed, flags=0):
+    from sudo_rm_rf_amd import ops
+    sums = ops.new_sums(x.shape[0], DEV) if with_sums else None
+    with ops.debug_flags(flags), ops.kernel_trace(DEV) as tr:
+        y = ops.pw_conv(x, w, bias, out_sums=sums, packed=packed, **kw)
+    torch.cuda.synchronize()
+    return y, sums, tr.names
+
+
+def _report(what, got, want, sums):
+    """measured errors, printed before anything is asserted: output max-abs, and the statistics relative to their bars"""
+    err = (got.double().cpu() - want).abs().max().item()
+    msg = "%s: max abs err %.3e (bar 1.0e-04, max|want| %.2f)" % (what, err, want.abs().max().item())
+    if sums is not None:
+        wf, tot = want.reshape(want.shape[0], -1), sums.cpu().sum(1)
+        e0 = ((tot[:, 0] - wf.sum(1)).abs() / wf.abs().sum(1)).max().item()
+        e1 = ((tot[:, 1] - (wf * wf).sum(1)).abs() / (wf * wf).sum(1)).max().item()
+        msg += "; sum err %.2e of sum|y|, sumsq err %.2e of sum y^2 (bars 4e-06)" % (e0, e1)
+    print(msg)
+
+
+@pytest.mark.parametrize("form,Bt,Cin,Cout,L", [("O_proj", 32, 1024, 1024, 132),     # 256 tiles: one full n-tile + 4 columns
+                                                ("ffn", 32, 1024, 1024, 132),
+                                                ("O_proj", 32, 1024, 512, 400),      # the bench shape's O_proj: 256 tiles
+                                                ("qkv", 11, 128, 3072, 132)])        # 264 tiles, 12 m-tiles
+def test_pw_conv_attentive_layer_forms(form, Bt, Cin, Cout, L):
+    """The 256 x 128 kernels at the shapes the attentive layer gives them when the launch fills the chip: as dispatched, under
+    GEMM_256_SWAP_FORMS (the form srf_forward prefers) and without the packed image (the 128 x 128 kernels) -- each against fp64
+    F.conv1d and its statistics against the fp64 sums, the three bitwise equal (same splits, same summation order over k)."""
+    from sudo_rm_rf_amd import ops
+    ops.set_kernel_mode(0)
+    pro = LAYER_FORMS[form][0]
+    x, w, bias, kw, want, with_sums = _layer_form_case(form, Bt, Cin, Cout, L)
+    packed = ops.pack_pw_weight(w)
+    assert packed is not None
+    runs = {"dispatched": _run_layer_form(x, w, bias, kw, with_sums, packed),
+            "swapped forms": _run_layer_form(x, w, bias, kw, with_sums, packed, DebugFlag.GEMM_256_SWAP_FORMS),
+            "no packed image": _run_layer_form(x, w, bias, kw, with_sums, None)}
+    for name, (y, sums, names) in runs.items():
+        _report("%s %s (%s, %s)" % (form, (Bt, Cin, Cout, L), name, sorted(names)), y, want, sums)
+    assert runs["dispatched"][2] == {"pw_conv_x3w<%d>" % pro}, runs["dispatched"][2]
+    # the paired-block form takes every epilogue but residual + statistics
+    assert runs["swapped forms"][2] == {"pw_conv_x3w<0>" if form == "O_proj" else "pw_conv_x3p<%d>" % pro}, runs["swapped forms"][2]
+    assert all(n.startswith("pw_conv_bf16x3") for n in runs["no packed image"][2]), runs["no packed image"][2]
+    for name, (y, sums, _) in runs.items():
+        check(y, want, 1e-4, "%s (%s)" % (form, name))
+        if with_sums:
+            check_sums(sums, want, "%s statistics (%s)" % (form, name))
+    assert torch.equal(runs["dispatched"][0], runs["swapped forms"][0])
+    assert torch.equal(runs["dispatched"][0], runs["no packed image"][0])
+
+
+@pytest.mark.parametrize("Cin,Cout", [(64, 3072), (1024, 64), (64, 64),      # the tiny layer's Q/K/V, O_proj, ffn
+                                      (512, 3072), (1024, 512)])             # the default model's Q/K/V and O_proj
+@pytest.mark.parametrize("L", [4, 28, 124])
+def test_pw_conv_attentive_layer_forms_shorter_than_a_tile(Cin, Cout, L):
+    """Lengths below one tile of any MFMA GEMM (the attentive layer asks for every Ld >= 4 that is a multiple of 4), batches 1 and
+    3, all three forms: an MFMA kernel serves them -- named by the trace -- and is right."""
+    from sudo_rm_rf_amd import ops
+    ops.set_kernel_mode(0)
+    for Bt in (1, 3):
+        for form in LAYER_FORMS:
+            x, w, bias, kw, want, with_sums = _layer_form_case(form, Bt, Cin, Cout, L)
+            y, sums, names = _run_layer_form(x, w, bias, kw, with_sums, ops.pack_pw_weight(w))
+            what = "%s %s" % (form, (Bt, Cin, Cout, L))
+            _report("%s (%s)" % (what, sorted(names)), y, want, sums)
+            assert len(names) == 1 and all(n.startswith(MFMA_GEMMS) for n in names), (what, names)
+            check(y, want, 1e-4, what)
+            if with_sums:
+                check_sums(sums, want, what + " statistics")
+
+
+def test_pw_conv_o_proj_form_inside_guard_bands():
+    """O_proj's form (residual + statistics on the 256 x 128 kernel) with x, residual, bias and the output inside the guard-banded
+    arena of tests/placement.py, on the 16-byte grid, the output pre-filled with NaN: the 4-column last tile stores nothing outside
+    the output (arena.check) and leaves no element unwritten (assert_clean); a store past column 132 of a row lands in the next
+    row and fails the comparison."""
+    from sudo_rm_rf_amd import ops
+    from tests import placement as pl
+    ops.set_kernel_mode(0)
+    Bt, Cin, Cout, L = 32, 1024, 1024, 132
+    x, w, bias, kw, want, _ = _layer_form_case("O_proj", Bt, Cin, Cout, L)
+    packed = ops.pack_pw_weight(w)
+    sums = ops.new_sums(Bt, DEV)
+    arena = pl.Arena(DEV, 64 << 20)
+    ax, ab = arena.put(x, name="x"), arena.put(bias, name="bias")
+    ares = arena.put(kw["residual"], name="residual")
+    with arena.allocating(ops, names=("y",)) as made, ops.kernel_trace(DEV) as tr:
+        y = ops.pw_conv(ax, w, ab, residual=ares, out_sums=sums, packed=packed)
+    torch.cuda.synchronize()
+    assert [n for n, _ in made] == ["y"] and arena.owns(y) and y.data_ptr() % 16 == 0 and ares.data_ptr() % 16 == 0
+    assert tr.names == {"pw_conv_x3w<0>"}, tr.names
+    arena.check()
+    arena.assert_clean(y)
+    assert torch.equal(ares, kw["residual"]) and torch.equal(ax, x)
+    _report("O_proj %s in the arena" % ((Bt, Cin, Cout, L),), y, want, sums)
+    check(y, want, 1e-4, "O_proj in the arena")
+    check_sums(sums, want, "O_proj in the arena: statistics")
+
+
 @pytest.mark.parametrize("Bt,Cin1,Cout2,L", [(32, 512, 512, 3200),      # cfg 2: res_conv -> proj_1x1 (800 tiles on 512 blocks: two rounds)
                                              (12, 512, 512, 3200),      # a sub-batch of the stream split: one round, blocks with one tile
                                              (24, 256, 384, 1604),      # ragged last tile (L % 128 = 68), three passes of conv 2, K1 = 256
