@@ -223,19 +223,6 @@ static long plan_padded_length(int T, int h, int D) {
   const long nls = (long)h << D;
   return (T < nls) ? nls : ((T / nls) + (T % nls ? 1 : 0)) * nls;
 }
-// A packed (split-bf16) image of parameter `param` ([cout, cin]) in the workspace, for the shapes the 256 x 128 GEMM supports
-static void plan_add_pack(srf_plan* p, size_t* off, int param, int cout, int cin) {
-  const size_t bytes = srf_packed_pw_weight_bytes(cout, cin);
-  if (!bytes) return;
-  const size_t o = *off;
-  *off = srf_align_up(*off + bytes, 256);
-  p->pk_param.push_back(param);
-  p->pk_cout.push_back(cout);
-  p->pk_cin.push_back(cin);
-  p->pk_off.push_back(o);
-  p->pk_of_param[param] = o;
-}
-
 static int plan_fail(srf_plan* p, int rc) {
   delete p;
   return rc;
@@ -348,10 +335,7 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   return SRF_OK;
 }
 
-// ---- causal variant (CausalSuDORMRF, causal_improved_sudormrf_v3.py) -----------------------------------------------------
-// state_dict order: encoder.weight, bottleneck.{weight,bias}; per block: skipinit_gain, proj_1x1.conv.{weight,bias},
-// proj_1x1.act.weight, D x spp_dw.k.{conv.weight, conv.bias, act.weight}, res_conv.{weight,bias}; tail: mask_net.0.weight,
-// mask_net.1.{weight,bias}, decoder.weight, mask_nl_class.weight.
+// ---- causal variant (CausalSuDORMRF, causal_improved_sudormrf_v3.py; parameter layout: srf_plan.h) ---------------------------
 static int causal_plan_create(const srf_config* c, int batch, int T, srf_plan** out) {
   SRF_CHECK_ARG(batch > 0 && T > 0, "srf_plan_create: batch and T must be positive");
   SRF_CHECK_ARG(c->in_audio_channels > 0 && c->out_channels > 0 && c->in_channels > 0 && c->num_blocks > 0 &&
@@ -387,11 +371,9 @@ static int causal_plan_create(const srf_config* c, int batch, int T, srf_plan** 
     srf_set_error("srf_plan_create: batch %d too large (max 65535 per call)", batch);
     return plan_fail(p, SRF_EINVAL);
   }
-  p->p_block0 = 3;
+  const SrfCausalLayout lay = causal_layout(U, D);
+  p->p_block0 = lay.block0, p->p_block_stride = lay.stride, p->p_tail = lay.tail, p->n_params = lay.n_params;
   p->p_ublock_off = 0;
-  p->p_block_stride = 6 + 3 * D;
-  p->p_tail = 3 + U * p->p_block_stride;
-  p->n_params = p->p_tail + 5;
   p->slots_per_block = 0;
   p->n_slots = 0;
   p->alpha.assign(U, 1.f);
@@ -416,18 +398,16 @@ static int causal_plan_create(const srf_config* c, int batch, int T, srf_plan** 
   p->off_dec = take(F * srf_decoder_scratch_floats(batch, p->SA * N, p->SA, K, p->L));
   p->fused_pyramid = srf_causal_pyramid_supported(Cc, p->L, D);
   p->off_pyr = 0;
-  // per block: res_conv weight * (gain * alpha) [B][C] | its bias [B]   and   proj_1x1 weight / beta [C][B]
-  const size_t res_floats = srf_align_up((size_t)B * Cc, 64) + srf_align_up((size_t)B, 64);
-  p->off_fold_res = take(F * res_floats * U);
+  // the folded weights of every block (srf_causal_fold)
+  p->off_fold_res = take(F * causal_fold_res_floats(B, Cc) * U);
   p->off_fold_proj = take(F * (size_t)Cc * B * U);
   p->pk_of_param.assign(p->n_params, 0);
-  plan_add_pack(p, &off, 1, B, N);
+  plan_add_pack(p, &off, SRF_PC_BOTTLENECK, B, N);
   for (int i = 0; i < U; ++i) {
-    const int pb = p->p_block0 + i * p->p_block_stride;
-    plan_add_pack(p, &off, pb + 1, Cc, B);
-    plan_add_pack(p, &off, pb + 4 + 3 * D, B, Cc);
+    plan_add_pack(p, &off, causal_p_proj(lay, i), Cc, B);
+    plan_add_pack(p, &off, causal_p_res(lay, i), B, Cc);
   }
-  plan_add_pack(p, &off, p->p_tail + 1, p->SA * N, B);
+  plan_add_pack(p, &off, causal_p_mask(lay), p->SA * N, B);
   p->off_wdpack = 0;
   p->total_bytes = off;
   p->n_launches = 3 /*fold, pack, encoder*/ + 1 + U * 3 + 1 + 4;
@@ -490,19 +470,6 @@ static int forward_check_args(const char* who, bool ptrs, const srf_plan* p, con
   SRF_CHECK_ARG((((size_t)workspace) & 255) == 0, "%s: workspace must be 256-byte aligned", who);
   for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "%s: parameter %d is null", who, i);
   return SRF_OK;
-}
-
-// split + lay out every packable 1x1 weight for the 256 x 128 split-precision GEMMs (srf_pwconv_x3w.hip / _x3p.hip), one launch
-// per forward.  source(parameter index): the fp32 weight that goes into the image (the causal forward: its folded copies)
-template <typename F>
-static int plan_pack_weights(const srf_plan* p, F source, char* ws, void* stream) {
-  std::vector<const float*> pw(p->pk_param.size());
-  std::vector<void*> pd(p->pk_param.size());
-  for (size_t i = 0; i < p->pk_param.size(); ++i) {
-    pw[i] = source(p->pk_param[i]);
-    pd[i] = ws + p->pk_off[i];
-  }
-  return srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
 }
 
 // ---- the steps of the walk, one per kernel family: the uniform entry point, or -- rg != NULL, srf_forward_ragged -- its ragged
@@ -595,9 +562,7 @@ static int forward_walk(const srf_plan* p, const float* const* P, const float* w
     rc = plan_pack_weights(p, [&](int param) { return P[param]; }, ws, stream);
     if (rc) return rc;
   }
-  auto packed = [&](int param_index) -> const void* {
-    return (use_pack && p->pk_of_param[param_index]) ? (const void*)(ws + p->pk_of_param[param_index]) : nullptr;
-  };
+  auto packed = [&](int param) { return plan_packed(p, ws, use_pack, param); };
 
   // ---- front end: encoder (+ ln statistics), ln folded into the bottleneck GEMM's operand load
   const SrfFront<const float> f = plan_front(P);
@@ -692,9 +657,22 @@ static int forward_walk(const srf_plan* p, const float* const* P, const float* w
     nxt = t;
   }
 
-  // ---- mask estimation + decoder                            :295-301
+  return srf_improved_tail(p, P, cur, out, workspace, use_pack, wav_stats, wav, mixture_consistency, rg, stream);
+}
+
+// ---- mask estimation + decoder of the Improved / GroupComm / attentive walks       improved_sudormrf.py:295-301
+// cur: the separation module's output; the encoder output is where the walk left it (off_enc); rg as in forward_walk
+int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur, float* out, void* workspace, bool use_pack,
+                      const float* wav_stats, const float* wav, int mixture_consistency, const Ragged* rg, void* stream) {
+  const srf_config& c = p->cfg;
+  const int N = c.enc_num_basis, K = c.enc_kernel_size, Bt = p->Bt, L = p->L;
+  char* ws = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
   const SrfTail<const float> t = plan_tail(p, P);
-  float* masked = fptr(p->off_masked);
+  const void* mask_packed = plan_packed(p, ws, use_pack, plan_p_mask(p));
+  const float* enc = (const float*)(ws + p->off_enc);
+  float* masked = (float*)(ws + p->off_masked);
+  int rc;
   // K5: mask GEMM and decoder contraction in ONE launch -- the [Bt, S N, L] masked tensor (the largest of the forward) never
   // reaches HBM; the GEMM leaves per-256-channel partial decoder frames (in the masked tensor's workspace region, <= 1/4 of
   // it) and the overlap-add sums them.  Only where the 256 x 128 GEMM would have run the mask conv anyway.  (Ragged: the
@@ -704,18 +682,16 @@ static int forward_walk(const srf_plan* p, const float* const* P, const float* w
     const int M = p->SA * K, nparts = (p->SA * N + 255) / 256;
     rc = srf_mask_decode_pack(t.dec_w, ws + p->off_wdpack, p->SA * N, M, st);
     if (rc) return rc;
-    rc = srf_mask_decode(cur, t.mask_w, packed(plan_p_mask(p)), t.mask_b, t.mask_prelu, enc, N, ws + p->off_wdpack, masked, Bt,
-                         c.out_channels, p->SA * N, L, M, st);
+    rc = srf_mask_decode(cur, t.mask_w, mask_packed, t.mask_b, t.mask_prelu, enc, N, ws + p->off_wdpack, masked, Bt, c.out_channels,
+                         p->SA * N, L, M, st);
     if (rc) return rc;
     return step_overlap_add(rg, masked, out, Bt, p->SA, K, L, p->T, nparts, wav_stats, wav, mixture_consistency, st);
   }
-  {
-    srf_norm pre{nullptr, nullptr, nullptr, t.mask_prelu};
-    rc = srf_pw_conv_packed(cur, t.mask_w, packed(plan_p_mask(p)), t.mask_b, masked, Bt, c.out_channels, p->SA * N, L,
-                            &pre, nullptr, nullptr, 1, enc, N, stream);
-    if (rc) return rc;
-  }
-  return srf_decoder_impl(masked, t.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, fptr(p->off_dec), wav_stats, wav,
+  srf_norm pre{nullptr, nullptr, nullptr, t.mask_prelu};
+  rc = srf_pw_conv_packed(cur, t.mask_w, mask_packed, t.mask_b, masked, Bt, c.out_channels, p->SA * N, L, &pre, nullptr, nullptr, 1,
+                          enc, N, stream);
+  if (rc) return rc;
+  return srf_decoder_impl(masked, t.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, (float*)(ws + p->off_dec), wav_stats, wav,
                           mixture_consistency, stream);
 }
 
@@ -890,6 +866,36 @@ extern "C" int srf_debug_fetch(const srf_plan* p, const void* workspace, int wha
 // causal forward (CausalSuDORMRF.forward): encoder -> bottleneck -> U x [proj_1x1 -> fused causal pyramid -> res_conv with
 // skipinit_gain * alpha folded into its weights, + residual] -> PReLU + mask conv -> PReLU folded into the decoder's load.
 // ---------------------------------------------------------------------------------------------
+// (srf_plan.h) entries of the one launch: per block res_conv weight, res_conv bias, then proj_1x1 weight where beta != 1
+int srf_causal_fold(const srf_plan* p, const float* const* P, float* fold_res, float* fold_proj, SrfCausalFolded* out, hipStream_t st) {
+  const int U = p->cfg.num_blocks, B = p->nB, Cc = p->nC;
+  const SrfCausalLayout lay = causal_layout(p);
+  std::vector<const float*> src, scale;
+  std::vector<float*> dst;
+  std::vector<long> n;
+  std::vector<float> h;
+  auto add = [&](const float* from, float* to, long count, const float* dscale, float hscale) {
+    src.push_back(from), dst.push_back(to), n.push_back(count), scale.push_back(dscale), h.push_back(hscale);
+  };
+  out->wproj.assign(U, nullptr), out->wres.assign(U, nullptr), out->bres.assign(U, nullptr);
+  for (int i = 0; i < U; ++i) {
+    const SrfCausalBlock<const float> b = causal_block<const float>(lay, P, i);
+    float* rw = fold_res + (size_t)i * causal_fold_res_floats(B, Cc);
+    float* rb = rw + srf_align_up((size_t)B * Cc, 64);
+    add(b.res_w, rw, (long)B * Cc, b.gain, p->alpha[i]);
+    add(b.res_b, rb, (long)B, b.gain, p->alpha[i]);
+    out->wres[i] = rw;
+    out->bres[i] = rb;
+    out->wproj[i] = b.proj_w;
+    if (p->beta[i] != 1.f) {
+      float* pw = fold_proj + (size_t)i * Cc * B;
+      add(b.proj_w, pw, (long)Cc * B, nullptr, 1.f / p->beta[i]);
+      out->wproj[i] = pw;
+    }
+  }
+  return srf_causal_scale_many(src.data(), dst.data(), n.data(), scale.data(), h.data(), (int)src.size(), st);
+}
+
 static int causal_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace, void* stream) {
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
@@ -897,58 +903,34 @@ static int causal_forward(const srf_plan* p, const float* const* P, const float*
   char* ws = (char*)workspace;
   hipStream_t st = (hipStream_t)stream;
   auto fptr = [&](size_t o) { return (float*)(ws + o); };
-  int rc;
-  // ---- fold: res_conv weight / bias * (skipinit_gain * alpha) for every block, proj_1x1 weight / beta where beta != 1
-  const size_t res_floats = srf_align_up((size_t)B * Cc, 64) + srf_align_up((size_t)B, 64);
-  std::vector<const float*> fsrc, fscale;
-  std::vector<float*> fdst;
-  std::vector<long> fn;
-  std::vector<float> fh;
-  std::vector<const float*> wproj(U), wres(U), bres(U);
-  for (int i = 0; i < U; ++i) {
-    const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
-    float* rw = fptr(p->off_fold_res) + (size_t)i * res_floats;
-    float* rb = rw + srf_align_up((size_t)B * Cc, 64);
-    fsrc.push_back(Pb[4 + 3 * D]); fdst.push_back(rw); fn.push_back((long)B * Cc); fscale.push_back(Pb[0]); fh.push_back(p->alpha[i]);
-    fsrc.push_back(Pb[5 + 3 * D]); fdst.push_back(rb); fn.push_back((long)B); fscale.push_back(Pb[0]); fh.push_back(p->alpha[i]);
-    wres[i] = rw;
-    bres[i] = rb;
-    wproj[i] = Pb[1];
-    if (p->beta[i] != 1.f) {
-      float* pw = fptr(p->off_fold_proj) + (size_t)i * Cc * B;
-      fsrc.push_back(Pb[1]); fdst.push_back(pw); fn.push_back((long)Cc * B); fscale.push_back(nullptr); fh.push_back(1.f / p->beta[i]);
-      wproj[i] = pw;
-    }
-  }
-  rc = srf_causal_scale_many(fsrc.data(), fdst.data(), fn.data(), fscale.data(), fh.data(), (int)fsrc.size(), st);
+  const SrfCausalLayout lay = causal_layout(p);
+  SrfCausalFolded w;
+  int rc = srf_causal_fold(p, P, fptr(p->off_fold_res), fptr(p->off_fold_proj), &w, st);
   if (rc) return rc;
   // ---- split-bf16 weight images of the packed shapes (kernel mode 0), from the folded copies where there are any
   const bool use_pack = plan_use_pack(p);
   auto source_of = [&](int param) -> const float* {
-    const int rel = param - p->p_block0;
-    if (param >= p->p_block0 && param < p->p_tail) {
-      const int i = rel / p->p_block_stride, r = rel % p->p_block_stride;
-      if (r == 1) return wproj[i];
-      if (r == 4 + 3 * D) return wres[i];
-    }
+    const SrfBlockParam q = plan_block_param(lay.block0, lay.stride, lay.tail, param);
+    if (q.block >= 0 && q.rel == SRF_PC_PROJ) return w.wproj[q.block];
+    if (q.block >= 0 && q.rel == causal_u_level(D)) return w.wres[q.block];
     return P[param];
   };
   if (use_pack) {
     rc = plan_pack_weights(p, source_of, ws, stream);
     if (rc) return rc;
   }
-  auto packed = [&](int param) -> const void* {
-    return (use_pack && p->pk_of_param[param]) ? (const void*)(ws + p->pk_of_param[param]) : nullptr;
-  };
+  auto packed = [&](int param) { return plan_packed(p, ws, use_pack, param); };
   // ---- front end: causal encoder, bottleneck (no norm)
+  const SrfCausalFront<const float> f = causal_front<const float>(P);
   float* enc = fptr(p->off_enc);
-  rc = srf_causal_encoder(wav, P[0], enc, Bt, p->A, p->T, N, K, L, stream);
+  rc = srf_causal_encoder(wav, f.enc_w, enc, Bt, p->A, p->T, N, K, L, stream);
   if (rc) return rc;
   float* cur = fptr(p->off_xa);
   float* nxt = fptr(p->off_xb);
   float* y1 = fptr(p->off_y1);
   float* merged = fptr(p->off_merged);
-  rc = srf_pw_conv_packed(enc, P[1], packed(1), P[2], cur, Bt, N, B, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
+  rc = srf_pw_conv_packed(enc, f.bott_w, packed(SRF_PC_BOTTLENECK), f.bott_b, cur, Bt, N, B, L, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                          stream);
   if (rc) return rc;
   // ---- separation module.  res_conv of block i + proj_1x1 of block i + 1 as one launch where the pair kernel takes the
   // shape (its no-prologue form: residual required), as in the Improved forward
@@ -956,43 +938,36 @@ static int causal_forward(const srf_plan* p, const float* const* P, const float*
   const bool pair = use_pack && !srf_dbg(SRF_DBG_NO_PAIRS) && srf_pw_conv_pair_supported(Bt, Cc, B, Cc, L);
   bool y1_ready = false;
   for (int i = 0; i < U; ++i) {
-    const int pb = p->p_block0 + i * p->p_block_stride;
-    const float* const* Pb = P + pb;
+    const SrfCausalBlock<const float> b = causal_block<const float>(lay, P, i);
     if (!y1_ready) {
-      rc = srf_pw_conv_packed(cur, wproj[i], packed(pb + 1), Pb[2], y1, Bt, B, Cc, L, nullptr, nullptr, nullptr, 0, nullptr, 0,
+      rc = srf_pw_conv_packed(cur, w.wproj[i], packed(b.i_proj), b.proj_b, y1, Bt, B, Cc, L, nullptr, nullptr, nullptr, 0, nullptr, 0,
                               stream);
       if (rc) return rc;
     }
     y1_ready = false;
     if (fused) {
-      const float *pw[SRF_MAX_DEPTH], *pbias[SRF_MAX_DEPTH], *pa[SRF_MAX_DEPTH];
-      for (int k = 0; k < D; ++k) {
-        pw[k] = Pb[4 + 3 * k];
-        pbias[k] = Pb[5 + 3 * k];
-        pa[k] = Pb[6 + 3 * k];
-      }
-      rc = srf_causal_pyramid(y1, merged, Pb[3], pw, pbias, pa, Bt, Cc, L, D, stream);
+      rc = srf_causal_pyramid(y1, merged, b.proj_prelu, b.lv_w, b.lv_b, b.lv_prelu, Bt, Cc, L, D, stream);
       if (rc) return rc;
     } else {
       const float* levels[SRF_MAX_DEPTH];
       for (int k = 0; k < D; ++k) {
         float* dk = fptr(p->off_lv[k]);
-        rc = srf_causal_dwconv(k == 0 ? y1 : levels[k - 1], Pb[4 + 3 * k], Pb[5 + 3 * k], k == 0 ? Pb[3] : nullptr,
-                               Pb[6 + 3 * k], dk, Bt, Cc, k == 0 ? L : (L >> (k - 1)), k == 0 ? 1 : 2, stream);
+        rc = srf_causal_dwconv(k == 0 ? y1 : levels[k - 1], b.lv_w[k], b.lv_b[k], k == 0 ? b.proj_prelu : nullptr, b.lv_prelu[k], dk,
+                               Bt, Cc, k == 0 ? L : (L >> (k - 1)), k == 0 ? 1 : 2, stream);
         if (rc) return rc;
         levels[k] = dk;
       }
       rc = srf_causal_merge(levels, D, merged, Bt, Cc, L, stream);
       if (rc) return rc;
     }
-    const int pn = pb + p->p_block_stride;
-    if (pair && i + 1 < U && packed(pb + 4 + 3 * D) && packed(pn + 1)) {
-      rc = srf_pw_conv_pair(merged, packed(pb + 4 + 3 * D), bres[i], nxt, nullptr, cur, packed(pn + 1), P[pn + 2], y1, nullptr,
-                            Bt, Cc, B, Cc, L, stream);
+    if (pair && i + 1 < U && packed(b.i_res) && packed(causal_p_proj(lay, i + 1))) {
+      const SrfCausalBlock<const float> nb = causal_block<const float>(lay, P, i + 1);
+      rc = srf_pw_conv_pair(merged, packed(b.i_res), w.bres[i], nxt, nullptr, cur, packed(nb.i_proj), nb.proj_b, y1, nullptr, Bt, Cc,
+                            B, Cc, L, stream);
       y1_ready = true;
     } else {
-      rc = srf_pw_conv_packed(merged, wres[i], packed(pb + 4 + 3 * D), bres[i], nxt, Bt, Cc, B, L, nullptr, cur, nullptr, 0,
-                              nullptr, 0, stream);
+      rc = srf_pw_conv_packed(merged, w.wres[i], packed(b.i_res), w.bres[i], nxt, Bt, Cc, B, L, nullptr, cur, nullptr, 0, nullptr, 0,
+                              stream);
     }
     if (rc) return rc;
     float* t = cur;
@@ -1000,14 +975,14 @@ static int causal_forward(const srf_plan* p, const float* const* P, const float*
     nxt = t;
   }
   // ---- mask_net (PReLU on load + 1x1) -> mask_nl_class PReLU on the decoder frame GEMM's load -> overlap-add + crop
-  const float* const* Pt = P + p->p_tail;
+  const SrfCausalTail<const float> t = causal_tail<const float>(lay, P);
   float* masks = fptr(p->off_masked);
   {
-    srf_norm pre{nullptr, nullptr, nullptr, Pt[0]};
-    rc = srf_pw_conv_packed(cur, Pt[1], packed(p->p_tail + 1), Pt[2], masks, Bt, B, p->SA * N, L, &pre, nullptr, nullptr, 0,
+    srf_norm pre{nullptr, nullptr, nullptr, t.mask_prelu};
+    rc = srf_pw_conv_packed(cur, t.mask_w, packed(causal_p_mask(lay)), t.mask_b, masks, Bt, B, p->SA * N, L, &pre, nullptr, nullptr, 0,
                             nullptr, 0, stream);
     if (rc) return rc;
   }
-  return srf_decoder_impl(masks, Pt[3], out, Bt, p->SA * N, p->SA, K, L, p->T, fptr(p->off_dec), nullptr, nullptr, 0, stream,
-                          Pt[4]);
+  return srf_decoder_impl(masks, t.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, fptr(p->off_dec), nullptr, nullptr, 0, stream,
+                          t.out_prelu);
 }

@@ -107,25 +107,15 @@ extern "C" int srf_attentive_plan_create(const srf_config* base, int n_heads, in
   p->off_pyr = 0;
   // packed (split-bf16) images for the 256 x 128 GEMM, where it takes the shape; the Q/K/V image hangs on Q_proj.weight's index
   p->pk_of_param.assign(p->n_params, 0);
-  auto add_pack = [&](int param, int cout, int cin) {
-    const size_t bytes = srf_packed_pw_weight_bytes(cout, cin);
-    if (!bytes) return;
-    p->pk_param.push_back(param);
-    p->pk_cout.push_back(cout);
-    p->pk_cin.push_back(cin);
-    p->pk_off.push_back(off);
-    p->pk_of_param[param] = off;
-    off = srf_align_up(off + bytes, 256);
-  };
-  add_pack(SRF_P_BOTTLENECK, c.out_channels, N);
+  plan_add_pack(p, &off, SRF_P_BOTTLENECK, c.out_channels, N);
   for (int i = 0; i < U; ++i) {
-    add_pack(plan_p_proj(p, i), C, c.out_channels);
-    add_pack(plan_p_res(p, i), c.out_channels, C);
-    add_pack(att_p_base(p, i) + SRF_PA_Q, 3 * HD, C);
-    add_pack(att_p_base(p, i) + SRF_PA_O, C, HD);
-    add_pack(att_p_base(p, i) + SRF_PA_FFN, C, C);
+    plan_add_pack(p, &off, plan_p_proj(p, i), C, c.out_channels);
+    plan_add_pack(p, &off, plan_p_res(p, i), c.out_channels, C);
+    plan_add_pack(p, &off, att_p_base(p, i) + SRF_PA_Q, 3 * HD, C);
+    plan_add_pack(p, &off, att_p_base(p, i) + SRF_PA_O, C, HD);
+    plan_add_pack(p, &off, att_p_base(p, i) + SRF_PA_FFN, C, C);
   }
-  add_pack(plan_p_mask(p), p->SA * N, c.out_channels);
+  plan_add_pack(p, &off, plan_p_mask(p), p->SA * N, c.out_channels);
   p->off_wdpack = (p->SA * K <= 64 && p->pk_of_param[plan_p_mask(p)]) ? take(srf_mask_decode_pack_bytes(p->SA * N)) : 0;
   p->total_bytes = off;
   p->n_launches = 1 /*zero*/ + (6 * U + 47) / 48 /*concat*/ + 1 /*pack*/ + 2 + U * (D + 9) + 1 + 4;
@@ -172,24 +162,18 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
   }
   const bool use_pack = plan_use_pack(p);
   if (use_pack) {
-    std::vector<const float*> pw(p->pk_param.size());
-    std::vector<void*> pd(p->pk_param.size());
-    for (size_t i = 0; i < pw.size(); ++i) {
-      const int param = p->pk_param[i], rel = param - p->p_block0;
-      const bool is_q = param >= p->p_block0 && param < p->p_tail &&
-                        rel % p->p_block_stride == plan_block_params(D, false) + SRF_PA_Q;
-      pw[i] = is_q ? wqkv[rel / p->p_block_stride] : P[param];
-      pd[i] = ws + p->pk_off[i];
-    }
-    rc = srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
+    // the image on Q_proj.weight's index is that of the concatenated Q/K/V weight
+    auto source_of = [&](int param) -> const float* {
+      const SrfBlockParam q = plan_block_param(p->p_block0, p->p_block_stride, p->p_tail, param);
+      return q.block >= 0 && q.rel == plan_block_params(D, false) + SRF_PA_Q ? wqkv[q.block] : P[param];
+    };
+    rc = plan_pack_weights(p, source_of, ws, stream);
     if (rc) return rc;
   }
-  auto packed = [&](int param) -> const void* {
-    return (use_pack && p->pk_of_param[param]) ? (const void*)(ws + p->pk_of_param[param]) : nullptr;
-  };
   auto conv = [&](const float* x, const float* w, int param, const float* bias, float* y, int Cin, int Cout, int len,
                   const srf_norm* in_norm, const float* residual, double* out_sums) {
-    return srf_pw_conv_packed(x, w, packed(param), bias, y, Bt, Cin, Cout, len, in_norm, residual, out_sums, 0, nullptr, 0, stream);
+    return srf_pw_conv_packed(x, w, plan_packed(p, ws, use_pack, param), bias, y, Bt, Cin, Cout, len, in_norm, residual, out_sums, 0,
+                              nullptr, 0, stream);
   };
 
   // ---- front end: encoder (+ ln statistics), ln folded into the bottleneck GEMM's operand load
@@ -261,21 +245,5 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
   }
 
   // ---- mask estimation + decoder: the Improved walk's tail
-  const SrfTail<const float> t = plan_tail(p, P);
-  float* masked = fptr(p->off_masked);
-  if (plan_fused_tail_now(p, use_pack)) {
-    const int M = p->SA * K, nparts = (p->SA * N + 255) / 256;
-    rc = srf_mask_decode_pack(t.dec_w, ws + p->off_wdpack, p->SA * N, M, st);
-    if (rc) return rc;
-    rc = srf_mask_decode(cur, t.mask_w, packed(plan_p_mask(p)), t.mask_b, t.mask_prelu, enc, N, ws + p->off_wdpack, masked, Bt,
-                         c.out_channels, p->SA * N, L, M, st);
-    if (rc) return rc;
-    return srf_overlap_add_launch(masked, out, Bt, p->SA, K, L, p->T, nparts, wav_stats, wav, mixture_consistency, st);
-  }
-  const srf_norm pre{nullptr, nullptr, nullptr, t.mask_prelu};
-  rc = srf_pw_conv_packed(cur, t.mask_w, packed(plan_p_mask(p)), t.mask_b, masked, Bt, c.out_channels, p->SA * N, L, &pre, nullptr,
-                          nullptr, 1, enc, N, stream);
-  if (rc) return rc;
-  return srf_decoder_impl(masked, t.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, fptr(p->off_dec), wav_stats, wav,
-                          mixture_consistency, stream);
+  return srf_improved_tail(p, P, cur, out, workspace, use_pack, wav_stats, wav, mixture_consistency, nullptr, stream);
 }

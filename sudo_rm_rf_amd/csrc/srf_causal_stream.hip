@@ -19,7 +19,7 @@
 #include <new>
 #include <vector>
 
-#include "srf_internal.h"
+#include "srf_plan.h"
 
 #define SRF_STREAM_HIST (SRF_CAUSAL_TAPS - 1)
 #define SRF_STREAM_TN 8      // columns per GEMM tile
@@ -395,7 +395,7 @@ struct srf_stream {
   srf_config cfg;
   int Bt, max_n, max_lc;
   int A, B, C, U, D, K, N, S, SA, M, h, g;
-  int n_params, p_block0, p_block_stride, p_tail;
+  SrfCausalLayout lay;         // the parameter order (srf_plan.h)
   std::vector<float> alpha, beta;
   std::vector<size_t> w_off;   // [n_params] float offsets into the prepared weight buffer
   std::vector<long> w_n;       // [n_params] element counts
@@ -439,30 +439,27 @@ extern "C" int srf_stream_create(const srf_config* c, int batch, int max_chunk_s
   s->Bt = batch; s->max_n = max_chunk_samples; s->max_lc = max_lc;
   s->A = c->in_audio_channels; s->B = c->out_channels; s->C = c->in_channels; s->U = U; s->D = D; s->K = K; s->N = N;
   s->S = c->num_sources; s->SA = SA; s->M = SA * K; s->h = h; s->g = g;
-  s->p_block0 = 3;
-  s->p_block_stride = 6 + 3 * D;
-  s->p_tail = 3 + U * s->p_block_stride;
-  s->n_params = s->p_tail + 5;
+  s->lay = causal_layout(U, D);
+  const int n_params = s->lay.n_params;
   s->alpha.assign(U, 1.f);
   s->beta.assign(U, 1.f);
   // prepared weights: one slot per parameter in state_dict order (64-float aligned); decoder.weight's slot holds its transpose
-  s->w_n.assign(s->n_params, 0);
-  s->w_n[0] = (long)N * s->A * (2 * K - 1);
-  s->w_n[1] = (long)s->B * N;
-  s->w_n[2] = s->B;
+  s->w_n.assign(n_params, 0);
+  std::vector<long*> wn(n_params);
+  for (int p = 0; p < n_params; ++p) wn[p] = &s->w_n[p];
+  const SrfCausalFront<long> nf = causal_front<long>(wn);
+  *nf.enc_w = (long)N * s->A * (2 * K - 1), *nf.bott_w = (long)s->B * N, *nf.bott_b = s->B;
   for (int i = 0; i < U; ++i) {
-    long* wn = s->w_n.data() + s->p_block0 + (size_t)i * s->p_block_stride;
-    wn[0] = 1; wn[1] = (long)s->C * s->B; wn[2] = s->C; wn[3] = 1;
-    for (int k = 0; k < D; ++k) { wn[4 + 3 * k] = (long)s->C * SRF_CAUSAL_KW; wn[5 + 3 * k] = s->C; wn[6 + 3 * k] = 1; }
-    wn[4 + 3 * D] = (long)s->B * s->C; wn[5 + 3 * D] = s->B;
+    const SrfCausalBlock<long> nb = causal_block<long>(s->lay, wn, i);
+    *nb.gain = 1, *nb.proj_w = (long)s->C * s->B, *nb.proj_b = s->C, *nb.proj_prelu = 1;
+    for (int k = 0; k < D; ++k) *nb.lv_w[k] = (long)s->C * SRF_CAUSAL_KW, *nb.lv_b[k] = s->C, *nb.lv_prelu[k] = 1;
+    *nb.res_w = (long)s->B * s->C, *nb.res_b = s->B;
   }
-  {
-    long* wn = s->w_n.data() + s->p_tail;
-    wn[0] = 1; wn[1] = (long)SAN * s->B; wn[2] = SAN; wn[3] = (long)SAN * s->M; wn[4] = 1;
-  }
-  s->w_off.assign(s->n_params, 0);
+  const SrfCausalTail<long> nt = causal_tail<long>(s->lay, wn);
+  *nt.mask_prelu = 1, *nt.mask_w = (long)SAN * s->B, *nt.mask_b = SAN, *nt.dec_w = (long)SAN * s->M, *nt.out_prelu = 1;
+  s->w_off.assign(n_params, 0);
   size_t off = 0;
-  for (int p = 0; p < s->n_params; ++p) {
+  for (int p = 0; p < n_params; ++p) {
     s->w_off[p] = off;
     off += srf_align_up((size_t)s->w_n[p], 64);
   }
@@ -509,29 +506,28 @@ extern "C" int srf_stream_set_block_scales(srf_stream* s, const float* alpha, co
 // folded into res_conv's weight and bias, 1 / beta into proj_1x1's weight, the decoder weight transposed to [Co K][Ci].
 extern "C" int srf_stream_prepare(const srf_stream* s, const float* const* P, int num_params, void* weights_buf, void* stream) {
   SRF_CHECK_ARG(s && P && weights_buf, "srf_stream_prepare: null pointer");
-  SRF_CHECK_ARG(num_params == s->n_params, "srf_stream_prepare: expected %d parameters, got %d", s->n_params, num_params);
+  SRF_CHECK_ARG(num_params == s->lay.n_params, "srf_stream_prepare: expected %d parameters, got %d", s->lay.n_params, num_params);
   SRF_CHECK_ARG(((size_t)weights_buf & 255) == 0, "srf_stream_prepare: weights_buf %p is not 256-byte aligned", weights_buf);
   for (int p = 0; p < num_params; ++p) SRF_CHECK_ARG(P[p] != nullptr, "srf_stream_prepare: parameter %d is null", p);
   float* wb = (float*)weights_buf;
   hipStream_t st = (hipStream_t)stream;
+  // per parameter: the device scalar and the host factor it is copied with (skipinit_gain * alpha, 1 / beta; else 1)
+  std::vector<const float*> gain_of(num_params, nullptr);
+  std::vector<float> factor_of(num_params, 1.f);
+  for (int i = 0; i < s->U; ++i) {
+    const SrfCausalBlock<const float> b = causal_block<const float>(s->lay, P, i);
+    factor_of[b.i_proj] = 1.f / s->beta[i];
+    gain_of[b.i_res] = gain_of[b.i_res + 1] = b.gain;      // res_conv weight and bias
+    factor_of[b.i_res] = factor_of[b.i_res + 1] = s->alpha[i];
+  }
   std::vector<const float*> src, dsc;
   std::vector<float*> dst;
   std::vector<long> cnt;
   std::vector<float> hs;
-  const int dec = s->p_tail + 3;
+  const int dec = causal_p_dec(s->lay);      // transposed below
   for (int p = 0; p < num_params; ++p) {
     if (p == dec) continue;
-    const float* d = nullptr;
-    float hsc = 1.f;
-    if (p >= s->p_block0 && p < s->p_tail) {
-      const int i = (p - s->p_block0) / s->p_block_stride, r = (p - s->p_block0) % s->p_block_stride;
-      if (r == 1) hsc = 1.f / s->beta[i];
-      if (r == 4 + 3 * s->D || r == 5 + 3 * s->D) {
-        d = P[s->p_block0 + i * s->p_block_stride];
-        hsc = s->alpha[i];
-      }
-    }
-    src.push_back(P[p]); dst.push_back(wb + s->w_off[p]); cnt.push_back(s->w_n[p]); dsc.push_back(d); hs.push_back(hsc);
+    src.push_back(P[p]); dst.push_back(wb + s->w_off[p]); cnt.push_back(s->w_n[p]); dsc.push_back(gain_of[p]); hs.push_back(factor_of[p]);
   }
   int rc = srf_causal_scale_many(src.data(), dst.data(), cnt.data(), dsc.data(), hs.data(), (int)src.size(), st);
   if (rc) return rc;
@@ -564,7 +560,9 @@ template <class M>
 static int stream_forward(const srf_stream* s, const float* wb, float* sp, const float* wav, float* out, float* ws, long ncol,
                           const M* grp, const int* maxf, const int* nrows, int ngrp, hipStream_t st) {
   const int D = s->D;
-  auto W = [&](int p) { return wb + s->w_off[p]; };
+  const SrfOffsetTable<const float> W{wb, s->w_off.data()};
+  const SrfCausalFront<const float> f = causal_front<const float>(W);
+  const SrfCausalTail<const float> t = causal_tail<const float>(s->lay, W);
   float* enc = ws + s->ws_enc;
   float* cur = ws + s->ws_xa;
   float* nxt = ws + s->ws_xb;
@@ -576,24 +574,22 @@ static int stream_forward(const srf_stream* s, const float* wb, float* sp, const
   for (int gi = 0; gi < ngrp; ++gi) {
     const size_t lds = sizeof(float) * (size_t)s->A * (7 * s->h + s->K);
     hipLaunchKernelGGL(srf_stream_enc_kernel<M>, dim3((s->N + 31) / 32, (maxf[gi] + 7) / 8, nrows[gi]), dim3(256), lds, st, wav,
-                       hist, W(0), enc, s->A, s->N, s->K, grp[gi]);
+                       hist, f.enc_w, enc, s->A, s->N, s->K, grp[gi]);
     SRF_CHECK_LAUNCH("stream_encoder", st);
   }
-  int rc = stream_pw(enc, W(1), W(2), nullptr, nullptr, cur, s->N, s->B, ncol, st);
+  int rc = stream_pw(enc, f.bott_w, f.bott_b, nullptr, nullptr, cur, s->N, s->B, ncol, st);
   if (rc) return rc;
   for (int i = 0; i < s->U; ++i) {
-    const int pb = s->p_block0 + i * s->p_block_stride;
-    rc = stream_pw(cur, W(pb + 1), W(pb + 2), nullptr, nullptr, y1, s->B, s->C, ncol, st);
+    const SrfCausalBlock<const float> b = causal_block<const float>(s->lay, W, i);
+    rc = stream_pw(cur, b.proj_w, b.proj_b, nullptr, nullptr, y1, s->B, s->C, ncol, st);
     if (rc) return rc;
     StreamPyrArgs a;
     a.y1 = y1;
     a.merged = merged;
-    a.in_prelu = W(pb + 3);
+    a.in_prelu = b.proj_prelu;
     for (int k = 0; k < D; ++k) {
       a.state[k] = sp + s->st_dw + ((size_t)i * D + k) * s->Bt * s->C * SRF_STREAM_HIST;
-      a.w[k] = W(pb + 4 + 3 * k);
-      a.b[k] = W(pb + 5 + 3 * k);
-      a.a[k] = W(pb + 6 + 3 * k);
+      a.w[k] = b.lv_w[k], a.b[k] = b.lv_b[k], a.a[k] = b.lv_prelu[k];
     }
     a.C = s->C;
     for (int gi = 0; gi < ngrp; ++gi) {
@@ -601,16 +597,15 @@ static int stream_forward(const srf_stream* s, const float* wb, float* sp, const
       rc = stream_pyramid_launch(a, grp[gi], maxf[gi], D, st);
       if (rc) return rc;
     }
-    rc = stream_pw(merged, W(pb + 4 + 3 * D), W(pb + 5 + 3 * D), nullptr, cur, nxt, s->C, s->B, ncol, st);
+    rc = stream_pw(merged, b.res_w, b.res_b, nullptr, cur, nxt, s->C, s->B, ncol, st);
     if (rc) return rc;
-    float* t = cur;
+    float* tmp = cur;
     cur = nxt;
-    nxt = t;
+    nxt = tmp;
   }
-  const int pt = s->p_tail;
-  rc = stream_pw(cur, W(pt + 1), W(pt + 2), W(pt), nullptr, masks, s->B, s->SA * s->N, ncol, st);
+  rc = stream_pw(cur, t.mask_w, t.mask_b, t.mask_prelu, nullptr, masks, s->B, s->SA * s->N, ncol, st);
   if (rc) return rc;
-  rc = stream_pw(masks, W(pt + 3), nullptr, W(pt + 4), nullptr, z, s->SA * s->N, s->M, ncol, st);
+  rc = stream_pw(masks, t.dec_w, nullptr, t.out_prelu, nullptr, z, s->SA * s->N, s->M, ncol, st);
   if (rc) return rc;
   for (int gi = 0; gi < ngrp; ++gi) {
     hipLaunchKernelGGL(srf_stream_ola_kernel<M>, dim3((s->h * maxf[gi] + 255) / 256, s->SA, nrows[gi]), dim3(256), 0, st, z,

@@ -47,7 +47,7 @@ CTrainLayout ctrain_layout(const srf_plan* p) {
 struct CScratchLayout {
   size_t dec, gv, genc, gxa, gxb, gm, gu, gd[SRF_MAX_DEPTH], frames, wt, zeros, wdpad, wg, pyr, fold_res, fold_proj, encw, pk3,
       pkT, total;
-  size_t res_floats, zero_floats;
+  size_t zero_floats;
   int dec_rows;
 };
 
@@ -92,8 +92,7 @@ CScratchLayout cscratch_layout(const srf_plan* p) {
   s.wg = take(wg);
   s.pyr = take(cmax(cmax(srf_causal_pyramid_bwd_scratch_bytes(p->Bt, C, p->L, D), srf_causal_dwconv_bwd_scratch_bytes(p->Bt, C, p->L)),
                     F * srf_causal_prelu_bwd_scratch_floats()));
-  s.res_floats = srf_align_up((size_t)B * C, 64) + srf_align_up((size_t)B, 64);
-  s.fold_res = take(F * s.res_floats * U);
+  s.fold_res = take(F * causal_fold_res_floats(B, C) * U);
   s.fold_proj = take(F * (size_t)C * B * U);
   s.encw = take(F * (size_t)N * enc_rows);
   {
@@ -124,34 +123,20 @@ int ctrain_check(const srf_plan* p, const char* who) {
   return SRF_OK;
 }
 
-// res_conv weight / bias * (skipinit_gain * alpha) for every block, proj_1x1 weight / beta where beta != 1 (as srf_forward)
-int ctrain_fold(const srf_plan* p, const float* const* P, const CScratchLayout& s, char* sc, std::vector<const float*>& wproj,
-                std::vector<const float*>& wres, std::vector<const float*>& bres, hipStream_t st) {
-  const int D = p->cfg.upsampling_depth, U = p->cfg.num_blocks, B = p->nB, Cc = p->nC;
-  std::vector<const float*> fsrc, fscale;
-  std::vector<float*> fdst;
-  std::vector<long> fn;
-  std::vector<float> fh;
-  wproj.assign(U, nullptr);
-  wres.assign(U, nullptr);
-  bres.assign(U, nullptr);
-  for (int i = 0; i < U; ++i) {
-    const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
-    float* rw = (float*)(sc + s.fold_res) + (size_t)i * s.res_floats;
-    float* rb = rw + srf_align_up((size_t)B * Cc, 64);
-    fsrc.push_back(Pb[4 + 3 * D]); fdst.push_back(rw); fn.push_back((long)B * Cc); fscale.push_back(Pb[0]); fh.push_back(p->alpha[i]);
-    fsrc.push_back(Pb[5 + 3 * D]); fdst.push_back(rb); fn.push_back((long)B); fscale.push_back(Pb[0]); fh.push_back(p->alpha[i]);
-    wres[i] = rw;
-    bres[i] = rb;
-    wproj[i] = Pb[1];
-    if (p->beta[i] != 1.f) {
-      float* pw = (float*)(sc + s.fold_proj) + (size_t)i * Cc * B;
-      fsrc.push_back(Pb[1]); fdst.push_back(pw); fn.push_back((long)Cc * B); fscale.push_back(nullptr); fh.push_back(1.f / p->beta[i]);
-      wproj[i] = pw;
-    }
+// weight images queued for ONE pack launch, carved from `at` in steps of 256 bytes
+struct PackQueue {
+  char* at;
+  std::vector<const float*> w;
+  std::vector<void*> d;
+  std::vector<int> cout, cin;
+  const void* add(const float* weight, size_t bytes, int co, int ci) {
+    if (!bytes) return nullptr;
+    void* dst = at;
+    at += srf_align_up(bytes, 256);
+    w.push_back(weight), d.push_back(dst), cout.push_back(co), cin.push_back(ci);
+    return dst;
   }
-  return srf_causal_scale_many(fsrc.data(), fdst.data(), fn.data(), fscale.data(), fh.data(), (int)fsrc.size(), st);
-}
+};
 
 int cforward_train_impl(const srf_plan* p, const float* const* P, const float* wav, float* out, void* saved, void* scratch,
                         bool split_tail, void* stream) {
@@ -164,74 +149,64 @@ int cforward_train_impl(const srf_plan* p, const float* const* P, const float* w
   char* sc = (char*)scratch;
   hipStream_t st = (hipStream_t)stream;
   auto xbuf = [&](int i) { return (float*)(sv + t.x0 + t.x_stride * i); };
-  std::vector<const float*> wproj, wres, bres;
-  int rc = ctrain_fold(p, P, s, sc, wproj, wres, bres, st);
+  const SrfCausalLayout lay = causal_layout(p);
+  const SrfCausalFront<const float> f = causal_front<const float>(P);
+  const SrfCausalTail<const float> tl = causal_tail<const float>(lay, P);
+  SrfCausalFolded w;
+  int rc = srf_causal_fold(p, P, (float*)(sc + s.fold_res), (float*)(sc + s.fold_proj), &w, st);
   if (rc) return rc;
   // three-part (or two-fp16-part) images of the 1x1 weights the 256 x 128 GEMM takes, as forward_train_impl packs them
   const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
-  std::vector<const float*> pk_w;
-  std::vector<void*> pk_d;
-  std::vector<int> pk_co, pk_ci;
-  size_t pk_off = s.pk3;
-  auto pack3 = [&](const float* w, int cout, int cin) -> const void* {
-    const size_t bytes = srf_packed3_pw_weight_bytes(cout, cin);
-    if (!three || !bytes) return nullptr;
-    void* d = sc + pk_off;
-    pk_off += srf_align_up(bytes, 256);
-    pk_w.push_back(w);
-    pk_d.push_back(d);
-    pk_co.push_back(cout);
-    pk_ci.push_back(cin);
-    return d;
+  PackQueue pk{sc + s.pk3};
+  auto pack3 = [&](const float* wt, int cout, int cin) {
+    return pk.add(wt, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin);
   };
-  const float* const* Pt = P + p->p_tail;
-  const void* pk_bott = pack3(P[1], B, N);
-  const void* pk_mask = pack3(Pt[1], SAN, B);
+  const void* pk_bott = pack3(f.bott_w, B, N);
+  const void* pk_mask = pack3(tl.mask_w, SAN, B);
   std::vector<const void*> pk_proj(U, nullptr);
-  for (int i = 0; i < U; ++i) pk_proj[i] = pack3(wproj[i], Cc, B);
-  if (!pk_w.empty()) {
-    rc = srf_pack3_pw_weights(pk_w.data(), pk_d.data(), pk_co.data(), pk_ci.data(), (int)pk_w.size(), stream);
+  for (int i = 0; i < U; ++i) pk_proj[i] = pack3(w.wproj[i], Cc, B);
+  if (!pk.w.empty()) {
+    rc = srf_pack3_pw_weights(pk.w.data(), pk.d.data(), pk.cout.data(), pk.cin.data(), (int)pk.w.size(), stream);
     if (rc) return rc;
   }
   float* enc = (float*)(sv + t.enc);
-  rc = srf_causal_encoder(wav, P[0], enc, Bt, p->A, p->T, N, K, L, stream);
+  rc = srf_causal_encoder(wav, f.enc_w, enc, Bt, p->A, p->T, N, K, L, stream);
   if (rc) return rc;
-  rc = srf_pw_conv_packed3(enc, P[1], pk_bott, P[2], xbuf(0), Bt, N, B, L, nullptr, nullptr, nullptr, stream);
+  rc = srf_pw_conv_packed3(enc, f.bott_w, pk_bott, f.bott_b, xbuf(0), Bt, N, B, L, nullptr, nullptr, nullptr, stream);
   if (rc) return rc;
   for (int i = 0; i < U; ++i) {
-    const float* const* Pb = P + p->p_block0 + (size_t)i * p->p_block_stride;
+    const SrfCausalBlock<const float> b = causal_block<const float>(lay, P, i);
     char* blk = sv + t.blk0 + t.blk_stride * i;
     float* u = (float*)(blk + t.u);
     float* merged = (float*)(blk + t.merged);
-    rc = srf_pw_conv_packed3(xbuf(i), wproj[i], pk_proj[i], Pb[2], u, Bt, B, Cc, L, nullptr, nullptr, nullptr, stream);
+    rc = srf_pw_conv_packed3(xbuf(i), w.wproj[i], pk_proj[i], b.proj_b, u, Bt, B, Cc, L, nullptr, nullptr, nullptr, stream);
     if (rc) return rc;
     // the per-level kernels with the activation moved to the consumer's load: d_k is stored BEFORE its PReLU
-    const float *dv[SRF_MAX_DEPTH], *av[SRF_MAX_DEPTH];
+    const float* dv[SRF_MAX_DEPTH];
     for (int k = 0; k < D; ++k) {
       float* dk = (float*)(blk + t.lv[k]);
-      rc = srf_causal_dwconv(k == 0 ? u : dv[k - 1], Pb[4 + 3 * k], Pb[5 + 3 * k], k == 0 ? Pb[3] : Pb[6 + 3 * (k - 1)], nullptr, dk,
-                             Bt, Cc, k == 0 ? L : (L >> (k - 1)), k == 0 ? 1 : 2, stream);
+      rc = srf_causal_dwconv(k == 0 ? u : dv[k - 1], b.lv_w[k], b.lv_b[k], k == 0 ? b.proj_prelu : b.lv_prelu[k - 1], nullptr, dk, Bt,
+                             Cc, k == 0 ? L : (L >> (k - 1)), k == 0 ? 1 : 2, stream);
       if (rc) return rc;
       dv[k] = dk;
-      av[k] = Pb[6 + 3 * k];
     }
-    rc = srf_causal_merge_act(dv, av, D, merged, Bt, Cc, L, st);
+    rc = srf_causal_merge_act(dv, b.lv_prelu, D, merged, Bt, Cc, L, st);
     if (rc) return rc;
-    rc = srf_pw_conv_packed3(merged, wres[i], nullptr, bres[i], xbuf(i + 1), Bt, Cc, B, L, nullptr, xbuf(i), nullptr, stream);
+    rc = srf_pw_conv_packed3(merged, w.wres[i], nullptr, w.bres[i], xbuf(i + 1), Bt, Cc, B, L, nullptr, xbuf(i), nullptr, stream);
     if (rc) return rc;
   }
   float* m = (float*)(sv + t.m);
   {
-    srf_norm pre{nullptr, nullptr, nullptr, Pt[0]};
-    rc = srf_pw_conv_packed3(xbuf(U), Pt[1], pk_mask, Pt[2], m, Bt, B, SAN, L, &pre, nullptr, nullptr, stream);
+    srf_norm pre{nullptr, nullptr, nullptr, tl.mask_prelu};
+    rc = srf_pw_conv_packed3(xbuf(U), tl.mask_w, pk_mask, tl.mask_b, m, Bt, B, SAN, L, &pre, nullptr, nullptr, stream);
     if (rc) return rc;
   }
   float* v = (float*)(sc + s.gv);
-  rc = srf_prelu_apply(m, Pt[4], v, (long)Bt * SAN * L, stream);
+  rc = srf_prelu_apply(m, tl.out_prelu, v, (long)Bt * SAN * L, stream);
   if (rc) return rc;
   // the decoder's frame GEMM is the last linear map: on the split kernel when the exact class was this call's own choice
   const int tail_prev = split_tail ? srf_kernel_mode_override(0) : -1;
-  rc = srf_decoder(v, Pt[3], out, Bt, SAN, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
+  rc = srf_decoder(v, tl.dec_w, out, Bt, SAN, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
   if (split_tail) srf_kernel_mode_override(tail_prev);
   return rc;
 }
@@ -291,7 +266,11 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   float* zeros = fp(s.zeros);
   float* wt = fp(s.wt);
   void* wg = sc + s.wg;
-  const int pt = p->p_tail;
+  const SrfCausalLayout lay = causal_layout(p);
+  const SrfCausalFront<const float> f = causal_front<const float>(P);
+  const SrfCausalFront<float> gf = causal_front<float>(G);
+  const SrfCausalTail<const float> tl = causal_tail<const float>(lay, P);
+  const SrfCausalTail<float> gtl = causal_tail<float>(lay, G);
   if (srf_profiling()) srf_prof_mark("(gap)", st);
   SRF_CHECK_HIP(hipMemsetAsync(zeros, 0, sizeof(float) * s.zero_floats, st));
   // the weight-gradient GEMMs of this call fold their partial sums in a fixed order: two backwards of one step give equal bits
@@ -299,34 +278,23 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
     Ordered() { srf_pw_wgrad_ordered(true); }
     ~Ordered() { srf_pw_wgrad_ordered(false); }
   } ordered_for_this_call;
-  std::vector<const float*> wproj, wres, bres;
-  rc = ctrain_fold(p, P, s, sc, wproj, wres, bres, st);
+  SrfCausalFolded w;
+  rc = srf_causal_fold(p, P, fp(s.fold_res), fp(s.fold_proj), &w, st);
   if (rc) return rc;
   // transposed weights of the data-gradient GEMMs, pre-split for the 256 x 128 kernel where it takes the shape
-  std::vector<const float*> pk_w;
-  std::vector<void*> pk_d;
-  std::vector<int> pk_co, pk_ci;
-  size_t pk_off = s.pkT;
-  auto packT = [&](const float* w, int cout_d, int cin_d) -> const void* {   // w: forward weight [cin_d][cout_d]
-    const size_t bytes = srf_packed_pw_weight_bytes(cout_d, cin_d);
-    if (!bytes || srf_kernel_mode() != 0) return nullptr;
-    void* d = sc + pk_off;
-    pk_off += srf_align_up(bytes, 256);
-    pk_w.push_back(w);
-    pk_d.push_back(d);
-    pk_co.push_back(cout_d);
-    pk_ci.push_back(cin_d);
-    return d;
+  PackQueue pk{sc + s.pkT};
+  auto packT = [&](const float* wf, int cout_d, int cin_d) {   // wf: forward weight [cin_d][cout_d]
+    return pk.add(wf, srf_kernel_mode() == 0 ? srf_packed_pw_weight_bytes(cout_d, cin_d) : 0, cout_d, cin_d);
   };
-  const void* pkT_mask = packT(P[pt + 1], B, SAN);
-  const void* pkT_bott = packT(P[1], N, B);
+  const void* pkT_mask = packT(tl.mask_w, B, SAN);
+  const void* pkT_bott = packT(f.bott_w, N, B);
   std::vector<const void*> pkT_res(U, nullptr), pkT_proj(U, nullptr);
   for (int i = 0; i < U; ++i) {
-    pkT_res[i] = packT(wres[i], C, B);
-    pkT_proj[i] = packT(wproj[i], B, C);
+    pkT_res[i] = packT(w.wres[i], C, B);
+    pkT_proj[i] = packT(w.wproj[i], B, C);
   }
-  if (!pk_w.empty()) {
-    rc = srf_pack_pw_weights_transposed(pk_w.data(), pk_d.data(), pk_co.data(), pk_ci.data(), (int)pk_w.size(), st);
+  if (!pk.w.empty()) {
+    rc = srf_pack_pw_weights_transposed(pk.w.data(), pk.d.data(), pk.cout.data(), pk.cin.data(), (int)pk.w.size(), st);
     if (rc) return rc;
   }
   // g_x = W^T g (+ residual): cin_d -> cout_d, w the forward weight [cin_d][cout_d]
@@ -338,28 +306,28 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   float* gv = fp(s.gv);
   rc = srf_frames_gather(grad_out, frames, Bt, SA, p->T, K, h, h, L, s.dec_rows, stream);
   if (rc) return rc;
-  rc = srf_prelu_apply(m, P[pt + 4], gv, (long)Bt * SAN * L, stream);     // v, re-computed
+  rc = srf_prelu_apply(m, tl.out_prelu, gv, (long)Bt * SAN * L, stream);     // v, re-computed
   if (rc) return rc;
-  rc = srf_pw_wgrad_cols(gv, frames, nullptr, Bt, s.dec_rows, SAN, L, G[pt + 3], SA * K, nullptr, 0, wg, stream);
+  rc = srf_pw_wgrad_cols(gv, frames, nullptr, Bt, s.dec_rows, SAN, L, gtl.dec_w, SA * K, nullptr, 0, wg, stream);
   if (rc) return rc;
   float* wdpad = fp(s.wdpad);
   SRF_CHECK_HIP(hipMemsetAsync(wdpad, 0, sizeof(float) * (size_t)SAN * s.dec_rows, st));
-  SRF_CHECK_HIP(hipMemcpy2DAsync(wdpad, sizeof(float) * s.dec_rows, P[pt + 3], sizeof(float) * SA * K, sizeof(float) * SA * K, SAN,
+  SRF_CHECK_HIP(hipMemcpy2DAsync(wdpad, sizeof(float) * s.dec_rows, tl.dec_w, sizeof(float) * SA * K, sizeof(float) * SA * K, SAN,
                                  hipMemcpyDeviceToDevice, st));
   rc = srf_pw_conv(frames, wdpad, zeros, gv, Bt, s.dec_rows, SAN, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
   if (rc) return rc;
   // ---- mask_nl_class, mask_net
-  rc = srf_causal_prelu_bwd(gv, m, P[pt + 4], gv, G[pt + 4], (long)Bt * SAN * L, fp(s.pyr), st);      // gv = g_m
+  rc = srf_causal_prelu_bwd(gv, m, tl.out_prelu, gv, gtl.out_prelu, (long)Bt * SAN * L, fp(s.pyr), st);      // gv = g_m
   if (rc) return rc;
   float* gx = fp(s.gxa);
   float* gx_other = fp(s.gxb);
   {
-    srf_norm pre{nullptr, nullptr, nullptr, P[pt]};
-    rc = srf_pw_wgrad(gv, xbuf(U), &pre, Bt, B, SAN, L, G[pt + 1], G[pt + 2], 0, wg, stream);
+    srf_norm pre{nullptr, nullptr, nullptr, tl.mask_prelu};
+    rc = srf_pw_wgrad(gv, xbuf(U), &pre, Bt, B, SAN, L, gtl.mask_w, gtl.mask_b, 0, wg, stream);
     if (rc) return rc;
-    rc = data_grad(gv, P[pt + 1], pkT_mask, gx, SAN, B, nullptr);
+    rc = data_grad(gv, tl.mask_w, pkT_mask, gx, SAN, B, nullptr);
     if (rc) return rc;
-    rc = srf_causal_prelu_bwd(gx, xbuf(U), P[pt], gx, G[pt], (long)Bt * B * L, fp(s.pyr), st);
+    rc = srf_causal_prelu_bwd(gx, xbuf(U), tl.mask_prelu, gx, gtl.mask_prelu, (long)Bt * B * L, fp(s.pyr), st);
     if (rc) return rc;
   }
   // ---- blocks in reverse
@@ -373,50 +341,42 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   std::vector<long> bn;
   std::vector<float> bh;
   for (int i = U - 1; i >= 0; --i) {
-    const int pb = p->p_block0 + i * p->p_block_stride;
-    const float* const* Pb = P + pb;
-    float* const* Gb = G + pb;
+    const SrfCausalBlock<const float> b = causal_block<const float>(lay, P, i);
+    const SrfCausalBlock<float> g = causal_block<float>(lay, G, i);
     const char* blk = sv + t.blk0 + t.blk_stride * i;
     const float* u = (const float*)(blk + t.u);
     const float* merged = (const float*)(blk + t.merged);
     // res_conv in its folded form: dW_f, db_f now (scaled to dW_r, db_r and reduced to d gain after the loop), g_M = W_f^T g_x'
-    rc = srf_pw_wgrad(gx, merged, nullptr, Bt, C, B, L, Gb[4 + 3 * D], Gb[5 + 3 * D], 0, wg, stream);
+    rc = srf_pw_wgrad(gx, merged, nullptr, Bt, C, B, L, g.res_w, g.res_b, 0, wg, stream);
     if (rc) return rc;
-    g_dw[i] = Gb[4 + 3 * D]; g_db[i] = Gb[5 + 3 * D]; g_gain[i] = Gb[0];
-    p_w[i] = Pb[4 + 3 * D]; p_b[i] = Pb[5 + 3 * D]; p_gain[i] = Pb[0];
-    rc = data_grad(gx, wres[i], pkT_res[i], gm, B, C, nullptr);
+    g_dw[i] = g.res_w; g_db[i] = g.res_b; g_gain[i] = g.gain;
+    p_w[i] = b.res_w; p_b[i] = b.res_b; p_gain[i] = b.gain;
+    rc = data_grad(gx, w.wres[i], pkT_res[i], gm, B, C, nullptr);
     if (rc) return rc;
-    const float *dv[SRF_MAX_DEPTH], *wv[SRF_MAX_DEPTH], *av[SRF_MAX_DEPTH];
-    float *dwv[SRF_MAX_DEPTH], *dbv[SRF_MAX_DEPTH], *dsv[SRF_MAX_DEPTH];
-    for (int k = 0; k < D; ++k) {
-      dv[k] = (const float*)(blk + t.lv[k]);
-      wv[k] = Pb[4 + 3 * k];
-      av[k] = Pb[6 + 3 * k];
-      dwv[k] = Gb[4 + 3 * k];
-      dbv[k] = Gb[5 + 3 * k];
-      dsv[k] = Gb[6 + 3 * k];
-    }
+    const float* dv[SRF_MAX_DEPTH];
+    for (int k = 0; k < D; ++k) dv[k] = (const float*)(blk + t.lv[k]);
     if (fused) {
-      rc = srf_causal_pyramid_bwd(gm, u, dv, Pb[3], wv, av, gu, dwv, dbv, dsv, Gb[3], Bt, C, L, D, sc + s.pyr, stream);
+      rc = srf_causal_pyramid_bwd(gm, u, dv, b.proj_prelu, b.lv_w, b.lv_prelu, gu, g.lv_w, g.lv_b, g.lv_prelu, g.proj_prelu, Bt, C, L,
+                                  D, sc + s.pyr, stream);
       if (rc) return rc;
     } else {
       for (int k = D - 1; k >= 0; --k) {
-        rc = srf_causal_dwconv_bwd(gm, k, k < D - 1 ? fp(s.gd[k + 1]) : nullptr, k < D - 1 ? wv[k + 1] : nullptr, 2, dv[k], av[k],
-                                   k == 0 ? u : dv[k - 1], k == 0 ? Pb[3] : av[k - 1], k == 0 ? 1 : 2, fp(s.gd[k]), dwv[k], dbv[k],
-                                   dsv[k], Bt, C, L >> k, sc + s.pyr, stream);
+        rc = srf_causal_dwconv_bwd(gm, k, k < D - 1 ? fp(s.gd[k + 1]) : nullptr, k < D - 1 ? b.lv_w[k + 1] : nullptr, 2, dv[k],
+                                   b.lv_prelu[k], k == 0 ? u : dv[k - 1], k == 0 ? b.proj_prelu : b.lv_prelu[k - 1], k == 0 ? 1 : 2,
+                                   fp(s.gd[k]), g.lv_w[k], g.lv_b[k], g.lv_prelu[k], Bt, C, L >> k, sc + s.pyr, stream);
         if (rc) return rc;
       }
-      rc = srf_causal_dwconv_bwd(nullptr, 0, fp(s.gd[0]), wv[0], 1, u, Pb[3], nullptr, nullptr, 1, gu, nullptr, nullptr, Gb[3], Bt,
-                                 C, L, sc + s.pyr, stream);
+      rc = srf_causal_dwconv_bwd(nullptr, 0, fp(s.gd[0]), b.lv_w[0], 1, u, b.proj_prelu, nullptr, nullptr, 1, gu, nullptr, nullptr,
+                                 g.proj_prelu, Bt, C, L, sc + s.pyr, stream);
       if (rc) return rc;
     }
     // proj_1x1 (its weight ran as W_p / beta): dW_p = gu x^T / beta, db_p, g_x = g_x' + W_p^T gu / beta
-    rc = srf_pw_wgrad(gu, xbuf(i), nullptr, Bt, B, C, L, Gb[1], Gb[2], 0, wg, stream);
+    rc = srf_pw_wgrad(gu, xbuf(i), nullptr, Bt, B, C, L, g.proj_w, g.proj_b, 0, wg, stream);
     if (rc) return rc;
     if (p->beta[i] != 1.f) {
-      bsrc.push_back(Gb[1]); bdst.push_back(Gb[1]); bn.push_back((long)C * B); bscale.push_back(nullptr); bh.push_back(1.f / p->beta[i]);
+      bsrc.push_back(g.proj_w); bdst.push_back(g.proj_w); bn.push_back((long)C * B); bscale.push_back(nullptr); bh.push_back(1.f / p->beta[i]);
     }
-    rc = data_grad(gu, wproj[i], pkT_proj[i], gx_other, C, B, gx);
+    rc = data_grad(gu, w.wproj[i], pkT_proj[i], gx_other, C, B, gx);
     if (rc) return rc;
     float* tmp = gx;
     gx = gx_other;
@@ -424,15 +384,15 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   }
   // ---- bottleneck, encoder
   float* genc = fp(s.genc);
-  rc = srf_pw_wgrad(gx, enc, nullptr, Bt, N, B, L, G[1], G[2], 0, wg, stream);
+  rc = srf_pw_wgrad(gx, enc, nullptr, Bt, N, B, L, gf.bott_w, gf.bott_b, 0, wg, stream);
   if (rc) return rc;
-  rc = data_grad(gx, P[1], pkT_bott, genc, B, N, nullptr);
+  rc = data_grad(gx, f.bott_w, pkT_bott, genc, B, N, nullptr);
   if (rc) return rc;
   rc = srf_frames_gather(wav, frames, Bt, p->A, p->T, K, h, 2 * h, L, p->A * K, stream);
   if (rc) return rc;
   rc = srf_pw_wgrad(genc, frames, nullptr, Bt, p->A * K, N, L, fp(s.encw), nullptr, 0, wg, stream);
   if (rc) return rc;
-  rc = srf_causal_enc_scatter(fp(s.encw), G[0], N, p->A, K, st);
+  rc = srf_causal_enc_scatter(fp(s.encw), gf.enc_w, N, p->A, K, st);
   if (rc) return rc;
   // ---- every block's skipinit_gain / res_conv gradients and the 1 / beta of the proj_1x1 weight gradients
   std::vector<float> alpha(p->alpha.begin(), p->alpha.end());

@@ -53,6 +53,10 @@ int srf_mha_attention_strided(const float* q, const float* k, const float* v, fl
 struct srf_plan;
 int srf_attentive_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                           const float* wav_stats, int mixture_consistency, void* stream);
+// the Improved walk's mask + decoder tail (srf_api.hip), shared with the attentive walk; rg: forward_walk's ragged batch, else NULL
+struct Ragged;
+int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur, float* out, void* workspace, bool use_pack,
+                      const float* wav_stats, const float* wav, int mixture_consistency, const Ragged* rg, void* stream);
 
 // ---- srf_encoder.hip
 int srf_encoder_impl(const float* wav, const float* w, float* out, double* sums, int Bt, int A, int T, int N, int K, int L,

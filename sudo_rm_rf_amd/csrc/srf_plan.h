@@ -32,8 +32,8 @@ struct srf_plan {
 enum { SRF_PA_Q = 0, SRF_PA_K = 2, SRF_PA_V = 4, SRF_PA_O = 6, SRF_PA_OUT_NORM = 8, SRF_PA_MHA_NORM = 10, SRF_PA_FFN = 12,
        SRF_PA_FFN_NORM = 14, SRF_PA_FFN_PRELU = 16, SRF_PA_PE = 17, SRF_PA_COUNT = 18 };
 
-// ---- named views of the parameter table and of the GlobLN statistic slots (Improved / GroupComm layout; the causal variant
-// has its own).  state_dict order:
+// ---- named views of the parameter table and of the GlobLN statistic slots (Improved / GroupComm layout, which the attentive
+// variant extends; the causal variant's views follow below).  state_dict order:
 //   front   encoder.weight | ln.{gamma, beta} | bottleneck.{weight, bias}
 //   block   [GroupComm: the 11 TAC tensors, the last two TAC_norm.{gamma, beta}] | proj_1x1.conv.{weight, bias},
 //           proj_1x1.norm.{gamma, beta}, proj_1x1.act.weight | D x {conv.weight, conv.bias, norm.gamma, norm.beta} |
@@ -111,6 +111,105 @@ static inline SrfSlots plan_slots(const srf_plan* p, double* stats, int i) {
   for (int k = 0; k < p->cfg.upsampling_depth; ++k) v.level[k] = s + (1 + k) * each;
   v.merged = s + (1 + p->cfg.upsampling_depth) * each;
   return v;
+}
+
+// ---- causal variant (CausalSuDORMRF, causal_improved_sudormrf_v3.py).  state_dict order:
+//   front   encoder.weight | bottleneck.{weight, bias}
+//   block   skipinit_gain | proj_1x1.conv.{weight, bias}, proj_1x1.act.weight | D x spp_dw.k.{conv.weight, conv.bias, act.weight} |
+//           res_conv.{weight, bias}
+//   tail    mask_net.0.weight (PReLU) | mask_net.1.{weight, bias} | decoder.weight | mask_nl_class.weight (PReLU)
+// The ONE place that spells this layout out, for the plan and for the streaming session (srf_stream is no srf_plan: both go through
+// SrfCausalLayout).  The views take any table t with t[parameter index] -> T*.  T = const float: the parameters (an array of
+// pointers, or SrfOffsetTable over the session's prepared weights); T = float: the backward's gradients; T = long: element counts.
+enum { SRF_PC_BOTTLENECK = 1, SRF_PC_FRONT = 3, SRF_PC_PROJ = 1, SRF_PC_TAIL = 5 };
+// inside a block's run of tensors: conv.weight of level k (k = D: res_conv.weight)
+static inline int causal_u_level(int k) { return 4 + 3 * k; }
+struct SrfCausalLayout { int block0, stride, tail, n_params, D; };
+static inline SrfCausalLayout causal_layout(int U, int D) {
+  SrfCausalLayout y{SRF_PC_FRONT, causal_u_level(D) + 2, 0, 0, D};
+  y.tail = y.block0 + U * y.stride;
+  y.n_params = y.tail + SRF_PC_TAIL;
+  return y;
+}
+static inline SrfCausalLayout causal_layout(const srf_plan* p) { return causal_layout(p->cfg.num_blocks, p->cfg.upsampling_depth); }
+static inline int causal_p_proj(const SrfCausalLayout& y, int i) { return y.block0 + i * y.stride + SRF_PC_PROJ; }
+static inline int causal_p_res(const SrfCausalLayout& y, int i) { return y.block0 + i * y.stride + causal_u_level(y.D); }
+static inline int causal_p_mask(const SrfCausalLayout& y) { return y.tail + 1; }
+static inline int causal_p_dec(const SrfCausalLayout& y) { return y.tail + 3; }
+
+template <typename T> struct SrfOffsetTable {   // entry p at base + off[p]
+  T* base; const size_t* off;
+  T* operator[](int p) const { return base + off[p]; }
+};
+template <typename T> struct SrfCausalFront { T *enc_w, *bott_w, *bott_b; };
+template <typename T> struct SrfCausalTail { T *mask_prelu, *mask_w, *mask_b, *dec_w, *out_prelu; };
+template <typename T> struct SrfCausalBlock {
+  T *gain, *proj_w, *proj_b, *proj_prelu;
+  T *lv_w[SRF_MAX_DEPTH], *lv_b[SRF_MAX_DEPTH], *lv_prelu[SRF_MAX_DEPTH];   // (as srf_causal_pyramid* take them)
+  T *res_w, *res_b;
+  int i_proj, i_res;   // parameter indices of the two packable weights (pk_of_param)
+};
+template <typename T, typename Tab> static inline SrfCausalFront<T> causal_front(const Tab& t) {
+  return SrfCausalFront<T>{t[0], t[SRF_PC_BOTTLENECK], t[SRF_PC_BOTTLENECK + 1]};
+}
+template <typename T, typename Tab> static inline SrfCausalBlock<T> causal_block(const SrfCausalLayout& y, const Tab& t, int i) {
+  SrfCausalBlock<T> b{};
+  b.i_proj = causal_p_proj(y, i);
+  b.i_res = causal_p_res(y, i);
+  b.gain = t[b.i_proj - SRF_PC_PROJ];
+  b.proj_w = t[b.i_proj], b.proj_b = t[b.i_proj + 1], b.proj_prelu = t[b.i_proj + 2];
+  for (int k = 0; k < y.D; ++k) {
+    const int l = b.i_proj - SRF_PC_PROJ + causal_u_level(k);
+    b.lv_w[k] = t[l], b.lv_b[k] = t[l + 1], b.lv_prelu[k] = t[l + 2];
+  }
+  b.res_w = t[b.i_res], b.res_b = t[b.i_res + 1];
+  return b;
+}
+template <typename T, typename Tab> static inline SrfCausalTail<T> causal_tail(const SrfCausalLayout& y, const Tab& t) {
+  return SrfCausalTail<T>{t[y.tail], t[causal_p_mask(y)], t[y.tail + 2], t[causal_p_dec(y)], t[y.tail + 4]};
+}
+// one block's share of a fold region: res_conv weight * (skipinit_gain * alpha) [B][C] | its bias [B]   (each 64-float aligned)
+static inline size_t causal_fold_res_floats(int B, int C) { return srf_align_up((size_t)B * C, 64) + srf_align_up((size_t)B, 64); }
+// The weights a causal forward runs on, per block: res_conv weight and bias * (skipinit_gain * alpha) in fold_res (U x
+// causal_fold_res_floats) and, where beta != 1, proj_1x1 weight / beta in fold_proj (U x [C][B]); else the parameter itself.
+// One srf_causal_scale_many launch (srf_api.hip).
+struct SrfCausalFolded { std::vector<const float*> wproj, wres, bres; };
+int srf_causal_fold(const srf_plan* p, const float* const* P, float* fold_res, float* fold_proj, SrfCausalFolded* out, hipStream_t st);
+
+// ---- the packed (split-bf16) weight images of a plan
+// parameter index -> (block, index inside the block's run of tensors); block = -1 outside the blocks
+struct SrfBlockParam { int block, rel; };
+static inline SrfBlockParam plan_block_param(int block0, int stride, int tail, int param) {
+  if (param < block0 || param >= tail) return SrfBlockParam{-1, 0};
+  return SrfBlockParam{(param - block0) / stride, (param - block0) % stride};
+}
+// A packed image of parameter `param` ([cout, cin]) in the workspace, for the shapes the 256 x 128 GEMM supports
+static inline void plan_add_pack(srf_plan* p, size_t* off, int param, int cout, int cin) {
+  const size_t bytes = srf_packed_pw_weight_bytes(cout, cin);
+  if (!bytes) return;
+  const size_t o = *off;
+  *off = srf_align_up(*off + bytes, 256);
+  p->pk_param.push_back(param);
+  p->pk_cout.push_back(cout);
+  p->pk_cin.push_back(cin);
+  p->pk_off.push_back(o);
+  p->pk_of_param[param] = o;
+}
+static inline const void* plan_packed(const srf_plan* p, const char* ws, bool use_pack, int param) {
+  return (use_pack && p->pk_of_param[param]) ? (const void*)(ws + p->pk_of_param[param]) : nullptr;
+}
+// split + lay out every packable 1x1 weight for the 256 x 128 split-precision GEMMs (srf_pwconv_x3w.hip / _x3p.hip), one launch
+// per forward.  source(parameter index): the fp32 weight that goes into the image (the causal forward: its folded copies; the
+// attentive one: its concatenated Q/K/V weights)
+template <typename F>
+static inline int plan_pack_weights(const srf_plan* p, F source, char* ws, void* stream) {
+  std::vector<const float*> pw(p->pk_param.size());
+  std::vector<void*> pd(p->pk_param.size());
+  for (size_t i = 0; i < p->pk_param.size(); ++i) {
+    pw[i] = source(p->pk_param[i]);
+    pd[i] = ws + p->pk_off[i];
+  }
+  return srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
 }
 
 // ---- dispatch decisions of a forward.  They depend on the kernel mode and the debug flags at CALL time, so they are

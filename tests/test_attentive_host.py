@@ -256,3 +256,20 @@ def test_wide_reference_for_64_examples_is_affordable():
     assert y.shape == (64, 2, af.WIDE_T) and bool(torch.isfinite(y).all())
     assert float(peak.max()) >= 0.1          # (the outputs are of a size at which 1e-4 absolute means something)
     assert dt < 60.0
+
+
+# ---- byte and count literals --------------------------------------------------------------------------------------------------
+# (workspace bytes, parameters, launches) of the plans of the two fixtures, recorded on commit 13ee426: the commit BEFORE the
+# attentive plan constructor took plan_add_pack from srf_plan.h and the walk the shared pack helpers and tail.
+SIZE_CASES = {"tiny": (af.TINY, 2, 1001), "wide": (af.WIDE, 8, af.WIDE_T)}
+PLAN_SIZES = {"tiny": (2940416, 89, 34), "wide": (92263168, 81, 32)}
+
+
+def plan_sizes(name):
+    p = _plan(*SIZE_CASES[name])
+    return p.workspace_bytes, p.num_params, p.num_launches
+
+
+@pytest.mark.parametrize("name", sorted(SIZE_CASES))
+def test_plan_sizes_are_what_they_were(name):
+    assert plan_sizes(name) == PLAN_SIZES[name]

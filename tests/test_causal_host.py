@@ -1,5 +1,6 @@
 """Causal SuDoRM-RF (v3) on the host: module schema, seeded weights and pickles against fixtures made by the reference
-(tools/make_golden_causal.py), plan geometry and the refusals.  No GPU needed."""
+(tools/make_golden_causal.py), plan geometry, the refusals and every byte count / launch count of a plan and of a streaming
+session as literals.  No GPU needed."""
 import ctypes as C
 import hashlib
 import os
@@ -128,3 +129,51 @@ def test_training_is_refused_before_anything_runs():
         assert getattr(lib, fn)(*args) == -1 and b"causal" in lib.srf_last_error()
     rc = lib.srf_separate(p.handle, None, 0, C.c_void_p(16), None, C.c_void_p(16), 0, None, 0, None)
     assert rc == -1 and b"causal" in lib.srf_last_error()
+
+
+# ---- byte and count literals ------------------------------------------------------------------------------------------------
+# Recorded on commit 13ee426, the commit BEFORE causal_plan_create, the training layouts and srf_stream_create took the causal
+# parameter layout from srf_plan.h: whatever spells the layout, these numbers stay.
+SIZE_CASES = ("causal_tiny", "causal_tiny_a2_k11", "causal_default", "causal_main")      # TINY, TINY_A2, DEFAULTS, MAIN
+PLAN_SIZES = {      # (workspace bytes, parameters, launches, frames, training saved bytes, training scratch bytes)
+    "causal_tiny": (502784, 38, 15, 104, 638976, 705792),
+    "causal_tiny_a2_k11": (1636608, 32, 15, 156, 1857024, 2754816),
+    "causal_default": (213487872, 296, 57, 3200, 1815347200, 237105408),
+    "causal_main": (109876736, 92, 21, 4416, 210272256, 138257920),
+}
+STREAM_SIZES = {      # (weights, state, workspace) bytes of a session at the case's batch, max_chunk_samples = 4 granules
+    "causal_tiny": (128000, 31232, 54528),
+    "causal_tiny_a2_k11": (230144, 31488, 67840),
+    "causal_default": (12385280, 5243904, 1463296),
+    "causal_main": (8602112, 410112, 1070080),
+}
+
+
+def plan_sizes(name):
+    """(workspace bytes, parameters, launches, frames, training saved bytes, training scratch bytes) at the case's batch and T"""
+    from sudo_rm_rf_amd import _lib
+    cfg, batch, T = cf.CASES[name][:3]
+    p = _plan(cfg, batch, T)
+    lib = _lib.load()
+    return (p.workspace_bytes, p.num_params, p.num_launches, p.frames, lib.srf_causal_train_saved_bytes(p.handle),
+            lib.srf_causal_train_scratch_bytes(p.handle))
+
+
+def stream_sizes(name):
+    """(weights, state, workspace) bytes of a session of the case's configuration and batch at max_chunk_samples = 4 granules"""
+    from sudo_rm_rf_amd.streaming import _Session
+    cfg, batch = cf.CASES[name][:2]
+    g = (cfg["enc_kernel_size"] // 2) << (cfg["upsampling_depth"] - 1)
+    s = _Session(("causal",) + tuple(cfg[f] for f in cf.FIELDS) + (1,), batch, 4 * g)
+    assert s.granule == g
+    return s.weights_bytes, s.state_bytes, s.workspace_bytes
+
+
+@pytest.mark.parametrize("name", SIZE_CASES)
+def test_plan_and_training_sizes_are_what_they_were(name):
+    assert plan_sizes(name) == PLAN_SIZES[name]
+
+
+@pytest.mark.parametrize("name", SIZE_CASES)
+def test_stream_session_sizes_are_what_they_were(name):
+    assert stream_sizes(name) == STREAM_SIZES[name]

@@ -1,6 +1,7 @@
 """Causal SuDoRM-RF (v3) on the MI355X: reference parity of every fixture (tests/golden/CAUSAL_MANIFEST.json, made by
 tools/make_golden_causal.py from the reference), the dispatch at the bench shape, fused vs per-level vs a CPU restatement,
-bit-exact causality, batch independence, the stand-alone block and the training refusal."""
+bit-exact causality, batch independence, the stand-alone block, the training refusal and the smallest shape that runs res_conv
+of one block and proj_1x1 of the next as one launch."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +10,8 @@ import torch
 import torch.nn.functional as F
 
 from tests import causal_fixtures as cf
+from tests import causal_train_ref as ctr
+from tests.causal_stream_ref import StreamRef, schedule_chunks
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -245,3 +248,112 @@ def test_training_is_refused(dev):
                                _lib.ptr(buf), buf.numel(), _lib.current_stream(dev))
     with pytest.raises(_lib.SrfError, match="causal"):
         _lib.check(rc, "srf_forward_train")
+
+
+# ---- res_conv of block i + proj_1x1 of block i + 1 as ONE launch (srf_pw_conv_pair) ---------------------------------------
+# causal_forward takes that branch only for out_channels = 256 and batch x ceil(L / 128) tiles >= the CU count: no fixture gets
+# there (causal_main: batch 1, 35 tiles; the bench shape: out_channels = 128).  The smallest shape that does: in_channels = 256
+# (the least C with C % 128 == 0 and C >= 192, what the 256 x 128 kernel asks of a Cout), L = 4096 frames, batch 8 = 256 tiles.
+# The block scales pack both a folded proj_1x1 copy (beta != 1) and an unfolded one.
+PAIR_CFG = dict(in_audio_channels=1, out_channels=256, in_channels=256, num_blocks=3, upsampling_depth=2, enc_kernel_size=21,
+                enc_num_basis=128, num_sources=2)
+PAIR_SEED, PAIR_BATCH, PAIR_T = 106, 8, 40960
+PAIR_SCALES = ((0.7, 1.3), (1.2, 0.8), (1.0, 1.0))
+# Reference: tests/causal_train_ref.py in fp64; max|out| = 0.096 here, its own fp32 evaluation differs from it by 8.0e-8.  The
+# file's absolute TOL would be 0.1 % of full scale, so the bar is relative: 1e-4 x max|reference| (about 1e-5).  Measured on commit
+# 13ee426 (before the causal walks took the named views of srf_plan.h), MI355X: max|hip - reference| = 9.7e-7
+# (flags 0 and NO_PAIRS alike), 8.1e-7 in training mode, 2.3e-8 streamed: a tenth of the bar, which therefore stays as it is.
+PAIR_REL_TOL = 1e-4
+PAIR_LAUNCH = "pw_pair_x3f<0>"      # the pair launch's name in the in-library trace, recorded on the same commit
+
+
+def pair_model(dev):
+    m = _model(None, dev, PAIR_CFG, PAIR_SEED)
+    for blk, (alpha, beta) in zip(m.sm, PAIR_SCALES):
+        blk.alpha, blk.beta = alpha, beta
+    return m
+
+
+@pytest.fixture(scope="module")
+def pair_case(dev):
+    """(model, input on the device, fp64 reference output, bar): computed once, shared, never written to"""
+    from oracle.weights import make_mixture
+    sd = cf.make_state_dict(PAIR_CFG, PAIR_SEED)
+    wav = make_mixture(PAIR_BATCH, PAIR_T, PAIR_SEED)
+    with torch.no_grad():
+        want = ctr.forward(PAIR_CFG, {k: torch.from_numpy(v).double() for k, v in sd.items()}, torch.from_numpy(wav).double(),
+                           list(PAIR_SCALES)).numpy()
+    assert ctr.padded_length(PAIR_CFG, PAIR_T) // (PAIR_CFG["enc_kernel_size"] // 2) == 4096
+    return pair_model(dev), torch.from_numpy(wav).to(dev), want, PAIR_REL_TOL * float(np.abs(want).max())
+
+
+def pair_trace(m, x, flags=0):
+    """(output, launch names in order) of one single-stream forward under debug flags"""
+    from sudo_rm_rf_amd import ops
+    eng = m._engine()
+    eng.multi_stream = False
+    try:
+        with torch.no_grad(), ops.debug_flags(flags), ops.kernel_trace(x.device) as tr:
+            out = m(x)
+        torch.cuda.synchronize()
+    finally:
+        eng.multi_stream = True
+    return out, [n for n, _ in tr.launches]
+
+
+def test_pair_branch_parity_and_launches(dev, pair_case):
+    from sudo_rm_rf_amd import ops
+    m, x, want, bar = pair_case
+    tiles = PAIR_BATCH * 4096 // 128
+    assert tiles >= torch.cuda.get_device_properties(dev).multi_processor_count, "the pair needs as many tiles as CUs"
+    out, names = pair_trace(m, x)
+    err = float(np.abs(out.cpu().numpy() - want).max())
+    print("pair case: max|hip - fp64 reference| = %.3e, bar %.3e (max|ref| %.4f)" % (err, bar, np.abs(want).max()))
+    assert names.count(PAIR_LAUNCH) == PAIR_CFG["num_blocks"] - 1, names
+    assert err <= bar
+    out1, names1 = pair_trace(m, x, int(ops.DebugFlag.NO_PAIRS))
+    err1 = float(np.abs(out1.cpu().numpy() - want).max())
+    print("pair case under NO_PAIRS: max|hip - fp64 reference| = %.3e" % err1)
+    assert not [n for n in names1 if n.startswith("pw_pair")], names1
+    assert err1 <= bar
+    # the two-stream engine path (what a caller gets by default) agrees as well
+    with torch.no_grad():
+        err2 = float(np.abs(_run(m, x).cpu().numpy() - want).max())
+    assert err2 <= bar, err2
+
+
+def test_pair_case_in_training_mode(dev, pair_case):
+    _, x, want, bar = pair_case
+    m = pair_model(dev).train().enable_hip_training()
+    out = m(x)
+    torch.cuda.synchronize()
+    assert out.requires_grad
+    err = float(np.abs(out.detach().cpu().numpy() - want).max())
+    print("pair case, training mode: max|hip - fp64 reference| = %.3e, bar %.3e" % (err, bar))
+    assert err <= bar
+
+
+def test_pair_case_streamed_in_four_granule_chunks(dev, pair_case):
+    """A session pushed in 4 x granule chunks against the fp64 recurrence (tests/causal_stream_ref.py, which has no block scales:
+    alpha and 1 / beta go into its res_conv and proj_1x1 weights in fp64, as the definition has them)."""
+    m, x, _, bar = pair_case
+    sd = {k: torch.from_numpy(v).double() for k, v in cf.make_state_dict(PAIR_CFG, PAIR_SEED).items()}
+    for i, (alpha, beta) in enumerate(PAIR_SCALES):
+        p = "sm.%d." % i
+        sd[p + "proj_1x1.conv.weight"] = sd[p + "proj_1x1.conv.weight"] / beta
+        sd[p + "res_conv.weight"] = sd[p + "res_conv.weight"] * alpha
+        sd[p + "res_conv.bias"] = sd[p + "res_conv.bias"] * alpha
+    ref = StreamRef(PAIR_CFG, sd, PAIR_BATCH)
+    xc = x.cpu()
+    with torch.no_grad():
+        want = torch.cat([ref.push(xc), ref.finish()], dim=-1).numpy()       # (the recurrence does not depend on the schedule)
+        s = m.stream(batch=PAIR_BATCH, max_chunk=4 * ref.granule)
+        assert s.granule == ref.granule == 20
+        outs = [s.push(x[..., a:b]) for a, b in schedule_chunks(PAIR_T, (4 * s.granule,))]
+        outs.append(s.finish())
+        torch.cuda.synchronize()
+    got = torch.cat(outs, dim=-1).cpu().numpy()
+    assert got.shape == want.shape == (PAIR_BATCH, 2, PAIR_T)
+    err = float(np.abs(got - want).max())
+    print("pair case, streamed in 4-granule chunks: max|stream - StreamRef| = %.3e, bar %.3e" % (err, bar))
+    assert err <= bar

@@ -13,12 +13,19 @@ and the fused pyramid away, and the training step at the shape of the golden cas
 
 Training steps (forward + backward; "train ..." below): srf_backward chooses every block's pyramid path -- chunked / row
 kernels, apply-on-load, the fused head -- from L, D, the kernel mode, the debug flags and its forward's record.  TRAIN_SHAPES are
-the smallest shapes that reach each of those paths, recorded on the commit BEFORE the path became a table."""
+the smallest shapes that reach each of those paths, recorded on the commit BEFORE the path became a table.
+
+Causal (v3) and attentive (v2) walks ("causal ...", "attentive ..." below): the forward, one opted-in training step and one
+streamed granule of the causal model, the attentive forward at the shapes of its two fixtures, and the causal shape that runs
+res_conv + proj_1x1 as one launch (tests/test_gpu_causal.py, PAIR_CASE).  Recorded on commit 13ee426, the commit BEFORE these walks
+took their parameters through the named views of srf_plan.h and shared their weight fold, pack helpers and tail."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import load_case
+from tests import attentive_fixtures as af
+from tests import causal_fixtures as cf
 from oracle import weights
 from oracle.schema import ModelConfig
 from test_gpu_model import build
@@ -123,6 +130,103 @@ def train_step_trace(shape, setting):
     finally:
         ops.set_kernel_mode(0)
     return [n for n, _ in tr.launches]
+
+
+def _setting(setting):
+    """(debug flags, kernel mode) of a setting: "0", a DebugFlag name, or kernel mode 1"""
+    from sudo_rm_rf_amd import ops
+    if setting == "kernel_mode_1":
+        return 0, 1
+    return (0 if setting == "0" else int(getattr(ops.DebugFlag, setting))), 0
+
+
+def causal_model(cfg, seed, scales=None):
+    from sudo_rm_rf_amd.dnn.models.causal_improved_sudormrf_v3 import CausalSuDORMRF
+    m = CausalSuDORMRF(**cfg)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in cf.make_state_dict(cfg, seed).items()})
+    for blk, (alpha, beta) in zip(m.sm, scales or ()):
+        blk.alpha, blk.beta = alpha, beta
+    return m.to(DEV).eval()
+
+
+def causal_forward_trace(m, x, setting="0"):
+    from sudo_rm_rf_amd import ops
+    flags, mode = _setting(setting)
+    try:
+        ops.set_kernel_mode(mode)
+        return _forward_trace(m, x, flags)
+    finally:
+        ops.set_kernel_mode(0)
+
+
+def causal_case_trace(name, setting="0"):
+    cfg, _, _, wseed, _, _ = cf.CASES[name]
+    return causal_forward_trace(causal_model(cfg, wseed), torch.from_numpy(cf.make_input(name)).to(DEV), setting)
+
+
+def causal_train_step_trace(setting):
+    """one opted-in training step (forward + backward of (out * out).mean()) of cf.TINY at batch 2, T = 1001"""
+    from sudo_rm_rf_amd import ops
+    m = causal_model(cf.TINY, cf.CASES["causal_tiny"][3]).train().enable_hip_training()
+    x = torch.from_numpy(cf.make_input("causal_tiny")).to(DEV)
+    assert tuple(x.shape) == (2, 1, 1001)
+    flags, mode = _setting(setting)
+    try:
+        ops.set_kernel_mode(mode)
+        with ops.debug_flags(flags), ops.kernel_trace(DEV) as tr:
+            out = m(x)
+            (out * out).mean().backward()
+    finally:
+        ops.set_kernel_mode(0)
+    return [n for n, _ in tr.launches]
+
+
+def causal_stream_push_trace():
+    """one srf_stream_push of one granule per stream, on a session of causal_tiny's model and batch"""
+    from sudo_rm_rf_amd import ops
+    cfg, batch, _, wseed, _, _ = cf.CASES["causal_tiny"]
+    m = causal_model(cfg, wseed)
+    with torch.no_grad():
+        s = m.stream(batch=batch)
+        x = torch.from_numpy(cf.make_input("causal_tiny")[..., :s.granule]).to(DEV).contiguous()
+        with ops.kernel_trace(DEV) as tr:
+            s.push(x)
+    return [n for n, _ in tr.launches]
+
+
+def causal_pair_trace(flags):
+    """the shape of tests/test_gpu_causal.py that runs res_conv + the next block's proj_1x1 as one launch"""
+    from oracle.weights import make_mixture
+    from tests import test_gpu_causal as tgc
+    x = torch.from_numpy(make_mixture(tgc.PAIR_BATCH, tgc.PAIR_T, tgc.PAIR_SEED)).to(DEV)
+    return tgc.pair_trace(tgc.pair_model(torch.device(DEV)), x, flags)[1]
+
+
+def attentive_trace(cfg, wseed, wav):
+    from sudo_rm_rf_amd import ops
+    from sudo_rm_rf_amd.dnn.models.attentive_sudormrf_v2 import SuDORMRF
+    m = SuDORMRF(**cfg)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in af.make_state_dict(cfg, wseed).items()})
+    m = m.to(DEV).eval()
+    with torch.no_grad(), ops.kernel_trace(DEV) as tr:
+        m(torch.from_numpy(wav).to(DEV))
+    return [n for n, _ in tr.launches]
+
+
+CAUSAL_TRACES = {
+    "causal_tiny 0": lambda: causal_case_trace("causal_tiny"),
+    "causal_tiny PYR_PER_LEVEL": lambda: causal_case_trace("causal_tiny", "PYR_PER_LEVEL"),
+    "causal_tiny kernel_mode_1": lambda: causal_case_trace("causal_tiny", "kernel_mode_1"),
+    "causal_tiny_a2_k11 0": lambda: causal_case_trace("causal_tiny_a2_k11"),
+    "causal train 0": lambda: causal_train_step_trace("0"),
+    "causal train PYR_PER_LEVEL": lambda: causal_train_step_trace("PYR_PER_LEVEL"),
+    "causal train kernel_mode_1": lambda: causal_train_step_trace("kernel_mode_1"),
+    "causal stream push": causal_stream_push_trace,
+    "attentive tiny": lambda: attentive_trace(af.TINY, af.CASES["attn_tiny"][3], af.make_input("attn_tiny")),
+    "causal pair 0": lambda: causal_pair_trace(0),
+    "causal pair NO_PAIRS": lambda: causal_pair_trace(1),
+    "attentive wide batch 8": lambda: attentive_trace(af.WIDE, af.WIDE_WSEED, af.make_distinct(8, af.WIDE_T, af.WIDE_INPUT_SEED)),
+}
 
 
 EXPECTED = {
@@ -305,6 +409,95 @@ EXPECTED = {
 }
 
 
+EXPECTED.update({      # recorded on commit 13ee426
+    "causal_tiny 0": [      # 14 launches
+        (("causal_scale", "causal_encoder", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_small", "causal_pyramid", "pw_conv_bf16x3_w4"), 2),
+        (("pw_conv_mfma", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add"), 1),
+    ],
+    "causal_tiny PYR_PER_LEVEL": [      # 20 launches
+        (("causal_scale", "causal_encoder", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_small", "causal_dwconv", "causal_dwconv", "causal_dwconv", "causal_merge", "pw_conv_bf16x3_w4"), 2),
+        (("pw_conv_mfma", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add"), 1),
+    ],
+    "causal_tiny kernel_mode_1": [      # 20 launches
+        (("causal_scale", "causal_encoder", "pw_conv_generic"), 1),
+        (("pw_conv_generic", "causal_dwconv", "causal_dwconv", "causal_dwconv", "causal_merge", "pw_conv_generic"), 2),
+        (("pw_conv_generic", "transpose", "zero_fill", "pw_conv_generic", "overlap_add"), 1),
+    ],
+    "causal_tiny_a2_k11 0": [      # 14 launches
+        (("causal_scale", "causal_encoder", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_small", "causal_pyramid", "pw_conv_bf16x3_w4"), 2),
+        (("pw_conv_mfma", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add"), 1),
+    ],
+    "causal train 0": [      # 66 launches
+        (("causal_scale", "causal_encoder", "pw_conv_mfma"), 1),
+        (("pw_conv_small", "causal_dwconv", "causal_dwconv", "causal_dwconv", "causal_merge_act", "pw_conv_mfma"), 2),
+        (("pw_conv_mfma", "prelu_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "causal_scale",
+          "frames_gather", "prelu_apply", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "causal_prelu_bwd",
+          "causal_prelu_fold", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "causal_prelu_bwd",
+          "causal_prelu_fold"), 1),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "causal_pyramid_bwd", "causal_bwd_finalize",
+          "causal_bwd_slope", "pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 2),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "frames_gather", "pw_wgrad", "pw_wgrad_reduce",
+          "causal_enc_scatter", "causal_gain_fold"), 1),
+    ],
+    "causal train PYR_PER_LEVEL": [      # 84 launches
+        (("causal_scale", "causal_encoder", "pw_conv_mfma"), 1),
+        (("pw_conv_small", "causal_dwconv", "causal_dwconv", "causal_dwconv", "causal_merge_act", "pw_conv_mfma"), 2),
+        (("pw_conv_mfma", "prelu_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "causal_scale",
+          "frames_gather", "prelu_apply", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "causal_prelu_bwd",
+          "causal_prelu_fold", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "causal_prelu_bwd",
+          "causal_prelu_fold"), 1),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small") +
+         ("causal_dw_bwd", "causal_bwd_finalize", "causal_bwd_slope") * 4 +
+         ("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 2),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "frames_gather", "pw_wgrad", "pw_wgrad_reduce",
+          "causal_enc_scatter", "causal_gain_fold"), 1),
+    ],
+    "causal train kernel_mode_1": [      # 84 launches
+        (("causal_scale", "causal_encoder", "pw_conv_generic"), 1),
+        (("pw_conv_generic", "causal_dwconv", "causal_dwconv", "causal_dwconv", "causal_merge_act", "pw_conv_generic"), 2),
+        (("pw_conv_generic", "prelu_apply", "transpose", "zero_fill", "pw_conv_generic", "overlap_add", "causal_scale",
+          "frames_gather", "prelu_apply", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_generic", "causal_prelu_bwd",
+          "causal_prelu_fold", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "causal_prelu_bwd",
+          "causal_prelu_fold"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic") +
+         ("causal_dw_bwd", "causal_bwd_finalize", "causal_bwd_slope") * 4 +
+         ("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic"), 2),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "frames_gather", "pw_wgrad", "pw_wgrad_reduce",
+          "causal_enc_scatter", "causal_gain_fold"), 1),
+    ],
+    "causal stream push": [      # 11 launches
+        (("stream_encoder", "stream_pw"), 1),
+        (("stream_pw", "stream_pyramid", "stream_pw"), 2),
+        (("stream_pw", "stream_pw", "stream_ola"), 1),
+    ],
+    "causal pair 0": [      # 16 launches
+        (("causal_scale", "pack_pw_weights", "causal_encoder", "pw_conv_x3p<0>", "pw_conv_x3p<0>"), 1),
+        (("causal_pyramid", "pw_pair_x3f<0>"), 2),
+        (("causal_pyramid", "pw_conv_x3p<0>", "pw_conv_x3p<3>", "transpose", "zero_fill", "pw_conv_bf16x3_w8", "overlap_add"), 1),
+    ],
+    "causal pair NO_PAIRS": [      # 18 launches
+        (("causal_scale", "pack_pw_weights", "causal_encoder", "pw_conv_x3p<0>"), 1),
+        (("pw_conv_x3p<0>", "causal_pyramid", "pw_conv_x3p<0>"), 3),
+        (("pw_conv_x3p<3>", "transpose", "zero_fill", "pw_conv_bf16x3_w8", "overlap_add"), 1),
+    ],
+    "attentive tiny": [      # 33 launches
+        (("zero_fill", "causal_scale", "encoder", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_small", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_generic", "posenc_apply", "pw_conv_generic",
+          "mha_attention_mfma", "pw_conv_generic", "pw_conv_generic", "gln_apply2_add", "merge_fast", "pw_conv_bf16x3_w4"), 2),
+        (("pw_conv_mfma", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add"), 1),
+    ],
+    "attentive wide batch 8": [      # 32 launches
+        (("zero_fill", "causal_scale", "pack_pw_weights", "encoder", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_bf16x3_w4", "dwconv5_s1_fast", "dwconv5_s2_fast", "posenc_apply", "pw_conv_bf16x3_w8", "mha_attention_mfma",
+          "pw_conv_bf16x3_w4", "pw_conv_bf16x3_w4", "gln_apply2_add", "merge_fast", "pw_conv_bf16x3_w4"), 2),
+        (("pw_conv_bf16x3_w4", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add"), 1),
+    ],
+})
+
+
 def _check(name, got):
     want = _expand(EXPECTED[name])
     first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
@@ -328,3 +521,8 @@ def test_launch_sequence_cfg2_under_debug_flags(cfg2, flags):
 @pytest.mark.parametrize("shape,setting", TRAIN_STEPS, ids=["%s-%s" % s for s in TRAIN_STEPS])
 def test_launch_sequence_of_a_training_step(shape, setting):
     _check("train %s %s" % (shape, setting), train_step_trace(shape, setting))
+
+
+@pytest.mark.parametrize("name", list(CAUSAL_TRACES))
+def test_launch_sequence_of_the_causal_and_attentive_walks(name):
+    _check(name, CAUSAL_TRACES[name]())
