@@ -1,6 +1,6 @@
 /*
  * sudormrf_hip.h -- C ABI of libsudormrf_hip.so, the MI355X (gfx950) hot path of
- * SuDoRM-RF (Improved SuDORMRF, GroupComm SuDoRM-RF v2, Causal SuDORMRF v3 and attentive SuDORMRF v2) inference forward.
+ * SuDoRM-RF (Improved SuDORMRF, GroupComm SuDoRM-RF v2, Causal SuDORMRF v3 and attentive SuDORMRF v2 / v3) inference forward.
  *
  * Boundary replaced (reference is pure PyTorch, paths relative to
  * /root/reference/sudo_rm_rf/dnn/):
@@ -23,6 +23,7 @@
  *   srf_perm_inv_sisdr     <- PermInvariantSISDR.forward (validation metric)        losses/sisdr.py:66-196
  *   srf_forward (causal)   <- CausalSuDORMRF.forward      models/causal_improved_sudormrf_v3.py (ABI 16)
  *   srf_forward (attentive)<- SuDORMRF.forward             models/attentive_sudormrf_v2.py (srf_attentive_plan_create, below)
+ *   srf_forward (att. v3)  <- SuDORMRF.forward             models/attentive_sudormrf_v3.py (srf_attentive_v3_plan_create, below)
  *   srf_mha_attention      <- MHAttentionLayer.forward: softmax(q k^T / sqrt(d)) v per head, between its four Linear layers
  *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17; row-table push: ABI 19)
  *   srf_zeroref_snr_*      <- PermInvariantSNRwithZeroRefs fwd/bwd (FUSS training loss)  losses/snr.py:13-142 (ABI 18)
@@ -940,6 +941,29 @@ int srf_posenc_apply(const float* a, const srf_norm* norm, const float* pe, floa
                      void* stream);
 int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z, double* out_sums,
                        int groups, int channels, int length, void* stream);
+
+/* ---- Attentive SuDoRM-RF v3 (additive to ABI 19; attentive_sudormrf_v3.py) ----
+ * The Improved model's front end and tail around blocks WITHOUT an upsample-and-add: the depthwise pyramid's levels are folded
+ * from the deepest up by D - 1 ConditionalTransformerLayers ("attentive resamplers": the shallower level asks, the deeper one --
+ * with its own position table added -- answers), and final_norm sits on the last one's out_norm.  Inference only.
+ * srf_attentive_v3_plan_create: arguments and padding (lcm(K / 2, 2^D)) as srf_attentive_plan_create.  Level k + 1 has
+ *   ceil(L_k / 2) positions -- the strided convolution's own arithmetic; no divisibility is asked of the frame count -- and
+ *   upsampling_depth = 1 is legal (no resampler: final_norm on spp_dw[0]'s GlobLN).  The plan works with srf_forward,
+ *   srf_separate, srf_plan_workspace_bytes / _num_params / _frames / _padded_length and the profiler.  Parameters in state_dict()
+ *   order, per block: the Improved block's tensors, then attentive_resamplers.0 .. D-2, each the 18 tensors listed for v2 above
+ *   (resampler r asks from level D - 2 - r: resampler 0 serves the DEEPEST pair).  Refused before anything is launched
+ *   (SRF_EINVAL, the message names the argument): more than SRF_ATT_MAX_LEN positions on level 1 (the table is added to the
+ *   answering side), a level with fewer than 1 position, n_heads / att_dims < 1, in_audio_channels or group_size != 1,
+ *   upsampling_depth > 8; srf_forward_train, srf_backward(_wav) and srf_forward_ragged / srf_separate_ragged refuse
+ *   such a plan, srf_plan_ragged_supported is 0.
+ * srf_gln_apply_stats: y = norm(x), a GlobLN (+ PReLU where norm->prelu is set) from norm->sums; out_sums (nullable) += {sum,
+ *   sumsq} of the STORED y in the bucket scheme of every other statistics producer (the moments of an already-normalised tensor,
+ *   which a second GlobLN on top needs and which do not follow from x's sums).  x, y: [groups, channels, length] at any
+ *   float-aligned address, any length; x and y do not overlap. */
+#define SRF_VARIANT_ATTENTIVE_V3 4
+int srf_attentive_v3_plan_create(const srf_config* base, int n_heads, int att_dims, int batch, int T, srf_plan** out);
+int srf_gln_apply_stats(const float* x, const srf_norm* norm, float* y, double* out_sums, int groups, int channels, int length,
+                        void* stream);
 
 #ifdef __cplusplus
 }

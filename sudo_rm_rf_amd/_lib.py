@@ -17,7 +17,7 @@ RAGGED_MAX_BATCH = 128     # SRF_RAGGED_MAX_BATCH
 STAT_BUCKETS = 64
 
 SRF_OK = 0
-VARIANT_IMPROVED, VARIANT_GROUPCOMM, VARIANT_CAUSAL, VARIANT_ATTENTIVE = 0, 1, 2, 3
+VARIANT_IMPROVED, VARIANT_GROUPCOMM, VARIANT_CAUSAL, VARIANT_ATTENTIVE, VARIANT_ATTENTIVE_V3 = 0, 1, 2, 3, 4
 ATT_MAX_LEN = 5000         # SRF_ATT_MAX_LEN
 
 
@@ -207,6 +207,8 @@ _PROTOS = {
     "srf_mha_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp]),
     "srf_posenc_apply": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _i, _vp]),
     "srf_gln_apply2_add": (_i, [_vp, C.POINTER(srf_norm), _vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _vp]),
+    "srf_attentive_v3_plan_create": (_i, [C.POINTER(srf_config), _i, _i, _i, _i, C.POINTER(_vp)]),
+    "srf_gln_apply_stats": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

@@ -1,7 +1,7 @@
-"""Thin ctypes wrappers of the attention kernels (csrc/srf_attention.hip; include/sudormrf_hip.h, "Attentive SuDoRM-RF v2").
+"""Thin ctypes wrappers of the attention kernels (csrc/srf_attention.hip; include/sudormrf_hip.h, "Attentive SuDoRM-RF v2" / "v3").
 
 Same conventions as ``ops``: CUDA float32 tensors in, new tensors out, torch's current stream.  Kept out of ``ops`` on
-purpose: these serve the attentive model's sub-module forwards and the kernel tests only."""
+purpose: these serve the attentive models' sub-module forwards and the kernel tests only."""
 import ctypes as C
 import math
 
@@ -58,4 +58,16 @@ def gln_apply2_add(f, f_sums, f_gamma, f_beta, f_prelu, y, y_sums, y_gamma, y_be
                                         _norm(y_sums, y_gamma, y_beta, y_prelu), _lib.ptr(out), _lib.ptr(out_sums), groups,
                                         channels, length, _lib.current_stream(dev))
     _lib.check(rc, "srf_gln_apply2_add")
+    return out
+
+
+def gln_apply_stats(x, sums, gamma, beta, prelu=None, out_sums=None, out=None):
+    """y = GlobLN(x) from `sums` (+ PReLU where a slope is given); out_sums += {sum, sumsq} of the stored y."""
+    dev = _chk(x, sums, gamma, beta, prelu, out_sums, out)
+    groups, channels, length = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    rc = _lib.load().srf_gln_apply_stats(_lib.ptr(x), _norm(sums, gamma, beta, prelu), _lib.ptr(out), _lib.ptr(out_sums), groups,
+                                         channels, length, _lib.current_stream(dev))
+    _lib.check(rc, "srf_gln_apply_stats")
     return out

@@ -233,8 +233,9 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   SRF_CHECK_ARG(c && out, "srf_plan_create: null pointer");
   *out = nullptr;
   SRF_CHECK_ARG(c->variant == SRF_VARIANT_IMPROVED || c->variant == SRF_VARIANT_GROUPCOMM || c->variant == SRF_VARIANT_CAUSAL,
-                c->variant == SRF_VARIANT_ATTENTIVE ? "srf_plan_create: variant %d (attentive) takes srf_attentive_plan_create"
-                                                    : "srf_plan_create: unknown variant %d",
+                c->variant == SRF_VARIANT_ATTENTIVE      ? "srf_plan_create: variant %d (attentive) takes srf_attentive_plan_create"
+                : c->variant == SRF_VARIANT_ATTENTIVE_V3 ? "srf_plan_create: variant %d (attentive v3) takes srf_attentive_v3_plan_create"
+                                                         : "srf_plan_create: unknown variant %d",
                 c->variant);
   if (c->variant == SRF_VARIANT_CAUSAL) return causal_plan_create(c, batch, T, out);
   SRF_CHECK_ARG(batch > 0 && T > 0, "srf_plan_create: batch and T must be positive");
@@ -660,7 +661,7 @@ static int forward_walk(const srf_plan* p, const float* const* P, const float* w
   return srf_improved_tail(p, P, cur, out, workspace, use_pack, wav_stats, wav, mixture_consistency, rg, stream);
 }
 
-// ---- mask estimation + decoder of the Improved / GroupComm / attentive walks       improved_sudormrf.py:295-301
+// ---- mask estimation + decoder of the Improved / GroupComm / attentive (v2, v3) walks      improved_sudormrf.py:295-301
 // cur: the separation module's output; the encoder output is where the walk left it (off_enc); rg as in forward_walk
 int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur, float* out, void* workspace, bool use_pack,
                       const float* wav_stats, const float* wav, int mixture_consistency, const Ragged* rg, void* stream) {
@@ -713,6 +714,8 @@ static int srf_forward_impl(const srf_plan* p, const float* const* P, int num_pa
   if (p->cfg.variant == SRF_VARIANT_CAUSAL) return causal_forward(p, P, wav, out, workspace, stream);
   if (p->cfg.variant == SRF_VARIANT_ATTENTIVE)
     return srf_attentive_forward(p, P, wav, out, workspace, wav_stats, mixture_consistency, stream);
+  if (p->cfg.variant == SRF_VARIANT_ATTENTIVE_V3)
+    return srf_attentive_v3_forward(p, P, wav, out, workspace, wav_stats, mixture_consistency, stream);
   return forward_walk(p, P, wav, out, workspace, wav_stats, mixture_consistency, nullptr, stream);
 }
 
@@ -743,7 +746,7 @@ static bool plan_ragged_now(const srf_plan* p, const char** why) {
   };
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
   if (c.variant == SRF_VARIANT_CAUSAL) return no("the causal model has no ragged kernels (per-example calls)");
-  if (c.variant == SRF_VARIANT_ATTENTIVE) return no("the attentive model has no ragged kernels (per-example calls)");
+  if (c.variant == SRF_VARIANT_ATTENTIVE || c.variant == SRF_VARIANT_ATTENTIVE_V3) return no("the attentive model has no ragged kernels (per-example calls)");
   if (p->A != 1 || c.enc_kernel_size != 21) return no("the ragged encoder is the one-channel K = 21 kernel");
   if (gc && (c.group_size != 16 || p->nB != 16))
     return no("GroupComm: the ragged TAC is the MFMA kernel (group_size = 16, out_channels = 256)");

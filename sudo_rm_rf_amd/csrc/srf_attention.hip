@@ -1,9 +1,11 @@
-// Softmax attention and the two small glue kernels of the attentive model's transformer layer
-// (attentive_sudormrf_v2.py: MHAttentionLayer.forward, TransformerLayer.forward).
+// Softmax attention and the small glue kernels of the attentive models' transformer layers
+// (attentive_sudormrf_v2.py: MHAttentionLayer.forward, TransformerLayer.forward; attentive_sudormrf_v3.py:
+// ConditionalTransformerLayer.forward, AttentiveUConvBlock.forward).
 //
 //   srf_mha_attention   o[b, h d + j, lq] = sum_lk softmax_lk(scale * sum_j q[b, h d + j, lq] k[b, h d + j, lk]) v[b, h d + j, lk]
 //   srf_posenc_apply    x[b, c, l] = GlobLN(a)[b, c, l] + pe[l, c]                      (PositionalEncoding on the transposed tensor)
 //   srf_gln_apply2_add  z = norm_f(f) + norm_y(y), {sum, sumsq} of z accumulated       (out_norm's input: ffn(y) + y)
+//   srf_gln_apply_stats y = norm(x), {sum, sumsq} of y accumulated                     (v3: O_proj's residual; final_norm's input)
 //
 // Every tensor is [batch, channel, time] like the rest of the library: q, k, v are the outputs of 1x1 convolutions, channel
 // h d + j belongs to head h, and nothing is transposed in memory.
@@ -337,5 +339,56 @@ extern "C" int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const f
   hipLaunchKernelGGL(srf_gln_apply2_add_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, f, srf_norm_dev(fnorm), y,
                      srf_norm_dev(ynorm), z, out_sums, 1.0 / ((double)channels * (double)length), channels, length, chunks);
   SRF_CHECK_LAUNCH("gln_apply2_add", stream);
+  return SRF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// y = norm(x) (a GlobLN with optional PReLU, statistics from its slot), out_sums += {sum, sumsq} of the stored y.
+// Attentive v3 needs a normalised tensor in memory twice per block: the asking level is the residual of O_proj (the GEMM's
+// residual is a raw pointer), and final_norm sits on top of the last resampler's out_norm -- a GlobLN over an already-normalised
+// tensor, whose moments (gamma and beta are per channel) do not follow from the global sums of its input.
+// One block per (row = (g, c), chunk of 1024 positions), as srf_gln_apply2_add; dword accesses: any address, any length.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void srf_gln_apply_stats_kernel(const float* __restrict__ x, SrfNormDev n, float* __restrict__ y,
+                                                                  double* __restrict__ out_sums, double inv_count, int channels,
+                                                                  int length, int chunks) {
+  __shared__ double red[8];
+  const long row = blockIdx.x / chunks;
+  const int chunk = blockIdx.x - row * chunks;
+  const int c = (int)(row % channels);
+  const long g = row / channels;
+  float mean, rstd;
+  srf_finalize_stats(n.sums, g, inv_count, mean, rstd);
+  const float sc = n.gamma[c] * rstd, sh = n.beta[c] - mean * sc;
+  const bool act = n.prelu != nullptr;
+  const float slope = act ? n.prelu[0] : 1.f;
+  const size_t base = (size_t)row * length;
+  double ds = 0.0, dq = 0.0;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int l = chunk * 1024 + u * 256 + threadIdx.x;
+    if (l < length) {
+      float v = fmaf(x[base + l], sc, sh);
+      if (act) v = srf_prelu(v, slope);
+      y[base + l] = v;
+      ds += (double)v;
+      dq += (double)v * (double)v;
+    }
+  }
+  if (out_sums) srf_block_stats_atomic<4>(ds, dq, srf_stat_slot(out_sums, g, blockIdx.x), red);
+}
+
+extern "C" int srf_gln_apply_stats(const float* x, const srf_norm* norm, float* y, double* out_sums, int groups, int channels,
+                                   int length, void* stream) {
+  SRF_CHECK_ARG(x && y && norm && groups > 0 && channels > 0 && length > 0, "srf_gln_apply_stats: bad arguments");
+  SRF_CHECK_ARG(norm->sums && norm->gamma && norm->beta, "srf_gln_apply_stats: the norm needs statistics, gamma and beta");
+  SRF_CHECK_ARG((const void*)norm->sums != (const void*)out_sums, "srf_gln_apply_stats: out_sums must not be norm.sums");
+  SRF_CHECK_ALIGNED16("srf_gln_apply_stats", {"norm.sums", norm->sums});
+  const int chunks = (length + 1023) / 1024;
+  const long blocks = (long)groups * channels * chunks;
+  SRF_CHECK_ARG(blocks < (1L << 31), "srf_gln_apply_stats: tensor too large");
+  hipLaunchKernelGGL(srf_gln_apply_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, srf_norm_dev(norm), y,
+                     out_sums, 1.0 / ((double)channels * (double)length), channels, length, chunks);
+  SRF_CHECK_LAUNCH("gln_apply_stats", stream);
   return SRF_OK;
 }

@@ -40,7 +40,7 @@ int srf_overlap_add_launch(const float* z, float* out, int Bt, int Co, int K, in
 // per-row {mean, unbiased std} over lens.n[r] samples of a padded [rows, T] tensor; `lens` already checked against T
 int srf_wav_stats_ragged_launch(const float* wav, const SrfFrames& lens, float* stats, int rows, int T, hipStream_t st);
 
-// ---- srf_api.hip: what the attentive model's walk (srf_attentive.hip) shares with forward_walk
+// ---- srf_api.hip: what the attentive models' walks (srf_attentive.hip, srf_attentive_v3.hip) share with forward_walk
 int srf_zero_launch(void* p, size_t bytes, hipStream_t st);
 // post_stats / post_wav / post_mc: the callers' rescale (+ mixture consistency) folded into the overlap-add (srf_separate)
 int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T, float* scratch,
@@ -53,7 +53,10 @@ int srf_mha_attention_strided(const float* q, const float* k, const float* v, fl
 struct srf_plan;
 int srf_attentive_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                           const float* wav_stats, int mixture_consistency, void* stream);
-// the Improved walk's mask + decoder tail (srf_api.hip), shared with the attentive walk; rg: forward_walk's ragged batch, else NULL
+// ---- srf_attentive_v3.hip
+int srf_attentive_v3_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
+                             const float* wav_stats, int mixture_consistency, void* stream);
+// the Improved walk's mask + decoder tail (srf_api.hip), shared with the attentive walks; rg: forward_walk's ragged batch, else NULL
 struct Ragged;
 int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur, float* out, void* workspace, bool use_pack,
                       const float* wav_stats, const float* wav, int mixture_consistency, const Ragged* rg, void* stream);

@@ -27,10 +27,24 @@ struct srf_plan {
   // activations x | qkv | o | y | f and the concatenated [3 H d, C] Q/K/V weights + biases of every block
   int att_heads = 0, att_dims = 0, att_len = 0;
   size_t off_att_x = 0, off_att_qkv = 0, off_att_o = 0, off_att_y = 0, off_att_f = 0, off_att_wqkv = 0;
+  // attentive v3 (SRF_VARIANT_ATTENTIVE_V3): positions of every pyramid level (ceil halving) and, next to the fields above
+  // (x: the answering level + its table, qkv: its [K; V] projection, wqkv: the concatenated [2 H d, C] K/V weights + biases
+  // of every resampler), the asking side's Q projection and normalised copy
+  int att_lv[SRF_MAX_DEPTH] = {};
+  size_t off_att_q = 0, off_att_qn = 0;
 };
 // attentive blocks: the Improved block's tensors, then these (state_dict order of TransformerLayer)
 enum { SRF_PA_Q = 0, SRF_PA_K = 2, SRF_PA_V = 4, SRF_PA_O = 6, SRF_PA_OUT_NORM = 8, SRF_PA_MHA_NORM = 10, SRF_PA_FFN = 12,
        SRF_PA_FFN_NORM = 14, SRF_PA_FFN_PRELU = 16, SRF_PA_PE = 17, SRF_PA_COUNT = 18 };
+
+// attentive v3 blocks: the Improved block's tensors (final_norm.norm.{gamma, beta}, final_norm.act.weight where the Improved
+// model has final_norm.{gamma, beta}, final_act.weight: the same places), then D - 1 groups of the SRF_PA_* tensors above,
+// attentive_resamplers.0 .. D-2 (ConditionalTransformerLayer has TransformerLayer's state_dict).  Resampler r asks from level
+// D - 2 - r and is answered by the result of resampler r - 1 (r = 0: by level D - 1).
+// slots     ln | per block: proj_1x1.norm, level 0 .. D-1, final_norm (its input: the last out_norm's OUTPUT; D = 1: level 0's
+//           norm's), then per resampler out_mha_norm, ffn.norm, out_norm
+static inline int plan_v3_block_params(int D) { return 5 + 4 * D + 5 + (D - 1) * SRF_PA_COUNT; }
+static inline int plan_v3_slots_per_block(int D) { return D + 2 + 3 * (D - 1); }
 
 // ---- named views of the parameter table and of the GlobLN statistic slots (Improved / GroupComm layout, which the attentive
 // variant extends; the causal variant's views follow below).  state_dict order:

@@ -51,10 +51,10 @@ class Plan:
         # (the causal model appends its blocks' (alpha, beta) attributes to the 10 constructor fields)
         cfg = _config_struct(*cfg_tuple[:10])
         handle = C.c_void_p()
-        attentive = cfg_tuple[0] == "attentive"      # (its 11th field: the blocks' (n_heads, att_dims))
+        attentive = cfg_tuple[0] in ("attentive", "attentive_v3")    # (11th field: the blocks' (n_heads, att_dims))
         if attentive:
-            _lib.check(lib.srf_attentive_plan_create(C.byref(cfg), cfg_tuple[10][0], cfg_tuple[10][1], batch, T, C.byref(handle)),
-                       "srf_attentive_plan_create")
+            create = "srf_attentive_plan_create" if cfg_tuple[0] == "attentive" else "srf_attentive_v3_plan_create"
+            _lib.check(getattr(lib, create)(C.byref(cfg), cfg_tuple[10][0], cfg_tuple[10][1], batch, T, C.byref(handle)), create)
         else:
             _lib.check(lib.srf_plan_create(C.byref(cfg), batch, T, C.byref(handle)), "srf_plan_create")
         self.handle = handle
