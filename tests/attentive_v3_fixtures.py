@@ -52,6 +52,41 @@ DIGEST_CONFIGS = {"tiny": TINY, "pickle": PICKLE}
 PICKLE_SEED, PICKLE_BATCH, PICKLE_T, PICKLE_INPUT_SEED = 9, 2, 777, 307
 DISTINCT_T, DISTINCT_SEED = 1001, 308                    # five distinct examples on the weights of attn3_tiny
 
+# ---- configurations without a golden (reference: tests/attentive_v3_ref.py in fp64) -----------------------------------------------
+# WIDE3: the default model's channel counts at D = 3, U = 2 (two resamplers in each of two blocks: block AND resampler index of
+# every packed image vary); T = 5280 gives levels 528 / 264 / 132, all multiples of 4, so that every 1x1 conv of the walk can take
+# the 256 x 128 packed-weight kernel once the batch fills the chip.  The fewest 256 x 128 tiles per example (O_proj and ffn of
+# resampler 0: 2 m-tiles x 3 n-tiles) decide the batch: ceil(CUs / 6).
+WIDE3 = _cfg(128, 512, 2, 3, 256, 4, 256, 2)
+WIDE3_T, WIDE3_LEVELS, WIDE3_WSEED, WIDE3_INPUT_SEED, WIDE3_MIN_TILES = 5280, [528, 264, 132], 310, 310, 6
+# 256 x 128 tiles per example of every conv the 256 x 128 kernel can take (Cout, L): resampler r asks with level 1 - r
+WIDE3_TILES = {"proj_1x1": 10, "mask": 10, 0: {"Q": 12, "KV": 16, "O": 6, "ffn": 6}, 1: {"Q": 20, "KV": 24, "O": 10, "ffn": 10}}
+# MANY: 6 blocks x (proj_1x1 + 4 resamplers x 4) = 102 packable weights -- more than one launch of the packing kernel holds (96) --
+# run with 3 heads of 64 (with_heads); T = 640 gives levels 64 / 32 / 16 / 8 / 4.  Every packable conv is one 256 x 128 tile per
+# example ([K; V]: two), so a batch of as many examples as the chip has CUs fills it at every level.
+MANY = _cfg(128, 192, 6, 5, 64, 3, 64, 2)
+MANY_T, MANY_LEVELS, MANY_HEADS, MANY_WSEED, MANY_INPUT_SEED, MANY_PACK_CHUNK = 640, [64, 32, 16, 8, 4], (3, 64), 311, 311, 96
+# NARROW: off the grids -- 2 heads of 9 make 2 HD C = 720 and 2 HD = 36 (no multiples of 64: the concatenated [K; V] weight and
+# bias sections are padded) and HD Lk = 126 / 234 (V's base inside the [K; V] projection is off the 16-byte grid), d = 9 takes the
+# generic attention, 12 and 20 channels are below every MFMA GEMM's minimum; levels 26 / 13 / 7
+NARROW = _cfg(12, 20, 2, 3, 24, 2, 9, 2, K=9)
+NARROW_T, NARROW_LEVELS, NARROW_HEADS, NARROW_WSEED, NARROW_INPUT_SEED = 100, [26, 13, 7], (2, 9), 312, 312
+# (heads, dims) -> the attention kernel and what of it the head dimension reaches
+HEAD_SHAPES = (((3, 16), "mha_attention_mfma"),          # one 32-channel chunk, half full
+               ((2, 48), "mha_attention_mfma"),          # two chunks, the second half full
+               ((1, 80), "mha_attention_mfma"),          # the four-chunk instance with one chunk skipped
+               ((1, 144), "mha_attention_mfma"),         # the eight-chunk instance with three skipped
+               ((2, 24), "mha_attention_generic"),
+               ((2, 9), "mha_attention_generic"))
+HEADS_WSEED, HEADS_INPUT_SEED = 313, 313
+# Levels of ONE position (K = 9: 4 samples per frame, ceil halving): (D, T) -> (levels, factor on decoder.weight).  One or two
+# frames give the decoder so little to add up that max |out| of the fixtures' weights is 0.03 .. 0.1; the factor, chosen on the CPU
+# from the fp64 restatement, brings every case (the other head shapes of (3, 8) included) back into [0.1, 10], where the 1e-4 bar
+# means what it means for every other case.
+ONE_POSITION = {(1, 3): ([1], 8.0), (2, 3): ([1, 1], 8.0), (3, 8): ([2, 1, 1], 4.0), (5, 30): ([8, 4, 2, 1, 1], 1.0)}
+ONE_POSITION_WSEED, ONE_POSITION_INPUT_SEED = 314, 314
+GRID_T, GRID_LEVELS, GRID_INPUT_SEED = 1120, [112, 56, 28], 315     # TINY on the MFMA grid at every level (kernel modes)
+
 
 def level_lengths(cfg, T):
     """Positions of level 0 .. D - 1: the encoder's frames, then the strided convolution's own ceil halving."""
@@ -122,6 +157,37 @@ def make_state_dict(cfg, seed):
             raise KeyError(key)
         sd[key] = np.ascontiguousarray(w, dtype=np.float32)
     return sd
+
+
+def with_heads(sd, cfg, heads, dims, seed):
+    """The state dict of a model whose resamplers have `heads` heads of `dims` channels (what AttentiveUConvBlock and
+    srf_attentive_v3_plan_create take and the reference's SuDORMRF cannot build): the first heads * dims rows of every Q / K / V
+    projection, and O_proj.weight drawn anew as [C, heads * dims], uniform(-1, 1) / sqrt(heads * dims).  A new dict; sd is kept."""
+    hd, C = heads * dims, cfg["in_channels"]
+    assert hd <= HEADS * ATT_DIMS
+    rng = np.random.default_rng(seed)
+    out = dict(sd)
+    for i in range(cfg["num_blocks"]):
+        for r in range(cfg["upsampling_depth"] - 1):
+            p = "sm.%d.attentive_resamplers.%d.mha." % (i, r)
+            for n in "QKV":
+                out[p + n + "_proj.weight"] = np.ascontiguousarray(sd[p + n + "_proj.weight"][:hd])
+                out[p + n + "_proj.bias"] = np.ascontiguousarray(sd[p + n + "_proj.bias"][:hd])
+            out[p + "O_proj.weight"] = (rng.uniform(-1, 1, size=(C, hd)) / np.sqrt(hd)).astype(np.float32)
+    return out
+
+
+def one_position_case(D, T):
+    """(cfg, state dict for 4 heads of 256, input [2, 1, T]) of ONE_POSITION[(D, T)], decoder.weight times the case's factor"""
+    cfg = dict(TINY_K9, upsampling_depth=D)
+    sd = make_state_dict(cfg, ONE_POSITION_WSEED + D)
+    sd["decoder.weight"] = sd["decoder.weight"] * np.float32(ONE_POSITION[(D, T)][1])
+    return cfg, sd, make_mixture(2, T, ONE_POSITION_INPUT_SEED + D)
+
+
+def tiles_256(batch, cout, length):
+    """Tiles of a 256 x 128 launch: the left side of the library's "fills the chip" test (>= the CU count)"""
+    return batch * -(-cout // 256) * -(-length // 128)
 
 
 def make_input(name):

@@ -3,7 +3,12 @@ reference (tools/make_golden_attentive_v3.py), the library's new symbols, the pl
 restatement tests/attentive_v3_ref.py against every golden.  No GPU needed.
 
 One refusal of srf_attentive_v3_plan_create has no test: "a level with fewer than 1 position".  The padding rule leaves at
-least one frame and ceil halving keeps every level at one or more, so no argument reaches it; the check stays as a guard."""
+least one frame and ceil halving keeps every level at one or more, so no argument reaches it; the check stays as a guard
+(levels of exactly ONE position are reached and tested: ONE_POSITION).
+
+Last part: the configurations that have no golden (WIDE3, MANY, NARROW, the other head shapes, the one-position levels) -- the
+conditions on them that the GPU tests of tests/test_gpu_attentive_v3_walk.py rest on, so that a later edit of a fixture cannot
+hollow those out."""
 import ctypes as C
 import hashlib
 import os
@@ -247,3 +252,122 @@ def test_restatement_agrees_with_the_reference(man, restated, name):
         assert q.shape[-1] == 52 and v.shape[-1] == 26
         for got, key in ((q, "res_q"), (v, "res_v"), (z, "res_out")):
             assert got.shape == gold[key].shape and np.abs(got.numpy() - gold[key]).max() <= 1e-5
+
+
+# ---- the configurations without a golden: the conditions the GPU tests of tests/test_gpu_attentive_v3_walk.py rest on ------------
+def _packable(lib, cfg, heads, dims):
+    """(Cout, Cin) of every 1x1 weight srf_attentive_v3_plan_create gives a packed image, in the order it adds them"""
+    B, C, N, S = cfg["out_channels"], cfg["in_channels"], cfg["enc_num_basis"], cfg["num_sources"]
+    hd = heads * dims
+    shapes = [(B, N)]
+    for _ in range(cfg["num_blocks"]):
+        shapes += [(C, B), (B, C)]
+        shapes += [(hd, C), (2 * hd, C), (C, hd), (C, C)] * (cfg["upsampling_depth"] - 1)
+    shapes.append((S * N, B))
+    return [s for s in shapes if lib.srf_packed_pw_weight_bytes(*s) > 0]
+
+
+def test_wide3_levels_and_tile_counts():
+    cfg, lv = af.WIDE3, af.level_lengths(af.WIDE3, af.WIDE3_T)
+    assert lv == af.WIDE3_LEVELS == [528, 264, 132] and all(n % 4 == 0 for n in lv)
+    assert cfg["num_blocks"] >= 2 and cfg["upsampling_depth"] >= 3          # block index and resampler index both vary
+    C_, B, hd = cfg["in_channels"], cfg["out_channels"], af.HEADS * af.ATT_DIMS
+    # the library's test (srf_pwconv.hip, pw256_fills_chip): Bt * ceil(Cout / 256) * ceil(L / 128) >= CUs
+    tiles = lambda cout, n: -(-cout // 256) * -(-n // 128)
+    got = {"proj_1x1": tiles(C_, lv[0]), "mask": tiles(cfg["num_sources"] * cfg["enc_num_basis"], lv[0])}
+    for r in range(2):                                                       # resampler r: level 1 - r asks level 2 - r
+        lq, lk = lv[1 - r], lv[2 - r]
+        got[r] = {"Q": tiles(hd, lq), "KV": tiles(2 * hd, lk), "O": tiles(C_, lq), "ffn": tiles(C_, lq)}
+    assert got == af.WIDE3_TILES
+    assert got[0] == {"Q": 12, "KV": 16, "O": 6, "ffn": 6} and got[1] == {"Q": 20, "KV": 24, "O": 10, "ffn": 10}
+    assert min(min(got[0].values()), min(got[1].values()), got["proj_1x1"], got["mask"]) == af.WIDE3_MIN_TILES == 6
+    assert all(af.tiles_256(1, c, n) == tiles(c, n) for c in (192, 256, 512, 2048) for n in lv)
+    assert -(-256 // af.WIDE3_MIN_TILES) == 43                                # the chip batch on 256 CUs
+    from sudo_rm_rf_amd import _lib
+    assert len(_packable(_lib.load(), cfg, af.HEADS, af.ATT_DIMS)) == 2 * (1 + 4 * 2) + 1       # every one but B-row outputs
+
+
+def test_many_has_more_packable_weights_than_one_packing_launch_holds():
+    from sudo_rm_rf_amd import _lib
+    cfg, (heads, dims) = af.MANY, af.MANY_HEADS
+    lv = af.level_lengths(cfg, af.MANY_T)
+    assert lv == af.MANY_LEVELS == [64, 32, 16, 8, 4] and all(n % 4 == 0 for n in lv)
+    packs = _packable(_lib.load(), cfg, heads, dims)
+    per_block = 1 + 4 * (cfg["upsampling_depth"] - 1)
+    assert len(packs) == cfg["num_blocks"] * per_block == 102 > af.MANY_PACK_CHUNK == 96
+    # the first launch is full; the second holds images 96 .. 101: all four of the last block's last resampler (from index 98) and
+    # O_proj and ffn of the one before
+    assert af.MANY_PACK_CHUNK < len(packs) <= 2 * af.MANY_PACK_CHUNK
+    assert (cfg["num_blocks"] - 1) * per_block + 1 + 4 * (cfg["upsampling_depth"] - 2) == 98 >= af.MANY_PACK_CHUNK
+    # one 256 x 128 tile per example ([K; V]: two) at every level: a batch of as many examples as CUs fills the chip
+    assert all(af.tiles_256(1, cout, n) == (2 if cout == 2 * heads * dims else 1) for cout, _ in packs for n in lv)
+
+
+def test_narrow_is_off_every_grid():
+    cfg, (heads, dims) = af.NARROW, af.NARROW_HEADS
+    hd, C_ = heads * dims, cfg["in_channels"]
+    assert af.level_lengths(cfg, af.NARROW_T) == af.NARROW_LEVELS == [26, 13, 7]
+    assert (2 * hd * C_) % 64 != 0 and (2 * hd) % 64 != 0          # padded [K; V] weight and bias sections
+    assert (hd * 7) % 4 != 0 and (hd * 13) % 4 != 0                 # V's base kv + HD Lk is off the 16-byte grid
+    assert C_ < 32 and cfg["out_channels"] < 32                      # below every MFMA GEMM's minimum: the scalar conv kernel
+    assert dims % 16 != 0                                                    # the generic attention
+    assert (2 * 16) % 64 != 0 and (16 * 7) % 4 == 0                          # (1, 16): a padded bias section, MFMA attention
+
+
+@pytest.mark.parametrize("which", ["WIDE3", "MANY", "NARROW", "NARROW_1x16"])
+def test_plans_of_the_new_configurations(which):
+    from sudo_rm_rf_amd import _lib
+    cfg, T, (heads, dims), wseed = {"WIDE3": (af.WIDE3, af.WIDE3_T, (af.HEADS, af.ATT_DIMS), af.WIDE3_WSEED),
+                                    "MANY": (af.MANY, af.MANY_T, af.MANY_HEADS, af.MANY_WSEED),
+                                    "NARROW": (af.NARROW, af.NARROW_T, af.NARROW_HEADS, af.NARROW_WSEED),
+                                    "NARROW_1x16": (af.NARROW, af.NARROW_T, (1, 16), af.NARROW_WSEED)}[which]
+    sd = af.with_heads(af.make_state_dict(cfg, wseed), cfg, heads, dims, wseed)
+    p = _plan(cfg, 3, T, heads, dims)
+    assert p.num_params == _lib.load().srf_plan_num_params(p.handle) == len(sd) == len(af.schema(cfg))
+    assert p.frames == af.level_lengths(cfg, T)[0] and p.workspace_bytes > 0
+    a = "sm.1.attentive_resamplers.1.mha."
+    assert sd[a + "K_proj.weight"].shape == (heads * dims, cfg["in_channels"]) and sd[a + "V_proj.bias"].shape == (heads * dims,)
+    assert sd[a + "O_proj.weight"].shape == (cfg["in_channels"], heads * dims)
+    assert np.abs(sd[a + "O_proj.weight"]).max() <= 1.0 / np.sqrt(heads * dims)
+
+
+def test_with_heads_cuts_rows_and_keeps_the_rest():
+    sd = af.make_state_dict(af.TINY, 5)
+    cut = af.with_heads(sd, af.TINY, 2, 24, 6)
+    assert list(cut) == list(sd)
+    for k in sd:
+        if ".mha.O_proj.weight" in k:
+            assert cut[k].shape == (64, 48) and cut[k].dtype == np.float32
+        elif ".mha." in k and "O_proj" not in k:
+            assert np.array_equal(cut[k], sd[k][:48]) and cut[k].flags["C_CONTIGUOUS"]
+        else:
+            assert cut[k] is sd[k]
+    assert sd["sm.0.attentive_resamplers.0.mha.Q_proj.weight"].shape == (1024, 64)          # the source is untouched
+    a, b = (af.with_heads(sd, af.TINY, 2, 24, s)["sm.1.attentive_resamplers.0.mha.O_proj.weight"] for s in (6, 6))
+    assert np.array_equal(a, b)
+    o = [v for k, v in cut.items() if k.endswith("O_proj.weight")]
+    assert all(not np.array_equal(x, y) for i, x in enumerate(o) for y in o[i + 1:])
+
+
+@pytest.mark.parametrize("D,T", sorted(af.ONE_POSITION))
+def test_levels_of_one_position(D, T):
+    """T < K and one or two frames: the plan takes them, the level list ends in 1s, and the restatement is finite with
+    max |out| inside the fixtures' [0.1, 10] (the decoder factor of the fixture)."""
+    levels, factor = af.ONE_POSITION[(D, T)]
+    cfg, sd, wav = af.one_position_case(D, T)
+    assert af.level_lengths(cfg, T) == levels and levels[-1] == 1 and T < cfg["enc_kernel_size"] * 4
+    variants = [(af.HEADS, af.ATT_DIMS, sd)]
+    if (D, T) == (3, 8):
+        variants += [(h, d, af.with_heads(sd, cfg, h, d, af.ONE_POSITION_WSEED + h)) for h, d in ((3, 16), (2, 24))]
+    for heads, dims, w in variants:
+        p = _plan(cfg, 2, T, heads, dims)
+        assert p.frames == levels[0] and p.num_params == len(w)
+        y = ar.forward(cfg, w, wav, torch.float64, heads=heads).numpy()
+        amax = float(np.abs(y).max())
+        print("D %d, T %d, %d x %d, decoder x %g: max|out| %.3f" % (D, T, heads, dims, factor, amax))
+        assert y.shape == (2, 2, T) and np.isfinite(y).all() and 0.1 <= amax <= 10.0
+
+
+def test_grid_case_of_the_kernel_modes_is_on_the_mfma_grid():
+    lv = af.level_lengths(af.TINY, af.GRID_T)
+    assert lv == af.GRID_LEVELS == [112, 56, 28] and all(n % 4 == 0 for n in lv)

@@ -1,6 +1,8 @@
 """Attentive SuDoRM-RF (v3) on the GPU: the reference's goldens through the module and through the raw C ABI, the stored
-resampler of attn3_tiny, the reference's pickle, a batch of distinct examples, the separate() recipe, the kernels the default
-configuration runs, the refusals, and srf_gln_apply_stats against fp64.  References: the stored reference outputs
+resampler of attn3_tiny, the reference's pickle, a batch of distinct examples, the separate() recipe, the kernels
+attn3_default_u2 runs at batch 2 (the kernels that split the fp32 weight on the fly; the batch-32 kernels of the published
+profile are covered by the WIDE3 and MANY tests of tests/test_gpu_attentive_v3_walk.py), the refusals, and srf_gln_apply_stats
+against fp64.  References: the stored reference outputs
 (tests/golden/attn3_*.npz) and, where there is no golden, tests/attentive_v3_ref.py in fp64 (pinned to the goldens within 1e-5
 by tests/test_attentive_v3_host.py).  Bar: the project's 1e-4 max-abs.
 Measured on an MI355X: goldens 1.8e-7 .. 2.4e-6 (module and C ABI alike), stored resampler 2.1e-5 at max |ref| 11.7, pickle
