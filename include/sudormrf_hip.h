@@ -24,6 +24,7 @@
  *   srf_forward (causal)   <- CausalSuDORMRF.forward      models/causal_improved_sudormrf_v3.py (ABI 16)
  *   srf_forward (attentive)<- SuDORMRF.forward             models/attentive_sudormrf_v2.py (srf_attentive_plan_create, below)
  *   srf_forward (att. v3)  <- SuDORMRF.forward             models/attentive_sudormrf_v3.py (srf_attentive_v3_plan_create, below)
+ *   srf_forward (original) <- SuDORMRF.forward             models/sudormrf.py (srf_original_plan_create, below)
  *   srf_mha_attention      <- MHAttentionLayer.forward: softmax(q k^T / sqrt(d)) v per head, between its four Linear layers
  *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17; row-table push: ABI 19)
  *   srf_zeroref_snr_*      <- PermInvariantSNRwithZeroRefs fwd/bwd (FUSS training loss)  losses/snr.py:13-142 (ABI 18)
@@ -964,6 +965,52 @@ int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const float* y, co
 int srf_attentive_v3_plan_create(const srf_config* base, int n_heads, int att_dims, int batch, int T, srf_plan** out);
 int srf_gln_apply_stats(const float* x, const srf_norm* norm, float* y, double* out_sums, int groups, int channels, int length,
                         void* stream);
+
+/* ---- Original SuDoRM-RF (additive to ABI 19; sudormrf.py) ----
+ * The model of the paper: an encoder WITH bias and ReLU, GroupNorm(1, C) everywhere (GlobLN's arithmetic), PReLU with one slope
+ * PER CHANNEL, blocks whose residual is added before the last norm, a mask layer that is a convolution along the basis axis
+ * (a [S N, N] Toeplitz GEMM) followed by a softmax over the sources (sigmoid for one source), and a grouped decoder with bias.
+ * Inference only, one stream.
+ * srf_original_plan_create: padding up to a multiple of lcm(K / 2, 2^D), only when T is not one already.  The plan works with
+ *   srf_forward, srf_separate (decoder.bias is added before the rescale and mixture consistency), srf_plan_workspace_bytes /
+ *   _num_params / _frames / _padded_length / _num_launches, srf_debug_fetch (1: always the separation module's output; 3: the
+ *   pre-softmax mask logits [Bt, S N, L]) and the profiler.  Parameters in state_dict() order: encoder.0.{weight, bias},
+ *   ln.{weight, bias}, l1.{weight, bias}; per block proj_1x1.{conv.weight, conv.bias, norm.weight, norm.bias, act.weight [C]},
+ *   D x spp_dw.k.{conv.weight, conv.bias, norm.weight, norm.bias}, conv_1x1_exp.{conv.weight, conv.bias, norm.weight,
+ *   norm.bias}, final_norm.{norm.weight, norm.bias, act.weight [C]}, module_act.{norm.weight, norm.bias, act.weight [B]};
+ *   reshape_before_masks.{weight, bias} only when out_channels != enc_num_basis; m.{weight [S, 1, N + 1, 1], bias},
+ *   decoder.{weight [S N, 1, K], bias [S]}, ln_mask_in.{weight, bias} (in the state_dict, never read).
+ *   Refused before anything is launched (SRF_EINVAL, the message names the argument): odd enc_num_basis (the reference's own
+ *   mask multiply fails there: the mask layer then has N + 1 rows), even or < 3 enc_kernel_size, in_audio_channels or group_size
+ *   != 1, upsampling_depth outside 1..8, a frame count that is no multiple of 2^(D-1), num_sources above
+ *   SRF_SOFTMAX_MASK_MAX_SOURCES, batch > 65535; srf_forward_train, srf_backward(_wav) and srf_forward_ragged /
+ *   srf_separate_ragged refuse such a plan, srf_plan_ragged_supported is 0.
+ * srf_gln_apply_c: y = norm(x), a GlobLN from norm->sums (norm->prelu is ignored), then PReLU with slopes[c] (nullable: none),
+ *   then + add (nullable); out_sums (nullable) += {sum, sumsq} of the STORED y.  x, add, y: [groups, channels, length] at any
+ *   float-aligned address, any length; y overlaps neither input.
+ * srf_encoder_bias_relu: out = relu(bias[n] + srf_encoder's sum) for one audio channel and any odd K; sums of the stored out;
+ *   in_stats (nullable): [Bt][2] {mean, std}, the row is normalised on load as in srf_separate.
+ * srf_mask_weight_fill: tz [S N, N], tz[s N + i, n] = mw[s, n - i + N - N / 2] where that tap exists (0 .. N), else 0;
+ *   bias_rows [S N] = mb[s] repeated N times.  N even.
+ * srf_softmax_mask: v[b, s N + i, l] = p_s(z[b, :, i, l]) * enc[b, i, l]; p = softmax over the S sources (maximum subtracted),
+ *   S = 1: the sigmoid.  v may be z.  1 <= S <= SRF_SOFTMAX_MASK_MAX_SOURCES.
+ * srf_decoder_weight_expand: the grouped ConvTranspose1d weight w [S N, 1, K] as the block-diagonal wexp [S N, S, K] of an
+ *   ungrouped one (zeros written).
+ * srf_bias_rescale: out[b, s, t] = est[b, s, t] + bias[s], in place over out [Bt, S, T]; stats (nullable) [Bt][2] {mean, std}
+ *   of the raw mixture wav [Bt, T]: then out = (est + bias) * std + mean and, mc != 0, mixture consistency against the
+ *   mixture normalised on the fly, exactly as srf_separate's overlap-add does it. */
+#define SRF_VARIANT_ORIGINAL 5
+#define SRF_SOFTMAX_MASK_MAX_SOURCES 16
+int srf_original_plan_create(const srf_config* cfg, int batch, int T, srf_plan** out);
+int srf_gln_apply_c(const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y, double* out_sums,
+                    int groups, int channels, int length, void* stream);
+int srf_encoder_bias_relu(const float* wav, const float* w, const float* bias, float* out, double* sums, int Bt, int T, int N,
+                          int K, int L, const float* in_stats, void* stream);
+int srf_mask_weight_fill(const float* mw, const float* mb, float* tz, float* bias_rows, int N, int S, void* stream);
+int srf_softmax_mask(const float* z, const float* enc, float* v, int Bt, int S, int N, int L, void* stream);
+int srf_decoder_weight_expand(const float* w, float* wexp, int N, int S, int K, void* stream);
+int srf_bias_rescale(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
+                     void* stream);
 
 #ifdef __cplusplus
 }

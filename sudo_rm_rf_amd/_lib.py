@@ -17,8 +17,9 @@ RAGGED_MAX_BATCH = 128     # SRF_RAGGED_MAX_BATCH
 STAT_BUCKETS = 64
 
 SRF_OK = 0
-VARIANT_IMPROVED, VARIANT_GROUPCOMM, VARIANT_CAUSAL, VARIANT_ATTENTIVE, VARIANT_ATTENTIVE_V3 = 0, 1, 2, 3, 4
+VARIANT_IMPROVED, VARIANT_GROUPCOMM, VARIANT_CAUSAL, VARIANT_ATTENTIVE, VARIANT_ATTENTIVE_V3, VARIANT_ORIGINAL = 0, 1, 2, 3, 4, 5
 ATT_MAX_LEN = 5000         # SRF_ATT_MAX_LEN
+SOFTMAX_MASK_MAX_SOURCES = 16   # SRF_SOFTMAX_MASK_MAX_SOURCES
 
 
 class SrfError(RuntimeError):
@@ -209,6 +210,13 @@ _PROTOS = {
     "srf_gln_apply2_add": (_i, [_vp, C.POINTER(srf_norm), _vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _vp]),
     "srf_attentive_v3_plan_create": (_i, [C.POINTER(srf_config), _i, _i, _i, _i, C.POINTER(_vp)]),
     "srf_gln_apply_stats": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _vp]),
+    "srf_original_plan_create": (_i, [C.POINTER(srf_config), _i, _i, C.POINTER(_vp)]),
+    "srf_gln_apply_c": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "srf_encoder_bias_relu": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "srf_mask_weight_fill": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "srf_softmax_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "srf_decoder_weight_expand": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "srf_bias_rescale": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

@@ -235,6 +235,7 @@ extern "C" int srf_plan_create(const srf_config* c, int batch, int T, srf_plan**
   SRF_CHECK_ARG(c->variant == SRF_VARIANT_IMPROVED || c->variant == SRF_VARIANT_GROUPCOMM || c->variant == SRF_VARIANT_CAUSAL,
                 c->variant == SRF_VARIANT_ATTENTIVE      ? "srf_plan_create: variant %d (attentive) takes srf_attentive_plan_create"
                 : c->variant == SRF_VARIANT_ATTENTIVE_V3 ? "srf_plan_create: variant %d (attentive v3) takes srf_attentive_v3_plan_create"
+                : c->variant == SRF_VARIANT_ORIGINAL     ? "srf_plan_create: variant %d (original) takes srf_original_plan_create"
                                                          : "srf_plan_create: unknown variant %d",
                 c->variant);
   if (c->variant == SRF_VARIANT_CAUSAL) return causal_plan_create(c, batch, T, out);
@@ -716,6 +717,8 @@ static int srf_forward_impl(const srf_plan* p, const float* const* P, int num_pa
     return srf_attentive_forward(p, P, wav, out, workspace, wav_stats, mixture_consistency, stream);
   if (p->cfg.variant == SRF_VARIANT_ATTENTIVE_V3)
     return srf_attentive_v3_forward(p, P, wav, out, workspace, wav_stats, mixture_consistency, stream);
+  if (p->cfg.variant == SRF_VARIANT_ORIGINAL)
+    return srf_original_forward(p, P, wav, out, workspace, wav_stats, mixture_consistency, stream);
   return forward_walk(p, P, wav, out, workspace, wav_stats, mixture_consistency, nullptr, stream);
 }
 
@@ -747,6 +750,7 @@ static bool plan_ragged_now(const srf_plan* p, const char** why) {
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
   if (c.variant == SRF_VARIANT_CAUSAL) return no("the causal model has no ragged kernels (per-example calls)");
   if (c.variant == SRF_VARIANT_ATTENTIVE || c.variant == SRF_VARIANT_ATTENTIVE_V3) return no("the attentive model has no ragged kernels (per-example calls)");
+  if (c.variant == SRF_VARIANT_ORIGINAL) return no("the original model has no ragged kernels (per-example calls)");
   if (p->A != 1 || c.enc_kernel_size != 21) return no("the ragged encoder is the one-channel K = 21 kernel");
   if (gc && (c.group_size != 16 || p->nB != 16))
     return no("GroupComm: the ragged TAC is the MFMA kernel (group_size = 16, out_channels = 256)");
@@ -843,8 +847,12 @@ extern "C" int srf_debug_fetch(const srf_plan* p, const void* workspace, int wha
   if (what == 0) {
     off = p->off_enc;
     n = (size_t)p->Bt * c.enc_num_basis * p->L;
+  } else if (what == 3 && c.variant == SRF_VARIANT_ORIGINAL) {      // the mask logits before the softmax
+    off = p->off_orig_z;
+    n = (size_t)p->Bt * p->SA * c.enc_num_basis * p->L;
   } else if (what == 1) {
-    off = (c.num_blocks % 2 == 0) ? p->off_xa : p->off_xb;
+    // (the original model's blocks write their output over their input)
+    off = (c.num_blocks % 2 == 0 || c.variant == SRF_VARIANT_ORIGINAL) ? p->off_xa : p->off_xb;
     n = (size_t)p->Bt * c.out_channels * p->L;
   } else if (what == 2) {
     // the fused tail (K5) never materialises the masked tensor: its workspace region holds partial decoder frames

@@ -56,6 +56,9 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
 // ---- srf_attentive_v3.hip
 int srf_attentive_v3_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                              const float* wav_stats, int mixture_consistency, void* stream);
+// ---- srf_original.hip
+int srf_original_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
+                         const float* wav_stats, int mixture_consistency, void* stream);
 // the Improved walk's mask + decoder tail (srf_api.hip), shared with the attentive walks; rg: forward_walk's ragged batch, else NULL
 struct Ragged;
 int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur, float* out, void* workspace, bool use_pack,

@@ -32,6 +32,10 @@ struct srf_plan {
   // of every resampler), the asking side's Q projection and normalised copy
   int att_lv[SRF_MAX_DEPTH] = {};
   size_t off_att_q = 0, off_att_qn = 0;
+  // original variant (SRF_VARIANT_ORIGINAL): the materialised activation a / e [C], conv_1x1_exp's output g and g + x with its
+  // norm applied [B], reshape_before_masks' output [N], the mask logits z [S N], the Toeplitz mask weight + its row bias and the
+  // block-diagonal decoder weight
+  size_t off_orig_act = 0, off_orig_g = 0, off_orig_gx = 0, off_orig_xr = 0, off_orig_z = 0, off_orig_tz = 0, off_orig_wdec = 0;
 };
 // attentive blocks: the Improved block's tensors, then these (state_dict order of TransformerLayer)
 enum { SRF_PA_Q = 0, SRF_PA_K = 2, SRF_PA_V = 4, SRF_PA_O = 6, SRF_PA_OUT_NORM = 8, SRF_PA_MHA_NORM = 10, SRF_PA_FFN = 12,
@@ -189,6 +193,70 @@ static inline size_t causal_fold_res_floats(int B, int C) { return srf_align_up(
 // One srf_causal_scale_many launch (srf_api.hip).
 struct SrfCausalFolded { std::vector<const float*> wproj, wres, bres; };
 int srf_causal_fold(const srf_plan* p, const float* const* P, float* fold_res, float* fold_proj, SrfCausalFolded* out, hipStream_t st);
+
+// ---- original variant (SuDORMRF, sudormrf.py).  state_dict order:
+//   front   encoder.0.{weight, bias} | ln.{weight, bias} | l1.{weight, bias}
+//   block   proj_1x1.{conv.weight, conv.bias, norm.weight, norm.bias, act.weight [C]} | D x spp_dw.k.{conv.weight, conv.bias,
+//           norm.weight, norm.bias} | conv_1x1_exp.{conv.weight, conv.bias, norm.weight, norm.bias} |
+//           final_norm.{norm.weight, norm.bias, act.weight [C]} | module_act.{norm.weight, norm.bias, act.weight [B]}
+//   tail    [B != N: reshape_before_masks.{weight, bias}] | m.{weight, bias} | decoder.{weight, bias} | ln_mask_in.{weight, bias}
+// slots     ln | per block: proj_1x1.norm, level 0 .. D-1, final_norm (the merged tensor), conv_1x1_exp.norm, module_act.norm
+// The ONE place that spells this layout out.
+enum { SRF_PO_L1 = 4, SRF_PO_FRONT = 6, SRF_PO_TAIL = 6 };
+static inline int orig_block_params(int D) { return 5 + 4 * D + 4 + 3 + 3; }
+static inline int orig_slots_per_block(int D) { return D + 4; }
+static inline int orig_p_proj(const srf_plan* p, int i) { return p->p_block0 + i * p->p_block_stride; }
+static inline int orig_p_exp(const srf_plan* p, int i) { return orig_p_proj(p, i) + 5 + 4 * p->cfg.upsampling_depth; }
+static inline bool orig_has_reshape(const srf_plan* p) { return p->cfg.out_channels != p->cfg.enc_num_basis; }
+static inline int orig_p_reshape(const srf_plan* p) { return p->p_tail; }                       // (only where orig_has_reshape)
+static inline int orig_p_mask(const srf_plan* p) { return p->p_tail + (orig_has_reshape(p) ? 2 : 0); }
+struct SrfOrigFront { const float *enc_w, *enc_b, *ln_g, *ln_b, *l1_w, *l1_b; };
+struct SrfOrigBlock {
+  const float *proj_w, *proj_b, *proj_g, *proj_be, *proj_slope;
+  const float *lv_w[SRF_MAX_DEPTH], *lv_b[SRF_MAX_DEPTH], *lv_g[SRF_MAX_DEPTH], *lv_be[SRF_MAX_DEPTH];
+  const float *exp_w, *exp_b, *exp_g, *exp_be;
+  const float *fin_g, *fin_be, *fin_slope;
+  const float *act_g, *act_be, *act_slope;
+  int i_proj, i_exp;   // parameter indices of the two packable weights (pk_of_param)
+};
+struct SrfOrigTail { const float *rs_w, *rs_b, *m_w, *m_b, *dec_w, *dec_b; int i_rs, i_m; };
+struct SrfOrigSlots { double *proj, *level[SRF_MAX_DEPTH], *merged, *exp, *act; };
+static inline SrfOrigFront orig_front(const float* const* t) { return SrfOrigFront{t[0], t[1], t[2], t[3], t[SRF_PO_L1], t[SRF_PO_L1 + 1]}; }
+static inline SrfOrigBlock orig_block(const srf_plan* p, const float* const* t, int i) {
+  const int D = p->cfg.upsampling_depth;
+  SrfOrigBlock b{};
+  b.i_proj = orig_p_proj(p, i);
+  b.i_exp = orig_p_exp(p, i);
+  const float* const* u = t + b.i_proj;
+  b.proj_w = u[0], b.proj_b = u[1], b.proj_g = u[2], b.proj_be = u[3], b.proj_slope = u[4];
+  for (int k = 0; k < D; ++k) {
+    const float* const* l = u + 5 + 4 * k;
+    b.lv_w[k] = l[0], b.lv_b[k] = l[1], b.lv_g[k] = l[2], b.lv_be[k] = l[3];
+  }
+  const float* const* e = t + b.i_exp;
+  b.exp_w = e[0], b.exp_b = e[1], b.exp_g = e[2], b.exp_be = e[3];
+  b.fin_g = e[4], b.fin_be = e[5], b.fin_slope = e[6];
+  b.act_g = e[7], b.act_be = e[8], b.act_slope = e[9];
+  return b;
+}
+static inline SrfOrigTail orig_tail(const srf_plan* p, const float* const* t) {
+  SrfOrigTail v{};
+  v.i_rs = orig_p_reshape(p);
+  v.i_m = orig_p_mask(p);
+  if (orig_has_reshape(p)) v.rs_w = t[v.i_rs], v.rs_b = t[v.i_rs + 1];
+  v.m_w = t[v.i_m], v.m_b = t[v.i_m + 1], v.dec_w = t[v.i_m + 2], v.dec_b = t[v.i_m + 3];
+  return v;
+}
+static inline SrfOrigSlots orig_slots(const srf_plan* p, double* stats, int i) {
+  const size_t each = (size_t)p->Bg * SRF_STAT_BUCKETS * 2;
+  const int D = p->cfg.upsampling_depth;
+  double* s = stats + (1 + (size_t)i * p->slots_per_block) * each;
+  SrfOrigSlots v{};
+  v.proj = s;
+  for (int k = 0; k < D; ++k) v.level[k] = s + (1 + k) * each;
+  v.merged = s + (1 + D) * each, v.exp = s + (2 + D) * each, v.act = s + (3 + D) * each;
+  return v;
+}
 
 // ---- the packed (split-bf16) weight images of a plan
 // parameter index -> (block, index inside the block's run of tensors); block = -1 outside the blocks

@@ -232,6 +232,10 @@ static bool causal_refused(const srf_plan* p, const char* who) {
     srf_set_error("%s: not available for the attentive v3 variant (attentive SuDORMRF v3 has an inference forward only)", who);
     return true;
   }
+  if (p && p->cfg.variant == SRF_VARIANT_ORIGINAL) {
+    srf_set_error("%s: not available for the original variant (the original SuDORMRF has an inference forward only)", who);
+    return true;
+  }
   if (!p || p->cfg.variant != SRF_VARIANT_CAUSAL) return false;
   srf_set_error("%s: not available for the causal variant (CausalSuDORMRF has an inference forward only)", who);
   return true;

@@ -1,0 +1,265 @@
+"""Original SuDoRM-RF (the model of the paper) on MI355X: the reference's module surface over hand-written HIP kernels.
+
+Mirrors the reference's sudo_rm_rf/dnn/models/sudormrf.py (the model of its ``run_sudormrf.py``): the same class names
+(whole-module pickles resolve), constructor signature and defaults, public attributes (``lcm`` included) and sub-module tree --
+therefore the same ``state_dict()`` keys, shapes and order: ``nn.GroupNorm(1, C, eps=1e-8)`` norms (``weight`` / ``bias``),
+``nn.PReLU(C)`` with one slope per channel, ``reshape_before_masks`` only when ``out_channels != enc_num_basis``, and
+``ln_mask_in``, which the reference's forward never uses but its checkpoints hold.  The torch sub-modules are PARAMETER
+CONTAINERS ONLY: ``SuDORMRF.forward`` hands the parameter pointers to one ``srf_forward`` call on a plan of
+``srf_original_plan_create`` (include/sudormrf_hip.h) and no ATen compute op runs.  Inference only; there is no CPU fallback.
+"""
+import math
+
+import torch
+import torch.nn as nn
+
+from ... import _lib, ops, original
+from ...engine import ModelEngine, _weights
+from .improved_sudormrf import _hip_only
+
+
+def _d(p):
+    return p.detach()
+
+
+class ConvNormAct(nn.Module):
+    """Conv1d + GroupNorm(1, nOut) + PReLU(nOut) (parameter container; forward: the 1x1 form on HIP)."""
+
+    def __init__(self, nIn, nOut, kSize, stride=1, groups=1):
+        super().__init__()
+        padding = int((kSize - 1) / 2)
+        self.conv = nn.Conv1d(nIn, nOut, kSize, stride=stride, padding=padding, bias=True, groups=groups)
+        self.norm = nn.GroupNorm(1, nOut, eps=1e-08)
+        self.act = nn.PReLU(nOut)
+
+    def forward(self, input):
+        x = _hip_only(input)
+        _only_1x1(self.conv)
+        s = ops.new_sums(x.shape[0], x.device)
+        y = ops.pw_conv(x, _d(self.conv.weight), _d(self.conv.bias), out_sums=s)
+        return original.gln_apply_c(y, s, _d(self.norm.weight), _d(self.norm.bias), slopes=_d(self.act.weight))
+
+
+class ConvNorm(nn.Module):
+    """Conv1d + GroupNorm(1, nOut)."""
+
+    def __init__(self, nIn, nOut, kSize, stride=1, groups=1):
+        super().__init__()
+        padding = int((kSize - 1) / 2)
+        self.conv = nn.Conv1d(nIn, nOut, kSize, stride=stride, padding=padding, bias=True, groups=groups)
+        self.norm = nn.GroupNorm(1, nOut, eps=1e-08)
+
+    def forward(self, input):
+        x = _hip_only(input)
+        _only_1x1(self.conv)
+        s = ops.new_sums(x.shape[0], x.device)
+        y = ops.pw_conv(x, _d(self.conv.weight), _d(self.conv.bias), out_sums=s)
+        return original.gln_apply_c(y, s, _d(self.norm.weight), _d(self.norm.bias))
+
+
+class NormAct(nn.Module):
+    """GroupNorm(1, nOut) + PReLU(nOut)."""
+
+    def __init__(self, nOut):
+        super().__init__()
+        self.norm = nn.GroupNorm(1, nOut, eps=1e-08)
+        self.act = nn.PReLU(nOut)
+
+    def forward(self, input):
+        x = _hip_only(input)
+        s = ops.gln_stats(x, x.shape[0])
+        return original.gln_apply_c(x, s, _d(self.norm.weight), _d(self.norm.bias), slopes=_d(self.act.weight))
+
+
+class DilatedConv(nn.Module):
+    """Conv1d with 'same' padding (dead code in the reference's model; kept so that pickles naming it resolve)."""
+
+    def __init__(self, nIn, nOut, kSize, stride=1, d=1, groups=1):
+        super().__init__()
+        self.conv = nn.Conv1d(nIn, nOut, kSize, stride=stride, dilation=d, padding=((kSize - 1) // 2) * d, groups=groups)
+
+    def forward(self, input):
+        c = self.conv
+        return ops.conv1d(_hip_only(input), _d(c.weight), _d(c.bias), stride=c.stride[0], padding=c.padding[0],
+                          dilation=c.dilation[0], groups=c.groups)
+
+
+class DilatedConvNorm(nn.Module):
+    """Depthwise Conv1d + GroupNorm(1, nOut)."""
+
+    def __init__(self, nIn, nOut, kSize, stride=1, d=1, groups=1):
+        super().__init__()
+        self.conv = nn.Conv1d(nIn, nOut, kSize, stride=stride, dilation=d, padding=((kSize - 1) // 2) * d, groups=groups)
+        self.norm = nn.GroupNorm(1, nOut, eps=1e-08)
+
+    def forward(self, input):
+        x = _hip_only(input)
+        c = self.conv
+        s = ops.new_sums(x.shape[0], x.device)
+        y = ops.conv1d(x, _d(c.weight), _d(c.bias), stride=c.stride[0], padding=c.padding[0], dilation=c.dilation[0],
+                       groups=c.groups, out_sums=s)
+        return original.gln_apply_c(y, s, _d(self.norm.weight), _d(self.norm.bias))
+
+
+def _only_1x1(conv):
+    if conv.kernel_size != (1,) or conv.stride != (1,) or conv.groups != 1:
+        raise _lib.SrfError("the HIP path runs this layer as a 1x1 convolution only (got kernel %s, stride %s, groups %d)"
+                            % (conv.kernel_size, conv.stride, conv.groups))
+
+
+class UBlock(nn.Module):
+    """REDUCE -> SPLIT -> TRANSFORM -> MERGE, with the residual added BEFORE the last norm."""
+
+    def __init__(self, out_channels=128, in_channels=512, upsampling_depth=4):
+        super().__init__()
+        self.proj_1x1 = ConvNormAct(out_channels, in_channels, 1, stride=1, groups=1)
+        self.depth = upsampling_depth
+        self.spp_dw = nn.ModuleList()
+        self.spp_dw.append(DilatedConvNorm(in_channels, in_channels, kSize=5, stride=1, groups=in_channels, d=1))
+        for _ in range(1, upsampling_depth):
+            self.spp_dw.append(DilatedConvNorm(in_channels, in_channels, kSize=5, stride=2, groups=in_channels, d=1))
+        if upsampling_depth > 1:
+            self.upsampler = torch.nn.Upsample(scale_factor=2)
+        self.conv_1x1_exp = ConvNorm(in_channels, out_channels, 1, 1, groups=1)
+        self.final_norm = NormAct(in_channels)
+        self.module_act = NormAct(out_channels)
+
+    def forward(self, x):
+        """The kernel sequence srf_forward runs for one block (stand-alone use / unit tests)."""
+        D = self.depth
+        x = _hip_only(x)
+        Bt, dev = x.shape[0], x.device
+        p = self.proj_1x1
+        s_proj = ops.new_sums(Bt, dev)
+        y1 = ops.pw_conv(x, _d(p.conv.weight), _d(p.conv.bias), out_sums=s_proj)
+        src = original.gln_apply_c(y1, s_proj, _d(p.norm.weight), _d(p.norm.bias), slopes=_d(p.act.weight))
+        levels, sums, norm = [], [], {}
+        for k in range(D):
+            m = self.spp_dw[k]
+            s_k = ops.new_sums(Bt, dev)
+            src = ops.dwconv5(src, _d(m.conv.weight), _d(m.conv.bias), 1 if k == 0 else 2, out_sums=s_k, **norm)
+            levels.append(src)
+            sums.append(s_k)
+            norm = dict(in_sums=s_k, in_gamma=_d(m.norm.weight), in_beta=_d(m.norm.bias))
+        s_fin, s_exp, s_act = (ops.new_sums(Bt, dev) for _ in range(3))
+        merged = ops.merge(levels, sums, [_d(m.norm.weight) for m in self.spp_dw], [_d(m.norm.bias) for m in self.spp_dw],
+                           out_sums=s_fin)
+        f, e, a = self.final_norm, self.conv_1x1_exp, self.module_act
+        act = original.gln_apply_c(merged, s_fin, _d(f.norm.weight), _d(f.norm.bias), slopes=_d(f.act.weight))
+        g = ops.pw_conv(act, _d(e.conv.weight), _d(e.conv.bias), out_sums=s_exp)
+        gx = original.gln_apply_c(g, s_exp, _d(e.norm.weight), _d(e.norm.bias), add=x, out_sums=s_act)
+        return original.gln_apply_c(gx, s_act, _d(a.norm.weight), _d(a.norm.bias), slopes=_d(a.act.weight))
+
+
+class SuDORMRF(nn.Module):
+    """Drop-in for the reference's original ``SuDORMRF``: forward([batch, 1, time]) -> [batch, num_sources, time]."""
+
+    def __init__(self,
+                 out_channels=128,
+                 in_channels=512,
+                 num_blocks=16,
+                 upsampling_depth=4,
+                 enc_kernel_size=21,
+                 enc_num_basis=512,
+                 num_sources=2):
+        super(SuDORMRF, self).__init__()
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.num_blocks = num_blocks
+        self.upsampling_depth = upsampling_depth
+        self.enc_kernel_size = enc_kernel_size
+        self.enc_num_basis = enc_num_basis
+        self.num_sources = num_sources
+        self.lcm = abs(self.enc_kernel_size // 2 * 2 ** self.upsampling_depth) // math.gcd(
+            self.enc_kernel_size // 2, 2 ** self.upsampling_depth)
+
+        self.encoder = nn.Sequential(*[
+            nn.Conv1d(in_channels=1, out_channels=enc_num_basis, kernel_size=enc_kernel_size, stride=enc_kernel_size // 2,
+                      padding=enc_kernel_size // 2),
+            nn.ReLU(),
+        ])
+        self.ln = nn.GroupNorm(1, enc_num_basis, eps=1e-08)
+        self.l1 = nn.Conv1d(in_channels=enc_num_basis, out_channels=out_channels, kernel_size=1)
+        self.sm = nn.Sequential(*[
+            UBlock(out_channels=out_channels, in_channels=in_channels, upsampling_depth=upsampling_depth)
+            for r in range(num_blocks)])
+        if out_channels != enc_num_basis:
+            self.reshape_before_masks = nn.Conv1d(in_channels=out_channels, out_channels=enc_num_basis, kernel_size=1)
+        self.m = nn.Conv2d(in_channels=1, out_channels=num_sources, kernel_size=(enc_num_basis + 1, 1),
+                           padding=(enc_num_basis - enc_num_basis // 2, 0))
+        self.decoder = nn.ConvTranspose1d(
+            in_channels=enc_num_basis * num_sources, out_channels=num_sources,
+            output_padding=(enc_kernel_size // 2) - 1, kernel_size=enc_kernel_size,
+            stride=enc_kernel_size // 2, padding=enc_kernel_size // 2, groups=num_sources)
+        self.ln_mask_in = nn.GroupNorm(1, enc_num_basis, eps=1e-08)      # (in the state_dict; never used in forward)
+
+    # -- engine plumbing (kept out of state_dict and rebuilt lazily, e.g. after unpickling) --------
+    def _config_tuple(self):
+        return ("original", 1, self.out_channels, self.in_channels, self.num_blocks, self.upsampling_depth,
+                self.enc_kernel_size, self.enc_num_basis, self.num_sources, 1)
+
+    def _engine(self):
+        eng = self.__dict__.get("_srf_engine")
+        if eng is None or eng.cfg_tuple != self._config_tuple():
+            eng = ModelEngine(self._config_tuple())
+            eng.multi_stream = False          # single stream only: the sub-batch split is not extended to this variant
+            self.__dict__["_srf_engine"] = eng
+        return eng
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state.pop("_srf_engine", None)
+        return state
+
+    def _check_inference(self, weights):
+        if torch.is_grad_enabled() and any(t.requires_grad for t in weights):
+            raise RuntimeError("original SuDoRM-RF on HIP has an inference forward only (no backward kernels): run it under "
+                               "torch.no_grad()")
+
+    def forward(self, input_wav):
+        """[batch, 1, time] float -> [batch, num_sources, time] float32: one srf_forward call on the caller's stream."""
+        if not isinstance(input_wav, torch.Tensor):
+            raise TypeError("input must be a torch.Tensor")
+        if input_wav.dim() != 3 or input_wav.shape[1] != 1:
+            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(input_wav.shape),))
+        weights = _weights(self)
+        self._check_inference(weights)
+        if input_wav.device.type != "cuda":
+            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
+                                "fallback (use the reference implementation for CPU inference)." % input_wav.device)
+        params = [p.detach() for p in weights]
+        for p in params:
+            if p.device != input_wav.device or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.SrfError("all parameters and buffers must be contiguous float32 on %s" % input_wav.device)
+        x = input_wav.detach().to(torch.float32).contiguous()
+        batch, _, T = x.shape
+        if batch == 0 or T == 0:
+            raise RuntimeError("empty input %s" % (tuple(input_wav.shape),))
+        eng = self._engine()
+        with torch.cuda.device(x.device), eng._run_lock(x.device):
+            plan = eng.plan_for(batch, T, x.device)
+            if plan.num_params != len(params):
+                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
+            out = torch.empty((batch, self.num_sources, T), dtype=torch.float32, device=x.device)
+            plan.forward(eng._param_table(params, x.device), x, out)
+            eng.last_plan = plan
+        return out
+
+    def forward_ragged(self, input_wav, lengths):
+        raise NotImplementedError("the original model has no ragged kernels: run the utterances one by one "
+                                  "(pipeline.separate_list does)")
+
+    def pad_to_appropriate_length(self, x):
+        """Kept for API parity: up to a multiple of lcm(K // 2, 2^D), only when the length is not one already.  The HIP path
+        folds the padding into its bounds checks and never materialises the padded tensor."""
+        values_to_pad = int(x.shape[-1]) % self.lcm
+        if values_to_pad:
+            padded = torch.zeros(list(x.shape[:-1]) + [x.shape[-1] + self.lcm - values_to_pad], dtype=torch.float32,
+                                 device=x.device)
+            padded[..., :x.shape[-1]] = x
+            return padded
+        return x
+
+    @staticmethod
+    def remove_trailing_zeros(padded_x, initial_x):
+        return padded_x[..., :initial_x.shape[-1]]

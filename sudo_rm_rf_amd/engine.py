@@ -34,7 +34,8 @@ _MAX_GRAPHS = 4
 
 def _config_struct(variant, in_audio_channels, out_channels, in_channels, num_blocks, upsampling_depth,
                    enc_kernel_size, enc_num_basis, num_sources, group_size):
-    variants = {"improved": _lib.VARIANT_IMPROVED, "groupcomm": _lib.VARIANT_GROUPCOMM, "causal": _lib.VARIANT_CAUSAL}
+    variants = {"improved": _lib.VARIANT_IMPROVED, "groupcomm": _lib.VARIANT_GROUPCOMM, "causal": _lib.VARIANT_CAUSAL,
+                "original": _lib.VARIANT_ORIGINAL}
     return _lib.srf_config(
         variant=variants.get(variant, _lib.VARIANT_IMPROVED),
         in_audio_channels=in_audio_channels, out_channels=out_channels, in_channels=in_channels,
@@ -55,6 +56,8 @@ class Plan:
         if attentive:
             create = "srf_attentive_plan_create" if cfg_tuple[0] == "attentive" else "srf_attentive_v3_plan_create"
             _lib.check(getattr(lib, create)(C.byref(cfg), cfg_tuple[10][0], cfg_tuple[10][1], batch, T, C.byref(handle)), create)
+        elif cfg_tuple[0] == "original":
+            _lib.check(lib.srf_original_plan_create(C.byref(cfg), batch, T, C.byref(handle)), "srf_original_plan_create")
         else:
             _lib.check(lib.srf_plan_create(C.byref(cfg), batch, T, C.byref(handle)), "srf_plan_create")
         self.handle = handle
