@@ -721,6 +721,12 @@ int srf_pit_sisdr_backward(const float* est, const float* tgt, int Bt, int S, in
 size_t srf_perm_inv_sisdr_work_bytes(int Bt, int S);
 int srf_perm_inv_sisdr(const float* pr, const float* tgt, const float* mix, int Bt, int S, int T, int zero_mean,
                        double eps, void* work, float* best, int* best_perm, float* base, void* stream);
+/* The class as a TRAINING loss (experiments/run_sudormrf.py:56-62,125-128 constructs it with backward_loss=True): the gradient of
+ * `best` w.r.t. the estimates with the class's own eps placement, from the `work` and `best_perm` the forward call above left
+ * (same Bt, S, T, zero_mean, eps): grad_pr[b] = upstream[b] * d best[b] / d pr[b]; upstream: [Bt] on the device; grad_pr
+ * [Bt,S,T], every element written, must not be pr or tgt.  The improvement baseline does not depend on the estimates. */
+int srf_perm_inv_sisdr_backward(const float* pr, const float* tgt, int Bt, int S, int T, int zero_mean, double eps,
+                                const void* work, const int* best_perm, const float* upstream, float* grad_pr, void* stream);
 
 /* ---- The FUSS recipe (ABI 18; experiments/run_fuss_separation.py) ----
  * Training loss PermInvariantSNRwithZeroRefs (losses/snr.py:13-142): up to 4 sources of which any number may be silent.
@@ -970,7 +976,7 @@ int srf_gln_apply_stats(const float* x, const srf_norm* norm, float* y, double* 
  * The model of the paper: an encoder WITH bias and ReLU, GroupNorm(1, C) everywhere (GlobLN's arithmetic), PReLU with one slope
  * PER CHANNEL, blocks whose residual is added before the last norm, a mask layer that is a convolution along the basis axis
  * (a [S N, N] Toeplitz GEMM) followed by a softmax over the sources (sigmoid for one source), and a grouped decoder with bias.
- * Inference only, one stream.
+ * One stream; inference through srf_forward / srf_separate, training through the opt-in walk further below.
  * srf_original_plan_create: padding up to a multiple of lcm(K / 2, 2^D), only when T is not one already.  The plan works with
  *   srf_forward, srf_separate (decoder.bias is added before the rescale and mixture consistency), srf_plan_workspace_bytes /
  *   _num_params / _frames / _padded_length / _num_launches, srf_debug_fetch (1: always the separation module's output; 3: the
@@ -1011,6 +1017,58 @@ int srf_softmax_mask(const float* z, const float* enc, float* v, int Bt, int S, 
 int srf_decoder_weight_expand(const float* w, float* wexp, int N, int S, int K, void* stream);
 int srf_bias_rescale(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
                      void* stream);
+
+/* ---- Original SuDoRM-RF: opt-in training step (csrc/srf_original_train.hip; additive to ABI 19) ----
+ * srf_original_forward_train is srf_forward's arithmetic for an original plan (the pyramid level by level, the 1x1 convolutions
+ *   in the exact-fp32 class as srf_forward_train runs them) and keeps what the backward needs in `saved`: the GroupNorm
+ *   statistics, the encoder output s, the block stream x_0 .. x_U, per block y1, the D raw levels, m, g and g + x, the mask GEMM's
+ *   input where reshape_before_masks exists, the logits z.  The activations a and e are NOT saved: the backward re-computes each
+ *   with one srf_gln_apply_c launch.
+ * srf_original_backward: grad_out [Bt, S, T] -> every parameter gradient, ACCUMULATED into grads[i] (same order and shapes as
+ *   params; the caller zeroes them).  Torch autograd over the reference's SuDORMRF.forward (sudormrf.py) -- there ln_mask_in.*
+ *   receives no gradient: the last two entries of grads may be NULL and are never written.  No gradient w.r.t. wav.
+ * saved / scratch: 256-byte aligned device buffers of srf_original_train_saved_bytes / _scratch_bytes (0 for any plan that is not
+ *   SRF_VARIANT_ORIGINAL); `saved` stays untouched between the two calls, `scratch` may be reused in between.  Both calls refuse
+ *   (SRF_EINVAL, before the first launch, naming the argument) any other plan, a parameter count that is not the plan's, a null
+ *   parameter / gradient, and a short or misaligned buffer.  The general srf_forward_train / srf_backward keep refusing the plan.
+ *
+ * The kernels this model's backward has that no other has.  Every parameter gradient is ACCUMULATED into; every reduction
+ * writes block partials and adds them in block order (no floating-point atomics): the same inputs give the same bits.
+ * srf_gln_c_bwd: backward of srf_gln_apply_c, y = [PReLU_c](norm(x)) [+ add] (the addend's gradient is gout itself).  gout
+ *   (+ optional gout2, added on load), x, gx: [groups, channels, length] at any float-aligned address, any length (16-byte
+ *   accesses where gout, gout2, x and gx share their phase on the 16-byte grid).  norm: {sums of x, gamma, beta}; slopes
+ *   [channels] or NULL (no activation).  With xh = (x - mean) rstd, v = gamma_c xh + beta_c, g' = gout (v >= 0 ? 1 : slope_c):
+ *   gx (accumulate_gx != 0: added to) = rstd (gamma_c g' - mean(gamma g') - xh mean(gamma g' xh)), the means over the example;
+ *   dgamma_c += sum g' xh, dbeta_c += sum g', dslope_c += sum gout v [v < 0] (each nullable; dslope ignored without slopes).
+ *   Two launches (reduce, apply); v is re-computed.  scratch: srf_gln_c_bwd_scratch_bytes(groups, channels, length), float-aligned.
+ * srf_softmax_mask_bwd: backward of srf_softmax_mask from the logits z and enc: p re-computed as the forward does (maximum
+ *   subtracted, expf), gz_s = p_s (gv_s enc - sum_r p_r gv_r enc) (S = 1: gv enc p (1 - p)), gz may be gv;
+ *   genc (accumulate_genc != 0: +=) sum_s gv_s p_s.  z, gv, gz: [Bt, S N, L]; enc, genc: [Bt, N, L].
+ * srf_mask_weight_fold: the transpose of srf_mask_weight_fill: dmw[s, j] += sum_{i, n: n - i + N - N / 2 = j} dtz[s N + i, n],
+ *   j = 0 .. N; dmb[s] += sum_i drow[s N + i].  dtz [S N, N], drow [S N].
+ * srf_decoder_weight_contract: dw[c, k] += dwexp[c, c / N, k]: the diagonal blocks of the [S N, S, K] gradient of the
+ *   block-diagonal decoder weight.
+ * srf_decoder_bias_grad: dbias[s] += sum_{b, t} grad_out[b, s, t], grad_out [Bt, S, T]; scratch:
+ *   srf_decoder_bias_grad_scratch_floats(S) floats.
+ * srf_relu_gate: g[i] = s[i] > 0 ? g[i] : 0 in place, s the saved post-ReLU output; n elements. */
+size_t srf_original_train_saved_bytes(const srf_plan* plan);
+size_t srf_original_train_scratch_bytes(const srf_plan* plan);
+int srf_original_forward_train(const srf_plan* plan, const float* const* params, int num_params, const float* wav, float* out,
+                               void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream);
+int srf_original_backward(const srf_plan* plan, const float* const* params, float* const* grads, int num_params, const float* wav,
+                          const float* grad_out, const void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
+                          void* stream);
+size_t srf_gln_c_bwd_scratch_bytes(int groups, int channels, int length);
+int srf_gln_c_bwd(const float* gout, const float* gout2, const float* x, const srf_norm* norm, const float* slopes, int groups,
+                  int channels, int length, float* gx, int accumulate_gx, float* dgamma, float* dbeta, float* dslope, void* scratch,
+                  void* stream);
+int srf_softmax_mask_bwd(const float* z, const float* enc, const float* gv, float* gz, float* genc, int accumulate_genc, int Bt,
+                         int S, int N, int L, void* stream);
+int srf_mask_weight_fold(const float* dtz, const float* drow, float* dmw, float* dmb, int N, int S, void* stream);
+int srf_decoder_weight_contract(const float* dwexp, float* dw, int N, int S, int K, void* stream);
+size_t srf_decoder_bias_grad_scratch_floats(int S);
+int srf_decoder_bias_grad(const float* grad_out, float* dbias, int Bt, int S, int T, float* scratch, void* stream);
+int srf_relu_gate(float* g, const float* s, long n, void* stream);
 
 #ifdef __cplusplus
 }

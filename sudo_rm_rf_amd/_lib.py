@@ -217,6 +217,19 @@ _PROTOS = {
     "srf_softmax_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "srf_decoder_weight_expand": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "srf_bias_rescale": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "srf_perm_inv_sisdr_backward": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "srf_original_train_saved_bytes": (_sz, [_vp]),
+    "srf_original_train_scratch_bytes": (_sz, [_vp]),
+    "srf_original_forward_train": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "srf_original_backward": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "srf_gln_c_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
+    "srf_gln_c_bwd": (_i, [_vp, _vp, _vp, C.POINTER(srf_norm), _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "srf_softmax_mask_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "srf_mask_weight_fold": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "srf_decoder_weight_contract": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "srf_decoder_bias_grad_scratch_floats": (_sz, [_i]),
+    "srf_decoder_bias_grad": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "srf_relu_gate": (_i, [_vp, _vp, _l, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

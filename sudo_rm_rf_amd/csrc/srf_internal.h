@@ -117,6 +117,9 @@ int srf_mask_decode(const float* x, const float* w, const void* w_packed, const 
 int srf_pack_pw_weights_transposed(const float* const* w, void* const* packed, const int* Cout, const int* Cin, int n,
                                    hipStream_t st);
 bool srf_pw_packed_only(const void* w_packed, const float* x, int Bt, int Cin, int Cout, int L);
+// srf_pack3_pw_weights / srf_pw_conv_packed3 of THIS thread take the three-bf16-part form (24 mantissa bits, what debug flag
+// 16384 selects process-wide) while on; returns the previous setting
+bool srf_train_three_parts_override(bool on);
 // A backward's data-gradient GEMM gx = W^T g (+ skip), Cin -> Cout, W the FORWARD weight [Cin][Cout]: from the packed image
 // of W^T where that serves the whole launch (srf_pw_packed_only), else from its fp32 transpose, made in `wt` first
 int srf_pw_data_grad(const float* g, const float* w, const void* wT_packed, float* wt, const float* zero_bias, float* gx, int Bt,

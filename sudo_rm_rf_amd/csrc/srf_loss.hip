@@ -475,3 +475,89 @@ extern "C" int srf_perm_inv_sisdr(const float* pr, const float* tgt, const float
   SRF_CHECK_LAUNCH("perm_inv_sisdr", st);
   return SRF_OK;
 }
+
+// =============================================================================================
+// PermInvariantSISDR as a training loss (run_sudormrf.py:56-62,125-128 trains with it): the gradient of `best` w.r.t. the
+// estimates, from what srf_perm_inv_sisdr left in `work` (the inner products) and `best_perm`.  For target j and its matched
+// estimate p = pr[perm[j]] (both centred when zero_mean), with al = <p,t> / (<t,t> + eps), ss = al^2 <t,t>,
+// ee = <p - al t, p - al t> and k = 10 / ln 10:
+//   d sisnr_j / d p = k [ (2 al <t,t> / ((<t,t> + eps) ss) + (4 al - 2 al <t,t> / (<t,t> + eps)) / (ee + eps)) t - 2 / (ee + eps) p ]
+// (a combination of two centred signals: the centring's own derivative changes nothing), and best = mean_j sisnr_j, so
+//   grad_pr[b, perm[j], :] = upstream[b] / S * d sisnr_j / d p.
+// One block per (chunk of T, example); the permutation (itertools order = lexicographic) and the S coefficient pairs in LDS.
+// =============================================================================================
+__global__ __launch_bounds__(256) void srf_perm_inv_bwd_kernel(const float* __restrict__ pr, const float* __restrict__ tgt,
+                                                               const double* __restrict__ work, const int* __restrict__ best_perm,
+                                                               const float* __restrict__ upstream, float* __restrict__ grad, int S,
+                                                               int T, int zero_mean, double eps, int per_block) {
+  // per target j: the matched estimate, the coefficients of the centred target / estimate, their means (block-uniform: LDS)
+  __shared__ int perm[SRF_LOSS_MAX_SRC_ANY];
+  __shared__ float ca[SRF_LOSS_MAX_SRC_ANY], cb[SRF_LOSS_MAX_SRC_ANY], me[SRF_LOSS_MAX_SRC_ANY], mt[SRF_LOSS_MAX_SRC_ANY];
+  const long b = blockIdx.y;
+  const int nstat = 4 * S + S * S;
+  const double* w = work + b * nstat;
+  if (threadIdx.x == 0) {      // permutation number -> perm[j]
+    int idx = best_perm[b];
+    unsigned used = 0;
+    for (int j = 0; j < S; ++j) {
+      int f = 1;
+      for (int r = 2; r <= S - 1 - j; ++r) f *= r;
+      const int q = idx / f;
+      idx -= q * f;
+      int pick = 0, seen = 0;
+      for (int e = 0; e < S; ++e)      // the q-th estimate not used yet (the last free one for an index past S! - 1: never out of [0, S))
+        if (!((used >> e) & 1)) {
+          if (seen <= q) pick = e;
+          ++seen;
+        }
+      used |= 1u << pick;
+      perm[j] = pick;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < S) {
+    const int j = threadIdx.x, i = perm[j];
+    const double dT = (double)T, zm = zero_mean ? 1.0 : 0.0;
+    const double up = (double)upstream[b] / (double)S, k = 10.0 / log(10.0);
+    const double mei = zm * w[i] / dT, mtj = zm * w[2 * S + j] / dT;
+    const double pp = w[S + i] - dT * mei * mei, tt = w[3 * S + j] - dT * mtj * mtj, pt = w[4 * S + i * S + j] - dT * mei * mtj;
+    const double al = pt / (tt + eps), ss = al * al * tt;
+    double ee = pp - 2.0 * al * pt + al * al * tt;
+    ee = ee < 0.0 ? 0.0 : ee;
+    const double r = tt / (tt + eps);
+    ca[j] = (float)(up * k * (2.0 * al * r / ss + (4.0 * al - 2.0 * al * r) / (ee + eps)));
+    cb[j] = (float)(up * k * (-2.0 / (ee + eps)));
+    me[j] = (float)mei;
+    mt[j] = (float)mtj;
+  }
+  __syncthreads();
+  const int beg = blockIdx.x * per_block, end = min(beg + per_block, T);
+  const float* pb = pr + b * (long)S * T;
+  const float* tb = tgt + b * (long)S * T;
+  float* gb = grad + b * (long)S * T;
+  for (int j = 0; j < S; ++j) {
+    const long at = (long)perm[j] * T;
+    const float a = ca[j], c = cb[j], mp = me[j], mq = mt[j];
+    for (int t = beg + threadIdx.x; t < end; t += 256) gb[at + t] = a * (tb[(long)j * T + t] - mq) + c * (pb[at + t] - mp);
+  }
+}
+
+extern "C" int srf_perm_inv_sisdr_backward(const float* pr, const float* tgt, int Bt, int S, int T, int zero_mean, double eps,
+                                           const void* work, const int* best_perm, const float* upstream, float* grad_pr,
+                                           void* stream) {
+  SRF_CHECK_ARG(pr && tgt && work && best_perm && upstream && grad_pr, "srf_perm_inv_sisdr_backward: null pointer");
+  SRF_CHECK_ARG(Bt > 0 && Bt <= 65535 && T > 0, "srf_perm_inv_sisdr_backward: bad sizes");
+  SRF_CHECK_ARG(S >= 1 && S <= SRF_LOSS_MAX_SRC_ANY, "srf_perm_inv_sisdr_backward: %d sources unsupported (1..%d)", S,
+                SRF_LOSS_MAX_SRC_ANY);
+  SRF_CHECK_ARG((((size_t)pr | (size_t)tgt | (size_t)upstream | (size_t)grad_pr | (size_t)best_perm) & 3) == 0 && ((size_t)work & 7) == 0,
+                "srf_perm_inv_sisdr_backward: misaligned operand");
+  SRF_CHECK_ARG((const void*)grad_pr != (const void*)pr && (const void*)grad_pr != (const void*)tgt,
+                "srf_perm_inv_sisdr_backward: grad_pr must not be pr or tgt");
+  const int per_block = 256 * 16;
+  dim3 grid((unsigned)((T + per_block - 1) / per_block), (unsigned)Bt);
+  const double* stats = reinterpret_cast<const double*>(work);
+  hipLaunchKernelGGL(srf_perm_inv_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, pr, tgt, stats, best_perm, upstream, grad_pr, S,
+                     T, zero_mean, eps, per_block);
+  SRF_CHECK_LAUNCH("perm_inv_sisdr_bwd", stream);
+  return SRF_OK;
+}

@@ -1,5 +1,6 @@
 // Original SuDoRM-RF (sudormrf.py, the model of the paper): plan constructor, the inference walk and the kernels it has that no
-// other variant has.  Inference only, single stream.  Parameter and slot layout: srf_plan.h.
+// other variant has.  Single stream.  The training walk over the same plan: srf_original_train.hip.  Parameter and slot layout:
+// srf_plan.h.
 //
 //   s   = relu(encoder.0(wav))                                srf_encoder_bias_relu (+ statistics of ln)
 //   x   = l1(ln(s))                                           srf_pw_conv_packed    (ln on load)
@@ -384,8 +385,6 @@ extern "C" int srf_bias_rescale(float* out, const float* bias, const float* stat
 // plan
 // ---------------------------------------------------------------------------------------------
 static long orig_gcd(long a, long b) { return b ? orig_gcd(b, a % b) : a; }
-// floats of the Toeplitz weight's region: tz [S N, N] | bias rows [S N]   (each section 64-float aligned)
-static inline size_t orig_tz_floats(int S, int N) { return srf_align_up((size_t)S * N * N, 64) + srf_align_up((size_t)S * N, 64); }
 
 extern "C" int srf_original_plan_create(const srf_config* base, int batch, int T, srf_plan** out) {
   SRF_CHECK_ARG(base && out, "srf_original_plan_create: null pointer");

@@ -210,43 +210,51 @@ static inline int orig_p_exp(const srf_plan* p, int i) { return orig_p_proj(p, i
 static inline bool orig_has_reshape(const srf_plan* p) { return p->cfg.out_channels != p->cfg.enc_num_basis; }
 static inline int orig_p_reshape(const srf_plan* p) { return p->p_tail; }                       // (only where orig_has_reshape)
 static inline int orig_p_mask(const srf_plan* p) { return p->p_tail + (orig_has_reshape(p) ? 2 : 0); }
-struct SrfOrigFront { const float *enc_w, *enc_b, *ln_g, *ln_b, *l1_w, *l1_b; };
-struct SrfOrigBlock {
-  const float *proj_w, *proj_b, *proj_g, *proj_be, *proj_slope;
-  const float *lv_w[SRF_MAX_DEPTH], *lv_b[SRF_MAX_DEPTH], *lv_g[SRF_MAX_DEPTH], *lv_be[SRF_MAX_DEPTH];
-  const float *exp_w, *exp_b, *exp_g, *exp_be;
-  const float *fin_g, *fin_be, *fin_slope;
-  const float *act_g, *act_be, *act_slope;
+// T = const float: the parameters; T = float: the training backward's gradients (same indices)
+template <typename T> struct SrfOrigFrontT { T *enc_w, *enc_b, *ln_g, *ln_b, *l1_w, *l1_b; };
+template <typename T> struct SrfOrigBlockT {
+  T *proj_w, *proj_b, *proj_g, *proj_be, *proj_slope;
+  T *lv_w[SRF_MAX_DEPTH], *lv_b[SRF_MAX_DEPTH], *lv_g[SRF_MAX_DEPTH], *lv_be[SRF_MAX_DEPTH];
+  T *exp_w, *exp_b, *exp_g, *exp_be;
+  T *fin_g, *fin_be, *fin_slope;
+  T *act_g, *act_be, *act_slope;
   int i_proj, i_exp;   // parameter indices of the two packable weights (pk_of_param)
 };
-struct SrfOrigTail { const float *rs_w, *rs_b, *m_w, *m_b, *dec_w, *dec_b; int i_rs, i_m; };
+template <typename T> struct SrfOrigTailT { T *rs_w, *rs_b, *m_w, *m_b, *dec_w, *dec_b; int i_rs, i_m; };
+using SrfOrigFront = SrfOrigFrontT<const float>;
+using SrfOrigBlock = SrfOrigBlockT<const float>;
+using SrfOrigTail = SrfOrigTailT<const float>;
 struct SrfOrigSlots { double *proj, *level[SRF_MAX_DEPTH], *merged, *exp, *act; };
-static inline SrfOrigFront orig_front(const float* const* t) { return SrfOrigFront{t[0], t[1], t[2], t[3], t[SRF_PO_L1], t[SRF_PO_L1 + 1]}; }
-static inline SrfOrigBlock orig_block(const srf_plan* p, const float* const* t, int i) {
+template <typename T> static inline SrfOrigFrontT<T> orig_front(T* const* t) {
+  return SrfOrigFrontT<T>{t[0], t[1], t[2], t[3], t[SRF_PO_L1], t[SRF_PO_L1 + 1]};
+}
+template <typename T> static inline SrfOrigBlockT<T> orig_block(const srf_plan* p, T* const* t, int i) {
   const int D = p->cfg.upsampling_depth;
-  SrfOrigBlock b{};
+  SrfOrigBlockT<T> b{};
   b.i_proj = orig_p_proj(p, i);
   b.i_exp = orig_p_exp(p, i);
-  const float* const* u = t + b.i_proj;
+  T* const* u = t + b.i_proj;
   b.proj_w = u[0], b.proj_b = u[1], b.proj_g = u[2], b.proj_be = u[3], b.proj_slope = u[4];
   for (int k = 0; k < D; ++k) {
-    const float* const* l = u + 5 + 4 * k;
+    T* const* l = u + 5 + 4 * k;
     b.lv_w[k] = l[0], b.lv_b[k] = l[1], b.lv_g[k] = l[2], b.lv_be[k] = l[3];
   }
-  const float* const* e = t + b.i_exp;
+  T* const* e = t + b.i_exp;
   b.exp_w = e[0], b.exp_b = e[1], b.exp_g = e[2], b.exp_be = e[3];
   b.fin_g = e[4], b.fin_be = e[5], b.fin_slope = e[6];
   b.act_g = e[7], b.act_be = e[8], b.act_slope = e[9];
   return b;
 }
-static inline SrfOrigTail orig_tail(const srf_plan* p, const float* const* t) {
-  SrfOrigTail v{};
+template <typename T> static inline SrfOrigTailT<T> orig_tail(const srf_plan* p, T* const* t) {
+  SrfOrigTailT<T> v{};
   v.i_rs = orig_p_reshape(p);
   v.i_m = orig_p_mask(p);
   if (orig_has_reshape(p)) v.rs_w = t[v.i_rs], v.rs_b = t[v.i_rs + 1];
   v.m_w = t[v.i_m], v.m_b = t[v.i_m + 1], v.dec_w = t[v.i_m + 2], v.dec_b = t[v.i_m + 3];
   return v;
 }
+// floats of the Toeplitz weight's region: tz [S N, N] | bias rows [S N]   (each section 64-float aligned)
+static inline size_t orig_tz_floats(int S, int N) { return srf_align_up((size_t)S * N * N, 64) + srf_align_up((size_t)S * N, 64); }
 static inline SrfOrigSlots orig_slots(const srf_plan* p, double* stats, int i) {
   const size_t each = (size_t)p->Bg * SRF_STAT_BUCKETS * 2;
   const int D = p->cfg.upsampling_depth;

@@ -391,7 +391,15 @@ int srf_mask_decode(const float* x, const float* w, const void* w_packed, const 
 // we have; an operand beyond the range (or NaN / inf) makes its output column non-finite -- loud, like the fp32 reference's own
 // overflow, not clamped (round 5) -- and flag 16384 (three bf16 parts) is the form without the limit.
 // The packed3 buffer then holds the fp16 image (half its size).
-static bool srf_train_f16_split() { return !srf_dbg(SRF_DBG_TRAIN_BF16X3); }
+// A walk that needs all 24 bits whatever the flag says asks for the three-part form for its own launches (per thread, like the
+// kernel mode override): the original model's training forward (srf_original_train.hip).
+static thread_local bool g_train_three_parts = false;
+bool srf_train_three_parts_override(bool on) {
+  const bool prev = g_train_three_parts;
+  g_train_three_parts = on;
+  return prev;
+}
+static bool srf_train_f16_split() { return !g_train_three_parts && !srf_dbg(SRF_DBG_TRAIN_BF16X3); }
 // The two image formats differ in layout and size, and which one a buffer holds is decided at PACK time: every
 // buffer srf_pack3_pw_weights has written is remembered with its format (device, address), and a launch whose flag disagrees
 // with the buffer it is handed is refused with SRF_EINVAL instead of reinterpreting the bits.  (A buffer this process never

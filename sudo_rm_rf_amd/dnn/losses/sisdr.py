@@ -145,13 +145,54 @@ class PITLossWrapper(nn.Module):
         return torch.gather(est_targets, 1, idx)
 
 
+class _PermInvBest(torch.autograd.Function):
+    """best [Bt] of srf_perm_inv_sisdr as a differentiable function of the estimates (srf_perm_inv_sisdr_backward: one streaming
+    pass from the forward's inner products and best permutation).  Returns (best, perm, base); only best carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, pr, tg, mix, zero_mean, eps):
+        lib = _lib.load()
+        Bt, S, T = pr.shape
+        dev = pr.device
+        with torch.cuda.device(dev):
+            work = torch.empty(lib.srf_perm_inv_sisdr_work_bytes(Bt, S), dtype=torch.uint8, device=dev)
+            best = torch.empty(Bt, dtype=torch.float32, device=dev)
+            perm = torch.empty(Bt, dtype=torch.int32, device=dev)
+            base = torch.empty(Bt * S, dtype=torch.float32, device=dev) if mix is not None else None
+            rc = lib.srf_perm_inv_sisdr(_lib.ptr(pr), _lib.ptr(tg), _lib.ptr(mix), Bt, S, T, zero_mean, C.c_double(eps), _lib.ptr(work),
+                                        _lib.ptr(best), _lib.ptr(perm), _lib.ptr(base), _lib.current_stream(dev))
+        _lib.check(rc, "srf_perm_inv_sisdr")
+        ctx.save_for_backward(pr, tg, work, perm)
+        ctx.args = (zero_mean, eps)
+        ctx.mark_non_differentiable(perm)
+        if base is None:
+            return best, perm
+        ctx.mark_non_differentiable(base)
+        return best, perm, base
+
+    @staticmethod
+    def backward(ctx, grad_best, *unused):
+        pr, tg, work, perm = ctx.saved_tensors
+        zero_mean, eps = ctx.args
+        Bt, S, T = pr.shape
+        dev = pr.device
+        up = grad_best.detach().to(torch.float32).contiguous()
+        grad = torch.empty_like(pr)
+        with torch.cuda.device(dev):
+            rc = _lib.load().srf_perm_inv_sisdr_backward(_lib.ptr(pr), _lib.ptr(tg), Bt, S, T, zero_mean, C.c_double(eps), _lib.ptr(work),
+                                                         _lib.ptr(perm), _lib.ptr(up), _lib.ptr(grad), _lib.current_stream(dev))
+        _lib.check(rc, "srf_perm_inv_sisdr_backward")
+        return grad, None, None, None, None
+
+
 class PermInvariantSISDR(nn.Module):
-    """The runners' validation metric (reference: losses/sisdr.py:66-196): permutation-invariant SI-SNR of
-    reconstructed vs target wavs, optionally as an improvement over the input mixture.  Same constructor and
-    ``forward`` arguments; one streaming pass over the signals + a per-example finalize (csrc/srf_loss.hip:
-    srf_perm_inv_sisdr) instead of the S! materialised permuted copies.  Evaluation only: it raises under autograd
-    (the runners train with PITLossWrapper; their PermInvariantSISDR training line is commented out,
-    run_improved_sudormrf.py:68-71)."""
+    """The runners' validation metric, and run_sudormrf.py's training loss (reference: losses/sisdr.py:66-196):
+    permutation-invariant SI-SNR of reconstructed vs target wavs, optionally as an improvement over the input mixture.  Same
+    constructor and ``forward`` arguments; one streaming pass over the signals + a per-example finalize (csrc/srf_loss.hip:
+    srf_perm_inv_sisdr) instead of the S! materialised permuted copies.  Constructed with ``backward_loss=True`` -- how the
+    runners that train with it construct it -- estimates that require grad get their gradient (srf_perm_inv_sisdr_backward, the
+    class's own eps placement); with ``backward_loss=False`` (the metric) it raises under autograd, as do targets that require
+    grad."""
 
     def __init__(self, batch_size=None, zero_mean=False, n_sources=None, backward_loss=True, improvement=False,
                  return_individual_results=False):
@@ -166,9 +207,11 @@ class PermInvariantSISDR(nn.Module):
         self.return_individual_results = return_individual_results
 
     def forward(self, pr_batch, t_batch, eps=1e-9, initial_mixtures=None, return_best_permutation=False):
-        if torch.is_grad_enabled() and (pr_batch.requires_grad or t_batch.requires_grad):
-            raise NotImplementedError("PermInvariantSISDR is an evaluation metric on the HIP path (no backward): "
-                                      "call it under torch.no_grad(), train with PITLossWrapper")
+        wants_grad = torch.is_grad_enabled() and (pr_batch.requires_grad or t_batch.requires_grad)
+        if wants_grad and (not self.backward_loss or t_batch.requires_grad):
+            raise NotImplementedError("PermInvariantSISDR is an evaluation metric on the HIP path (no backward) unless it was "
+                                      "constructed with backward_loss=True, and then for the estimates only: call it under "
+                                      "torch.no_grad(), or train with backward_loss=True / PITLossWrapper")
         if pr_batch.dim() != 3 or t_batch.dim() != 3 or pr_batch.shape[:2] != t_batch.shape[:2]:
             raise RuntimeError("expected [batch, n_src, time] estimates and targets, got %s and %s" %
                                (tuple(pr_batch.shape), tuple(t_batch.shape)))
@@ -186,22 +229,14 @@ class PermInvariantSISDR(nn.Module):
         if initial_mixtures is not None:
             min_len = min(min_len, initial_mixtures.shape[-1])
         dev = pr_batch.device
-        pr = pr_batch.detach()[:, :, :min_len].to(torch.float32).contiguous()
+        pr = (pr_batch if wants_grad else pr_batch.detach())[:, :, :min_len].to(torch.float32).contiguous()
         tg = t_batch.detach()[:, :, :min_len].to(torch.float32).contiguous()
         mix = None
         if initial_mixtures is not None and self.improvement:
             mix = initial_mixtures.detach()[:, :1, :min_len].to(device=dev, dtype=torch.float32).contiguous()
-        Bt, S, T = pr.shape
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            work = torch.empty(lib.srf_perm_inv_sisdr_work_bytes(Bt, S), dtype=torch.uint8, device=dev)
-            best = torch.empty(Bt, dtype=torch.float32, device=dev)
-            perm = torch.empty(Bt, dtype=torch.int32, device=dev)
-            base = torch.empty(Bt * S, dtype=torch.float32, device=dev) if mix is not None else None
-            rc = lib.srf_perm_inv_sisdr(_lib.ptr(pr), _lib.ptr(tg), _lib.ptr(mix), Bt, S, T,
-                                        1 if self.perform_zero_mean else 0, C.c_double(float(eps)), _lib.ptr(work),
-                                        _lib.ptr(best), _lib.ptr(perm), _lib.ptr(base), _lib.current_stream(dev))
-        _lib.check(rc, "srf_perm_inv_sisdr")
+        res = _PermInvBest.apply(pr, tg, mix, 1 if self.perform_zero_mean else 0, float(eps))
+        best, perm = res[0], res[1]
+        base = res[2] if mix is not None else None
         best_sisdr = best
         if self.improvement:
             best_sisdr = best_sisdr - base.mean()             # one batch-and-source mean, as sisdr.py:154

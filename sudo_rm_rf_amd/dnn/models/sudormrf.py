@@ -6,7 +6,9 @@ therefore the same ``state_dict()`` keys, shapes and order: ``nn.GroupNorm(1, C,
 ``nn.PReLU(C)`` with one slope per channel, ``reshape_before_masks`` only when ``out_channels != enc_num_basis``, and
 ``ln_mask_in``, which the reference's forward never uses but its checkpoints hold.  The torch sub-modules are PARAMETER
 CONTAINERS ONLY: ``SuDORMRF.forward`` hands the parameter pointers to one ``srf_forward`` call on a plan of
-``srf_original_plan_create`` (include/sudormrf_hip.h) and no ATen compute op runs.  Inference only; there is no CPU fallback.
+``srf_original_plan_create`` (include/sudormrf_hip.h) and no ATen compute op runs.  By default the path is inference-only: a forward
+that autograd would have to differentiate raises.  ``SuDORMRF.enable_hip_training()`` opts a model into the HIP training step
+(srf_original_forward_train / srf_original_backward).  There is no CPU fallback.
 """
 import math
 
@@ -209,7 +211,22 @@ class SuDORMRF(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state.pop("_srf_engine", None)
+        state.pop("_srf_hip_training", None)
         return state
+
+    def enable_hip_training(self, flag=True):
+        """Opt this model into (flag=False: out of) the HIP training step and return self.  With it, a forward that autograd
+        has to differentiate -- in train() or eval() mode alike: GroupNorm does not differ between them -- runs
+        srf_original_forward_train and its backward srf_original_backward: gradients for every parameter as torch autograd over
+        the reference's forward gives them; ``ln_mask_in.*``, which that forward never reads, keep ``.grad is None``.  Without
+        autograd the inference path is untouched; the sub-module forwards keep refusing autograd; a mixture that requires grad
+        is refused (no gradient w.r.t. the input).  The flag is a plain attribute beside the engine: not in state_dict() and
+        dropped from pickles, so a model that was unpickled has to opt in again."""
+        if flag:
+            self.__dict__["_srf_hip_training"] = True
+        else:
+            self.__dict__.pop("_srf_hip_training", None)
+        return self
 
     def _check_inference(self, weights):
         if torch.is_grad_enabled() and any(t.requires_grad for t in weights):
@@ -217,12 +234,19 @@ class SuDORMRF(nn.Module):
                                "torch.no_grad()")
 
     def forward(self, input_wav):
-        """[batch, 1, time] float -> [batch, num_sources, time] float32: one srf_forward call on the caller's stream."""
+        """[batch, 1, time] float -> [batch, num_sources, time] float32: one srf_forward call on the caller's stream.  Inference
+        only, unless enable_hip_training() was called: then a forward under autograd is the HIP training step."""
         if not isinstance(input_wav, torch.Tensor):
             raise TypeError("input must be a torch.Tensor")
         if input_wav.dim() != 3 or input_wav.shape[1] != 1:
             raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(input_wav.shape),))
         weights = _weights(self)
+        if self.__dict__.get("_srf_hip_training") and torch.is_grad_enabled() and (
+                input_wav.requires_grad or any(t.requires_grad for t in weights)):
+            if input_wav.requires_grad:
+                raise NotImplementedError("SuDORMRF.forward: the HIP training step has no gradient w.r.t. the input mixture; "
+                                          "pass a mixture that does not require grad")
+            return self._engine().run_original_train(self, input_wav)
         self._check_inference(weights)
         if input_wav.device.type != "cuda":
             raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "

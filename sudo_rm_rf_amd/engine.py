@@ -116,6 +116,17 @@ class Plan:
             self._causal_train_scratch = torch.empty(self.causal_train_sizes()[1], dtype=torch.uint8, device=self.device)
         return self._causal_train_scratch
 
+    def original_train_sizes(self):
+        """(saved bytes, scratch bytes) of the original model's training step (srf_original_forward_train / srf_original_backward)."""
+        lib = _lib.load()
+        return lib.srf_original_train_saved_bytes(self.handle), lib.srf_original_train_scratch_bytes(self.handle)
+
+    def original_train_scratch(self):
+        """Scratch of the original model's training step, shared by every step of this plan (stream-ordered reuse)."""
+        if getattr(self, "_original_train_scratch", None) is None:
+            self._original_train_scratch = torch.empty(self.original_train_sizes()[1], dtype=torch.uint8, device=self.device)
+        return self._original_train_scratch
+
     def forward(self, param_ptrs, wav, out):
         lib = _lib.load()
         rc = lib.srf_forward(self.handle, param_ptrs, self.num_params, _lib.ptr(wav), _lib.ptr(out),
@@ -287,6 +298,65 @@ class _CausalTrainStep(torch.autograd.Function):
         return (None, None, None) + tuple(grads)
 
 
+class _OriginalTrainStep(torch.autograd.Function):
+    """The original SuDORMRF.forward under autograd (opt-in, SuDORMRF.enable_hip_training): srf_original_forward_train keeps
+    what the backward needs in one `saved` buffer, srf_original_backward accumulates every parameter gradient into one zeroed
+    flat buffer that is returned as per-parameter views -- the mirror of _CausalTrainStep.  ln_mask_in.{weight, bias}, the last
+    two tensors of the state_dict, are never read by the forward: they get None, as under the reference's autograd.  The
+    mixture gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, engine, out_ch, wav, *params):
+        lib = _lib.load()
+        x = wav.detach().to(torch.float32).contiguous()
+        batch, _, T = x.shape
+        dev = x.device
+        with torch.cuda.device(dev), engine._run_lock(dev):
+            plan = engine.plan_for(batch, T, dev)
+            if plan.num_params != len(params):
+                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
+            saved_bytes, scratch_bytes = plan.original_train_sizes()
+            saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+            scratch = plan.original_train_scratch()
+            out = torch.empty((batch, out_ch, T), dtype=torch.float32, device=dev)
+            table = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
+            rc = lib.srf_original_forward_train(plan.handle, table, len(params), _lib.ptr(x), _lib.ptr(out), _lib.ptr(saved),
+                                                saved_bytes, _lib.ptr(scratch), scratch_bytes, _lib.current_stream(dev))
+            _lib.check(rc, "srf_original_forward_train")
+        ctx.plan, ctx.saved_buf, ctx.x, ctx.engine = plan, saved, x, engine
+        ctx.save_for_backward(*params)
+        engine.last_plan = plan
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        params = ctx.saved_tensors
+        plan, saved, x = ctx.plan, ctx.saved_buf, ctx.x
+        if saved is None:
+            raise RuntimeError("the saved activations of this step were released by its first backward")
+        dev = x.device
+        g = grad_out.detach().to(torch.float32).contiguous()
+        live = params[:-2]                        # (ln_mask_in.*: no gradient)
+        sizes = [p.numel() for p in live]
+        flat = ctx.engine._flat_grad_buffer(live, sum(sizes), dev)
+        grads, off = [], 0
+        for p, n in zip(live, sizes):
+            grads.append(flat[off:off + n].view_as(p))
+            off += n
+        with torch.cuda.device(dev), ctx.engine._run_lock(dev):
+            scratch = plan.original_train_scratch()
+            ptab = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
+            gtab = (C.c_void_p * len(params))(*([t.data_ptr() for t in grads] + [None, None]))
+            rc = lib.srf_original_backward(plan.handle, ptab, gtab, len(params), _lib.ptr(x), _lib.ptr(g), _lib.ptr(saved),
+                                           saved.numel(), _lib.ptr(scratch), scratch.numel(), _lib.current_stream(dev))
+            _lib.check(rc, "srf_original_backward")
+        if not ctx.engine.keep_saved_for_repeat:
+            ctx.saved_buf = None
+        ctx.engine.last_flat_grad = flat
+        return (None, None, None) + tuple(grads) + (None, None)
+
+
 def _weights(module):
     """The module's weight tensors in state_dict() order.  For an ordinary module that is exactly
     state_dict(keep_vars=True).values(); a torch.nn.DataParallel replica keeps its (broadcast, non-leaf) weights in
@@ -414,6 +484,23 @@ class ModelEngine:
         if wav.shape[0] == 0 or wav.shape[-1] == 0:
             raise RuntimeError("empty input %s" % (tuple(wav.shape),))
         return _CausalTrainStep.apply(self, module.num_sources * expected_channels, wav, *params)
+
+    def run_original_train(self, module, wav):
+        """The opted-in original model under autograd: one _OriginalTrainStep ([batch, 1, time] on the MI355X)."""
+        if not isinstance(wav, torch.Tensor):
+            raise TypeError("input must be a torch.Tensor")
+        if wav.dim() != 3 or wav.shape[1] != 1:
+            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(wav.shape),))
+        if wav.device.type != "cuda":
+            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
+                                "fallback." % wav.device)
+        params = _weights(module)
+        for p in params:
+            if p.device != wav.device or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % wav.device)
+        if wav.shape[0] == 0 or wav.shape[-1] == 0:
+            raise RuntimeError("empty input %s" % (tuple(wav.shape),))
+        return _OriginalTrainStep.apply(self, module.num_sources, wav, *params)
 
     def _run_train(self, module, wav, expected_channels):
         params = _weights(module)

@@ -1,4 +1,5 @@
-"""Thin ctypes wrappers of the original SuDoRM-RF's own kernels (csrc/srf_original.hip; include/sudormrf_hip.h, "Original SuDoRM-RF").
+"""Thin ctypes wrappers of the original SuDoRM-RF's own kernels (csrc/srf_original.hip, csrc/srf_original_train.hip;
+include/sudormrf_hip.h, "Original SuDoRM-RF").
 
 Same conventions as ``ops``: CUDA float32 tensors in, new tensors out (or ``out=``), torch's current stream.  Kept out of ``ops``
 on purpose: these serve the original model's sub-module forwards and the kernel tests only."""
@@ -85,3 +86,77 @@ def bias_rescale(est, bias, stats=None, wav=None, mixture_consistency=False):
                                       Bt, S, T, _lib.current_stream(dev))
     _lib.check(rc, "srf_bias_rescale")
     return est
+
+
+# ---- the training step's own kernels (csrc/srf_original_train.hip).  Parameter gradients are ACCUMULATED into the tensors given.
+def gln_c_bwd(gout, x, sums, gamma, beta, slopes=None, gout2=None, gx=None, accumulate=False, dgamma=None, dbeta=None, dslope=None):
+    """Backward of gln_apply_c: gout (+ gout2) is the gradient w.r.t. [PReLU_c](GlobLN(x)); returns gx [groups, C, L] (given and
+    accumulate: added to); dgamma, dbeta, dslope [C] += their sums where given."""
+    dev = _chk(gout, x, sums, gamma, beta, slopes, gout2, gx, dgamma, dbeta, dslope)
+    groups, channels, length = x.shape
+    lib = _lib.load()
+    if gx is None:
+        if accumulate:
+            raise _lib.SrfError("gln_c_bwd: accumulate needs the gx to add to")
+        gx = torch.empty_like(x)
+    scratch = torch.empty(lib.srf_gln_c_bwd_scratch_bytes(groups, channels, length), dtype=torch.uint8, device=dev)
+    rc = lib.srf_gln_c_bwd(_lib.ptr(gout), _lib.ptr(gout2), _lib.ptr(x), _norm(sums, gamma, beta, None), _lib.ptr(slopes), groups,
+                           channels, length, _lib.ptr(gx), int(bool(accumulate)), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(dslope),
+                           _lib.ptr(scratch), _lib.current_stream(dev))
+    _lib.check(rc, "srf_gln_c_bwd")
+    return gx
+
+
+def softmax_mask_bwd(z, enc, gv, sources, gz=None, genc=None, accumulate_genc=False):
+    """Backward of softmax_mask from the logits: (gz [Bt, S N, L] -- may be gv --, genc [Bt, N, L])."""
+    dev = _chk(z, enc, gv, gz, genc)
+    Bt, SN, L = z.shape
+    N = enc.shape[1]
+    if SN != sources * N or enc.shape != (Bt, N, L) or gv.shape != z.shape:
+        raise _lib.SrfError("softmax_mask_bwd: z %s, gv %s and enc %s do not fit %d sources"
+                            % (tuple(z.shape), tuple(gv.shape), tuple(enc.shape), sources))
+    if gz is None:
+        gz = torch.empty_like(z)
+    if genc is None:
+        if accumulate_genc:
+            raise _lib.SrfError("softmax_mask_bwd: accumulate_genc needs the genc to add to")
+        genc = torch.empty_like(enc)
+    rc = _lib.load().srf_softmax_mask_bwd(_lib.ptr(z), _lib.ptr(enc), _lib.ptr(gv), _lib.ptr(gz), _lib.ptr(genc),
+                                          int(bool(accumulate_genc)), Bt, sources, N, L, _lib.current_stream(dev))
+    _lib.check(rc, "srf_softmax_mask_bwd")
+    return gz, genc
+
+
+def mask_weight_fold(dtz, drow, dm_weight, dm_bias):
+    """dm_weight [S, 1, N + 1, 1] += the diagonals of dtz [S N, N]; dm_bias [S] += the sums of drow [S N].  In place."""
+    dev = _chk(dtz, drow, dm_weight, dm_bias)
+    S, N = dm_weight.shape[0], dm_weight.shape[2] - 1
+    rc = _lib.load().srf_mask_weight_fold(_lib.ptr(dtz), _lib.ptr(drow), _lib.ptr(dm_weight), _lib.ptr(dm_bias), N, S,
+                                          _lib.current_stream(dev))
+    _lib.check(rc, "srf_mask_weight_fold")
+
+
+def decoder_weight_contract(dwexp, dweight):
+    """dweight [S N, 1, K] += the diagonal blocks of dwexp [S N, S, K].  In place."""
+    dev = _chk(dwexp, dweight)
+    SN, S, K = dwexp.shape
+    rc = _lib.load().srf_decoder_weight_contract(_lib.ptr(dwexp), _lib.ptr(dweight), SN // S, S, K, _lib.current_stream(dev))
+    _lib.check(rc, "srf_decoder_weight_contract")
+
+
+def decoder_bias_grad(grad_out, dbias):
+    """dbias [S] += grad_out [Bt, S, T] summed over batch and time.  In place."""
+    dev = _chk(grad_out, dbias)
+    Bt, S, T = grad_out.shape
+    lib = _lib.load()
+    scratch = torch.empty(lib.srf_decoder_bias_grad_scratch_floats(S), dtype=torch.float32, device=dev)
+    rc = lib.srf_decoder_bias_grad(_lib.ptr(grad_out), _lib.ptr(dbias), Bt, S, T, _lib.ptr(scratch), _lib.current_stream(dev))
+    _lib.check(rc, "srf_decoder_bias_grad")
+
+
+def relu_gate(g, s):
+    """g = 0 where the saved post-ReLU output s is not positive.  In place; returns g."""
+    dev = _chk(g, s)
+    rc = _lib.load().srf_relu_gate(_lib.ptr(g), _lib.ptr(s), g.numel(), _lib.current_stream(dev))
+    _lib.check(rc, "srf_relu_gate")
+    return g
