@@ -155,7 +155,11 @@ enum srf_debug_flag {
   /* swap the two forms of the 256 x 128 GEMM: srf_forward / srf_separate run the one-block-per-CU kernel (srf_pwconv_x3w.hip),
    * every other caller the paired-block kernel (srf_pwconv_x3p.hip) -- default: the paired form inside the forward only */
   SRF_DBG_GEMM_256_SWAP_FORMS = 8192,
-  /* training forward: three bf16 parts per operand (6 MFMAs, round 3) instead of two fp16 parts (3 MFMAs, round 4) */
+  /* training forward: three bf16 parts per operand (6 MFMAs, round 3) instead of two fp16 parts (3 MFMAs, round 4).
+   * Range of the two-fp16-part form: an operand at or beyond 65520 makes its outputs non-finite (fp16 ends at 65504); an
+   * activation tensor whose level as a whole is below 1e-2 leaves the 2e-6 accuracy class (relative error 1.6e-5 at 1e-3, ten
+   * times more per decade below: fp16's normal numbers end at 6.1e-5, its subnormals at 6e-8).  The three-part form has fp32's
+   * exponent range and neither limit. */
   SRF_DBG_TRAIN_BF16X3 = 16384,
   /* WITHOUT the fused tail: mask GEMM -> masked tensor -> decoder frame GEMM -> overlap-add as separate launches */
   SRF_DBG_NO_FUSED_TAIL = 32768,

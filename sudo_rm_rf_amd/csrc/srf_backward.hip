@@ -17,7 +17,7 @@
 
 // =============================================================================================
 // GlobLN (+PReLU) backward.   z = gamma_c * xh + beta_c, xh = (x - mean_b) * rstd_b, out = PReLU_a(z)
-//   g_z   = g_out * (z >= 0 ? 1 : a)                 d a    += sum g_out * z [z < 0]
+//   g_z   = g_out * (z > 0 ? 1 : a)                  d a    += sum g_out * z [z <= 0]     (the slope at 0 and -0.0: torch's)
 //   d gamma_c += sum_{b,t} g_z xh                    d beta_c += sum_{b,t} g_z
 //   g_x   = rstd_b * (gamma_c g_z - S1_b / n - xh * S2_b / n),   S1_b = sum_{c,t} gamma_c g_z,  S2_b = sum gamma_c g_z xh
 // Pass A: one block per row (b, c): {sum g_z, sum g_z xh, slope term} -> rowpart (plain stores) and S1/S2 into
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void srf_gln_bwd_reduce_kernel(GlnBwdArgs a) {
     const float xh = (xr[l] - mean) * rstd;
     const float z = fmaf(gam, xh, bet);
     float gz = gv;
-    if (act && z < 0.f) {
+    if (act && z <= 0.f) {
       s2 = fmaf(gv, z, s2);
       gz = gv * slope;
     }
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void srf_gln_bwd_apply_kernel(GlnBwdArgs a, in
       if (a.gout2) gv += a.gout2[base + l];
       const float xh = (a.x[base + l] - mean) * rstd;
       const float z = fmaf(gam, xh, bet);
-      const float gz = (act && z < 0.f) ? gv * slope : gv;
+      const float gz = (act && z <= 0.f) ? gv * slope : gv;
       float r = rstd * (gam * gz - m1 - xh * m2);
       if (a.accumulate) r += a.gx[base + l];
       a.gx[base + l] = r;
@@ -223,7 +223,7 @@ __device__ __forceinline__ void srf_gln_bwd_elem(float gv, float x, float mean, 
                                                  bool act, float slope, float& xh, float& gz, float& sneg) {
   xh = (x - mean) * rstd;
   const float z = fmaf(gam, xh, bet);
-  const bool neg = act && z < 0.f;
+  const bool neg = act && z <= 0.f;
   sneg = fmaf(neg ? gv : 0.f, z, sneg);
   gz = neg ? gv * slope : gv;
 }
@@ -1741,7 +1741,7 @@ extern "C" int srf_mask_bwd(const float* gv, const float* m, const float* enc, f
 }
 
 // =============================================================================================
-// PReLU backward for a stand-alone PReLU (mask_net.0, improved_sudormrf.py:268): gx = gout * (x >= 0 ? 1 : a),
+// PReLU backward for a stand-alone PReLU (mask_net.0, improved_sudormrf.py:268): gx = gout * (x > 0 ? 1 : a)  (the slope at 0 and -0.0, as torch's autograd gives it),
 // d a += sum gout * x [x < 0].  gx may alias gout.
 // =============================================================================================
 // (round 4: a persistent grid with float4 accesses -- the first form's one block per 1 024 elements ended in 25 600 atomicAdds on
@@ -1758,10 +1758,10 @@ __global__ __launch_bounds__(256) void srf_prelu_bwd_kernel(const float* __restr
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
       const float4 g = reinterpret_cast<const float4*>(gout)[i], xv = reinterpret_cast<const float4*>(x)[i];
       float4 o;
-      o.x = xv.x < 0.f ? g.x * a : g.x;
-      o.y = xv.y < 0.f ? g.y * a : g.y;
-      o.z = xv.z < 0.f ? g.z * a : g.z;
-      o.w = xv.w < 0.f ? g.w * a : g.w;
+      o.x = xv.x <= 0.f ? g.x * a : g.x;
+      o.y = xv.y <= 0.f ? g.y * a : g.y;
+      o.z = xv.z <= 0.f ? g.z * a : g.z;
+      o.w = xv.w <= 0.f ? g.w * a : g.w;
       acc += (xv.x < 0.f ? (double)g.x * (double)xv.x : 0.0) + (xv.y < 0.f ? (double)g.y * (double)xv.y : 0.0);
       acc += (xv.z < 0.f ? (double)g.z * (double)xv.z : 0.0) + (xv.w < 0.f ? (double)g.w * (double)xv.w : 0.0);
       reinterpret_cast<float4*>(gx)[i] = o;
@@ -1769,7 +1769,7 @@ __global__ __launch_bounds__(256) void srf_prelu_bwd_kernel(const float* __restr
   } else {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
       const float g = gout[i], xv = x[i];
-      if (xv < 0.f) {
+      if (xv <= 0.f) {
         acc += (double)g * (double)xv;
         gx[i] = g * a;
       } else {

@@ -298,7 +298,27 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
     if (rc) return rc;
   }
   // g_x = W^T g (+ residual): cin_d -> cout_d, w the forward weight [cin_d][cout_d]
+  // Where no packed image serves the launch the GEMM would fall to the kernels that split fp32 into two bf16 parts on the fly (16
+  // mantissa bits per operand); those launches, and the decoder's frame GEMM below, run in the exact-fp32 class instead (kernel
+  // mode 2 for this thread, as the training forward does and as srf_original_backward does for the same launches).  Measured on
+  // causal_tiny with a batch that falls silent half-way: mask_net.0's slope gradient, one sum of 3104 terms that cancels to 6e-4
+  // of their size, carried 1.0e-5 of absolute error from the two GEMMs that feed it (4.4e-4 of its value, 2.3e-2) against 4.7e-7
+  // in the exact class.  Launches the 256 x 128 kernel serves from a packed image keep it, and so does every launch of more than
+  // 2^28 multiply-adds: below that a GEMM's time is its launch (microseconds in either class), above it the exact-fp32 MFMA kernel
+  // costs 2.5 x the split one (the 16-block bench step: 18 such launches, 39.9 -> 41.0 ms when they were moved too).
+  auto small_gemm = [&](int cin_d, int cout_d) { return (long)Bt * L * cin_d * cout_d <= (1L << 28); };
+  struct ExactClass {
+    int prev;
+    bool on;
+    explicit ExactClass(bool want) : prev(-1), on(want && srf_kernel_mode() == 0) {
+      if (on) prev = srf_kernel_mode_override(2);
+    }
+    ~ExactClass() {
+      if (on) srf_kernel_mode_override(prev);
+    }
+  };
   auto data_grad = [&](const float* g, const float* w, const void* pk, float* y, int cin_d, int cout_d, const float* residual) -> int {
+    const ExactClass exact(small_gemm(cin_d, cout_d) && !srf_pw_packed_only(pk, g, Bt, cin_d, cout_d, L));
     return srf_pw_data_grad(g, w, pk, wt, zeros, y, Bt, cin_d, cout_d, L, residual, st);
   };
   // ---- decoder: out = overlap_add(W_d^T PReLU_c(m))
@@ -314,7 +334,10 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   SRF_CHECK_HIP(hipMemsetAsync(wdpad, 0, sizeof(float) * (size_t)SAN * s.dec_rows, st));
   SRF_CHECK_HIP(hipMemcpy2DAsync(wdpad, sizeof(float) * s.dec_rows, tl.dec_w, sizeof(float) * SA * K, sizeof(float) * SA * K, SAN,
                                  hipMemcpyDeviceToDevice, st));
-  rc = srf_pw_conv(frames, wdpad, zeros, gv, Bt, s.dec_rows, SAN, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
+  {
+    const ExactClass exact(small_gemm(s.dec_rows, SAN));
+    rc = srf_pw_conv(frames, wdpad, zeros, gv, Bt, s.dec_rows, SAN, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
+  }
   if (rc) return rc;
   // ---- mask_nl_class, mask_net
   rc = srf_causal_prelu_bwd(gv, m, tl.out_prelu, gv, gtl.out_prelu, (long)Bt * SAN * L, fp(s.pyr), st);      // gv = g_m

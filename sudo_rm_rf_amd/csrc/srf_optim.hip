@@ -8,6 +8,7 @@
 //      the device by the update kernel from the buckets);
 //   2. g' = g * min(1, max_norm / (norm + 1e-6));  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;
 //      p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)       -- torch.optim.Adam (no amsgrad / decay).
+//      A step whose gradient norm is not finite updates nothing (parameters and moments keep their values; the norm is reported).
 // Arithmetic order follows torch's _single_tensor_adam so that the two agree to fp32 round-off.
 #include "srf_common.h"
 
@@ -52,6 +53,10 @@ __global__ __launch_bounds__(256) void srf_adam_kernel(const srf_opt_tensor* __r
     clip = clip > 1.f ? 1.f : clip;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
+  // A gradient that holds a NaN or an inf (a loss evaluated on an all-silent batch: log10(0 / (0 + eps)) - log10(0 / (0 + eps)))
+  // makes the norm non-finite.  torch's Adam would write NaN into every parameter and both moments; this step leaves all three
+  // untouched instead (grid-uniform: every block reads the same buckets) and still reports the norm, so check_finite() sees it.
+  if (!isfinite(norm)) return;
   const int2 ch = chunks[blockIdx.x];
   const srf_opt_tensor t = tens[ch.x];
   const long beg = (long)ch.y * OPT_CHUNK;

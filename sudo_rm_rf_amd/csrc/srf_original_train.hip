@@ -58,11 +58,11 @@ struct GlnCBwdRow {
   float mean, rstd, gam, bet, slope;
   bool act;
 };
-// g' and xh of one element; sneg += gout v where v < 0 (the convention of srf_gln_bwd: v >= 0 takes the slope 1)
+// g' and xh of one element; sneg += gout v where v <= 0 (torch's convention, as in srf_gln_bwd: the slope at 0 and -0.0)
 __device__ __forceinline__ void gln_c_bwd_elem(float gv, float x, const GlnCBwdRow& r, float& xh, float& gp, float& sneg) {
   xh = (x - r.mean) * r.rstd;
   const float v = fmaf(r.gam, xh, r.bet);
-  const bool neg = r.act && v < 0.f;
+  const bool neg = r.act && v <= 0.f;
   sneg = fmaf(neg ? gv : 0.f, v, sneg);
   gp = neg ? gv * r.slope : gv;
 }

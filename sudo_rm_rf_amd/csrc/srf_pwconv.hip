@@ -390,6 +390,16 @@ int srf_mask_decode(const float* x, const float* w, const void* w_packed, const 
 // Range: fp16 parts end at 65504 where bf16's do not.  GlobLN'ed tensors are O(1), the residual stream O(1..100) in every model
 // we have; an operand beyond the range (or NaN / inf) makes its output column non-finite -- loud, like the fp32 reference's own
 // overflow, not clamped (round 5) -- and flag 16384 (three bf16 parts) is the form without the limit.
+// Lower limit: fp16's smallest normal number is 2^-14 = 6.1e-5 and its subnormals end at 2^-24 = 6e-8 (the matrix pipe keeps them:
+// the kernel reproduces a numpy emulation of the split digit for digit), so an ACTIVATION tensor that is small AS A WHOLE loses
+// its lo part first and then bits of its hi part -- the weights are pre-scaled by 2^4 and do not.  Error relative to the output's
+// scale on a 256 x 256 x 3200 GEMM, operands N(0, s^2): s = 1 .. 1e3 4e-7, 1e-2 1.6e-6, 1e-3 1.6e-5, 1e-4 1.6e-4, 1e-5 1.6e-3,
+// 1e-6 1.6e-2 (ten times per decade; below s ~ 1e-8 the operand is zero), the three-part form 6e-7 throughout
+// (test_pw_conv_fp16_split_accuracy_over_magnitudes, profiles/edge_signals.txt).  Isolated small entries of an O(1) tensor cost
+// <= 3e-8 absolute each and do not matter; a GEMM is inside the 2e-6 class while its operand's level is >= 1e-2.  Every GEMM of the
+// training forwards reads a normalised tensor or the residual stream; the one fed by the signal-level norm (the bottleneck behind
+// a first GlobLN whose beta is 0) sees rstd <= 1e4 times the encoder output, i.e. ~1e-4 for a 1e-8 input: its gradients stay
+// inside the 2e-4 bar there (tests/test_gpu_edge_train.py, near_silent_row_beta0), so the dispatch does not special-case it.
 // The packed3 buffer then holds the fp16 image (half its size).
 // A walk that needs all 24 bits whatever the flag says asks for the three-part form for its own launches (per thread, like the
 // kernel mode override): the original model's training forward (srf_original_train.hip).

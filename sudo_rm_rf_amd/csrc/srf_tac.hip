@@ -831,7 +831,7 @@ __global__ __launch_bounds__(256) void srf_tac_bwd_lanes_kernel(TacBwdArgs a, co
     for (int i = 0; i < NN; ++i) {
       const float pv = (po[i] + srf_group_allsum<G>(r[i])) + bo[i];
       const float gv = valid ? a.go[(rowg * NN + i) * L + lc] : 0.f;
-      gpo[i] = pv >= 0.f ? gv : gv * ao;
+      gpo[i] = pv > 0.f ? gv : gv * ao;
       if (pv < 0.f) d_ao = fmaf(gv, pv, d_ao);
       if (valid) a.GPO[(rowg * NN + i) * L + l] = gpo[i];
       gs[i] = srf_group_allsum<G>(gpo[i]);
@@ -848,7 +848,7 @@ __global__ __launch_bounds__(256) void srf_tac_bwd_lanes_kernel(TacBwdArgs a, co
 #pragma unroll
       for (int i = 0; i < NN; ++i) gq = fmaf(wq[i], gs[i], gq);
       gq = jm ? gq : 0.f;
-      gpq[t] = pq[t] >= 0.f ? gq : gq * am;
+      gpq[t] = pq[t] > 0.f ? gq : gq * am;
       if (valid && jm) {
         if (pq[t] < 0.f) d_am = fmaf(gq, pq[t], d_am);
         a.GPQ[((size_t)b * HH + jc) * L + l] = gpq[t];
@@ -875,7 +875,7 @@ __global__ __launch_bounds__(256) void srf_tac_bwd_lanes_kernel(TacBwdArgs a, co
         t = fmaf(s_wm[jr * PM + j], gpq[t2], t);
       }
       gz = fmaf(srf_group_allsum<G>(t), 1.f / (float)G, gz);
-      const float gp = pz >= 0.f ? gz : gz * ai;
+      const float gp = pz > 0.f ? gz : gz * ai;
       if (valid) {
         if (pz < 0.f) d_ai = fmaf(gz, pz, d_ai);
         a.GPZ[(rowg * HH + j) * L + l] = gp;
@@ -1234,7 +1234,7 @@ __global__ __launch_bounds__(256, 2) void srf_tac_bwd_mfma_kernel(TacBwdArgs a, 
       for (int r = 0; r < 8; ++r) {
         const float pv = o[r] * (1.f / (TAC_WS * TAC_WS));
         const float gv = gov[r];                 // (out-of-range columns loaded 0)
-        gpo[r] = pv >= 0.f ? gv : gv * ao;
+        gpo[r] = pv > 0.f ? gv : gv * ao;
         d_ao = pv < 0.f ? fmaf(gv, pv, d_ao) : d_ao;
         gs[r] += gpo[r];
       }
@@ -1271,14 +1271,14 @@ __global__ __launch_bounds__(256, 2) void srf_tac_bwd_mfma_kernel(TacBwdArgs a, 
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float gq = gqA[r], pv = pqv[r];
-        gqA[r] = pv >= 0.f ? gq : gq * am;
+        gqA[r] = pv > 0.f ? gq : gq * am;
         d_am = pv < 0.f ? fmaf(gq * vmask, pv, d_am) : d_am;
         gpq[r] = gqA[r];
       }
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         const float gq = gqB[r], pv = pqv[16 + r];
-        gqB[r] = pv >= 0.f ? gq : gq * am;
+        gqB[r] = pv > 0.f ? gq : gq * am;
         d_am = pv < 0.f ? fmaf(gq * vmask, pv, d_am) : d_am;
         gpq[16 + r] = gqB[r];
       }
@@ -1321,14 +1321,14 @@ __global__ __launch_bounds__(256, 2) void srf_tac_bwd_mfma_kernel(TacBwdArgs a, 
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float pv = pzA[r] * (1.f / TAC_WS), gz = gzA[r];
-        gzA[r] = pv >= 0.f ? gz : gz * ai;
+        gzA[r] = pv > 0.f ? gz : gz * ai;
         d_ai = pv < 0.f ? fmaf(gz * vmask, pv, d_ai) : d_ai;
         gpz[r] = gzA[r];
       }
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
         const float pv = pzB[r] * (1.f / TAC_WS), gz = gzB[r];
-        gzB[r] = pv >= 0.f ? gz : gz * ai;
+        gzB[r] = pv > 0.f ? gz : gz * ai;
         d_ai = pv < 0.f ? fmaf(gz * vmask, pv, d_ai) : d_ai;
         gpz[16 + r] = gzB[r];
       }

@@ -15,13 +15,18 @@ _CHECK_FINITE = os.environ.get("SRF_CHECK_FINITE") == "1"   # check_finite() aft
 class FusedClipAdam(torch.optim.Optimizer):
     """Drop-in for ``torch.optim.Adam(params, lr, betas, eps)`` (no weight decay / amsgrad) that also applies
     ``clip_grad_norm_(params, clip_grad_norm)`` inside ``step()``.  State (``exp_avg``, ``exp_avg_sq``, ``step``) uses
-    torch's names, so ``state_dict()`` is interchangeable with torch.optim.Adam's."""
+    torch's names, so ``state_dict()`` is interchangeable with torch.optim.Adam's.
+    One departure from torch: a step whose total gradient norm is NaN or inf (a loss evaluated on an all-silent batch, an
+    operand beyond the fp16 range) is not applied -- parameters and both moments keep their values, where torch's Adam would
+    write NaN into all three; ``step`` still counts, ``check_finite()`` reports the last step and ``skipped_steps`` counts them all
+    (kept on the device: reading it is the one host sync)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, clip_grad_norm=0.0):
         defaults = dict(lr=lr, betas=betas, eps=eps, clip_grad_norm=clip_grad_norm)
         super().__init__(params, defaults)
         self._tables = {}
         self.last_grad_norm = None          # device scalar: total gradient norm before clipping (last step)
+        self._skipped = None                # device int64 scalar: steps left unapplied because that norm was not finite
 
     def _table(self, gi, group, plist):
         """Device tables of one parameter group: {param, grad, exp_avg, exp_avg_sq, numel} per tensor and the chunk list.
@@ -101,9 +106,17 @@ class FusedClipAdam(torch.optim.Optimizer):
                                             _lib.current_stream(dev))
             _lib.check(rc, "srf_clip_adam_step")
             self.last_grad_norm = norm
+            bad = torch.isfinite(norm).logical_not().sum()          # (no host sync: the count stays on the device)
+            self._skipped = bad if self._skipped is None or self._skipped.device != bad.device else self._skipped + bad
         if _CHECK_FINITE:
             self.check_finite()
         return loss
+
+    @property
+    def skipped_steps(self):
+        """How many steps (summed over the parameter groups) were left unapplied because their gradient norm was NaN or inf.
+        One synchronising read; a training loop that never looks at it or at check_finite() stalls silently on such batches."""
+        return 0 if self._skipped is None else int(self._skipped.item())
 
     def check_finite(self):
         """Host check of the last step's total gradient norm (ONE synchronising read; off the hot path unless

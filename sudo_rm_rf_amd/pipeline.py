@@ -26,9 +26,11 @@ def separate(model, mixture, mixture_consistency=None):
         mixture_consistency = type(model).__name__ == "GroupCommSudoRmRf"
     x = mixture.detach().to(torch.float32).contiguous()
     with torch.no_grad():
-        if getattr(model, "in_audio_channels", 1) == 1 and hasattr(model, "_engine"):
+        # srf_separate has no causal form (it refuses that variant): the causal model takes the three-kernel form below, as the
+        # multi-channel front ends do -- before, a one-channel CausalSuDORMRF fell into the refusal
+        if getattr(model, "in_audio_channels", 1) == 1 and hasattr(model, "_engine") and type(model).__name__ != "CausalSuDORMRF":
             return model._engine().separate(model, x, bool(mixture_consistency))
-        norm, stats = ops.wav_normalize(x)          # (multi-channel front ends: the three-kernel form)
+        norm, stats = ops.wav_normalize(x)          # (multi-channel front ends, the causal model: the three-kernel form)
         est = model(norm)
         return ops.wav_denormalize(est, stats, norm if mixture_consistency else None)
 

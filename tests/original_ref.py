@@ -20,7 +20,9 @@ def gn(x, weight, bias):
 
 
 def prelu_c(x, slopes):
-    return torch.where(x >= 0, x, x * slopes[None, :, None])
+    """Per-channel PReLU.  The value at 0 is 0 either way; under autograd the branch decides the subgradient there, and it is
+    torch's own (F.prelu: the slope at x == 0 and at -0.0)."""
+    return torch.where(x > 0, x, x * slopes[None, :, None])
 
 
 def block(x, sd, p, D):

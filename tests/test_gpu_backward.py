@@ -263,3 +263,83 @@ def test_tac_bwd(Bt, G, n, L):
     assert rel_err(gx, x.grad) <= 3e-5, rel_err(gx, x.grad)
     for i, (g, p) in enumerate(zip(grads, P)):
         assert rel_err(g, p.grad) <= 5e-5, (i, rel_err(g, p.grad))
+
+
+# ---- the kink: exact zeros at the activation's input ------------------------------------------------------------------------
+# torch's autograd gives PReLU's SLOPE at x == 0 and at -0.0 (F.prelu backward at [0., -0., 1., -1.] with slope 0.25 is
+# [0.25, 0.25, 1, 0.25]).  The fixtures above never meet the kink; a silent row behind a norm whose beta is 0 (as at initialisation)
+# puts every element on it.  The reference below is fp64 autograd of F.prelu itself, the bars are the ones of the tests above.
+
+@pytest.mark.parametrize("shape", [(3, 40, 1001), (3, 7, 1001)], ids=["float4", "dword"])
+def test_prelu_bwd_at_exact_zeros(shape):
+    from sudo_rm_rf_amd import ops
+    x = rnd(*shape, seed=62)
+    flat = x.view(-1)
+    flat[0::3] = 0.0
+    flat[1::7] = -0.0
+    assert int((flat == 0).sum()) > flat.numel() // 3 and bool(torch.signbit(flat[1]))
+    x.requires_grad_(True)
+    a = torch.tensor([0.31], dtype=torch.float64, requires_grad=True)
+    g = rnd(*shape, seed=63, shift=0.5)            # a mean of 0.5: dslope is then a sum that does not cancel (its bar is relative)
+    F.prelu(x, a).backward(g)
+    xd = dev32(x.detach())
+    assert bool(torch.signbit(xd.view(-1)[1]))                     # the float32 copy keeps the sign of -0.0
+    gx, da = ops.prelu_bwd(dev32(g), xd, dev32(a.detach()))
+    assert rel_err(gx, x.grad) <= 1e-6 and rel_err(da, a.grad) <= 1e-5
+    zero = (x.detach() == 0)
+    assert torch.equal(gx.cpu()[zero], (g.float() * a.detach().float())[zero])          # the slope, bit for bit
+
+
+@pytest.mark.parametrize("Bt,C,L", [(3, 64, 3200), (2, 20, 203), (4, 5, 1)], ids=["float4", "dword", "L1"])
+def test_gln_bwd_zero_channels_take_the_slope(Bt, C, L):
+    """Channels whose gamma and beta are 0 have z == 0 everywhere: gx is the same under either convention (gamma is 0), dgamma and dbeta of those
+    channels are the slope times what the other convention gives."""
+    from sudo_rm_rf_amd import ops
+    x = rnd(Bt, C, L, seed=15, scale=1.7, shift=-0.4).requires_grad_(True)
+    gamma, beta = rnd(C, seed=16, scale=0.3, shift=1.0), rnd(C, seed=17, scale=0.3)
+    dead = [0, C // 2, C - 1]
+    gamma[dead], beta[dead] = 0.0, 0.0
+    gamma.requires_grad_(True), beta.requires_grad_(True)
+    slope = torch.tensor([0.23], dtype=torch.float64, requires_grad=True)
+    gout, gout2 = rnd(Bt, C, L, seed=18), rnd(Bt, C, L, seed=19, scale=0.5)
+    F.prelu(gln64(x, gamma, beta), slope).backward(gout + gout2)
+    gx, dg, db, ds = ops.gln_bwd(dev32(gout), dev32(x.detach()), sums64(x.detach()), dev32(gamma.detach()),
+                                 dev32(beta.detach()), prelu=dev32(slope.detach()), gout2=dev32(gout2))
+    assert rel_err(gx, x.grad) <= 3e-5, rel_err(gx, x.grad)
+    assert rel_err(dg, gamma.grad) <= 3e-5 and rel_err(db, beta.grad) <= 3e-5 and rel_err(ds, slope.grad) <= 3e-5
+    for got, want in ((dg, gamma.grad), (db, beta.grad)):          # the dead channels are visible at the tensor's scale
+        assert float(want[dead].abs().max()) >= 1e-2 * float(want.abs().max())
+
+
+@pytest.mark.parametrize("valu", [False, True], ids=["mfma", "valu"])
+@pytest.mark.parametrize("Bt,G,n,L", [(2, 16, 16, 300), (1, 4, 8, 76), (3, 16, 8, 40)])
+def test_tac_bwd_exact_zero_rows_take_the_slope(Bt, G, n, L, valu):
+    """One hidden unit of each of the three layers is made exactly 0 at every position through a zero weight row and a zero bias:
+    that row's weight and bias gradients carry the activation's slope at 0 (F.prelu under fp64 autograd)."""
+    from sudo_rm_rf_amd import ops
+    H = 3 * n
+    x = rnd(Bt, G, n, L, seed=190).requires_grad_(True)
+    P = [rnd(H, n, seed=191, scale=n ** -0.5), rnd(H, seed=192, scale=0.2), torch.tensor([0.2], dtype=torch.float64),
+         rnd(H, H, seed=193, scale=H ** -0.5), rnd(H, seed=194, scale=0.2), torch.tensor([0.3], dtype=torch.float64),
+         rnd(n, 2 * H, seed=195, scale=(2 * H) ** -0.5), rnd(n, seed=196, scale=0.2),
+         torch.tensor([0.15], dtype=torch.float64)]
+    dead = {0: 1, 3: H - 2, 6: n - 1}                              # weight index -> the row that is zero
+    for i, r in dead.items():
+        P[i][r], P[i + 1][r] = 0.0, 0.0
+    P = [p.requires_grad_(True) for p in P]
+    rows = x.permute(0, 3, 1, 2).reshape(-1, n)
+    z = F.prelu(rows @ P[0].T + P[1], P[2]).view(Bt, L, G, H)
+    q = F.prelu(z.mean(2).view(Bt * L, H) @ P[3].T + P[4], P[5])
+    cat = torch.cat([z.view(Bt * L, G, H), q.unsqueeze(1).expand(Bt * L, G, H)], 2).reshape(-1, 2 * H)
+    o = F.prelu(cat @ P[6].T + P[7], P[8]).view(Bt, L, G, n).permute(0, 2, 3, 1).contiguous()
+    assert float(o.detach()[:, :, n - 1].abs().max()) == 0.0
+    go = rnd(Bt, G, n, L, seed=197)
+    o.backward(go)
+    with ops.debug_flags(DebugFlag.TAC_VALU if valu else 0):
+        gx, grads = ops.tac_bwd(dev32(x.detach()), dev32(go), [dev32(p.detach()) for p in P])
+    assert rel_err(gx, x.grad) <= 3e-5, rel_err(gx, x.grad)
+    for i, (g, p) in enumerate(zip(grads, P)):
+        assert rel_err(g, p.grad) <= 5e-5, (i, rel_err(g, p.grad))
+    for i, r in dead.items():                 # the rows the convention decides are visible at their tensor's scale: the other
+        # side of the kink multiplies them by 1 / slope (5, 3.3 and 6.7 times), far outside the bar above
+        assert float(P[i].grad[r].abs().max()) >= 1e-2 * float(P[i].grad.abs().max()), i

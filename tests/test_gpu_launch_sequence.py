@@ -434,11 +434,11 @@ EXPECTED.update({      # recorded on commit 13ee426
         (("causal_scale", "causal_encoder", "pw_conv_mfma"), 1),
         (("pw_conv_small", "causal_dwconv", "causal_dwconv", "causal_dwconv", "causal_merge_act", "pw_conv_mfma"), 2),
         (("pw_conv_mfma", "prelu_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "causal_scale",
-          "frames_gather", "prelu_apply", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "causal_prelu_bwd",
-          "causal_prelu_fold", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "causal_prelu_bwd",
+          "frames_gather", "prelu_apply", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_mfma", "causal_prelu_bwd",
+          "causal_prelu_fold", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_mfma", "causal_prelu_bwd",
           "causal_prelu_fold"), 1),
         (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "causal_pyramid_bwd", "causal_bwd_finalize",
-          "causal_bwd_slope", "pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 2),
+          "causal_bwd_slope", "pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_mfma"), 2),
         (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "frames_gather", "pw_wgrad", "pw_wgrad_reduce",
           "causal_enc_scatter", "causal_gain_fold"), 1),
     ],
@@ -446,12 +446,12 @@ EXPECTED.update({      # recorded on commit 13ee426
         (("causal_scale", "causal_encoder", "pw_conv_mfma"), 1),
         (("pw_conv_small", "causal_dwconv", "causal_dwconv", "causal_dwconv", "causal_merge_act", "pw_conv_mfma"), 2),
         (("pw_conv_mfma", "prelu_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "causal_scale",
-          "frames_gather", "prelu_apply", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "causal_prelu_bwd",
-          "causal_prelu_fold", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "causal_prelu_bwd",
+          "frames_gather", "prelu_apply", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_mfma", "causal_prelu_bwd",
+          "causal_prelu_fold", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_mfma", "causal_prelu_bwd",
           "causal_prelu_fold"), 1),
         (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small") +
          ("causal_dw_bwd", "causal_bwd_finalize", "causal_bwd_slope") * 4 +
-         ("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 2),
+         ("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_mfma"), 2),
         (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "frames_gather", "pw_wgrad", "pw_wgrad_reduce",
           "causal_enc_scatter", "causal_gain_fold"), 1),
     ],

@@ -513,11 +513,29 @@ def test_pw_conv_three_part_split(Bt, Cin, Cout, L, pro, parts):
         assert torch.allclose(tot, ref, rtol=1e-5, atol=1e-6 * got[0].numel())
 
 
-@pytest.mark.parametrize("scale", [1e-2, 1.0, 30.0, 1e3])
+def _fp16_split_emulation(w, x, cols):
+    """The two-part arithmetic itself, in numpy on the kernel's own operands: hi = fp16(v), lo = fp16(v - hi) (round to nearest
+    even, subnormals kept), the weights times 2^4 first, the three products hi hi + lo hi + hi lo accumulated in fp32, times 2^-4.
+    w [Cout, Cin], x [Bt, Cin, L] float32 numpy; returns [Bt, Cout, len(cols)] float32."""
+    def split(v):
+        hi = v.astype(np.float16)
+        return hi.astype(np.float32), (v - hi.astype(np.float32)).astype(np.float16).astype(np.float32)
+    wh, wl = split(w * np.float32(16.0))
+    xh, xl = split(np.ascontiguousarray(x[:, :, cols]))
+    y = np.einsum("mk,bkl->bml", wh, xh) + np.einsum("mk,bkl->bml", wl, xh) + np.einsum("mk,bkl->bml", wh, xl)
+    return (y * np.float32(1.0 / 16.0)).astype(np.float32)
+
+
+@pytest.mark.parametrize("scale", [1e-2, 1.0, 30.0, 1e3, 1e-3, 1e-4, 1e-5, 1e-6])
 def test_pw_conv_fp16_split_accuracy_over_magnitudes(scale):
     """The training forward's default GEMM (two fp16 parts per operand) against fp64 over five decades of operand magnitude:
     the error relative to the output's scale stays in the exact-fp32 class (a per-example GlobLN downstream makes relative error
-    the quantity that matters)."""
+    the quantity that matters).
+    Below 1e-2 the lo parts, then the hi parts, fall into fp16's subnormal range and the form loses bits by construction (the
+    range contract in csrc/srf_pwconv.hip): there the kernel is held to 2 x what the two-part arithmetic itself gives on the
+    same operands (a numpy emulation of the split, not the kernel's output), and the three-bf16-part form (DebugFlag.TRAIN_BF16X3),
+    which has fp32's exponent range, to the 2e-6 of the upper decades -- at every scale."""
+    from tests import edge_signals as es
     from sudo_rm_rf_amd import ops
     ops.set_kernel_mode(0)
     Bt, Cin, Cout, L = 16, 256, 256, 3200          # 400 tiles: served by the 256 x 128 kernel (asserted below)
@@ -531,7 +549,28 @@ def test_pw_conv_fp16_split_accuracy_over_magnitudes(scale):
         got = ops.pw_conv3(x, w, bias, packed)
     assert tr.names == {"pw_conv_x3w4<0>"}, tr.names
     rel = float((got.double() - want).abs().max()) / float(want.abs().max())
-    assert rel <= 2e-6, (scale, rel)
+    with ops.debug_flags(DebugFlag.TRAIN_BF16X3):
+        packed3 = ops.pack3_pw_weight(w)
+        with ops.kernel_trace(DEV) as tr3:
+            got3 = ops.pw_conv3(x, w, bias, packed3)
+    assert tr3.names == {"pw_conv_x3w3<0>"}, tr3.names
+    rel3 = float((got3.double() - want).abs().max()) / float(want.abs().max())
+    line = "operand scale %g: two fp16 parts %.3e, three bf16 parts %.3e (relative to max|y| = %.3e)" % (
+        scale, rel, rel3, float(want.abs().max()))
+    if scale >= 1e-2:
+        print(line)
+        assert rel <= 2e-6, (scale, rel)
+    else:
+        cols = np.arange(0, L, 17)
+        emu = _fp16_split_emulation(w[:, :, 0].cpu().numpy(), x.cpu().numpy(), cols)
+        wc = want[:, :, cols].cpu().numpy()
+        emu_rel = float(np.abs(emu.astype(np.float64) - wc).max()) / float(np.abs(wc).max())
+        rel_c = float((got[:, :, cols].double() - want[:, :, cols]).abs().max()) / float(np.abs(wc).max())
+        line += "; on every 17th column: kernel %.3e, the split's own arithmetic %.3e, bar %.3e" % (rel_c, emu_rel, 2 * emu_rel)
+        print(line)
+        es.write_profile_lines("fp16_split_%g" % scale, [line])
+        assert torch.isfinite(got).all() and rel_c <= 2.0 * emu_rel, line
+    assert rel3 <= 2e-6, (scale, rel3)
 
 
 def test_pw_conv_fp16_split_is_loud_beyond_its_range():

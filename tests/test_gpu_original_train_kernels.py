@@ -6,7 +6,8 @@ inside the guard-banded arena of tests/placement.py.
 The bar of every float result is the rule of tests/test_gpu_original_kernels.py: torch's own fp32 CPU autograd on the same inputs
 deviates from the fp64 one by some max-abs amount; the kernel may deviate by 8 times that.  Copies and gates (srf_relu_gate, the
 contract) are compared bit for bit.  Every reduction of these kernels has a fixed order: a second call gives the same bits.
-PReLU inputs come from fixed seeds for which NO pre-activation lies within 1e-5 of the kink in fp64 (asserted, nothing masked)."""
+PReLU inputs come from fixed seeds for which NO pre-activation lies within 1e-5 of the kink in fp64 (asserted, nothing masked);
+test_gln_c_bwd_zero_channels_take_the_slope alone puts whole channels exactly ON it, to pin torch's convention there."""
 import functools
 
 import numpy as np
@@ -188,6 +189,43 @@ def test_gln_c_bwd_dword_kernels_in_kernel_mode_1():
     r64, r32 = refs[(True, True)]
     for name, got, i in (("gx", gx, 0), ("dgamma", dg, 1), ("dbeta", db, 2), ("dslope", ds, 3)):
         bar_check("gln_c_bwd mode 1 " + name, got, r64[i], r32[i])
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["float4", "dword"])
+@pytest.mark.parametrize("shape", [(3, 5, 7), (2, 64, 130)], ids=lambda s: "g%d_C%d_L%d" % s)
+def test_gln_c_bwd_zero_channels_take_the_slope(shape, mode):
+    """The kink itself, which every case above stays away from: channels whose weight and bias are 0 have the pre-activation
+    exactly 0 at every position.  torch's autograd gives PReLU's slope there (F.prelu: slope where x <= 0, -0.0 included), so
+    their dgamma / dbeta are the slope times what the other side of the kink gives (gx is the same either way: gamma is 0).  Reference:
+    fp64 autograd of F.prelu with per-channel slopes; bar: this file's rule."""
+    import torch.nn.functional as F
+    from sudo_rm_rf_amd import ops, original
+    x, gamma, beta, sl, gout, gout2, gx0, p0, sums, refs = gln_case(shape)
+    Cc = shape[1]
+    dead = [0, Cc // 2, Cc - 1]
+    gamma, beta = gamma.clone(), beta.clone()
+    gamma[dead], beta[dead] = 0.0, 0.0
+
+    def run(dt):
+        xs, ga, be, s_ = (t.to(dt).clone().requires_grad_() for t in (x, gamma, beta, sl))
+        (F.prelu(orf.gn(xs, ga, be), s_) * (gout.to(dt) + gout2.to(dt))).sum().backward()
+        return xs.grad, ga.grad, be.grad, s_.grad
+    r64, r32 = run(torch.float64), run(torch.float32)
+    for i in (1, 2):                      # the dead channels are visible at the tensor's scale
+        assert float(r64[i][dead].abs().max()) >= 1e-2 * float(r64[i].abs().max())
+    d = lambda t: t.to(DEV)
+    dg, db, ds = (torch.zeros(Cc, device=DEV) for _ in range(3))
+    ops.set_kernel_mode(mode)
+    try:
+        with ops.kernel_trace(DEV) as tr:
+            gx = original.gln_c_bwd(d(gout), d(x), d(sums), d(gamma), d(beta), slopes=d(sl), gout2=d(gout2), dgamma=dg, dbeta=db, dslope=ds)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_kernel_mode(0)
+    suffix = "_scalar" if mode else ""
+    assert tr.names == {"gln_c_bwd_reduce" + suffix, "gln_c_bwd_apply" + suffix}
+    for name, got, i in (("gx", gx, 0), ("dgamma", dg, 1), ("dbeta", db, 2), ("dslope", ds, 3)):
+        bar_check("gln_c_bwd kink %s mode %d %s" % (shape, mode, name), got, r64[i], r32[i])
 
 
 # ---- srf_softmax_mask_bwd ----------------------------------------------------------------------------------------------------------------

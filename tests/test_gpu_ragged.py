@@ -363,6 +363,60 @@ def test_ragged_forward_matches_the_oracle_row_by_row(setup):
         assert (out[i, :, n:] == 0).all(), "row %d is not exactly zero past its length %d" % (i, n)
 
 
+# rows that take degenerate content (tests/edge_signals.py): none of ragged_lengths' fixed rows, lengths of their own
+DEGENERATE_ROWS = {6: "silence", 13: "dc", 21: "near_silent"}
+
+
+def degenerate_batch(x, lens, nan_past_end=False):
+    """x with the valid part of three rows replaced: a silent utterance, one that is DC, a near-silent one (1e-8, unnormalised).
+    What lies past those rows' ends stays what it was (or NaN): it must not be read."""
+    from tests import edge_signals as es
+    sig = es.signals(1, 1, x.shape[-1])
+    x2 = x.clone()
+    for r, name in DEGENERATE_ROWS.items():
+        x2[r, 0, :lens[r]] = torch.from_numpy(sig[name][0, 0, :lens[r]])
+        if nan_past_end:
+            x2[r, 0, lens[r]:] = float("nan")
+    return x2
+
+
+def check_degenerate_rows_forward(manifest, case, setup):
+    """forward_ragged on a batch that contains a silent, a DC and a near-silent utterance among ordinary ones: each of the three
+    against the fp64 oracle of that row ALONE at its own length under edge_signals.inference_bar (relative to the row's own output
+    scale: 1e-9 for the near-silent one; the silent row's reference is identically zero), every other row against the reference
+    it had before within TOL -- a statistic leaking into or out of the silent row shows in one or the other -- and every row
+    exactly zero past its end."""
+    from tests import edge_signals as es
+    cfg, model, x, lens, want = setup
+    _, sd, _, _ = load_case(manifest, case)
+    sd64 = {k: v.double() for k, v in torch_oracle.to_torch(sd).items()}
+    x2 = degenerate_batch(x, lens, nan_past_end=True)
+    assert model._engine().ragged_plan_supported(BATCH, T, torch.device(DEV)), "the batch must take the ragged kernels"
+    with torch.no_grad():
+        out = model.forward_ragged(x2.to(DEV), lens).cpu()
+    assert torch.isfinite(out).all()
+    for r, name in DEGENERATE_ROWS.items():
+        n = lens[r]
+        with torch.no_grad():
+            ref = torch_oracle.forward(cfg, sd64, x2[r:r + 1, :, :n].double())[0]
+        wmax = float(ref.abs().max())
+        zero = name == "silence"
+        assert (wmax == 0.0) == zero, (name, wmax)
+        bar = es.inference_bar(wmax, zero)
+        err = float((out[r, :, :n].double() - ref).abs().max())
+        print("forward_ragged row %d (%s, %d samples): err %.3e bar %.3e (max|want| %.3e)" % (r, name, n, err, bar, wmax))
+        assert err <= bar, (name, err, bar)
+    others = [i for i in range(BATCH) if i not in DEGENERATE_ROWS]
+    errs = _row_errors(out, want, lens)
+    report("forward_ragged, the ordinary rows beside the degenerate ones", errs[others], TOL, labels=others)
+    for i, n in enumerate(lens):
+        assert (out[i, :, n:] == 0).all(), "row %d is not exactly zero past its length %d" % (i, n)
+
+
+def test_ragged_forward_with_silent_dc_and_near_silent_rows(manifest, setup):
+    check_degenerate_rows_forward(manifest, CASE, setup)
+
+
 @pytest.mark.parametrize("keep", [0, 1], ids=["even-rows", "odd-rows"])
 def test_ragged_rows_are_isolated(setup, keep):
     """Same call again with everything a row must not depend on changed: the input past every length NaN, the workspace and

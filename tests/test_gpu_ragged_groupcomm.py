@@ -20,7 +20,7 @@ from oracle import torch_oracle, weights
 from oracle.schema import ModelConfig
 from test_gpu_batch_distinct import per_example_error, report
 from test_gpu_model import TOL, build
-from test_gpu_ragged import (ORDER_TOL, PW_FRAMES, PW_L, PYR_CASES, _check_rows, _check_sums_rows, _nan_tail, _pyramid_ref,
+from test_gpu_ragged import (ORDER_TOL, check_degenerate_rows_forward, PW_FRAMES, PW_L, PYR_CASES, _check_rows, _check_sums_rows, _nan_tail, _pyramid_ref,
                              _sums64_valid, ragged_lengths)
 from tests.placement import poisoned_allocations
 from tests.test_gpu_ops import DEV, check, check_sums, dev32, gln64, rnd, sums64
@@ -254,6 +254,11 @@ def setup(manifest):
 def _row_errors(out, rows, lens):
     out = out.detach().cpu()
     return np.array([float((out[i, :, :lens[i]] - rows[i]).abs().max()) for i in range(len(lens))])
+
+
+def test_ragged_forward_with_silent_dc_and_near_silent_rows(manifest, setup):
+    """(the helper and its bars: tests/test_gpu_ragged.py)"""
+    check_degenerate_rows_forward(manifest, CASE, setup)
 
 
 def test_ragged_forward_matches_the_oracle_row_by_row(setup):

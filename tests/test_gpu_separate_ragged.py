@@ -13,7 +13,8 @@ import torch.nn.functional as F
 
 from conftest import load_case
 from oracle import torch_oracle, weights
-from test_gpu_ragged import ORDER_TOL, TOL, _check_rows, _check_sums_rows, build, ragged_lengths, report
+from test_gpu_ragged import (DEGENERATE_ROWS, ORDER_TOL, TOL, _check_rows, _check_sums_rows, build, degenerate_batch,
+                             ragged_lengths, report)
 from tests.placement import SENTINEL_WORD, poisoned_allocations
 from tests.test_gpu_ops import DEV, dev32, rnd
 
@@ -211,6 +212,49 @@ def test_separate_ragged_matches_the_oracle_recipe_row_by_row(setup, mc):
     if not mc:          # the Improved model's default is no mixture consistency
         check_against_the_oracle(model, x, lens, want, st, False)
     check_against_the_oracle(model, x, lens, want, st, mc, mixture_consistency=mc)
+
+
+def check_degenerate_rows_recipe(manifest, case, setup, mc):
+    """separate_ragged and separate_list on a batch that contains a silent, a DC and a near-silent utterance (the rows of
+    test_gpu_ragged.DEGENERATE_ROWS) among the raw ordinary ones: each of the three against the fp64 recipe of that row alone at
+    its own length -- mean / unbiased std over its own samples, (x - mean) / (std + 1e-9), the oracle forward, rescale, mixture
+    consistency on request -- within 1e-4 max(1, std_i); the other rows against the references they had; finite everywhere
+    (std = 0 meets the 1e-9 in the silent and the DC row); exactly zero past every end."""
+    from sudo_rm_rf_amd import pipeline
+    cfg, model, x, lens, want, st = setup
+    _, sd, _, _ = load_case(manifest, case)
+    sd64 = {k: v.double() for k, v in torch_oracle.to_torch(sd).items()}
+    x2 = degenerate_batch(x, lens)
+    with torch.no_grad():
+        out, _ = model.separate_ragged(nan_tails(x2, lens).to(DEV), lens, mixture_consistency=mc)
+        listed = pipeline.separate_list(model, [x2[i, 0, :n].to(DEV) for i, n in enumerate(lens)], mixture_consistency=mc)
+    out = out.cpu()
+    assert torch.isfinite(out).all() and all(torch.isfinite(y).all() for y in listed)
+    for r, name in DEGENERATE_ROWS.items():
+        n = lens[r]
+        row = x2[r:r + 1, :, :n].double()
+        mean, std = row.mean(), row.std()
+        norm = (row - mean) / (std + 1e-9)
+        with torch.no_grad():
+            ref = torch_oracle.forward(cfg, sd64, norm)[0] * std + mean
+        if mc:
+            ref = ref + (norm[0] - ref.sum(0, keepdim=True)) / ref.shape[0]
+        bar = TOL * max(1.0, float(std))
+        err = float((out[r, :, :n].double() - ref).abs().max())
+        err_l = float((listed[r].cpu().double() - ref).abs().max())
+        print("separate_ragged(mc=%s) row %d (%s, %d samples): err %.3e, separate_list %.3e, bar %.3e (max|want| %.3e)"
+              % (mc, r, name, n, err, err_l, bar, float(ref.abs().max())))
+        assert err <= bar and err_l <= bar, (name, err, err_l, bar)
+    others = [i for i in range(BATCH) if i not in DEGENERATE_ROWS]
+    report("separate_ragged(mc=%s), the ordinary rows beside the degenerate ones" % mc,
+           row_errors(out, want[mc], lens)[others], row_bars(TOL, st)[others], labels=others)
+    for i, n in enumerate(lens):
+        assert (out[i, :, n:] == 0).all(), "row %d is not exactly zero past its length %d" % (i, n)
+
+
+@pytest.mark.parametrize("mc", [False, True], ids=["plain", "mixture-consistency"])
+def test_separate_ragged_with_silent_dc_and_near_silent_rows(manifest, setup, mc):
+    check_degenerate_rows_recipe(manifest, CASE, setup, mc)
 
 
 def test_separate_ragged_launch_set(setup):

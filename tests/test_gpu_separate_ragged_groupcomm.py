@@ -6,8 +6,8 @@ then isolation and separate_list end to end.  The helpers are those of tests/tes
 import pytest
 import torch
 
-from test_gpu_separate_ragged import (BATCH, DEV, T, check_against_the_oracle, check_isolation, check_separate_list,
-                                      recipe_setup)
+from test_gpu_separate_ragged import (BATCH, DEV, T, check_against_the_oracle, check_degenerate_rows_recipe, check_isolation,
+                                      check_separate_list, recipe_setup)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +35,11 @@ def test_separate_ragged_matches_the_oracle_recipe_row_by_row(setup):
     check_against_the_oracle(model, x, lens, want, st, True)
     check_against_the_oracle(model, x, lens, want, st, True, mixture_consistency=True)
     check_against_the_oracle(model, x, lens, want, st, False, mixture_consistency=False)
+
+
+def test_separate_ragged_with_silent_dc_and_near_silent_rows(manifest, setup):
+    """mixture consistency on, as the README prescribes for this model (the helper and its bars: tests/test_gpu_separate_ragged.py)"""
+    check_degenerate_rows_recipe(manifest, CASE, setup, True)
 
 
 def test_separate_ragged_launch_set(setup):

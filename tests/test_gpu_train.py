@@ -431,10 +431,23 @@ def test_fused_clip_adam_survives_a_stream_change_and_reports_non_finite_steps()
     for p, q in zip(pa, pb):
         assert (p - q).abs().max().item() <= 5e-6 * max(1.0, p.abs().max().item())
     fused.check_finite()                               # finite so far: no error
+    before = [q.detach().clone() for q in pb]
+    state = [{k: v.clone() for k, v in fused.state[q].items() if k.startswith("exp_avg")} for q in pb]
     pb[0].grad = torch.full_like(pb[0], float("inf"))
     fused.step()
     with pytest.raises(_lib.SrfError, match="16384"):
         fused.check_finite()
+    # ... and the step itself wrote nothing: one NaN / inf gradient entry must not poison every parameter and both moments
+    torch.cuda.synchronize()
+    for q, b, st in zip(pb, before, state):
+        assert torch.equal(q.detach(), b)
+        assert all(torch.equal(fused.state[q][k], v) for k, v in st.items())
+    assert fused.skipped_steps == 1
+    pb[1].grad = torch.full_like(pb[1], float("nan"))
+    fused.step()
+    torch.cuda.synchronize()
+    assert all(torch.equal(q.detach(), b) for q, b in zip(pb, before))
+    assert fused.skipped_steps == 2                    # (counted on the device; the six finite steps before are not)
 
 
 def test_data_parallel_replicas_forward_and_train():
