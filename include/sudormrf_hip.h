@@ -269,6 +269,31 @@ int srf_separate_ragged(const srf_plan* plan, const float* const* params, int nu
                         const int* lengths /* host, [batch] */, float* out, float* stats /* [batch][2], written */,
                         int mixture_consistency, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The ragged forward of the ORIGINAL model (plans of srf_original_plan_create; additive to ABI 19).
+ * Opt-in through entry points of its own: srf_plan_ragged_supported stays 0 for such a plan and srf_forward_ragged /
+ * srf_separate_ragged keep refusing it.  Same contract as the two above: out[b, :, :lengths[b]] is what srf_forward (resp.
+ * srf_separate) on a batch-1 plan of length lengths[b] returns for row b alone -- the row padded to ITS OWN multiple of
+ * lcm(K / 2, 2^D), this model's rule, every GroupNorm over its own frames --, out[b, :, lengths[b]:] is exactly 0 and
+ * wav[b, :, lengths[b]:] is never read.  srf_original_separate_ragged: stats [batch][2] receives {mean, unbiased std} per row.
+ * srf_original_ragged_supported: 1 only for an original plan with K = 21, batch <= SRF_RAGGED_MAX_BATCH, num_sources <= 16, under
+ * kernel mode 0 with packed weights on, whose 1x1 convolutions -- l1, proj_1x1, conv_1x1_exp, reshape_before_masks where present,
+ * the mask GEMM N -> S N -- all are shapes of the 256 x 128 GEMM (Cin % 64 == 0, Cin >= 128, Cout >= 192) within its 32-bit reach
+ * and with at least 8 tiles, and whose frame count the register-resident fused pyramid takes.  (The README recipe, B 256 / C 512
+ * / N 512, passes; out_channels = 128 does not: conv_1x1_exp then has 128 < 192 output rows.)
+ * srf_original_ragged_workspace_bytes: the workspace the ragged call needs (0 = not supported).
+ * Refused with SRF_EINVAL BEFORE anything is launched, srf_last_error() containing "original" and naming the example: a plan
+ * the gate does not take (plans of other variants included), a length outside 1..T, a row whose own frame count the pyramid
+ * does not take (srf_pyramid_ragged_frames_ok: at D <= 4 the lengths off the 16-frame chunk grid; at D = 5 every length of at
+ * least 1280 samples passes).  Placement as srf_forward_ragged. */
+int srf_original_ragged_supported(const srf_plan* plan);
+size_t srf_original_ragged_workspace_bytes(const srf_plan* plan);
+int srf_original_forward_ragged(const srf_plan* plan, const float* const* params, int num_params, const float* wav,
+                                const int* lengths /* host, [batch] */, float* out, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int srf_original_separate_ragged(const srf_plan* plan, const float* const* params, int num_params, const float* wav,
+                                 const int* lengths /* host, [batch] */, float* out, float* stats /* [batch][2], written */,
+                                 int mixture_consistency, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Causal plans only: the per-block plain attributes alpha / beta of UConvBlock (both 1.0 as the reference constructs them,
  * the default of a new plan).  srf_forward computes res_conv(.) * skipinit_gain * alpha[i] + x and proj_1x1(x / beta[i]).
  * alpha, beta: host arrays of n = num_blocks floats.  Call before the plan's first forward. */
@@ -357,6 +382,24 @@ int srf_wav_stats_ragged(const float* wav, const int* lengths /* host */, float*
  * length outside 1..T.  Sources and wav: any float-aligned address (4-byte copies); a source must not overlap wav. */
 int srf_wav_gather_ragged(const float* const* rows /* host array of device pointers */, const int* lengths /* host */,
                           float* wav /* [batch, 1, T] */, int batch, int T, void* stream);
+/* The original model's own kernels over a ragged batch (their uniform twins: "Original SuDoRM-RF" below; additive to ABI 19).
+ * srf_gln_apply_c_ragged: group g is frames[g] columns long (frames[g] % 4 == 0).  x and add are not read at columns >=
+ *   frames[g]; y is exact 0 on [frames[g], length); the GlobLN count is channels * frames[g]; out_sums run over the group's own
+ *   columns.  With frames[g] == length for every g, y is bit for bit srf_gln_apply_c's.  Any float-aligned address.
+ * srf_encoder_bias_relu_ragged (K = 21 only, not under kernel mode 1): samples at or past lengths[b] are never read (with
+ *   in_stats the zero padding is that of the normalised signal); frames at or past frames[b] are stored as exact 0 -- relu(bias)
+ *   is not zero -- and the sums run over the example's own frames.  Requires lengths[b] <= (K/2) * frames[b].
+ * srf_softmax_mask_ragged: z and enc are not read at columns >= frames[b] (z may hold anything there, NaN included); v is
+ *   exact 0 there.  v may be z.
+ * srf_bias_rescale_ragged: t < lengths[b]: as srf_bias_rescale; t >= lengths[b]: exactly 0.f, and wav is never read there. */
+int srf_gln_apply_c_ragged(const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y,
+                           double* out_sums, int groups, int channels, int length, const int* frames, void* stream);
+int srf_encoder_bias_relu_ragged(const float* wav, const float* w, const float* bias, float* out, double* sums, int Bt, int T,
+                                 int N, int K, int L, const int* lengths, const int* frames, const float* in_stats, void* stream);
+int srf_softmax_mask_ragged(const float* z, const float* enc, float* v, int Bt, int S, int N, int L, const int* frames,
+                            void* stream);
+int srf_bias_rescale_ragged(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
+                            const int* lengths, void* stream);
 
 /* sums[g][bucket][0..1] += {sum, sumsq} of x[g, :, :] (x: [groups, channels*length]). */
 int srf_gln_stats(const float* x, double* sums, int groups, long per_group, void* stream);

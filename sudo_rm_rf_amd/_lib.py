@@ -217,6 +217,14 @@ _PROTOS = {
     "srf_softmax_mask": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "srf_decoder_weight_expand": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "srf_bias_rescale": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "srf_gln_apply_c_ragged": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(_i), _vp]),
+    "srf_encoder_bias_relu_ragged": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _vp, _vp]),
+    "srf_softmax_mask_ragged": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), _vp]),
+    "srf_bias_rescale_ragged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), _vp]),
+    "srf_original_ragged_supported": (_i, [_vp]),
+    "srf_original_ragged_workspace_bytes": (_sz, [_vp]),
+    "srf_original_forward_ragged": (_i, [_vp, C.POINTER(_vp), _i, _vp, C.POINTER(_i), _vp, _vp, _sz, _vp]),
+    "srf_original_separate_ragged": (_i, [_vp, C.POINTER(_vp), _i, _vp, C.POINTER(_i), _vp, _vp, _i, _vp, _sz, _vp]),
     "srf_perm_inv_sisdr_backward": (_i, [_vp, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "srf_original_train_saved_bytes": (_sz, [_vp]),
     "srf_original_train_scratch_bytes": (_sz, [_vp]),

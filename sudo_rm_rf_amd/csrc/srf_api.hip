@@ -191,9 +191,10 @@ extern "C" int srf_decoder(const float* v, const float* w, float* out, int Bt, i
 }
 // post_stats / post_wav / post_mc: the callers' rescale (+ mixture consistency) folded into the overlap-add (srf_separate)
 // in_prelu: a PReLU slope applied to v as the frame GEMM loads it (the causal model's mask_nl_class), NULL = none
+// lens / frames: the ragged overlap-add (srf_original_forward_ragged); the transpose and the frame GEMM run over every column
 int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T,
                      float* scratch, const float* post_stats, const float* post_wav, int post_mc, void* stream,
-                     const float* in_prelu) {
+                     const float* in_prelu, const SrfFrames* lens, const SrfFrames* frames) {
   SRF_CHECK_ARG(v && w && out && scratch, "srf_decoder: null pointer");
   SRF_CHECK_ARG(Bt > 0 && Ci > 0 && Co > 0 && L > 0 && T > 0, "srf_decoder: bad sizes");
   SRF_CHECK_ARG(K >= 3 && (K & 1), "srf_decoder: kernel size must be odd (got %d)", K);
@@ -212,7 +213,7 @@ int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci,
   const srf_norm act{nullptr, nullptr, nullptr, in_prelu};
   rc = srf_pw_conv(v, wt, zb, z, Bt, Ci, M, L, in_prelu ? &act : nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
   if (rc) return rc;
-  return srf_overlap_add_launch(z, out, Bt, Co, K, L, T, 1, post_stats, post_wav, post_mc, st);
+  return srf_overlap_add_launch(z, out, Bt, Co, K, L, T, 1, post_stats, post_wav, post_mc, st, lens, frames);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -476,11 +477,7 @@ static int forward_check_args(const char* who, bool ptrs, const srf_plan* p, con
 
 // ---- the steps of the walk, one per kernel family: the uniform entry point, or -- rg != NULL, srf_forward_ragged -- its ragged
 // twin with the batch's frame counts.  Every per-launch refusal stays with the entry point.
-struct Ragged {
-  const int* lengths;                 // samples per example (host, the caller's)
-  int frames[SRF_RAGGED_MAX_BATCH];   // frames per example: its own padded length / hop, as its batch-1 plan would have it
-  SrfFrames lens_t, frames_t;         // the same two by value, for the overlap-add
-};
+// (struct Ragged: srf_internal.h)
 static int step_encoder(const Ragged* rg, const float* wav, const float* w, float* enc, double* sums, int Bt, int A, int T, int N,
                         int K, int L, const float* wav_stats, void* stream) {
   return rg ? srf_encoder_ragged_impl(wav, w, enc, sums, Bt, A, T, N, K, L, rg->lengths, rg->frames, wav_stats, stream)

@@ -44,7 +44,8 @@ int srf_wav_stats_ragged_launch(const float* wav, const SrfFrames& lens, float* 
 int srf_zero_launch(void* p, size_t bytes, hipStream_t st);
 // post_stats / post_wav / post_mc: the callers' rescale (+ mixture consistency) folded into the overlap-add (srf_separate)
 int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci, int Co, int K, int L, int T, float* scratch,
-                     const float* post_stats, const float* post_wav, int post_mc, void* stream, const float* in_prelu = nullptr);
+                     const float* post_stats, const float* post_wav, int post_mc, void* stream, const float* in_prelu = nullptr,
+                     const SrfFrames* lens = nullptr, const SrfFrames* frames = nullptr);   // (both or neither: the ragged overlap-add)
 
 // ---- srf_attention.hip / srf_attentive.hip
 // srf_mha_attention with an example stride per operand (q, k, v as thirds of one [Bt, 3 H d, L] projection)
@@ -56,11 +57,16 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
 // ---- srf_attentive_v3.hip
 int srf_attentive_v3_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                              const float* wav_stats, int mixture_consistency, void* stream);
+// A ragged batch as the walks carry it (forward_walk in srf_api.hip, srf_original_forward): NULL = the uniform call
+struct Ragged {
+  const int* lengths;                 // samples per example (host, the caller's)
+  int frames[SRF_RAGGED_MAX_BATCH];   // frames per example: its own padded length / hop, as its batch-1 plan would have it
+  SrfFrames lens_t, frames_t;         // the same two by value, for the overlap-add
+};
 // ---- srf_original.hip
 int srf_original_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
-                         const float* wav_stats, int mixture_consistency, void* stream);
+                         const float* wav_stats, int mixture_consistency, void* stream, const Ragged* rg = nullptr);
 // the Improved walk's mask + decoder tail (srf_api.hip), shared with the attentive walks; rg: forward_walk's ragged batch, else NULL
-struct Ragged;
 int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur, float* out, void* workspace, bool use_pack,
                       const float* wav_stats, const float* wav, int mixture_consistency, const Ragged* rg, void* stream);
 

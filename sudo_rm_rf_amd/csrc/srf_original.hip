@@ -18,6 +18,16 @@
 //   z   = Tz xr + m.bias                                      srf_pw_conv_packed over the Toeplitz weight srf_mask_weight_fill wrote
 //   v   = softmax_s(z) * s                                    srf_softmax_mask
 //   out = decoder(v) + decoder.bias [rescale, mixture consistency]   srf_decoder_impl over the block-diagonal weight, srf_bias_rescale
+//
+// Ragged batches (opt-in: srf_original_forward_ragged / srf_original_separate_ragged): the SAME walk with a
+// frames table.  L stays the row stride; example b has L_b = frames[b] columns (its own length padded to a multiple of
+// lcm(hop, 2^D), over the hop) and len_b samples, and every kernel above runs as its ragged twin.  Invariants:
+//   * every tensor whose statistics are taken -- s, y1, the merged pyramid output m, g and g + x -- is exact zero on [L_b, L);
+//   * a and e are zero there too;
+//   * the block stream x is written by srf_gln_apply_c, so it is zero there as well; l1's output is the one block-stream tensor
+//     the invariant does not rest on (only pointwise consumers read it);
+//   * z is unspecified there; srf_softmax_mask stores v as exact zeros, so the decoder's frame GEMM sees zeros, and out is exactly
+//     0 from len_b on.
 #include <vector>
 #include "srf_plan.h"
 
@@ -38,16 +48,42 @@ __device__ __forceinline__ float gln_c_one(float x, const GlnCRow& r) {
   return v;
 }
 
-template <bool VEC, bool ADD>
+// RAGGED (srf_gln_apply_c_ragged; FR = SrfFrames): `length` stays the row stride, group g is frames[g] columns long (a multiple
+// of 4).  x and add are not read at columns >= frames[g], y is stored as exact 0 there, the GlobLN count is channels * frames[g]
+// and out_sums run over the group's own columns; a (row, chunk) block wholly past the end stores its zeros and loads nothing.
+// The end may cut a chunk anywhere: with a base off the 16-byte grid it falls inside one 16-byte group, which then goes
+// element by element.
+template <bool VEC, bool ADD, typename... FR>
 __global__ __launch_bounds__(256) void srf_gln_apply_c_kernel(const float* __restrict__ x, SrfNormDev n, const float* __restrict__ slopes,
                                                               const float* __restrict__ add, float* __restrict__ y,
                                                               double* __restrict__ out_sums, double inv_count, int channels,
-                                                              int length, int chunks) {
+                                                              int length, int chunks, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   __shared__ double red[8];
   const long row = blockIdx.x / chunks;
   const int chunk = (int)(blockIdx.x - row * chunks);
   const int c = (int)(row % channels);
   const long g = row / channels;
+  int own = 0;      // (RAGGED only) elements of this chunk inside the group's own columns: 1 .. cnt
+  if constexpr (RAGGED) {
+    const int Lg = srf_frames_of((int)g, fr...);
+    const int cnt = min(GC_CHUNK, length - chunk * GC_CHUNK);
+    own = min(cnt, Lg - chunk * GC_CHUNK);
+    inv_count = 1.0 / ((double)channels * (double)Lg);
+    if (own <= 0) {      // block-uniform: zeros, nothing loaded, nothing added to the statistics
+      float* yp = y + (size_t)row * length + (size_t)chunk * GC_CHUNK;
+      if constexpr (VEC) {
+        const int head = min(cnt, (int)(((16 - ((size_t)yp & 15)) & 15) >> 2));
+        const int nv = (cnt - head) >> 2, tail0 = head + 4 * nv;
+        if ((int)threadIdx.x < head) yp[threadIdx.x] = 0.f;
+        for (int i = threadIdx.x; i < nv; i += 256) *reinterpret_cast<float4*>(yp + head + 4 * i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if ((int)threadIdx.x < cnt - tail0) yp[tail0 + threadIdx.x] = 0.f;
+      } else {
+        for (int i = threadIdx.x; i < cnt; i += 256) yp[i] = 0.f;
+      }
+      return;
+    }
+  }
   float mean, rstd;
   srf_finalize_stats(n.sums, g, inv_count, mean, rstd);
   GlnCRow r;
@@ -68,12 +104,28 @@ __global__ __launch_bounds__(256) void srf_gln_apply_c_kernel(const float* __res
     ds += (double)v;
     dq += (double)v * (double)v;
   };
+  // (RAGGED) element i of the chunk: the group's own, or zero padding
+  auto one_or_zero = [&](int i) {
+    if (!RAGGED || i < own) one(i);
+    else yp[i] = 0.f;
+  };
   if constexpr (VEC) {
     const int head = min(cnt, (int)(((16 - ((size_t)xp & 15)) & 15) >> 2));      // dwords up to the 16-byte grid
     const int nv = (cnt - head) >> 2;
     const int tail0 = head + 4 * nv;
-    if ((int)threadIdx.x < head) one(threadIdx.x);
+    if ((int)threadIdx.x < head) one_or_zero(threadIdx.x);
     for (int i = threadIdx.x; i < nv; i += 256) {
+      if constexpr (RAGGED) {
+        const int p = head + 4 * i;
+        if (p >= own) {
+          *reinterpret_cast<float4*>(yp + p) = make_float4(0.f, 0.f, 0.f, 0.f);
+          continue;
+        }
+        if (p + 4 > own) {      // the one group the end cuts
+          for (int e = 0; e < 4; ++e) one_or_zero(p + e);
+          continue;
+        }
+      }
       const float4 a = *reinterpret_cast<const float4*>(xp + head + 4 * i);
       float4 o;
       o.x = gln_c_one(a.x, r), o.y = gln_c_one(a.y, r), o.z = gln_c_one(a.z, r), o.w = gln_c_one(a.w, r);
@@ -85,34 +137,52 @@ __global__ __launch_bounds__(256) void srf_gln_apply_c_kernel(const float* __res
       ds += ((double)o.x + (double)o.y) + ((double)o.z + (double)o.w);
       dq += ((double)o.x * o.x + (double)o.y * o.y) + ((double)o.z * o.z + (double)o.w * o.w);
     }
-    if ((int)threadIdx.x < cnt - tail0) one(tail0 + threadIdx.x);
+    if ((int)threadIdx.x < cnt - tail0) one_or_zero(tail0 + threadIdx.x);
   } else {
-    for (int i = threadIdx.x; i < cnt; i += 256) one(i);
+    for (int i = threadIdx.x; i < cnt; i += 256) one_or_zero(i);
   }
   if (out_sums) srf_block_stats_atomic<4>(ds, dq, srf_stat_slot(out_sums, g, blockIdx.x), red);
 }
 
-extern "C" int srf_gln_apply_c(const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y, double* out_sums,
-                               int groups, int channels, int length, void* stream) {
-  SRF_CHECK_ARG(x && y && norm && groups > 0 && channels > 0 && length > 0, "srf_gln_apply_c: bad arguments");
-  SRF_CHECK_ARG(norm->sums && norm->gamma && norm->beta, "srf_gln_apply_c: the norm needs statistics, gamma and beta");
-  SRF_CHECK_ARG((const void*)norm->sums != (const void*)out_sums, "srf_gln_apply_c: out_sums must not be norm.sums");
+// who: the entry point's name in its refusals; frames: NULL = the uniform call, else one entry per group (srf_gln_apply_c_ragged)
+static int gln_apply_c_impl(const char* who, const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y,
+                            double* out_sums, int groups, int channels, int length, const int* frames, void* stream) {
+  SRF_CHECK_ARG(x && y && norm && groups > 0 && channels > 0 && length > 0, "%s: bad arguments", who);
+  SRF_CHECK_ARG(norm->sums && norm->gamma && norm->beta, "%s: the norm needs statistics, gamma and beta", who);
+  SRF_CHECK_ARG((const void*)norm->sums != (const void*)out_sums, "%s: out_sums must not be norm.sums", who);
   {
     // y overlaps neither input: blocks of other rows would read what this one has already overwritten
     const size_t bytes = sizeof(float) * (size_t)groups * channels * length;
     auto overlaps = [&](const float* in) { return in && (const char*)y < (const char*)in + bytes && (const char*)in < (const char*)y + bytes; };
-    SRF_CHECK_ARG(!overlaps(x) && !overlaps(add), "srf_gln_apply_c: y must not overlap x or add");
+    SRF_CHECK_ARG(!overlaps(x) && !overlaps(add), "%s: y must not overlap x or add", who);
   }
-  SRF_CHECK_ALIGNED16("srf_gln_apply_c", {"norm.sums", norm->sums});
-  SRF_CHECK_ARG((((size_t)x | (size_t)y | (size_t)add) & 3) == 0, "srf_gln_apply_c: x, add and y must be float-aligned");
+  SRF_CHECK_ALIGNED16(who, {"norm.sums", norm->sums});
+  SRF_CHECK_ARG((((size_t)x | (size_t)y | (size_t)add) & 3) == 0, "%s: x, add and y must be float-aligned", who);
   const int chunks = (length + GC_CHUNK - 1) / GC_CHUNK;
   const long blocks = (long)groups * channels * chunks;
-  SRF_CHECK_ARG(blocks < (1L << 31), "srf_gln_apply_c: tensor too large");
+  SRF_CHECK_ARG(blocks < (1L << 31), "%s: tensor too large", who);
   const bool vec = srf_kernel_mode() != 1 && (((size_t)x ^ (size_t)y) & 15) == 0 && (!add || (((size_t)x ^ (size_t)add) & 15) == 0);
   const SrfNormDev nd{norm->sums, norm->gamma, norm->beta, nullptr};
   const double inv = 1.0 / ((double)channels * (double)length);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)blocks), blk(256);
+  if (frames) {
+    SrfFrames fr;
+    const int rc = srf_frames_table(who, frames, groups, length, &fr);
+    if (rc) return rc;
+    for (int g = 0; g < groups; ++g)
+      SRF_CHECK_ARG(frames[g] % 4 == 0, "%s: example %d has %d frames: not a multiple of 4", who, g, frames[g]);
+    if (vec && add)
+      hipLaunchKernelGGL((srf_gln_apply_c_kernel<true, true, SrfFrames>), grid, blk, 0, st, x, nd, slopes, add, y, out_sums, inv, channels, length, chunks, fr);
+    else if (vec)
+      hipLaunchKernelGGL((srf_gln_apply_c_kernel<true, false, SrfFrames>), grid, blk, 0, st, x, nd, slopes, add, y, out_sums, inv, channels, length, chunks, fr);
+    else if (add)
+      hipLaunchKernelGGL((srf_gln_apply_c_kernel<false, true, SrfFrames>), grid, blk, 0, st, x, nd, slopes, add, y, out_sums, inv, channels, length, chunks, fr);
+    else
+      hipLaunchKernelGGL((srf_gln_apply_c_kernel<false, false, SrfFrames>), grid, blk, 0, st, x, nd, slopes, add, y, out_sums, inv, channels, length, chunks, fr);
+    SRF_CHECK_LAUNCH(vec ? "gln_apply_c_ragged" : "gln_apply_c_scalar_ragged", st);
+    return SRF_OK;
+  }
   if (vec && add)
     hipLaunchKernelGGL((srf_gln_apply_c_kernel<true, true>), grid, blk, 0, st, x, nd, slopes, add, y, out_sums, inv, channels, length, chunks);
   else if (vec)
@@ -124,6 +194,15 @@ extern "C" int srf_gln_apply_c(const float* x, const srf_norm* norm, const float
   SRF_CHECK_LAUNCH(vec ? "gln_apply_c" : "gln_apply_c_scalar", st);
   return SRF_OK;
 }
+extern "C" int srf_gln_apply_c(const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y, double* out_sums,
+                               int groups, int channels, int length, void* stream) {
+  return gln_apply_c_impl("srf_gln_apply_c", x, norm, slopes, add, y, out_sums, groups, channels, length, nullptr, stream);
+}
+extern "C" int srf_gln_apply_c_ragged(const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y,
+                                      double* out_sums, int groups, int channels, int length, const int* frames, void* stream) {
+  SRF_CHECK_ARG(frames != nullptr, "srf_gln_apply_c_ragged: null frames table");
+  return gln_apply_c_impl("srf_gln_apply_c_ragged", x, norm, slopes, add, y, out_sums, groups, channels, length, frames, stream);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Encoder with bias and ReLU: out[b, n, l] = relu(bias[n] + sum_k w[n, k] xpad[b, h l + k - h]), one audio channel, any odd K.
@@ -131,11 +210,17 @@ extern "C" int srf_gln_apply_c(const float* x, const srf_norm* norm, const float
 // function is wave-uniform: taps and bias are scalar operands.  KT = the compile-time K with the lane's window in registers;
 // KT = 0: any K, the window read from LDS in the inner loop.  Statistics of the stored (post-ReLU) output.
 // ---------------------------------------------------------------------------------------------
-template <int KT>
+// RAGGED (srf_encoder_bias_relu_ragged; TABS = SrfFrames samples, SrfFrames frames; KT = 21 only): T and L stay the row strides,
+// example b is lens[b] samples and frames[b] frames long.  Samples at or past lens[b] are never read -- with in_stats the padding
+// is that of the NORMALISED signal, zero -- and frames at or past frames[b] are stored as exact 0: relu(bias) is not zero, and
+// frame frames[b] would see the example's last H samples.  The statistics run over the example's own frames; a time tile
+// wholly past the end stores its zeros without staging a window.
+template <int KT, typename... TABS>
 __global__ __launch_bounds__(256) void srf_encoder_bias_relu_kernel(const float* __restrict__ wav, const float* __restrict__ w,
                                                                     const float* __restrict__ bias, float* __restrict__ out,
                                                                     double* __restrict__ sums, int T, int N, int K, int L,
-                                                                    const float* __restrict__ in_stats) {
+                                                                    const float* __restrict__ in_stats, TABS... tabs) {
+  constexpr bool RAGGED = sizeof...(TABS) != 0;
   extern __shared__ __attribute__((aligned(16))) char eb_smem[];
   double* red = reinterpret_cast<double*>(eb_smem);        // 8 doubles
   float* win = reinterpret_cast<float*>(eb_smem + 64);     // [63 H + K]
@@ -144,10 +229,22 @@ __global__ __launch_bounds__(256) void srf_encoder_bias_relu_kernel(const float*
   const int b = blockIdx.y;
   const int l0 = blockIdx.x * 64;
   const float* xb = wav + (size_t)b * T;
+  const int Tb = RAGGED ? srf_frames_of(b, tabs...) : T;     // samples / frames of this example
+  const int Lb = RAGGED ? srf_frames2_of(b, tabs...) : L;
+  if constexpr (RAGGED) {
+    if (l0 >= Lb) {   // block-uniform
+      const int per = ((N + (int)gridDim.z - 1) / (int)gridDim.z + 3) & ~3;
+      const int n_lo = blockIdx.z * per, n_hi = min(N, n_lo + per);
+      const int l = l0 + (int)(threadIdx.x & 63);
+      if (l < L)
+        for (int n = n_lo + (int)(threadIdx.x >> 6); n < n_hi; n += 4) out[((size_t)b * N + n) * L + l] = 0.f;
+      return;
+    }
+  }
   const float im = in_stats ? in_stats[2 * b] : 0.f, iden = in_stats ? in_stats[2 * b + 1] + 1e-9f : 1.f;
   for (int i = threadIdx.x; i < WIN; i += 256) {
     const long t = (long)H * l0 - H + i;
-    win[i] = (t >= 0 && t < T) ? (in_stats ? (xb[t] - im) / iden : xb[t]) : 0.f;
+    win[i] = (t >= 0 && t < Tb) ? (in_stats ? (xb[t] - im) / iden : xb[t]) : 0.f;
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -166,6 +263,7 @@ __global__ __launch_bounds__(256) void srf_encoder_bias_relu_kernel(const float*
 #pragma unroll
       for (int k = 0; k < KT; ++k) acc = fmaf(wn[k], xw[k], acc);
       acc = fmaxf(acc, 0.f);
+      if constexpr (RAGGED) acc = l < Lb ? acc : 0.f;
       if (l < L) {
         out[((size_t)b * N + n) * L + l] = acc;
         ds += (double)acc;
@@ -213,6 +311,35 @@ extern "C" int srf_encoder_bias_relu(const float* wav, const float* w, const flo
   return SRF_OK;
 }
 
+// The ragged form exists for the register-window kernel (K = 21, the model's default; not under kernel mode 1).
+extern "C" int srf_encoder_bias_relu_ragged(const float* wav, const float* w, const float* bias, float* out, double* sums, int Bt, int T,
+                                            int N, int K, int L, const int* lengths, const int* frames, const float* in_stats,
+                                            void* stream) {
+  SRF_CHECK_ARG(wav && w && bias && out, "srf_encoder_bias_relu_ragged: null pointer");
+  SRF_CHECK_ARG(Bt > 0 && T > 0 && N > 0 && L > 0, "srf_encoder_bias_relu_ragged: bad sizes");
+  SRF_CHECK_ARG(K == 21 && srf_kernel_mode() != 1,
+                "srf_encoder_bias_relu_ragged: only the K = 21 kernel has a ragged form (K=%d, kernel mode %d)", K, srf_kernel_mode());
+  SRF_CHECK_ALIGNED16("srf_encoder_bias_relu_ragged", {"sums", sums});
+  SrfFrames lens, fr;
+  int rc = srf_frames_table("srf_encoder_bias_relu_ragged (lengths)", lengths, Bt, T, &lens);
+  if (rc) return rc;
+  rc = srf_frames_table("srf_encoder_bias_relu_ragged (frames)", frames, Bt, L, &fr);
+  if (rc) return rc;
+  for (int b = 0; b < Bt; ++b)
+    SRF_CHECK_ARG((long)lengths[b] <= (long)(K / 2) * frames[b],
+                  "srf_encoder_bias_relu_ragged: example %d: %d samples exceed hop * frames = %d", b, lengths[b], (K / 2) * frames[b]);
+  const size_t lds = 64 + sizeof(float) * (size_t)(63 * (K / 2) + K);
+  hipStream_t st = (hipStream_t)stream;
+  const long bxy = (long)((L + 63) / 64) * Bt, want = 32L * srf_device_cus();      // (grid: as srf_encoder_bias_relu)
+  int nz = bxy >= want ? 1 : (int)((want + bxy - 1) / bxy);
+  nz = nz > N / 16 ? (N / 16 > 0 ? N / 16 : 1) : nz;
+  dim3 grid((L + 63) / 64, Bt, nz);
+  hipLaunchKernelGGL((srf_encoder_bias_relu_kernel<21, SrfFrames, SrfFrames>), grid, dim3(256), lds, st, wav, w, bias, out, sums, T, N, K,
+                     L, in_stats, lens, fr);
+  SRF_CHECK_LAUNCH("encoder_bias_relu_ragged", st);
+  return SRF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // The mask layer Conv2d(1 -> S, (N + 1, 1), padding (N - N / 2, 0)) as a GEMM weight: tz[s N + i, n] = mw[s, n - i + pad] where
 // 0 <= n - i + pad <= N, else 0 (written); bias_rows[s N + i] = mb[s].  A copy: no arithmetic on the values.
@@ -250,13 +377,23 @@ extern "C" int srf_mask_weight_fill(const float* mw, const float* mb, float* tz,
 // throughout and no table of S plane offsets in scalar registers.  v may be z: a thread reads all of its S logits before it
 // writes any.
 // ---------------------------------------------------------------------------------------------
-template <int SMAX>
+// RAGGED (srf_softmax_mask_ragged; FR = SrfFrames): z and enc are not read at columns >= frames[b] -- z comes out of the block
+// stream through pointwise GEMMs and is unspecified there -- and v is stored as exact 0, so the decoder's frame GEMM sees zeros.
+template <int SMAX, typename... FR>
 __global__ __launch_bounds__(256) void srf_softmax_mask_kernel(const float* z, const float* __restrict__ enc, float* v, int S, int N,
-                                                               int L, size_t per_example, size_t total) {
+                                                               int L, size_t per_example, size_t total, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   const size_t plane = (size_t)N * L;      // one source of one example
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
     const size_t b = idx / per_example, r = idx - b * per_example;      // r = i L + l
     const size_t at = b * S * plane + r;
+    if constexpr (RAGGED) {
+      if ((int)(r % (size_t)L) >= srf_frames_of((int)b, fr...)) {
+        float* vp = v + at;
+        for (int s = 0; s < S; ++s, vp += plane) *vp = 0.f;
+        continue;
+      }
+    }
     const float e = enc[idx];
     float zv[SMAX];
     float mx = -__builtin_inff();
@@ -308,6 +445,27 @@ extern "C" int srf_softmax_mask(const float* z, const float* enc, float* v, int 
   return SRF_OK;
 }
 
+extern "C" int srf_softmax_mask_ragged(const float* z, const float* enc, float* v, int Bt, int S, int N, int L, const int* frames,
+                                       void* stream) {
+  SRF_CHECK_ARG(z && enc && v, "srf_softmax_mask_ragged: null pointer");
+  SRF_CHECK_ARG(Bt > 0 && N > 0 && L > 0, "srf_softmax_mask_ragged: bad sizes");
+  SRF_CHECK_ARG(S >= 1 && S <= SRF_SOFTMAX_MASK_MAX_SOURCES, "srf_softmax_mask_ragged: num_sources = %d unsupported (1..%d)", S,
+                SRF_SOFTMAX_MASK_MAX_SOURCES);
+  SRF_CHECK_ARG((const void*)enc != (const void*)v, "srf_softmax_mask_ragged: v must not be enc");
+  SrfFrames fr;
+  const int rc = srf_frames_table("srf_softmax_mask_ragged", frames, Bt, L, &fr);
+  if (rc) return rc;
+  const size_t per = (size_t)N * L, total = per * Bt, blocks = (total + 255) / 256;
+  const dim3 grid((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20)));
+  if (S <= 4)
+    hipLaunchKernelGGL((srf_softmax_mask_kernel<4, SrfFrames>), grid, dim3(256), 0, (hipStream_t)stream, z, enc, v, S, N, L, per, total, fr);
+  else
+    hipLaunchKernelGGL((srf_softmax_mask_kernel<SRF_SOFTMAX_MASK_MAX_SOURCES, SrfFrames>), grid, dim3(256), 0, (hipStream_t)stream, z, enc,
+                       v, S, N, L, per, total, fr);
+  SRF_CHECK_LAUNCH("softmax_mask_ragged", stream);
+  return SRF_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Grouped ConvTranspose1d weight [S N, 1, K] -> block-diagonal [S N, S, K]: row c keeps its K taps in column group c / N, zeros
 // elsewhere (written: the workspace holds anything).
@@ -338,13 +496,22 @@ extern "C" int srf_decoder_weight_expand(const float* w, float* wexp, int N, int
 // decoder.bias, then the callers' recipe exactly as the overlap-add's POST form has it (srf_elementwise.hip): est = out + bias[s];
 // stats: est = est * std + mean; mc: + ((wav - mean) / (std + 1e-9) - sum_s est_s) / S.  One thread per (b, t), in place.
 // ---------------------------------------------------------------------------------------------
-template <bool POST>
+// RAGGED (srf_bias_rescale_ragged; FR = SrfFrames samples): t >= lens[b] is stored as exactly 0 and wav is never read there.
+template <bool POST, typename... FR>
 __global__ __launch_bounds__(256) void srf_bias_rescale_kernel(float* __restrict__ out, const float* __restrict__ bias,
                                                                const float* __restrict__ stats, const float* __restrict__ wav, int mc,
-                                                               int S, int T) {
+                                                               int S, int T, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   const long b = blockIdx.y;
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= T) return;
+  if constexpr (RAGGED) {
+    if (t >= srf_frames_of((int)b, fr...)) {
+      float* ob = out + (size_t)b * S * T + t;
+      for (int s = 0; s < S; ++s) ob[(size_t)s * T] = 0.f;
+      return;
+    }
+  }
   float mean = 0.f, sd = 1.f;
   if constexpr (POST) {
     mean = stats[2 * b];
@@ -379,6 +546,29 @@ extern "C" int srf_bias_rescale(float* out, const float* bias, const float* stat
     hipLaunchKernelGGL(srf_bias_rescale_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, out, bias, stats, wav, 0, S, T);
   SRF_CHECK_LAUNCH("bias_rescale", stream);
   return SRF_OK;
+}
+
+// the launch alone, from a table the caller has checked (srf_original_forward's ragged walk: the one its overlap-add uses)
+static int bias_rescale_ragged_launch(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
+                                      const SrfFrames& lens, void* stream) {
+  const dim3 grid((T + 255) / 256, Bt);
+  if (stats)
+    hipLaunchKernelGGL((srf_bias_rescale_kernel<true, SrfFrames>), grid, dim3(256), 0, (hipStream_t)stream, out, bias, stats, wav, mc, S, T,
+                       lens);
+  else
+    hipLaunchKernelGGL((srf_bias_rescale_kernel<false, SrfFrames>), grid, dim3(256), 0, (hipStream_t)stream, out, bias, stats, wav, 0, S, T,
+                       lens);
+  SRF_CHECK_LAUNCH("bias_rescale_ragged", stream);
+  return SRF_OK;
+}
+extern "C" int srf_bias_rescale_ragged(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
+                                       const int* lengths, void* stream) {
+  SRF_CHECK_ARG(out && bias && Bt > 0 && S > 0 && T > 0, "srf_bias_rescale_ragged: bad arguments");
+  SRF_CHECK_ARG(!stats || !mc || wav, "srf_bias_rescale_ragged: mixture consistency needs the raw mixture");
+  SrfFrames lens;
+  const int rc = srf_frames_table("srf_bias_rescale_ragged", lengths, Bt, T, &lens);
+  if (rc) return rc;
+  return bias_rescale_ragged_launch(out, bias, stats, wav, mc, Bt, S, T, lens, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -486,8 +676,58 @@ extern "C" int srf_original_plan_create(const srf_config* base, int batch, int T
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
+// ---- the steps of the walk, one per kernel family: the uniform entry point, or -- rg != NULL, srf_original_forward_ragged --
+// its ragged twin with the batch's tables.  Every per-launch refusal stays with the entry point.
+static int step_encoder(const Ragged* rg, const float* wav, const float* w, const float* bias, float* enc, double* sums, int Bt, int T,
+                        int N, int K, int L, const float* wav_stats, void* stream) {
+  return rg ? srf_encoder_bias_relu_ragged(wav, w, bias, enc, sums, Bt, T, N, K, L, rg->lengths, rg->frames, wav_stats, stream)
+            : srf_encoder_bias_relu(wav, w, bias, enc, sums, Bt, T, N, K, L, wav_stats, stream);
+}
+// ragged: always the 256 x 128 kernel (the gate has made sure every conv of the model has a packed image and a shape it takes)
+static int step_conv(const Ragged* rg, const float* x, const float* w, const void* w_packed, const float* bias, float* y, int Bt, int Cin,
+                     int Cout, int L, const srf_norm* in_norm, double* out_sums, void* stream) {
+  return rg ? srf_pw_conv_packed_ragged(x, w, w_packed, bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, 0, nullptr, 0, rg->frames,
+                                        stream)
+            : srf_pw_conv_packed(x, w, w_packed, bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, 0, nullptr, 0, stream);
+}
+static int step_gln(const Ragged* rg, const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y,
+                    double* out_sums, int Bt, int C, int L, void* stream) {
+  return rg ? srf_gln_apply_c_ragged(x, norm, slopes, add, y, out_sums, Bt, C, L, rg->frames, stream)
+            : srf_gln_apply_c(x, norm, slopes, add, y, out_sums, Bt, C, L, stream);
+}
+// the fused pyramid over the materialised activation: no norm on load
+static int step_pyramid(const Ragged* rg, const float* act, float* merged, const SrfOrigBlock& b, int Bt, int C, int L, int D,
+                        void* scratch, double* out_sums, void* stream) {
+  return rg ? srf_pyramid_ragged(act, merged, nullptr, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bt, C, L, D, scratch, out_sums, rg->frames, stream)
+            : srf_pyramid(act, merged, nullptr, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bt, C, L, D, scratch, out_sums, stream);
+}
+static int step_softmax(const Ragged* rg, const float* z, const float* enc, float* v, int Bt, int S, int N, int L, void* stream) {
+  return rg ? srf_softmax_mask_ragged(z, enc, v, Bt, S, N, L, rg->frames, stream) : srf_softmax_mask(z, enc, v, Bt, S, N, L, stream);
+}
+static int step_bias(const Ragged* rg, float* out, const float* bias, const float* wav_stats, const float* wav, int mc, int Bt, int S,
+                     int T, void* stream) {
+  return rg ? bias_rescale_ragged_launch(out, bias, wav_stats, wav, mc, Bt, S, T, rg->lens_t, stream)
+            : srf_bias_rescale(out, bias, wav_stats, wav, mc, Bt, S, T, stream);
+}
+
+// THE walk of the original model's inference forward: srf_forward, srf_separate (wav_stats), srf_original_forward_ragged (rg) and
+// srf_original_separate_ragged (both).
+// The ragged forward keeps the layout -- [batch, C, L] with L the PLAN's frame count as row stride, the same workspace carve-up --
+// and every kernel takes the example's own frame count L_b (its own length padded by THIS model's rule, lcm(hop, 2^D), over the
+// hop) from a by-value table.  The invariants:
+//   * every tensor whose GlobLN statistics are taken -- s, y1, the merged pyramid output m, g and g + x -- is exactly zero on
+//     [L_b, L), so the sums come out right and only the count changes (C * L_b);
+//   * a and e (srf_gln_apply_c's outputs, the pyramid's and conv_1x1_exp's inputs) are zero there too: the pyramid reads its
+//     input with a halo only up to L_b, the GEMM is pointwise;
+//   * the block stream x is written by srf_gln_apply_c, so it is zero there as well.  l1's output is the one block-stream tensor
+//     the invariant does not rest on (only pointwise consumers read it: proj_1x1 and, below L_b, the residual add);
+//   * the mask logits z are unspecified on [L_b, L): srf_softmax_mask reads neither them nor s there and stores v as exact
+//     zeros, so the decoder's frame GEMM (unchanged, over every column) sees zeros and the ragged overlap-add reads the example's
+//     own frames only; out is exactly 0 from the example's length on.
+// srf_mask_weight_fill, srf_decoder_weight_expand, the mask GEMM / reshape_before_masks (the plain ragged GEMM) and the decoder's
+// transpose + frame GEMM run over every column.
 int srf_original_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
-                         const float* wav_stats, int mixture_consistency, void* stream) {
+                         const float* wav_stats, int mixture_consistency, void* stream, const Ragged* rg) {
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, S = c.num_sources;
   const int Bt = p->Bt, L = p->L, B = p->nB, C = p->nC;
@@ -508,20 +748,20 @@ int srf_original_forward(const srf_plan* p, const float* const* P, const float* 
   if (rc) return rc;
   rc = srf_decoder_weight_expand(t.dec_w, wdec, N, S, K, stream);
   if (rc) return rc;
-  const bool use_pack = plan_use_pack(p);
+  // (a ragged batch runs what srf_original_ragged_supported has made sure of: packed weights, the register-resident fused pyramid)
+  const bool use_pack = rg || plan_use_pack(p);
   if (use_pack) {
     rc = plan_pack_weights(p, [&](int param) -> const float* { return param == t.i_m ? tz : P[param]; }, ws, stream);
     if (rc) return rc;
   }
   auto conv = [&](const float* x, const float* w, int param, const float* bias, float* y, int Cin, int Cout, const srf_norm* in_norm,
                   double* out_sums) {
-    return srf_pw_conv_packed(x, w, plan_packed(p, ws, use_pack, param), bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, 0,
-                              nullptr, 0, stream);
+    return step_conv(rg, x, w, plan_packed(p, ws, use_pack, param), bias, y, Bt, Cin, Cout, L, in_norm, out_sums, stream);
   };
 
   // ---- front end: encoder with bias and ReLU (+ ln statistics), ln folded into l1's operand load
   float* enc = fptr(p->off_enc);
-  rc = srf_encoder_bias_relu(wav, f.enc_w, f.enc_b, enc, stats, Bt, p->T, N, K, L, wav_stats, stream);
+  rc = step_encoder(rg, wav, f.enc_w, f.enc_b, enc, stats, Bt, p->T, N, K, L, wav_stats, stream);
   if (rc) return rc;
   float* cur = fptr(p->off_xa);
   {
@@ -532,20 +772,20 @@ int srf_original_forward(const srf_plan* p, const float* const* P, const float* 
 
   // ---- separation module
   float *y1 = fptr(p->off_y1), *act = fptr(p->off_orig_act), *g = fptr(p->off_orig_g), *gx = fptr(p->off_orig_gx);
-  const bool fused = plan_fused_pyramid_now(p);
+  const bool fused = rg || plan_fused_pyramid_now(p);
   for (int i = 0; i < U; ++i) {
     const SrfOrigBlock b = orig_block(p, P, i);
     const SrfOrigSlots s = orig_slots(p, stats, i);
     rc = conv(cur, b.proj_w, b.i_proj, b.proj_b, y1, B, C, nullptr, s.proj);
     if (rc) return rc;
     const srf_norm pn{s.proj, b.proj_g, b.proj_be, nullptr};
-    rc = srf_gln_apply_c(y1, &pn, b.proj_slope, nullptr, act, nullptr, Bt, C, L, stream);
+    rc = step_gln(rg, y1, &pn, b.proj_slope, nullptr, act, nullptr, Bt, C, L, stream);
     if (rc) return rc;
     // the pyramid, its result m into y1 (dead since a exists) with the statistics of final_norm: the fused kernels where they
     // take the shape -- level 0 reads the materialised activation as it is, no norm on load -- else level by level + merge
     // (D = 1: the normalised level 0)
     if (fused) {
-      rc = srf_pyramid(act, y1, nullptr, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bt, C, L, D, ws + p->off_pyr, s.merged, stream);
+      rc = step_pyramid(rg, act, y1, b, Bt, C, L, D, ws + p->off_pyr, s.merged, stream);
       if (rc) return rc;
     } else {
       const float* levels[SRF_MAX_DEPTH];
@@ -563,16 +803,16 @@ int srf_original_forward(const srf_plan* p, const float* const* P, const float* 
     }
     // final_norm + PReLU_c (into a's buffer)
     const srf_norm fn{s.merged, b.fin_g, b.fin_be, nullptr};
-    rc = srf_gln_apply_c(y1, &fn, b.fin_slope, nullptr, act, nullptr, Bt, C, L, stream);
+    rc = step_gln(rg, y1, &fn, b.fin_slope, nullptr, act, nullptr, Bt, C, L, stream);
     if (rc) return rc;
     rc = conv(act, b.exp_w, b.i_exp, b.exp_b, g, C, B, nullptr, s.exp);
     if (rc) return rc;
     // the residual goes in BEFORE module_act's norm
     const srf_norm en{s.exp, b.exp_g, b.exp_be, nullptr};
-    rc = srf_gln_apply_c(g, &en, nullptr, cur, gx, s.act, Bt, B, L, stream);
+    rc = step_gln(rg, g, &en, nullptr, cur, gx, s.act, Bt, B, L, stream);
     if (rc) return rc;
     const srf_norm an{s.act, b.act_g, b.act_be, nullptr};
-    rc = srf_gln_apply_c(gx, &an, b.act_slope, nullptr, cur, nullptr, Bt, B, L, stream);
+    rc = step_gln(rg, gx, &an, b.act_slope, nullptr, cur, nullptr, Bt, B, L, stream);
     if (rc) return rc;
   }
 
@@ -588,10 +828,104 @@ int srf_original_forward(const srf_plan* p, const float* const* P, const float* 
   float* masked = fptr(p->off_masked);
   rc = conv(xm, tz, t.i_m, tz_bias, z, N, S * N, nullptr, nullptr);
   if (rc) return rc;
-  rc = srf_softmax_mask(z, enc, masked, Bt, S, N, L, stream);
+  rc = step_softmax(rg, z, enc, masked, Bt, S, N, L, stream);
   if (rc) return rc;
   // ---- decoder: the frame GEMM + overlap-add over the block-diagonal weight, then the bias (+ the callers' recipe)
-  rc = srf_decoder_impl(masked, wdec, out, Bt, S * N, S, K, L, p->T, fptr(p->off_dec), nullptr, nullptr, 0, stream);
+  rc = srf_decoder_impl(masked, wdec, out, Bt, S * N, S, K, L, p->T, fptr(p->off_dec), nullptr, nullptr, 0, stream, nullptr,
+                        rg ? &rg->lens_t : nullptr, rg ? &rg->frames_t : nullptr);
   if (rc) return rc;
-  return srf_bias_rescale(out, t.dec_b, wav_stats, wav, mixture_consistency, Bt, S, p->T, stream);
+  return step_bias(rg, out, t.dec_b, wav_stats, wav, mixture_consistency, Bt, S, p->T, stream);
 }
+
+// ---------------------------------------------------------------------------------------------
+// ragged forward (opt-in: srf_plan_ragged_supported / srf_forward_ragged / srf_separate_ragged keep refusing an original plan)
+// ---------------------------------------------------------------------------------------------
+// the gate: whether the walk above, with a frames table, has a ragged kernel for every step of this plan -- now, under the current
+// kernel mode and debug flags
+static bool orig_ragged_now(const srf_plan* p, const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (p->cfg.variant != SRF_VARIANT_ORIGINAL) return no("not a plan of srf_original_plan_create");
+  const srf_config& c = p->cfg;
+  const int D = c.upsampling_depth, N = c.enc_num_basis, S = c.num_sources, B = p->nB, C = p->nC, L = p->L, Bt = p->Bt;
+  if (c.enc_kernel_size != 21) return no("the ragged encoder is the K = 21 kernel");
+  if (Bt > SRF_RAGGED_MAX_BATCH) return no("the batch exceeds SRF_RAGGED_MAX_BATCH");
+  if (S > 16) return no("more than 16 sources");
+  if (srf_kernel_mode() != 0 || !plan_use_pack(p)) return no("the forward does not run the packed 256 x 128 GEMMs (kernel mode / debug flags / shapes)");
+  if (srf_dbg(SRF_DBG_NO_GEMM_256)) return no("the 256 x 128 GEMM is switched off (debug flags)");
+  // every conv of the walk on the 256 x 128 kernel: shape, 32-bit reach of its input, at least 8 tiles
+  auto takes = [&](int Cin, int Cout) {
+    return srf_x3w_shape_supported(Cin, Cout, L) && (long)Bt * Cin * L * 4 < (1L << 31) &&
+           (long)Bt * ((Cout + 255) / 256) * ((L + 127) / 128) >= 8;
+  };
+  if (!takes(N, B)) return no("l1's shape is outside the 256 x 128 GEMM (or too few tiles)");
+  if (!takes(B, C)) return no("proj_1x1's shape is outside the 256 x 128 GEMM (or too few tiles)");
+  if (!takes(C, B)) return no("conv_1x1_exp's shape is outside the 256 x 128 GEMM (needs at least 192 output channels; or too few tiles)");
+  if (orig_has_reshape(p) && !takes(B, N)) return no("reshape_before_masks' shape is outside the 256 x 128 GEMM (or too few tiles)");
+  if (!takes(N, S * N)) return no("the mask GEMM's shape is outside the 256 x 128 GEMM (or too few tiles)");
+  if (!plan_fused_pyramid_now(p) || srf_dbg(SRF_DBG_PYR_NO_REG) || !srf_pyramid_reg_supported(L, D))
+    return no("the forward does not run the register-resident fused pyramid at this length");
+  return true;
+}
+extern "C" int srf_original_ragged_supported(const srf_plan* p) { return p && orig_ragged_now(p, nullptr) ? 1 : 0; }
+extern "C" size_t srf_original_ragged_workspace_bytes(const srf_plan* p) { return p && orig_ragged_now(p, nullptr) ? p->total_bytes : 0; }
+
+// What the two entry points (`who`) share: the gate, the argument checks and every example's own padded length, as its batch-1
+// plan would have it -- all refusals BEFORE the first launch
+static int orig_ragged_prepare(const char* who, const srf_plan* p, const float* const* P, int num_params, const int* lengths,
+                               const void* workspace, size_t workspace_bytes, Ragged* rg) {
+  const char* why = "";
+  SRF_CHECK_ARG(orig_ragged_now(p, &why), "%s: plan not supported by the original model's ragged forward: %s", who, why);
+  SRF_CHECK_ARG(num_params == p->n_params, "%s (original): expected %d parameter tensors, got %d", who, p->n_params, num_params);
+  if (workspace_bytes < p->total_bytes) {
+    srf_set_error("%s (original): workspace too small (%zu < %zu bytes)", who, workspace_bytes, p->total_bytes);
+    return SRF_EWORKSPACE;
+  }
+  SRF_CHECK_ARG((((size_t)workspace) & 255) == 0, "%s (original): workspace must be 256-byte aligned", who);
+  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "%s (original): parameter %d is null", who, i);
+  const int D = p->cfg.upsampling_depth, h = p->cfg.enc_kernel_size / 2;
+  const long lcm = (long)h * (1L << D) / orig_gcd(h, 1L << D);
+  rg->lengths = lengths;
+  for (int b = 0; b < p->Bt; ++b) {
+    SRF_CHECK_ARG(lengths[b] >= 1 && lengths[b] <= p->T, "%s (original): example %d has length %d (allowed: 1..%d)", who, b, lengths[b],
+                  p->T);
+    // pad_to_appropriate_length of the example alone: up to a multiple of lcm(hop, 2^D), only when it is not one already
+    const long Tb = lengths[b] % lcm ? lengths[b] + lcm - lengths[b] % lcm : lengths[b];
+    rg->frames[b] = (int)(Tb / h);
+    SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(rg->frames[b], p->L, D),
+                  "%s (original): example %d (length %d = %d frames) is too short for the fused pyramid or off its chunk grid", who, b,
+                  lengths[b], rg->frames[b]);
+  }
+  int rc = srf_frames_table(who, lengths, p->Bt, p->T, &rg->lens_t);
+  if (rc) return rc;
+  return srf_frames_table(who, rg->frames, p->Bt, p->L, &rg->frames_t);
+}
+
+extern "C" int srf_original_forward_ragged(const srf_plan* p, const float* const* P, int num_params, const float* wav, const int* lengths,
+                                           float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  SRF_CHECK_ARG(p && P && wav && lengths && out && workspace, "srf_original_forward_ragged: null pointer");
+  Ragged rg;
+  const int rc = orig_ragged_prepare("srf_original_forward_ragged", p, P, num_params, lengths, workspace, workspace_bytes, &rg);
+  if (rc) return rc;
+  if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
+  return srf_original_forward(p, P, wav, out, workspace, nullptr, 0, stream, &rg);
+}
+
+// srf_separate over a ragged batch: the ragged forward with a statistics launch over every row's own samples in front, the
+// normalisation in the ragged encoder's load and the rescale (+ mixture consistency) in the ragged srf_bias_rescale.  wav: the RAW
+// padded mixture; nothing at or past lengths[b] is read by any of the three.
+extern "C" int srf_original_separate_ragged(const srf_plan* p, const float* const* P, int num_params, const float* wav,
+                                            const int* lengths, float* out, float* stats, int mixture_consistency, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  SRF_CHECK_ARG(p && P && wav && lengths && out && stats && workspace, "srf_original_separate_ragged: null pointer");
+  Ragged rg;
+  int rc = orig_ragged_prepare("srf_original_separate_ragged", p, P, num_params, lengths, workspace, workspace_bytes, &rg);
+  if (rc) return rc;
+  if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
+  rc = srf_wav_stats_ragged_launch(wav, rg.lens_t, stats, p->Bt, p->T, (hipStream_t)stream);
+  if (rc) return rc;
+  return srf_original_forward(p, P, wav, out, workspace, stats, mixture_consistency, stream, &rg);
+}
+

@@ -8,7 +8,8 @@ therefore the same ``state_dict()`` keys, shapes and order: ``nn.GroupNorm(1, C,
 CONTAINERS ONLY: ``SuDORMRF.forward`` hands the parameter pointers to one ``srf_forward`` call on a plan of
 ``srf_original_plan_create`` (include/sudormrf_hip.h) and no ATen compute op runs.  By default the path is inference-only: a forward
 that autograd would have to differentiate raises.  ``SuDORMRF.enable_hip_training()`` opts a model into the HIP training step
-(srf_original_forward_train / srf_original_backward).  There is no CPU fallback.
+(srf_original_forward_train / srf_original_backward), ``SuDORMRF.enable_ragged()`` into ragged-batch
+inference (srf_original_forward_ragged / srf_original_separate_ragged, section 18.2).  There is no CPU fallback.
 """
 import math
 
@@ -206,13 +207,55 @@ class SuDORMRF(nn.Module):
             eng = ModelEngine(self._config_tuple())
             eng.multi_stream = False          # single stream only: the sub-batch split is not extended to this variant
             self.__dict__["_srf_engine"] = eng
+        eng.original_ragged = bool(self.__dict__.get("_srf_ragged"))
         return eng
 
     def __getstate__(self):
         state = self.__dict__.copy()
         state.pop("_srf_engine", None)
         state.pop("_srf_hip_training", None)
+        state.pop("_srf_ragged", None)
         return state
+
+    def __getattr__(self, name):
+        # separate_ragged exists only on a model that has opted in (enable_ragged): without the call hasattr() stays False,
+        # which is what pipeline.ragged_route reads
+        if name == "separate_ragged" and self.__dict__.get("_srf_ragged"):
+            return self._separate_ragged
+        return super().__getattr__(name)
+
+    def enable_ragged(self, flag=True):
+        """Opt this model into (flag=False: out of) ragged-batch inference and return self.  With it, forward_ragged(wav,
+        lengths) and separate_ragged(wav, lengths, mixture_consistency=False) exist and return what the Improved model's
+        return -- unequal-length rows in one set of launches (srf_original_forward_ragged / srf_original_separate_ragged,
+        DESIGN.md section 18.2), each row treated exactly as its own batch-1 forward would treat it -- and
+        pipeline.separate_list batches the utterances whose configuration and length pass the gate.  Without it nothing
+        changes: forward_ragged raises, separate_ragged does not exist, separate_list goes utterance by utterance.  The flag
+        is a plain attribute beside the engine: not in state_dict() and dropped from pickles."""
+        if flag:
+            self.__dict__["_srf_ragged"] = True
+        else:
+            self.__dict__.pop("_srf_ragged", None)
+        return self
+
+    def _ragged_route(self, length=None):
+        """pipeline.ragged_route for this model, from the configuration alone: "ragged" when the model has opted in, its
+        configuration passes the part of srf_original_ragged_supported that does not depend on the batch (K = 21, at most 16
+        sources, every 1x1 convolution a shape of the 256 x 128 GEMM: Cin a multiple of 64 and >= 128, Cout >= 192) and, with
+        `length`, the utterance's own frame count is one the register-resident pyramid takes; else "single"."""
+        if not self.__dict__.get("_srf_ragged"):
+            return "single"
+        B, C, N, S, D = self.out_channels, self.in_channels, self.enc_num_basis, self.num_sources, self.upsampling_depth
+        takes = lambda cin, cout: cin % 64 == 0 and cin >= 128 and cout >= 192 and cout * cin * 4 < 2 ** 31
+        convs = [(N, B), (B, C), (C, B), (N, S * N)] + ([(B, N)] if B != N else [])
+        if self.enc_kernel_size != 21 or S > 16 or D > 6 or not all(takes(i, o) for i, o in convs):
+            return "single"
+        if length is not None:
+            frames = original.padded_frames(length, self.enc_kernel_size, D)
+            chunk = 16 if D <= 5 else 32
+            if (frames >> (D - 1)) < 8 or frames % (1 << (D - 1)) or frames % chunk or frames // chunk < 4:
+                return "single"
+        return "ragged"
 
     def enable_hip_training(self, flag=True):
         """Opt this model into (flag=False: out of) the HIP training step and return self.  With it, a forward that autograd
@@ -270,8 +313,20 @@ class SuDORMRF(nn.Module):
         return out
 
     def forward_ragged(self, input_wav, lengths):
-        raise NotImplementedError("the original model has no ragged kernels: run the utterances one by one "
-                                  "(pipeline.separate_list does)")
+        """After enable_ragged(): unequal-length utterances in ONE forward.  input_wav [batch, 1, time] on the GPU, row b valid
+        up to lengths[b] (a list or CPU int tensor; what lies past it is never read).  Returns [batch, num_sources, time]: row b
+        equals self(input_wav[b:b+1, :, :lengths[b]]) up to lengths[b] and is exactly zero past it.  Inference only."""
+        if not self.__dict__.get("_srf_ragged"):
+            raise NotImplementedError("the original model runs a ragged batch only after enable_ragged(): without it, run the "
+                                      "utterances one by one (pipeline.separate_list does)")
+        return self._engine().run_ragged(self, input_wav, lengths)
+
+    def _separate_ragged(self, input_wav, lengths, mixture_consistency=False):
+        """separate_ragged of a model that has opted in: the caller-side recipe over a ragged batch in ONE call.  input_wav
+        [batch, 1, time] RAW padded mixtures on the GPU.  Returns (estimates [batch, num_sources, time], stats [batch, 2]): row b
+        normalised by the mean / std of its own samples, forward_ragged, rescaled (mixture consistency on request) -- and
+        exactly zero past lengths[b]."""
+        return self._engine().run_separate_ragged(self, input_wav, lengths, mixture_consistency)
 
     def pad_to_appropriate_length(self, x):
         """Kept for API parity: up to a multiple of lcm(K // 2, 2^D), only when the length is not one already.  The HIP path

@@ -147,29 +147,44 @@ class Plan:
         """Whether srf_forward_ragged takes this plan under the current kernel mode (srf_plan_ragged_supported)."""
         return bool(_lib.load().srf_plan_ragged_supported(self.handle))
 
+    @property
+    def original_ragged_supported(self):
+        """Whether srf_original_forward_ragged takes this plan under the current kernel mode (srf_original_ragged_supported): the
+        original model's opt-in gate; `ragged_supported` stays False for its plans."""
+        return bool(_lib.load().srf_original_ragged_supported(self.handle))
+
+    def _ragged_entries(self):
+        """(workspace query, forward, separate) of this plan's variant: the original model has entry points of its own."""
+        if self.cfg_tuple[0] == "original":
+            return ("srf_original_ragged_workspace_bytes", "srf_original_forward_ragged", "srf_original_separate_ragged")
+        return ("srf_plan_ragged_workspace_bytes", "srf_forward_ragged", "srf_separate_ragged")
+
     def forward_ragged(self, param_ptrs, wav, lengths, out):
-        """srf_forward_ragged: `lengths` is a host list; it travels in the launch arguments (nothing synchronises)."""
+        """srf_forward_ragged (the original model: srf_original_forward_ragged): `lengths` is a host list; it travels in the
+        launch arguments (nothing synchronises)."""
         lib = _lib.load()
-        need = lib.srf_plan_ragged_workspace_bytes(self.handle)
+        ws_bytes, forward, _ = self._ragged_entries()
+        need = getattr(lib, ws_bytes)(self.handle)
         if need > self.workspace_bytes:
             raise _lib.SrfError("the ragged forward needs %d workspace bytes, the plan holds %d" % (need, self.workspace_bytes))
         arr = (C.c_int * len(lengths))(*lengths)
-        rc = lib.srf_forward_ragged(self.handle, param_ptrs, self.num_params, _lib.ptr(wav), arr, _lib.ptr(out),
-                                    _lib.ptr(self.workspace), self.workspace_bytes, _lib.current_stream(wav.device))
-        _lib.check(rc, "srf_forward_ragged")
+        rc = getattr(lib, forward)(self.handle, param_ptrs, self.num_params, _lib.ptr(wav), arr, _lib.ptr(out),
+                                   _lib.ptr(self.workspace), self.workspace_bytes, _lib.current_stream(wav.device))
+        _lib.check(rc, forward)
 
     def separate_ragged(self, param_ptrs, wav, lengths, out, stats, mixture_consistency):
         """srf_separate_ragged: per-row statistics over the row's own samples, normalise-on-load, the ragged forward, rescale
         (+ mixture consistency) -- `wav` is the RAW padded mixture, `stats` [batch, 2] is written."""
         lib = _lib.load()
-        need = lib.srf_plan_ragged_workspace_bytes(self.handle)
+        ws_bytes, _, separate = self._ragged_entries()
+        need = getattr(lib, ws_bytes)(self.handle)
         if need > self.workspace_bytes:
             raise _lib.SrfError("the ragged forward needs %d workspace bytes, the plan holds %d" % (need, self.workspace_bytes))
         arr = (C.c_int * len(lengths))(*lengths)
-        rc = lib.srf_separate_ragged(self.handle, param_ptrs, self.num_params, _lib.ptr(wav), arr, _lib.ptr(out), _lib.ptr(stats),
-                                     int(bool(mixture_consistency)), _lib.ptr(self.workspace), self.workspace_bytes,
-                                     _lib.current_stream(wav.device))
-        _lib.check(rc, "srf_separate_ragged")
+        rc = getattr(lib, separate)(self.handle, param_ptrs, self.num_params, _lib.ptr(wav), arr, _lib.ptr(out), _lib.ptr(stats),
+                                    int(bool(mixture_consistency)), _lib.ptr(self.workspace), self.workspace_bytes,
+                                    _lib.current_stream(wav.device))
+        _lib.check(rc, separate)
 
     def debug_fetch(self, what, shape):
         dst = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -398,6 +413,8 @@ class ModelEngine:
         # the causal training step frees its saved activations after the first backward (a step's memory is its activations);
         # True keeps them, for callers that run backward twice over one graph (retain_graph=True)
         self.keep_saved_for_repeat = False
+        # the original model's ragged forward is opt-in (SuDORMRF.enable_ragged sets this)
+        self.original_ragged = False
 
     def _flat_grad_buffer(self, params, total, device):
         """The flat fp32 buffer srf_backward writes all parameter gradients into (zeroed: the weight-gradient kernels
@@ -617,7 +634,9 @@ class ModelEngine:
     def ragged_plan_supported(self, batch, T, device):
         """Whether run_ragged would take a [batch, 1, T] input on `device` (creates / caches the plan, no workspace)."""
         with torch.cuda.device(device):
-            return self.plan_for(batch, T, torch.device(device)).ragged_supported
+            plan = self.plan_for(batch, T, torch.device(device))
+            # (the original model: its own gate, and only for a model that has opted in -- SuDORMRF.enable_ragged)
+            return (plan.original_ragged_supported and self.original_ragged) if self.cfg_tuple[0] == "original" else plan.ragged_supported
 
     def separate(self, module, mixture, mixture_consistency):
         """The reference's caller-side recipe around model() (README.md:100-114) as one srf_separate call: mixture

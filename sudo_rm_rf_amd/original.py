@@ -3,10 +3,13 @@ include/sudormrf_hip.h, "Original SuDoRM-RF").
 
 Same conventions as ``ops``: CUDA float32 tensors in, new tensors out (or ``out=``), torch's current stream.  Kept out of ``ops``
 on purpose: these serve the original model's sub-module forwards and the kernel tests only."""
+import math
+
 import torch
 
 from . import _lib
 from .ops import _chk, _norm
+from .ragged import _table as _host_table
 
 MAX_SOURCES = _lib.SOFTMAX_MASK_MAX_SOURCES
 
@@ -85,6 +88,79 @@ def bias_rescale(est, bias, stats=None, wav=None, mixture_consistency=False):
     rc = _lib.load().srf_bias_rescale(_lib.ptr(est), _lib.ptr(bias), _lib.ptr(stats), _lib.ptr(wav), int(bool(mixture_consistency)),
                                       Bt, S, T, _lib.current_stream(dev))
     _lib.check(rc, "srf_bias_rescale")
+    return est
+
+
+# ---- the ragged forms (include/sudormrf_hip.h, "Ragged forms"): `frames` / `lengths` are host lists, one entry per example
+def _table(values, what, n):
+    arr, got = _host_table(values, what)
+    if got != n:
+        raise _lib.SrfError("%s: %d entries for a batch of %d" % (what, got, n))
+    return arr
+
+
+def padded_frames(length, kernel_size, depth):
+    """Frames of one example of `length` samples as its own batch-1 forward has them: the length padded up to a multiple of
+    lcm(K // 2, 2^depth), only when it is not one already (sudormrf.py, pad_to_appropriate_length), in hops."""
+    h = kernel_size // 2
+    lcm = h * 2 ** depth // math.gcd(h, 2 ** depth)
+    return -(-int(length) // lcm) * lcm // h
+
+
+def gln_apply_c_ragged(x, sums, gamma, beta, frames, slopes=None, add=None, out_sums=None, out=None):
+    """gln_apply_c over groups of unequal length: group g is frames[g] columns long (a multiple of 4); x and add are not read past
+    it, y is exact 0 there, the GlobLN count is C * frames[g] and out_sums run over the group's own columns."""
+    dev = _chk(x, sums, gamma, beta, slopes, add, out_sums, out)
+    groups, channels, length = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    rc = _lib.load().srf_gln_apply_c_ragged(_lib.ptr(x), _norm(sums, gamma, beta, None), _lib.ptr(slopes), _lib.ptr(add), _lib.ptr(out),
+                                            _lib.ptr(out_sums), groups, channels, length, _table(frames, "frames", groups),
+                                            _lib.current_stream(dev))
+    _lib.check(rc, "srf_gln_apply_c_ragged")
+    return out
+
+
+def encoder_bias_relu_ragged(wav, weight, bias, L, lengths, frames, sums=None, in_stats=None):
+    """encoder_bias_relu over rows of unequal length (K = 21): row b is lengths[b] samples = frames[b] frames long; nothing at or
+    past lengths[b] is read, frames at or past frames[b] are exact 0, the sums run over the row's own frames."""
+    dev = _chk(wav, weight, bias, sums, in_stats)
+    Bt, A, T = wav.shape
+    N, A2, K = weight.shape
+    if A != 1 or A2 != 1:
+        raise _lib.SrfError("encoder_bias_relu_ragged: one audio channel only")
+    out = torch.empty((Bt, N, L), dtype=torch.float32, device=dev)
+    rc = _lib.load().srf_encoder_bias_relu_ragged(_lib.ptr(wav), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(out), _lib.ptr(sums), Bt, T,
+                                                  N, K, L, _table(lengths, "lengths", Bt), _table(frames, "frames", Bt),
+                                                  _lib.ptr(in_stats), _lib.current_stream(dev))
+    _lib.check(rc, "srf_encoder_bias_relu_ragged")
+    return out
+
+
+def softmax_mask_ragged(z, enc, sources, frames, out=None):
+    """softmax_mask over examples of unequal length: z and enc are not read at columns >= frames[b], the result is exact 0 there."""
+    dev = _chk(z, enc, out)
+    Bt, SN, L = z.shape
+    N = enc.shape[1]
+    if SN != sources * N or enc.shape != (Bt, N, L):
+        raise _lib.SrfError("softmax_mask_ragged: z %s and enc %s do not fit %d sources" % (tuple(z.shape), tuple(enc.shape), sources))
+    if out is None:
+        out = torch.empty_like(z)
+    rc = _lib.load().srf_softmax_mask_ragged(_lib.ptr(z), _lib.ptr(enc), _lib.ptr(out), Bt, sources, N, L, _table(frames, "frames", Bt),
+                                             _lib.current_stream(dev))
+    _lib.check(rc, "srf_softmax_mask_ragged")
+    return out
+
+
+def bias_rescale_ragged(est, bias, lengths, stats=None, wav=None, mixture_consistency=False):
+    """bias_rescale IN PLACE over rows of unequal length: t < lengths[b] as bias_rescale, t >= lengths[b] exactly 0; wav is never
+    read at or past lengths[b].  Returns est."""
+    dev = _chk(est, bias, stats, wav)
+    Bt, S, T = est.shape
+    rc = _lib.load().srf_bias_rescale_ragged(_lib.ptr(est), _lib.ptr(bias), _lib.ptr(stats), _lib.ptr(wav),
+                                             int(bool(mixture_consistency)), Bt, S, T, _table(lengths, "lengths", Bt),
+                                             _lib.current_stream(dev))
+    _lib.check(rc, "srf_bias_rescale_ragged")
     return est
 
 

@@ -60,12 +60,15 @@ def ragged_route(model, length=None):
     """Where separate_list sends an utterance, decided from the model's configuration alone (no GPU): "ragged" = a candidate
     for the ragged batch (the Improved model with one input channel, K = 21, 256 bottleneck channels; the GroupComm model with
     one input channel, K = 21, 16 groups of 16 -> 32 channels, i.e. 256 / 512 channels; with `length`, also long enough for
-    the fused pyramid to take it as an example of its own), "single" = the per-example path (the causal model, other
-    configurations, too-short utterances).  A candidate batch still falls back as a whole when the plan of its (batch, T) is
-    refused (srf_plan_ragged_supported: small shapes)."""
+    the fused pyramid to take it as an example of its own; the original model after enable_ragged(), see
+    SuDORMRF._ragged_route), "single" = the per-example path (the causal model, other configurations, too-short utterances).
+    A candidate batch still falls back as a whole when the plan of its (batch, T) is refused (srf_plan_ragged_supported,
+    srf_original_ragged_supported: small shapes)."""
     kind = type(model).__name__
     if kind not in ("SuDORMRF", "GroupCommSudoRmRf") or not hasattr(model, "separate_ragged"):
         return "single"
+    if hasattr(model, "_ragged_route"):      # the original model after enable_ragged(): its own shapes and padding rule
+        return model._ragged_route(length)
     if getattr(model, "enc_kernel_size", 0) != 21 or getattr(model, "out_channels", 0) != 256:
         return "single"
     if kind == "GroupCommSudoRmRf" and (model.in_audio_channels != 1 or model._group_size() != 16 or model.in_channels != 512):

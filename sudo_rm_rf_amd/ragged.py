@@ -3,7 +3,11 @@
 The tensors keep their uniform layout -- [batch, channels, L] with L the row stride -- and every example brings its own length
 in a host-side list.  What lies at or past an example's end is never read and may hold anything; outputs that carry GlobLN
 statistics are exact zeros there, and the statistics count the example's own elements only, so every example is treated as
-its own batch-1 call would treat it.  The lists travel in the launch arguments: nothing is uploaded, nothing synchronises."""
+its own batch-1 call would treat it.  The lists travel in the launch arguments: nothing is uploaded, nothing synchronises.
+
+The ragged forms of the original model's own kernels (gln_apply_c, encoder_bias_relu, softmax_mask, bias_rescale) live next to
+their uniform twins in ``original``; that model pads a row to a multiple of lcm(K // 2, 2^depth) (``original.padded_frames``), not
+to the Improved model's (K // 2) * 2^depth (``padded_frames`` below)."""
 import ctypes as C
 
 import torch

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Ragged-batch forward against what it replaces, on one MI355X: cfg 2 weights (--model improved, the default) or cfg 3
-weights (--model groupcomm), batch 32, T = 32000, seeded lengths uniform on [T/2, T].  In ONE process, warmed up,
+"""Ragged-batch forward against what it replaces, on one MI355X: cfg 2 weights (--model improved, the default), cfg 3
+weights (--model groupcomm) or the original model in the README recipe's configuration, 16 blocks, opted in with
+enable_ragged() (--model original), batch 32, T = 32000, seeded lengths uniform on [T/2, T].  In ONE process, warmed up,
 alternating, timed with device events:
 
   (a) model.forward_ragged(x, lengths)                       one set of launches, single stream
@@ -9,9 +10,11 @@ alternating, timed with device events:
   (d) (c) again                                              the A/A spread of (c) is the margin for "(a) no slower than (c)"
   (c1) (c) on a single stream                                 what (a), which does not split the batch over two streams, is built like
 
-Writes profiles/ragged_forward.txt (--model groupcomm: profiles/ragged_forward_groupcomm.txt), or --out.  The Improved mode
-exits 1 unless (a) beats (b) and is no slower than (c) by more than the spread; the GroupComm mode only reports -- for that
-model the comparison that matters is (a) against (b), the per-utterance path separate_list took before.
+Writes profiles/ragged_forward.txt (--model groupcomm: profiles/ragged_forward_groupcomm.txt, --model original:
+profiles/ragged_forward_original.txt), or --out.  The Improved mode exits 1 unless (a) beats (b) and is no slower than (c) by
+more than the spread; the GroupComm and original modes only report -- for those models the comparison that matters is (a)
+against (b), the per-utterance path separate_list took before.  The original mode also lists the launches of one call of (a),
+of one batch-1 forward of (b) and of (c).
 
 --mode separate_list: pipeline.separate_list on a length-sorted list of 32 utterances, lengths on [T/2, T], both models
 (--model picks one), two arms in one process, alternating, device events, median over the rounds:
@@ -23,7 +26,7 @@ model the comparison that matters is (a) against (b), the per-utterance path sep
 with the library's launches (ops.kernel_trace) and the ATen operators that launch a kernel (a TorchDispatchMode count; views
 and allocations left out) of one call of each arm.  The arms are not symmetric: (s) is the whole of separate_list, its Python
 sort, bucketing and plan lookup included; (p) only the recipe on the batch already sorted and bucketed -- the ratio understates
-the gain.  Writes profiles/ragged_separate_list.txt, or --out."""
+the gain.  Writes profiles/ragged_separate_list.txt (--model original: profiles/ragged_separate_list_original.txt), or --out."""
 import argparse
 import json
 import os
@@ -37,8 +40,19 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def load_original(dev):
+    """the original model, README recipe with 16 blocks, seeded fixture weights, opted into the ragged forward"""
+    from tests import original_fixtures as of
+    from sudo_rm_rf.dnn.models.sudormrf import SuDORMRF
+    model = SuDORMRF(**of.RECIPE)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in of.make_state_dict(of.RECIPE, 408).items()})
+    return model.to(dev).eval().enable_ragged()
+
+
 def load_model(gc, dev):
-    """cfg 3 (GroupComm) or cfg 2 (Improved) with the golden weights, in eval mode on `dev`"""
+    """cfg 3 (GroupComm) or cfg 2 (Improved) with the golden weights, in eval mode on `dev`; gc == "original": load_original"""
+    if gc == "original":
+        return load_original(dev)
     from oracle import weights
     from oracle.schema import ModelConfig
     import sudo_rm_rf.dnn.models.groupcomm_sudormrf_v2 as groupcomm_sudormrf_v2
@@ -110,14 +124,14 @@ def separate_list_mode(args):
     rng = np.random.default_rng(2026)
     lens = sorted(int(v) for v in rng.integers(T // 2, T + 1, B))
     gain = np.geomspace(0.05, 20.0, B)[rng.permutation(B)]
-    for gc in ([False, True] if args.model is None else [args.model == "groupcomm"]):
+    for gc in ([False, True] if args.model is None else ["original" if args.model == "original" else args.model == "groupcomm"]):
         model = load_model(gc, dev)
         mixes = [torch.from_numpy((gain[i] * weights.make_mixture(1, n, 9400 + i)[0, 0] + 0.1).astype(np.float32)).to(dev)
                  for i, n in enumerate(lens)]
         (idx, Tb), = pipeline.ragged_batches(lens, B)
         assert idx == list(range(B)) and model._engine().ragged_plan_supported(B, Tb, dev)
         runs = [("s", lambda: pipeline.separate_list(model, mixes, max_batch=B)),
-                ("p", lambda: torch_op_recipe(model, mixes, gc, Tb))]
+                ("p", lambda: torch_op_recipe(model, mixes, gc is True, Tb))]
         times = {k: [] for k, _ in runs}
         with torch.no_grad():
             for _ in range(args.warmup):
@@ -139,7 +153,8 @@ def separate_list_mode(args):
         med = {k: float(np.median(v)) for k, v in times.items()}
         lines.append("")
         lines.append("%s weights, mixture consistency %s, padded length %d: %.1f %% of the padded samples are real"
-                     % ("cfg 3 (GroupComm)" if gc else "cfg 2 (Improved)", "on" if gc else "off", Tb, 100 * sum(lens) / float(B * Tb)))
+                     % ("original model (README recipe, 16 blocks)" if gc == "original" else "cfg 3 (GroupComm)" if gc else "cfg 2 (Improved)",
+                        "on" if gc is True else "off", Tb, 100 * sum(lens) / float(B * Tb)))
         lines.append("max |(s) - (p)| / max(1, std) over the utterances: %.3e" % worst)
         for k, name in (("s", "(s) separate_list"), ("p", "(p) torch-operator recipe")):
             lib, aten = counts[k]
@@ -162,17 +177,19 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--T", type=int, default=32000)
     ap.add_argument("--mode", choices=["forward", "separate_list"], default="forward")
-    ap.add_argument("--model", choices=["improved", "groupcomm"], default=None,
+    ap.add_argument("--model", choices=["improved", "groupcomm", "original"], default=None,
                     help="default: improved (--mode forward), both in turn (--mode separate_list)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.mode == "separate_list":
         if args.out is None:
-            args.out = os.path.join(ROOT, "profiles", "ragged_separate_list.txt")
+            args.out = os.path.join(ROOT, "profiles", "ragged_separate_list_original.txt" if args.model == "original"
+                                    else "ragged_separate_list.txt")
         return separate_list_mode(args)
-    gc = args.model == "groupcomm"
+    gc = "original" if args.model == "original" else args.model == "groupcomm"
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "ragged_forward_groupcomm.txt" if gc else "ragged_forward.txt")
+        args.out = os.path.join(ROOT, "profiles", "ragged_forward_original.txt" if gc == "original" else
+                                "ragged_forward_groupcomm.txt" if gc else "ragged_forward.txt")
     from oracle import weights
     dev = torch.device("cuda:0")
     model = load_model(gc, dev)
@@ -207,11 +224,12 @@ def main():
         return model(x)
 
     def run_c1():
+        was = eng.multi_stream          # (the original model's engine is single-stream to begin with)
         eng.multi_stream = False
         try:
             return model(x)
         finally:
-            eng.multi_stream = True
+            eng.multi_stream = was
 
     runs = [("a", run_a), ("b", run_b), ("c", run_c), ("d", run_c), ("c1", run_c1)]
     times = {k: [] for k, _ in runs}
@@ -223,6 +241,8 @@ def main():
         # sanity: the ragged rows are the batch-1 answers
         got, want = run_a(), run_b()
         worst = max(float((got[i, :, :n] - want[i][0]).abs().max()) for i, n in enumerate(lens))
+        launches = {k: count_launches(fn, dev)[0] for k, fn in (("a", run_a), ("b1", lambda: model(rows[0])), ("c", run_c))} \
+            if gc == "original" else None
         made_in_warmup = created[0]
         for _ in range(args.rounds):
             for k, fn in runs:
@@ -237,7 +257,7 @@ def main():
     spread = abs(med["c"] - med["d"])
     valid = sum(lens) / float(B * T)
     lines = ["ragged forward, %s weights, batch %d, T = %d, lengths uniform on [T/2, T] (seed 2026): %.1f %% of the padded samples are real"
-             % ("cfg 3 (GroupComm)" if gc else "cfg 2", B, T, 100 * valid),
+             % ("original model (README recipe, 16 blocks)" if gc == "original" else "cfg 3 (GroupComm)" if gc else "cfg 2", B, T, 100 * valid),
              "device: %s; %d alternating rounds after %d warm-up rounds; device-event times in ms: median [min .. max]"
              % (torch.cuda.get_device_name(dev), args.rounds, args.warmup),
              "max |forward_ragged row - its batch-1 forward| over the batch: %.3e" % worst,
@@ -250,12 +270,17 @@ def main():
     lines.append("(b) / (a) = %.2f   (a) / (c) = %.3f   (a) / (c1) = %.3f" % (med["b"] / med["a"], med["a"] / med["c"], med["a"] / med["c1"]))
     lines.append("(a) faster than (b): %s;  (a) no slower than (c) by more than the spread: %s"
                  % (med["a"] < med["b"], med["a"] <= med["c"] + spread))
+    if launches:
+        lines.append("library launches: (a) %d, one batch-1 forward of (b) %d (x %d = %d), (c) %d"
+                     % (sum(launches["a"].values()), sum(launches["b1"].values()), B, B * sum(launches["b1"].values()),
+                        sum(launches["c"].values())))
+        lines.append("launches of (a): %s" % dict(sorted(launches["a"].items())))
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         f.write(text)
-    if not gc and not (med["a"] < med["b"] and med["a"] <= med["c"] + spread):
+    if gc is False and not (med["a"] < med["b"] and med["a"] <= med["c"] + spread):
         sys.exit(1)
 
 
