@@ -882,7 +882,9 @@ int srf_frames_gather(const float* src, float* out, int Bt, int R, int T, int K,
  *   params; the caller zeroes them like optimizer.zero_grad()).  Reference: torch autograd over
  *   SuDORMRF.forward (improved_sudormrf.py:283-301), run_improved_sudormrf.py:167-172.
  * saved / scratch: 256-byte aligned device buffers of srf_train_saved_bytes / srf_train_scratch_bytes; `saved`
- *   must stay untouched between the two calls, `scratch` may be reused by anything in between.
+ *   must stay untouched between the two calls, `scratch` may be reused by anything in between.  srf_backward and
+ *   srf_backward_wav refuse a `saved` or `scratch` off the 256-byte grid (SRF_EINVAL, "256-byte aligned"), as
+ *   srf_forward_train does on the same two buffers; before the training entry points shared one entry check they did not look.
  * The backward follows what the srf_forward_train that filled `saved` did (recorded host-side per device and address),
  *   not the kernel mode / debug flags at its own call: when that forward left the level-0 depthwise output out (the fused
  *   backward head re-computes it) and the head cannot run under the current settings, it returns SRF_EINVAL naming both. */

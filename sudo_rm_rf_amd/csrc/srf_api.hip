@@ -700,10 +700,7 @@ static int srf_forward_impl(const srf_plan* p, const float* const* P, int num_pa
                             void* stream) {
   // The inference forward is what the engine runs as two sub-batches on two streams: its GEMMs take the half-CU blocks of
   // srf_pwconv_x3p.hip so that the other stream's kernels can co-reside (srf_pwconv.hip, srf_pw_256_launch).
-  struct Paired {
-    Paired() { srf_pw_prefer_paired(true); }
-    ~Paired() { srf_pw_prefer_paired(false); }
-  } paired_for_this_call;
+  const SrfPairedScope paired_for_this_call;
   const int rc = forward_check_args("srf_forward", p && P && wav && out && workspace, p, P, num_params, workspace, workspace_bytes);
   if (rc) return rc;
   // profiler: intervals run from mark to mark, so without this one the first kernel's interval would also hold the

@@ -19,28 +19,17 @@ CTrainLayout ctrain_layout(const srf_plan* p) {
   const srf_config& c = p->cfg;
   const size_t F = sizeof(float), L = p->L, Bt = p->Bt;
   const int D = c.upsampling_depth, U = c.num_blocks;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = srf_align_up(off + bytes, 256);
-    return o;
-  };
-  t.enc = take(F * Bt * c.enc_num_basis * L);
+  SrfCarve all, blk;      // (blk: one block's slices, offsets relative to the block's start)
+  t.enc = all.take(F * Bt * c.enc_num_basis * L);
   t.x_stride = srf_align_up(F * Bt * c.out_channels * L, 256);
-  t.x0 = take(t.x_stride * (U + 1));
-  size_t rel = 0;
-  auto rtake = [&](size_t bytes) {
-    const size_t o = rel;
-    rel = srf_align_up(rel + bytes, 256);
-    return o;
-  };
-  t.u = rtake(F * Bt * c.in_channels * L);
-  for (int k = 0; k < D; ++k) t.lv[k] = rtake(F * Bt * c.in_channels * (L >> k));
-  t.merged = rtake(F * Bt * c.in_channels * L);
-  t.blk_stride = rel;
-  t.blk0 = take(rel * U);
-  t.m = take(F * Bt * p->SA * c.enc_num_basis * L);
-  t.total = off;
+  t.x0 = all.take(t.x_stride * (U + 1));
+  t.u = blk.take(F * Bt * c.in_channels * L);
+  for (int k = 0; k < D; ++k) t.lv[k] = blk.take(F * Bt * c.in_channels * (L >> k));
+  t.merged = blk.take(F * Bt * c.in_channels * L);
+  t.blk_stride = blk.off;
+  t.blk0 = all.take(blk.off * U);
+  t.m = all.take(F * Bt * p->SA * c.enc_num_basis * L);
+  t.total = all.off;
   return t;
 }
 
@@ -60,27 +49,22 @@ CScratchLayout cscratch_layout(const srf_plan* p) {
   const int D = c.upsampling_depth, U = c.num_blocks, K = c.enc_kernel_size, N = c.enc_num_basis, B = c.out_channels,
             C = c.in_channels;
   const int SAN = p->SA * N;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = srf_align_up(off + (bytes ? bytes : 1), 256);
-    return o;
-  };
-  s.dec = take(F * srf_decoder_scratch_floats(p->Bt, SAN, p->SA, K, p->L));
-  s.gv = take(F * Bt * SAN * L);
-  s.genc = take(F * Bt * N * L);
-  s.gxa = take(F * Bt * B * L);
-  s.gxb = take(F * Bt * B * L);
-  s.gm = take(F * Bt * C * L);
-  s.gu = take(F * Bt * C * L);
-  for (int k = 0; k < D; ++k) s.gd[k] = take(F * Bt * C * (L >> k));
+  SrfCarve all{0, /*min_one=*/true};
+  s.dec = all.take(F * srf_decoder_scratch_floats(p->Bt, SAN, p->SA, K, p->L));
+  s.gv = all.take(F * Bt * SAN * L);
+  s.genc = all.take(F * Bt * N * L);
+  s.gxa = all.take(F * Bt * B * L);
+  s.gxb = all.take(F * Bt * B * L);
+  s.gm = all.take(F * Bt * C * L);
+  s.gu = all.take(F * Bt * C * L);
+  for (int k = 0; k < D; ++k) s.gd[k] = all.take(F * Bt * C * (L >> k));
   s.dec_rows = (p->SA * K + 63) / 64 * 64;
   const size_t enc_rows = (size_t)p->A * K;
-  s.frames = take(F * Bt * L * cmax((size_t)s.dec_rows, enc_rows));
-  s.wt = take(F * cmax(cmax((size_t)B * N, (size_t)B * C), (size_t)B * SAN));
+  s.frames = all.take(F * Bt * L * cmax((size_t)s.dec_rows, enc_rows));
+  s.wt = all.take(F * cmax(cmax((size_t)B * N, (size_t)B * C), (size_t)B * SAN));
   s.zero_floats = cmax(cmax(C, SAN), cmax(N, B));
-  s.zeros = take(F * s.zero_floats);
-  s.wdpad = take(F * (size_t)SAN * s.dec_rows);
+  s.zeros = all.take(F * s.zero_floats);
+  s.wdpad = all.take(F * (size_t)SAN * s.dec_rows);
   size_t wg = 0;
   auto wgmax = [&](int cout, int cin) { wg = cmax(wg, srf_pw_wgrad_scratch_bytes(p->Bt, cout, cin, p->L)); };
   wgmax(B, N);
@@ -89,23 +73,23 @@ CScratchLayout cscratch_layout(const srf_plan* p) {
   wgmax(N, (int)enc_rows);
   wgmax(C, B);
   wgmax(B, C);
-  s.wg = take(wg);
-  s.pyr = take(cmax(cmax(srf_causal_pyramid_bwd_scratch_bytes(p->Bt, C, p->L, D), srf_causal_dwconv_bwd_scratch_bytes(p->Bt, C, p->L)),
+  s.wg = all.take(wg);
+  s.pyr = all.take(cmax(cmax(srf_causal_pyramid_bwd_scratch_bytes(p->Bt, C, p->L, D), srf_causal_dwconv_bwd_scratch_bytes(p->Bt, C, p->L)),
                     F * srf_causal_prelu_bwd_scratch_floats()));
-  s.fold_res = take(F * causal_fold_res_floats(B, C) * U);
-  s.fold_proj = take(F * (size_t)C * B * U);
-  s.encw = take(F * (size_t)N * enc_rows);
+  s.fold_res = all.take(F * causal_fold_res_floats(B, C) * U);
+  s.fold_proj = all.take(F * (size_t)C * B * U);
+  s.encw = all.take(F * (size_t)N * enc_rows);
   {
     size_t pk = srf_align_up(srf_packed3_pw_weight_bytes(B, N), 256) + srf_align_up(srf_packed3_pw_weight_bytes(SAN, B), 256);
     pk += (size_t)U * srf_align_up(srf_packed3_pw_weight_bytes(C, B), 256);
-    s.pk3 = take(pk);
+    s.pk3 = all.take(pk);
   }
   {
     size_t pk = srf_align_up(srf_packed_pw_weight_bytes(B, SAN), 256) + srf_align_up(srf_packed_pw_weight_bytes(N, B), 256);
     pk += (size_t)U * (srf_align_up(srf_packed_pw_weight_bytes(C, B), 256) + srf_align_up(srf_packed_pw_weight_bytes(B, C), 256));
-    s.pkT = take(pk);
+    s.pkT = all.take(pk);
   }
-  s.total = off;
+  s.total = all.off;
   return s;
 }
 
@@ -122,21 +106,6 @@ int ctrain_check(const srf_plan* p, const char* who) {
   }
   return SRF_OK;
 }
-
-// weight images queued for ONE pack launch, carved from `at` in steps of 256 bytes
-struct PackQueue {
-  char* at;
-  std::vector<const float*> w;
-  std::vector<void*> d;
-  std::vector<int> cout, cin;
-  const void* add(const float* weight, size_t bytes, int co, int ci) {
-    if (!bytes) return nullptr;
-    void* dst = at;
-    at += srf_align_up(bytes, 256);
-    w.push_back(weight), d.push_back(dst), cout.push_back(co), cin.push_back(ci);
-    return dst;
-  }
-};
 
 int cforward_train_impl(const srf_plan* p, const float* const* P, const float* wav, float* out, void* saved, void* scratch,
                         bool split_tail, void* stream) {
@@ -157,7 +126,7 @@ int cforward_train_impl(const srf_plan* p, const float* const* P, const float* w
   if (rc) return rc;
   // three-part (or two-fp16-part) images of the 1x1 weights the 256 x 128 GEMM takes, as forward_train_impl packs them
   const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
-  PackQueue pk{sc + s.pk3};
+  SrfPackQueue pk{sc + s.pk3};
   auto pack3 = [&](const float* wt, int cout, int cin) {
     return pk.add(wt, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin);
   };
@@ -165,10 +134,8 @@ int cforward_train_impl(const srf_plan* p, const float* const* P, const float* w
   const void* pk_mask = pack3(tl.mask_w, SAN, B);
   std::vector<const void*> pk_proj(U, nullptr);
   for (int i = 0; i < U; ++i) pk_proj[i] = pack3(w.wproj[i], Cc, B);
-  if (!pk.w.empty()) {
-    rc = srf_pack3_pw_weights(pk.w.data(), pk.d.data(), pk.cout.data(), pk.cin.data(), (int)pk.w.size(), stream);
-    if (rc) return rc;
-  }
+  rc = pk.pack3(stream);
+  if (rc) return rc;
   float* enc = (float*)(sv + t.enc);
   rc = srf_causal_encoder(wav, f.enc_w, enc, Bt, p->A, p->T, N, K, L, stream);
   if (rc) return rc;
@@ -205,10 +172,8 @@ int cforward_train_impl(const srf_plan* p, const float* const* P, const float* w
   rc = srf_prelu_apply(m, tl.out_prelu, v, (long)Bt * SAN * L, stream);
   if (rc) return rc;
   // the decoder's frame GEMM is the last linear map: on the split kernel when the exact class was this call's own choice
-  const int tail_prev = split_tail ? srf_kernel_mode_override(0) : -1;
-  rc = srf_decoder(v, tl.dec_w, out, Bt, SAN, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
-  if (split_tail) srf_kernel_mode_override(tail_prev);
-  return rc;
+  const SrfKernelModeScope split_class(split_tail, 0);
+  return srf_decoder(v, tl.dec_w, out, Bt, SAN, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
 }
 
 }  // namespace
@@ -223,36 +188,27 @@ extern "C" size_t srf_causal_train_scratch_bytes(const srf_plan* p) {
 extern "C" int srf_causal_forward_train(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                                         void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
   if (!causal_plan(p, "srf_causal_forward_train")) return SRF_EINVAL;
-  SRF_CHECK_ARG(P && wav && out && saved && scratch, "srf_causal_forward_train: null pointer");
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_causal_forward_train: expected %d parameter tensors, got %d", p->n_params, num_params);
-  int rc = ctrain_check(p, "srf_causal_forward_train");
+  int rc = srf_train_entry_check("srf_causal_forward_train", p, P, nullptr, num_params, 0, {wav, out},
+                                 {saved, saved_bytes, ctrain_layout(p).total, scratch, scratch_bytes, cscratch_layout(p).total});
+  if (!rc) rc = ctrain_check(p, "srf_causal_forward_train");
   if (rc) return rc;
-  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "srf_causal_forward_train: parameter %d is null", i);
-  SRF_CHECK_ARG(saved_bytes >= ctrain_layout(p).total && scratch_bytes >= cscratch_layout(p).total,
-                "srf_causal_forward_train: saved / scratch buffer too small");
-  SRF_CHECK_ARG(((((size_t)saved) | ((size_t)scratch)) & 255) == 0, "srf_causal_forward_train: buffers must be 256-byte aligned");
   // the exact-fp32 class for the 1x1 convolutions, under the flags of srf_forward_train (srf_train.hip has the reasons)
   const bool exact = srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_TRAIN_FWD_SPLIT_BF16);
-  const int prev = exact ? srf_kernel_mode_override(2) : -1;
+  const SrfKernelModeScope exact_class(exact, 2);
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
-  rc = cforward_train_impl(p, P, wav, out, saved, scratch, exact, stream);
-  if (exact) srf_kernel_mode_override(prev);
-  return rc;
+  return cforward_train_impl(p, P, wav, out, saved, scratch, exact, stream);
 }
 
 extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
                                    const float* grad_out, const void* saved, size_t saved_bytes, void* scratch,
                                    size_t scratch_bytes, void* stream) {
   if (!causal_plan(p, "srf_causal_backward")) return SRF_EINVAL;
-  SRF_CHECK_ARG(P && G && wav && grad_out && saved && scratch, "srf_causal_backward: null pointer");
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_causal_backward: expected %d parameter tensors, got %d", p->n_params, num_params);
-  int rc = ctrain_check(p, "srf_causal_backward");
-  if (rc) return rc;
-  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] && G[i], "srf_causal_backward: parameter / gradient %d is null", i);
   const CTrainLayout t = ctrain_layout(p);
   const CScratchLayout s = cscratch_layout(p);
-  SRF_CHECK_ARG(saved_bytes >= t.total && scratch_bytes >= s.total, "srf_causal_backward: saved / scratch buffer too small");
-  SRF_CHECK_ARG(((((size_t)saved) | ((size_t)scratch)) & 255) == 0, "srf_causal_backward: buffers must be 256-byte aligned");
+  int rc = srf_train_entry_check("srf_causal_backward", p, P, G, num_params, 0, {G, wav, grad_out},
+                                 {saved, saved_bytes, t.total, scratch, scratch_bytes, s.total});
+  if (!rc) rc = ctrain_check(p, "srf_causal_backward");
+  if (rc) return rc;
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, h = K / 2;
   const int Bt = p->Bt, L = p->L, B = p->nB, C = p->nC, SA = p->SA, SAN = p->SA * N;
@@ -274,15 +230,12 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   if (srf_profiling()) srf_prof_mark("(gap)", st);
   SRF_CHECK_HIP(hipMemsetAsync(zeros, 0, sizeof(float) * s.zero_floats, st));
   // the weight-gradient GEMMs of this call fold their partial sums in a fixed order: two backwards of one step give equal bits
-  struct Ordered {
-    Ordered() { srf_pw_wgrad_ordered(true); }
-    ~Ordered() { srf_pw_wgrad_ordered(false); }
-  } ordered_for_this_call;
+  const SrfWgradOrderedScope ordered_for_this_call;
   SrfCausalFolded w;
   rc = srf_causal_fold(p, P, fp(s.fold_res), fp(s.fold_proj), &w, st);
   if (rc) return rc;
   // transposed weights of the data-gradient GEMMs, pre-split for the 256 x 128 kernel where it takes the shape
-  PackQueue pk{sc + s.pkT};
+  SrfPackQueue pk{sc + s.pkT};
   auto packT = [&](const float* wf, int cout_d, int cin_d) {   // wf: forward weight [cin_d][cout_d]
     return pk.add(wf, srf_kernel_mode() == 0 ? srf_packed_pw_weight_bytes(cout_d, cin_d) : 0, cout_d, cin_d);
   };
@@ -293,10 +246,8 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
     pkT_res[i] = packT(w.wres[i], C, B);
     pkT_proj[i] = packT(w.wproj[i], B, C);
   }
-  if (!pk.w.empty()) {
-    rc = srf_pack_pw_weights_transposed(pk.w.data(), pk.d.data(), pk.cout.data(), pk.cin.data(), (int)pk.w.size(), st);
-    if (rc) return rc;
-  }
+  rc = pk.packT(st);
+  if (rc) return rc;
   // g_x = W^T g (+ residual): cin_d -> cout_d, w the forward weight [cin_d][cout_d]
   // Where no packed image serves the launch the GEMM would fall to the kernels that split fp32 into two bf16 parts on the fly (16
   // mantissa bits per operand); those launches, and the decoder's frame GEMM below, run in the exact-fp32 class instead (kernel
@@ -307,18 +258,9 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   // 2^28 multiply-adds: below that a GEMM's time is its launch (microseconds in either class), above it the exact-fp32 MFMA kernel
   // costs 2.5 x the split one (the 16-block bench step: 18 such launches, 39.9 -> 41.0 ms when they were moved too).
   auto small_gemm = [&](int cin_d, int cout_d) { return (long)Bt * L * cin_d * cout_d <= (1L << 28); };
-  struct ExactClass {
-    int prev;
-    bool on;
-    explicit ExactClass(bool want) : prev(-1), on(want && srf_kernel_mode() == 0) {
-      if (on) prev = srf_kernel_mode_override(2);
-    }
-    ~ExactClass() {
-      if (on) srf_kernel_mode_override(prev);
-    }
-  };
   auto data_grad = [&](const float* g, const float* w, const void* pk, float* y, int cin_d, int cout_d, const float* residual) -> int {
-    const ExactClass exact(small_gemm(cin_d, cout_d) && !srf_pw_packed_only(pk, g, Bt, cin_d, cout_d, L));
+    const bool on_the_fly = small_gemm(cin_d, cout_d) && !srf_pw_packed_only(pk, g, Bt, cin_d, cout_d, L);
+    const SrfKernelModeScope exact(on_the_fly && srf_kernel_mode() == 0, 2);
     return srf_pw_data_grad(g, w, pk, wt, zeros, y, Bt, cin_d, cout_d, L, residual, st);
   };
   // ---- decoder: out = overlap_add(W_d^T PReLU_c(m))
@@ -335,7 +277,7 @@ extern "C" int srf_causal_backward(const srf_plan* p, const float* const* P, flo
   SRF_CHECK_HIP(hipMemcpy2DAsync(wdpad, sizeof(float) * s.dec_rows, tl.dec_w, sizeof(float) * SA * K, sizeof(float) * SA * K, SAN,
                                  hipMemcpyDeviceToDevice, st));
   {
-    const ExactClass exact(small_gemm(s.dec_rows, SAN));
+    const SrfKernelModeScope exact(small_gemm(s.dec_rows, SAN) && srf_kernel_mode() == 0, 2);
     rc = srf_pw_conv(frames, wdpad, zeros, gv, Bt, s.dec_rows, SAN, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
   }
   if (rc) return rc;

@@ -17,6 +17,18 @@
 void srf_set_error(const char* fmt, ...);
 int srf_kernel_mode();  // 0 = fast paths, 1 = generic kernels only, 2 = fast paths with exact-fp32 MFMA GEMMs
 int srf_kernel_mode_override(int mode);   // per-thread override (-1 = none); returns the previous override
+// `on`: this thread's launches run under kernel mode `mode` until the scope ends, on every path out of it; then the previous
+// override is back.  Not on: nothing happens.
+struct SrfKernelModeScope {
+  const bool on;
+  const int prev;
+  SrfKernelModeScope(bool on, int mode) : on(on), prev(on ? srf_kernel_mode_override(mode) : -1) {}
+  ~SrfKernelModeScope() {
+    if (on) srf_kernel_mode_override(prev);
+  }
+  SrfKernelModeScope(const SrfKernelModeScope&) = delete;
+  SrfKernelModeScope& operator=(const SrfKernelModeScope&) = delete;
+};
 int srf_debug_flags();  // kernel-variant switches for A/B runs and tests (enum srf_debug_flag: include/sudormrf_hip.h, SRF_DIAGNOSTICS)
 static inline bool srf_dbg(int mask) { return (srf_debug_flags() & mask) != 0; }   // any of the SRF_DBG_* bits of `mask` set
 bool srf_profiling();
@@ -81,6 +93,17 @@ static inline bool srf_launch_lds(int max_lds, dim3 grid, dim3 block, size_t lds
 
 static inline bool srf_aligned16(const void* p) { return (((size_t)p) & 15) == 0; }
 static inline size_t srf_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Carves a buffer into 256-byte-aligned slices: take(bytes) returns the slice's offset, `off` is the total so far.
+// min_one: an empty request still takes one byte (no two slices share an offset).
+struct SrfCarve {
+  size_t off = 0;
+  bool min_one = false;
+  size_t take(size_t bytes) {
+    const size_t o = off;
+    off = srf_align_up(off + (min_one && !bytes ? 1 : bytes), 256);
+    return o;
+  }
+};
 
 // Refusal of a misplaced operand, BEFORE anything is launched, naming it: every (name, pointer) pair whose pointer is not
 // NULL must be 16-byte aligned.  SRF_CHECK_ALIGNED16("srf_x", {"g", g}, {"x", x});

@@ -109,6 +109,10 @@ int srf_pyramid_impl(const float* y1, float* merged, const srf_norm* in_norm, co
 
 // ---- srf_pwconv.hip
 void srf_pw_prefer_paired(bool on);   // the paired-block form of the 256 x 128 GEMM for this thread's launches
+struct SrfPairedScope {               // ... for the launches of one call, on every path out of it
+  SrfPairedScope() { srf_pw_prefer_paired(true); }
+  ~SrfPairedScope() { srf_pw_prefer_paired(false); }
+};
 bool srf_pw_conv_preadd_supported(int Cin, int Cout, int L, const void* const* ptrs, int nptrs);
 int srf_pw_conv_preadd(const float* x, const float* q, const srf_norm* qnorm, float* u, const float* w, const float* bias,
                        float* y, int Bt, int Cin, int Cout, int L, double* out_sums, hipStream_t st);
@@ -126,6 +130,11 @@ bool srf_pw_packed_only(const void* w_packed, const float* x, int Bt, int Cin, i
 // srf_pack3_pw_weights / srf_pw_conv_packed3 of THIS thread take the three-bf16-part form (24 mantissa bits, what debug flag
 // 16384 selects process-wide) while on; returns the previous setting
 bool srf_train_three_parts_override(bool on);
+struct SrfThreePartsScope {           // ... on until the scope ends, then the previous setting is back
+  const bool prev;
+  SrfThreePartsScope() : prev(srf_train_three_parts_override(true)) {}
+  ~SrfThreePartsScope() { srf_train_three_parts_override(prev); }
+};
 // A backward's data-gradient GEMM gx = W^T g (+ skip), Cin -> Cout, W the FORWARD weight [Cin][Cout]: from the packed image
 // of W^T where that serves the whole launch (srf_pw_packed_only), else from its fp32 transpose, made in `wt` first
 int srf_pw_data_grad(const float* g, const float* w, const void* wT_packed, float* wt, const float* zero_bias, float* gx, int Bt,
@@ -151,6 +160,10 @@ bool srf_pw_small_ragged_supported(int Cin, int Cout, int L);   // the shapes it
 
 // ---- srf_pwconv_wgrad.hip: this thread's weight-gradient GEMMs fold their partial sums in a fixed order (no atomic split)
 void srf_pw_wgrad_ordered(bool on);
+struct SrfWgradOrderedScope {         // ... for the weight-gradient GEMMs of one call, on every path out of it
+  SrfWgradOrderedScope() { srf_pw_wgrad_ordered(true); }
+  ~SrfWgradOrderedScope() { srf_pw_wgrad_ordered(false); }
+};
 
 // ---- srf_backward.hip
 int srf_accumulate_launch(float* dst, const float* src, long n, hipStream_t st);

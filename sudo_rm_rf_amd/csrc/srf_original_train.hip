@@ -491,32 +491,21 @@ OTrainLayout otrain_layout(const srf_plan* p) {
   const srf_config& c = p->cfg;
   const size_t F = sizeof(float), L = p->L, Bt = p->Bt;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, B = p->nB, C = p->nC, S = c.num_sources;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = srf_align_up(off + bytes, 256);
-    return o;
-  };
-  t.stats = take(p->stats_bytes);
-  t.enc = take(F * Bt * N * L);
+  SrfCarve all, blk;      // (blk: one block's slices, offsets relative to the block's start)
+  t.stats = all.take(p->stats_bytes);
+  t.enc = all.take(F * Bt * N * L);
   t.x_stride = srf_align_up(F * Bt * B * L, 256);
-  t.x0 = take(t.x_stride * (U + 1));
-  size_t rel = 0;
-  auto rtake = [&](size_t bytes) {
-    const size_t o = rel;
-    rel = srf_align_up(rel + bytes, 256);
-    return o;
-  };
-  t.y1 = rtake(F * Bt * C * L);
-  for (int k = 0; k < D; ++k) t.lv[k] = rtake(F * Bt * C * (L >> k));
-  t.m = rtake(F * Bt * C * L);
-  t.g = rtake(F * Bt * B * L);
-  t.gx = rtake(F * Bt * B * L);
-  t.blk_stride = rel;
-  t.blk0 = take(rel * U);
-  t.xr = orig_has_reshape(p) ? take(F * Bt * N * L) : 0;
-  t.z = take(F * Bt * S * N * L);
-  t.total = off;
+  t.x0 = all.take(t.x_stride * (U + 1));
+  t.y1 = blk.take(F * Bt * C * L);
+  for (int k = 0; k < D; ++k) t.lv[k] = blk.take(F * Bt * C * (L >> k));
+  t.m = blk.take(F * Bt * C * L);
+  t.g = blk.take(F * Bt * B * L);
+  t.gx = blk.take(F * Bt * B * L);
+  t.blk_stride = blk.off;
+  t.blk0 = all.take(blk.off * U);
+  t.xr = orig_has_reshape(p) ? all.take(F * Bt * N * L) : 0;
+  t.z = all.take(F * Bt * S * N * L);
+  t.total = all.off;
   return t;
 }
 
@@ -533,35 +522,30 @@ OScratchLayout oscratch_layout(const srf_plan* p) {
   const size_t F = sizeof(float), L = p->L, Bt = p->Bt;
   const int D = c.upsampling_depth, U = c.num_blocks, K = c.enc_kernel_size, N = c.enc_num_basis, B = p->nB, C = p->nC,
             S = c.num_sources, SN = S * N;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = srf_align_up(off + (bytes ? bytes : 1), 256);
-    return o;
-  };
+  SrfCarve all{0, /*min_one=*/true};
   s.dec_rows = (S * K + 63) / 64 * 64;
   s.L4 = (p->L + 3) / 4 * 4;      // the weight-gradient GEMM takes L % 4 == 0 only: else its operands are copied to this pitch
-  s.dec = take(F * srf_decoder_scratch_floats(p->Bt, SN, S, K, p->L));
-  s.vbuf = take(F * Bt * SN * L);
-  s.gv = take(F * Bt * SN * L);
-  s.genc = take(F * Bt * N * L);
-  s.gxm = take(F * Bt * N * L);
-  for (int i = 0; i < 4; ++i) s.gb[i] = take(F * Bt * B * L);
-  s.act = take(F * Bt * C * L);
-  s.gc1 = take(F * Bt * C * L);
-  s.gc2 = take(F * Bt * C * L);
-  s.gd = take(F * Bt * C * L);
-  for (int k = 0; k + 1 < D; ++k) s.gu[k] = take(F * Bt * C * (L >> k));
-  for (int k = 1; k < D; ++k) s.gn[k] = take(F * Bt * C * (L >> k));
-  s.frames = take(F * Bt * L * omax((size_t)s.dec_rows, (size_t)K));
-  s.wt = take(F * omax(omax((size_t)B * N, (size_t)B * C), (size_t)SN * N));
+  s.dec = all.take(F * srf_decoder_scratch_floats(p->Bt, SN, S, K, p->L));
+  s.vbuf = all.take(F * Bt * SN * L);
+  s.gv = all.take(F * Bt * SN * L);
+  s.genc = all.take(F * Bt * N * L);
+  s.gxm = all.take(F * Bt * N * L);
+  for (int i = 0; i < 4; ++i) s.gb[i] = all.take(F * Bt * B * L);
+  s.act = all.take(F * Bt * C * L);
+  s.gc1 = all.take(F * Bt * C * L);
+  s.gc2 = all.take(F * Bt * C * L);
+  s.gd = all.take(F * Bt * C * L);
+  for (int k = 0; k + 1 < D; ++k) s.gu[k] = all.take(F * Bt * C * (L >> k));
+  for (int k = 1; k < D; ++k) s.gn[k] = all.take(F * Bt * C * (L >> k));
+  s.frames = all.take(F * Bt * L * omax((size_t)s.dec_rows, (size_t)K));
+  s.wt = all.take(F * omax(omax((size_t)B * N, (size_t)B * C), (size_t)SN * N));
   s.zero_floats = omax(omax(C, SN), omax(N, B));
-  s.zeros = take(F * s.zero_floats);
-  s.tz = take(F * orig_tz_floats(S, N));
-  s.wdec = take(F * (size_t)SN * S * K);
-  s.wdpad = take(F * (size_t)SN * s.dec_rows);
-  s.dtz = take(F * orig_tz_floats(S, N));
-  s.dwexp = take(F * (size_t)SN * S * K);
+  s.zeros = all.take(F * s.zero_floats);
+  s.tz = all.take(F * orig_tz_floats(S, N));
+  s.wdec = all.take(F * (size_t)SN * S * K);
+  s.wdpad = all.take(F * (size_t)SN * s.dec_rows);
+  s.dtz = all.take(F * orig_tz_floats(S, N));
+  s.dwexp = all.take(F * (size_t)SN * S * K);
   size_t wg = 0;
   auto wgmax = [&](int cout, int cin) { wg = omax(wg, srf_pw_wgrad_scratch_bytes(p->Bt, cout, cin, s.L4)); };
   wgmax(SN, s.dec_rows);
@@ -571,29 +555,29 @@ OScratchLayout oscratch_layout(const srf_plan* p) {
   wgmax(C, B);
   wgmax(B, N);
   wgmax(N, K);
-  s.wg = take(wg);
-  s.gln = take(srf_gln_bwd_scratch_bytes(p->Bt, C > N ? C : N));
-  s.glnc = take(srf_gln_c_bwd_scratch_bytes(p->Bt, C > B ? C : B, p->L));
-  s.dwb = take(srf_dwconv5_bwd_scratch_bytes(p->Bt, C));
-  s.bias = take(F * srf_decoder_bias_grad_scratch_floats(S));
+  s.wg = all.take(wg);
+  s.gln = all.take(srf_gln_bwd_scratch_bytes(p->Bt, C > N ? C : N));
+  s.glnc = all.take(srf_gln_c_bwd_scratch_bytes(p->Bt, C > B ? C : B, p->L));
+  s.dwb = all.take(srf_dwconv5_bwd_scratch_bytes(p->Bt, C));
+  s.bias = all.take(F * srf_decoder_bias_grad_scratch_floats(S));
   if (s.L4 != p->L) {
     const size_t rows = omax(omax(omax(C, SN), omax(N, B)), omax((size_t)s.dec_rows, (size_t)K));
-    s.padg = take(F * Bt * rows * s.L4);
-    s.padx = take(F * Bt * rows * s.L4);
+    s.padg = all.take(F * Bt * rows * s.L4);
+    s.padx = all.take(F * Bt * rows * s.L4);
   }
   {
     size_t pk = srf_align_up(srf_packed3_pw_weight_bytes(B, N), 256) + srf_align_up(srf_packed3_pw_weight_bytes(SN, N), 256) +
                 srf_align_up(srf_packed3_pw_weight_bytes(N, B), 256);
     pk += (size_t)U * (srf_align_up(srf_packed3_pw_weight_bytes(C, B), 256) + srf_align_up(srf_packed3_pw_weight_bytes(B, C), 256));
-    s.pk3 = take(pk);
+    s.pk3 = all.take(pk);
   }
   {
     size_t pk = srf_align_up(srf_packed_pw_weight_bytes(N, SN), 256) + srf_align_up(srf_packed_pw_weight_bytes(N, B), 256) +
                 srf_align_up(srf_packed_pw_weight_bytes(B, N), 256);
     pk += (size_t)U * (srf_align_up(srf_packed_pw_weight_bytes(B, C), 256) + srf_align_up(srf_packed_pw_weight_bytes(C, B), 256));
-    s.pkT = take(pk);
+    s.pkT = all.take(pk);
   }
-  s.total = off;
+  s.total = all.off;
   return s;
 }
 
@@ -604,21 +588,6 @@ bool original_plan(const srf_plan* p, const char* who) {
                                  : "null plan");
   return false;
 }
-
-// weight images queued for ONE pack launch, carved from `at` in steps of 256 bytes
-struct OPackQueue {
-  char* at;
-  std::vector<const float*> w;
-  std::vector<void*> d;
-  std::vector<int> cout, cin;
-  const void* add(const float* weight, size_t bytes, int co, int ci) {
-    if (!bytes) return nullptr;
-    void* dst = at;
-    at += srf_align_up(bytes, 256);
-    w.push_back(weight), d.push_back(dst), cout.push_back(co), cin.push_back(ci);
-    return dst;
-  }
-};
 
 int oforward_train_impl(const srf_plan* p, const float* const* P, const float* wav, float* out, void* saved, void* scratch,
                         bool split_tail, void* stream) {
@@ -646,7 +615,7 @@ int oforward_train_impl(const srf_plan* p, const float* const* P, const float* w
   if (rc) return rc;
   // the exact-class images of the 1x1 weights the 256 x 128 GEMM takes, as srf_forward_train packs them
   const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
-  OPackQueue pk{sc + s.pk3};
+  SrfPackQueue pk{sc + s.pk3};
   auto pack3 = [&](const float* w, int cout, int cin) { return pk.add(w, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin); };
   const void* pk_l1 = pack3(f.l1_w, B, N);
   const void* pk_mask = pack3(tz, SN, N);
@@ -657,10 +626,8 @@ int oforward_train_impl(const srf_plan* p, const float* const* P, const float* w
     pk_proj[i] = pack3(b.proj_w, C, B);
     pk_exp[i] = pack3(b.exp_w, B, C);
   }
-  if (!pk.w.empty()) {
-    rc = srf_pack3_pw_weights(pk.w.data(), pk.d.data(), pk.cout.data(), pk.cin.data(), (int)pk.w.size(), stream);
-    if (rc) return rc;
-  }
+  rc = pk.pack3(stream);
+  if (rc) return rc;
   auto conv = [&](const float* x, const float* w, const void* w3, const float* bias, float* y, int Cin, int Cout, const srf_norm* in_norm,
                   double* out_sums) {
     return srf_pw_conv_packed3(x, w, w3, bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, stream);
@@ -725,9 +692,10 @@ int oforward_train_impl(const srf_plan* p, const float* const* P, const float* w
   rc = srf_softmax_mask(z, enc, masked, Bt, S, N, L, stream);
   if (rc) return rc;
   // the decoder's frame GEMM is the last linear map: on the split kernel when the exact class was this call's own choice
-  const int tail_prev = split_tail ? srf_kernel_mode_override(0) : -1;
-  rc = srf_decoder_impl(masked, wdec, out, Bt, SN, S, K, L, p->T, fp(s.dec), nullptr, nullptr, 0, stream);
-  if (split_tail) srf_kernel_mode_override(tail_prev);
+  {
+    const SrfKernelModeScope split_class(split_tail, 0);
+    rc = srf_decoder_impl(masked, wdec, out, Bt, SN, S, K, L, p->T, fp(s.dec), nullptr, nullptr, 0, stream);
+  }
   if (rc) return rc;
   return srf_bias_rescale(out, tl.dec_b, nullptr, nullptr, 0, Bt, S, p->T, stream);
 }
@@ -744,14 +712,9 @@ extern "C" size_t srf_original_train_scratch_bytes(const srf_plan* p) {
 extern "C" int srf_original_forward_train(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                                           void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
   if (!original_plan(p, "srf_original_forward_train")) return SRF_EINVAL;
-  SRF_CHECK_ARG(P && wav && out && saved && scratch, "srf_original_forward_train: null pointer");
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_original_forward_train: expected %d parameter tensors, got %d", p->n_params, num_params);
-  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "srf_original_forward_train: parameter %d is null", i);
-  SRF_CHECK_ARG(saved_bytes >= otrain_layout(p).total, "srf_original_forward_train: saved buffer too small (%zu bytes, needs %zu)",
-                saved_bytes, otrain_layout(p).total);
-  SRF_CHECK_ARG(scratch_bytes >= oscratch_layout(p).total, "srf_original_forward_train: scratch buffer too small (%zu bytes, needs %zu)",
-                scratch_bytes, oscratch_layout(p).total);
-  SRF_CHECK_ARG(((((size_t)saved) | ((size_t)scratch)) & 255) == 0, "srf_original_forward_train: saved and scratch must be 256-byte aligned");
+  int rc = srf_train_entry_check("srf_original_forward_train", p, P, nullptr, num_params, 0, {wav, out},
+                                 {saved, saved_bytes, otrain_layout(p).total, scratch, scratch_bytes, oscratch_layout(p).total});
+  if (rc) return rc;
   // the exact-fp32 class for the 1x1 convolutions, under the flags of srf_forward_train (srf_train.hip has the reasons) -- and of
   // its two forms the THREE-bf16-part one (24 mantissa bits), not the two-fp16-part default (22): this model puts three per-channel
   // PReLUs behind GroupNorms into every block, and every pre-activation that the forward's rounding moves across 0 flips a slope in
@@ -759,31 +722,24 @@ extern "C" int srf_original_forward_train(const srf_plan* p, const float* const*
   // autograd: two parts leave l1.weight 5.8e-3 of its largest entry off (torch's own fp32 autograd: 4.5e-4) and five tensors over
   // the 2e-3 bar; three parts 3.0e-4 and none.
   const bool exact = srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_TRAIN_FWD_SPLIT_BF16);
-  const int prev = exact ? srf_kernel_mode_override(2) : -1;
-  const bool prev3 = srf_train_three_parts_override(true);
+  const SrfKernelModeScope exact_class(exact, 2);
+  const SrfThreePartsScope three_parts;
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
   // (the decoder's frame GEMM stays in the exact class too, unlike srf_forward_train's: its rounding is the output's, and the
   // runner's loss and its gradient go with 1 / <estimate, target>)
-  const int rc = oforward_train_impl(p, P, wav, out, saved, scratch, /*split_tail=*/false, stream);
-  srf_train_three_parts_override(prev3);
-  if (exact) srf_kernel_mode_override(prev);
-  return rc;
+  return oforward_train_impl(p, P, wav, out, saved, scratch, /*split_tail=*/false, stream);
 }
 
 extern "C" int srf_original_backward(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
                                      const float* grad_out, const void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
                                      void* stream) {
   if (!original_plan(p, "srf_original_backward")) return SRF_EINVAL;
-  SRF_CHECK_ARG(P && G && wav && grad_out && saved && scratch, "srf_original_backward: null pointer");
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_original_backward: expected %d parameter tensors, got %d", p->n_params, num_params);
-  // (ln_mask_in.{weight, bias}, the last two, receive no gradient: their entries may be NULL)
-  for (int i = 0; i < num_params; ++i)
-    SRF_CHECK_ARG(P[i] && (G[i] || i >= num_params - 2), "srf_original_backward: parameter / gradient %d is null", i);
   const OTrainLayout t = otrain_layout(p);
   const OScratchLayout s = oscratch_layout(p);
-  SRF_CHECK_ARG(saved_bytes >= t.total, "srf_original_backward: saved buffer too small (%zu bytes, needs %zu)", saved_bytes, t.total);
-  SRF_CHECK_ARG(scratch_bytes >= s.total, "srf_original_backward: scratch buffer too small (%zu bytes, needs %zu)", scratch_bytes, s.total);
-  SRF_CHECK_ARG(((((size_t)saved) | ((size_t)scratch)) & 255) == 0, "srf_original_backward: saved and scratch must be 256-byte aligned");
+  // (ln_mask_in.{weight, bias}, the last two, receive no gradient: their entries may be NULL)
+  int rc = srf_train_entry_check("srf_original_backward", p, P, G, num_params, 2, {G, wav, grad_out},
+                                 {saved, saved_bytes, t.total, scratch, scratch_bytes, s.total});
+  if (rc) return rc;
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, h = K / 2, S = c.num_sources,
             SN = S * N;
@@ -806,20 +762,17 @@ extern "C" int srf_original_backward(const srf_plan* p, const float* const* P, f
   if (srf_profiling()) srf_prof_mark("(gap)", st);
   SRF_CHECK_HIP(hipMemsetAsync(zeros, 0, sizeof(float) * s.zero_floats, st));
   // the weight-gradient GEMMs of this call fold their partial sums in a fixed order
-  struct Ordered {
-    Ordered() { srf_pw_wgrad_ordered(true); }
-    ~Ordered() { srf_pw_wgrad_ordered(false); }
-  } ordered_for_this_call;
+  const SrfWgradOrderedScope ordered_for_this_call;
   // ---- the two weights in their GEMM forms, again (scratch is not kept between the calls)
   float* tz = fp(s.tz);
   float* tz_bias = tz + srf_align_up((size_t)S * N * N, 64);
   float* wdec = fp(s.wdec);
-  int rc = srf_mask_weight_fill(tl.m_w, tl.m_b, tz, tz_bias, N, S, stream);
+  rc = srf_mask_weight_fill(tl.m_w, tl.m_b, tz, tz_bias, N, S, stream);
   if (rc) return rc;
   rc = srf_decoder_weight_expand(tl.dec_w, wdec, N, S, K, stream);
   if (rc) return rc;
   // transposed weights of the data-gradient GEMMs, pre-split for the 256 x 128 kernel where it takes the shape
-  OPackQueue pk{sc + s.pkT};
+  SrfPackQueue pk{sc + s.pkT};
   auto packT = [&](const float* wf, int cout_d, int cin_d) {   // wf: forward weight [cin_d][cout_d]
     return pk.add(wf, srf_kernel_mode() == 0 ? srf_packed_pw_weight_bytes(cout_d, cin_d) : 0, cout_d, cin_d);
   };
@@ -832,28 +785,16 @@ extern "C" int srf_original_backward(const srf_plan* p, const float* const* P, f
     pkT_proj[i] = packT(b.proj_w, B, C);
     pkT_exp[i] = packT(b.exp_w, C, B);
   }
-  if (!pk.w.empty()) {
-    rc = srf_pack_pw_weights_transposed(pk.w.data(), pk.d.data(), pk.cout.data(), pk.cin.data(), (int)pk.w.size(), st);
-    if (rc) return rc;
-  }
+  rc = pk.packT(st);
+  if (rc) return rc;
   // g_x = W^T g (+ skip): cin_d -> cout_d, w the forward weight [cin_d][cout_d]
   // Where no packed image serves the launch the GEMM would fall to the kernels that split fp32 into two bf16 parts on the fly (16
   // mantissa bits per operand); those launches run in the exact-fp32 class instead (kernel mode 2 for this thread, as the
   // training forward does).  Measured on the trajectory fixture: with the on-the-fly split a gradient entry of 9.7e-7 (2.8e-6 of
   // its tensor's largest) came out as 1.74e-6, in the exact class as 1.04e-6 -- after the clip that entry sits inside Adam's eps,
   // where the step follows the gradient's size, and the first moved one tensor's update by 4.3e-3 of its norm, the second by 6e-4.
-  struct ExactClass {
-    int prev;
-    bool on;
-    explicit ExactClass(bool want) : prev(-1), on(want && srf_kernel_mode() == 0) {
-      if (on) prev = srf_kernel_mode_override(2);
-    }
-    ~ExactClass() {
-      if (on) srf_kernel_mode_override(prev);
-    }
-  };
   auto data_grad = [&](const float* g, const float* w, const void* pkT, float* y, int cin_d, int cout_d, const float* skip) -> int {
-    const ExactClass exact(!srf_pw_packed_only(pkT, g, Bt, cin_d, cout_d, L));
+    const SrfKernelModeScope exact(!srf_pw_packed_only(pkT, g, Bt, cin_d, cout_d, L) && srf_kernel_mode() == 0, 2);
     return srf_pw_data_grad(g, w, pkT, wt, zeros, y, Bt, cin_d, cout_d, L, skip, st);
   };
   // dW (+ db) of y = W x + b.  The GEMM takes L % 4 == 0; any other L (D = 1 models only) goes through copies at a pitch of L4
@@ -891,7 +832,8 @@ extern "C" int srf_original_backward(const srf_plan* p, const float* const* P, f
                                  hipMemcpyDeviceToDevice, st));
   float* gv = fp(s.gv);
   {
-    const ExactClass exact(true);      // (the backward's FIRST linear map: its rounding reaches every gradient)
+    // (the backward's FIRST linear map: its rounding reaches every gradient)
+    const SrfKernelModeScope exact(srf_kernel_mode() == 0, 2);
     rc = srf_pw_conv(frames, wdpad, zeros, gv, Bt, s.dec_rows, SN, L, nullptr, nullptr, nullptr, 0, nullptr, 0, stream);
   }
   if (rc) return rc;

@@ -302,6 +302,44 @@ static inline int plan_pack_weights(const srf_plan* p, F source, char* ws, void*
   return srf_pack_pw_weights(pw.data(), pd.data(), p->pk_cout.data(), p->pk_cin.data(), (int)pw.size(), stream);
 }
 
+// weight images queued for ONE pack launch, carved from `at` in steps of 256 bytes (the training steps: their images live in
+// `scratch`, which images there are depends on the kernel mode of the call)
+struct SrfPackQueue {
+  char* at;
+  std::vector<const float*> w;
+  std::vector<void*> d;
+  std::vector<int> cout, cin;
+  // bytes: the image's size, 0 = none wanted (returns null)
+  const void* add(const float* weight, size_t bytes, int co, int ci) {
+    if (!bytes) return nullptr;
+    void* dst = at;
+    at += srf_align_up(bytes, 256);
+    w.push_back(weight), d.push_back(dst), cout.push_back(co), cin.push_back(ci);
+    return dst;
+  }
+  // the exact-class images of the training forward / the images of the TRANSPOSED weights of a backward's data-gradient GEMMs
+  int pack3(void* stream) const {
+    return w.empty() ? SRF_OK : srf_pack3_pw_weights(w.data(), d.data(), cout.data(), cin.data(), (int)w.size(), stream);
+  }
+  int packT(hipStream_t st) const {
+    return w.empty() ? SRF_OK : srf_pack_pw_weights_transposed(w.data(), d.data(), cout.data(), cin.data(), (int)w.size(), st);
+  }
+};
+
+// ---- what every training entry point refuses before its first launch (srf_train.hip), in this order: a null pointer (the
+// plan, P, any of `others`: G, wav, out, grad_out), a wrong num_params, a null P[i], a null G[i] (G = NULL: a forward, no
+// gradient table; the last null_grad_tail entries may be NULL: parameters the forward never reads), a `saved` or `scratch`
+// smaller than needed, either of them off the 256-byte grid.  SRF_EINVAL with `who` in front of the reason.  The refusals of
+// one family -- which plans it takes, its shape limits -- stay with the family.
+struct SrfTrainBuffers {
+  const void* saved;
+  size_t saved_bytes, saved_need;
+  const void* scratch;
+  size_t scratch_bytes, scratch_need;
+};
+int srf_train_entry_check(const char* who, const srf_plan* p, const float* const* P, float* const* G, int num_params,
+                          int null_grad_tail, std::initializer_list<const void*> others, const SrfTrainBuffers& b);
+
 // ---- dispatch decisions of a forward.  They depend on the kernel mode and the debug flags at CALL time, so they are
 // functions of the plan, not fields of it.
 

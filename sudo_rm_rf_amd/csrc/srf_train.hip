@@ -90,34 +90,22 @@ static TrainLayout train_layout(const srf_plan* p) {
   const srf_config& c = p->cfg;
   const size_t F = sizeof(float), L = p->L, Bt = p->Bt;
   const int D = c.upsampling_depth, U = c.num_blocks;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = srf_align_up(off + bytes, 256);
-    return o;
-  };
-  t.stats = take(p->stats_bytes);
-  t.enc = take(F * Bt * c.enc_num_basis * L);
+  SrfCarve all, blk;      // (blk: one block's slices, offsets relative to the block's start)
+  t.stats = all.take(p->stats_bytes);
+  t.enc = all.take(F * Bt * c.enc_num_basis * L);
   t.x_stride = srf_align_up(F * Bt * c.out_channels * L, 256);
-  t.x0 = take(t.x_stride * (U + 1));
-  // per block (relative offsets)
-  size_t rel = 0;
-  auto rtake = [&](size_t bytes) {
-    const size_t o = rel;
-    rel = srf_align_up(rel + bytes, 256);
-    return o;
-  };
-  t.y1 = rtake(F * Bt * c.in_channels * L);
-  for (int k = 0; k < SRF_MAX_DEPTH; ++k) t.lv[k] = k < D ? rtake(F * Bt * c.in_channels * (L >> k)) : 0;
-  t.merged = rtake(F * Bt * c.in_channels * L);
+  t.x0 = all.take(t.x_stride * (U + 1));
+  t.y1 = blk.take(F * Bt * c.in_channels * L);
+  for (int k = 0; k < SRF_MAX_DEPTH; ++k) t.lv[k] = k < D ? blk.take(F * Bt * c.in_channels * (L >> k)) : 0;
+  t.merged = blk.take(F * Bt * c.in_channels * L);
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
-  t.q = gc ? rtake(F * Bt * c.out_channels * L) : 0;
-  t.u = gc ? rtake(F * Bt * c.out_channels * L) : 0;
-  t.blk_stride = rel;
-  t.blk0 = take(rel * U);
-  t.m = take(F * Bt * p->SA * c.enc_num_basis * L);
-  t.v = take(F * Bt * p->SA * c.enc_num_basis * L);
-  t.total = off;
+  t.q = gc ? blk.take(F * Bt * c.out_channels * L) : 0;
+  t.u = gc ? blk.take(F * Bt * c.out_channels * L) : 0;
+  t.blk_stride = blk.off;
+  t.blk0 = all.take(blk.off * U);
+  t.m = all.take(F * Bt * p->SA * c.enc_num_basis * L);
+  t.v = all.take(F * Bt * p->SA * c.enc_num_basis * L);
+  t.total = all.off;
   return t;
 }
 
@@ -135,30 +123,25 @@ static ScratchLayout scratch_layout(const srf_plan* p) {
   const size_t F = sizeof(float), L = p->L, Bt = p->Bt;
   const int D = c.upsampling_depth, K = c.enc_kernel_size, N = c.enc_num_basis, B = c.out_channels, C = c.in_channels;
   const int SAN = p->SA * N;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = srf_align_up(off + bytes, 256);
-    return o;
-  };
-  s.dec = take(F * srf_decoder_scratch_floats(p->Bt, SAN, p->SA, K, p->L));
-  s.gv = take(F * Bt * SAN * L);
-  s.genc = take(F * Bt * N * L);
-  s.gxa = take(F * Bt * B * L);
-  s.gxb = take(F * Bt * B * L);
-  s.gf = take(F * Bt * C * L);
-  s.go = take(F * Bt * C * L);
-  s.gd = take(F * Bt * C * L);
+  SrfCarve all;
+  s.dec = all.take(F * srf_decoder_scratch_floats(p->Bt, SAN, p->SA, K, p->L));
+  s.gv = all.take(F * Bt * SAN * L);
+  s.genc = all.take(F * Bt * N * L);
+  s.gxa = all.take(F * Bt * B * L);
+  s.gxb = all.take(F * Bt * B * L);
+  s.gf = all.take(F * Bt * C * L);
+  s.go = all.take(F * Bt * C * L);
+  s.gd = all.take(F * Bt * C * L);
   for (int k = 0; k < SRF_MAX_DEPTH; ++k) {
-    s.gn[k] = (k >= 1 && k < D) ? take(F * Bt * C * (L >> k)) : 0;
-    s.gu[k] = (k >= 1 && k < D) ? take(F * Bt * C * (L >> k)) : 0;   // gradient w.r.t. normalised level k from level k+1
+    s.gn[k] = (k >= 1 && k < D) ? all.take(F * Bt * C * (L >> k)) : 0;
+    s.gu[k] = (k >= 1 && k < D) ? all.take(F * Bt * C * (L >> k)) : 0;   // gradient w.r.t. normalised level k from level k+1
   }
   s.dec_rows = (p->SA * K + 63) / 64 * 64;
   const size_t enc_rows = (size_t)p->A * K;
-  s.frames = take(F * Bt * L * (s.dec_rows > (int)enc_rows ? s.dec_rows : enc_rows));
-  s.wt = take(F * max3((size_t)B * N, (size_t)B * C, (size_t)B * SAN));
-  s.zeros = take(F * max3(C, SAN, N));
-  s.wdpad = take(F * (size_t)SAN * s.dec_rows);
+  s.frames = all.take(F * Bt * L * (s.dec_rows > (int)enc_rows ? s.dec_rows : enc_rows));
+  s.wt = all.take(F * max3((size_t)B * N, (size_t)B * C, (size_t)B * SAN));
+  s.zeros = all.take(F * max3(C, SAN, N));
+  s.wdpad = all.take(F * (size_t)SAN * s.dec_rows);
   size_t wg = 0;
   auto wgmax = [&](int cout, int cin) {
     const size_t b = srf_pw_wgrad_scratch_bytes(p->Bt, cout, cin, p->L);
@@ -173,34 +156,34 @@ static ScratchLayout scratch_layout(const srf_plan* p) {
     if (b1 > wg) wg = b1;
     if (b2 > wg) wg = b2;
   }
-  s.wg = take(wg);
-  s.gln = take(max3(srf_gln_bwd_scratch_bytes(p->Bg, p->nC), srf_gln_bwd_scratch_bytes(p->Bt, N),
+  s.wg = all.take(wg);
+  s.gln = all.take(max3(srf_gln_bwd_scratch_bytes(p->Bg, p->nC), srf_gln_bwd_scratch_bytes(p->Bt, N),
                     srf_gln_bwd_scratch_bytes(p->Bg, p->nB)));
-  s.gln2 = take(srf_gln_bwd_scratch_bytes(p->Bg, p->nC));   // the pyramid's norms alternate between gln and gln2
-  s.dw = take(srf_dwconv5_bwd_scratch_bytes(p->Bg, p->nC));
+  s.gln2 = all.take(srf_gln_bwd_scratch_bytes(p->Bg, p->nC));   // the pyramid's norms alternate between gln and gln2
+  s.dw = all.take(srf_dwconv5_bwd_scratch_bytes(p->Bg, p->nC));
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
-  s.gq = gc ? take(F * Bt * B * L) : 0;
-  s.gxm = gc ? take(F * Bt * B * L) : 0;
-  s.tac = gc ? take(srf_tac_bwd_scratch_bytes(p->Bt, c.group_size, p->nB, p->L)) : 0;
+  s.gq = gc ? all.take(F * Bt * B * L) : 0;
+  s.gxm = gc ? all.take(F * Bt * B * L) : 0;
+  s.tac = gc ? all.take(srf_tac_bwd_scratch_bytes(p->Bt, c.group_size, p->nB, p->L)) : 0;
   // per-call scratch slices of the blocks' norm / depthwise-conv backwards (zeroed once per backward; their parameter-gradient
   // reductions are deferred to one batched flush: srf_backward.hip, SrfDeferCtx): per block D + 2 norm slices and D conv slices
   s.gln_slice = srf_align_up(srf_gln_bwd_scratch_bytes(p->Bg, p->nC), 256);
   s.dw_slice = srf_align_up(srf_dwconv5_bwd_scratch_bytes(p->Bg, p->nC), 256);
   s.arena_bytes = (size_t)c.num_blocks * ((size_t)(D + 2) * s.gln_slice + (size_t)D * s.dw_slice);
-  s.arena = take(s.arena_bytes);
+  s.arena = all.take(s.arena_bytes);
   // two-part images of the TRANSPOSED weights for the backward's data-gradient GEMMs (packed once per backward)
   {
     size_t pk = srf_align_up(srf_packed_pw_weight_bytes(B, SAN), 256) + srf_align_up(srf_packed_pw_weight_bytes(N, B), 256);
     pk += (size_t)c.num_blocks * (srf_align_up(srf_packed_pw_weight_bytes(p->nC, p->nB), 256) + srf_align_up(srf_packed_pw_weight_bytes(p->nB, p->nC), 256));
-    s.pkT = take(pk);
+    s.pkT = all.take(pk);
   }
   // three-part weight images of the forward's 1x1 convolutions (packed once per step by srf_forward_train)
   {
     size_t pk = srf_align_up(srf_packed3_pw_weight_bytes(B, N), 256) + srf_align_up(srf_packed3_pw_weight_bytes(SAN, B), 256);
     pk += (size_t)c.num_blocks * (srf_align_up(srf_packed3_pw_weight_bytes(p->nC, p->nB), 256) + srf_align_up(srf_packed3_pw_weight_bytes(p->nB, p->nC), 256));
-    s.pk3 = take(pk);
+    s.pk3 = all.take(pk);
   }
-  s.total = off;
+  s.total = all.off;
   return s;
 }
 
@@ -221,30 +204,55 @@ static int train_check(const srf_plan* p, const char* who) {
   return SRF_OK;
 }
 
-// The causal variant (CausalSuDORMRF) has an inference forward only: every training entry point refuses its plans before
-// anything is launched; the two size queries return 0 with the same message in srf_last_error().
-static bool causal_refused(const srf_plan* p, const char* who) {
-  if (p && p->cfg.variant == SRF_VARIANT_ATTENTIVE) {
+// The entry points of this file train the Improved and GroupComm models.  The plans of every other family are refused before
+// anything is launched, with where that family trains: the causal and the original model through entry points of their own
+// (srf_causal_train.hip, srf_original_train.hip), the attentive models nowhere (inference forward only).  A null plan is refused too.  The two
+// size queries return 0 with the same message in srf_last_error().
+static bool other_family_refused(const srf_plan* p, const char* who) {
+  if (!p) {
+    srf_set_error("%s: null plan", who);
+    return true;
+  }
+  if (p->cfg.variant == SRF_VARIANT_ATTENTIVE) {
     srf_set_error("%s: not available for the attentive variant (attentive SuDORMRF v2 has an inference forward only)", who);
     return true;
   }
-  if (p && p->cfg.variant == SRF_VARIANT_ATTENTIVE_V3) {
+  if (p->cfg.variant == SRF_VARIANT_ATTENTIVE_V3) {
     srf_set_error("%s: not available for the attentive v3 variant (attentive SuDORMRF v3 has an inference forward only)", who);
     return true;
   }
-  if (p && p->cfg.variant == SRF_VARIANT_ORIGINAL) {
-    srf_set_error("%s: not available for the original variant (the original SuDORMRF has an inference forward only)", who);
+  if (p->cfg.variant == SRF_VARIANT_ORIGINAL) {
+    srf_set_error("%s: not available for the original variant (the original SuDORMRF trains through srf_original_forward_train / "
+                  "srf_original_backward)", who);
     return true;
   }
-  if (!p || p->cfg.variant != SRF_VARIANT_CAUSAL) return false;
-  srf_set_error("%s: not available for the causal variant (CausalSuDORMRF has an inference forward only)", who);
+  if (p->cfg.variant != SRF_VARIANT_CAUSAL) return false;
+  srf_set_error("%s: not available for the causal variant (CausalSuDORMRF trains through srf_causal_forward_train / "
+                "srf_causal_backward)", who);
   return true;
 }
 extern "C" size_t srf_train_saved_bytes(const srf_plan* p) {
-  return p && !causal_refused(p, "srf_train_saved_bytes") ? train_layout(p).total : 0;
+  return !other_family_refused(p, "srf_train_saved_bytes") ? train_layout(p).total : 0;
 }
 extern "C" size_t srf_train_scratch_bytes(const srf_plan* p) {
-  return p && !causal_refused(p, "srf_train_scratch_bytes") ? scratch_layout(p).total : 0;
+  return !other_family_refused(p, "srf_train_scratch_bytes") ? scratch_layout(p).total : 0;
+}
+
+int srf_train_entry_check(const char* who, const srf_plan* p, const float* const* P, float* const* G, int num_params,
+                          int null_grad_tail, std::initializer_list<const void*> others, const SrfTrainBuffers& b) {
+  bool all = p && P && b.saved && b.scratch;
+  for (const void* o : others) all = all && o;
+  SRF_CHECK_ARG(all, "%s: null pointer", who);
+  SRF_CHECK_ARG(num_params == p->n_params, "%s: expected %d parameter tensors, got %d", who, p->n_params, num_params);
+  for (int i = 0; i < num_params; ++i) {
+    SRF_CHECK_ARG(P[i], "%s: parameter %d is null", who, i);
+    SRF_CHECK_ARG(!G || G[i] || i >= num_params - null_grad_tail, "%s: gradient %d is null", who, i);
+  }
+  SRF_CHECK_ARG(b.saved_bytes >= b.saved_need, "%s: saved buffer too small (%zu bytes, needs %zu)", who, b.saved_bytes, b.saved_need);
+  SRF_CHECK_ARG(b.scratch_bytes >= b.scratch_need, "%s: scratch buffer too small (%zu bytes, needs %zu)", who, b.scratch_bytes,
+                b.scratch_need);
+  SRF_CHECK_ARG(((((size_t)b.saved) | ((size_t)b.scratch)) & 255) == 0, "%s: saved and scratch must be 256-byte aligned", who);
+  return SRF_OK;
 }
 
 static int forward_train_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
@@ -261,13 +269,15 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
 // split-bf16: with an exact forward every parameter gradient is within 2e-5 of the reference's.
 extern "C" int srf_forward_train(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                                  void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-  if (causal_refused(p, "srf_forward_train")) return SRF_EINVAL;
+  if (other_family_refused(p, "srf_forward_train")) return SRF_EINVAL;
   const int mode = srf_kernel_mode(), flags = srf_debug_flags();
   const bool exact = mode == 0 && !(flags & SRF_DBG_TRAIN_FWD_SPLIT_BF16);
-  const int prev = exact ? srf_kernel_mode_override(2) : -1;
   bool skip_d0 = false;
-  const int rc = forward_train_impl(p, P, num_params, wav, out, saved, saved_bytes, scratch, scratch_bytes, exact, &skip_d0, stream);
-  if (exact) srf_kernel_mode_override(prev);
+  int rc;
+  {
+    const SrfKernelModeScope exact_class(exact, 2);
+    rc = forward_train_impl(p, P, num_params, wav, out, saved, saved_bytes, scratch, scratch_bytes, exact, &skip_d0, stream);
+  }
   if (saved) train_rec_put(saved, saved_bytes, rc == SRF_OK, skip_d0, mode, flags);
   return rc;
 }
@@ -275,15 +285,12 @@ extern "C" int srf_forward_train(const srf_plan* p, const float* const* P, int n
 static int forward_train_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                               void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, bool split_tail, bool* skip_d0_out,
                               void* stream) {
-  SRF_CHECK_ARG(p && P && wav && out && saved && scratch, "srf_forward_train: null pointer");
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_forward_train: expected %d parameter tensors, got %d", p->n_params,
-                num_params);
-  int rc = train_check(p, "srf_forward_train");
-  if (rc) return rc;
   const TrainLayout t = train_layout(p);
   const ScratchLayout s = scratch_layout(p);
-  SRF_CHECK_ARG(saved_bytes >= t.total && scratch_bytes >= s.total, "srf_forward_train: saved / scratch buffer too small");
-  SRF_CHECK_ARG(((((size_t)saved) | ((size_t)scratch)) & 255) == 0, "srf_forward_train: buffers must be 256-byte aligned");
+  int rc = srf_train_entry_check("srf_forward_train", p, P, nullptr, num_params, 0, {wav, out},
+                                 {saved, saved_bytes, t.total, scratch, scratch_bytes, s.total});
+  if (!rc) rc = train_check(p, "srf_forward_train");
+  if (rc) return rc;
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
   const int Bt = p->Bt, L = p->L, B = c.out_channels;
@@ -300,20 +307,9 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
   // block, 24-bit operands: srf_pwconv_x3w.hip NP 3) where the 256 x 128 kernel takes the launch; their weights are split and
   // laid out once per step, here.  Debug flag 1 << 31: the exact-fp32 MFMA kernel instead (A/B).
   const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
-  std::vector<const float*> pk_w;
-  std::vector<void*> pk_d;
-  std::vector<int> pk_co, pk_ci;
-  size_t pk_off = s.pk3;
-  auto pack3 = [&](const float* w, int cout, int cin) -> const void* {
-    const size_t bytes = srf_packed3_pw_weight_bytes(cout, cin);
-    if (!three || !bytes) return nullptr;
-    void* d = sc + pk_off;
-    pk_off += srf_align_up(bytes, 256);
-    pk_w.push_back(w);
-    pk_d.push_back(d);
-    pk_co.push_back(cout);
-    pk_ci.push_back(cin);
-    return d;
+  SrfPackQueue pk{sc + s.pk3};
+  auto pack3 = [&](const float* w, int cout, int cin) {
+    return pk.add(w, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin);
   };
   const SrfFront<const float> f = plan_front(P);
   const SrfTail<const float> tl = plan_tail(p, P);
@@ -325,10 +321,8 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
     pk_res[i] = pack3(b.res_w, nB, nC);
   }
   const void* pk_mask = pack3(tl.mask_w, p->SA * N, B);
-  if (!pk_w.empty()) {
-    rc = srf_pack3_pw_weights(pk_w.data(), pk_d.data(), pk_co.data(), pk_ci.data(), (int)pk_w.size(), stream);
-    if (rc) return rc;
-  }
+  rc = pk.pack3(stream);
+  if (rc) return rc;
 
   float* enc = (float*)(sv + t.enc);
   rc = srf_encoder(wav, f.enc_w, enc, stats, Bt, p->A, p->T, N, K, L, stream);
@@ -426,10 +420,8 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
   // rounding of the split-bf16 GEMM (the loss is smooth in the estimates), unlike the early layers' (see above) -- so when the
   // exact class was this function's own choice it runs on the split kernel (round 6: 292 -> 130 us at cfg 2, 4 x that at N = 2048)
   // instead of the exact-fp32 MFMA kernel the thin output (42 rows) would otherwise fall to.
-  const int tail_prev = split_tail ? srf_kernel_mode_override(0) : -1;
-  rc = srf_decoder(v, tl.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
-  if (split_tail) srf_kernel_mode_override(tail_prev);
-  return rc;
+  const SrfKernelModeScope split_class(split_tail, 0);
+  return srf_decoder(v, tl.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
 }
 
 // ---- srf_backward: the graph in reverse, in stages over one walk state (as the forwards of srf_api.hip) ----------------------
@@ -547,20 +539,9 @@ struct BwdWalk {
 // stage images, all of them in one launch here (shapes / launches that kernel does not take keep the transposed fp32 copy
 // `wt` and the 128 x 128 kernels).
 int BwdWalk::pack_weights() {
-  std::vector<const float*> pk_w;
-  std::vector<void*> pk_d;
-  std::vector<int> pk_co, pk_ci;
-  size_t pk_off = s.pkT;
-  auto packT = [&](const float* w, int cout_d, int cin_d) -> const void* {   // w: forward weight [cin_d][cout_d]
-    const size_t bytes = srf_packed_pw_weight_bytes(cout_d, cin_d);
-    if (!bytes || srf_kernel_mode() != 0) return nullptr;
-    void* d = sc + pk_off;
-    pk_off += srf_align_up(bytes, 256);
-    pk_w.push_back(w);
-    pk_d.push_back(d);
-    pk_co.push_back(cout_d);
-    pk_ci.push_back(cin_d);
-    return d;
+  SrfPackQueue pk{sc + s.pkT};
+  auto packT = [&](const float* w, int cout_d, int cin_d) {   // w: forward weight [cin_d][cout_d]
+    return pk.add(w, srf_kernel_mode() == 0 ? srf_packed_pw_weight_bytes(cout_d, cin_d) : 0, cout_d, cin_d);
   };
   pkT_mask = packT(plan_tail(p, P).mask_w, B, SAN);
   pkT_bott = packT(plan_front(P).bott_w, N, B);
@@ -571,8 +552,7 @@ int BwdWalk::pack_weights() {
     pkT_res[i] = packT(b.res_w, nC, nB);               // res_conv: forward [nB][nC], gradient GEMM nB -> nC
     pkT_proj[i] = packT(b.proj_w, nB, nC);             // proj_1x1: forward [nC][nB], gradient GEMM nC -> nB
   }
-  if (pk_w.empty()) return SRF_OK;
-  return srf_pack_pw_weights_transposed(pk_w.data(), pk_d.data(), pk_co.data(), pk_ci.data(), (int)pk_w.size(), st);
+  return pk.packT(st);
 }
 
 // Decoder, mask, mask_net: grad_out -> gx = gradient w.r.t. x_U; leaves the mask path's g_enc in s.genc
@@ -760,17 +740,15 @@ int BwdWalk::front(const float* wav, float* grad_wav) {
 static int backward_impl(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
                          const float* grad_out, const void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes,
                          float* grad_wav, void* stream) {
-  if (causal_refused(p, grad_wav ? "srf_backward_wav" : "srf_backward")) return SRF_EINVAL;
-  SRF_CHECK_ARG(p && P && G && wav && grad_out && saved && scratch, "srf_backward: null pointer");
-  SRF_CHECK_ARG(num_params == p->n_params, "srf_backward: expected %d parameter tensors, got %d", p->n_params, num_params);
-  int rc = train_check(p, "srf_backward");
-  if (rc) return rc;
-  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] && G[i], "srf_backward: parameter / gradient %d is null", i);
+  const char* who = grad_wav ? "srf_backward_wav" : "srf_backward";
+  if (other_family_refused(p, who)) return SRF_EINVAL;
   // (freed on every exit path: a backward that fails half-way leaves nothing behind)
   const std::unique_ptr<SrfBwdCtx, void (*)(SrfBwdCtx*)> ctx(srf_bwd_ctx_new(), srf_bwd_ctx_free);
   BwdWalk w(p, P, G, saved, scratch, stream, ctx.get());
-  SRF_CHECK_ARG(saved_bytes >= w.t.total && scratch_bytes >= w.s.total, "srf_backward: saved / scratch buffer too small");
-  rc = pyr_bwd_path(p, saved, scratch, grad_wav ? "srf_backward_wav" : "srf_backward", &w.path);
+  int rc = srf_train_entry_check(who, p, P, G, num_params, 0, {G, wav, grad_out},
+                                 {saved, saved_bytes, w.t.total, scratch, scratch_bytes, w.s.total});
+  if (!rc) rc = train_check(p, who);
+  if (!rc) rc = pyr_bwd_path(p, saved, scratch, who, &w.path);
   if (rc) return rc;
   SRF_CHECK_HIP(hipMemsetAsync(w.fp(w.s.zeros), 0, sizeof(float) * max3(p->cfg.in_channels, w.SAN, w.N), w.st));
   // the blocks' norm / conv backwards get one scratch slice per call (statistic buckets zeroed here, once)

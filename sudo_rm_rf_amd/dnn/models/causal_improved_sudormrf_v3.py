@@ -271,7 +271,7 @@ class CausalSuDORMRF(nn.Module):
             if tensors[0] is not None and tensors[0].requires_grad:
                 raise NotImplementedError("CausalSuDORMRF.forward: the HIP training step has no gradient w.r.t. the input "
                                           "mixture; pass a mixture that does not require grad")
-            return self._engine().run_causal_train(self, input_wav, self.in_audio_channels)
+            return self._engine().run_train(self, input_wav, self.in_audio_channels)
         _refuse_autograd("CausalSuDORMRF.forward", tensors)
         return self._engine().run(self, input_wav, self.in_audio_channels)
 

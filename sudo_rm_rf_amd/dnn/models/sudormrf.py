@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from ... import _lib, ops, original
-from ...engine import ModelEngine, _weights
+from ...engine import ModelEngine, _check_mixture, _checked_params, _weights
 from .improved_sudormrf import _hip_only
 
 
@@ -279,29 +279,19 @@ class SuDORMRF(nn.Module):
     def forward(self, input_wav):
         """[batch, 1, time] float -> [batch, num_sources, time] float32: one srf_forward call on the caller's stream.  Inference
         only, unless enable_hip_training() was called: then a forward under autograd is the HIP training step."""
-        if not isinstance(input_wav, torch.Tensor):
-            raise TypeError("input must be a torch.Tensor")
-        if input_wav.dim() != 3 or input_wav.shape[1] != 1:
-            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(input_wav.shape),))
         weights = _weights(self)
+        mixture_grad = isinstance(input_wav, torch.Tensor) and input_wav.requires_grad
         if self.__dict__.get("_srf_hip_training") and torch.is_grad_enabled() and (
-                input_wav.requires_grad or any(t.requires_grad for t in weights)):
-            if input_wav.requires_grad:
+                mixture_grad or any(t.requires_grad for t in weights)):
+            if mixture_grad:
                 raise NotImplementedError("SuDORMRF.forward: the HIP training step has no gradient w.r.t. the input mixture; "
                                           "pass a mixture that does not require grad")
-            return self._engine().run_original_train(self, input_wav)
+            return self._engine().run_train(self, input_wav, 1)
         self._check_inference(weights)
-        if input_wav.device.type != "cuda":
-            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
-                                "fallback (use the reference implementation for CPU inference)." % input_wav.device)
-        params = [p.detach() for p in weights]
-        for p in params:
-            if p.device != input_wav.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters and buffers must be contiguous float32 on %s" % input_wav.device)
+        _check_mixture(input_wav, 1)
+        params = _checked_params(weights, input_wav.device, detach=True)
         x = input_wav.detach().to(torch.float32).contiguous()
         batch, _, T = x.shape
-        if batch == 0 or T == 0:
-            raise RuntimeError("empty input %s" % (tuple(input_wav.shape),))
         eng = self._engine()
         with torch.cuda.device(x.device), eng._run_lock(x.device):
             plan = eng.plan_for(batch, T, x.device)

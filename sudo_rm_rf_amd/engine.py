@@ -6,7 +6,7 @@ import ctypes as C
 import os
 import threading
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
@@ -95,37 +95,15 @@ class Plan:
             pass
 
     def train_sizes(self):
-        """(saved bytes, scratch bytes) of the training step (srf_forward_train / srf_backward)."""
-        lib = _lib.load()
-        return lib.srf_train_saved_bytes(self.handle), lib.srf_train_scratch_bytes(self.handle)
+        """(saved bytes, scratch bytes) of this plan's training step, asked of its own family's size queries."""
+        lib, query = _lib.load(), _train_family(self.cfg_tuple).sizes
+        return getattr(lib, query + "_saved_bytes")(self.handle), getattr(lib, query + "_scratch_bytes")(self.handle)
 
     def train_scratch(self):
-        """Backward scratch, shared by every training step of this plan (stream-ordered reuse)."""
+        """Scratch of the training step, shared by every step of this plan (stream-ordered reuse)."""
         if getattr(self, "_train_scratch", None) is None:
             self._train_scratch = torch.empty(self.train_sizes()[1], dtype=torch.uint8, device=self.device)
         return self._train_scratch
-
-    def causal_train_sizes(self):
-        """(saved bytes, scratch bytes) of the causal model's training step (srf_causal_forward_train / srf_causal_backward)."""
-        lib = _lib.load()
-        return lib.srf_causal_train_saved_bytes(self.handle), lib.srf_causal_train_scratch_bytes(self.handle)
-
-    def causal_train_scratch(self):
-        """Scratch of the causal training step, shared by every step of this plan (stream-ordered reuse)."""
-        if getattr(self, "_causal_train_scratch", None) is None:
-            self._causal_train_scratch = torch.empty(self.causal_train_sizes()[1], dtype=torch.uint8, device=self.device)
-        return self._causal_train_scratch
-
-    def original_train_sizes(self):
-        """(saved bytes, scratch bytes) of the original model's training step (srf_original_forward_train / srf_original_backward)."""
-        lib = _lib.load()
-        return lib.srf_original_train_saved_bytes(self.handle), lib.srf_original_train_scratch_bytes(self.handle)
-
-    def original_train_scratch(self):
-        """Scratch of the original model's training step, shared by every step of this plan (stream-ordered reuse)."""
-        if getattr(self, "_original_train_scratch", None) is None:
-            self._original_train_scratch = torch.empty(self.original_train_sizes()[1], dtype=torch.uint8, device=self.device)
-        return self._original_train_scratch
 
     def forward(self, param_ptrs, wav, out):
         lib = _lib.load()
@@ -194,30 +172,50 @@ class Plan:
         return dst
 
 
+# What tells one family's training step from another's.  sizes: prefix of its two size queries; backward_wav: the backward
+# that also returns the mixture's gradient (None: the family has none, the models refuse a mixture that requires grad);
+# no_grad_tail: trailing tensors of the state_dict the forward never reads -- NULL gradient slots, .grad stays None.
+_TrainFamily = namedtuple("_TrainFamily", "sizes forward backward backward_wav no_grad_tail")
+_TRAIN_FAMILIES = {
+    "causal": _TrainFamily("srf_causal_train", "srf_causal_forward_train", "srf_causal_backward", None, 0),
+    "original": _TrainFamily("srf_original_train", "srf_original_forward_train", "srf_original_backward", None, 2),   # (ln_mask_in.*)
+}
+_IMPROVED_FAMILY = _TrainFamily("srf_train", "srf_forward_train", "srf_backward", "srf_backward_wav", 0)      # and GroupComm
+
+
+def _train_family(cfg_tuple):
+    return _TRAIN_FAMILIES.get(cfg_tuple[0], _IMPROVED_FAMILY)
+
+
 class _TrainStep(torch.autograd.Function):
-    """SuDORMRF.forward under autograd: srf_forward_train keeps the activations the backward needs in one
-    `saved` buffer, srf_backward turns d loss / d output into all parameter gradients (one flat buffer, returned
-    as per-parameter views).  Replaces torch autograd over the reference's ~1.8 k ATen nodes
-    (run_improved_sudormrf.py:167-172).  A mixture that requires grad also gets its gradient (srf_backward_wav: the encoder's
-    transposed convolution of the encoder-output gradient), as the reference's autograd would return it."""
+    """A model's forward under autograd, for every family that trains (_train_family): the family's forward entry keeps what
+    its backward needs in one `saved` buffer, the backward entry turns d loss / d output into all parameter gradients (one
+    zeroed flat buffer, returned as per-parameter views).  Replaces torch autograd over the reference's ~1.8 k ATen nodes
+    (run_improved_sudormrf.py:167-172).  Improved / GroupComm: a mixture that requires grad also gets its gradient
+    (srf_backward_wav: the encoder's transposed convolution of the encoder-output gradient), as the reference's autograd would
+    return it, in the mixture's dtype.  The causal and the original model are opt-in (enable_hip_training) and give the mixture
+    none; the original model's ln_mask_in.{weight, bias}, never read by its forward, get None as under the reference's
+    autograd."""
 
     @staticmethod
     def forward(ctx, engine, out_ch, wav, *params):
-        lib = _lib.load()
+        lib, fam = _lib.load(), _train_family(engine.cfg_tuple)
         x = wav.detach().to(torch.float32).contiguous()
         batch, _, T = x.shape
         dev = x.device
         with torch.cuda.device(dev), engine._run_lock(dev):
             plan = engine.plan_for(batch, T, dev)
+            if plan.num_params != len(params):
+                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
             saved_bytes, scratch_bytes = plan.train_sizes()
             saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
             scratch = plan.train_scratch()
             out = torch.empty((batch, out_ch, T), dtype=torch.float32, device=dev)
             table = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-            rc = lib.srf_forward_train(plan.handle, table, len(params), _lib.ptr(x), _lib.ptr(out), _lib.ptr(saved),
-                                       saved_bytes, _lib.ptr(scratch), scratch_bytes, _lib.current_stream(dev))
-            _lib.check(rc, "srf_forward_train")
-        ctx.plan, ctx.saved_buf, ctx.x, ctx.engine = plan, saved, x, engine
+            rc = getattr(lib, fam.forward)(plan.handle, table, len(params), _lib.ptr(x), _lib.ptr(out), _lib.ptr(saved),
+                                           saved_bytes, _lib.ptr(scratch), scratch_bytes, _lib.current_stream(dev))
+            _lib.check(rc, fam.forward)
+        ctx.plan, ctx.saved_buf, ctx.x, ctx.engine, ctx.family = plan, saved, x, engine, fam
         ctx.wav_dtype = wav.dtype
         ctx.save_for_backward(*params)
         engine.last_plan = plan
@@ -225,134 +223,14 @@ class _TrainStep(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
-        params = ctx.saved_tensors
-        plan, saved, x = ctx.plan, ctx.saved_buf, ctx.x
-        dev = x.device
-        g = grad_out.detach().to(torch.float32).contiguous()
-        sizes = [p.numel() for p in params]
-        flat = ctx.engine._flat_grad_buffer(params, sum(sizes), dev)
-        grads, off = [], 0
-        for p, n in zip(params, sizes):
-            grads.append(flat[off:off + n].view_as(p))
-            off += n
-        with torch.cuda.device(dev), ctx.engine._run_lock(dev):
-            scratch = plan.train_scratch()
-            ptab = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-            gtab = (C.c_void_p * len(params))(*[t.data_ptr() for t in grads])
-            gwav = None
-            if ctx.needs_input_grad[2]:
-                gwav = torch.empty_like(x)
-                rc = lib.srf_backward_wav(plan.handle, ptab, gtab, len(params), _lib.ptr(x), _lib.ptr(g), _lib.ptr(saved),
-                                          saved.numel(), _lib.ptr(scratch), scratch.numel(), _lib.ptr(gwav),
-                                          _lib.current_stream(dev))
-            else:
-                rc = lib.srf_backward(plan.handle, ptab, gtab, len(params), _lib.ptr(x), _lib.ptr(g), _lib.ptr(saved),
-                                      saved.numel(), _lib.ptr(scratch), scratch.numel(), _lib.current_stream(dev))
-            _lib.check(rc, "srf_backward")
-        ctx.saved_buf = None
-        ctx.engine.last_flat_grad = flat      # (autograd adopts the views below as the .grad tensors: this IS the gradient)
-        if gwav is not None and gwav.dtype != ctx.wav_dtype:
-            gwav = gwav.to(ctx.wav_dtype)
-        return (None, None, gwav) + tuple(grads)
-
-
-class _CausalTrainStep(torch.autograd.Function):
-    """CausalSuDORMRF.forward under autograd (opt-in, CausalSuDORMRF.enable_hip_training): srf_causal_forward_train keeps the
-    pre-activations the backward needs in one `saved` buffer, srf_causal_backward writes every parameter gradient into one flat
-    buffer that is returned as per-parameter views -- the mirror of _TrainStep.  The mixture gets no gradient."""
-
-    @staticmethod
-    def forward(ctx, engine, out_ch, wav, *params):
-        lib = _lib.load()
-        x = wav.detach().to(torch.float32).contiguous()
-        batch, _, T = x.shape
-        dev = x.device
-        with torch.cuda.device(dev), engine._run_lock(dev):
-            plan = engine.plan_for(batch, T, dev)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
-            saved_bytes, scratch_bytes = plan.causal_train_sizes()
-            saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-            scratch = plan.causal_train_scratch()
-            out = torch.empty((batch, out_ch, T), dtype=torch.float32, device=dev)
-            table = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-            rc = lib.srf_causal_forward_train(plan.handle, table, len(params), _lib.ptr(x), _lib.ptr(out), _lib.ptr(saved),
-                                              saved_bytes, _lib.ptr(scratch), scratch_bytes, _lib.current_stream(dev))
-            _lib.check(rc, "srf_causal_forward_train")
-        ctx.plan, ctx.saved_buf, ctx.x, ctx.engine = plan, saved, x, engine
-        ctx.save_for_backward(*params)
-        engine.last_plan = plan
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        lib = _lib.load()
+        lib, fam = _lib.load(), ctx.family
         params = ctx.saved_tensors
         plan, saved, x = ctx.plan, ctx.saved_buf, ctx.x
         if saved is None:
             raise RuntimeError("the saved activations of this step were released by its first backward")
         dev = x.device
         g = grad_out.detach().to(torch.float32).contiguous()
-        sizes = [p.numel() for p in params]
-        flat = ctx.engine._flat_grad_buffer(params, sum(sizes), dev)
-        grads, off = [], 0
-        for p, n in zip(params, sizes):
-            grads.append(flat[off:off + n].view_as(p))
-            off += n
-        with torch.cuda.device(dev), ctx.engine._run_lock(dev):
-            scratch = plan.causal_train_scratch()
-            ptab = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-            gtab = (C.c_void_p * len(params))(*[t.data_ptr() for t in grads])
-            rc = lib.srf_causal_backward(plan.handle, ptab, gtab, len(params), _lib.ptr(x), _lib.ptr(g), _lib.ptr(saved),
-                                         saved.numel(), _lib.ptr(scratch), scratch.numel(), _lib.current_stream(dev))
-            _lib.check(rc, "srf_causal_backward")
-        if not ctx.engine.keep_saved_for_repeat:
-            ctx.saved_buf = None
-        ctx.engine.last_flat_grad = flat
-        return (None, None, None) + tuple(grads)
-
-
-class _OriginalTrainStep(torch.autograd.Function):
-    """The original SuDORMRF.forward under autograd (opt-in, SuDORMRF.enable_hip_training): srf_original_forward_train keeps
-    what the backward needs in one `saved` buffer, srf_original_backward accumulates every parameter gradient into one zeroed
-    flat buffer that is returned as per-parameter views -- the mirror of _CausalTrainStep.  ln_mask_in.{weight, bias}, the last
-    two tensors of the state_dict, are never read by the forward: they get None, as under the reference's autograd.  The
-    mixture gets no gradient."""
-
-    @staticmethod
-    def forward(ctx, engine, out_ch, wav, *params):
-        lib = _lib.load()
-        x = wav.detach().to(torch.float32).contiguous()
-        batch, _, T = x.shape
-        dev = x.device
-        with torch.cuda.device(dev), engine._run_lock(dev):
-            plan = engine.plan_for(batch, T, dev)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
-            saved_bytes, scratch_bytes = plan.original_train_sizes()
-            saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-            scratch = plan.original_train_scratch()
-            out = torch.empty((batch, out_ch, T), dtype=torch.float32, device=dev)
-            table = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-            rc = lib.srf_original_forward_train(plan.handle, table, len(params), _lib.ptr(x), _lib.ptr(out), _lib.ptr(saved),
-                                                saved_bytes, _lib.ptr(scratch), scratch_bytes, _lib.current_stream(dev))
-            _lib.check(rc, "srf_original_forward_train")
-        ctx.plan, ctx.saved_buf, ctx.x, ctx.engine = plan, saved, x, engine
-        ctx.save_for_backward(*params)
-        engine.last_plan = plan
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        lib = _lib.load()
-        params = ctx.saved_tensors
-        plan, saved, x = ctx.plan, ctx.saved_buf, ctx.x
-        if saved is None:
-            raise RuntimeError("the saved activations of this step were released by its first backward")
-        dev = x.device
-        g = grad_out.detach().to(torch.float32).contiguous()
-        live = params[:-2]                        # (ln_mask_in.*: no gradient)
+        live = params[:len(params) - fam.no_grad_tail]
         sizes = [p.numel() for p in live]
         flat = ctx.engine._flat_grad_buffer(live, sum(sizes), dev)
         grads, off = [], 0
@@ -360,16 +238,47 @@ class _OriginalTrainStep(torch.autograd.Function):
             grads.append(flat[off:off + n].view_as(p))
             off += n
         with torch.cuda.device(dev), ctx.engine._run_lock(dev):
-            scratch = plan.original_train_scratch()
+            scratch = plan.train_scratch()
             ptab = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
-            gtab = (C.c_void_p * len(params))(*([t.data_ptr() for t in grads] + [None, None]))
-            rc = lib.srf_original_backward(plan.handle, ptab, gtab, len(params), _lib.ptr(x), _lib.ptr(g), _lib.ptr(saved),
-                                           saved.numel(), _lib.ptr(scratch), scratch.numel(), _lib.current_stream(dev))
-            _lib.check(rc, "srf_original_backward")
+            gtab = (C.c_void_p * len(params))(*([t.data_ptr() for t in grads] + [None] * fam.no_grad_tail))
+            args = (plan.handle, ptab, gtab, len(params), _lib.ptr(x), _lib.ptr(g), _lib.ptr(saved), saved.numel(),
+                    _lib.ptr(scratch), scratch.numel())
+            gwav = None
+            if fam.backward_wav and ctx.needs_input_grad[2]:
+                gwav = torch.empty_like(x)
+                rc = getattr(lib, fam.backward_wav)(*args, _lib.ptr(gwav), _lib.current_stream(dev))
+            else:
+                rc = getattr(lib, fam.backward)(*args, _lib.current_stream(dev))
+            _lib.check(rc, fam.backward)
         if not ctx.engine.keep_saved_for_repeat:
             ctx.saved_buf = None
-        ctx.engine.last_flat_grad = flat
-        return (None, None, None) + tuple(grads) + (None, None)
+        ctx.engine.last_flat_grad = flat      # (autograd adopts the views below as the .grad tensors: this IS the gradient)
+        if gwav is not None and gwav.dtype != ctx.wav_dtype:
+            gwav = gwav.to(ctx.wav_dtype)
+        return (None, None, gwav) + tuple(grads) + (None,) * fam.no_grad_tail
+
+
+def _check_mixture(wav, channels):
+    """The input contract of every entry: a [batch, channels, time] tensor on the MI355X with no empty dimension."""
+    if not isinstance(wav, torch.Tensor):
+        raise TypeError("input must be a torch.Tensor")
+    if wav.dim() != 3 or wav.shape[1] != channels:
+        # the reference fails on non-3D input too (Conv1d on the padded tensor)
+        raise RuntimeError("expected input of shape [batch, %d, time], got %s" % (channels, tuple(wav.shape)))
+    if wav.device.type != "cuda":
+        raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
+                            "fallback (use the reference implementation for CPU inference)." % wav.device)
+    if wav.shape[0] == 0 or wav.shape[-1] == 0:
+        raise RuntimeError("empty input %s" % (tuple(wav.shape),))
+
+
+def _checked_params(weights, device, detach):
+    """`weights` (what _weights returns) as the library takes them: contiguous float32 on `device`, detached on request."""
+    params = [p.detach() for p in weights] if detach else weights
+    for p in params:
+        if p.device != device or p.dtype != torch.float32 or not p.is_contiguous():
+            raise _lib.SrfError("all parameters must be contiguous float32 on %s" % device)
+    return params
 
 
 def _weights(module):
@@ -410,7 +319,7 @@ class ModelEngine:
         self._graph_seen = {}
         self._run_locks = {}
         self.last_flat_grad = None
-        # the causal training step frees its saved activations after the first backward (a step's memory is its activations);
+        # a training step frees its saved activations after the first backward (a step's memory is its activations);
         # True keeps them, for callers that run backward twice over one graph (retain_graph=True)
         self.keep_saved_for_repeat = False
         # the original model's ragged forward is opt-in (SuDORMRF.enable_ragged sets this)
@@ -485,62 +394,14 @@ class ModelEngine:
         self._ptr_cache[dkey] = (key, arr)
         return arr
 
-    def run_causal_train(self, module, wav, expected_channels):
-        """The opted-in causal model under autograd: one _CausalTrainStep (same input contract as run())."""
-        if not isinstance(wav, torch.Tensor):
-            raise TypeError("input must be a torch.Tensor")
-        if wav.dim() != 3 or wav.shape[1] != expected_channels:
-            raise RuntimeError("expected input of shape [batch, %d, time], got %s" % (expected_channels, tuple(wav.shape)))
-        if wav.device.type != "cuda":
-            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
-                                "fallback." % wav.device)
-        params = _weights(module)
-        for p in params:
-            if p.device != wav.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % wav.device)
-        if wav.shape[0] == 0 or wav.shape[-1] == 0:
-            raise RuntimeError("empty input %s" % (tuple(wav.shape),))
-        return _CausalTrainStep.apply(self, module.num_sources * expected_channels, wav, *params)
-
-    def run_original_train(self, module, wav):
-        """The opted-in original model under autograd: one _OriginalTrainStep ([batch, 1, time] on the MI355X)."""
-        if not isinstance(wav, torch.Tensor):
-            raise TypeError("input must be a torch.Tensor")
-        if wav.dim() != 3 or wav.shape[1] != 1:
-            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(wav.shape),))
-        if wav.device.type != "cuda":
-            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
-                                "fallback." % wav.device)
-        params = _weights(module)
-        for p in params:
-            if p.device != wav.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % wav.device)
-        if wav.shape[0] == 0 or wav.shape[-1] == 0:
-            raise RuntimeError("empty input %s" % (tuple(wav.shape),))
-        return _OriginalTrainStep.apply(self, module.num_sources, wav, *params)
-
-    def _run_train(self, module, wav, expected_channels):
-        params = _weights(module)
-        for p in params:
-            if p.device != wav.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % wav.device)
-        if wav.shape[0] == 0 or wav.shape[-1] == 0:
-            raise RuntimeError("empty input %s" % (tuple(wav.shape),))
+    def run_train(self, module, wav, expected_channels):
+        """The model under autograd: one _TrainStep of this engine's family (same input contract as run())."""
+        _check_mixture(wav, expected_channels)
+        params = _checked_params(_weights(module), wav.device, detach=False)
         return _TrainStep.apply(self, module.num_sources * expected_channels, wav, *params)
 
     def run(self, module, wav, expected_channels):
-        if not isinstance(wav, torch.Tensor):
-            raise TypeError("input must be a torch.Tensor")
-        if wav.dim() != 3:
-            # the reference fails on non-3D input too (Conv1d on the padded tensor)
-            raise RuntimeError("expected input of shape [batch, %d, time], got %s" %
-                               (expected_channels, tuple(wav.shape)))
-        if wav.shape[1] != expected_channels:
-            raise RuntimeError("expected %d input channel(s), got %d" % (expected_channels, wav.shape[1]))
-        if wav.device.type != "cuda":
-            raise _lib.SrfError(
-                "sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
-                "fallback (use the reference implementation for CPU inference)." % wav.device)
+        _check_mixture(wav, expected_channels)
         # (from the state_dict tensors, not module.parameters(): DataParallel replicas hold their weights as plain
         # tensors -- views that require grad through the Broadcast node -- and report no parameters at all)
         weights = _weights(module)
@@ -548,21 +409,16 @@ class ModelEngine:
         # model.train() + grad mode = the training step (what the reference's runner does before its loop,
         # run_improved_sudormrf.py:144); model.eval() always takes the fused inference path
         if wants_grad and module.training:
-            return self._run_train(module, wav, expected_channels)
+            return self.run_train(module, wav, expected_channels)
         if wants_grad and not self._warned_grad:
             self._warned_grad = True
             warnings.warn("sudo_rm_rf_amd: forward in eval() mode with gradients enabled returns a DETACHED output (the "
                           "fused inference path keeps no activations); call model.train() for the HIP training step or "
                           "wrap inference in torch.no_grad()", stacklevel=3)
-        params = [p.detach() for p in weights]
-        for p in params:
-            if p.device != wav.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % wav.device)
+        params = _checked_params(weights, wav.device, detach=True)
         # the reference's pad buffer is float32 whatever the input dtype (improved_sudormrf.py:312)
         x = wav.detach().to(torch.float32).contiguous()
         batch, _, T = x.shape
-        if batch == 0 or T == 0:
-            raise RuntimeError("empty input %s" % (tuple(wav.shape),))
         with torch.cuda.device(x.device), self._run_lock(x.device):
             plan = self.plan_for(batch, T, x.device)
             if plan.num_params != len(params):
@@ -594,11 +450,7 @@ class ModelEngine:
 
     def _run_ragged(self, module, wav, lengths, separate_mc):
         """separate_mc: None = the plain ragged forward, else srf_separate_ragged with that mixture-consistency setting"""
-        if not isinstance(wav, torch.Tensor) or wav.dim() != 3 or wav.shape[1] != 1:
-            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(getattr(wav, "shape", ())),))
-        if wav.device.type != "cuda":
-            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
-                                "fallback." % wav.device)
+        _check_mixture(wav, 1)
         if isinstance(lengths, torch.Tensor):
             if lengths.device.type != "cpu":
                 raise _lib.SrfError("lengths must be a list or a CPU tensor (reading a device tensor would synchronise)")
@@ -608,14 +460,9 @@ class ModelEngine:
         if module.training or (torch.is_grad_enabled() and any(t.requires_grad for t in weights)):
             raise NotImplementedError("forward_ragged: the ragged batch is an inference path (model.eval() under "
                                       "torch.no_grad()); there is no ragged training step")
-        params = [p.detach() for p in weights]
-        for p in params:
-            if p.device != wav.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % wav.device)
+        params = _checked_params(weights, wav.device, detach=True)
         x = wav.detach().to(torch.float32).contiguous()
         batch, _, T = x.shape
-        if batch == 0 or T == 0:
-            raise RuntimeError("empty input %s" % (tuple(wav.shape),))
         if len(lengths) != batch:
             raise RuntimeError("%d lengths for a batch of %d" % (len(lengths), batch))
         with torch.cuda.device(x.device), self._run_lock(x.device):
@@ -641,24 +488,16 @@ class ModelEngine:
     def separate(self, module, mixture, mixture_consistency):
         """The reference's caller-side recipe around model() (README.md:100-114) as one srf_separate call: mixture
         [batch, 1, time] RAW (un-normalised) on the MI355X -> estimates [batch, num_sources, time] in the mixture's scale."""
-        if mixture.device.type != "cuda":
-            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s" % mixture.device)
-        params = [p.detach() for p in _weights(module)]
-        for p in params:
-            if p.device != mixture.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters must be contiguous float32 on %s" % mixture.device)
         # same shape contract as run(): srf_separate reads batch * T floats, so a [B, 2, T] tensor handed to a 1-channel
         # model would silently be processed as its first B * T samples
         channels = int(getattr(module, "in_audio_channels", 1) or 1)
-        if mixture.dim() != 3:
-            raise RuntimeError("expected a mixture of shape [batch, %d, time], got %s" % (channels, tuple(mixture.shape)))
-        if mixture.shape[1] != channels or channels != 1:
-            raise _lib.SrfError("separate() takes single-channel mixtures [batch, 1, time] (the README recipe); got %s for a "
-                                "model with %d input channel(s)" % (tuple(mixture.shape), channels))
+        if channels != 1:
+            raise _lib.SrfError("separate() takes single-channel mixtures [batch, 1, time] (the README recipe); this model has "
+                                "%d input channels" % channels)
+        _check_mixture(mixture, 1)
+        params = _checked_params(_weights(module), mixture.device, detach=True)
         x = mixture.detach().to(torch.float32).contiguous()
         batch, _, T = x.shape
-        if batch == 0 or T == 0:
-            raise RuntimeError("empty input %s" % (tuple(mixture.shape),))
         with torch.cuda.device(x.device), self._run_lock(x.device):
             plan = self.plan_for(batch, T, x.device)
             if plan.num_params != len(params):

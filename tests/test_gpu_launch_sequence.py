@@ -18,7 +18,11 @@ the smallest shapes that reach each of those paths, recorded on the commit BEFOR
 Causal (v3) and attentive (v2) walks ("causal ...", "attentive ..." below): the forward, one opted-in training step and one
 streamed granule of the causal model, the attentive forward at the shapes of its two fixtures, and the causal shape that runs
 res_conv + proj_1x1 as one launch (tests/test_gpu_causal.py, PAIR_CASE).  Recorded on commit 13ee426, the commit BEFORE these walks
-took their parameters through the named views of srf_plan.h and shared their weight fold, pack helpers and tail."""
+took their parameters through the named views of srf_plan.h and shared their weight fold, pack helpers and tail.
+
+The original model's training step ("original train ..." below): one opted-in step at three fixture shapes -- orig_tiny (also
+under kernel mode 1), orig_same (no reshape_before_masks) and orig_d1 (34 frames: the padded weight-gradient path) -- recorded on
+commit 4711e9b, the commit BEFORE the three training steps took their pack queue, call guards and entry check from one place."""
 import numpy as np
 import pytest
 import torch
@@ -26,6 +30,7 @@ import torch
 from conftest import load_case
 from tests import attentive_fixtures as af
 from tests import causal_fixtures as cf
+from tests import original_fixtures as of
 from oracle import weights
 from oracle.schema import ModelConfig
 from test_gpu_model import build
@@ -181,6 +186,28 @@ def causal_train_step_trace(setting):
     return [n for n, _ in tr.launches]
 
 
+def original_train_step_trace(name, setting="0"):
+    """one opted-in training step (forward + backward of (out * out).mean()) of the original model at the shape of an
+    of.CASES fixture"""
+    from sudo_rm_rf_amd import ops
+    from sudo_rm_rf_amd.dnn.models.sudormrf import SuDORMRF
+    cfg, batch, T_, wseed, _ = of.CASES[name]
+    m = SuDORMRF(**cfg)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in of.make_state_dict(cfg, wseed).items()})
+    m = m.to(DEV).train().enable_hip_training()
+    x = torch.from_numpy(of.make_input(name)).to(DEV)
+    assert tuple(x.shape) == (batch, 1, T_)
+    flags, mode = _setting(setting)
+    try:
+        ops.set_kernel_mode(mode)
+        with ops.debug_flags(flags), ops.kernel_trace(DEV) as tr:
+            out = m(x)
+            (out * out).mean().backward()
+    finally:
+        ops.set_kernel_mode(0)
+    return [n for n, _ in tr.launches]
+
+
 def causal_stream_push_trace():
     """one srf_stream_push of one granule per stream, on a session of causal_tiny's model and batch"""
     from sudo_rm_rf_amd import ops
@@ -226,6 +253,10 @@ CAUSAL_TRACES = {
     "causal pair 0": lambda: causal_pair_trace(0),
     "causal pair NO_PAIRS": lambda: causal_pair_trace(1),
     "attentive wide batch 8": lambda: attentive_trace(af.WIDE, af.WIDE_WSEED, af.make_distinct(8, af.WIDE_T, af.WIDE_INPUT_SEED)),
+    "original train orig_tiny 0": lambda: original_train_step_trace("orig_tiny"),
+    "original train orig_tiny kernel_mode_1": lambda: original_train_step_trace("orig_tiny", "kernel_mode_1"),
+    "original train orig_same 0": lambda: original_train_step_trace("orig_same"),          # B == N: no reshape_before_masks
+    "original train orig_d1 0": lambda: original_train_step_trace("orig_d1"),              # 34 frames: the padded weight-gradient path
 }
 
 
@@ -494,6 +525,83 @@ EXPECTED.update({      # recorded on commit 13ee426
         (("pw_conv_bf16x3_w4", "dwconv5_s1_fast", "dwconv5_s2_fast", "posenc_apply", "pw_conv_bf16x3_w8", "mha_attention_mfma",
           "pw_conv_bf16x3_w4", "pw_conv_bf16x3_w4", "gln_apply2_add", "merge_fast", "pw_conv_bf16x3_w4"), 2),
         (("pw_conv_bf16x3_w4", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add"), 1),
+    ],
+})
+
+
+EXPECTED.update({      # recorded on commit 4711e9b
+    "original train orig_tiny 0": [      # 132 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_mfma"), 1),
+        (("pw_conv_small", "gln_apply_c", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_generic", "merge_fast",
+          "gln_apply_c", "pw_conv_mfma", "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_small", "pw_conv_mfma", "softmax_mask", "transpose", "zero_fill", "pw_conv_mfma", "overlap_add",
+          "bias_rescale", "mask_weight_fill", "decoder_weight_expand", "decoder_bias_part", "decoder_bias_fold",
+          "frames_gather", "pw_conv_mfma", "softmax_mask", "pw_wgrad", "pw_wgrad_reduce", "decoder_weight_contract",
+          "softmax_mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "mask_weight_fold", "transpose", "pw_conv_mfma"), 1),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_mfma", "gln_c_bwd_reduce", "gln_c_bwd_apply",
+          "gln_c_bwd_reduce", "gln_c_bwd_apply", "gln_apply_c", "pw_wgrad_small", "pw_wgrad_reduce", "transpose",
+          "pw_conv_small", "gln_c_bwd_reduce", "gln_c_bwd_apply", "merge_bwd", "gln_apply_c", "gln_bwd_reduce",
+          "gln_bwd_params", "gln_bwd_apply", "dwconv5_bwd", "dwconv5_bwd_params", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "dwconv5_bwd", "dwconv5_bwd_params", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply",
+          "dwconv5_bwd", "dwconv5_bwd_params", "gln_c_bwd_reduce", "gln_c_bwd_apply"), 2),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_mfma", "pw_wgrad_small", "pw_wgrad_reduce",
+          "transpose", "pw_conv_small", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "relu_gate",
+          "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "original train orig_tiny kernel_mode_1": [      # 132 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_generic"), 1),
+        (("pw_conv_generic", "gln_apply_c_scalar", "dwconv5_generic", "dwconv5_generic", "dwconv5_generic",
+          "merge_generic", "gln_apply_c_scalar", "pw_conv_generic", "gln_apply_c_scalar", "gln_apply_c_scalar"), 2),
+        (("pw_conv_generic", "pw_conv_generic", "softmax_mask", "transpose", "zero_fill", "pw_conv_generic",
+          "overlap_add", "bias_rescale", "mask_weight_fill", "decoder_weight_expand", "decoder_bias_part",
+          "decoder_bias_fold", "frames_gather", "pw_conv_generic", "softmax_mask", "pw_wgrad", "pw_wgrad_reduce",
+          "decoder_weight_contract", "softmax_mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "mask_weight_fold",
+          "transpose", "pw_conv_generic"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_c_bwd_reduce_scalar",
+          "gln_c_bwd_apply_scalar", "gln_c_bwd_reduce_scalar", "gln_c_bwd_apply_scalar", "gln_apply_c_scalar",
+          "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_c_bwd_reduce_scalar",
+          "gln_c_bwd_apply_scalar", "merge_bwd", "gln_apply_c_scalar", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "dwconv5_bwd", "dwconv5_bwd_params", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply",
+          "dwconv5_bwd", "dwconv5_bwd_params", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "dwconv5_bwd",
+          "dwconv5_bwd_params", "gln_c_bwd_reduce_scalar", "gln_c_bwd_apply_scalar"), 2),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic"), 2),
+        (("gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "relu_gate", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce"), 1),
+    ],
+    "original train orig_same 0": [      # 127 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_small"), 1),
+        (("pw_conv_small", "gln_apply_c", "dwconv5_s1_fast", "dwconv5_generic", "dwconv5_generic", "merge_fast",
+          "gln_apply_c", "pw_conv_mfma", "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_small", "softmax_mask", "transpose", "zero_fill", "pw_conv_mfma", "overlap_add", "bias_rescale",
+          "mask_weight_fill", "decoder_weight_expand", "decoder_bias_part", "decoder_bias_fold", "frames_gather",
+          "pw_conv_mfma", "softmax_mask", "pw_wgrad_small", "pw_wgrad_reduce", "decoder_weight_contract",
+          "softmax_mask_bwd", "pw_wgrad_small", "pw_wgrad_reduce", "mask_weight_fold"), 1),
+        (("transpose", "pw_conv_mfma", "gln_c_bwd_reduce", "gln_c_bwd_apply", "gln_c_bwd_reduce", "gln_c_bwd_apply",
+          "gln_apply_c", "pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small", "gln_c_bwd_reduce",
+          "gln_c_bwd_apply", "merge_bwd", "gln_apply_c", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply",
+          "dwconv5_bwd", "dwconv5_bwd_params", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "dwconv5_bwd",
+          "dwconv5_bwd_params", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "dwconv5_bwd",
+          "dwconv5_bwd_params", "gln_c_bwd_reduce", "gln_c_bwd_apply", "pw_wgrad_small", "pw_wgrad_reduce"), 2),
+        (("transpose", "pw_conv_mfma", "pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_small",
+          "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "relu_gate", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce"), 1),
+    ],
+    "original train orig_d1 0": [      # 107 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_generic"), 1),
+        (("pw_conv_generic", "gln_apply_c", "dwconv5_generic", "merge_generic", "gln_apply_c", "pw_conv_generic",
+          "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_generic", "pw_conv_generic", "softmax_mask", "transpose", "zero_fill", "pw_conv_generic",
+          "overlap_add", "bias_rescale", "mask_weight_fill", "decoder_weight_expand", "decoder_bias_part",
+          "decoder_bias_fold", "frames_gather", "pw_conv_generic", "softmax_mask", "pw_wgrad", "pw_wgrad_reduce",
+          "decoder_weight_contract", "softmax_mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "mask_weight_fold",
+          "transpose", "pw_conv_generic"), 1),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_c_bwd_reduce", "gln_c_bwd_apply",
+          "gln_c_bwd_reduce", "gln_c_bwd_apply", "gln_apply_c", "pw_wgrad_small", "pw_wgrad_reduce", "transpose",
+          "pw_conv_generic", "gln_c_bwd_reduce", "gln_c_bwd_apply", "gln_apply_c", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "dwconv5_bwd", "dwconv5_bwd_params", "gln_c_bwd_reduce", "gln_c_bwd_apply"), 2),
+        (("pw_wgrad_small", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_apply_c", "pw_wgrad_small",
+          "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply",
+          "relu_gate", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
     ],
 })
 

@@ -215,6 +215,43 @@ def test_backward_that_cannot_follow_its_forward_is_refused_before_any_device_ca
         lib.srf_plan_destroy(h)
 
 
+def test_training_entry_points_share_their_refusals():
+    """srf_forward_train, srf_backward and srf_backward_wav go through the entry check of the causal and the original step
+    (tests/test_causal_train_host.py, tests/test_original_train_host.py pin those): same wordings, and the two backwards refuse
+    a `saved` / `scratch` off the 256-byte grid as the forward always did.  Fake pointers: every call is refused before it
+    reads one."""
+    import ctypes as C
+    from sudo_rm_rf_amd import _lib
+    from sudo_rm_rf_amd.engine import Plan
+    lib = _lib.load()
+    cfg = ModelConfig("improved", 16, 32, 2, 3, 21, 24, 2)
+    plan = Plan((cfg.variant, cfg.in_audio_channels, cfg.out_channels, cfg.in_channels, cfg.num_blocks, cfg.upsampling_depth,
+                 cfg.enc_kernel_size, cfg.enc_num_basis, cfg.num_sources, cfg.group_size), 2, 517, torch.device("cpu"))
+    h, n = plan.handle, plan.num_params
+    saved, scratch = plan.train_sizes()
+    assert saved > 0 and scratch > 0
+    fake, off = C.c_void_p(256), C.c_void_p(260)
+    tab = (C.c_void_p * n)(*[256] * n)
+    hole = (C.c_void_p * n)(*([256] * (n - 1) + [None]))
+    fwd, bwd, wav = lib.srf_forward_train, lib.srf_backward, lib.srf_backward_wav
+    cases = [
+        (fwd, (None, tab, n, fake, fake, fake, saved, fake, scratch, None), b"srf_forward_train: null plan"),
+        (fwd, (h, tab, n, None, fake, fake, saved, fake, scratch, None), b"srf_forward_train: null pointer"),
+        (bwd, (h, tab, None, n, fake, fake, fake, saved, fake, scratch, None), b"srf_backward: null pointer"),
+        (wav, (h, tab, tab, n, fake, fake, fake, saved, fake, scratch, None, None), b"srf_backward_wav: null grad_wav"),
+        (fwd, (h, tab, n + 1, fake, fake, fake, saved, fake, scratch, None), b"parameter tensors"),
+        (fwd, (h, hole, n, fake, fake, fake, saved, fake, scratch, None), b"parameter %d is null" % (n - 1)),
+        (bwd, (h, tab, hole, n, fake, fake, fake, saved, fake, scratch, None), b"gradient %d is null" % (n - 1)),
+        (fwd, (h, tab, n, fake, fake, fake, saved - 1, fake, scratch, None), b"saved buffer too small"),
+        (wav, (h, tab, tab, n, fake, fake, fake, saved, fake, scratch - 1, fake, None), b"srf_backward_wav: scratch buffer too small"),
+        (fwd, (h, tab, n, fake, fake, off, saved, fake, scratch, None), b"256-byte aligned"),
+        (bwd, (h, tab, tab, n, fake, fake, off, saved, fake, scratch, None), b"256-byte aligned"),
+        (wav, (h, tab, tab, n, fake, fake, fake, saved, off, scratch, fake, None), b"256-byte aligned"),
+    ]
+    for fn, args, text in cases:
+        assert fn(*args) == -1 and text in lib.srf_last_error(), (text, lib.srf_last_error())
+
+
 # ---------------------------------------------------------------------------------------------
 # checkpoint tooling (SURVEY.md §8f rank 4): DataParallel prefixes, whole-module pickles, wrapped dicts
 # ---------------------------------------------------------------------------------------------

@@ -47,7 +47,7 @@ def test_size_queries(name):
     p = _plan(cfg, batch, T)
     saved, scratch = lib.srf_original_train_saved_bytes(p.handle), lib.srf_original_train_scratch_bytes(p.handle)
     assert saved > 0 and scratch > 0 and saved % 256 == 0 and scratch % 256 == 0
-    assert p.original_train_sizes() == (saved, scratch)
+    assert p.train_sizes() == (saved, scratch)
     B, C_, U, D, K, N, S = (cfg[f] for f in of.FIELDS)
     L = p.frames
     assert L == of.frames(cfg, T)
@@ -76,7 +76,7 @@ def test_walks_refuse_before_any_launch():
     lib = _lib.load()
     orig = _plan(of.TINY, 1, 1000)
     other = _plan(of.TINY, 1, 1000, variant="improved")
-    saved, scratch = orig.original_train_sizes()
+    saved, scratch = orig.train_sizes()
     n = orig.num_params
     assert n == len(of.schema(of.TINY))
     fake = C.c_void_p(256)

@@ -77,7 +77,7 @@ def main():
     plan_sizes = None
     med, lo, hi = timed(run, a.steps, a.warmup)
     plan = model._engine().last_plan
-    plan_sizes = plan.causal_train_sizes()
+    plan_sizes = plan.train_sizes()
     L, C, D, U = plan.frames, model.in_channels, model.upsampling_depth, a.blocks
     print("saved %.2f GB, scratch %.2f GB, L = %d" % (plan_sizes[0] / 1e9, plan_sizes[1] / 1e9, L))
     print("step (forward + backward), fused pyramid backward : median %.2f ms (min %.2f, max %.2f) over %d steps" % (med, lo, hi, a.steps))

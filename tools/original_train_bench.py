@@ -45,7 +45,7 @@ def main():
     for _ in range(a.warmup):
         step(model, x, g)
     plan = model._engine().last_plan
-    saved, scratch = plan.original_train_sizes()
+    saved, scratch = plan.train_sizes()
     print("frames %d; saved %.2f GiB, scratch %.2f GiB" % (plan.frames, saved / 2 ** 30, scratch / 2 ** 30))
     beg, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     beg.record()
