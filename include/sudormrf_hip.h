@@ -26,6 +26,7 @@
  *   srf_forward (att. v3)  <- SuDORMRF.forward             models/attentive_sudormrf_v3.py (srf_attentive_v3_plan_create, below)
  *   srf_forward (original) <- SuDORMRF.forward             models/sudormrf.py (srf_original_plan_create, below)
  *   srf_mha_attention      <- MHAttentionLayer.forward: softmax(q k^T / sqrt(d)) v per head, between its four Linear layers
+ *   srf_mha_attention_lse / _bwd <- the same under autograd: forward that keeps the log-sum-exp, and its gradient
  *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17; row-table push: ABI 19)
  *   srf_zeroref_snr_*      <- PermInvariantSNRwithZeroRefs fwd/bwd (FUSS training loss)  losses/snr.py:13-142 (ABI 18)
  *   srf_stab_sisdr         <- StabilizedPermInvSISDRMetric.forward (FUSS validation)    losses/sisdr.py:460-576
@@ -984,6 +985,19 @@ int srf_feeder_normalize(const float* raw, const int* len, const float* stat, in
  *   tiles, the score matrix never reaches memory).  Kernels: the exact-fp32 MFMA form for d % 16 == 0, 16 <= d <= 256
  *   (srf_mha_attention_mfma_supported, kernel modes 0 and 2; profiler name mha_attention_mfma), a VALU form for every other
  *   d <= 1024 (mha_attention_generic).
+ * srf_mha_attention_lse: srf_mha_attention that also WRITES lse[Bt, H, Lq] = log sum_lk exp(score), the per-query log-sum-exp
+ *   of the scaled scores.  o is bit-identical to srf_mha_attention's; profiler names mha_attention_lse_mfma / _generic.
+ * srf_mha_attention_bwd: the gradient of srf_mha_attention.  q, k, v as above, o and lse as srf_mha_attention_lse wrote them for
+ *   the same (q, k, v, scale), go: [Bt, H d, Lq] the gradient of o; gq [Bt, H d, Lq], gk, gv [Bt, H d, Lk] are WRITTEN in full
+ *   (no accumulation).  P is recomputed from lse: no tensor of size Lq x Lk reaches memory.  workspace: at least
+ *   srf_mha_attention_bwd_workspace_bytes(Bt, H, d, Lq, Lk) bytes of device memory at any float-aligned address, the caller's,
+ *   contents irrelevant before and after.  Deterministic: no float atomics, every output element is summed by one wavefront in
+ *   a fixed order.  Kernels: mha_attention_bwd_delta, then the exact-fp32 MFMA form where
+ *   srf_mha_attention_bwd_mfma_supported(d) (the forward's predicate: d % 16 == 0, 16 <= d <= 256, kernel modes 0 and 2):
+ *   mha_attention_bwd_dq_mfma + mha_attention_bwd_dkv_mfma (d <= 128) or + mha_attention_bwd_dv_mfma, mha_attention_bwd_dk_mfma
+ *   (d > 128: one pass per output); a VALU form for every other d <= 1024 (mha_attention_bwd_dq_generic, _dkv_generic).
+ *   Refused before the first launch (SRF_EINVAL, the message names the argument): a null pointer, the workspace included;
+ *   sizes < 1; d > 1024 on the VALU form; more than 2^31 elements per example; Bt or H > 65535.  Any Lq, Lk >= 1, independent.
  * srf_posenc_apply: x[b, c, l] = norm(a)[b, c, l] + pe[l, c] (norm nullable = identity; prelu ignored); pe: [max_len, C].
  * srf_gln_apply2_add: z = fnorm(f) + ynorm(y), each GlobLN (+ PReLU where its prelu is set) from its own statistics;
  *   out_sums (nullable) += {sum, sumsq} of z.  f, y, z: [groups, channels, length] at any float-aligned address. */
@@ -993,6 +1007,13 @@ int srf_attentive_plan_create(const srf_config* base, int n_heads, int att_dims,
 int srf_mha_attention_mfma_supported(int d);
 int srf_mha_attention(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq, int Lk, float scale,
                       void* stream);
+int srf_mha_attention_lse(const float* q, const float* k, const float* v, float* o, float* lse, int Bt, int H, int d, int Lq, int Lk,
+                          float scale, void* stream);
+int srf_mha_attention_bwd_mfma_supported(int d);
+size_t srf_mha_attention_bwd_workspace_bytes(int Bt, int H, int d, int Lq, int Lk);
+int srf_mha_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                          float* gq, float* gk, float* gv, void* workspace, int Bt, int H, int d, int Lq, int Lk, float scale,
+                          void* stream);
 int srf_posenc_apply(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L, int max_len,
                      void* stream);
 int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z, double* out_sums,

@@ -206,6 +206,10 @@ _PROTOS = {
     "srf_attentive_plan_create": (_i, [C.POINTER(srf_config), _i, _i, _i, _i, C.POINTER(_vp)]),
     "srf_mha_attention_mfma_supported": (_i, [_i]),
     "srf_mha_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp]),
+    "srf_mha_attention_lse": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp]),
+    "srf_mha_attention_bwd_mfma_supported": (_i, [_i]),
+    "srf_mha_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "srf_mha_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp]),
     "srf_posenc_apply": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _i, _vp]),
     "srf_gln_apply2_add": (_i, [_vp, C.POINTER(srf_norm), _vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _vp]),
     "srf_attentive_v3_plan_create": (_i, [C.POINTER(srf_config), _i, _i, _i, _i, C.POINTER(_vp)]),

@@ -3,6 +3,7 @@
 // ConditionalTransformerLayer.forward, AttentiveUConvBlock.forward).
 //
 //   srf_mha_attention   o[b, h d + j, lq] = sum_lk softmax_lk(scale * sum_j q[b, h d + j, lq] k[b, h d + j, lk]) v[b, h d + j, lk]
+//   srf_mha_attention_lse   the same, + lse[b, h, lq] = log sum_lk exp(score): what srf_mha_attention_bwd recomputes P from
 //   srf_posenc_apply    x[b, c, l] = GlobLN(a)[b, c, l] + pe[l, c]                      (PositionalEncoding on the transposed tensor)
 //   srf_gln_apply2_add  z = norm_f(f) + norm_y(y), {sum, sumsq} of z accumulated       (out_norm's input: ffn(y) + y)
 //   srf_gln_apply_stats y = norm(x), {sum, sumsq} of y accumulated                     (v3: O_proj's residual; final_norm's input)
@@ -46,8 +47,14 @@ struct MhaArgs {
 
 #define SRF_MHA_NEG_INF (-__builtin_inff())
 
-template <int NCH>   // 32-channel chunks of the head dimension (d <= 32 NCH): 16 accumulator registers each
-__global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a) {
+// The forms that also write the per-query log-sum-exp (srf_mha_attention_lse: what the backward recomputes P from) take the
+// [Bt, H, Lq] table as a trailing parameter PACK, the idiom of the ragged forms (srf_internal.h): empty in the plain
+// instantiations, whose arguments and code stay what they were.
+__device__ __forceinline__ void srf_mha_store_lse(size_t, float) {}   // (plain: never evaluated)
+__device__ __forceinline__ void srf_mha_store_lse(size_t at, float v, float* lse) { lse[at] = v; }
+
+template <int NCH, typename... Lse>   // 32-channel chunks of the head dimension (d <= 32 NCH): 16 accumulator registers each
+__global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a, Lse... lse) {
   __shared__ float Qs[NCH * 32 * 32];   // [channel][query], pre-scaled
   __shared__ float Vs[32 * 32];         // one 32-channel chunk of the key tile: [channel][key ^ channel]
   const int lane = threadIdx.x, col = lane & 31, half = lane >> 5;
@@ -137,6 +144,8 @@ __global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a) {
     }
   }
   const float inv = 1.f / den;
+  if constexpr (sizeof...(Lse) > 0)
+    if (qok && half == 0) srf_mha_store_lse(((size_t)b * a.H + h) * Lq + ql, m + logf(den), lse...);
   if (qok) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
@@ -160,7 +169,8 @@ __device__ __forceinline__ float srf_mha_wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__global__ __launch_bounds__(256) void srf_mha_generic_kernel(MhaArgs a) {
+template <typename... Lse>
+__global__ __launch_bounds__(256) void srf_mha_generic_kernel(MhaArgs a, Lse... lse) {
   const int lane = threadIdx.x & 63;
   const int ql = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int h = blockIdx.y, b = blockIdx.z, d = a.d, Lq = a.Lq, Lk = a.Lk;
@@ -198,6 +208,8 @@ __global__ __launch_bounds__(256) void srf_mha_generic_kernel(MhaArgs a) {
     }
   }
   const float inv = 1.f / den;
+  if constexpr (sizeof...(Lse) > 0)
+    if (lane == 0) srf_mha_store_lse(((size_t)b * a.H + h) * Lq + ql, m + logf(den), lse...);
 #pragma unroll
   for (int t = 0; t < SRF_MHA_GEN_T; ++t) {
     const int j = lane + 64 * t;
@@ -210,28 +222,50 @@ extern "C" int srf_mha_attention_mfma_supported(int d) {
   return srf_kernel_mode() != 1 && d % 16 == 0 && d >= 16 && d <= 256;
 }
 
-int srf_mha_attention_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os, int Bt,
-                              int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
+// one dispatch for the plain and the lse forms: lse = the empty pack or one float*
+template <typename... Lse>
+static int srf_mha_launch(const MhaArgs& a, int Bt, hipStream_t st, const char* mfma_name, const char* generic_name, Lse... lse) {
+  const int H = a.H, d = a.d, Lq = a.Lq;
+  if (srf_mha_attention_mfma_supported(d)) {
+    const dim3 grid((Lq + 31) / 32, H, Bt), block(64);
+    if (d <= 32) hipLaunchKernelGGL((srf_mha_mfma_kernel<1, Lse...>), grid, block, 0, st, a, lse...);
+    else if (d <= 64) hipLaunchKernelGGL((srf_mha_mfma_kernel<2, Lse...>), grid, block, 0, st, a, lse...);
+    else if (d <= 128) hipLaunchKernelGGL((srf_mha_mfma_kernel<4, Lse...>), grid, block, 0, st, a, lse...);
+    else hipLaunchKernelGGL((srf_mha_mfma_kernel<8, Lse...>), grid, block, 0, st, a, lse...);
+    SRF_CHECK_LAUNCH(mfma_name, st);
+    return SRF_OK;
+  }
+  SRF_CHECK_ARG(d <= 64 * SRF_MHA_GEN_T, "srf_mha_attention: head dimension d = %d exceeds the generic kernel's %d", d,
+                64 * SRF_MHA_GEN_T);
+  hipLaunchKernelGGL((srf_mha_generic_kernel<Lse...>), dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a, lse...);
+  SRF_CHECK_LAUNCH(generic_name, st);
+  return SRF_OK;
+}
+
+static int srf_mha_check(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq, int Lk) {
   SRF_CHECK_ARG(q && k && v && o, "srf_mha_attention: null pointer");
   SRF_CHECK_ARG(Bt > 0 && H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention: bad sizes (Bt %d, H %d, d %d, Lq %d, Lk %d)", Bt,
                 H, d, Lq, Lk);
   SRF_CHECK_ARG(Bt <= 65535 && H <= 65535, "srf_mha_attention: batch / heads too large (max 65535 each)");
   SRF_CHECK_ARG((long)H * d * (Lq > Lk ? Lq : Lk) < (1L << 31), "srf_mha_attention: one example exceeds 2^31 elements");
-  const MhaArgs a{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale};
-  if (srf_mha_attention_mfma_supported(d)) {
-    const dim3 grid((Lq + 31) / 32, H, Bt), block(64);
-    if (d <= 32) hipLaunchKernelGGL(srf_mha_mfma_kernel<1>, grid, block, 0, st, a);
-    else if (d <= 64) hipLaunchKernelGGL(srf_mha_mfma_kernel<2>, grid, block, 0, st, a);
-    else if (d <= 128) hipLaunchKernelGGL(srf_mha_mfma_kernel<4>, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(srf_mha_mfma_kernel<8>, grid, block, 0, st, a);
-    SRF_CHECK_LAUNCH("mha_attention_mfma", st);
-    return SRF_OK;
-  }
-  SRF_CHECK_ARG(d <= 64 * SRF_MHA_GEN_T, "srf_mha_attention: head dimension d = %d exceeds the generic kernel's %d", d,
-                64 * SRF_MHA_GEN_T);
-  hipLaunchKernelGGL(srf_mha_generic_kernel, dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a);
-  SRF_CHECK_LAUNCH("mha_attention_generic", st);
   return SRF_OK;
+}
+
+int srf_mha_attention_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os, int Bt,
+                              int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
+  const int rc = srf_mha_check(q, k, v, o, Bt, H, d, Lq, Lk);
+  if (rc != SRF_OK) return rc;
+  return srf_mha_launch(MhaArgs{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale}, Bt, st, "mha_attention_mfma",
+                        "mha_attention_generic");
+}
+
+int srf_mha_attention_lse_strided(const float* q, const float* k, const float* v, float* o, float* lse, long qs, long ks, long vs,
+                                  long os, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
+  const int rc = srf_mha_check(q, k, v, o, Bt, H, d, Lq, Lk);
+  if (rc != SRF_OK) return rc;
+  SRF_CHECK_ARG(lse, "srf_mha_attention_lse: lse is null");
+  return srf_mha_launch(MhaArgs{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale}, Bt, st, "mha_attention_lse_mfma",
+                        "mha_attention_lse_generic", lse);
 }
 
 extern "C" int srf_mha_attention(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq, int Lk,
@@ -239,6 +273,13 @@ extern "C" int srf_mha_attention(const float* q, const float* k, const float* v,
   SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
   const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
   return srf_mha_attention_strided(q, k, v, o, sq, sk, sk, sq, Bt, H, d, Lq, Lk, scale, (hipStream_t)stream);
+}
+
+extern "C" int srf_mha_attention_lse(const float* q, const float* k, const float* v, float* o, float* lse, int Bt, int H, int d,
+                                     int Lq, int Lk, float scale, void* stream) {
+  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_lse: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
+  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
+  return srf_mha_attention_lse_strided(q, k, v, o, lse, sq, sk, sk, sq, Bt, H, d, Lq, Lk, scale, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

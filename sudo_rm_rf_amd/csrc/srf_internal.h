@@ -51,6 +51,12 @@ int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci,
 // srf_mha_attention with an example stride per operand (q, k, v as thirds of one [Bt, 3 H d, L] projection)
 int srf_mha_attention_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os, int Bt,
                               int H, int d, int Lq, int Lk, float scale, hipStream_t st);
+// the same for srf_mha_attention_lse and srf_mha_attention_bwd (srf_attention_bwd.hip); lse and the workspace stay contiguous
+int srf_mha_attention_lse_strided(const float* q, const float* k, const float* v, float* o, float* lse, long qs, long ks, long vs,
+                                  long os, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st);
+int srf_mha_attention_bwd_strided(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                                  float* gq, float* gk, float* gv, void* workspace, long qs, long ks, long vs, long os, long gos,
+                                  long gqs, long gks, long gvs, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st);
 struct srf_plan;
 int srf_attentive_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                           const float* wav_stats, int mixture_consistency, void* stream);

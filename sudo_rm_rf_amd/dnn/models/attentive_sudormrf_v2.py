@@ -76,6 +76,14 @@ def _no_random_dropout(module, p):
                            "random; call model.eval()" % p)
 
 
+def _hip_float(t):
+    """_hip_only for a tensor autograd has to differentiate: the same refusal, nothing detached or converted."""
+    if t.device.type != "cuda" or t.dtype != torch.float32:
+        raise RuntimeError("sudo_rm_rf_amd modules train on float32 tensors on an MI355X only (no CPU fallback); got %s on %s"
+                           % (t.dtype, t.device))
+    return t
+
+
 class MHAttentionLayer(nn.Module):
     """Q / K / V / O projections around softmax attention; forward(Q, K, V) takes [batch, len, emb_dim] like the reference."""
 
@@ -90,8 +98,29 @@ class MHAttentionLayer(nn.Module):
         self.d_model = d_model
         self.q_normalizer = 1. / math.sqrt(d_model)
 
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state.pop("_srf_hip_training", None)
+        return state
+
+    def enable_hip_training(self, flag=True):
+        """Opt this layer into (flag=False: out of) a differentiable forward and return self.  With it, forward(Q, K, V) under
+        autograd returns a tensor whose backward runs on HIP (srf_mha_attention_bwd between ops.pw_conv / ops.pw_wgrad,
+        DESIGN.md section 16.1): gradients for the eight parameters of Q_proj, K_proj, V_proj, O_proj and for whichever of Q, K,
+        V require grad -- self-attention (one tensor three times) and cross-attention (Lq != Lk) alike.  Without autograd, and
+        without the opt-in, the inference forward on detached weights is untouched; train() with dropout.p > 0 keeps raising.
+        The flag is a plain attribute: not in state_dict() and dropped from pickles."""
+        if flag:
+            self.__dict__["_srf_hip_training"] = True
+        else:
+            self.__dict__.pop("_srf_hip_training", None)
+        return self
+
     def forward(self, Q, K, V):
         _no_random_dropout(self, self.dropout.p)
+        if self.__dict__.get("_srf_hip_training") and torch.is_grad_enabled() and any(
+                t.requires_grad for t in [Q, K, V] + list(self.parameters())):
+            return attention.mha_layer_train(self, *(_hip_float(x) for x in (Q, K, V)))
         t = lambda x: _hip_only(x).transpose(1, 2).contiguous()
         lin = lambda m, x: ops.pw_conv(x, m.weight.detach(), m.bias.detach())
         o = attention.mha_attention(lin(self.Q_proj, t(Q)), lin(self.K_proj, t(K)), lin(self.V_proj, t(V)), self.n_heads,
