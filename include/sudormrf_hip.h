@@ -999,6 +999,18 @@ int srf_feeder_normalize(const float* raw, const int* len, const float* stat, in
  *   Refused before the first launch (SRF_EINVAL, the message names the argument): a null pointer, the workspace included;
  *   sizes < 1; d > 1024 on the VALU form; more than 2^31 elements per example; Bt or H > 65535.  Any Lq, Lk >= 1, independent.
  * srf_posenc_apply: x[b, c, l] = norm(a)[b, c, l] + pe[l, c] (norm nullable = identity; prelu ignored); pe: [max_len, C].
+ * srf_posenc_apply_dropout: srf_posenc_apply under the PositionalEncoding's dropout (train() mode):
+ *   x[b, c, l] = keep(i) ? (norm(a)[b, c, l] + pe[l, c]) * inv_keep : 0.f, i = (b C + c) L + l as a 64-bit index.
+ *   keep(i) is a pure function of (seed, offset, i) -- not of the launch geometry, the tile or the device: word i & 3 of
+ *   Philox4x32-10 with the key {lo32(seed), hi32(seed)} on the counter {lo32(i >> 2), hi32(i >> 2), lo32(offset), hi32(offset)}
+ *   (multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85), kept where word >= floor(p 2^32); the threshold
+ *   is formed on the host in double and compared as a 64-bit number, so p = 1 drops everything.  inv_keep is the host's fp32
+ *   1.f / (1.f - p); a dropped element is SELECTED 0.f, never multiplied (p = 1: exact zeros, no inf * 0).  p == 0 runs the plain
+ *   kernel (profiler name posenc_apply, srf_posenc_apply's bits); otherwise posenc_apply_dropout.  Refused before the launch
+ *   (SRF_EINVAL, the message names the argument): p outside [0, 1] or NaN, a null a / pe / x, and srf_posenc_apply's own limits.
+ * srf_posenc_dropout_bwd: gn[i] = keep(i) ? gx[i] * inv_keep : 0.f over i < Bt C L, the mask RECOMPUTED from the forward's
+ *   (p, seed, offset), never stored; gn may alias gx.  gn is the gradient w.r.t. norm(a) + pe, which srf_gln_bwd takes as gout.
+ * srf_dropout_mask: keep[i] in {0, 1} for i < n, the same function as bytes (tests; a building block for other dropouts).
  * srf_gln_apply2_add: z = fnorm(f) + ynorm(y), each GlobLN (+ PReLU where its prelu is set) from its own statistics;
  *   out_sums (nullable) += {sum, sumsq} of z.  f, y, z: [groups, channels, length] at any float-aligned address. */
 #define SRF_VARIANT_ATTENTIVE 3
@@ -1016,6 +1028,11 @@ int srf_mha_attention_bwd(const float* q, const float* k, const float* v, const 
                           void* stream);
 int srf_posenc_apply(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L, int max_len,
                      void* stream);
+int srf_posenc_apply_dropout(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L, int max_len,
+                             float p, unsigned long long seed, unsigned long long offset, void* stream);
+int srf_posenc_dropout_bwd(const float* gx, float* gn, int Bt, int C, int L, float p, unsigned long long seed,
+                           unsigned long long offset, void* stream);
+int srf_dropout_mask(unsigned char* keep, long n, float p, unsigned long long seed, unsigned long long offset, void* stream);
 int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z, double* out_sums,
                        int groups, int channels, int length, void* stream);
 

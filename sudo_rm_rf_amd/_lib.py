@@ -211,6 +211,10 @@ _PROTOS = {
     "srf_mha_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "srf_mha_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp]),
     "srf_posenc_apply": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _i, _vp]),
+    "srf_posenc_apply_dropout": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_ulonglong,
+                                      _vp]),
+    "srf_posenc_dropout_bwd": (_i, [_vp, _vp, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_ulonglong, _vp]),
+    "srf_dropout_mask": (_i, [_vp, _l, C.c_float, C.c_ulonglong, C.c_ulonglong, _vp]),
     "srf_gln_apply2_add": (_i, [_vp, C.POINTER(srf_norm), _vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _vp]),
     "srf_attentive_v3_plan_create": (_i, [C.POINTER(srf_config), _i, _i, _i, _i, C.POINTER(_vp)]),
     "srf_gln_apply_stats": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _vp]),

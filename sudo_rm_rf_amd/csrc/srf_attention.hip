@@ -5,6 +5,7 @@
 //   srf_mha_attention   o[b, h d + j, lq] = sum_lk softmax_lk(scale * sum_j q[b, h d + j, lq] k[b, h d + j, lk]) v[b, h d + j, lk]
 //   srf_mha_attention_lse   the same, + lse[b, h, lq] = log sum_lk exp(score): what srf_mha_attention_bwd recomputes P from
 //   srf_posenc_apply    x[b, c, l] = GlobLN(a)[b, c, l] + pe[l, c]                      (PositionalEncoding on the transposed tensor)
+//   srf_posenc_apply_dropout / srf_posenc_dropout_bwd / srf_dropout_mask   the same under a Philox keep mask, and its gradient
 //   srf_gln_apply2_add  z = norm_f(f) + norm_y(y), {sum, sumsq} of z accumulated       (out_norm's input: ffn(y) + y)
 //   srf_gln_apply_stats y = norm(x), {sum, sumsq} of y accumulated                     (v3: O_proj's residual; final_norm's input)
 //
@@ -285,9 +286,50 @@ extern "C" int srf_mha_attention_lse(const float* q, const float* k, const float
 // ---------------------------------------------------------------------------------------------
 // x[b, c, l] = GlobLN(a)[b, c, l] + pe[l, c]: the level's lazy norm applied on load, the position table read through a
 // 32 x 32 LDS tile (pe is [max_len, C]: consecutive lanes read consecutive channels, then write consecutive positions)
+//
+// Dropout (srf_posenc_apply_dropout, the PositionalEncoding's nn.Dropout in train() mode).  The keep bit of element
+// i = (b C + c) L + l is a pure function of (seed, offset, i): word i & 3 of Philox4x32-10 with the key {lo(seed), hi(seed)} on the
+// counter {lo(i >> 2), hi(i >> 2), lo(offset), hi(offset)}, kept where word >= floor(p 2^32) (the threshold is a 64-bit number:
+// p = 1 gives 2^32, which no word reaches).  Nothing of the launch enters it, so the backward and a numpy restatement
+// (tests/attentive_train_ref.py) recompute the same bit and the mask is never stored.  A dropped element is SELECTED 0.f, never
+// multiplied: inv_keep = 1.f / (1.f - p) comes from the host and is inf at p = 1.
+// The dropout form takes its state as a trailing parameter PACK (the idiom of the lse forms above): the plain instantiation's
+// arguments and code stay what they were.
 // ---------------------------------------------------------------------------------------------
+struct SrfDropoutDev {
+  unsigned key0, key1, off0, off1;
+  unsigned long long threshold;   // floor(p * 2^32), in [0, 2^32]
+  float inv_keep;                 // 1.f / (1.f - p)
+};
+
+__device__ __forceinline__ bool srf_dropout_keep(const SrfDropoutDev& d, unsigned long long i) {
+  const unsigned long long blk = i >> 2;
+  unsigned c0 = (unsigned)blk, c1 = (unsigned)(blk >> 32), c2 = d.off0, c3 = d.off1;
+  unsigned k0 = d.key0, k1 = d.key1;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0;
+    c1 = l1;
+    c2 = h0 ^ c3 ^ k1;
+    c3 = l0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  const unsigned w = (unsigned)i & 3u;
+  const unsigned word = w == 0 ? c0 : (w == 1 ? c1 : (w == 2 ? c2 : c3));
+  return (unsigned long long)word >= d.threshold;
+}
+
+__device__ __forceinline__ float srf_posenc_drop(size_t, float v) { return v; }   // (plain)
+__device__ __forceinline__ float srf_posenc_drop(size_t at, float v, SrfDropoutDev d) {
+  return srf_dropout_keep(d, at) ? v * d.inv_keep : 0.f;
+}
+
+template <typename... Drop>
 __global__ __launch_bounds__(256) void srf_posenc_apply_kernel(const float* __restrict__ a, SrfNormDev nrm, const float* __restrict__ pe,
-                                                               float* __restrict__ x, double inv_count, int C, int L) {
+                                                               float* __restrict__ x, double inv_count, int C, int L, Drop... drop) {
   __shared__ float tile[32][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
@@ -310,7 +352,7 @@ __global__ __launch_bounds__(256) void srf_posenc_apply_kernel(const float* __re
         sh = nrm.beta[c] - mean * sc;
       }
       const size_t at = ((size_t)g * C + c) * L + l;
-      x[at] = fmaf(a[at], sc, sh) + tile[tx][ty + 8 * i];
+      x[at] = srf_posenc_drop(at, fmaf(a[at], sc, sh) + tile[tx][ty + 8 * i], drop...);
     }
   }
 }
@@ -323,9 +365,85 @@ extern "C" int srf_posenc_apply(const float* a, const srf_norm* norm, const floa
   const SrfNormDev nd = srf_norm_dev(norm);
   if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_posenc_apply: norm without gamma/beta");
   SRF_CHECK_ALIGNED16("srf_posenc_apply", {"norm.sums", nd.sums});
-  hipLaunchKernelGGL(srf_posenc_apply_kernel, dim3((L + 31) / 32, (C + 31) / 32, Bt), dim3(256), 0, (hipStream_t)stream, a, nd, pe, x,
-                     1.0 / ((double)C * (double)L), C, L);
+  hipLaunchKernelGGL(srf_posenc_apply_kernel<>, dim3((L + 31) / 32, (C + 31) / 32, Bt), dim3(256), 0, (hipStream_t)stream, a, nd, pe,
+                     x, 1.0 / ((double)C * (double)L), C, L);
   SRF_CHECK_LAUNCH("posenc_apply", stream);
+  return SRF_OK;
+}
+
+// p in [0, 1] (NaN fails both comparisons) -> the by-value state of the dropout kernels
+static int srf_dropout_state(const char* fn, float p, unsigned long long seed, unsigned long long offset, SrfDropoutDev* out) {
+  SRF_CHECK_ARG(p >= 0.f && p <= 1.f, "%s: p = %g is outside [0, 1]", fn, (double)p);
+  out->key0 = (unsigned)seed;
+  out->key1 = (unsigned)(seed >> 32);
+  out->off0 = (unsigned)offset;
+  out->off1 = (unsigned)(offset >> 32);
+  out->threshold = (unsigned long long)((double)p * 4294967296.0);   // floor: the product is exact in double and >= 0
+  out->inv_keep = 1.f / (1.f - p);
+  return SRF_OK;
+}
+
+extern "C" int srf_posenc_apply_dropout(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L,
+                                        int max_len, float p, unsigned long long seed, unsigned long long offset, void* stream) {
+  SrfDropoutDev dd;
+  const int rc = srf_dropout_state("srf_posenc_apply_dropout", p, seed, offset, &dd);
+  if (rc != SRF_OK) return rc;
+  if (p == 0.f) return srf_posenc_apply(a, norm, pe, x, Bt, C, L, max_len, stream);   // the plain kernel: today's bits
+  SRF_CHECK_ARG(a, "srf_posenc_apply_dropout: a is null");
+  SRF_CHECK_ARG(pe, "srf_posenc_apply_dropout: pe is null");
+  SRF_CHECK_ARG(x, "srf_posenc_apply_dropout: x is null");
+  SRF_CHECK_ARG(Bt > 0 && C > 0 && L > 0, "srf_posenc_apply_dropout: bad sizes (Bt %d, C %d, L %d)", Bt, C, L);
+  SRF_CHECK_ARG(L <= max_len, "srf_posenc_apply_dropout: L = %d positions exceed the table's max_len = %d", L, max_len);
+  SRF_CHECK_ARG(Bt <= 65535 && (C + 31) / 32 <= 65535, "srf_posenc_apply_dropout: batch / channels too large");
+  const SrfNormDev nd = srf_norm_dev(norm);
+  if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_posenc_apply_dropout: norm without gamma/beta");
+  SRF_CHECK_ALIGNED16("srf_posenc_apply_dropout", {"norm.sums", nd.sums});
+  hipLaunchKernelGGL(srf_posenc_apply_kernel<SrfDropoutDev>, dim3((L + 31) / 32, (C + 31) / 32, Bt), dim3(256), 0,
+                     (hipStream_t)stream, a, nd, pe, x, 1.0 / ((double)C * (double)L), C, L, dd);
+  SRF_CHECK_LAUNCH("posenc_apply_dropout", stream);
+  return SRF_OK;
+}
+
+// gn[i] = keep(i) ? gx[i] * inv_keep : 0 (in place when gn == gx: every element is read and written by one thread), and the
+// mask itself as bytes.  Grid-stride over a 64-bit index; every access is under i < n.
+__global__ __launch_bounds__(256) void srf_posenc_dropout_bwd_kernel(const float* gx, float* gn, long n, SrfDropoutDev dd) {
+  const long step = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += step)
+    gn[i] = srf_dropout_keep(dd, (unsigned long long)i) ? gx[i] * dd.inv_keep : 0.f;
+}
+
+__global__ __launch_bounds__(256) void srf_dropout_mask_kernel(unsigned char* __restrict__ keep, long n, SrfDropoutDev dd) {
+  const long step = (long)gridDim.x * 256;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += step)
+    keep[i] = srf_dropout_keep(dd, (unsigned long long)i) ? 1 : 0;
+}
+
+static unsigned srf_dropout_blocks(long n) { return (unsigned)std::min<long>((n + 255) / 256, 1L << 20); }
+
+extern "C" int srf_posenc_dropout_bwd(const float* gx, float* gn, int Bt, int C, int L, float p, unsigned long long seed,
+                                      unsigned long long offset, void* stream) {
+  SrfDropoutDev dd;
+  const int rc = srf_dropout_state("srf_posenc_dropout_bwd", p, seed, offset, &dd);
+  if (rc != SRF_OK) return rc;
+  SRF_CHECK_ARG(gx, "srf_posenc_dropout_bwd: gx is null");
+  SRF_CHECK_ARG(gn, "srf_posenc_dropout_bwd: gn is null");
+  SRF_CHECK_ARG(Bt > 0 && C > 0 && L > 0, "srf_posenc_dropout_bwd: bad sizes (Bt %d, C %d, L %d)", Bt, C, L);
+  const long n = (long)Bt * C * L;
+  if (p == 0.f && gn == gx) return SRF_OK;   // the identity in place
+  hipLaunchKernelGGL(srf_posenc_dropout_bwd_kernel, dim3(srf_dropout_blocks(n)), dim3(256), 0, (hipStream_t)stream, gx, gn, n, dd);
+  SRF_CHECK_LAUNCH("posenc_dropout_bwd", stream);
+  return SRF_OK;
+}
+
+extern "C" int srf_dropout_mask(unsigned char* keep, long n, float p, unsigned long long seed, unsigned long long offset,
+                                void* stream) {
+  SrfDropoutDev dd;
+  const int rc = srf_dropout_state("srf_dropout_mask", p, seed, offset, &dd);
+  if (rc != SRF_OK) return rc;
+  SRF_CHECK_ARG(keep, "srf_dropout_mask: keep is null");
+  SRF_CHECK_ARG(n > 0, "srf_dropout_mask: n = %ld", n);
+  hipLaunchKernelGGL(srf_dropout_mask_kernel, dim3(srf_dropout_blocks(n)), dim3(256), 0, (hipStream_t)stream, keep, n, dd);
+  SRF_CHECK_LAUNCH("dropout_mask", stream);
   return SRF_OK;
 }
 

@@ -64,10 +64,45 @@ class PositionalEncoding(nn.Module):
         pe[:, 1::2] = torch.cos(position * div_term)
         self.register_buffer('pe', pe.unsqueeze(0))
 
+    def __getstate__(self):
+        return _without_opt_in(self)
+
+    def enable_hip_training(self, flag=True):
+        """Opt this module into (flag=False: out of) train() mode with dropout.p > 0 and return self.  With it, every forward
+        call in train() mode draws one (seed, offset) pair from torch's CPU default generator (one torch.randint of two int64
+        values: no device synchronisation; torch.manual_seed(s) in front of two runs gives the same masks) and runs
+        srf_posenc_apply_dropout, whose keep mask is a pure function of (seed, offset, element index): DESIGN.md section 16.2.
+        eval() or p == 0 runs the plain kernel.  The output is not differentiable here (TransformerLayer's opt-in is).  The flag
+        is a plain attribute: not in state_dict() and dropped from pickles."""
+        return _set_opt_in(self, flag)
+
     def forward(self, x):
-        _no_random_dropout(self, self.dropout.p)
+        p = float(self.dropout.p) if self.training else 0.0
+        if not self.__dict__.get("_srf_hip_training"):
+            _no_random_dropout(self, self.dropout.p)
         x = _hip_only(x)                                        # [batch, len, d_model]
-        return attention.posenc_apply(x.transpose(1, 2).contiguous(), self.pe.detach()).transpose(1, 2).contiguous()
+        seed, offset = attention.draw_dropout_state() if p > 0 else (0, 0)
+        return attention.posenc_apply(x.transpose(1, 2).contiguous(), self.pe.detach(), p=p, seed=seed,
+                                      offset=offset).transpose(1, 2).contiguous()
+
+
+def _set_opt_in(module, flag):
+    if flag:
+        module.__dict__["_srf_hip_training"] = True
+    else:
+        module.__dict__.pop("_srf_hip_training", None)
+    return module
+
+
+def _without_opt_in(module):
+    state = module.__dict__.copy()
+    state.pop("_srf_hip_training", None)
+    return state
+
+
+def _wants_grad(module, *tensors):
+    return bool(module.__dict__.get("_srf_hip_training")) and torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in list(tensors) + list(module.parameters()))
 
 
 def _no_random_dropout(module, p):
@@ -139,9 +174,26 @@ class TransformerLayer(nn.Module):
         self.ffn = ConvNormAct(emb_dim, emb_dim, 1, stride=1, groups=1)
         self.pos_enc = PositionalEncoding(d_model=emb_dim, dropout=dropout, max_len=max_len)
 
+    def __getstate__(self):
+        return _without_opt_in(self)
+
+    def enable_hip_training(self, flag=True):
+        """Opt this layer -- and the pos_enc and mha it owns -- into (flag=False: out of) a differentiable forward and return
+        self.  With it, forward(x, in_sums, in_gamma, in_beta) under autograd is one autograd node around the whole layer
+        (attention.transformer_layer_train): the inference kernel sequence with srf_mha_attention_lse and, in train() mode with
+        pos_enc.dropout.p > 0, srf_posenc_apply_dropout; the backward runs on HIP in the order of DESIGN.md section 16.2 and
+        returns gradients for the layer's 17 parameters, for x and for in_gamma / in_beta.  With p = 0 (or eval()) the output
+        has the inference forward's bits.  Without autograd the inference forward is untouched; without the opt-in train() with
+        p > 0 keeps raising.  The flag is a plain attribute: not in state_dict() and dropped from pickles."""
+        self.pos_enc.enable_hip_training(flag)
+        self.mha.enable_hip_training(flag)
+        return _set_opt_in(self, flag)
+
     def forward(self, x, in_sums=None, in_gamma=None, in_beta=None):
         """The kernel sequence srf_forward runs on the deepest level (stand-alone use / unit tests).  in_sums / in_gamma /
         in_beta: a GlobLN to apply to x on load (the level's lazy norm); returns the layer's output, out_norm applied."""
+        if _wants_grad(self, x, in_gamma, in_beta):
+            return attention.transformer_layer_train(self, _hip_float(x), in_sums, in_gamma, in_beta)
         _no_random_dropout(self, self.pos_enc.dropout.p)
         x = _hip_only(x)
         Bt, dev = x.shape[0], x.device
@@ -180,15 +232,29 @@ class AttentiveUConvBlock(nn.Module):
         self.res_conv = nn.Conv1d(in_channels, out_channels, 1)
         self.attention = TransformerLayer(in_channels, att_dims, n_heads, dropout=att_dropout, max_len=5000)
 
+    def __getstate__(self):
+        return _without_opt_in(self)
+
+    def enable_hip_training(self, flag=True):
+        """Opt this block -- and the TransformerLayer it owns -- into (flag=False: out of) a differentiable forward and return
+        self.  With it, forward(x) under autograd is one autograd node around the block (attention.uconv_block_train) whose
+        backward runs on HIP: gradients for every parameter of the block and for x; pos_enc.pe is a
+        buffer and gets none.  Dropout as in TransformerLayer.enable_hip_training.  Without autograd, and without the opt-in,
+        nothing changes.  The flag is a plain attribute: not in state_dict() and dropped from pickles."""
+        self.attention.enable_hip_training(flag)
+        return _set_opt_in(self, flag)
+
     def forward(self, x):
         """The kernel sequence srf_forward runs for one block (stand-alone use / unit tests)."""
         D = self.depth
         if D < 2:
             raise RuntimeError("AttentiveUConvBlock: upsampling_depth = %d; the HIP path needs at least 2 levels" % D)
+        if x.dim() == 3 and x.shape[-1] % (1 << (D - 1)):
+            raise RuntimeError("time length %d must be divisible by 2^(depth-1)" % x.shape[-1])
+        if _wants_grad(self, x):
+            return attention.uconv_block_train(self, _hip_float(x).contiguous())
         x = _hip_only(x)
         Bt, _, L = x.shape
-        if L % (1 << (D - 1)):
-            raise RuntimeError("time length %d must be divisible by 2^(depth-1)" % L)
         dev = x.device
         d = lambda p: p.detach()
         s_in = ops.new_sums(Bt, dev)
