@@ -27,6 +27,7 @@
  *   srf_forward (original) <- SuDORMRF.forward             models/sudormrf.py (srf_original_plan_create, below)
  *   srf_mha_attention      <- MHAttentionLayer.forward: softmax(q k^T / sqrt(d)) v per head, between its four Linear layers
  *   srf_mha_attention_lse / _bwd <- the same under autograd: forward that keeps the log-sum-exp, and its gradient
+ *   srf_mha_attention_ragged / _lse_ragged / _bwd_ragged <- the three with one query and one key length per example
  *   srf_stream_*           <- the same model run chunk by chunk with device-side state (ABI 17; row-table push: ABI 19)
  *   srf_zeroref_snr_*      <- PermInvariantSNRwithZeroRefs fwd/bwd (FUSS training loss)  losses/snr.py:13-142 (ABI 18)
  *   srf_stab_sisdr         <- StabilizedPermInvSISDRMetric.forward (FUSS validation)    losses/sisdr.py:460-576
@@ -998,6 +999,21 @@ int srf_feeder_normalize(const float* raw, const int* len, const float* stat, in
  *   (d > 128: one pass per output); a VALU form for every other d <= 1024 (mha_attention_bwd_dq_generic, _dkv_generic).
  *   Refused before the first launch (SRF_EINVAL, the message names the argument): a null pointer, the workspace included;
  *   sizes < 1; d > 1024 on the VALU form; more than 2^31 elements per example; Bt or H > 65535.  Any Lq, Lk >= 1, independent.
+ * srf_mha_attention_ragged, srf_mha_attention_lse_ragged, srf_mha_attention_bwd_ragged (additive; SRF_ABI_VERSION unchanged): the
+ *   three calls above over examples of unequal length.  Tensors, layout and workspace are the uniform calls': Lq and Lk stay
+ *   the ROW STRIDES; example b owns q_lengths[b] <= Lq queries and k_lengths[b] <= Lk keys.  q_lengths / k_lengths: HOST int
+ *   arrays of Bt entries (NULL = every example is full on that side), handed to the kernels by value in the launch arguments:
+ *   nothing is uploaded, nothing synchronises, Bt <= SRF_RAGGED_MAX_BATCH.  Per example b:
+ *     reads    nothing at queries >= q_lengths[b] (q, go, o, lse) and nothing at keys >= k_lengths[b] (k, v): may hold NaN;
+ *     writes   o, lse and gq are exact 0.f at queries >= q_lengths[b] up to Lq, gk and gv exact 0.f at keys >= k_lengths[b] up
+ *              to Lk; delta in the workspace is unspecified there;
+ *     cost     a block whose whole tile lies at or past the owned side's length stores its zeros and returns before any load;
+ *              the loop over the other side runs to that side's own length: work follows sum_b q_lengths[b] k_lengths[b];
+ *     bits     inside the lengths, those of the uniform call on example b alone with Lq = q_lengths[b], Lk = k_lengths[b]
+ *              (same arithmetic in the same order); deterministic, no float atomics, a masked position has P = 0 by selection.
+ *   Dispatch is the uniform predicate (srf_mha_attention_mfma_supported(d) and the kernel mode); profiler names are the uniform
+ *   ones + "_ragged".  Refused before the first launch (SRF_EINVAL, the message names the example and the argument): a length
+ *   < 1 or above its row stride, Bt > SRF_RAGGED_MAX_BATCH, and everything the uniform call refuses.
  * srf_posenc_apply: x[b, c, l] = norm(a)[b, c, l] + pe[l, c] (norm nullable = identity; prelu ignored); pe: [max_len, C].
  * srf_posenc_apply_dropout: srf_posenc_apply under the PositionalEncoding's dropout (train() mode):
  *   x[b, c, l] = keep(i) ? (norm(a)[b, c, l] + pe[l, c]) * inv_keep : 0.f, i = (b C + c) L + l as a 64-bit index.
@@ -1026,6 +1042,13 @@ size_t srf_mha_attention_bwd_workspace_bytes(int Bt, int H, int d, int Lq, int L
 int srf_mha_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
                           float* gq, float* gk, float* gv, void* workspace, int Bt, int H, int d, int Lq, int Lk, float scale,
                           void* stream);
+int srf_mha_attention_ragged(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq, int Lk,
+                             const int* q_lengths, const int* k_lengths, float scale, void* stream);
+int srf_mha_attention_lse_ragged(const float* q, const float* k, const float* v, float* o, float* lse, int Bt, int H, int d, int Lq,
+                                 int Lk, const int* q_lengths, const int* k_lengths, float scale, void* stream);
+int srf_mha_attention_bwd_ragged(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                                 float* gq, float* gk, float* gv, void* workspace, int Bt, int H, int d, int Lq, int Lk,
+                                 const int* q_lengths, const int* k_lengths, float scale, void* stream);
 int srf_posenc_apply(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L, int max_len,
                      void* stream);
 int srf_posenc_apply_dropout(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L, int max_len,

@@ -210,6 +210,10 @@ _PROTOS = {
     "srf_mha_attention_bwd_mfma_supported": (_i, [_i]),
     "srf_mha_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "srf_mha_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _vp]),
+    "srf_mha_attention_ragged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp]),
+    "srf_mha_attention_lse_ragged": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp]),
+    "srf_mha_attention_bwd_ragged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, C.c_float,
+                                          _vp]),
     "srf_posenc_apply": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _i, _vp]),
     "srf_posenc_apply_dropout": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _i, C.c_float, C.c_ulonglong, C.c_ulonglong,
                                       _vp]),

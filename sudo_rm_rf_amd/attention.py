@@ -7,7 +7,7 @@ import math
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, ragged
 from .ops import _chk, _norm
 
 
@@ -34,36 +34,73 @@ def _mha_scale(scale, d):
     return C.c_float(1.0 / math.sqrt(d) if scale is None else scale)
 
 
-def mha_attention(q, k, v, heads, scale=None, out=None):
+def _mha_lengths(what, Bt, q_lengths, k_lengths):
+    """The two host tables of a ragged call: -> (q table or None, k table or None, ragged?).  None = every example is full on
+    that side (NULL in C); the range of every entry and the batch cap are checked in C, before the first launch."""
+    tabs = []
+    for name, values in (("q_lengths", q_lengths), ("k_lengths", k_lengths)):
+        if values is None:
+            tabs.append(None)
+            continue
+        tab, n = ragged._table(values, name)
+        if n != Bt:
+            raise _lib.SrfError("%s: %d %s for a batch of %d" % (what, n, name, Bt))
+        tabs.append(tab)
+    return tabs[0], tabs[1], q_lengths is not None or k_lengths is not None
+
+
+def _host_lengths(values, what):
+    """lengths as a list of ints (None stays None); a device tensor is refused as ragged._table refuses it"""
+    return None if values is None else list(ragged._table(values, what)[0])
+
+
+def mha_attention(q, k, v, heads, scale=None, out=None, q_lengths=None, k_lengths=None):
     """q [Bt, H d, Lq], k / v [Bt, H d, Lk] -> [Bt, H d, Lq]: softmax(scale q^T k) v per (example, head); channel h d + j
     belongs to head h.  scale defaults to 1 / sqrt(d).
     Differentiable: with autograd on and q, k or v requiring grad the result carries a grad_fn whose backward is
-    mha_attention_bwd (the forward then is mha_attention_lse, same output bits); otherwise the plain launch, as ever."""
+    mha_attention_bwd (the forward then is mha_attention_lse, same output bits); otherwise the plain launch, as ever.
+    q_lengths / k_lengths (each a list or a CPU tensor of Bt entries, or None = full): the ragged form -- example b attends
+    from its first q_lengths[b] queries to its first k_lengths[b] keys; nothing past them is read, the output is exact 0 at
+    queries past q_lengths[b], and inside the lengths the bits are those of the call on the example's own slices.  Both None:
+    today's code path and bits."""
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         if out is not None:
             raise _lib.SrfError("mha_attention: out= cannot be combined with autograd")
-        return _MHAttention.apply(q, k, v, heads, scale)
+        return _MHAttention.apply(q, k, v, heads, scale, _host_lengths(q_lengths, "q_lengths"),
+                                  _host_lengths(k_lengths, "k_lengths"))
     dev = _chk(q, k, v, out)
     Bt, HD, d, Lq, Lk = _mha_shapes("mha_attention", q, k, v, heads)
+    ql, kl, is_ragged = _mha_lengths("mha_attention", Bt, q_lengths, k_lengths)
     if out is None:
         out = torch.empty((Bt, HD, Lq), dtype=torch.float32, device=dev)
+    if is_ragged:
+        rc = _lib.load().srf_mha_attention_ragged(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), Bt, heads, d, Lq, Lk, ql, kl,
+                                                  _mha_scale(scale, d), _lib.current_stream(dev))
+        _lib.check(rc, "srf_mha_attention_ragged")
+        return out
     rc = _lib.load().srf_mha_attention(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), Bt, heads, d, Lq, Lk,
                                        _mha_scale(scale, d), _lib.current_stream(dev))
     _lib.check(rc, "srf_mha_attention")
     return out
 
 
-def mha_attention_lse(q, k, v, heads, scale=None, out=None, lse=None):
+def mha_attention_lse(q, k, v, heads, scale=None, out=None, lse=None, q_lengths=None, k_lengths=None):
     """mha_attention that also returns lse [Bt, H, Lq], the per-query log-sum-exp of the scaled scores: -> (out, lse).  out has
-    mha_attention's bits."""
+    mha_attention's bits.  q_lengths / k_lengths: the ragged form (mha_attention); lse is exact 0 past q_lengths[b] too."""
     dev = _chk(q, k, v, out, lse)
     Bt, HD, d, Lq, Lk = _mha_shapes("mha_attention_lse", q, k, v, heads)
+    ql, kl, is_ragged = _mha_lengths("mha_attention_lse", Bt, q_lengths, k_lengths)
     if out is None:
         out = torch.empty((Bt, HD, Lq), dtype=torch.float32, device=dev)
     if lse is None:
         lse = torch.empty((Bt, heads, Lq), dtype=torch.float32, device=dev)
     elif lse.numel() != Bt * heads * Lq:
         raise _lib.SrfError("mha_attention_lse: lse has %d elements, [Bt, H, Lq] = %d" % (lse.numel(), Bt * heads * Lq))
+    if is_ragged:
+        rc = _lib.load().srf_mha_attention_lse_ragged(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), Bt, heads,
+                                                      d, Lq, Lk, ql, kl, _mha_scale(scale, d), _lib.current_stream(dev))
+        _lib.check(rc, "srf_mha_attention_lse_ragged")
+        return out, lse
     rc = _lib.load().srf_mha_attention_lse(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), Bt, heads, d, Lq, Lk,
                                            _mha_scale(scale, d), _lib.current_stream(dev))
     _lib.check(rc, "srf_mha_attention_lse")
@@ -74,11 +111,15 @@ def mha_attention_bwd_workspace_bytes(Bt, heads, d, Lq, Lk):
     return int(_lib.load().srf_mha_attention_bwd_workspace_bytes(Bt, heads, d, Lq, Lk))
 
 
-def mha_attention_bwd(q, k, v, o, lse, go, heads, scale=None, gq=None, gk=None, gv=None, workspace=None):
+def mha_attention_bwd(q, k, v, o, lse, go, heads, scale=None, gq=None, gk=None, gv=None, workspace=None, q_lengths=None,
+                      k_lengths=None):
     """The gradient of mha_attention: o, lse as mha_attention_lse returned them for (q, k, v, scale), go the gradient of o
-    -> (gq, gk, gv), written in full.  workspace: a tensor of at least mha_attention_bwd_workspace_bytes() (default: a new one)."""
+    -> (gq, gk, gv), written in full.  workspace: a tensor of at least mha_attention_bwd_workspace_bytes() (default: a new one).
+    q_lengths / k_lengths: the ragged form, for o and lse of the ragged forward with the same lengths -- go, o and lse are not
+    read past q_lengths[b]; gq is exact 0 past q_lengths[b], gk and gv past k_lengths[b]."""
     dev = _chk(q, k, v, o, lse, go, gq, gk, gv, workspace)
     Bt, HD, d, Lq, Lk = _mha_shapes("mha_attention_bwd", q, k, v, heads)
+    ql, kl, is_ragged = _mha_lengths("mha_attention_bwd", Bt, q_lengths, k_lengths)
     if o.shape != q.shape or go.shape != q.shape:
         raise _lib.SrfError("mha_attention_bwd: o %s / go %s differ from q %s" % (tuple(o.shape), tuple(go.shape), tuple(q.shape)))
     if lse.numel() != Bt * heads * Lq:
@@ -94,6 +135,12 @@ def mha_attention_bwd(q, k, v, o, lse, go, heads, scale=None, gq=None, gk=None, 
     gv = torch.empty_like(v) if gv is None else gv
     if gq.shape != q.shape or gk.shape != k.shape or gv.shape != v.shape:
         raise _lib.SrfError("mha_attention_bwd: gq / gk / gv do not have the shapes of q / k / v")
+    if is_ragged:
+        rc = _lib.load().srf_mha_attention_bwd_ragged(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), _lib.ptr(go),
+                                                      _lib.ptr(gq), _lib.ptr(gk), _lib.ptr(gv), _lib.ptr(workspace), Bt, heads, d, Lq,
+                                                      Lk, ql, kl, _mha_scale(scale, d), _lib.current_stream(dev))
+        _lib.check(rc, "srf_mha_attention_bwd_ragged")
+        return gq, gk, gv
     rc = _lib.load().srf_mha_attention_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), _lib.ptr(go),
                                            _lib.ptr(gq), _lib.ptr(gk), _lib.ptr(gv), _lib.ptr(workspace), Bt, heads, d, Lq, Lk,
                                            _mha_scale(scale, d), _lib.current_stream(dev))
@@ -105,42 +152,61 @@ class _MHAttention(torch.autograd.Function):
     """mha_attention under autograd: the forward with lse, the HIP backward.  Saves q, k, v, o, lse -- nothing of size Lq x Lk."""
 
     @staticmethod
-    def forward(ctx, q, k, v, heads, scale):
+    def forward(ctx, q, k, v, heads, scale, q_lengths=None, k_lengths=None):
         q, k, v = q.detach(), k.detach(), v.detach()
-        o, lse = mha_attention_lse(q, k, v, heads, scale)
+        o, lse = mha_attention_lse(q, k, v, heads, scale, q_lengths=q_lengths, k_lengths=k_lengths)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.heads, ctx.scale = heads, scale
+        ctx.heads, ctx.scale, ctx.lengths = heads, scale, (q_lengths, k_lengths)
         return o
 
     @staticmethod
     def backward(ctx, go):
         q, k, v, o, lse = ctx.saved_tensors
-        g = mha_attention_bwd(q, k, v, o, lse, go.contiguous(), ctx.heads, ctx.scale)
-        return tuple(t if need else None for t, need in zip(g, ctx.needs_input_grad[:3])) + (None, None)
+        g = mha_attention_bwd(q, k, v, o, lse, go.contiguous(), ctx.heads, ctx.scale, q_lengths=ctx.lengths[0],
+                              k_lengths=ctx.lengths[1])
+        return tuple(t if need else None for t, need in zip(g, ctx.needs_input_grad[:3])) + (None, None, None, None)
+
+
+def zero_past(x, lengths):
+    """x [Bt, C, L], in place: exact 0.f at positions >= lengths[b] of example b (None: nothing to do) -> x.  One strided fill per
+    shortened example on the current stream: nothing is uploaded, nothing synchronises."""
+    if lengths is not None:
+        for b, n in enumerate(lengths):
+            if n < x.shape[-1]:
+                x[b, :, n:].zero_()
+    return x
 
 
 class _MHALayer(torch.autograd.Function):
     """MHAttentionLayer.forward under autograd (enable_hip_training): the layer's own kernel sequence with the lse forward, and a
     backward of mha_attention_bwd, ops.pw_conv on the transposed weights (data gradients) and ops.pw_wgrad (weight and bias
-    gradients).  Saves the transposed inputs and q, k, v, o, lse -- nothing of size Lq x Lk."""
+    gradients).  Saves the transposed inputs and q, k, v, o, lse -- nothing of size Lq x Lk.
+    With lengths (the ragged layer): the projections stay uniform -- a column of a 1x1 convolution depends on that column alone
+    -- and the ragged attention sits between them.  The output is zeroed past q_lengths (it would hold O_proj.bias), and the
+    backward zeroes its copy of the incoming gradient there, so o, go, gq, gk and gv are all exact zeros past the lengths:
+    every weight-gradient GEMM multiplies the (finite) padding of its other operand by 0, every bias sum adds 0, and the data
+    gradients past the lengths are W^T 0 = 0."""
 
     @staticmethod
-    def forward(ctx, heads, scale, Q, K, V, wq, bq, wk, bk, wv, bv, wo, bo):
+    def forward(ctx, heads, scale, q_lengths, k_lengths, Q, K, V, wq, bq, wk, bk, wv, bv, wo, bo):
         t = lambda x: x.detach().transpose(1, 2).contiguous()
         xq = t(Q)
         xk = xq if K is Q else t(K)
         xv = xk if V is K else (xq if V is Q else t(V))
         q, k, v = ops.pw_conv(xq, wq, bq), ops.pw_conv(xk, wk, bk), ops.pw_conv(xv, wv, bv)
-        o, lse = mha_attention_lse(q, k, v, heads, scale)
+        o, lse = mha_attention_lse(q, k, v, heads, scale, q_lengths=q_lengths, k_lengths=k_lengths)
         ctx.save_for_backward(xq, xk, xv, q, k, v, o, lse, wq, wk, wv, wo)
-        ctx.heads, ctx.scale = heads, scale
-        return ops.pw_conv(o, wo, bo).transpose(1, 2).contiguous()
+        ctx.heads, ctx.scale, ctx.lengths = heads, scale, (q_lengths, k_lengths)
+        return zero_past(ops.pw_conv(o, wo, bo), q_lengths).transpose(1, 2).contiguous()
 
     @staticmethod
     def backward(ctx, gy):
         xq, xk, xv, q, k, v, o, lse, wq, wk, wv, wo = ctx.saved_tensors
-        need = ctx.needs_input_grad
+        need = ctx.needs_input_grad[2:]
+        q_lengths, k_lengths = ctx.lengths
         g = gy.transpose(1, 2).contiguous()
+        if q_lengths is not None:      # the gradient arriving at rows past q_lengths is ignored: zeroed in a copy of our own
+            g = zero_past(g.clone() if g.data_ptr() == gy.data_ptr() else g, q_lengths)
 
         def data(gout, w):       # the data gradient of y = W x + b: W^T gout
             wt = w.t().contiguous()
@@ -153,8 +219,8 @@ class _MHALayer(torch.autograd.Function):
             return ops.pw_wgrad(gout, x)
 
         dwo, dbo = wgrad(g, o)
-        gq, gk, gv = mha_attention_bwd(q, k, v, o, lse, data(g, wo), ctx.heads, ctx.scale)
-        grads = [None, None]
+        gq, gk, gv = mha_attention_bwd(q, k, v, o, lse, data(g, wo), ctx.heads, ctx.scale, q_lengths=q_lengths, k_lengths=k_lengths)
+        grads = [None, None, None, None]
         for i, (gp, w) in enumerate(((gq, wq), (gk, wk), (gv, wv))):
             grads.append(data(gp, w).transpose(1, 2).contiguous() if need[2 + i] else None)
         for gp, x in ((gq, xq), (gk, xk), (gv, xv)):
@@ -162,13 +228,14 @@ class _MHALayer(torch.autograd.Function):
         return tuple(grads) + (dwo, dbo)
 
 
-def mha_layer_train(layer, Q, K, V):
+def mha_layer_train(layer, Q, K, V, q_lengths=None, k_lengths=None):
     """MHAttentionLayer.forward of an opted-in layer under autograd (the attentive models v2 and v3 share the class):
     Q [batch, Lq, emb_dim], K / V [batch, Lk, emb_dim] -> [batch, Lq, emb_dim], differentiable in the eight projection parameters
-    and in Q, K, V."""
+    and in Q, K, V.  q_lengths / k_lengths: the ragged layer (MHAttentionLayer.forward)."""
     par = [p for m in (layer.Q_proj, layer.K_proj, layer.V_proj, layer.O_proj) for p in (m.weight, m.bias)]
     _chk(*par)
-    return _MHALayer.apply(layer.n_heads, layer.q_normalizer, Q, K, V, *par)
+    return _MHALayer.apply(layer.n_heads, layer.q_normalizer, _host_lengths(q_lengths, "q_lengths"),
+                           _host_lengths(k_lengths, "k_lengths"), Q, K, V, *par)
 
 
 def _u64(v):

@@ -51,21 +51,41 @@ struct MhaArgs {
 // The forms that also write the per-query log-sum-exp (srf_mha_attention_lse: what the backward recomputes P from) take the
 // [Bt, H, Lq] table as a trailing parameter PACK, the idiom of the ragged forms (srf_internal.h): empty in the plain
 // instantiations, whose arguments and code stay what they were.
+// The ragged forms (srf_mha_attention*_ragged) append two SrfFrames to that pack: example b owns q_len[b] <= Lq queries and
+// k_len[b] <= Lk keys.  Lq and Lk stay the ROW STRIDES of every address; every predicate and loop bound uses the example's own
+// count (qn, kn below -- the strides themselves in the uniform instantiations).  Nothing at or past a count is read; o and lse
+// are written as exact 0.f from qn up to the stride; a block whose whole tile lies at or past qn stores those zeros and returns
+// before any load, LDS write or MFMA.  Inside the counts the arithmetic and its order are the uniform kernel's on example b
+// alone with Lq = qn, Lk = kn: the tiles start at position 0 of the example either way.
 __device__ __forceinline__ void srf_mha_store_lse(size_t, float) {}   // (plain: never evaluated)
 __device__ __forceinline__ void srf_mha_store_lse(size_t at, float v, float* lse) { lse[at] = v; }
+__device__ __forceinline__ void srf_mha_store_lse(size_t, float, const SrfFrames&, const SrfFrames&) {}
+__device__ __forceinline__ void srf_mha_store_lse(size_t at, float v, float* lse, const SrfFrames&, const SrfFrames&) { lse[at] = v; }
 
-template <int NCH, typename... Lse>   // 32-channel chunks of the head dimension (d <= 32 NCH): 16 accumulator registers each
-__global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a, Lse... lse) {
+template <int NCH, typename... X>   // 32-channel chunks of the head dimension (d <= 32 NCH): 16 accumulator registers each
+__global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a, X... x) {
+  constexpr bool LSE = sizeof...(X) & 1, RAGGED = sizeof...(X) >= 2;
   __shared__ float Qs[NCH * 32 * 32];   // [channel][query], pre-scaled
   __shared__ float Vs[32 * 32];         // one 32-channel chunk of the key tile: [channel][key ^ channel]
   const int lane = threadIdx.x, col = lane & 31, half = lane >> 5;
   const int h = blockIdx.y, b = blockIdx.z, d = a.d, Lq = a.Lq, Lk = a.Lk;
+  const int qn = srf_mha_qlen(b, Lq, x...), kn = srf_mha_klen(b, Lk, x...);   // the example's own counts (block-uniform)
   const float* qh = a.q + (size_t)b * a.qs + (size_t)h * d * Lq;
   const float* kh = a.k + (size_t)b * a.ks + (size_t)h * d * Lk;
   const float* vh = a.v + (size_t)b * a.vs + (size_t)h * d * Lk;
   float* oh = a.o + (size_t)b * a.os + (size_t)h * d * Lq;
   const int ql = blockIdx.x * 32 + col;
-  const bool qok = ql < Lq;
+  const bool qok = ql < qn;
+  const bool wok = RAGGED ? ql < Lq : qok;   // ragged: the queries from qn up to the stride are written, as zeros
+  if constexpr (RAGGED) {
+    if ((int)blockIdx.x * 32 >= qn) {   // the whole tile lies past the example's end
+      if (wok) {
+        for (int j = half; j < d; j += 2) oh[(size_t)j * Lq + ql] = 0.f;
+        if (LSE && half == 0) srf_mha_store_lse(((size_t)b * a.H + h) * Lq + ql, 0.f, x...);
+      }
+      return;
+    }
+  }
 
   // (a uniform row pointer + one per-lane offset per operand: 32-bit offsets, checked by the launcher)
   for (int j0 = 0; j0 < NCH * 32; j0 += 2) {
@@ -80,9 +100,9 @@ __global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a, Lse... lse)
   float m = SRF_MHA_NEG_INF, den = 0.f;
   __syncthreads();
 
-  for (int kt = 0; kt < Lk; kt += 32) {
+  for (int kt = 0; kt < kn; kt += 32) {
     const int key = kt + col;
-    const bool kok = key < Lk;
+    const bool kok = key < kn;
     const float* kp = kh + (size_t)half * Lk + key;   // (dereferenced under kok only)
     const float* vp = vh + (size_t)half * Lk + key;
     // ---- S^T = K^T Q, 16 contraction steps (32 channels) at a time
@@ -105,7 +125,7 @@ __global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a, Lse... lse)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int ki = kt + (r & 3) + 8 * (r >> 2) + 4 * half;
-      st[r] = ki < Lk ? st[r] : SRF_MHA_NEG_INF;
+      st[r] = ki < kn ? st[r] : SRF_MHA_NEG_INF;
       tmax = fmaxf(tmax, st[r]);
     }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
@@ -145,15 +165,15 @@ __global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a, Lse... lse)
     }
   }
   const float inv = 1.f / den;
-  if constexpr (sizeof...(Lse) > 0)
-    if (qok && half == 0) srf_mha_store_lse(((size_t)b * a.H + h) * Lq + ql, m + logf(den), lse...);
-  if (qok) {
+  if constexpr (LSE)
+    if (wok && half == 0) srf_mha_store_lse(((size_t)b * a.H + h) * Lq + ql, (RAGGED && !qok) ? 0.f : m + logf(den), x...);
+  if (wok) {
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int j = c * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if (j < d) oh[(size_t)j * Lq + ql] = acc[c][r] * inv;
+        if (j < d) oh[(size_t)j * Lq + ql] = (RAGGED && !qok) ? 0.f : acc[c][r] * inv;
       }
   }
 }
@@ -170,23 +190,32 @@ __device__ __forceinline__ float srf_mha_wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-template <typename... Lse>
-__global__ __launch_bounds__(256) void srf_mha_generic_kernel(MhaArgs a, Lse... lse) {
+template <typename... X>   // (the pack and the ragged contract: srf_mha_mfma_kernel above)
+__global__ __launch_bounds__(256) void srf_mha_generic_kernel(MhaArgs a, X... x) {
+  constexpr bool LSE = sizeof...(X) & 1, RAGGED = sizeof...(X) >= 2;
   const int lane = threadIdx.x & 63;
   const int ql = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int h = blockIdx.y, b = blockIdx.z, d = a.d, Lq = a.Lq, Lk = a.Lk;
   if (ql >= Lq) return;   // (wavefront-uniform; the kernel has no block-wide barrier)
+  const int qn = srf_mha_qlen(b, Lq, x...), kn = srf_mha_klen(b, Lk, x...);   // the example's own counts
   const float* qh = a.q + (size_t)b * a.qs + (size_t)h * d * Lq + ql;
   const float* kh = a.k + (size_t)b * a.ks + (size_t)h * d * Lk;
   const float* vh = a.v + (size_t)b * a.vs + (size_t)h * d * Lk;
   float* oh = a.o + (size_t)b * a.os + (size_t)h * d * Lq + ql;
+  if constexpr (RAGGED) {
+    if (ql >= qn) {   // a query past the example's end: zeros, nothing read
+      for (int j = lane; j < d; j += 64) oh[(size_t)j * Lq] = 0.f;
+      if (LSE && lane == 0) srf_mha_store_lse(((size_t)b * a.H + h) * Lq + ql, 0.f, x...);
+      return;
+    }
+  }
   float acc[SRF_MHA_GEN_T];
 #pragma unroll
   for (int t = 0; t < SRF_MHA_GEN_T; ++t) acc[t] = 0.f;
   float m = SRF_MHA_NEG_INF, den = 0.f;
-  for (int kt = 0; kt < Lk; kt += 64) {
+  for (int kt = 0; kt < kn; kt += 64) {
     const int key = kt + lane;
-    const bool kok = key < Lk;
+    const bool kok = key < kn;
     float s = 0.f;
     if (kok)
       for (int j = 0; j < d; ++j) s = fmaf(qh[(size_t)j * Lq] * a.scale, kh[(size_t)j * Lk + key], s);
@@ -198,7 +227,7 @@ __global__ __launch_bounds__(256) void srf_mha_generic_kernel(MhaArgs a, Lse... 
     m = mn;
 #pragma unroll
     for (int t = 0; t < SRF_MHA_GEN_T; ++t) acc[t] *= alpha;
-    const int nk = Lk - kt < 64 ? Lk - kt : 64;
+    const int nk = kn - kt < 64 ? kn - kt : 64;
     for (int kk = 0; kk < nk; ++kk) {
       const float pk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), kk));
 #pragma unroll
@@ -209,8 +238,8 @@ __global__ __launch_bounds__(256) void srf_mha_generic_kernel(MhaArgs a, Lse... 
     }
   }
   const float inv = 1.f / den;
-  if constexpr (sizeof...(Lse) > 0)
-    if (lane == 0) srf_mha_store_lse(((size_t)b * a.H + h) * Lq + ql, m + logf(den), lse...);
+  if constexpr (LSE)
+    if (lane == 0) srf_mha_store_lse(((size_t)b * a.H + h) * Lq + ql, m + logf(den), x...);
 #pragma unroll
   for (int t = 0; t < SRF_MHA_GEN_T; ++t) {
     const int j = lane + 64 * t;
@@ -223,22 +252,22 @@ extern "C" int srf_mha_attention_mfma_supported(int d) {
   return srf_kernel_mode() != 1 && d % 16 == 0 && d >= 16 && d <= 256;
 }
 
-// one dispatch for the plain and the lse forms: lse = the empty pack or one float*
-template <typename... Lse>
-static int srf_mha_launch(const MhaArgs& a, int Bt, hipStream_t st, const char* mfma_name, const char* generic_name, Lse... lse) {
+// one dispatch for the plain, the lse and the ragged forms: x = the kernels' pack ([float* lse] [SrfFrames, SrfFrames])
+template <typename... X>
+static int srf_mha_launch(const MhaArgs& a, int Bt, hipStream_t st, const char* mfma_name, const char* generic_name, X... x) {
   const int H = a.H, d = a.d, Lq = a.Lq;
   if (srf_mha_attention_mfma_supported(d)) {
     const dim3 grid((Lq + 31) / 32, H, Bt), block(64);
-    if (d <= 32) hipLaunchKernelGGL((srf_mha_mfma_kernel<1, Lse...>), grid, block, 0, st, a, lse...);
-    else if (d <= 64) hipLaunchKernelGGL((srf_mha_mfma_kernel<2, Lse...>), grid, block, 0, st, a, lse...);
-    else if (d <= 128) hipLaunchKernelGGL((srf_mha_mfma_kernel<4, Lse...>), grid, block, 0, st, a, lse...);
-    else hipLaunchKernelGGL((srf_mha_mfma_kernel<8, Lse...>), grid, block, 0, st, a, lse...);
+    if (d <= 32) hipLaunchKernelGGL((srf_mha_mfma_kernel<1, X...>), grid, block, 0, st, a, x...);
+    else if (d <= 64) hipLaunchKernelGGL((srf_mha_mfma_kernel<2, X...>), grid, block, 0, st, a, x...);
+    else if (d <= 128) hipLaunchKernelGGL((srf_mha_mfma_kernel<4, X...>), grid, block, 0, st, a, x...);
+    else hipLaunchKernelGGL((srf_mha_mfma_kernel<8, X...>), grid, block, 0, st, a, x...);
     SRF_CHECK_LAUNCH(mfma_name, st);
     return SRF_OK;
   }
   SRF_CHECK_ARG(d <= 64 * SRF_MHA_GEN_T, "srf_mha_attention: head dimension d = %d exceeds the generic kernel's %d", d,
                 64 * SRF_MHA_GEN_T);
-  hipLaunchKernelGGL((srf_mha_generic_kernel<Lse...>), dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a, lse...);
+  hipLaunchKernelGGL((srf_mha_generic_kernel<X...>), dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a, x...);
   SRF_CHECK_LAUNCH(generic_name, st);
   return SRF_OK;
 }
@@ -281,6 +310,69 @@ extern "C" int srf_mha_attention_lse(const float* q, const float* k, const float
   SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_lse: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
   const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
   return srf_mha_attention_lse_strided(q, k, v, o, lse, sq, sk, sk, sq, Bt, H, d, Lq, Lk, scale, (hipStream_t)stream);
+}
+
+// ---- ragged forms: the uniform checks, then the two tables (NULL = every example full on that side), then the same dispatch
+int srf_mha_ragged_tables(const char* fn, int Bt, int Lq, int Lk, const int* q_lengths, const int* k_lengths, SrfFrames* qf,
+                          SrfFrames* kf) {
+  SRF_CHECK_ARG(Bt >= 1 && Bt <= SRF_RAGGED_MAX_BATCH, "%s: a ragged batch holds 1..%d examples (got Bt = %d)", fn,
+                SRF_RAGGED_MAX_BATCH, Bt);
+  const int* given[2] = {q_lengths, k_lengths};
+  const int stride[2] = {Lq, Lk};
+  SrfFrames* out[2] = {qf, kf};
+  for (int s = 0; s < 2; ++s) {
+    for (int b = 0; b < SRF_RAGGED_MAX_BATCH; ++b) out[s]->n[b] = 0;
+    for (int b = 0; b < Bt; ++b) {
+      const int n = given[s] ? given[s][b] : stride[s];
+      SRF_CHECK_ARG(n >= 1 && n <= stride[s], "%s: example %d has %s = %d (allowed: 1..%s = %d)", fn, b,
+                    s ? "k_lengths[b]" : "q_lengths[b]", n, s ? "Lk" : "Lq", stride[s]);
+      out[s]->n[b] = n;
+    }
+  }
+  return SRF_OK;
+}
+
+int srf_mha_attention_ragged_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os,
+                                     int Bt, int H, int d, int Lq, int Lk, const int* q_lengths, const int* k_lengths, float scale,
+                                     hipStream_t st) {
+  int rc = srf_mha_check(q, k, v, o, Bt, H, d, Lq, Lk);
+  if (rc != SRF_OK) return rc;
+  SrfFrames qf, kf;
+  rc = srf_mha_ragged_tables("srf_mha_attention_ragged", Bt, Lq, Lk, q_lengths, k_lengths, &qf, &kf);
+  if (rc != SRF_OK) return rc;
+  return srf_mha_launch(MhaArgs{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale}, Bt, st, "mha_attention_mfma_ragged",
+                        "mha_attention_generic_ragged", qf, kf);
+}
+
+int srf_mha_attention_lse_ragged_strided(const float* q, const float* k, const float* v, float* o, float* lse, long qs, long ks,
+                                         long vs, long os, int Bt, int H, int d, int Lq, int Lk, const int* q_lengths,
+                                         const int* k_lengths, float scale, hipStream_t st) {
+  int rc = srf_mha_check(q, k, v, o, Bt, H, d, Lq, Lk);
+  if (rc != SRF_OK) return rc;
+  SRF_CHECK_ARG(lse, "srf_mha_attention_lse_ragged: lse is null");
+  SrfFrames qf, kf;
+  rc = srf_mha_ragged_tables("srf_mha_attention_lse_ragged", Bt, Lq, Lk, q_lengths, k_lengths, &qf, &kf);
+  if (rc != SRF_OK) return rc;
+  return srf_mha_launch(MhaArgs{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale}, Bt, st, "mha_attention_lse_mfma_ragged",
+                        "mha_attention_lse_generic_ragged", lse, qf, kf);
+}
+
+extern "C" int srf_mha_attention_ragged(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq,
+                                        int Lk, const int* q_lengths, const int* k_lengths, float scale, void* stream) {
+  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_ragged: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
+  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
+  return srf_mha_attention_ragged_strided(q, k, v, o, sq, sk, sk, sq, Bt, H, d, Lq, Lk, q_lengths, k_lengths, scale,
+                                          (hipStream_t)stream);
+}
+
+extern "C" int srf_mha_attention_lse_ragged(const float* q, const float* k, const float* v, float* o, float* lse, int Bt, int H,
+                                            int d, int Lq, int Lk, const int* q_lengths, const int* k_lengths, float scale,
+                                            void* stream) {
+  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_lse_ragged: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq,
+                Lk);
+  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
+  return srf_mha_attention_lse_ragged_strided(q, k, v, o, lse, sq, sk, sk, sq, Bt, H, d, Lq, Lk, q_lengths, k_lengths, scale,
+                                              (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -33,6 +33,14 @@
 //   for gK / gV, a lane per other-side position for the scores and a lane per channel for the sums (v_readlane), plain FMA.
 // Edges, as in the forward: every global access is one dword wide and predicated; keys >= Lk, queries >= Lq and channels >= d
 // read nothing, count as 0 and store nothing; a masked position has P = 0 EXACTLY (selected, never exp of a stale register).
+//
+// Ragged forms (srf_mha_attention_bwd_ragged): every kernel takes a trailing parameter pack, empty in the uniform instantiations
+// (arguments and code unchanged) and (SrfFrames q_len, SrfFrames k_len) -- delta: q_len alone -- in the ragged ones.  Lq and Lk
+// stay the row strides of every address; every predicate and loop bound uses example b's own counts.  Nothing at or past a count
+// is read (q, go, o, lse, delta on the query side; k, v on the key side); gq, gk and gv are written as exact 0.f from the count
+// up to the stride, delta is left alone there; a block whose whole owned tile lies past the count stores its zeros and returns
+// before any load, LDS write or MFMA, and the loop over the other side runs to that side's own count.  Inside the counts the
+// arithmetic and its order are those of the uniform kernel on example b alone.
 #include "srf_internal.h"
 
 typedef float srf_f32x16 __attribute__((ext_vector_type(16)));
@@ -46,11 +54,15 @@ struct MhaBwdArgs {
 };
 
 // ---- delta[b, h, lq] = sum_j gO[j, lq] O[j, lq]: one thread per query, channels in order
+template <typename... R>
 __global__ __launch_bounds__(256) void srf_mha_bwd_delta_kernel(const float* __restrict__ o, const float* __restrict__ go,
-                                                                float* __restrict__ delta, long os, long gos, int H, int d, int Lq) {
+                                                                float* __restrict__ delta, long os, long gos, int H, int d, int Lq,
+                                                                R... qlen) {
   const int lq = blockIdx.x * 256 + threadIdx.x;
   const int h = blockIdx.y, b = blockIdx.z;
   if (lq >= Lq) return;
+  if constexpr (sizeof...(R) > 0)
+    if (lq >= srf_frames_of(b, qlen...)) return;   // (past the example's end: nothing read, delta left as it is)
   const float* oh = o + (size_t)b * os + (size_t)h * d * Lq + lq;
   const float* gh = go + (size_t)b * gos + (size_t)h * d * Lq + lq;
   float s = 0.f;
@@ -96,8 +108,9 @@ __device__ __forceinline__ void srf_mha_bwd_accumulate(srf_f32x16& acc, const sr
   }
 }
 
-template <int NCH, int ROLE>   // 32-channel chunks of the head dimension (d <= 32 NCH): 16 accumulator registers each per output
-__global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a) {
+template <int NCH, int ROLE, typename... R>   // 32-channel chunks of the head dimension (d <= 32 NCH): 16 accumulator registers each per output
+__global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a, R... r2) {
+  constexpr bool RAGGED = sizeof...(R) > 0;
   constexpr bool OQ = ROLE == SRF_MHA_BWD_Q;                                // the owned side is the query
   constexpr bool WANT_DS = ROLE != SRF_MHA_BWD_V;                            // gQ / gK: needs dP and dS
   constexpr bool WANT_P = ROLE == SRF_MHA_BWD_KV || ROLE == SRF_MHA_BWD_V;   // gV
@@ -105,7 +118,10 @@ __global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a) {
   __shared__ float Ys[32 * 32];         // one 32-channel chunk of the other side's tile: [channel][position ^ channel]
   const int lane = threadIdx.x, col = lane & 31, half = lane >> 5;
   const int h = blockIdx.y, b = blockIdx.z, d = a.d;
-  const int Lo = OQ ? a.Lq : a.Lk, Lt = OQ ? a.Lk : a.Lq;   // owned / other length
+  const int Lo = OQ ? a.Lq : a.Lk, Lt = OQ ? a.Lk : a.Lq;   // owned / other row stride
+  // owned / other count: the example's own (block-uniform), the strides themselves in the uniform instantiation
+  const int no = OQ ? srf_mha_qlen(b, a.Lq, r2...) : srf_mha_klen(b, a.Lk, r2...);
+  const int nt = OQ ? srf_mha_klen(b, a.Lk, r2...) : srf_mha_qlen(b, a.Lq, r2...);
   const float* qh = a.q + (size_t)b * a.qs + (size_t)h * d * a.Lq;
   const float* kh = a.k + (size_t)b * a.ks + (size_t)h * d * a.Lk;
   const float* vh = a.v + (size_t)b * a.vs + (size_t)h * d * a.Lk;
@@ -115,7 +131,21 @@ __global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a) {
   const float *x1 = OQ ? qh : kh, *x2 = OQ ? gh : vh, *y1 = OQ ? kh : qh, *y2 = OQ ? vh : gh;
   const float sx = OQ ? a.scale : 1.f, sy = OQ ? 1.f : a.scale;   // q is scaled before the product, as in the forward
   const int oi = blockIdx.x * 32 + col;
-  const bool ook = oi < Lo;
+  const bool ook = oi < no;
+  const bool wok = RAGGED ? oi < Lo : ook;   // ragged: the owned positions from the count up to the stride are written, as zeros
+  if constexpr (RAGGED) {
+    if ((int)blockIdx.x * 32 >= no) {   // the whole owned tile lies past the example's end
+      if (wok) {
+        float* gd = (OQ ? a.gq + (size_t)b * a.gqs : a.gk + (size_t)b * a.gks) + (size_t)h * d * Lo + oi;
+        float* gp = a.gv + (size_t)b * a.gvs + (size_t)h * d * Lo + oi;
+        for (int j = half; j < d; j += 2) {
+          if constexpr (WANT_DS) gd[(size_t)j * Lo] = 0.f;
+          if constexpr (WANT_P) gp[(size_t)j * Lo] = 0.f;
+        }
+      }
+      return;
+    }
+  }
   const int nch = (d + 31) / 32;   // chunks in use (<= NCH)
 
   // (a uniform row pointer + one per-lane offset per operand: 32-bit offsets, checked by the launcher)
@@ -139,9 +169,9 @@ __global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a) {
   }
   __syncthreads();
 
-  for (int t0 = 0; t0 < Lt; t0 += 32) {
+  for (int t0 = 0; t0 < nt; t0 += 32) {
     const int ti = t0 + col;
-    const bool tok = ti < Lt;
+    const bool tok = ti < nt;
     const float* y1p = y1 + (size_t)half * Lt + ti;   // (dereferenced under tok only)
     const float* y2p = y2 + (size_t)half * Lt + ti;
     // ---- T = Y1^T X1 (S^T in role Q, S on the key side), 16 contraction steps (32 channels) at a time
@@ -174,7 +204,7 @@ __global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int ri = t0 + (r & 3) + 8 * (r >> 2) + 4 * half;   // the other-side position register r holds
-      const bool rok = ri < Lt;
+      const bool rok = ri < nt;
       float l = lse_l, dl = delta_l;
       if (!OQ) {
         l = rok ? lse[ri] : 0.f;
@@ -193,7 +223,7 @@ __global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a) {
       }
     }
   }
-  if (ook) {
+  if (wok) {
     float* gd = (OQ ? a.gq + (size_t)b * a.gqs : a.gk + (size_t)b * a.gks) + (size_t)h * d * Lo + oi;
     float* gp = a.gv + (size_t)b * a.gvs + (size_t)h * d * Lo + oi;
 #pragma unroll
@@ -202,8 +232,8 @@ __global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a) {
       for (int r = 0; r < 16; ++r) {
         const int j = c * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
         if (j < d) {
-          if constexpr (WANT_DS) gd[(size_t)j * Lo] = accd[c][r] * a.scale;
-          if constexpr (WANT_P) gp[(size_t)j * Lo] = accp[c][r];
+          if constexpr (WANT_DS) gd[(size_t)j * Lo] = (RAGGED && !ook) ? 0.f : accd[c][r] * a.scale;
+          if constexpr (WANT_P) gp[(size_t)j * Lo] = (RAGGED && !ook) ? 0.f : accp[c][r];
         }
       }
   }
@@ -212,11 +242,20 @@ __global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a) {
 // ---- generic form
 #define SRF_MHA_GEN_T 16   // channels per lane: d <= 64 * 16
 // gQ: one wavefront per query, a lane per key for dS, a lane per channel for the sum over keys
-__global__ __launch_bounds__(256) void srf_mha_bwd_dq_generic_kernel(MhaBwdArgs a) {
+template <typename... R>
+__global__ __launch_bounds__(256) void srf_mha_bwd_dq_generic_kernel(MhaBwdArgs a, R... r2) {
   const int lane = threadIdx.x & 63;
   const int ql = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int h = blockIdx.y, b = blockIdx.z, d = a.d, Lq = a.Lq, Lk = a.Lk;
   if (ql >= Lq) return;   // (wavefront-uniform; the kernel has no block-wide barrier)
+  const int kn = srf_mha_klen(b, Lk, r2...);   // the example's own key count
+  if constexpr (sizeof...(R) > 0) {
+    if (ql >= srf_mha_qlen(b, Lq, r2...)) {   // a query past the example's end: zeros, nothing read
+      float* gz = a.gq + (size_t)b * a.gqs + (size_t)h * d * Lq + ql;
+      for (int j = lane; j < d; j += 64) gz[(size_t)j * Lq] = 0.f;
+      return;
+    }
+  }
   const float* qh = a.q + (size_t)b * a.qs + (size_t)h * d * Lq + ql;
   const float* gh = a.go + (size_t)b * a.gos + (size_t)h * d * Lq + ql;
   const float* kh = a.k + (size_t)b * a.ks + (size_t)h * d * Lk;
@@ -225,10 +264,10 @@ __global__ __launch_bounds__(256) void srf_mha_bwd_dq_generic_kernel(MhaBwdArgs 
   float acc[SRF_MHA_GEN_T];
 #pragma unroll
   for (int t = 0; t < SRF_MHA_GEN_T; ++t) acc[t] = 0.f;
-  for (int kt = 0; kt < Lk; kt += 64) {
+  for (int kt = 0; kt < kn; kt += 64) {
     const int key = kt + lane;
     float ds = 0.f;   // masked keys: 0
-    if (key < Lk) {
+    if (key < kn) {
       float s = 0.f, dp = 0.f;
       for (int j = 0; j < d; ++j) {
         s = fmaf(qh[(size_t)j * Lq] * a.scale, kh[(size_t)j * Lk + key], s);
@@ -236,7 +275,7 @@ __global__ __launch_bounds__(256) void srf_mha_bwd_dq_generic_kernel(MhaBwdArgs 
       }
       ds = expf(s - lse) * (dp - delta);
     }
-    const int nk = Lk - kt < 64 ? Lk - kt : 64;
+    const int nk = kn - kt < 64 ? kn - kt : 64;
     for (int kk = 0; kk < nk; ++kk) {
       const float dk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ds), kk));
 #pragma unroll
@@ -255,11 +294,21 @@ __global__ __launch_bounds__(256) void srf_mha_bwd_dq_generic_kernel(MhaBwdArgs 
 }
 
 // gK, gV: one wavefront per key, a lane per query for P and dS, a lane per channel for the sums over queries
-__global__ __launch_bounds__(256) void srf_mha_bwd_dkv_generic_kernel(MhaBwdArgs a) {
+template <typename... R>
+__global__ __launch_bounds__(256) void srf_mha_bwd_dkv_generic_kernel(MhaBwdArgs a, R... r2) {
   const int lane = threadIdx.x & 63;
   const int kl = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int h = blockIdx.y, b = blockIdx.z, d = a.d, Lq = a.Lq, Lk = a.Lk;
   if (kl >= Lk) return;   // (wavefront-uniform; the kernel has no block-wide barrier)
+  const int qn = srf_mha_qlen(b, Lq, r2...);   // the example's own query count
+  if constexpr (sizeof...(R) > 0) {
+    if (kl >= srf_mha_klen(b, Lk, r2...)) {   // a key past the example's end: zeros, nothing read
+      float* gzk = a.gk + (size_t)b * a.gks + (size_t)h * d * Lk + kl;
+      float* gzv = a.gv + (size_t)b * a.gvs + (size_t)h * d * Lk + kl;
+      for (int j = lane; j < d; j += 64) gzk[(size_t)j * Lk] = gzv[(size_t)j * Lk] = 0.f;
+      return;
+    }
+  }
   const float* qh = a.q + (size_t)b * a.qs + (size_t)h * d * Lq;
   const float* gh = a.go + (size_t)b * a.gos + (size_t)h * d * Lq;
   const float* kh = a.k + (size_t)b * a.ks + (size_t)h * d * Lk + kl;
@@ -269,10 +318,10 @@ __global__ __launch_bounds__(256) void srf_mha_bwd_dkv_generic_kernel(MhaBwdArgs
   float acck[SRF_MHA_GEN_T], accv[SRF_MHA_GEN_T];
 #pragma unroll
   for (int t = 0; t < SRF_MHA_GEN_T; ++t) acck[t] = accv[t] = 0.f;
-  for (int qt = 0; qt < Lq; qt += 64) {
+  for (int qt = 0; qt < qn; qt += 64) {
     const int ql = qt + lane;
     float p = 0.f, ds = 0.f;   // queries >= Lq: 0
-    if (ql < Lq) {
+    if (ql < qn) {
       float s = 0.f, dp = 0.f;
       for (int j = 0; j < d; ++j) {
         s = fmaf(qh[(size_t)j * Lq + ql] * a.scale, kh[(size_t)j * Lk], s);
@@ -281,7 +330,7 @@ __global__ __launch_bounds__(256) void srf_mha_bwd_dkv_generic_kernel(MhaBwdArgs
       p = expf(s - lse[ql]);
       ds = p * (dp - delta[ql]);
     }
-    const int nq = Lq - qt < 64 ? Lq - qt : 64;
+    const int nq = qn - qt < 64 ? qn - qt : 64;
     for (int qq = 0; qq < nq; ++qq) {
       const float pq = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), qq));
       const float dq = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ds), qq));
@@ -319,19 +368,18 @@ extern "C" size_t srf_mha_attention_bwd_workspace_bytes(int Bt, int H, int d, in
 }
 
 // (role KV has no <8> instantiation: the caller sends d > 128 to roles V and K)
-template <int ROLE>
-static void srf_mha_bwd_mfma_launch(const MhaBwdArgs& a, int Bt, hipStream_t st) {
+template <int ROLE, typename... R>
+static void srf_mha_bwd_mfma_launch(const MhaBwdArgs& a, int Bt, hipStream_t st, const R&... r2) {
   const int L = ROLE == SRF_MHA_BWD_Q ? a.Lq : a.Lk;
   const dim3 grid((L + 31) / 32, a.H, Bt), block(64);
-  if (a.d <= 32) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<1, ROLE>), grid, block, 0, st, a);
-  else if (a.d <= 64) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<2, ROLE>), grid, block, 0, st, a);
-  else if (a.d <= 128) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<4, ROLE>), grid, block, 0, st, a);
-  else if constexpr (ROLE != SRF_MHA_BWD_KV) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<8, ROLE>), grid, block, 0, st, a);
+  if (a.d <= 32) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<1, ROLE, R...>), grid, block, 0, st, a, r2...);
+  else if (a.d <= 64) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<2, ROLE, R...>), grid, block, 0, st, a, r2...);
+  else if (a.d <= 128) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<4, ROLE, R...>), grid, block, 0, st, a, r2...);
+  else if constexpr (ROLE != SRF_MHA_BWD_KV) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<8, ROLE, R...>), grid, block, 0, st, a, r2...);
 }
 
-int srf_mha_attention_bwd_strided(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
-                                  float* gq, float* gk, float* gv, void* workspace, long qs, long ks, long vs, long os, long gos,
-                                  long gqs, long gks, long gvs, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
+static int srf_mha_bwd_check(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                             float* gq, float* gk, float* gv, void* workspace, int Bt, int H, int d, int Lq, int Lk) {
   SRF_CHECK_ARG(q && k && v && o && lse && go, "srf_mha_attention_bwd: null input (q, k, v, o, lse or go)");
   SRF_CHECK_ARG(gq && gk && gv, "srf_mha_attention_bwd: null output (gq, gk or gv)");
   SRF_CHECK_ARG(workspace, "srf_mha_attention_bwd: workspace is null (srf_mha_attention_bwd_workspace_bytes)");
@@ -342,11 +390,19 @@ int srf_mha_attention_bwd_strided(const float* q, const float* k, const float* v
   const bool mfma = srf_mha_attention_bwd_mfma_supported(d);
   SRF_CHECK_ARG(mfma || d <= 64 * SRF_MHA_GEN_T, "srf_mha_attention_bwd: head dimension d = %d exceeds the generic kernel's %d", d,
                 64 * SRF_MHA_GEN_T);
+  return SRF_OK;
+}
+
+int srf_mha_attention_bwd_strided(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
+                                  float* gq, float* gk, float* gv, void* workspace, long qs, long ks, long vs, long os, long gos,
+                                  long gqs, long gks, long gvs, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
+  const int rc = srf_mha_bwd_check(q, k, v, o, lse, go, gq, gk, gv, workspace, Bt, H, d, Lq, Lk);
+  if (rc != SRF_OK) return rc;
   float* delta = (float*)workspace;
   const MhaBwdArgs a{q, k, v, go, lse, delta, gq, gk, gv, qs, ks, vs, gos, gqs, gks, gvs, H, d, Lq, Lk, scale};
-  hipLaunchKernelGGL(srf_mha_bwd_delta_kernel, dim3((Lq + 255) / 256, H, Bt), dim3(256), 0, st, o, go, delta, os, gos, H, d, Lq);
+  hipLaunchKernelGGL(srf_mha_bwd_delta_kernel<>, dim3((Lq + 255) / 256, H, Bt), dim3(256), 0, st, o, go, delta, os, gos, H, d, Lq);
   SRF_CHECK_LAUNCH("mha_attention_bwd_delta", st);
-  if (mfma) {
+  if (srf_mha_attention_bwd_mfma_supported(d)) {
     srf_mha_bwd_mfma_launch<SRF_MHA_BWD_Q>(a, Bt, st);
     SRF_CHECK_LAUNCH("mha_attention_bwd_dq_mfma", st);
     if (d <= 128) {
@@ -360,11 +416,56 @@ int srf_mha_attention_bwd_strided(const float* q, const float* k, const float* v
     }
     return SRF_OK;
   }
-  hipLaunchKernelGGL(srf_mha_bwd_dq_generic_kernel, dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(srf_mha_bwd_dq_generic_kernel<>, dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a);
   SRF_CHECK_LAUNCH("mha_attention_bwd_dq_generic", st);
-  hipLaunchKernelGGL(srf_mha_bwd_dkv_generic_kernel, dim3((Lk + 3) / 4, H, Bt), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(srf_mha_bwd_dkv_generic_kernel<>, dim3((Lk + 3) / 4, H, Bt), dim3(256), 0, st, a);
   SRF_CHECK_LAUNCH("mha_attention_bwd_dkv_generic", st);
   return SRF_OK;
+}
+
+// the ragged form: the uniform checks, the two tables, then the same launches on the ragged instantiations
+int srf_mha_attention_bwd_ragged_strided(const float* q, const float* k, const float* v, const float* o, const float* lse,
+                                         const float* go, float* gq, float* gk, float* gv, void* workspace, long qs, long ks, long vs,
+                                         long os, long gos, long gqs, long gks, long gvs, int Bt, int H, int d, int Lq, int Lk,
+                                         const int* q_lengths, const int* k_lengths, float scale, hipStream_t st) {
+  int rc = srf_mha_bwd_check(q, k, v, o, lse, go, gq, gk, gv, workspace, Bt, H, d, Lq, Lk);
+  if (rc != SRF_OK) return rc;
+  SrfFrames qf, kf;
+  rc = srf_mha_ragged_tables("srf_mha_attention_bwd_ragged", Bt, Lq, Lk, q_lengths, k_lengths, &qf, &kf);
+  if (rc != SRF_OK) return rc;
+  float* delta = (float*)workspace;
+  const MhaBwdArgs a{q, k, v, go, lse, delta, gq, gk, gv, qs, ks, vs, gos, gqs, gks, gvs, H, d, Lq, Lk, scale};
+  hipLaunchKernelGGL(srf_mha_bwd_delta_kernel<SrfFrames>, dim3((Lq + 255) / 256, H, Bt), dim3(256), 0, st, o, go, delta, os, gos, H,
+                     d, Lq, qf);
+  SRF_CHECK_LAUNCH("mha_attention_bwd_delta_ragged", st);
+  if (srf_mha_attention_bwd_mfma_supported(d)) {
+    srf_mha_bwd_mfma_launch<SRF_MHA_BWD_Q>(a, Bt, st, qf, kf);
+    SRF_CHECK_LAUNCH("mha_attention_bwd_dq_mfma_ragged", st);
+    if (d <= 128) {
+      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_KV>(a, Bt, st, qf, kf);
+      SRF_CHECK_LAUNCH("mha_attention_bwd_dkv_mfma_ragged", st);
+    } else {
+      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_V>(a, Bt, st, qf, kf);
+      SRF_CHECK_LAUNCH("mha_attention_bwd_dv_mfma_ragged", st);
+      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_K>(a, Bt, st, qf, kf);
+      SRF_CHECK_LAUNCH("mha_attention_bwd_dk_mfma_ragged", st);
+    }
+    return SRF_OK;
+  }
+  hipLaunchKernelGGL((srf_mha_bwd_dq_generic_kernel<SrfFrames, SrfFrames>), dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a, qf, kf);
+  SRF_CHECK_LAUNCH("mha_attention_bwd_dq_generic_ragged", st);
+  hipLaunchKernelGGL((srf_mha_bwd_dkv_generic_kernel<SrfFrames, SrfFrames>), dim3((Lk + 3) / 4, H, Bt), dim3(256), 0, st, a, qf, kf);
+  SRF_CHECK_LAUNCH("mha_attention_bwd_dkv_generic_ragged", st);
+  return SRF_OK;
+}
+
+extern "C" int srf_mha_attention_bwd_ragged(const float* q, const float* k, const float* v, const float* o, const float* lse,
+                                            const float* go, float* gq, float* gk, float* gv, void* workspace, int Bt, int H, int d,
+                                            int Lq, int Lk, const int* q_lengths, const int* k_lengths, float scale, void* stream) {
+  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_bwd_ragged: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
+  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
+  return srf_mha_attention_bwd_ragged_strided(q, k, v, o, lse, go, gq, gk, gv, workspace, sq, sk, sk, sq, sq, sq, sk, sk, Bt, H, d,
+                                              Lq, Lk, q_lengths, k_lengths, scale, (hipStream_t)stream);
 }
 
 extern "C" int srf_mha_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse,

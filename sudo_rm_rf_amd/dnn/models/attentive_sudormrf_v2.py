@@ -120,7 +120,8 @@ def _hip_float(t):
 
 
 class MHAttentionLayer(nn.Module):
-    """Q / K / V / O projections around softmax attention; forward(Q, K, V) takes [batch, len, emb_dim] like the reference."""
+    """Q / K / V / O projections around softmax attention; forward(Q, K, V) takes [batch, len, emb_dim] like the reference.
+    forward(Q, K, V, q_lengths, k_lengths) is the ragged form: example b has q_lengths[b] real rows in Q and k_lengths[b] in K / V."""
 
     def __init__(self, emb_dim, d_model, n_heads, dropout=0.0):
         super().__init__()
@@ -151,16 +152,25 @@ class MHAttentionLayer(nn.Module):
             self.__dict__.pop("_srf_hip_training", None)
         return self
 
-    def forward(self, Q, K, V):
+    def forward(self, Q, K, V, q_lengths=None, k_lengths=None):
+        """q_lengths / k_lengths (each a list or a CPU tensor of `batch` entries, or None = full; both None: nothing changes):
+        a ragged batch.  Example b attends from its first q_lengths[b] rows of Q to its first k_lengths[b] rows of K / V -- the
+        ragged attention kernels between the unchanged projections -- and equals its own batch-1 call on the slices.  Output
+        rows at or past q_lengths[b] are exactly zero.  Under enable_hip_training() the gradient arriving at those rows is
+        ignored, Q / K / V get exactly zero gradient at or past their lengths, and the eight parameter gradients are the sum of
+        the examples' own batch-1 gradients; the padding must hold finite values and influences nothing."""
         _no_random_dropout(self, self.dropout.p)
         if self.__dict__.get("_srf_hip_training") and torch.is_grad_enabled() and any(
                 t.requires_grad for t in [Q, K, V] + list(self.parameters())):
-            return attention.mha_layer_train(self, *(_hip_float(x) for x in (Q, K, V)))
+            return attention.mha_layer_train(self, *(_hip_float(x) for x in (Q, K, V)), q_lengths=q_lengths, k_lengths=k_lengths)
         t = lambda x: _hip_only(x).transpose(1, 2).contiguous()
         lin = lambda m, x: ops.pw_conv(x, m.weight.detach(), m.bias.detach())
         o = attention.mha_attention(lin(self.Q_proj, t(Q)), lin(self.K_proj, t(K)), lin(self.V_proj, t(V)), self.n_heads,
-                                    self.q_normalizer)
-        return lin(self.O_proj, o).transpose(1, 2).contiguous()
+                                    self.q_normalizer, q_lengths=q_lengths, k_lengths=k_lengths)
+        if q_lengths is None:
+            return lin(self.O_proj, o).transpose(1, 2).contiguous()
+        # (past q_lengths o is 0 and the projection would leave O_proj.bias there)
+        return attention.zero_past(lin(self.O_proj, o), attention._host_lengths(q_lengths, "q_lengths")).transpose(1, 2).contiguous()
 
 
 class TransformerLayer(nn.Module):
@@ -381,7 +391,8 @@ class SuDORMRF(nn.Module):
 
     def forward_ragged(self, input_wav, lengths):
         raise NotImplementedError("the attentive model has no ragged kernels: run the utterances one by one "
-                                  "(pipeline.separate_list does)")
+                                  "(pipeline.separate_list does).  Attention alone takes a ragged batch: "
+                                  "MHAttentionLayer.forward(Q, K, V, q_lengths, k_lengths).")
 
     def pad_to_appropriate_length(self, x):
         """Kept for API parity: up to a multiple of lcm(K // 2, 2^D), only when the length is not one already.  The HIP path

@@ -227,7 +227,8 @@ class SuDORMRF(nn.Module):
 
     def forward_ragged(self, input_wav, lengths):
         raise NotImplementedError("the attentive model has no ragged kernels: run the utterances one by one "
-                                  "(pipeline.separate_list does)")
+                                  "(pipeline.separate_list does).  Attention alone takes a ragged batch: "
+                                  "MHAttentionLayer.forward(Q, K, V, q_lengths, k_lengths).")
 
     def pad_to_appropriate_length(self, x):
         """Kept for API parity: up to a multiple of lcm(K // 2, 2^D), only when the length is not one already.  The HIP path

@@ -7,7 +7,8 @@ device assembly and compare, kernel by kernel, the instruction streams of every 
 The ragged forms are instantiations of the uniform kernels' templates with a trailing parameter pack (empty in the uniform
 instantiations), so a uniform kernel's mangled name gains an empty pack ("J E" in the template arguments, "DpT<n>_" in the
 parameter list); names are compared with that removed -- also where the pack is the ONLY template parameter, i.e. the old
-tree's kernel was not a template at all.  Labels are renumbered; comments and directives are dropped."""
+tree's kernel was not a template at all (a template's own name is a substitution candidate of its mangled name, so the
+S<n>_ back-references of its parameter list are shifted back by one).  Labels are renumbered; comments and directives are dropped."""
 import os
 import re
 import subprocess
@@ -17,6 +18,26 @@ import tempfile
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT = ["srf_encoder.hip", "srf_elementwise.hip", "srf_pyramid.hip", "srf_pyramid_reg.hip", "srf_pwconv_x3w.hip", "srf_pwconv_x3f.hip",
            "srf_tac.hip", "srf_pwconv_small.hip"]
+
+
+_B36 = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ"
+
+
+def _unshift(m):
+    """A template's name is the first substitution candidate of its mangled name, a plain function's is not: S_ / S0_ / S1_ ...
+    in the parameter list of the templated form are S<one less>_ in the plain form (base-36 sequence ids, S_ before S0_)."""
+    seq = m.group(1)
+    if seq == "":
+        return m.group(0)                                                      # (the template itself: not in a parameter list)
+    n = int(seq, 36) - 1
+    if n < 0:
+        return "S_"
+    digits = ""
+    while True:
+        digits = _B36[n % 36] + digits
+        n //= 36
+        if not n:
+            return "S%s_" % digits
 
 
 def kernels(asm):
@@ -31,7 +52,10 @@ def kernels(asm):
         t = line.split(";")[0].strip()
         if t.startswith(".Lfunc_end"):
             key = re.sub(r"JE(E.*?)DpT\d*_$", r"\1", name)
-            out[key.replace("IEv", "", 1) if key != name else key] = cur      # (a plain kernel that became a template: "I E v")
+            if key != name and "IEv" in key:                                   # (a plain kernel that became a template: "I E v")
+                head, tail = key.split("IEv", 1)
+                key = head + re.sub(r"S([0-9A-Z]*)_", _unshift, tail)
+            out[key] = cur
             cur = None
         elif t.startswith(".LBB"):
             cur.append(re.sub(r"\d+_", "_", t))
