@@ -34,19 +34,23 @@ def _mha_scale(scale, d):
     return C.c_float(1.0 / math.sqrt(d) if scale is None else scale)
 
 
-def _mha_lengths(what, Bt, q_lengths, k_lengths):
-    """The two host tables of a ragged call: -> (q table or None, k table or None, ragged?).  None = every example is full on
-    that side (NULL in C); the range of every entry and the batch cap are checked in C, before the first launch."""
-    tabs = []
-    for name, values in (("q_lengths", q_lengths), ("k_lengths", k_lengths)):
-        if values is None:
-            tabs.append(None)
-            continue
-        tab, n = ragged._table(values, name)
-        if n != Bt:
-            raise _lib.SrfError("%s: %d %s for a batch of %d" % (what, n, name, Bt))
-        tabs.append(tab)
-    return tabs[0], tabs[1], q_lengths is not None or k_lengths is not None
+def _mha_entry(name, Bt, q_lengths, k_lengths):
+    """The C entry of one of the three ops and what its call inserts between the sizes and the scale: -> (function, its name,
+    tables).  Neither list given: (srf_<name>, (): today's entry and profiler names).  Else srf_<name>_ragged and the two host
+    tables (q table or None, k table or None); None = every example is full on that side (NULL in C).  The range of every
+    entry and the batch cap are checked in C, before the first launch."""
+    tabs, entry = [], "srf_" + name
+    if q_lengths is not None or k_lengths is not None:
+        entry += "_ragged"
+        for what, values in (("q_lengths", q_lengths), ("k_lengths", k_lengths)):
+            if values is None:
+                tabs.append(None)
+                continue
+            tab, n = ragged._table(values, what)
+            if n != Bt:
+                raise _lib.SrfError("%s: %d %s for a batch of %d" % (name, n, what, Bt))
+            tabs.append(tab)
+    return getattr(_lib.load(), entry), entry, tabs
 
 
 def _host_lengths(values, what):
@@ -70,17 +74,11 @@ def mha_attention(q, k, v, heads, scale=None, out=None, q_lengths=None, k_length
                                   _host_lengths(k_lengths, "k_lengths"))
     dev = _chk(q, k, v, out)
     Bt, HD, d, Lq, Lk = _mha_shapes("mha_attention", q, k, v, heads)
-    ql, kl, is_ragged = _mha_lengths("mha_attention", Bt, q_lengths, k_lengths)
+    fn, entry, tables = _mha_entry("mha_attention", Bt, q_lengths, k_lengths)
     if out is None:
         out = torch.empty((Bt, HD, Lq), dtype=torch.float32, device=dev)
-    if is_ragged:
-        rc = _lib.load().srf_mha_attention_ragged(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), Bt, heads, d, Lq, Lk, ql, kl,
-                                                  _mha_scale(scale, d), _lib.current_stream(dev))
-        _lib.check(rc, "srf_mha_attention_ragged")
-        return out
-    rc = _lib.load().srf_mha_attention(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), Bt, heads, d, Lq, Lk,
-                                       _mha_scale(scale, d), _lib.current_stream(dev))
-    _lib.check(rc, "srf_mha_attention")
+    _lib.check(fn(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), Bt, heads, d, Lq, Lk, *tables, _mha_scale(scale, d),
+                  _lib.current_stream(dev)), entry)
     return out
 
 
@@ -89,21 +87,15 @@ def mha_attention_lse(q, k, v, heads, scale=None, out=None, lse=None, q_lengths=
     mha_attention's bits.  q_lengths / k_lengths: the ragged form (mha_attention); lse is exact 0 past q_lengths[b] too."""
     dev = _chk(q, k, v, out, lse)
     Bt, HD, d, Lq, Lk = _mha_shapes("mha_attention_lse", q, k, v, heads)
-    ql, kl, is_ragged = _mha_lengths("mha_attention_lse", Bt, q_lengths, k_lengths)
+    fn, entry, tables = _mha_entry("mha_attention_lse", Bt, q_lengths, k_lengths)
     if out is None:
         out = torch.empty((Bt, HD, Lq), dtype=torch.float32, device=dev)
     if lse is None:
         lse = torch.empty((Bt, heads, Lq), dtype=torch.float32, device=dev)
     elif lse.numel() != Bt * heads * Lq:
         raise _lib.SrfError("mha_attention_lse: lse has %d elements, [Bt, H, Lq] = %d" % (lse.numel(), Bt * heads * Lq))
-    if is_ragged:
-        rc = _lib.load().srf_mha_attention_lse_ragged(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), Bt, heads,
-                                                      d, Lq, Lk, ql, kl, _mha_scale(scale, d), _lib.current_stream(dev))
-        _lib.check(rc, "srf_mha_attention_lse_ragged")
-        return out, lse
-    rc = _lib.load().srf_mha_attention_lse(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), Bt, heads, d, Lq, Lk,
-                                           _mha_scale(scale, d), _lib.current_stream(dev))
-    _lib.check(rc, "srf_mha_attention_lse")
+    _lib.check(fn(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(lse), Bt, heads, d, Lq, Lk, *tables,
+                  _mha_scale(scale, d), _lib.current_stream(dev)), entry)
     return out, lse
 
 
@@ -119,7 +111,7 @@ def mha_attention_bwd(q, k, v, o, lse, go, heads, scale=None, gq=None, gk=None, 
     read past q_lengths[b]; gq is exact 0 past q_lengths[b], gk and gv past k_lengths[b]."""
     dev = _chk(q, k, v, o, lse, go, gq, gk, gv, workspace)
     Bt, HD, d, Lq, Lk = _mha_shapes("mha_attention_bwd", q, k, v, heads)
-    ql, kl, is_ragged = _mha_lengths("mha_attention_bwd", Bt, q_lengths, k_lengths)
+    fn, entry, tables = _mha_entry("mha_attention_bwd", Bt, q_lengths, k_lengths)
     if o.shape != q.shape or go.shape != q.shape:
         raise _lib.SrfError("mha_attention_bwd: o %s / go %s differ from q %s" % (tuple(o.shape), tuple(go.shape), tuple(q.shape)))
     if lse.numel() != Bt * heads * Lq:
@@ -135,16 +127,9 @@ def mha_attention_bwd(q, k, v, o, lse, go, heads, scale=None, gq=None, gk=None, 
     gv = torch.empty_like(v) if gv is None else gv
     if gq.shape != q.shape or gk.shape != k.shape or gv.shape != v.shape:
         raise _lib.SrfError("mha_attention_bwd: gq / gk / gv do not have the shapes of q / k / v")
-    if is_ragged:
-        rc = _lib.load().srf_mha_attention_bwd_ragged(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), _lib.ptr(go),
-                                                      _lib.ptr(gq), _lib.ptr(gk), _lib.ptr(gv), _lib.ptr(workspace), Bt, heads, d, Lq,
-                                                      Lk, ql, kl, _mha_scale(scale, d), _lib.current_stream(dev))
-        _lib.check(rc, "srf_mha_attention_bwd_ragged")
-        return gq, gk, gv
-    rc = _lib.load().srf_mha_attention_bwd(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), _lib.ptr(go),
-                                           _lib.ptr(gq), _lib.ptr(gk), _lib.ptr(gv), _lib.ptr(workspace), Bt, heads, d, Lq, Lk,
-                                           _mha_scale(scale, d), _lib.current_stream(dev))
-    _lib.check(rc, "srf_mha_attention_bwd")
+    _lib.check(fn(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(o), _lib.ptr(lse), _lib.ptr(go), _lib.ptr(gq), _lib.ptr(gk),
+                  _lib.ptr(gv), _lib.ptr(workspace), Bt, heads, d, Lq, Lk, *tables, _mha_scale(scale, d), _lib.current_stream(dev)),
+               entry)
     return gq, gk, gv
 
 
@@ -177,6 +162,26 @@ def zero_past(x, lengths):
     return x
 
 
+def _data(gout, w):
+    """the data gradient of y = W x + b: W^T gout, on the GEMM kernels"""
+    wt = w.reshape(w.shape[0], -1).t().contiguous()
+    return ops.pw_conv(gout, wt, torch.zeros(wt.shape[0], dtype=torch.float32, device=gout.device))
+
+
+def _wgrad(gout, x, sums=None, gamma=None, beta=None, prelu=None):
+    """ops.pw_wgrad for any length.  srf_pw_wgrad reads rows as float4 (L % 4 == 0): other lengths are zero-padded -- zero
+    columns of gout add nothing to either sum, whatever the norm on load makes of x's padding.
+    The kernel derives mean and variance from `sums` and the length it is GIVEN, so the padded call gets the sums scaled by
+    padded / real length: the same mean and variance."""
+    L = gout.shape[-1]
+    pad = -L % 4
+    if pad:
+        gout, x = torch.nn.functional.pad(gout, (0, pad)), torch.nn.functional.pad(x, (0, pad))
+        if sums is not None:
+            sums = sums * ((L + pad) / L)
+    return ops.pw_wgrad(gout, x, sums, gamma, beta, prelu)
+
+
 class _MHALayer(torch.autograd.Function):
     """MHAttentionLayer.forward under autograd (enable_hip_training): the layer's own kernel sequence with the lse forward, and a
     backward of mha_attention_bwd, ops.pw_conv on the transposed weights (data gradients) and ops.pw_wgrad (weight and bias
@@ -207,24 +212,13 @@ class _MHALayer(torch.autograd.Function):
         g = gy.transpose(1, 2).contiguous()
         if q_lengths is not None:      # the gradient arriving at rows past q_lengths is ignored: zeroed in a copy of our own
             g = zero_past(g.clone() if g.data_ptr() == gy.data_ptr() else g, q_lengths)
-
-        def data(gout, w):       # the data gradient of y = W x + b: W^T gout
-            wt = w.t().contiguous()
-            return ops.pw_conv(gout, wt, torch.zeros(wt.shape[0], dtype=torch.float32, device=gout.device))
-
-        def wgrad(gout, x):      # srf_pw_wgrad reads rows as float4 (L % 4 == 0): zero columns add nothing to either sum
-            pad = -gout.shape[-1] % 4
-            if pad:
-                gout, x = torch.nn.functional.pad(gout, (0, pad)), torch.nn.functional.pad(x, (0, pad))
-            return ops.pw_wgrad(gout, x)
-
-        dwo, dbo = wgrad(g, o)
-        gq, gk, gv = mha_attention_bwd(q, k, v, o, lse, data(g, wo), ctx.heads, ctx.scale, q_lengths=q_lengths, k_lengths=k_lengths)
+        dwo, dbo = _wgrad(g, o)
+        gq, gk, gv = mha_attention_bwd(q, k, v, o, lse, _data(g, wo), ctx.heads, ctx.scale, q_lengths=q_lengths, k_lengths=k_lengths)
         grads = [None, None, None, None]
         for i, (gp, w) in enumerate(((gq, wq), (gk, wk), (gv, wv))):
-            grads.append(data(gp, w).transpose(1, 2).contiguous() if need[2 + i] else None)
+            grads.append(_data(gp, w).transpose(1, 2).contiguous() if need[2 + i] else None)
         for gp, x in ((gq, xq), (gk, xk), (gv, xv)):
-            grads.extend(wgrad(gp, x))
+            grads.extend(_wgrad(gp, x))
         return tuple(grads) + (dwo, dbo)
 
 
@@ -294,27 +288,14 @@ def draw_dropout_state():
     return int(s[0]), int(s[1])
 
 
+def _drop_state(training, layer):
+    """(p, seed, offset) of one call of a transformer layer's position-table dropout: in train() mode with p > 0 one pair from
+    draw_dropout_state, else (0.0, 0, 0) = the plain kernels"""
+    p = float(layer.pos_enc.dropout.p) if training else 0.0
+    return (p,) + draw_dropout_state() if p > 0 else (0.0, 0, 0)
+
+
 # ---- TransformerLayer / AttentiveUConvBlock under autograd (DESIGN.md section 16.2) -----------------------------------
-def _data(gout, w):
-    """the data gradient of y = W x + b: W^T gout, on the GEMM kernels"""
-    wt = w.reshape(w.shape[0], -1).t().contiguous()
-    return ops.pw_conv(gout, wt, torch.zeros(wt.shape[0], dtype=torch.float32, device=gout.device))
-
-
-def _wgrad(gout, x, sums=None, gamma=None, beta=None, prelu=None):
-    """ops.pw_wgrad for any length.  srf_pw_wgrad reads rows as float4 (L % 4 == 0): other lengths are zero-padded, as
-    mha_layer_train does -- zero columns of gout add nothing to either sum, whatever the norm on load makes of x's padding.
-    The kernel derives mean and variance from `sums` and the length it is GIVEN, so the padded call gets the sums scaled by
-    padded / real length: the same mean and variance."""
-    L = gout.shape[-1]
-    pad = -L % 4
-    if pad:
-        gout, x = torch.nn.functional.pad(gout, (0, pad)), torch.nn.functional.pad(x, (0, pad))
-        if sums is not None:
-            sums = sums * ((L + pad) / L)
-    return ops.pw_wgrad(gout, x, sums, gamma, beta, prelu)
-
-
 _TL_PARAMS = 17   # mha.{Q,K,V,O}_proj.{weight, bias}, out_norm, out_mha_norm, ffn.conv, ffn.norm, ffn.act: state_dict() order
 _TL_OUT_NORM = slice(8, 10)        # out_norm.{gamma, beta} in that list
 _TL_Z, _TL_S_OUT = 9, 12           # z and out_norm's statistics slot in _tl_forward's saved tuple
@@ -402,10 +383,8 @@ def transformer_layer_train(layer, x, in_sums=None, in_gamma=None, in_beta=None)
     generator per call; eval() or p == 0 runs the plain kernels (the inference forward's bits)."""
     par = _tl_params(layer)
     _chk(*par)
-    p = float(layer.pos_enc.dropout.p) if layer.training else 0.0
-    drop = (p,) + draw_dropout_state() if p > 0 else (0.0, 0, 0)
-    return _TransformerLayerTrain.apply(layer.mha.n_heads, layer.mha.q_normalizer, drop, layer.pos_enc.pe.detach(), x, in_sums,
-                                        in_gamma, in_beta, *par)
+    return _TransformerLayerTrain.apply(layer.mha.n_heads, layer.mha.q_normalizer, _drop_state(layer.training, layer),
+                                        layer.pos_enc.pe.detach(), x, in_sums, in_gamma, in_beta, *par)
 
 
 def _ub_params(block):
@@ -419,6 +398,11 @@ def _ub_params(block):
                   block.res_conv.bias] + _tl_params(block.attention)
 
 
+def _ub_split(par, D):
+    """_ub_params' list by module: -> (proj_1x1's five, [the four of each level], final_norm's three + res_conv's two, the layer's)"""
+    return par[:5], [par[5 + 4 * k:9 + 4 * k] for k in range(D)], par[5 + 4 * D:10 + 4 * D], par[10 + 4 * D:]
+
+
 class _AttentiveUConvBlockTrain(torch.autograd.Function):
     """AttentiveUConvBlock.forward under autograd (enable_hip_training): one node around the block -- proj_1x1, the D dwconv5
     levels, the transformer layer on level D - 1 with that level's lazy norm, srf_merge, res_conv with final_norm on load plus
@@ -427,10 +411,7 @@ class _AttentiveUConvBlockTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, D, heads, scale, drop, pe, x, *par):
         x, par = x.detach(), [t.detach() for t in par]
-        w_in, b_in, g_in, be_in, a_in = par[:5]
-        lv = [par[5 + 4 * k:9 + 4 * k] for k in range(D)]
-        g_fin, b_fin, a_fin, w_res, b_res = par[5 + 4 * D:10 + 4 * D]
-        tl = par[10 + 4 * D:]
+        (w_in, b_in, g_in, be_in, a_in), lv, (g_fin, b_fin, a_fin, w_res, b_res), tl = _ub_split(par, D)
         Bt, dev = x.shape[0], x.device
         s_in = ops.new_sums(Bt, dev)
         y1 = ops.pw_conv(x, w_in, b_in, out_sums=s_in)
@@ -460,10 +441,7 @@ class _AttentiveUConvBlockTrain(torch.autograd.Function):
         x, y1, s_in, merged, s_m = t[:5]
         levels, sums = t[5:4 + D], t[4 + D:4 + 2 * D]
         saved, par = t[4 + 2 * D:4 + 2 * D + n_saved], t[4 + 2 * D + n_saved:]
-        w_in, b_in, g_in, be_in, a_in = par[:5]
-        lv = [par[5 + 4 * k:9 + 4 * k] for k in range(D)]
-        g_fin, b_fin, a_fin, w_res, b_res = par[5 + 4 * D:10 + 4 * D]
-        tl = par[10 + 4 * D:]
+        (w_in, b_in, g_in, be_in, a_in), lv, (g_fin, b_fin, a_fin, w_res, b_res), tl = _ub_split(par, D)
         g = g.contiguous()
         dw_res, db_res = _wgrad(g, merged, s_m, g_fin, b_fin, a_fin)
         gm, dg_fin, db_fin, da_fin = ops.gln_bwd(_data(g, w_res), merged, s_m, g_fin, b_fin, a_fin)
@@ -493,10 +471,8 @@ def uconv_block_train(block, x):
     par = _ub_params(block)
     _chk(*par)
     layer = block.attention
-    p = float(layer.pos_enc.dropout.p) if block.training else 0.0
-    drop = (p,) + draw_dropout_state() if p > 0 else (0.0, 0, 0)
-    return _AttentiveUConvBlockTrain.apply(block.depth, layer.mha.n_heads, layer.mha.q_normalizer, drop, layer.pos_enc.pe.detach(),
-                                           x, *par)
+    return _AttentiveUConvBlockTrain.apply(block.depth, layer.mha.n_heads, layer.mha.q_normalizer, _drop_state(block.training, layer),
+                                           layer.pos_enc.pe.detach(), x, *par)
 
 
 def gln_apply2_add(f, f_sums, f_gamma, f_beta, f_prelu, y, y_sums, y_gamma, y_beta, y_prelu=None, out_sums=None, out=None):

@@ -34,17 +34,10 @@
 //
 // The generic form (any other d <= 1024): one wavefront per query, a lane per key for the scores and a lane per output channel
 // for the weighted sum (the probabilities travel by v_readlane), plain fp32 FMA.
-#include "srf_internal.h"
-
-typedef float srf_f32x16 __attribute__((ext_vector_type(16)));
-
-struct MhaArgs {
-  const float *q, *k, *v;
-  float* o;
-  long qs, ks, vs, os;   // example strides (floats)
-  int H, d, Lq, Lk;
-  float scale;
-};
+//
+// Host path: the four public entries (plain, lse, and the ragged form of each) check their sizes, set the contiguous strides
+// and call srf_mha_forward, which the attentive walks call with strides of their own: checks, tables, one dispatch.
+#include "srf_mha.h"
 
 #define SRF_MHA_NEG_INF (-__builtin_inff())
 
@@ -56,12 +49,7 @@ struct MhaArgs {
 // count (qn, kn below -- the strides themselves in the uniform instantiations).  Nothing at or past a count is read; o and lse
 // are written as exact 0.f from qn up to the stride; a block whose whole tile lies at or past qn stores those zeros and returns
 // before any load, LDS write or MFMA.  Inside the counts the arithmetic and its order are the uniform kernel's on example b
-// alone with Lq = qn, Lk = kn: the tiles start at position 0 of the example either way.
-__device__ __forceinline__ void srf_mha_store_lse(size_t, float) {}   // (plain: never evaluated)
-__device__ __forceinline__ void srf_mha_store_lse(size_t at, float v, float* lse) { lse[at] = v; }
-__device__ __forceinline__ void srf_mha_store_lse(size_t, float, const SrfFrames&, const SrfFrames&) {}
-__device__ __forceinline__ void srf_mha_store_lse(size_t at, float v, float* lse, const SrfFrames&, const SrfFrames&) { lse[at] = v; }
-
+// alone with Lq = qn, Lk = kn: the tiles start at position 0 of the example either way.  (The pack's readers: srf_mha.h.)
 template <int NCH, typename... X>   // 32-channel chunks of the head dimension (d <= 32 NCH): 16 accumulator registers each
 __global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a, X... x) {
   constexpr bool LSE = sizeof...(X) & 1, RAGGED = sizeof...(X) >= 2;
@@ -178,8 +166,7 @@ __global__ __launch_bounds__(64) void srf_mha_mfma_kernel(MhaArgs a, X... x) {
   }
 }
 
-// ---- generic form: one wavefront per query
-#define SRF_MHA_GEN_T 16   // output channels per lane: d <= 64 * 16
+// ---- generic form: one wavefront per query (SRF_MHA_GEN_T output channels per lane)
 __device__ __forceinline__ float srf_mha_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -281,38 +268,7 @@ static int srf_mha_check(const float* q, const float* k, const float* v, float* 
   return SRF_OK;
 }
 
-int srf_mha_attention_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os, int Bt,
-                              int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
-  const int rc = srf_mha_check(q, k, v, o, Bt, H, d, Lq, Lk);
-  if (rc != SRF_OK) return rc;
-  return srf_mha_launch(MhaArgs{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale}, Bt, st, "mha_attention_mfma",
-                        "mha_attention_generic");
-}
-
-int srf_mha_attention_lse_strided(const float* q, const float* k, const float* v, float* o, float* lse, long qs, long ks, long vs,
-                                  long os, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
-  const int rc = srf_mha_check(q, k, v, o, Bt, H, d, Lq, Lk);
-  if (rc != SRF_OK) return rc;
-  SRF_CHECK_ARG(lse, "srf_mha_attention_lse: lse is null");
-  return srf_mha_launch(MhaArgs{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale}, Bt, st, "mha_attention_lse_mfma",
-                        "mha_attention_lse_generic", lse);
-}
-
-extern "C" int srf_mha_attention(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq, int Lk,
-                                 float scale, void* stream) {
-  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
-  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
-  return srf_mha_attention_strided(q, k, v, o, sq, sk, sk, sq, Bt, H, d, Lq, Lk, scale, (hipStream_t)stream);
-}
-
-extern "C" int srf_mha_attention_lse(const float* q, const float* k, const float* v, float* o, float* lse, int Bt, int H, int d,
-                                     int Lq, int Lk, float scale, void* stream) {
-  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_lse: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
-  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
-  return srf_mha_attention_lse_strided(q, k, v, o, lse, sq, sk, sk, sq, Bt, H, d, Lq, Lk, scale, (hipStream_t)stream);
-}
-
-// ---- ragged forms: the uniform checks, then the two tables (NULL = every example full on that side), then the same dispatch
+// ---- the two tables of a ragged call (NULL = every example full on that side)
 int srf_mha_ragged_tables(const char* fn, int Bt, int Lq, int Lk, const int* q_lengths, const int* k_lengths, SrfFrames* qf,
                           SrfFrames* kf) {
   SRF_CHECK_ARG(Bt >= 1 && Bt <= SRF_RAGGED_MAX_BATCH, "%s: a ragged batch holds 1..%d examples (got Bt = %d)", fn,
@@ -332,37 +288,53 @@ int srf_mha_ragged_tables(const char* fn, int Bt, int Lq, int Lk, const int* q_l
   return SRF_OK;
 }
 
-int srf_mha_attention_ragged_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os,
-                                     int Bt, int H, int d, int Lq, int Lk, const int* q_lengths, const int* k_lengths, float scale,
-                                     hipStream_t st) {
-  int rc = srf_mha_check(q, k, v, o, Bt, H, d, Lq, Lk);
+// ---- the host path of all four forms: the uniform checks, lse, the two tables, then the one dispatch on the form's pack.
+// Row `form` of each table: the public entry (the error strings) and the profiler names, string literals that outlive the call.
+int srf_mha_forward(int form, const MhaArgs& a, int Bt, float* lse, const int* q_lengths, const int* k_lengths, hipStream_t st) {
+  static const char* const entry[4] = {"srf_mha_attention", "srf_mha_attention_lse", "srf_mha_attention_ragged",
+                                       "srf_mha_attention_lse_ragged"};
+  static const char* const name[4][2] = {{"mha_attention_mfma", "mha_attention_generic"},
+                                         {"mha_attention_lse_mfma", "mha_attention_lse_generic"},
+                                         {"mha_attention_mfma_ragged", "mha_attention_generic_ragged"},
+                                         {"mha_attention_lse_mfma_ragged", "mha_attention_lse_generic_ragged"}};
+  int rc = srf_mha_check(a.q, a.k, a.v, a.o, Bt, a.H, a.d, a.Lq, a.Lk);
   if (rc != SRF_OK) return rc;
+  if (form & SRF_MHA_LSE) SRF_CHECK_ARG(lse, "%s: lse is null", entry[form]);
+  const char *mfma = name[form][0], *generic = name[form][1];
+  if (form == 0) return srf_mha_launch(a, Bt, st, mfma, generic);
+  if (form == SRF_MHA_LSE) return srf_mha_launch(a, Bt, st, mfma, generic, lse);
   SrfFrames qf, kf;
-  rc = srf_mha_ragged_tables("srf_mha_attention_ragged", Bt, Lq, Lk, q_lengths, k_lengths, &qf, &kf);
+  rc = srf_mha_ragged_tables(entry[form], Bt, a.Lq, a.Lk, q_lengths, k_lengths, &qf, &kf);
   if (rc != SRF_OK) return rc;
-  return srf_mha_launch(MhaArgs{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale}, Bt, st, "mha_attention_mfma_ragged",
-                        "mha_attention_generic_ragged", qf, kf);
+  if (form == SRF_MHA_RAGGED) return srf_mha_launch(a, Bt, st, mfma, generic, qf, kf);
+  return srf_mha_launch(a, Bt, st, mfma, generic, lse, qf, kf);
 }
 
-int srf_mha_attention_lse_ragged_strided(const float* q, const float* k, const float* v, float* o, float* lse, long qs, long ks,
-                                         long vs, long os, int Bt, int H, int d, int Lq, int Lk, const int* q_lengths,
-                                         const int* k_lengths, float scale, hipStream_t st) {
-  int rc = srf_mha_check(q, k, v, o, Bt, H, d, Lq, Lk);
-  if (rc != SRF_OK) return rc;
-  SRF_CHECK_ARG(lse, "srf_mha_attention_lse_ragged: lse is null");
-  SrfFrames qf, kf;
-  rc = srf_mha_ragged_tables("srf_mha_attention_lse_ragged", Bt, Lq, Lk, q_lengths, k_lengths, &qf, &kf);
-  if (rc != SRF_OK) return rc;
-  return srf_mha_launch(MhaArgs{q, k, v, o, qs, ks, vs, os, H, d, Lq, Lk, scale}, Bt, st, "mha_attention_lse_mfma_ragged",
-                        "mha_attention_lse_generic_ragged", lse, qf, kf);
+// the contiguous tensors of the public entries: q, o [Bt, H d, Lq], k, v [Bt, H d, Lk]
+static MhaArgs srf_mha_contiguous(const float* q, const float* k, const float* v, float* o, int H, int d, int Lq, int Lk,
+                                  float scale) {
+  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
+  return MhaArgs{q, k, v, o, sq, sk, sk, sq, H, d, Lq, Lk, scale};
+}
+
+extern "C" int srf_mha_attention(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq, int Lk,
+                                 float scale, void* stream) {
+  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
+  return srf_mha_forward(0, srf_mha_contiguous(q, k, v, o, H, d, Lq, Lk, scale), Bt, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int srf_mha_attention_lse(const float* q, const float* k, const float* v, float* o, float* lse, int Bt, int H, int d,
+                                     int Lq, int Lk, float scale, void* stream) {
+  SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_lse: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
+  return srf_mha_forward(SRF_MHA_LSE, srf_mha_contiguous(q, k, v, o, H, d, Lq, Lk, scale), Bt, lse, nullptr, nullptr,
+                         (hipStream_t)stream);
 }
 
 extern "C" int srf_mha_attention_ragged(const float* q, const float* k, const float* v, float* o, int Bt, int H, int d, int Lq,
                                         int Lk, const int* q_lengths, const int* k_lengths, float scale, void* stream) {
   SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_ragged: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
-  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
-  return srf_mha_attention_ragged_strided(q, k, v, o, sq, sk, sk, sq, Bt, H, d, Lq, Lk, q_lengths, k_lengths, scale,
-                                          (hipStream_t)stream);
+  return srf_mha_forward(SRF_MHA_RAGGED, srf_mha_contiguous(q, k, v, o, H, d, Lq, Lk, scale), Bt, nullptr, q_lengths, k_lengths,
+                         (hipStream_t)stream);
 }
 
 extern "C" int srf_mha_attention_lse_ragged(const float* q, const float* k, const float* v, float* o, float* lse, int Bt, int H,
@@ -370,9 +342,8 @@ extern "C" int srf_mha_attention_lse_ragged(const float* q, const float* k, cons
                                             void* stream) {
   SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_lse_ragged: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq,
                 Lk);
-  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
-  return srf_mha_attention_lse_ragged_strided(q, k, v, o, lse, sq, sk, sk, sq, Bt, H, d, Lq, Lk, q_lengths, k_lengths, scale,
-                                              (hipStream_t)stream);
+  return srf_mha_forward(SRF_MHA_LSE | SRF_MHA_RAGGED, srf_mha_contiguous(q, k, v, o, H, d, Lq, Lk, scale), Bt, lse, q_lengths,
+                         k_lengths, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -449,6 +420,14 @@ __global__ __launch_bounds__(256) void srf_posenc_apply_kernel(const float* __re
   }
 }
 
+// the grid and the launch of both entries (drop: nothing, or the dropout state); the arguments are the entry's to check
+template <typename... Drop>
+static void srf_posenc_launch(const float* a, const SrfNormDev& nd, const float* pe, float* x, int Bt, int C, int L, void* stream,
+                              Drop... drop) {
+  hipLaunchKernelGGL(srf_posenc_apply_kernel<Drop...>, dim3((L + 31) / 32, (C + 31) / 32, Bt), dim3(256), 0, (hipStream_t)stream, a, nd,
+                     pe, x, 1.0 / ((double)C * (double)L), C, L, drop...);
+}
+
 extern "C" int srf_posenc_apply(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L,
                                 int max_len, void* stream) {
   SRF_CHECK_ARG(a && pe && x && Bt > 0 && C > 0 && L > 0, "srf_posenc_apply: bad arguments");
@@ -457,8 +436,7 @@ extern "C" int srf_posenc_apply(const float* a, const srf_norm* norm, const floa
   const SrfNormDev nd = srf_norm_dev(norm);
   if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_posenc_apply: norm without gamma/beta");
   SRF_CHECK_ALIGNED16("srf_posenc_apply", {"norm.sums", nd.sums});
-  hipLaunchKernelGGL(srf_posenc_apply_kernel<>, dim3((L + 31) / 32, (C + 31) / 32, Bt), dim3(256), 0, (hipStream_t)stream, a, nd, pe,
-                     x, 1.0 / ((double)C * (double)L), C, L);
+  srf_posenc_launch(a, nd, pe, x, Bt, C, L, stream);
   SRF_CHECK_LAUNCH("posenc_apply", stream);
   return SRF_OK;
 }
@@ -490,8 +468,7 @@ extern "C" int srf_posenc_apply_dropout(const float* a, const srf_norm* norm, co
   const SrfNormDev nd = srf_norm_dev(norm);
   if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_posenc_apply_dropout: norm without gamma/beta");
   SRF_CHECK_ALIGNED16("srf_posenc_apply_dropout", {"norm.sums", nd.sums});
-  hipLaunchKernelGGL(srf_posenc_apply_kernel<SrfDropoutDev>, dim3((L + 31) / 32, (C + 31) / 32, Bt), dim3(256), 0,
-                     (hipStream_t)stream, a, nd, pe, x, 1.0 / ((double)C * (double)L), C, L, dd);
+  srf_posenc_launch(a, nd, pe, x, Bt, C, L, stream, dd);
   SRF_CHECK_LAUNCH("posenc_apply_dropout", stream);
   return SRF_OK;
 }

@@ -41,17 +41,10 @@
 // up to the stride, delta is left alone there; a block whose whole owned tile lies past the count stores its zeros and returns
 // before any load, LDS write or MFMA, and the loop over the other side runs to that side's own count.  Inside the counts the
 // arithmetic and its order are those of the uniform kernel on example b alone.
-#include "srf_internal.h"
-
-typedef float srf_f32x16 __attribute__((ext_vector_type(16)));
-
-struct MhaBwdArgs {
-  const float *q, *k, *v, *go, *lse, *delta;   // lse, delta: [Bt, H, Lq] contiguous
-  float *gq, *gk, *gv;
-  long qs, ks, vs, gos, gqs, gks, gvs;          // example strides (floats)
-  int H, d, Lq, Lk;
-  float scale;
-};
+//
+// Host path: both public entries check their sizes, set the contiguous strides and call srf_mha_backward: checks, (ragged)
+// tables, then srf_mha_bwd_run, the one launch sequence, instantiated without and with the tables.
+#include "srf_mha.h"
 
 // ---- delta[b, h, lq] = sum_j gO[j, lq] O[j, lq]: one thread per query, channels in order
 template <typename... R>
@@ -239,8 +232,7 @@ __global__ __launch_bounds__(64) void srf_mha_bwd_mfma_kernel(MhaBwdArgs a, R...
   }
 }
 
-// ---- generic form
-#define SRF_MHA_GEN_T 16   // channels per lane: d <= 64 * 16
+// ---- generic form (SRF_MHA_GEN_T channels per lane)
 // gQ: one wavefront per query, a lane per key for dS, a lane per channel for the sum over keys
 template <typename... R>
 __global__ __launch_bounds__(256) void srf_mha_bwd_dq_generic_kernel(MhaBwdArgs a, R... r2) {
@@ -378,11 +370,11 @@ static void srf_mha_bwd_mfma_launch(const MhaBwdArgs& a, int Bt, hipStream_t st,
   else if constexpr (ROLE != SRF_MHA_BWD_KV) hipLaunchKernelGGL((srf_mha_bwd_mfma_kernel<8, ROLE, R...>), grid, block, 0, st, a, r2...);
 }
 
-static int srf_mha_bwd_check(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
-                             float* gq, float* gk, float* gv, void* workspace, int Bt, int H, int d, int Lq, int Lk) {
-  SRF_CHECK_ARG(q && k && v && o && lse && go, "srf_mha_attention_bwd: null input (q, k, v, o, lse or go)");
-  SRF_CHECK_ARG(gq && gk && gv, "srf_mha_attention_bwd: null output (gq, gk or gv)");
-  SRF_CHECK_ARG(workspace, "srf_mha_attention_bwd: workspace is null (srf_mha_attention_bwd_workspace_bytes)");
+static int srf_mha_bwd_check(const MhaBwdArgs& a, const float* o, int Bt) {
+  const int H = a.H, d = a.d, Lq = a.Lq, Lk = a.Lk;
+  SRF_CHECK_ARG(a.q && a.k && a.v && o && a.lse && a.go, "srf_mha_attention_bwd: null input (q, k, v, o, lse or go)");
+  SRF_CHECK_ARG(a.gq && a.gk && a.gv, "srf_mha_attention_bwd: null output (gq, gk or gv)");
+  SRF_CHECK_ARG(a.delta, "srf_mha_attention_bwd: workspace is null (srf_mha_attention_bwd_workspace_bytes)");
   SRF_CHECK_ARG(Bt > 0 && H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_bwd: bad sizes (Bt %d, H %d, d %d, Lq %d, Lk %d)",
                 Bt, H, d, Lq, Lk);
   SRF_CHECK_ARG(Bt <= 65535 && H <= 65535, "srf_mha_attention_bwd: batch / heads too large (max 65535 each)");
@@ -393,86 +385,75 @@ static int srf_mha_bwd_check(const float* q, const float* k, const float* v, con
   return SRF_OK;
 }
 
-int srf_mha_attention_bwd_strided(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
-                                  float* gq, float* gk, float* gv, void* workspace, long qs, long ks, long vs, long os, long gos,
-                                  long gqs, long gks, long gvs, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st) {
-  const int rc = srf_mha_bwd_check(q, k, v, o, lse, go, gq, gk, gv, workspace, Bt, H, d, Lq, Lk);
-  if (rc != SRF_OK) return rc;
-  float* delta = (float*)workspace;
-  const MhaBwdArgs a{q, k, v, go, lse, delta, gq, gk, gv, qs, ks, vs, gos, gqs, gks, gvs, H, d, Lq, Lk, scale};
-  hipLaunchKernelGGL(srf_mha_bwd_delta_kernel<>, dim3((Lq + 255) / 256, H, Bt), dim3(256), 0, st, o, go, delta, os, gos, H, d, Lq);
-  SRF_CHECK_LAUNCH("mha_attention_bwd_delta", st);
-  if (srf_mha_attention_bwd_mfma_supported(d)) {
-    srf_mha_bwd_mfma_launch<SRF_MHA_BWD_Q>(a, Bt, st);
-    SRF_CHECK_LAUNCH("mha_attention_bwd_dq_mfma", st);
-    if (d <= 128) {
-      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_KV>(a, Bt, st);
-      SRF_CHECK_LAUNCH("mha_attention_bwd_dkv_mfma", st);
+// The launch sequence, once: tables = nothing (the uniform instantiations) or (q_len, k_len), of which delta takes the first.
+// A profiler name is a string literal either way (the profiler keeps the pointer): the uniform name, + "_ragged" with tables.
+#define SRF_MHA_BWD_NAME(base) (sizeof...(R) ? base "_ragged" : base)
+static const SrfFrames& srf_mha_bwd_first(const SrfFrames& qf, const SrfFrames&) { return qf; }
+template <typename... Q>
+static void srf_mha_bwd_delta_launch(const MhaBwdArgs& a, const float* o, long os, int Bt, hipStream_t st, const Q&... qf) {
+  hipLaunchKernelGGL(srf_mha_bwd_delta_kernel<Q...>, dim3((a.Lq + 255) / 256, a.H, Bt), dim3(256), 0, st, o, a.go,
+                     const_cast<float*>(a.delta), os, a.gos, a.H, a.d, a.Lq, qf...);   // (delta: the caller's workspace)
+}
+
+template <typename... R>
+static int srf_mha_bwd_run(const MhaBwdArgs& a, const float* o, long os, int Bt, hipStream_t st, R... tables) {
+  const dim3 block(256);
+  if constexpr (sizeof...(R) == 0) srf_mha_bwd_delta_launch(a, o, os, Bt, st);
+  else srf_mha_bwd_delta_launch(a, o, os, Bt, st, srf_mha_bwd_first(tables...));
+  SRF_CHECK_LAUNCH(SRF_MHA_BWD_NAME("mha_attention_bwd_delta"), st);
+  if (srf_mha_attention_bwd_mfma_supported(a.d)) {
+    srf_mha_bwd_mfma_launch<SRF_MHA_BWD_Q>(a, Bt, st, tables...);
+    SRF_CHECK_LAUNCH(SRF_MHA_BWD_NAME("mha_attention_bwd_dq_mfma"), st);
+    if (a.d <= 128) {
+      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_KV>(a, Bt, st, tables...);
+      SRF_CHECK_LAUNCH(SRF_MHA_BWD_NAME("mha_attention_bwd_dkv_mfma"), st);
     } else {   // 2 x 128 accumulator registers would not fit beside the operands: one pass per output
-      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_V>(a, Bt, st);
-      SRF_CHECK_LAUNCH("mha_attention_bwd_dv_mfma", st);
-      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_K>(a, Bt, st);
-      SRF_CHECK_LAUNCH("mha_attention_bwd_dk_mfma", st);
+      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_V>(a, Bt, st, tables...);
+      SRF_CHECK_LAUNCH(SRF_MHA_BWD_NAME("mha_attention_bwd_dv_mfma"), st);
+      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_K>(a, Bt, st, tables...);
+      SRF_CHECK_LAUNCH(SRF_MHA_BWD_NAME("mha_attention_bwd_dk_mfma"), st);
     }
     return SRF_OK;
   }
-  hipLaunchKernelGGL(srf_mha_bwd_dq_generic_kernel<>, dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a);
-  SRF_CHECK_LAUNCH("mha_attention_bwd_dq_generic", st);
-  hipLaunchKernelGGL(srf_mha_bwd_dkv_generic_kernel<>, dim3((Lk + 3) / 4, H, Bt), dim3(256), 0, st, a);
-  SRF_CHECK_LAUNCH("mha_attention_bwd_dkv_generic", st);
+  hipLaunchKernelGGL((srf_mha_bwd_dq_generic_kernel<R...>), dim3((a.Lq + 3) / 4, a.H, Bt), block, 0, st, a, tables...);
+  SRF_CHECK_LAUNCH(SRF_MHA_BWD_NAME("mha_attention_bwd_dq_generic"), st);
+  hipLaunchKernelGGL((srf_mha_bwd_dkv_generic_kernel<R...>), dim3((a.Lk + 3) / 4, a.H, Bt), block, 0, st, a, tables...);
+  SRF_CHECK_LAUNCH(SRF_MHA_BWD_NAME("mha_attention_bwd_dkv_generic"), st);
   return SRF_OK;
 }
 
-// the ragged form: the uniform checks, the two tables, then the same launches on the ragged instantiations
-int srf_mha_attention_bwd_ragged_strided(const float* q, const float* k, const float* v, const float* o, const float* lse,
-                                         const float* go, float* gq, float* gk, float* gv, void* workspace, long qs, long ks, long vs,
-                                         long os, long gos, long gqs, long gks, long gvs, int Bt, int H, int d, int Lq, int Lk,
-                                         const int* q_lengths, const int* k_lengths, float scale, hipStream_t st) {
-  int rc = srf_mha_bwd_check(q, k, v, o, lse, go, gq, gk, gv, workspace, Bt, H, d, Lq, Lk);
+// The host path of both entries: the uniform checks, (ragged) the two tables, the launches.  o with its own example stride like
+// the operands in `a`; lse and the workspace (a.delta) contiguous.  ragged with both tables NULL still runs the ragged kernels.
+static int srf_mha_backward(const MhaBwdArgs& a, const float* o, long os, int Bt, bool ragged, const int* q_lengths,
+                            const int* k_lengths, hipStream_t st) {
+  int rc = srf_mha_bwd_check(a, o, Bt);
   if (rc != SRF_OK) return rc;
+  if (!ragged) return srf_mha_bwd_run(a, o, os, Bt, st);
   SrfFrames qf, kf;
-  rc = srf_mha_ragged_tables("srf_mha_attention_bwd_ragged", Bt, Lq, Lk, q_lengths, k_lengths, &qf, &kf);
+  rc = srf_mha_ragged_tables("srf_mha_attention_bwd_ragged", Bt, a.Lq, a.Lk, q_lengths, k_lengths, &qf, &kf);
   if (rc != SRF_OK) return rc;
-  float* delta = (float*)workspace;
-  const MhaBwdArgs a{q, k, v, go, lse, delta, gq, gk, gv, qs, ks, vs, gos, gqs, gks, gvs, H, d, Lq, Lk, scale};
-  hipLaunchKernelGGL(srf_mha_bwd_delta_kernel<SrfFrames>, dim3((Lq + 255) / 256, H, Bt), dim3(256), 0, st, o, go, delta, os, gos, H,
-                     d, Lq, qf);
-  SRF_CHECK_LAUNCH("mha_attention_bwd_delta_ragged", st);
-  if (srf_mha_attention_bwd_mfma_supported(d)) {
-    srf_mha_bwd_mfma_launch<SRF_MHA_BWD_Q>(a, Bt, st, qf, kf);
-    SRF_CHECK_LAUNCH("mha_attention_bwd_dq_mfma_ragged", st);
-    if (d <= 128) {
-      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_KV>(a, Bt, st, qf, kf);
-      SRF_CHECK_LAUNCH("mha_attention_bwd_dkv_mfma_ragged", st);
-    } else {
-      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_V>(a, Bt, st, qf, kf);
-      SRF_CHECK_LAUNCH("mha_attention_bwd_dv_mfma_ragged", st);
-      srf_mha_bwd_mfma_launch<SRF_MHA_BWD_K>(a, Bt, st, qf, kf);
-      SRF_CHECK_LAUNCH("mha_attention_bwd_dk_mfma_ragged", st);
-    }
-    return SRF_OK;
-  }
-  hipLaunchKernelGGL((srf_mha_bwd_dq_generic_kernel<SrfFrames, SrfFrames>), dim3((Lq + 3) / 4, H, Bt), dim3(256), 0, st, a, qf, kf);
-  SRF_CHECK_LAUNCH("mha_attention_bwd_dq_generic_ragged", st);
-  hipLaunchKernelGGL((srf_mha_bwd_dkv_generic_kernel<SrfFrames, SrfFrames>), dim3((Lk + 3) / 4, H, Bt), dim3(256), 0, st, a, qf, kf);
-  SRF_CHECK_LAUNCH("mha_attention_bwd_dkv_generic_ragged", st);
-  return SRF_OK;
+  return srf_mha_bwd_run(a, o, os, Bt, st, qf, kf);
+}
+
+// the contiguous tensors of the public entries: q, o, go, gq [Bt, H d, Lq], k, v, gk, gv [Bt, H d, Lk]
+static MhaBwdArgs srf_mha_bwd_contiguous(const float* q, const float* k, const float* v, const float* lse, const float* go, float* gq,
+                                         float* gk, float* gv, void* workspace, int H, int d, int Lq, int Lk, float scale) {
+  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
+  return MhaBwdArgs{q, k, v, go, lse, (const float*)workspace, gq, gk, gv, sq, sk, sk, sq, sq, sk, sk, H, d, Lq, Lk, scale};
 }
 
 extern "C" int srf_mha_attention_bwd_ragged(const float* q, const float* k, const float* v, const float* o, const float* lse,
                                             const float* go, float* gq, float* gk, float* gv, void* workspace, int Bt, int H, int d,
                                             int Lq, int Lk, const int* q_lengths, const int* k_lengths, float scale, void* stream) {
   SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_bwd_ragged: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
-  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
-  return srf_mha_attention_bwd_ragged_strided(q, k, v, o, lse, go, gq, gk, gv, workspace, sq, sk, sk, sq, sq, sq, sk, sk, Bt, H, d,
-                                              Lq, Lk, q_lengths, k_lengths, scale, (hipStream_t)stream);
+  const MhaBwdArgs a = srf_mha_bwd_contiguous(q, k, v, lse, go, gq, gk, gv, workspace, H, d, Lq, Lk, scale);
+  return srf_mha_backward(a, o, a.qs, Bt, true, q_lengths, k_lengths, (hipStream_t)stream);
 }
 
 extern "C" int srf_mha_attention_bwd(const float* q, const float* k, const float* v, const float* o, const float* lse,
                                      const float* go, float* gq, float* gk, float* gv, void* workspace, int Bt, int H, int d, int Lq,
                                      int Lk, float scale, void* stream) {
   SRF_CHECK_ARG(H > 0 && d > 0 && Lq > 0 && Lk > 0, "srf_mha_attention_bwd: bad sizes (H %d, d %d, Lq %d, Lk %d)", H, d, Lq, Lk);
-  const long sq = (long)H * d * Lq, sk = (long)H * d * Lk;
-  return srf_mha_attention_bwd_strided(q, k, v, o, lse, go, gq, gk, gv, workspace, sq, sk, sk, sq, sq, sq, sk, sk, Bt, H, d, Lq, Lk,
-                                       scale, (hipStream_t)stream);
+  const MhaBwdArgs a = srf_mha_bwd_contiguous(q, k, v, lse, go, gq, gk, gv, workspace, H, d, Lq, Lk, scale);
+  return srf_mha_backward(a, o, a.qs, Bt, false, nullptr, nullptr, (hipStream_t)stream);
 }

@@ -16,6 +16,7 @@
 //   x' = res_conv(PReLU(final_norm(merged))) + x              srf_pw_conv_packed
 // Front end and tail are those of the Improved walk (srf_api.hip, forward_walk) without the fused conv pairs.
 #include <vector>
+#include "srf_mha.h"
 #include "srf_plan.h"
 
 static long att_gcd(long a, long b) { return b ? att_gcd(b, a % b) : a; }
@@ -220,8 +221,8 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
     rc = conv(xp, wqkv[i], pa + SRF_PA_Q, bqkv[i], qkv, C, 3 * HD, Ld, nullptr, nullptr, nullptr);
     if (rc) return rc;
     const long s3 = (long)3 * HD * Ld;
-    rc = srf_mha_attention_strided(qkv, qkv + (size_t)HD * Ld, qkv + (size_t)2 * HD * Ld, ao, s3, s3, s3, (long)HD * Ld, Bt, H, d, Ld,
-                                   Ld, q_normalizer, st);
+    const MhaArgs att{qkv, qkv + (size_t)HD * Ld, qkv + (size_t)2 * HD * Ld, ao, s3, s3, s3, (long)HD * Ld, H, d, Ld, Ld, q_normalizer};
+    rc = srf_mha_forward(0, att, Bt, nullptr, nullptr, nullptr, st);
     if (rc) return rc;
     rc = conv(ao, A[SRF_PA_O], pa + SRF_PA_O, A[SRF_PA_O + 1], ay, HD, C, Ld, nullptr, xp, s_mha);
     if (rc) return rc;

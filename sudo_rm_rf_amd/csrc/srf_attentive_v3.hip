@@ -10,7 +10,7 @@
 //     vp = norm(v) + pe_r[:Lk]                                srf_posenc_apply
 //     kv = [K; V]_proj(vp)                                    srf_pw_conv_packed, ONE conv over the concatenated [2 H d, C] weight
 //     qp = Q_proj(norm(q))                                    srf_pw_conv_packed   (norm on load)
-//     o  = softmax(qp^T k / sqrt(d)) v per head               srf_mha_attention_strided(Lq, Lk)
+//     o  = softmax(qp^T k / sqrt(d)) v per head               srf_mha_forward(Lq, Lk)
 //     qn = norm(q)                                            srf_gln_apply_stats  (no statistics: O_proj's residual is a raw pointer)
 //     y  = O_proj(o) + qn                                     srf_pw_conv_packed   (residual, + statistics of out_mha_norm)
 //     f  = ffn.conv(out_mha_norm(y))                          srf_pw_conv_packed   (norm on load, + statistics of ffn.norm)
@@ -20,6 +20,7 @@
 //   x'  = res_conv(PReLU(final_norm(e))) + x                  srf_pw_conv_packed
 // D = 1 has no resampler: v = d_0 goes straight to the last two steps.
 #include <vector>
+#include "srf_mha.h"
 #include "srf_plan.h"
 
 static long att3_gcd(long a, long b) { return b ? att3_gcd(b, a % b) : a; }
@@ -244,7 +245,8 @@ int srf_attentive_v3_forward(const srf_plan* p, const float* const* P, const flo
       rc = conv(levels[ql], A[SRF_PA_Q], pa + SRF_PA_Q, A[SRF_PA_Q + 1], qp, C, HD, Lq, &norms[ql], nullptr, nullptr);
       if (rc) return rc;
       const long s2 = (long)2 * HD * Lk, s1 = (long)HD * Lq;
-      rc = srf_mha_attention_strided(qp, kv, kv + (size_t)HD * Lk, ao, s1, s2, s2, s1, Bt, H, d, Lq, Lk, q_normalizer, st);
+      const MhaArgs att{qp, kv, kv + (size_t)HD * Lk, ao, s1, s2, s2, s1, H, d, Lq, Lk, q_normalizer};
+      rc = srf_mha_forward(0, att, Bt, nullptr, nullptr, nullptr, st);
       if (rc) return rc;
       rc = srf_gln_apply_stats(levels[ql], &norms[ql], qn, nullptr, Bt, C, Lq, stream);
       if (rc) return rc;

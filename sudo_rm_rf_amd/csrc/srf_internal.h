@@ -1,5 +1,5 @@
 // Library-internal entry points: every non-static function that one .hip defines and another calls is declared here, once
-// (those that take PwArgs / PwPairArgs: srf_pw.h; PyrRegArgs: srf_pyr.h).  The defining file includes this header too, so the
+// (those that take PwArgs / PwPairArgs: srf_pw.h; PyrRegArgs: srf_pyr.h; MhaArgs: srf_mha.h).  The defining file includes this header too, so the
 // compiler checks each definition against the declaration its callers see.  The public extern "C" functions come from
 // include/sudormrf_hip.h (through srf_common.h) and are never re-declared.
 #pragma once
@@ -47,42 +47,7 @@ int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci,
                      const float* post_stats, const float* post_wav, int post_mc, void* stream, const float* in_prelu = nullptr,
                      const SrfFrames* lens = nullptr, const SrfFrames* frames = nullptr);   // (both or neither: the ragged overlap-add)
 
-// ---- srf_attention.hip / srf_attentive.hip
-// srf_mha_attention with an example stride per operand (q, k, v as thirds of one [Bt, 3 H d, L] projection)
-int srf_mha_attention_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os, int Bt,
-                              int H, int d, int Lq, int Lk, float scale, hipStream_t st);
-// the same for srf_mha_attention_lse and srf_mha_attention_bwd (srf_attention_bwd.hip); lse and the workspace stay contiguous
-int srf_mha_attention_lse_strided(const float* q, const float* k, const float* v, float* o, float* lse, long qs, long ks, long vs,
-                                  long os, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st);
-int srf_mha_attention_bwd_strided(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* go,
-                                  float* gq, float* gk, float* gv, void* workspace, long qs, long ks, long vs, long os, long gos,
-                                  long gqs, long gks, long gvs, int Bt, int H, int d, int Lq, int Lk, float scale, hipStream_t st);
-// The ragged attention forms (srf_mha_attention*_ragged): the same tensors and row strides Lq / Lk; example b owns
-// q_lengths[b] <= Lq queries and k_lengths[b] <= Lk keys (host arrays of Bt entries, NULL = every example full on that side)
-int srf_mha_attention_ragged_strided(const float* q, const float* k, const float* v, float* o, long qs, long ks, long vs, long os,
-                                     int Bt, int H, int d, int Lq, int Lk, const int* q_lengths, const int* k_lengths, float scale,
-                                     hipStream_t st);
-int srf_mha_attention_lse_ragged_strided(const float* q, const float* k, const float* v, float* o, float* lse, long qs, long ks,
-                                         long vs, long os, int Bt, int H, int d, int Lq, int Lk, const int* q_lengths,
-                                         const int* k_lengths, float scale, hipStream_t st);
-int srf_mha_attention_bwd_ragged_strided(const float* q, const float* k, const float* v, const float* o, const float* lse,
-                                         const float* go, float* gq, float* gk, float* gv, void* workspace, long qs, long ks, long vs,
-                                         long os, long gos, long gqs, long gks, long gvs, int Bt, int H, int d, int Lq, int Lk,
-                                         const int* q_lengths, const int* k_lengths, float scale, hipStream_t st);
-// the two tables of those calls (one per side), checked against the row strides; fn names the caller in the error string
-int srf_mha_ragged_tables(const char* fn, int Bt, int Lq, int Lk, const int* q_lengths, const int* k_lengths, SrfFrames* qf,
-                          SrfFrames* kf);
-// The attention kernels' trailing parameter pack: [float* lse] [SrfFrames q_len, SrfFrames k_len].  Without the tables the row
-// stride is the edge (the uniform instantiations: their arguments and code stay what they were); with them example b's own
-// counts are, read once from the launch arguments into scalar registers.
-__device__ __forceinline__ int srf_mha_qlen(int, int L) { return L; }
-__device__ __forceinline__ int srf_mha_qlen(int, int L, const float*) { return L; }
-__device__ __forceinline__ int srf_mha_qlen(int b, int, const SrfFrames& ql, const SrfFrames&) { return ql.n[b]; }
-__device__ __forceinline__ int srf_mha_qlen(int b, int, const float*, const SrfFrames& ql, const SrfFrames&) { return ql.n[b]; }
-__device__ __forceinline__ int srf_mha_klen(int, int L) { return L; }
-__device__ __forceinline__ int srf_mha_klen(int, int L, const float*) { return L; }
-__device__ __forceinline__ int srf_mha_klen(int b, int, const SrfFrames&, const SrfFrames& kl) { return kl.n[b]; }
-__device__ __forceinline__ int srf_mha_klen(int b, int, const float*, const SrfFrames&, const SrfFrames& kl) { return kl.n[b]; }
+// ---- srf_attentive.hip (softmax attention, which its walk and the next one call: srf_mha.h)
 struct srf_plan;
 int srf_attentive_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                           const float* wav_stats, int mixture_consistency, void* stream);
