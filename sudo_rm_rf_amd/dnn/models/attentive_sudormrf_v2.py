@@ -16,9 +16,9 @@ import math
 import torch
 import torch.nn as nn
 
-from ... import _lib, attention, ops
-from ...engine import ModelEngine, _weights
-from .improved_sudormrf import (_LayerNorm, GlobLN, ConvNormAct, NormAct, DilatedConvNorm, _hip_only)  # noqa: F401
+from ... import attention, ops
+from ._base import _AttentiveModel, _OptIn, _hip_float, _hip_only, _no_random_dropout
+from .improved_sudormrf import _LayerNorm, GlobLN, ConvNormAct, NormAct, DilatedConvNorm, _lazy_levels  # noqa: F401
 
 
 class ConvNorm(nn.Module):
@@ -50,7 +50,7 @@ class DilatedConv(nn.Module):
         return ops.conv1d(_hip_only(input), c.weight.detach(), c.bias.detach(), c.stride[0], c.padding[0], c.dilation[0], c.groups)
 
 
-class PositionalEncoding(nn.Module):
+class PositionalEncoding(_OptIn, nn.Module):
     """The sinusoid table as a registered buffer ``pe`` [1, max_len, d_model]; forward adds its first rows to [batch, len, d_model].
     The kernels READ the buffer (a checkpoint's values are the values used)."""
 
@@ -64,9 +64,6 @@ class PositionalEncoding(nn.Module):
         pe[:, 1::2] = torch.cos(position * div_term)
         self.register_buffer('pe', pe.unsqueeze(0))
 
-    def __getstate__(self):
-        return _without_opt_in(self)
-
     def enable_hip_training(self, flag=True):
         """Opt this module into (flag=False: out of) train() mode with dropout.p > 0 and return self.  With it, every forward
         call in train() mode draws one (seed, offset) pair from torch's CPU default generator (one torch.randint of two int64
@@ -74,7 +71,7 @@ class PositionalEncoding(nn.Module):
         srf_posenc_apply_dropout, whose keep mask is a pure function of (seed, offset, element index): DESIGN.md section 16.2.
         eval() or p == 0 runs the plain kernel.  The output is not differentiable here (TransformerLayer's opt-in is).  The flag
         is a plain attribute: not in state_dict() and dropped from pickles."""
-        return _set_opt_in(self, flag)
+        return self._opt_in(flag)
 
     def forward(self, x):
         p = float(self.dropout.p) if self.training else 0.0
@@ -86,40 +83,7 @@ class PositionalEncoding(nn.Module):
                                       offset=offset).transpose(1, 2).contiguous()
 
 
-def _set_opt_in(module, flag):
-    if flag:
-        module.__dict__["_srf_hip_training"] = True
-    else:
-        module.__dict__.pop("_srf_hip_training", None)
-    return module
-
-
-def _without_opt_in(module):
-    state = module.__dict__.copy()
-    state.pop("_srf_hip_training", None)
-    return state
-
-
-def _wants_grad(module, *tensors):
-    return bool(module.__dict__.get("_srf_hip_training")) and torch.is_grad_enabled() and any(
-        t is not None and t.requires_grad for t in list(tensors) + list(module.parameters()))
-
-
-def _no_random_dropout(module, p):
-    if module.training and p > 0:
-        raise RuntimeError("attentive SuDoRM-RF on HIP is an inference path: in train() mode the reference's dropout (p = %g) is "
-                           "random; call model.eval()" % p)
-
-
-def _hip_float(t):
-    """_hip_only for a tensor autograd has to differentiate: the same refusal, nothing detached or converted."""
-    if t.device.type != "cuda" or t.dtype != torch.float32:
-        raise RuntimeError("sudo_rm_rf_amd modules train on float32 tensors on an MI355X only (no CPU fallback); got %s on %s"
-                           % (t.dtype, t.device))
-    return t
-
-
-class MHAttentionLayer(nn.Module):
+class MHAttentionLayer(_OptIn, nn.Module):
     """Q / K / V / O projections around softmax attention; forward(Q, K, V) takes [batch, len, emb_dim] like the reference.
     forward(Q, K, V, q_lengths, k_lengths) is the ragged form: example b has q_lengths[b] real rows in Q and k_lengths[b] in K / V."""
 
@@ -134,11 +98,6 @@ class MHAttentionLayer(nn.Module):
         self.d_model = d_model
         self.q_normalizer = 1. / math.sqrt(d_model)
 
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_srf_hip_training", None)
-        return state
-
     def enable_hip_training(self, flag=True):
         """Opt this layer into (flag=False: out of) a differentiable forward and return self.  With it, forward(Q, K, V) under
         autograd returns a tensor whose backward runs on HIP (srf_mha_attention_bwd between ops.pw_conv / ops.pw_wgrad,
@@ -146,11 +105,7 @@ class MHAttentionLayer(nn.Module):
         V require grad -- self-attention (one tensor three times) and cross-attention (Lq != Lk) alike.  Without autograd, and
         without the opt-in, the inference forward on detached weights is untouched; train() with dropout.p > 0 keeps raising.
         The flag is a plain attribute: not in state_dict() and dropped from pickles."""
-        if flag:
-            self.__dict__["_srf_hip_training"] = True
-        else:
-            self.__dict__.pop("_srf_hip_training", None)
-        return self
+        return self._opt_in(flag)
 
     def forward(self, Q, K, V, q_lengths=None, k_lengths=None):
         """q_lengths / k_lengths (each a list or a CPU tensor of `batch` entries, or None = full; both None: nothing changes):
@@ -160,8 +115,7 @@ class MHAttentionLayer(nn.Module):
         ignored, Q / K / V get exactly zero gradient at or past their lengths, and the eight parameter gradients are the sum of
         the examples' own batch-1 gradients; the padding must hold finite values and influences nothing."""
         _no_random_dropout(self, self.dropout.p)
-        if self.__dict__.get("_srf_hip_training") and torch.is_grad_enabled() and any(
-                t.requires_grad for t in [Q, K, V] + list(self.parameters())):
+        if self._wants_grad(Q, K, V):
             return attention.mha_layer_train(self, *(_hip_float(x) for x in (Q, K, V)), q_lengths=q_lengths, k_lengths=k_lengths)
         t = lambda x: _hip_only(x).transpose(1, 2).contiguous()
         lin = lambda m, x: ops.pw_conv(x, m.weight.detach(), m.bias.detach())
@@ -173,7 +127,24 @@ class MHAttentionLayer(nn.Module):
         return attention.zero_past(lin(self.O_proj, o), attention._host_lengths(q_lengths, "q_lengths")).transpose(1, 2).contiguous()
 
 
-class TransformerLayer(nn.Module):
+def _transformer_tail(layer, o, residual, raw=False):
+    """What both transformer layers end in: O projection of the attention output `o` + `residual`, out_mha_norm on load of the
+    1x1 FFN, the FFN's norm and PReLU added to the normed residual branch (srf_gln_apply2_add), out_norm.  raw = True:
+    (z, sums of z) with out_norm still to apply."""
+    d = lambda p: p.detach()
+    m = layer.mha
+    s_mha, s_ffn, s_out = (ops.new_sums(o.shape[0], o.device) for _ in range(3))
+    y = ops.pw_conv(o, d(m.O_proj.weight), d(m.O_proj.bias), residual=residual, out_sums=s_mha)
+    g, b = d(layer.out_mha_norm.gamma), d(layer.out_mha_norm.beta)
+    f = ops.pw_conv(y, d(layer.ffn.conv.weight), d(layer.ffn.conv.bias), in_sums=s_mha, in_gamma=g, in_beta=b, out_sums=s_ffn)
+    z = attention.gln_apply2_add(f, s_ffn, d(layer.ffn.norm.gamma), d(layer.ffn.norm.beta), d(layer.ffn.act.weight), y, s_mha, g, b,
+                                 out_sums=s_out)
+    if raw:
+        return z, s_out
+    return ops.gln_apply(z, s_out, d(layer.out_norm.gamma), d(layer.out_norm.beta))
+
+
+class TransformerLayer(_OptIn, nn.Module):
     """[batch, channels, len] -> the same: position table, attention + residual, GlobLN, 1x1 FFN + residual, GlobLN."""
 
     def __init__(self, emb_dim, d_model, n_heads, dropout=0.1, max_len=5000):
@@ -183,9 +154,6 @@ class TransformerLayer(nn.Module):
         self.out_mha_norm = GlobLN(emb_dim)
         self.ffn = ConvNormAct(emb_dim, emb_dim, 1, stride=1, groups=1)
         self.pos_enc = PositionalEncoding(d_model=emb_dim, dropout=dropout, max_len=max_len)
-
-    def __getstate__(self):
-        return _without_opt_in(self)
 
     def enable_hip_training(self, flag=True):
         """Opt this layer -- and the pos_enc and mha it owns -- into (flag=False: out of) a differentiable forward and return
@@ -197,16 +165,15 @@ class TransformerLayer(nn.Module):
         p > 0 keeps raising.  The flag is a plain attribute: not in state_dict() and dropped from pickles."""
         self.pos_enc.enable_hip_training(flag)
         self.mha.enable_hip_training(flag)
-        return _set_opt_in(self, flag)
+        return self._opt_in(flag)
 
     def forward(self, x, in_sums=None, in_gamma=None, in_beta=None):
         """The kernel sequence srf_forward runs on the deepest level (stand-alone use / unit tests).  in_sums / in_gamma /
         in_beta: a GlobLN to apply to x on load (the level's lazy norm); returns the layer's output, out_norm applied."""
-        if _wants_grad(self, x, in_gamma, in_beta):
+        if self._wants_grad(x, in_gamma, in_beta):
             return attention.transformer_layer_train(self, _hip_float(x), in_sums, in_gamma, in_beta)
         _no_random_dropout(self, self.pos_enc.dropout.p)
         x = _hip_only(x)
-        Bt, dev = x.shape[0], x.device
         d = lambda p: p.detach()
         m = self.mha
         xp = attention.posenc_apply(x, d(self.pos_enc.pe), in_sums, in_gamma, in_beta)
@@ -215,17 +182,10 @@ class TransformerLayer(nn.Module):
         qkv = ops.pw_conv(xp, wqkv, bqkv)
         hd = m.n_heads * m.d_model
         q, k, v = (qkv[:, i * hd:(i + 1) * hd].contiguous() for i in range(3))
-        o = attention.mha_attention(q, k, v, m.n_heads, m.q_normalizer)
-        s_mha, s_ffn, s_out = (ops.new_sums(Bt, dev) for _ in range(3))
-        y = ops.pw_conv(o, d(m.O_proj.weight), d(m.O_proj.bias), residual=xp, out_sums=s_mha)
-        g, b = d(self.out_mha_norm.gamma), d(self.out_mha_norm.beta)
-        f = ops.pw_conv(y, d(self.ffn.conv.weight), d(self.ffn.conv.bias), in_sums=s_mha, in_gamma=g, in_beta=b, out_sums=s_ffn)
-        z = attention.gln_apply2_add(f, s_ffn, d(self.ffn.norm.gamma), d(self.ffn.norm.beta), d(self.ffn.act.weight), y, s_mha, g, b,
-                                     out_sums=s_out)
-        return ops.gln_apply(z, s_out, d(self.out_norm.gamma), d(self.out_norm.beta))
+        return _transformer_tail(self, attention.mha_attention(q, k, v, m.n_heads, m.q_normalizer), xp)
 
 
-class AttentiveUConvBlock(nn.Module):
+class AttentiveUConvBlock(_OptIn, nn.Module):
     """U-ConvBlock whose deepest level goes through a TransformerLayer before the upsample-and-add."""
 
     def __init__(self, out_channels=128, in_channels=512, upsampling_depth=4, n_heads=4, att_dims=256, att_dropout=0.1):
@@ -242,9 +202,6 @@ class AttentiveUConvBlock(nn.Module):
         self.res_conv = nn.Conv1d(in_channels, out_channels, 1)
         self.attention = TransformerLayer(in_channels, att_dims, n_heads, dropout=att_dropout, max_len=5000)
 
-    def __getstate__(self):
-        return _without_opt_in(self)
-
     def enable_hip_training(self, flag=True):
         """Opt this block -- and the TransformerLayer it owns -- into (flag=False: out of) a differentiable forward and return
         self.  With it, forward(x) under autograd is one autograd node around the block (attention.uconv_block_train) whose
@@ -252,7 +209,7 @@ class AttentiveUConvBlock(nn.Module):
         buffer and gets none.  Dropout as in TransformerLayer.enable_hip_training.  Without autograd, and without the opt-in,
         nothing changes.  The flag is a plain attribute: not in state_dict() and dropped from pickles."""
         self.attention.enable_hip_training(flag)
-        return _set_opt_in(self, flag)
+        return self._opt_in(flag)
 
     def forward(self, x):
         """The kernel sequence srf_forward runs for one block (stand-alone use / unit tests)."""
@@ -261,36 +218,21 @@ class AttentiveUConvBlock(nn.Module):
             raise RuntimeError("AttentiveUConvBlock: upsampling_depth = %d; the HIP path needs at least 2 levels" % D)
         if x.dim() == 3 and x.shape[-1] % (1 << (D - 1)):
             raise RuntimeError("time length %d must be divisible by 2^(depth-1)" % x.shape[-1])
-        if _wants_grad(self, x):
+        if self._wants_grad(x):
             return attention.uconv_block_train(self, _hip_float(x).contiguous())
         x = _hip_only(x)
-        Bt, _, L = x.shape
-        dev = x.device
         d = lambda p: p.detach()
-        s_in = ops.new_sums(Bt, dev)
-        src = ops.pw_conv(x, d(self.proj_1x1.conv.weight), d(self.proj_1x1.conv.bias), out_sums=s_in)
-        g_in, b_in, a_in = d(self.proj_1x1.norm.gamma), d(self.proj_1x1.norm.beta), d(self.proj_1x1.act.weight)
-        levels, sums = [], []
-        for k in range(D):
-            m = self.spp_dw[k]
-            s_k = ops.new_sums(Bt, dev)
-            src = ops.dwconv5(src, d(m.conv.weight), d(m.conv.bias), 1 if k == 0 else 2, in_sums=s_in, in_gamma=g_in, in_beta=b_in,
-                              in_prelu=a_in, out_sums=s_k)
-            levels.append(src)
-            sums.append(s_k)
-            s_in, g_in, b_in, a_in = s_k, d(m.norm.gamma), d(m.norm.beta), None
-        z = self.attention(levels[-1], s_in, g_in, b_in)          # (out_norm already applied: merged as a plain level below)
-        top = z
+        levels, norms = _lazy_levels(self, x)
+        top = self.attention(levels[-1], *norms[-1])              # (out_norm already applied: merged as a plain level below)
         for k in range(D - 2, -1, -1):
-            m = self.spp_dw[k]
-            top = ops.gln_apply(levels[k], sums[k], d(m.norm.gamma), d(m.norm.beta)) + top.repeat_interleave(2, dim=-1)
-        s_m = ops.gln_stats(top.contiguous(), Bt)
+            top = ops.gln_apply(levels[k], *norms[k]) + top.repeat_interleave(2, dim=-1)
+        s_m = ops.gln_stats(top.contiguous(), x.shape[0])
         return ops.pw_conv(top.contiguous(), d(self.res_conv.weight), d(self.res_conv.bias), in_sums=s_m,
                            in_gamma=d(self.final_norm.norm.gamma), in_beta=d(self.final_norm.norm.beta),
                            in_prelu=d(self.final_norm.act.weight), residual=x)
 
 
-class SuDORMRF(nn.Module):
+class SuDORMRF(_AttentiveModel):
     """Drop-in for the reference's attentive ``SuDORMRF``: forward([batch, 1, time]) -> [batch, num_sources, time]."""
 
     def __init__(self,
@@ -334,77 +276,10 @@ class SuDORMRF(nn.Module):
         torch.nn.init.xavier_uniform_(self.decoder.weight)
         self.mask_nl_class = nn.ReLU()
 
-    # -- engine plumbing (kept out of state_dict and rebuilt lazily, e.g. after unpickling) --------
     def _config_tuple(self):
         mha = self.sm[0].attention.mha
         return ("attentive", 1, self.out_channels, self.in_channels, self.num_blocks, self.upsampling_depth,
                 self.enc_kernel_size, self.enc_num_basis, self.num_sources, 1, (mha.n_heads, mha.d_model))
 
-    def _engine(self):
-        eng = self.__dict__.get("_srf_engine")
-        if eng is None or eng.cfg_tuple != self._config_tuple():
-            eng = ModelEngine(self._config_tuple())
-            eng.multi_stream = False          # single stream only: the sub-batch split is not extended to this variant
-            self.__dict__["_srf_engine"] = eng
-        return eng
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_srf_engine", None)
-        return state
-
-    def _check_inference(self, weights):
-        dropout = max([self.sm[0].attention.pos_enc.dropout.p] + [b.attention.pos_enc.dropout.p for b in self.sm])
-        _no_random_dropout(self, dropout)
-        if torch.is_grad_enabled() and any(t.requires_grad for t in weights):
-            raise RuntimeError("attentive SuDoRM-RF on HIP has an inference forward only (no backward kernels): run it under "
-                               "torch.no_grad()")
-
-    def forward(self, input_wav):
-        """[batch, 1, time] float -> [batch, num_sources, time] float32: one srf_forward call on the caller's stream."""
-        if not isinstance(input_wav, torch.Tensor):
-            raise TypeError("input must be a torch.Tensor")
-        if input_wav.dim() != 3 or input_wav.shape[1] != 1:
-            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(input_wav.shape),))
-        weights = _weights(self)
-        self._check_inference(weights)
-        if input_wav.device.type != "cuda":
-            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
-                                "fallback (use the reference implementation for CPU inference)." % input_wav.device)
-        params = [p.detach() for p in weights]
-        for p in params:
-            if p.device != input_wav.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters and buffers must be contiguous float32 on %s" % input_wav.device)
-        x = input_wav.detach().to(torch.float32).contiguous()
-        batch, _, T = x.shape
-        if batch == 0 or T == 0:
-            raise RuntimeError("empty input %s" % (tuple(input_wav.shape),))
-        eng = self._engine()
-        with torch.cuda.device(x.device), eng._run_lock(x.device):
-            plan = eng.plan_for(batch, T, x.device)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
-            out = torch.empty((batch, self.num_sources, T), dtype=torch.float32, device=x.device)
-            plan.forward(eng._param_table(params, x.device), x, out)
-            eng.last_plan = plan
-        return out
-
-    def forward_ragged(self, input_wav, lengths):
-        raise NotImplementedError("the attentive model has no ragged kernels: run the utterances one by one "
-                                  "(pipeline.separate_list does).  Attention alone takes a ragged batch: "
-                                  "MHAttentionLayer.forward(Q, K, V, q_lengths, k_lengths).")
-
-    def pad_to_appropriate_length(self, x):
-        """Kept for API parity: up to a multiple of lcm(K // 2, 2^D), only when the length is not one already.  The HIP path
-        folds the padding into its bounds checks and never materialises the padded tensor."""
-        values_to_pad = int(x.shape[-1]) % self.lcm
-        if values_to_pad:
-            padded = torch.zeros(list(x.shape[:-1]) + [x.shape[-1] + self.lcm - values_to_pad], dtype=torch.float32,
-                                 device=x.device)
-            padded[..., :x.shape[-1]] = x
-            return padded
-        return x
-
-    @staticmethod
-    def remove_trailing_zeros(padded_x, initial_x):
-        return padded_x[..., :initial_x.shape[-1]]
+    def _transformer_layers(self):
+        return [blk.attention for blk in self.sm]

@@ -20,11 +20,11 @@ import math
 import torch
 import torch.nn as nn
 
-from ... import _lib, attention, ops
-from ...engine import ModelEngine, _weights
-from .improved_sudormrf import (_LayerNorm, GlobLN, ConvNormAct, NormAct, DilatedConvNorm, _hip_only)  # noqa: F401
+from ... import attention, ops
+from ._base import _AttentiveModel, _hip_only, _no_random_dropout
+from .improved_sudormrf import _LayerNorm, GlobLN, ConvNormAct, NormAct, DilatedConvNorm, _lazy_levels  # noqa: F401
 from .attentive_sudormrf_v2 import (ConvNorm, DilatedConv, PositionalEncoding, MHAttentionLayer, TransformerLayer,  # noqa: F401
-                                    _no_random_dropout)
+                                    _transformer_tail)
 
 
 class ConditionalTransformerLayer(nn.Module):
@@ -45,7 +45,6 @@ class ConditionalTransformerLayer(nn.Module):
         out_norm applied; raw = True: (z, sums of z) with out_norm still to apply, as the walk keeps it."""
         _no_random_dropout(self, self.pos_enc.dropout.p)
         q, v = _hip_only(q), _hip_only(v)
-        Bt, dev = q.shape[0], q.device
         d = lambda p: p.detach()
         m = self.mha
         hd = m.n_heads * m.d_model
@@ -61,15 +60,7 @@ class ConditionalTransformerLayer(nn.Module):
             qp = ops.pw_conv(q, d(m.Q_proj.weight), d(m.Q_proj.bias))
             qn = q
         o = attention.mha_attention(qp, kv[:, :hd].contiguous(), kv[:, hd:].contiguous(), m.n_heads, m.q_normalizer)
-        s_mha, s_ffn, s_out = (ops.new_sums(Bt, dev) for _ in range(3))
-        y = ops.pw_conv(o, d(m.O_proj.weight), d(m.O_proj.bias), residual=qn, out_sums=s_mha)
-        g, b = d(self.out_mha_norm.gamma), d(self.out_mha_norm.beta)
-        f = ops.pw_conv(y, d(self.ffn.conv.weight), d(self.ffn.conv.bias), in_sums=s_mha, in_gamma=g, in_beta=b, out_sums=s_ffn)
-        z = attention.gln_apply2_add(f, s_ffn, d(self.ffn.norm.gamma), d(self.ffn.norm.beta), d(self.ffn.act.weight), y, s_mha, g, b,
-                                     out_sums=s_out)
-        if raw:
-            return z, s_out
-        return ops.gln_apply(z, s_out, d(self.out_norm.gamma), d(self.out_norm.beta))
+        return _transformer_tail(self, o, qn, raw=raw)
 
 
 class AttentiveUConvBlock(nn.Module):
@@ -95,32 +86,20 @@ class AttentiveUConvBlock(nn.Module):
         """The kernel sequence srf_forward runs for one block (stand-alone use / unit tests)."""
         D = self.depth
         x = _hip_only(x)
-        Bt, dev = x.shape[0], x.device
         d = lambda p: p.detach()
-        s_in = ops.new_sums(Bt, dev)
-        src = ops.pw_conv(x, d(self.proj_1x1.conv.weight), d(self.proj_1x1.conv.bias), out_sums=s_in)
-        g_in, b_in, a_in = d(self.proj_1x1.norm.gamma), d(self.proj_1x1.norm.beta), d(self.proj_1x1.act.weight)
-        levels, norms = [], []
-        for k in range(D):
-            m = self.spp_dw[k]
-            s_k = ops.new_sums(Bt, dev)
-            src = ops.dwconv5(src, d(m.conv.weight), d(m.conv.bias), 1 if k == 0 else 2, in_sums=s_in, in_gamma=g_in, in_beta=b_in,
-                              in_prelu=a_in, out_sums=s_k)
-            levels.append(src)
-            norms.append((s_k, d(m.norm.gamma), d(m.norm.beta)))
-            s_in, g_in, b_in, a_in = s_k, d(m.norm.gamma), d(m.norm.beta), None
+        levels, norms = _lazy_levels(self, x)
         v, v_norm = levels[-1], norms[-1]
         for r, layer in enumerate(self.attentive_resamplers):
             v, s_out = layer(levels[D - 2 - r], v, norms[D - 2 - r], v_norm, raw=True)
             v_norm = (s_out, d(layer.out_norm.gamma), d(layer.out_norm.beta))
-        s_fin = ops.new_sums(Bt, dev)
+        s_fin = ops.new_sums(x.shape[0], x.device)
         e = attention.gln_apply_stats(v, *v_norm, out_sums=s_fin)
         return ops.pw_conv(e, d(self.res_conv.weight), d(self.res_conv.bias), in_sums=s_fin,
                            in_gamma=d(self.final_norm.norm.gamma), in_beta=d(self.final_norm.norm.beta),
                            in_prelu=d(self.final_norm.act.weight), residual=x)
 
 
-class SuDORMRF(nn.Module):
+class SuDORMRF(_AttentiveModel):
     """Drop-in for the reference's attentive v3 ``SuDORMRF``: forward([batch, 1, time]) -> [batch, num_sources, time]."""
 
     def __init__(self,
@@ -164,83 +143,15 @@ class SuDORMRF(nn.Module):
         torch.nn.init.xavier_uniform_(self.decoder.weight)
         self.mask_nl_class = nn.ReLU()
 
-    # -- engine plumbing (kept out of state_dict and rebuilt lazily, e.g. after unpickling) --------
+    def _transformer_layers(self):
+        return [layer for blk in self.sm for layer in blk.attentive_resamplers]
+
     def _heads_dims(self):
         """(n_heads, att_dims) of the blocks' resamplers; a depth-1 model has none and the plan only asks for positive values."""
-        for blk in self.sm:
-            for layer in blk.attentive_resamplers:
-                return (layer.mha.n_heads, layer.mha.d_model)
+        for layer in self._transformer_layers():
+            return (layer.mha.n_heads, layer.mha.d_model)
         return (4, 256)
 
     def _config_tuple(self):
         return ("attentive_v3", 1, self.out_channels, self.in_channels, self.num_blocks, self.upsampling_depth,
                 self.enc_kernel_size, self.enc_num_basis, self.num_sources, 1, self._heads_dims())
-
-    def _engine(self):
-        eng = self.__dict__.get("_srf_engine")
-        if eng is None or eng.cfg_tuple != self._config_tuple():
-            eng = ModelEngine(self._config_tuple())
-            eng.multi_stream = False          # single stream only: the sub-batch split is not extended to this variant
-            self.__dict__["_srf_engine"] = eng
-        return eng
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_srf_engine", None)
-        return state
-
-    def _check_inference(self, weights):
-        dropout = max([0.0] + [layer.pos_enc.dropout.p for blk in self.sm for layer in blk.attentive_resamplers])
-        _no_random_dropout(self, dropout)
-        if torch.is_grad_enabled() and any(t.requires_grad for t in weights):
-            raise RuntimeError("attentive SuDoRM-RF on HIP has an inference forward only (no backward kernels): run it under "
-                               "torch.no_grad()")
-
-    def forward(self, input_wav):
-        """[batch, 1, time] float -> [batch, num_sources, time] float32: one srf_forward call on the caller's stream."""
-        if not isinstance(input_wav, torch.Tensor):
-            raise TypeError("input must be a torch.Tensor")
-        if input_wav.dim() != 3 or input_wav.shape[1] != 1:
-            raise RuntimeError("expected input of shape [batch, 1, time], got %s" % (tuple(input_wav.shape),))
-        weights = _weights(self)
-        self._check_inference(weights)
-        if input_wav.device.type != "cuda":
-            raise _lib.SrfError("sudo_rm_rf_amd runs on an MI355X only: input is on %s.  There is deliberately no CPU "
-                                "fallback (use the reference implementation for CPU inference)." % input_wav.device)
-        params = [p.detach() for p in weights]
-        for p in params:
-            if p.device != input_wav.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise _lib.SrfError("all parameters and buffers must be contiguous float32 on %s" % input_wav.device)
-        x = input_wav.detach().to(torch.float32).contiguous()
-        batch, _, T = x.shape
-        if batch == 0 or T == 0:
-            raise RuntimeError("empty input %s" % (tuple(input_wav.shape),))
-        eng = self._engine()
-        with torch.cuda.device(x.device), eng._run_lock(x.device):
-            plan = eng.plan_for(batch, T, x.device)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
-            out = torch.empty((batch, self.num_sources, T), dtype=torch.float32, device=x.device)
-            plan.forward(eng._param_table(params, x.device), x, out)
-            eng.last_plan = plan
-        return out
-
-    def forward_ragged(self, input_wav, lengths):
-        raise NotImplementedError("the attentive model has no ragged kernels: run the utterances one by one "
-                                  "(pipeline.separate_list does).  Attention alone takes a ragged batch: "
-                                  "MHAttentionLayer.forward(Q, K, V, q_lengths, k_lengths).")
-
-    def pad_to_appropriate_length(self, x):
-        """Kept for API parity: up to a multiple of lcm(K // 2, 2^D), only when the length is not one already.  The HIP path
-        folds the padding into its bounds checks and never materialises the padded tensor."""
-        values_to_pad = int(x.shape[-1]) % self.lcm
-        if values_to_pad:
-            padded = torch.zeros(list(x.shape[:-1]) + [x.shape[-1] + self.lcm - values_to_pad], dtype=torch.float32,
-                                 device=x.device)
-            padded[..., :x.shape[-1]] = x
-            return padded
-        return x
-
-    @staticmethod
-    def remove_trailing_zeros(padded_x, initial_x):
-        return padded_x[..., :initial_x.shape[-1]]

@@ -13,22 +13,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine import ModelEngine
-
-
-def _hip_only(t):
-    if t.device.type != "cuda":
-        raise RuntimeError("sudo_rm_rf_amd modules run on an MI355X only (no CPU fallback); got a "
-                           "tensor on %s" % t.device)
-    return t.detach().to(torch.float32).contiguous()
-
-
-def _refuse_autograd(what, tensors):
-    """The causal model has no HIP backward: never return an output that autograd cannot differentiate."""
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
-        raise NotImplementedError(
-            "%s: the causal SuDoRM-RF (v3) model is forward-only on this path (no training / backward); run it under "
-            "torch.no_grad() or torch.inference_mode()" % what)
+from ._base import _Model, _OptIn, _hip_only, _refuse_autograd, pad_to_multiple_of_least_samples
 
 
 def _pw(x, weight, bias, **kw):
@@ -163,7 +148,7 @@ class UConvBlock(nn.Module):
         return _pw(merged, wr, br, residual=x)
 
 
-class CausalSuDORMRF(nn.Module):
+class CausalSuDORMRF(_OptIn, _Model):
     """Drop-in for the reference ``CausalSuDORMRF``: forward([batch, A, time]) -> [batch, S * A, time]."""
 
     def __init__(self,
@@ -228,24 +213,10 @@ class CausalSuDORMRF(nn.Module):
         torch.nn.init.xavier_uniform_(self.decoder.weight)
         self.mask_nl_class = nn.PReLU()
 
-    # -- engine plumbing (kept out of state_dict and rebuilt lazily, e.g. after unpickling) --------
     def _config_tuple(self):
         scales = tuple((float(b.alpha), float(b.beta)) for b in self.sm)
         return ("causal", self.in_audio_channels, self.out_channels, self.in_channels, self.num_blocks,
                 self.upsampling_depth, self.enc_kernel_size, self.enc_num_basis, self.num_sources, 1, scales)
-
-    def _engine(self):
-        eng = self.__dict__.get("_srf_engine")
-        if eng is None or eng.cfg_tuple != self._config_tuple():
-            eng = ModelEngine(self._config_tuple())
-            self.__dict__["_srf_engine"] = eng
-        return eng
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_srf_engine", None)
-        state.pop("_srf_hip_training", None)
-        return state
 
     def enable_hip_training(self, flag=True):
         """Opt this model into (flag=False: out of) the HIP training step and return self.  With it, a forward that autograd
@@ -256,23 +227,18 @@ class CausalSuDORMRF(nn.Module):
         The flag is a plain attribute beside the engine: not in state_dict() and dropped from pickles, so a model that was
         unpickled has to opt in again.  Not claimed: torch.nn.DataParallel replicas and copy.deepcopy of an opted-in model
         (neither carries the flag)."""
-        if flag:
-            self.__dict__["_srf_hip_training"] = True
-        else:
-            self.__dict__.pop("_srf_hip_training", None)
-        return self
+        return self._opt_in(flag)
 
     def forward(self, input_wav):
         """[batch, A, time] float -> [batch, num_sources * A, time] float32, one srf_forward call.  Inference only, unless
         enable_hip_training() was called: then a forward under autograd is the HIP training step."""
-        tensors = [input_wav if isinstance(input_wav, torch.Tensor) else None] + list(self.parameters())
-        if self.__dict__.get("_srf_hip_training") and torch.is_grad_enabled() and any(
-                t is not None and t.requires_grad for t in tensors):
-            if tensors[0] is not None and tensors[0].requires_grad:
+        mixture = input_wav if isinstance(input_wav, torch.Tensor) else None
+        if self._wants_grad(mixture):
+            if mixture is not None and mixture.requires_grad:
                 raise NotImplementedError("CausalSuDORMRF.forward: the HIP training step has no gradient w.r.t. the input "
                                           "mixture; pass a mixture that does not require grad")
             return self._engine().run_train(self, input_wav, self.in_audio_channels)
-        _refuse_autograd("CausalSuDORMRF.forward", tensors)
+        _refuse_autograd("CausalSuDORMRF.forward", [mixture] + list(self.parameters()))
         return self._engine().run(self, input_wav, self.in_audio_channels)
 
     def stream(self, batch=1, max_chunk=None, device=None):
@@ -290,21 +256,7 @@ class CausalSuDORMRF(nn.Module):
         from ...streaming import CausalStreamPool
         return CausalStreamPool(self, capacity, max_chunk=max_chunk, device=device)
 
-    def pad_to_appropriate_length(self, x):
-        """Kept for API parity; the HIP path folds the padding into its bounds checks."""
-        input_length = x.shape[-1]
-        n = self.n_least_samples_req
-        if input_length < n:
-            values_to_pad = n
-        else:
-            values_to_pad = (input_length // n + (1 if input_length % n else 0)) * n
-        padded = torch.zeros(list(x.shape[:-1]) + [values_to_pad], dtype=torch.float32, device=x.device)
-        padded[..., :input_length] = x
-        return padded
-
-    @staticmethod
-    def remove_trailing_zeros(padded_x, initial_x):
-        return padded_x[..., :initial_x.shape[-1]]
+    pad_to_appropriate_length = pad_to_multiple_of_least_samples
 
 
 __all__ = ["ScaledWSConv1d", "ConvAct", "UConvBlock", "CausalSuDORMRF"]

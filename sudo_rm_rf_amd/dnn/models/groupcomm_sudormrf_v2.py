@@ -10,9 +10,8 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine import ModelEngine
-from .improved_sudormrf import (_LayerNorm, GlobLN, ConvNormAct, NormAct, DilatedConvNorm,  # noqa: F401
-                                UConvBlock, _hip_only)
+from ._base import _Model, _hip_only, pad_to_multiple_of_least_samples
+from .improved_sudormrf import _LayerNorm, GlobLN, ConvNormAct, NormAct, DilatedConvNorm, UConvBlock  # noqa: F401
 
 
 class TAC(nn.Module):
@@ -60,7 +59,7 @@ class GC_UConvBlock(nn.Module):
         return output.view(batch_size, N, L)
 
 
-class GroupCommSudoRmRf(nn.Module):
+class GroupCommSudoRmRf(_Model):
     """Drop-in for the reference ``GroupCommSudoRmRf``: forward([batch, in_audio_channels, time]) ->
     [batch, num_sources * in_audio_channels, time]."""
 
@@ -119,18 +118,6 @@ class GroupCommSudoRmRf(nn.Module):
                 self.upsampling_depth, self.enc_kernel_size, self.enc_num_basis, self.num_sources,
                 self._group_size())
 
-    def _engine(self):
-        eng = self.__dict__.get("_srf_engine")
-        if eng is None or eng.cfg_tuple != self._config_tuple():
-            eng = ModelEngine(self._config_tuple())
-            self.__dict__["_srf_engine"] = eng
-        return eng
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_srf_engine", None)
-        return state
-
     def forward(self, input_wav):
         return self._engine().run(self, input_wav, self.in_audio_channels)
 
@@ -148,18 +135,4 @@ class GroupCommSudoRmRf(nn.Module):
         model, on by default) -- and exactly zero past it; stats [batch, 2] = {mean, std} per row.  eval() / no_grad only."""
         return self._engine().run_separate_ragged(self, input_wav, lengths, mixture_consistency)
 
-    def pad_to_appropriate_length(self, x):
-        """Kept for API parity (reference :324-335); the HIP path never materialises the padding."""
-        input_length = x.shape[-1]
-        n = self.n_least_samples_req
-        if input_length < n:
-            values_to_pad = n
-        else:
-            values_to_pad = (input_length // n + (1 if input_length % n else 0)) * n
-        padded = torch.zeros(list(x.shape[:-1]) + [values_to_pad], dtype=torch.float32, device=x.device)
-        padded[..., :input_length] = x
-        return padded
-
-    @staticmethod
-    def remove_trailing_zeros(padded_x, initial_x):
-        return padded_x[..., :initial_x.shape[-1]]
+    pad_to_appropriate_length = pad_to_multiple_of_least_samples       # (reference :324-335)

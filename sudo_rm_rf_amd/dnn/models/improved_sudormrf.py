@@ -12,14 +12,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...engine import ModelEngine
-
-
-def _hip_only(t):
-    if t.device.type != "cuda":
-        raise RuntimeError("sudo_rm_rf_amd modules run on an MI355X only (no CPU fallback); got a "
-                           "tensor on %s" % t.device)
-    return t.detach().to(torch.float32).contiguous()
+from ._base import _Model, _hip_only, pad_to_multiple_of_least_samples
 
 
 class _LayerNorm(nn.Module):
@@ -101,6 +94,29 @@ class DilatedConvNorm(nn.Module):
         return ops.gln_apply(y, sums, self.norm.gamma.detach(), self.norm.beta.detach())
 
 
+def _lazy_levels(block, x):
+    """What the Improved and both attentive blocks begin with: proj_1x1's convolution, then the block's `depth` depthwise
+    levels (srf_dwconv5, stride 1 then 2), each applying its producer's GlobLN (+ proj_1x1's PReLU in front of level 0) on
+    load and leaving its own statistics behind.  Returns (levels, norms): norms[k] = (sums, gamma, beta) of level k, not yet
+    applied.  x: what _hip_only returned."""
+    Bt, dev = x.shape[0], x.device
+    d = lambda p: p.detach()
+    p = block.proj_1x1
+    s_in = ops.new_sums(Bt, dev)
+    src = ops.pw_conv(x, d(p.conv.weight), d(p.conv.bias), out_sums=s_in)
+    g_in, b_in, a_in = d(p.norm.gamma), d(p.norm.beta), d(p.act.weight)
+    levels, norms = [], []
+    for k in range(block.depth):
+        m = block.spp_dw[k]
+        s_k = ops.new_sums(Bt, dev)
+        src = ops.dwconv5(src, d(m.conv.weight), d(m.conv.bias), 1 if k == 0 else 2, in_sums=s_in, in_gamma=g_in, in_beta=b_in,
+                          in_prelu=a_in, out_sums=s_k)
+        levels.append(src)
+        norms.append((s_k, d(m.norm.gamma), d(m.norm.beta)))
+        s_in, g_in, b_in, a_in = s_k, d(m.norm.gamma), d(m.norm.beta), None
+    return levels, norms
+
+
 class UConvBlock(nn.Module):
     """U-ConvBlock (reference :162-220): 1x1 expand -> depthwise pyramid -> upsample/add -> 1x1."""
 
@@ -126,30 +142,17 @@ class UConvBlock(nn.Module):
         D = self.depth
         if L % (1 << (D - 1)):
             raise RuntimeError("time length %d must be divisible by 2^(depth-1)" % L)
-        dev = x.device
         d = lambda p: p.detach()
-        s_proj = ops.new_sums(Bt, dev)
-        y1 = ops.pw_conv(x, d(self.proj_1x1.conv.weight), d(self.proj_1x1.conv.bias), out_sums=s_proj)
-        levels, sums = [], []
-        src, s_in, g_in, b_in, a_in = y1, s_proj, d(self.proj_1x1.norm.gamma), d(self.proj_1x1.norm.beta), \
-            d(self.proj_1x1.act.weight)
-        for k in range(D):
-            m = self.spp_dw[k]
-            s_k = ops.new_sums(Bt, dev)
-            lv = ops.dwconv5(src, d(m.conv.weight), d(m.conv.bias), 1 if k == 0 else 2, in_sums=s_in,
-                             in_gamma=g_in, in_beta=b_in, in_prelu=a_in, out_sums=s_k)
-            levels.append(lv)
-            sums.append(s_k)
-            src, s_in, g_in, b_in, a_in = lv, s_k, d(m.norm.gamma), d(m.norm.beta), None
-        s_m = ops.new_sums(Bt, dev)
-        merged = ops.merge(levels, sums, [d(m.norm.gamma) for m in self.spp_dw],
-                           [d(m.norm.beta) for m in self.spp_dw], out_sums=s_m)
+        levels, norms = _lazy_levels(self, x)
+        s_m = ops.new_sums(Bt, x.device)
+        sums, gammas, betas = zip(*norms)
+        merged = ops.merge(levels, sums, gammas, betas, out_sums=s_m)
         return ops.pw_conv(merged, d(self.res_conv.weight), d(self.res_conv.bias), in_sums=s_m,
                            in_gamma=d(self.final_norm.norm.gamma), in_beta=d(self.final_norm.norm.beta),
                            in_prelu=d(self.final_norm.act.weight), residual=x)
 
 
-class SuDORMRF(nn.Module):
+class SuDORMRF(_Model):
     """Drop-in for the reference ``SuDORMRF`` (:223-318): forward([batch,1,time]) -> [batch,S,time]."""
 
     def __init__(self,
@@ -188,22 +191,9 @@ class SuDORMRF(nn.Module):
         torch.nn.init.xavier_uniform_(self.decoder.weight)
         self.mask_nl_class = nn.ReLU()
 
-    # -- engine plumbing (kept out of state_dict and rebuilt lazily, e.g. after unpickling) --------
     def _config_tuple(self):
         return ("improved", 1, self.out_channels, self.in_channels, self.num_blocks, self.upsampling_depth,
                 self.enc_kernel_size, self.enc_num_basis, self.num_sources, 1)
-
-    def _engine(self):
-        eng = self.__dict__.get("_srf_engine")
-        if eng is None or eng.cfg_tuple != self._config_tuple():
-            eng = ModelEngine(self._config_tuple())
-            self.__dict__["_srf_engine"] = eng
-        return eng
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_srf_engine", None)
-        return state
 
     def forward(self, input_wav):
         """[batch, 1, time] float -> [batch, num_sources, time] float32, one srf_forward call."""
@@ -222,19 +212,4 @@ class SuDORMRF(nn.Module):
         it; stats [batch, 2] = {mean, std} per row.  eval() / no_grad only."""
         return self._engine().run_separate_ragged(self, input_wav, lengths, mixture_consistency)
 
-    def pad_to_appropriate_length(self, x):
-        """Kept for API parity (reference :303-314); the HIP path folds the padding into its bounds
-        checks and never materialises the padded tensor."""
-        input_length = x.shape[-1]
-        n = self.n_least_samples_req
-        if input_length < n:
-            values_to_pad = n
-        else:
-            values_to_pad = (input_length // n + (1 if input_length % n else 0)) * n
-        padded = torch.zeros(list(x.shape[:-1]) + [values_to_pad], dtype=torch.float32, device=x.device)
-        padded[..., :input_length] = x
-        return padded
-
-    @staticmethod
-    def remove_trailing_zeros(padded_x, initial_x):
-        return padded_x[..., :initial_x.shape[-1]]
+    pad_to_appropriate_length = pad_to_multiple_of_least_samples       # (reference :303-314)

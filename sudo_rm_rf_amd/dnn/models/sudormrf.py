@@ -17,8 +17,8 @@ import torch
 import torch.nn as nn
 
 from ... import _lib, ops, original
-from ...engine import ModelEngine, _check_mixture, _checked_params, _weights
-from .improved_sudormrf import _hip_only
+from ...engine import _weights
+from ._base import _Model, _OptIn, _hip_only, pad_to_multiple_of_lcm
 
 
 def _d(p):
@@ -154,7 +154,7 @@ class UBlock(nn.Module):
         return original.gln_apply_c(gx, s_act, _d(a.norm.weight), _d(a.norm.bias), slopes=_d(a.act.weight))
 
 
-class SuDORMRF(nn.Module):
+class SuDORMRF(_OptIn, _Model):
     """Drop-in for the reference's original ``SuDORMRF``: forward([batch, 1, time]) -> [batch, num_sources, time]."""
 
     def __init__(self,
@@ -196,26 +196,11 @@ class SuDORMRF(nn.Module):
             stride=enc_kernel_size // 2, padding=enc_kernel_size // 2, groups=num_sources)
         self.ln_mask_in = nn.GroupNorm(1, enc_num_basis, eps=1e-08)      # (in the state_dict; never used in forward)
 
-    # -- engine plumbing (kept out of state_dict and rebuilt lazily, e.g. after unpickling) --------
+    _single_stream = True
+
     def _config_tuple(self):
         return ("original", 1, self.out_channels, self.in_channels, self.num_blocks, self.upsampling_depth,
                 self.enc_kernel_size, self.enc_num_basis, self.num_sources, 1)
-
-    def _engine(self):
-        eng = self.__dict__.get("_srf_engine")
-        if eng is None or eng.cfg_tuple != self._config_tuple():
-            eng = ModelEngine(self._config_tuple())
-            eng.multi_stream = False          # single stream only: the sub-batch split is not extended to this variant
-            self.__dict__["_srf_engine"] = eng
-        eng.original_ragged = bool(self.__dict__.get("_srf_ragged"))
-        return eng
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_srf_engine", None)
-        state.pop("_srf_hip_training", None)
-        state.pop("_srf_ragged", None)
-        return state
 
     def __getattr__(self, name):
         # separate_ragged exists only on a model that has opted in (enable_ragged): without the call hasattr() stays False,
@@ -265,11 +250,7 @@ class SuDORMRF(nn.Module):
         autograd the inference path is untouched; the sub-module forwards keep refusing autograd; a mixture that requires grad
         is refused (no gradient w.r.t. the input).  The flag is a plain attribute beside the engine: not in state_dict() and
         dropped from pickles, so a model that was unpickled has to opt in again."""
-        if flag:
-            self.__dict__["_srf_hip_training"] = True
-        else:
-            self.__dict__.pop("_srf_hip_training", None)
-        return self
+        return self._opt_in(flag)
 
     def _check_inference(self, weights):
         if torch.is_grad_enabled() and any(t.requires_grad for t in weights):
@@ -279,28 +260,15 @@ class SuDORMRF(nn.Module):
     def forward(self, input_wav):
         """[batch, 1, time] float -> [batch, num_sources, time] float32: one srf_forward call on the caller's stream.  Inference
         only, unless enable_hip_training() was called: then a forward under autograd is the HIP training step."""
-        weights = _weights(self)
-        mixture_grad = isinstance(input_wav, torch.Tensor) and input_wav.requires_grad
-        if self.__dict__.get("_srf_hip_training") and torch.is_grad_enabled() and (
-                mixture_grad or any(t.requires_grad for t in weights)):
-            if mixture_grad:
+        weights = _weights(self)           # (not self.parameters(): a DataParallel replica reports none)
+        mixture = input_wav if isinstance(input_wav, torch.Tensor) else None
+        if self._wants_grad(mixture, *weights):
+            if mixture is not None and mixture.requires_grad:
                 raise NotImplementedError("SuDORMRF.forward: the HIP training step has no gradient w.r.t. the input mixture; "
                                           "pass a mixture that does not require grad")
             return self._engine().run_train(self, input_wav, 1)
         self._check_inference(weights)
-        _check_mixture(input_wav, 1)
-        params = _checked_params(weights, input_wav.device, detach=True)
-        x = input_wav.detach().to(torch.float32).contiguous()
-        batch, _, T = x.shape
-        eng = self._engine()
-        with torch.cuda.device(x.device), eng._run_lock(x.device):
-            plan = eng.plan_for(batch, T, x.device)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
-            out = torch.empty((batch, self.num_sources, T), dtype=torch.float32, device=x.device)
-            plan.forward(eng._param_table(params, x.device), x, out)
-            eng.last_plan = plan
-        return out
+        return self._engine().run_plain(self, input_wav, 1, weights)
 
     def forward_ragged(self, input_wav, lengths):
         """After enable_ragged(): unequal-length utterances in ONE forward.  input_wav [batch, 1, time] on the GPU, row b valid
@@ -318,17 +286,4 @@ class SuDORMRF(nn.Module):
         exactly zero past lengths[b]."""
         return self._engine().run_separate_ragged(self, input_wav, lengths, mixture_consistency)
 
-    def pad_to_appropriate_length(self, x):
-        """Kept for API parity: up to a multiple of lcm(K // 2, 2^D), only when the length is not one already.  The HIP path
-        folds the padding into its bounds checks and never materialises the padded tensor."""
-        values_to_pad = int(x.shape[-1]) % self.lcm
-        if values_to_pad:
-            padded = torch.zeros(list(x.shape[:-1]) + [x.shape[-1] + self.lcm - values_to_pad], dtype=torch.float32,
-                                 device=x.device)
-            padded[..., :x.shape[-1]] = x
-            return padded
-        return x
-
-    @staticmethod
-    def remove_trailing_zeros(padded_x, initial_x):
-        return padded_x[..., :initial_x.shape[-1]]
+    pad_to_appropriate_length = pad_to_multiple_of_lcm

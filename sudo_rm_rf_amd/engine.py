@@ -2,6 +2,7 @@
 
 Python owns tensors and module structure only; all arithmetic happens in libsudormrf_hip.so.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -198,15 +199,12 @@ class _TrainStep(torch.autograd.Function):
     autograd."""
 
     @staticmethod
-    def forward(ctx, engine, out_ch, wav, *params):
+    def forward(ctx, engine, out_ch, wav, x, *params):
+        """wav: the caller's mixture (its gradient slot and dtype); x: the same as _checked_input returns it."""
         lib, fam = _lib.load(), _train_family(engine.cfg_tuple)
-        x = wav.detach().to(torch.float32).contiguous()
         batch, _, T = x.shape
         dev = x.device
-        with torch.cuda.device(dev), engine._run_lock(dev):
-            plan = engine.plan_for(batch, T, dev)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
+        with engine._planned(x, params) as plan:
             saved_bytes, scratch_bytes = plan.train_sizes()
             saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
             scratch = plan.train_scratch()
@@ -218,7 +216,6 @@ class _TrainStep(torch.autograd.Function):
         ctx.plan, ctx.saved_buf, ctx.x, ctx.engine, ctx.family = plan, saved, x, engine, fam
         ctx.wav_dtype = wav.dtype
         ctx.save_for_backward(*params)
-        engine.last_plan = plan
         return out
 
     @staticmethod
@@ -255,7 +252,7 @@ class _TrainStep(torch.autograd.Function):
         ctx.engine.last_flat_grad = flat      # (autograd adopts the views below as the .grad tensors: this IS the gradient)
         if gwav is not None and gwav.dtype != ctx.wav_dtype:
             gwav = gwav.to(ctx.wav_dtype)
-        return (None, None, gwav) + tuple(grads) + (None,) * fam.no_grad_tail
+        return (None, None, gwav, None) + tuple(grads) + (None,) * fam.no_grad_tail
 
 
 def _check_mixture(wav, channels):
@@ -272,12 +269,19 @@ def _check_mixture(wav, channels):
         raise RuntimeError("empty input %s" % (tuple(wav.shape),))
 
 
+def _checked_input(wav, channels):
+    """_check_mixture, then the mixture as the library reads it: detached contiguous float32 (the reference's pad buffer is
+    float32 whatever the input dtype, improved_sudormrf.py:312)."""
+    _check_mixture(wav, channels)
+    return wav.detach().to(torch.float32).contiguous()
+
+
 def _checked_params(weights, device, detach):
     """`weights` (what _weights returns) as the library takes them: contiguous float32 on `device`, detached on request."""
     params = [p.detach() for p in weights] if detach else weights
     for p in params:
         if p.device != device or p.dtype != torch.float32 or not p.is_contiguous():
-            raise _lib.SrfError("all parameters must be contiguous float32 on %s" % device)
+            raise _lib.SrfError("all parameters and buffers must be contiguous float32 on %s" % device)
     return params
 
 
@@ -394,14 +398,38 @@ class ModelEngine:
         self._ptr_cache[dkey] = (key, arr)
         return arr
 
+    @contextlib.contextmanager
+    def _planned(self, x, params):
+        """What every entry does around its launches, once: under x's device and its run lock, hand out the plan of x's
+        (batch, T) on the caller's stream with its parameter count checked against `params`; a body that returns normally
+        leaves it as last_plan.  x: what _checked_input returned, params: what _checked_params returned."""
+        with torch.cuda.device(x.device), self._run_lock(x.device):
+            plan = self.plan_for(x.shape[0], x.shape[-1], x.device)
+            if plan.num_params != len(params):
+                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
+            yield plan
+            self.last_plan = plan
+
     def run_train(self, module, wav, expected_channels):
         """The model under autograd: one _TrainStep of this engine's family (same input contract as run())."""
-        _check_mixture(wav, expected_channels)
-        params = _checked_params(_weights(module), wav.device, detach=False)
-        return _TrainStep.apply(self, module.num_sources * expected_channels, wav, *params)
+        return self._train_step(module, wav, _checked_input(wav, expected_channels), _weights(module))
+
+    def _train_step(self, module, wav, x, weights):
+        params = _checked_params(weights, x.device, detach=False)
+        return _TrainStep.apply(self, module.num_sources * x.shape[1], wav, x, *params)
+
+    def run_plain(self, module, wav, channels=1, weights=None):
+        """The single-stream plan forward on the caller's stream: no graph replay, no split, no training dispatch -- what the
+        original and the attentive models run.  weights: _weights(module), from a caller that has read them already."""
+        x = _checked_input(wav, channels)
+        params = _checked_params(_weights(module) if weights is None else weights, x.device, detach=True)
+        with self._planned(x, params) as plan:
+            out = torch.empty((x.shape[0], module.num_sources * channels, x.shape[-1]), dtype=torch.float32, device=x.device)
+            plan.forward(self._param_table(params, x.device), x, out)
+        return out
 
     def run(self, module, wav, expected_channels):
-        _check_mixture(wav, expected_channels)
+        x = _checked_input(wav, expected_channels)
         # (from the state_dict tensors, not module.parameters(): DataParallel replicas hold their weights as plain
         # tensors -- views that require grad through the Broadcast node -- and report no parameters at all)
         weights = _weights(module)
@@ -409,30 +437,21 @@ class ModelEngine:
         # model.train() + grad mode = the training step (what the reference's runner does before its loop,
         # run_improved_sudormrf.py:144); model.eval() always takes the fused inference path
         if wants_grad and module.training:
-            return self.run_train(module, wav, expected_channels)
+            return self._train_step(module, wav, x, weights)
         if wants_grad and not self._warned_grad:
             self._warned_grad = True
             warnings.warn("sudo_rm_rf_amd: forward in eval() mode with gradients enabled returns a DETACHED output (the "
                           "fused inference path keeps no activations); call model.train() for the HIP training step or "
                           "wrap inference in torch.no_grad()", stacklevel=3)
-        params = _checked_params(weights, wav.device, detach=True)
-        # the reference's pad buffer is float32 whatever the input dtype (improved_sudormrf.py:312)
-        x = wav.detach().to(torch.float32).contiguous()
+        params = _checked_params(weights, x.device, detach=True)
         batch, _, T = x.shape
-        with torch.cuda.device(x.device), self._run_lock(x.device):
-            plan = self.plan_for(batch, T, x.device)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" %
-                                    (len(params), plan.num_params))
+        with self._planned(x, params) as plan:
             out_ch = module.num_sources * expected_channels
             table = self._param_table(params, x.device)
             if self._wants_graph(plan, batch, T, x.device):
-                out = self._forward_graph(batch, T, out_ch, x, params, table)
-                self.last_plan = plan
-                return out
+                return self._forward_graph(batch, T, out_ch, x, params, table)
             out = torch.empty((batch, out_ch, T), dtype=torch.float32, device=x.device)
             self._forward_split(self._splits(batch, T, x, out, table), x, out, table)
-            self.last_plan = plan
         return out
 
     def run_ragged(self, module, wav, lengths):
@@ -450,7 +469,7 @@ class ModelEngine:
 
     def _run_ragged(self, module, wav, lengths, separate_mc):
         """separate_mc: None = the plain ragged forward, else srf_separate_ragged with that mixture-consistency setting"""
-        _check_mixture(wav, 1)
+        x = _checked_input(wav, 1)
         if isinstance(lengths, torch.Tensor):
             if lengths.device.type != "cpu":
                 raise _lib.SrfError("lengths must be a list or a CPU tensor (reading a device tensor would synchronise)")
@@ -460,22 +479,17 @@ class ModelEngine:
         if module.training or (torch.is_grad_enabled() and any(t.requires_grad for t in weights)):
             raise NotImplementedError("forward_ragged: the ragged batch is an inference path (model.eval() under "
                                       "torch.no_grad()); there is no ragged training step")
-        params = _checked_params(weights, wav.device, detach=True)
-        x = wav.detach().to(torch.float32).contiguous()
+        params = _checked_params(weights, x.device, detach=True)
         batch, _, T = x.shape
         if len(lengths) != batch:
             raise RuntimeError("%d lengths for a batch of %d" % (len(lengths), batch))
-        with torch.cuda.device(x.device), self._run_lock(x.device):
-            plan = self.plan_for(batch, T, x.device)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
+        with self._planned(x, params) as plan:
             out = torch.empty((batch, module.num_sources, T), dtype=torch.float32, device=x.device)
             if separate_mc is None:
                 plan.forward_ragged(self._param_table(params, x.device), x, lengths, out)
             else:
                 stats = torch.empty((batch, 2), dtype=torch.float32, device=x.device)
                 plan.separate_ragged(self._param_table(params, x.device), x, lengths, out, stats, separate_mc)
-            self.last_plan = plan
         return out if separate_mc is None else (out, stats)
 
     def ragged_plan_supported(self, batch, T, device):
@@ -494,18 +508,13 @@ class ModelEngine:
         if channels != 1:
             raise _lib.SrfError("separate() takes single-channel mixtures [batch, 1, time] (the README recipe); this model has "
                                 "%d input channels" % channels)
-        _check_mixture(mixture, 1)
-        params = _checked_params(_weights(module), mixture.device, detach=True)
-        x = mixture.detach().to(torch.float32).contiguous()
+        x = _checked_input(mixture, 1)
+        params = _checked_params(_weights(module), x.device, detach=True)
         batch, _, T = x.shape
-        with torch.cuda.device(x.device), self._run_lock(x.device):
-            plan = self.plan_for(batch, T, x.device)
-            if plan.num_params != len(params):
-                raise _lib.SrfError("state_dict has %d tensors, plan expects %d" % (len(params), plan.num_params))
+        with self._planned(x, params) as plan:
             out = torch.empty((batch, module.num_sources, T), dtype=torch.float32, device=x.device)
             stats = torch.empty((batch, 2), dtype=torch.float32, device=x.device)
             plan.separate(self._param_table(params, x.device), x, out, stats, mixture_consistency)
-            self.last_plan = plan
         return out
 
     # ---- HIP-graph replay of small forwards -----------------------------------------------------------

@@ -12,7 +12,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import _config_struct, _weights
+from .dnn.models._base import _refuse_autograd
+from .engine import _checked_params, _config_struct, _weights
 
 
 class _Session:
@@ -60,10 +61,7 @@ def _prepare_weights(owner, who):
     """srf_stream_prepare of owner._module's parameters into owner._weights (CausalStream and CausalStreamPool)."""
     if owner._module._config_tuple() != owner._cfg_tuple:
         raise _lib.SrfError("%s: the module's configuration or block scales changed; open a new stream" % who)
-    params = [p.detach() for p in _weights(owner._module)]
-    for p in params:
-        if p.device != owner.device or p.dtype != torch.float32 or not p.is_contiguous():
-            raise _lib.SrfError("all parameters must be contiguous float32 on %s" % owner.device)
+    params = _checked_params(_weights(owner._module), owner.device, detach=True)
     arr = (C.c_void_p * len(params))(*[p.data_ptr() for p in params])
     with torch.cuda.device(owner.device):
         rc = _lib.load().srf_stream_prepare(owner._s.handle, arr, len(params), _lib.ptr(owner._weights), owner._stream())
@@ -77,7 +75,6 @@ class CausalStream:
     parameters do not reach a running session until it is refreshed."""
 
     def __init__(self, module, batch=1, max_chunk=None, device=None):
-        from .dnn.models.causal_improved_sudormrf_v3 import _refuse_autograd
         self._module = module
         _refuse_autograd("CausalSuDORMRF.stream", list(module.parameters()))
         weights = _weights(module)
@@ -142,7 +139,6 @@ class CausalStream:
 
     # -- data path ---------------------------------------------------------------------------
     def _check_input(self, x):
-        from .dnn.models.causal_improved_sudormrf_v3 import _refuse_autograd
         if not isinstance(x, torch.Tensor):
             raise TypeError("input must be a torch.Tensor")
         _refuse_autograd("CausalStream.push", [x])
@@ -233,7 +229,6 @@ class CausalStreamPool:
     The weights are snapshot at construction (and by ``refresh_weights()``), as for ``CausalStream``."""
 
     def __init__(self, module, capacity, max_chunk=None, device=None):
-        from .dnn.models.causal_improved_sudormrf_v3 import _refuse_autograd
         self._module = module
         _refuse_autograd("CausalSuDORMRF.stream_pool", list(module.parameters()))
         weights = _weights(module)
@@ -318,7 +313,6 @@ class CausalStreamPool:
         return sid
 
     def _check_input(self, sid, x):
-        from .dnn.models.causal_improved_sudormrf_v3 import _refuse_autograd
         if not isinstance(x, torch.Tensor):
             raise TypeError("input must be a torch.Tensor")
         _refuse_autograd("CausalStreamPool.push", [x])
