@@ -16,7 +16,7 @@ SOURCES = ["srf_api.hip", "srf_encoder.hip", "srf_elementwise.hip", "srf_dwconv.
            "srf_tac.hip", "srf_loss.hip", "srf_pwconv_wgrad.hip", "srf_backward.hip", "srf_train.hip", "srf_augment.hip", "srf_optim.hip", "srf_feeder.hip",
            "srf_causal.hip", "srf_causal_stream.hip", "srf_loss_fuss.hip", "srf_causal_bwd.hip", "srf_causal_train.hip",
            "srf_attention.hip", "srf_attention_bwd.hip", "srf_attentive.hip", "srf_attentive_v3.hip", "srf_original.hip", "srf_original_train.hip"]
-HEADERS = [os.path.join(CSRC, "srf_common.h"), os.path.join(CSRC, "srf_internal.h"), os.path.join(CSRC, "srf_pw.h"), os.path.join(CSRC, "srf_plan.h"), os.path.join(CSRC, "srf_pyr.h"), os.path.join(CSRC, "srf_mha.h"),
+HEADERS = [os.path.join(CSRC, "srf_common.h"), os.path.join(CSRC, "srf_internal.h"), os.path.join(CSRC, "srf_pw.h"), os.path.join(CSRC, "srf_plan.h"), os.path.join(CSRC, "srf_pyr.h"), os.path.join(CSRC, "srf_mha.h"), os.path.join(CSRC, "srf_original_walk.h"),
            os.path.join(os.path.dirname(PKG), "include", "sudormrf_hip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function"]

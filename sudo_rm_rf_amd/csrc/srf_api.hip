@@ -461,9 +461,9 @@ extern "C" int srf_separate(const srf_plan* p, const float* const* P, int num_pa
   return srf_forward_impl(p, P, num_params, wav, out, workspace, workspace_bytes, stats, mixture_consistency, stream);
 }
 
-// what srf_forward / srf_separate and srf_forward_ragged (`who`) ask of their arguments; ptrs: none of the caller's pointers is null
-static int forward_check_args(const char* who, bool ptrs, const srf_plan* p, const float* const* P, int num_params,
-                              const void* workspace, size_t workspace_bytes) {
+// what the forward entry points (`who`) ask of their arguments (srf_internal.h); ptrs: none of the caller's pointers is null
+int forward_check_args(const char* who, bool ptrs, const srf_plan* p, const float* const* P, int num_params, const void* workspace,
+                       size_t workspace_bytes) {
   SRF_CHECK_ARG(ptrs, "%s: null pointer", who);
   SRF_CHECK_ARG(num_params == p->n_params, "%s: expected %d parameter tensors, got %d", who, p->n_params, num_params);
   if (workspace_bytes < p->total_bytes) {
@@ -629,13 +629,13 @@ static int forward_walk(const srf_plan* p, const float* const* P, const float* w
     // unfused path: the merged tensor aliases y1 (dead once every level has been produced); fused path:
     // its own buffer (the otherwise unused level-0 buffer), because pass 2 re-reads y1 with halos
     float* merged = fused ? fptr(p->off_lv[0]) : y1;
+    const srf_norm in{s.proj, b.proj_g, b.proj_be, b.proj_prelu};
     if (fused) {
-      srf_norm in{s.proj, b.proj_g, b.proj_be, b.proj_prelu};
       rc = step_pyramid(rg, G, y1, merged, &in, b, Bg, nC, L, D, ws + p->off_pyr, s.merged, stream);
     } else {
       float* lv[SRF_MAX_DEPTH];
       for (int k = 0; k < D; ++k) lv[k] = fptr(p->off_lv[k]);
-      rc = srf_pyramid_per_level(y1, lv, merged, b, s, Bg, nC, L, D, stream);
+      rc = srf_pyramid_per_level(y1, &in, lv, merged, b.lv_w, b.lv_b, b.lv_g, b.lv_be, s.level, s.merged, Bg, nC, L, D, stream);
     }
     if (rc) return rc;
     // final_norm + PReLU folded into res_conv, + residual     :218-220

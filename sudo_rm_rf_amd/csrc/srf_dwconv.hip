@@ -381,21 +381,22 @@ extern "C" int srf_merge(const float* const* levels, const srf_norm* norms, int 
 }
 
 // A block's pyramid as D depthwise launches + the merge: what the forwards run where the fused kernels (srf_pyramid.hip) do
-// not.  lv[k]: level k's output [Bg, nC, L >> k]; level 0 reads y1 through proj_1x1's norm + PReLU, level k > 0 reads level
-// k - 1 through that level's norm with stride 2; merged may alias y1 (dead once every level has been produced).
-int srf_pyramid_per_level(const float* y1, float* const* lv, float* merged, const SrfBlock<const float>& b, const SrfSlots& s,
-                          int Bg, int nC, int L, int D, void* stream) {
+// not.  lv[k]: level k's output [Bg, nC, L >> k]; level 0 reads x through in_norm (the Improved model: proj_1x1's norm + PReLU;
+// NULL, the original model: x as it is), level k > 0 reads level k - 1 through that level's norm with stride 2; merged may alias
+// x (dead once every level has been produced).
+int srf_pyramid_per_level(const float* x, const srf_norm* in_norm, float* const* lv, float* merged, const float* const* w,
+                          const float* const* bias, const float* const* gamma, const float* const* beta, double* const* lv_sums,
+                          double* merged_sums, int Bg, int nC, int L, int D, void* stream) {
   const float* levels[SRF_MAX_DEPTH];
   srf_norm norms[SRF_MAX_DEPTH];
   for (int k = 0; k < D; ++k) {
-    const srf_norm in = k == 0 ? srf_norm{s.proj, b.proj_g, b.proj_be, b.proj_prelu} : norms[k - 1];
-    const int rc = srf_dwconv5(k == 0 ? y1 : lv[k - 1], b.lv_w[k], b.lv_b[k], lv[k], Bg, nC, k == 0 ? L : L >> (k - 1), k == 0 ? 1 : 2,
-                               &in, s.level[k], stream);
+    const int rc = srf_dwconv5(k == 0 ? x : lv[k - 1], w[k], bias[k], lv[k], Bg, nC, k == 0 ? L : L >> (k - 1), k == 0 ? 1 : 2,
+                               k == 0 ? in_norm : &norms[k - 1], lv_sums[k], stream);
     if (rc) return rc;
     levels[k] = lv[k];
-    norms[k] = srf_norm{s.level[k], b.lv_g[k], b.lv_be[k], nullptr};
+    norms[k] = srf_norm{lv_sums[k], gamma[k], beta[k], nullptr};
   }
-  return srf_merge(levels, norms, D, merged, Bg, nC, L, s.merged, stream);   // upsample + add   improved_sudormrf.py:214-216
+  return srf_merge(levels, norms, D, merged, Bg, nC, L, merged_sums, stream);   // upsample + add   improved_sudormrf.py:214-216
 }
 
 

@@ -47,8 +47,14 @@ int srf_decoder_impl(const float* v, const float* w, float* out, int Bt, int Ci,
                      const float* post_stats, const float* post_wav, int post_mc, void* stream, const float* in_prelu = nullptr,
                      const SrfFrames* lens = nullptr, const SrfFrames* frames = nullptr);   // (both or neither: the ragged overlap-add)
 
-// ---- srf_attentive.hip (softmax attention, which its walk and the next one call: srf_mha.h)
 struct srf_plan;
+// what srf_forward / srf_separate, srf_forward_ragged and the original model's ragged entries (`who`, in front of every reason) ask
+// of their arguments, in this order: ptrs (none of the caller's pointers is null), num_params, the workspace's size
+// (SRF_EWORKSPACE) and its 256-byte alignment, no null P[i]
+int forward_check_args(const char* who, bool ptrs, const srf_plan* p, const float* const* P, int num_params, const void* workspace,
+                       size_t workspace_bytes);
+
+// ---- srf_attentive.hip (softmax attention, which its walk and the next one call: srf_mha.h)
 int srf_attentive_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                           const float* wav_stats, int mixture_consistency, void* stream);
 // ---- srf_attentive_v3.hip
@@ -61,8 +67,34 @@ struct Ragged {
   SrfFrames lens_t, frames_t;         // the same two by value, for the overlap-add
 };
 // ---- srf_original.hip
+// Where the original model's ONE forward walk keeps its tensors.  Block i reads the block stream at x + i * x_stride and writes
+// it one stride further; its own tensors lie at blk + i * blk_stride + the o_* byte offsets.  The inference forward overwrites one
+// set block after block (both strides 0, m on y1: the plan's workspace); the training forward keeps every block's (`saved`, the
+// rest in `scratch`: srf_original_train.hip).
+struct SrfOrigAddrs {
+  double* stats;
+  float* enc;
+  char *x, *blk;
+  size_t x_stride, blk_stride;
+  size_t o_y1, o_m, o_g, o_gx, o_lv[SRF_MAX_DEPTH];
+  float *act, *xr, *z, *masked, *dec, *tz, *wdec;   // act: a, then e; xr: only with reshape_before_masks; dec: the decoder's scratch
+  void* pyr;                                         // the fused pyramid's scratch (NULL where the pyramid never runs fused)
+  float* x_in(int i) const { return (float*)(x + x_stride * i); }
+  float* x_out(int i) const { return (float*)(x + x_stride * (i + 1)); }
+  float* y1(int i) const { return (float*)(blk + blk_stride * i + o_y1); }
+  float* m(int i) const { return (float*)(blk + blk_stride * i + o_m); }
+  float* g(int i) const { return (float*)(blk + blk_stride * i + o_g); }
+  float* gx(int i) const { return (float*)(blk + blk_stride * i + o_gx); }
+  float* lv(int i, int k) const { return (float*)(blk + blk_stride * i + o_lv[k]); }
+};
 int srf_original_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                          const float* wav_stats, int mixture_consistency, void* stream, const Ragged* rg = nullptr);
+// srf_bias_rescale_ragged's launch alone, from a table the caller has checked (the walk: srf_original_walk.h)
+int srf_bias_rescale_ragged_launch(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
+                                   const SrfFrames& lens, void* stream);
+// m.{weight, bias} as the [S N, N] GEMM weight + its bias rows (tz: orig_tz_floats of srf_plan.h, the rows at orig_tz_bias_at) and
+// decoder.weight as the block-diagonal one (wdec): two launches, at the start of the walk and of srf_original_backward
+int srf_original_weight_forms(const srf_plan* p, const float* const* P, float* tz, float* wdec, void* stream);
 // the Improved walk's mask + decoder tail (srf_api.hip), shared with the attentive walks; rg: forward_walk's ragged batch, else NULL
 int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur, float* out, void* workspace, bool use_pack,
                       const float* wav_stats, const float* wav, int mixture_consistency, const Ragged* rg, void* stream);
@@ -89,12 +121,11 @@ size_t srf_causal_prelu_bwd_scratch_floats();
 int srf_causal_prelu_bwd(const float* gout, const float* x, const float* slope, float* gx, float* dslope, long n, float* scratch,
                          hipStream_t st);
 
-// ---- srf_dwconv.hip: the per-level pyramid of the inference and the training forward (views: srf_plan.h)
-template <typename T>
-struct SrfBlock;
-struct SrfSlots;
-int srf_pyramid_per_level(const float* y1, float* const* lv, float* merged, const SrfBlock<const float>& b, const SrfSlots& s,
-                          int Bg, int nC, int L, int D, void* stream);
+// ---- srf_dwconv.hip: the per-level pyramid of the Improved and the original model's inference and training forwards
+// (w, bias, gamma, beta: the level arrays of a block view of srf_plan.h; lv_sums, merged_sums: its statistic slots)
+int srf_pyramid_per_level(const float* x, const srf_norm* in_norm, float* const* lv, float* merged, const float* const* w,
+                          const float* const* bias, const float* const* gamma, const float* const* beta, double* const* lv_sums,
+                          double* merged_sums, int Bg, int nC, int L, int D, void* stream);
 
 // ---- srf_pyramid.hip / srf_pyramid_reg.hip
 bool srf_pyramid_reg_supported(int L, int D);

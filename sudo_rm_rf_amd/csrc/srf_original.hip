@@ -1,6 +1,6 @@
-// Original SuDoRM-RF (sudormrf.py, the model of the paper): plan constructor, the inference walk and the kernels it has that no
-// other variant has.  Single stream.  The training walk over the same plan: srf_original_train.hip.  Parameter and slot layout:
-// srf_plan.h.
+// Original SuDoRM-RF (sudormrf.py, the model of the paper): plan constructor, the inference and ragged forwards and the kernels
+// it has that no other variant has.  Single stream.  THE forward walk, which the training forward runs too: srf_original_walk.h;
+// the training step: srf_original_train.hip.  Parameter and slot layout: srf_plan.h.
 //
 //   s   = relu(encoder.0(wav))                                srf_encoder_bias_relu (+ statistics of ln)
 //   x   = l1(ln(s))                                           srf_pw_conv_packed    (ln on load)
@@ -21,15 +21,9 @@
 //
 // Ragged batches (opt-in: srf_original_forward_ragged / srf_original_separate_ragged): the SAME walk with a
 // frames table.  L stays the row stride; example b has L_b = frames[b] columns (its own length padded to a multiple of
-// lcm(hop, 2^D), over the hop) and len_b samples, and every kernel above runs as its ragged twin.  Invariants:
-//   * every tensor whose statistics are taken -- s, y1, the merged pyramid output m, g and g + x -- is exact zero on [L_b, L);
-//   * a and e are zero there too;
-//   * the block stream x is written by srf_gln_apply_c, so it is zero there as well; l1's output is the one block-stream tensor
-//     the invariant does not rest on (only pointwise consumers read it);
-//   * z is unspecified there; srf_softmax_mask stores v as exact zeros, so the decoder's frame GEMM sees zeros, and out is exactly
-//     0 from len_b on.
+// lcm(hop, 2^D), over the hop) and len_b samples, and every kernel above runs as its ragged twin.  The invariants: with the walk.
 #include <vector>
-#include "srf_plan.h"
+#include "srf_original_walk.h"
 
 // ---------------------------------------------------------------------------------------------
 // y = [PReLU_c](norm(x)) [+ add], out_sums += {sum, sumsq} of the stored y.  Bandwidth-bound: one block per (row = (g, c), chunk
@@ -548,8 +542,8 @@ extern "C" int srf_bias_rescale(float* out, const float* bias, const float* stat
   return SRF_OK;
 }
 
-// the launch alone, from a table the caller has checked (srf_original_forward's ragged walk: the one its overlap-add uses)
-static int bias_rescale_ragged_launch(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
+// the launch alone, from a table the caller has checked (the ragged walk's step_bias: the one its overlap-add uses)
+int srf_bias_rescale_ragged_launch(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
                                       const SrfFrames& lens, void* stream) {
   const dim3 grid((T + 255) / 256, Bt);
   if (stats)
@@ -568,14 +562,12 @@ extern "C" int srf_bias_rescale_ragged(float* out, const float* bias, const floa
   SrfFrames lens;
   const int rc = srf_frames_table("srf_bias_rescale_ragged", lengths, Bt, T, &lens);
   if (rc) return rc;
-  return bias_rescale_ragged_launch(out, bias, stats, wav, mc, Bt, S, T, lens, stream);
+  return srf_bias_rescale_ragged_launch(out, bias, stats, wav, mc, Bt, S, T, lens, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
 // plan
 // ---------------------------------------------------------------------------------------------
-static long orig_gcd(long a, long b) { return b ? orig_gcd(b, a % b) : a; }
-
 extern "C" int srf_original_plan_create(const srf_config* base, int batch, int T, srf_plan** out) {
   SRF_CHECK_ARG(base && out, "srf_original_plan_create: null pointer");
   *out = nullptr;
@@ -597,9 +589,7 @@ extern "C" int srf_original_plan_create(const srf_config* base, int batch, int T
                 SRF_SOFTMAX_MASK_MAX_SOURCES);
   const int D = c.upsampling_depth, U = c.num_blocks, K = c.enc_kernel_size, N = c.enc_num_basis, h = K / 2, S = c.num_sources;
   const int B = c.out_channels, C = c.in_channels;
-  // pad_to_appropriate_length: up to a multiple of lcm(K / 2, 2^D) -- only when T is not one already
-  const long lcm = (long)h * (1L << D) / orig_gcd(h, 1L << D);
-  const long Tp = T % lcm ? T + lcm - T % lcm : T;
+  const long Tp = orig_padded_length(T, h, D);
   SRF_CHECK_ARG(Tp <= (1L << 30), "srf_original_plan_create: T = %d too long", T);
   const long L = (Tp + 2 * h - K) / h + 1;
   SRF_CHECK_ARG(L % (1L << (D - 1)) == 0,
@@ -676,165 +666,41 @@ extern "C" int srf_original_plan_create(const srf_config* base, int batch, int T
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
-// ---- the steps of the walk, one per kernel family: the uniform entry point, or -- rg != NULL, srf_original_forward_ragged --
-// its ragged twin with the batch's tables.  Every per-launch refusal stays with the entry point.
-static int step_encoder(const Ragged* rg, const float* wav, const float* w, const float* bias, float* enc, double* sums, int Bt, int T,
-                        int N, int K, int L, const float* wav_stats, void* stream) {
-  return rg ? srf_encoder_bias_relu_ragged(wav, w, bias, enc, sums, Bt, T, N, K, L, rg->lengths, rg->frames, wav_stats, stream)
-            : srf_encoder_bias_relu(wav, w, bias, enc, sums, Bt, T, N, K, L, wav_stats, stream);
-}
-// ragged: always the 256 x 128 kernel (the gate has made sure every conv of the model has a packed image and a shape it takes)
-static int step_conv(const Ragged* rg, const float* x, const float* w, const void* w_packed, const float* bias, float* y, int Bt, int Cin,
-                     int Cout, int L, const srf_norm* in_norm, double* out_sums, void* stream) {
-  return rg ? srf_pw_conv_packed_ragged(x, w, w_packed, bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, 0, nullptr, 0, rg->frames,
-                                        stream)
-            : srf_pw_conv_packed(x, w, w_packed, bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, 0, nullptr, 0, stream);
-}
-static int step_gln(const Ragged* rg, const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y,
-                    double* out_sums, int Bt, int C, int L, void* stream) {
-  return rg ? srf_gln_apply_c_ragged(x, norm, slopes, add, y, out_sums, Bt, C, L, rg->frames, stream)
-            : srf_gln_apply_c(x, norm, slopes, add, y, out_sums, Bt, C, L, stream);
-}
-// the fused pyramid over the materialised activation: no norm on load
-static int step_pyramid(const Ragged* rg, const float* act, float* merged, const SrfOrigBlock& b, int Bt, int C, int L, int D,
-                        void* scratch, double* out_sums, void* stream) {
-  return rg ? srf_pyramid_ragged(act, merged, nullptr, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bt, C, L, D, scratch, out_sums, rg->frames, stream)
-            : srf_pyramid(act, merged, nullptr, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bt, C, L, D, scratch, out_sums, stream);
-}
-static int step_softmax(const Ragged* rg, const float* z, const float* enc, float* v, int Bt, int S, int N, int L, void* stream) {
-  return rg ? srf_softmax_mask_ragged(z, enc, v, Bt, S, N, L, rg->frames, stream) : srf_softmax_mask(z, enc, v, Bt, S, N, L, stream);
-}
-static int step_bias(const Ragged* rg, float* out, const float* bias, const float* wav_stats, const float* wav, int mc, int Bt, int S,
-                     int T, void* stream) {
-  return rg ? bias_rescale_ragged_launch(out, bias, wav_stats, wav, mc, Bt, S, T, rg->lens_t, stream)
-            : srf_bias_rescale(out, bias, wav_stats, wav, mc, Bt, S, T, stream);
+// ---- the two weights this model needs in another form: the mask layer as a [S N, N] GEMM weight, the grouped decoder's as a
+// block-diagonal one
+int srf_original_weight_forms(const srf_plan* p, const float* const* P, float* tz, float* wdec, void* stream) {
+  const int N = p->cfg.enc_num_basis, S = p->cfg.num_sources;
+  const SrfOrigTail t = orig_tail(p, P);
+  const int rc = srf_mask_weight_fill(t.m_w, t.m_b, tz, tz + orig_tz_bias_at(S, N), N, S, stream);
+  if (rc) return rc;
+  return srf_decoder_weight_expand(t.dec_w, wdec, N, S, p->cfg.enc_kernel_size, stream);
 }
 
-// THE walk of the original model's inference forward: srf_forward, srf_separate (wav_stats), srf_original_forward_ragged (rg) and
-// srf_original_separate_ragged (both).
-// The ragged forward keeps the layout -- [batch, C, L] with L the PLAN's frame count as row stride, the same workspace carve-up --
-// and every kernel takes the example's own frame count L_b (its own length padded by THIS model's rule, lcm(hop, 2^D), over the
-// hop) from a by-value table.  The invariants:
-//   * every tensor whose GlobLN statistics are taken -- s, y1, the merged pyramid output m, g and g + x -- is exactly zero on
-//     [L_b, L), so the sums come out right and only the count changes (C * L_b);
-//   * a and e (srf_gln_apply_c's outputs, the pyramid's and conv_1x1_exp's inputs) are zero there too: the pyramid reads its
-//     input with a halo only up to L_b, the GEMM is pointwise;
-//   * the block stream x is written by srf_gln_apply_c, so it is zero there as well.  l1's output is the one block-stream tensor
-//     the invariant does not rest on (only pointwise consumers read it: proj_1x1 and, below L_b, the residual add);
-//   * the mask logits z are unspecified on [L_b, L): srf_softmax_mask reads neither them nor s there and stores v as exact
-//     zeros, so the decoder's frame GEMM (unchanged, over every column) sees zeros and the ragged overlap-add reads the example's
-//     own frames only; out is exactly 0 from the example's length on.
-// srf_mask_weight_fill, srf_decoder_weight_expand, the mask GEMM / reshape_before_masks (the plain ragged GEMM) and the decoder's
-// transpose + frame GEMM run over every column.
+// the inference forward (rg: a ragged batch): one set of tensors in the plan's workspace, the plan's packed images
 int srf_original_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                          const float* wav_stats, int mixture_consistency, void* stream, const Ragged* rg) {
-  const srf_config& c = p->cfg;
-  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, S = c.num_sources;
-  const int Bt = p->Bt, L = p->L, B = p->nB, C = p->nC;
   char* ws = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
   auto fptr = [&](size_t o) { return (float*)(ws + o); };
-  double* stats = (double*)(ws + p->off_stats);
-  const SrfOrigFront f = orig_front(P);
-  const SrfOrigTail t = orig_tail(p, P);
-  int rc = srf_zero_launch(stats, p->stats_bytes, st);
-  if (rc) return rc;
-  // ---- the two weights this model needs in another form: the mask layer as a [S N, N] GEMM weight, the grouped decoder's as a
-  // block-diagonal one
-  float* tz = fptr(p->off_orig_tz);
-  float* tz_bias = tz + srf_align_up((size_t)S * N * N, 64);
-  float* wdec = fptr(p->off_orig_wdec);
-  rc = srf_mask_weight_fill(t.m_w, t.m_b, tz, tz_bias, N, S, stream);
-  if (rc) return rc;
-  rc = srf_decoder_weight_expand(t.dec_w, wdec, N, S, K, stream);
-  if (rc) return rc;
+  SrfOrigAddrs a{};
+  a.stats = (double*)(ws + p->off_stats);
+  a.enc = fptr(p->off_enc);
+  a.x = ws + p->off_xa, a.blk = ws;      // (strides 0)
+  a.o_y1 = a.o_m = p->off_y1, a.o_g = p->off_orig_g, a.o_gx = p->off_orig_gx;
+  for (int k = 0; k < p->cfg.upsampling_depth; ++k) a.o_lv[k] = p->off_lv[k];
+  a.act = fptr(p->off_orig_act), a.xr = fptr(p->off_orig_xr), a.z = fptr(p->off_orig_z), a.masked = fptr(p->off_masked);
+  a.dec = fptr(p->off_dec), a.tz = fptr(p->off_orig_tz), a.wdec = fptr(p->off_orig_wdec);
+  a.pyr = ws + p->off_pyr;
   // (a ragged batch runs what srf_original_ragged_supported has made sure of: packed weights, the register-resident fused pyramid)
   const bool use_pack = rg || plan_use_pack(p);
-  if (use_pack) {
-    rc = plan_pack_weights(p, [&](int param) -> const float* { return param == t.i_m ? tz : P[param]; }, ws, stream);
-    if (rc) return rc;
-  }
+  const int i_m = orig_p_mask(p);
+  auto pack = [&](const float* tz) -> int {
+    return use_pack ? plan_pack_weights(p, [&](int param) -> const float* { return param == i_m ? tz : P[param]; }, ws, stream) : SRF_OK;
+  };
   auto conv = [&](const float* x, const float* w, int param, const float* bias, float* y, int Cin, int Cout, const srf_norm* in_norm,
                   double* out_sums) {
-    return step_conv(rg, x, w, plan_packed(p, ws, use_pack, param), bias, y, Bt, Cin, Cout, L, in_norm, out_sums, stream);
+    return step_conv(rg, x, w, plan_packed(p, ws, use_pack, param), bias, y, p->Bt, Cin, Cout, p->L, in_norm, out_sums, stream);
   };
-
-  // ---- front end: encoder with bias and ReLU (+ ln statistics), ln folded into l1's operand load
-  float* enc = fptr(p->off_enc);
-  rc = step_encoder(rg, wav, f.enc_w, f.enc_b, enc, stats, Bt, p->T, N, K, L, wav_stats, stream);
-  if (rc) return rc;
-  float* cur = fptr(p->off_xa);
-  {
-    const srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
-    rc = conv(enc, f.l1_w, SRF_PO_L1, f.l1_b, cur, N, B, &ln, nullptr);
-    if (rc) return rc;
-  }
-
-  // ---- separation module
-  float *y1 = fptr(p->off_y1), *act = fptr(p->off_orig_act), *g = fptr(p->off_orig_g), *gx = fptr(p->off_orig_gx);
-  const bool fused = rg || plan_fused_pyramid_now(p);
-  for (int i = 0; i < U; ++i) {
-    const SrfOrigBlock b = orig_block(p, P, i);
-    const SrfOrigSlots s = orig_slots(p, stats, i);
-    rc = conv(cur, b.proj_w, b.i_proj, b.proj_b, y1, B, C, nullptr, s.proj);
-    if (rc) return rc;
-    const srf_norm pn{s.proj, b.proj_g, b.proj_be, nullptr};
-    rc = step_gln(rg, y1, &pn, b.proj_slope, nullptr, act, nullptr, Bt, C, L, stream);
-    if (rc) return rc;
-    // the pyramid, its result m into y1 (dead since a exists) with the statistics of final_norm: the fused kernels where they
-    // take the shape -- level 0 reads the materialised activation as it is, no norm on load -- else level by level + merge
-    // (D = 1: the normalised level 0)
-    if (fused) {
-      rc = step_pyramid(rg, act, y1, b, Bt, C, L, D, ws + p->off_pyr, s.merged, stream);
-      if (rc) return rc;
-    } else {
-      const float* levels[SRF_MAX_DEPTH];
-      srf_norm norms[SRF_MAX_DEPTH];
-      for (int k = 0; k < D; ++k) {
-        float* lv = fptr(p->off_lv[k]);
-        rc = srf_dwconv5(k == 0 ? act : levels[k - 1], b.lv_w[k], b.lv_b[k], lv, Bt, C, k == 0 ? L : L >> (k - 1), k == 0 ? 1 : 2,
-                         k == 0 ? nullptr : &norms[k - 1], s.level[k], stream);
-        if (rc) return rc;
-        levels[k] = lv;
-        norms[k] = srf_norm{s.level[k], b.lv_g[k], b.lv_be[k], nullptr};
-      }
-      rc = srf_merge(levels, norms, D, y1, Bt, C, L, s.merged, stream);
-      if (rc) return rc;
-    }
-    // final_norm + PReLU_c (into a's buffer)
-    const srf_norm fn{s.merged, b.fin_g, b.fin_be, nullptr};
-    rc = step_gln(rg, y1, &fn, b.fin_slope, nullptr, act, nullptr, Bt, C, L, stream);
-    if (rc) return rc;
-    rc = conv(act, b.exp_w, b.i_exp, b.exp_b, g, C, B, nullptr, s.exp);
-    if (rc) return rc;
-    // the residual goes in BEFORE module_act's norm
-    const srf_norm en{s.exp, b.exp_g, b.exp_be, nullptr};
-    rc = step_gln(rg, g, &en, nullptr, cur, gx, s.act, Bt, B, L, stream);
-    if (rc) return rc;
-    const srf_norm an{s.act, b.act_g, b.act_be, nullptr};
-    rc = step_gln(rg, gx, &an, b.act_slope, nullptr, cur, nullptr, Bt, B, L, stream);
-    if (rc) return rc;
-  }
-
-  // ---- masks: [reshape_before_masks,] the basis-axis convolution as a GEMM, softmax over the sources times the encoder output
-  const float* xm = cur;
-  if (orig_has_reshape(p)) {
-    float* xr = fptr(p->off_orig_xr);
-    rc = conv(cur, t.rs_w, t.i_rs, t.rs_b, xr, B, N, nullptr, nullptr);
-    if (rc) return rc;
-    xm = xr;
-  }
-  float* z = fptr(p->off_orig_z);
-  float* masked = fptr(p->off_masked);
-  rc = conv(xm, tz, t.i_m, tz_bias, z, N, S * N, nullptr, nullptr);
-  if (rc) return rc;
-  rc = step_softmax(rg, z, enc, masked, Bt, S, N, L, stream);
-  if (rc) return rc;
-  // ---- decoder: the frame GEMM + overlap-add over the block-diagonal weight, then the bias (+ the callers' recipe)
-  rc = srf_decoder_impl(masked, wdec, out, Bt, S * N, S, K, L, p->T, fptr(p->off_dec), nullptr, nullptr, 0, stream, nullptr,
-                        rg ? &rg->lens_t : nullptr, rg ? &rg->frames_t : nullptr);
-  if (rc) return rc;
-  return step_bias(rg, out, t.dec_b, wav_stats, wav, mixture_consistency, Bt, S, p->T, stream);
+  return orig_walk(p, P, wav, out, a, pack, conv, rg || plan_fused_pyramid_now(p), rg, wav_stats, mixture_consistency, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -878,27 +744,24 @@ static int orig_ragged_prepare(const char* who, const srf_plan* p, const float* 
                                const void* workspace, size_t workspace_bytes, Ragged* rg) {
   const char* why = "";
   SRF_CHECK_ARG(orig_ragged_now(p, &why), "%s: plan not supported by the original model's ragged forward: %s", who, why);
-  SRF_CHECK_ARG(num_params == p->n_params, "%s (original): expected %d parameter tensors, got %d", who, p->n_params, num_params);
-  if (workspace_bytes < p->total_bytes) {
-    srf_set_error("%s (original): workspace too small (%zu < %zu bytes)", who, workspace_bytes, p->total_bytes);
-    return SRF_EWORKSPACE;
-  }
-  SRF_CHECK_ARG((((size_t)workspace) & 255) == 0, "%s (original): workspace must be 256-byte aligned", who);
-  for (int i = 0; i < num_params; ++i) SRF_CHECK_ARG(P[i] != nullptr, "%s (original): parameter %d is null", who, i);
+  // (the entry checks' messages carry the suffix; the gate's above and the tables' below do not.  `who` is one of the two entry
+  // points' names below, 28 characters at the most: nothing is cut)
+  char who_original[64];
+  snprintf(who_original, sizeof(who_original), "%s (original)", who);
+  int rc = forward_check_args(who_original, true /* checked by the caller */, p, P, num_params, workspace, workspace_bytes);
+  if (rc) return rc;
   const int D = p->cfg.upsampling_depth, h = p->cfg.enc_kernel_size / 2;
-  const long lcm = (long)h * (1L << D) / orig_gcd(h, 1L << D);
   rg->lengths = lengths;
   for (int b = 0; b < p->Bt; ++b) {
     SRF_CHECK_ARG(lengths[b] >= 1 && lengths[b] <= p->T, "%s (original): example %d has length %d (allowed: 1..%d)", who, b, lengths[b],
                   p->T);
-    // pad_to_appropriate_length of the example alone: up to a multiple of lcm(hop, 2^D), only when it is not one already
-    const long Tb = lengths[b] % lcm ? lengths[b] + lcm - lengths[b] % lcm : lengths[b];
-    rg->frames[b] = (int)(Tb / h);
+    // the example alone, padded by the model's own rule
+    rg->frames[b] = (int)(orig_padded_length(lengths[b], h, D) / h);
     SRF_CHECK_ARG(srf_pyramid_ragged_frames_ok(rg->frames[b], p->L, D),
                   "%s (original): example %d (length %d = %d frames) is too short for the fused pyramid or off its chunk grid", who, b,
                   lengths[b], rg->frames[b]);
   }
-  int rc = srf_frames_table(who, lengths, p->Bt, p->T, &rg->lens_t);
+  rc = srf_frames_table(who, lengths, p->Bt, p->T, &rg->lens_t);
   if (rc) return rc;
   return srf_frames_table(who, rg->frames, p->Bt, p->L, &rg->frames_t);
 }

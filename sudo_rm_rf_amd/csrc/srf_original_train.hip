@@ -8,7 +8,7 @@
 //   grads   : ACCUMULATED into, same order and shapes as the parameters; ln_mask_in.* (the last two) are never touched.
 // Every reduction of the new kernels writes block partials and adds them in a fixed order: no floating-point atomics.
 #include <vector>
-#include "srf_plan.h"
+#include "srf_original_walk.h"
 
 namespace {
 
@@ -565,18 +565,14 @@ OScratchLayout oscratch_layout(const srf_plan* p) {
     s.padg = all.take(F * Bt * rows * s.L4);
     s.padx = all.take(F * Bt * rows * s.L4);
   }
-  {
-    size_t pk = srf_align_up(srf_packed3_pw_weight_bytes(B, N), 256) + srf_align_up(srf_packed3_pw_weight_bytes(SN, N), 256) +
-                srf_align_up(srf_packed3_pw_weight_bytes(N, B), 256);
-    pk += (size_t)U * (srf_align_up(srf_packed3_pw_weight_bytes(C, B), 256) + srf_align_up(srf_packed3_pw_weight_bytes(B, C), 256));
-    s.pk3 = all.take(pk);
-  }
-  {
-    size_t pk = srf_align_up(srf_packed_pw_weight_bytes(N, SN), 256) + srf_align_up(srf_packed_pw_weight_bytes(N, B), 256) +
-                srf_align_up(srf_packed_pw_weight_bytes(B, N), 256);
-    pk += (size_t)U * (srf_align_up(srf_packed_pw_weight_bytes(B, C), 256) + srf_align_up(srf_packed_pw_weight_bytes(C, B), 256));
-    s.pkT = all.take(pk);
-  }
+  // the images of every 1x1 weight [cout, cin]: l1, the Toeplitz weight, reshape_before_masks, U x (proj_1x1, conv_1x1_exp) -- the
+  // forward's exact-class images, and the backward's images of the transposes
+  auto images = [&](size_t (*bytes)(int, int), bool transposed) {
+    auto one = [&](int cout, int cin) { return srf_align_up(transposed ? bytes(cin, cout) : bytes(cout, cin), 256); };
+    return one(B, N) + one(SN, N) + one(N, B) + (size_t)U * (one(C, B) + one(B, C));
+  };
+  s.pk3 = all.take(images(srf_packed3_pw_weight_bytes, false));
+  s.pkT = all.take(images(srf_packed_pw_weight_bytes, true));
   s.total = all.off;
   return s;
 }
@@ -589,115 +585,20 @@ bool original_plan(const srf_plan* p, const char* who) {
   return false;
 }
 
-int oforward_train_impl(const srf_plan* p, const float* const* P, const float* wav, float* out, void* saved, void* scratch,
-                        bool split_tail, void* stream) {
-  const OTrainLayout t = otrain_layout(p);
-  const OScratchLayout s = oscratch_layout(p);
-  const srf_config& c = p->cfg;
-  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size, S = c.num_sources, SN = S * N;
-  const int Bt = p->Bt, L = p->L, B = p->nB, C = p->nC;
-  char* sv = (char*)saved;
-  char* sc = (char*)scratch;
-  hipStream_t st = (hipStream_t)stream;
-  auto xbuf = [&](int i) { return (float*)(sv + t.x0 + t.x_stride * i); };
+// where the training forward keeps the walk's tensors: what the backward reads in `saved`, every block's own slices and one
+// block-stream buffer per block boundary; the rest (a / e, the masked tensor, the decoder's scratch, the two weight forms) in `scratch`
+SrfOrigAddrs otrain_addrs(const srf_plan* p, const OTrainLayout& t, const OScratchLayout& s, char* sv, char* sc) {
   auto fp = [&](size_t o) { return (float*)(sc + o); };
-  double* stats = (double*)(sv + t.stats);
-  const SrfOrigFront f = orig_front(P);
-  const SrfOrigTail tl = orig_tail(p, P);
-  int rc = srf_zero_launch(stats, p->stats_bytes, st);
-  if (rc) return rc;
-  float* tz = fp(s.tz);
-  float* tz_bias = tz + srf_align_up((size_t)S * N * N, 64);
-  float* wdec = fp(s.wdec);
-  rc = srf_mask_weight_fill(tl.m_w, tl.m_b, tz, tz_bias, N, S, stream);
-  if (rc) return rc;
-  rc = srf_decoder_weight_expand(tl.dec_w, wdec, N, S, K, stream);
-  if (rc) return rc;
-  // the exact-class images of the 1x1 weights the 256 x 128 GEMM takes, as srf_forward_train packs them
-  const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
-  SrfPackQueue pk{sc + s.pk3};
-  auto pack3 = [&](const float* w, int cout, int cin) { return pk.add(w, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin); };
-  const void* pk_l1 = pack3(f.l1_w, B, N);
-  const void* pk_mask = pack3(tz, SN, N);
-  const void* pk_rs = orig_has_reshape(p) ? pack3(tl.rs_w, N, B) : nullptr;
-  std::vector<const void*> pk_proj(U, nullptr), pk_exp(U, nullptr);
-  for (int i = 0; i < U; ++i) {
-    const SrfOrigBlock b = orig_block(p, P, i);
-    pk_proj[i] = pack3(b.proj_w, C, B);
-    pk_exp[i] = pack3(b.exp_w, B, C);
-  }
-  rc = pk.pack3(stream);
-  if (rc) return rc;
-  auto conv = [&](const float* x, const float* w, const void* w3, const float* bias, float* y, int Cin, int Cout, const srf_norm* in_norm,
-                  double* out_sums) {
-    return srf_pw_conv_packed3(x, w, w3, bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, stream);
-  };
-  // ---- front end
-  float* enc = (float*)(sv + t.enc);
-  rc = srf_encoder_bias_relu(wav, f.enc_w, f.enc_b, enc, stats, Bt, p->T, N, K, L, nullptr, stream);
-  if (rc) return rc;
-  {
-    const srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
-    rc = conv(enc, f.l1_w, pk_l1, f.l1_b, xbuf(0), N, B, &ln, nullptr);
-    if (rc) return rc;
-  }
-  // ---- separation module: the pyramid level by level, every raw level kept
-  float* act = fp(s.act);
-  for (int i = 0; i < U; ++i) {
-    const SrfOrigBlock b = orig_block(p, P, i);
-    const SrfOrigSlots sl = orig_slots(p, stats, i);
-    char* blk = sv + t.blk0 + t.blk_stride * i;
-    float *y1 = (float*)(blk + t.y1), *m = (float*)(blk + t.m), *g = (float*)(blk + t.g), *gx = (float*)(blk + t.gx);
-    rc = conv(xbuf(i), b.proj_w, pk_proj[i], b.proj_b, y1, B, C, nullptr, sl.proj);
-    if (rc) return rc;
-    const srf_norm pn{sl.proj, b.proj_g, b.proj_be, nullptr};
-    rc = srf_gln_apply_c(y1, &pn, b.proj_slope, nullptr, act, nullptr, Bt, C, L, stream);
-    if (rc) return rc;
-    const float* levels[SRF_MAX_DEPTH];
-    srf_norm norms[SRF_MAX_DEPTH];
-    for (int k = 0; k < D; ++k) {
-      float* lv = (float*)(blk + t.lv[k]);
-      rc = srf_dwconv5(k == 0 ? act : levels[k - 1], b.lv_w[k], b.lv_b[k], lv, Bt, C, k == 0 ? L : L >> (k - 1), k == 0 ? 1 : 2,
-                       k == 0 ? nullptr : &norms[k - 1], sl.level[k], stream);
-      if (rc) return rc;
-      levels[k] = lv;
-      norms[k] = srf_norm{sl.level[k], b.lv_g[k], b.lv_be[k], nullptr};
-    }
-    rc = srf_merge(levels, norms, D, m, Bt, C, L, sl.merged, stream);
-    if (rc) return rc;
-    const srf_norm fn{sl.merged, b.fin_g, b.fin_be, nullptr};
-    rc = srf_gln_apply_c(m, &fn, b.fin_slope, nullptr, act, nullptr, Bt, C, L, stream);
-    if (rc) return rc;
-    rc = conv(act, b.exp_w, pk_exp[i], b.exp_b, g, C, B, nullptr, sl.exp);
-    if (rc) return rc;
-    const srf_norm en{sl.exp, b.exp_g, b.exp_be, nullptr};
-    rc = srf_gln_apply_c(g, &en, nullptr, xbuf(i), gx, sl.act, Bt, B, L, stream);
-    if (rc) return rc;
-    const srf_norm an{sl.act, b.act_g, b.act_be, nullptr};
-    rc = srf_gln_apply_c(gx, &an, b.act_slope, nullptr, xbuf(i + 1), nullptr, Bt, B, L, stream);
-    if (rc) return rc;
-  }
-  // ---- masks and decoder
-  const float* xm = xbuf(U);
-  if (orig_has_reshape(p)) {
-    float* xr = (float*)(sv + t.xr);
-    rc = conv(xbuf(U), tl.rs_w, pk_rs, tl.rs_b, xr, B, N, nullptr, nullptr);
-    if (rc) return rc;
-    xm = xr;
-  }
-  float* z = (float*)(sv + t.z);
-  rc = conv(xm, tz, pk_mask, tz_bias, z, N, SN, nullptr, nullptr);
-  if (rc) return rc;
-  float* masked = fp(s.vbuf);
-  rc = srf_softmax_mask(z, enc, masked, Bt, S, N, L, stream);
-  if (rc) return rc;
-  // the decoder's frame GEMM is the last linear map: on the split kernel when the exact class was this call's own choice
-  {
-    const SrfKernelModeScope split_class(split_tail, 0);
-    rc = srf_decoder_impl(masked, wdec, out, Bt, SN, S, K, L, p->T, fp(s.dec), nullptr, nullptr, 0, stream);
-  }
-  if (rc) return rc;
-  return srf_bias_rescale(out, tl.dec_b, nullptr, nullptr, 0, Bt, S, p->T, stream);
+  SrfOrigAddrs a{};
+  a.stats = (double*)(sv + t.stats);
+  a.enc = (float*)(sv + t.enc);
+  a.x = sv + t.x0, a.x_stride = t.x_stride;
+  a.blk = sv + t.blk0, a.blk_stride = t.blk_stride;
+  a.o_y1 = t.y1, a.o_m = t.m, a.o_g = t.g, a.o_gx = t.gx;
+  for (int k = 0; k < p->cfg.upsampling_depth; ++k) a.o_lv[k] = t.lv[k];
+  a.act = fp(s.act), a.xr = (float*)(sv + t.xr), a.z = (float*)(sv + t.z), a.masked = fp(s.vbuf);
+  a.dec = fp(s.dec), a.tz = fp(s.tz), a.wdec = fp(s.wdec);
+  return a;
 }
 
 }  // namespace
@@ -727,7 +628,32 @@ extern "C" int srf_original_forward_train(const srf_plan* p, const float* const*
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
   // (the decoder's frame GEMM stays in the exact class too, unlike srf_forward_train's: its rounding is the output's, and the
   // runner's loss and its gradient go with 1 / <estimate, target>)
-  return oforward_train_impl(p, P, wav, out, saved, scratch, /*split_tail=*/false, stream);
+  // the walk of the inference forward with every block's tensors kept, the pyramid level by level (the backward reads every raw
+  // level) and the exact-class images of the 1x1 weights the 256 x 128 GEMM takes, as srf_forward_train packs them
+  const OScratchLayout s = oscratch_layout(p);
+  const int U = p->cfg.num_blocks, N = p->cfg.enc_num_basis, SN = p->cfg.num_sources * N, B = p->nB, C = p->nC;
+  const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
+  std::vector<const void*> image(p->n_params, nullptr);      // parameter index -> its packed image (NULL: none)
+  auto pack = [&](const float* tz) {
+    SrfPackQueue pk{(char*)scratch + s.pk3};
+    auto add = [&](int param, const float* w, int cout, int cin) {
+      image[param] = pk.add(w, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin);
+    };
+    add(SRF_PO_L1, P[SRF_PO_L1], B, N);
+    add(orig_p_mask(p), tz, SN, N);
+    if (orig_has_reshape(p)) add(orig_p_reshape(p), P[orig_p_reshape(p)], N, B);
+    for (int i = 0; i < U; ++i) {
+      add(orig_p_proj(p, i), P[orig_p_proj(p, i)], C, B);
+      add(orig_p_exp(p, i), P[orig_p_exp(p, i)], B, C);
+    }
+    return pk.pack3(stream);
+  };
+  auto conv = [&](const float* x, const float* w, int param, const float* bias, float* y, int Cin, int Cout, const srf_norm* in_norm,
+                  double* out_sums) {
+    return srf_pw_conv_packed3(x, w, image[param], bias, y, p->Bt, Cin, Cout, p->L, in_norm, nullptr, out_sums, stream);
+  };
+  return orig_walk(p, P, wav, out, otrain_addrs(p, otrain_layout(p), s, (char*)saved, (char*)scratch), pack, conv, /*fused=*/false,
+                   nullptr, nullptr, 0, stream);
 }
 
 extern "C" int srf_original_backward(const srf_plan* p, const float* const* P, float* const* G, int num_params, const float* wav,
@@ -765,11 +691,8 @@ extern "C" int srf_original_backward(const srf_plan* p, const float* const* P, f
   const SrfWgradOrderedScope ordered_for_this_call;
   // ---- the two weights in their GEMM forms, again (scratch is not kept between the calls)
   float* tz = fp(s.tz);
-  float* tz_bias = tz + srf_align_up((size_t)S * N * N, 64);
   float* wdec = fp(s.wdec);
-  rc = srf_mask_weight_fill(tl.m_w, tl.m_b, tz, tz_bias, N, S, stream);
-  if (rc) return rc;
-  rc = srf_decoder_weight_expand(tl.dec_w, wdec, N, S, K, stream);
+  rc = srf_original_weight_forms(p, P, tz, wdec, stream);
   if (rc) return rc;
   // transposed weights of the data-gradient GEMMs, pre-split for the 256 x 128 kernel where it takes the shape
   SrfPackQueue pk{sc + s.pkT};
@@ -852,7 +775,7 @@ extern "C" int srf_original_backward(const srf_plan* p, const float* const* P, f
   // ---- 3. mask GEMM z = Tz xm + bias rows
   const float* xm = orig_has_reshape(p) ? (const float*)(sv + t.xr) : xbuf(U);
   float* dtz = fp(s.dtz);
-  float* drow = dtz + srf_align_up((size_t)S * N * N, 64);
+  float* drow = dtz + orig_tz_bias_at(S, N);
   rc = wgrad(gv, xm, nullptr, N, SN, dtz, N, drow, 0);
   if (rc) return rc;
   rc = srf_mask_weight_fold(dtz, drow, gtl.m_w, gtl.m_b, N, S, stream);

@@ -253,8 +253,17 @@ template <typename T> static inline SrfOrigTailT<T> orig_tail(const srf_plan* p,
   v.m_w = t[v.i_m], v.m_b = t[v.i_m + 1], v.dec_w = t[v.i_m + 2], v.dec_b = t[v.i_m + 3];
   return v;
 }
-// floats of the Toeplitz weight's region: tz [S N, N] | bias rows [S N]   (each section 64-float aligned)
-static inline size_t orig_tz_floats(int S, int N) { return srf_align_up((size_t)S * N * N, 64) + srf_align_up((size_t)S * N, 64); }
+// the Toeplitz weight's region: tz [S N, N] | bias rows [S N]   (each section 64-float aligned; the same layout holds the two
+// gradients in the backward).  orig_tz_bias_at: floats in front of the bias rows; orig_tz_floats: floats of the region
+static inline size_t orig_tz_bias_at(int S, int N) { return srf_align_up((size_t)S * N * N, 64); }
+static inline size_t orig_tz_floats(int S, int N) { return orig_tz_bias_at(S, N) + srf_align_up((size_t)S * N, 64); }
+// pad_to_appropriate_length: T up to a multiple of lcm(hop, 2^D), only when it is not one already (the plan's Tp, and every
+// example's own padded length in a ragged batch)
+static inline long orig_gcd(long a, long b) { return b ? orig_gcd(b, a % b) : a; }
+static inline long orig_padded_length(long T, int h, int D) {
+  const long lcm = (long)h * (1L << D) / orig_gcd(h, 1L << D);
+  return T % lcm ? T + lcm - T % lcm : T;
+}
 static inline SrfOrigSlots orig_slots(const srf_plan* p, double* stats, int i) {
   const size_t each = (size_t)p->Bg * SRF_STAT_BUCKETS * 2;
   const int D = p->cfg.upsampling_depth;

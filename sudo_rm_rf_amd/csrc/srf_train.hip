@@ -389,12 +389,12 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
     // otherwise D depthwise kernels + the merge kernel.
     float* lv[SRF_MAX_DEPTH];
     for (int k = 0; k < D; ++k) lv[k] = (float*)(blk + t.lv[k]);
+    const srf_norm in{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
     if (fused_pyr) {
       if (skip_d0) lv[0] = nullptr;
-      const srf_norm in{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
       rc = srf_pyramid_impl(y1, merged, &in, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bg, nC, L, D, sc + s.gf, sl.merged, lv, sl.level, stream);
     } else {
-      rc = srf_pyramid_per_level(y1, lv, merged, b, sl, Bg, nC, L, D, stream);
+      rc = srf_pyramid_per_level(y1, &in, lv, merged, b.lv_w, b.lv_b, b.lv_g, b.lv_be, sl.level, sl.merged, Bg, nC, L, D, stream);
     }
     if (rc) return rc;
     srf_norm fn{sl.merged, b.fin_g, b.fin_be, b.fin_prelu};

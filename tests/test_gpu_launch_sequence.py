@@ -22,7 +22,13 @@ took their parameters through the named views of srf_plan.h and shared their wei
 
 The original model's training step ("original train ..." below): one opted-in step at three fixture shapes -- orig_tiny (also
 under kernel mode 1), orig_same (no reshape_before_masks) and orig_d1 (34 frames: the padded weight-gradient path) -- recorded on
-commit 4711e9b, the commit BEFORE the three training steps took their pack queue, call guards and entry check from one place."""
+commit 4711e9b, the commit BEFORE the three training steps took their pack queue, call guards and entry check from one place.
+
+The original model's inference, separate and ragged walks ("original ..." below, without "train"): four fixture shapes at their own
+batch and T (orig_tiny, orig_same, orig_d1, orig_s3_k9: the pyramid level by level), orig_default_u2 (the one uniform shape of
+these that runs the fused pyramid), orig_tiny again under PYR_PER_LEVEL, under kernel mode 1 and through
+pipeline.separate with mixture consistency, and rg_c -- the smallest configuration the ragged gate takes -- through forward_ragged
+and separate_ragged.  Recorded on commit 30e11c2, the commit BEFORE the inference walk and the training forward became one walk."""
 import numpy as np
 import pytest
 import torch
@@ -31,6 +37,7 @@ from conftest import load_case
 from tests import attentive_fixtures as af
 from tests import causal_fixtures as cf
 from tests import original_fixtures as of
+from tests import original_ragged_fixtures as rf
 from oracle import weights
 from oracle.schema import ModelConfig
 from test_gpu_model import build
@@ -208,6 +215,45 @@ def original_train_step_trace(name, setting="0"):
     return [n for n, _ in tr.launches]
 
 
+def original_model(cfg, wseed):
+    from sudo_rm_rf_amd.dnn.models.sudormrf import SuDORMRF
+    m = SuDORMRF(**cfg)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in of.make_state_dict(cfg, wseed).items()})
+    return m.to(DEV).eval()
+
+
+def original_forward_trace(name, setting="0"):
+    """one inference forward of the original model at the batch and T of an of.CASES fixture"""
+    cfg, batch, T_, wseed, _ = of.CASES[name]
+    x = torch.from_numpy(of.make_input(name)).to(DEV)
+    assert tuple(x.shape) == (batch, 1, T_)
+    return causal_forward_trace(original_model(cfg, wseed), x, setting)
+
+
+def original_separate_trace(name):
+    """pipeline.separate (srf_separate) with mixture consistency on: the statistics launch, then the forward's walk"""
+    from sudo_rm_rf_amd import ops, pipeline
+    cfg, batch, T_, wseed, _ = of.CASES[name]
+    m = original_model(cfg, wseed)
+    m._engine().multi_stream = False
+    with ops.kernel_trace(DEV) as tr:
+        pipeline.separate(m, torch.from_numpy(of.make_input(name)).to(DEV), mixture_consistency=True)
+    return [n for n, _ in tr.launches]
+
+
+def original_ragged_trace(name, entry):
+    """forward_ragged / separate_ragged of an opted-in model over the padded batch of an rf.CASES fixture"""
+    from sudo_rm_rf_amd import ops
+    cfg, T_, lengths, wseed, _ = rf.CASES[name]
+    m = original_model(cfg, wseed).enable_ragged()
+    m._engine().multi_stream = False
+    x = torch.from_numpy(rf.make_wav(name)).to(DEV)
+    assert tuple(x.shape) == (len(lengths), 1, T_)
+    with torch.no_grad(), ops.kernel_trace(DEV) as tr:
+        getattr(m, entry)(x, list(lengths))
+    return [n for n, _ in tr.launches]
+
+
 def causal_stream_push_trace():
     """one srf_stream_push of one granule per stream, on a session of causal_tiny's model and batch"""
     from sudo_rm_rf_amd import ops
@@ -257,6 +303,19 @@ CAUSAL_TRACES = {
     "original train orig_tiny kernel_mode_1": lambda: original_train_step_trace("orig_tiny", "kernel_mode_1"),
     "original train orig_same 0": lambda: original_train_step_trace("orig_same"),          # B == N: no reshape_before_masks
     "original train orig_d1 0": lambda: original_train_step_trace("orig_d1"),              # 34 frames: the padded weight-gradient path
+}
+
+ORIGINAL_TRACES = {
+    "original orig_tiny 0": lambda: original_forward_trace("orig_tiny"),
+    "original orig_same 0": lambda: original_forward_trace("orig_same"),                   # B == N: no reshape_before_masks
+    "original orig_d1 0": lambda: original_forward_trace("orig_d1"),
+    "original orig_s3_k9 0": lambda: original_forward_trace("orig_s3_k9"),                 # K = 9: the any-K encoder; three sources
+    "original orig_default_u2 0": lambda: original_forward_trace("orig_default_u2"),       # the fused pyramid, uniform
+    "original orig_tiny PYR_PER_LEVEL": lambda: original_forward_trace("orig_tiny", "PYR_PER_LEVEL"),
+    "original orig_tiny kernel_mode_1": lambda: original_forward_trace("orig_tiny", "kernel_mode_1"),
+    "original separate orig_tiny mixture_consistency": lambda: original_separate_trace("orig_tiny"),
+    "original forward_ragged rg_c": lambda: original_ragged_trace("rg_c", "forward_ragged"),
+    "original separate_ragged rg_c": lambda: original_ragged_trace("rg_c", "separate_ragged"),
 }
 
 
@@ -606,6 +665,81 @@ EXPECTED.update({      # recorded on commit 4711e9b
 })
 
 
+EXPECTED.update({      # recorded on commit 30e11c2
+    "original orig_tiny 0": [      # 33 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_small", "gln_apply_c", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_generic", "merge_fast",
+          "gln_apply_c", "pw_conv_bf16x3_w4", "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_small", "pw_conv_bf16x3_w4", "softmax_mask", "transpose", "zero_fill", "pw_conv_bf16x3_w4",
+          "overlap_add", "bias_rescale"), 1),
+    ],
+    "original orig_same 0": [      # 32 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_small"), 1),
+        (("pw_conv_small", "gln_apply_c", "dwconv5_s1_fast", "dwconv5_generic", "dwconv5_generic", "merge_fast",
+          "gln_apply_c", "pw_conv_bf16x3_w4", "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_small", "softmax_mask", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "bias_rescale"), 1),
+    ],
+    "original orig_d1 0": [      # 29 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_generic"), 1),
+        (("pw_conv_generic", "gln_apply_c", "dwconv5_generic", "merge_generic", "gln_apply_c", "pw_conv_generic",
+          "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_generic", "pw_conv_generic", "softmax_mask", "transpose", "zero_fill", "pw_conv_generic",
+          "overlap_add", "bias_rescale"), 1),
+    ],
+    "original orig_s3_k9 0": [      # 33 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_small", "gln_apply_c", "dwconv5_s1_fast", "dwconv5_generic", "dwconv5_generic", "merge_fast",
+          "gln_apply_c", "pw_conv_bf16x3_w4", "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_small", "pw_conv_bf16x3_w4", "softmax_mask", "transpose", "zero_fill", "pw_conv_generic",
+          "overlap_add", "bias_rescale"), 1),
+    ],
+    "original orig_default_u2 0": [      # 32 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "pack_pw_weights", "encoder_bias_relu",
+          "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_bf16x3_w4", "gln_apply_c", "pyramid_moments", "pyramid_finalize", "pyramid_merge", "gln_apply_c",
+          "pw_conv_bf16x3_w4", "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_bf16x3_w4", "pw_conv_bf16x3_w8", "softmax_mask", "transpose", "zero_fill", "pw_conv_bf16x3_w4",
+          "overlap_add", "bias_rescale"), 1),
+    ],
+    "original orig_tiny PYR_PER_LEVEL": [      # 33 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_small", "gln_apply_c", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_generic", "merge_fast",
+          "gln_apply_c", "pw_conv_bf16x3_w4", "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_small", "pw_conv_bf16x3_w4", "softmax_mask", "transpose", "zero_fill", "pw_conv_bf16x3_w4",
+          "overlap_add", "bias_rescale"), 1),
+    ],
+    "original orig_tiny kernel_mode_1": [      # 33 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_generic"), 1),
+        (("pw_conv_generic", "gln_apply_c_scalar", "dwconv5_generic", "dwconv5_generic", "dwconv5_generic",
+          "merge_generic", "gln_apply_c_scalar", "pw_conv_generic", "gln_apply_c_scalar", "gln_apply_c_scalar"), 2),
+        (("pw_conv_generic", "pw_conv_generic", "softmax_mask", "transpose", "zero_fill", "pw_conv_generic",
+          "overlap_add", "bias_rescale"), 1),
+    ],
+    "original separate orig_tiny mixture_consistency": [      # 34 launches
+        (("wav_stats", "zero_fill", "mask_weight_fill", "decoder_weight_expand", "encoder_bias_relu", "pw_conv_bf16x3_w4"), 1),
+        (("pw_conv_small", "gln_apply_c", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_generic", "merge_fast",
+          "gln_apply_c", "pw_conv_bf16x3_w4", "gln_apply_c", "gln_apply_c"), 2),
+        (("pw_conv_small", "pw_conv_bf16x3_w4", "softmax_mask", "transpose", "zero_fill", "pw_conv_bf16x3_w4",
+          "overlap_add", "bias_rescale"), 1),
+    ],
+    "original forward_ragged rg_c": [      # 22 launches
+        (("zero_fill", "mask_weight_fill", "decoder_weight_expand", "pack_pw_weights", "encoder_bias_relu_ragged",
+          "pw_conv_x3w_ragged<1>", "pw_conv_x3w_ragged<0>", "gln_apply_c_ragged", "pyramid_moments_ragged",
+          "pyramid_finalize_ragged", "pyramid_merge_ragged", "gln_apply_c_ragged", "pw_conv_x3w_ragged<0>",
+          "gln_apply_c_ragged", "gln_apply_c_ragged", "pw_conv_x3w_ragged<0>", "softmax_mask_ragged", "transpose",
+          "zero_fill", "pw_conv_bf16x3_w4", "overlap_add_ragged", "bias_rescale_ragged"), 1),
+    ],
+    "original separate_ragged rg_c": [      # 23 launches
+        (("wav_stats_ragged", "zero_fill", "mask_weight_fill", "decoder_weight_expand", "pack_pw_weights",
+          "encoder_bias_relu_ragged", "pw_conv_x3w_ragged<1>", "pw_conv_x3w_ragged<0>", "gln_apply_c_ragged",
+          "pyramid_moments_ragged", "pyramid_finalize_ragged", "pyramid_merge_ragged", "gln_apply_c_ragged",
+          "pw_conv_x3w_ragged<0>", "gln_apply_c_ragged", "gln_apply_c_ragged", "pw_conv_x3w_ragged<0>",
+          "softmax_mask_ragged", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add_ragged",
+          "bias_rescale_ragged"), 1),
+    ],
+})
+
+
 def _check(name, got):
     want = _expand(EXPECTED[name])
     first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
@@ -634,3 +768,8 @@ def test_launch_sequence_of_a_training_step(shape, setting):
 @pytest.mark.parametrize("name", list(CAUSAL_TRACES))
 def test_launch_sequence_of_the_causal_and_attentive_walks(name):
     _check(name, CAUSAL_TRACES[name]())
+
+
+@pytest.mark.parametrize("name", list(ORIGINAL_TRACES))
+def test_launch_sequence_of_the_original_inference_and_ragged_walks(name):
+    _check(name, ORIGINAL_TRACES[name]())
