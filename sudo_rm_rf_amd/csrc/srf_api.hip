@@ -11,7 +11,7 @@
 #include <new>
 #include <vector>
 
-#include "srf_plan.h"
+#include "srf_improved_walk.h"
 
 // ---------------------------------------------------------------------------------------------
 // error string / kernel mode
@@ -475,83 +475,17 @@ int forward_check_args(const char* who, bool ptrs, const srf_plan* p, const floa
   return SRF_OK;
 }
 
-// ---- the steps of the walk, one per kernel family: the uniform entry point, or -- rg != NULL, srf_forward_ragged -- its ragged
-// twin with the batch's frame counts.  Every per-launch refusal stays with the entry point.
-// (struct Ragged: srf_internal.h)
-static int step_encoder(const Ragged* rg, const float* wav, const float* w, float* enc, double* sums, int Bt, int A, int T, int N,
-                        int K, int L, const float* wav_stats, void* stream) {
-  return rg ? srf_encoder_ragged_impl(wav, w, enc, sums, Bt, A, T, N, K, L, rg->lengths, rg->frames, wav_stats, stream)
-            : srf_encoder_impl(wav, w, enc, sums, Bt, A, T, N, K, L, wav_stats, stream);
-}
-// rows = examples * rows_per_example (GroupComm's per-group convs run over the folded rows).  Ragged: as in srf_pw_conv_packed
-// the thin-shape kernel has precedence, everything else is the 256 x 128 kernel (rows_per_example = 1)
-static int step_conv(const Ragged* rg, int rows_per_example, const float* x, const float* w, const void* w_packed, const float* bias,
-                     float* y, int rows, int Cin, int Cout, int L, const srf_norm* in_norm, const float* residual, double* out_sums,
-                     void* stream) {
-  if (!rg) return srf_pw_conv_packed(x, w, w_packed, bias, y, rows, Cin, Cout, L, in_norm, residual, out_sums, 0, nullptr, 0, stream);
-  if (srf_pw_small_ragged_supported(Cin, Cout, L))
-    return srf_pw_conv_small_ragged(x, w, bias, y, rows, Cin, Cout, L, in_norm, residual, out_sums, nullptr, nullptr, nullptr,
-                                    rg->frames, rows_per_example, stream);
-  return srf_pw_conv_packed_ragged(x, w, w_packed, bias, y, rows, Cin, Cout, L, in_norm, residual, out_sums, 0, nullptr, 0, rg->frames,
-                                   stream);
-}
-static int step_pair(const Ragged* rg, const float* x, const void* w1_packed, const float* bias1, float* y, const srf_norm* in_norm,
-                     const float* residual, const void* w2_packed, const float* bias2, float* y2, double* out_sums2, int Bt, int Cin1,
-                     int Cmid, int Cout2, int L, void* stream) {
-  return rg ? srf_pw_conv_pair_ragged(x, w1_packed, bias1, y, in_norm, residual, w2_packed, bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2,
-                                      L, rg->frames, stream)
-            : srf_pw_conv_pair(x, w1_packed, bias1, y, in_norm, residual, w2_packed, bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2, L,
-                               stream);
-}
-static int step_tac(const Ragged* rg, const float* x, float* q, const float* const* params, int Bt, int G, int n, int H, int L,
-                    double* out_sums, void* stream) {
-  return rg ? srf_tac_ragged(x, q, params, Bt, G, n, H, L, out_sums, rg->frames, stream)
-            : srf_tac(x, q, params, Bt, G, n, H, L, out_sums, stream);
-}
-// proj_1x1 with u = x + GlobLN(q) folded into its operand load (u is written for the block's residual as it goes)
-static int step_preadd(const Ragged* rg, int G, const float* x, const float* q, const srf_norm* qnorm, float* u, const float* w,
-                       const float* bias, float* y, int Bg, int Cin, int Cout, int L, double* out_sums, void* stream) {
-  return rg ? srf_pw_conv_small_ragged(x, w, bias, y, Bg, Cin, Cout, L, nullptr, nullptr, out_sums, q, qnorm, u, rg->frames, G, stream)
-            : srf_pw_conv_preadd(x, q, qnorm, u, w, bias, y, Bg, Cin, Cout, L, out_sums, (hipStream_t)stream);
-}
-// the fused pyramid: two passes with every level kept on chip (srf_pyramid.hip), over G folded rows per example
-static int step_pyramid(const Ragged* rg, int G, const float* y1, float* merged, const srf_norm* in_norm, const SrfBlock<const float>& b,
-                        int Bg, int C, int L, int D, void* scratch, double* out_sums, void* stream) {
-  return rg ? srf_pyramid_ragged_rows(y1, merged, in_norm, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bg, C, L, D, scratch, out_sums, rg->frames, G,
-                                      stream)
-            : srf_pyramid(y1, merged, in_norm, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bg, C, L, D, scratch, out_sums, stream);
-}
-// the ragged form reads the example's own frames only; its post-processing (wav_stats: srf_separate_ragged) stays on the example's
-// own samples
-static int step_overlap_add(const Ragged* rg, const float* z, float* out, int Bt, int Co, int K, int L, int T, int nparts,
-                            const float* wav_stats, const float* wav, int mc, hipStream_t st) {
-  return rg ? srf_overlap_add_launch(z, out, Bt, Co, K, L, T, nparts, wav_stats, wav, mc, st, &rg->lens_t, &rg->frames_t)
-            : srf_overlap_add_launch(z, out, Bt, Co, K, L, T, nparts, wav_stats, wav, mc, st);
-}
-
-// THE walk of the Improved / GroupComm inference forward: srf_forward, srf_separate (wav_stats), srf_forward_ragged (rg) and
-// srf_separate_ragged (both).
-// The ragged forward keeps the layout -- [batch, C, L] with L the PLAN's frame count as row stride, the same workspace carve-up
-// and two-buffer scheme -- and every kernel takes the example's own frame count L_b from a by-value table.  The invariant:
-//   * a tensor whose GlobLN statistics are taken (enc, y1, merged; GroupComm: q) is exactly zero at columns >= L_b, so the
-//     sums come out right and only the count changes (C * L_b);
-//   * a tensor read with a halo (the wave by the encoder, y1 by the pyramid) is never read past the example's end;
-//   * the block stream (cur / nxt / u: pointwise consumers only) may hold anything there -- so may the partial decoder frames the
-//     unchanged mask + decoder GEMM leaves at those columns: the ragged overlap-add never reads them.
+// The Improved / GroupComm inference forward: srf_forward, srf_separate (wav_stats), srf_forward_ragged (rg) and
+// srf_separate_ragged (both).  It is improved_walk (srf_improved_walk.h, which also has the ragged invariant) over the plan's
+// workspace -- two alternating stream buffers, one set of block tensors -- with the statistics cleared by a launch, the plan's
+// packed images behind step helpers that pick the ragged twins, and srf_improved_tail.
 static int forward_walk(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                         const float* wav_stats, int mixture_consistency, const Ragged* rg, void* stream) {
   const srf_config& c = p->cfg;
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
-  const int G = gc ? c.group_size : 1;
-  const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
-  const int Bt = p->Bt, L = p->L, Bg = p->Bg, nB = p->nB, nC = p->nC;
+  const int N = c.enc_num_basis, Bt = p->Bt, L = p->L, nB = p->nB, nC = p->nC;
   char* ws = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  auto fptr = [&](size_t o) { return (float*)(ws + o); };
-  double* stats = (double*)(ws + p->off_stats);      // (the slot of ln is the first)
-  int rc;
-
-  rc = srf_zero_launch(stats, p->stats_bytes, st);
+  int rc = srf_zero_launch(ws + p->off_stats, p->stats_bytes, (hipStream_t)stream);
   if (rc) return rc;
   // A ragged batch runs what plan_ragged_now has made sure the uniform forward would choose here -- the packed weights, the fused
   // pyramid, the pair at the head and after every block (Improved) or the pre-add form (GroupComm), the fused tail -- whatever
@@ -562,101 +496,36 @@ static int forward_walk(const srf_plan* p, const float* const* P, const float* w
     if (rc) return rc;
   }
   auto packed = [&](int param) { return plan_packed(p, ws, use_pack, param); };
-
-  // ---- front end: encoder (+ ln statistics), ln folded into the bottleneck GEMM's operand load
-  const SrfFront<const float> f = plan_front(P);
-  const SrfBlock<const float> b0 = plan_block(p, P, 0);
-  float* enc = fptr(p->off_enc);
-  rc = step_encoder(rg, wav, f.enc_w, enc, stats, Bt, p->A, p->T, N, K, L, wav_stats, stream);
-  if (rc) return rc;
-  float* cur = fptr(p->off_xa);
-  float* nxt = fptr(p->off_xb);
-  float* y1 = fptr(p->off_y1);
+  auto conv = [&](int rows_per_example, const float* x, const float* w, int param, const float* bias, float* y, int rows, int Cin,
+                  int Cout, const srf_norm* in_norm, const float* residual, double* out_sums) {
+    return imp_conv(rg, rows_per_example, x, w, packed(param), bias, y, rows, Cin, Cout, L, in_norm, residual, out_sums, stream);
+  };
+  auto pair = [&](const float* x, int param1, const float* bias1, float* y, const srf_norm* in_norm, const float* residual, int param2,
+                  const float* bias2, float* y2, double* out_sums2, int Cin1, int Cmid, int Cout2) {
+    return imp_pair(rg, x, packed(param1), bias1, y, in_norm, residual, packed(param2), bias2, y2, out_sums2, Bt, Cin1, Cmid, Cout2, L,
+                    stream);
+  };
   // Round 5: a 1x1 conv with 256 output channels and the proj_1x1 that consumes its output run as ONE launch, the 256-channel
   // tensor handed over in registers (srf_pwconv_x3f.hip): bottleneck -> proj_1x1 of block 0, res_conv of block i -> proj_1x1 of
-  // block i + 1 (improved_sudormrf.py:292 -> :205, :220 -> :205).  Needs the fused pyramid (its merged tensor has a buffer of
-  // its own: the pair kernel writes y1 while it reads the merged tensor).  Debug flag 1 = separate launches.
+  // block i + 1.  Needs the fused pyramid (its merged tensor has a buffer of its own: the pair kernel writes y1 while it reads the
+  // merged tensor), and the head pair only runs where the block pairs do.  Debug flag 1 = separate launches.
   const bool fused = rg || plan_fused_pyramid_now(p);
-  const bool pair_res = !gc && (rg || (use_pack && fused && packed(b0.i_proj) && packed(b0.i_res) &&
-                                       srf_pw_conv_pair_supported(Bt, nC, nB, nC, L)));
+  const int i_proj = plan_p_proj(p, 0), i_res = plan_p_res(p, 0);
+  const bool pair_res = !gc && (rg || (use_pack && fused && packed(i_proj) && packed(i_res) && srf_pw_conv_pair_supported(Bt, nC, nB, nC, L)));
   const bool pair_head = pair_res && (rg || (packed(SRF_P_BOTTLENECK) && srf_pw_conv_pair_supported(Bt, N, nB, nC, L)));
-  bool y1_ready = false;      // proj_1x1 of the coming block has already been computed (with its statistics) by a pair launch
-  {
-    srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
-    if (pair_head) {
-      rc = step_pair(rg, enc, packed(SRF_P_BOTTLENECK), f.bott_b, cur, &ln, nullptr, packed(b0.i_proj), b0.proj_b, y1,
-                     plan_slots(p, stats, 0).proj, Bt, N, nB, nC, L, stream);
-      y1_ready = true;
-    } else {
-      rc = step_conv(rg, 1, enc, f.bott_w, packed(SRF_P_BOTTLENECK), f.bott_b, cur, Bt, N, c.out_channels, L, &ln, nullptr, nullptr,
-                     stream);
-    }
-    if (rc) return rc;
-  }
 
-  // ---- separation module (GroupComm: every kernel of a block over the Bt * G folded rows, finding its example as row / G)
-  for (int i = 0; i < U; ++i) {
-    const SrfBlock<const float> b = plan_block(p, P, i);
-    const SrfSlots s = plan_slots(p, stats, i);
-    const float* xin = cur;
-    bool tac_norm_fused = false;
-    if (gc) {
-      // TAC (groupcomm_sudormrf_v2.py:356-384): q = TAC MLPs, u = x + GlobLN_(b,g)(q)
-      float* xq = fptr(p->off_xq);
-      float* xu = fptr(p->off_xu);
-      rc = step_tac(rg, cur, xq, b.tac, Bt, G, nB, 3 * nB, L, s.tac, stream);
-      if (rc) return rc;
-      srf_norm tn{s.tac, b.tac_g, b.tac_b, nullptr};
-      // u = x + GlobLN(q): folded into the proj conv's operand load where the thin-shape kernel runs it (it writes u for
-      // the block's residual as it goes); else its own kernel
-      const void* al[4] = {cur, xq, xu, y1};
-      tac_norm_fused = rg || srf_pw_conv_preadd_supported(nB, nC, L, al, 4);
-      if (tac_norm_fused) {
-        rc = step_preadd(rg, G, cur, xq, &tn, xu, b.proj_w, b.proj_b, y1, Bg, nB, nC, L, s.proj, stream);
-      } else {
-        rc = srf_gln_apply_add(cur, xq, xu, &tn, Bg, nB, L, stream);
-      }
-      if (rc) return rc;
-      xin = xu;
-    }
-    // proj_1x1 conv (+ statistics for its GlobLN)            improved_sudormrf.py:205
-    if (!tac_norm_fused && !y1_ready) {
-      rc = step_conv(rg, G, xin, b.proj_w, packed(b.i_proj), b.proj_b, y1, Bg, nB, nC, L, nullptr, nullptr, s.proj, stream);
-      if (rc) return rc;
-    }
-    y1_ready = false;
-    // depthwise pyramid + upsample/add                         :206-216
-    // unfused path: the merged tensor aliases y1 (dead once every level has been produced); fused path:
-    // its own buffer (the otherwise unused level-0 buffer), because pass 2 re-reads y1 with halos
-    float* merged = fused ? fptr(p->off_lv[0]) : y1;
-    const srf_norm in{s.proj, b.proj_g, b.proj_be, b.proj_prelu};
-    if (fused) {
-      rc = step_pyramid(rg, G, y1, merged, &in, b, Bg, nC, L, D, ws + p->off_pyr, s.merged, stream);
-    } else {
-      float* lv[SRF_MAX_DEPTH];
-      for (int k = 0; k < D; ++k) lv[k] = fptr(p->off_lv[k]);
-      rc = srf_pyramid_per_level(y1, &in, lv, merged, b.lv_w, b.lv_b, b.lv_g, b.lv_be, s.level, s.merged, Bg, nC, L, D, stream);
-    }
-    if (rc) return rc;
-    // final_norm + PReLU folded into res_conv, + residual     :218-220
-    srf_norm fn{s.merged, b.fin_g, b.fin_be, b.fin_prelu};
-    if (pair_res && i + 1 < U) {
-      // res_conv of this block + proj_1x1 of the next one (its output into y1 -- dead since this block's pyramid -- and its
-      // statistics into the next block's first slot)
-      const SrfBlock<const float> nb = plan_block(p, P, i + 1);
-      rc = step_pair(rg, merged, packed(b.i_res), b.res_b, nxt, &fn, xin, packed(nb.i_proj), nb.proj_b, y1,
-                     plan_slots(p, stats, i + 1).proj, Bt, nC, nB, nC, L, stream);
-      y1_ready = true;
-    } else {
-      rc = step_conv(rg, G, merged, b.res_w, packed(b.i_res), b.res_b, nxt, Bg, nC, nB, L, &fn, xin, nullptr, stream);
-    }
-    if (rc) return rc;
-    float* t = cur;
-    cur = nxt;
-    nxt = t;
-  }
-
-  return srf_improved_tail(p, P, cur, out, workspace, use_pack, wav_stats, wav, mixture_consistency, rg, stream);
+  // merged: on y1 (dead once every level exists), or -- fused: pass 2 re-reads y1 with halos -- in the unused level-0 buffer
+  SrfImpAddrs a{};
+  a.stats = (double*)(ws + p->off_stats);
+  a.enc = (float*)(ws + p->off_enc);
+  a.x[0] = ws + p->off_xa, a.x[1] = ws + p->off_xb, a.blk = ws;
+  a.o_y1 = p->off_y1, a.o_merged = fused ? p->off_lv[0] : p->off_y1, a.o_q = p->off_xq, a.o_u = p->off_xu;
+  for (int k = 0; k < c.upsampling_depth; ++k) a.o_lv[k] = p->off_lv[k];
+  a.lv_mask = fused ? 0u : ~0u;
+  a.pyr = ws + p->off_pyr;
+  rc = improved_walk(p, P, wav, a, conv, pair, pair_head, pair_res, fused, rg, wav_stats, stream);
+  if (rc) return rc;
+  return srf_improved_tail(p, P, a.x_in(c.num_blocks), out, workspace, use_pack, wav_stats, wav, mixture_consistency, rg, stream);
 }
 
 // ---- mask estimation + decoder of the Improved / GroupComm / attentive (v2, v3) walks      improved_sudormrf.py:295-301
@@ -684,7 +553,7 @@ int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur
     rc = srf_mask_decode(cur, t.mask_w, mask_packed, t.mask_b, t.mask_prelu, enc, N, ws + p->off_wdpack, masked, Bt, c.out_channels,
                          p->SA * N, L, M, st);
     if (rc) return rc;
-    return step_overlap_add(rg, masked, out, Bt, p->SA, K, L, p->T, nparts, wav_stats, wav, mixture_consistency, st);
+    return imp_overlap_add(rg, masked, out, Bt, p->SA, K, L, p->T, nparts, wav_stats, wav, mixture_consistency, st);
   }
   srf_norm pre{nullptr, nullptr, nullptr, t.mask_prelu};
   rc = srf_pw_conv_packed(cur, t.mask_w, mask_packed, t.mask_b, masked, Bt, c.out_channels, p->SA * N, L, &pre, nullptr, nullptr, 1,

@@ -40,8 +40,6 @@ struct CScratchLayout {
   int dec_rows;
 };
 
-size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
-
 CScratchLayout cscratch_layout(const srf_plan* p) {
   CScratchLayout s{};
   const srf_config& c = p->cfg;
@@ -60,13 +58,13 @@ CScratchLayout cscratch_layout(const srf_plan* p) {
   for (int k = 0; k < D; ++k) s.gd[k] = all.take(F * Bt * C * (L >> k));
   s.dec_rows = (p->SA * K + 63) / 64 * 64;
   const size_t enc_rows = (size_t)p->A * K;
-  s.frames = all.take(F * Bt * L * cmax((size_t)s.dec_rows, enc_rows));
-  s.wt = all.take(F * cmax(cmax((size_t)B * N, (size_t)B * C), (size_t)B * SAN));
-  s.zero_floats = cmax(cmax(C, SAN), cmax(N, B));
+  s.frames = all.take(F * Bt * L * std::max((size_t)s.dec_rows, enc_rows));
+  s.wt = all.take(F * std::max({(size_t)B * N, (size_t)B * C, (size_t)B * SAN}));
+  s.zero_floats = std::max({C, SAN, N, B});
   s.zeros = all.take(F * s.zero_floats);
   s.wdpad = all.take(F * (size_t)SAN * s.dec_rows);
   size_t wg = 0;
-  auto wgmax = [&](int cout, int cin) { wg = cmax(wg, srf_pw_wgrad_scratch_bytes(p->Bt, cout, cin, p->L)); };
+  auto wgmax = [&](int cout, int cin) { wg = std::max(wg, srf_pw_wgrad_scratch_bytes(p->Bt, cout, cin, p->L)); };
   wgmax(B, N);
   wgmax(SAN, B);
   wgmax(SAN, s.dec_rows);
@@ -74,8 +72,8 @@ CScratchLayout cscratch_layout(const srf_plan* p) {
   wgmax(C, B);
   wgmax(B, C);
   s.wg = all.take(wg);
-  s.pyr = all.take(cmax(cmax(srf_causal_pyramid_bwd_scratch_bytes(p->Bt, C, p->L, D), srf_causal_dwconv_bwd_scratch_bytes(p->Bt, C, p->L)),
-                    F * srf_causal_prelu_bwd_scratch_floats()));
+  s.pyr = all.take(std::max({srf_causal_pyramid_bwd_scratch_bytes(p->Bt, C, p->L, D), srf_causal_dwconv_bwd_scratch_bytes(p->Bt, C, p->L),
+                              F * srf_causal_prelu_bwd_scratch_floats()}));
   s.fold_res = all.take(F * causal_fold_res_floats(B, C) * U);
   s.fold_proj = all.take(F * (size_t)C * B * U);
   s.encw = all.take(F * (size_t)N * enc_rows);
@@ -124,16 +122,12 @@ int cforward_train_impl(const srf_plan* p, const float* const* P, const float* w
   SrfCausalFolded w;
   int rc = srf_causal_fold(p, P, (float*)(sc + s.fold_res), (float*)(sc + s.fold_proj), &w, st);
   if (rc) return rc;
-  // three-part (or two-fp16-part) images of the 1x1 weights the 256 x 128 GEMM takes, as forward_train_impl packs them
-  const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
+  // the exact-class images of the 1x1 weights the 256 x 128 GEMM takes, as srf_forward_train packs them (SrfPackQueue::add3)
   SrfPackQueue pk{sc + s.pk3};
-  auto pack3 = [&](const float* wt, int cout, int cin) {
-    return pk.add(wt, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin);
-  };
-  const void* pk_bott = pack3(f.bott_w, B, N);
-  const void* pk_mask = pack3(tl.mask_w, SAN, B);
+  const void* pk_bott = pk.add3(f.bott_w, B, N);
+  const void* pk_mask = pk.add3(tl.mask_w, SAN, B);
   std::vector<const void*> pk_proj(U, nullptr);
-  for (int i = 0; i < U; ++i) pk_proj[i] = pack3(w.wproj[i], Cc, B);
+  for (int i = 0; i < U; ++i) pk_proj[i] = pk.add3(w.wproj[i], Cc, B);
   rc = pk.pack3(stream);
   if (rc) return rc;
   float* enc = (float*)(sv + t.enc);
@@ -192,8 +186,7 @@ extern "C" int srf_causal_forward_train(const srf_plan* p, const float* const* P
                                  {saved, saved_bytes, ctrain_layout(p).total, scratch, scratch_bytes, cscratch_layout(p).total});
   if (!rc) rc = ctrain_check(p, "srf_causal_forward_train");
   if (rc) return rc;
-  // the exact-fp32 class for the 1x1 convolutions, under the flags of srf_forward_train (srf_train.hip has the reasons)
-  const bool exact = srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_TRAIN_FWD_SPLIT_BF16);
+  const bool exact = srf_train_fwd_exact();
   const SrfKernelModeScope exact_class(exact, 2);
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
   return cforward_train_impl(p, P, wav, out, saved, scratch, exact, stream);

@@ -87,6 +87,26 @@ struct SrfOrigAddrs {
   float* gx(int i) const { return (float*)(blk + blk_stride * i + o_gx); }
   float* lv(int i, int k) const { return (float*)(blk + blk_stride * i + o_lv[k]); }
 };
+// Where the Improved / GroupComm model's ONE forward walk (srf_improved_walk.h) keeps its tensors.  Block i reads the block stream
+// at x[i & 1] + i * x_stride and writes it at x[(i + 1) & 1] + (i + 1) * x_stride; its own tensors lie at blk + i * blk_stride + the
+// o_* byte offsets.  The inference forward alternates two stream buffers and overwrites one set of block tensors (both strides 0,
+// merged on y1 unless the pyramid runs fused: the plan's workspace); the training forward keeps every block's (x[0] = x[1], `saved`).
+struct SrfImpAddrs {
+  double* stats;
+  float* enc;
+  char *x[2], *blk;
+  size_t x_stride, blk_stride;
+  size_t o_y1, o_merged, o_q, o_u, o_lv[SRF_MAX_DEPTH];   // q, u: GroupComm only
+  unsigned lv_mask;   // bit k: the raw level d_k has a place (none: the fused pyramid writes no levels; all, all but d_0: it does)
+  void* pyr;          // the fused pyramid's scratch
+  float* x_in(int i) const { return (float*)(x[i & 1] + x_stride * i); }
+  float* x_out(int i) const { return x_in(i + 1); }
+  float* y1(int i) const { return (float*)(blk + blk_stride * i + o_y1); }
+  float* merged(int i) const { return (float*)(blk + blk_stride * i + o_merged); }
+  float* q(int i) const { return (float*)(blk + blk_stride * i + o_q); }
+  float* u(int i) const { return (float*)(blk + blk_stride * i + o_u); }
+  float* lv(int i, int k) const { return (lv_mask >> k & 1) ? (float*)(blk + blk_stride * i + o_lv[k]) : nullptr; }
+};
 int srf_original_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                          const float* wav_stats, int mixture_consistency, void* stream, const Ragged* rg = nullptr);
 // srf_bias_rescale_ragged's launch alone, from a table the caller has checked (the walk: srf_original_walk.h)

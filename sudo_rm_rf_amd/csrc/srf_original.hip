@@ -542,7 +542,7 @@ extern "C" int srf_bias_rescale(float* out, const float* bias, const float* stat
   return SRF_OK;
 }
 
-// the launch alone, from a table the caller has checked (the ragged walk's step_bias: the one its overlap-add uses)
+// the launch alone, from a table the caller has checked (the ragged walk's orig_bias: the one its overlap-add uses)
 int srf_bias_rescale_ragged_launch(float* out, const float* bias, const float* stats, const float* wav, int mc, int Bt, int S, int T,
                                       const SrfFrames& lens, void* stream) {
   const dim3 grid((T + 255) / 256, Bt);
@@ -698,7 +698,7 @@ int srf_original_forward(const srf_plan* p, const float* const* P, const float* 
   };
   auto conv = [&](const float* x, const float* w, int param, const float* bias, float* y, int Cin, int Cout, const srf_norm* in_norm,
                   double* out_sums) {
-    return step_conv(rg, x, w, plan_packed(p, ws, use_pack, param), bias, y, p->Bt, Cin, Cout, p->L, in_norm, out_sums, stream);
+    return orig_conv(rg, x, w, plan_packed(p, ws, use_pack, param), bias, y, p->Bt, Cin, Cout, p->L, in_norm, out_sums, stream);
   };
   return orig_walk(p, P, wav, out, a, pack, conv, rg || plan_fused_pyramid_now(p), rg, wav_stats, mixture_consistency, stream);
 }

@@ -480,8 +480,6 @@ extern "C" int srf_relu_gate(float* g, const float* s, long n, void* stream) {
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-size_t omax(size_t a, size_t b) { return a > b ? a : b; }
-
 struct OTrainLayout {
   size_t stats, enc, x0, x_stride, blk0, blk_stride, y1, lv[SRF_MAX_DEPTH], m, g, gx, xr, z, total;
 };
@@ -537,9 +535,9 @@ OScratchLayout oscratch_layout(const srf_plan* p) {
   s.gd = all.take(F * Bt * C * L);
   for (int k = 0; k + 1 < D; ++k) s.gu[k] = all.take(F * Bt * C * (L >> k));
   for (int k = 1; k < D; ++k) s.gn[k] = all.take(F * Bt * C * (L >> k));
-  s.frames = all.take(F * Bt * L * omax((size_t)s.dec_rows, (size_t)K));
-  s.wt = all.take(F * omax(omax((size_t)B * N, (size_t)B * C), (size_t)SN * N));
-  s.zero_floats = omax(omax(C, SN), omax(N, B));
+  s.frames = all.take(F * Bt * L * std::max((size_t)s.dec_rows, (size_t)K));
+  s.wt = all.take(F * std::max({(size_t)B * N, (size_t)B * C, (size_t)SN * N}));
+  s.zero_floats = std::max({C, SN, N, B});
   s.zeros = all.take(F * s.zero_floats);
   s.tz = all.take(F * orig_tz_floats(S, N));
   s.wdec = all.take(F * (size_t)SN * S * K);
@@ -547,7 +545,7 @@ OScratchLayout oscratch_layout(const srf_plan* p) {
   s.dtz = all.take(F * orig_tz_floats(S, N));
   s.dwexp = all.take(F * (size_t)SN * S * K);
   size_t wg = 0;
-  auto wgmax = [&](int cout, int cin) { wg = omax(wg, srf_pw_wgrad_scratch_bytes(p->Bt, cout, cin, s.L4)); };
+  auto wgmax = [&](int cout, int cin) { wg = std::max(wg, srf_pw_wgrad_scratch_bytes(p->Bt, cout, cin, s.L4)); };
   wgmax(SN, s.dec_rows);
   wgmax(SN, N);
   wgmax(N, B);
@@ -561,7 +559,7 @@ OScratchLayout oscratch_layout(const srf_plan* p) {
   s.dwb = all.take(srf_dwconv5_bwd_scratch_bytes(p->Bt, C));
   s.bias = all.take(F * srf_decoder_bias_grad_scratch_floats(S));
   if (s.L4 != p->L) {
-    const size_t rows = omax(omax(omax(C, SN), omax(N, B)), omax((size_t)s.dec_rows, (size_t)K));
+    const size_t rows = std::max({C, SN, N, B, s.dec_rows, K});
     s.padg = all.take(F * Bt * rows * s.L4);
     s.padx = all.take(F * Bt * rows * s.L4);
   }
@@ -616,14 +614,13 @@ extern "C" int srf_original_forward_train(const srf_plan* p, const float* const*
   int rc = srf_train_entry_check("srf_original_forward_train", p, P, nullptr, num_params, 0, {wav, out},
                                  {saved, saved_bytes, otrain_layout(p).total, scratch, scratch_bytes, oscratch_layout(p).total});
   if (rc) return rc;
-  // the exact-fp32 class for the 1x1 convolutions, under the flags of srf_forward_train (srf_train.hip has the reasons) -- and of
+  // the exact-fp32 class for the 1x1 convolutions where srf_train_fwd_exact() says so -- and of
   // its two forms the THREE-bf16-part one (24 mantissa bits), not the two-fp16-part default (22): this model puts three per-channel
   // PReLUs behind GroupNorms into every block, and every pre-activation that the forward's rounding moves across 0 flips a slope in
   // the backward.  Measured at the recipe's channel counts (256 / 512 / N 512, U 2, D 3, 512 frames, 64 examples) against fp64
   // autograd: two parts leave l1.weight 5.8e-3 of its largest entry off (torch's own fp32 autograd: 4.5e-4) and five tensors over
   // the 2e-3 bar; three parts 3.0e-4 and none.
-  const bool exact = srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_TRAIN_FWD_SPLIT_BF16);
-  const SrfKernelModeScope exact_class(exact, 2);
+  const SrfKernelModeScope exact_class(srf_train_fwd_exact(), 2);
   const SrfThreePartsScope three_parts;
   if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
   // (the decoder's frame GEMM stays in the exact class too, unlike srf_forward_train's: its rounding is the output's, and the
@@ -632,12 +629,11 @@ extern "C" int srf_original_forward_train(const srf_plan* p, const float* const*
   // level) and the exact-class images of the 1x1 weights the 256 x 128 GEMM takes, as srf_forward_train packs them
   const OScratchLayout s = oscratch_layout(p);
   const int U = p->cfg.num_blocks, N = p->cfg.enc_num_basis, SN = p->cfg.num_sources * N, B = p->nB, C = p->nC;
-  const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
   std::vector<const void*> image(p->n_params, nullptr);      // parameter index -> its packed image (NULL: none)
   auto pack = [&](const float* tz) {
     SrfPackQueue pk{(char*)scratch + s.pk3};
     auto add = [&](int param, const float* w, int cout, int cin) {
-      image[param] = pk.add(w, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin);
+      image[param] = pk.add3(w, cout, cin);
     };
     add(SRF_PO_L1, P[SRF_PO_L1], B, N);
     add(orig_p_mask(p), tz, SN, N);

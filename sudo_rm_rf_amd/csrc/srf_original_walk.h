@@ -6,33 +6,33 @@
 
 // ---- the steps of the walk, one per kernel family: the uniform entry point, or -- rg != NULL, srf_original_forward_ragged --
 // its ragged twin with the batch's tables.  Every per-launch refusal stays with the entry point.
-static inline int step_encoder(const Ragged* rg, const float* wav, const float* w, const float* bias, float* enc, double* sums, int Bt, int T,
+static inline int orig_encoder(const Ragged* rg, const float* wav, const float* w, const float* bias, float* enc, double* sums, int Bt, int T,
                         int N, int K, int L, const float* wav_stats, void* stream) {
   return rg ? srf_encoder_bias_relu_ragged(wav, w, bias, enc, sums, Bt, T, N, K, L, rg->lengths, rg->frames, wav_stats, stream)
             : srf_encoder_bias_relu(wav, w, bias, enc, sums, Bt, T, N, K, L, wav_stats, stream);
 }
 // ragged: always the 256 x 128 kernel (the gate has made sure every conv of the model has a packed image and a shape it takes)
-static inline int step_conv(const Ragged* rg, const float* x, const float* w, const void* w_packed, const float* bias, float* y, int Bt, int Cin,
+static inline int orig_conv(const Ragged* rg, const float* x, const float* w, const void* w_packed, const float* bias, float* y, int Bt, int Cin,
                      int Cout, int L, const srf_norm* in_norm, double* out_sums, void* stream) {
   return rg ? srf_pw_conv_packed_ragged(x, w, w_packed, bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, 0, nullptr, 0, rg->frames,
                                         stream)
             : srf_pw_conv_packed(x, w, w_packed, bias, y, Bt, Cin, Cout, L, in_norm, nullptr, out_sums, 0, nullptr, 0, stream);
 }
-static inline int step_gln(const Ragged* rg, const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y,
+static inline int orig_gln(const Ragged* rg, const float* x, const srf_norm* norm, const float* slopes, const float* add, float* y,
                     double* out_sums, int Bt, int C, int L, void* stream) {
   return rg ? srf_gln_apply_c_ragged(x, norm, slopes, add, y, out_sums, Bt, C, L, rg->frames, stream)
             : srf_gln_apply_c(x, norm, slopes, add, y, out_sums, Bt, C, L, stream);
 }
 // the fused pyramid over the materialised activation: no norm on load
-static inline int step_pyramid(const Ragged* rg, const float* act, float* merged, const SrfOrigBlock& b, int Bt, int C, int L, int D,
+static inline int orig_pyramid(const Ragged* rg, const float* act, float* merged, const SrfOrigBlock& b, int Bt, int C, int L, int D,
                         void* scratch, double* out_sums, void* stream) {
   return rg ? srf_pyramid_ragged(act, merged, nullptr, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bt, C, L, D, scratch, out_sums, rg->frames, stream)
             : srf_pyramid(act, merged, nullptr, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bt, C, L, D, scratch, out_sums, stream);
 }
-static inline int step_softmax(const Ragged* rg, const float* z, const float* enc, float* v, int Bt, int S, int N, int L, void* stream) {
+static inline int orig_softmax(const Ragged* rg, const float* z, const float* enc, float* v, int Bt, int S, int N, int L, void* stream) {
   return rg ? srf_softmax_mask_ragged(z, enc, v, Bt, S, N, L, rg->frames, stream) : srf_softmax_mask(z, enc, v, Bt, S, N, L, stream);
 }
-static inline int step_bias(const Ragged* rg, float* out, const float* bias, const float* wav_stats, const float* wav, int mc, int Bt, int S,
+static inline int orig_bias(const Ragged* rg, float* out, const float* bias, const float* wav_stats, const float* wav, int mc, int Bt, int S,
                      int T, void* stream) {
   return rg ? srf_bias_rescale_ragged_launch(out, bias, wav_stats, wav, mc, Bt, S, T, rg->lens_t, stream)
             : srf_bias_rescale(out, bias, wav_stats, wav, mc, Bt, S, T, stream);
@@ -76,7 +76,7 @@ static inline int orig_walk(const srf_plan* p, const float* const* P, const floa
   if (rc) return rc;
 
   // ---- front end: encoder with bias and ReLU (+ ln statistics), ln folded into l1's operand load
-  rc = step_encoder(rg, wav, f.enc_w, f.enc_b, a.enc, a.stats, Bt, p->T, N, K, L, wav_stats, stream);
+  rc = orig_encoder(rg, wav, f.enc_w, f.enc_b, a.enc, a.stats, Bt, p->T, N, K, L, wav_stats, stream);
   if (rc) return rc;
   {
     const srf_norm ln{a.stats, f.ln_g, f.ln_b, nullptr};
@@ -92,13 +92,13 @@ static inline int orig_walk(const srf_plan* p, const float* const* P, const floa
     rc = conv(x, b.proj_w, b.i_proj, b.proj_b, y1, B, C, nullptr, s.proj);
     if (rc) return rc;
     const srf_norm pn{s.proj, b.proj_g, b.proj_be, nullptr};
-    rc = step_gln(rg, y1, &pn, b.proj_slope, nullptr, a.act, nullptr, Bt, C, L, stream);
+    rc = orig_gln(rg, y1, &pn, b.proj_slope, nullptr, a.act, nullptr, Bt, C, L, stream);
     if (rc) return rc;
     // the pyramid, its result m (the inference forward: into y1, dead since a exists) with the statistics of final_norm: the
     // fused kernels where they take the shape, else level by level + merge (D = 1: the normalised level 0).  Either way level 0
     // reads the materialised activation as it is, no norm on load
     if (fused) {
-      rc = step_pyramid(rg, a.act, m, b, Bt, C, L, D, a.pyr, s.merged, stream);
+      rc = orig_pyramid(rg, a.act, m, b, Bt, C, L, D, a.pyr, s.merged, stream);
     } else {
       float* lv[SRF_MAX_DEPTH];
       for (int k = 0; k < D; ++k) lv[k] = a.lv(i, k);
@@ -107,16 +107,16 @@ static inline int orig_walk(const srf_plan* p, const float* const* P, const floa
     if (rc) return rc;
     // final_norm + PReLU_c (into a's buffer)
     const srf_norm fn{s.merged, b.fin_g, b.fin_be, nullptr};
-    rc = step_gln(rg, m, &fn, b.fin_slope, nullptr, a.act, nullptr, Bt, C, L, stream);
+    rc = orig_gln(rg, m, &fn, b.fin_slope, nullptr, a.act, nullptr, Bt, C, L, stream);
     if (rc) return rc;
     rc = conv(a.act, b.exp_w, b.i_exp, b.exp_b, g, C, B, nullptr, s.exp);
     if (rc) return rc;
     // the residual goes in BEFORE module_act's norm
     const srf_norm en{s.exp, b.exp_g, b.exp_be, nullptr};
-    rc = step_gln(rg, g, &en, nullptr, x, gx, s.act, Bt, B, L, stream);
+    rc = orig_gln(rg, g, &en, nullptr, x, gx, s.act, Bt, B, L, stream);
     if (rc) return rc;
     const srf_norm an{s.act, b.act_g, b.act_be, nullptr};
-    rc = step_gln(rg, gx, &an, b.act_slope, nullptr, a.x_out(i), nullptr, Bt, B, L, stream);
+    rc = orig_gln(rg, gx, &an, b.act_slope, nullptr, a.x_out(i), nullptr, Bt, B, L, stream);
     if (rc) return rc;
   }
 
@@ -129,11 +129,11 @@ static inline int orig_walk(const srf_plan* p, const float* const* P, const floa
   }
   rc = conv(xm, a.tz, t.i_m, a.tz + orig_tz_bias_at(S, N), a.z, N, S * N, nullptr, nullptr);
   if (rc) return rc;
-  rc = step_softmax(rg, a.z, a.enc, a.masked, Bt, S, N, L, stream);
+  rc = orig_softmax(rg, a.z, a.enc, a.masked, Bt, S, N, L, stream);
   if (rc) return rc;
   // ---- decoder: the frame GEMM + overlap-add over the block-diagonal weight, then the bias (+ the callers' recipe)
   rc = srf_decoder_impl(a.masked, a.wdec, out, Bt, S * N, S, K, L, p->T, a.dec, nullptr, nullptr, 0, stream, nullptr,
                         rg ? &rg->lens_t : nullptr, rg ? &rg->frames_t : nullptr);
   if (rc) return rc;
-  return step_bias(rg, out, t.dec_b, wav_stats, wav, mixture_consistency, Bt, S, p->T, stream);
+  return orig_bias(rg, out, t.dec_b, wav_stats, wav, mixture_consistency, Bt, S, p->T, stream);
 }

@@ -1,5 +1,6 @@
 // The plan object behind the opaque srf_plan* of include/sudormrf_hip.h (shared by srf_api.hip and srf_train.hip).
 #pragma once
+#include <algorithm>
 #include <vector>
 #include "srf_internal.h"
 
@@ -326,6 +327,13 @@ struct SrfPackQueue {
     w.push_back(weight), d.push_back(dst), cout.push_back(co), cin.push_back(ci);
     return dst;
   }
+  // An image for a training forward: its exact-class 1x1 convolutions (kernel mode 2) run on the THREE-part split GEMM (six bf16
+  // MFMAs per product block, 24-bit operands: srf_pwconv_x3w.hip NP 3) where the 256 x 128 kernel takes the launch, on weights
+  // split and laid out once per step.  Debug flag 1 << 31: no image, the exact-fp32 MFMA kernel instead (A/B).
+  const void* add3(const float* weight, int co, int ci) {
+    const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
+    return add(weight, three ? srf_packed3_pw_weight_bytes(co, ci) : 0, co, ci);
+  }
   // the exact-class images of the training forward / the images of the TRANSPOSED weights of a backward's data-gradient GEMMs
   int pack3(void* stream) const {
     return w.empty() ? SRF_OK : srf_pack3_pw_weights(w.data(), d.data(), cout.data(), cin.data(), (int)w.size(), stream);
@@ -334,6 +342,16 @@ struct SrfPackQueue {
     return w.empty() ? SRF_OK : srf_pack_pw_weights_transposed(w.data(), d.data(), cout.data(), cin.data(), (int)w.size(), st);
   }
 };
+
+// A training forward runs its 1x1 convolutions in the EXACT-fp32 CLASS (kernel mode 2: since round 3 the three-part split
+// GEMM where the 256 x 128 kernel takes the launch, else the exact fp32 MFMA kernel) unless debug flag 1<<28 is set.
+// The split-bf16 GEMMs are accurate to ~2^-17 of sum|terms| per output -- far inside the 1e-4 forward bar -- but
+// the gradients of the first blocks' parameters are ill-conditioned with respect to exactly that rounding:
+// injecting 2^-17 noise into the bottleneck GEMM's output alone moves d loss / d sm.0.proj_1x1.conv.weight by 5 %
+// in an fp64 autograd experiment (2^-24 noise: 3e-6), and the HIP step reproduces both numbers against the
+// reference's own gradients (tests/golden/train_*).  The backward GEMMs (data / weight gradients) stay split-bf16:
+// with an exact forward every parameter gradient is within 2e-5 of the reference's.  (Ask before SrfKernelModeScope sets mode 2.)
+static inline bool srf_train_fwd_exact() { return srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_TRAIN_FWD_SPLIT_BF16); }
 
 // ---- what every training entry point refuses before its first launch (srf_train.hip), in this order: a null pointer (the
 // plan, P, any of `others`: G, wav, out, grad_out), a wrong num_params, a null P[i], a null G[i] (G = NULL: a forward, no

@@ -3,12 +3,11 @@
 // per-kernel entry points of this library.  The reference gets the same result from torch autograd over ~1.8 k
 // ATen nodes (run_improved_sudormrf.py:167-172: rec = model(x); l = clamp(loss(rec, clean)); l.backward()).
 //
-//   srf_forward_train : encoder -> bottleneck -> U x [proj, D depthwise levels, merge, res_conv] -> mask GEMM ->
-//                       mask -> decoder, every GlobLN still folded into its neighbours, but un-fused where the
-//                       backward needs an intermediate (pyramid levels, mask pre-activation).  `saved` holds:
-//                       GlobLN statistics, encoder output, the residual stream x_0..x_U, and per block the
-//                       projection output y1, the D pre-norm levels and the merged tensor; the mask
-//                       pre-activation m and the masked encoding v.
+//   srf_forward_train : the inference forward's walk (improved_walk, srf_improved_walk.h: encoder -> bottleneck -> U x [proj,
+//                       pyramid, res_conv], every GlobLN folded into its neighbours) over `saved`, which keeps what the
+//                       backward reads: GlobLN statistics, encoder output, the residual stream x_0..x_U, per block y1, the
+//                       D pre-norm levels (written on the side by the fused pyramid, or per level) and the merged tensor;
+//                       then its own tail: the mask pre-activation m, the masked encoding v, the decoder.
 //   srf_backward      : walks the graph in reverse; parameter gradients are ACCUMULATED into `grads` (same
 //                       order / shapes as the parameters; the caller zeroes them, like optimizer.zero_grad()).
 //                       In stages over one BwdWalk: tail (decoder, mask, mask_net), U x block (res_conv, the pyramid,
@@ -23,7 +22,7 @@
 #include <memory>
 #include <mutex>
 
-#include "srf_plan.h"
+#include "srf_improved_walk.h"
 
 // Round 6: levels 1 and 0 of a block's pyramid backward and proj_1x1's norm backward run on the fused-head kernels
 // (srf_backward.hip: srf_bwd_l1h_kernel, srf_bwd_l0p_kernel), which re-compute d_0 from y1 -- so srf_forward_train does not WRITE
@@ -115,8 +114,6 @@ struct ScratchLayout {
   int dec_rows;
 };
 
-static size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
-
 static ScratchLayout scratch_layout(const srf_plan* p) {
   ScratchLayout s;
   const srf_config& c = p->cfg;
@@ -139,8 +136,8 @@ static ScratchLayout scratch_layout(const srf_plan* p) {
   s.dec_rows = (p->SA * K + 63) / 64 * 64;
   const size_t enc_rows = (size_t)p->A * K;
   s.frames = all.take(F * Bt * L * (s.dec_rows > (int)enc_rows ? s.dec_rows : enc_rows));
-  s.wt = all.take(F * max3((size_t)B * N, (size_t)B * C, (size_t)B * SAN));
-  s.zeros = all.take(F * max3(C, SAN, N));
+  s.wt = all.take(F * std::max({(size_t)B * N, (size_t)B * C, (size_t)B * SAN}));
+  s.zeros = all.take(F * std::max({C, SAN, N}));
   s.wdpad = all.take(F * (size_t)SAN * s.dec_rows);
   size_t wg = 0;
   auto wgmax = [&](int cout, int cin) {
@@ -157,8 +154,8 @@ static ScratchLayout scratch_layout(const srf_plan* p) {
     if (b2 > wg) wg = b2;
   }
   s.wg = all.take(wg);
-  s.gln = all.take(max3(srf_gln_bwd_scratch_bytes(p->Bg, p->nC), srf_gln_bwd_scratch_bytes(p->Bt, N),
-                    srf_gln_bwd_scratch_bytes(p->Bg, p->nB)));
+  s.gln = all.take(std::max({srf_gln_bwd_scratch_bytes(p->Bg, p->nC), srf_gln_bwd_scratch_bytes(p->Bt, N),
+                              srf_gln_bwd_scratch_bytes(p->Bg, p->nB)}));
   s.gln2 = all.take(srf_gln_bwd_scratch_bytes(p->Bg, p->nC));   // the pyramid's norms alternate between gln and gln2
   s.dw = all.take(srf_dwconv5_bwd_scratch_bytes(p->Bg, p->nC));
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
@@ -255,33 +252,8 @@ int srf_train_entry_check(const char* who, const srf_plan* p, const float* const
   return SRF_OK;
 }
 
-static int forward_train_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
-                              void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, bool split_tail, bool* skip_d0_out,
-                              void* stream);
-
-// The training forward runs its 1x1 convolutions in the EXACT-fp32 CLASS (kernel mode 2: since round 3 the three-part split
-// GEMM where the 256 x 128 kernel takes the launch, else the exact fp32 MFMA kernel) unless debug flag 1<<28 is set.
-// The split-bf16 GEMMs are accurate to ~2^-17 of sum|terms| per output -- far inside the 1e-4 forward bar -- but
-// the gradients of the first blocks' parameters are ill-conditioned with respect to exactly that rounding:
-// injecting 2^-17 noise into the bottleneck GEMM's output alone moves d loss / d sm.0.proj_1x1.conv.weight by 5 %
-// in an fp64 autograd experiment (2^-24 noise: 3e-6), and the HIP step reproduces both numbers against the
-// reference's own gradients (tests/golden/train_*).  The backward GEMMs (data / weight gradients) stay
-// split-bf16: with an exact forward every parameter gradient is within 2e-5 of the reference's.
-extern "C" int srf_forward_train(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
-                                 void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-  if (other_family_refused(p, "srf_forward_train")) return SRF_EINVAL;
-  const int mode = srf_kernel_mode(), flags = srf_debug_flags();
-  const bool exact = mode == 0 && !(flags & SRF_DBG_TRAIN_FWD_SPLIT_BF16);
-  bool skip_d0 = false;
-  int rc;
-  {
-    const SrfKernelModeScope exact_class(exact, 2);
-    rc = forward_train_impl(p, P, num_params, wav, out, saved, saved_bytes, scratch, scratch_bytes, exact, &skip_d0, stream);
-  }
-  if (saved) train_rec_put(saved, saved_bytes, rc == SRF_OK, skip_d0, mode, flags);
-  return rc;
-}
-
+// The training forward's walk and tail.  split_tail: the exact class was srf_forward_train's own choice;  *skip_d0_out: d_0 was
+// left out (srf_forward_train records it for the backward).
 static int forward_train_impl(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
                               void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, bool split_tail, bool* skip_d0_out,
                               void* stream) {
@@ -294,134 +266,91 @@ static int forward_train_impl(const srf_plan* p, const float* const* P, int num_
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
   const int Bt = p->Bt, L = p->L, B = c.out_channels;
-  char* sv = (char*)saved;
-  char* sc = (char*)scratch;
-  hipStream_t st = (hipStream_t)stream;
-  double* stats = (double*)(sv + t.stats);      // (the slot of ln is the first)
-  auto xbuf = [&](int i) { return (float*)(sv + t.x0 + t.x_stride * i); };
-  SRF_CHECK_HIP(hipMemsetAsync(stats, 0, p->stats_bytes, st));
-
+  char *sv = (char*)saved, *sc = (char*)scratch;
+  double* stats = (double*)(sv + t.stats);
+  SRF_CHECK_HIP(hipMemsetAsync(stats, 0, p->stats_bytes, (hipStream_t)stream));
   const bool gc = c.variant == SRF_VARIANT_GROUPCOMM;
-  const int G = gc ? c.group_size : 1, Bg = p->Bg, nB = p->nB, nC = p->nC;
-  // The 1x1 convolutions of the exact forward (kernel mode 2) run on the THREE-part split GEMM (six bf16 MFMAs per product
-  // block, 24-bit operands: srf_pwconv_x3w.hip NP 3) where the 256 x 128 kernel takes the launch; their weights are split and
-  // laid out once per step, here.  Debug flag 1 << 31: the exact-fp32 MFMA kernel instead (A/B).
-  const bool three = srf_kernel_mode() == 2 && !srf_dbg(SRF_DBG_TRAIN_FWD_EXACT_MFMA);
+  const int Bg = p->Bg, nB = p->nB, nC = p->nC;
+  // the exact-class images of the 1x1 weights (SrfPackQueue::add3), split and laid out once per step, here
   SrfPackQueue pk{sc + s.pk3};
-  auto pack3 = [&](const float* w, int cout, int cin) {
-    return pk.add(w, three ? srf_packed3_pw_weight_bytes(cout, cin) : 0, cout, cin);
-  };
-  const SrfFront<const float> f = plan_front(P);
+  std::vector<const void*> image(p->n_params, nullptr);      // parameter index -> its packed image (NULL: none)
   const SrfTail<const float> tl = plan_tail(p, P);
-  const void* pk_bottleneck = pack3(f.bott_w, B, N);
-  std::vector<const void*> pk_proj(U, nullptr), pk_res(U, nullptr);
+  const int i_mask = plan_p_mask(p), i_proj = plan_p_proj(p, 0), i_res = plan_p_res(p, 0);
+  image[SRF_P_BOTTLENECK] = pk.add3(P[SRF_P_BOTTLENECK], B, N);
   for (int i = 0; i < U; ++i) {
-    const SrfBlock<const float> b = plan_block(p, P, i);
-    pk_proj[i] = pack3(b.proj_w, nC, nB);
-    pk_res[i] = pack3(b.res_w, nB, nC);
+    image[plan_p_proj(p, i)] = pk.add3(P[plan_p_proj(p, i)], nC, nB);
+    image[plan_p_res(p, i)] = pk.add3(P[plan_p_res(p, i)], nB, nC);
   }
-  const void* pk_mask = pack3(tl.mask_w, p->SA * N, B);
+  image[i_mask] = pk.add3(tl.mask_w, p->SA * N, B);
   rc = pk.pack3(stream);
   if (rc) return rc;
-
-  float* enc = (float*)(sv + t.enc);
-  rc = srf_encoder(wav, f.enc_w, enc, stats, Bt, p->A, p->T, N, K, L, stream);
-  if (rc) return rc;
+  auto conv = [&](int, const float* x, const float* w, int param, const float* bias, float* y, int rows, int Cin, int Cout,
+                  const srf_norm* in_norm, const float* residual, double* out_sums) {
+    return srf_pw_conv_packed3(x, w, image[param], bias, y, rows, Cin, Cout, L, in_norm, residual, out_sums, stream);
+  };
+  auto pair = [&](const float* x, int param1, const float* bias1, float* y, const srf_norm* in_norm, const float* residual, int param2,
+                  const float* bias2, float* y2, double* out_sums2, int Cin1, int Cmid, int Cout2) {
+    return srf_pw_conv_pair_packed3(x, image[param1], bias1, y, in_norm, residual, image[param2], bias2, y2, out_sums2, Bt, Cin1, Cmid,
+                                    Cout2, L, stream);
+  };
   // Round 5: like srf_forward, the B = 256 Improved models run bottleneck + proj_1x1(0) and res_conv(i) + proj_1x1(i + 1) as ONE
-  // launch each (srf_pwconv_x3f.hip on the two-fp16-part images: both outputs bit-identical to the two launches; both are saved
-  // activations anyway -- the residual stream and the block's y1).  Debug flag 1 = without.
-  bool y1_ready = false;          // block i's y1 (and its statistics) came out of the pair that ended block i - 1
-  auto y1_of = [&](int i) { return (float*)(sv + t.blk0 + t.blk_stride * i + t.y1); };
-  {
-    srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
-    if (!gc && pk_bottleneck && pk_proj[0] && srf_pw_conv_pair_packed3_supported(Bt, N, B, nC, (int)L)) {
-      rc = srf_pw_conv_pair_packed3(enc, pk_bottleneck, f.bott_b, xbuf(0), &ln, nullptr, pk_proj[0], plan_block(p, P, 0).proj_b, y1_of(0),
-                                    plan_slots(p, stats, 0).proj, Bt, N, B, nC, (int)L, stream);
-      y1_ready = true;
-    } else {
-      rc = srf_pw_conv_packed3(enc, f.bott_w, pk_bottleneck, f.bott_b, xbuf(0), Bt, N, B, L, &ln, nullptr, nullptr, stream);
-    }
-    if (rc) return rc;
-  }
+  // launch each (srf_pwconv_x3f.hip on the two-fp16-part images: outputs bit-identical to the two launches), each where its own two
+  // images and its shape allow (every block's images have one shape: block 0's stand for all).  Debug flag 1 = without.
+  const bool pair_head = !gc && image[SRF_P_BOTTLENECK] && image[i_proj] && srf_pw_conv_pair_packed3_supported(Bt, N, B, nC, L);
+  const bool pair_block = !gc && image[i_res] && image[i_proj] && srf_pw_conv_pair_packed3_supported(Bg, nC, nB, nC, L);
   // fused pyramid with level outputs (register-resident kernels only); its scratch lives in the backward's gradient
   // buffers gf | go | gd, idle during the forward.  SRF_DBG_PYR_PER_LEVEL (as in srf_forward) selects the per-level kernels.
   // Not plan_fused_pyramid_now(p): p->fused_pyramid was decided under the flags of the plan's creation and also admits the
   // LDS kernels; this test needs the register kernels, under the flags of this call.
-  const size_t F_ = sizeof(float);
   const bool fused_pyr = !srf_dbg(SRF_DBG_PYR_PER_LEVEL | SRF_DBG_PYR_NO_REG | SRF_DBG_PYR_PASS1_NONPERSISTENT) && srf_kernel_mode() != 1 &&
-                         srf_pyramid_supported(nC, (int)L, D) && srf_pyramid_reg_supported((int)L, D) &&
-                         srf_pyramid_scratch_bytes(Bg, nC, (int)L, D) <= (s.gd + F_ * Bt * c.in_channels * L) - s.gf;
+                         srf_pyramid_supported(nC, L, D) && srf_pyramid_reg_supported(L, D) &&
+                         srf_pyramid_scratch_bytes(Bg, nC, L, D) <= (s.gd + sizeof(float) * Bt * c.in_channels * L) - s.gf;
   const bool skip_d0 = fused_pyr && train_fused_head(p);     // (the backward re-computes d_0: nothing reads it)
-  *skip_d0_out = skip_d0;                                     // (srf_forward_train records it for the backward)
-  for (int i = 0; i < U; ++i) {
-    const SrfBlock<const float> b = plan_block(p, P, i);
-    const SrfSlots sl = plan_slots(p, stats, i);
-    char* blk = sv + t.blk0 + t.blk_stride * i;
-    float* y1 = (float*)(blk + t.y1);
-    float* merged = (float*)(blk + t.merged);
-    const float* xin = xbuf(i);
-    bool tac_norm_fused = false;
-    if (gc) {
-      // TAC: q = MLPs(x), u = x + GlobLN_(b,g)(q)                 groupcomm_sudormrf_v2.py:356-384
-      float* q = (float*)(blk + t.q);
-      float* u = (float*)(blk + t.u);
-      rc = srf_tac(xin, q, b.tac, Bt, G, nB, 3 * nB, L, sl.tac, stream);
-      if (rc) return rc;
-      srf_norm tn{sl.tac, b.tac_g, b.tac_b, nullptr};
-      // u = x + GlobLN(q) folded into the proj conv's operand load where the thin-shape kernel runs it (as in srf_forward;
-      // bitwise the separate kernels' results, u is still written: the backward reads it)
-      const void* al[4] = {xin, q, u, y1};
-      tac_norm_fused = srf_pw_conv_preadd_supported(nB, nC, L, al, 4);
-      if (tac_norm_fused)
-        rc = srf_pw_conv_preadd(xin, q, &tn, u, b.proj_w, b.proj_b, y1, Bg, nB, nC, L, sl.proj, st);
-      else
-        rc = srf_gln_apply_add(xin, q, u, &tn, Bg, nB, L, stream);
-      if (rc) return rc;
-      xin = u;
-    }
-    if (!tac_norm_fused && !y1_ready) {
-      rc = srf_pw_conv_packed3(xin, b.proj_w, pk_proj[i], b.proj_b, y1, Bg, nB, nC, L, nullptr, nullptr, sl.proj, stream);
-      if (rc) return rc;
-    }
-    y1_ready = false;
-    // The pyramid: the two fused passes of the inference path with the per-level conv outputs d_k and their
-    // statistics written on the side (what the backward reads) when the register-resident kernels cover the shape;
-    // otherwise D depthwise kernels + the merge kernel.
-    float* lv[SRF_MAX_DEPTH];
-    for (int k = 0; k < D; ++k) lv[k] = (float*)(blk + t.lv[k]);
-    const srf_norm in{sl.proj, b.proj_g, b.proj_be, b.proj_prelu};
-    if (fused_pyr) {
-      if (skip_d0) lv[0] = nullptr;
-      rc = srf_pyramid_impl(y1, merged, &in, b.lv_w, b.lv_b, b.lv_g, b.lv_be, Bg, nC, L, D, sc + s.gf, sl.merged, lv, sl.level, stream);
-    } else {
-      rc = srf_pyramid_per_level(y1, &in, lv, merged, b.lv_w, b.lv_b, b.lv_g, b.lv_be, sl.level, sl.merged, Bg, nC, L, D, stream);
-    }
-    if (rc) return rc;
-    srf_norm fn{sl.merged, b.fin_g, b.fin_be, b.fin_prelu};
-    if (i + 1 < U && !gc && pk_res[i] && pk_proj[i + 1] && srf_pw_conv_pair_packed3_supported(Bg, nC, nB, nC, (int)L)) {
-      rc = srf_pw_conv_pair_packed3(merged, pk_res[i], b.res_b, xbuf(i + 1), &fn, xin, pk_proj[i + 1], plan_block(p, P, i + 1).proj_b,
-                                    y1_of(i + 1), plan_slots(p, stats, i + 1).proj, Bg, nC, nB, nC, (int)L, stream);
-      y1_ready = true;
-    } else {
-      rc = srf_pw_conv_packed3(merged, b.res_w, pk_res[i], b.res_b, xbuf(i + 1), Bg, nC, nB, L, &fn, xin, nullptr, stream);
-    }
-    if (rc) return rc;
-  }
+  *skip_d0_out = skip_d0;
+  SrfImpAddrs a{};
+  a.stats = stats;
+  a.enc = (float*)(sv + t.enc);
+  a.x[0] = a.x[1] = sv + t.x0, a.x_stride = t.x_stride;
+  a.blk = sv + t.blk0, a.blk_stride = t.blk_stride;
+  a.o_y1 = t.y1, a.o_merged = t.merged, a.o_q = t.q, a.o_u = t.u;
+  for (int k = 0; k < D; ++k) a.o_lv[k] = t.lv[k];
+  a.lv_mask = skip_d0 ? ~1u : ~0u;
+  a.pyr = sc + s.gf;
+  rc = improved_walk(p, P, wav, a, conv, pair, pair_head, pair_block, fused_pyr, nullptr, nullptr, stream);
+  if (rc) return rc;
+
   float* m = (float*)(sv + t.m);
   float* v = (float*)(sv + t.v);
   {
     srf_norm pre{nullptr, nullptr, nullptr, tl.mask_prelu};
-    rc = srf_pw_conv_packed3(xbuf(U), tl.mask_w, pk_mask, tl.mask_b, m, Bt, B, p->SA * N, L, &pre, nullptr, nullptr, stream);
+    rc = srf_pw_conv_packed3(a.x_in(U), tl.mask_w, image[i_mask], tl.mask_b, m, Bt, B, p->SA * N, L, &pre, nullptr, nullptr, stream);
     if (rc) return rc;
   }
-  rc = srf_mask_apply(m, enc, v, Bt, p->SA, N, L, stream);
+  rc = srf_mask_apply(m, a.enc, v, Bt, p->SA, N, L, stream);
   if (rc) return rc;
   // The decoder's frame GEMM (S N -> S K rows) is the LAST linear map of the forward: nothing downstream amplifies the 2^-17
-  // rounding of the split-bf16 GEMM (the loss is smooth in the estimates), unlike the early layers' (see above) -- so when the
-  // exact class was this function's own choice it runs on the split kernel (round 6: 292 -> 130 us at cfg 2, 4 x that at N = 2048)
+  // rounding of the split-bf16 GEMM (the loss is smooth in the estimates), unlike the early layers' (srf_train_fwd_exact) -- so when
+  // the exact class was this function's own choice it runs on the split kernel (round 6: 292 -> 130 us at cfg 2, 4 x that at N = 2048)
   // instead of the exact-fp32 MFMA kernel the thin output (42 rows) would otherwise fall to.
   const SrfKernelModeScope split_class(split_tail, 0);
   return srf_decoder(v, tl.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, (float*)(sc + s.dec), stream);
+}
+
+// The 1x1 convolutions run in the exact-fp32 class where srf_train_fwd_exact() says so (srf_plan.h has the reasons).  What the
+// forward did to `saved` is recorded for the backward, under the kernel mode and the debug flags of the call.
+extern "C" int srf_forward_train(const srf_plan* p, const float* const* P, int num_params, const float* wav, float* out,
+                                 void* saved, size_t saved_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (other_family_refused(p, "srf_forward_train")) return SRF_EINVAL;
+  const int mode = srf_kernel_mode(), flags = srf_debug_flags();
+  const bool exact = srf_train_fwd_exact();
+  bool skip_d0 = false;
+  int rc;
+  {
+    const SrfKernelModeScope exact_class(exact, 2);
+    rc = forward_train_impl(p, P, num_params, wav, out, saved, saved_bytes, scratch, scratch_bytes, exact, &skip_d0, stream);
+  }
+  if (saved) train_rec_put(saved, saved_bytes, rc == SRF_OK, skip_d0, mode, flags);
+  return rc;
 }
 
 // ---- srf_backward: the graph in reverse, in stages over one walk state (as the forwards of srf_api.hip) ----------------------
@@ -750,7 +679,7 @@ static int backward_impl(const srf_plan* p, const float* const* P, float* const*
   if (!rc) rc = train_check(p, who);
   if (!rc) rc = pyr_bwd_path(p, saved, scratch, who, &w.path);
   if (rc) return rc;
-  SRF_CHECK_HIP(hipMemsetAsync(w.fp(w.s.zeros), 0, sizeof(float) * max3(p->cfg.in_channels, w.SAN, w.N), w.st));
+  SRF_CHECK_HIP(hipMemsetAsync(w.fp(w.s.zeros), 0, sizeof(float) * std::max({p->cfg.in_channels, w.SAN, w.N}), w.st));
   // the blocks' norm / conv backwards get one scratch slice per call (statistic buckets zeroed here, once)
   // (the WHOLE arena, 75 MB at cfg 2 / 170 MB at cfg 4 = 0.1 % of a step, not just the fp64 buckets at the head of each norm slice
   // -- the chunked fallback kernels (debug flags 1<<29 / 1<<30, rows beyond the row kernels' limits) accumulate

@@ -28,7 +28,14 @@ The original model's inference, separate and ragged walks ("original ..." below,
 batch and T (orig_tiny, orig_same, orig_d1, orig_s3_k9: the pyramid level by level), orig_default_u2 (the one uniform shape of
 these that runs the fused pyramid), orig_tiny again under PYR_PER_LEVEL, under kernel mode 1 and through
 pipeline.separate with mixture consistency, and rg_c -- the smallest configuration the ragged gate takes -- through forward_ragged
-and separate_ragged.  Recorded on commit 30e11c2, the commit BEFORE the inference walk and the training forward became one walk."""
+and separate_ragged.  Recorded on commit 30e11c2, the commit BEFORE the inference walk and the training forward became one walk.
+
+The branches of the Improved / GroupComm walk that the lists above leave out ("IMPROVED_WALK_TRACES" below): a training step whose
+forward runs the fp16 pairs (improved_pairs: out_channels = in_channels = 256 and 8 x 32 tiles of 128 frames, one per CU), improved_d5's step under
+PYR_PER_LEVEL, TRAIN_FWD_SPLIT_BF16 and TRAIN_FWD_EXACT_MFMA, the GroupComm forward and step under kernel mode 1 (no pre-add: u = x +
+GlobLN(q) as a kernel of its own), and the ragged forwards of cfg 2 and cfg 3 and separate_ragged of cfg 2 in order (the shapes of
+test_gpu_ragged.py, test_gpu_ragged_groupcomm.py, test_gpu_separate_ragged.py).  Recorded on commit 2377517, the commit BEFORE the
+inference walk and the training forward of these two models became one walk."""
 import numpy as np
 import pytest
 import torch
@@ -118,6 +125,7 @@ TRAIN_SHAPES = {      # name: (configuration, batch, T)
     "improved_d2_l36": (ModelConfig("improved", 8, 16, 1, 2, 11, 8, 3), 3, 180),    # L = 36: nine float4 per row, L % 8 == 4
     "improved_d1": (ModelConfig("improved", 16, 24, 2, 1, 21, 32, 2), 2, 1000),     # no head, no pyramid loop beyond level 0
     "groupcomm_d4": (ModelConfig("groupcomm", 64, 128, 2, 4, 21, 64, 2, 1, 4), 2, 4000),   # TAC; the non-deferred srf_gln_bwd
+    "improved_pairs": (ModelConfig("improved", 256, 256, 2, 2, 21, 128, 2), 8, 40000),     # 4000 frames: the forward's fp16 pairs
 }
 TRAIN_STEPS = [("improved_d5", "0"), ("improved_d5", "BWD_NO_FUSED_HEAD"), ("improved_d5", "BWD_DW_CHUNKED"),
                ("improved_d5", "BWD_GLN_SCALAR"), ("improved_d5", "kernel_mode_1"), ("improved_d2", "0"), ("improved_d2_l36", "0"),
@@ -126,16 +134,16 @@ TRAIN_STEPS = [("improved_d5", "0"), ("improved_d5", "BWD_NO_FUSED_HEAD"), ("imp
 
 def train_step_trace(shape, setting):
     """launch names, in order, of one training step (forward + backward) of TRAIN_SHAPES[shape] under a debug flag, or under
-    kernel mode 1 (forward and backward both)"""
+    kernel mode 1 (forward and backward both): _setting"""
     from sudo_rm_rf_amd import ops
     cfg, batch, T_ = TRAIN_SHAPES[shape]
     if shape == "improved_d2_l36":
         assert cfg.frames(T_) == 36
     model = build(cfg, weights.make_state_dict(cfg, seed=31)).train()
     x = torch.from_numpy(weights.make_mixture(batch, T_, 9120).astype(np.float32)).to(DEV)
-    flags = int(getattr(ops.DebugFlag, setting)) if setting.startswith("BWD_") else 0
+    flags, mode = _setting(setting)
     try:
-        ops.set_kernel_mode(1 if setting == "kernel_mode_1" else 0)
+        ops.set_kernel_mode(mode)
         with ops.debug_flags(flags), ops.kernel_trace(DEV) as tr:
             rec = model(x)
             (rec * rec).mean().backward()
@@ -316,6 +324,32 @@ ORIGINAL_TRACES = {
     "original separate orig_tiny mixture_consistency": lambda: original_separate_trace("orig_tiny"),
     "original forward_ragged rg_c": lambda: original_ragged_trace("rg_c", "forward_ragged"),
     "original separate_ragged rg_c": lambda: original_ragged_trace("rg_c", "separate_ragged"),
+}
+
+
+def ragged_trace(manifest, case, entry, **kw):
+    """forward_ragged / separate_ragged of a golden case's model over BATCH rows of test_gpu_ragged.ragged_lengths"""
+    from sudo_rm_rf_amd import ops
+    from test_gpu_ragged import ragged_lengths
+    cfg, sd, _, _ = load_case(manifest, case)
+    model = build(cfg, sd)
+    model._engine().multi_stream = False
+    x = torch.from_numpy(weights.make_mixture(BATCH, T, 9120).astype(np.float32)).to(DEV)
+    with torch.no_grad(), ops.kernel_trace(DEV) as tr:
+        getattr(model, entry)(x, ragged_lengths(cfg), **kw)
+    return [n for n, _ in tr.launches]
+
+
+IMPROVED_WALK_TRACES = {
+    "train improved_pairs 0": lambda m: train_step_trace("improved_pairs", "0"),
+    "train improved_d5 PYR_PER_LEVEL": lambda m: train_step_trace("improved_d5", "PYR_PER_LEVEL"),
+    "train improved_d5 TRAIN_FWD_SPLIT_BF16": lambda m: train_step_trace("improved_d5", "TRAIN_FWD_SPLIT_BF16"),
+    "train improved_d5 TRAIN_FWD_EXACT_MFMA": lambda m: train_step_trace("improved_d5", "TRAIN_FWD_EXACT_MFMA"),
+    "tiny_groupcomm kernel_mode_1": lambda m: causal_forward_trace(*_golden_model(m, "tiny_groupcomm"), "kernel_mode_1"),
+    "train groupcomm_d4 kernel_mode_1": lambda m: train_step_trace("groupcomm_d4", "kernel_mode_1"),
+    "forward_ragged cfg2": lambda m: ragged_trace(m, "cfg2_improved_u16", "forward_ragged"),
+    "forward_ragged cfg3": lambda m: ragged_trace(m, "cfg3_groupcomm_u8", "forward_ragged"),
+    "separate_ragged cfg2 mixture_consistency": lambda m: ragged_trace(m, "cfg2_improved_u16", "separate_ragged", mixture_consistency=True),
 }
 
 
@@ -740,6 +774,106 @@ EXPECTED.update({      # recorded on commit 30e11c2
 })
 
 
+EXPECTED.update({      # recorded on commit 2377517
+    "train improved_pairs 0": [      # 62 launches
+        (("pack_pw_weights_f16", "encoder", "pw_pair_x3f4<1>", "pyramid_moments", "pyramid_finalize",
+          "pyramid_merge_save", "pw_pair_x3f4<2>", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save",
+          "pw_conv_x3w4<2>", "pw_conv_x3w4<3>", "mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w8",
+          "overlap_add", "pack_pw_weights", "frames_gather", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_bf16x3_w8",
+          "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "pw_conv_x3w<0>", "prelu_bwd", "pw_wgrad", "pw_wgrad_reduce",
+          "pw_conv_x3w<0>", "gln_bwd_reduce", "gln_bwd_apply", "gln_bwd_reduce", "bwd_l1h", "bwd_l0p_reduce",
+          "bwd_l0p_apply", "pw_wgrad", "pw_wgrad_reduce", "pw_pair_x3f<0>", "pw_wgrad", "pw_wgrad_reduce",
+          "gln_bwd_reduce", "gln_bwd_apply", "gln_bwd_reduce", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_x3w<0>", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w8",
+          "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather",
+          "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d5 PYR_PER_LEVEL": [      # 105 launches
+        (("encoder",), 1),
+        (("pw_conv_mfma", "pw_conv_mfma", "dwconv5_s1_fast", "dwconv5_s2_fast", "dwconv5_s2_fast", "dwconv5_s2_fast",
+          "dwconv5_generic", "merge_fast"), 3),
+        (("pw_conv_mfma",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose",
+          "pw_conv_bf16x3_w4", "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "dwconv5_bwd", "dwconv5_bwd", "dwconv5_bwd", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply",
+          "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 3),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d5 TRAIN_FWD_SPLIT_BF16": [      # 96 launches
+        (("encoder",), 1),
+        (("pw_conv_bf16x3_w4", "pw_conv_bf16x3_w4", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save"), 3),
+        (("pw_conv_bf16x3_w4",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose",
+          "pw_conv_bf16x3_w4", "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "dwconv5_bwd", "dwconv5_bwd", "dwconv5_bwd", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply",
+          "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 3),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "train improved_d5 TRAIN_FWD_EXACT_MFMA": [      # 96 launches
+        (("encoder",), 1),
+        (("pw_conv_mfma", "pw_conv_mfma", "pyramid_moments", "pyramid_finalize", "pyramid_merge_save"), 3),
+        (("pw_conv_mfma",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_bf16x3_w4", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_bf16x3_w4", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose",
+          "pw_conv_bf16x3_w4", "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_apply",
+          "gln_bwd_reduce", "dwconv5_bwd", "dwconv5_bwd", "dwconv5_bwd", "bwd_l1h", "bwd_l0p_reduce", "bwd_l0p_apply",
+          "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4"), 3),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_bf16x3_w4", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "tiny_groupcomm kernel_mode_1": [      # 24 launches
+        (("zero_fill", "encoder"), 1),
+        (("pw_conv_generic", "tac", "gln_apply_add", "pw_conv_generic", "dwconv5_generic", "dwconv5_generic",
+          "dwconv5_generic", "merge_generic"), 2),
+        (("pw_conv_generic",), 2),
+        (("transpose", "zero_fill", "pw_conv_generic", "overlap_add"), 1),
+    ],
+    "train groupcomm_d4 kernel_mode_1": [      # 126 launches
+        (("encoder",), 1),
+        (("pw_conv_generic", "tac", "gln_apply_add", "pw_conv_generic", "dwconv5_generic", "dwconv5_generic",
+          "dwconv5_generic", "dwconv5_generic", "merge_generic"), 2),
+        (("pw_conv_generic",), 2),
+        (("mask_apply", "transpose", "zero_fill", "pw_conv_generic", "overlap_add", "frames_gather", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_conv_generic", "mask_bwd", "pw_wgrad", "pw_wgrad_reduce", "transpose",
+          "pw_conv_generic", "prelu_bwd"), 1),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_bwd_reduce", "gln_bwd_apply", "merge_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd", "gln_bwd_reduce", "gln_bwd_apply", "dwconv5_bwd",
+          "gln_bwd_reduce", "gln_bwd_apply", "pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic",
+          "gln_bwd_reduce", "gln_bwd_params", "gln_bwd_apply", "tac_bwd", "pw_wgrad", "pw_wgrad_reduce", "pw_wgrad",
+          "pw_wgrad_reduce", "pw_wgrad", "pw_wgrad_reduce", "pw_wgrad", "pw_wgrad_reduce", "tac_bwd_slopes",
+          "accumulate"), 2),
+        (("pw_wgrad", "pw_wgrad_reduce", "transpose", "pw_conv_generic", "gln_bwd_reduce", "gln_bwd_params",
+          "gln_bwd_apply", "gln_bwd_params", "dwconv5_bwd_params", "frames_gather", "pw_wgrad", "pw_wgrad_reduce"), 1),
+    ],
+    "forward_ragged cfg2": [      # 71 launches
+        (("zero_fill", "pack_pw_weights", "encoder_ragged", "pw_pair_x3f_ragged<1>"), 1),
+        (("pyramid_moments_ragged", "pyramid_finalize_ragged", "pyramid_merge_ragged", "pw_pair_x3f_ragged<2>"), 15),
+        (("pyramid_moments_ragged", "pyramid_finalize_ragged", "pyramid_merge_ragged", "pw_conv_x3w_ragged<2>",
+          "pack_decoder", "pw_mask_decode", "overlap_add_ragged"), 1),
+    ],
+    "forward_ragged cfg3": [      # 55 launches
+        (("zero_fill", "pack_pw_weights", "encoder_ragged", "pw_conv_x3w_ragged<1>"), 1),
+        (("tac_mfma_ragged", "pw_conv_small_ragged", "pyramid_moments_ragged", "pyramid_finalize_ragged",
+          "pyramid_merge_ragged", "pw_conv_small_ragged"), 8),
+        (("pack_decoder", "pw_mask_decode", "overlap_add_ragged"), 1),
+    ],
+    "separate_ragged cfg2 mixture_consistency": [      # 72 launches
+        (("wav_stats_ragged", "zero_fill", "pack_pw_weights", "encoder_ragged", "pw_pair_x3f_ragged<1>"), 1),
+        (("pyramid_moments_ragged", "pyramid_finalize_ragged", "pyramid_merge_ragged", "pw_pair_x3f_ragged<2>"), 15),
+        (("pyramid_moments_ragged", "pyramid_finalize_ragged", "pyramid_merge_ragged", "pw_conv_x3w_ragged<2>",
+          "pack_decoder", "pw_mask_decode", "overlap_add_ragged"), 1),
+    ],
+})
+
+
 def _check(name, got):
     want = _expand(EXPECTED[name])
     first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
@@ -773,3 +907,13 @@ def test_launch_sequence_of_the_causal_and_attentive_walks(name):
 @pytest.mark.parametrize("name", list(ORIGINAL_TRACES))
 def test_launch_sequence_of_the_original_inference_and_ragged_walks(name):
     _check(name, ORIGINAL_TRACES[name]())
+
+
+@pytest.mark.parametrize("name", list(IMPROVED_WALK_TRACES))
+def test_launch_sequence_of_the_improved_walk_branches(manifest, name):
+    got = IMPROVED_WALK_TRACES[name](manifest)
+    if name == "train improved_pairs 0":      # the shape is the right one: one forward pair per block
+        assert sum(1 for n in got if n.startswith("pw_pair_x3f4<")) == TRAIN_SHAPES["improved_pairs"][0].num_blocks
+    if name.endswith("kernel_mode_1"):        # ... and these take the branch without the pre-add
+        assert "gln_apply_add" in got
+    _check(name, got)
