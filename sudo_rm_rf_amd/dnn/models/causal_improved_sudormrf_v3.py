@@ -245,7 +245,7 @@ class CausalSuDORMRF(_OptIn, _Model):
         """A streaming session over `batch` independent streams (sudo_rm_rf_amd.streaming.CausalStream): push() samples as
         they arrive, get separated samples back with a delay of enc_kernel_size // 2; finish() ends the streams so that the
         concatenated outputs equal forward() on the whole signal.  max_chunk: the most samples one kernel pass takes (a
-        multiple of the granule, default 16 granules; longer pushes are cut).  Nothing is stored on the module."""
+        multiple of the granule, default 16 granules, 10 at depth 8; longer pushes are cut).  Nothing is stored on the module."""
         from ...streaming import CausalStream
         return CausalStream(self, batch=batch, max_chunk=max_chunk, device=device)
 

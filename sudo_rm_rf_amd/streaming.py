@@ -16,6 +16,25 @@ from .dnn.models._base import _refuse_autograd
 from .engine import _checked_params, _config_struct, _weights
 
 
+def _pyramid_lds_bytes(depth, frames):
+    """LDS of srf_stream_pyramid_kernel for a chunk of `frames` frames (stream_pyr_lds of csrc/srf_causal_stream.hip): four rows per
+    wavefront, per row [10 of state | input] of every level and the last level's output."""
+    per_row = sum(10 + (frames if k == 0 else frames >> (k - 1)) for k in range(depth)) + (frames >> (depth - 1))
+    return 4 * 4 * per_row
+
+
+def default_max_chunk(enc_kernel_size, upsampling_depth):
+    """max_chunk_samples of a session opened without one: 16 granules where the streaming pyramid holds such a chunk in its
+    64 KiB of LDS (every depth up to 7), else the most granules that fit (10 at depth 8, where 16 granules are 2048 frames
+    and srf_stream_create refuses them)."""
+    h, depth = enc_kernel_size // 2, max(upsampling_depth, 1)
+    unit = 1 << (depth - 1)
+    n = 16
+    while n > 1 and _pyramid_lds_bytes(depth, n * unit) > 64 * 1024:
+        n -= 1
+    return n * h * unit
+
+
 class _Session:
     """The srf_stream handle and its geometry (needs no GPU)."""
 
@@ -23,8 +42,9 @@ class _Session:
         lib = _lib.load()
         cfg = _config_struct(*cfg_tuple[:10])
         if max_chunk is None:
-            # 16 granules, from the config alone (the library checks the same arithmetic)
-            max_chunk = 16 * (cfg.enc_kernel_size // 2) * 2 ** max(cfg.upsampling_depth - 1, 0)
+            # 16 granules, or as many as the streaming pyramid's LDS takes (10 at depth 8), from the config alone (the
+            # library checks the same arithmetic)
+            max_chunk = default_max_chunk(cfg.enc_kernel_size, cfg.upsampling_depth)
         handle = C.c_void_p()
         _lib.check(lib.srf_stream_create(C.byref(cfg), int(batch), int(max_chunk), C.byref(handle)), "srf_stream_create")
         self.handle = handle

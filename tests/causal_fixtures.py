@@ -26,6 +26,10 @@ TINY = dict(in_audio_channels=1, out_channels=32, in_channels=64, num_blocks=2, 
             enc_num_basis=64, num_sources=2)
 TINY_A2 = dict(in_audio_channels=2, out_channels=32, in_channels=64, num_blocks=2, upsampling_depth=2, enc_kernel_size=11,
                enc_num_basis=64, num_sources=3)
+# depth 8 (the deepest the library takes): one block, 16 channels; 23001 samples pad to 2304 frames = three 1024-frame tiles of
+# the fused pyramid, the third one's 1280-frame left halo reaching into the first
+TINY_D8 = dict(in_audio_channels=1, out_channels=8, in_channels=16, num_blocks=1, upsampling_depth=8, enc_kernel_size=21,
+               enc_num_basis=16, num_sources=2)
 
 # name -> (constructor kwargs, batch, T, weight seed, input seed, stored arrays)
 CASES = {
@@ -34,6 +38,7 @@ CASES = {
     "causal_tiny_short": (TINY, 2, 50, 103, 103, ("out",)),
     "causal_default": (DEFAULTS, 4, 32000, 104, 104, ("out",)),
     "causal_main": (MAIN, 1, 44100, 105, 105, ("out",)),
+    "causal_tiny_d8": (TINY_D8, 2, 23001, 107, 107, ("out",)),
 }
 # configurations whose seeded reference state_dict is pinned by sha256 digests (CPU test)
 DIGEST_CONFIGS = {"tiny": TINY, "main": MAIN}

@@ -31,6 +31,9 @@ GRAD_CASES = {
     "causal_train_tiny": (cf.TINY, 2, 1001, "tiny"),
     "causal_train_a2_k11": (cf.TINY_A2, 3, 777, "tiny"),
     "causal_train_default_u8": (DEFAULT_U8, 2, 12000, "default"),
+    # depth 8: 12001 samples pad to 1280 frames, two tiles of the fused backward; the first one's 1280-frame right halo of
+    # g_merged is clipped at the end of the row
+    "causal_train_tiny_d8": (cf.TINY_D8, 2, 12001, "tiny"),
 }
 # the bars of the GPU test per kind: check_grads_against_golden(tol, fp32_yardstick, flip_budget)
 GRAD_BARS = {"tiny": (2e-4, 0.0, 0.0), "default": (2e-3, 4.0, 0.01)}

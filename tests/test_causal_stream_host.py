@@ -53,12 +53,14 @@ def test_session_geometry(name):
     s = _Session(_tuple(cfg), batch)
     assert s.granule == h * 2 ** (D - 1) and s.delay == h
     assert {"causal_tiny": 40, "causal_tiny_a2_k11": 10, "causal_tiny_short": 40, "causal_default": 80,
-            "causal_main": 160}[name] == s.granule
+            "causal_main": 160, "causal_tiny_d8": 1280}[name] == s.granule
     # three sections, each padded to 64 floats (include/sudormrf_hip.h)
     assert s.state_bytes == 4 * (_align64(batch * A * 2 * h) + _align64(U * D * batch * Cc * 10) + _align64(batch * S * A * (h + 1)))
     assert s.state_bytes >= 4 * (A * 2 * h + U * D * Cc * 10 + S * A * (h + 1)) * batch
     assert s.num_launches == 3 * U + 5
-    assert s.max_chunk == 16 * s.granule
+    # 16 granules by default; at depth 8 those are 2048 frames, more than the streaming pyramid's LDS holds (srf_stream_create
+    # refuses them), and the default is the 10 granules = 1280 frames = 62 560 bytes that fit
+    assert s.max_chunk == (10 if D == 8 else 16) * s.granule
     n_floats = sum(int(np.prod(shape)) if shape else 1 for _, shape in cf.schema(cfg))
     assert 4 * n_floats <= s.weights_bytes <= 4 * (n_floats + 64 * len(cf.schema(cfg)))
     assert s.workspace_bytes >= 4 * batch * (s.max_chunk // h) * (N + 2 * B + 2 * Cc + S * A * N + S * A * K)
@@ -90,6 +92,25 @@ def test_create_refusals():
     from sudo_rm_rf_amd.streaming import _Session
     with pytest.raises(_lib.SrfError, match="causal"):
         _Session(_tuple(cf.TINY, "improved"), 1)
+
+
+@pytest.mark.parametrize("D", range(1, 9))
+def test_default_max_chunk_is_the_largest_the_library_takes_up_to_16_granules(D):
+    """srf_stream_create takes the default of every depth; where the default is below 16 granules (depth 8: 10), one granule more
+    is refused for the pyramid's LDS."""
+    from sudo_rm_rf_amd import _lib
+    from sudo_rm_rf_amd.engine import _config_struct
+    from sudo_rm_rf_amd.streaming import _Session, default_max_chunk
+    cfg = dict(cf.TINY_D8, upsampling_depth=D)
+    g = 10 << (D - 1)
+    n = default_max_chunk(21, D)
+    assert n % g == 0 and n // g == (10 if D == 8 else 16)
+    s = _Session(_tuple(cfg), 2)
+    assert (s.granule, s.max_chunk) == (g, n)
+    if n < 16 * g:
+        lib, h = _lib.load(), C.c_void_p()
+        c = _config_struct(*_tuple(cfg))
+        assert lib.srf_stream_create(C.byref(c), 2, n + g, C.byref(h)) == -1 and "LDS" in _err(lib)
 
 
 def test_push_reset_and_prepare_refusals_come_before_any_launch():

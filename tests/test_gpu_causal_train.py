@@ -61,8 +61,13 @@ def _tile():
 
 
 def _lengths(D):
+    """Multiples of the granule q = 2^(D-1).  Up to D = 6 the last length is two tiles plus 11 granules; at D = 7 and 8 it is
+    2432 (two tiles plus 6 and 3 granules: a third, partial tile whose frames lie inside the right halo, 10 * 2^(D-1) = 640 and
+    1280 frames, of BOTH earlier tiles).  At D = 8 the list is 128 and 896 (below a tile), 1024, 1152 (a tile plus 128), 2432."""
     q, t = 1 << (D - 1), _tile()
-    return [q, 8 * q, t - q, t, t + q, 2 * t + 11 * q]
+    last = 2 * t + 11 * q if D <= 6 else 2432
+    assert last % q == 0 and last > 2 * t
+    return sorted({q, 8 * q, t - q, t, t + q, last})
 
 
 _REF_CACHE = {}
@@ -122,7 +127,7 @@ def _flat(out):
     return [out["gu"], out["da_p"]] + out["dw"] + out["db"] + out["ds"]
 
 
-@pytest.mark.parametrize("D", [1, 3, 5])
+@pytest.mark.parametrize("D", [1, 3, 5, 6, 7, 8])
 def test_pyramid_backward_kernels_match_autograd(dev, D):
     """Both forms on Bt = 2, C = 5 at every length where the fused kernel's tiling changes: a fraction of a tile, one tile less /
     exactly / more than a granule, and two tiles plus more than the deepest level's right halo.  One slope negative, one zero,

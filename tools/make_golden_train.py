@@ -42,6 +42,13 @@ CASES = {
     "train_cfg4_bench": (ModelConfig("improved", 512, 512, 36, 6, 21, 2048, 2), 4, 32000, 105, 205),
     # cfg 3 (GroupComm U8, G = 16) at the bench length: the TAC and (batch x group)-folded norm kernels at L = 3200
     "train_cfg3_bench": (ModelConfig("groupcomm", 256, 512, 8, 5, 21, 512, 2, 1, 16), 4, 32000, 106, 206),
+    # depths 7 and 8 (the register-resident pyramid stops at 6: the training forward runs level by level; the backward's apply
+    # pass folds the merge backward of levels 6 and 7 in with its cross-lane shuffles).  L = padded T / 10 frames, L / 2^D:
+    #   d7: T = 5000 -> L = 512, 4 (even);  d8: T = 7600 -> L = 768, 3 (odd: the deepest conv's input has 12 frames, 12 % 8 == 4,
+    #   the chunked depthwise backward);  groupcomm d7: T = 3700 -> L = 384, 3 (odd)
+    "train_tiny_improved_d7": (ModelConfig("improved", 8, 16, 2, 7, 21, 16, 2), 2, 5000, 114, 207),    # (seeds with an unclamped loss)
+    "train_tiny_improved_d8": (ModelConfig("improved", 8, 16, 2, 8, 21, 16, 2), 2, 7600, 116, 207),
+    "train_tiny_groupcomm_d7": (ModelConfig("groupcomm", 16, 16, 2, 7, 21, 16, 2, 1, 4), 2, 3700, 109, 209),
 }
 # fp64 cases that ALSO pin the gradient w.r.t. the input waveform (srf_backward_wav at a bench shape)
 GWAV_F64 = {"train_cfg3_bench"}
