@@ -1082,6 +1082,54 @@ int srf_attentive_v3_plan_create(const srf_config* base, int n_heads, int att_di
 int srf_gln_apply_stats(const float* x, const srf_norm* norm, float* y, double* out_sums, int groups, int channels, int length,
                         void* stream);
 
+/* ---- Attentive block on a ragged batch (additive to ABI 19) ----
+ * The ragged forms of the kernels an AttentiveUConvBlock runs besides its GEMMs and the attention: the same kernel templates as
+ * their uniform twins with the table behind their arguments (profiler names: the twin's + "_ragged").  Tensors keep the uniform
+ * layout, the length argument stays the ROW STRIDE, and example (group) b brings its own count of columns in a HOST table of Bt
+ * (groups) ints that travels by value in the launch arguments: no upload, no synchronisation, at most SRF_RAGGED_MAX_BATCH
+ * entries.  Every example is treated as its own batch-1 call on its slice would treat it: a GlobLN applied on load counts
+ * C * (its own columns), a convolution meets literal zeros at its own end, nothing is read at or past an example's end (it may
+ * hold NaN), outputs are exact 0.f from the example's own end to the row stride, and out_sums (where the twin has them;
+ * nullable, accumulated in the twin's bucket scheme) run over the example's own columns.  A row's output does not depend on any
+ * other row's content, nor on its length while the launch stays on the same kernel (the float4 kernels below serve a launch whose
+ * EVERY length lies on their grid; they pre-add a lane's four outputs in fp32 before the fp64 out_sums, the generic ones do not).
+ * srf_dwconv5_ragged: in_frames[b] input columns under row stride Lin; for stride 2 Lin and every in_frames[b] are even.  The
+ *   output row stride is srf_dwconv5's, the example's own outputs are in_frames[b] / stride.  The float4 kernels serve a launch
+ *   whose Lin and every in_frames[b] are multiples of 4 * stride (and 16-byte aligned x, y), the generic kernel any other.
+ * srf_merge_ragged: frames[b] level-0 columns, a multiple of 2^(D-1); level k has frames[b] >> k columns under row stride
+ *   L >> k and its norm counts C * (frames[b] >> k).  The float4 kernel serves a launch whose L and every frames[b] are multiples
+ *   of 4, the generic kernel any other.
+ * srf_posenc_apply_ragged: the inference form (no dropout): x[b, c, l] = norm(a)[b, c, l] + pe[l, c] for l < frames[b], the
+ *   norm counting C * frames[b]; neither a nor pe is read at l >= frames[b].
+ * srf_gln_apply2_add_ragged, srf_gln_apply_ragged: any frames[g] >= 1 (dword accesses throughout); both need the statistics,
+ *   gamma and beta of their norm(s).
+ * srf_gln_stats_ragged: WRITES sums[g] ([SRF_STAT_BUCKETS][2], srf_gln_stats' layout; no zeroing needed) = {sum, sumsq} over
+ *   x[g, :, :frames[g]].  Bucket k holds the rows c = k mod SRF_STAT_BUCKETS, added in a fixed order by the bucket's one block: no
+ *   atomics, the same bits on every run, and a group's numbers do not depend on the other groups.
+ * srf_sums_scale_ragged: out[g][*] = in[g][*] * (double) L / frames[g], not in place, one launch.  This is the copy a UNIFORM
+ *   kernel's on-load norm takes (e.g. srf_pw_conv_packed on a ragged batch): with the count C * L it assumes, the scaled sums
+ *   give the mean and variance of the example's own C * frames[g] elements.  Ragged kernels take the unscaled sums.
+ * Refused before any launch (SRF_EINVAL, the message names the example): a null table, more than SRF_RAGGED_MAX_BATCH entries,
+ *   an entry < 1 or above its row stride, an odd entry (or Lin) under stride 2, a frames[b] that is no multiple of 2^(D-1) in the
+ *   merge, and everything the uniform twin refuses. */
+int srf_dwconv5_ragged(const float* x, const float* w, const float* bias, float* y, int Bt, int C, int Lin, int stride,
+                       const srf_norm* in_norm, double* out_sums, const int* in_frames, void* stream);
+int srf_merge_ragged(const float* const* levels, const srf_norm* norms, int D, float* y, int Bt, int C, int L, double* out_sums,
+                     const int* frames, void* stream);
+int srf_posenc_apply_ragged(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L, int max_len,
+                            const int* frames, void* stream);
+int srf_gln_apply2_add_ragged(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z,
+                              double* out_sums, int groups, int channels, int length, const int* frames, void* stream);
+int srf_gln_apply_ragged(const float* x, float* y, const srf_norm* norm, int groups, int channels, int length, const int* frames,
+                         void* stream);
+int srf_gln_stats_ragged(const float* x, double* sums, int groups, int channels, int length, const int* frames, void* stream);
+int srf_sums_scale_ragged(const double* in, double* out, int groups, int length, const int* frames, void* stream);
+/* 1 where srf_pw_conv_packed_ragged takes (Bt, Cin, Cout, L) with these frames NOW -- the 256 x 128 kernel's shape and reach,
+ * kernel mode 0, no debug flag that takes the kernel or the packed images away, 1 <= frames[b] <= L and frames[b] % 4 == 0 --
+ * else 0 (no GPU needed; frames on the host).  Left to the call: the forms built, non-null pointers, the 16-byte alignment of x, y,
+ * residual and the packed image.  For a caller with another path to take: the attentive block falls back to the uniform GEMM. */
+int srf_pw_conv_packed_ragged_supported(int Bt, int Cin, int Cout, int L, const int* frames);
+
 /* ---- Original SuDoRM-RF (additive to ABI 19; sudormrf.py) ----
  * The model of the paper: an encoder WITH bias and ReLU, GroupNorm(1, C) everywhere (GlobLN's arithmetic), PReLU with one slope
  * PER CHANNEL, blocks whose residual is added before the last norm, a mask layer that is a convolution along the basis axis

@@ -250,6 +250,15 @@ _PROTOS = {
     "srf_decoder_bias_grad_scratch_floats": (_sz, [_i]),
     "srf_decoder_bias_grad": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "srf_relu_gate": (_i, [_vp, _vp, _l, _vp]),
+    "srf_dwconv5_ragged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(srf_norm), _vp, C.POINTER(_i), _vp]),
+    "srf_merge_ragged": (_i, [C.POINTER(_vp), C.POINTER(srf_norm), _i, _vp, _i, _i, _i, _vp, C.POINTER(_i), _vp]),
+    "srf_posenc_apply_ragged": (_i, [_vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, _i, C.POINTER(_i), _vp]),
+    "srf_gln_apply2_add_ragged": (_i, [_vp, C.POINTER(srf_norm), _vp, C.POINTER(srf_norm), _vp, _vp, _i, _i, _i, C.POINTER(_i),
+                                       _vp]),
+    "srf_gln_apply_ragged": (_i, [_vp, _vp, C.POINTER(srf_norm), _i, _i, _i, C.POINTER(_i), _vp]),
+    "srf_gln_stats_ragged": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i), _vp]),
+    "srf_sums_scale_ragged": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), _vp]),
+    "srf_pw_conv_packed_ragged_supported": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

@@ -236,16 +236,27 @@ def _u64(v):
     return C.c_ulonglong(int(v) & 0xFFFFFFFFFFFFFFFF)
 
 
-def posenc_apply(a, pe, sums=None, gamma=None, beta=None, out=None, p=0.0, seed=0, offset=0):
+def posenc_apply(a, pe, sums=None, gamma=None, beta=None, out=None, p=0.0, seed=0, offset=0, lengths=None):
     """x[b, c, l] = GlobLN(a)[b, c, l] + pe[l, c] (no norm when sums is None).  a [Bt, C, L]; pe [max_len, C] or [1, max_len, C].
     p > 0: under dropout (srf_posenc_apply_dropout): an element is kept and scaled by the fp32 1 / (1 - p), or exactly 0, by
-    the Philox bit of (seed, offset, its flat index); p == 0 is the plain kernel."""
+    the Philox bit of (seed, offset, its flat index); p == 0 is the plain kernel.
+    lengths (a list or a CPU tensor of Bt entries; None: nothing changes): the ragged form (srf_posenc_apply_ragged, inference
+    only) -- example b is lengths[b] positions long, `sums` are its own-column sums and the norm counts C * lengths[b]; a and pe
+    are not read at or past lengths[b] and x is exact 0 there."""
     dev = _chk(a, pe, sums, gamma, beta, out)
     Bt, Cc, L = a.shape
     if pe.shape[-1] != Cc:
         raise _lib.SrfError("posenc_apply: the table has %d channels, the input %d" % (pe.shape[-1], Cc))
     if out is None:
         out = torch.empty_like(a)
+    if lengths is not None:
+        if p != 0.0:
+            raise _lib.SrfError("posenc_apply: the ragged form has no dropout (p = %g)" % p)
+        frs = ragged._frames_for("srf_posenc_apply_ragged", lengths, Bt, "lengths")
+        rc = _lib.load().srf_posenc_apply_ragged(_lib.ptr(a), _norm(sums, gamma, beta, None), _lib.ptr(pe), _lib.ptr(out), Bt, Cc, L,
+                                                 pe.shape[-2], frs, _lib.current_stream(dev))
+        _lib.check(rc, "srf_posenc_apply_ragged")
+        return out
     if p == 0.0 and seed == 0 and offset == 0:
         rc = _lib.load().srf_posenc_apply(_lib.ptr(a), _norm(sums, gamma, beta, None), _lib.ptr(pe), _lib.ptr(out), Bt, Cc, L,
                                           pe.shape[-2], _lib.current_stream(dev))
@@ -475,12 +486,23 @@ def uconv_block_train(block, x):
                                            layer.pos_enc.pe.detach(), x, *par)
 
 
-def gln_apply2_add(f, f_sums, f_gamma, f_beta, f_prelu, y, y_sums, y_gamma, y_beta, y_prelu=None, out_sums=None, out=None):
-    """z = norm_f(f) + norm_y(y), each GlobLN (+ PReLU where a slope is given); out_sums += {sum, sumsq} of z."""
+def gln_apply2_add(f, f_sums, f_gamma, f_beta, f_prelu, y, y_sums, y_gamma, y_beta, y_prelu=None, out_sums=None, out=None,
+                   lengths=None):
+    """z = norm_f(f) + norm_y(y), each GlobLN (+ PReLU where a slope is given); out_sums += {sum, sumsq} of z.
+    lengths (a list or a CPU tensor of `groups` entries; None: nothing changes): the ragged form (srf_gln_apply2_add_ragged) --
+    group g is lengths[g] columns long (any count >= 1), both sums are own-column sums and both norms count C * lengths[g];
+    z is exact 0 at or past lengths[g] and out_sums run over the group's own columns."""
     dev = _chk(f, f_sums, f_gamma, f_beta, f_prelu, y, y_sums, y_gamma, y_beta, y_prelu, out_sums, out)
     groups, channels, length = f.shape
     if out is None:
         out = torch.empty_like(f)
+    if lengths is not None:
+        frs = ragged._frames_for("srf_gln_apply2_add_ragged", lengths, groups, "lengths")
+        rc = _lib.load().srf_gln_apply2_add_ragged(_lib.ptr(f), _norm(f_sums, f_gamma, f_beta, f_prelu), _lib.ptr(y),
+                                                   _norm(y_sums, y_gamma, y_beta, y_prelu), _lib.ptr(out), _lib.ptr(out_sums),
+                                                   groups, channels, length, frs, _lib.current_stream(dev))
+        _lib.check(rc, "srf_gln_apply2_add_ragged")
+        return out
     rc = _lib.load().srf_gln_apply2_add(_lib.ptr(f), _norm(f_sums, f_gamma, f_beta, f_prelu), _lib.ptr(y),
                                         _norm(y_sums, y_gamma, y_beta, y_prelu), _lib.ptr(out), _lib.ptr(out_sums), groups,
                                         channels, length, _lib.current_stream(dev))

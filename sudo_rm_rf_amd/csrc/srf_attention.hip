@@ -389,26 +389,39 @@ __device__ __forceinline__ float srf_posenc_drop(size_t, float v) { return v; } 
 __device__ __forceinline__ float srf_posenc_drop(size_t at, float v, SrfDropoutDev d) {
   return srf_dropout_keep(d, at) ? v * d.inv_keep : 0.f;
 }
+__device__ __forceinline__ float srf_posenc_drop(size_t, float v, const SrfFrames&) { return v; }   // (ragged: inference only)
+template <typename... X>
+struct SrfPosencRagged { static constexpr bool value = false; };
+template <>
+struct SrfPosencRagged<SrfFrames> { static constexpr bool value = true; };
 
+// RAGGED (srf_posenc_apply_ragged; the pack is one SrfFrames): L stays the row stride, example g is frames[g] positions long;
+// the norm counts C * frames[g], neither a nor pe is read at positions >= frames[g], and x is exact 0 there.
 template <typename... Drop>
 __global__ __launch_bounds__(256) void srf_posenc_apply_kernel(const float* __restrict__ a, SrfNormDev nrm, const float* __restrict__ pe,
                                                                float* __restrict__ x, double inv_count, int C, int L, Drop... drop) {
+  constexpr bool RAGGED = SrfPosencRagged<Drop...>::value;
   __shared__ float tile[32][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int l0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
   const long g = blockIdx.z;
+  int own = L;      // (RAGGED) the example's own positions
+  if constexpr (RAGGED) {
+    own = srf_frames_of((int)g, drop...);
+    inv_count = 1.0 / ((double)C * (double)own);
+  }
   float mean = 0.f, rstd = 1.f;
   if (nrm.sums) srf_finalize_stats(nrm.sums, g, inv_count, mean, rstd);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int l = l0 + ty + 8 * i, c = c0 + tx;
-    tile[ty + 8 * i][tx] = (l < L && c < C) ? pe[(size_t)l * C + c] : 0.f;
+    tile[ty + 8 * i][tx] = (l < own && c < C) ? pe[(size_t)l * C + c] : 0.f;
   }
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = c0 + ty + 8 * i, l = l0 + tx;
-    if (c < C && l < L) {
+    if (c < C && l < own) {
       float sc = 1.f, sh = 0.f;
       if (nrm.sums) {
         sc = nrm.gamma[c] * rstd;
@@ -416,6 +429,8 @@ __global__ __launch_bounds__(256) void srf_posenc_apply_kernel(const float* __re
       }
       const size_t at = ((size_t)g * C + c) * L + l;
       x[at] = srf_posenc_drop(at, fmaf(a[at], sc, sh) + tile[tx][ty + 8 * i], drop...);
+    } else if constexpr (RAGGED) {
+      if (c < C && l < L) x[((size_t)g * C + c) * L + l] = 0.f;
     }
   }
 }
@@ -438,6 +453,22 @@ extern "C" int srf_posenc_apply(const float* a, const srf_norm* norm, const floa
   SRF_CHECK_ALIGNED16("srf_posenc_apply", {"norm.sums", nd.sums});
   srf_posenc_launch(a, nd, pe, x, Bt, C, L, stream);
   SRF_CHECK_LAUNCH("posenc_apply", stream);
+  return SRF_OK;
+}
+
+extern "C" int srf_posenc_apply_ragged(const float* a, const srf_norm* norm, const float* pe, float* x, int Bt, int C, int L,
+                                       int max_len, const int* frames, void* stream) {
+  SRF_CHECK_ARG(a && pe && x && Bt > 0 && C > 0 && L > 0, "srf_posenc_apply_ragged: bad arguments");
+  SRF_CHECK_ARG(L <= max_len, "srf_posenc_apply_ragged: L = %d positions exceed the table's max_len = %d", L, max_len);
+  SRF_CHECK_ARG((C + 31) / 32 <= 65535, "srf_posenc_apply_ragged: channels too large");
+  const SrfNormDev nd = srf_norm_dev(norm);
+  if (nd.sums) SRF_CHECK_ARG(nd.gamma && nd.beta, "srf_posenc_apply_ragged: norm without gamma/beta");
+  SRF_CHECK_ALIGNED16("srf_posenc_apply_ragged", {"norm.sums", nd.sums});
+  SrfFrames fr;
+  const int rc = srf_frames_table("srf_posenc_apply_ragged", frames, Bt, L, &fr);
+  if (rc) return rc;
+  srf_posenc_launch(a, nd, pe, x, Bt, C, L, stream, fr);
+  SRF_CHECK_LAUNCH("posenc_apply_ragged", stream);
   return SRF_OK;
 }
 
@@ -521,14 +552,24 @@ extern "C" int srf_dropout_mask(unsigned char* keep, long n, float p, unsigned l
 // The transformer layer's closing step: ffn's GlobLN + PReLU and out_mha_norm applied on load, the sum's statistics for out_norm.
 // One block per (row = (g, c), chunk of 1024 positions), as srf_gln_apply.
 // ---------------------------------------------------------------------------------------------
+// RAGGED (srf_gln_apply2_add_ragged; FR = SrfFrames): `length` stays the row stride, group g is frames[g] columns long (any count
+// >= 1: every access is a dword); both norms count channels * frames[g], f and y are not read at columns >= frames[g], z is
+// exact 0 there and out_sums run over the group's own columns.
+template <typename... FR>
 __global__ __launch_bounds__(256) void srf_gln_apply2_add_kernel(const float* __restrict__ f, SrfNormDev nf, const float* __restrict__ y,
                                                                  SrfNormDev ny, float* __restrict__ z, double* __restrict__ out_sums,
-                                                                 double inv_count, int channels, int length, int chunks) {
+                                                                 double inv_count, int channels, int length, int chunks, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   __shared__ double red[8];
   const long row = blockIdx.x / chunks;
   const int chunk = blockIdx.x - row * chunks;
   const int c = (int)(row % channels);
   const long g = row / channels;
+  int own = length;      // (RAGGED) the group's own columns
+  if constexpr (RAGGED) {
+    own = srf_frames_of((int)g, fr...);
+    inv_count = 1.0 / ((double)channels * (double)own);
+  }
   float mf, rf, my, ry;
   srf_finalize_stats(nf.sums, g, inv_count, mf, rf);
   srf_finalize_stats(ny.sums, g, inv_count, my, ry);
@@ -541,7 +582,7 @@ __global__ __launch_bounds__(256) void srf_gln_apply2_add_kernel(const float* __
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int l = chunk * 1024 + u * 256 + threadIdx.x;
-    if (l < length) {
+    if (l < own) {
       float vf = fmaf(f[base + l], scf, shf);
       if (actf) vf = srf_prelu(vf, slf);
       float vy = fmaf(y[base + l], scy, shy);
@@ -550,24 +591,48 @@ __global__ __launch_bounds__(256) void srf_gln_apply2_add_kernel(const float* __
       z[base + l] = v;
       ds += (double)v;
       dq += (double)v * (double)v;
+    } else if constexpr (RAGGED) {
+      if (l < length) z[base + l] = 0.f;
     }
   }
   if (out_sums) srf_block_stats_atomic<4>(ds, dq, srf_stat_slot(out_sums, g, blockIdx.x), red);
 }
 
-extern "C" int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z,
-                                  double* out_sums, int groups, int channels, int length, void* stream) {
-  SRF_CHECK_ARG(f && y && z && fnorm && ynorm && groups > 0 && channels > 0 && length > 0, "srf_gln_apply2_add: bad arguments");
+// who: the entry point's name in its refusals; frames: NULL = the uniform call, else one entry per group (srf_gln_apply2_add_ragged)
+static int gln_apply2_add_impl(const char* who, const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z,
+                               double* out_sums, int groups, int channels, int length, const int* frames, void* stream) {
+  SRF_CHECK_ARG(f && y && z && fnorm && ynorm && groups > 0 && channels > 0 && length > 0, "%s: bad arguments", who);
   SRF_CHECK_ARG(fnorm->sums && fnorm->gamma && fnorm->beta && ynorm->sums && ynorm->gamma && ynorm->beta,
-                "srf_gln_apply2_add: both norms need statistics, gamma and beta");
-  SRF_CHECK_ALIGNED16("srf_gln_apply2_add", {"fnorm.sums", fnorm->sums}, {"ynorm.sums", ynorm->sums});
+                "%s: both norms need statistics, gamma and beta", who);
+  SRF_CHECK_ALIGNED16(who, {"fnorm.sums", fnorm->sums}, {"ynorm.sums", ynorm->sums});
   const int chunks = (length + 1023) / 1024;
   const long blocks = (long)groups * channels * chunks;
-  SRF_CHECK_ARG(blocks < (1L << 31), "srf_gln_apply2_add: tensor too large");
-  hipLaunchKernelGGL(srf_gln_apply2_add_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, f, srf_norm_dev(fnorm), y,
+  SRF_CHECK_ARG(blocks < (1L << 31), "%s: tensor too large", who);
+  if (frames) {
+    SrfFrames fr;
+    const int rc = srf_frames_table(who, frames, groups, length, &fr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(srf_gln_apply2_add_kernel<SrfFrames>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, f,
+                       srf_norm_dev(fnorm), y, srf_norm_dev(ynorm), z, out_sums, 1.0 / ((double)channels * (double)length), channels,
+                       length, chunks, fr);
+    SRF_CHECK_LAUNCH("gln_apply2_add_ragged", stream);
+    return SRF_OK;
+  }
+  hipLaunchKernelGGL(srf_gln_apply2_add_kernel<>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, f, srf_norm_dev(fnorm), y,
                      srf_norm_dev(ynorm), z, out_sums, 1.0 / ((double)channels * (double)length), channels, length, chunks);
   SRF_CHECK_LAUNCH("gln_apply2_add", stream);
   return SRF_OK;
+}
+
+extern "C" int srf_gln_apply2_add(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z,
+                                  double* out_sums, int groups, int channels, int length, void* stream) {
+  return gln_apply2_add_impl("srf_gln_apply2_add", f, fnorm, y, ynorm, z, out_sums, groups, channels, length, nullptr, stream);
+}
+
+extern "C" int srf_gln_apply2_add_ragged(const float* f, const srf_norm* fnorm, const float* y, const srf_norm* ynorm, float* z,
+                                         double* out_sums, int groups, int channels, int length, const int* frames, void* stream) {
+  SRF_CHECK_ARG(frames != nullptr, "srf_gln_apply2_add_ragged: null frames table");
+  return gln_apply2_add_impl("srf_gln_apply2_add_ragged", f, fnorm, y, ynorm, z, out_sums, groups, channels, length, frames, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

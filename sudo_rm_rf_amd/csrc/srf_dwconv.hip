@@ -61,56 +61,77 @@ __device__ __forceinline__ float srf_tap5(float bs, float w0, float w1, float w2
 
 // ---------------------------------------------------------------------------------------------
 // depthwise conv, generic: block = (row, chunk of 256 outputs), thread = one output
+// RAGGED (srf_dwconv5_ragged; FR = SrfFrames): Lin and Lout stay the row strides, example b is in_frames[b] columns long.  x is
+// not read at columns >= in_frames[b] (the taps meet literal zeros there), the on-load norm counts C * in_frames[b], y is exact
+// 0 from its own output length on and out_sums run over its own outputs.
 // ---------------------------------------------------------------------------------------------
+template <typename... FR>
 __global__ __launch_bounds__(256) void srf_dwconv5_generic_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
     float* __restrict__ y, SrfNormDev nrm, double inv_count, double* __restrict__ out_sums, int C,
-    int Lin, int Lout, int stride, int chunks) {
+    int Lin, int Lout, int stride, int chunks, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   __shared__ double red[8];
   const long row = blockIdx.x / chunks;
   const int chunk = blockIdx.x - row * chunks;
   const int c = (int)(row % C);
   const long b = row / C;
+  int own_in = Lin, own_out = Lout;      // (RAGGED) the example's own input and output columns
+  if constexpr (RAGGED) {
+    own_in = srf_frames_of((int)b, fr...);
+    own_out = (own_in - 1) / stride + 1;
+    inv_count = 1.0 / ((double)C * (double)own_in);
+  }
   const RowCoef rc = srf_row_coef(nrm, b, c, inv_count);
   const int j = chunk * 256 + threadIdx.x;
   double ds = 0.0, dq = 0.0;
-  if (j < Lout) {
+  if (j < own_out) {
     const float* xr = x + (size_t)row * Lin;
     float acc = bias[c];
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
       const int i = stride * j + k - 2;
-      const float v = (i >= 0 && i < Lin) ? srf_tf(xr[i], rc) : 0.f;
+      const float v = (i >= 0 && i < own_in) ? srf_tf(xr[i], rc) : 0.f;
       acc = fmaf(w[c * 5 + k], v, acc);
     }
     y[(size_t)row * Lout + j] = acc;
     ds = (double)acc;
     dq = (double)acc * (double)acc;
+  } else if constexpr (RAGGED) {
+    if (j < Lout) y[(size_t)row * Lout + j] = 0.f;
   }
   if (out_sums) srf_block_stats_atomic<4>(ds, dq, srf_stat_slot(out_sums, b, blockIdx.x), red);
 }
 
 // ---------------------------------------------------------------------------------------------
 // depthwise conv, fast: one wavefront per row; requires Lin % (4*STRIDE) == 0, 16-B aligned bases
+// RAGGED (FR = SrfFrames; every in_frames[b] % (4*STRIDE) == 0 too): the row's own float4 groups take the place of the row's,
+// and the output groups between the example's own end and the row stride are stored as zeros.
 // ---------------------------------------------------------------------------------------------
-template <int STRIDE>
+template <int STRIDE, typename... FR>
 __global__ __launch_bounds__(256) void srf_dwconv5_fast_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
     float* __restrict__ y, SrfNormDev nrm, double inv_count, double* __restrict__ out_sums, int C,
-    int Lin, int Lout, long rows) {
+    int Lin, int Lout, long rows, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (row >= rows) return;  // wave-uniform; no block-level barrier below
   const int c = (int)(row % C);
   const long b = row / C;
+  int own_in = Lin;      // (RAGGED) the example's own input columns
+  if constexpr (RAGGED) {
+    own_in = srf_frames_of((int)b, fr...);
+    inv_count = 1.0 / ((double)C * (double)own_in);
+  }
   const RowCoef rc = srf_row_coef(nrm, b, c, inv_count);
   const float w0 = w[c * 5 + 0], w1 = w[c * 5 + 1], w2 = w[c * 5 + 2], w3 = w[c * 5 + 3],
               w4 = w[c * 5 + 4];
   const float bs = bias[c];
   const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * Lin);
   float4* yr = reinterpret_cast<float4*>(y + (size_t)row * Lout);
-  const int nin4 = Lin >> 2, nout4 = Lout >> 2;
-  const int nchunks = (nout4 + 63) >> 6;
+  const int nin4 = own_in >> 2, nout4 = RAGGED ? (own_in / STRIDE) >> 2 : Lout >> 2;
+  const int nchunks = ((Lout >> 2) + 63) >> 6;
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
   double ds = 0.0, dq = 0.0;
   float cz = 0.f, cw = 0.f;  // last two (transformed) inputs of the previous chunk = left halo of lane 0
@@ -149,6 +170,8 @@ __global__ __launch_bounds__(256) void srf_dwconv5_fast_kernel(
         const float q = fmaf(o.x, o.x, fmaf(o.y, o.y, fmaf(o.z, o.z, o.w * o.w)));
         ds += (double)s;
         dq += (double)q;
+      } else if constexpr (RAGGED) {
+        if (g < (Lout >> 2)) yr[g] = zero4;
       }
     }
   } else {
@@ -187,6 +210,8 @@ __global__ __launch_bounds__(256) void srf_dwconv5_fast_kernel(
         const float q = fmaf(o.x, o.x, fmaf(o.y, o.y, fmaf(o.z, o.z, o.w * o.w)));
         ds += (double)s;
         dq += (double)q;
+      } else if constexpr (RAGGED) {
+        if (g < (Lout >> 2)) yr[g] = zero4;
       }
     }
   }
@@ -219,10 +244,53 @@ extern "C" int srf_dwconv5(const float* x, const float* w, const float* bias, fl
     const int chunks = (Lout + 255) / 256;
     const long blocks = rows * chunks;
     SRF_CHECK_ARG(blocks < (1L << 31), "srf_dwconv5: tensor too large");
-    hipLaunchKernelGGL(srf_dwconv5_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, w, bias,
+    hipLaunchKernelGGL(srf_dwconv5_generic_kernel<>, dim3((unsigned)blocks), dim3(256), 0, st, x, w, bias,
                        y, nd, inv_count, out_sums, C, Lin, Lout, stride, chunks);
   }
   SRF_CHECK_LAUNCH(fast ? (stride == 1 ? "dwconv5_s1_fast" : "dwconv5_s2_fast") : "dwconv5_generic", st);
+  return SRF_OK;
+}
+
+// The ragged form: srf_dwconv5's kernels with the table of input lengths behind their arguments.  The fast kernels serve a batch
+// whose every in_frames[b] lies on their grid of 4 * stride columns, the generic kernel any other.
+extern "C" int srf_dwconv5_ragged(const float* x, const float* w, const float* bias, float* y, int Bt, int C, int Lin, int stride,
+                                  const srf_norm* in_norm, double* out_sums, const int* in_frames, void* stream) {
+  SRF_CHECK_ARG(x && w && bias && y, "srf_dwconv5_ragged: null pointer");
+  SRF_CHECK_ARG(Bt > 0 && C > 0 && Lin > 0, "srf_dwconv5_ragged: bad sizes");
+  SRF_CHECK_ALIGNED16("srf_dwconv5_ragged", {"in_norm.sums", in_norm ? in_norm->sums : nullptr});
+  SRF_CHECK_ARG(stride == 1 || stride == 2, "srf_dwconv5_ragged: stride must be 1 or 2 (got %d)", stride);
+  SRF_CHECK_ARG(stride == 1 || Lin % 2 == 0, "srf_dwconv5_ragged: stride 2 needs an even row stride (Lin = %d)", Lin);
+  SrfFrames fr;
+  const int rc = srf_frames_table("srf_dwconv5_ragged", in_frames, Bt, Lin, &fr);
+  if (rc) return rc;
+  bool grid = true;      // every example on the fast kernels' grid
+  for (int b = 0; b < Bt; ++b) {
+    SRF_CHECK_ARG(stride == 1 || in_frames[b] % 2 == 0, "srf_dwconv5_ragged: example %d has %d input frames: stride 2 needs an even count",
+                  b, in_frames[b]);
+    grid = grid && in_frames[b] % (4 * stride) == 0;
+  }
+  const int Lout = (Lin - 1) / stride + 1;
+  const long rows = (long)Bt * C;
+  const double inv_count = 1.0 / ((double)C * (double)Lin);      // (the kernels count the example's own columns)
+  SrfNormDev nd = srf_norm_dev(in_norm);
+  hipStream_t st = (hipStream_t)stream;
+  const bool fast = srf_kernel_mode() != 1 && (Lin % (4 * stride) == 0) && grid && srf_aligned16(x) && srf_aligned16(y);
+  if (fast) {
+    const unsigned blocks = (unsigned)((rows + 3) / 4);
+    if (stride == 1)
+      hipLaunchKernelGGL((srf_dwconv5_fast_kernel<1, SrfFrames>), dim3(blocks), dim3(256), 0, st, x, w, bias, y, nd, inv_count, out_sums,
+                         C, Lin, Lout, rows, fr);
+    else
+      hipLaunchKernelGGL((srf_dwconv5_fast_kernel<2, SrfFrames>), dim3(blocks), dim3(256), 0, st, x, w, bias, y, nd, inv_count, out_sums,
+                         C, Lin, Lout, rows, fr);
+  } else {
+    const int chunks = (Lout + 255) / 256;
+    const long blocks = rows * chunks;
+    SRF_CHECK_ARG(blocks < (1L << 31), "srf_dwconv5_ragged: tensor too large");
+    hipLaunchKernelGGL(srf_dwconv5_generic_kernel<SrfFrames>, dim3((unsigned)blocks), dim3(256), 0, st, x, w, bias, y, nd, inv_count,
+                       out_sums, C, Lin, Lout, stride, chunks, fr);
+  }
+  SRF_CHECK_LAUNCH(fast ? (stride == 1 ? "dwconv5_s1_fast_ragged" : "dwconv5_s2_fast_ragged") : "dwconv5_generic_ragged", st);
   return SRF_OK;
 }
 
@@ -236,15 +304,22 @@ struct MergeArgs {
   int D;
 };
 
+// RAGGED (srf_merge_ragged; FR = SrfFrames): L stays the level-0 row stride, example b is frames[b] columns long on level 0 (a
+// multiple of 2^(D-1)) and frames[b] >> k on level k, whose norm counts C * (frames[b] >> k); no level is read past its own end,
+// y is exact 0 on [frames[b], L) and out_sums run over the example's own columns.
+template <typename... FR>
 __global__ __launch_bounds__(256) void srf_merge_generic_kernel(MergeArgs a, float* __restrict__ y,
                                                                 double* __restrict__ out_sums, int C,
-                                                                int L, int chunks) {
+                                                                int L, int chunks, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   __shared__ double red[8];
   const long row = blockIdx.x / chunks;
   const int chunk = blockIdx.x - row * chunks;
   const int c = (int)(row % C);
   const long b = row / C;
   const int j = chunk * 256 + threadIdx.x;
+  int own = L;      // (RAGGED) the example's own level-0 columns
+  if constexpr (RAGGED) own = srf_frames_of((int)b, fr...);
   double ds = 0.0, dq = 0.0;
   RowCoef rcs[SRF_MAX_DEPTH];  // statistics are finalised by the whole (converged) wavefront
 #pragma unroll
@@ -252,9 +327,11 @@ __global__ __launch_bounds__(256) void srf_merge_generic_kernel(MergeArgs a, flo
     SrfNormDev nk = a.nrm[k];
     nk.prelu = nullptr;
     if (k >= a.D) nk.sums = nullptr;
-    rcs[k] = srf_row_coef(nk, b, c, a.inv_count[k]);
+    rcs[k] = srf_row_coef(nk, b, c, RAGGED ? 1.0 / ((double)C * (double)max(own >> k, 1)) : a.inv_count[k]);
   }
-  if (j < L) {
+  if (RAGGED && j >= own) {
+    if (j < L) y[(size_t)row * L + j] = 0.f;
+  } else if (j < L) {
     float t = 0.f;
 #pragma unroll
     for (int k = SRF_MAX_DEPTH - 1; k >= 0; --k) {
@@ -273,15 +350,20 @@ __global__ __launch_bounds__(256) void srf_merge_generic_kernel(MergeArgs a, flo
 
 // fast: one wavefront per row, lane = one float4 of level-0 output; level 1 as float2, deeper levels
 // as (lane-shared) dwords.  Requires L % 4 == 0 and L % 2^(D-1) == 0, aligned bases.
+// RAGGED (every frames[b] % 4 == 0 too): the example's own float4 groups, then zeros up to the row stride.
+template <typename... FR>
 __global__ __launch_bounds__(256) void srf_merge_fast_kernel(MergeArgs a, float* __restrict__ y,
                                                              double* __restrict__ out_sums, int C, int L,
-                                                             long rows) {
+                                                             long rows, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (row >= rows) return;
   const int c = (int)(row % C);
   const long b = row / C;
   const int D = a.D;
+  int own = L;      // (RAGGED) the example's own level-0 columns
+  if constexpr (RAGGED) own = srf_frames_of((int)b, fr...);
   float sc[SRF_MAX_DEPTH], sh[SRF_MAX_DEPTH];
 #pragma unroll
   for (int k = 0; k < SRF_MAX_DEPTH; ++k) {
@@ -290,7 +372,7 @@ __global__ __launch_bounds__(256) void srf_merge_fast_kernel(MergeArgs a, float*
     if (k < D) {
       SrfNormDev nk = a.nrm[k];
       nk.prelu = nullptr;
-      const RowCoef rc = srf_row_coef(nk, b, c, a.inv_count[k]);
+      const RowCoef rc = srf_row_coef(nk, b, c, RAGGED ? 1.0 / ((double)C * (double)max(own >> k, 1)) : a.inv_count[k]);
       sc[k] = rc.sc;
       sh[k] = rc.sh;
     }
@@ -298,8 +380,10 @@ __global__ __launch_bounds__(256) void srf_merge_fast_kernel(MergeArgs a, float*
   const float4* l0 = reinterpret_cast<const float4*>(a.lv[0] + (size_t)row * L);
   const float2* l1 = (D > 1) ? reinterpret_cast<const float2*>(a.lv[1] + (size_t)row * (L >> 1)) : nullptr;
   float4* yr = reinterpret_cast<float4*>(y + (size_t)row * L);
-  const int n4 = L >> 2;
+  const int n4 = own >> 2;
   double ds = 0.0, dq = 0.0;
+  if constexpr (RAGGED)
+    for (int g = n4 + lane; g < (L >> 2); g += 64) yr[g] = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int g = lane; g < n4; g += 64) {
     const float4 d0 = l0[g];
     // levels >= 2 are constant over this lane's 4 outputs: bottom-up chain n_k + (n_{k+1} + ...)
@@ -341,12 +425,24 @@ __global__ __launch_bounds__(256) void srf_merge_fast_kernel(MergeArgs a, float*
   if (out_sums) srf_wave_stats_atomic(ds, dq, srf_stat_slot(out_sums, b, row));
 }
 
-extern "C" int srf_merge(const float* const* levels, const srf_norm* norms, int D, float* y, int Bt,
-                         int C, int L, double* out_sums, void* stream) {
-  SRF_CHECK_ARG(levels && norms && y, "srf_merge: null pointer");
-  SRF_CHECK_ARG(D >= 1 && D <= SRF_MAX_DEPTH, "srf_merge: depth %d unsupported (1..%d)", D, SRF_MAX_DEPTH);
-  SRF_CHECK_ARG(Bt > 0 && C > 0 && L > 0, "srf_merge: bad sizes");
-  SRF_CHECK_ARG(L % (1 << (D - 1)) == 0, "srf_merge: L=%d not divisible by 2^(D-1)", L);
+// who: the entry point's name in its refusals; frames: NULL = the uniform call, else one entry per example (srf_merge_ragged)
+static int merge_impl(const char* who, const float* const* levels, const srf_norm* norms, int D, float* y, int Bt, int C, int L,
+                      double* out_sums, const int* frames, void* stream) {
+  SRF_CHECK_ARG(levels && norms && y, "%s: null pointer", who);
+  SRF_CHECK_ARG(D >= 1 && D <= SRF_MAX_DEPTH, "%s: depth %d unsupported (1..%d)", who, D, SRF_MAX_DEPTH);
+  SRF_CHECK_ARG(Bt > 0 && C > 0 && L > 0, "%s: bad sizes", who);
+  SRF_CHECK_ARG(L % (1 << (D - 1)) == 0, "%s: L=%d not divisible by 2^(D-1)", who, L);
+  SrfFrames fr;
+  bool grid = true;      // (ragged) every example on the fast kernel's grid of 4 columns
+  if (frames) {
+    const int rc = srf_frames_table(who, frames, Bt, L, &fr);
+    if (rc) return rc;
+    for (int b = 0; b < Bt; ++b) {
+      SRF_CHECK_ARG(frames[b] % (1 << (D - 1)) == 0, "%s: example %d has %d frames: not a multiple of 2^(D-1) = %d", who, b, frames[b],
+                    1 << (D - 1));
+      grid = grid && frames[b] % 4 == 0;
+    }
+  }
   MergeArgs a;
   bool aligned = srf_aligned16(y);
   for (int k = 0; k < SRF_MAX_DEPTH; ++k) {
@@ -354,8 +450,8 @@ extern "C" int srf_merge(const float* const* levels, const srf_norm* norms, int 
     a.nrm[k] = SrfNormDev{nullptr, nullptr, nullptr, nullptr};
     a.inv_count[k] = 1.0;
     if (k < D) {
-      SRF_CHECK_ARG(levels[k] != nullptr, "srf_merge: null level %d", k);
-      SRF_CHECK_ALIGNED16("srf_merge", {"norms.sums", norms[k].sums});
+      SRF_CHECK_ARG(levels[k] != nullptr, "%s: null level %d", who, k);
+      SRF_CHECK_ALIGNED16(who, {"norms.sums", norms[k].sums});
       a.lv[k] = levels[k];
       a.nrm[k] = srf_norm_dev(&norms[k]);
       a.inv_count[k] = 1.0 / ((double)C * (double)(L >> k));
@@ -365,19 +461,40 @@ extern "C" int srf_merge(const float* const* levels, const srf_norm* norms, int 
   a.D = D;
   const long rows = (long)Bt * C;
   hipStream_t st = (hipStream_t)stream;
-  const bool fast = srf_kernel_mode() != 1 && (L % 4 == 0) && aligned && rows < (1L << 32);
+  const bool fast = srf_kernel_mode() != 1 && (L % 4 == 0) && grid && aligned && rows < (1L << 32);
+  const int chunks = (L + 255) / 256;
+  const long blocks = rows * chunks;
+  SRF_CHECK_ARG(fast || blocks < (1L << 31), "%s: tensor too large", who);
+  if (frames) {
+    if (fast)
+      hipLaunchKernelGGL(srf_merge_fast_kernel<SrfFrames>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, y, out_sums, C, L,
+                         rows, fr);
+    else
+      hipLaunchKernelGGL(srf_merge_generic_kernel<SrfFrames>, dim3((unsigned)blocks), dim3(256), 0, st, a, y, out_sums, C, L, chunks,
+                         fr);
+    SRF_CHECK_LAUNCH(fast ? "merge_fast_ragged" : "merge_generic_ragged", st);
+    return SRF_OK;
+  }
   if (fast) {
-    hipLaunchKernelGGL(srf_merge_fast_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, y,
+    hipLaunchKernelGGL(srf_merge_fast_kernel<>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a, y,
                        out_sums, C, L, rows);
   } else {
-    const int chunks = (L + 255) / 256;
-    const long blocks = rows * chunks;
-    SRF_CHECK_ARG(blocks < (1L << 31), "srf_merge: tensor too large");
-    hipLaunchKernelGGL(srf_merge_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, y, out_sums,
+    hipLaunchKernelGGL(srf_merge_generic_kernel<>, dim3((unsigned)blocks), dim3(256), 0, st, a, y, out_sums,
                        C, L, chunks);
   }
   SRF_CHECK_LAUNCH(fast ? "merge_fast" : "merge_generic", st);
   return SRF_OK;
+}
+
+extern "C" int srf_merge(const float* const* levels, const srf_norm* norms, int D, float* y, int Bt,
+                         int C, int L, double* out_sums, void* stream) {
+  return merge_impl("srf_merge", levels, norms, D, y, Bt, C, L, out_sums, nullptr, stream);
+}
+
+extern "C" int srf_merge_ragged(const float* const* levels, const srf_norm* norms, int D, float* y, int Bt, int C, int L,
+                                double* out_sums, const int* frames, void* stream) {
+  SRF_CHECK_ARG(frames != nullptr, "srf_merge_ragged: null frames table");
+  return merge_impl("srf_merge_ragged", levels, norms, D, y, Bt, C, L, out_sums, frames, stream);
 }
 
 // A block's pyramid as D depthwise launches + the merge: what the forwards run where the fused kernels (srf_pyramid.hip) do

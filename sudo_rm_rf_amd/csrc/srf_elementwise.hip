@@ -38,18 +38,97 @@ extern "C" int srf_gln_stats(const float* x, double* sums, int groups, long per_
   return SRF_OK;
 }
 
+// ---- GlobLN statistics of a ragged batch (srf_gln_stats_ragged) ---------------------------------
+// x [groups, channels, length], group g valid on its first frames[g] columns.  Block (k, g) adds the rows c = k, k + BUCKETS, ...
+// of group g over their own columns and WRITES bucket k of sums[g]: every bucket has one writer, every sum one order (a
+// thread's columns in order, the wavefront's shuffle tree, the four wavefronts in order) -- no atomics, and nothing of another
+// group enters a group's numbers.  Nothing is read at columns >= frames[g].
+__global__ __launch_bounds__(256) void srf_gln_stats_ragged_kernel(const float* __restrict__ x, double* __restrict__ sums, int channels,
+                                                                   int length, SrfFrames fr) {
+  __shared__ double red[8];
+  const int k = blockIdx.x;
+  const long g = blockIdx.y;
+  const int own = fr.n[g];
+  double ds = 0.0, dq = 0.0;
+  for (int c = k; c < channels; c += SRF_STAT_BUCKETS) {
+    const float* xr = x + ((size_t)g * channels + c) * length;
+    for (int l = threadIdx.x; l < own; l += 256) {
+      const float v = xr[l];
+      ds += (double)v;
+      dq += (double)v * (double)v;
+    }
+  }
+  ds = srf_wave_sum(ds);
+  dq = srf_wave_sum(dq);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[w] = ds;
+    red[4 + w] = dq;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* dst = sums + 2 * (g * SRF_STAT_BUCKETS + k);
+    dst[0] = ((red[0] + red[1]) + red[2]) + red[3];
+    dst[1] = ((red[4] + red[5]) + red[6]) + red[7];
+  }
+}
+
+extern "C" int srf_gln_stats_ragged(const float* x, double* sums, int groups, int channels, int length, const int* frames,
+                                    void* stream) {
+  SRF_CHECK_ARG(x && sums && groups > 0 && channels > 0 && length > 0, "srf_gln_stats_ragged: bad arguments");
+  SrfFrames fr;
+  const int rc = srf_frames_table("srf_gln_stats_ragged", frames, groups, length, &fr);
+  if (rc) return rc;
+  hipLaunchKernelGGL(srf_gln_stats_ragged_kernel, dim3(SRF_STAT_BUCKETS, (unsigned)groups), dim3(256), 0, (hipStream_t)stream, x, sums,
+                     channels, length, fr);
+  SRF_CHECK_LAUNCH("gln_stats_ragged", stream);
+  return SRF_OK;
+}
+
+// ---- the copy of a ragged batch's statistics that a UNIFORM kernel's on-load norm takes (srf_sums_scale_ragged) ----------
+// out[g][*] = in[g][*] * L / frames[g], in double: with the count C * L such a kernel assumes, the scaled sums give the mean and
+// variance of the example's own C * frames[g] elements.  One thread per double; not in place.
+__global__ __launch_bounds__(256) void srf_sums_scale_ragged_kernel(const double* __restrict__ in, double* __restrict__ out, int groups,
+                                                                    int length, SrfFrames fr) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= groups * SRF_STAT_BUCKETS * 2) return;
+  const int g = i / (SRF_STAT_BUCKETS * 2);
+  out[i] = in[i] * ((double)length / (double)fr.n[g]);
+}
+
+extern "C" int srf_sums_scale_ragged(const double* in, double* out, int groups, int length, const int* frames, void* stream) {
+  SRF_CHECK_ARG(in && out && groups > 0 && length > 0, "srf_sums_scale_ragged: bad arguments");
+  SRF_CHECK_ARG(in != out, "srf_sums_scale_ragged: out must not be in");
+  SrfFrames fr;
+  const int rc = srf_frames_table("srf_sums_scale_ragged", frames, groups, length, &fr);
+  if (rc) return rc;
+  const int n = groups * SRF_STAT_BUCKETS * 2;
+  hipLaunchKernelGGL(srf_sums_scale_ragged_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, out,
+                     groups, length, fr);
+  SRF_CHECK_LAUNCH("sums_scale_ragged", stream);
+  return SRF_OK;
+}
+
 // ---- GlobLN apply (optionally + residual input) ------------------------------------------------
 // One block per (row = (g,c), chunk of 1024 time steps).  ADD: y = xres + GlobLN(q).
-template <bool ADD>
+// RAGGED (srf_gln_apply_ragged; FR = SrfFrames): `length` stays the row stride, group g is frames[g] columns long (any count
+// >= 1: every access is a dword); the count is channels * frames[g], q is not read at columns >= frames[g] and y is exact 0 there.
+template <bool ADD, typename... FR>
 __global__ __launch_bounds__(256) void srf_gln_apply_kernel(const float* __restrict__ xres,
                                                             const float* __restrict__ q,
                                                             float* __restrict__ y, SrfNormDev nrm,
                                                             double inv_count, int channels, int length,
-                                                            int chunks) {
+                                                            int chunks, FR... fr) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   const long row = blockIdx.x / chunks;
   const int chunk = blockIdx.x - row * chunks;
   const int c = (int)(row % channels);
   const long g = row / channels;
+  int own = length;      // (RAGGED) the group's own columns
+  if constexpr (RAGGED) {
+    own = srf_frames_of((int)g, fr...);
+    inv_count = 1.0 / ((double)channels * (double)own);
+  }
   float sc = 1.f, sh = 0.f;
   if (nrm.sums) {
     float mean, rstd;
@@ -63,24 +142,37 @@ __global__ __launch_bounds__(256) void srf_gln_apply_kernel(const float* __restr
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int l = chunk * 1024 + u * 256 + threadIdx.x;
-    if (l < length) {
+    if (l < own) {
       float v = fmaf(q[base + l], sc, sh);
       if (act) v = srf_prelu(v, slope);
       if (ADD) v = xres[base + l] + v;
       y[base + l] = v;
+    } else if constexpr (RAGGED) {
+      if (l < length) y[base + l] = 0.f;
     }
   }
 }
 
+// frames: NULL = the uniform call, else one entry per group (srf_gln_apply_ragged: no residual form)
 static int gln_apply_launch(const float* xres, const float* q, float* y, const srf_norm* norm, int groups,
-                            int channels, int length, void* stream, bool add) {
-  SRF_CHECK_ARG(q && y && norm && groups > 0 && channels > 0 && length > 0, "srf_gln_apply: bad arguments");
-  SRF_CHECK_ALIGNED16("srf_gln_apply", {"norm.sums", norm->sums});     // (read as pairs of doubles)
+                            int channels, int length, void* stream, bool add, const int* frames = nullptr) {
+  const char* who = frames ? "srf_gln_apply_ragged" : "srf_gln_apply";     // the entry point's name in its refusals
+  SRF_CHECK_ARG(q && y && norm && groups > 0 && channels > 0 && length > 0, "%s: bad arguments", who);
+  SRF_CHECK_ALIGNED16(who, {"norm.sums", norm->sums});     // (read as pairs of doubles)
   const int chunks = (length + 1023) / 1024;
   const long blocks = (long)groups * channels * chunks;
-  SRF_CHECK_ARG(blocks < (1L << 31), "srf_gln_apply: tensor too large");
+  SRF_CHECK_ARG(blocks < (1L << 31), "%s: tensor too large", who);
   const double inv_count = 1.0 / ((double)channels * (double)length);
   SrfNormDev nd = srf_norm_dev(norm);
+  if (frames) {
+    SrfFrames fr;
+    const int rc = srf_frames_table(who, frames, groups, length, &fr);
+    if (rc) return rc;
+    hipLaunchKernelGGL((srf_gln_apply_kernel<false, SrfFrames>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xres, q, y,
+                       nd, inv_count, channels, length, chunks, fr);
+    SRF_CHECK_LAUNCH("gln_apply_ragged", stream);
+    return SRF_OK;
+  }
   if (add)
     hipLaunchKernelGGL(srf_gln_apply_kernel<true>, dim3((unsigned)blocks), dim3(256), 0,
                        (hipStream_t)stream, xres, q, y, nd, inv_count, channels, length, chunks);
@@ -94,6 +186,13 @@ static int gln_apply_launch(const float* xres, const float* q, float* y, const s
 extern "C" int srf_gln_apply(const float* x, float* y, const srf_norm* norm, int groups, int channels,
                              int length, void* stream) {
   return gln_apply_launch(nullptr, x, y, norm, groups, channels, length, stream, false);
+}
+
+extern "C" int srf_gln_apply_ragged(const float* x, float* y, const srf_norm* norm, int groups, int channels, int length,
+                                    const int* frames, void* stream) {
+  SRF_CHECK_ARG(frames != nullptr, "srf_gln_apply_ragged: null frames table");
+  SRF_CHECK_ARG(norm && norm->sums && norm->gamma && norm->beta, "srf_gln_apply_ragged: the norm needs statistics, gamma and beta");
+  return gln_apply_launch(nullptr, x, y, norm, groups, channels, length, stream, false, frames);
 }
 
 extern "C" int srf_gln_apply_add(const float* x, const float* q, float* y, const srf_norm* norm,

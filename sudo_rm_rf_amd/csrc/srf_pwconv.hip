@@ -663,6 +663,21 @@ extern "C" int srf_pw_conv(const float* x, const float* w, const float* bias, fl
 // srf_pw_conv_packed says, a ragged batch has no other kernel to go to -- so the packed image is required and the fp32
 // weight is never read.  Forms: no prologue / GlobLN (out_sums allowed: y is then exact zeros past every example's end),
 // GlobLN + PReLU with residual (the res_conv form: no statistics; y past an example's end is unspecified).
+// The gate of srf_pw_conv_packed_ragged for a caller that has another path to take (the attentive block: the uniform GEMM between a
+// statistics pass and the scaled sums): shape and reach of the 256 x 128 kernel, kernel mode 0, no debug flag that takes the kernel
+// or the packed images away, every example on the grid of 4 columns.  What is left to the call itself: the forms built, the
+// pointers and their 16-byte alignment.
+static bool pw_packed_ragged_shape_ok(int Bt, int Cin, int Cout, int L) {
+  return Bt > 0 && Cin > 0 && Cout > 0 && L > 0 && srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS) &&
+         srf_x3w_shape_supported(Cin, Cout, L) && pw256_reach(Bt, Cin, L);
+}
+extern "C" int srf_pw_conv_packed_ragged_supported(int Bt, int Cin, int Cout, int L, const int* frames) {
+  if (!frames || Bt < 1 || Bt > SRF_RAGGED_MAX_BATCH || !pw_packed_ragged_shape_ok(Bt, Cin, Cout, L)) return 0;
+  for (int b = 0; b < Bt; ++b)
+    if (frames[b] < 1 || frames[b] > L || frames[b] % 4) return 0;
+  return 1;
+}
+
 extern "C" int srf_pw_conv_packed_ragged(const float* x, const float* w, const void* w_packed, const float* bias, float* y,
                                          int Bt, int Cin, int Cout, int L, const srf_norm* in_norm, const float* residual,
                                          double* out_sums, int epilogue_mask, const float* mul, int mul_channels,
@@ -685,8 +700,7 @@ extern "C" int srf_pw_conv_packed_ragged(const float* x, const float* w, const v
                 "without statistics");
   if (a.nrm.sums) SRF_CHECK_ARG(a.nrm.gamma && a.nrm.beta, "srf_pw_conv_packed_ragged: norm without gamma/beta");
   // (shape and reach, no "fills the chip": see above; the statistics table's limit on Bt is the launch's own check and message)
-  SRF_CHECK_ARG(srf_kernel_mode() == 0 && !srf_dbg(SRF_DBG_NO_GEMM_256 | SRF_DBG_NO_PACKED_WEIGHTS) &&
-                    srf_x3w_shape_supported(Cin, Cout, L) && pw256_reach(Bt, Cin, L),
+  SRF_CHECK_ARG(pw_packed_ragged_shape_ok(Bt, Cin, Cout, L),
                 "srf_pw_conv_packed_ragged: the 256 x 128 kernel does not take %d -> %d channels, L=%d in kernel mode %d", Cin, Cout, L,
                 srf_kernel_mode());
   SRF_CHECK_ALIGNED16("srf_pw_conv_packed_ragged", {"in_norm.sums", a.nrm.sums}, {"x", x}, {"y", y}, {"residual", residual},

@@ -142,5 +142,6 @@ class _AttentiveModel(_Model):
 
     def forward_ragged(self, input_wav, lengths):
         raise NotImplementedError("the attentive model has no ragged kernels: run the utterances one by one "
-                                  "(pipeline.separate_list does).  Attention alone takes a ragged batch: "
-                                  "MHAttentionLayer.forward(Q, K, V, q_lengths, k_lengths).")
+                                  "(pipeline.separate_list does).  Its parts take a ragged batch: "
+                                  "MHAttentionLayer.forward(Q, K, V, q_lengths, k_lengths), and in attentive v2 "
+                                  "TransformerLayer.forward(x, ..., lengths=...) and AttentiveUConvBlock.forward(x, lengths).")

@@ -16,7 +16,7 @@ import math
 import torch
 import torch.nn as nn
 
-from ... import attention, ops
+from ... import attention, ops, ragged
 from ._base import _AttentiveModel, _OptIn, _hip_float, _hip_only, _no_random_dropout
 from .improved_sudormrf import _LayerNorm, GlobLN, ConvNormAct, NormAct, DilatedConvNorm, _lazy_levels  # noqa: F401
 
@@ -127,21 +127,45 @@ class MHAttentionLayer(_OptIn, nn.Module):
         return attention.zero_past(lin(self.O_proj, o), attention._host_lengths(q_lengths, "q_lengths")).transpose(1, 2).contiguous()
 
 
-def _transformer_tail(layer, o, residual, raw=False):
+def _transformer_tail(layer, o, residual, raw=False, lengths=None):
     """What both transformer layers end in: O projection of the attention output `o` + `residual`, out_mha_norm on load of the
     1x1 FFN, the FFN's norm and PReLU added to the normed residual branch (srf_gln_apply2_add), out_norm.  raw = True:
-    (z, sums of z) with out_norm still to apply."""
+    (z, sums of z) with out_norm still to apply.
+    lengths (a list; None: nothing changes): a ragged batch, o and residual exact zeros past lengths[b].  The two GEMMs stay
+    uniform and leave no statistics (a column of a 1x1 convolution depends on that column alone; what they write past an
+    example's end is never read); each norm's own-column sums come from a fixed-order pass (srf_gln_stats_ragged), the FFN GEMM
+    applies out_mha_norm from their copy scaled by row stride / own length, and the two closing kernels
+    are the ragged forms: z (raw) and the output are exact zeros past lengths[b]."""
     d = lambda p: p.detach()
     m = layer.mha
-    s_mha, s_ffn, s_out = (ops.new_sums(o.shape[0], o.device) for _ in range(3))
+    rg = lengths is not None
+    L = o.shape[-1]
+    s_mha, s_ffn, s_out = (None if rg and i < 2 else ops.new_sums(o.shape[0], o.device) for i in range(3))
     y = ops.pw_conv(o, d(m.O_proj.weight), d(m.O_proj.bias), residual=residual, out_sums=s_mha)
+    if rg:
+        s_mha = ragged.gln_stats(y, lengths)
     g, b = d(layer.out_mha_norm.gamma), d(layer.out_mha_norm.beta)
-    f = ops.pw_conv(y, d(layer.ffn.conv.weight), d(layer.ffn.conv.bias), in_sums=s_mha, in_gamma=g, in_beta=b, out_sums=s_ffn)
+    f = ops.pw_conv(y, d(layer.ffn.conv.weight), d(layer.ffn.conv.bias), in_sums=ragged.sums_scale(s_mha, L, lengths) if rg else s_mha,
+                    in_gamma=g, in_beta=b, out_sums=s_ffn)
+    if rg:
+        s_ffn = ragged.gln_stats(f, lengths)
     z = attention.gln_apply2_add(f, s_ffn, d(layer.ffn.norm.gamma), d(layer.ffn.norm.beta), d(layer.ffn.act.weight), y, s_mha, g, b,
-                                 out_sums=s_out)
+                                 out_sums=s_out, lengths=lengths)
     if raw:
         return z, s_out
+    if rg:
+        return ragged.gln_apply(z, s_out, d(layer.out_norm.gamma), d(layer.out_norm.beta), lengths)
     return ops.gln_apply(z, s_out, d(layer.out_norm.gamma), d(layer.out_norm.beta))
+
+
+def _ragged_inference_only(module, what, lengths, *tensors):
+    """lengths of a ragged call as a list (a device tensor is refused), after the two refusals of the ragged forwards: under
+    autograd (the opted-in module would have to differentiate) and in train() mode with dropout"""
+    lengths = attention._host_lengths(lengths, "lengths")
+    if module._wants_grad(*tensors):
+        raise NotImplementedError("%s: a ragged batch (lengths=...) is an inference path -- there is no ragged training; run it "
+                                  "under torch.no_grad()" % what)
+    return lengths
 
 
 class TransformerLayer(_OptIn, nn.Module):
@@ -167,22 +191,39 @@ class TransformerLayer(_OptIn, nn.Module):
         self.mha.enable_hip_training(flag)
         return self._opt_in(flag)
 
-    def forward(self, x, in_sums=None, in_gamma=None, in_beta=None):
+    def forward(self, x, in_sums=None, in_gamma=None, in_beta=None, lengths=None):
         """The kernel sequence srf_forward runs on the deepest level (stand-alone use / unit tests).  in_sums / in_gamma /
-        in_beta: a GlobLN to apply to x on load (the level's lazy norm); returns the layer's output, out_norm applied."""
+        in_beta: a GlobLN to apply to x on load (the level's lazy norm); returns the layer's output, out_norm applied.
+        lengths (a list or a CPU tensor of `batch` entries; None: nothing changes): a ragged batch.
+        x keeps its layout, example b has lengths[b] >= 1 positions of its own and is treated as its batch-1 call on
+        x[b:b+1, :, :lengths[b]] would treat it: in_sums are its own-column sums, both norms run over its own positions, pe is
+        indexed by its own position, attention runs over its own queries and keys.  What x holds at or past lengths[b]
+        influences nothing (it may be NaN) and the output is exact 0 there.  Inference only: under autograd (an opted-in layer)
+        this raises NotImplementedError, and train() mode with pos_enc.dropout.p > 0 raises as it does without the opt-in."""
+        if lengths is not None:
+            return self._forward_ragged(x, in_sums, in_gamma, in_beta, lengths)
         if self._wants_grad(x, in_gamma, in_beta):
             return attention.transformer_layer_train(self, _hip_float(x), in_sums, in_gamma, in_beta)
+        return self._inference(x, in_sums, in_gamma, in_beta)
+
+    def _forward_ragged(self, x, in_sums, in_gamma, in_beta, lengths, raw=False):
+        """forward(..., lengths=) after its two refusals; raw=True (the block's use): (z, sums of z), out_norm still to apply"""
+        lengths = _ragged_inference_only(self, "TransformerLayer", lengths, x, in_gamma, in_beta)
+        return self._inference(x, in_sums, in_gamma, in_beta, lengths, raw)
+
+    def _inference(self, x, in_sums, in_gamma, in_beta, lengths=None, raw=False):
         _no_random_dropout(self, self.pos_enc.dropout.p)
         x = _hip_only(x)
         d = lambda p: p.detach()
         m = self.mha
-        xp = attention.posenc_apply(x, d(self.pos_enc.pe), in_sums, in_gamma, in_beta)
+        xp = attention.posenc_apply(x, d(self.pos_enc.pe), in_sums, in_gamma, in_beta, lengths=lengths)
         wqkv = torch.cat([d(m.Q_proj.weight), d(m.K_proj.weight), d(m.V_proj.weight)], 0).contiguous()
         bqkv = torch.cat([d(m.Q_proj.bias), d(m.K_proj.bias), d(m.V_proj.bias)], 0).contiguous()
         qkv = ops.pw_conv(xp, wqkv, bqkv)
         hd = m.n_heads * m.d_model
         q, k, v = (qkv[:, i * hd:(i + 1) * hd].contiguous() for i in range(3))
-        return _transformer_tail(self, attention.mha_attention(q, k, v, m.n_heads, m.q_normalizer), xp)
+        o = attention.mha_attention(q, k, v, m.n_heads, m.q_normalizer, q_lengths=lengths, k_lengths=lengths)
+        return _transformer_tail(self, o, xp, raw=raw, lengths=lengths)
 
 
 class AttentiveUConvBlock(_OptIn, nn.Module):
@@ -211,13 +252,74 @@ class AttentiveUConvBlock(_OptIn, nn.Module):
         self.attention.enable_hip_training(flag)
         return self._opt_in(flag)
 
-    def forward(self, x):
-        """The kernel sequence srf_forward runs for one block (stand-alone use / unit tests)."""
+    def _forward_ragged(self, x, lengths):
+        """forward(x, lengths): DESIGN.md section 16.4.  proj_1x1 and res_conv run the packed ragged GEMM where its gate passes
+        (ragged.pw_conv_supported: the library's own gate), else the uniform GEMM between a fixed-order statistics pass and the scaled sums; the levels
+        and the merge are the ragged kernels, the layer is TransformerLayer's ragged forward on level D - 1 with that level's lazy
+        norm, and out_norm is merged as level D - 1's lazy norm on the un-normalised z (as the whole-model walk merges it)."""
+        D = self.depth
+        L = x.shape[-1]
+        unit = 1 << (D - 1)
+        if len(lengths) != x.shape[0]:
+            raise RuntimeError("AttentiveUConvBlock: %d lengths for a batch of %d" % (len(lengths), x.shape[0]))
+        for b, n in enumerate(lengths):
+            if n < unit or n > L or n % unit:
+                raise RuntimeError("AttentiveUConvBlock: example %d has length %d: a ragged batch needs multiples of 2^(depth-1) = %d "
+                                   "between %d and the row stride %d" % (b, n, unit, unit, L))
+        _no_random_dropout(self, self.attention.pos_enc.dropout.p)
+        x = _hip_only(x)
+        Bt, dev = x.shape[0], x.device
+        d = lambda p: p.detach()
+        p = self.proj_1x1
+        w_in, b_in = d(p.conv.weight), d(p.conv.bias)
+        if ragged.pw_conv_supported(Bt, w_in.shape[1], w_in.shape[0], L, lengths, x):
+            s_in = ops.new_sums(Bt, dev)
+            src = ragged.pw_conv(x, ops.pack_pw_weight(w_in), b_in, w_in.shape[0], lengths, out_sums=s_in)
+        else:
+            src = ops.pw_conv(x, w_in, b_in)
+            s_in = ragged.gln_stats(src, lengths)
+        norm = (s_in, d(p.norm.gamma), d(p.norm.beta), d(p.act.weight))
+        levels, sums, gammas, betas = [], [], [], []
+        for k in range(D):
+            m = self.spp_dw[k]
+            s_k = ops.new_sums(Bt, dev)
+            src = ragged.dwconv5(src, d(m.conv.weight), d(m.conv.bias), 1 if k == 0 else 2, [n >> max(k - 1, 0) for n in lengths],
+                                 *norm, out_sums=s_k)
+            levels.append(src)
+            sums.append(s_k)
+            gammas.append(d(m.norm.gamma))
+            betas.append(d(m.norm.beta))
+            norm = (s_k, gammas[k], betas[k], None)
+        z, s_out = self.attention._forward_ragged(levels[-1], *norm[:3], [n >> (D - 1) for n in lengths], raw=True)
+        out_norm = self.attention.out_norm
+        s_m = ops.new_sums(Bt, dev)
+        merged = ragged.merge(levels[:-1] + [z], sums[:-1] + [s_out], gammas[:-1] + [d(out_norm.gamma)],
+                              betas[:-1] + [d(out_norm.beta)], lengths, out_sums=s_m)
+        w_res, b_res = d(self.res_conv.weight), d(self.res_conv.bias)
+        fin = dict(in_gamma=d(self.final_norm.norm.gamma), in_beta=d(self.final_norm.norm.beta),
+                   in_prelu=d(self.final_norm.act.weight), residual=x)
+        if ragged.pw_conv_supported(Bt, w_res.shape[1], w_res.shape[0], L, lengths, merged, x):
+            out = ragged.pw_conv(merged, ops.pack_pw_weight(w_res), b_res, w_res.shape[0], lengths, in_sums=s_m, **fin)
+        else:
+            out = ops.pw_conv(merged, w_res, b_res, in_sums=ragged.sums_scale(s_m, L, lengths), **fin)
+        return attention.zero_past(out, lengths)
+
+    def forward(self, x, lengths=None):
+        """The kernel sequence srf_forward runs for one block (stand-alone use / unit tests).
+        lengths (a list or a CPU tensor of `batch` entries; None: nothing changes): a ragged batch.
+        Example b has lengths[b] positions of its own -- a multiple of 2^(depth-1), at least that, at most x.shape[-1] -- and is
+        treated as its batch-1 call on x[b:b+1, :, :lengths[b]] would treat it; what x holds at or past lengths[b] influences
+        nothing (it may be NaN) and the output is exact 0 there; a row's bits do not depend on the other rows' content, nor on
+        their lengths while the batch stays on the same kernels (dispatch is per launch).  Inference only: under autograd (an
+        opted-in block) this raises
+        NotImplementedError, and train() mode with dropout raises as it does without the opt-in."""
         D = self.depth
         if D < 2:
             raise RuntimeError("AttentiveUConvBlock: upsampling_depth = %d; the HIP path needs at least 2 levels" % D)
         if x.dim() == 3 and x.shape[-1] % (1 << (D - 1)):
             raise RuntimeError("time length %d must be divisible by 2^(depth-1)" % x.shape[-1])
+        if lengths is not None:
+            return self._forward_ragged(x, _ragged_inference_only(self, "AttentiveUConvBlock", lengths, x))
         if self._wants_grad(x):
             return attention.uconv_block_train(self, _hip_float(x).contiguous())
         x = _hip_only(x)

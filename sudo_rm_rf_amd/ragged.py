@@ -146,6 +146,15 @@ def pw_conv(x, packed, bias, Cout, frames, in_sums=None, in_gamma=None, in_beta=
     return y
 
 
+def pw_conv_supported(Bt, Cin, Cout, L, frames, *tensors):
+    """Whether pw_conv (srf_pw_conv_packed_ragged) takes this call now: the library's own gate
+    (srf_pw_conv_packed_ragged_supported: the 256 x 128 kernel's shape and reach, kernel mode, debug flags, every frames[b] a
+    multiple of 4) and the 16-byte alignment of `tensors` (x, the residual; None entries allowed).  No GPU needed."""
+    tab, n = _table(frames, "frames")
+    return bool(n == Bt and _lib.load().srf_pw_conv_packed_ragged_supported(Bt, Cin, Cout, L, tab)
+                and all(t is None or t.data_ptr() % 16 == 0 for t in tensors))
+
+
 def pw_conv_pair_supported(Cin1, Cmid, Cout2, L):
     """Whether srf_pw_conv_pair_ragged serves these channel counts / this row stride (no GPU needed)."""
     return bool(_lib.load().srf_pw_conv_pair_ragged_supported(Cin1, Cmid, Cout2, L))
@@ -215,3 +224,78 @@ def pw_conv_small(x, weight, bias, frames, rows_per_example=1, in_sums=None, in_
                                               int(rows_per_example), _lib.current_stream(dev))
     _lib.check(rc, "srf_pw_conv_small_ragged")
     return (y, u) if pre_q is not None else y
+
+
+# ---- the attentive block's kernels (include/sudormrf_hip.h, "Attentive block on a ragged batch") ----
+def _frames_for(name, values, groups, what="frames"):
+    tab, n = _table(values, what)
+    if n != groups:
+        raise _lib.SrfError("%s: %d %s for a batch of %d" % (name, n, what, groups))
+    return tab
+
+
+def dwconv5(x, weight, bias, stride, in_frames, in_sums=None, in_gamma=None, in_beta=None, in_prelu=None, out_sums=None):
+    """srf_dwconv5_ragged: ops.dwconv5 on x [Bt,C,Lin] whose row b is valid up to in_frames[b] (even under stride 2): the norm on
+    load counts C * in_frames[b], the taps meet zeros at the example's own end, y [Bt,C,Lout] is exact 0 from in_frames[b] //
+    stride on and out_sums run over the example's own outputs."""
+    dev = _chk(x, weight, bias, in_sums, in_gamma, in_beta, in_prelu, out_sums)
+    Bt, Cc, Lin = x.shape
+    frs = _frames_for("srf_dwconv5_ragged", in_frames, Bt, "in_frames")
+    y = torch.empty((Bt, Cc, (Lin - 1) // stride + 1), dtype=torch.float32, device=dev)
+    nrm = None if in_sums is None and in_prelu is None else C.byref(_lib.make_norm(in_sums, in_gamma, in_beta, in_prelu))
+    rc = _lib.load().srf_dwconv5_ragged(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), Bt, Cc, Lin, stride, nrm,
+                                        _lib.ptr(out_sums), frs, _lib.current_stream(dev))
+    _lib.check(rc, "srf_dwconv5_ragged")
+    return y
+
+
+def merge(levels, sums, gammas, betas, frames, out_sums=None):
+    """srf_merge_ragged: ops.merge on levels[k] [Bt,C,L>>k] whose row b is valid up to frames[b] >> k (frames[b] a multiple of
+    2^(D-1)): level k's norm counts C * (frames[b] >> k), merged is exact 0 on [frames[b], L), out_sums run over own columns."""
+    dev = _chk(*levels, *sums, *gammas, *betas, out_sums)
+    D = len(levels)
+    Bt, Cc, L = levels[0].shape
+    frs = _frames_for("srf_merge_ragged", frames, Bt)
+    y = torch.empty((Bt, Cc, L), dtype=torch.float32, device=dev)
+    lv = (C.c_void_p * D)(*[t.data_ptr() for t in levels])
+    norms = (_lib.srf_norm * D)(*[_lib.make_norm(s, g, b, None) for s, g, b in zip(sums, gammas, betas)])
+    rc = _lib.load().srf_merge_ragged(lv, norms, D, _lib.ptr(y), Bt, Cc, L, _lib.ptr(out_sums), frs, _lib.current_stream(dev))
+    _lib.check(rc, "srf_merge_ragged")
+    return y
+
+
+def gln_stats(x, frames):
+    """srf_gln_stats_ragged: x [groups, C, L] -> sums [groups, STAT_BUCKETS, 2] over x[g, :, :frames[g]], written in a fixed order
+    (no atomics: the same bits on every run, and a group's numbers do not depend on the other groups)."""
+    dev = _chk(x)
+    groups, Cc, L = x.shape
+    frs = _frames_for("srf_gln_stats_ragged", frames, groups)
+    sums = torch.empty((groups, _lib.STAT_BUCKETS, 2), dtype=torch.float64, device=dev)
+    rc = _lib.load().srf_gln_stats_ragged(_lib.ptr(x), _lib.ptr(sums), groups, Cc, L, frs, _lib.current_stream(dev))
+    _lib.check(rc, "srf_gln_stats_ragged")
+    return sums
+
+
+def gln_apply(x, sums, gamma, beta, frames, prelu=None):
+    """srf_gln_apply_ragged: y = GlobLN(x) (+ PReLU) counting C * frames[g] per group, exact 0 from frames[g] on (any
+    frames[g] >= 1); `sums` are the group's own-column sums."""
+    dev = _chk(x, sums, gamma, beta, prelu)
+    groups, Cc, L = x.shape
+    frs = _frames_for("srf_gln_apply_ragged", frames, groups)
+    y = torch.empty_like(x)
+    n = _lib.make_norm(sums, gamma, beta, prelu)
+    rc = _lib.load().srf_gln_apply_ragged(_lib.ptr(x), _lib.ptr(y), C.byref(n), groups, Cc, L, frs, _lib.current_stream(dev))
+    _lib.check(rc, "srf_gln_apply_ragged")
+    return y
+
+
+def sums_scale(sums, L, frames):
+    """srf_sums_scale_ragged: a copy of own-column `sums` scaled by L / frames[g] in double -- what a UNIFORM kernel's on-load
+    norm takes on a ragged batch: with the count C * L it assumes, the example's own mean and variance."""
+    dev = _chk(sums)
+    groups = sums.shape[0]
+    frs = _frames_for("srf_sums_scale_ragged", frames, groups)
+    out = torch.empty_like(sums)
+    rc = _lib.load().srf_sums_scale_ragged(_lib.ptr(sums), _lib.ptr(out), groups, int(L), frs, _lib.current_stream(dev))
+    _lib.check(rc, "srf_sums_scale_ragged")
+    return out
