@@ -1130,6 +1130,42 @@ int srf_sums_scale_ragged(const double* in, double* out, int groups, int length,
  * residual and the packed image.  For a caller with another path to take: the attentive block falls back to the uniform GEMM. */
 int srf_pw_conv_packed_ragged_supported(int Bt, int Cin, int Cout, int L, const int* frames);
 
+/* ---- Attentive v2 on a ragged batch: the whole model (additive to ABI 19) ----
+ * srf_pw_conv_ragged: the ragged form of the 128 x 128 split-bf16 GEMM (profiler name pw_conv_bf16x3_ragged<PRO>), for the 1x1
+ *   convolutions the 256 x 128 ragged GEMM does not take: Cout < 192 and lengths off the grid of 4.  It reads the fp32 weight (no
+ *   packed image).  L stays the row stride; example b owns columns [0, frames[b]) for ANY 1 <= frames[b] <= L.  A 128-column
+ *   tile that starts at or past frames[b] is skipped before any load: y is unspecified there.  In the tile that holds the
+ *   example's end, columns >= frames[b] are stored as exact 0.f.  What x and residual hold at columns >= frames[b] (NaN
+ *   included) reaches no own column and no statistic; out_sums (nullable, the uniform kernel's buckets) run over own columns;
+ *   the norm on load counts Cin * frames[b] against own-column sums (no scaled copy).  Every prologue, with or without
+ *   residual and out_sums; no mask epilogue.
+ * srf_pw_conv_ragged_supported: 1 under kernel mode 0 for Cin % 64 == 0, Cout >= 32, L % 4 == 0, W and x within the 2 GB reach
+ *   of 32-bit offsets, 1 <= Bt <= SRF_RAGGED_MAX_BATCH and every frames[b] in 1..L; else 0.  No GPU needed.
+ *   srf_pw_conv_ragged refuses, before any launch and naming the example where there is one, everything the gate refuses, null
+ *   pointers and x / w / y / residual / in_norm.sums off the 16-byte grid. */
+int srf_pw_conv_ragged_supported(int Bt, int Cin, int Cout, int L, const int* frames);
+int srf_pw_conv_ragged(const float* x, const float* w, const float* bias, float* y, int Bt, int Cin, int Cout, int L,
+                       const srf_norm* in_norm, const float* residual, double* out_sums, const int* frames, void* stream);
+/* The whole attentive v2 model over unequal-length examples in one set of launches.  Opt-in through entry points of its own:
+ * srf_plan_ragged_supported stays 0 for an attentive plan and srf_forward_ragged / srf_separate_ragged keep refusing it.  Same
+ * contract as those two: out[b, :, :lengths[b]] is what srf_forward (resp. srf_separate) gives for example b alone at its own
+ * length (to rounding: the GEMM kernels differ), out[b, :, lengths[b]:] is exact 0, wav[b, :, lengths[b]:] is never read.
+ * Every 1x1 convolution is decided per launch: the 256 x 128 packed ragged GEMM, else srf_pw_conv_ragged, else the uniform GEMM
+ * over every column between srf_sums_scale_ragged and srf_gln_stats_ragged.
+ * srf_attentive_ragged_supported: 1 for a plan of srf_attentive_plan_create with enc_kernel_size = 21 (one audio channel),
+ *   batch <= SRF_RAGGED_MAX_BATCH, kernel mode != 1, num_sources * enc_num_basis * frames >= 256 (one slot of scaled sums lives at
+ *   the start of the masked tensor's workspace region while the blocks run); with K = 21 every length in 1..T is taken.
+ *   Attentive v3 plans: 0.
+ * srf_attentive_ragged_workspace_bytes: the workspace the ragged call needs (0 = not supported).
+ * Refused with SRF_EINVAL before anything is launched, srf_last_error() naming the example: a length outside 1..T. */
+int srf_attentive_ragged_supported(const srf_plan* plan);
+size_t srf_attentive_ragged_workspace_bytes(const srf_plan* plan);
+int srf_attentive_forward_ragged(const srf_plan* plan, const float* const* params, int num_params, const float* wav,
+                                 const int* lengths /* host */, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int srf_attentive_separate_ragged(const srf_plan* plan, const float* const* params, int num_params, const float* wav,
+                                  const int* lengths /* host */, float* out, float* stats, int mixture_consistency, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* ---- Original SuDoRM-RF (additive to ABI 19; sudormrf.py) ----
  * The model of the paper: an encoder WITH bias and ReLU, GroupNorm(1, C) everywhere (GlobLN's arithmetic), PReLU with one slope
  * PER CHANNEL, blocks whose residual is added before the last norm, a mask layer that is a convolution along the basis axis

@@ -259,6 +259,12 @@ _PROTOS = {
     "srf_gln_stats_ragged": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_i), _vp]),
     "srf_sums_scale_ragged": (_i, [_vp, _vp, _i, _i, C.POINTER(_i), _vp]),
     "srf_pw_conv_packed_ragged_supported": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
+    "srf_pw_conv_ragged_supported": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
+    "srf_pw_conv_ragged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(srf_norm), _vp, _vp, C.POINTER(_i), _vp]),
+    "srf_attentive_ragged_supported": (_i, [_vp]),
+    "srf_attentive_ragged_workspace_bytes": (_sz, [_vp]),
+    "srf_attentive_forward_ragged": (_i, [_vp, C.POINTER(_vp), _i, _vp, C.POINTER(_i), _vp, _vp, _sz, _vp]),
+    "srf_attentive_separate_ragged": (_i, [_vp, C.POINTER(_vp), _i, _vp, C.POINTER(_i), _vp, _vp, _i, _vp, _sz, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 

@@ -546,7 +546,9 @@ int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur
   // it) and the overlap-add sums them.  Only where the 256 x 128 GEMM would have run the mask conv anyway.  (Ragged: the
   // uniform GEMM over every column -- the block stream is unspecified past an example's end, and so are the partial frames it
   // makes there -- then the ragged overlap-add.)
-  if (rg || plan_fused_tail_now(p, use_pack)) {
+  // (The attentive model's ragged walk has no gate on the tail: where its plan does not run the fused launch, it takes the
+  // unfused path below with the ragged overlap-add.)
+  if ((rg && c.variant != SRF_VARIANT_ATTENTIVE) || plan_fused_tail_now(p, use_pack)) {
     const int M = p->SA * K, nparts = (p->SA * N + 255) / 256;
     rc = srf_mask_decode_pack(t.dec_w, ws + p->off_wdpack, p->SA * N, M, st);
     if (rc) return rc;
@@ -559,8 +561,10 @@ int srf_improved_tail(const srf_plan* p, const float* const* P, const float* cur
   rc = srf_pw_conv_packed(cur, t.mask_w, mask_packed, t.mask_b, masked, Bt, c.out_channels, p->SA * N, L, &pre, nullptr, nullptr, 1,
                           enc, N, stream);
   if (rc) return rc;
+  // (ragged: the mask GEMM and the decoder's frame GEMM run over every column -- columns are independent in both -- and the
+  // overlap-add reads the example's own frames, as in the original model's ragged walk)
   return srf_decoder_impl(masked, t.dec_w, out, Bt, p->SA * N, p->SA, K, L, p->T, (float*)(ws + p->off_dec), wav_stats, wav,
-                          mixture_consistency, stream);
+                          mixture_consistency, stream, nullptr, rg ? &rg->lens_t : nullptr, rg ? &rg->frames_t : nullptr);
 }
 
 static int causal_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace, void* stream);

@@ -15,6 +15,9 @@
 //   merged = upsample-and-add of norm_k(d_k), k < D - 1, and out_norm(z)      srf_merge (z takes level D - 1's place and buffer)
 //   x' = res_conv(PReLU(final_norm(merged))) + x              srf_pw_conv_packed
 // Front end and tail are those of the Improved walk (srf_api.hip, forward_walk) without the fused conv pairs.
+// A ragged batch (opt-in: srf_attentive_forward_ragged / srf_attentive_separate_ragged) is the SAME walk
+// with a Ragged: every step picks its ragged twin with example b's own frames[b] >> k columns at level k, and every 1x1
+// convolution goes through att_conv_ragged, which decides per launch.
 #include <vector>
 #include "srf_mha.h"
 #include "srf_plan.h"
@@ -124,8 +127,37 @@ extern "C" int srf_attentive_plan_create(const srf_config* base, int n_heads, in
   return SRF_OK;
 }
 
+// One 1x1 convolution of the ragged walk, decided PER LAUNCH: (1) the 256 x 128 packed ragged GEMM where its gate, its built
+// forms, its statistics table and its "at least 8 tiles" pass; (2) the 128 x 128 ragged GEMM where its gate passes; (3) what
+// neither takes (Cin % 64 != 0, a row stride off the grid of 4): the uniform GEMM over every column without out_sums -- columns
+// are independent, no consumer reads past an example's end -- with srf_gln_stats_ragged for the statistics it should leave behind
+// and srf_sums_scale_ragged (into `rsums`) in front of a norm on load.
+static int att_conv_ragged(const float* x, const float* w, const void* w_packed, const float* bias, float* y, int Bt, int Cin, int Cout,
+                           int len, const srf_norm* in_norm, const float* residual, double* out_sums, const int* frames, double* rsums,
+                           void* stream) {
+  const int pro = in_norm ? (in_norm->sums ? (in_norm->prelu ? 2 : 1) : (in_norm->prelu ? 3 : 0)) : 0;
+  const bool packed_form = pro != 3 && (pro == 2) == (residual != nullptr) && !(pro == 2 && out_sums);
+  if (w_packed && packed_form && srf_x3w_supported(Bt, pro) && (long)Bt * ((Cout + 255) / 256) * ((len + 127) / 128) >= 8 &&
+      srf_pw_conv_packed_ragged_supported(Bt, Cin, Cout, len, frames))
+    return srf_pw_conv_packed_ragged(x, w, w_packed, bias, y, Bt, Cin, Cout, len, in_norm, residual, out_sums, 0, nullptr, 0, frames,
+                                     stream);
+  if (srf_pw_conv_ragged_supported(Bt, Cin, Cout, len, frames))
+    return srf_pw_conv_ragged(x, w, bias, y, Bt, Cin, Cout, len, in_norm, residual, out_sums, frames, stream);
+  srf_norm scaled;
+  if (in_norm && in_norm->sums) {
+    const int rc = srf_sums_scale_ragged(in_norm->sums, rsums, Bt, len, frames, stream);
+    if (rc) return rc;
+    scaled = *in_norm;
+    scaled.sums = rsums;
+    in_norm = &scaled;
+  }
+  const int rc = srf_pw_conv_packed(x, w, w_packed, bias, y, Bt, Cin, Cout, len, in_norm, residual, nullptr, 0, nullptr, 0, stream);
+  if (rc || !out_sums) return rc;
+  return srf_gln_stats_ragged(y, out_sums, Bt, Cout, len, frames, stream);
+}
+
 int srf_attentive_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
-                          const float* wav_stats, int mixture_consistency, void* stream) {
+                          const float* wav_stats, int mixture_consistency, void* stream, const Ragged* rg) {
   const srf_config& c = p->cfg;
   const int D = c.upsampling_depth, U = c.num_blocks, N = c.enc_num_basis, K = c.enc_kernel_size;
   const int Bt = p->Bt, L = p->L, nB = p->nB, C = p->nC, H = p->att_heads, d = p->att_dims, HD = H * d, Ld = p->att_len;
@@ -171,23 +203,34 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
     rc = plan_pack_weights(p, source_of, ws, stream);
     if (rc) return rc;
   }
-  auto conv = [&](const float* x, const float* w, int param, const float* bias, float* y, int Cin, int Cout, int len,
+  // ragged: example b's own columns at level k (its frames are a multiple of 2^(D-1): K = 21, see the gate)
+  std::vector<int> fr_lv(rg ? (size_t)D * Bt : 0);
+  for (int k = 0; rg && k < D; ++k)
+    for (int e = 0; e < Bt; ++e) fr_lv[(size_t)k * Bt + e] = rg->frames[e] >> k;
+  const int *fr0 = rg ? fr_lv.data() : nullptr, *frd = rg ? fr_lv.data() + (size_t)(D - 1) * Bt : nullptr;
+  // the scaled sums a uniform GEMM's norm on load takes (att_conv_ragged): one statistics slot at the start of the masked tensor's
+  // region, which is dead until the tail (the gate has made sure it is large enough)
+  double* rsums = (double*)(ws + p->off_masked);
+  // fr: the ragged batch's table at the conv's level (fr0 or frd; NULL in the uniform walk)
+  auto conv = [&](const float* x, const float* w, int param, const float* bias, float* y, int Cin, int Cout, int len, const int* fr,
                   const srf_norm* in_norm, const float* residual, double* out_sums) {
-    return srf_pw_conv_packed(x, w, plan_packed(p, ws, use_pack, param), bias, y, Bt, Cin, Cout, len, in_norm, residual, out_sums, 0,
-                              nullptr, 0, stream);
+    const void* packed = plan_packed(p, ws, use_pack, param);
+    if (rg) return att_conv_ragged(x, w, packed, bias, y, Bt, Cin, Cout, len, in_norm, residual, out_sums, fr, rsums, stream);
+    return srf_pw_conv_packed(x, w, packed, bias, y, Bt, Cin, Cout, len, in_norm, residual, out_sums, 0, nullptr, 0, stream);
   };
 
   // ---- front end: encoder (+ ln statistics), ln folded into the bottleneck GEMM's operand load
   const SrfFront<const float> f = plan_front(P);
   float* enc = fptr(p->off_enc);
-  rc = srf_encoder_impl(wav, f.enc_w, enc, stats, Bt, 1, p->T, N, K, L, wav_stats, stream);
+  rc = rg ? srf_encoder_ragged_impl(wav, f.enc_w, enc, stats, Bt, 1, p->T, N, K, L, rg->lengths, rg->frames, wav_stats, stream)
+          : srf_encoder_impl(wav, f.enc_w, enc, stats, Bt, 1, p->T, N, K, L, wav_stats, stream);
   if (rc) return rc;
   float* cur = fptr(p->off_xa);
   float* nxt = fptr(p->off_xb);
   float* y1 = fptr(p->off_y1);
   {
     const srf_norm ln{stats, f.ln_g, f.ln_b, nullptr};
-    rc = conv(enc, f.bott_w, SRF_P_BOTTLENECK, f.bott_b, cur, N, nB, L, &ln, nullptr, nullptr);
+    rc = conv(enc, f.bott_w, SRF_P_BOTTLENECK, f.bott_b, cur, N, nB, L, fr0, &ln, nullptr, nullptr);
     if (rc) return rc;
   }
 
@@ -201,7 +244,7 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
     double *s_mha = s.merged + each, *s_ffn = s.merged + 2 * each, *s_out = s.merged + 3 * each;
     const int pa = att_p_base(p, i);
     const float* const* A = P + pa;
-    rc = conv(cur, b.proj_w, b.i_proj, b.proj_b, y1, nB, C, L, nullptr, nullptr, s.proj);
+    rc = conv(cur, b.proj_w, b.i_proj, b.proj_b, y1, nB, C, L, fr0, nullptr, nullptr, s.proj);
     if (rc) return rc;
     // the pyramid level by level; the deepest one stays un-merged until the transformer layer has replaced it
     const float* levels[SRF_MAX_DEPTH];
@@ -209,36 +252,42 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
     for (int k = 0; k < D; ++k) {
       const srf_norm in = k == 0 ? srf_norm{s.proj, b.proj_g, b.proj_be, b.proj_prelu} : norms[k - 1];
       float* lv = fptr(p->off_lv[k]);
-      rc = srf_dwconv5(k == 0 ? y1 : levels[k - 1], b.lv_w[k], b.lv_b[k], lv, Bt, C, k == 0 ? L : L >> (k - 1), k == 0 ? 1 : 2, &in,
-                       s.level[k], stream);
+      const float* src = k == 0 ? y1 : levels[k - 1];
+      const int Lin = k == 0 ? L : L >> (k - 1), stride = k == 0 ? 1 : 2;
+      rc = rg ? srf_dwconv5_ragged(src, b.lv_w[k], b.lv_b[k], lv, Bt, C, Lin, stride, &in, s.level[k],
+                                   fr_lv.data() + (size_t)(k == 0 ? 0 : k - 1) * Bt, stream)
+              : srf_dwconv5(src, b.lv_w[k], b.lv_b[k], lv, Bt, C, Lin, stride, &in, s.level[k], stream);
       if (rc) return rc;
       levels[k] = lv;
       norms[k] = srf_norm{s.level[k], b.lv_g[k], b.lv_be[k], nullptr};
     }
     // ---- TransformerLayer on level D - 1
-    rc = srf_posenc_apply(levels[D - 1], &norms[D - 1], A[SRF_PA_PE], xp, Bt, C, Ld, SRF_ATT_MAX_LEN, stream);
+    rc = rg ? srf_posenc_apply_ragged(levels[D - 1], &norms[D - 1], A[SRF_PA_PE], xp, Bt, C, Ld, SRF_ATT_MAX_LEN, frd, stream)
+            : srf_posenc_apply(levels[D - 1], &norms[D - 1], A[SRF_PA_PE], xp, Bt, C, Ld, SRF_ATT_MAX_LEN, stream);
     if (rc) return rc;
-    rc = conv(xp, wqkv[i], pa + SRF_PA_Q, bqkv[i], qkv, C, 3 * HD, Ld, nullptr, nullptr, nullptr);
+    rc = conv(xp, wqkv[i], pa + SRF_PA_Q, bqkv[i], qkv, C, 3 * HD, Ld, frd, nullptr, nullptr, nullptr);
     if (rc) return rc;
     const long s3 = (long)3 * HD * Ld;
     const MhaArgs att{qkv, qkv + (size_t)HD * Ld, qkv + (size_t)2 * HD * Ld, ao, s3, s3, s3, (long)HD * Ld, H, d, Ld, Ld, q_normalizer};
-    rc = srf_mha_forward(0, att, Bt, nullptr, nullptr, nullptr, st);
+    rc = srf_mha_forward(rg ? SRF_MHA_RAGGED : 0, att, Bt, nullptr, frd, frd, st);
     if (rc) return rc;
-    rc = conv(ao, A[SRF_PA_O], pa + SRF_PA_O, A[SRF_PA_O + 1], ay, HD, C, Ld, nullptr, xp, s_mha);
+    rc = conv(ao, A[SRF_PA_O], pa + SRF_PA_O, A[SRF_PA_O + 1], ay, HD, C, Ld, frd, nullptr, xp, s_mha);
     if (rc) return rc;
     const srf_norm mha_norm{s_mha, A[SRF_PA_MHA_NORM], A[SRF_PA_MHA_NORM + 1], nullptr};
-    rc = conv(ay, A[SRF_PA_FFN], pa + SRF_PA_FFN, A[SRF_PA_FFN + 1], af, C, C, Ld, &mha_norm, nullptr, s_ffn);
+    rc = conv(ay, A[SRF_PA_FFN], pa + SRF_PA_FFN, A[SRF_PA_FFN + 1], af, C, C, Ld, frd, &mha_norm, nullptr, s_ffn);
     if (rc) return rc;
     const srf_norm ffn_norm{s_ffn, A[SRF_PA_FFN_NORM], A[SRF_PA_FFN_NORM + 1], A[SRF_PA_FFN_PRELU]};
     float* z = fptr(p->off_lv[D - 1]);      // (level D - 1 is dead since srf_posenc_apply)
-    rc = srf_gln_apply2_add(af, &ffn_norm, ay, &mha_norm, z, s_out, Bt, C, Ld, stream);
+    rc = rg ? srf_gln_apply2_add_ragged(af, &ffn_norm, ay, &mha_norm, z, s_out, Bt, C, Ld, frd, stream)
+            : srf_gln_apply2_add(af, &ffn_norm, ay, &mha_norm, z, s_out, Bt, C, Ld, stream);
     if (rc) return rc;
     norms[D - 1] = srf_norm{s_out, A[SRF_PA_OUT_NORM], A[SRF_PA_OUT_NORM + 1], nullptr};
     // ---- upsample-and-add (into y1: dead once level 0 exists), final_norm + PReLU folded into res_conv, + residual
-    rc = srf_merge(levels, norms, D, y1, Bt, C, L, s.merged, stream);
+    rc = rg ? srf_merge_ragged(levels, norms, D, y1, Bt, C, L, s.merged, fr0, stream)
+            : srf_merge(levels, norms, D, y1, Bt, C, L, s.merged, stream);
     if (rc) return rc;
     const srf_norm fn{s.merged, b.fin_g, b.fin_be, b.fin_prelu};
-    rc = conv(y1, b.res_w, b.i_res, b.res_b, nxt, C, nB, L, &fn, cur, nullptr);
+    rc = conv(y1, b.res_w, b.i_res, b.res_b, nxt, C, nB, L, fr0, &fn, cur, nullptr);
     if (rc) return rc;
     float* t = cur;
     cur = nxt;
@@ -246,5 +295,78 @@ int srf_attentive_forward(const srf_plan* p, const float* const* P, const float*
   }
 
   // ---- mask estimation + decoder: the Improved walk's tail
-  return srf_improved_tail(p, P, cur, out, workspace, use_pack, wav_stats, wav, mixture_consistency, nullptr, stream);
+  return srf_improved_tail(p, P, cur, out, workspace, use_pack, wav_stats, wav, mixture_consistency, rg, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// ragged forward (opt-in: srf_plan_ragged_supported / srf_forward_ragged / srf_separate_ragged keep refusing an attentive plan)
+// ---------------------------------------------------------------------------------------------
+// The gate.  There is none on the GEMM shapes (att_conv_ragged has a path for every launch) and none on the tail.  With K = 21 the
+// hop is 10, an example's own padded length is a multiple of lcm(10, 2^D) = 5 * 2^D, so its frame count is a multiple of 2^(D-1):
+// what the merge needs; no length inside 1..T is refused for its grid.
+static bool att_ragged_now(const srf_plan* p, const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (p->cfg.variant != SRF_VARIANT_ATTENTIVE) return no("not a plan of srf_attentive_plan_create");
+  if (p->A != 1 || p->cfg.enc_kernel_size != 21) return no("the ragged encoder is the one-channel K = 21 kernel");
+  if (srf_kernel_mode() == 1) return no("kernel mode 1 (generic kernels only) has no ragged encoder");
+  if (p->Bt > SRF_RAGGED_MAX_BATCH) return no("the batch exceeds SRF_RAGGED_MAX_BATCH");
+  // (the walk keeps one statistics slot of scaled sums in the masked tensor's region while the blocks run)
+  if ((size_t)p->SA * p->cfg.enc_num_basis * p->L * sizeof(float) < SRF_STAT_BUCKETS * 2 * sizeof(double))
+    return no("the model is too small (sources x basis x frames < 256)");
+  return true;
+}
+extern "C" int srf_attentive_ragged_supported(const srf_plan* p) { return p && att_ragged_now(p, nullptr) ? 1 : 0; }
+extern "C" size_t srf_attentive_ragged_workspace_bytes(const srf_plan* p) { return p && att_ragged_now(p, nullptr) ? p->total_bytes : 0; }
+
+// What the two entry points (`who`) share: the gate, the argument checks and every example's own padded length, as its batch-1
+// plan would have it -- all refusals BEFORE the first launch
+static int att_ragged_prepare(const char* who, const srf_plan* p, const float* const* P, int num_params, const int* lengths,
+                              const void* workspace, size_t workspace_bytes, Ragged* rg) {
+  const char* why = "";
+  SRF_CHECK_ARG(att_ragged_now(p, &why), "%s: plan not supported by the attentive model's ragged forward: %s", who, why);
+  int rc = forward_check_args(who, true /* checked by the caller */, p, P, num_params, workspace, workspace_bytes);
+  if (rc) return rc;
+  const int D = p->cfg.upsampling_depth, h = p->cfg.enc_kernel_size / 2;
+  const long lcm = (long)h * (1L << D) / att_gcd(h, 1L << D);
+  rg->lengths = lengths;
+  for (int b = 0; b < p->Bt; ++b) {
+    SRF_CHECK_ARG(lengths[b] >= 1 && lengths[b] <= p->T, "%s: example %d has length %d (allowed: 1..%d)", who, b, lengths[b], p->T);
+    const long Tp = lengths[b] % lcm ? lengths[b] + lcm - lengths[b] % lcm : lengths[b];   // the example alone, padded by the model's rule
+    rg->frames[b] = (int)(Tp / h);
+    SRF_CHECK_ARG(rg->frames[b] <= p->L && rg->frames[b] % (1 << (D - 1)) == 0,
+                  "%s: example %d (length %d = %d frames) is off the grid of 2^(D-1) frames or longer than the plan", who, b, lengths[b],
+                  rg->frames[b]);
+  }
+  rc = srf_frames_table(who, lengths, p->Bt, p->T, &rg->lens_t);
+  if (rc) return rc;
+  return srf_frames_table(who, rg->frames, p->Bt, p->L, &rg->frames_t);
+}
+
+extern "C" int srf_attentive_forward_ragged(const srf_plan* p, const float* const* P, int num_params, const float* wav, const int* lengths,
+                                            float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  SRF_CHECK_ARG(p && P && wav && lengths && out && workspace, "srf_attentive_forward_ragged: null pointer");
+  Ragged rg;
+  const int rc = att_ragged_prepare("srf_attentive_forward_ragged", p, P, num_params, lengths, workspace, workspace_bytes, &rg);
+  if (rc) return rc;
+  if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
+  return srf_attentive_forward(p, P, wav, out, workspace, nullptr, 0, stream, &rg);
+}
+
+// srf_separate over a ragged batch: the ragged forward with a statistics launch over every row's own samples in front, the
+// normalisation in the ragged encoder's load and the rescale (+ mixture consistency) in the ragged overlap-add.  wav: the RAW padded
+// mixture; nothing at or past lengths[b] is read by any of the three.
+extern "C" int srf_attentive_separate_ragged(const srf_plan* p, const float* const* P, int num_params, const float* wav,
+                                             const int* lengths, float* out, float* stats, int mixture_consistency, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  SRF_CHECK_ARG(p && P && wav && lengths && out && stats && workspace, "srf_attentive_separate_ragged: null pointer");
+  Ragged rg;
+  int rc = att_ragged_prepare("srf_attentive_separate_ragged", p, P, num_params, lengths, workspace, workspace_bytes, &rg);
+  if (rc) return rc;
+  if (srf_profiling()) srf_prof_mark("(gap)", (hipStream_t)stream);
+  rc = srf_wav_stats_ragged_launch(wav, rg.lens_t, stats, p->Bt, p->T, (hipStream_t)stream);
+  if (rc) return rc;
+  return srf_attentive_forward(p, P, wav, out, workspace, stats, mixture_consistency, stream, &rg);
 }

@@ -55,8 +55,10 @@ int forward_check_args(const char* who, bool ptrs, const srf_plan* p, const floa
                        size_t workspace_bytes);
 
 // ---- srf_attentive.hip (softmax attention, which its walk and the next one call: srf_mha.h)
+struct Ragged;
+// rg: NULL = the uniform forward; else the ragged batch of srf_attentive_forward_ragged / srf_attentive_separate_ragged
 int srf_attentive_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
-                          const float* wav_stats, int mixture_consistency, void* stream);
+                          const float* wav_stats, int mixture_consistency, void* stream, const Ragged* rg = nullptr);
 // ---- srf_attentive_v3.hip
 int srf_attentive_v3_forward(const srf_plan* p, const float* const* P, const float* wav, float* out, void* workspace,
                              const float* wav_stats, int mixture_consistency, void* stream);

@@ -68,6 +68,8 @@ struct PwPairArgs {
 
 // ---- launchers of the GEMM files, called by the dispatch in srf_pwconv.hip (the rest of the cross-file surface: srf_internal.h)
 int srf_pw_bf16x3_launch(const PwArgs& a, int pro, hipStream_t st);
+// its ragged form (one tile per block, buffer loads; the caller has checked the table, the shape and the 32-bit reach)
+int srf_pw_bf16x3_ragged_launch(const PwArgs& a, int pro, hipStream_t st, const SrfFrames& frames);
 int srf_pw_w4_launch(const PwArgs& a, int pro, hipStream_t st);   // 64 x 64 tiles for small launches (srf_pwconv_w4.hip)
 bool srf_pw_w4_wanted(const PwArgs& a);
 // the 256 x 128 kernel (srf_pwconv_x3w.hip); frames: null = the uniform kernels, else its ragged form
@@ -105,11 +107,15 @@ __device__ __forceinline__ int srf_xcd_remap(int id, int total) {
 //   C/D layout of v_mfma_f32_32x32x*: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 // bias / residual / ReLU*enc / {sum,sumsq} are applied on the float4 side.  `strip` = 32*SRF_EPI_PITCH
 // floats, 16-B aligned, private to the calling wavefront (all 64 lanes must call).
+// RAGGED (srf_pw_conv_ragged; `own` = the example's column count, any value in 1..L): after bias and residual -- which may have
+// read anything past the example's end -- the components at columns >= own are SELECTED to exact 0.f, so the 16-byte stores stay
+// whole, the straddling tile holds zeros up to its end and the statistics run over own columns only.
 constexpr int SRF_EPI_PITCH = 68;
 
+template <bool RAGGED = false>
 __device__ __forceinline__ void srf_pw_epilogue_strip(const PwArgs& a, const f32x16& accL, const f32x16& accR,
                                                       float* strip, long b, int m_base, int l_base, int lane,
-                                                      float& s, float& q) {
+                                                      float& s, float& q, int own = 0) {
   const int col = lane & 31, kh = lane >> 5;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
@@ -151,6 +157,12 @@ __device__ __forceinline__ void srf_pw_epilogue_strip(const PwArgs& a, const f32
       v.y = fmaxf(v.y, 0.f) * e.y;
       v.z = fmaxf(v.z, 0.f) * e.z;
       v.w = fmaxf(v.w, 0.f) * e.w;
+    }
+    if constexpr (RAGGED) {
+      v.x = l + 0 < own ? v.x : 0.f;
+      v.y = l + 1 < own ? v.y : 0.f;
+      v.z = l + 2 < own ? v.z : 0.f;
+      v.w = l + 3 < own ? v.w : 0.f;
     }
     if (ok) {
       *reinterpret_cast<float4*>(a.y + idx) = v;

@@ -708,6 +708,36 @@ extern "C" int srf_pw_conv_packed_ragged(const float* x, const float* w, const v
   return srf_pw_x3w_launch(a, reinterpret_cast<const char*>(w_packed), pro, (hipStream_t)stream, &fr);
 }
 
+// The ragged form of the 128 x 128 kernel (srf_pwconv_bf16x3.hip): the 1x1 convolutions the 256 x 128 ragged GEMM does not take
+// -- Cout < 192 (the attentive model's bottleneck and res_conv) and lengths off the grid of 4 (its deepest level).  Reads the
+// fp32 weight; any 1 <= frames[b] <= L.  The gate needs no GPU: kernel mode 0, Cin % 64 == 0, Cout >= 32, L % 4 == 0, W and X
+// within the 32-bit reach of the buffer loads, at most SRF_RAGGED_MAX_BATCH examples, every frame count in range.
+static bool pw_ragged_shape_ok(int Bt, int Cin, int Cout, int L) {
+  return Bt >= 1 && Bt <= SRF_RAGGED_MAX_BATCH && Cin > 0 && L > 0 && srf_kernel_mode() == 0 && Cin % 64 == 0 && Cout >= 32 && L % 4 == 0 &&
+         (long)Cout * Cin * 4 < (1L << 31) && (long)Bt * Cin * L * 4 < (1L << 31);
+}
+extern "C" int srf_pw_conv_ragged_supported(int Bt, int Cin, int Cout, int L, const int* frames) {
+  if (!frames || !pw_ragged_shape_ok(Bt, Cin, Cout, L)) return 0;
+  for (int b = 0; b < Bt; ++b)
+    if (frames[b] < 1 || frames[b] > L) return 0;
+  return 1;
+}
+
+extern "C" int srf_pw_conv_ragged(const float* x, const float* w, const float* bias, float* y, int Bt, int Cin, int Cout, int L,
+                                  const srf_norm* in_norm, const float* residual, double* out_sums, const int* frames, void* stream) {
+  SrfFrames fr;
+  const int rc = srf_frames_table("srf_pw_conv_ragged", frames, Bt, L, &fr);
+  if (rc) return rc;
+  SRF_CHECK_ARG(x && w && bias && y, "srf_pw_conv_ragged: null pointer");
+  const PwArgs a = pw_args(x, w, bias, y, residual, out_sums, nullptr, 1, 0, srf_norm_dev(in_norm), Bt, Cin, Cout, L);
+  if (a.nrm.sums) SRF_CHECK_ARG(a.nrm.gamma && a.nrm.beta, "srf_pw_conv_ragged: norm without gamma/beta");
+  SRF_CHECK_ARG(pw_ragged_shape_ok(Bt, Cin, Cout, L),
+                "srf_pw_conv_ragged: the 128 x 128 kernel does not take %d examples of %d -> %d channels, L=%d in kernel mode %d (needs "
+                "Cin %% 64 == 0, Cout >= 32, L %% 4 == 0, tensors within 2 GB, mode 0)", Bt, Cin, Cout, L, srf_kernel_mode());
+  SRF_CHECK_ALIGNED16("srf_pw_conv_ragged", {"in_norm.sums", a.nrm.sums}, {"x", x}, {"w", w}, {"y", y}, {"residual", residual});
+  return srf_pw_bf16x3_ragged_launch(a, srf_pw_pro(a.nrm), (hipStream_t)stream, fr);
+}
+
 extern "C" int srf_pw_conv_packed(const float* x, const float* w, const void* w_packed, const float* bias,
                                   float* y, int Bt, int Cin, int Cout, int L, const srf_norm* in_norm,
                                   const float* residual, double* out_sums, int epilogue_mask, const float* mul,

@@ -52,8 +52,15 @@ constexpr int X3_STAGE = 4 * X3_IMG;            // A_hi, A_lo, B_hi, B_lo
 // dropped.)
 // BUF: operand loads as buffer loads (see the persistent kernel); false = 64-bit pointer form for tensors whose
 // byte offsets do not fit 32 bits.
-template <int PRO, bool BUF = true>
-__global__ __launch_bounds__(512, 4) void srf_pw_bf16x3_w8_kernel(PwArgs a, int nMt, int nLt, int total) {
+// FR: empty, or one SrfFrames = the RAGGED form (srf_pw_conv_ragged, profiler name pw_conv_bf16x3_ragged<PRO>): L stays the row
+//     stride and example b owns columns [0, frames[b]), ANY count in 1..L (the deepest level of the attentive block has arbitrary
+//     lengths).  A tile whose first column lies at or past frames[b] returns before any load, LDS write or MFMA (y is unspecified
+//     there).  Columns are independent in a 1x1 convolution, so nothing is masked on load: what x and the residual hold past the
+//     end (NaN included) only reaches output columns past the end, and those the epilogue selects to exact zeros, component by
+//     component inside its 16-byte rows, before the store and the statistics.  The norm on load counts Cin * frames[b].
+template <int PRO, bool BUF = true, typename... FR>
+__global__ __launch_bounds__(512, 4) void srf_pw_bf16x3_w8_kernel(PwArgs a, int nMt, int nLt, int total, FR... rg) {
+  constexpr bool RAGGED = sizeof...(FR) != 0;
   __shared__ __attribute__((aligned(16))) char smem[2 * X3_STAGE];   // exactly 80 KB
 
   const int v = srf_xcd_remap(blockIdx.x, total);
@@ -61,13 +68,16 @@ __global__ __launch_bounds__(512, 4) void srf_pw_bf16x3_w8_kernel(PwArgs a, int 
   const int lt = (v / nMt) % nLt;
   const long b = v / (nMt * nLt);
   const int m0 = mt * X3_BM, l0 = lt * X3_BN;
+  const int own = RAGGED ? srf_frames_of((int)b, rg...) : 0;   // (block-uniform)
+  if (RAGGED && l0 >= own) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;   // 4 x 2 waves, 32 x 64 each
 
 
   float mean = 0.f, rstd = 1.f, slope = 1.f;
-  if (PRO == 1 || PRO == 2) srf_finalize_stats(a.nrm.sums, b, a.inv_count, mean, rstd);
+  if (PRO == 1 || PRO == 2)
+    srf_finalize_stats(a.nrm.sums, b, RAGGED ? 1.0 / ((double)a.Cin * (double)own) : a.inv_count, mean, rstd);
   if (PRO == 2 || PRO == 3) slope = a.nrm.prelu[0];
 
   const int Cin = a.Cin, L = a.L, Cout = a.Cout;
@@ -187,7 +197,7 @@ __global__ __launch_bounds__(512, 4) void srf_pw_bf16x3_w8_kernel(PwArgs a, int 
 
   float s = 0.f, q = 0.f;
   float* strip = reinterpret_cast<float*>(smem) + wave * (32 * SRF_EPI_PITCH);
-  srf_pw_epilogue_strip(a, acc0, acc1, strip, b, m0 + wm * 32, l0 + wn * 64, lane, s, q);
+  srf_pw_epilogue_strip<RAGGED>(a, acc0, acc1, strip, b, m0 + wm * 32, l0 + wn * 64, lane, s, q, own);
   __syncthreads();
   if (a.out_sums)
     srf_block_stats_atomic<8>((double)s, (double)q, srf_stat_slot(a.out_sums, b, v),
@@ -534,4 +544,23 @@ int srf_pw_bf16x3_launch(const PwArgs& a, int pro, hipStream_t st) {
     SRF_CHECK_LAUNCH("pw_conv_bf16x3_w8", st);
     return SRF_OK;
   }
+}
+
+// The ragged form: always one tile per block (a tile list with holes is another schedule than the persistent kernel's) and always
+// buffer loads (srf_pw_conv_ragged has checked the 32-bit reach of W and X).
+int srf_pw_bf16x3_ragged_launch(const PwArgs& a, int pro, hipStream_t st, const SrfFrames& frames) {
+  const int nMt = (a.Cout + X3_BM - 1) / X3_BM, nLt = (a.L + X3_BN - 1) / X3_BN;
+  const long total = (long)a.Bt * nMt * nLt;
+  SRF_CHECK_ARG(total < (1L << 31), "srf_pw_conv_ragged: too many tiles");
+  dim3 grid((unsigned)total), block(512);
+  switch (pro) {
+    case 0: hipLaunchKernelGGL((srf_pw_bf16x3_w8_kernel<0, true, SrfFrames>), grid, block, 0, st, a, nMt, nLt, (int)total, frames); break;
+    case 1: hipLaunchKernelGGL((srf_pw_bf16x3_w8_kernel<1, true, SrfFrames>), grid, block, 0, st, a, nMt, nLt, (int)total, frames); break;
+    case 2: hipLaunchKernelGGL((srf_pw_bf16x3_w8_kernel<2, true, SrfFrames>), grid, block, 0, st, a, nMt, nLt, (int)total, frames); break;
+    default: hipLaunchKernelGGL((srf_pw_bf16x3_w8_kernel<3, true, SrfFrames>), grid, block, 0, st, a, nMt, nLt, (int)total, frames); break;
+  }
+  static const char* const kLabel[4] = {"pw_conv_bf16x3_ragged<0>", "pw_conv_bf16x3_ragged<1>", "pw_conv_bf16x3_ragged<2>",
+                                        "pw_conv_bf16x3_ragged<3>"};
+  SRF_CHECK_LAUNCH(kLabel[pro < 0 || pro > 3 ? 3 : pro], st);
+  return SRF_OK;
 }

@@ -112,8 +112,10 @@ class _Model(nn.Module):
             eng = ModelEngine(self._config_tuple())
             eng.multi_stream = not self._single_stream
             self.__dict__["_srf_engine"] = eng
-        # the ragged opt-in (enable_ragged: the original model alone has one) is the model's: the engine follows it
-        eng.original_ragged = bool(self.__dict__.get("_srf_ragged"))
+        # the ragged opt-in (enable_ragged: the original and the attentive v2 model have one) is the model's: the engine follows it
+        opted = bool(self.__dict__.get("_srf_ragged"))
+        eng.original_ragged = opted and eng.cfg_tuple[0] == "original"
+        eng.attentive_ragged = opted and eng.cfg_tuple[0] == "attentive"
         return eng
 
     @staticmethod
@@ -122,8 +124,9 @@ class _Model(nn.Module):
 
 
 class _AttentiveModel(_Model):
-    """What attentive v2 and v3 share beyond their constructors: an inference forward on one stream, no ragged kernels.  The
-    subclass says where its blocks keep their transformer layers (_transformer_layers)."""
+    """What attentive v2 and v3 share beyond their constructors: an inference forward on one stream and a forward_ragged that
+    raises (v2 overrides it for a model that has opted in: SuDORMRF.enable_ragged).  The subclass says where its blocks keep their
+    transformer layers (_transformer_layers)."""
 
     _single_stream = True
     pad_to_appropriate_length = pad_to_multiple_of_lcm

@@ -385,3 +385,47 @@ class SuDORMRF(_AttentiveModel):
 
     def _transformer_layers(self):
         return [blk.attention for blk in self.sm]
+
+    def __getattr__(self, name):
+        # separate_ragged exists only on a model that has opted in (enable_ragged): without the call hasattr() stays False,
+        # which is what pipeline.ragged_route reads
+        if name == "separate_ragged" and self.__dict__.get("_srf_ragged"):
+            return self._separate_ragged
+        return super().__getattr__(name)
+
+    def enable_ragged(self, flag=True):
+        """Opt this model into (flag=False: out of) ragged-batch inference and return self.  With it, forward_ragged(wav,
+        lengths) and separate_ragged(wav, lengths, mixture_consistency=False) exist -- unequal-length rows in one set of
+        launches (srf_attentive_forward_ragged / srf_attentive_separate_ragged), each row treated as
+        its own batch-1 forward would treat it -- and pipeline.separate_list batches the utterances.  Without it nothing
+        changes: forward_ragged raises, separate_ragged does not exist, separate_list goes utterance by utterance.  Inference
+        only: under autograd or in train() mode the ragged calls raise.  The flag is a plain attribute beside the engine: not
+        in state_dict() and dropped from pickles."""
+        if flag:
+            self.__dict__["_srf_ragged"] = True
+        else:
+            self.__dict__.pop("_srf_ragged", None)
+        return self
+
+    def _ragged_route(self, length=None):
+        """pipeline.ragged_route for this model, from the configuration alone: "ragged" when the model has opted in and its
+        configuration passes srf_attentive_ragged_supported's batch-independent part (K = 21: then every length is on the
+        grid the merge needs, and every 1x1 convolution has a path); else "single"."""
+        if not self.__dict__.get("_srf_ragged") or self.enc_kernel_size != 21:
+            return "single"
+        return "ragged"
+
+    def forward_ragged(self, input_wav, lengths):
+        """After enable_ragged(): unequal-length utterances in ONE forward.  input_wav [batch, 1, time] on the GPU, row b valid
+        up to lengths[b] (a list or CPU int tensor; what lies past it is never read).  Returns [batch, num_sources, time]: row b
+        equals self(input_wav[b:b+1, :, :lengths[b]]) up to lengths[b] (to rounding) and is exactly zero past it."""
+        if not self.__dict__.get("_srf_ragged"):
+            return super().forward_ragged(input_wav, lengths)
+        return self._engine().run_ragged(self, input_wav, lengths)
+
+    def _separate_ragged(self, input_wav, lengths, mixture_consistency=False):
+        """separate_ragged of a model that has opted in: the caller-side recipe over a ragged batch in ONE call.  input_wav
+        [batch, 1, time] RAW padded mixtures on the GPU.  Returns (estimates [batch, num_sources, time], stats [batch, 2]): row b
+        normalised by the mean / std of its own samples, forward_ragged, rescaled (mixture consistency on request) -- and
+        exactly zero past lengths[b]."""
+        return self._engine().run_separate_ragged(self, input_wav, lengths, mixture_consistency)

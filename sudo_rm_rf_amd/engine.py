@@ -132,8 +132,17 @@ class Plan:
         original model's opt-in gate; `ragged_supported` stays False for its plans."""
         return bool(_lib.load().srf_original_ragged_supported(self.handle))
 
+    @property
+    def attentive_ragged_supported(self):
+        """Whether srf_attentive_forward_ragged takes this plan under the current kernel mode (srf_attentive_ragged_supported): the
+        attentive v2 model's opt-in gate; `ragged_supported` stays False for its plans."""
+        return bool(_lib.load().srf_attentive_ragged_supported(self.handle))
+
     def _ragged_entries(self):
-        """(workspace query, forward, separate) of this plan's variant: the original model has entry points of its own."""
+        """(workspace query, forward, separate) of this plan's variant: the original and the attentive v2 model have entry points
+        of their own."""
+        if self.cfg_tuple[0] == "attentive":
+            return ("srf_attentive_ragged_workspace_bytes", "srf_attentive_forward_ragged", "srf_attentive_separate_ragged")
         if self.cfg_tuple[0] == "original":
             return ("srf_original_ragged_workspace_bytes", "srf_original_forward_ragged", "srf_original_separate_ragged")
         return ("srf_plan_ragged_workspace_bytes", "srf_forward_ragged", "srf_separate_ragged")
@@ -326,8 +335,10 @@ class ModelEngine:
         # a training step frees its saved activations after the first backward (a step's memory is its activations);
         # True keeps them, for callers that run backward twice over one graph (retain_graph=True)
         self.keep_saved_for_repeat = False
-        # the original model's ragged forward is opt-in (SuDORMRF.enable_ragged sets this)
+        # the original and the attentive v2 model's ragged forwards are opt-in (their SuDORMRF.enable_ragged; _Model._engine sets
+        # the flag of the engine's own family)
         self.original_ragged = False
+        self.attentive_ragged = False
 
     def _flat_grad_buffer(self, params, total, device):
         """The flat fp32 buffer srf_backward writes all parameter gradients into (zeroed: the weight-gradient kernels
@@ -497,6 +508,8 @@ class ModelEngine:
         with torch.cuda.device(device):
             plan = self.plan_for(batch, T, torch.device(device))
             # (the original model: its own gate, and only for a model that has opted in -- SuDORMRF.enable_ragged)
+            if self.cfg_tuple[0] == "attentive":
+                return plan.attentive_ragged_supported and self.attentive_ragged
             return (plan.original_ragged_supported and self.original_ragged) if self.cfg_tuple[0] == "original" else plan.ragged_supported
 
     def separate(self, module, mixture, mixture_consistency):

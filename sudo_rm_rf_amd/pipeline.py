@@ -67,7 +67,7 @@ def ragged_route(model, length=None):
     kind = type(model).__name__
     if kind not in ("SuDORMRF", "GroupCommSudoRmRf") or not hasattr(model, "separate_ragged"):
         return "single"
-    if hasattr(model, "_ragged_route"):      # the original model after enable_ragged(): its own shapes and padding rule
+    if hasattr(model, "_ragged_route"):      # the original / attentive v2 model after enable_ragged(): its own shapes and padding rule
         return model._ragged_route(length)
     if getattr(model, "enc_kernel_size", 0) != 21 or getattr(model, "out_channels", 0) != 256:
         return "single"

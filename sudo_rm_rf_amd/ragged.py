@@ -155,6 +155,32 @@ def pw_conv_supported(Bt, Cin, Cout, L, frames, *tensors):
                 and all(t is None or t.data_ptr() % 16 == 0 for t in tensors))
 
 
+def pw_conv_mfma(x, weight, bias, frames, in_sums=None, in_gamma=None, in_beta=None, in_prelu=None, residual=None, out_sums=None):
+    """srf_pw_conv_ragged (the 128 x 128 split-bf16 GEMM's ragged form): x [Bt,Cin,L] (row b valid up to frames[b], ANY count
+    in 1..L), weight [Cout,Cin(,1)] fp32 -> y [Bt,Cout,L] from torch.empty.  A 128-column tile wholly past frames[b] is not
+    written; in the tile that holds the example's end y is exact 0 from frames[b] on.  out_sums and the norm on load run over
+    the example's own columns."""
+    dev = _chk(x, weight, bias, in_sums, in_gamma, in_beta, in_prelu, residual, out_sums)
+    Bt, Cin, L = x.shape
+    Cout = weight.shape[0]
+    frs, n = _table(frames, "frames")
+    if n != Bt:
+        raise _lib.SrfError("srf_pw_conv_ragged: %d frames for a batch of %d" % (n, Bt))
+    y = torch.empty((Bt, Cout, L), dtype=torch.float32, device=dev)
+    nrm = None if in_sums is None and in_prelu is None else C.byref(_lib.make_norm(in_sums, in_gamma, in_beta, in_prelu))
+    rc = _lib.load().srf_pw_conv_ragged(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(y), Bt, Cin, Cout, L, nrm,
+                                        _lib.ptr(residual), _lib.ptr(out_sums), frs, _lib.current_stream(dev))
+    _lib.check(rc, "srf_pw_conv_ragged")
+    return y
+
+
+def pw_conv_mfma_supported(Bt, Cin, Cout, L, frames):
+    """Whether pw_conv_mfma (srf_pw_conv_ragged) takes this call now: the library's own gate (srf_pw_conv_ragged_supported).
+    No GPU needed."""
+    tab, n = _table(frames, "frames")
+    return bool(n == Bt and _lib.load().srf_pw_conv_ragged_supported(Bt, Cin, Cout, L, tab))
+
+
 def pw_conv_pair_supported(Cin1, Cmid, Cout2, L):
     """Whether srf_pw_conv_pair_ragged serves these channel counts / this row stride (no GPU needed)."""
     return bool(_lib.load().srf_pw_conv_pair_ragged_supported(Cin1, Cmid, Cout2, L))

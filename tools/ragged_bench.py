@@ -14,7 +14,9 @@ Writes profiles/ragged_forward.txt (--model groupcomm: profiles/ragged_forward_g
 profiles/ragged_forward_original.txt), or --out.  The Improved mode exits 1 unless (a) beats (b) and is no slower than (c) by
 more than the spread; the GroupComm and original modes only report -- for those models the comparison that matters is (a)
 against (b), the per-utterance path separate_list took before.  The original mode also lists the launches of one call of (a),
-of one batch-1 forward of (b) and of (c).
+of one batch-1 forward of (b) and of (c).  --model attentive: attentive v2 at the reference defaults (16 blocks), opted in with
+enable_ragged(); writes profiles/ragged_forward_attentive.txt, only reports, and adds the per-kernel table of one ragged call
+and the work ratio; the padded uniform forward (c) is a floor there, not a correct answer.
 
 --mode separate_list: pipeline.separate_list on a length-sorted list of 32 utterances, lengths on [T/2, T], both models
 (--model picks one), two arms in one process, alternating, device events, median over the rounds:
@@ -26,7 +28,7 @@ of one batch-1 forward of (b) and of (c).
 with the library's launches (ops.kernel_trace) and the ATen operators that launch a kernel (a TorchDispatchMode count; views
 and allocations left out) of one call of each arm.  The arms are not symmetric: (s) is the whole of separate_list, its Python
 sort, bucketing and plan lookup included; (p) only the recipe on the batch already sorted and bucketed -- the ratio understates
-the gain.  Writes profiles/ragged_separate_list.txt (--model original: profiles/ragged_separate_list_original.txt), or --out."""
+the gain.  Writes profiles/ragged_separate_list.txt (--model original / attentive: profiles/ragged_separate_list_<model>.txt), or --out."""
 import argparse
 import json
 import os
@@ -49,10 +51,26 @@ def load_original(dev):
     return model.to(dev).eval().enable_ragged()
 
 
+def load_attentive(dev):
+    """attentive v2, the reference defaults (16 blocks), seeded fixture weights, opted into the ragged forward"""
+    from tests import attentive_fixtures as af
+    from sudo_rm_rf_amd.dnn.models.attentive_sudormrf_v2 import SuDORMRF
+    cfg = dict(af.DEFAULT_U2, num_blocks=16)
+    model = SuDORMRF(**cfg)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in af.make_state_dict(cfg, 409).items()})
+    return model.to(dev).eval().enable_ragged()
+
+
+OPT_IN = {"original": "original model (README recipe, 16 blocks)", "attentive": "attentive v2 (reference defaults, 16 blocks)"}
+
+
 def load_model(gc, dev):
-    """cfg 3 (GroupComm) or cfg 2 (Improved) with the golden weights, in eval mode on `dev`; gc == "original": load_original"""
+    """cfg 3 (GroupComm) or cfg 2 (Improved) with the golden weights, in eval mode on `dev`; gc == "original": load_original;
+    gc == "attentive": load_attentive"""
     if gc == "original":
         return load_original(dev)
+    if gc == "attentive":
+        return load_attentive(dev)
     from oracle import weights
     from oracle.schema import ModelConfig
     import sudo_rm_rf.dnn.models.groupcomm_sudormrf_v2 as groupcomm_sudormrf_v2
@@ -124,7 +142,7 @@ def separate_list_mode(args):
     rng = np.random.default_rng(2026)
     lens = sorted(int(v) for v in rng.integers(T // 2, T + 1, B))
     gain = np.geomspace(0.05, 20.0, B)[rng.permutation(B)]
-    for gc in ([False, True] if args.model is None else ["original" if args.model == "original" else args.model == "groupcomm"]):
+    for gc in ([False, True] if args.model is None else [args.model if args.model in OPT_IN else args.model == "groupcomm"]):
         model = load_model(gc, dev)
         mixes = [torch.from_numpy((gain[i] * weights.make_mixture(1, n, 9400 + i)[0, 0] + 0.1).astype(np.float32)).to(dev)
                  for i, n in enumerate(lens)]
@@ -153,7 +171,7 @@ def separate_list_mode(args):
         med = {k: float(np.median(v)) for k, v in times.items()}
         lines.append("")
         lines.append("%s weights, mixture consistency %s, padded length %d: %.1f %% of the padded samples are real"
-                     % ("original model (README recipe, 16 blocks)" if gc == "original" else "cfg 3 (GroupComm)" if gc else "cfg 2 (Improved)",
+                     % (OPT_IN[gc] if gc in OPT_IN else "cfg 3 (GroupComm)" if gc else "cfg 2 (Improved)",
                         "on" if gc is True else "off", Tb, 100 * sum(lens) / float(B * Tb)))
         lines.append("max |(s) - (p)| / max(1, std) over the utterances: %.3e" % worst)
         for k, name in (("s", "(s) separate_list"), ("p", "(p) torch-operator recipe")):
@@ -177,18 +195,18 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--T", type=int, default=32000)
     ap.add_argument("--mode", choices=["forward", "separate_list"], default="forward")
-    ap.add_argument("--model", choices=["improved", "groupcomm", "original"], default=None,
+    ap.add_argument("--model", choices=["improved", "groupcomm", "original", "attentive"], default=None,
                     help="default: improved (--mode forward), both in turn (--mode separate_list)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.mode == "separate_list":
         if args.out is None:
-            args.out = os.path.join(ROOT, "profiles", "ragged_separate_list_original.txt" if args.model == "original"
+            args.out = os.path.join(ROOT, "profiles", "ragged_separate_list_%s.txt" % args.model if args.model in OPT_IN
                                     else "ragged_separate_list.txt")
         return separate_list_mode(args)
-    gc = "original" if args.model == "original" else args.model == "groupcomm"
+    gc = args.model if args.model in OPT_IN else args.model == "groupcomm"
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "ragged_forward_original.txt" if gc == "original" else
+        args.out = os.path.join(ROOT, "profiles", "ragged_forward_%s.txt" % gc if gc in OPT_IN else
                                 "ragged_forward_groupcomm.txt" if gc else "ragged_forward.txt")
     from oracle import weights
     dev = torch.device("cuda:0")
@@ -242,7 +260,17 @@ def main():
         got, want = run_a(), run_b()
         worst = max(float((got[i, :, :n] - want[i][0]).abs().max()) for i, n in enumerate(lens))
         launches = {k: count_launches(fn, dev)[0] for k, fn in (("a", run_a), ("b1", lambda: model(rows[0])), ("c", run_c))} \
-            if gc == "original" else None
+            if gc in OPT_IN else None
+        # --model attentive: the per-kernel table of one ragged call (in-library profiler: one interval per launch)
+        table = None
+        if gc == "attentive":
+            from sudo_rm_rf_amd import ops
+            with ops.kernel_trace(dev) as tr:
+                run_a()
+            table = {}
+            for n, ms in tr.launches:
+                cnt, tot = table.get(n, (0, 0.0))
+                table[n] = (cnt + 1, tot + ms)
         made_in_warmup = created[0]
         for _ in range(args.rounds):
             for k, fn in runs:
@@ -257,7 +285,7 @@ def main():
     spread = abs(med["c"] - med["d"])
     valid = sum(lens) / float(B * T)
     lines = ["ragged forward, %s weights, batch %d, T = %d, lengths uniform on [T/2, T] (seed 2026): %.1f %% of the padded samples are real"
-             % ("original model (README recipe, 16 blocks)" if gc == "original" else "cfg 3 (GroupComm)" if gc else "cfg 2", B, T, 100 * valid),
+             % (OPT_IN[gc] if gc in OPT_IN else "cfg 3 (GroupComm)" if gc else "cfg 2", B, T, 100 * valid),
              "device: %s; %d alternating rounds after %d warm-up rounds; device-event times in ms: median [min .. max]"
              % (torch.cuda.get_device_name(dev), args.rounds, args.warmup),
              "max |forward_ragged row - its batch-1 forward| over the batch: %.3e" % worst,
@@ -275,6 +303,24 @@ def main():
                      % (sum(launches["a"].values()), sum(launches["b1"].values()), B, B * sum(launches["b1"].values()),
                         sum(launches["c"].values())))
         lines.append("launches of (a): %s" % dict(sorted(launches["a"].items())))
+    if table:
+        total = sum(ms for _, ms in table.values())
+        lines.append("")
+        lines.append("one ragged call under the in-library profiler (per launch intervals, serialised): %.3f ms in %d launches"
+                     % (total, sum(c for c, _ in table.values())))
+        lines.append("%-32s %8s %10s %7s" % ("kernel", "launches", "ms", "share"))
+        for n, (cnt, ms) in sorted(table.items(), key=lambda kv: -kv[1][1]):
+            lines.append("%-32s %8d %10.3f %6.1f%%" % (n, cnt, ms, 100 * ms / total))
+        # work ratio: 128-column GEMM tiles that hold own columns / tiles of the padded batch, at full length -- frames from the
+        # model's own hop, depth and padding rule (every row padded alone, as its batch-1 forward pads it)
+        hop, deep, tile = model.enc_kernel_size // 2, model.upsampling_depth - 1, 128
+        padded = lambda n: model.pad_to_appropriate_length(torch.zeros(1, 1, n)).shape[-1]
+        L = padded(T) // hop
+        fr = [padded(n) // hop for n in lens]
+        tiles = sum(-(-f // tile) for f in fr) / float(B * -(-L // tile))
+        lines.append("work ratio: real samples / padded samples = %.3f; %d-column tiles that hold own columns / all tiles = %.3f "
+                     "(full length; the deepest level, %d columns, has %d tile(s) per row)"
+                     % (valid, tile, tiles, L >> deep, -(-(L >> deep) // tile)))
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
